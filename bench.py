@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: training samples/s (image0 + image1 + flow) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--full] [--dump-outputs DIR]
     N > 1, started by hand: the script launches its N ranks itself (one child process per GPU with RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_ADDR / MASTER_PORT in its environment; the parent never touches the GPU, relays rank 0's JSON
     line and exits non-zero if any rank does).  Started by `python -m torch.distributed.run --nproc-per-node N ...`
@@ -30,12 +30,21 @@ header + texture index table (ofdg_comm_bcast_setup, csrc/comm.cpp); the JSON li
 ncclCommCount says, `shards` = every rank's first global index of steps 0 and 1).  If the native start-up fails the run
 exits non-zero on every rank (--allow-fallback: the same header over torch.distributed instead, and the line says so).
 
-The headline `value` (and the `cpu_baseline` next to it) is the REFERENCE-EQUIVALENT workload: background_prep = 1 -
+The headline `value` (and, with --full, the `cpu_baseline` next to it) is the REFERENCE-EQUIVALENT workload: background_prep = 1 -
 Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift) on every sample's background, which the reference runs per sample
-(DataGenerator.cpp:1186-1192) - the CImg chain stage by stage on the device.  `centre_crop_backgrounds` in the same line is
+(DataGenerator.cpp:1186-1192) - the CImg chain stage by stage on the device.  `centre_crop_backgrounds` in the --full line is
 the lighter form (background_prep = 0: every background is the centre crop of its pool image; the headline of rounds 1-3),
 measured after the headline context is closed.  --background-prep 0 makes that form the headline instead (and says so in
 `config`).
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed steps, the outputs of the
+last timed step (--dump-outputs DIR), the JSON line.  --full adds what takes runs of its own: the per-kernel passes
+(`kernel_ms`, `kernel_ms_alone`, the compose launch alone under `roofline.per_launch`, `background_prep_kernel`), the pass
+with the other background mode (`centre_crop_backgrounds` / `reference_equivalent`) and the `cpu_baseline`.
+
+--dump-outputs DIR: rank 0 writes image0.npy [k,3,H,W], image1.npy [k,3,H,W] and flow.npy [k,2,H,W] (float32) of the
+last timed step: k samples of its batch, chosen by a fixed seed (all of them when the batch fits DUMP_BYTES), listed in
+the line's `outputs`.  The inputs are seeded: the same arguments give the same arrays.
 """
 import argparse
 import importlib
@@ -73,6 +82,31 @@ SEED = 20261003
 EXIT_PORT_TAKEN = 98                    # a rank's exit code: the rendezvous port was taken between the launcher's probe and rank 0's bind
 HBM_PEAK_GBS = 8000.0                   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2     # G wave64 vector instructions/s: 256 CUs x 4 SIMDs (32 lanes wide) at 2.4 GHz, 2 cycles per wave64 instruction (MI355X_MICROARCH.md; ONE wave sustains one per 4 cycles)
+DUMP_BYTES = 60_000_000                 # --dump-outputs: at most this many bytes of arrays (whole samples)
+DUMP_SEED = 7                           # --dump-outputs: which samples of the batch, when not all of them fit
+
+
+def dump_selection(batch, height, width):
+    """Indices of the samples --dump-outputs writes: every sample if the batch fits DUMP_BYTES, else a fixed seeded subset
+    (at least one sample), sorted."""
+    import numpy as np
+    per_sample = 8 * height * width * 4          # image0 + image1 + flow: 8 float32 planes
+    k = max(1, min(batch, DUMP_BYTES // per_sample))
+    return sorted(int(i) for i in np.random.default_rng(DUMP_SEED).choice(batch, k, replace=False))
+
+
+def dump_outputs(directory, bufs, which):
+    """Samples `which` of one output buffer set (image0, image1, flow) as DIR/<name>.npy, float32."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    idx = torch.tensor(which, dtype=torch.int64, device=bufs[0].device)
+    files = {}
+    for name, t in zip(("image0", "image1", "flow"), bufs):
+        a = t.index_select(0, idx).cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return files
 
 
 def cpu_baseline(ofdg, gen, cfg, budget_s=24.0, host_pool=128, background_prep=0):
@@ -135,7 +169,7 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
     ap.add_argument("--cpu-pool", type=int, default=128, help="textures of the pool the CPU baseline works on")
     ap.add_argument("--sampler", choices=("counter", "resident"), default=None)
     ap.add_argument("--allow-fallback", action="store_true",
@@ -143,7 +177,7 @@ def parse_args(argv=None):
     ap.add_argument("--background-prep", type=int, choices=(0, 1, 2), default=1,
                     help="the headline's background mode: 1 (default) = Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift) on every "
                          "background like the reference (DataGenerator.cpp:1186-1192); 0 = centre crops; 2 = one resampling")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the pass with the other background mode (centre_crop_backgrounds)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the pass with the other background mode (centre_crop_backgrounds)")
     ap.add_argument("--chains", type=int, default=0, help="ofdg_params.chains (0: the context's own choice; 1: every kernel of a step runs alone, one step after the other)")
     ap.add_argument("--launcher", action="store_true", help="start the rank(s) as child processes even for --gpus 1 (what --gpus N > 1 does by itself)")
     ap.add_argument("--native-startup", action="store_true",
@@ -152,7 +186,17 @@ def parse_args(argv=None):
                          "on the context a RECEIVER builds from the broadcast")
     ap.add_argument("--launch-only", action="store_true",
                     help="launcher check: every rank prints its rank environment as one JSON line and exits (no torch, no GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: per-kernel passes (kernel_ms, kernel_ms_alone, the compose "
+                         "launch alone, background_prep_kernel), the pass with the other background mode and the cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0; image0 / image1 / flow as float32 .npy) into DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ---- the launcher: `python3 bench.py --gpus N` starts its own ranks ----------------------------------------------------
@@ -243,7 +287,10 @@ class Plumbing:
                     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(so.getsockname()[1]), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
             os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")
             try:
-                dist.init_process_group()  # default backends: gloo for CPU tensors, nccl (RCCL) for device tensors, the latter made on first use
+                # gloo for CPU tensors, nccl (RCCL) for device tensors, the latter made on first use.  Named: without a backend
+                # torch picks the accelerator's alone (nccl) when a GPU is present, and CPU tensors have none.
+                import torch
+                dist.init_process_group(backend="cpu:gloo,cuda:nccl" if torch.cuda.is_available() else "gloo")
             except Exception as e:  # noqa: BLE001
                 if "OFDG_BENCH_LAUNCHED" in os.environ and any(k in str(e).lower() for k in ("address already in use", "eaddrinuse")):
                     raise SystemExit(EXIT_PORT_TAKEN)  # (bench.py's own launcher picks another port and starts again)
@@ -456,6 +503,15 @@ def main():
     outs = [ofdg.alloc_outputs(BATCH, H, W) for _ in range(NBUF)]
 
     dt, step, host_sampler_rate, dt_mine = timed_pass(ofdg, gen, cfg, pl, outs, args.steps, args.warmup, rank, world, stream)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the buffer set the last timed step wrote (call warmup + steps - 1 of the context), before any later pass reuses it
+        which = dump_selection(BATCH, H, W)
+        last = args.warmup + args.steps - 1
+        dumped = {"dir": args.dump_outputs, "step": last, "samples": which,
+                  "files": dump_outputs(args.dump_outputs, outs[(args.steps - 1) % NBUF], which)}
+        if counter:
+            dumped["first_global_index"] = ofdg.shard_first_index(last, BATCH, world, rank)
     # every rank's own rate beside the aggregate (which divides by the SLOWEST rank's time): a straggler shows
     rank_rates = [args.steps * BATCH / t[0] for t in pl.gather_floats([dt_mine])]
 
@@ -466,8 +522,8 @@ def main():
     parts = alone = cpu_base = None
     # the background preparation's launch is timed where it runs behind raster (batches the library prepares itself)
     names = ("geom", "raster", "compose") + (("background_prep",) if bgp and counter else ())
-    prep_ms = gen.kernel_ms("background_prep") if "background_prep" in names else None
-    if rank == 0:
+    prep_ms = gen.kernel_ms("background_prep") if "background_prep" in names and args.full else None
+    if rank == 0 and args.full:
         # second short pass with all three kernels timed (not part of `value`)
         gen.set_profiling(2)
         for i in range(min(args.steps, 48)):
@@ -494,7 +550,7 @@ def main():
     # the secondary pass: the same workload with the other background mode (headline 1 or 2 -> centre crops; 0 -> mode 1)
     secondary = None
     bgp2 = 0 if bgp else 1
-    if not args.no_secondary and counter:
+    if args.full and not args.no_secondary and counter:
         gen2 = ofdg.Generator(params(bgp2))
         gen2.pool_synthetic(*cfg["pool"], POOL_SEED)
         if cfg["mode"] == 9:
@@ -571,18 +627,20 @@ def main():
                          "kernel": kernel,
                          "per_launch": {"kernel": kernel, "algorithmic_bytes_per_launch": alg_step,
                                         "kernel_ms": compose_ms, "achieved": per_launch, "frac": per_launch / HBM_PEAK_GBS,
-                                        # the same launch with the device to itself (serialised pass after the timed region)
-                                        "kernel_ms_alone": alone["compose"],
-                                        "achieved_alone": alg_step / (alone["compose"] * 1e-3) / 1e9,
-                                        "frac_alone": alg_step / (alone["compose"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                         # launches in flight on average = kernel_ms / ms_per_step
                                         "launches_in_flight": compose_ms / ms_per_step,
                                         "traffic": traffic},
                          "note": "achieved = algorithmic bytes of a step (38 B/px x W x H x batch) / ms_per_step, per GPU; frac = achieved / peak; "
-                                 "per_launch: the compose launch by live HIP events (overlapped span) and with the device to itself"},
-            "kernel_ms": parts, "kernel_ms_alone": alone,
+                                 "per_launch: the compose launch by live HIP events (overlapped span) and (--full) with the device to itself"},
             "hbm_gbs_whole_step": step_gbs,
         }
+        if args.full:
+            # the same launch with the device to itself (serialised pass after the timed region)
+            out["roofline"]["per_launch"].update({
+                "kernel_ms_alone": alone["compose"],
+                "achieved_alone": alg_step / (alone["compose"] * 1e-3) / 1e9,
+                "frac_alone": alg_step / (alone["compose"] * 1e-3) / 1e9 / HBM_PEAK_GBS})
+            out["kernel_ms"], out["kernel_ms_alone"] = parts, alone
         if prep_ms is not None:
             # The step's other heavy kernel is bound by neither HBM nor MFMA (the instruction issue of its own waves - 6 300 instructions per
             # 64 x 32 tile - and what the co-running kernels leave of the wave slots); reported: its launch, and its vector instructions against
@@ -599,11 +657,14 @@ def main():
                 "hbm_bytes_per_launch": (prep_pmc or {}).get("hbm_bytes_per_launch"),
                 "source": (prep_pmc or {}).get("source"),
                 "note": "runs at issue priority 0 beside the other chains' kernels (priority 3): in the pipeline its launch stretches over their gaps"}
-        out["centre_crop_backgrounds" if bgp2 == 0 else "reference_equivalent"] = secondary
+        if args.full:
+            out["centre_crop_backgrounds" if bgp2 == 0 else "reference_equivalent"] = secondary
         if host_sampler_rate is not None:
             out["host_ref_sampler_samples_per_s"] = host_sampler_rate
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
+        if dumped is not None:
+            out["outputs"] = dumped
         print(json.dumps(out))
     pl.close()
     return 0

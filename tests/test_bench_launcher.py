@@ -80,7 +80,7 @@ sys.path.insert(0, os.environ["OFDG_ROOT"])
 import bench
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 pl = bench.Plumbing(world)
-assert "gloo" in pl.how, pl.how
+assert pl.how.startswith("torch.distributed over gloo"), pl.how
 pl.barrier()
 assert pl.reduce(10.0 + rank, "max") == 10.0 + world - 1
 assert pl.reduce(10.0 + rank, "min") == 10.0

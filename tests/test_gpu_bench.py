@@ -1,6 +1,7 @@
 """The bench line's contract (the driver parses ONE JSON line from `python bench.py ...`): run the script as the driver
 does - a child process, a few steps - and check the fields the contract names; the headline is the reference-equivalent
-workload (background_prep = 1), the centre-crop form rides along.  The same through the script's own launcher path."""
+workload (background_prep = 1), the centre-crop form rides along (--full).  The same through the script's own launcher path.
+A plain run (no --full) carries the headline alone, and --dump-outputs writes what its last timed step rendered."""
 import json
 import os
 import subprocess
@@ -11,9 +12,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def bench(*extra):
+def bench(*extra, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", *extra],
+    mode = ["--full", "--no-cpu-baseline"] if full else []
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", *mode, *extra],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -78,6 +80,47 @@ def test_bench_line_carries_the_contract_fields():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_lean_and_dumps_the_last_timed_step(ofdg, tmp_path):
+    """No --full: the headline fields for exactly --steps timed steps and none of what takes runs of its own.  --dump-outputs:
+    the samples of the last timed step's batch (context call warmup + steps - 1, global indices 7 x 32 + [0, 32)), float32,
+    within 64 MB, equal to what the library renders for those indices in a context of its own."""
+    import numpy as np
+    import torch
+    import bench as b
+    d = bench("--dump-outputs", str(tmp_path / "out"), full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    B = d["config"]["batch_per_gpu"]
+    assert d["value"] > 0 and abs(d["value"] - 6 * B / (d["ms_per_step"] * 6e-3)) < 1e-3 * d["value"]
+    for key in ("cpu_baseline", "kernel_ms", "kernel_ms_alone", "background_prep_kernel", "centre_crop_backgrounds", "reference_equivalent"):
+        assert key not in d, key
+    assert "kernel_ms_alone" not in d["roofline"]["per_launch"]
+    o = d["outputs"]
+    cfg = b.CONFIGS[2]
+    W, H = cfg["W"], cfg["H"]
+    assert o["step"] == 2 + 6 - 1 and o["first_global_index"] == 7 * B and o["samples"] == b.dump_selection(B, H, W)
+    arrays = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("image0", "image1", "flow")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    k = len(o["samples"])
+    for n, c in (("image0", 3), ("image1", 3), ("flow", 2)):
+        assert arrays[n].dtype == np.float32 and arrays[n].shape == (k, c, H, W) and o["files"][n] == [k, c, H, W]
+    prm = ofdg.default_params(width=W, height=H, mode=cfg["mode"], num_objects=cfg["nobj"], batch_size=B, sampler=1, seed=b.SEED,
+                              background_prep=1)
+    g = ofdg.Generator(prm)
+    g.pool_synthetic(*cfg["pool"], b.POOL_SEED)
+    got = ofdg.alloc_outputs(B, H, W)
+    g.forward_counter(o["first_global_index"], B, *got, ofdg.STREAM_OWN)
+    g.synchronize()
+    torch.cuda.synchronize()
+    which = o["samples"]
+    assert np.array_equal(got[0].cpu().numpy()[which], arrays["image0"])
+    assert np.array_equal(got[1].cpu().numpy()[which], arrays["image1"])
+    assert np.array_equal(got[2].cpu().numpy()[which], arrays["flow"], equal_nan=True)
+    g.close()
+
+
+@pytest.mark.gpu
 def test_bench_line_through_the_launcher_path_has_the_same_contract():
     """`--launcher`: the rank is a child of the script's own launcher (what `--gpus N > 1` does by itself); the relayed
     line obeys the same contract as the direct form."""
@@ -94,7 +137,7 @@ def check_native_startup(d):
     c = d["config"]
     assert c["rccl_ranks"] == 1, c
     assert c["startup"].startswith("ofdg_comm_bcast_setup: one ncclBroadcast") and "built from the broadcast" in c["startup"], c["startup"]
-    assert "gloo" in c["plumbing"]
+    assert c["plumbing"].startswith("torch.distributed over gloo"), c["plumbing"]
     assert c["shards"]["first_index_of_steps_0_and_1_by_rank"] == [[0, c["batch_per_gpu"]]]
 
 

@@ -10,20 +10,21 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 tag=${1:-r05}
 part=${2:-all}   # bench: the bench lines; prof: the rocprofv3 passes (each fits one gpurun call); all: both
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
+root=$PWD
 mkdir -p $out
 if [ "$part" != "prof" ]; then
-echo "[bench] default"; timeout -k 10 500 python3 bench.py > $out/bench_line.json 2> $out/bench_stderr.txt
+echo "[bench] default"; timeout -k 10 500 python3 bench.py --full > $out/bench_line.json 2> $out/bench_stderr.txt
 echo "[bench] driver-like"; timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_line_driver_like_20_steps.json 2>> $out/bench_stderr.txt
 for cfg in 1 3 4 5; do
-  echo "[bench] config $cfg"; timeout -k 10 400 python3 bench.py --config $cfg > $out/bench_line_config$cfg.json 2>> $out/bench_stderr.txt
+  echo "[bench] config $cfg"; timeout -k 10 400 python3 bench.py --full --config $cfg > $out/bench_line_config$cfg.json 2>> $out/bench_stderr.txt
 done
-echo "[bench] centre crops as the headline"; timeout -k 10 300 python3 bench.py --background-prep 0 --no-cpu-baseline --no-secondary > $out/bench_line_config2_centre_crop.json 2>> $out/bench_stderr.txt
-echo "[bench] resident"; timeout -k 10 300 python3 bench.py --sampler resident --no-cpu-baseline --no-secondary > $out/bench_line_config2_resident.json 2>> $out/bench_stderr.txt
+echo "[bench] centre crops as the headline"; timeout -k 10 300 python3 bench.py --full --background-prep 0 --no-cpu-baseline --no-secondary > $out/bench_line_config2_centre_crop.json 2>> $out/bench_stderr.txt
+echo "[bench] resident"; timeout -k 10 300 python3 bench.py --full --sampler resident --no-cpu-baseline --no-secondary > $out/bench_line_config2_resident.json 2>> $out/bench_stderr.txt
 fi
 if [ "$part" != "bench" ]; then
 cd /tmp && export TMPDIR=/tmp
 echo "[rocprofv3] kernel trace"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > $out/bench_line_under_rocprof.json 2>/dev/null
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $root/bench.py --full --no-cpu-baseline --no-secondary > $out/bench_line_under_rocprof.json 2>/dev/null
 for arm in "2 1" "2 0" "3 1"; do
   set -- $arm; cfg=$1; bgp=$2
   echo "[rocprofv3] pmc config $cfg background_prep $bgp"
