@@ -240,6 +240,36 @@ int ofdg_forward_counter(ofdg_ctx* ctx, long long first_index, int n_samples,
 int ofdg_sample_counter(ofdg_ctx* ctx, long long first_index, int n_samples,
                         ofdg_task* tasks, ofdg_blueprint* bps);
 
+/*
+ * Optional outputs besides image0 / image1 / flow (rigid modes 1-8 and 10-13; caller-owned DEVICE buffers, slot i = task i):
+ *   flow1   float32 [n,2,H,W]  backward flow (frame 1 -> frame 0): RenderCore::computeFlowImage(objects_map, true) (DG:801-818),
+ *                              i.e. getPointFlow(x, y, inverse = true) of the object that owns index_image1(x, y) (DG:388-407,
+ *                              background DG:692-718) with m_motion_inv (DG:320-321, 333-334) - the reference computes it but
+ *                              never calls it (Process_TaskBucket, DG:1226)
+ *   label0  uint8   [n,H,W]    index_image0 / index_image1 of blitObject (DG:762-775) as the painter's position of the owner:
+ *   label1                     0 = background, k = the k-th top-level foreground object in ascending obj_id; an object owns a
+ *                              pixel where its non-AA mask of that frame is 255 (a composite: its composed mask, DG:591-646),
+ *                              the last owner in painter's order wins
+ *   occ0    float32 [n,1,H,W]  1.0f where the forward flow, rounded as xr = (int)floorf((float)x + u + 0.5f) (likewise y), leaves
+ *                              the frame or lands on a frame-1 pixel of another label (label1[yr][xr] != label0[y][x]), else 0.0f
+ *   occ1    float32 [n,1,H,W]  the same for frame-1 pixels with flow1, label1 at (x, y) and label0 at the target
+ * Every member may be NULL independently.  ex == NULL (or all members NULL) is exactly the plain call.  Occlusion without
+ * the labels / flow1 it needs keeps them in a workspace of the context.  Everything is written on the call's stream, in
+ * the same order as the outputs.  Mode 9 with any member set fails with OFDG_EINVAL and enqueues nothing.
+ */
+typedef struct ofdg_extras {
+  float*   flow1;   /* [n,2,H,W] or NULL */
+  float*   occ0;    /* [n,1,H,W] or NULL */
+  float*   occ1;    /* [n,1,H,W] or NULL */
+  uint8_t* label0;  /* [n,H,W]   or NULL */
+  uint8_t* label1;  /* [n,H,W]   or NULL */
+} ofdg_extras;
+int ofdg_render_ex(ofdg_ctx* ctx, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                   float* d_image0, float* d_image1, float* d_flow, const ofdg_extras* ex, void* stream);
+int ofdg_forward_ex(ofdg_ctx* ctx, float* d_image0, float* d_image1, float* d_flow, const ofdg_extras* ex, void* stream);
+int ofdg_forward_counter_ex(ofdg_ctx* ctx, long long first_index, int n_samples, float* d_image0, float* d_image1,
+                            float* d_flow, const ofdg_extras* ex, void* stream);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

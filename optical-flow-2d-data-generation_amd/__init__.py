@@ -99,7 +99,16 @@ EXPORTS = [
     "ofdg_comm_unique_id", "ofdg_comm_init", "ofdg_comm_adopt", "ofdg_comm_destroy", "ofdg_comm_rank", "ofdg_comm_world_size",
     "ofdg_comm_last_error", "ofdg_comm_bcast_setup", "ofdg_comm_bcast_abort", "ofdg_comm_nccl_count", "ofdg_comm_bcast_pool", "ofdg_comm_agree", "ofdg_setup_of", "ofdg_setup_params",
     "ofdg_setup_alloc_pool", "ofdg_pool_device_mixed", "ofdg_pool_device_image", "ofdg_layer_create_dist",
+    "ofdg_render_ex", "ofdg_forward_ex", "ofdg_forward_counter_ex",
 ]
+
+# the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
+EXTRAS = {"flow1": (2, "float32"), "occ0": (1, "float32"), "occ1": (1, "float32"), "label0": (None, "uint8"), "label1": (None, "uint8")}
+
+
+class Extras(C.Structure):
+    """ofdg_extras: device pointers of the optional outputs (NULL = not requested)."""
+    _fields_ = [("flow1", C.c_void_p), ("occ0", C.c_void_p), ("occ1", C.c_void_p), ("label0", C.c_void_p), ("label1", C.c_void_p)]
 
 
 def build(verbose=False):
@@ -162,6 +171,9 @@ def lib():
         L.ofdg_set_profiling.argtypes = [vp, i32]
         L.ofdg_kernel_ms.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
         L.ofdg_forward_counter.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, vp]
+        L.ofdg_render_ex.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(Extras), vp]
+        L.ofdg_forward_ex.argtypes = [vp, vp, vp, vp, C.POINTER(Extras), vp]
+        L.ofdg_forward_counter_ex.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(Extras), vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -364,10 +376,32 @@ class Generator:
         return tasks, bps, n.value
 
     # -- hot path --
-    def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0):
-        """img0/img1/flow: device pointers (int) or torch CUDA tensors."""
-        self._check(lib().ofdg_render(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
-                                      _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+    def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0, extras=None):
+        """img0/img1/flow: device pointers (int) or torch CUDA tensors.  extras: {name: tensor} of optional outputs
+        (alloc_extras; rigid modes): flow1, occ0, occ1, label0, label1."""
+        if extras is None:
+            self._check(lib().ofdg_render(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
+                                          _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+            return
+        ex = self._extras(extras, n_tasks)
+        self._check(lib().ofdg_render_ex(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
+                                         _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex), C.c_void_p(stream)))
+
+    def _extras(self, extras, n):
+        """Check an extras dict against the batch (n samples of the ctx's frame size) and return its ofdg_extras."""
+        ex = Extras()
+        H, W = self.params.height, self.params.width
+        for name, t in extras.items():
+            if name not in EXTRAS:
+                raise ValueError("unknown extra output %r (known: %s)" % (name, ", ".join(EXTRAS)))
+            if t is None:
+                continue
+            ch, dt = EXTRAS[name]
+            shape = (n, H, W) if ch is None else (n, ch, H, W)
+            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dt:
+                raise ValueError("extra %r must be %s %s, got %s %s" % (name, dt, shape, str(t.dtype).replace("torch.", ""), tuple(t.shape)))
+            setattr(ex, name, _dptr(t).value)
+        return ex
 
     def render_resident(self, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_resident(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
@@ -379,11 +413,20 @@ class Generator:
     def render_slot(self, slot, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_slot(self.h, slot, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
 
-    def forward(self, img0, img1, flow, stream=0):
-        self._check(lib().ofdg_forward(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+    def forward(self, img0, img1, flow, stream=0, extras=None):
+        if extras is None:
+            self._check(lib().ofdg_forward(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+            return
+        ex = self._extras(extras, self.params.batch_size)
+        self._check(lib().ofdg_forward_ex(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex), C.c_void_p(stream)))
 
-    def forward_counter(self, first_index, n, img0, img1, flow, stream=0):
-        self._check(lib().ofdg_forward_counter(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+    def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None):
+        if extras is None:
+            self._check(lib().ofdg_forward_counter(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+            return
+        ex = self._extras(extras, n)
+        self._check(lib().ofdg_forward_counter_ex(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex),
+                                                  C.c_void_p(stream)))
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -656,6 +699,20 @@ def alloc_outputs(n, height, width, device="cuda"):
             torch.zeros((n, 2, height, width), dtype=torch.float32, device=device))
 
 
+def alloc_extras(n, height, width, names=("flow1", "occ0", "occ1", "label0", "label1"), device="cuda"):
+    """Buffers of the optional outputs, {name: tensor}: flow1 float32 [n,2,H,W], occ0 / occ1 float32 [n,1,H,W],
+    label0 / label1 uint8 [n,H,W] (see include/ofdg.h, ofdg_extras)."""
+    import torch
+    out = {}
+    for name in names:
+        if name not in EXTRAS:
+            raise ValueError("unknown extra output %r (known: %s)" % (name, ", ".join(EXTRAS)))
+        ch, dt = EXTRAS[name]
+        shape = (n, height, width) if ch is None else (n, ch, height, width)
+        out[name] = torch.zeros(shape, dtype=getattr(torch, dt), device=device)
+    return out
+
+
 class HostSampler:
     """The reference-stream blueprint sampler on its own (host only, no GPU needed)."""
 
@@ -777,9 +834,11 @@ class FlowLoader:
     per batch: the consumer stream (`stream`, default: torch's current stream) waits for the batch it is given,
     and a buffer set is re-rendered only after the consumer work enqueued up to the next `next()` is done.
     Use the tensors on the consumer stream, or synchronise before touching them elsewhere.  Samples shard
-    over ranks by global index (params.rank / params.world_size): no communication."""
+    over ranks by global index (params.rank / params.world_size): no communication.
+    extras=("flow1", "occ0", ...): the optional outputs are rendered too, into buffers cycled with the ring, and every
+    batch is (image0, image1, flow, {name: tensor})."""
 
-    def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, **kw):
+    def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, **kw):
         import torch
         self.gen = Generator(params, **kw)
         p = self.gen.params
@@ -793,6 +852,9 @@ class FlowLoader:
         self.prefetch = max(2, int(prefetch))
         self.consumer = torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(int(stream))
         self.bufs = [alloc_outputs(p.batch_size, p.height, p.width) for _ in range(self.prefetch)]
+        self.extras = tuple(extras) if extras is not None else None
+        self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras) if self.extras is not None else None
+                      for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -806,7 +868,7 @@ class FlowLoader:
         chain = torch.cuda.ExternalStream(s)
         if self.released[j] is not None:
             chain.wait_event(self.released[j])
-        self.gen.forward(*self.bufs[j], s)
+        self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
         self.ready[j].record(chain)
 
     @property
@@ -831,6 +893,8 @@ class FlowLoader:
             self._enqueue(f)
             self.head += 1
         self.k += 1
+        if self.extras is not None:
+            return self.bufs[j] + (self.xbufs[j],)
         return self.bufs[j]
 
 

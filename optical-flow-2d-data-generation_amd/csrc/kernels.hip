@@ -34,6 +34,17 @@ __device__ __forceinline__ void xform(const Mat& m, double& x, double& y) {  // 
   x = t * m.sx + y * m.shx + m.tx;
   y = t * m.shy + y * m.sy + m.ty;
 }
+// trans_affine::invert (AGG 2.4), the operation order of realize.h:mat_invert (built with -ffp-contract=off: bit-identical)
+__device__ __forceinline__ Mat d_inv(const Mat& a) {
+  Mat r;
+  const double d = 1.0 / (a.sx * a.sy - a.shy * a.shx);
+  const double t0 = a.sy * d;
+  r.sy = a.sx * d; r.shy = -a.shy * d; r.shx = -a.shx * d;
+  const double t4 = -a.tx * t0 - a.ty * r.shx;
+  r.ty = -a.tx * r.shy - a.ty * r.sy;
+  r.sx = t0; r.tx = t4;
+  return r;
+}
 // floor(a / b) for b > 0, |a| < 2^52: fp64 quotient + exact integer correction.
 __device__ __forceinline__ long long floordiv64(long long a, long long b) {
   long long q = (long long)floor((double)a / (double)b);
@@ -1100,15 +1111,29 @@ constexpr int kPre = 2;  // objects of a block whose header / coverage / record 
 #define OFDG_DEFORM_FENCE 1
 #endif
 
-template <bool kPow2, bool kDeform = false>
+// Optional outputs of the extras variant (kExtra; rigid modes only): computeFlowImage(objects_map, true) (DG:801-818) and
+// the two index images (DG:762-775) as painter's positions.  A NULL pointer is not written.
+struct ExtOut {
+  float* flow1;     // [n,2,H,W]
+  uint8_t* label0;  // [n,H,W]
+  uint8_t* label1;  // [n,H,W]
+};
+// Stores of the extras variant: non-temporal like the plain kernels (OFDG_EXT_NT 1), or ordinary stores that leave the flows
+// and labels in L2 / MALL for the occlusion pass that reads them next (0).
+#ifndef OFDG_EXT_NT
+#define OFDG_EXT_NT 1
+#endif
+
+template <bool kPow2, bool kDeform = false, bool kExtra = false>
 __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask,
                                               const DevObject* __restrict__ objects, const uint8_t* __restrict__ cov,
                                               int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
                                               const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool,
                                               float* __restrict__ img0, float* __restrict__ img1, float* __restrict__ flow,
                                               const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count,
-                                              const DevCropRef* __restrict__ crops = nullptr) {
+                                              const DevCropRef* __restrict__ crops = nullptr, ExtOut ext = ExtOut{nullptr, nullptr, nullptr}) {
   static_assert(kPx == 4, "mask bytes are packed four to a word");
+  static_assert(!(kDeform && kExtra), "the extras are defined for the rigid modes only");
   step_kernel_priority();
   if (blockIdx.x == 0 && threadIdx.x == 0) *item_count = 0;  // raster_kernel has consumed the work list
   // XCD-aware strip mapping: blocks b and b + 8 share an XCD (round-robin dispatch).  Every XCD takes every 8th run of 32
@@ -1262,6 +1287,24 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
 #pragma unroll
     for (int p = 0; p < kPx; ++p) { fu[p] = fv[p] = 0.f; px0[p] = px1[p] = 0; }
   }
+  // extras: the background's backward flow, getPointFlow(.., inverse = true) (DG:692-718) with m_motion_inv = invert(bg_motion)
+  // (wave-uniform fp64, once); the labels start as the background's (painter's position 0)
+  float fu1[kPx], fv1[kPx];
+  uint32_t lab0 = 0, lab1 = 0;
+  if constexpr (kExtra) {
+    const Mat bi = d_inv(smp.bg_motion);
+    const double by = (double)(y + H / 2) + (double)(-H);
+#pragma unroll
+    for (int p = 0; p < kPx; ++p) {
+      double ix = (double)(x0 + p + W / 2), iy = by;
+      const float save_x = (float)(x0 + p + W / 2), save_y = (float)(y + H / 2);
+      ix = ix + (double)(-W);
+      xform(bi, ix, iy);
+      ix = ix + (double)W; iy = iy + (double)H;
+      fu1[p] = (float)(ix - (double)save_x);
+      fv1[p] = (float)(iy - (double)save_y);
+    }
+  }
 
   // ---- foreground objects in z-order ----
   WarpGeom g_frame;
@@ -1343,6 +1386,7 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
     int odef = 0;  // mode 9: the object's warp slot + 1 (0: rigid)
 
     uint32_t m0w, m1w, n0w;  // blending masks of the two frames and the thresholded frame-0 mask, byte p = pixel p
+    uint32_t n1w = 0;        // extras: the thresholded frame-1 mask
     if (!(sh & kShapeComposite)) {
       if constexpr (kDeform) odef = __builtin_amdgcn_readlane((int)recw, 31);
       // the box touches the block but the outline covers none of this strip's pixels: nothing to mask, sample or blend
@@ -1356,6 +1400,7 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
         n0w |= (uint32_t)na0 << (8 * p);
         m0w |= (uint32_t)(use_aa ? aa_byte(c0) : na0) << (8 * p);
         m1w |= (uint32_t)(use_aa ? aa_byte(c1) : (c1 >= 128 ? 255 : 0)) << (8 * p);
+        if constexpr (kExtra) n1w |= (uint32_t)(c1 >= 128 ? 255 : 0) << (8 * p);
       }
       if constexpr (kDeform) {
         if (odef > 0) {
@@ -1418,8 +1463,9 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
         m0w |= (uint32_t)(use_aa ? ua0[p] : na0[p]) << (8 * p);
         m1w |= (uint32_t)(use_aa ? ua1[p] : un1[p]) << (8 * p);
         n0w |= (uint32_t)na0[p] << (8 * p);
+        if constexpr (kExtra) n1w |= (uint32_t)un1[p] << (8 * p);
       }
-      if (__ballot((m0w | m1w | n0w) != 0u) == 0ull) continue;
+      if (__ballot((m0w | m1w | n0w | n1w) != 0u) == 0ull) continue;
       recw = reinterpret_cast<const uint32_t*>(&objs[oi])[min(lane, kRecLast)];
     }
 
@@ -1489,6 +1535,33 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
         }
       }
     }
+    if constexpr (kExtra) {
+      // blitObject's index images (DG:762-775): where the non-AA mask is 255 the object (painter's position oi) owns the pixel
+      uint32_t s0 = 0, s1 = 0;
+#pragma unroll
+      for (int p = 0; p < kPx; ++p) {
+        if (((n0w >> (8 * p)) & 255u) == 255u) s0 |= 0xFFu << (8 * p);
+        if (((n1w >> (8 * p)) & 255u) == 255u) s1 |= 0xFFu << (8 * p);
+      }
+      const uint32_t rep = (uint32_t)oi * 0x01010101u;
+      lab0 = (lab0 & ~s0) | (rep & s0);
+      lab1 = (lab1 & ~s1) | (rep & s1);
+      if (__ballot(s1 != 0u)) {
+        // getPointFlow(.., inverse = true) (DG:388-407): m_motion_inv is the record's tex_inv (dwords 12-23, = invert(motion))
+        Mat mi;
+        mi.sx = rec_double(6); mi.shy = rec_double(7); mi.shx = rec_double(8); mi.sy = rec_double(9); mi.tx = rec_double(10); mi.ty = rec_double(11);
+#pragma unroll
+        for (int p = 0; p < kPx; ++p) {
+          if ((s1 >> (8 * p)) & 1u) {
+            double ix = (double)(xv + p), iy = (double)yv;
+            const float save_x = (float)(xv + p), save_y = (float)yv;
+            xform(mi, ix, iy);
+            fu1[p] = (float)(ix - (double)save_x);
+            fv1[p] = (float)(iy - (double)save_y);
+          }
+        }
+      }
+    }
   }
 
   if (!inside) return;
@@ -1513,8 +1586,37 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
   }
   f32x4 u = {fu[0], fu[1], fu[2], fu[3]};
   f32x4 v = {fv[0], fv[1], fv[2], fv[3]};
-  __builtin_nontemporal_store(u, reinterpret_cast<f32x4*>(bf + ob));
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(bf + plane * 4 + ob));
+  if constexpr (kExtra && !OFDG_EXT_NT) {
+    *reinterpret_cast<f32x4*>(bf + ob) = u;
+    *reinterpret_cast<f32x4*>(bf + plane * 4 + ob) = v;
+  } else {
+    __builtin_nontemporal_store(u, reinterpret_cast<f32x4*>(bf + ob));
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(bf + plane * 4 + ob));
+  }
+  if constexpr (kExtra) {
+    // (the pointers are kernel arguments: every test below is wave-uniform)
+    if (ext.flow1) {
+      char* bf1 = reinterpret_cast<char*>(ext.flow1 + (size_t)s * 2 * plane);
+      const f32x4 u1 = {fu1[0], fu1[1], fu1[2], fu1[3]};
+      const f32x4 v1 = {fv1[0], fv1[1], fv1[2], fv1[3]};
+      if constexpr (!OFDG_EXT_NT) {
+        *reinterpret_cast<f32x4*>(bf1 + ob) = u1;
+        *reinterpret_cast<f32x4*>(bf1 + plane * 4 + ob) = v1;
+      } else {
+        __builtin_nontemporal_store(u1, reinterpret_cast<f32x4*>(bf1 + ob));
+        __builtin_nontemporal_store(v1, reinterpret_cast<f32x4*>(bf1 + plane * 4 + ob));
+      }
+    }
+    const uint32_t lb = ob >> 2;  // byte offset of the lane's 4 label bytes in the sample's plane (W is a multiple of 8)
+    if (ext.label0) {
+      uint32_t* d = reinterpret_cast<uint32_t*>(ext.label0 + (size_t)s * plane + lb);
+      if constexpr (!OFDG_EXT_NT) *d = lab0; else __builtin_nontemporal_store(lab0, d);
+    }
+    if (ext.label1) {
+      uint32_t* d = reinterpret_cast<uint32_t*>(ext.label1 + (size_t)s * plane + lb);
+      if constexpr (!OFDG_EXT_NT) *d = lab1; else __builtin_nontemporal_store(lab1, d);
+    }
+  }
 }
 
 // Leading scalar parameters are preloaded into SGPRs (no load, no wait before the first record fetch).
@@ -1534,6 +1636,72 @@ __global__ __launch_bounds__(64) void compose_rigid_pow2_kernel(
     float* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count) {
   compose_rigid<true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool, bgpool, img0, img1,
                       flow, frames, item_count);
+}
+// The same two with the optional outputs (backward flow, index images of both frames) written as well.
+__global__ __launch_bounds__(64) void compose_rigid_ext_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, float* __restrict__ img0, float* __restrict__ img1,
+    float* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, ExtOut ext) {
+  compose_rigid<false, false, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool, bgpool,
+                                    img0, img1, flow, frames, item_count, nullptr, ext);
+}
+__global__ __launch_bounds__(64) void compose_rigid_ext_pow2_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, float* __restrict__ img0, float* __restrict__ img1,
+    float* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, ExtOut ext) {
+  compose_rigid<true, false, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool, bgpool,
+                                   img0, img1, flow, frames, item_count, nullptr, ext);
+}
+
+// Occlusion maps from the labels and flows compose wrote (one pass per batch, behind compose on the same stream).  A pixel
+// of frame f is occluded (1.0f) when its flow, rounded as (int)floorf((float)x + u + 0.5f), leaves the frame or lands on a
+// pixel of the other frame with another label.  A lane takes 4 adjacent pixels: 16-byte flow loads, one 4-byte label load,
+// 4 byte gathers of the other frame's label (local: mostly L2 hits), 16-byte stores.  occ0 / occ1 NULL: not computed.
+typedef float occ_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ occ_f32x4 occlusion_quad(const float* __restrict__ u_plane, const float* __restrict__ v_plane,
+                                                 const uint8_t* __restrict__ own, const uint8_t* __restrict__ other, int x0, int y,
+                                                 int W, int H) {
+  const float4 u = *reinterpret_cast<const float4*>(u_plane);
+  const float4 v = *reinterpret_cast<const float4*>(v_plane);
+  const uint32_t l = *reinterpret_cast<const uint32_t*>(own);
+  const float uu[4] = {u.x, u.y, u.z, u.w}, vv[4] = {v.x, v.y, v.z, v.w};
+  float o[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const float fx = floorf(__fadd_rn(__fadd_rn((float)(x0 + p), uu[p]), 0.5f));
+    const float fy = floorf(__fadd_rn(__fadd_rn((float)y, vv[p]), 0.5f));
+    // (compared as floats: the same as testing the int of floorf against [0, W) x [0, H), and defined for any value)
+    const bool in = fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H;
+    const int off = in ? ((int)fy - y) * W + ((int)fx - x0) : 0;  // relative to pixel x0 of row y of the other frame
+    const uint32_t t = in ? (uint32_t)other[off] : 0u;
+    o[p] = (in && t == ((l >> (8 * p)) & 255u)) ? 0.f : 1.f;
+  }
+  const occ_f32x4 r = {o[0], o[1], o[2], o[3]};
+  return r;
+}
+__global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict__ flow, const float* __restrict__ flow1,
+                                                        const uint8_t* __restrict__ label0, const uint8_t* __restrict__ label1,
+                                                        float* __restrict__ occ0, float* __restrict__ occ1, int W, int H, int n) {
+  const int qpr = W >> 2;  // quads per row
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (long long)n * H * qpr) return;
+  const int row = (int)(q / qpr);  // s * H + y
+  const int x0 = (int)(q - (long long)row * qpr) * 4;
+  const int s = row / H, y = row - s * H;
+  const size_t plane = (size_t)W * H;
+  const size_t pix = (size_t)y * W + x0;
+  if (occ0) {
+    const float* f = flow + (size_t)s * 2 * plane + pix;
+    const occ_f32x4 o = occlusion_quad(f, f + plane, label0 + s * plane + pix, label1 + s * plane + pix, x0, y, W, H);
+    __builtin_nontemporal_store(o, reinterpret_cast<occ_f32x4*>(occ0 + s * plane + pix));
+  }
+  if (occ1) {
+    const float* f = flow1 + (size_t)s * 2 * plane + pix;
+    const occ_f32x4 o = occlusion_quad(f, f + plane, label1 + s * plane + pix, label0 + s * plane + pix, x0, y, W, H);
+    __builtin_nontemporal_store(o, reinterpret_cast<occ_f32x4*>(occ1 + s * plane + pix));
+  }
 }
 
 // Mode 9: the same body with the deformation paths compiled in (masks, textures and flow of deformed objects and backgrounds

@@ -131,6 +131,10 @@ struct ofdg_ctx {
   struct Chain {
     hipStream_t stream = nullptr;
     DevBuf<uint8_t> cov;
+    // extras: the labels [2][n][H][W] / backward flow [n][2][H][W] an occlusion pass needs when the caller does not want them
+    // (written by compose, read by the occlusion pass behind it; guarded by ev_done like `cov`)
+    DevBuf<uint8_t> x_labels;
+    DevBuf<float> x_flow1;
     Slot slot;
     Stage stage;
     hipEvent_t ev_prep = nullptr;  // coverage ready (hand-over to a caller's stream)
@@ -408,6 +412,8 @@ void ofdg_destroy(ofdg_ctx* c) {
     drop_slot(ch.slot);
     drop_stage(ch.stage);
     ch.cov.release();
+    ch.x_labels.release();
+    ch.x_flow1.release();
     if (ch.ev_prep) (void)hipEventDestroy(ch.ev_prep);
     if (ch.ev_done) (void)hipEventDestroy(ch.ev_done);
     if (ch.stream) (void)hipStreamDestroy(ch.stream);
@@ -1032,11 +1038,29 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
 // compose of the batch chain `ch` has prepared.  `st` is the caller's stream: if it is not the chain's own stream
 // (ofdg_stream), compose runs on `st` instead, behind what the caller enqueued there (the outputs may still be read) and
 // behind the chain's preparation kernels.
-static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float* d_img1, float* d_flow, hipStream_t st) {
+static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float* d_img1, float* d_flow, hipStream_t st,
+                          const ofdg_extras* ex = nullptr) {
   if (!ch.prep.valid) { c->err = "internal: compose without a prepared batch"; return OFDG_EINVAL; }
   ofdg_ctx::Slot& sl = *ch.prep.slot;
   const int W = c->prm.width, H = c->prm.height;
   const RenderDims dm = render_dims(c, sl);
+  // extras (rigid modes): where compose writes the backward flow and the labels - the caller's buffers, or the chain's
+  // workspace when only the occlusion pass needs them (grown only; growing waits for the device, like reserve_workspaces)
+  ExtOut xo{nullptr, nullptr, nullptr};
+  const bool extras = ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1);
+  const bool occ = extras && (ex->occ0 || ex->occ1);
+  if (extras) {
+    const size_t plane = (size_t)W * H, n = (size_t)dm.n_samples;
+    const bool ws_labels = occ && (!ex->label0 || !ex->label1), ws_flow1 = ex->occ1 && !ex->flow1;
+    if ((ws_labels && 2 * n * plane > ch.x_labels.cap) || (ws_flow1 && 2 * n * plane > ch.x_flow1.cap)) {
+      HIP_OK(c, hipDeviceSynchronize());
+      if (ws_labels) HIP_OK(c, ch.x_labels.reserve(2 * n * plane));
+      if (ws_flow1) HIP_OK(c, ch.x_flow1.reserve(2 * n * plane));
+    }
+    xo.flow1 = ex->flow1 ? ex->flow1 : (ws_flow1 ? ch.x_flow1.p : nullptr);
+    xo.label0 = ex->label0 ? ex->label0 : (occ ? ch.x_labels.p : nullptr);
+    xo.label1 = ex->label1 ? ex->label1 : (occ ? ch.x_labels.p + n * plane : nullptr);
+  }
   const int compose_grid = dm.tiles_x * dm.tiles_y * dm.n_samples * 4;  // one 64 x 4 strip per single-wave workgroup
   hipEvent_t* ev = ch.prep.ev;
   unsigned long long* box_cur = ch.prep.box_cur;
@@ -1066,8 +1090,16 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float
   // the completion of its predecessor on the chain (the last preparation kernel's own packet, ev[4], launch_prepare) to its
   // own completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
   // kernel's own start (a marker, ev[4]) and end.
-  hipEvent_t k_start = (ev && c->profiling == 2) ? ev[4] : nullptr, k_stop = ev ? ev[5] : done;
-  if (c->prm.mode == 9 && (W & (W - 1)) == 0)
+  hipEvent_t k_start = (ev && c->profiling == 2) ? ev[4] : nullptr, k_stop = ev ? ev[5] : (occ ? nullptr : done);
+  if (extras && (W & (W - 1)) == 0)
+    hipExtLaunchKernelGGL(compose_rigid_ext_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count, xo);
+  else if (extras)
+    hipExtLaunchKernelGGL(compose_rigid_ext_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count, xo);
+  else if (c->prm.mode == 9 && (W & (W - 1)) == 0)
     hipExtLaunchKernelGGL(compose_deform_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
                           sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0, d_img1, d_flow, sl.d_frames.p, croptab,
                           sl.d_item_count);
@@ -1084,6 +1116,12 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float
                           sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
                           d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count);
   HIP_OK(c, hipGetLastError());
+  if (occ) {  // behind compose on the same stream; the chain's completion event (workspace, slot) goes on THIS packet
+    const long long quads = (long long)dm.n_samples * H * (W / 4);
+    hipExtLaunchKernelGGL(occlusion_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0, d_flow,
+                          xo.flow1, xo.label0, xo.label1, ex->occ0, ex->occ1, W, H, dm.n_samples);
+    HIP_OK(c, hipGetLastError());
+  }
   if (ev) {
     if (done) HIP_OK(c, hipEventRecord(done, CS));
     // profiling 1 times compose from the completion of the chain's last preparation kernel: that is the launch's time only
@@ -1106,11 +1144,22 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float
 
 // preparation + compose of the batch resident in `sl`, in order on chain `ch`
 static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, float* d_img0, float* d_img1, float* d_flow,
-                           hipStream_t st, long long cs_first_index = -1) {
+                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras* ex = nullptr) {
   // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
   int rc = launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st);
   if (rc != OFDG_OK) return rc;
-  return launch_compose(c, ch, d_img0, d_img1, d_flow, st);
+  return launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex);
+}
+
+// The optional outputs are defined for the rigid modes: checked before anything is enqueued.
+static bool extras_requested(const ofdg_extras* ex) { return ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1); }
+static int check_extras(ofdg_ctx* c, const ofdg_extras* ex, const char* fn) {
+  if (extras_requested(ex) && c->prm.mode == 9) {
+    c->err = std::string(fn) + ": backward flow, labels and occlusion are defined for the rigid modes only (mode 9: the reference's "
+             "inverse branch adds the forward warp field, DG:403-406, 715-716)";
+    return OFDG_EINVAL;
+  }
+  return OFDG_OK;
 }
 
 // CImg get_resize(.., 3), enlarging branch: source index and weight of every destination pixel (running double sums,
@@ -1311,16 +1360,21 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
 
 int ofdg_render(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                 float* d_img0, float* d_img1, float* d_flow, void* stream) {
+  return ofdg_render_ex(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, stream);
+}
+int ofdg_render_ex(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                   float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
     if (c) c->err = "ofdg_render: invalid argument";
     return OFDG_EINVAL;
   }
+  { int rcx = check_extras(c, ex, "ofdg_render_ex"); if (rcx != OFDG_OK) return rcx; }
   stream = own_stream(c, stream);
   // the batch's records travel on the chain's own stream into its private slot
   ofdg_ctx::Chain& ch = take_chain(c);
   int rc = upload_slot(c, ch.slot, tasks, n_tasks, bps, n_bps, chain_stream(c, ch, (hipStream_t)stream), ch.stage, false);
   if (rc != OFDG_OK) return rc;
-  return launch_resident(c, ch, ch.slot, d_img0, d_img1, d_flow, (hipStream_t)stream);
+  return launch_resident(c, ch, ch.slot, d_img0, d_img1, d_flow, (hipStream_t)stream, -1, ex);
 }
 
 int ofdg_upload_slot(ofdg_ctx* c, int slot, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
@@ -1390,7 +1444,12 @@ static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
 // sampler: a sample is a pure function of (seed, global index)) and render them.
 int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
                          void* stream) {
+  return ofdg_forward_counter_ex(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, stream);
+}
+int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
+                            const ofdg_extras* ex, void* stream) {
   if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
+  { int rcx = check_extras(c, ex, "ofdg_forward_counter_ex"); if (rcx != OFDG_OK) return rcx; }
   stream = own_stream(c, stream);
   // A sample is a pure function of (seed, global index): the chain samples, realises and prepares the batch on the device
   // and composes it, all in order on its stream.  Like the reference's prefetch thread (data_generation_layer.cpp:141-172)
@@ -1409,7 +1468,7 @@ int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, floa
   };
   int rc = prepare_on(ch, first_index, st, chain_stream(c, ch, st) != st);
   if (rc != OFDG_OK) return rc;
-  rc = launch_compose(c, ch, d_img0, d_img1, d_flow, st);
+  rc = launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex);
   if (rc != OFDG_OK) return rc;
   // (the caller's batch is composed: from here on the call has succeeded, whatever happens to the batches prepared ahead)
   const long long prev_first = c->last_first;
@@ -1470,13 +1529,17 @@ long long ofdg_shard_first_index(long long step, int batch, int world_size, int 
 }
 
 int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
+  return ofdg_forward_ex(c, d_img0, d_img1, d_flow, nullptr, stream);
+}
+int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c) return OFDG_EINVAL;
+  { int rcx = check_extras(c, ex, "ofdg_forward_ex"); if (rcx != OFDG_OK) return rcx; }
   if (c->prm.sampler == OFDG_SAMPLER_COUNTER) {
     // rank r owns global indices step*B*world + r*B + [0, B)
     const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
     if (B < 1 || rank < 0 || rank >= world) { c->err = "ofdg_forward: bad batch_size / rank"; return OFDG_EINVAL; }
     const long long first = ofdg_shard_first_index(c->step, B, world, rank);
-    const int rc = ofdg_forward_counter(c, first, B, d_img0, d_img1, d_flow, stream);
+    const int rc = ofdg_forward_counter_ex(c, first, B, d_img0, d_img1, d_flow, ex, stream);
     if (rc == OFDG_OK) c->step++;  // (a failed call does not advance the checkpoint counter)
     return rc;
   }
@@ -1490,8 +1553,8 @@ int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void*
     int rc = c->sampler->next_task(&c->fw_bps, &c->fw_tasks[i], &c->err);
     if (rc != OFDG_OK) return rc;
   }
-  const int rc = ofdg_render(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), d_img0, d_img1,
-                             d_flow, stream);
+  const int rc = ofdg_render_ex(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), d_img0, d_img1,
+                                d_flow, ex, stream);
   // the streams have moved on either way; the batch counts once it is in flight
   if (rc == OFDG_OK) c->step++;
   else ofdg_set_step(c, c->step);  // rewind the streams (and the crop server) to the start of this batch
