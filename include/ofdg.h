@@ -270,6 +270,34 @@ int ofdg_forward_ex(ofdg_ctx* ctx, float* d_image0, float* d_image1, float* d_fl
 int ofdg_forward_counter_ex(ofdg_ctx* ctx, long long first_index, int n_samples, float* d_image0, float* d_image1,
                             float* d_flow, const ofdg_extras* ex, void* stream);
 
+/*
+ * Compact output formats: the same calls with the frames as uint8 and / or the flow as IEEE binary16, chosen per call (like
+ * ofdg_extras the format belongs to the call, not to the context).
+ *   image  OFDG_FMT_F32  float32 [n,3,H,W] as in the plain calls
+ *          OFDG_FMT_U8   uint8   [n,3,H,W], planar B,G,R: the byte itself - the value whose float is what the plain call stores
+ *                        (the u8 -> float widening of DG:1229-1244 skipped; exact)
+ *   flow   OFDG_FMT_F32  float32 [n,2,H,W] as in the plain calls
+ *          OFDG_FMT_F16  binary16 [n,2,H,W]: the plain call's float32 value converted ONCE, round to nearest even.  This is
+ *                        lossy: a half has 11 significant bits, so the spacing is 0.125 px from |flow| = 128 and 0.25 px from
+ *                        256 (0.0625 px below 128), and values beyond 65504 become infinite.
+ * Valid: image F32 | U8, flow F32 | F16.  fmt == NULL or {F32, F32} IS the plain call (same kernels, same bytes).  Any other
+ * code in `image` / `flow`, or a non-zero `reserved`, fails with OFDG_EINVAL, enqueues nothing and names the field in
+ * ofdg_last_error.  All 13 modes (mode 9 included), both samplers, every background_prep.  Layout, sample slots, stream
+ * semantics, chains, tickets and error words are those of the plain calls.
+ * Not offered: a compact format together with the optional outputs of ofdg_extras - these calls take none, the occlusion
+ * pass reads the float32 flow -, ofdg_render_slot / ofdg_render_resident, and the Caffe-shaped layer (ofdg_layer_forward returns float blobs, as the
+ * layer it stands for does).
+ */
+#define OFDG_FMT_F32 0   /* float32 (the plain calls) */
+#define OFDG_FMT_U8  1   /* frames only: the byte itself, uint8 [n,3,H,W] planar B,G,R */
+#define OFDG_FMT_F16 2   /* flow only: IEEE binary16 [n,2,H,W], the float32 flow rounded to nearest even, once */
+typedef struct ofdg_out_format { int32_t image; int32_t flow; int32_t reserved[2]; } ofdg_out_format;
+int ofdg_render_fmt(ofdg_ctx* ctx, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                    void* d_image0, void* d_image1, void* d_flow, const ofdg_out_format* fmt, void* stream);
+int ofdg_forward_fmt(ofdg_ctx* ctx, void* d_image0, void* d_image1, void* d_flow, const ofdg_out_format* fmt, void* stream);
+int ofdg_forward_counter_fmt(ofdg_ctx* ctx, long long first_index, int n_samples, void* d_image0, void* d_image1,
+                             void* d_flow, const ofdg_out_format* fmt, void* stream);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -100,6 +100,7 @@ EXPORTS = [
     "ofdg_comm_last_error", "ofdg_comm_bcast_setup", "ofdg_comm_bcast_abort", "ofdg_comm_nccl_count", "ofdg_comm_bcast_pool", "ofdg_comm_agree", "ofdg_setup_of", "ofdg_setup_params",
     "ofdg_setup_alloc_pool", "ofdg_pool_device_mixed", "ofdg_pool_device_image", "ofdg_layer_create_dist",
     "ofdg_render_ex", "ofdg_forward_ex", "ofdg_forward_counter_ex",
+    "ofdg_render_fmt", "ofdg_forward_fmt", "ofdg_forward_counter_fmt",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -109,6 +110,44 @@ EXTRAS = {"flow1": (2, "float32"), "occ0": (1, "float32"), "occ1": (1, "float32"
 class Extras(C.Structure):
     """ofdg_extras: device pointers of the optional outputs (NULL = not requested)."""
     _fields_ = [("flow1", C.c_void_p), ("occ0", C.c_void_p), ("occ1", C.c_void_p), ("label0", C.c_void_p), ("label1", C.c_void_p)]
+
+
+# the compact output formats (ofdg_out_format, include/ofdg.h)
+FMT_F32, FMT_U8, FMT_F16 = 0, 1, 2
+_FMT_NAMES = {"f32": FMT_F32, "u8": FMT_U8, "f16": FMT_F16}
+
+
+class OutFormat(C.Structure):
+    """ofdg_out_format: element types of the frames (FMT_F32 | FMT_U8) and of the flow (FMT_F32 | FMT_F16)."""
+    _fields_ = [("image", C.c_int32), ("flow", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def output_format(image0, image1, flow, n, height, width):
+    """The format codes (image, flow) of three output tensors for n samples of height x width: uint8 or float32 frames (both
+    alike), float16 or float32 flow.  Raises ValueError for anything else, or for a tensor with fewer elements than
+    [n,3,H,W] / [n,2,H,W].  Looks at dtype and size only (works on CPU tensors)."""
+    def name(t):
+        return str(t.dtype).replace("torch.", "")
+
+    if image0.dtype != image1.dtype:
+        raise ValueError("image0 and image1 must have one dtype, got %s and %s" % (name(image0), name(image1)))
+    codes = []
+    for what, t, valid in (("image0", image0, {"float32": FMT_F32, "uint8": FMT_U8}), ("flow", flow, {"float32": FMT_F32, "float16": FMT_F16})):
+        if name(t) not in valid:
+            raise ValueError("%s must be %s, got %s" % (what, " or ".join(sorted(valid)), name(t)))
+        codes.append(valid[name(t)])
+    for what, t, ch in (("image0", image0, 3), ("image1", image1, 3), ("flow", flow, 2)):
+        if t.numel() < n * ch * height * width:
+            raise ValueError("%s holds %d elements, [%d,%d,%d,%d] needs %d" % (what, t.numel(), n, ch, height, width, n * ch * height * width))
+    return tuple(codes)
+
+
+def _fmt_codes(fmt):
+    """fmt=("u8", "f16") (names or FMT_* codes) -> (image code, flow code); None -> float32 everywhere."""
+    if fmt is None:
+        return FMT_F32, FMT_F32
+    image, flow = fmt
+    return tuple(_FMT_NAMES[f] if isinstance(f, str) else int(f) for f in (image, flow))
 
 
 def build(verbose=False):
@@ -174,6 +213,9 @@ def lib():
         L.ofdg_render_ex.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(Extras), vp]
         L.ofdg_forward_ex.argtypes = [vp, vp, vp, vp, C.POINTER(Extras), vp]
         L.ofdg_forward_counter_ex.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(Extras), vp]
+        L.ofdg_render_fmt.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(OutFormat), vp]
+        L.ofdg_forward_fmt.argtypes = [vp, vp, vp, vp, C.POINTER(OutFormat), vp]
+        L.ofdg_forward_counter_fmt.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(OutFormat), vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -376,9 +418,31 @@ class Generator:
         return tasks, bps, n.value
 
     # -- hot path --
-    def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0, extras=None):
+    def _out_format(self, img0, img1, flow, n, fmt, extras):
+        """The ofdg_out_format of a call, or None for the plain entry points: from the tensors' dtypes (output_format) when
+        tensors are passed, from fmt=("u8", "f16") for raw pointers.  A compact format does not combine with extras."""
+        if all(hasattr(t, "data_ptr") for t in (img0, img1, flow)):
+            codes = output_format(img0, img1, flow, n, self.params.height, self.params.width)
+            if fmt is not None and _fmt_codes(fmt) != codes:
+                raise ValueError("fmt=%r does not match the tensors' dtypes" % (fmt,))
+        else:
+            codes = _fmt_codes(fmt)
+        if codes == (FMT_F32, FMT_F32):
+            return None
+        if extras is not None:
+            raise ValueError("the compact output formats do not combine with extras= (the occlusion pass reads the float32 flow)")
+        return OutFormat(codes[0], codes[1])
+
+    def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0, extras=None, fmt=None):
         """img0/img1/flow: device pointers (int) or torch CUDA tensors.  extras: {name: tensor} of optional outputs
-        (alloc_extras; rigid modes): flow1, occ0, occ1, label0, label1."""
+        (alloc_extras; rigid modes): flow1, occ0, occ1, label0, label1.  Tensors may be uint8 frames and / or a float16 flow
+        (alloc_outputs(image_dtype=, flow_dtype=)): the call then writes those formats; with raw pointers say
+        fmt=("u8", "f16")."""
+        of = self._out_format(img0, img1, flow, n_tasks, fmt, extras)
+        if of is not None:
+            self._check(lib().ofdg_render_fmt(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
+                                              _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of), C.c_void_p(stream)))
+            return
         if extras is None:
             self._check(lib().ofdg_render(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
                                           _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
@@ -413,14 +477,23 @@ class Generator:
     def render_slot(self, slot, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_slot(self.h, slot, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
 
-    def forward(self, img0, img1, flow, stream=0, extras=None):
+    def forward(self, img0, img1, flow, stream=0, extras=None, fmt=None):
+        of = self._out_format(img0, img1, flow, self.params.batch_size, fmt, extras)
+        if of is not None:
+            self._check(lib().ofdg_forward_fmt(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of), C.c_void_p(stream)))
+            return
         if extras is None:
             self._check(lib().ofdg_forward(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
             return
         ex = self._extras(extras, self.params.batch_size)
         self._check(lib().ofdg_forward_ex(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex), C.c_void_p(stream)))
 
-    def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None):
+    def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None, fmt=None):
+        of = self._out_format(img0, img1, flow, n, fmt, extras)
+        if of is not None:
+            self._check(lib().ofdg_forward_counter_fmt(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of),
+                                                       C.c_void_p(stream)))
+            return
         if extras is None:
             self._check(lib().ofdg_forward_counter(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
             return
@@ -691,12 +764,19 @@ def device_pointers(tensors):
     return tuple(_dptr(t) for t in tensors)
 
 
-def alloc_outputs(n, height, width, device="cuda"):
-    """The three top blobs: image0 [n,3,H,W], image1 [n,3,H,W], flow [n,2,H,W] (float32)."""
+def alloc_outputs(n, height, width, device="cuda", image_dtype=None, flow_dtype=None):
+    """The three top blobs: image0 [n,3,H,W], image1 [n,3,H,W], flow [n,2,H,W]; float32, or the compact formats
+    image_dtype=torch.uint8 / flow_dtype=torch.float16 (ofdg_out_format, include/ofdg.h)."""
     import torch
-    return (torch.zeros((n, 3, height, width), dtype=torch.float32, device=device),
-            torch.zeros((n, 3, height, width), dtype=torch.float32, device=device),
-            torch.zeros((n, 2, height, width), dtype=torch.float32, device=device))
+    image_dtype = torch.float32 if image_dtype is None else image_dtype
+    flow_dtype = torch.float32 if flow_dtype is None else flow_dtype
+    if image_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("image_dtype must be torch.float32 or torch.uint8, got %s" % image_dtype)
+    if flow_dtype not in (torch.float32, torch.float16):
+        raise ValueError("flow_dtype must be torch.float32 or torch.float16, got %s" % flow_dtype)
+    return (torch.zeros((n, 3, height, width), dtype=image_dtype, device=device),
+            torch.zeros((n, 3, height, width), dtype=image_dtype, device=device),
+            torch.zeros((n, 2, height, width), dtype=flow_dtype, device=device))
 
 
 def alloc_extras(n, height, width, names=("flow1", "occ0", "occ1", "label0", "label1"), device="cuda"):
@@ -836,10 +916,16 @@ class FlowLoader:
     Use the tensors on the consumer stream, or synchronise before touching them elsewhere.  Samples shard
     over ranks by global index (params.rank / params.world_size): no communication.
     extras=("flow1", "occ0", ...): the optional outputs are rendered too, into buffers cycled with the ring, and every
-    batch is (image0, image1, flow, {name: tensor})."""
+    batch is (image0, image1, flow, {name: tensor}).
+    image_dtype=torch.uint8 / flow_dtype=torch.float16: the ring's buffers are allocated and rendered in the compact formats
+    (not together with extras)."""
 
-    def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, **kw):
+    def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
+                 **kw):
         import torch
+        compact = image_dtype not in (None, torch.float32) or flow_dtype not in (None, torch.float32)
+        if compact and extras is not None:
+            raise ValueError("the compact output formats do not combine with extras= (the occlusion pass reads the float32 flow)")
         self.gen = Generator(params, **kw)
         p = self.gen.params
         if pool is not None:
@@ -851,7 +937,8 @@ class FlowLoader:
         self.start = int(start)
         self.prefetch = max(2, int(prefetch))
         self.consumer = torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(int(stream))
-        self.bufs = [alloc_outputs(p.batch_size, p.height, p.width) for _ in range(self.prefetch)]
+        self.bufs = [alloc_outputs(p.batch_size, p.height, p.width, image_dtype=image_dtype, flow_dtype=flow_dtype)
+                     for _ in range(self.prefetch)]
         self.extras = tuple(extras) if extras is not None else None
         self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras) if self.extras is not None else None
                       for _ in range(self.prefetch)]

@@ -1124,16 +1124,22 @@ struct ExtOut {
 #define OFDG_EXT_NT 1
 #endif
 
-template <bool kPow2, bool kDeform = false, bool kExtra = false>
+// Compact output formats (kCompact; the bits of the wrapper kernels' out_fmt argument, wave-uniform): the frames as the bytes
+// the kernel holds anyway instead of their floats, the flow rounded once to binary16.
+constexpr int kOutImageU8 = 1, kOutFlowF16 = 2;
+
+template <bool kPow2, bool kDeform = false, bool kExtra = false, bool kCompact = false>
 __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask,
                                               const DevObject* __restrict__ objects, const uint8_t* __restrict__ cov,
                                               int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
                                               const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool,
                                               float* __restrict__ img0, float* __restrict__ img1, float* __restrict__ flow,
                                               const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count,
-                                              const DevCropRef* __restrict__ crops = nullptr, ExtOut ext = ExtOut{nullptr, nullptr, nullptr}) {
+                                              const DevCropRef* __restrict__ crops = nullptr, ExtOut ext = ExtOut{nullptr, nullptr, nullptr},
+                                              int out_fmt = 0) {
   static_assert(kPx == 4, "mask bytes are packed four to a word");
   static_assert(!(kDeform && kExtra), "the extras are defined for the rigid modes only");
+  static_assert(!(kCompact && kExtra), "the compact formats do not combine with the extras");
   step_kernel_priority();
   if (blockIdx.x == 0 && threadIdx.x == 0) *item_count = 0;  // raster_kernel has consumed the work list
   // XCD-aware strip mapping: blocks b and b + 8 share an XCD (round-robin dispatch).  Every XCD takes every 8th run of 32
@@ -1565,6 +1571,63 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
   }
 
   if (!inside) return;
+  if constexpr (kCompact) {
+    // Compact epilogue.  uint8 frames: DG:1229-1244 skipped - the B, G, R bytes of the lane's four BGRX words gathered into one
+    // dword per plane (v_perm_b32, no conversion), 4-byte streaming stores (a row of a plane is 8-byte aligned: W % 8 == 0).
+    // fp16 flow: the float32 flow converted once, round to nearest even (v_cvt_f16_f32 under the default rounding mode - not
+    // v_cvt_pkrtz, which rounds towards zero), 8-byte stores.  Offsets in pixels, scaled by the element size of each output.
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    const size_t plane = (size_t)W * H;
+    uint32_t op = (uint32_t)y * (uint32_t)W + (uint32_t)x0;
+    asm volatile("" : "+v"(op));
+    if (out_fmt & kOutImageU8) {
+      char* b0 = reinterpret_cast<char*>(img0) + (size_t)s * 3 * plane;
+      char* b1 = reinterpret_cast<char*>(img1) + (size_t)s * 3 * plane;
+      // v_perm_b32 selectors (bytes 0-3: second operand, 4-7: first): two words -> {B0, B1, G0, G1} and {R0, R1, 0, 0}, then
+      // the halves of two such pairs side by side: seven instructions per frame
+      auto planes = [](const uint32_t (&px)[kPx], uint32_t& b, uint32_t& g, uint32_t& r) {
+        const uint32_t lo_bg = __builtin_amdgcn_perm(px[1], px[0], 0x05010400u), lo_r = __builtin_amdgcn_perm(px[1], px[0], 0x0C0C0602u);
+        const uint32_t hi_bg = __builtin_amdgcn_perm(px[3], px[2], 0x05010400u), hi_r = __builtin_amdgcn_perm(px[3], px[2], 0x0C0C0602u);
+        b = __builtin_amdgcn_perm(hi_bg, lo_bg, 0x05040100u);
+        g = __builtin_amdgcn_perm(hi_bg, lo_bg, 0x07060302u);
+        r = __builtin_amdgcn_perm(hi_r, lo_r, 0x05040100u);
+      };
+      uint32_t c[3];
+      planes(px0, c[0], c[1], c[2]);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(c[k], reinterpret_cast<uint32_t*>(b0 + (size_t)k * plane + op));
+      planes(px1, c[0], c[1], c[2]);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) __builtin_nontemporal_store(c[k], reinterpret_cast<uint32_t*>(b1 + (size_t)k * plane + op));
+    } else {
+      char* b0 = reinterpret_cast<char*>(img0 + (size_t)s * 3 * plane);
+      char* b1 = reinterpret_cast<char*>(img1 + (size_t)s * 3 * plane);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        f32x4 a = {(float)((px0[0] >> (8 * c)) & 255u), (float)((px0[1] >> (8 * c)) & 255u),
+                   (float)((px0[2] >> (8 * c)) & 255u), (float)((px0[3] >> (8 * c)) & 255u)};
+        f32x4 b = {(float)((px1[0] >> (8 * c)) & 255u), (float)((px1[1] >> (8 * c)) & 255u),
+                   (float)((px1[2] >> (8 * c)) & 255u), (float)((px1[3] >> (8 * c)) & 255u)};
+        __builtin_nontemporal_store(a, reinterpret_cast<f32x4*>(b0 + ((size_t)c * plane + op) * 4));
+        __builtin_nontemporal_store(b, reinterpret_cast<f32x4*>(b1 + ((size_t)c * plane + op) * 4));
+      }
+    }
+    if (out_fmt & kOutFlowF16) {
+      char* bf = reinterpret_cast<char*>(flow) + (size_t)s * 2 * plane * 2;
+      const f16x4 u = {(_Float16)fu[0], (_Float16)fu[1], (_Float16)fu[2], (_Float16)fu[3]};
+      const f16x4 v = {(_Float16)fv[0], (_Float16)fv[1], (_Float16)fv[2], (_Float16)fv[3]};
+      __builtin_nontemporal_store(u, reinterpret_cast<f16x4*>(bf + (size_t)op * 2));
+      __builtin_nontemporal_store(v, reinterpret_cast<f16x4*>(bf + (plane + op) * 2));
+    } else {
+      char* bf = reinterpret_cast<char*>(flow + (size_t)s * 2 * plane);
+      const f32x4 u = {fu[0], fu[1], fu[2], fu[3]};
+      const f32x4 v = {fv[0], fv[1], fv[2], fv[3]};
+      __builtin_nontemporal_store(u, reinterpret_cast<f32x4*>(bf + (size_t)op * 4));
+      __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(bf + (plane + op) * 4));
+    }
+    return;
+  }
   // u8 -> float planes (DG:1229-1245); streaming 16-byte stores, never re-read.  Every plane is a wave-uniform base
   // (SGPR pair) + one 32-bit byte offset per lane; the offset is made opaque so that no address arithmetic is
   // hoisted above the object loop (it would hold registers there).
@@ -1654,6 +1717,26 @@ __global__ __launch_bounds__(64) void compose_rigid_ext_pow2_kernel(
   compose_rigid<true, false, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool, bgpool,
                                    img0, img1, flow, frames, item_count, nullptr, ext);
 }
+// ... and with the compact output formats (out_fmt: kOutImageU8 | kOutFlowF16; img0 / img1 / flow point at buffers of
+// those element types).
+__global__ __launch_bounds__(64) void compose_rigid_fmt_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1,
+    void* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, int out_fmt) {
+  compose_rigid<false, false, false, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool,
+                                           bgpool, static_cast<float*>(img0), static_cast<float*>(img1), static_cast<float*>(flow), frames,
+                                           item_count, nullptr, ExtOut{nullptr, nullptr, nullptr}, out_fmt);
+}
+__global__ __launch_bounds__(64) void compose_rigid_fmt_pow2_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1,
+    void* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, int out_fmt) {
+  compose_rigid<true, false, false, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool,
+                                          bgpool, static_cast<float*>(img0), static_cast<float*>(img1), static_cast<float*>(flow), frames,
+                                          item_count, nullptr, ExtOut{nullptr, nullptr, nullptr}, out_fmt);
+}
 
 // Occlusion maps from the labels and flows compose wrote (one pass per batch, behind compose on the same stream).  A pixel
 // of frame f is occluded (1.0f) when its flow, rounded as (int)floorf((float)x + u + 0.5f), leaves the frame or lands on a
@@ -1727,6 +1810,25 @@ __global__ __launch_bounds__(64) OFDG_DEFORM_OCC void compose_deform_pow2_kernel
     const DevShapeFrame* __restrict__ frames, const DevCropRef* __restrict__ crops, int* __restrict__ item_count) {
   compose_rigid<true, true>(samples, blockmask, objects, cov, (int)gridDim.x, dm.tiles_x, dm.tiles_y, dm.W, dm.H, dm.use_aa, dm.bg_pitch, dm.fg_pitch,
                             pool, bgpool, img0, img1, flow, frames, item_count, crops);
+}
+// Mode 9 with the compact output formats (out_fmt as for compose_rigid_fmt_kernel).
+__global__ __launch_bounds__(64) void compose_deform_fmt_kernel(
+    RenderDims dm, const DevSample* __restrict__ samples, const DevObject* __restrict__ objects,
+    const unsigned long long* __restrict__ blockmask, const uint8_t* __restrict__ cov, const uint32_t* __restrict__ pool,
+    const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1, void* __restrict__ flow,
+    const DevShapeFrame* __restrict__ frames, const DevCropRef* __restrict__ crops, int* __restrict__ item_count, int out_fmt) {
+  compose_rigid<false, true, false, true>(samples, blockmask, objects, cov, (int)gridDim.x, dm.tiles_x, dm.tiles_y, dm.W, dm.H, dm.use_aa, dm.bg_pitch,
+                                          dm.fg_pitch, pool, bgpool, static_cast<float*>(img0), static_cast<float*>(img1),
+                                          static_cast<float*>(flow), frames, item_count, crops, ExtOut{nullptr, nullptr, nullptr}, out_fmt);
+}
+__global__ __launch_bounds__(64) OFDG_DEFORM_OCC void compose_deform_fmt_pow2_kernel(
+    RenderDims dm, const DevSample* __restrict__ samples, const DevObject* __restrict__ objects,
+    const unsigned long long* __restrict__ blockmask, const uint8_t* __restrict__ cov, const uint32_t* __restrict__ pool,
+    const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1, void* __restrict__ flow,
+    const DevShapeFrame* __restrict__ frames, const DevCropRef* __restrict__ crops, int* __restrict__ item_count, int out_fmt) {
+  compose_rigid<true, true, false, true>(samples, blockmask, objects, cov, (int)gridDim.x, dm.tiles_x, dm.tiles_y, dm.W, dm.H, dm.use_aa, dm.bg_pitch,
+                                         dm.fg_pitch, pool, bgpool, static_cast<float*>(img0), static_cast<float*>(img1),
+                                         static_cast<float*>(flow), frames, item_count, crops, ExtOut{nullptr, nullptr, nullptr}, out_fmt);
 }
 
 // --------------------------------------------------------------------------

@@ -1038,8 +1038,12 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
 // compose of the batch chain `ch` has prepared.  `st` is the caller's stream: if it is not the chain's own stream
 // (ofdg_stream), compose runs on `st` instead, behind what the caller enqueued there (the outputs may still be read) and
 // behind the chain's preparation kernels.
-static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float* d_img1, float* d_flow, hipStream_t st,
-                          const ofdg_extras* ex = nullptr) {
+// out_fmt != 0 (kOutImageU8 | kOutFlowF16): the compact kernels; the outputs then hold those element types.
+static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void* d_img1v, void* d_flowv, hipStream_t st,
+                          const ofdg_extras* ex = nullptr, int out_fmt = 0) {
+  float* const d_img0 = static_cast<float*>(d_img0v);
+  float* const d_img1 = static_cast<float*>(d_img1v);
+  float* const d_flow = static_cast<float*>(d_flowv);
   if (!ch.prep.valid) { c->err = "internal: compose without a prepared batch"; return OFDG_EINVAL; }
   ofdg_ctx::Slot& sl = *ch.prep.slot;
   const int W = c->prm.width, H = c->prm.height;
@@ -1091,7 +1095,23 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float
   // own completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
   // kernel's own start (a marker, ev[4]) and end.
   hipEvent_t k_start = (ev && c->profiling == 2) ? ev[4] : nullptr, k_stop = ev ? ev[5] : (occ ? nullptr : done);
-  if (extras && (W & (W - 1)) == 0)
+  if (out_fmt && c->prm.mode == 9 && (W & (W - 1)) == 0)
+    hipExtLaunchKernelGGL(compose_deform_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
+                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0v, d_img1v, d_flowv, sl.d_frames.p, croptab,
+                          sl.d_item_count, out_fmt);
+  else if (out_fmt && c->prm.mode == 9)
+    hipExtLaunchKernelGGL(compose_deform_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
+                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0v, d_img1v, d_flowv, sl.d_frames.p, croptab,
+                          sl.d_item_count, out_fmt);
+  else if (out_fmt && (W & (W - 1)) == 0)
+    hipExtLaunchKernelGGL(compose_rigid_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, out_fmt);
+  else if (out_fmt)
+    hipExtLaunchKernelGGL(compose_rigid_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, out_fmt);
+  else if (extras && (W & (W - 1)) == 0)
     hipExtLaunchKernelGGL(compose_rigid_ext_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
                           sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
                           d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count, xo);
@@ -1143,12 +1163,12 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, float* d_img0, float
 }
 
 // preparation + compose of the batch resident in `sl`, in order on chain `ch`
-static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, float* d_img0, float* d_img1, float* d_flow,
-                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras* ex = nullptr) {
+static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, void* d_img0, void* d_img1, void* d_flow,
+                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras* ex = nullptr, int out_fmt = 0) {
   // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
   int rc = launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st);
   if (rc != OFDG_OK) return rc;
-  return launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex);
+  return launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex, out_fmt);
 }
 
 // The optional outputs are defined for the rigid modes: checked before anything is enqueued.
@@ -1159,6 +1179,21 @@ static int check_extras(ofdg_ctx* c, const ofdg_extras* ex, const char* fn) {
              "inverse branch adds the forward warp field, DG:403-406, 715-716)";
     return OFDG_EINVAL;
   }
+  return OFDG_OK;
+}
+// ofdg_out_format -> the compose kernels' out_fmt bits (0: the plain call), checked before anything is enqueued.
+static int check_out_format(ofdg_ctx* c, const ofdg_out_format* fmt, const char* fn, int* out_fmt) {
+  *out_fmt = 0;
+  if (!fmt) return OFDG_OK;
+  auto fail = [&](const char* field, int value, const char* valid) {
+    c->err = std::string(fn) + ": ofdg_out_format." + field + " = " + std::to_string(value) + " (valid: " + valid + ")";
+    return OFDG_EINVAL;
+  };
+  if (fmt->image != OFDG_FMT_F32 && fmt->image != OFDG_FMT_U8) return fail("image", fmt->image, "OFDG_FMT_F32, OFDG_FMT_U8");
+  if (fmt->flow != OFDG_FMT_F32 && fmt->flow != OFDG_FMT_F16) return fail("flow", fmt->flow, "OFDG_FMT_F32, OFDG_FMT_F16");
+  for (int k = 0; k < 2; ++k)
+    if (fmt->reserved[k] != 0) return fail(k ? "reserved[1]" : "reserved[0]", fmt->reserved[k], "0");
+  *out_fmt = (fmt->image == OFDG_FMT_U8 ? kOutImageU8 : 0) | (fmt->flow == OFDG_FMT_F16 ? kOutFlowF16 : 0);
   return OFDG_OK;
 }
 
@@ -1362,6 +1397,9 @@ int ofdg_render(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blu
                 float* d_img0, float* d_img1, float* d_flow, void* stream) {
   return ofdg_render_ex(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, stream);
 }
+// ofdg_render / _ex / _fmt: `ex` and `fmt` are already checked; out_fmt as for launch_compose
+static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream);
 int ofdg_render_ex(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                    float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
@@ -1369,12 +1407,26 @@ int ofdg_render_ex(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_
     return OFDG_EINVAL;
   }
   { int rcx = check_extras(c, ex, "ofdg_render_ex"); if (rcx != OFDG_OK) return rcx; }
+  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex, 0, stream);
+}
+int ofdg_render_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                    void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
+  if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
+    if (c) c->err = "ofdg_render_fmt: invalid argument";
+    return OFDG_EINVAL;
+  }
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_render_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
+}
+static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream) {
   stream = own_stream(c, stream);
   // the batch's records travel on the chain's own stream into its private slot
   ofdg_ctx::Chain& ch = take_chain(c);
   int rc = upload_slot(c, ch.slot, tasks, n_tasks, bps, n_bps, chain_stream(c, ch, (hipStream_t)stream), ch.stage, false);
   if (rc != OFDG_OK) return rc;
-  return launch_resident(c, ch, ch.slot, d_img0, d_img1, d_flow, (hipStream_t)stream, -1, ex);
+  return launch_resident(c, ch, ch.slot, d_img0, d_img1, d_flow, (hipStream_t)stream, -1, ex, out_fmt);
 }
 
 int ofdg_upload_slot(ofdg_ctx* c, int slot, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
@@ -1446,10 +1498,23 @@ int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, floa
                          void* stream) {
   return ofdg_forward_counter_ex(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, stream);
 }
+static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                                const ofdg_extras* ex, int out_fmt, void* stream);
 int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
                             const ofdg_extras* ex, void* stream) {
   if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
   { int rcx = check_extras(c, ex, "ofdg_forward_counter_ex"); if (rcx != OFDG_OK) return rcx; }
+  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex, 0, stream);
+}
+int ofdg_forward_counter_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                             const ofdg_out_format* fmt, void* stream) {
+  if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_forward_counter_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
+}
+static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                                const ofdg_extras* ex, int out_fmt, void* stream) {
   stream = own_stream(c, stream);
   // A sample is a pure function of (seed, global index): the chain samples, realises and prepares the batch on the device
   // and composes it, all in order on its stream.  Like the reference's prefetch thread (data_generation_layer.cpp:141-172)
@@ -1468,7 +1533,7 @@ int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, f
   };
   int rc = prepare_on(ch, first_index, st, chain_stream(c, ch, st) != st);
   if (rc != OFDG_OK) return rc;
-  rc = launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex);
+  rc = launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex, out_fmt);
   if (rc != OFDG_OK) return rc;
   // (the caller's batch is composed: from here on the call has succeeded, whatever happens to the batches prepared ahead)
   const long long prev_first = c->last_first;
@@ -1531,15 +1596,26 @@ long long ofdg_shard_first_index(long long step, int batch, int world_size, int 
 int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
   return ofdg_forward_ex(c, d_img0, d_img1, d_flow, nullptr, stream);
 }
+static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream);
 int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c) return OFDG_EINVAL;
   { int rcx = check_extras(c, ex, "ofdg_forward_ex"); if (rcx != OFDG_OK) return rcx; }
+  return forward_impl(c, d_img0, d_img1, d_flow, ex, 0, stream);
+}
+int ofdg_forward_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_forward_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  return forward_impl(c, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
+}
+static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream) {
   if (c->prm.sampler == OFDG_SAMPLER_COUNTER) {
     // rank r owns global indices step*B*world + r*B + [0, B)
     const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
     if (B < 1 || rank < 0 || rank >= world) { c->err = "ofdg_forward: bad batch_size / rank"; return OFDG_EINVAL; }
     const long long first = ofdg_shard_first_index(c->step, B, world, rank);
-    const int rc = ofdg_forward_counter_ex(c, first, B, d_img0, d_img1, d_flow, ex, stream);
+    if (!d_img0 || !d_img1 || !d_flow || first < 0) return OFDG_EINVAL;
+    const int rc = forward_counter_impl(c, first, B, d_img0, d_img1, d_flow, ex, out_fmt, stream);
     if (rc == OFDG_OK) c->step++;  // (a failed call does not advance the checkpoint counter)
     return rc;
   }
@@ -1553,8 +1629,10 @@ int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, co
     int rc = c->sampler->next_task(&c->fw_bps, &c->fw_tasks[i], &c->err);
     if (rc != OFDG_OK) return rc;
   }
-  const int rc = ofdg_render_ex(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), d_img0, d_img1,
-                                d_flow, ex, stream);
+  int rc = OFDG_EINVAL;
+  if (!d_img0 || !d_img1 || !d_flow) c->err = "ofdg_render: invalid argument";
+  else rc = render_impl(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), d_img0, d_img1, d_flow, ex,
+                        out_fmt, stream);
   // the streams have moved on either way; the batch counts once it is in flight
   if (rc == OFDG_OK) c->step++;
   else ofdg_set_step(c, c->step);  // rewind the streams (and the crop server) to the start of this batch
