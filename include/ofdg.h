@@ -284,9 +284,9 @@ int ofdg_forward_counter_ex(ofdg_ctx* ctx, long long first_index, int n_samples,
  * code in `image` / `flow`, or a non-zero `reserved`, fails with OFDG_EINVAL, enqueues nothing and names the field in
  * ofdg_last_error.  All 13 modes (mode 9 included), both samplers, every background_prep.  Layout, sample slots, stream
  * semantics, chains, tickets and error words are those of the plain calls.
- * Not offered: a compact format together with the optional outputs of ofdg_extras - these calls take none, the occlusion
- * pass reads the float32 flow -, ofdg_render_slot / ofdg_render_resident, and the Caffe-shaped layer (ofdg_layer_forward returns float blobs, as the
- * layer it stands for does).
+ * The optional outputs of ofdg_extras in these formats: ofdg_*_ex_fmt below (these three calls take none).
+ * Not offered: ofdg_render_slot / ofdg_render_resident, and the Caffe-shaped layer (ofdg_layer_forward returns float blobs,
+ * as the layer it stands for does).
  */
 #define OFDG_FMT_F32 0   /* float32 (the plain calls) */
 #define OFDG_FMT_U8  1   /* frames only: the byte itself, uint8 [n,3,H,W] planar B,G,R */
@@ -297,6 +297,41 @@ int ofdg_render_fmt(ofdg_ctx* ctx, const ofdg_task* tasks, int n_tasks, const of
 int ofdg_forward_fmt(ofdg_ctx* ctx, void* d_image0, void* d_image1, void* d_flow, const ofdg_out_format* fmt, void* stream);
 int ofdg_forward_counter_fmt(ofdg_ctx* ctx, long long first_index, int n_samples, void* d_image0, void* d_image1,
                              void* d_flow, const ofdg_out_format* fmt, void* stream);
+
+/*
+ * The optional outputs together with the compact formats: ofdg_*_ex with an ofdg_out_format, and the extras in formats of
+ * their own.  Everything is exact; nothing here has a tolerance.
+ *   frames, flow    exactly what ofdg_*_fmt stores for `fmt`
+ *   flow1           the float32 value ofdg_*_ex stores, in the element type of the flow (fmt->flow): with OFDG_FMT_F16 converted
+ *                   once, round to nearest even - the same conversion as the flow
+ *   label0, label1  as in ofdg_extras
+ *   occ0, occ1      the definition of ofdg_extras, word for word: the target is rounded from the FLOAT32 flow,
+ *                   xr = (int)floorf((float)x + u + 0.5f), whatever format the flow is stored in - asking for an fp16 flow never
+ *                   changes an occlusion bit.  `occ` = OFDG_FMT_F32: float32 maps (1.0f / 0.0f, as ofdg_extras);
+ *                   OFDG_FMT_U8: uint8 [n,1,H,W], 1 where the float32 map is 1.0f, else 0
+ * ex == NULL or all pointers NULL behaves as the ofdg_*_fmt call; fmt == NULL or {F32, F32} with occ == OFDG_FMT_F32 behaves as
+ * the ofdg_*_ex call: in both cases the kernels and the bytes are those calls'.  An invalid `occ` code, a non-zero `reserved`,
+ * an invalid `fmt`, or mode 9 with any pointer set fail with OFDG_EINVAL, enqueue nothing and name the field in
+ * ofdg_last_error.  As in the calls above every pointer is optional independently, occlusion without the labels it needs
+ * keeps them (and the rounded targets) in a workspace of the context, and stream order, chains, tickets and error words are
+ * the same.  Rigid modes 1-8 and 10-13, both samplers, every background_prep.
+ */
+typedef struct ofdg_extras_fmt {
+  void*    flow1;   /* [n,2,H,W], element type = fmt->flow (float32 or binary16), or NULL */
+  void*    occ0;    /* [n,1,H,W], element type by `occ`, or NULL */
+  void*    occ1;    /* [n,1,H,W], element type by `occ`, or NULL */
+  uint8_t* label0;  /* [n,H,W] or NULL, as in ofdg_extras */
+  uint8_t* label1;  /* [n,H,W] or NULL, as in ofdg_extras */
+  int32_t  occ;     /* OFDG_FMT_F32 (1.0f / 0.0f) | OFDG_FMT_U8 (1 / 0) */
+  int32_t  reserved[3];
+} ofdg_extras_fmt;
+int ofdg_render_ex_fmt(ofdg_ctx* ctx, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                       void* d_image0, void* d_image1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt,
+                       void* stream);
+int ofdg_forward_ex_fmt(ofdg_ctx* ctx, void* d_image0, void* d_image1, void* d_flow, const ofdg_extras_fmt* ex,
+                        const ofdg_out_format* fmt, void* stream);
+int ofdg_forward_counter_ex_fmt(ofdg_ctx* ctx, long long first_index, int n_samples, void* d_image0, void* d_image1,
+                                void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream);
 
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).

@@ -101,6 +101,7 @@ EXPORTS = [
     "ofdg_setup_alloc_pool", "ofdg_pool_device_mixed", "ofdg_pool_device_image", "ofdg_layer_create_dist",
     "ofdg_render_ex", "ofdg_forward_ex", "ofdg_forward_counter_ex",
     "ofdg_render_fmt", "ofdg_forward_fmt", "ofdg_forward_counter_fmt",
+    "ofdg_render_ex_fmt", "ofdg_forward_ex_fmt", "ofdg_forward_counter_ex_fmt",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -140,6 +141,44 @@ def output_format(image0, image1, flow, n, height, width):
         if t.numel() < n * ch * height * width:
             raise ValueError("%s holds %d elements, [%d,%d,%d,%d] needs %d" % (what, t.numel(), n, ch, height, width, n * ch * height * width))
     return tuple(codes)
+
+
+class ExtrasFmt(C.Structure):
+    """ofdg_extras_fmt: ofdg_extras with flow1 in the flow's element type and the occlusion maps float32 (FMT_F32) or uint8
+    (FMT_U8)."""
+    _fields_ = [("flow1", C.c_void_p), ("occ0", C.c_void_p), ("occ1", C.c_void_p), ("label0", C.c_void_p), ("label1", C.c_void_p),
+                ("occ", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def extras_format(extras, flow_code, n, height, width):
+    """The occlusion format code (FMT_F32 | FMT_U8) of an extras dict {name: tensor or None} that goes with a flow of format
+    flow_code (FMT_F32 | FMT_F16) for n samples of height x width: flow1 must have the flow's dtype, occ0 / occ1 one dtype,
+    float32 or uint8, the labels are uint8, every tensor its shape ([n,2,H,W], [n,1,H,W], [n,H,W]).  Raises ValueError for
+    anything else.  Looks at dtype and shape only (works on CPU tensors)."""
+    def name(t):
+        return str(t.dtype).replace("torch.", "")
+
+    flow_dt = {FMT_F32: "float32", FMT_F16: "float16"}[flow_code]
+    occ_dt = None
+    for key, t in extras.items():
+        if key not in EXTRAS:
+            raise ValueError("unknown extra output %r (known: %s)" % (key, ", ".join(EXTRAS)))
+        if t is None:
+            continue
+        ch = EXTRAS[key][0]
+        shape = (n, height, width) if ch is None else (n, ch, height, width)
+        if key == "flow1":
+            valid = (flow_dt,)
+        elif key in ("occ0", "occ1"):
+            valid = ("float32", "uint8") if occ_dt is None else (occ_dt,)
+        else:
+            valid = ("uint8",)
+        if tuple(t.shape) != shape or name(t) not in valid:
+            why = " (the dtype of flow)" if key == "flow1" else " (occ0 and occ1 alike)" if key in ("occ0", "occ1") else ""
+            raise ValueError("extra %r must be %s %s%s, got %s %s" % (key, " or ".join(valid), shape, why, name(t), tuple(t.shape)))
+        if key in ("occ0", "occ1"):
+            occ_dt = name(t)
+    return FMT_U8 if occ_dt == "uint8" else FMT_F32
 
 
 def _fmt_codes(fmt):
@@ -216,6 +255,9 @@ def lib():
         L.ofdg_render_fmt.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(OutFormat), vp]
         L.ofdg_forward_fmt.argtypes = [vp, vp, vp, vp, C.POINTER(OutFormat), vp]
         L.ofdg_forward_counter_fmt.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(OutFormat), vp]
+        L.ofdg_render_ex_fmt.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
+        L.ofdg_forward_ex_fmt.argtypes = [vp, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
+        L.ofdg_forward_counter_ex_fmt.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -418,54 +460,45 @@ class Generator:
         return tasks, bps, n.value
 
     # -- hot path --
-    def _out_format(self, img0, img1, flow, n, fmt, extras):
-        """The ofdg_out_format of a call, or None for the plain entry points: from the tensors' dtypes (output_format) when
-        tensors are passed, from fmt=("u8", "f16") for raw pointers.  A compact format does not combine with extras."""
+    def _formats(self, img0, img1, flow, n, fmt, extras):
+        """(ofdg_out_format, ofdg_extras / ofdg_extras_fmt) of a call, each None where the call needs none: the output format
+        from the tensors' dtypes (output_format) when tensors are passed, from fmt=("u8", "f16") for raw pointers; the extras
+        checked against it (extras_format).  Float32 throughout gives the ofdg_extras of the float32 entry points."""
         if all(hasattr(t, "data_ptr") for t in (img0, img1, flow)):
             codes = output_format(img0, img1, flow, n, self.params.height, self.params.width)
             if fmt is not None and _fmt_codes(fmt) != codes:
                 raise ValueError("fmt=%r does not match the tensors' dtypes" % (fmt,))
         else:
             codes = _fmt_codes(fmt)
-        if codes == (FMT_F32, FMT_F32):
-            return None
-        if extras is not None:
-            raise ValueError("the compact output formats do not combine with extras= (the occlusion pass reads the float32 flow)")
-        return OutFormat(codes[0], codes[1])
+        of = None if codes == (FMT_F32, FMT_F32) else OutFormat(codes[0], codes[1])
+        if extras is None:
+            return of, None
+        occ = extras_format(extras, codes[1], n, self.params.height, self.params.width)
+        ex = Extras() if (of is None and occ == FMT_F32) else ExtrasFmt(occ=occ)
+        for name, t in extras.items():
+            if t is not None:
+                setattr(ex, name, _dptr(t).value)
+        return of, ex
 
     def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0, extras=None, fmt=None):
         """img0/img1/flow: device pointers (int) or torch CUDA tensors.  extras: {name: tensor} of optional outputs
         (alloc_extras; rigid modes): flow1, occ0, occ1, label0, label1.  Tensors may be uint8 frames and / or a float16 flow
         (alloc_outputs(image_dtype=, flow_dtype=)): the call then writes those formats; with raw pointers say
-        fmt=("u8", "f16")."""
-        of = self._out_format(img0, img1, flow, n_tasks, fmt, extras)
-        if of is not None:
-            self._check(lib().ofdg_render_fmt(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
-                                              _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of), C.c_void_p(stream)))
-            return
-        if extras is None:
-            self._check(lib().ofdg_render(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
-                                          _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
-            return
-        ex = self._extras(extras, n_tasks)
-        self._check(lib().ofdg_render_ex(self.h, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
-                                         _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex), C.c_void_p(stream)))
-
-    def _extras(self, extras, n):
-        """Check an extras dict against the batch (n samples of the ctx's frame size) and return its ofdg_extras."""
-        ex = Extras()
-        H, W = self.params.height, self.params.width
-        for name, t in extras.items():
-            if name not in EXTRAS:
-                raise ValueError("unknown extra output %r (known: %s)" % (name, ", ".join(EXTRAS)))
-            if t is None:
-                continue
-            ch, dt = EXTRAS[name]
-            shape = (n, H, W) if ch is None else (n, ch, H, W)
-            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dt:
-                raise ValueError("extra %r must be %s %s, got %s %s" % (name, dt, shape, str(t.dtype).replace("torch.", ""), tuple(t.shape)))
-            setattr(ex, name, _dptr(t).value)
-        return ex
+        fmt=("u8", "f16").  The extras follow: flow1 has the dtype of flow, occ0 / occ1 are float32 or uint8
+        (alloc_extras(flow_dtype=, occ_dtype=))."""
+        of, ex = self._formats(img0, img1, flow, n_tasks, fmt, extras)
+        L, t, b = lib(), C.cast(tasks, C.c_void_p), C.cast(bps, C.c_void_p)
+        out = (_dptr(img0), _dptr(img1), _dptr(flow))
+        if isinstance(ex, ExtrasFmt):
+            rc = L.ofdg_render_ex_fmt(self.h, t, n_tasks, b, n_bps, *out, C.byref(ex), C.byref(of) if of is not None else None,
+                                      C.c_void_p(stream))
+        elif of is not None:
+            rc = L.ofdg_render_fmt(self.h, t, n_tasks, b, n_bps, *out, C.byref(of), C.c_void_p(stream))
+        elif ex is not None:
+            rc = L.ofdg_render_ex(self.h, t, n_tasks, b, n_bps, *out, C.byref(ex), C.c_void_p(stream))
+        else:
+            rc = L.ofdg_render(self.h, t, n_tasks, b, n_bps, *out, C.c_void_p(stream))
+        self._check(rc)
 
     def render_resident(self, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_resident(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
@@ -478,28 +511,31 @@ class Generator:
         self._check(lib().ofdg_render_slot(self.h, slot, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
 
     def forward(self, img0, img1, flow, stream=0, extras=None, fmt=None):
-        of = self._out_format(img0, img1, flow, self.params.batch_size, fmt, extras)
-        if of is not None:
-            self._check(lib().ofdg_forward_fmt(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of), C.c_void_p(stream)))
-            return
-        if extras is None:
-            self._check(lib().ofdg_forward(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
-            return
-        ex = self._extras(extras, self.params.batch_size)
-        self._check(lib().ofdg_forward_ex(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex), C.c_void_p(stream)))
+        of, ex = self._formats(img0, img1, flow, self.params.batch_size, fmt, extras)
+        L, out = lib(), (_dptr(img0), _dptr(img1), _dptr(flow))
+        if isinstance(ex, ExtrasFmt):
+            rc = L.ofdg_forward_ex_fmt(self.h, *out, C.byref(ex), C.byref(of) if of is not None else None, C.c_void_p(stream))
+        elif of is not None:
+            rc = L.ofdg_forward_fmt(self.h, *out, C.byref(of), C.c_void_p(stream))
+        elif ex is not None:
+            rc = L.ofdg_forward_ex(self.h, *out, C.byref(ex), C.c_void_p(stream))
+        else:
+            rc = L.ofdg_forward(self.h, *out, C.c_void_p(stream))
+        self._check(rc)
 
     def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None, fmt=None):
-        of = self._out_format(img0, img1, flow, n, fmt, extras)
-        if of is not None:
-            self._check(lib().ofdg_forward_counter_fmt(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(of),
-                                                       C.c_void_p(stream)))
-            return
-        if extras is None:
-            self._check(lib().ofdg_forward_counter(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
-            return
-        ex = self._extras(extras, n)
-        self._check(lib().ofdg_forward_counter_ex(self.h, first_index, n, _dptr(img0), _dptr(img1), _dptr(flow), C.byref(ex),
-                                                  C.c_void_p(stream)))
+        of, ex = self._formats(img0, img1, flow, n, fmt, extras)
+        L, out = lib(), (_dptr(img0), _dptr(img1), _dptr(flow))
+        if isinstance(ex, ExtrasFmt):
+            rc = L.ofdg_forward_counter_ex_fmt(self.h, first_index, n, *out, C.byref(ex), C.byref(of) if of is not None else None,
+                                               C.c_void_p(stream))
+        elif of is not None:
+            rc = L.ofdg_forward_counter_fmt(self.h, first_index, n, *out, C.byref(of), C.c_void_p(stream))
+        elif ex is not None:
+            rc = L.ofdg_forward_counter_ex(self.h, first_index, n, *out, C.byref(ex), C.c_void_p(stream))
+        else:
+            rc = L.ofdg_forward_counter(self.h, first_index, n, *out, C.c_void_p(stream))
+        self._check(rc)
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -779,17 +815,26 @@ def alloc_outputs(n, height, width, device="cuda", image_dtype=None, flow_dtype=
             torch.zeros((n, 2, height, width), dtype=flow_dtype, device=device))
 
 
-def alloc_extras(n, height, width, names=("flow1", "occ0", "occ1", "label0", "label1"), device="cuda"):
+def alloc_extras(n, height, width, names=("flow1", "occ0", "occ1", "label0", "label1"), device="cuda", flow_dtype=None,
+                 occ_dtype=None):
     """Buffers of the optional outputs, {name: tensor}: flow1 float32 [n,2,H,W], occ0 / occ1 float32 [n,1,H,W],
-    label0 / label1 uint8 [n,H,W] (see include/ofdg.h, ofdg_extras)."""
+    label0 / label1 uint8 [n,H,W] (see include/ofdg.h, ofdg_extras); flow_dtype=torch.float16 (the dtype of the flow they go
+    with) / occ_dtype=torch.uint8 for the compact formats (ofdg_extras_fmt)."""
     import torch
+    flow_dtype = torch.float32 if flow_dtype is None else flow_dtype
+    occ_dtype = torch.float32 if occ_dtype is None else occ_dtype
+    if flow_dtype not in (torch.float32, torch.float16):
+        raise ValueError("flow_dtype must be torch.float32 or torch.float16, got %s" % flow_dtype)
+    if occ_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("occ_dtype must be torch.float32 or torch.uint8, got %s" % occ_dtype)
+    dtypes = {"flow1": flow_dtype, "occ0": occ_dtype, "occ1": occ_dtype}
     out = {}
     for name in names:
         if name not in EXTRAS:
             raise ValueError("unknown extra output %r (known: %s)" % (name, ", ".join(EXTRAS)))
         ch, dt = EXTRAS[name]
         shape = (n, height, width) if ch is None else (n, ch, height, width)
-        out[name] = torch.zeros(shape, dtype=getattr(torch, dt), device=device)
+        out[name] = torch.zeros(shape, dtype=dtypes.get(name, getattr(torch, dt)), device=device)
     return out
 
 
@@ -917,15 +962,17 @@ class FlowLoader:
     over ranks by global index (params.rank / params.world_size): no communication.
     extras=("flow1", "occ0", ...): the optional outputs are rendered too, into buffers cycled with the ring, and every
     batch is (image0, image1, flow, {name: tensor}).
-    image_dtype=torch.uint8 / flow_dtype=torch.float16: the ring's buffers are allocated and rendered in the compact formats
-    (not together with extras)."""
+    image_dtype=torch.uint8 / flow_dtype=torch.float16: the ring's buffers are allocated and rendered in the compact formats.
+    With extras= that takes extras_compact=True: flow1 then has flow_dtype and the occlusion maps are uint8 (1 / 0); without
+    it the extras are float32 and a compact format with them raises."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
-                 **kw):
+                 extras_compact=False, **kw):
         import torch
         compact = image_dtype not in (None, torch.float32) or flow_dtype not in (None, torch.float32)
-        if compact and extras is not None:
-            raise ValueError("the compact output formats do not combine with extras= (the occlusion pass reads the float32 flow)")
+        if compact and extras is not None and not extras_compact:
+            raise ValueError("the compact output formats combine with extras= only with extras_compact=True (flow1 in flow_dtype, "
+                             "uint8 occlusion maps)")
         self.gen = Generator(params, **kw)
         p = self.gen.params
         if pool is not None:
@@ -940,7 +987,8 @@ class FlowLoader:
         self.bufs = [alloc_outputs(p.batch_size, p.height, p.width, image_dtype=image_dtype, flow_dtype=flow_dtype)
                      for _ in range(self.prefetch)]
         self.extras = tuple(extras) if extras is not None else None
-        self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras) if self.extras is not None else None
+        xfmt = dict(flow_dtype=flow_dtype, occ_dtype=torch.uint8) if extras_compact else {}
+        self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras, **xfmt) if self.extras is not None else None
                       for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set

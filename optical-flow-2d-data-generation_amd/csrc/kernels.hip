@@ -1127,6 +1127,10 @@ struct ExtOut {
 // Compact output formats (kCompact; the bits of the wrapper kernels' out_fmt argument, wave-uniform): the frames as the bytes
 // the kernel holds anyway instead of their floats, the flow rounded once to binary16.
 constexpr int kOutImageU8 = 1, kOutFlowF16 = 2;
+// ... and of the occlusion pass that goes with them: its maps as bytes (1 / 0) instead of floats; a rounded flow target
+// outside the frame in the packed targets compose leaves for it.
+constexpr int kOutOccU8 = 4;
+constexpr uint32_t kOccOutside = 0xFFFFFFFFu;
 
 template <bool kPow2, bool kDeform = false, bool kExtra = false, bool kCompact = false>
 __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask,
@@ -1136,10 +1140,10 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
                                               float* __restrict__ img0, float* __restrict__ img1, float* __restrict__ flow,
                                               const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count,
                                               const DevCropRef* __restrict__ crops = nullptr, ExtOut ext = ExtOut{nullptr, nullptr, nullptr},
-                                              int out_fmt = 0) {
+                                              int out_fmt = 0, uint32_t* __restrict__ tgt0 = nullptr,
+                                              uint32_t* __restrict__ tgt1 = nullptr) {
   static_assert(kPx == 4, "mask bytes are packed four to a word");
   static_assert(!(kDeform && kExtra), "the extras are defined for the rigid modes only");
-  static_assert(!(kCompact && kExtra), "the compact formats do not combine with the extras");
   step_kernel_priority();
   if (blockIdx.x == 0 && threadIdx.x == 0) *item_count = 0;  // raster_kernel has consumed the work list
   // XCD-aware strip mapping: blocks b and b + 8 share an XCD (round-robin dispatch).  Every XCD takes every 8th run of 32
@@ -1626,6 +1630,46 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
       __builtin_nontemporal_store(u, reinterpret_cast<f32x4*>(bf + (size_t)op * 4));
       __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(bf + (plane + op) * 4));
     }
+    if constexpr (kExtra) {
+      // The optional outputs behind a compact epilogue (every test is wave-uniform: kernel arguments).  flow1 goes through the
+      // same out_fmt bit as the flow, the labels are stored as in the float32 variant.
+      if (ext.flow1) {
+        if (out_fmt & kOutFlowF16) {
+          char* bf1 = reinterpret_cast<char*>(ext.flow1) + (size_t)s * 2 * plane * 2;
+          const f16x4 u1 = {(_Float16)fu1[0], (_Float16)fu1[1], (_Float16)fu1[2], (_Float16)fu1[3]};
+          const f16x4 v1 = {(_Float16)fv1[0], (_Float16)fv1[1], (_Float16)fv1[2], (_Float16)fv1[3]};
+          __builtin_nontemporal_store(u1, reinterpret_cast<f16x4*>(bf1 + (size_t)op * 2));
+          __builtin_nontemporal_store(v1, reinterpret_cast<f16x4*>(bf1 + (plane + op) * 2));
+        } else {
+          char* bf1 = reinterpret_cast<char*>(ext.flow1 + (size_t)s * 2 * plane);
+          const f32x4 u1 = {fu1[0], fu1[1], fu1[2], fu1[3]};
+          const f32x4 v1 = {fv1[0], fv1[1], fv1[2], fv1[3]};
+          __builtin_nontemporal_store(u1, reinterpret_cast<f32x4*>(bf1 + (size_t)op * 4));
+          __builtin_nontemporal_store(v1, reinterpret_cast<f32x4*>(bf1 + (plane + op) * 4));
+        }
+      }
+      if (ext.label0) __builtin_nontemporal_store(lab0, reinterpret_cast<uint32_t*>(ext.label0 + (size_t)s * plane + op));
+      if (ext.label1) __builtin_nontemporal_store(lab1, reinterpret_cast<uint32_t*>(ext.label1 + (size_t)s * plane + op));
+      // Occlusion targets for occlusion_fmt_kernel: where the float32 flow, rounded as occlusion_quad rounds it (the same
+      // __fadd_rn / floorf / float compares), sends each of the lane's four pixels - the linear index yr * W + xr of the other
+      // frame's pixel, kOccOutside when it leaves the frame.  Taken here, from the registers: the stored flow may be binary16,
+      // and an occlusion bit must not depend on that.  One 16-byte vector store per frame into the chain's workspace.
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      auto targets = [&](const float (&uu)[kPx], const float (&vv)[kPx]) {
+        uint32_t t[kPx];
+#pragma unroll
+        for (int p = 0; p < kPx; ++p) {
+          const float fx = floorf(__fadd_rn(__fadd_rn((float)(x0 + p), uu[p]), 0.5f));
+          const float fy = floorf(__fadd_rn(__fadd_rn((float)y, vv[p]), 0.5f));
+          const bool in = fx >= 0.f && fx < (float)W && fy >= 0.f && fy < (float)H;
+          t[p] = in ? (uint32_t)((int)fy * W + (int)fx) : kOccOutside;
+        }
+        const u32x4 r = {t[0], t[1], t[2], t[3]};
+        return r;
+      };
+      if (tgt0) __builtin_nontemporal_store(targets(fu, fv), reinterpret_cast<u32x4*>(tgt0 + (size_t)s * plane + op));
+      if (tgt1) __builtin_nontemporal_store(targets(fu1, fv1), reinterpret_cast<u32x4*>(tgt1 + (size_t)s * plane + op));
+    }
     return;
   }
   // u8 -> float planes (DG:1229-1245); streaming 16-byte stores, never re-read.  Every plane is a wave-uniform base
@@ -1785,6 +1829,70 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict_
     const occ_f32x4 o = occlusion_quad(f, f + plane, label1 + s * plane + pix, label0 + s * plane + pix, x0, y, W, H);
     __builtin_nontemporal_store(o, reinterpret_cast<occ_f32x4*>(occ1 + s * plane + pix));
   }
+}
+
+// The optional outputs together with the compact formats: the kExtra body with the compact epilogue (out_fmt as for
+// compose_rigid_fmt_kernel; ext.flow1 has the flow's element type), plus the packed occlusion targets of the frames whose
+// occlusion map is asked for (tgt0 / tgt1 [n,H,W], NULL: not stored).
+__global__ __launch_bounds__(64) void compose_rigid_ext_fmt_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1,
+    void* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, ExtOut ext, int out_fmt,
+    uint32_t* __restrict__ tgt0, uint32_t* __restrict__ tgt1) {
+  compose_rigid<false, false, true, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool,
+                                          bgpool, static_cast<float*>(img0), static_cast<float*>(img1), static_cast<float*>(flow), frames,
+                                          item_count, nullptr, ext, out_fmt, tgt0, tgt1);
+}
+__global__ __launch_bounds__(64) void compose_rigid_ext_fmt_pow2_kernel(
+    const DevSample* __restrict__ samples, const unsigned long long* __restrict__ blockmask, const DevObject* __restrict__ objects,
+    const uint8_t* __restrict__ cov, int n_strips, int tiles_x, int tiles_y, int W, int H, int use_aa, int bg_pitch, int fg_pitch,
+    const uint32_t* __restrict__ pool, const uint32_t* __restrict__ bgpool, void* __restrict__ img0, void* __restrict__ img1,
+    void* __restrict__ flow, const DevShapeFrame* __restrict__ frames, int* __restrict__ item_count, ExtOut ext, int out_fmt,
+    uint32_t* __restrict__ tgt0, uint32_t* __restrict__ tgt1) {
+  compose_rigid<true, false, true, true>(samples, blockmask, objects, cov, n_strips, tiles_x, tiles_y, W, H, use_aa, bg_pitch, fg_pitch, pool,
+                                         bgpool, static_cast<float*>(img0), static_cast<float*>(img1), static_cast<float*>(flow), frames,
+                                         item_count, nullptr, ext, out_fmt, tgt0, tgt1);
+}
+
+// Occlusion maps from the labels and the packed targets compose_rigid_ext_fmt_kernel wrote (behind it on the same stream):
+// the definition of occlusion_kernel with the rounding already done from the float32 flow.  A lane takes 4 adjacent pixels
+// of a frame: one 16-byte load of targets, one 4-byte load of its own labels, 4 byte gathers of the other frame's labels,
+// one 4-byte (uint8 maps: 1 / 0) or 16-byte (float32: 1.0f / 0.0f) store.  occ0 / occ1 NULL: not computed.
+__device__ __forceinline__ uint32_t occlusion_fmt_quad(const uint32_t* __restrict__ tgt, const uint8_t* __restrict__ own,
+                                                       const uint8_t* __restrict__ other, uint32_t plane) {
+  const uint4 t = *reinterpret_cast<const uint4*>(tgt);
+  const uint32_t l = *reinterpret_cast<const uint32_t*>(own);
+  const uint32_t tt[4] = {t.x, t.y, t.z, t.w};
+  uint32_t o = 0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const bool in = tt[p] < plane;  // (kOccOutside is not; nothing else is ever stored, and no index leaves the sample's plane)
+    const uint32_t b = (uint32_t)other[in ? tt[p] : 0u];  // (`other`: the sample's plane)
+    o |= ((in && b == ((l >> (8 * p)) & 255u)) ? 0u : 1u) << (8 * p);
+  }
+  return o;
+}
+__global__ __launch_bounds__(256) void occlusion_fmt_kernel(const uint32_t* __restrict__ tgt0, const uint32_t* __restrict__ tgt1,
+                                                            const uint8_t* __restrict__ label0, const uint8_t* __restrict__ label1,
+                                                            void* __restrict__ occ0, void* __restrict__ occ1, int W, int H, int n,
+                                                            int out_fmt) {
+  const int qpr = W >> 2;  // quads per row
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (long long)n * H * qpr) return;
+  const size_t plane = (size_t)W * H;
+  const size_t pix = (size_t)q * 4;  // s * plane + y * W + x0
+  const size_t sp = (size_t)(q / ((long long)H * qpr)) * plane;  // the sample's plane
+  auto store = [&](void* dst, uint32_t o) {
+    if (out_fmt & kOutOccU8) {
+      __builtin_nontemporal_store(o, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(dst) + pix));
+    } else {
+      const occ_f32x4 f = {(float)(o & 1u), (float)((o >> 8) & 1u), (float)((o >> 16) & 1u), (float)(o >> 24)};
+      __builtin_nontemporal_store(f, reinterpret_cast<occ_f32x4*>(static_cast<float*>(dst) + pix));
+    }
+  };
+  if (occ0) store(occ0, occlusion_fmt_quad(tgt0 + pix, label0 + pix, label1 + sp, (uint32_t)plane));
+  if (occ1) store(occ1, occlusion_fmt_quad(tgt1 + pix, label1 + pix, label0 + sp, (uint32_t)plane));
 }
 
 // Mode 9: the same body with the deformation paths compiled in (masks, textures and flow of deformed objects and backgrounds

@@ -135,6 +135,9 @@ struct ofdg_ctx {
     // (written by compose, read by the occlusion pass behind it; guarded by ev_done like `cov`)
     DevBuf<uint8_t> x_labels;
     DevBuf<float> x_flow1;
+    // ... and the packed occlusion targets [2][n][H][W] of the calls that combine the extras with a compact format (written by
+    // compose, read by occlusion_fmt_kernel behind it; guarded likewise)
+    DevBuf<uint32_t> x_targets;
     Slot slot;
     Stage stage;
     hipEvent_t ev_prep = nullptr;  // coverage ready (hand-over to a caller's stream)
@@ -414,6 +417,7 @@ void ofdg_destroy(ofdg_ctx* c) {
     ch.cov.release();
     ch.x_labels.release();
     ch.x_flow1.release();
+    ch.x_targets.release();
     if (ch.ev_prep) (void)hipEventDestroy(ch.ev_prep);
     if (ch.ev_done) (void)hipEventDestroy(ch.ev_done);
     if (ch.stream) (void)hipStreamDestroy(ch.stream);
@@ -1039,8 +1043,10 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
 // (ofdg_stream), compose runs on `st` instead, behind what the caller enqueued there (the outputs may still be read) and
 // behind the chain's preparation kernels.
 // out_fmt != 0 (kOutImageU8 | kOutFlowF16): the compact kernels; the outputs then hold those element types.
+// ex (checked): the optional outputs; float32 throughout (out_fmt 0, ex->occ F32) they take the kernels of ofdg_*_ex, with a
+// compact format or uint8 occlusion maps compose_rigid_ext_fmt_kernel + occlusion_fmt_kernel (ex->flow1: the flow's type).
 static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void* d_img1v, void* d_flowv, hipStream_t st,
-                          const ofdg_extras* ex = nullptr, int out_fmt = 0) {
+                          const ofdg_extras_fmt* ex = nullptr, int out_fmt = 0) {
   float* const d_img0 = static_cast<float*>(d_img0v);
   float* const d_img1 = static_cast<float*>(d_img1v);
   float* const d_flow = static_cast<float*>(d_flowv);
@@ -1053,15 +1059,24 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void*
   ExtOut xo{nullptr, nullptr, nullptr};
   const bool extras = ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1);
   const bool occ = extras && (ex->occ0 || ex->occ1);
+  const bool xfmt = extras && (out_fmt || ex->occ == OFDG_FMT_U8);  // the extras in a compact format of the outputs or of their own
+  uint32_t *tgt0 = nullptr, *tgt1 = nullptr;
   if (extras) {
     const size_t plane = (size_t)W * H, n = (size_t)dm.n_samples;
-    const bool ws_labels = occ && (!ex->label0 || !ex->label1), ws_flow1 = ex->occ1 && !ex->flow1;
-    if ((ws_labels && 2 * n * plane > ch.x_labels.cap) || (ws_flow1 && 2 * n * plane > ch.x_flow1.cap)) {
+    // (with a compact format the occlusion pass reads compose's rounded targets, not flow / flow1: no flow1 workspace)
+    const bool ws_labels = occ && (!ex->label0 || !ex->label1), ws_flow1 = !xfmt && ex->occ1 && !ex->flow1, ws_tgt = xfmt && occ;
+    if ((ws_labels && 2 * n * plane > ch.x_labels.cap) || (ws_flow1 && 2 * n * plane > ch.x_flow1.cap) ||
+        (ws_tgt && 2 * n * plane > ch.x_targets.cap)) {
       HIP_OK(c, hipDeviceSynchronize());
       if (ws_labels) HIP_OK(c, ch.x_labels.reserve(2 * n * plane));
       if (ws_flow1) HIP_OK(c, ch.x_flow1.reserve(2 * n * plane));
+      if (ws_tgt) HIP_OK(c, ch.x_targets.reserve(2 * n * plane));
     }
-    xo.flow1 = ex->flow1 ? ex->flow1 : (ws_flow1 ? ch.x_flow1.p : nullptr);
+    if (ws_tgt) {  // stored only for the frames whose map is asked for
+      tgt0 = ex->occ0 ? ch.x_targets.p : nullptr;
+      tgt1 = ex->occ1 ? ch.x_targets.p + n * plane : nullptr;
+    }
+    xo.flow1 = ex->flow1 ? static_cast<float*>(ex->flow1) : (ws_flow1 ? ch.x_flow1.p : nullptr);
     xo.label0 = ex->label0 ? ex->label0 : (occ ? ch.x_labels.p : nullptr);
     xo.label1 = ex->label1 ? ex->label1 : (occ ? ch.x_labels.p + n * plane : nullptr);
   }
@@ -1095,7 +1110,15 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void*
   // own completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
   // kernel's own start (a marker, ev[4]) and end.
   hipEvent_t k_start = (ev && c->profiling == 2) ? ev[4] : nullptr, k_stop = ev ? ev[5] : (occ ? nullptr : done);
-  if (out_fmt && c->prm.mode == 9 && (W & (W - 1)) == 0)
+  if (xfmt && (W & (W - 1)) == 0)
+    hipExtLaunchKernelGGL(compose_rigid_ext_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, xo, out_fmt, tgt0, tgt1);
+  else if (xfmt)
+    hipExtLaunchKernelGGL(compose_rigid_ext_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
+                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
+                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, xo, out_fmt, tgt0, tgt1);
+  else if (out_fmt && c->prm.mode == 9 && (W & (W - 1)) == 0)
     hipExtLaunchKernelGGL(compose_deform_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
                           sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0v, d_img1v, d_flowv, sl.d_frames.p, croptab,
                           sl.d_item_count, out_fmt);
@@ -1138,8 +1161,14 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void*
   HIP_OK(c, hipGetLastError());
   if (occ) {  // behind compose on the same stream; the chain's completion event (workspace, slot) goes on THIS packet
     const long long quads = (long long)dm.n_samples * H * (W / 4);
-    hipExtLaunchKernelGGL(occlusion_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0, d_flow,
-                          xo.flow1, xo.label0, xo.label1, ex->occ0, ex->occ1, W, H, dm.n_samples);
+    if (xfmt)
+      hipExtLaunchKernelGGL(occlusion_fmt_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0,
+                            tgt0, tgt1, xo.label0, xo.label1, ex->occ0, ex->occ1, W, H, dm.n_samples,
+                            ex->occ == OFDG_FMT_U8 ? kOutOccU8 : 0);
+    else
+      hipExtLaunchKernelGGL(occlusion_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0, d_flow,
+                            xo.flow1, xo.label0, xo.label1, static_cast<float*>(ex->occ0), static_cast<float*>(ex->occ1), W, H,
+                            dm.n_samples);
     HIP_OK(c, hipGetLastError());
   }
   if (ev) {
@@ -1164,7 +1193,7 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void*
 
 // preparation + compose of the batch resident in `sl`, in order on chain `ch`
 static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, void* d_img0, void* d_img1, void* d_flow,
-                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras* ex = nullptr, int out_fmt = 0) {
+                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras_fmt* ex = nullptr, int out_fmt = 0) {
   // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
   int rc = launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st);
   if (rc != OFDG_OK) return rc;
@@ -1172,14 +1201,33 @@ static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl,
 }
 
 // The optional outputs are defined for the rigid modes: checked before anything is enqueued.
-static bool extras_requested(const ofdg_extras* ex) { return ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1); }
-static int check_extras(ofdg_ctx* c, const ofdg_extras* ex, const char* fn) {
+static bool extras_requested(const ofdg_extras_fmt* ex) { return ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1); }
+// (internally every call carries its optional outputs as an ofdg_extras_fmt; ofdg_extras is that with float32 occlusion maps)
+static ofdg_extras_fmt widen_extras(const ofdg_extras* ex) {
+  ofdg_extras_fmt x{};
+  if (ex) { x.flow1 = ex->flow1; x.occ0 = ex->occ0; x.occ1 = ex->occ1; x.label0 = ex->label0; x.label1 = ex->label1; }
+  x.occ = OFDG_FMT_F32;
+  return x;
+}
+static int check_extras(ofdg_ctx* c, const ofdg_extras_fmt* ex, const char* fn) {
   if (extras_requested(ex) && c->prm.mode == 9) {
     c->err = std::string(fn) + ": backward flow, labels and occlusion are defined for the rigid modes only (mode 9: the reference's "
              "inverse branch adds the forward warp field, DG:403-406, 715-716)";
     return OFDG_EINVAL;
   }
   return OFDG_OK;
+}
+// ofdg_extras_fmt: its own fields first (whether or not a pointer is set), then what ofdg_extras is checked for.
+static int check_extras_fmt(ofdg_ctx* c, const ofdg_extras_fmt* ex, const char* fn) {
+  if (!ex) return OFDG_OK;
+  auto fail = [&](const std::string& field, int value, const char* valid) {
+    c->err = std::string(fn) + ": ofdg_extras_fmt." + field + " = " + std::to_string(value) + " (valid: " + valid + ")";
+    return OFDG_EINVAL;
+  };
+  if (ex->occ != OFDG_FMT_F32 && ex->occ != OFDG_FMT_U8) return fail("occ", ex->occ, "OFDG_FMT_F32, OFDG_FMT_U8");
+  for (int k = 0; k < 3; ++k)
+    if (ex->reserved[k] != 0) return fail("reserved[" + std::to_string(k) + "]", ex->reserved[k], "0");
+  return check_extras(c, ex, fn);
 }
 // ofdg_out_format -> the compose kernels' out_fmt bits (0: the plain call), checked before anything is enqueued.
 static int check_out_format(ofdg_ctx* c, const ofdg_out_format* fmt, const char* fn, int* out_fmt) {
@@ -1399,15 +1447,27 @@ int ofdg_render(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blu
 }
 // ofdg_render / _ex / _fmt: `ex` and `fmt` are already checked; out_fmt as for launch_compose
 static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
-                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream);
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream);
 int ofdg_render_ex(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                    float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
     if (c) c->err = "ofdg_render: invalid argument";
     return OFDG_EINVAL;
   }
-  { int rcx = check_extras(c, ex, "ofdg_render_ex"); if (rcx != OFDG_OK) return rcx; }
-  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex, 0, stream);
+  const ofdg_extras_fmt x = widen_extras(ex);
+  { int rcx = check_extras(c, &x, "ofdg_render_ex"); if (rcx != OFDG_OK) return rcx; }
+  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
+}
+int ofdg_render_ex_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
+  if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
+    if (c) c->err = "ofdg_render_ex_fmt: invalid argument";
+    return OFDG_EINVAL;
+  }
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_render_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  { int rcx = check_extras_fmt(c, ex, "ofdg_render_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
+  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex, out_fmt, stream);
 }
 int ofdg_render_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                     void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
@@ -1420,7 +1480,7 @@ int ofdg_render_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg
   return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
 }
 static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
-                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream) {
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
   stream = own_stream(c, stream);
   // the batch's records travel on the chain's own stream into its private slot
   ofdg_ctx::Chain& ch = take_chain(c);
@@ -1499,12 +1559,21 @@ int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, floa
   return ofdg_forward_counter_ex(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, stream);
 }
 static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                                const ofdg_extras* ex, int out_fmt, void* stream);
+                                const ofdg_extras_fmt* ex, int out_fmt, void* stream);
 int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
                             const ofdg_extras* ex, void* stream) {
   if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
-  { int rcx = check_extras(c, ex, "ofdg_forward_counter_ex"); if (rcx != OFDG_OK) return rcx; }
-  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex, 0, stream);
+  const ofdg_extras_fmt x = widen_extras(ex);
+  { int rcx = check_extras(c, &x, "ofdg_forward_counter_ex"); if (rcx != OFDG_OK) return rcx; }
+  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
+}
+int ofdg_forward_counter_ex_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                                const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
+  if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_forward_counter_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  { int rcx = check_extras_fmt(c, ex, "ofdg_forward_counter_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
+  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex, out_fmt, stream);
 }
 int ofdg_forward_counter_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
                              const ofdg_out_format* fmt, void* stream) {
@@ -1514,7 +1583,7 @@ int ofdg_forward_counter_fmt(ofdg_ctx* c, long long first_index, int n_samples, 
   return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
 }
 static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                                const ofdg_extras* ex, int out_fmt, void* stream) {
+                                const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
   stream = own_stream(c, stream);
   // A sample is a pure function of (seed, global index): the chain samples, realises and prepares the batch on the device
   // and composes it, all in order on its stream.  Like the reference's prefetch thread (data_generation_layer.cpp:141-172)
@@ -1596,11 +1665,20 @@ long long ofdg_shard_first_index(long long step, int batch, int world_size, int 
 int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
   return ofdg_forward_ex(c, d_img0, d_img1, d_flow, nullptr, stream);
 }
-static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream);
+static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream);
 int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
   if (!c) return OFDG_EINVAL;
-  { int rcx = check_extras(c, ex, "ofdg_forward_ex"); if (rcx != OFDG_OK) return rcx; }
-  return forward_impl(c, d_img0, d_img1, d_flow, ex, 0, stream);
+  const ofdg_extras_fmt x = widen_extras(ex);
+  { int rcx = check_extras(c, &x, "ofdg_forward_ex"); if (rcx != OFDG_OK) return rcx; }
+  return forward_impl(c, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
+}
+int ofdg_forward_ex_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt,
+                        void* stream) {
+  if (!c) return OFDG_EINVAL;
+  int out_fmt;
+  { int rcf = check_out_format(c, fmt, "ofdg_forward_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
+  { int rcx = check_extras_fmt(c, ex, "ofdg_forward_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
+  return forward_impl(c, d_img0, d_img1, d_flow, ex, out_fmt, stream);
 }
 int ofdg_forward_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
   if (!c) return OFDG_EINVAL;
@@ -1608,7 +1686,7 @@ int ofdg_forward_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, cons
   { int rcf = check_out_format(c, fmt, "ofdg_forward_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
   return forward_impl(c, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
 }
-static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras* ex, int out_fmt, void* stream) {
+static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
   if (c->prm.sampler == OFDG_SAMPLER_COUNTER) {
     // rank r owns global indices step*B*world + r*B + [0, B)
     const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
