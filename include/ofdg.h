@@ -333,6 +333,52 @@ int ofdg_forward_ex_fmt(ofdg_ctx* ctx, void* d_image0, void* d_image1, void* d_f
 int ofdg_forward_counter_ex_fmt(ofdg_ctx* ctx, long long first_index, int n_samples, void* d_image0, void* d_image1,
                                 void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream);
 
+/*
+ * Per-object annotation table: which objects a sample holds, where each one is visible in frame 0 and in frame 1, how much
+ * of it, and the affine motion that produced its flow.  It restates what the reference keeps per object while it renders:
+ * the index images of RenderCore::blitObject (DG:762-775) - here the label planes of ofdg_extras - reduced per object, and
+ * m_motion as setMotion / addBackgroundMotion leave it (DG:312-335), the matrix the flow of the object's pixels is computed
+ * with.  Rigid modes 1-8 and 10-13, both samplers.
+ *
+ * ofdg_object_table annotates the batch of the LAST render / forward call of this context (the batch ofdg_render_resident
+ * and ofdg_debug_coverage speak of).  Row k of sample i is d_rows[i * rows_per_sample + k] and describes the object whose
+ * label is k in the numbering of ofdg_extras: row 0 the background, row k the k-th top-level foreground object in ascending
+ * obj_id.  d_counts[i] = 1 + n_objects of sample i whatever rows_per_sample is; rows k >= d_counts[i] inside the table are
+ * all-zero bytes; objects k >= rows_per_sample are not reported (the count shows the truncation; no error flag is raised).
+ * Areas and boxes are of VISIBLE pixels - those whose label is the row's index, i.e. after the painter's order has hidden
+ * what lies below: an object wholly covered or moved out of the frame has area 0 and the empty box.
+ *
+ * d_label0 / d_label1: the [n,H,W] uint8 planes that call wrote (the caller's buffers; the workspace labels of an
+ * occlusion-only call are not used).  Either may be NULL: that frame's areas are 0 and its boxes empty; both NULL leaves ids,
+ * types, motions and counts.  The library cannot verify that the planes belong to that batch: it reduces what it is given
+ * (a byte that is no label of the sample is counted nowhere).  d_rows is 8-byte, the planes and d_counts 4-byte aligned.
+ *
+ * Asynchronous: two small kernels on `stream`, nothing on the host beyond the argument checks.  `stream` is the stream the
+ * labels were written on, i.e. the `stream` of that call; OFDG_STREAM_OWN: the internal stream that call worked on (which the
+ * context remembers - ofdg_stream() already names the next call's).  The batch's records stay valid until the kernels have
+ * read them: a later call that reuses them waits, as it does for a compose on a caller's stream.
+ *
+ * OFDG_EINVAL, nothing enqueued, the cause in ofdg_last_error: d_rows or d_counts NULL, rows_per_sample < 1, a misaligned
+ * pointer, no render / forward call made yet on this context, a mode-9 context.
+ */
+#define OFDG_MAX_OBJECT_ROWS 65          /* background + 64 foreground objects */
+typedef struct ofdg_object_row {         /* 96 bytes, no padding */
+  int32_t obj_id;      /* blueprint obj_id (background: OFDG_BACKGROUND_ID) */
+  int32_t obj_type;    /* OFDG_OBJ_ELLIPSE / POLYGON / COMPOSITE; 0 for the background row */
+  int32_t area0, area1;/* pixels of frame 0 / frame 1 whose label is this row's index */
+  int32_t box0[4];     /* x0, y0, x1, y1 inclusive, of those pixels in frame 0; area0 == 0: {W, H, -1, -1} */
+  int32_t box1[4];     /* the same in frame 1 */
+  double  motion[6];   /* m_motion as compose uses it (sx, shy, shx, sy, tx, ty; foreground: incl. background motion) */
+} ofdg_object_row;
+int ofdg_object_table(ofdg_ctx* ctx, const uint8_t* d_label0, const uint8_t* d_label1,
+                      ofdg_object_row* d_rows, int rows_per_sample, int32_t* d_counts, void* stream);
+/* The same reduction on the host (no GPU): fills area0 / area1 / box0 / box1 of the first min(counts[i], rows_per_sample)
+ * rows of each of the n samples from HOST label planes [n,height,width] (either may be NULL: area 0, the empty box) and
+ * leaves every other field and every other row alone.  OFDG_EINVAL (ofdg_host_last_error) for NULL counts / rows or sizes
+ * below 1. */
+int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, int width, int height,
+                           const int32_t* counts, ofdg_object_row* rows, int rows_per_sample);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -102,6 +102,7 @@ EXPORTS = [
     "ofdg_render_ex", "ofdg_forward_ex", "ofdg_forward_counter_ex",
     "ofdg_render_fmt", "ofdg_forward_fmt", "ofdg_forward_counter_fmt",
     "ofdg_render_ex_fmt", "ofdg_forward_ex_fmt", "ofdg_forward_counter_ex_fmt",
+    "ofdg_object_table", "ofdg_host_object_table",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -189,6 +190,53 @@ def _fmt_codes(fmt):
     return tuple(_FMT_NAMES[f] if isinstance(f, str) else int(f) for f in (image, flow))
 
 
+# the per-object annotation table (ofdg_object_row / ofdg_object_table, include/ofdg.h)
+MAX_OBJECT_ROWS = 65  # OFDG_MAX_OBJECT_ROWS: background + 64 foreground objects
+BACKGROUND_ID = 1     # OFDG_BACKGROUND_ID
+
+
+class ObjectRow(C.Structure):
+    """ofdg_object_row: one object of one sample (96 bytes, no padding)."""
+    _fields_ = [("obj_id", C.c_int32), ("obj_type", C.c_int32), ("area0", C.c_int32), ("area1", C.c_int32),
+                ("box0", C.c_int32 * 4), ("box1", C.c_int32 * 4), ("motion", C.c_double * 6)]
+
+
+def _object_row_dtype():
+    import numpy as np
+    return np.dtype([("obj_id", "<i4"), ("obj_type", "<i4"), ("area0", "<i4"), ("area1", "<i4"), ("box0", "<i4", (4,)),
+                     ("box1", "<i4", (4,)), ("motion", "<f8", (6,))])
+
+
+def __getattr__(name):
+    # OBJECT_ROW_DTYPE: the numpy structured dtype of ofdg_object_row (built on first use: numpy is imported lazily here)
+    if name == "OBJECT_ROW_DTYPE":
+        globals()[name] = _object_row_dtype()
+        return globals()[name]
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def object_table_format(label0, label1, rows, counts, height, width, n=None):
+    """(n, rows_per_sample) of the arguments of Generator.object_table: rows uint8 [n, rows_per_sample, 96] with
+    rows_per_sample >= 1, counts int32 [n], label0 / label1 None or uint8 [n,H,W]; n (the batch the table is of), when given,
+    must be theirs.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors)."""
+    def name(t):
+        return str(t.dtype).replace("torch.", "")
+
+    if rows is None or counts is None:
+        raise ValueError("object_table needs rows and counts (alloc_object_table)")
+    if name(rows) != "uint8" or len(rows.shape) != 3 or rows.shape[2] != C.sizeof(ObjectRow) or rows.shape[1] < 1 or rows.shape[0] < 1:
+        raise ValueError("rows must be uint8 [n, rows_per_sample >= 1, %d], got %s %s" % (C.sizeof(ObjectRow), name(rows), tuple(rows.shape)))
+    nn, per = int(rows.shape[0]), int(rows.shape[1])
+    if n is not None and nn != n:
+        raise ValueError("rows holds %d samples, the batch the table is of has %d" % (nn, n))
+    if name(counts) != "int32" or tuple(counts.shape) != (nn,):
+        raise ValueError("counts must be int32 %s, got %s %s" % ((nn,), name(counts), tuple(counts.shape)))
+    for key, t in (("label0", label0), ("label1", label1)):
+        if t is not None and (name(t) != "uint8" or tuple(t.shape) != (nn, height, width)):
+            raise ValueError("%s must be None or uint8 %s, got %s %s" % (key, (nn, height, width), name(t), tuple(t.shape)))
+    return nn, per
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -258,6 +306,8 @@ def lib():
         L.ofdg_render_ex_fmt.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
         L.ofdg_forward_ex_fmt.argtypes = [vp, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
         L.ofdg_forward_counter_ex_fmt.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
+        L.ofdg_object_table.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        L.ofdg_host_object_table.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -332,6 +382,8 @@ class Generator:
         if rc != OK:
             raise OfdgError(rc, lib().ofdg_last_error(None).decode())
         self.h = h
+        self._last_n = None   # samples of the batch the last render / forward call enqueued (object_table checks its buffers)
+        self._slot_n = {}
 
     def _check(self, rc):
         if rc != OK:
@@ -499,6 +551,7 @@ class Generator:
         else:
             rc = L.ofdg_render(self.h, t, n_tasks, b, n_bps, *out, C.c_void_p(stream))
         self._check(rc)
+        self._last_n = n_tasks
 
     def render_resident(self, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_resident(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
@@ -506,9 +559,11 @@ class Generator:
     def upload_slot(self, slot, tasks, n_tasks, bps, n_bps, stream=0):
         self._check(lib().ofdg_upload_slot(self.h, slot, C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps,
                                            C.c_void_p(stream)))
+        self._slot_n[slot] = n_tasks
 
     def render_slot(self, slot, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_slot(self.h, slot, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
+        self._last_n = self._slot_n.get(slot)
 
     def forward(self, img0, img1, flow, stream=0, extras=None, fmt=None):
         of, ex = self._formats(img0, img1, flow, self.params.batch_size, fmt, extras)
@@ -522,6 +577,7 @@ class Generator:
         else:
             rc = L.ofdg_forward(self.h, *out, C.c_void_p(stream))
         self._check(rc)
+        self._last_n = self.params.batch_size
 
     def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None, fmt=None):
         of, ex = self._formats(img0, img1, flow, n, fmt, extras)
@@ -536,6 +592,18 @@ class Generator:
         else:
             rc = L.ofdg_forward_counter(self.h, first_index, n, *out, C.c_void_p(stream))
         self._check(rc)
+        self._last_n = n
+
+    def object_table(self, label0, label1, rows, counts, stream=0):
+        """The per-object annotation table (ofdg_object_table, include/ofdg.h) of the batch the last render / forward call
+        enqueued, into rows / counts (alloc_object_table): per sample the objects' ids, types, visible areas and boxes in both
+        frames and motions.  label0 / label1: the label planes THAT call wrote (tensors uint8 [n,H,W]) or None (that frame's
+        areas stay 0).  stream: the stream the labels were written on - the stream of that call, or STREAM_OWN for the
+        internal stream it worked on.  Asynchronous; read the table with object_table_numpy after synchronising."""
+        n, per = object_table_format(label0, label1, rows, counts, self.params.height, self.params.width, self._last_n)
+        self._check(lib().ofdg_object_table(self.h, _dptr(label0) if label0 is not None else None,
+                                            _dptr(label1) if label1 is not None else None, _dptr(rows), per, _dptr(counts),
+                                            C.c_void_p(stream)))
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -838,6 +906,49 @@ def alloc_extras(n, height, width, names=("flow1", "occ0", "occ1", "label0", "la
     return out
 
 
+def alloc_object_table(n, rows=MAX_OBJECT_ROWS, device="cuda"):
+    """Buffers of the per-object annotation table of n samples: (rows uint8 [n, rows, 96], counts int32 [n]); a row is one
+    ofdg_object_row (OBJECT_ROW_DTYPE, object_table_numpy)."""
+    import torch
+    if n < 1 or rows < 1:
+        raise ValueError("alloc_object_table needs n >= 1 and rows >= 1, got %d and %d" % (n, rows))
+    return (torch.zeros((n, rows, C.sizeof(ObjectRow)), dtype=torch.uint8, device=device),
+            torch.zeros((n,), dtype=torch.int32, device=device))
+
+
+def object_table_numpy(rows, counts):
+    """The table as a list of numpy structured arrays (OBJECT_ROW_DTYPE), one per sample, cut to the sample's count (or to
+    the rows the table holds, if fewer).  rows / counts: the tensors (or arrays) Generator.object_table filled; synchronise
+    first."""
+    import numpy as np
+    r = np.ascontiguousarray(rows.cpu().numpy() if hasattr(rows, "cpu") else rows, np.uint8)
+    c = np.asarray(counts.cpu().numpy() if hasattr(counts, "cpu") else counts)
+    t = r.view(_object_row_dtype()).reshape(r.shape[0], r.shape[1])
+    return [t[i, :min(int(c[i]), r.shape[1])].copy() for i in range(r.shape[0])]
+
+
+def host_object_table(label0, label1, counts, rows_per_sample=MAX_OBJECT_ROWS, width=None, height=None):
+    """ofdg_host_object_table (no GPU): areas and boxes of host label planes uint8 [n,H,W] (either may be None) as a
+    structured array [n, rows_per_sample] of OBJECT_ROW_DTYPE; rows past counts[i] and every other field are zero.
+    width / height: only needed when both planes are None."""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, np.int32)
+    planes = [None if t is None else np.ascontiguousarray(t, np.uint8) for t in (label0, label1)]
+    shape = next((t.shape for t in planes if t is not None), None)
+    if shape is None:
+        if width is None or height is None:
+            raise ValueError("host_object_table without label planes needs width= and height=")
+        shape = (len(counts), height, width)
+    if len(shape) != 3 or shape[0] != len(counts) or any(t is not None and t.shape != shape for t in planes):
+        raise ValueError("label planes must be uint8 [n,H,W] with n = len(counts) = %d, got %s" % (len(counts), [None if t is None else t.shape for t in planes]))
+    out = np.zeros((shape[0], rows_per_sample), _object_row_dtype())
+    rc = lib().ofdg_host_object_table(*(None if t is None else t.ctypes.data_as(C.c_void_p) for t in planes), shape[0], shape[2], shape[1],
+                                      counts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), rows_per_sample)
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    return out
+
+
 class HostSampler:
     """The reference-stream blueprint sampler on its own (host only, no GPU needed)."""
 
@@ -964,11 +1075,16 @@ class FlowLoader:
     batch is (image0, image1, flow, {name: tensor}).
     image_dtype=torch.uint8 / flow_dtype=torch.float16: the ring's buffers are allocated and rendered in the compact formats.
     With extras= that takes extras_compact=True: flow1 then has flow_dtype and the occlusion maps are uint8 (1 / 0); without
-    it the extras are float32 and a compact format with them raises."""
+    it the extras are float32 and a compact format with them raises.
+    objects=True (needs label0 and label1 among extras=): the per-object annotation table of every batch (Generator.object_table,
+    enqueued right behind the batch on the same internal stream) in buffers cycled with the ring; the batch's extras dict then
+    also holds "objects" (uint8 [n, 65, 96], see object_table_numpy) and "object_counts" (int32 [n])."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
-                 extras_compact=False, **kw):
+                 extras_compact=False, objects=False, **kw):
         import torch
+        if objects and (extras is None or "label0" not in extras or "label1" not in extras):
+            raise ValueError("objects=True needs the label planes it reduces: extras= must contain \"label0\" and \"label1\"")
         compact = image_dtype not in (None, torch.float32) or flow_dtype not in (None, torch.float32)
         if compact and extras is not None and not extras_compact:
             raise ValueError("the compact output formats combine with extras= only with extras_compact=True (flow1 in flow_dtype, "
@@ -990,6 +1106,7 @@ class FlowLoader:
         xfmt = dict(flow_dtype=flow_dtype, occ_dtype=torch.uint8) if extras_compact else {}
         self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras, **xfmt) if self.extras is not None else None
                       for _ in range(self.prefetch)]
+        self.obufs = [alloc_object_table(p.batch_size) if objects else None for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -1004,6 +1121,8 @@ class FlowLoader:
         if self.released[j] is not None:
             chain.wait_event(self.released[j])
         self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
+        if self.obufs[j] is not None:
+            self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         self.ready[j].record(chain)
 
     @property
@@ -1028,6 +1147,8 @@ class FlowLoader:
             self._enqueue(f)
             self.head += 1
         self.k += 1
+        if self.obufs[j] is not None:
+            return self.bufs[j] + (dict(self.xbufs[j], objects=self.obufs[j][0], object_counts=self.obufs[j][1]),)
         if self.extras is not None:
             return self.bufs[j] + (self.xbufs[j],)
         return self.bufs[j]

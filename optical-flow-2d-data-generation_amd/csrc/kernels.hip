@@ -1895,6 +1895,106 @@ __global__ __launch_bounds__(256) void occlusion_fmt_kernel(const uint32_t* __re
   if (occ1) store(occ1, occlusion_fmt_quad(tgt1 + pix, label1 + pix, label0 + sp, (uint32_t)plane));
 }
 
+// --------------------------------------------------------------------------
+// Per-object annotation table (ofdg_object_table): what the label planes and the batch's records say about each object.
+// Two launches behind the call that wrote the labels.
+// --------------------------------------------------------------------------
+// The header: one thread per (sample, row).  Row k < count takes id, type and motion from objects[first_object + k] (row 0: the
+// background), area 0 and the empty box {W, H, -1, -1} of both frames; rows past the count are zero bytes; row 0's thread writes
+// the count.  Every byte of the table is written here, so the reduction behind it only ever adds to it.
+__global__ __launch_bounds__(256) void object_table_header_kernel(const DevSample* __restrict__ samples, const DevObject* __restrict__ objects,
+                                                                  const DevShape* __restrict__ shapes, int n, int rows_per_sample, int W,
+                                                                  int H, DevObjectRow* __restrict__ rows, int32_t* __restrict__ counts) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)n * rows_per_sample) return;
+  const int s = (int)(t / rows_per_sample), k = (int)(t - (long long)s * rows_per_sample);
+  const int count = samples[s].n_objects;  // (the background counts)
+  if (k == 0) counts[s] = count;
+  DevObjectRow r = DevObjectRow();
+  if (k < count) {
+    const DevObject& o = objects[samples[s].first_object + k];
+    r.obj_id = o.id;
+    // ObjType_t of the blueprint: a composite's record says so itself, a simple object's outline carries the type
+    r.obj_type = o.kind == 2 ? 3 : (o.kind == 1 && o.n_shapes > 0) ? shapes[o.first_shape].type : 0;
+#pragma unroll
+    for (int f = 0; f < 2; ++f) { r.box[f][0] = W; r.box[f][1] = H; r.box[f][2] = -1; r.box[f][3] = -1; }
+    r.motion[0] = o.motion.sx; r.motion[1] = o.motion.shy; r.motion[2] = o.motion.shx;
+    r.motion[3] = o.motion.sy; r.motion[4] = o.motion.tx; r.motion[5] = o.motion.ty;
+  }
+  rows[t] = r;
+}
+
+// The reduction: one workgroup per (band of kTabBand rows, frame, sample), a wave per row, a lane per 4 adjacent label bytes
+// (one 4-byte load; the planes are dense uint8 and W is a multiple of 8).  Labels are spatially coherent, so a wave first
+// reduces per DISTINCT label of its row segment: it takes the first unretired byte's label, one ballot per byte position says
+// which lanes hold it there, and count / min x / max x fall out of the four masks in scalar code (a lane's x grows with the
+// lane: the first and last set bit of a mask are its extremes) - no cross-lane data movement; y is the wave's row.  Lane 0
+// adds the result to the workgroup's table in LDS (65 rows x {count, min x, min y, max x, max y}); at the end the non-empty
+// rows below min(count, rows_per_sample) go to the global table with one int32 atomic per field.  A byte that is no valid
+// label of the sample (the planes are the caller's word) is counted nowhere.
+constexpr int kTabBand = 16;   // rows of a frame per workgroup
+constexpr int kTabWaves = 4;
+__global__ __launch_bounds__(64 * kTabWaves) void object_table_reduce_kernel(const DevSample* __restrict__ samples,
+                                                                             const uint8_t* __restrict__ label0,
+                                                                             const uint8_t* __restrict__ label1, int W, int H,
+                                                                             int rows_per_sample, DevObjectRow* __restrict__ rows) {
+  __shared__ int tab[kObjectRows * 5];
+  const int band = (int)blockIdx.x, f = (int)blockIdx.y, s = (int)blockIdx.z;
+  const uint8_t* const labels = f ? label1 : label0;
+  if (!labels) return;  // (that frame was not asked for: its areas stay 0, its boxes empty)
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < kObjectRows * 5; i += 64 * kTabWaves) {
+    const int j = i % 5;
+    tab[i] = j == 0 ? 0 : (j < 3 ? 0x7FFFFFFF : -1);
+  }
+  __syncthreads();
+  const uint8_t* const plane = labels + (size_t)s * W * H;
+  const int y_end = min(H, (band + 1) * kTabBand);
+  for (int y = band * kTabBand + wave; y < y_end; y += kTabWaves) {
+    for (int xc = 0; xc < W; xc += 256) {
+      const int x0 = xc + 4 * lane;
+      const bool act = x0 < W;  // (W % 4 == 0: the whole quad is inside)
+      const uint32_t w = act ? *reinterpret_cast<const uint32_t*>(plane + (size_t)y * W + x0) : 0u;
+      uint32_t rem = act ? 0xFu : 0u;  // bytes of this lane no label has taken yet
+      for (;;) {
+        const unsigned long long live = __ballot(rem != 0u);
+        if (!live) break;
+        const int leader = __ffsll(live) - 1;
+        const uint32_t mine = rem ? (w >> (8 * (__ffs((int)rem) - 1))) & 255u : 0u;
+        const uint32_t lab = (uint32_t)__shfl((int)mine, leader, 64);
+        int cnt = 0, lo = 0x7FFFFFFF, hi = -1;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const bool hit = act && ((w >> (8 * p)) & 255u) == lab;
+          const unsigned long long m = __ballot(hit);
+          if (hit) rem &= ~(1u << p);
+          if (m) {
+            cnt += __popcll(m);
+            lo = min(lo, xc + 4 * (__ffsll(m) - 1) + p);
+            hi = max(hi, xc + 4 * (63 - __clzll((long long)m)) + p);
+          }
+        }
+        if (lane == 0 && lab < (uint32_t)kObjectRows) {
+          int* const e = tab + lab * 5;
+          atomicAdd(e, cnt);
+          atomicMin(e + 1, lo); atomicMin(e + 2, y);
+          atomicMax(e + 3, hi); atomicMax(e + 4, y);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int limit = min(min(samples[s].n_objects, rows_per_sample), kObjectRows);
+  DevObjectRow* const out = rows + (size_t)s * rows_per_sample;
+  for (int i = tid; i < limit * 5; i += 64 * kTabWaves) {
+    const int k = i / 5, j = i - 5 * k;
+    if (tab[k * 5] == 0) continue;
+    if (j == 0) atomicAdd(&out[k].area[f], tab[i]);
+    else if (j < 3) atomicMin(&out[k].box[f][j - 1], tab[i]);
+    else atomicMax(&out[k].box[f][j - 1], tab[i]);
+  }
+}
+
 // Mode 9: the same body with the deformation paths compiled in (masks, textures and flow of deformed objects and backgrounds
 // re-sampled through their warp crops).
 __global__ __launch_bounds__(64) void compose_deform_kernel(

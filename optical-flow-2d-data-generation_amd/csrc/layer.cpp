@@ -4,7 +4,9 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cctype>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -677,6 +679,42 @@ int ofdg_host_bg_prep(int pool_w, int pool_h, int width, int height, float angle
   const ofdg::DevBgPrep p = ofdg::make_bg_prep(pool_w, pool_h, width, height, angle, zoom, shift_x, shift_y, 0);
   f[0] = p.ca; f[1] = p.sa; f[2] = p.w2; f[3] = p.h2; f[4] = p.rw2; f[5] = p.rh2; f[6] = p.fx; f[7] = p.fy;
   i[0] = p.x0; i[1] = p.y0; i[2] = p.cw; i[3] = p.ch; i[4] = p.shx; i[5] = p.shy;
+  return OFDG_OK;
+}
+
+// ofdg_object_table's reduction on host label planes (no GPU): areas and boxes of the visible pixels of each label.
+static_assert(sizeof(ofdg_object_row) == 96 && offsetof(ofdg_object_row, box0) == 16 && offsetof(ofdg_object_row, motion) == 48,
+              "ofdg_object_row: 96 bytes, no padding");
+int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, int width, int height, const int32_t* counts,
+                           ofdg_object_row* rows, int rows_per_sample) {
+  if (!counts || !rows || n < 1 || width < 1 || height < 1 || rows_per_sample < 1) {
+    g_host_error = "ofdg_host_object_table: counts / rows NULL, or n, width, height or rows_per_sample below 1";
+    return OFDG_EINVAL;
+  }
+  const size_t plane = (size_t)width * height;
+  for (int s = 0; s < n; ++s) {
+    ofdg_object_row* const r = rows + (size_t)s * rows_per_sample;
+    const int limit = std::min(std::max(counts[s], 0), rows_per_sample);
+    for (int f = 0; f < 2; ++f) {
+      const uint8_t* const lab = f ? label1 : label0;
+      for (int k = 0; k < limit; ++k) {
+        int32_t* const box = f ? r[k].box1 : r[k].box0;
+        (f ? r[k].area1 : r[k].area0) = 0;
+        box[0] = width; box[1] = height; box[2] = -1; box[3] = -1;
+      }
+      if (!lab) continue;
+      const uint8_t* px = lab + (size_t)s * plane;
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x, ++px) {
+          const int k = *px;
+          if (k >= limit) continue;  // (no label of this sample, or a row the table does not hold)
+          int32_t* const box = f ? r[k].box1 : r[k].box0;
+          ++(f ? r[k].area1 : r[k].area0);
+          box[0] = std::min(box[0], x); box[1] = std::min(box[1], y);
+          box[2] = std::max(box[2], x); box[3] = std::max(box[3], y);
+        }
+    }
+  }
   return OFDG_OK;
 }
 

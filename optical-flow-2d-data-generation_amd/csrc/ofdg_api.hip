@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -167,6 +168,8 @@ struct ofdg_ctx {
   unsigned next_chain = 0;
   int last_chain = 0;     // the chain and the slot the last launch used (ofdg_render_resident, debug read-back)
   Slot* last_slot = nullptr;
+  Chain* last_ch = nullptr;            // the chain that composed the batch in last_slot ...
+  hipStream_t last_stream = nullptr;   // ... and the internal stream that call worked on (ofdg_object_table: OFDG_STREAM_OWN)
   hipStream_t last_user_st = nullptr;  // serial mode: the caller's stream of the last launch
   bool have_last_user_st = false;
   // device counter sampler (OFDG_SAMPLER_COUNTER)
@@ -1091,6 +1094,8 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void*
   const uint32_t* fgpool = c->pool_fg ? c->pool_fg : c->pool;
   if (c->prm.background_prep && !bgpool) { c->err = "background_prep: the slot has no prepared backgrounds"; return OFDG_EINVAL; }
   c->last_slot = &sl;
+  c->last_ch = &ch;
+  c->last_stream = ch.prep.stream;
   c->last_ticket = ch.prep.ticket;
   ch.prep.valid = false;  // (consumed from here on; an argument error above leaves it to discard_prepared, which resets the work list)
   // Where compose runs: on the chain's stream, right behind the preparation - or, if the caller passed another stream,
@@ -1513,6 +1518,56 @@ int ofdg_render_resident(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flo
   for (int k = 0; k < c->n_chains; ++k)
     if (&c->chains[k].slot == c->last_slot && !c->last_slot->compose_pending) HIP_OK(c, hipStreamSynchronize(c->chains[k].stream));
   return launch_resident(c, take_chain(c), *c->last_slot, d_img0, d_img1, d_flow, (hipStream_t)stream);
+}
+
+// The per-object annotation table of the batch the last render / forward call composed (c->last_slot): two small kernels on
+// `stream` - the stream the labels were written on - that read the slot's records and the caller's label planes.  Nothing but
+// argument checks happens on the host.
+static_assert(sizeof(ofdg_object_row) == sizeof(DevObjectRow) && sizeof(ofdg_object_row) == 96 && offsetof(ofdg_object_row, area0) == 8 &&
+              offsetof(ofdg_object_row, area0) == offsetof(DevObjectRow, area) && offsetof(ofdg_object_row, box0) == 16 &&
+              offsetof(ofdg_object_row, box0) == offsetof(DevObjectRow, box) && offsetof(ofdg_object_row, box1) == 32 &&
+              offsetof(ofdg_object_row, motion) == 48 && offsetof(ofdg_object_row, motion) == offsetof(DevObjectRow, motion),
+              "ofdg_object_row: 96 bytes without padding, the layout the kernels write");
+static_assert(OFDG_MAX_OBJECT_ROWS == kObjectRows, "background + kMaxFgObjects");
+int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_label1, ofdg_object_row* d_rows, int rows_per_sample,
+                      int32_t* d_counts, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  auto fail = [&](const std::string& why) { c->err = "ofdg_object_table: " + why; return OFDG_EINVAL; };
+  if (c->prm.mode == 9) return fail("the table restates the label planes, which are defined for the rigid modes only (mode 9)");
+  if (!d_rows) return fail("d_rows is NULL");
+  if (!d_counts) return fail("d_counts is NULL");
+  if (rows_per_sample < 1) return fail("rows_per_sample = " + std::to_string(rows_per_sample) + " (valid: >= 1)");
+  if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_counts & 3) || ((uintptr_t)d_label0 & 3) || ((uintptr_t)d_label1 & 3))
+    return fail("d_rows must be 8-byte aligned, d_counts and the label planes 4-byte aligned");
+  if (!c->last_slot || !c->last_ch || c->last_slot->res_samples <= 0)
+    return fail("no render / forward call has been made yet on this context");
+  ofdg_ctx::Slot& sl = *c->last_slot;
+  ofdg_ctx::Chain& ch = *c->last_ch;
+  const hipStream_t S = c->last_stream;  // the internal stream that call worked on
+  const hipStream_t st = stream == OFDG_STREAM_OWN ? S : (hipStream_t)stream;
+  const int W = c->prm.width, H = c->prm.height, n = sl.res_samples;
+  // The slot's records must outlive the kernels.  On the chain's own stream the order of the stream sees to that (a private
+  // slot is rewritten there only); on a caller's stream - or for a caller's slot, which any stream may rewrite - the last
+  // kernel carries the chain's completion event, as a compose on a caller's stream does (launch_compose): a later call
+  // that reuses the slot or the chain's workspaces waits for it.
+  const bool tracked = st != S || &sl != &ch.slot;
+  const hipEvent_t done = tracked ? ch.ev_done : nullptr;
+  const bool reduce = d_label0 || d_label1;
+  DevObjectRow* const rows = reinterpret_cast<DevObjectRow*>(d_rows);
+  const long long cells = (long long)n * rows_per_sample;
+  hipExtLaunchKernelGGL(object_table_header_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, nullptr, reduce ? nullptr : done, 0,
+                        sl.d_samples.p, sl.d_objects.p, sl.d_shapes.p, n, rows_per_sample, W, H, rows, d_counts);
+  HIP_OK(c, hipGetLastError());
+  if (reduce) {
+    hipExtLaunchKernelGGL(object_table_reduce_kernel, dim3((unsigned)((H + kTabBand - 1) / kTabBand), 2, (unsigned)n), dim3(64 * kTabWaves), 0,
+                          st, nullptr, done, 0, sl.d_samples.p, d_label0, d_label1, W, H, rows_per_sample, rows);
+    HIP_OK(c, hipGetLastError());
+  }
+  if (tracked) {
+    sl.compose_pending = true; sl.compose_stream = st; sl.compose_event = done;
+    ch.done_pending = true; ch.done_stream = st;
+  }
+  return OFDG_OK;
 }
 
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample

@@ -93,6 +93,17 @@ struct DevObjectHdr {
   int32_t kind, id, deform;
 };
 
+// One row of the per-object annotation table (ofdg_object_row of include/ofdg.h, field for field): the kernels update the
+// int32 fields of a frame with atomics, so area and box are arrays over the frame here.
+struct DevObjectRow {
+  int32_t obj_id, obj_type;
+  int32_t area[2];    // [frame]
+  int32_t box[2][4];  // [frame]{x0, y0, x1, y1}
+  double motion[6];
+};
+static_assert(sizeof(DevObjectRow) == 96, "ofdg_object_row is 96 bytes without padding");
+constexpr int kObjectRows = kMaxFgObjects + 1;  // OFDG_MAX_OBJECT_ROWS: background + foreground objects
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
