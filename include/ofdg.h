@@ -379,6 +379,63 @@ int ofdg_object_table(ofdg_ctx* ctx, const uint8_t* d_label0, const uint8_t* d_l
 int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, int width, int height,
                            const int32_t* counts, ofdg_object_row* rows, int rows_per_sample);
 
+/*
+ * Per-sample flow statistics: what the flow of a batch looks like, without copying the planes to the host - the histogram
+ * of the displacement |flow| in bins of bin_px pixels (the sampler's tables were tuned against such a histogram), how many
+ * pixels are unusable or occluded, the Q8 sums behind the mean u, v and |flow|, and the largest |flow|^2 with the pixel it
+ * occurs at (what decides whether OFDG_FMT_F16 is safe: 0.125 px spacing from 128 px, infinite beyond 65504).  The reference
+ * drops a "bad" task silently (DG:1285-1292); n_bad is the per-sample count a training loop can screen with.
+ *
+ * d_flow: any [n,2,H,W] flow tensor of the context's frame size - the forward flow or flow1 of ofdg_extras - float32
+ * (flow_fmt = OFDG_FMT_F32, 16-byte aligned) or binary16 (OFDG_FMT_F16, 8-byte aligned).  d_occ: NULL, or the [n,1,H,W] map
+ * that goes with it, float32 (occ_fmt = OFDG_FMT_F32, 16-byte aligned) or uint8 (OFDG_FMT_U8, 4-byte aligned); occ_fmt is not
+ * looked at when d_occ is NULL.  All 13 modes, both samplers.  The result is a pure function of the buffers: the context
+ * supplies W, H, the device and the stream only.
+ *
+ * Definition - integers and an order-independent maximum only, so every field is exact and the same on every run.  For pixel
+ * (x, y) of sample i, u and v widened to float32 (exact for a binary16):
+ *   1. d_occ given and occ != 0: n_occluded += 1; with OFDG_STATS_VISIBLE_ONLY the pixel contributes nothing else.
+ *   2. not (fabsf(u) < 1048576.0f && fabsf(v) < 1048576.0f): n_bad += 1 and nothing else (NaN, +-inf, an overflowed half).
+ *   3. otherwise n_counted += 1, and with m2 = fl32(fl32(u*u) + fl32(v*v)) (float32, no contraction):
+ *        hist[b] += 1, b = the number of k in 1..63 with edge2[k] <= m2, edge2[k] = fl32(fl32((float)k * bin_px)^2)
+ *                      (bins bin_px wide in pixels, a value on an edge belongs to the bin above, the last bin is open);
+ *        sum_u_q8 += (int64)rintf(u * 256.0f), sum_v_q8 likewise, sum_mag_q8 += (int64)rintf(sqrtf(m2) * 256.0f)
+ *                      (sqrtf correctly rounded, rintf to nearest even);
+ *        max_key = max(max_key, ((uint64)bits(m2) << 32) | (0xFFFFFFFFu - idx)), idx = y*W + x, or (i*H + y)*W + x with
+ *                      OFDG_STATS_ONE_ROW.
+ * max_key >> 32 is the bit pattern of the largest |flow|^2, 0xFFFFFFFF - (uint32)max_key its first pixel in row-major order;
+ * max_key == 0: no pixel was counted.  hist sums to n_counted; n_counted + n_bad (+ n_occluded with VISIBLE_ONLY) = H*W.
+ *
+ * Row i of d_rows is sample i's; with OFDG_STATS_ONE_ROW all n samples reduce into d_rows[0].  Without
+ * OFDG_STATS_ACCUMULATE the call first writes every byte of its rows as zero on `stream`, then reduces; with it the rows are
+ * added to (max for the key) - an all-zero row is the identity, so a caller zeroes rows once and keeps a running histogram
+ * over an epoch with no host work.  d_rows is 8-byte aligned.
+ *
+ * Asynchronous on `stream`, the stream the flow was written on; OFDG_STREAM_OWN: the internal stream the last render /
+ * forward call worked on, as in ofdg_object_table.  One kernel (behind the clearing of the rows), integer atomics only.
+ *
+ * OFDG_EINVAL, nothing enqueued, the rows untouched, the field named in ofdg_last_error: d_flow or d_rows NULL, flow_fmt /
+ * occ_fmt not one of the codes above, n_samples < 1, bin_px NaN or outside [2^-10, 2^14], unknown bits in flags,
+ * OFDG_STATS_VISIBLE_ONLY without d_occ, OFDG_STATS_ONE_ROW with n*H*W >= 2^32, a misaligned pointer, OFDG_STREAM_OWN before
+ * any render / forward call on the context.
+ */
+#define OFDG_FLOW_HIST_BINS 64
+#define OFDG_STATS_ACCUMULATE   1  /* add to the rows instead of overwriting them */
+#define OFDG_STATS_VISIBLE_ONLY 2  /* pixels with occ != 0 count in n_occluded only */
+#define OFDG_STATS_ONE_ROW      4  /* all n samples reduce into d_rows[0] */
+typedef struct ofdg_flow_stats_row {   /* 304 bytes, no padding, 8-byte aligned */
+  uint32_t hist[OFDG_FLOW_HIST_BINS];
+  uint32_t n_counted, n_bad, n_occluded, reserved;
+  int64_t  sum_u_q8, sum_v_q8, sum_mag_q8;
+  uint64_t max_key;
+} ofdg_flow_stats_row;
+int ofdg_flow_stats(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
+                    int n_samples, float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream);
+/* The same on HOST buffers (no GPU): flow [n,2,height,width], occ NULL or [n,1,height,width], any width / height >= 1, no
+ * alignment asked of the planes.  Errors as above (and for width / height < 1) through ofdg_host_last_error. */
+int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
+                         float bin_px, int flags, ofdg_flow_stats_row* rows);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -103,6 +103,7 @@ EXPORTS = [
     "ofdg_render_fmt", "ofdg_forward_fmt", "ofdg_forward_counter_fmt",
     "ofdg_render_ex_fmt", "ofdg_forward_ex_fmt", "ofdg_forward_counter_ex_fmt",
     "ofdg_object_table", "ofdg_host_object_table",
+    "ofdg_flow_stats", "ofdg_host_flow_stats",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -207,10 +208,32 @@ def _object_row_dtype():
                      ("box1", "<i4", (4,)), ("motion", "<f8", (6,))])
 
 
+# the per-sample flow statistics (ofdg_flow_stats_row / ofdg_flow_stats, include/ofdg.h)
+FLOW_HIST_BINS = 64  # OFDG_FLOW_HIST_BINS
+STATS_ACCUMULATE, STATS_VISIBLE_ONLY, STATS_ONE_ROW = 1, 2, 4
+
+
+class FlowStatsRow(C.Structure):
+    """ofdg_flow_stats_row: the statistics of one sample (304 bytes, no padding)."""
+    _fields_ = [("hist", C.c_uint32 * FLOW_HIST_BINS), ("n_counted", C.c_uint32), ("n_bad", C.c_uint32), ("n_occluded", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum_u_q8", C.c_int64), ("sum_v_q8", C.c_int64), ("sum_mag_q8", C.c_int64),
+                ("max_key", C.c_uint64)]
+
+
+def _flow_stats_dtype():
+    import numpy as np
+    return np.dtype([("hist", "<u4", (FLOW_HIST_BINS,)), ("n_counted", "<u4"), ("n_bad", "<u4"), ("n_occluded", "<u4"), ("reserved", "<u4"),
+                     ("sum_u_q8", "<i8"), ("sum_v_q8", "<i8"), ("sum_mag_q8", "<i8"), ("max_key", "<u8")])
+
+
 def __getattr__(name):
-    # OBJECT_ROW_DTYPE: the numpy structured dtype of ofdg_object_row (built on first use: numpy is imported lazily here)
+    # OBJECT_ROW_DTYPE / FLOW_STATS_DTYPE: the numpy structured dtypes of ofdg_object_row / ofdg_flow_stats_row (built on first
+    # use: numpy is imported lazily here)
     if name == "OBJECT_ROW_DTYPE":
         globals()[name] = _object_row_dtype()
+        return globals()[name]
+    if name == "FLOW_STATS_DTYPE":
+        globals()[name] = _flow_stats_dtype()
         return globals()[name]
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
@@ -235,6 +258,35 @@ def object_table_format(label0, label1, rows, counts, height, width, n=None):
         if t is not None and (name(t) != "uint8" or tuple(t.shape) != (nn, height, width)):
             raise ValueError("%s must be None or uint8 %s, got %s %s" % (key, (nn, height, width), name(t), tuple(t.shape)))
     return nn, per
+
+
+def flow_stats_format(flow, occ, rows, height, width, one_row=False):
+    """(n, flow code, occ code) of the arguments of Generator.flow_stats / host_flow_stats: flow float32 or float16 [n,2,H,W],
+    occ None or float32 / uint8 [n,1,H,W], rows uint8 [n, 304] ([1, 304] with one_row).  Raises ValueError for anything else.
+    Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    def name(t):
+        return str(t.dtype).replace("torch.", "")
+
+    if flow is None or rows is None:
+        raise ValueError("flow_stats needs flow and rows (alloc_flow_stats)")
+    codes = {"float32": FMT_F32, "float16": FMT_F16}
+    if name(flow) not in codes or len(flow.shape) != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (2, height, width):
+        raise ValueError("flow must be float32 or float16 [n,2,%d,%d], got %s %s" % (height, width, name(flow), tuple(flow.shape)))
+    n = int(flow.shape[0])
+    occ_code = FMT_F32
+    if occ is not None:
+        occ_codes = {"float32": FMT_F32, "uint8": FMT_U8}
+        if name(occ) not in occ_codes or tuple(occ.shape) != (n, 1, height, width):
+            raise ValueError("occ must be None or float32 / uint8 %s, got %s %s" % ((n, 1, height, width), name(occ), tuple(occ.shape)))
+        occ_code = occ_codes[name(occ)]
+    want = (1 if one_row else n, C.sizeof(FlowStatsRow))
+    if name(rows) != "uint8" or tuple(rows.shape) != want:
+        raise ValueError("rows must be uint8 %s, got %s %s" % (want, name(rows), tuple(rows.shape)))
+    return n, codes[name(flow)], occ_code
+
+
+def _stats_flags(accumulate, visible_only, one_row):
+    return (STATS_ACCUMULATE if accumulate else 0) | (STATS_VISIBLE_ONLY if visible_only else 0) | (STATS_ONE_ROW if one_row else 0)
 
 
 def build(verbose=False):
@@ -308,6 +360,8 @@ def lib():
         L.ofdg_forward_counter_ex_fmt.argtypes = [vp, C.c_longlong, i32, vp, vp, vp, C.POINTER(ExtrasFmt), C.POINTER(OutFormat), vp]
         L.ofdg_object_table.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         L.ofdg_host_object_table.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32]
+        L.ofdg_flow_stats.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, i32, vp, vp]
+        L.ofdg_host_flow_stats.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_float, i32, vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -604,6 +658,18 @@ class Generator:
         self._check(lib().ofdg_object_table(self.h, _dptr(label0) if label0 is not None else None,
                                             _dptr(label1) if label1 is not None else None, _dptr(rows), per, _dptr(counts),
                                             C.c_void_p(stream)))
+
+    def flow_stats(self, flow, rows, occ=None, bin_px=2.0, accumulate=False, visible_only=False, one_row=False, stream=0):
+        """Per-sample statistics of a flow tensor (ofdg_flow_stats, include/ofdg.h) into rows (alloc_flow_stats): the histogram
+        of |flow| in bins of bin_px pixels, counted / bad / occluded pixels, Q8 sums of u, v and |flow|, the largest |flow|^2
+        and where it is.  flow: float32 or float16 [n,2,H,W] (the forward flow or flow1), occ: None or the float32 / uint8
+        [n,1,H,W] map that goes with it; the formats come from the dtypes.  accumulate: add to the rows instead of overwriting
+        them; visible_only: occluded pixels count in n_occluded only; one_row: all samples reduce into rows[0].  stream: the
+        stream the flow was written on, or STREAM_OWN for the internal stream the last render / forward call worked on.
+        Asynchronous; read the rows with flow_stats_numpy after synchronising."""
+        n, fcode, ocode = flow_stats_format(flow, occ, rows, self.params.height, self.params.width, one_row)
+        self._check(lib().ofdg_flow_stats(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, float(bin_px),
+                                          _stats_flags(accumulate, visible_only, one_row), _dptr(rows), C.c_void_p(stream)))
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -949,6 +1015,62 @@ def host_object_table(label0, label1, counts, rows_per_sample=MAX_OBJECT_ROWS, w
     return out
 
 
+def alloc_flow_stats(n, device="cuda"):
+    """Zeroed rows of the flow statistics of n samples (or of n running histograms): uint8 [n, 304]; a row is one
+    ofdg_flow_stats_row (FLOW_STATS_DTYPE, flow_stats_numpy)."""
+    import torch
+    if n < 1:
+        raise ValueError("alloc_flow_stats needs n >= 1, got %d" % n)
+    return torch.zeros((n, C.sizeof(FlowStatsRow)), dtype=torch.uint8, device=device)
+
+
+def flow_stats_numpy(rows, width=None, height=None, one_row=False):
+    """The rows Generator.flow_stats filled (a tensor or an array; synchronise first) as a dict: "rows" the structured array
+    (FLOW_STATS_DTYPE, one element per row), "max_mag2" float32 - the largest |flow|^2 of each row, 0 where nothing was
+    counted - and "max_index" int64, the row-major index of its first pixel, -1 where nothing was counted.  With width= and
+    height= the index is taken apart too: "max_x", "max_y" and "max_sample" - the row's own number, or, for rows reduced with
+    one_row (whose index runs over the whole batch), the sample inside the batch."""
+    import numpy as np
+    r = np.ascontiguousarray(rows.cpu().numpy() if hasattr(rows, "cpu") else rows, np.uint8)
+    t = r.reshape(-1, C.sizeof(FlowStatsRow)).view(_flow_stats_dtype()).reshape(-1).copy()
+    key = t["max_key"]
+    some = key != 0
+    idx = np.where(some, 0xFFFFFFFF - (key & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)
+    out = {"rows": t, "max_mag2": (key >> np.uint64(32)).astype(np.uint32).view(np.float32), "max_index": idx}
+    if width is not None and height is not None:
+        plane = width * height
+        out["max_x"] = np.where(some, idx % width, -1)
+        out["max_y"] = np.where(some, idx % plane // width, -1)
+        out["max_sample"] = np.where(some, idx // plane if one_row else np.arange(len(t)), -1)
+    return out
+
+
+def host_flow_stats(flow, occ=None, bin_px=2.0, accumulate=False, visible_only=False, one_row=False, rows=None):
+    """ofdg_host_flow_stats (no GPU): the statistics of HOST arrays - flow float32 or float16 [n,2,H,W], occ None or float32 /
+    uint8 [n,1,H,W] - as a structured array of FLOW_STATS_DTYPE, one element per sample (one in all with one_row).  rows: the
+    array a former call returned, to add to with accumulate=True."""
+    import numpy as np
+    flow = np.ascontiguousarray(flow)
+    occ = None if occ is None else np.ascontiguousarray(occ)
+    if flow.ndim != 4:
+        raise ValueError("flow must be [n,2,H,W], got %s" % (flow.shape,))
+    height, width = flow.shape[2:]
+    m = 1 if one_row else flow.shape[0]
+    if rows is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs rows= to add to")
+        rows = np.zeros((m,), _flow_stats_dtype())
+    elif rows.dtype != _flow_stats_dtype() or rows.shape != (m,) or not rows.flags["C_CONTIGUOUS"]:
+        raise ValueError("rows must be a contiguous FLOW_STATS_DTYPE array of shape %s" % ((m,),))
+    n, fcode, ocode = flow_stats_format(flow, occ, rows.view(np.uint8).reshape(m, -1), height, width, one_row)
+    rc = lib().ofdg_host_flow_stats(flow.ctypes.data_as(C.c_void_p), fcode, None if occ is None else occ.ctypes.data_as(C.c_void_p), ocode,
+                                    n, width, height, float(bin_px), _stats_flags(accumulate, visible_only, one_row),
+                                    rows.ctypes.data_as(C.c_void_p))
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    return rows
+
+
 class HostSampler:
     """The reference-stream blueprint sampler on its own (host only, no GPU needed)."""
 
@@ -1078,10 +1200,13 @@ class FlowLoader:
     it the extras are float32 and a compact format with them raises.
     objects=True (needs label0 and label1 among extras=): the per-object annotation table of every batch (Generator.object_table,
     enqueued right behind the batch on the same internal stream) in buffers cycled with the ring; the batch's extras dict then
-    also holds "objects" (uint8 [n, 65, 96], see object_table_numpy) and "object_counts" (int32 [n])."""
+    also holds "objects" (uint8 [n, 65, 96], see object_table_numpy) and "object_counts" (int32 [n]).
+    stats=True: the flow statistics of every batch (Generator.flow_stats with bin_px=stats_bin_px, enqueued right behind the
+    batch on the same internal stream; with "occ0" among extras= the map is passed) in rows cycled with the ring; every batch
+    is then (image0, image1, flow, {...}) and the dict also holds "flow_stats" (uint8 [n, 304], see flow_stats_numpy)."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
-                 extras_compact=False, objects=False, **kw):
+                 extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, **kw):
         import torch
         if objects and (extras is None or "label0" not in extras or "label1" not in extras):
             raise ValueError("objects=True needs the label planes it reduces: extras= must contain \"label0\" and \"label1\"")
@@ -1107,6 +1232,8 @@ class FlowLoader:
         self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras, **xfmt) if self.extras is not None else None
                       for _ in range(self.prefetch)]
         self.obufs = [alloc_object_table(p.batch_size) if objects else None for _ in range(self.prefetch)]
+        self.sbufs = [alloc_flow_stats(p.batch_size) if stats else None for _ in range(self.prefetch)]
+        self.stats_bin_px = float(stats_bin_px)
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -1123,6 +1250,9 @@ class FlowLoader:
         self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
+        if self.sbufs[j] is not None:
+            occ = self.xbufs[j].get("occ0") if self.xbufs[j] is not None else None
+            self.gen.flow_stats(self.bufs[j][2], self.sbufs[j], occ=occ, bin_px=self.stats_bin_px, stream=s)
         self.ready[j].record(chain)
 
     @property
@@ -1147,8 +1277,13 @@ class FlowLoader:
             self._enqueue(f)
             self.head += 1
         self.k += 1
-        if self.obufs[j] is not None:
-            return self.bufs[j] + (dict(self.xbufs[j], objects=self.obufs[j][0], object_counts=self.obufs[j][1]),)
+        if self.obufs[j] is not None or self.sbufs[j] is not None:
+            more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
+            if self.obufs[j] is not None:
+                more.update(objects=self.obufs[j][0], object_counts=self.obufs[j][1])
+            if self.sbufs[j] is not None:
+                more["flow_stats"] = self.sbufs[j]
+            return self.bufs[j] + (more,)
         if self.extras is not None:
             return self.bufs[j] + (self.xbufs[j],)
         return self.bufs[j]

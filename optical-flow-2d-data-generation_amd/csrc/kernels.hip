@@ -3128,4 +3128,156 @@ __global__ void tables_kernel(uint8_t* add_tbl, uint8_t* sub_tbl, uint8_t* aa_tb
   if (i < 256) aa_tbl[i] = (uint8_t)aa_byte(i);
 }
 
+// --------------------------------------------------------------------------
+// Per-sample flow statistics (ofdg_flow_stats): displacement histogram, counts, Q8 sums and the largest |flow|^2 of a
+// [n,2,H,W] flow tensor, float32 or binary16, with an optional [n,1,H,W] occlusion map (float32 or uint8).  One launch
+// behind the call that wrote the planes; a pure function of the buffers.
+// --------------------------------------------------------------------------
+// Squared upper edge of bin k - 1 / lower edge of bin k: fl32(fl32(k * bin_px)^2).  Non-decreasing in k (rounding is monotone),
+// so "the number of k in 1..63 with edge2(k) <= m2" is the one b with edge2(b) <= m2 < edge2(b + 1).
+__device__ __forceinline__ float stats_edge2(int k, float bin_px) {
+  const float e = __fmul_rn((float)k, bin_px);
+  return __fmul_rn(e, e);
+}
+
+// One workgroup per (piece of kStatsQuads quads of a sample's plane, sample); a lane takes a quad - 4 adjacent pixels of each
+// plane in one 16-byte (float32), 8-byte (binary16) or 4-byte (uint8 map) load; H * W is a multiple of 16, so a plane is whole
+// quads and every plane of an aligned tensor is aligned.  The bin of a counted pixel starts from sqrt(m2) / bin_px and is
+// walked to the exact one with the edges recomputed in two multiplications - no table, no LDS read.  Histogram: one copy of
+// the 64 bins per wave in LDS.  Flow is spatially coherent, so per pixel position the wave first votes: the lanes whose bin is
+// the first live lane's are counted with one ballot and added once (kStatsPeel rounds), and only lanes still left add their
+// own 1 with an LDS atomic.  Counts, Q8 sums (int64 per lane: 16 values of up to 2^29) and the key go across the wave with
+// __shfl_xor, then through LDS; at the end the workgroup issues one global atomicAdd per non-empty bin and count, one
+// 64-bit atomicAdd per sum and one 64-bit atomicMax for the key.  Integer atomics only: no result depends on arrival order.
+// sqrtf is the correctly rounded root here (hipcc expands it so unless told otherwise); __fsqrt_rn of this toolchain is the
+// native 1-ulp approximation, which would make sum_mag_q8 differ from the host's.
+constexpr int kStatsThreads = 256;
+constexpr int kStatsQuads = 1024;  // 4 quads per lane
+constexpr int kStatsPeel = 2;
+template <bool kHalf, int kOcc>  // kOcc: 0 no map, 1 float32, 2 uint8
+__global__ __launch_bounds__(kStatsThreads) void flow_stats_kernel(const void* __restrict__ flow, const void* __restrict__ occ, int n,
+                                                                   uint32_t plane_quads, float bin_px, float inv_bin, int visible_only,
+                                                                   int one_row, DevFlowStatsRow* __restrict__ rows) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  __shared__ uint32_t s_hist[kStatsThreads / 64][kFlowHistBins];
+  __shared__ uint32_t s_cnt[3];
+  __shared__ unsigned long long s_sum[3];
+  __shared__ unsigned long long s_key;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t q_begin = blockIdx.x * (uint32_t)kStatsQuads;
+  const uint32_t q_end = min(q_begin + (uint32_t)kStatsQuads, plane_quads);
+  for (int s = (int)blockIdx.y; s < n; s += (int)gridDim.y) {
+    for (int i = tid; i < (kStatsThreads / 64) * kFlowHistBins; i += kStatsThreads) (&s_hist[0][0])[i] = 0u;
+    if (tid < 3) { s_cnt[tid] = 0u; s_sum[tid] = 0ull; }
+    if (tid == 3) s_key = 0ull;
+    __syncthreads();
+    const size_t pu = (size_t)s * 2 * plane_quads, pv = pu + plane_quads, po = (size_t)s * plane_quads;  // in quads
+    const uint32_t idx_base = one_row ? (uint32_t)s * plane_quads * 4u : 0u;
+    uint32_t n_counted = 0, n_bad = 0, n_occ = 0;
+    long long sum_u = 0, sum_v = 0, sum_m = 0;
+    unsigned long long key = 0;
+    for (uint32_t q0 = q_begin; q0 < q_end; q0 += kStatsThreads) {  // (wave-uniform trip count: the ballots below see whole waves)
+      const uint32_t q = q0 + (uint32_t)tid;
+      const bool act = q < q_end;
+      float u[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
+      uint32_t hidden = 0;  // bit j: the map says pixel j is occluded
+      if (act) {
+        if constexpr (kHalf) {
+          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu + q], b = reinterpret_cast<const f16x4*>(flow)[pv + q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { u[j] = (float)a[j]; v[j] = (float)b[j]; }
+        } else {
+          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu + q], b = reinterpret_cast<const f32x4*>(flow)[pv + q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { u[j] = a[j]; v[j] = b[j]; }
+        }
+        if constexpr (kOcc == 1) {
+          const f32x4 o = reinterpret_cast<const f32x4*>(occ)[po + q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) hidden |= (o[j] != 0.0f ? 1u : 0u) << j;
+        } else if constexpr (kOcc == 2) {
+          const uint32_t o = reinterpret_cast<const uint32_t*>(occ)[po + q];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) hidden |= (((o >> (8 * j)) & 255u) != 0u ? 1u : 0u) << j;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool occluded = (hidden >> j) & 1u;
+        n_occ += occluded ? 1u : 0u;
+        const bool look = act && !(occluded && visible_only);
+        const bool good = fabsf(u[j]) < 1048576.0f && fabsf(v[j]) < 1048576.0f;
+        n_bad += (look && !good) ? 1u : 0u;
+        const bool counted = look && good;
+        int b = -1;
+        if (counted) {
+          ++n_counted;
+          const float m2 = __fadd_rn(__fmul_rn(u[j], u[j]), __fmul_rn(v[j], v[j]));
+          const float r = sqrtf(m2);
+          b = (int)fminf(__fmul_rn(r, inv_bin), (float)(kFlowHistBins - 1));
+          while (b < kFlowHistBins - 1 && stats_edge2(b + 1, bin_px) <= m2) ++b;
+          while (b > 0 && stats_edge2(b, bin_px) > m2) --b;
+          sum_u += (long long)rintf(__fmul_rn(u[j], 256.0f));
+          sum_v += (long long)rintf(__fmul_rn(v[j], 256.0f));
+          sum_m += (long long)rintf(__fmul_rn(r, 256.0f));
+          const uint32_t idx = idx_base + q * 4u + (uint32_t)j;
+          const unsigned long long k = ((unsigned long long)__float_as_uint(m2) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+          key = k > key ? k : key;
+        }
+        bool live = counted;
+#pragma unroll
+        for (int p = 0; p < kStatsPeel; ++p) {
+          const unsigned long long todo = __ballot(live);
+          if (!todo) break;
+          const int leader = __ffsll(todo) - 1;
+          const int lb = __shfl(b, leader, 64);
+          const bool same = live && b == lb;
+          const unsigned long long m = __ballot(same);
+          if (lane == leader) atomicAdd(&s_hist[wave][lb], (uint32_t)__popcll(m));
+          live = live && !same;
+        }
+        if (live) atomicAdd(&s_hist[wave][b], 1u);
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      n_counted += (uint32_t)__shfl_xor((int)n_counted, d, 64);
+      n_bad += (uint32_t)__shfl_xor((int)n_bad, d, 64);
+      n_occ += (uint32_t)__shfl_xor((int)n_occ, d, 64);
+      sum_u += __shfl_xor(sum_u, d, 64);
+      sum_v += __shfl_xor(sum_v, d, 64);
+      sum_m += __shfl_xor(sum_m, d, 64);
+      const unsigned long long other = (unsigned long long)__shfl_xor((long long)key, d, 64);
+      key = other > key ? other : key;
+    }
+    if (lane == 0) {
+      if (n_counted) atomicAdd(&s_cnt[0], n_counted);
+      if (n_bad) atomicAdd(&s_cnt[1], n_bad);
+      if (n_occ) atomicAdd(&s_cnt[2], n_occ);
+      if (n_counted) {
+        atomicAdd(&s_sum[0], (unsigned long long)sum_u);
+        atomicAdd(&s_sum[1], (unsigned long long)sum_v);
+        atomicAdd(&s_sum[2], (unsigned long long)sum_m);
+        atomicMax(&s_key, key);
+      }
+    }
+    __syncthreads();
+    DevFlowStatsRow* const out = rows + (one_row ? 0 : s);
+    if (wave == 0) {
+      uint32_t h = 0;
+#pragma unroll
+      for (int w = 0; w < kStatsThreads / 64; ++w) h += s_hist[w][lane];
+      if (h) atomicAdd(&out->hist[lane], h);
+    } else if (wave == 1) {
+      if (lane < 3 && s_cnt[lane]) atomicAdd(&out->count[lane], s_cnt[lane]);
+    } else if (wave == 2) {
+      if (lane < 3 && s_sum[lane]) atomicAdd(&out->sum_q8[lane], s_sum[lane]);
+    } else if (lane == 0 && s_key) {
+      atomicMax(&out->max_key, s_key);
+    }
+    __syncthreads();  // (the next sample of this workgroup clears the tables)
+  }
+}
+
 }  // namespace ofdg

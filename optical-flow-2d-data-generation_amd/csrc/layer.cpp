@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -713,6 +714,73 @@ int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, 
           box[0] = std::min(box[0], x); box[1] = std::min(box[1], y);
           box[2] = std::max(box[2], x); box[3] = std::max(box[3], y);
         }
+    }
+  }
+  return OFDG_OK;
+}
+
+// ofdg_flow_stats on host buffers (no GPU): the definition of include/ofdg.h pixel by pixel.  This file is compiled with
+// -ffp-contract=off, so m2 is two products and one sum, each rounded to float32.
+static_assert(sizeof(ofdg_flow_stats_row) == 304 && offsetof(ofdg_flow_stats_row, n_counted) == 256 &&
+              offsetof(ofdg_flow_stats_row, sum_u_q8) == 272 && offsetof(ofdg_flow_stats_row, max_key) == 296,
+              "ofdg_flow_stats_row: 304 bytes, no padding");
+static float half_bits_to_float(uint16_t h) {  // binary16 -> float32, exact
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
+  uint32_t bits;
+  if (e == 31u) bits = sign | 0x7F800000u | (m << 13);
+  else if (e != 0u) bits = sign | ((e + 112u) << 23) | (m << 13);
+  else if (m == 0u) bits = sign;
+  else {  // subnormal: m * 2^-24
+    float f = (float)m * 5.9604644775390625e-8f;
+    std::memcpy(&bits, &f, 4);
+    bits |= sign;
+  }
+  float f;
+  std::memcpy(&f, &bits, 4);
+  return f;
+}
+int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height, float bin_px,
+                         int flags, ofdg_flow_stats_row* rows) {
+  if (const char* why = flow_stats_arg_error(flow, flow_fmt, occ, occ_fmt, n, width, height, bin_px, flags, rows)) {
+    g_host_error = std::string("ofdg_host_flow_stats: ") + why;
+    return OFDG_EINVAL;
+  }
+  const bool one_row = flags & OFDG_STATS_ONE_ROW, visible_only = flags & OFDG_STATS_VISIBLE_ONLY;
+  if (!(flags & OFDG_STATS_ACCUMULATE)) std::memset(rows, 0, sizeof(ofdg_flow_stats_row) * (one_row ? 1 : (size_t)n));
+  float edge2[OFDG_FLOW_HIST_BINS];
+  for (int k = 0; k < OFDG_FLOW_HIST_BINS; ++k) {
+    const float e = (float)k * bin_px;
+    edge2[k] = e * e;
+  }
+  const size_t plane = (size_t)width * height;
+  auto flow_at = [&](size_t i) {
+    return flow_fmt == OFDG_FMT_F16 ? half_bits_to_float(static_cast<const uint16_t*>(flow)[i]) : static_cast<const float*>(flow)[i];
+  };
+  for (int s = 0; s < n; ++s) {
+    ofdg_flow_stats_row& r = rows[one_row ? 0 : s];
+    for (size_t p = 0; p < plane; ++p) {
+      if (occ) {
+        const size_t o = (size_t)s * plane + p;
+        const bool hidden = occ_fmt == OFDG_FMT_U8 ? static_cast<const uint8_t*>(occ)[o] != 0 : static_cast<const float*>(occ)[o] != 0.0f;
+        if (hidden) {
+          ++r.n_occluded;
+          if (visible_only) continue;
+        }
+      }
+      const float u = flow_at((size_t)s * 2 * plane + p), v = flow_at(((size_t)s * 2 + 1) * plane + p);
+      if (!(std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f)) { ++r.n_bad; continue; }
+      ++r.n_counted;
+      const float uu = u * u, vv = v * v, m2 = uu + vv;
+      int b = 0;
+      for (int k = 1; k < OFDG_FLOW_HIST_BINS; ++k) b += edge2[k] <= m2;
+      ++r.hist[b];
+      r.sum_u_q8 += (int64_t)std::rint(u * 256.0f);
+      r.sum_v_q8 += (int64_t)std::rint(v * 256.0f);
+      r.sum_mag_q8 += (int64_t)std::rint(std::sqrt(m2) * 256.0f);
+      uint32_t bits;
+      std::memcpy(&bits, &m2, 4);
+      const uint32_t idx = (uint32_t)((one_row ? (size_t)s * plane : 0) + p);
+      r.max_key = std::max(r.max_key, ((uint64_t)bits << 32) | (uint64_t)(0xFFFFFFFFu - idx));
     }
   }
   return OFDG_OK;

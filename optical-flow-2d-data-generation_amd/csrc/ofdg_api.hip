@@ -1570,6 +1570,52 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   return OFDG_OK;
 }
 
+// Flow statistics of caller-given planes: the clearing of the rows and one kernel on `stream`.  It reads nothing of the
+// context's own (no slot record, no workspace), so no completion bookkeeping is needed on any stream.
+static_assert(sizeof(ofdg_flow_stats_row) == sizeof(DevFlowStatsRow) && OFDG_FLOW_HIST_BINS == kFlowHistBins &&
+              offsetof(ofdg_flow_stats_row, n_counted) == offsetof(DevFlowStatsRow, count) &&
+              offsetof(ofdg_flow_stats_row, sum_u_q8) == offsetof(DevFlowStatsRow, sum_q8) &&
+              offsetof(ofdg_flow_stats_row, max_key) == offsetof(DevFlowStatsRow, max_key) && offsetof(ofdg_flow_stats_row, max_key) == 296,
+              "ofdg_flow_stats_row: 304 bytes without padding, the layout the kernel adds to");
+static_assert(OFDG_FMT_F32 == 0 && OFDG_FMT_U8 == 1 && OFDG_FMT_F16 == 2 && OFDG_STATS_ACCUMULATE == 1 && OFDG_STATS_VISIBLE_ONLY == 2 &&
+              OFDG_STATS_ONE_ROW == 4, "flow_stats_arg_error spells these codes out");
+int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, float bin_px,
+                    int flags, ofdg_flow_stats_row* d_rows, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  auto fail = [&](const std::string& why) { c->err = "ofdg_flow_stats: " + why; return OFDG_EINVAL; };
+  const int W = c->prm.width, H = c->prm.height;
+  if (const char* why = flow_stats_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, bin_px, flags, d_rows)) return fail(why);
+  const bool half = flow_fmt == OFDG_FMT_F16;
+  if ((uintptr_t)d_flow & (half ? 7 : 15)) return fail(half ? "d_flow must be 8-byte aligned (binary16)" : "d_flow must be 16-byte aligned (float32)");
+  if (d_occ && ((uintptr_t)d_occ & (occ_fmt == OFDG_FMT_U8 ? 3 : 15)))
+    return fail(occ_fmt == OFDG_FMT_U8 ? "d_occ must be 4-byte aligned (uint8)" : "d_occ must be 16-byte aligned (float32)");
+  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
+  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+  const bool one_row = flags & OFDG_STATS_ONE_ROW;
+  if (!(flags & OFDG_STATS_ACCUMULATE))
+    HIP_OK(c, hipMemsetAsync(d_rows, 0, sizeof(ofdg_flow_stats_row) * (one_row ? 1 : (size_t)n_samples), st));
+  const uint32_t plane_quads = (uint32_t)((size_t)W * H / 4);  // (W % 8 == 0: whole quads)
+  const dim3 grid((plane_quads + kStatsQuads - 1) / kStatsQuads, (unsigned)std::min(n_samples, 65535));
+  const int kind = (half ? 3 : 0) + (d_occ ? (occ_fmt == OFDG_FMT_U8 ? 2 : 1) : 0);
+  DevFlowStatsRow* const rows = reinterpret_cast<DevFlowStatsRow*>(d_rows);
+  const float inv_bin = 1.0f / bin_px;
+  const int vis = (flags & OFDG_STATS_VISIBLE_ONLY) ? 1 : 0, one = one_row ? 1 : 0;
+#define OFDG_STATS_LAUNCH(HALF, OCC)                                                                                               \
+  hipLaunchKernelGGL((flow_stats_kernel<HALF, OCC>), grid, dim3(kStatsThreads), 0, st, d_flow, d_occ, n_samples, plane_quads, bin_px, \
+                     inv_bin, vis, one, rows)
+  switch (kind) {
+    case 0: OFDG_STATS_LAUNCH(false, 0); break;
+    case 1: OFDG_STATS_LAUNCH(false, 1); break;
+    case 2: OFDG_STATS_LAUNCH(false, 2); break;
+    case 3: OFDG_STATS_LAUNCH(true, 0); break;
+    case 4: OFDG_STATS_LAUNCH(true, 1); break;
+    default: OFDG_STATS_LAUNCH(true, 2); break;
+  }
+#undef OFDG_STATS_LAUNCH
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
 static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {

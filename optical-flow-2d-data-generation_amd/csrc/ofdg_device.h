@@ -104,6 +104,35 @@ struct DevObjectRow {
 static_assert(sizeof(DevObjectRow) == 96, "ofdg_object_row is 96 bytes without padding");
 constexpr int kObjectRows = kMaxFgObjects + 1;  // OFDG_MAX_OBJECT_ROWS: background + foreground objects
 
+// One row of the flow statistics (ofdg_flow_stats_row of include/ofdg.h, field for field): the kernel adds to the counts and
+// the Q8 sums with unsigned atomics (two's complement: the sums are int64 to the caller), so they are arrays here.
+constexpr int kFlowHistBins = 64;  // OFDG_FLOW_HIST_BINS
+struct DevFlowStatsRow {
+  uint32_t hist[kFlowHistBins];
+  uint32_t count[4];              // n_counted, n_bad, n_occluded, reserved
+  unsigned long long sum_q8[3];   // sum_u_q8, sum_v_q8, sum_mag_q8
+  unsigned long long max_key;
+};
+static_assert(sizeof(DevFlowStatsRow) == 304, "ofdg_flow_stats_row is 304 bytes without padding");
+// The argument rules ofdg_flow_stats and ofdg_host_flow_stats share (format codes and flag bits are those of include/ofdg.h:
+// float32 0, uint8 1, binary16 2; ACCUMULATE 1, VISIBLE_ONLY 2, ONE_ROW 4): the first rule broken, or nullptr.
+inline const char* flow_stats_arg_error(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
+                                        float bin_px, int flags, const void* rows) {
+  if (!flow) return "d_flow is NULL";
+  if (!rows) return "d_rows is NULL";
+  if (flow_fmt != 0 && flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (occ && occ_fmt != 0 && occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (n < 1) return "n_samples must be at least 1";
+  if (width < 1 || height < 1) return "width and height must be at least 1";
+  if (!(bin_px >= 0.0009765625f && bin_px <= 16384.0f)) return "bin_px must lie in [2^-10, 2^14]";
+  if (flags & ~7) return "flags holds unknown bits";
+  if ((flags & 2) && !occ) return "flags: OFDG_STATS_VISIBLE_ONLY needs d_occ";
+  if ((flags & 4) && (unsigned long long)n * (unsigned long long)width * (unsigned long long)height >= (1ull << 32))
+    return "flags: OFDG_STATS_ONE_ROW needs n*H*W below 2^32";
+  if ((uintptr_t)rows & 7) return "d_rows must be 8-byte aligned";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
