@@ -586,26 +586,31 @@ class Generator:
                 setattr(ex, name, _dptr(t).value)
         return of, ex
 
+    def _call(self, family, lead, img0, img1, flow, n, stream, extras, fmt):
+        """One render / forward call of n samples: ofdg_<family> in the form the outputs need - plain, _ex (optional outputs,
+        float32 throughout), _fmt (a compact format) or _ex_fmt (both, or uint8 occlusion maps) - with `lead` as the arguments
+        between the context and the output pointers."""
+        of, ex = self._formats(img0, img1, flow, n, fmt, extras)
+        if isinstance(ex, ExtrasFmt):   # (of None: uint8 occlusion maps behind float32 outputs)
+            suffix, tail = "_ex_fmt", (C.byref(ex), C.byref(of) if of is not None else None)
+        elif of is not None:
+            suffix, tail = "_fmt", (C.byref(of),)
+        elif ex is not None:
+            suffix, tail = "_ex", (C.byref(ex),)
+        else:
+            suffix, tail = "", ()
+        fn = getattr(lib(), "ofdg_" + family + suffix)
+        self._check(fn(self.h, *lead, _dptr(img0), _dptr(img1), _dptr(flow), *tail, C.c_void_p(stream)))
+        self._last_n = n
+
     def render(self, tasks, n_tasks, bps, n_bps, img0, img1, flow, stream=0, extras=None, fmt=None):
         """img0/img1/flow: device pointers (int) or torch CUDA tensors.  extras: {name: tensor} of optional outputs
         (alloc_extras; rigid modes): flow1, occ0, occ1, label0, label1.  Tensors may be uint8 frames and / or a float16 flow
         (alloc_outputs(image_dtype=, flow_dtype=)): the call then writes those formats; with raw pointers say
         fmt=("u8", "f16").  The extras follow: flow1 has the dtype of flow, occ0 / occ1 are float32 or uint8
         (alloc_extras(flow_dtype=, occ_dtype=))."""
-        of, ex = self._formats(img0, img1, flow, n_tasks, fmt, extras)
-        L, t, b = lib(), C.cast(tasks, C.c_void_p), C.cast(bps, C.c_void_p)
-        out = (_dptr(img0), _dptr(img1), _dptr(flow))
-        if isinstance(ex, ExtrasFmt):
-            rc = L.ofdg_render_ex_fmt(self.h, t, n_tasks, b, n_bps, *out, C.byref(ex), C.byref(of) if of is not None else None,
-                                      C.c_void_p(stream))
-        elif of is not None:
-            rc = L.ofdg_render_fmt(self.h, t, n_tasks, b, n_bps, *out, C.byref(of), C.c_void_p(stream))
-        elif ex is not None:
-            rc = L.ofdg_render_ex(self.h, t, n_tasks, b, n_bps, *out, C.byref(ex), C.c_void_p(stream))
-        else:
-            rc = L.ofdg_render(self.h, t, n_tasks, b, n_bps, *out, C.c_void_p(stream))
-        self._check(rc)
-        self._last_n = n_tasks
+        lead = (C.cast(tasks, C.c_void_p), n_tasks, C.cast(bps, C.c_void_p), n_bps)
+        self._call("render", lead, img0, img1, flow, n_tasks, stream, extras, fmt)
 
     def render_resident(self, img0, img1, flow, stream=0):
         self._check(lib().ofdg_render_resident(self.h, _dptr(img0), _dptr(img1), _dptr(flow), C.c_void_p(stream)))
@@ -620,33 +625,10 @@ class Generator:
         self._last_n = self._slot_n.get(slot)
 
     def forward(self, img0, img1, flow, stream=0, extras=None, fmt=None):
-        of, ex = self._formats(img0, img1, flow, self.params.batch_size, fmt, extras)
-        L, out = lib(), (_dptr(img0), _dptr(img1), _dptr(flow))
-        if isinstance(ex, ExtrasFmt):
-            rc = L.ofdg_forward_ex_fmt(self.h, *out, C.byref(ex), C.byref(of) if of is not None else None, C.c_void_p(stream))
-        elif of is not None:
-            rc = L.ofdg_forward_fmt(self.h, *out, C.byref(of), C.c_void_p(stream))
-        elif ex is not None:
-            rc = L.ofdg_forward_ex(self.h, *out, C.byref(ex), C.c_void_p(stream))
-        else:
-            rc = L.ofdg_forward(self.h, *out, C.c_void_p(stream))
-        self._check(rc)
-        self._last_n = self.params.batch_size
+        self._call("forward", (), img0, img1, flow, self.params.batch_size, stream, extras, fmt)
 
     def forward_counter(self, first_index, n, img0, img1, flow, stream=0, extras=None, fmt=None):
-        of, ex = self._formats(img0, img1, flow, n, fmt, extras)
-        L, out = lib(), (_dptr(img0), _dptr(img1), _dptr(flow))
-        if isinstance(ex, ExtrasFmt):
-            rc = L.ofdg_forward_counter_ex_fmt(self.h, first_index, n, *out, C.byref(ex), C.byref(of) if of is not None else None,
-                                               C.c_void_p(stream))
-        elif of is not None:
-            rc = L.ofdg_forward_counter_fmt(self.h, first_index, n, *out, C.byref(of), C.c_void_p(stream))
-        elif ex is not None:
-            rc = L.ofdg_forward_counter_ex(self.h, first_index, n, *out, C.byref(ex), C.c_void_p(stream))
-        else:
-            rc = L.ofdg_forward_counter(self.h, first_index, n, *out, C.c_void_p(stream))
-        self._check(rc)
-        self._last_n = n
+        self._call("forward_counter", (first_index, n), img0, img1, flow, n, stream, extras, fmt)
 
     def object_table(self, label0, label1, rows, counts, stream=0):
         """The per-object annotation table (ofdg_object_table, include/ofdg.h) of the batch the last render / forward call

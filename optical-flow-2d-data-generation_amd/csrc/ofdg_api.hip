@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ofdg.h"
@@ -234,6 +235,26 @@ struct ofdg_ctx {
       return OFDG_EHIP;                                                                       \
     }                                                                                         \
   } while (0)
+// ... and for the functions of this file that return an OFDG_* code themselves
+#define OFDG_TRY(expr)                                                                        \
+  do {                                                                                        \
+    const int rc_ = (expr);                                                                   \
+    if (rc_ != OFDG_OK) return rc_;                                                           \
+  } while (0)
+
+// One kernel launch with events on its own dispatch packet (`start` / `stop`, either may be null).  An argument has its
+// parameter's type or, for a pointer parameter, converts to it implicitly - or is a void*: an output buffer travels as void* and
+// arrives as the float* of the float32 kernels.  Nothing else compiles (no int for a float, no pointer of another type).
+template <typename P, typename A>
+constexpr bool kArgFits = std::is_same<A, P>::value ||
+                          (std::is_pointer<P>::value && (std::is_convertible<A, P>::value || std::is_same<A, void*>::value));
+struct Launch { unsigned grid, block; hipStream_t stream; hipEvent_t start, stop; };
+template <typename... P, typename... A>
+static void launch_kernel(const Launch& l, void (*kernel)(P...), A... args) {
+  static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+  static_assert((kArgFits<P, A> && ...), "an argument that is neither of its parameter's type nor a void* for a pointer");
+  hipExtLaunchKernelGGL(kernel, dim3(l.grid), dim3(l.block), 0, l.stream, l.start, l.stop, 0, static_cast<P>(args)...);
+}
 
 // the error word of the call being made (its ticket is taken - c->ticket advanced - when the call's first kernel is enqueued)
 static uint32_t* err_word(ofdg_ctx* c, long long ticket) { return c->d_err + (size_t)(ticket % ofdg_ctx::kErrWords); }
@@ -450,9 +471,8 @@ static int pool_check_dims(ofdg_ctx* c, int n, int w, int h) {
 
 int ofdg_pool_alloc(ofdg_ctx* c, int n, int w, int h) {
   if (!c) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
-  int rc = pool_check_dims(c, n, w, h);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(pool_check_dims(c, n, w, h));
   HIP_OK(c, hipDeviceSynchronize());
   if (c->pool) { HIP_OK(c, hipFree(c->pool)); c->pool = nullptr; }
   HIP_OK(c, hipMalloc((void**)&c->pool, (size_t)n * w * h * sizeof(uint32_t)));
@@ -469,7 +489,7 @@ int ofdg_pool_alloc(ofdg_ctx* c, int n, int w, int h) {
 // it is smaller; DG:96-106), in two uniform arrays.  background_prep needs the originals: not available here.
 int ofdg_pool_alloc_mixed(ofdg_ctx* c, int n) {
   if (!c) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   if (n < 1) { c->err = "texture pool needs at least one image"; return OFDG_ETEXTURES; }
   const int W = c->prm.width, H = c->prm.height;
   HIP_OK(c, hipDeviceSynchronize());
@@ -498,7 +518,7 @@ int ofdg_pool_alloc_mixed(ofdg_ctx* c, int n) {
 // image `index` of a mixed pool: planar B,G,R u8 of any size >= 2 x 2
 int ofdg_pool_upload_mixed(ofdg_ctx* c, int index, const uint8_t* bgr_planar, int w, int h) {
   if (!c || !bgr_planar) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   if (!c->pool_mixed || index < 0 || index >= c->pool_n || w < 2 || h < 2) {
     c->err = "pool_upload_mixed: no mixed pool (ofdg_pool_alloc_mixed), bad index or image smaller than 2 x 2";
     return OFDG_ETEXTURES;
@@ -530,8 +550,7 @@ int ofdg_pool_upload_mixed(ofdg_ctx* c, int index, const uint8_t* bgr_planar, in
 }
 
 int ofdg_pool_synthetic(ofdg_ctx* c, int n, int w, int h, uint32_t seed) {
-  int rc = ofdg_pool_alloc(c, n, w, h);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(ofdg_pool_alloc(c, n, w, h));
   hipLaunchKernelGGL(pool_synth_kernel, dim3(256 * 8), dim3(256), 0, 0, c->pool, n, w, h, seed);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipDeviceSynchronize());
@@ -543,7 +562,7 @@ int ofdg_pool_synthetic(ofdg_ctx* c, int n, int w, int h, uint32_t seed) {
 
 int ofdg_pool_upload(ofdg_ctx* c, int index, const uint8_t* bgr_planar, int w, int h) {
   if (!c || !bgr_planar) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   if (!c->pool || index < 0 || index >= c->pool_n || w != c->pool_w || h != c->pool_h) {
     c->err = "pool_upload: index / size does not match the allocated pool";
     return OFDG_ETEXTURES;
@@ -592,8 +611,7 @@ int ofdg_pool_device(ofdg_ctx* c, void** ptr, unsigned long long* bytes, int mar
   *bytes = (unsigned long long)c->pool_n * c->pool_w * c->pool_h * sizeof(uint32_t);
   if (mark_written) {
     c->pool_final = false;
-    int rcd = discard_all_prepared(c);  // (batches prepared ahead would render the old contents)
-    if (rcd != OFDG_OK) return rcd;
+    OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead would render the old contents)
   }
   return OFDG_OK;
 }
@@ -601,7 +619,7 @@ int ofdg_pool_device(ofdg_ctx* c, void** ptr, unsigned long long* bytes, int mar
 int ofdg_pool_device_mixed(ofdg_ctx* c, void** fg, unsigned long long* fg_bytes, void** bg, unsigned long long* bg_bytes) {
   if (!c || !fg || !fg_bytes || !bg || !bg_bytes) return OFDG_EINVAL;
   if (!c->pool_mixed) { c->err = "pool_device_mixed: needs a mixed pool (ofdg_pool_alloc_mixed)"; return OFDG_ETEXTURES; }
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (the caller is about to write the textures)
+  OFDG_TRY(discard_all_prepared(c));  // (the caller is about to write the textures)
   HIP_OK(c, hipDeviceSynchronize());
   const unsigned long long px = (unsigned long long)c->prm.width * c->prm.height;
   *fg = (void*)c->pool_fg; *fg_bytes = (unsigned long long)c->pool_n * px * sizeof(uint32_t);
@@ -639,12 +657,11 @@ int ofdg_setup_of(const ofdg_ctx* c, ofdg_setup* su, ofdg_tex_entry* table, int 
 
 int ofdg_setup_alloc_pool(ofdg_ctx* c, const ofdg_setup* su, const ofdg_tex_entry* table) {
   if (!c || !su) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   if (su->width != c->prm.width || su->height != c->prm.height) { c->err = "setup_alloc_pool: the context was not created from this setup"; return OFDG_EINVAL; }
   if (su->pool_kind == OFDG_POOL_SYNTHETIC) return ofdg_pool_synthetic(c, su->n_tex, su->pool_w, su->pool_h, su->pool_seed);
   if (su->pool_kind != OFDG_POOL_MIXED) return ofdg_pool_alloc(c, su->n_tex, su->pool_w, su->pool_h);
-  int rc = ofdg_pool_alloc_mixed(c, su->n_tex);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(ofdg_pool_alloc_mixed(c, su->n_tex));
   if (!table || su->n_table < su->n_tex) { c->err = "setup_alloc_pool: a mixed pool needs the index table (image sizes)"; return OFDG_EINVAL; }
   for (int i = 0; i < su->n_tex; ++i) {
     c->mixed_sizes[(size_t)i] = std::make_pair((int)table[i].w, (int)table[i].h);
@@ -673,8 +690,7 @@ int ofdg_sample(ofdg_ctx* c, int n_tasks, ofdg_task* tasks, ofdg_blueprint* bps,
   if (c->prm.sampler != OFDG_SAMPLER_REF) { c->err = "only OFDG_SAMPLER_REF is implemented on the host"; return OFDG_EINVAL; }
   std::vector<ofdg_blueprint> pool;
   for (int i = 0; i < n_tasks; ++i) {
-    int rc = c->sampler->next_task(&pool, &tasks[i], &c->err);
-    if (rc != OFDG_OK) return rc;
+    OFDG_TRY(c->sampler->next_task(&pool, &tasks[i], &c->err));
   }
   *n_bps = (int)pool.size();
   if ((int)pool.size() > bps_capacity) { c->err = "blueprint capacity exceeded"; return OFDG_ECAPACITY; }
@@ -737,8 +753,7 @@ static int ensure_counter_croptab(ofdg_ctx* c) {
   if (c->d_cs_croptab) return OFDG_OK;
   const int n = c->crop_server.n_crops;
   if (!c->d_warp || n < 1) { c->err = "mode 9 needs warp fields: call ofdg_warp_generate or ofdg_warp_upload first"; return OFDG_EINVAL; }
-  int rc = ensure_resize_tables(c);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(ensure_resize_tables(c));
   const int W = c->prm.width, H = c->prm.height;
   const size_t crop_floats = (size_t)4 * (W + 1) * (H + 1), bg_floats = (size_t)4 * 2 * W * 2 * H;
   HIP_OK(c, hipDeviceSynchronize());
@@ -836,15 +851,13 @@ static int finalise_pool(ofdg_ctx* c) {
   if (w >= W && h >= H) {
     c->fg_src = TexSource{img, (uint64_t)(h / 2 - H / 2) * w + (uint64_t)(w / 2 - W / 2), w, 0};
   } else {
-    int rc = pool_resized_copy(c, W, H, &c->pool_fg);
-    if (rc != OFDG_OK) return rc;
+    OFDG_TRY(pool_resized_copy(c, W, H, &c->pool_fg));
     c->fg_src = TexSource{(uint64_t)W * H, 0, W, 0};
   }
   if (w >= 2 * W && h >= 2 * H) {
     c->bg_src = TexSource{img, (uint64_t)(h / 2 - H) * w + (uint64_t)(w / 2 - W), w, 0};
   } else {
-    int rc = pool_resized_copy(c, 2 * W, 2 * H, &c->pool_bg);
-    if (rc != OFDG_OK) return rc;
+    OFDG_TRY(pool_resized_copy(c, 2 * W, 2 * H, &c->pool_bg));
     c->bg_src = TexSource{(uint64_t)4 * W * H, 0, 2 * W, 0};
   }
   c->pool_final = true;
@@ -934,7 +947,7 @@ static int discard_prepared(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
 }
 static int discard_all_prepared(ofdg_ctx* c) {
   c->bg_cap_n = -1;  // (called by everything that changes the pool)
-  for (int k = 0; k < c->n_chains; ++k) { int rc = discard_prepared(c, c->chains[k]); if (rc != OFDG_OK) return rc; }
+  for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_prepared(c, c->chains[k]));
   return OFDG_OK;
 }
 
@@ -952,6 +965,22 @@ static RenderDims render_dims(const ofdg_ctx* c, const ofdg_ctx::Slot& sl) {
   return dm;
 }
 
+// Work about to be enqueued on `s` must follow what `ev` marks on another stream.  An event that has already fired costs a
+// query and clears `*pending`; otherwise `s` waits for it, and `*pending` stays set for the other streams that may still
+// have to wait - unless `settles`: the waiting stream is the only one that ever asks.
+static int wait_unless_fired(ofdg_ctx* c, hipStream_t s, hipEvent_t ev, bool* pending, bool settles = false) {
+  if (hipEventQuery(ev) == hipSuccess) { *pending = false; return OFDG_OK; }
+  HIP_OK(c, hipStreamWaitEvent(s, ev, 0));
+  if (settles) *pending = false;
+  return OFDG_OK;
+}
+// Kernels that read slot `sl` and the workspaces of chain `ch` were enqueued on `s`, the last one with `done` (the chain's
+// ev_done) on its packet: whoever rewrites either from another stream waits for it (launch_prepare, upload_slot).
+static void track_completion(ofdg_ctx::Slot& sl, ofdg_ctx::Chain& ch, hipStream_t s, hipEvent_t done) {
+  sl.compose_pending = true; sl.compose_stream = s; sl.compose_event = done;
+  ch.done_pending = true; ch.done_stream = s;
+}
+
 // The preparation kernels of the batch resident in `sl`, in order on chain `ch`: [counter sampler ->] geom -> raster
 //   `st` is the stream of the call the batch is prepared for (only the serial mode prepares on it).
 static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, hipStream_t st, long long cs_first_index = -1,
@@ -959,7 +988,7 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   const int W = c->prm.width, H = c->prm.height;
   const int n_sf = sl.res_shapes * 2;
   const RenderDims dm = render_dims(c, sl);
-  { int rc = discard_prepared(c, ch); if (rc != OFDG_OK) return rc; }
+  OFDG_TRY(discard_prepared(c, ch));
   const long long ticket = c->ticket++;  // this batch's number: its kernels raise their flags in its own word
   uint32_t* const err = err_word(c, ticket);
   hipEvent_t* ev = nullptr;
@@ -979,25 +1008,16 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   uint8_t* cov = ch.cov.p;
   // the slot's records: written on another stream, or still read by a compose of another chain
   // (a user slot rendered again; the chain's private slot only ever sees its own stream)
-  if (sl.upload_pending && sl.upload_stream != S) {
-    if (hipEventQuery(sl.ev_uploaded) == hipSuccess) sl.upload_pending = false;
-    else HIP_OK(c, hipStreamWaitEvent(S, sl.ev_uploaded, 0));
-  }
+  if (sl.upload_pending && sl.upload_stream != S) OFDG_TRY(wait_unless_fired(c, S, sl.ev_uploaded, &sl.upload_pending));
   // the chain's workspace (and private slot) may still be read by its previous compose if that ran on a caller's stream
-  if (ch.done_pending && ch.done_stream != S) {
-    if (hipEventQuery(ch.ev_done) != hipSuccess) HIP_OK(c, hipStreamWaitEvent(S, ch.ev_done, 0));
-    ch.done_pending = false;  // (the chain's stream is ordered behind it from here on)
-  }
-  if (sl.compose_pending && sl.compose_stream != S) {
-    if (hipEventQuery(sl.compose_event) == hipSuccess) sl.compose_pending = false;
-    else HIP_OK(c, hipStreamWaitEvent(S, sl.compose_event, 0));
-  }
+  // (the chain's stream is ordered behind it from here on: settled either way)
+  if (ch.done_pending && ch.done_stream != S) OFDG_TRY(wait_unless_fired(c, S, ch.ev_done, &ch.done_pending, /*settles=*/true));
+  if (sl.compose_pending && sl.compose_stream != S) OFDG_TRY(wait_unless_fired(c, S, sl.compose_event, &sl.compose_pending));
   // mode 9: the batch's own crop table (host path) or the static table of all crops (counter sampler)
   const DevCropRef* croptab = cs_first_index >= 0 ? c->d_cs_croptab : sl.d_croptab.p;
   HIP_OK(c, take_err_word(c, ticket, S));  // (nothing is enqueued unless this caller asks by ticket AND the word's last owner was never asked about)
   if (cs_first_index >= 0) {  // device counter sampler + device realize
-    int rc = launch_counter_sampler(c, sl, cs_first_index, S, err);
-    if (rc != OFDG_OK) return rc;
+    OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, err));
   }
   // (the background preparation of the batch goes LAST, right in front of compose: below)
   // geom: outlines, bounding boxes, per-object boxes (parity `bp`), raster work list
@@ -1030,8 +1050,7 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
                         sl.d_frames.p, sl.d_items.p, sl.d_item_count, sl.d_verts.p, W, H, cov, box_next, n_mask_words, box_cur);
   HIP_OK(c, hipGetLastError());
   if (prep_last) {
-    int rcb = prepare_backgrounds(c, sl, sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2] : last_stop);
-    if (rcb != OFDG_OK) return rcb;
+    OFDG_TRY(prepare_backgrounds(c, sl, sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2] : last_stop));
     sl.bgprep_pending = false;
     if (ev) c->ev_bgprep[(size_t)(ev - c->ev.data()) / 6] = 1;
   }
@@ -1042,178 +1061,27 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   return OFDG_OK;
 }
 
-// compose of the batch chain `ch` has prepared.  `st` is the caller's stream: if it is not the chain's own stream
-// (ofdg_stream), compose runs on `st` instead, behind what the caller enqueued there (the outputs may still be read) and
-// behind the chain's preparation kernels.
-// out_fmt != 0 (kOutImageU8 | kOutFlowF16): the compact kernels; the outputs then hold those element types.
-// ex (checked): the optional outputs; float32 throughout (out_fmt 0, ex->occ F32) they take the kernels of ofdg_*_ex, with a
-// compact format or uint8 occlusion maps compose_rigid_ext_fmt_kernel + occlusion_fmt_kernel (ex->flow1: the flow's type).
-static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, void* d_img0v, void* d_img1v, void* d_flowv, hipStream_t st,
-                          const ofdg_extras_fmt* ex = nullptr, int out_fmt = 0) {
-  float* const d_img0 = static_cast<float*>(d_img0v);
-  float* const d_img1 = static_cast<float*>(d_img1v);
-  float* const d_flow = static_cast<float*>(d_flowv);
-  if (!ch.prep.valid) { c->err = "internal: compose without a prepared batch"; return OFDG_EINVAL; }
-  ofdg_ctx::Slot& sl = *ch.prep.slot;
-  const int W = c->prm.width, H = c->prm.height;
-  const RenderDims dm = render_dims(c, sl);
-  // extras (rigid modes): where compose writes the backward flow and the labels - the caller's buffers, or the chain's
-  // workspace when only the occlusion pass needs them (grown only; growing waits for the device, like reserve_workspaces)
-  ExtOut xo{nullptr, nullptr, nullptr};
-  const bool extras = ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1);
-  const bool occ = extras && (ex->occ0 || ex->occ1);
-  const bool xfmt = extras && (out_fmt || ex->occ == OFDG_FMT_U8);  // the extras in a compact format of the outputs or of their own
-  uint32_t *tgt0 = nullptr, *tgt1 = nullptr;
-  if (extras) {
-    const size_t plane = (size_t)W * H, n = (size_t)dm.n_samples;
-    // (with a compact format the occlusion pass reads compose's rounded targets, not flow / flow1: no flow1 workspace)
-    const bool ws_labels = occ && (!ex->label0 || !ex->label1), ws_flow1 = !xfmt && ex->occ1 && !ex->flow1, ws_tgt = xfmt && occ;
-    if ((ws_labels && 2 * n * plane > ch.x_labels.cap) || (ws_flow1 && 2 * n * plane > ch.x_flow1.cap) ||
-        (ws_tgt && 2 * n * plane > ch.x_targets.cap)) {
-      HIP_OK(c, hipDeviceSynchronize());
-      if (ws_labels) HIP_OK(c, ch.x_labels.reserve(2 * n * plane));
-      if (ws_flow1) HIP_OK(c, ch.x_flow1.reserve(2 * n * plane));
-      if (ws_tgt) HIP_OK(c, ch.x_targets.reserve(2 * n * plane));
-    }
-    if (ws_tgt) {  // stored only for the frames whose map is asked for
-      tgt0 = ex->occ0 ? ch.x_targets.p : nullptr;
-      tgt1 = ex->occ1 ? ch.x_targets.p + n * plane : nullptr;
-    }
-    xo.flow1 = ex->flow1 ? static_cast<float*>(ex->flow1) : (ws_flow1 ? ch.x_flow1.p : nullptr);
-    xo.label0 = ex->label0 ? ex->label0 : (occ ? ch.x_labels.p : nullptr);
-    xo.label1 = ex->label1 ? ex->label1 : (occ ? ch.x_labels.p + n * plane : nullptr);
-  }
-  const int compose_grid = dm.tiles_x * dm.tiles_y * dm.n_samples * 4;  // one 64 x 4 strip per single-wave workgroup
-  hipEvent_t* ev = ch.prep.ev;
-  unsigned long long* box_cur = ch.prep.box_cur;
-  const DevCropRef* croptab = ch.prep.croptab;
-  uint8_t* cov = ch.cov.p;
-  const hipStream_t S = ch.prep.stream;
-  const bool foreign = S != st;  // the caller's stream is not the chain's
-  const uint32_t* bgpool = c->prm.background_prep ? sl.d_bgtex.p : (c->pool_bg ? c->pool_bg : c->pool);  // (after the slot's buffers are final)
-  const uint32_t* fgpool = c->pool_fg ? c->pool_fg : c->pool;
-  if (c->prm.background_prep && !bgpool) { c->err = "background_prep: the slot has no prepared backgrounds"; return OFDG_EINVAL; }
-  c->last_slot = &sl;
-  c->last_ch = &ch;
-  c->last_stream = ch.prep.stream;
-  c->last_ticket = ch.prep.ticket;
-  ch.prep.valid = false;  // (consumed from here on; an argument error above leaves it to discard_prepared, which resets the work list)
-  // Where compose runs: on the chain's stream, right behind the preparation - or, if the caller passed another stream,
-  // on THAT stream (in order with the caller's own work, which may still read the outputs) once the batch is prepared.
-  // It is tracked by the chain's event whenever somebody else may have to wait for it: the chain
-  // itself (workspace, private slot) after a compose on a caller's stream, other chains for a shared slot.
-  hipStream_t CS = S;
-  if (foreign) {
-    HIP_OK(c, hipStreamWaitEvent(st, ch.ev_prep, 0));
-    CS = st;
-  }
-  const bool shared_slot = &sl != &ch.slot;
-  hipEvent_t done = (foreign || shared_slot) ? ch.ev_done : nullptr;
-  // (profiled launches: start and stop are the timestamps of the compose kernel's own dispatch packet)
-  // profiling 1 (compose only, what bench.py runs the timed region with): NO start marker - the compose launch is timed from
-  // the completion of its predecessor on the chain (the last preparation kernel's own packet, ev[4], launch_prepare) to its
-  // own completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
-  // kernel's own start (a marker, ev[4]) and end.
-  hipEvent_t k_start = (ev && c->profiling == 2) ? ev[4] : nullptr, k_stop = ev ? ev[5] : (occ ? nullptr : done);
-  if (xfmt && (W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_rigid_ext_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, xo, out_fmt, tgt0, tgt1);
-  else if (xfmt)
-    hipExtLaunchKernelGGL(compose_rigid_ext_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, xo, out_fmt, tgt0, tgt1);
-  else if (out_fmt && c->prm.mode == 9 && (W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_deform_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
-                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0v, d_img1v, d_flowv, sl.d_frames.p, croptab,
-                          sl.d_item_count, out_fmt);
-  else if (out_fmt && c->prm.mode == 9)
-    hipExtLaunchKernelGGL(compose_deform_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
-                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0v, d_img1v, d_flowv, sl.d_frames.p, croptab,
-                          sl.d_item_count, out_fmt);
-  else if (out_fmt && (W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_rigid_fmt_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, out_fmt);
-  else if (out_fmt)
-    hipExtLaunchKernelGGL(compose_rigid_fmt_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0v, d_img1v, d_flowv, sl.d_frames.p, sl.d_item_count, out_fmt);
-  else if (extras && (W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_rigid_ext_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count, xo);
-  else if (extras)
-    hipExtLaunchKernelGGL(compose_rigid_ext_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count, xo);
-  else if (c->prm.mode == 9 && (W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_deform_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
-                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0, d_img1, d_flow, sl.d_frames.p, croptab,
-                          sl.d_item_count);
-  else if (c->prm.mode == 9)
-    hipExtLaunchKernelGGL(compose_deform_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, dm, sl.d_samples.p,
-                          sl.d_objects.p, box_cur, cov, fgpool, bgpool, d_img0, d_img1, d_flow, sl.d_frames.p, croptab,
-                          sl.d_item_count);
-  else if ((W & (W - 1)) == 0)
-    hipExtLaunchKernelGGL(compose_rigid_pow2_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count);
-  else
-    hipExtLaunchKernelGGL(compose_rigid_kernel, dim3(compose_grid), dim3(64), 0, CS, k_start, k_stop, 0, sl.d_samples.p, box_cur,
-                          sl.d_objects.p, cov, compose_grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch, dm.fg_pitch, fgpool, bgpool,
-                          d_img0, d_img1, d_flow, sl.d_frames.p, sl.d_item_count);
-  HIP_OK(c, hipGetLastError());
-  if (occ) {  // behind compose on the same stream; the chain's completion event (workspace, slot) goes on THIS packet
-    const long long quads = (long long)dm.n_samples * H * (W / 4);
-    if (xfmt)
-      hipExtLaunchKernelGGL(occlusion_fmt_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0,
-                            tgt0, tgt1, xo.label0, xo.label1, ex->occ0, ex->occ1, W, H, dm.n_samples,
-                            ex->occ == OFDG_FMT_U8 ? kOutOccU8 : 0);
-    else
-      hipExtLaunchKernelGGL(occlusion_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, CS, nullptr, ev ? nullptr : done, 0, d_flow,
-                            xo.flow1, xo.label0, xo.label1, static_cast<float*>(ex->occ0), static_cast<float*>(ex->occ1), W, H,
-                            dm.n_samples);
-    HIP_OK(c, hipGetLastError());
-  }
-  if (ev) {
-    if (done) HIP_OK(c, hipEventRecord(done, CS));
-    // profiling 1 times compose from the completion of the chain's last preparation kernel: that is the launch's time only
-    // when compose is enqueued right behind it on the same stream.  A batch prepared ahead by an earlier call, or composed
-    // on a caller's stream behind the hand-over event, would count host and queue idle time: such a set is not a sample.
-    const bool span_is_the_launch = c->profiling == 2 || (!foreign && !ch.prep.ahead);
-    if (span_is_the_launch) {
-      c->ev_count++;
-      c->ev_composed[(size_t)(ev - c->ev.data()) / 6] = 1;
-    }
-  }
-  if (done) {
-    sl.compose_pending = true; sl.compose_stream = CS; sl.compose_event = done;
-    ch.done_pending = true; ch.done_stream = CS;
-  } else {
-    sl.compose_pending = false;  // private slot on its own chain: stream order is all it needs
-  }
-  return OFDG_OK;
+// ---- what one render / forward call writes -----------------------------------------------------------
+// The twelve entry points (ofdg_render, ofdg_forward, ofdg_forward_counter; plain, _ex, _fmt, _ex_fmt) differ in how the
+// caller says it; from check_call on a call is this.
+struct CallOut {
+  const char* fn;           // the entry point, for messages
+  void *img0, *img1, *flow; // element types as out_fmt says
+  ofdg_extras_fmt ex;       // the optional outputs (an ofdg_extras is this with float32 occlusion maps); no pointer set: none
+  int out_fmt;              // the compose kernels' bits, kOutImageU8 | kOutFlowF16 (0: float32 throughout)
+};
+static int invalid_argument(ofdg_ctx* c, const char* fn) {
+  if (c) c->err = std::string(fn) + ": invalid argument";
+  return OFDG_EINVAL;
 }
-
-// preparation + compose of the batch resident in `sl`, in order on chain `ch`
-static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, void* d_img0, void* d_img1, void* d_flow,
-                           hipStream_t st, long long cs_first_index = -1, const ofdg_extras_fmt* ex = nullptr, int out_fmt = 0) {
-  // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
-  int rc = launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st);
-  if (rc != OFDG_OK) return rc;
-  return launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex, out_fmt);
-}
-
-// The optional outputs are defined for the rigid modes: checked before anything is enqueued.
 static bool extras_requested(const ofdg_extras_fmt* ex) { return ex && (ex->flow1 || ex->occ0 || ex->occ1 || ex->label0 || ex->label1); }
-// (internally every call carries its optional outputs as an ofdg_extras_fmt; ofdg_extras is that with float32 occlusion maps)
 static ofdg_extras_fmt widen_extras(const ofdg_extras* ex) {
   ofdg_extras_fmt x{};
   if (ex) { x.flow1 = ex->flow1; x.occ0 = ex->occ0; x.occ1 = ex->occ1; x.label0 = ex->label0; x.label1 = ex->label1; }
   x.occ = OFDG_FMT_F32;
   return x;
 }
+// The optional outputs are defined for the rigid modes.
 static int check_extras(ofdg_ctx* c, const ofdg_extras_fmt* ex, const char* fn) {
   if (extras_requested(ex) && c->prm.mode == 9) {
     c->err = std::string(fn) + ": backward flow, labels and occlusion are defined for the rigid modes only (mode 9: the reference's "
@@ -1234,7 +1102,7 @@ static int check_extras_fmt(ofdg_ctx* c, const ofdg_extras_fmt* ex, const char* 
     if (ex->reserved[k] != 0) return fail("reserved[" + std::to_string(k) + "]", ex->reserved[k], "0");
   return check_extras(c, ex, fn);
 }
-// ofdg_out_format -> the compose kernels' out_fmt bits (0: the plain call), checked before anything is enqueued.
+// ofdg_out_format -> the compose kernels' out_fmt bits (0: the plain call)
 static int check_out_format(ofdg_ctx* c, const ofdg_out_format* fmt, const char* fn, int* out_fmt) {
   *out_fmt = 0;
   if (!fmt) return OFDG_OK;
@@ -1248,6 +1116,163 @@ static int check_out_format(ofdg_ctx* c, const ofdg_out_format* fmt, const char*
     if (fmt->reserved[k] != 0) return fail(k ? "reserved[1]" : "reserved[0]", fmt->reserved[k], "0");
   *out_fmt = (fmt->image == OFDG_FMT_U8 ? kOutImageU8 : 0) | (fmt->flow == OFDG_FMT_F16 ? kOutFlowF16 : 0);
   return OFDG_OK;
+}
+// What entry point `fn` received, as a CallOut, before anything is enqueued: its own argument test (`args_ok`; it speaks as
+// `args_fn` where that is given), then the format, then the extras (at most one of ex / exf is given; any of the three may be NULL).
+static int check_call(ofdg_ctx* c, const char* fn, bool args_ok, void* img0, void* img1, void* flow, const ofdg_extras* ex,
+                      const ofdg_extras_fmt* exf, const ofdg_out_format* fmt, CallOut* o, const char* args_fn = nullptr) {
+  if (!args_ok) return invalid_argument(c, args_fn ? args_fn : fn);
+  *o = CallOut{fn, img0, img1, flow, exf ? *exf : widen_extras(ex), 0};
+  OFDG_TRY(check_out_format(c, fmt, fn, &o->out_fmt));
+  return exf ? check_extras_fmt(c, exf, fn) : check_extras(c, &o->ex, fn);
+}
+
+// ---- compose ------------------------------------------------------------------------------------------
+// The optional outputs of one compose launch (rigid modes) as the kernels take them.
+struct ComposeExtras {
+  bool any = false;   // the _ext kernels
+  bool occ = false;   // ... with an occlusion pass behind compose
+  bool fmt = false;   // in a compact format of the outputs or of their own (uint8 maps): compose_rigid_ext_fmt + occlusion_fmt
+  ExtOut xo{nullptr, nullptr, nullptr};       // where compose writes the backward flow and the labels
+  uint32_t *tgt0 = nullptr, *tgt1 = nullptr;  // ... and, `fmt`, its rounded targets for the occlusion pass
+};
+// Where compose writes the backward flow and the labels: the caller's buffers, or the chain's workspace when only the
+// occlusion pass needs them (grown only; growing waits for the device, like reserve_workspaces).
+static int plan_extras(ofdg_ctx* c, ofdg_ctx::Chain& ch, int n_samples, const CallOut& o, ComposeExtras* x) {
+  const ofdg_extras_fmt& ex = o.ex;
+  if (!extras_requested(&ex)) return OFDG_OK;
+  x->any = true;
+  x->occ = ex.occ0 || ex.occ1;
+  x->fmt = o.out_fmt || ex.occ == OFDG_FMT_U8;
+  const size_t plane = (size_t)c->prm.width * c->prm.height, n = (size_t)n_samples;
+  // (with a compact format the occlusion pass reads compose's rounded targets, not flow / flow1: no flow1 workspace)
+  const bool ws_labels = x->occ && (!ex.label0 || !ex.label1), ws_flow1 = !x->fmt && ex.occ1 && !ex.flow1, ws_tgt = x->fmt && x->occ;
+  if ((ws_labels && 2 * n * plane > ch.x_labels.cap) || (ws_flow1 && 2 * n * plane > ch.x_flow1.cap) ||
+      (ws_tgt && 2 * n * plane > ch.x_targets.cap)) {
+    HIP_OK(c, hipDeviceSynchronize());
+    if (ws_labels) HIP_OK(c, ch.x_labels.reserve(2 * n * plane));
+    if (ws_flow1) HIP_OK(c, ch.x_flow1.reserve(2 * n * plane));
+    if (ws_tgt) HIP_OK(c, ch.x_targets.reserve(2 * n * plane));
+  }
+  if (ws_tgt) {  // stored only for the frames whose map is asked for
+    x->tgt0 = ex.occ0 ? ch.x_targets.p : nullptr;
+    x->tgt1 = ex.occ1 ? ch.x_targets.p + n * plane : nullptr;
+  }
+  x->xo.flow1 = ex.flow1 ? static_cast<float*>(ex.flow1) : (ws_flow1 ? ch.x_flow1.p : nullptr);
+  x->xo.label0 = ex.label0 ? ex.label0 : (x->occ ? ch.x_labels.p : nullptr);
+  x->xo.label1 = ex.label1 ? ex.label1 : (x->occ ? ch.x_labels.p + n * plane : nullptr);
+  return OFDG_OK;
+}
+
+// Where compose runs: on the chain's stream, right behind the preparation - or, if the caller passed another stream,
+// on THAT stream (in order with the caller's own work, which may still read the outputs) once the batch is prepared.
+static int compose_stream(ofdg_ctx* c, ofdg_ctx::Chain& ch, hipStream_t st, hipStream_t* cs) {
+  *cs = ch.prep.stream;
+  if (*cs == st) return OFDG_OK;
+  HIP_OK(c, hipStreamWaitEvent(st, ch.ev_prep, 0));
+  *cs = st;
+  return OFDG_OK;
+}
+
+// The compose kernel of the prepared batch on `cs`, and the occlusion pass behind it.  `done` (or null) goes on the packet of
+// the last kernel.
+//   Profiled launches (ev): start and stop are the timestamps of the compose kernel's own dispatch packet.  profiling 1
+//   (compose only, what bench.py runs the timed region with): NO start marker - the compose launch is timed from the
+//   completion of its predecessor on the chain (the last preparation kernel's own packet, ev[4], launch_prepare) to its own
+//   completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
+//   kernel's own start (a marker, ev[4]) and end.
+static int launch_compose_kernels(ofdg_ctx* c, const ofdg_ctx::Chain& ch, const ofdg_ctx::Slot& sl, const CallOut& o, const ComposeExtras& x,
+                                  const uint32_t* fgpool, const uint32_t* bgpool, hipStream_t cs, hipEvent_t done) {
+  const int W = c->prm.width, H = c->prm.height;
+  const RenderDims dm = render_dims(c, sl);
+  const int grid = dm.tiles_x * dm.tiles_y * dm.n_samples * 4;  // one 64 x 4 strip per single-wave workgroup
+  hipEvent_t* const ev = ch.prep.ev;
+  // the variant, decided here once (the optional outputs exist in the rigid modes only: check_extras)
+  enum class Kind { kRigid, kRigidExt, kRigidFmt, kRigidExtFmt, kDeform, kDeformFmt };
+  const Kind kind = c->prm.mode == 9 ? (o.out_fmt ? Kind::kDeformFmt : Kind::kDeform)
+                                     : x.fmt ? Kind::kRigidExtFmt : x.any ? Kind::kRigidExt : o.out_fmt ? Kind::kRigidFmt : Kind::kRigid;
+  const bool pow2 = (W & (W - 1)) == 0;
+  const Launch lc{(unsigned)grid, 64, cs, (ev && c->profiling == 2) ? ev[4] : nullptr, ev ? ev[5] : (x.occ ? nullptr : done)};
+  // every family has a _pow2 and a general kernel of one function type: this is the one place a compose kernel is launched
+  auto compose = [&](auto* k_pow2, auto* k, auto... args) { launch_kernel(lc, pow2 ? k_pow2 : k, args...); };
+  auto rigid = [&](auto* k_pow2, auto* k, auto... tail) {
+    compose(k_pow2, k, sl.d_samples.p, ch.prep.box_cur, sl.d_objects.p, ch.cov.p, grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch,
+            dm.fg_pitch, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p, sl.d_item_count, tail...);
+  };
+  auto deform = [&](auto* k_pow2, auto* k, auto... tail) {
+    compose(k_pow2, k, dm, sl.d_samples.p, sl.d_objects.p, ch.prep.box_cur, ch.cov.p, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p,
+            ch.prep.croptab, sl.d_item_count, tail...);
+  };
+  switch (kind) {
+    case Kind::kRigid: rigid(compose_rigid_pow2_kernel, compose_rigid_kernel); break;
+    case Kind::kRigidExt: rigid(compose_rigid_ext_pow2_kernel, compose_rigid_ext_kernel, x.xo); break;
+    case Kind::kRigidFmt: rigid(compose_rigid_fmt_pow2_kernel, compose_rigid_fmt_kernel, o.out_fmt); break;
+    case Kind::kRigidExtFmt: rigid(compose_rigid_ext_fmt_pow2_kernel, compose_rigid_ext_fmt_kernel, x.xo, o.out_fmt, x.tgt0, x.tgt1); break;
+    case Kind::kDeform: deform(compose_deform_pow2_kernel, compose_deform_kernel); break;
+    case Kind::kDeformFmt: deform(compose_deform_fmt_pow2_kernel, compose_deform_fmt_kernel, o.out_fmt); break;
+  }
+  HIP_OK(c, hipGetLastError());
+  if (x.occ) {  // behind compose on the same stream; the chain's completion event (workspace, slot) goes on THIS packet
+    const long long quads = (long long)dm.n_samples * H * (W / 4);
+    const Launch lo{(unsigned)((quads + 255) / 256), 256, cs, nullptr, ev ? nullptr : done};
+    if (x.fmt)
+      launch_kernel(lo, occlusion_fmt_kernel, x.tgt0, x.tgt1, x.xo.label0, x.xo.label1, o.ex.occ0, o.ex.occ1, W, H, dm.n_samples,
+                    o.ex.occ == OFDG_FMT_U8 ? kOutOccU8 : 0);
+    else
+      launch_kernel(lo, occlusion_kernel, o.flow, x.xo.flow1, x.xo.label0, x.xo.label1, o.ex.occ0, o.ex.occ1, W, H, dm.n_samples);
+    HIP_OK(c, hipGetLastError());
+  }
+  return OFDG_OK;
+}
+
+// What a compose launch leaves behind on the host: the profiled launch's event set, and who has to wait for it.
+static int note_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, hipStream_t cs, bool foreign, hipEvent_t done) {
+  if (hipEvent_t* const ev = ch.prep.ev) {
+    if (done) HIP_OK(c, hipEventRecord(done, cs));
+    // profiling 1 times compose from the completion of the chain's last preparation kernel: that is the launch's time only
+    // when compose is enqueued right behind it on the same stream.  A batch prepared ahead by an earlier call, or composed
+    // on a caller's stream behind the hand-over event, would count host and queue idle time: such a set is not a sample.
+    const bool span_is_the_launch = c->profiling == 2 || (!foreign && !ch.prep.ahead);
+    if (span_is_the_launch) {
+      c->ev_count++;
+      c->ev_composed[(size_t)(ev - c->ev.data()) / 6] = 1;
+    }
+  }
+  if (done) track_completion(sl, ch, cs, done);
+  else sl.compose_pending = false;  // private slot on its own chain: stream order is all it needs
+  return OFDG_OK;
+}
+
+// compose of the batch chain `ch` has prepared, into what `o` (checked) describes.  `st` is the caller's stream: if it is
+// not the chain's own stream (ofdg_stream), compose runs on `st` instead, behind what the caller enqueued there (the outputs
+// may still be read) and behind the chain's preparation kernels.
+static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, const CallOut& o, hipStream_t st) {
+  if (!ch.prep.valid) { c->err = "internal: compose without a prepared batch"; return OFDG_EINVAL; }
+  ofdg_ctx::Slot& sl = *ch.prep.slot;
+  ComposeExtras x;
+  OFDG_TRY(plan_extras(c, ch, sl.res_samples, o, &x));
+  const uint32_t* bgpool = c->prm.background_prep ? sl.d_bgtex.p : (c->pool_bg ? c->pool_bg : c->pool);  // (after the slot's buffers are final)
+  const uint32_t* fgpool = c->pool_fg ? c->pool_fg : c->pool;
+  if (c->prm.background_prep && !bgpool) { c->err = "background_prep: the slot has no prepared backgrounds"; return OFDG_EINVAL; }
+  c->last_slot = &sl; c->last_ch = &ch;
+  c->last_stream = ch.prep.stream; c->last_ticket = ch.prep.ticket;
+  ch.prep.valid = false;  // (consumed from here on; an argument error above leaves it to discard_prepared, which resets the work list)
+  const bool foreign = ch.prep.stream != st;  // the caller's stream is not the chain's
+  hipStream_t cs;
+  OFDG_TRY(compose_stream(c, ch, st, &cs));
+  // It is tracked by the chain's event whenever somebody else may have to wait for it: the chain itself (workspace, private
+  // slot) after a compose on a caller's stream, other chains for a shared slot.
+  const bool shared_slot = &sl != &ch.slot;
+  const hipEvent_t done = (foreign || shared_slot) ? ch.ev_done : nullptr;
+  OFDG_TRY(launch_compose_kernels(c, ch, sl, o, x, fgpool, bgpool, cs, done));
+  return note_compose(c, ch, sl, cs, foreign, done);
+}
+
+// preparation + compose of the batch resident in `sl`, in order on chain `ch`
+static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, const CallOut& o, hipStream_t st, long long cs_first_index = -1) {
+  // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
+  OFDG_TRY(launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st));
+  return launch_compose(c, ch, o, st);
 }
 
 // CImg get_resize(.., 3), enlarging branch: source index and weight of every destination pixel (running double sums,
@@ -1299,8 +1324,7 @@ static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool reco
   const bool staged = c->prm.background_prep == 1;
   constexpr int kBgPrepBlocks = 192;  // x 256 threads per sample, grid-stride over the (device-known) region
   if (staged) {
-    int rct = ensure_bgprep_tables(c);
-    if (rct != OFDG_OK) return rct;
+    OFDG_TRY(ensure_bgprep_tables(c));
   }
   if (!staged) {
     hipExtLaunchKernelGGL(bgprep_kernel, dim3((W * H + 255) / 256, n), dim3(256), 0, s, nullptr, stop, 0, sl.d_bgprep.p, W, H, sl.d_bgtex.p);
@@ -1328,8 +1352,8 @@ static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool reco
 static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps,
                        int n_bps, hipStream_t st, ofdg_ctx::Stage& stage, bool shared) {
   if (!c->pool && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
-  { int rcf = finalise_pool(c); if (rcf != OFDG_OK) return rcf; }
-  { int rct = ensure_tex_table(c); if (rct != OFDG_OK) return rct; }
+  OFDG_TRY(finalise_pool(c));
+  OFDG_TRY(ensure_tex_table(c));
   RealizeConfig cfg{c->prm.width, c->prm.height, c->prm.mode, c->pool_n, c->pool_w, c->pool_h, c->prm.background_prep};
   cfg.pool_addr = (uint64_t)(uintptr_t)c->pool;
   cfg.tex_table = c->pool_mixed && c->prm.background_prep ? c->tex_table.data() : nullptr;
@@ -1345,8 +1369,7 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
     sl.compose_pending = false;
   }
   sl.res_samples = 0;
-  int rc = realize_batch(cfg, tasks, n_tasks, bps, n_bps, &sl.batch, &c->err, &c->crop_server);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(realize_batch(cfg, tasks, n_tasks, bps, n_bps, &sl.batch, &c->err, &c->crop_server));
   const RealizedBatch& B = sl.batch;
   const size_t n_shapes = B.shapes.size(), n_obj = B.objects.size();
   // the batch's records - shapes | objects | samples - travel as ONE copy into one allocation (three copies cost the host
@@ -1367,9 +1390,9 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
   HIP_OK(c, sl.d_verts.reserve(n_shapes * 2 * kMaxVerts));
   {
     const int W = c->prm.width, H = c->prm.height;
-    { int rcw = reserve_workspaces(c, n_shapes); if (rcw != OFDG_OK) return rcw; }
+    OFDG_TRY(reserve_workspaces(c, n_shapes));
     HIP_OK(c, sl.d_items.reserve(n_shapes * 2 * (size_t)((H + kBandRows - 1) / kBandRows) * ((W + kChunkW - 1) / kChunkW) + 1));
-    { int rcm = reserve_blockmask(c, sl, n_tasks); if (rcm != OFDG_OK) return rcm; }
+    OFDG_TRY(reserve_blockmask(c, sl, n_tasks));
     if (!sl.d_item_count) {
       HIP_OK(c, hipMalloc((void**)&sl.d_item_count, sizeof(int)));
       HIP_OK(c, hipMemset(sl.d_item_count, 0, sizeof(int)));
@@ -1398,7 +1421,7 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
       HIP_OK(c, sl.d_bgwarp.reserve(n_bg * bg_floats));
       HIP_OK(c, sl.d_bgwarp_max.reserve(n_bg));
       HIP_OK(c, hipMemsetAsync(sl.d_bgwarp_max.p, 0, n_bg * sizeof(unsigned), st));
-      { int rct = ensure_resize_tables(c); if (rct != OFDG_OK) return rct; }
+      OFDG_TRY(ensure_resize_tables(c));
     }
     std::vector<DevCropRef> tab(B.crops.size());
     size_t bg_at = 0;
@@ -1423,8 +1446,7 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
     if (shared) {  // a caller's slot is prepared once, here, and rendered any number of times
       // (flags go into the word of the call that renders this batch next; that call must not clear them: word_reserved)
       if (c->word_reserved != c->ticket) { HIP_OK(c, take_err_word(c, c->ticket, st)); c->word_reserved = c->ticket; }
-      int rcb = prepare_backgrounds(c, sl, n_tasks, /*records_resident=*/true, st, err_word(c, c->ticket));
-      if (rcb != OFDG_OK) return rcb;
+      OFDG_TRY(prepare_backgrounds(c, sl, n_tasks, /*records_resident=*/true, st, err_word(c, c->ticket)));
       sl.bgprep_pending = false;
     } else {
       sl.bgprep_pending = true;  // (a chain's private slot: behind raster, launch_prepare)
@@ -1446,78 +1468,67 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
   return OFDG_OK;
 }
 
+// ofdg_render / _ex / _fmt / _ex_fmt: the batch's records travel on the chain's own stream into its private slot
+static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps, const CallOut& o, void* stream) {
+  stream = own_stream(c, stream);
+  ofdg_ctx::Chain& ch = take_chain(c);
+  OFDG_TRY(upload_slot(c, ch.slot, tasks, n_tasks, bps, n_bps, chain_stream(c, ch, (hipStream_t)stream), ch.stage, false));
+  return launch_resident(c, ch, ch.slot, o, (hipStream_t)stream);
+}
+static bool render_args_ok(const ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, const void* d_img0,
+                           const void* d_img1, const void* d_flow) {
+  return c && tasks && bps && n_tasks >= 1 && d_img0 && d_img1 && d_flow;
+}
 int ofdg_render(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                 float* d_img0, float* d_img1, float* d_flow, void* stream) {
-  return ofdg_render_ex(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, stream);
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_render", render_args_ok(c, tasks, n_tasks, bps, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, nullptr, nullptr, &o));
+  return render_impl(c, tasks, n_tasks, bps, n_bps, o, stream);
 }
-// ofdg_render / _ex / _fmt: `ex` and `fmt` are already checked; out_fmt as for launch_compose
-static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
-                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream);
 int ofdg_render_ex(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                    float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
-  if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
-    if (c) c->err = "ofdg_render: invalid argument";
-    return OFDG_EINVAL;
-  }
-  const ofdg_extras_fmt x = widen_extras(ex);
-  { int rcx = check_extras(c, &x, "ofdg_render_ex"); if (rcx != OFDG_OK) return rcx; }
-  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
-}
-int ofdg_render_ex_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
-                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
-  if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
-    if (c) c->err = "ofdg_render_ex_fmt: invalid argument";
-    return OFDG_EINVAL;
-  }
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_render_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  { int rcx = check_extras_fmt(c, ex, "ofdg_render_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
-  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, ex, out_fmt, stream);
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_render_ex", render_args_ok(c, tasks, n_tasks, bps, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, ex, nullptr, nullptr, &o, /*args_fn=*/"ofdg_render"));  // (as it always has)
+  return render_impl(c, tasks, n_tasks, bps, n_bps, o, stream);
 }
 int ofdg_render_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                     void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
-  if (!c || !tasks || !bps || n_tasks < 1 || !d_img0 || !d_img1 || !d_flow) {
-    if (c) c->err = "ofdg_render_fmt: invalid argument";
-    return OFDG_EINVAL;
-  }
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_render_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  return render_impl(c, tasks, n_tasks, bps, n_bps, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_render_fmt", render_args_ok(c, tasks, n_tasks, bps, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, nullptr, fmt, &o));
+  return render_impl(c, tasks, n_tasks, bps, n_bps, o, stream);
 }
-static int render_impl(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
-                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
-  stream = own_stream(c, stream);
-  // the batch's records travel on the chain's own stream into its private slot
-  ofdg_ctx::Chain& ch = take_chain(c);
-  int rc = upload_slot(c, ch.slot, tasks, n_tasks, bps, n_bps, chain_stream(c, ch, (hipStream_t)stream), ch.stage, false);
-  if (rc != OFDG_OK) return rc;
-  return launch_resident(c, ch, ch.slot, d_img0, d_img1, d_flow, (hipStream_t)stream, -1, ex, out_fmt);
+int ofdg_render_ex_fmt(ofdg_ctx* c, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
+                       void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_render_ex_fmt", render_args_ok(c, tasks, n_tasks, bps, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, ex, fmt, &o));
+  return render_impl(c, tasks, n_tasks, bps, n_bps, o, stream);
 }
 
 int ofdg_upload_slot(ofdg_ctx* c, int slot, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps, int n_bps,
                      void* stream) {
-  if (!c || !tasks || !bps || n_tasks < 1 || slot < 0 || slot >= ofdg_ctx::kUserSlots) {
-    if (c) c->err = "ofdg_upload_slot: invalid argument";
-    return OFDG_EINVAL;
-  }
+  if (!c || !tasks || !bps || n_tasks < 1 || slot < 0 || slot >= ofdg_ctx::kUserSlots) return invalid_argument(c, "ofdg_upload_slot");
   return upload_slot(c, c->slots[slot], tasks, n_tasks, bps, n_bps, (hipStream_t)stream, c->user_stage, true);
 }
 
 int ofdg_render_slot(ofdg_ctx* c, int slot, float* d_img0, float* d_img1, float* d_flow, void* stream) {
-  if (!c || !d_img0 || !d_img1 || !d_flow || slot < 0 || slot >= ofdg_ctx::kUserSlots) return OFDG_EINVAL;
+  if (!c || !d_img0 || !d_img1 || !d_flow || slot < 0 || slot >= ofdg_ctx::kUserSlots) return invalid_argument(c, "ofdg_render_slot");
   if (c->slots[slot].res_samples <= 0) { c->err = "ofdg_render_slot: no batch is resident in this slot"; return OFDG_EINVAL; }
   stream = own_stream(c, stream);
-  return launch_resident(c, take_chain(c), c->slots[slot], d_img0, d_img1, d_flow, (hipStream_t)stream);
+  return launch_resident(c, take_chain(c), c->slots[slot], CallOut{"ofdg_render_slot", d_img0, d_img1, d_flow, {}, 0}, (hipStream_t)stream);
 }
 
 int ofdg_render_resident(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
-  if (!c || !d_img0 || !d_img1 || !d_flow) return OFDG_EINVAL;
+  if (!c || !d_img0 || !d_img1 || !d_flow) return invalid_argument(c, "ofdg_render_resident");
   if (!c->last_slot || c->last_slot->res_samples <= 0) { c->err = "ofdg_render_resident: nothing has been rendered yet"; return OFDG_EINVAL; }
   stream = own_stream(c, stream);
   // a chain's private slot is not tracked by events while only that chain uses it: let its owner drain first
   for (int k = 0; k < c->n_chains; ++k)
     if (&c->chains[k].slot == c->last_slot && !c->last_slot->compose_pending) HIP_OK(c, hipStreamSynchronize(c->chains[k].stream));
-  return launch_resident(c, take_chain(c), *c->last_slot, d_img0, d_img1, d_flow, (hipStream_t)stream);
+  return launch_resident(c, take_chain(c), *c->last_slot, CallOut{"ofdg_render_resident", d_img0, d_img1, d_flow, {}, 0}, (hipStream_t)stream);
 }
 
 // The per-object annotation table of the batch the last render / forward call composed (c->last_slot): two small kernels on
@@ -1563,10 +1574,7 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
                           st, nullptr, done, 0, sl.d_samples.p, d_label0, d_label1, W, H, rows_per_sample, rows);
     HIP_OK(c, hipGetLastError());
   }
-  if (tracked) {
-    sl.compose_pending = true; sl.compose_stream = st; sl.compose_event = done;
-    ch.done_pending = true; ch.done_stream = st;
-  }
+  if (tracked) track_completion(sl, ch, st, done);
   return OFDG_OK;
 }
 
@@ -1619,9 +1627,9 @@ int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
 static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
-  if (c->prm.mode == 9) { int rcw = ensure_counter_croptab(c); if (rcw != OFDG_OK) return rcw; }
-  { int rcf = finalise_pool(c); if (rcf != OFDG_OK) return rcf; }
-  { int rct = ensure_tex_table(c); if (rct != OFDG_OK) return rct; }
+  if (c->prm.mode == 9) OFDG_TRY(ensure_counter_croptab(c));
+  OFDG_TRY(finalise_pool(c));
+  OFDG_TRY(ensure_tex_table(c));
   if (!c->pool && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
   if (n < 1 || n > 512) { c->err = "counter sampler: batch must be 1..512 samples"; return OFDG_EINVAL; }
   const int W = c->prm.width, H = c->prm.height;
@@ -1634,9 +1642,9 @@ static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
   HIP_OK(c, sl.d_verts.reserve(shapes_cap * 2 * kMaxVerts));
   HIP_OK(c, sl.d_objects.reserve(n_obj));
   HIP_OK(c, sl.d_samples.reserve(n));
-  { int rcw = reserve_workspaces(c, shapes_cap); if (rcw != OFDG_OK) return rcw; }
+  OFDG_TRY(reserve_workspaces(c, shapes_cap));
   HIP_OK(c, sl.d_items.reserve(shapes_cap * 2 * (size_t)((H + kBandRows - 1) / kBandRows) * ((W + kChunkW - 1) / kChunkW) + 1));
-  { int rcm = reserve_blockmask(c, sl, n); if (rcm != OFDG_OK) return rcm; }
+  OFDG_TRY(reserve_blockmask(c, sl, n));
   if (c->prm.background_prep) {
     HIP_OK(c, sl.d_bgprep.reserve(n));
     HIP_OK(c, sl.d_bgtex.reserve((size_t)n * 4 * W * H));
@@ -1655,36 +1663,7 @@ static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
 
 // Sample n_samples blueprints with global indices first_index.. on the DEVICE (counter
 // sampler: a sample is a pure function of (seed, global index)) and render them.
-int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
-                         void* stream) {
-  return ofdg_forward_counter_ex(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, stream);
-}
-static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                                const ofdg_extras_fmt* ex, int out_fmt, void* stream);
-int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
-                            const ofdg_extras* ex, void* stream) {
-  if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
-  const ofdg_extras_fmt x = widen_extras(ex);
-  { int rcx = check_extras(c, &x, "ofdg_forward_counter_ex"); if (rcx != OFDG_OK) return rcx; }
-  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
-}
-int ofdg_forward_counter_ex_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                                const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
-  if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_forward_counter_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  { int rcx = check_extras_fmt(c, ex, "ofdg_forward_counter_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
-  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, ex, out_fmt, stream);
-}
-int ofdg_forward_counter_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                             const ofdg_out_format* fmt, void* stream) {
-  if (!c || !d_img0 || !d_img1 || !d_flow || first_index < 0) return OFDG_EINVAL;
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_forward_counter_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  return forward_counter_impl(c, first_index, n_samples, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
-}
-static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
-                                const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
+static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_samples, const CallOut& o, void* stream) {
   stream = own_stream(c, stream);
   // A sample is a pure function of (seed, global index): the chain samples, realises and prepares the batch on the device
   // and composes it, all in order on its stream.  Like the reference's prefetch thread (data_generation_layer.cpp:141-172)
@@ -1697,14 +1676,11 @@ static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_sample
   hipStream_t st = (hipStream_t)stream;
   auto prepare_on = [&](ofdg_ctx::Chain& cj, long long first, hipStream_t s_, bool hand_over) -> int {
     if (cj.prep.valid && cj.prep.slot == &cj.slot && cj.prep.first_index == first && cj.prep.n == n_samples) return OFDG_OK;
-    int rc = prepare_counter_slot(c, cj.slot, n_samples);
-    if (rc != OFDG_OK) return rc;
+    OFDG_TRY(prepare_counter_slot(c, cj.slot, n_samples));
     return launch_prepare(c, cj, cj.slot, s_, first, hand_over);
   };
-  int rc = prepare_on(ch, first_index, st, chain_stream(c, ch, st) != st);
-  if (rc != OFDG_OK) return rc;
-  rc = launch_compose(c, ch, d_img0, d_img1, d_flow, st, ex, out_fmt);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(prepare_on(ch, first_index, st, chain_stream(c, ch, st) != st));
+  OFDG_TRY(launch_compose(c, ch, o, st));
   // (the caller's batch is composed: from here on the call has succeeded, whatever happens to the batches prepared ahead)
   const long long prev_first = c->last_first;
   c->last_first = first_index;
@@ -1720,6 +1696,38 @@ static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_sample
     }
   }
   return OFDG_OK;
+}
+
+static bool forward_counter_args_ok(const ofdg_ctx* c, long long first_index, const void* d_img0, const void* d_img1, const void* d_flow) {
+  return c && d_img0 && d_img1 && d_flow && first_index >= 0;
+}
+int ofdg_forward_counter(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
+                         void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_counter", forward_counter_args_ok(c, first_index, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, nullptr, nullptr, &o));
+  return forward_counter_impl(c, first_index, n_samples, o, stream);
+}
+int ofdg_forward_counter_ex(ofdg_ctx* c, long long first_index, int n_samples, float* d_img0, float* d_img1, float* d_flow,
+                            const ofdg_extras* ex, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_counter_ex", forward_counter_args_ok(c, first_index, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, ex, nullptr, nullptr, &o));
+  return forward_counter_impl(c, first_index, n_samples, o, stream);
+}
+int ofdg_forward_counter_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                             const ofdg_out_format* fmt, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_counter_fmt", forward_counter_args_ok(c, first_index, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, nullptr, fmt, &o));
+  return forward_counter_impl(c, first_index, n_samples, o, stream);
+}
+int ofdg_forward_counter_ex_fmt(ofdg_ctx* c, long long first_index, int n_samples, void* d_img0, void* d_img1, void* d_flow,
+                                const ofdg_extras_fmt* ex, const ofdg_out_format* fmt, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_counter_ex_fmt", forward_counter_args_ok(c, first_index, d_img0, d_img1, d_flow),
+                      d_img0, d_img1, d_flow, nullptr, ex, fmt, &o));
+  return forward_counter_impl(c, first_index, n_samples, o, stream);
 }
 
 // The internal stream the NEXT render / forward call of this context works on (the chains take turns).
@@ -1763,59 +1771,53 @@ long long ofdg_shard_first_index(long long step, int batch, int world_size, int 
   return step * (long long)batch * world_size + (long long)rank * batch;
 }
 
-int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
-  return ofdg_forward_ex(c, d_img0, d_img1, d_flow, nullptr, stream);
-}
-static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream);
-int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
-  if (!c) return OFDG_EINVAL;
-  const ofdg_extras_fmt x = widen_extras(ex);
-  { int rcx = check_extras(c, &x, "ofdg_forward_ex"); if (rcx != OFDG_OK) return rcx; }
-  return forward_impl(c, d_img0, d_img1, d_flow, ex ? &x : nullptr, 0, stream);
-}
-int ofdg_forward_ex_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt,
-                        void* stream) {
-  if (!c) return OFDG_EINVAL;
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_forward_ex_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  { int rcx = check_extras_fmt(c, ex, "ofdg_forward_ex_fmt"); if (rcx != OFDG_OK) return rcx; }
-  return forward_impl(c, d_img0, d_img1, d_flow, ex, out_fmt, stream);
-}
-int ofdg_forward_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
-  if (!c) return OFDG_EINVAL;
-  int out_fmt;
-  { int rcf = check_out_format(c, fmt, "ofdg_forward_fmt", &out_fmt); if (rcf != OFDG_OK) return rcf; }
-  return forward_impl(c, d_img0, d_img1, d_flow, nullptr, out_fmt, stream);
-}
-static int forward_impl(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, int out_fmt, void* stream) {
+// ofdg_forward / _ex / _fmt / _ex_fmt: the next batch_size samples of this rank's share of the stream.  The output pointers
+// are tested here, behind the format and the extras: a failed call leaves the step counter (and the streams) where they were.
+static int forward_impl(ofdg_ctx* c, const CallOut& o, void* stream) {
+  const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
+  if (B < 1 || rank < 0 || rank >= world) { c->err = "ofdg_forward: bad batch_size / rank"; return OFDG_EINVAL; }
+  const bool outputs = o.img0 && o.img1 && o.flow;
+  int rc = OFDG_EINVAL;
   if (c->prm.sampler == OFDG_SAMPLER_COUNTER) {
     // rank r owns global indices step*B*world + r*B + [0, B)
-    const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
-    if (B < 1 || rank < 0 || rank >= world) { c->err = "ofdg_forward: bad batch_size / rank"; return OFDG_EINVAL; }
     const long long first = ofdg_shard_first_index(c->step, B, world, rank);
-    if (!d_img0 || !d_img1 || !d_flow || first < 0) return OFDG_EINVAL;
-    const int rc = forward_counter_impl(c, first, B, d_img0, d_img1, d_flow, ex, out_fmt, stream);
+    if (!outputs || first < 0) return invalid_argument(c, o.fn);
+    rc = forward_counter_impl(c, first, B, o, stream);
     if (rc == OFDG_OK) c->step++;  // (a failed call does not advance the checkpoint counter)
     return rc;
   }
-  const int B = c->prm.batch_size, world = c->prm.world_size, rank = c->prm.rank;
-  if (B < 1 || rank < 0 || rank >= world) { c->err = "ofdg_forward: bad batch_size / rank"; return OFDG_EINVAL; }
   // every rank walks the identical sequential stream and keeps its own block of
   // B consecutive tasks out of each B*world (disjoint shards, no communication)
   c->fw_bps.clear();
   c->fw_tasks.assign((size_t)B * world, ofdg_task());
-  for (int i = 0; i < B * world; ++i) {
-    int rc = c->sampler->next_task(&c->fw_bps, &c->fw_tasks[i], &c->err);
-    if (rc != OFDG_OK) return rc;
-  }
-  int rc = OFDG_EINVAL;
-  if (!d_img0 || !d_img1 || !d_flow) c->err = "ofdg_render: invalid argument";
-  else rc = render_impl(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), d_img0, d_img1, d_flow, ex,
-                        out_fmt, stream);
+  for (int i = 0; i < B * world; ++i) OFDG_TRY(c->sampler->next_task(&c->fw_bps, &c->fw_tasks[i], &c->err));
+  if (!outputs) c->err = "ofdg_render: invalid argument";
+  else rc = render_impl(c, c->fw_tasks.data() + (size_t)rank * B, B, c->fw_bps.data(), (int)c->fw_bps.size(), o, stream);
   // the streams have moved on either way; the batch counts once it is in flight
   if (rc == OFDG_OK) c->step++;
   else ofdg_set_step(c, c->step);  // rewind the streams (and the crop server) to the start of this batch
   return rc;
+}
+int ofdg_forward(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward", c != nullptr, d_img0, d_img1, d_flow, nullptr, nullptr, nullptr, &o));
+  return forward_impl(c, o, stream);
+}
+int ofdg_forward_ex(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flow, const ofdg_extras* ex, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_ex", c != nullptr, d_img0, d_img1, d_flow, ex, nullptr, nullptr, &o));
+  return forward_impl(c, o, stream);
+}
+int ofdg_forward_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_out_format* fmt, void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_fmt", c != nullptr, d_img0, d_img1, d_flow, nullptr, nullptr, fmt, &o));
+  return forward_impl(c, o, stream);
+}
+int ofdg_forward_ex_fmt(ofdg_ctx* c, void* d_img0, void* d_img1, void* d_flow, const ofdg_extras_fmt* ex, const ofdg_out_format* fmt,
+                        void* stream) {
+  CallOut o;
+  OFDG_TRY(check_call(c, "ofdg_forward_ex_fmt", c != nullptr, d_img0, d_img1, d_flow, nullptr, ex, fmt, &o));
+  return forward_impl(c, o, stream);
 }
 
 // Checkpoint / resume of ofdg_forward (the reference has none: a restarted job replays its streams from the
@@ -1836,8 +1838,7 @@ int ofdg_set_step(ofdg_ctx* c, long long step) {
     if (crops) { c->crop_server.head = 0; c->crop_server.counter = 0; }
     for (long long i = 0; i < n; ++i) {
       bps.clear();
-      int rc = c->sampler->next_task(&bps, &t, &c->err);
-      if (rc != OFDG_OK) return rc;
+      OFDG_TRY(c->sampler->next_task(&bps, &t, &c->err));
       if (crops && (i / B) % world == rank) {  // realize_batch serves one crop per deforming background / object
         if (bps[t.background].do_warpfield_deformation) (void)c->crop_server.get();
         for (int k = 0; k < t.n_objects; ++k)
@@ -1895,8 +1896,7 @@ static int poll_words(ofdg_ctx* c, int first, int n, uint32_t* flags) {
 int ofdg_poll_errors(ofdg_ctx* c) {
   if (!c) return OFDG_EINVAL;
   uint32_t e = 0;
-  int rc = poll_words(c, 0, ofdg_ctx::kErrWords, &e);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(poll_words(c, 0, ofdg_ctx::kErrWords, &e));
   if (e) { c->err = err_text(e); return OFDG_ECAPACITY; }
   return OFDG_OK;
 }
@@ -1910,8 +1910,7 @@ int ofdg_poll_errors_of(ofdg_ctx* c, long long ticket) {
   if (ticket < 0 || ticket >= c->ticket || ticket + ofdg_ctx::kErrWords <= c->ticket) { c->err = "ofdg_poll_errors_of: no such batch (tickets of the last " + std::to_string(ofdg_ctx::kErrWords) + " calls are kept)"; return OFDG_EINVAL; }
   uint32_t e = 0;
   c->asked_by_ticket = true;
-  int rc = poll_words(c, (int)(ticket % ofdg_ctx::kErrWords), 1, &e);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(poll_words(c, (int)(ticket % ofdg_ctx::kErrWords), 1, &e));
   c->word_clean[(size_t)(ticket % ofdg_ctx::kErrWords)] = true;  // (read and cleared; the caller waited for this batch before asking)
   if (e) { c->err = "batch " + std::to_string(ticket) + ": " + err_text(e); return OFDG_ECAPACITY; }
   return OFDG_OK;
@@ -1937,15 +1936,14 @@ static int warp_alloc(ofdg_ctx* c, int n_crops) {
 // 17 times with themselves (x 2^17), cleaned, and cut into (W+1) x (H+1) crops.
 int ofdg_warp_generate(ofdg_ctx* c, int n_fields, uint32_t seed) {
   if (!c || n_fields < 1) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   const int W = c->prm.width, H = c->prm.height;
   const int S = std::max(W, H) * 3;
   std::vector<std::pair<int, int>> org;  // crop grid (WF:617-633)
   for (int y = H / 4; y < S - 5 * H / 4; y += H / 3)
     for (int x = W / 4; x < S - 5 * W / 4; x += W / 3) org.push_back({x, y});
   if (org.empty()) { c->err = "frame too small for warp crops"; return OFDG_EINVAL; }
-  int rc = warp_alloc(c, n_fields * (int)org.size());
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(warp_alloc(c, n_fields * (int)org.size()));
   const size_t n = (size_t)S * S;
   float *fa = nullptr, *fb = nullptr;
   uint8_t* flagged = nullptr;
@@ -1985,9 +1983,8 @@ int ofdg_warp_generate(ofdg_ctx* c, int n_fields, uint32_t seed) {
 // Install caller-provided crops: n x 4 planes (flow x, flow y, iflow x, iflow y) of (H+1)*(W+1) floats.
 int ofdg_warp_upload(ofdg_ctx* c, const float* crops, int n) {
   if (!c || !crops || n < 1) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }  // (batches prepared ahead read the old pool / crops)
-  int rc = warp_alloc(c, n);
-  if (rc != OFDG_OK) return rc;
+  OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
+  OFDG_TRY(warp_alloc(c, n));
   const size_t plane = (size_t)(c->prm.width + 1) * (c->prm.height + 1), crop_floats = 4 * plane;
   {  // the kernels read a crop as two planes of interleaved pairs: (flow x, flow y), (iflow x, iflow y)
     std::vector<float> il((size_t)n * crop_floats);
@@ -2086,7 +2083,7 @@ static int debug_rasterize_verts(ofdg_ctx* c, const std::vector<int2>& v, int n,
 
 int ofdg_debug_rasterize(ofdg_ctx* c, const double* xy, int n, uint8_t* coverage_host) {
   if (!c || !xy || !coverage_host || n < 1 || n > kMaxVerts) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }
+  OFDG_TRY(discard_all_prepared(c));
   std::vector<int2> v(kMaxVerts);
   for (int i = 0; i < n; ++i) v[i] = make_int2(iround_h(xy[2 * i] * 256.0), iround_h(xy[2 * i + 1] * 256.0));
   return debug_rasterize_verts(c, v, n, coverage_host);
@@ -2096,7 +2093,7 @@ int ofdg_debug_rasterize(ofdg_ctx* c, const double* xy, int n, uint8_t* coverage
 // move_to vertex) through the DEVICE's flattening (path_verts / flatten_curve3, what geom_kernel runs) and rasteriser.
 int ofdg_debug_rasterize_path(ofdg_ctx* c, const double* xy, const int* types, int n, uint8_t* coverage_host) {
   if (!c || !xy || !types || !coverage_host || n < 1 || n > 64) return OFDG_EINVAL;
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }
+  OFDG_TRY(discard_all_prepared(c));
   HIP_OK(c, hipDeviceSynchronize());
   double* d_xy = nullptr; int* d_ty = nullptr; int2* d_v = nullptr; int* d_n = nullptr;
   HIP_OK(c, hipMalloc((void**)&d_xy, sizeof(double) * 2 * n));
@@ -2210,7 +2207,7 @@ int ofdg_debug_bgprep_paths(ofdg_ctx* c, unsigned* counts9) {
 int ofdg_set_profiling(ofdg_ctx* c, int mode) {
   if (!c || mode < 0 || mode > 2) return OFDG_EINVAL;
   HIP_OK(c, hipDeviceSynchronize());
-  { int rcd = discard_all_prepared(c); if (rcd != OFDG_OK) return rcd; }
+  OFDG_TRY(discard_all_prepared(c));
   HIP_OK(c, hipDeviceSynchronize());
   c->profiling = mode;
   c->ev_count = 0; c->ev_alloc = 0;
