@@ -19,6 +19,7 @@
 
 #include "../../include/ofdg_detmath.h"
 #include "ofdg_device.h"
+#include "realize.h"  // mat_invert
 #include "warpfields.h"
 
 namespace ofdg {
@@ -33,17 +34,6 @@ __device__ __forceinline__ void xform(const Mat& m, double& x, double& y) {  // 
   double t = x;
   x = t * m.sx + y * m.shx + m.tx;
   y = t * m.shy + y * m.sy + m.ty;
-}
-// trans_affine::invert (AGG 2.4), the operation order of realize.h:mat_invert (built with -ffp-contract=off: bit-identical)
-__device__ __forceinline__ Mat d_inv(const Mat& a) {
-  Mat r;
-  const double d = 1.0 / (a.sx * a.sy - a.shy * a.shx);
-  const double t0 = a.sy * d;
-  r.sy = a.sx * d; r.shy = -a.shy * d; r.shx = -a.shx * d;
-  const double t4 = -a.tx * t0 - a.ty * r.shx;
-  r.ty = -a.tx * r.shy - a.ty * r.sy;
-  r.sx = t0; r.tx = t4;
-  return r;
 }
 // floor(a / b) for b > 0, |a| < 2^52: fp64 quotient + exact integer correction.
 __device__ __forceinline__ long long floordiv64(long long a, long long b) {
@@ -1302,7 +1292,7 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
   float fu1[kPx], fv1[kPx];
   uint32_t lab0 = 0, lab1 = 0;
   if constexpr (kExtra) {
-    const Mat bi = d_inv(smp.bg_motion);
+    const Mat bi = mat_invert(smp.bg_motion);
     const double by = (double)(y + H / 2) + (double)(-H);
 #pragma unroll
     for (int p = 0; p < kPx; ++p) {

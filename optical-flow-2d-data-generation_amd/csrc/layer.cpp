@@ -677,7 +677,7 @@ int ofdg_layer_forward(ofdg_layer* L, float** image0, float** image1, float** fl
 int ofdg_host_bg_prep(int pool_w, int pool_h, int width, int height, float angle, float zoom, int shift_x, int shift_y, float* f,
                       int* i) {
   if (!f || !i || pool_w < 2 * width || pool_h < 2 * height || !(zoom > 0)) return OFDG_EINVAL;
-  const ofdg::DevBgPrep p = ofdg::make_bg_prep(pool_w, pool_h, width, height, angle, zoom, shift_x, shift_y, 0);
+  const ofdg::DevBgPrep p = ofdg::make_bg_prep_host(pool_w, pool_h, width, height, angle, zoom, shift_x, shift_y, 0);
   f[0] = p.ca; f[1] = p.sa; f[2] = p.w2; f[3] = p.h2; f[4] = p.rw2; f[5] = p.rh2; f[6] = p.fx; f[7] = p.fy;
   i[0] = p.x0; i[1] = p.y0; i[2] = p.cw; i[3] = p.ch; i[4] = p.shx; i[5] = p.shy;
   return OFDG_OK;

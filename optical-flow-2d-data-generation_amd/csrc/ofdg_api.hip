@@ -328,36 +328,7 @@ int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {
   if (c->prm.world_size < 1) c->prm.world_size = 1;
   c->sampler.reset(new RefSampler(params->mode, params->width, params->height, params->num_objects));
   if (!c->sampler->ok()) { g_create_error = "BAD MODE"; return OFDG_EBADMODE; }
-  {  // constants of the device counter sampler: the 13 mode tables as deltas to mode 7 (DG:1363-2001)
-    CsMode& M = c->cs_mode;
-    const double pi = 3.14159265358979323846;
-    struct Mag { double bg_rot, bg_trans, bg_s0, bg_s1, obj_trans, obj_rot, obj_s0, obj_s1, t_bgr, t_bgs, t_or, t_os; };
-    Mag g{10, 40, 0.93, 1.07, 120, 30, 0.8, 1.2, 0.3, 0.6, 0.7, 0.7};
-    const int mode = params->mode;
-    if (mode == 10) g = Mag{5, 20, 0.965, 1.035, 60, 15, 0.9, 1.1, 0.176, 0.429, 0.539, 0.539};
-    if (mode == 11) g = Mag{20, 80, 0.86, 1.14, 240, 60, 0.6, 1.4, 0.462, 0.75, 0.824, 0.824};
-    if (mode == 12) g = Mag{3.3, 13.3, 0.976, 1.023, 40, 10, 0.933, 1.066, 0.125, 0.333, 0.437, 0.437};
-    if (mode == 13) g = Mag{30, 120, 0.79, 1.21, 360, 90, 0.4, 1.6, 0.563, 0.818, 0.875, 0.875};
-    const bool tonly = (mode == 1 || mode == 2 || mode == 3 || mode == 8);
-    const bool rot = !tonly, scl = !tonly && mode != 4;
-    M.bg_rot_a = rot ? (float)(-g.bg_rot * pi / 180.) : 0.f; M.bg_rot_b = rot ? (float)(g.bg_rot * pi / 180.) : 0.f;
-    M.bg_trans = (float)g.bg_trans;
-    M.bg_scale_a = scl ? (float)g.bg_s0 : 1.f; M.bg_scale_b = scl ? (float)g.bg_s1 : 1.f;
-    M.t_bg_rot = rot ? (float)g.t_bgr : -1.f; M.t_bg_scale = scl ? (float)g.t_bgs : -1.f;
-    M.t_obj_rot = rot ? (float)g.t_or : -1.f; M.t_obj_scale = scl ? (float)g.t_os : -1.f;
-    M.obj_trans = (float)g.obj_trans;
-    M.obj_rot_a = rot ? (float)(-g.obj_rot * pi / 180.) : 0.f; M.obj_rot_b = rot ? (float)(g.obj_rot * pi / 180.) : 0.f;
-    M.obj_scale_a = scl ? (float)g.obj_s0 : 1.f; M.obj_scale_b = scl ? (float)g.obj_s1 : 1.f;
-    M.init_rot_a = mode == 1 ? 0.f : (float)-pi; M.init_rot_b = mode == 1 ? 0.f : (float)pi;
-    M.deform_thr = mode == 9 ? 0.2f : 0.f;
-    M.type_mask = (mode == 1 || mode == 2) ? 2 : mode == 3 ? 1 : (mode == 4 || mode == 5 || mode == 8) ? 3 : 7;
-    M.n_types = 0;
-    if (M.type_mask & 1) M.types[M.n_types++] = OFDG_OBJ_ELLIPSE;
-    if (M.type_mask & 2) M.types[M.n_types++] = OFDG_OBJ_POLYGON;
-    if (M.type_mask & 4) M.types[M.n_types++] = OFDG_OBJ_COMPOSITE;
-    M.mode = mode; M.W = params->width; M.H = params->height; M.num_objects = params->num_objects;
-    M.seed = (uint32_t)params->seed;
-  }
+  c->cs_mode = make_cs_mode(params->mode, params->width, params->height, params->num_objects, (uint32_t)params->seed);  // the device sampler's constants
   // cos/sin of agg::ellipse's 100 step angles, from the host libm
   double tab[200];
   const double pi = 3.14159265358979323846;

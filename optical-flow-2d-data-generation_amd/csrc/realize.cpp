@@ -24,42 +24,6 @@ Motion object_motion(const ofdg_blueprint& p, const Mat& bg_motion, int W, int H
   return r;
 }
 
-}  // namespace
-
-// CImg 2.x: rotate() takes degrees and grows the image to round(1 + |(w-1)cos| + |(h-1)sin|);
-// crop(x0, y0, x1, y1) with float -> int truncation of x1 = x0 + 2W/zoom - 1; linear
-// get_resize with boundary 0 steps (w - 1)/(sx - 1) when enlarging, w/sx otherwise.
-DevBgPrep make_bg_prep(int pw, int ph, int W, int H, float angle, float zoom, int shift_x, int shift_y, uint64_t image_addr) {
-  DevBgPrep p;
-  const int TW = 2 * W, TH = 2 * H;
-  const float nangle = (float)(angle - 360.0f * std::floor((double)angle / 360.0f));
-  const float rad = (float)(nangle * 3.14159265358979323846 / 180.0);
-  p.ca = std::cos(rad);
-  p.sa = std::sin(rad);
-  const float ux = std::fabs((pw - 1) * p.ca), uy = std::fabs((pw - 1) * p.sa);
-  const float vx = std::fabs((ph - 1) * p.sa), vy = std::fabs((ph - 1) * p.ca);
-  const int rw = (int)std::floor(1 + ux + vx + 0.5f), rh = (int)std::floor(1 + uy + vy + 0.5f);
-  p.w2 = 0.5f * (pw - 1); p.h2 = 0.5f * (ph - 1);
-  p.rw2 = 0.5f * (rw - 1); p.rh2 = 0.5f * (rh - 1);
-  p.rw = rw; p.rh = rh;
-  if (pw >= TW && ph >= TH) {
-    p.x0 = pw / 2 - TW / 2; p.y0 = ph / 2 - TH / 2;
-    const int x1 = (int)((float)p.x0 + (float)TW / zoom - 1.0f), y1 = (int)((float)p.y0 + (float)TH / zoom - 1.0f);
-    p.cw = x1 - p.x0 + 1; p.ch = y1 - p.y0 + 1;
-  } else {  // smaller image: no crop, the whole rotated image is resized (DG:102-106)
-    p.x0 = 0; p.y0 = 0; p.cw = rw; p.ch = rh;
-  }
-  p.fx = TW > p.cw ? (float)((p.cw - 1.0) / (TW - 1.0)) : (float)((double)p.cw / TW);
-  p.fy = TH > p.ch ? (float)((p.ch - 1.0) / (TH - 1.0)) : (float)((double)p.ch / TH);
-  p.shx = shift_x; p.shy = shift_y;
-  p.image_addr = image_addr;
-  p.pw = pw; p.ph = ph;
-  p.rx0 = 0; p.ry0 = 0; p.rx1 = TW - 1; p.ry1 = TH - 1;
-  return p;
-}
-
-namespace {
-
 int push_shape(const RealizeConfig& cfg, const ofdg_blueprint& p, const Mat& bg_motion, int sample, int object, int obj_local, int deform,
                std::vector<DevShape>* shapes, std::string* msg) {
   if (p.obj_type != OFDG_OBJ_ELLIPSE && p.obj_type != OFDG_OBJ_POLYGON) {
@@ -166,11 +130,11 @@ int realize_batch(const RealizeConfig& cfg, const ofdg_task* tasks, int n_tasks,
         // the sample's own prepared 2W x 2H texture (bgprep_kernel), in the slot's buffer
         const int ti = pb.tex_id % cfg.pool_n;
         DevBgPrep bp = cfg.tex_table
-            ? make_bg_prep(cfg.tex_table[ti].w, cfg.tex_table[ti].h, W, H, pb.tex_rot, pb.tex_scale, pb.tex_shift_x, pb.tex_shift_y, cfg.tex_table[ti].addr)
-            : make_bg_prep(cfg.pool_w, cfg.pool_h, W, H, pb.tex_rot, pb.tex_scale, pb.tex_shift_x, pb.tex_shift_y,
-                           cfg.pool_addr + (uint64_t)ti * img_texels * sizeof(uint32_t));
-        // (mode 9 re-samples the background through a warp field: anything may be read)
-        if (!(mode9 && pb.do_warpfield_deformation)) bg_prep_region(o.tex_inv, W, H, &bp.rx0, &bp.ry0, &bp.rx1, &bp.ry1);
+            ? make_bg_prep_host(cfg.tex_table[ti].w, cfg.tex_table[ti].h, W, H, pb.tex_rot, pb.tex_scale, pb.tex_shift_x, pb.tex_shift_y, cfg.tex_table[ti].addr)
+            : make_bg_prep_host(cfg.pool_w, cfg.pool_h, W, H, pb.tex_rot, pb.tex_scale, pb.tex_shift_x, pb.tex_shift_y,
+                                cfg.pool_addr + (uint64_t)ti * img_texels * sizeof(uint32_t));
+        // (mode 9 re-samples the background through a warp field; the displacements are not known here: anything may be read)
+        if (!(mode9 && pb.do_warpfield_deformation)) bg_prep_region(o.tex_inv, W, H, 0., &bp);
         out->bgprep.push_back(bp);
         o.tex_base = (uint64_t)t * 4ull * (uint64_t)W * (uint64_t)H;
       } else {

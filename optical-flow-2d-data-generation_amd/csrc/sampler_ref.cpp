@@ -105,16 +105,9 @@ float RefSampler::draw_gauss_pow(Stream& s, int power, float normalize) {
 // ---------------------------------------------------------------------------
 // the 13 modes (DataGenerator.cpp:1363-2001) as deltas to mode 7
 // ---------------------------------------------------------------------------
-RefSampler::RefSampler(int mode, int W, int H, int num_objects_override)
-    : mode_(mode), W_(W), H_(H), num_objects_(num_objects_override) {
-  if (mode < 1 || mode > 13) return;  // "BAD MODE"
-  for (int i = 0; i < kNumStreams; ++i) st_[i].eng.reseed((uint32_t)i);
+CsMode make_cs_mode(int mode, int W, int H, int num_objects, uint32_t seed) {
+  CsMode M;
   const double pi = 3.14159265358979323846;  // agg::pi
-  auto range = [&](int id, double a, double b) { st_[id].a = (float)a; st_[id].b = (float)b; };
-  auto trig = [&](int id, bool enabled, double thr) {
-    // a disabled motion is Trigger(0, 0, 1): always fires, still consumes its draws
-    st_[id].a = 0.f; st_[id].b = enabled ? 1.f : 0.f; st_[id].thr = enabled ? (float)thr : 1.f;
-  };
   // motion magnitudes: {bg rot deg, bg trans, bg scale lo/hi, obj trans, obj rot deg, obj scale lo/hi,
   //                     trigger thresholds bg rot / bg scale / obj rot / obj scale}
   struct Mag { double bg_rot, bg_trans, bg_s0, bg_s1, obj_trans, obj_rot, obj_s0, obj_s1, t_bgr, t_bgs, t_or, t_os; };
@@ -123,54 +116,74 @@ RefSampler::RefSampler(int mode, int W, int H, int num_objects_override)
   if (mode == 11) g = Mag{20, 80, 0.86, 1.14, 240, 60, 0.6, 1.4, 0.462, 0.75, 0.824, 0.824};
   if (mode == 12) g = Mag{3.3, 13.3, 0.976, 1.023, 40, 10, 0.933, 1.066, 0.125, 0.333, 0.437, 0.437};
   if (mode == 13) g = Mag{30, 120, 0.79, 1.21, 360, 90, 0.4, 1.6, 0.563, 0.818, 0.875, 0.875};
-  const bool translation_only = (mode == 1 || mode == 2 || mode == 3 || mode == 8);
-  const bool bg_rot = !translation_only;
-  const bool bg_scale = !translation_only && mode != 4;
-  const bool obj_rot = !translation_only;
-  const bool obj_scale = !translation_only && mode != 4;
+  const bool tonly = (mode == 1 || mode == 2 || mode == 3 || mode == 8);  // translation only
+  const bool rot = !tonly, scl = !tonly && mode != 4;
+  M.bg_rot_a = rot ? (float)(-g.bg_rot * pi / 180.) : 0.f; M.bg_rot_b = rot ? (float)(g.bg_rot * pi / 180.) : 0.f;
+  M.bg_trans = (float)g.bg_trans;
+  M.bg_scale_a = scl ? (float)g.bg_s0 : 1.f; M.bg_scale_b = scl ? (float)g.bg_s1 : 1.f;
+  M.t_bg_rot = rot ? (float)g.t_bgr : -1.f; M.t_bg_scale = scl ? (float)g.t_bgs : -1.f;
+  M.t_obj_rot = rot ? (float)g.t_or : -1.f; M.t_obj_scale = scl ? (float)g.t_os : -1.f;
+  M.obj_trans = (float)g.obj_trans;
+  M.obj_rot_a = rot ? (float)(-g.obj_rot * pi / 180.) : 0.f; M.obj_rot_b = rot ? (float)(g.obj_rot * pi / 180.) : 0.f;
+  M.obj_scale_a = scl ? (float)g.obj_s0 : 1.f; M.obj_scale_b = scl ? (float)g.obj_s1 : 1.f;
+  M.init_rot_a = mode == 1 ? 0.f : (float)-pi; M.init_rot_b = mode == 1 ? 0.f : (float)pi;
+  M.deform_thr = mode == 9 ? 0.2f : 0.f;
+  M.type_mask = (mode == 1 || mode == 2) ? 2 : mode == 3 ? 1 : (mode == 4 || mode == 5 || mode == 8) ? 3 : 7;
+  M.n_types = 0;
+  M.types[0] = M.types[1] = M.types[2] = 0;
+  if (M.type_mask & 1) M.types[M.n_types++] = OFDG_OBJ_ELLIPSE;
+  if (M.type_mask & 2) M.types[M.n_types++] = OFDG_OBJ_POLYGON;
+  if (M.type_mask & 4) M.types[M.n_types++] = OFDG_OBJ_COMPOSITE;
+  M.mode = mode; M.W = W; M.H = H; M.num_objects = num_objects;
+  M.seed = seed;
+  return M;
+}
 
+// The reference's 45 streams set up from the mode's constants (the seed is the counter sampler's alone).
+RefSampler::RefSampler(int mode, int W, int H, int num_objects_override)
+    : mode_(mode), W_(W), H_(H), num_objects_(num_objects_override), m_(make_cs_mode(mode, W, H, num_objects_override, 0)) {
+  if (mode < 1 || mode > 13) return;  // "BAD MODE"
+  for (int i = 0; i < kNumStreams; ++i) st_[i].eng.reseed((uint32_t)i);
+  const double pi = 3.14159265358979323846;  // agg::pi
+  auto range = [&](int id, double a, double b) { st_[id].a = (float)a; st_[id].b = (float)b; };
+  auto trig = [&](int id, float thr) {
+    // a disabled motion (thr < 0) is Trigger(0, 0, 1): always fires, still consumes its draws
+    st_[id].a = 0.f; st_[id].b = thr < 0 ? 0.f : 1.f; st_[id].thr = thr < 0 ? 1.f : thr;
+  };
+  const CsMode& M = m_;
   range(kBgInitRot, -pi, pi);
-  trig(kBgRotTrigger, bg_rot, g.t_bgr);
-  if (bg_rot) range(kBgRot, -g.bg_rot * pi / 180., g.bg_rot * pi / 180.); else range(kBgRot, 0, 0);
-  range(kBgTransX, -g.bg_trans, g.bg_trans);
-  range(kBgTransY, -g.bg_trans, g.bg_trans);
-  trig(kBgScaleTrigger, bg_scale, g.t_bgs);
+  trig(kBgRotTrigger, M.t_bg_rot);
+  range(kBgRot, M.bg_rot_a, M.bg_rot_b);
+  range(kBgTransX, -M.bg_trans, M.bg_trans);
+  range(kBgTransY, -M.bg_trans, M.bg_trans);
+  trig(kBgScaleTrigger, M.t_bg_scale);
   range(kBgInitScale, 0.8, 1.2);
-  if (bg_scale) range(kBgScale, g.bg_s0, g.bg_s1); else range(kBgScale, 1, 1);
+  range(kBgScale, M.bg_scale_a, M.bg_scale_b);
   range(kNumberOfFgObjects, 16, 24);
-  switch (mode) {
-    case 1: case 2: type_mask_ = 2; break;
-    case 3: type_mask_ = 1; break;
-    case 4: case 5: case 8: type_mask_ = 3; break;
-    default: type_mask_ = 7; break;
-  }
-  if (type_mask_ & 1) types_[n_types_++] = OFDG_OBJ_ELLIPSE;
-  if (type_mask_ & 2) types_[n_types_++] = OFDG_OBJ_POLYGON;
-  if (type_mask_ & 4) types_[n_types_++] = OFDG_OBJ_COMPOSITE;
   range(kObjInitTransX, -W / 2. - 50, W * 3. / 2. + 50);
   range(kObjInitTransY, -H / 2. - 50, H * 3. / 2. + 50);
-  range(kObjTransX, -g.obj_trans, g.obj_trans);
-  range(kObjTransY, -g.obj_trans, g.obj_trans);
-  if (mode == 1) range(kObjInitRot, 0, 0); else range(kObjInitRot, -pi, pi);
-  trig(kObjRotTrigger, obj_rot, g.t_or);
-  if (obj_rot) range(kObjRot, -g.obj_rot * pi / 180., g.obj_rot * pi / 180.); else range(kObjRot, 0, 0);
-  trig(kObjScaleTrigger, obj_scale, g.t_os);
-  if (obj_scale) range(kObjScale, g.obj_s0, g.obj_s1); else range(kObjScale, 1, 1);
+  range(kObjTransX, -M.obj_trans, M.obj_trans);
+  range(kObjTransY, -M.obj_trans, M.obj_trans);
+  range(kObjInitRot, M.init_rot_a, M.init_rot_b);
+  trig(kObjRotTrigger, M.t_obj_rot);
+  range(kObjRot, M.obj_rot_a, M.obj_rot_b);
+  trig(kObjScaleTrigger, M.t_obj_scale);
+  range(kObjScale, M.obj_scale_a, M.obj_scale_b);
   range(kElliScaleX, 0.5, 2);
   range(kElliScaleY, 0.5, 2);
   range(kPolyDphi, -10, 10);
   range(kPolyR, 20, 80);
   range(kPolyScaleX, 0.5, 2);
   range(kPolyScaleY, 0.5, 2);
-  trig(kPolyCurveTrigger, true, 0.33);
+  trig(kPolyCurveTrigger, 0.33f);
   range(kCompInitTransX, -15, 15);
   range(kCompInitTransY, -15, 15);
-  trig(kComponentIsAdditive, true, 0.5);
+  trig(kComponentIsAdditive, 0.5f);
   range(kComponentOffset, -20, 20);
-  trig(kObjIsExtraThin, true, 0.2);
-  trig(kObjDeformsNonrigidly, true, mode == 9 ? 0.2 : 0.0);
+  trig(kObjIsExtraThin, 0.2f);
+  trig(kObjDeformsNonrigidly, M.deform_thr);
   range(kGenericUniform, 0, 1);
-  trig(kGenericTrigger, true, 0.5);
+  trig(kGenericTrigger, 0.5f);
   // kObjInitScale, kObjTexShiftX/Y, kObjTexRot, kObjTexZoom are constructed by the
   // reference but never drawn from (DataGenerator.cpp:1678-1684): nothing to set up.
   ok_ = true;
@@ -255,7 +268,7 @@ int RefSampler::foreground(std::vector<ofdg_blueprint>* bps, size_t bi, bool is_
   const bool curves = (mode_ >= 4);
   int type;
   do {
-    type = types_[draw_int(st_[kObjType], 0, n_types_ - 1)];
+    type = m_.types[draw_int(st_[kObjType], 0, m_.n_types - 1)];
   } while (is_component && type == OFDG_OBJ_COMPOSITE);
   {
     ofdg_blueprint* b = &(*bps)[bi];

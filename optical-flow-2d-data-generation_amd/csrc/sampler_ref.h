@@ -43,6 +43,23 @@ enum StreamId {
   kObjIsExtraThin, kObjDeformsNonrigidly, kGenericUniform, kGenericTrigger, kNumStreams
 };
 
+// Per-mode constants of both samplers (DataGenerator.cpp:1363-2001), from make_cs_mode().  The device counter sampler
+// (sampler_counter.hip) takes the struct by value as a kernel argument: field order and size are part of that interface.
+struct CsMode {
+  float bg_rot_a, bg_rot_b, bg_trans, bg_scale_a, bg_scale_b;
+  float t_bg_rot, t_bg_scale, t_obj_rot, t_obj_scale;  // trigger thresholds; < 0: "disabled" (always fires, value = midpoint)
+  float obj_trans, obj_rot_a, obj_rot_b, obj_scale_a, obj_scale_b;
+  float init_rot_a, init_rot_b;
+  float deform_thr;
+  int32_t type_mask, n_types;  // bit0 ellipse, bit1 polygon, bit2 composite
+  int32_t types[3];
+  int32_t mode, W, H, num_objects;
+  uint32_t seed;
+};
+static_assert(sizeof(CsMode) == 108, "CsMode is a by-value kernel argument: keep its layout");
+// The one copy of the 13 mode tables (mode in 1..13), as deltas to mode 7.
+CsMode make_cs_mode(int mode, int W, int H, int num_objects, uint32_t seed);
+
 class RefSampler {
  public:
   // Throws nothing; check ok() (bad mode => "BAD MODE", DataGenerator.cpp:2004).
@@ -75,9 +92,7 @@ class RefSampler {
 
   int mode_, W_, H_, num_objects_;
   bool ok_ = false;
-  unsigned type_mask_ = 0;  // bit0 ellipse, bit1 polygon, bit2 composite
-  int n_types_ = 0;
-  int types_[3];
+  CsMode m_;
   Stream st_[kNumStreams];
 };
 

@@ -132,12 +132,12 @@ def ulp_diff(got, exp):
     return np.abs(a - b)
 
 
-def counter_vs_oracle(ofdg, oracle, mode, W, H, B, first, seed=77, pool=(4, 256, 192), threads=1, num_objects=0):
+def counter_vs_oracle(ofdg, oracle, mode, W, H, B, first, seed=77, pool=(4, 256, 192), threads=1, num_objects=0, background_prep=0, pool_seed=5):
     """ofdg_forward_counter (device sampling + device realize + render: the path bench.py times) against the oracle
     fed with the blueprints ofdg_sample_counter downloads.  The device builds its affines with include/ofdg_detmath.h;
     so does the oracle here (oracle.detmath()): every byte must agree."""
-    g = ofdg.Generator(ofdg.default_params(width=W, height=H, mode=mode, sampler=1, seed=seed, num_objects=num_objects))
-    g.pool_synthetic(pool[0], pool[1], pool[2], 5)
+    g = ofdg.Generator(ofdg.default_params(width=W, height=H, mode=mode, sampler=1, seed=seed, num_objects=num_objects, background_prep=background_prep))
+    g.pool_synthetic(pool[0], pool[1], pool[2], pool_seed)
     crops = None
     if mode == 9:
         crops = oracle.warp_crops(W, H, seed=5)[::5][:6] * 4.0
@@ -147,8 +147,10 @@ def counter_vs_oracle(ofdg, oracle, mode, W, H, B, first, seed=77, pool=(4, 256,
     g.forward_counter(first, B, i0, i1, fl)
     g.synchronize()
     tasks, bps, n = g.sample_counter(first, B)
+    q = oracle.default_params(W, H, mode)
+    q.background_prep = background_prep
     with oracle.detmath():
-        e0, e1, ef = oracle.render(oracle.default_params(W, H, mode), tasks, B, bps, n, pl, warp_crops=crops, reuse=-1, n_threads=threads)
+        e0, e1, ef = oracle.render(q, tasks, B, bps, n, pl, warp_crops=crops, reuse=-1, n_threads=threads)
     g0, g1, gf = i0.cpu().numpy(), i1.cpu().numpy(), fl.cpu().numpy()
     assert np.array_equal(g0, e0), (np.abs(g0 - e0) > 0).sum()
     assert np.array_equal(g1, e1), (np.abs(g1 - e1) > 0).sum()
@@ -235,6 +237,19 @@ def test_counter_sampler_mode9_matches_oracle_with_named_crops(ofdg, oracle):
     with oracle.detmath():
         r0, r1, rf = oracle.render(oracle.default_params(W, H, 9), tasks, B, bps, n, pool.pool_download_all(), warp_crops=crops, reuse=-1)
     assert (r1 != e1).mean() > 0.01
+
+
+def test_counter_sampler_mode9_prepared_backgrounds_match_oracle(ofdg, oracle):
+    """Mode 9 on the device sampler with prepared backgrounds (background_prep = 1): a background that deforms reads its
+    own 2W x 2H texture at displaced positions, so the device realize grows the prepared region by the crop's largest
+    displacement (bg_prep_region with grow > 0); a rigid one gets the plain region (grow = 0).  A batch with both kinds
+    against the oracle, which prepares whole textures: frames bit-exact, flow <= 1 ULP."""
+    W, H, B = 128, 96, 16
+    tasks, bps, crops, _ = counter_vs_oracle(ofdg, oracle, 9, W, H, B, first=300, seed=12, pool=(4, 2 * W + 64, 2 * H + 56),
+                                             background_prep=1, pool_seed=7)
+    flags = [bps[t.background].do_warpfield_deformation for t in tasks]
+    assert any(f != 0 for f in flags) and any(f == 0 for f in flags), flags
+    assert max(flags) <= len(crops)
 
 
 def test_flow_loader_ring_yields_the_index_stream_in_order(ofdg):
