@@ -19,7 +19,9 @@
 #include "../../include/ofdg.h"
 #include "kernels.hip"
 #include "sampler_counter.hip"
+#include "cimg_resize.h"
 #include "ofdg_device.h"
+#include "owners.h"
 #include "realize.h"
 #include "sampler_ref.h"
 #include "warpfields.h"
@@ -31,49 +33,27 @@ static thread_local std::string g_create_error;
 // runtime starts, so what counts is the environment the process was started with
 static const int g_hw_queues_env = [] { const char* q = std::getenv("GPU_MAX_HW_QUEUES"); return q ? std::atoi(q) : 0; }();
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;  // elements
-  bool view = false;  // p points into another allocation (the record arena of an uploaded batch): not ours to free
-  hipError_t reserve(size_t n) {
-    if (n <= cap && !view) return hipSuccess;
-    if (p && !view) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; }
-    p = nullptr; cap = 0; view = false;
-    size_t want = n + n / 4 + 16;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  // look at n elements of somebody else's memory (what we own is given up first)
-  hipError_t alias(T* q, size_t n) {
-    if (p && !view) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; }
-    p = q; cap = n; view = true;
-    return hipSuccess;
-  }
-  void release() { if (p && !view) (void)hipFree(p); p = nullptr; cap = 0; view = false; }
-};
-
+// (every device, pinned, event and stream resource below is held by an owner of owners.h: the context's destructor is its teardown)
 struct ofdg_ctx {
   ofdg_params prm;
   std::string err;
   std::string info;
-  uint32_t* d_prep_paths = nullptr;  // diagnostics: tiles of bgprep_stream_kernel by form (ofdg_debug_bgprep_paths switches it on)
+  DevBuf<uint32_t> d_prep_paths;  // diagnostics: tiles of bgprep_stream_kernel by form (ofdg_debug_bgprep_paths switches it on)
   // texture pool
-  uint32_t* pool = nullptr;
+  DevBuf<uint32_t> pool;
   int pool_n = 0, pool_w = 0, pool_h = 0;
   // where foreground (W x H) and background (2W x 2H) textures are read from: the pool images
   // themselves (centre crops) or pools of resized copies when the images are smaller (DG:96-106)
-  uint32_t* pool_fg = nullptr;   // [n][H][W] if the images are smaller than W x H
-  uint32_t* pool_bg = nullptr;   // [n][2H][2W] if the images are smaller than 2W x 2H
+  DevBuf<uint32_t> pool_fg;   // [n][H][W] if the images are smaller than W x H
+  DevBuf<uint32_t> pool_bg;   // [n][2H][2W] if the images are smaller than 2W x 2H
   TexSource fg_src{}, bg_src{};
   bool pool_final = false;       // derived pools match the current pool contents
   bool pool_mixed = false;       // ofdg_pool_alloc_mixed: only the derived pools exist (images of different sizes)
   std::vector<std::pair<int, int>> mixed_sizes;  // source image sizes of a mixed pool (index table)
   // background_prep on a mixed pool: the whole images stay resident (getRandomizedCrop works on the original image)
-  std::vector<uint32_t*> mixed_images;
+  std::vector<DevBuf<uint32_t>> mixed_images;
   std::vector<DevTexEntry> tex_table;   // host copy of ...
-  DevTexEntry* d_tex_table = nullptr;   // ... the per-image table the device sampler reads
+  DevBuf<DevTexEntry> d_tex_table;      // ... the per-image table the device sampler reads
   int pool_kind = OFDG_POOL_UNIFORM;
   uint32_t pool_seed = 0;
   // sampler
@@ -101,25 +81,24 @@ struct ofdg_ctx {
     int box_parity = 0;
     size_t box_stride = 0;   // mask words per parity
     int mask_used[2] = {0, 0};  // words the last launch on each parity marked (what the next clear must cover)
-    hipEvent_t ev_uploaded = nullptr;
+    Event ev_uploaded;
     bool upload_pending = false;
     hipStream_t upload_stream = nullptr;   // where the records were (last) written
     DevBuf<DevCropRef> d_croptab;      // mode 9: crops of this batch's deforming objects
     DevBuf<float> d_bgwarp;            // mode 9: upscaled (2W x 2H) background crops
     DevBuf<unsigned> d_bgwarp_max;
-    hipEvent_t compose_event = nullptr;  // last tracked compose that read this slot's records (alias of a chain's ev_done) ...
+    hipEvent_t compose_event = nullptr;  // last tracked compose that read this slot's records: NOT owned, an alias of a chain's ev_done ...
     bool compose_pending = false;
     hipStream_t compose_stream = nullptr;  // ... and the stream it ran on
-    int* d_item_count = nullptr;
+    DevBuf<int> d_item_count;  // raster work items of the batch (ensure_item_count)
     int res_samples = 0, res_shapes = 0;
   };
   static constexpr int kUserSlots = 16;              // ofdg_upload_slot / ofdg_render_slot
   Slot slots[kUserSlots];
   // pinned staging of one batch's records on their way to the device
   struct Stage {
-    void* h = nullptr;
-    size_t bytes = 0;
-    hipEvent_t free_ev = nullptr;
+    PinnedBuf h;
+    Event free_ev;
     bool pending = false;
   };
   Stage user_stage;  // ofdg_upload_slot
@@ -131,7 +110,7 @@ struct ofdg_ctx {
   // Each chain owns its coverage workspace, a private record slot (ofdg_render / ofdg_forward*)
   // and its staging buffer, so chains share nothing that is written per call.
   struct Chain {
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf<uint8_t> cov;
     // extras: the labels [2][n][H][W] / backward flow [n][2][H][W] an occlusion pass needs when the caller does not want them
     // (written by compose, read by the occlusion pass behind it; guarded by ev_done like `cov`)
@@ -142,8 +121,8 @@ struct ofdg_ctx {
     DevBuf<uint32_t> x_targets;
     Slot slot;
     Stage stage;
-    hipEvent_t ev_prep = nullptr;  // coverage ready (hand-over to a caller's stream)
-    hipEvent_t ev_done = nullptr;  // the chain's last tracked compose ...
+    Event ev_prep;  // coverage ready (hand-over to a caller's stream)
+    Event ev_done;  // the chain's last tracked compose ...
     bool done_pending = false;
     hipStream_t done_stream = nullptr;  // ... and the stream it ran on (the chain's own, or a caller's)
     // A batch whose preparation kernels have been enqueued on this chain and whose compose has not: what launch_prepare
@@ -155,7 +134,7 @@ struct ofdg_ctx {
       int n = 0;
       unsigned long long* box_cur = nullptr;
       const DevCropRef* croptab = nullptr;
-      hipEvent_t* ev = nullptr;    // profiled launch: its event set
+      Event* ev = nullptr;         // profiled launch: its event set
       hipStream_t stream = nullptr;  // where the preparation was enqueued
       long long ticket = -1;       // the batch's number (its error word)
       bool ahead = false;          // prepared by an EARLIER call (look-ahead): the end of its preparation says nothing about when compose could start
@@ -180,19 +159,19 @@ struct ofdg_ctx {
   long long next_index = 0;  // next global sample index of this rank's stream
   long long last_ticket = -1;  // ticket of the batch the last render / forward call composed
   // mode 9: served warp crops, each 4 planes of (W+1)*(H+1) floats, contiguous
-  float* d_warp = nullptr;         // [n_crops][2 pairs][(H+1)][(W+1)][2]: (flow x, flow y), (iflow x, iflow y) interleaved
-  unsigned* d_warp_max = nullptr;  // [n_crops] float bits of max |iflow|
+  DevBuf<float> d_warp;            // [n_crops][2 pairs][(H+1)][(W+1)][2]: (flow x, flow y), (iflow x, iflow y) interleaved
+  DevBuf<unsigned> d_warp_max;     // [n_crops] float bits of max |iflow|
   // counter sampler, mode 9: every crop as the kernels see it, [k] the crop itself (foreground), [n_crops + k] its
   // 2W x 2H upscaled copy (backgrounds); built once per set of crops
-  DevCropRef* d_cs_croptab = nullptr;
-  float* d_cs_bgwarp = nullptr;
-  unsigned* d_cs_bgwarp_max = nullptr;
+  DevBuf<DevCropRef> d_cs_croptab;
+  DevBuf<float> d_cs_bgwarp;
+  DevBuf<unsigned> d_cs_bgwarp_max;
   CropServer crop_server;
   int rs_w = 0, rs_h = 0;          // CImg resize tables for the background crops
-  int *d_rs_xi = nullptr, *d_rs_yi = nullptr;
-  double *d_rs_xa = nullptr, *d_rs_ya = nullptr;
+  DevBuf<int> d_rs_xi, d_rs_yi;
+  DevBuf<double> d_rs_xa, d_rs_ya;
   bool overlap = true;
-  double* d_cs_tab = nullptr;
+  DevBuf<double> d_cs_tab;
   // Device error flags, ONE WORD PER CALL: call number q ("ticket") raises its flags in word q mod kErrWords, so that a prefetch
   // ring can ask at a batch's hand-over whether THAT batch was truncated (ofdg_poll_errors_of) - the reference drops a bad
   // sample silently (DG:1285-1292).  A word is cleared when it is read; one that was never asked for is read by
@@ -202,7 +181,7 @@ struct ofdg_ctx {
   // the first kernel of the call that takes it over (`word_clean`, launch_prepare).  A caller that only ever uses the
   // device-wide forms (bench.py) pays nothing.  Word kErrWords belongs to the debug entry points.
   static constexpr int kErrWords = 256;
-  uint32_t* d_err = nullptr;     // [kErrWords + 1]
+  DevBuf<uint32_t> d_err;        // [kErrWords + 1]
   bool asked_by_ticket = false;  // ofdg_poll_errors_of has been called on this context
   bool word_clean[kErrWords];    // the word holds nothing of a call before the one that owns it now (all true at creation)
   long long word_reserved = -1;  // the ticket whose word an upload's background preparation already writes into (ofdg_upload_slot)
@@ -213,12 +192,12 @@ struct ofdg_ctx {
   int bg_tab_w = 0, bg_tab_h = 0;
   int bg_cap_cw = 0, bg_cap_ch = 0, bg_cap_n = -1;  // bgprep_caps of the current pool (reset when the pool changes)
   bool bg_fusable = false;
-  uint32_t* h_err = nullptr;        // pinned copy for ofdg_poll_errors, on its own stream
-  hipStream_t err_stream = nullptr;
+  PinnedBuf h_err;                  // pinned copy for ofdg_poll_errors, on its own stream
+  Stream err_stream;
   // profiling: ring of event sets, 6 events per launch: start/stop of geom, raster and compose,
   // attached to the kernels' own dispatch packets
   int profiling = 0;  // 0 off, 1 compose kernel only, 2 all three kernels
-  std::vector<hipEvent_t> ev;
+  std::vector<Event> ev;
   int ev_sets = 0, ev_stride = 1;
   long long ev_count = 0, ev_alloc = 0, launch_count = 0;  // event sets: composed / handed out (a prepared batch holds one)
   std::vector<char> ev_composed;  // per set: its compose was enqueued (a prepared batch that is discarded leaves its set incomplete)
@@ -257,14 +236,14 @@ static void launch_kernel(const Launch& l, void (*kernel)(P...), A... args) {
 }
 
 // the error word of the call being made (its ticket is taken - c->ticket advanced - when the call's first kernel is enqueued)
-static uint32_t* err_word(ofdg_ctx* c, long long ticket) { return c->d_err + (size_t)(ticket % ofdg_ctx::kErrWords); }
+static uint32_t* err_word(ofdg_ctx* c, long long ticket) { return c->d_err.p + (size_t)(ticket % ofdg_ctx::kErrWords); }
 // The call with this ticket is about to enqueue its first kernel on `s`: what an earlier owner left in its word goes first
 // (only for callers that ask by ticket; see ofdg_ctx::word_clean).
 static hipError_t take_err_word(ofdg_ctx* c, long long ticket, hipStream_t s) {
   const size_t i = (size_t)(ticket % ofdg_ctx::kErrWords);
   hipError_t e = hipSuccess;
   if (c->word_reserved == ticket) c->word_reserved = -1;  // (an upload for this very call already raised its flags here: they are this call's)
-  else if (c->asked_by_ticket && !c->word_clean[i]) e = hipMemsetAsync(c->d_err + i, 0, sizeof(uint32_t), s);
+  else if (c->asked_by_ticket && !c->word_clean[i]) e = hipMemsetAsync(c->d_err.p + i, 0, sizeof(uint32_t), s);
   c->word_clean[i] = false;
   return e;
 }
@@ -277,7 +256,6 @@ static std::string err_text(uint32_t e) {
   return t;
 }
 
-static void drop_counter_croptab(ofdg_ctx* c);
 static int discard_all_prepared(ofdg_ctx* c);
 static int texture_of_image(ofdg_ctx* c, const uint32_t* image, int w, int h, int tw, int th, uint32_t* out);
 
@@ -322,7 +300,7 @@ int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {
   }
   e = hipSetDevice(params->device);
   if (e != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return OFDG_EHIP; }
-  std::unique_ptr<ofdg_ctx> c(new ofdg_ctx());
+  std::unique_ptr<ofdg_ctx> c(new ofdg_ctx());  // (an early return below frees what the context holds by then)
   std::fill(c->word_clean, c->word_clean + ofdg_ctx::kErrWords, true);
   c->prm = *params;
   if (c->prm.world_size < 1) c->prm.world_size = 1;
@@ -337,11 +315,11 @@ int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {
     tab[2 * step] = std::cos(angle);
     tab[2 * step + 1] = std::sin(angle);
   }
-  if ((e = hipMalloc((void**)&c->d_cs_tab, sizeof(tab))) != hipSuccess ||
-      (e = hipMemcpy(c->d_cs_tab, tab, sizeof(tab), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->d_err, (ofdg_ctx::kErrWords + 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMemset(c->d_err, 0, (ofdg_ctx::kErrWords + 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&c->user_stage.free_ev, hipEventDisableTiming)) != hipSuccess) {
+  if ((e = c->d_cs_tab.alloc(sizeof(tab) / sizeof(tab[0]))) != hipSuccess ||
+      (e = hipMemcpy(c->d_cs_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = c->d_err.alloc(ofdg_ctx::kErrWords + 1)) != hipSuccess ||
+      (e = hipMemset(c->d_err.p, 0, (ofdg_ctx::kErrWords + 1) * sizeof(uint32_t))) != hipSuccess ||
+      (e = c->user_stage.free_ev.create(hipEventDisableTiming)) != hipSuccess) {
     g_create_error = std::string("HIP initialisation: ") + hipGetErrorString(e);
     return OFDG_EHIP;
   }
@@ -359,10 +337,10 @@ int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {
             " lookahead=" + std::to_string(c->lookahead) + (c->overlap ? "" : " serial");
   for (int i = 0; i < c->n_chains; ++i) {
     ofdg_ctx::Chain& ch = c->chains[i];
-    if ((e = hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ch.stage.free_ev, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ch.ev_prep, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ch.ev_done, hipEventDisableTiming)) != hipSuccess) {
+    if ((e = ch.stream.create(hipStreamNonBlocking)) != hipSuccess ||
+        (e = ch.stage.free_ev.create(hipEventDisableTiming)) != hipSuccess ||
+        (e = ch.ev_prep.create(hipEventDisableTiming)) != hipSuccess ||
+        (e = ch.ev_done.create(hipEventDisableTiming)) != hipSuccess) {
       g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e);
       return OFDG_EHIP;
     }
@@ -385,49 +363,7 @@ const char* ofdg_ctx_info(const ofdg_ctx* c) { return c ? c->info.c_str() : ""; 
 
 void ofdg_destroy(ofdg_ctx* c) {
   if (!c) return;
-  (void)hipDeviceSynchronize();
-  if (c->pool) (void)hipFree(c->pool);
-  if (c->d_prep_paths) (void)hipFree(c->d_prep_paths);
-  if (c->pool_fg) (void)hipFree(c->pool_fg);
-  if (c->pool_bg) (void)hipFree(c->pool_bg);
-  for (uint32_t* im : c->mixed_images) if (im) (void)hipFree(im);
-  if (c->d_tex_table) (void)hipFree(c->d_tex_table);
-  auto drop_slot = [](ofdg_ctx::Slot& sl) {
-    sl.d_shapes.release(); sl.d_frames.release(); sl.d_verts.release(); sl.d_objects.release(); sl.d_samples.release(); sl.d_rec.release();
-    sl.d_items.release(); sl.d_blockmask.release(); sl.d_bgprep.release(); sl.d_bgtex.release();
-    sl.d_bgC.release();
-    sl.d_croptab.release(); sl.d_bgwarp.release(); sl.d_bgwarp_max.release();
-    if (sl.d_item_count) (void)hipFree(sl.d_item_count);
-    if (sl.ev_uploaded) (void)hipEventDestroy(sl.ev_uploaded);
-  };
-  auto drop_stage = [](ofdg_ctx::Stage& g) {
-    if (g.h) (void)hipHostFree(g.h);
-    if (g.free_ev) (void)hipEventDestroy(g.free_ev);
-  };
-  for (auto& sl : c->slots) drop_slot(sl);
-  drop_stage(c->user_stage);
-  for (auto& ch : c->chains) {
-    drop_slot(ch.slot);
-    drop_stage(ch.stage);
-    ch.cov.release();
-    ch.x_labels.release();
-    ch.x_flow1.release();
-    ch.x_targets.release();
-    if (ch.ev_prep) (void)hipEventDestroy(ch.ev_prep);
-    if (ch.ev_done) (void)hipEventDestroy(ch.ev_done);
-    if (ch.stream) (void)hipStreamDestroy(ch.stream);
-  }
-  if (c->d_rs_xi) { (void)hipFree(c->d_rs_xi); (void)hipFree(c->d_rs_xa); (void)hipFree(c->d_rs_yi); (void)hipFree(c->d_rs_ya); }
-  drop_counter_croptab(c);
-  if (c->d_warp) (void)hipFree(c->d_warp);
-  if (c->d_warp_max) (void)hipFree(c->d_warp_max);
-  c->d_cs_bps.release(); c->d_cs_nobj.release();
-  if (c->d_cs_tab) (void)hipFree(c->d_cs_tab);
-  if (c->d_err) (void)hipFree(c->d_err);
-  c->d_bg_at_x.release(); c->d_bg_at_y.release(); c->d_bg_alpha_x.release(); c->d_bg_alpha_y.release();
-  if (c->h_err) (void)hipHostFree(c->h_err);
-  if (c->err_stream) (void)hipStreamDestroy(c->err_stream);
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+  (void)hipDeviceSynchronize();  // (nothing is freed under a kernel that still runs)
   delete c;
 }
 
@@ -445,9 +381,8 @@ int ofdg_pool_alloc(ofdg_ctx* c, int n, int w, int h) {
   OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
   OFDG_TRY(pool_check_dims(c, n, w, h));
   HIP_OK(c, hipDeviceSynchronize());
-  if (c->pool) { HIP_OK(c, hipFree(c->pool)); c->pool = nullptr; }
-  HIP_OK(c, hipMalloc((void**)&c->pool, (size_t)n * w * h * sizeof(uint32_t)));
-  HIP_OK(c, hipMemset(c->pool, 0, (size_t)n * w * h * sizeof(uint32_t)));
+  HIP_OK(c, c->pool.alloc((size_t)n * w * h));
+  HIP_OK(c, hipMemset(c->pool.p, 0, (size_t)n * w * h * sizeof(uint32_t)));
   c->pool_n = n; c->pool_w = w; c->pool_h = h;
   c->pool_final = false;
   c->pool_mixed = false;
@@ -464,17 +399,15 @@ int ofdg_pool_alloc_mixed(ofdg_ctx* c, int n) {
   if (n < 1) { c->err = "texture pool needs at least one image"; return OFDG_ETEXTURES; }
   const int W = c->prm.width, H = c->prm.height;
   HIP_OK(c, hipDeviceSynchronize());
-  for (uint32_t* im : c->mixed_images) if (im) (void)hipFree(im);
-  c->mixed_images.assign((size_t)n, nullptr);
-  if (c->d_tex_table) { (void)hipFree(c->d_tex_table); c->d_tex_table = nullptr; }
+  c->mixed_images.clear();
+  c->mixed_images.resize((size_t)n);
+  c->d_tex_table.release();
   c->tex_table.clear();
-  if (c->pool) { HIP_OK(c, hipFree(c->pool)); c->pool = nullptr; }
-  if (c->pool_fg) { HIP_OK(c, hipFree(c->pool_fg)); c->pool_fg = nullptr; }
-  if (c->pool_bg) { HIP_OK(c, hipFree(c->pool_bg)); c->pool_bg = nullptr; }
-  HIP_OK(c, hipMalloc((void**)&c->pool_fg, (size_t)n * W * H * sizeof(uint32_t)));
-  HIP_OK(c, hipMalloc((void**)&c->pool_bg, (size_t)n * 4 * W * H * sizeof(uint32_t)));
-  HIP_OK(c, hipMemset(c->pool_fg, 0, (size_t)n * W * H * sizeof(uint32_t)));
-  HIP_OK(c, hipMemset(c->pool_bg, 0, (size_t)n * 4 * W * H * sizeof(uint32_t)));
+  c->pool.release(); c->pool_fg.release(); c->pool_bg.release();  // (all three go before the new ones come)
+  HIP_OK(c, c->pool_fg.alloc((size_t)n * W * H));
+  HIP_OK(c, c->pool_bg.alloc((size_t)n * 4 * W * H));
+  HIP_OK(c, hipMemset(c->pool_fg.p, 0, (size_t)n * W * H * sizeof(uint32_t)));
+  HIP_OK(c, hipMemset(c->pool_bg.p, 0, (size_t)n * 4 * W * H * sizeof(uint32_t)));
   HIP_OK(c, hipDeviceSynchronize());
   c->pool_n = n; c->pool_w = 0; c->pool_h = 0;
   c->fg_src = TexSource{(uint64_t)W * H, 0, W, 0};
@@ -495,26 +428,22 @@ int ofdg_pool_upload_mixed(ofdg_ctx* c, int index, const uint8_t* bgr_planar, in
     return OFDG_ETEXTURES;
   }
   const int W = c->prm.width, H = c->prm.height;
-  uint8_t* tmp = nullptr;
-  uint32_t* img = nullptr;
+  DevBuf<uint8_t> tmp;
+  DevBuf<uint32_t> img;
   const size_t n = (size_t)w * h;
   HIP_OK(c, hipDeviceSynchronize());
-  HIP_OK(c, hipMalloc((void**)&tmp, 3 * n));
-  HIP_OK(c, hipMalloc((void**)&img, n * sizeof(uint32_t)));
-  HIP_OK(c, hipMemcpy(tmp, bgr_planar, 3 * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pool_pack_kernel, dim3(1024), dim3(256), 0, 0, tmp, img, w, h);
+  HIP_OK(c, tmp.alloc(3 * n));
+  HIP_OK(c, img.alloc(n));
+  HIP_OK(c, hipMemcpy(tmp.p, bgr_planar, 3 * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pool_pack_kernel, dim3(1024), dim3(256), 0, 0, tmp.p, img.p, w, h);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipDeviceSynchronize());
-  int rc = texture_of_image(c, img, w, h, W, H, c->pool_fg + (size_t)index * W * H);
-  if (rc == OFDG_OK) rc = texture_of_image(c, img, w, h, 2 * W, 2 * H, c->pool_bg + (size_t)index * 4 * W * H);
+  int rc = texture_of_image(c, img.p, w, h, W, H, c->pool_fg.p + (size_t)index * W * H);
+  if (rc == OFDG_OK) rc = texture_of_image(c, img.p, w, h, 2 * W, 2 * H, c->pool_bg.p + (size_t)index * 4 * W * H);
   HIP_OK(c, hipDeviceSynchronize());
-  (void)hipFree(tmp);
   if (rc == OFDG_OK && c->prm.background_prep) {  // the background preparation reads the original image
-    if (c->mixed_images[(size_t)index]) (void)hipFree(c->mixed_images[(size_t)index]);
-    c->mixed_images[(size_t)index] = img;
-    if (c->d_tex_table) { (void)hipFree(c->d_tex_table); c->d_tex_table = nullptr; }
-  } else {
-    (void)hipFree(img);
+    c->mixed_images[(size_t)index] = std::move(img);  // (the image it replaces goes with `img`)
+    c->d_tex_table.release();
   }
   if (rc == OFDG_OK) c->mixed_sizes[(size_t)index] = std::make_pair(w, h);
   return rc;
@@ -522,7 +451,7 @@ int ofdg_pool_upload_mixed(ofdg_ctx* c, int index, const uint8_t* bgr_planar, in
 
 int ofdg_pool_synthetic(ofdg_ctx* c, int n, int w, int h, uint32_t seed) {
   OFDG_TRY(ofdg_pool_alloc(c, n, w, h));
-  hipLaunchKernelGGL(pool_synth_kernel, dim3(256 * 8), dim3(256), 0, 0, c->pool, n, w, h, seed);
+  hipLaunchKernelGGL(pool_synth_kernel, dim3(256 * 8), dim3(256), 0, 0, c->pool.p, n, w, h, seed);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipDeviceSynchronize());
   c->pool_final = false;
@@ -534,32 +463,30 @@ int ofdg_pool_synthetic(ofdg_ctx* c, int n, int w, int h, uint32_t seed) {
 int ofdg_pool_upload(ofdg_ctx* c, int index, const uint8_t* bgr_planar, int w, int h) {
   if (!c || !bgr_planar) return OFDG_EINVAL;
   OFDG_TRY(discard_all_prepared(c));  // (batches prepared ahead read the old pool / crops)
-  if (!c->pool || index < 0 || index >= c->pool_n || w != c->pool_w || h != c->pool_h) {
+  if (!c->pool.p || index < 0 || index >= c->pool_n || w != c->pool_w || h != c->pool_h) {
     c->err = "pool_upload: index / size does not match the allocated pool";
     return OFDG_ETEXTURES;
   }
-  uint8_t* tmp = nullptr;
+  DevBuf<uint8_t> tmp;
   const size_t n = (size_t)w * h;
-  HIP_OK(c, hipMalloc((void**)&tmp, 3 * n));
-  HIP_OK(c, hipMemcpy(tmp, bgr_planar, 3 * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pool_pack_kernel, dim3(1024), dim3(256), 0, 0, tmp, c->pool + (size_t)index * n, w, h);
+  HIP_OK(c, tmp.alloc(3 * n));
+  HIP_OK(c, hipMemcpy(tmp.p, bgr_planar, 3 * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pool_pack_kernel, dim3(1024), dim3(256), 0, 0, tmp.p, c->pool.p + (size_t)index * n, w, h);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipDeviceSynchronize());
-  HIP_OK(c, hipFree(tmp));
   c->pool_final = false;
   return OFDG_OK;
 }
 
 int ofdg_pool_download(ofdg_ctx* c, int index, uint8_t* bgr_planar) {
   if (!c || !bgr_planar) return OFDG_EINVAL;
-  if (!c->pool || index < 0 || index >= c->pool_n) { c->err = "pool_download: bad index"; return OFDG_ETEXTURES; }
-  uint8_t* tmp = nullptr;
+  if (!c->pool.p || index < 0 || index >= c->pool_n) { c->err = "pool_download: bad index"; return OFDG_ETEXTURES; }
+  DevBuf<uint8_t> tmp;
   const size_t n = (size_t)c->pool_w * c->pool_h;
-  HIP_OK(c, hipMalloc((void**)&tmp, 3 * n));
-  hipLaunchKernelGGL(pool_unpack_kernel, dim3(1024), dim3(256), 0, 0, c->pool + (size_t)index * n, tmp, c->pool_w, c->pool_h);
+  HIP_OK(c, tmp.alloc(3 * n));
+  hipLaunchKernelGGL(pool_unpack_kernel, dim3(1024), dim3(256), 0, 0, c->pool.p + (size_t)index * n, tmp.p, c->pool_w, c->pool_h);
   HIP_OK(c, hipGetLastError());
-  HIP_OK(c, hipMemcpy(bgr_planar, tmp, 3 * n, hipMemcpyDeviceToHost));
-  HIP_OK(c, hipFree(tmp));
+  HIP_OK(c, hipMemcpy(bgr_planar, tmp.p, 3 * n, hipMemcpyDeviceToHost));  // (waits for the kernel: tmp is idle when it goes)
   return OFDG_OK;
 }
 
@@ -576,9 +503,9 @@ int ofdg_pool_info(const ofdg_ctx* c, int* n, int* w, int* h) {
 // `mark_written` != 0 tells the context that the contents changed (derived textures are rebuilt at the next use).
 int ofdg_pool_device(ofdg_ctx* c, void** ptr, unsigned long long* bytes, int mark_written) {
   if (!c || !ptr || !bytes) return OFDG_EINVAL;
-  if (!c->pool || c->pool_mixed) { c->err = "pool_device: needs a pool of one image size (ofdg_pool_alloc / ofdg_pool_synthetic)"; return OFDG_ETEXTURES; }
+  if (!c->pool.p || c->pool_mixed) { c->err = "pool_device: needs a pool of one image size (ofdg_pool_alloc / ofdg_pool_synthetic)"; return OFDG_ETEXTURES; }
   HIP_OK(c, hipDeviceSynchronize());
-  *ptr = (void*)c->pool;
+  *ptr = (void*)c->pool.p;
   *bytes = (unsigned long long)c->pool_n * c->pool_w * c->pool_h * sizeof(uint32_t);
   if (mark_written) {
     c->pool_final = false;
@@ -593,8 +520,8 @@ int ofdg_pool_device_mixed(ofdg_ctx* c, void** fg, unsigned long long* fg_bytes,
   OFDG_TRY(discard_all_prepared(c));  // (the caller is about to write the textures)
   HIP_OK(c, hipDeviceSynchronize());
   const unsigned long long px = (unsigned long long)c->prm.width * c->prm.height;
-  *fg = (void*)c->pool_fg; *fg_bytes = (unsigned long long)c->pool_n * px * sizeof(uint32_t);
-  *bg = (void*)c->pool_bg; *bg_bytes = (unsigned long long)c->pool_n * 4 * px * sizeof(uint32_t);
+  *fg = (void*)c->pool_fg.p; *fg_bytes = (unsigned long long)c->pool_n * px * sizeof(uint32_t);
+  *bg = (void*)c->pool_bg.p; *bg_bytes = (unsigned long long)c->pool_n * 4 * px * sizeof(uint32_t);
   return OFDG_OK;
 }
 
@@ -637,7 +564,7 @@ int ofdg_setup_alloc_pool(ofdg_ctx* c, const ofdg_setup* su, const ofdg_tex_entr
   for (int i = 0; i < su->n_tex; ++i) {
     c->mixed_sizes[(size_t)i] = std::make_pair((int)table[i].w, (int)table[i].h);
     if (c->prm.background_prep)  // the whole images arrive with ofdg_comm_bcast_pool
-      HIP_OK(c, hipMalloc((void**)&c->mixed_images[(size_t)i], (size_t)table[i].w * table[i].h * sizeof(uint32_t)));
+      HIP_OK(c, c->mixed_images[(size_t)i].alloc((size_t)table[i].w * table[i].h));
   }
   return OFDG_OK;
 }
@@ -645,12 +572,12 @@ int ofdg_setup_alloc_pool(ofdg_ctx* c, const ofdg_setup* su, const ofdg_tex_entr
 // image `index` of a mixed pool kept whole for the background preparation, as raw device memory (w * h BGRX texels)
 int ofdg_pool_device_image(ofdg_ctx* c, int index, void** ptr, unsigned long long* bytes) {
   if (!c || !ptr || !bytes) return OFDG_EINVAL;
-  if (!c->pool_mixed || !c->prm.background_prep || index < 0 || index >= c->pool_n || !c->mixed_images[(size_t)index]) {
+  if (!c->pool_mixed || !c->prm.background_prep || index < 0 || index >= c->pool_n || !c->mixed_images[(size_t)index].p) {
     c->err = "pool_device_image: no whole image " + std::to_string(index) + " (mixed pool with background_prep only)";
     return OFDG_ETEXTURES;
   }
   HIP_OK(c, hipDeviceSynchronize());
-  *ptr = (void*)c->mixed_images[(size_t)index];
+  *ptr = (void*)c->mixed_images[(size_t)index].p;
   *bytes = (unsigned long long)c->mixed_sizes[(size_t)index].first * c->mixed_sizes[(size_t)index].second * sizeof(uint32_t);
   return OFDG_OK;
 }
@@ -689,115 +616,90 @@ static int reserve_blockmask(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n_samples) {
 static int ensure_resize_tables(ofdg_ctx* c) {
   const int W = c->prm.width, H = c->prm.height;
   if (c->rs_w == W && c->rs_h == H) return OFDG_OK;
-  auto table = [](int w, int sx, std::vector<int>& idx, std::vector<double>& alpha) {
-    idx.resize(sx); alpha.resize(sx);
-    const double f = (sx > w) ? (sx > 1 ? (w - 1.) / (sx - 1) : 0) : (double)w / sx;
-    double curr = 0, old = 0;
-    int at = 0;
-    for (int x = 0; x < sx; ++x) {
-      alpha[x] = curr - (unsigned int)curr;
-      idx[x] = at;
-      old = curr;
-      curr = std::min(w - 1., curr + f);
-      at += (int)((unsigned int)curr - (unsigned int)old);
-    }
+  auto table = [&](int w, int sx, DevBuf<int>& d_at, DevBuf<double>& d_alpha) -> int {
+    std::vector<int> at(sx);
+    std::vector<double> alpha(sx);
+    cimg_enlarge_table(w, sx, at.data(), alpha.data());
+    HIP_OK(c, d_at.alloc(at.size()));
+    HIP_OK(c, d_alpha.alloc(alpha.size()));
+    HIP_OK(c, hipMemcpy(d_at.p, at.data(), at.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_OK(c, hipMemcpy(d_alpha.p, alpha.data(), alpha.size() * sizeof(double), hipMemcpyHostToDevice));
+    return OFDG_OK;
   };
-  std::vector<int> xi, yi;
-  std::vector<double> xa, ya;
-  table(W + 1, 2 * W, xi, xa);
-  table(H + 1, 2 * H, yi, ya);
-  if (c->d_rs_xi) { (void)hipFree(c->d_rs_xi); (void)hipFree(c->d_rs_xa); (void)hipFree(c->d_rs_yi); (void)hipFree(c->d_rs_ya); }
-  HIP_OK(c, hipMalloc((void**)&c->d_rs_xi, xi.size() * sizeof(int)));
-  HIP_OK(c, hipMalloc((void**)&c->d_rs_xa, xa.size() * sizeof(double)));
-  HIP_OK(c, hipMalloc((void**)&c->d_rs_yi, yi.size() * sizeof(int)));
-  HIP_OK(c, hipMalloc((void**)&c->d_rs_ya, ya.size() * sizeof(double)));
-  HIP_OK(c, hipMemcpy(c->d_rs_xi, xi.data(), xi.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemcpy(c->d_rs_xa, xa.data(), xa.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemcpy(c->d_rs_yi, yi.data(), yi.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemcpy(c->d_rs_ya, ya.data(), ya.size() * sizeof(double), hipMemcpyHostToDevice));
+  OFDG_TRY(table(W + 1, 2 * W, c->d_rs_xi, c->d_rs_xa));
+  OFDG_TRY(table(H + 1, 2 * H, c->d_rs_yi, c->d_rs_ya));
   c->rs_w = W; c->rs_h = H;
+  return OFDG_OK;
+}
+
+// mode 9: a (W+1) x (H+1) warp crop upscaled on stream `s` into the 2W x 2H crop `dst` a background reads; returns dst's table entry
+static int upscale_crop(ofdg_ctx* c, const float* src, float* dst, unsigned* dst_max, hipStream_t s, DevCropRef* ref) {
+  const int W = c->prm.width, H = c->prm.height;
+  hipLaunchKernelGGL(wf_resize2_kernel, dim3((2 * W * 2 * H + 255) / 256), dim3(256), 0, s, src, W + 1, H + 1, 2 * W, 2 * H,
+                     c->d_rs_xi.p, c->d_rs_xa.p, c->d_rs_yi.p, c->d_rs_ya.p, dst, dst_max);
+  HIP_OK(c, hipGetLastError());
+  *ref = make_crop_ref(dst, dst_max, 2 * W, 2 * H);
   return OFDG_OK;
 }
 
 // counter sampler, mode 9: the static crop table (see ofdg_ctx::d_cs_croptab)
 static int ensure_counter_croptab(ofdg_ctx* c) {
-  if (c->d_cs_croptab) return OFDG_OK;
+  if (c->d_cs_croptab.p) return OFDG_OK;
   const int n = c->crop_server.n_crops;
-  if (!c->d_warp || n < 1) { c->err = "mode 9 needs warp fields: call ofdg_warp_generate or ofdg_warp_upload first"; return OFDG_EINVAL; }
+  if (!c->d_warp.p || n < 1) { c->err = "mode 9 needs warp fields: call ofdg_warp_generate or ofdg_warp_upload first"; return OFDG_EINVAL; }
   OFDG_TRY(ensure_resize_tables(c));
   const int W = c->prm.width, H = c->prm.height;
   const size_t crop_floats = (size_t)4 * (W + 1) * (H + 1), bg_floats = (size_t)4 * 2 * W * 2 * H;
   HIP_OK(c, hipDeviceSynchronize());
-  HIP_OK(c, hipMalloc((void**)&c->d_cs_bgwarp, (size_t)n * bg_floats * sizeof(float)));
-  HIP_OK(c, hipMalloc((void**)&c->d_cs_bgwarp_max, (size_t)n * sizeof(unsigned)));
-  HIP_OK(c, hipMemset(c->d_cs_bgwarp_max, 0, (size_t)n * sizeof(unsigned)));
-  HIP_OK(c, hipMalloc((void**)&c->d_cs_croptab, (size_t)2 * n * sizeof(DevCropRef)));
+  HIP_OK(c, c->d_cs_bgwarp.alloc((size_t)n * bg_floats));
+  HIP_OK(c, c->d_cs_bgwarp_max.alloc((size_t)n));
+  HIP_OK(c, hipMemset(c->d_cs_bgwarp_max.p, 0, (size_t)n * sizeof(unsigned)));
+  HIP_OK(c, c->d_cs_croptab.alloc((size_t)2 * n));
   std::vector<DevCropRef> tab((size_t)2 * n);
   for (int k = 0; k < n; ++k) {
-    const float* src = c->d_warp + (size_t)k * crop_floats;
-    float* dst = c->d_cs_bgwarp + (size_t)k * bg_floats;
-    hipLaunchKernelGGL(wf_resize2_kernel, dim3((2 * W * 2 * H + 255) / 256), dim3(256), 0, 0, src, W + 1, H + 1, 2 * W, 2 * H,
-                       c->d_rs_xi, c->d_rs_xa, c->d_rs_yi, c->d_rs_ya, dst, c->d_cs_bgwarp_max + k);
-    HIP_OK(c, hipGetLastError());
-    tab[k] = make_crop_ref(src, c->d_warp_max + k, W + 1, H + 1);
-    tab[(size_t)n + k] = make_crop_ref(dst, c->d_cs_bgwarp_max + k, 2 * W, 2 * H);
+    const float* src = c->d_warp.p + (size_t)k * crop_floats;
+    OFDG_TRY(upscale_crop(c, src, c->d_cs_bgwarp.p + (size_t)k * bg_floats, c->d_cs_bgwarp_max.p + k, 0, &tab[(size_t)n + k]));
+    tab[k] = make_crop_ref(src, c->d_warp_max.p + k, W + 1, H + 1);
   }
-  HIP_OK(c, hipMemcpy(c->d_cs_croptab, tab.data(), tab.size() * sizeof(DevCropRef), hipMemcpyHostToDevice));
+  HIP_OK(c, hipMemcpy(c->d_cs_croptab.p, tab.data(), tab.size() * sizeof(DevCropRef), hipMemcpyHostToDevice));
   HIP_OK(c, hipDeviceSynchronize());
   return OFDG_OK;
 }
-static void drop_counter_croptab(ofdg_ctx* c) {
-  if (c->d_cs_croptab) { (void)hipFree(c->d_cs_croptab); c->d_cs_croptab = nullptr; }
-  if (c->d_cs_bgwarp) { (void)hipFree(c->d_cs_bgwarp); c->d_cs_bgwarp = nullptr; }
-  if (c->d_cs_bgwarp_max) { (void)hipFree(c->d_cs_bgwarp_max); c->d_cs_bgwarp_max = nullptr; }
-}
+static void drop_counter_croptab(ofdg_ctx* c) { c->d_cs_croptab.release(); c->d_cs_bgwarp.release(); c->d_cs_bgwarp_max.release(); }
 
 // CImg<unsigned char>::get_resize(tw, th, -100, -100, 3) of every pool image (X pass, then Y pass, u8 in
 // between) into dst[n][th][tw]
 static int resize_images(ofdg_ctx* c, const uint32_t* images, int n, int w, int h, int tw, int th, uint32_t* out_images) {
-  uint32_t* mid = nullptr;  // [n][h][tw]
-  HIP_OK(c, hipMalloc((void**)&mid, (size_t)n * tw * h * sizeof(uint32_t)));
+  DevBuf<uint32_t> mid;  // [n][h][tw]
+  HIP_OK(c, mid.alloc((size_t)n * tw * h));
   auto pass = [&](const uint32_t* src, uint32_t* out, int sw, int sh, int s, int along_x) -> int {
     const int len = along_x ? sw : sh;
-    int* d_at = nullptr;
-    double* d_alpha = nullptr;
-    if (s > len) {  // enlarging: CImg's running sums (boundary 0)
+    DevBuf<int> d_at;
+    DevBuf<double> d_alpha;
+    if (s > len) {  // enlarging
       std::vector<int> at(s);
       std::vector<double> alpha(s);
-      const double f = s > 1 ? (len - 1.) / (s - 1) : 0;
-      double curr = 0, old = 0;
-      int pos = 0;
-      for (int x = 0; x < s; ++x) {
-        alpha[x] = curr - (unsigned int)curr;
-        at[x] = pos;
-        old = curr;
-        curr = std::min(len - 1., curr + f);
-        pos += (int)((unsigned int)curr - (unsigned int)old);
-      }
-      HIP_OK(c, hipMalloc((void**)&d_at, s * sizeof(int)));
-      HIP_OK(c, hipMalloc((void**)&d_alpha, s * sizeof(double)));
-      HIP_OK(c, hipMemcpy(d_at, at.data(), s * sizeof(int), hipMemcpyHostToDevice));
-      HIP_OK(c, hipMemcpy(d_alpha, alpha.data(), s * sizeof(double), hipMemcpyHostToDevice));
+      cimg_enlarge_table(len, s, at.data(), alpha.data());
+      HIP_OK(c, d_at.alloc(s));
+      HIP_OK(c, d_alpha.alloc(s));
+      HIP_OK(c, hipMemcpy(d_at.p, at.data(), s * sizeof(int), hipMemcpyHostToDevice));
+      HIP_OK(c, hipMemcpy(d_alpha.p, alpha.data(), s * sizeof(double), hipMemcpyHostToDevice));
     }
     if (s == len) {
       HIP_OK(c, hipMemcpy(out, src, (size_t)n * sw * sh * sizeof(uint32_t), hipMemcpyDeviceToDevice));
     } else {
-      hipLaunchKernelGGL(pool_resize_axis_kernel, dim3(2048), dim3(256), 0, 0, src, out, n, sw, sh, s, along_x, d_at, d_alpha);
+      hipLaunchKernelGGL(pool_resize_axis_kernel, dim3(2048), dim3(256), 0, 0, src, out, n, sw, sh, s, along_x, d_at.p, d_alpha.p);
       HIP_OK(c, hipGetLastError());
     }
-    HIP_OK(c, hipDeviceSynchronize());
-    if (d_at) { (void)hipFree(d_at); (void)hipFree(d_alpha); }
+    HIP_OK(c, hipDeviceSynchronize());  // (the tables go with this scope)
     return OFDG_OK;
   };
-  int rc = pass(images, mid, w, h, tw, 1);
-  if (rc == OFDG_OK) rc = pass(mid, out_images, tw, h, th, 0);
-  (void)hipFree(mid);
-  return rc;
+  OFDG_TRY(pass(images, mid.p, w, h, tw, 1));
+  return pass(mid.p, out_images, tw, h, th, 0);
 }
-static int pool_resized_copy(ofdg_ctx* c, int tw, int th, uint32_t** dst) {
-  if (*dst) { HIP_OK(c, hipFree(*dst)); *dst = nullptr; }
-  HIP_OK(c, hipMalloc((void**)dst, (size_t)c->pool_n * tw * th * sizeof(uint32_t)));
-  return resize_images(c, c->pool, c->pool_n, c->pool_w, c->pool_h, tw, th, *dst);
+static int pool_resized_copy(ofdg_ctx* c, int tw, int th, DevBuf<uint32_t>& dst) {
+  HIP_OK(c, dst.alloc((size_t)c->pool_n * tw * th));
+  return resize_images(c, c->pool.p, c->pool_n, c->pool_w, c->pool_h, tw, th, dst.p);
 }
 // the tw x th texture of ONE image of any size (getRandomizedCrop with default arguments, DG:96-106):
 // its centre crop if it is large enough, else the resized whole image
@@ -817,18 +719,18 @@ static int finalise_pool(ofdg_ctx* c) {
   HIP_OK(c, hipDeviceSynchronize());
   const int W = c->prm.width, H = c->prm.height, w = c->pool_w, h = c->pool_h;
   const uint64_t img = (uint64_t)w * h;
-  if (c->pool_fg) { (void)hipFree(c->pool_fg); c->pool_fg = nullptr; }
-  if (c->pool_bg) { (void)hipFree(c->pool_bg); c->pool_bg = nullptr; }
+  c->pool_fg.release();
+  c->pool_bg.release();
   if (w >= W && h >= H) {
     c->fg_src = TexSource{img, (uint64_t)(h / 2 - H / 2) * w + (uint64_t)(w / 2 - W / 2), w, 0};
   } else {
-    OFDG_TRY(pool_resized_copy(c, W, H, &c->pool_fg));
+    OFDG_TRY(pool_resized_copy(c, W, H, c->pool_fg));
     c->fg_src = TexSource{(uint64_t)W * H, 0, W, 0};
   }
   if (w >= 2 * W && h >= 2 * H) {
     c->bg_src = TexSource{img, (uint64_t)(h / 2 - H) * w + (uint64_t)(w / 2 - W), w, 0};
   } else {
-    OFDG_TRY(pool_resized_copy(c, 2 * W, 2 * H, &c->pool_bg));
+    OFDG_TRY(pool_resized_copy(c, 2 * W, 2 * H, c->pool_bg));
     c->bg_src = TexSource{(uint64_t)4 * W * H, 0, 2 * W, 0};
   }
   c->pool_final = true;
@@ -838,14 +740,14 @@ static int finalise_pool(ofdg_ctx* c) {
 // background_prep on a mixed pool: the per-image table (address, size) on the device, and the workspace the staged chain
 // needs for the largest crop of a rotated image
 static int ensure_tex_table(ofdg_ctx* c) {
-  if (!c->pool_mixed || !c->prm.background_prep || c->d_tex_table) return OFDG_OK;
+  if (!c->pool_mixed || !c->prm.background_prep || c->d_tex_table.p) return OFDG_OK;
   c->tex_table.resize((size_t)c->pool_n);
   for (int i = 0; i < c->pool_n; ++i) {
-    if (!c->mixed_images[(size_t)i]) { c->err = "background_prep: image " + std::to_string(i) + " of the mixed pool has not been uploaded"; return OFDG_ETEXTURES; }
-    c->tex_table[(size_t)i] = DevTexEntry{(uint64_t)(uintptr_t)c->mixed_images[(size_t)i], c->mixed_sizes[(size_t)i].first, c->mixed_sizes[(size_t)i].second};
+    if (!c->mixed_images[(size_t)i].p) { c->err = "background_prep: image " + std::to_string(i) + " of the mixed pool has not been uploaded"; return OFDG_ETEXTURES; }
+    c->tex_table[(size_t)i] = DevTexEntry{(uint64_t)(uintptr_t)c->mixed_images[(size_t)i].p, c->mixed_sizes[(size_t)i].first, c->mixed_sizes[(size_t)i].second};
   }
-  HIP_OK(c, hipMalloc((void**)&c->d_tex_table, c->tex_table.size() * sizeof(DevTexEntry)));
-  HIP_OK(c, hipMemcpy(c->d_tex_table, c->tex_table.data(), c->tex_table.size() * sizeof(DevTexEntry), hipMemcpyHostToDevice));
+  HIP_OK(c, c->d_tex_table.alloc(c->tex_table.size()));
+  HIP_OK(c, hipMemcpy(c->d_tex_table.p, c->tex_table.data(), c->tex_table.size() * sizeof(DevTexEntry), hipMemcpyHostToDevice));
   return OFDG_OK;
 }
 // `fusable`: every pool image is at least 2W x 2H, so a crop is at most 4/3 of the texture (beyond that it is refused), which
@@ -874,6 +776,36 @@ static int reserve_workspaces(ofdg_ctx* c, size_t n_shapes) {
   return OFDG_OK;
 }
 
+// the slot's count of raster work items: allocated, cleared and waited for once
+static int ensure_item_count(ofdg_ctx* c, ofdg_ctx::Slot& sl) {
+  if (sl.d_item_count.p) return OFDG_OK;
+  HIP_OK(c, sl.d_item_count.alloc(1));
+  HIP_OK(c, hipMemset(sl.d_item_count.p, 0, sizeof(int)));
+  HIP_OK(c, hipDeviceSynchronize());
+  return OFDG_OK;
+}
+// What slot `sl` (and the chains) need for a batch of n_samples samples with n_shapes outlines.  n_objects > 0: the records are
+// written on the device (counter sampler), so the slot owns them too; 0: they are views of the uploaded arena (upload_slot).
+// The reservations come in the order they always had.
+static int size_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n_samples, size_t n_shapes, size_t n_objects = 0) {
+  const int W = c->prm.width, H = c->prm.height;
+  if (n_objects) HIP_OK(c, sl.d_shapes.reserve(n_shapes));
+  HIP_OK(c, sl.d_frames.reserve(n_shapes * 2));
+  HIP_OK(c, sl.d_verts.reserve(n_shapes * 2 * kMaxVerts));
+  if (n_objects) {
+    HIP_OK(c, sl.d_objects.reserve(n_objects));
+    HIP_OK(c, sl.d_samples.reserve(n_samples));
+  }
+  OFDG_TRY(reserve_workspaces(c, n_shapes));
+  HIP_OK(c, sl.d_items.reserve(n_shapes * 2 * (size_t)((H + kBandRows - 1) / kBandRows) * ((W + kChunkW - 1) / kChunkW) + 1));
+  OFDG_TRY(reserve_blockmask(c, sl, n_samples));
+  if (n_objects && c->prm.background_prep) {
+    HIP_OK(c, sl.d_bgprep.reserve(n_samples));
+    HIP_OK(c, sl.d_bgtex.reserve((size_t)n_samples * 4 * W * H));
+  }
+  return ensure_item_count(c, sl);
+}
+
 // ---- render -------------------------------------------------------------------------------
 // device counter sampler + device realize fill the slot's records (no host data)
 static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop = nullptr);
@@ -882,7 +814,7 @@ static int launch_counter_sampler(ofdg_ctx* c, ofdg_ctx::Slot& sl, long long fir
   const int prep = c->prm.background_prep ? 1 : 0;
   CsRealizeDims D{c->prm.width, c->prm.height, c->pool_n, c->pool_w, c->pool_h, sl.res_samples, stride, prep,
                   c->prm.mode == 9 ? c->crop_server.n_crops : 0, c->fg_src.stride, c->fg_src.origin, c->bg_src.stride, c->bg_src.origin,
-                  (unsigned long long)(uintptr_t)c->pool, c->d_tex_table, c->prm.mode == 9 ? c->d_cs_croptab : nullptr};
+                  (unsigned long long)(uintptr_t)c->pool.p, c->d_tex_table.p, c->prm.mode == 9 ? c->d_cs_croptab.p : nullptr};
   hipLaunchKernelGGL(cs_sample_realize_kernel, dim3(sl.res_samples * kCsGroups), dim3(64), 0, s, c->cs_mode, D, first_index,
                      sl.d_shapes.p, sl.d_objects.p, sl.d_samples.p, err, sl.d_bgprep.p);
   HIP_OK(c, hipGetLastError());
@@ -900,14 +832,14 @@ static ofdg_ctx::Chain& take_chain(ofdg_ctx* c) {
   return c->chains[k];
 }
 // the stream chain `ch` works on for a call made with the caller's stream `st`
-static hipStream_t chain_stream(const ofdg_ctx* c, const ofdg_ctx::Chain& ch, hipStream_t st) { return c->overlap ? ch.stream : st; }
+static hipStream_t chain_stream(const ofdg_ctx* c, const ofdg_ctx::Chain& ch, hipStream_t st) { return c->overlap ? ch.stream.s : st; }
 
 // A prepared batch that will never be composed (the caller's sequence jumped, the pool changed, the chain's private slot is
 // needed for something else): forget it.  compose is what resets the slot's raster work list, so do that here.
 static int discard_prepared(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
   if (!ch.prep.valid) return OFDG_OK;
   ch.prep.valid = false;
-  if (ch.prep.slot && ch.prep.slot->d_item_count) HIP_OK(c, hipMemsetAsync(ch.prep.slot->d_item_count, 0, sizeof(int), ch.prep.stream));
+  if (ch.prep.slot && ch.prep.slot->d_item_count.p) HIP_OK(c, hipMemsetAsync(ch.prep.slot->d_item_count.p, 0, sizeof(int), ch.prep.stream));
   // ... and what its kernels flagged is nobody's: the batch is never handed over (its word must not speak for ticket + kErrWords,
   // nor make ofdg_synchronize report a batch that was never composed)
   if (ch.prep.ticket >= 0 && ch.prep.ticket + ofdg_ctx::kErrWords > c->ticket) {
@@ -962,7 +894,7 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   OFDG_TRY(discard_prepared(c, ch));
   const long long ticket = c->ticket++;  // this batch's number: its kernels raise their flags in its own word
   uint32_t* const err = err_word(c, ticket);
-  hipEvent_t* ev = nullptr;
+  Event* ev = nullptr;
   if (c->profiling && c->ev_sets > 0 && (c->launch_count % c->ev_stride) == 0) {
     const size_t set = (size_t)(c->ev_alloc++ % c->ev_sets);
     ev = &c->ev[set * 6];
@@ -985,7 +917,7 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   if (ch.done_pending && ch.done_stream != S) OFDG_TRY(wait_unless_fired(c, S, ch.ev_done, &ch.done_pending, /*settles=*/true));
   if (sl.compose_pending && sl.compose_stream != S) OFDG_TRY(wait_unless_fired(c, S, sl.compose_event, &sl.compose_pending));
   // mode 9: the batch's own crop table (host path) or the static table of all crops (counter sampler)
-  const DevCropRef* croptab = cs_first_index >= 0 ? c->d_cs_croptab : sl.d_croptab.p;
+  const DevCropRef* croptab = cs_first_index >= 0 ? c->d_cs_croptab.p : sl.d_croptab.p;
   HIP_OK(c, take_err_word(c, ticket, S));  // (nothing is enqueued unless this caller asks by ticket AND the word's last owner was never asked about)
   if (cs_first_index >= 0) {  // device counter sampler + device realize
     OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, err));
@@ -1005,8 +937,8 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   // ~6-10 us: geom (first of the three) and compose (ev[4], launch_compose) have one, raster has none.
   // geom: outlines, boxes, raster work list -> raster: coverage slots + block masks (persistent waves over the list)
   hipExtLaunchKernelGGL(geom_kernel, dim3(std::max(1, (n_sf + kGeomWaves - 1) / kGeomWaves)), dim3(64 * kGeomWaves), 0, S,
-                        prof_prep ? ev[0] : nullptr, prof_prep ? ev[1] : nullptr, 0, sl.d_shapes.p, sl.res_shapes, c->d_cs_tab, W, H,
-                        sl.d_frames.p, sl.d_verts.p, box_cur, err, sl.d_item_count, sl.d_items.p, croptab);
+                        prof_prep ? ev[0].e : nullptr, prof_prep ? ev[1].e : nullptr, 0, sl.d_shapes.p, sl.res_shapes, c->d_cs_tab.p, W, H,
+                        sl.d_frames.p, sl.d_verts.p, box_cur, err, sl.d_item_count.p, sl.d_items.p, croptab);
   HIP_OK(c, hipGetLastError());
   // The batch's last preparation kernel - raster, or the background preparation behind it - carries two things on its own
   // packet: the hand-over event of a compose on a caller's stream, or (profiling 1) the start of the compose launch's time.
@@ -1014,14 +946,14 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   // compose is 4 % faster in the steady state than with the preparation behind the sampler (the latency-bound kernels of a
   // chain follow each other, the two heavy ones too; profiles/r04_experiments_log.md section 11).
   const bool prep_last = sl.bgprep_pending;
-  hipEvent_t last_stop = ev ? (c->profiling == 2 ? nullptr : ev[4]) : (hand_over ? ch.ev_prep : nullptr);
+  hipEvent_t last_stop = ev ? (c->profiling == 2 ? nullptr : ev[4].e) : (hand_over ? ch.ev_prep.e : nullptr);
   // (a profiled batch with a preparation behind raster also takes raster's completion: the preparation is timed from there)
   hipExtLaunchKernelGGL(raster_kernel, dim3(kRasterGrid * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, S, nullptr,
-                        (ev && (c->profiling == 2 || prep_last)) ? ev[3] : (prep_last ? nullptr : last_stop), 0,
-                        sl.d_frames.p, sl.d_items.p, sl.d_item_count, sl.d_verts.p, W, H, cov, box_next, n_mask_words, box_cur);
+                        (ev && (c->profiling == 2 || prep_last)) ? ev[3].e : (prep_last ? nullptr : last_stop), 0,
+                        sl.d_frames.p, sl.d_items.p, sl.d_item_count.p, sl.d_verts.p, W, H, cov, box_next, n_mask_words, box_cur);
   HIP_OK(c, hipGetLastError());
   if (prep_last) {
-    OFDG_TRY(prepare_backgrounds(c, sl, sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2] : last_stop));
+    OFDG_TRY(prepare_backgrounds(c, sl, sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2].e : last_stop));
     sl.bgprep_pending = false;
     if (ev) c->ev_bgprep[(size_t)(ev - c->ev.data()) / 6] = 1;
   }
@@ -1157,22 +1089,22 @@ static int launch_compose_kernels(ofdg_ctx* c, const ofdg_ctx::Chain& ch, const 
   const int W = c->prm.width, H = c->prm.height;
   const RenderDims dm = render_dims(c, sl);
   const int grid = dm.tiles_x * dm.tiles_y * dm.n_samples * 4;  // one 64 x 4 strip per single-wave workgroup
-  hipEvent_t* const ev = ch.prep.ev;
+  Event* const ev = ch.prep.ev;
   // the variant, decided here once (the optional outputs exist in the rigid modes only: check_extras)
   enum class Kind { kRigid, kRigidExt, kRigidFmt, kRigidExtFmt, kDeform, kDeformFmt };
   const Kind kind = c->prm.mode == 9 ? (o.out_fmt ? Kind::kDeformFmt : Kind::kDeform)
                                      : x.fmt ? Kind::kRigidExtFmt : x.any ? Kind::kRigidExt : o.out_fmt ? Kind::kRigidFmt : Kind::kRigid;
   const bool pow2 = (W & (W - 1)) == 0;
-  const Launch lc{(unsigned)grid, 64, cs, (ev && c->profiling == 2) ? ev[4] : nullptr, ev ? ev[5] : (x.occ ? nullptr : done)};
+  const Launch lc{(unsigned)grid, 64, cs, (ev && c->profiling == 2) ? ev[4].e : nullptr, ev ? ev[5].e : (x.occ ? nullptr : done)};
   // every family has a _pow2 and a general kernel of one function type: this is the one place a compose kernel is launched
   auto compose = [&](auto* k_pow2, auto* k, auto... args) { launch_kernel(lc, pow2 ? k_pow2 : k, args...); };
   auto rigid = [&](auto* k_pow2, auto* k, auto... tail) {
     compose(k_pow2, k, sl.d_samples.p, ch.prep.box_cur, sl.d_objects.p, ch.cov.p, grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch,
-            dm.fg_pitch, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p, sl.d_item_count, tail...);
+            dm.fg_pitch, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p, sl.d_item_count.p, tail...);
   };
   auto deform = [&](auto* k_pow2, auto* k, auto... tail) {
     compose(k_pow2, k, dm, sl.d_samples.p, sl.d_objects.p, ch.prep.box_cur, ch.cov.p, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p,
-            ch.prep.croptab, sl.d_item_count, tail...);
+            ch.prep.croptab, sl.d_item_count.p, tail...);
   };
   switch (kind) {
     case Kind::kRigid: rigid(compose_rigid_pow2_kernel, compose_rigid_kernel); break;
@@ -1198,7 +1130,7 @@ static int launch_compose_kernels(ofdg_ctx* c, const ofdg_ctx::Chain& ch, const 
 
 // What a compose launch leaves behind on the host: the profiled launch's event set, and who has to wait for it.
 static int note_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, hipStream_t cs, bool foreign, hipEvent_t done) {
-  if (hipEvent_t* const ev = ch.prep.ev) {
+  if (Event* const ev = ch.prep.ev) {
     if (done) HIP_OK(c, hipEventRecord(done, cs));
     // profiling 1 times compose from the completion of the chain's last preparation kernel: that is the launch's time only
     // when compose is enqueued right behind it on the same stream.  A batch prepared ahead by an earlier call, or composed
@@ -1222,8 +1154,8 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, const CallOut& o, hi
   ofdg_ctx::Slot& sl = *ch.prep.slot;
   ComposeExtras x;
   OFDG_TRY(plan_extras(c, ch, sl.res_samples, o, &x));
-  const uint32_t* bgpool = c->prm.background_prep ? sl.d_bgtex.p : (c->pool_bg ? c->pool_bg : c->pool);  // (after the slot's buffers are final)
-  const uint32_t* fgpool = c->pool_fg ? c->pool_fg : c->pool;
+  const uint32_t* bgpool = c->prm.background_prep ? sl.d_bgtex.p : (c->pool_bg.p ? c->pool_bg.p : c->pool.p);  // (after the slot's buffers are final)
+  const uint32_t* fgpool = c->pool_fg.p ? c->pool_fg.p : c->pool.p;
   if (c->prm.background_prep && !bgpool) { c->err = "background_prep: the slot has no prepared backgrounds"; return OFDG_EINVAL; }
   c->last_slot = &sl; c->last_ch = &ch;
   c->last_stream = ch.prep.stream; c->last_ticket = ch.prep.ticket;
@@ -1234,7 +1166,7 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, const CallOut& o, hi
   // It is tracked by the chain's event whenever somebody else may have to wait for it: the chain itself (workspace, private
   // slot) after a compose on a caller's stream, other chains for a shared slot.
   const bool shared_slot = &sl != &ch.slot;
-  const hipEvent_t done = (foreign || shared_slot) ? ch.ev_done : nullptr;
+  const hipEvent_t done = (foreign || shared_slot) ? ch.ev_done.e : nullptr;
   OFDG_TRY(launch_compose_kernels(c, ch, sl, o, x, fgpool, bgpool, cs, done));
   return note_compose(c, ch, sl, cs, foreign, done);
 }
@@ -1246,8 +1178,8 @@ static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl,
   return launch_compose(c, ch, o, st);
 }
 
-// CImg get_resize(.., 3), enlarging branch: source index and weight of every destination pixel (running double sums,
-// boundary 0) for EVERY source length n < s, entry [n * s + x]; once per context and frame size
+// CImg get_resize(.., 3), enlarging branch: source index and weight of every destination pixel (cimg_enlarge_table) for
+// EVERY source length n < s, entry [n * s + x]; once per context and frame size
 constexpr int kPrepGrid = 4096;  // single-wave workgroups of bgprep_stream_kernel: four per SIMD (2048 / 3072 / 8192: -6 % / -2 % / -1 %, profiles/r05_experiments_log.md section 2)
 static int ensure_bgprep_tables(ofdg_ctx* c) {
   const int TW = 2 * c->prm.width, TH = 2 * c->prm.height;
@@ -1255,18 +1187,7 @@ static int ensure_bgprep_tables(ofdg_ctx* c) {
   auto build = [&](int s, DevBuf<uint16_t>& d_at, DevBuf<double>& d_alpha) -> int {
     std::vector<uint16_t> at((size_t)s * s, 0);
     std::vector<double> alpha((size_t)s * s, 0.0);
-    for (int n = 1; n < s; ++n) {
-      const double f = s > 1 ? (n - 1.) / (s - 1) : 0;
-      double curr = 0, old = 0;
-      int pos = 0;
-      for (int x = 0; x < s; ++x) {
-        alpha[(size_t)n * s + x] = curr - (unsigned int)curr;
-        at[(size_t)n * s + x] = (uint16_t)pos;
-        old = curr;
-        curr = std::min(n - 1., curr + f);
-        pos += (int)((unsigned int)curr - (unsigned int)old);
-      }
-    }
+    for (int n = 1; n < s; ++n) cimg_enlarge_table(n, s, &at[(size_t)n * s], &alpha[(size_t)n * s]);
     HIP_OK(c, d_at.reserve(at.size()));
     HIP_OK(c, d_alpha.reserve(alpha.size()));
     HIP_OK(c, hipMemcpy(d_at.p, at.data(), at.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -1305,7 +1226,7 @@ static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool reco
   const DevResizeTabs T{c->d_bg_at_x.p, c->d_bg_alpha_x.p, c->d_bg_at_y.p, c->d_bg_alpha_y.p};
   if (fusable && n <= kPrepMaxSamples) {
     hipExtLaunchKernelGGL(bgprep_stream_kernel, dim3(kPrepGrid), dim3(64), (size_t)(n + 1) * sizeof(int), s, nullptr, stop, 0, sl.d_bgprep.p, T, W, H, n, cap_cw, cap_ch, sl.d_bgtex.p, err,
-                          c->d_prep_paths);
+                          c->d_prep_paths.p);
     HIP_OK(c, hipGetLastError());
     return OFDG_OK;
   }
@@ -1322,11 +1243,11 @@ static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool reco
 //   `shared`: the slot may be rendered on other streams than `st` (a caller's slot): the upload is tracked by an event
 static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, int n_tasks, const ofdg_blueprint* bps,
                        int n_bps, hipStream_t st, ofdg_ctx::Stage& stage, bool shared) {
-  if (!c->pool && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
+  if (!c->pool.p && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
   OFDG_TRY(finalise_pool(c));
   OFDG_TRY(ensure_tex_table(c));
   RealizeConfig cfg{c->prm.width, c->prm.height, c->prm.mode, c->pool_n, c->pool_w, c->pool_h, c->prm.background_prep};
-  cfg.pool_addr = (uint64_t)(uintptr_t)c->pool;
+  cfg.pool_addr = (uint64_t)(uintptr_t)c->pool.p;
   cfg.tex_table = c->pool_mixed && c->prm.background_prep ? c->tex_table.data() : nullptr;
   cfg.fg_stride = c->fg_src.stride; cfg.fg_origin = c->fg_src.origin; cfg.bg_stride = c->bg_src.stride; cfg.bg_origin = c->bg_src.origin;
   // the previous copies out of this staging buffer must have left it
@@ -1357,26 +1278,9 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
   HIP_OK(c, sl.d_objects.alias((DevObject*)(sl.d_rec.p + b_shapes), n_obj));
   HIP_OK(c, sl.d_samples.alias((DevSample*)(sl.d_rec.p + b_shapes + b_obj), (size_t)n_tasks));
   if (b_prep) HIP_OK(c, sl.d_bgprep.alias((DevBgPrep*)(sl.d_rec.p + b_shapes + b_obj + b_smp), B.bgprep.size()));
-  HIP_OK(c, sl.d_frames.reserve(n_shapes * 2));
-  HIP_OK(c, sl.d_verts.reserve(n_shapes * 2 * kMaxVerts));
-  {
-    const int W = c->prm.width, H = c->prm.height;
-    OFDG_TRY(reserve_workspaces(c, n_shapes));
-    HIP_OK(c, sl.d_items.reserve(n_shapes * 2 * (size_t)((H + kBandRows - 1) / kBandRows) * ((W + kChunkW - 1) / kChunkW) + 1));
-    OFDG_TRY(reserve_blockmask(c, sl, n_tasks));
-    if (!sl.d_item_count) {
-      HIP_OK(c, hipMalloc((void**)&sl.d_item_count, sizeof(int)));
-      HIP_OK(c, hipMemset(sl.d_item_count, 0, sizeof(int)));
-      HIP_OK(c, hipDeviceSynchronize());
-    }
-  }
-  if (need > stage.bytes) {
-    if (stage.h) HIP_OK(c, hipHostFree(stage.h));
-    stage.h = nullptr;
-    HIP_OK(c, hipHostMalloc(&stage.h, need * 2, hipHostMallocDefault));
-    stage.bytes = need * 2;
-  }
-  char* hs = (char*)stage.h;
+  OFDG_TRY(size_slot(c, sl, n_tasks, n_shapes));
+  if (need > stage.h.bytes) HIP_OK(c, stage.h.alloc(need * 2, hipHostMallocDefault));
+  char* hs = (char*)stage.h.p;
   if (n_shapes) std::memcpy(hs, B.shapes.data(), n_shapes * sizeof(DevShape));
   std::memcpy(hs + b_shapes, B.objects.data(), n_obj * sizeof(DevObject));
   std::memcpy(hs + b_shapes + b_obj, B.samples.data(), (size_t)n_tasks * sizeof(DevSample));
@@ -1397,16 +1301,12 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
     std::vector<DevCropRef> tab(B.crops.size());
     size_t bg_at = 0;
     for (size_t k = 0; k < B.crops.size(); ++k) {
-      const float* src = c->d_warp + (size_t)B.crops[k].crop * crop_floats;
+      const float* src = c->d_warp.p + (size_t)B.crops[k].crop * crop_floats;
       if (B.crops[k].background) {
-        float* dst = sl.d_bgwarp.p + bg_at * bg_floats;
-        hipLaunchKernelGGL(wf_resize2_kernel, dim3((2 * W * 2 * H + 255) / 256), dim3(256), 0, st, src, W + 1, H + 1, 2 * W, 2 * H,
-                           c->d_rs_xi, c->d_rs_xa, c->d_rs_yi, c->d_rs_ya, dst, sl.d_bgwarp_max.p + bg_at);
-        HIP_OK(c, hipGetLastError());
-        tab[k] = make_crop_ref(dst, sl.d_bgwarp_max.p + bg_at, 2 * W, 2 * H);
+        OFDG_TRY(upscale_crop(c, src, sl.d_bgwarp.p + bg_at * bg_floats, sl.d_bgwarp_max.p + bg_at, st, &tab[k]));
         ++bg_at;
       } else {
-        tab[k] = make_crop_ref(src, c->d_warp_max + B.crops[k].crop, W + 1, H + 1);
+        tab[k] = make_crop_ref(src, c->d_warp_max.p + B.crops[k].crop, W + 1, H + 1);
       }
     }
     // small table: a synchronous copy from pageable memory is fine here (upload path)
@@ -1426,7 +1326,7 @@ static int upload_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, const ofdg_task* tasks, 
   HIP_OK(c, hipEventRecord(stage.free_ev, st));
   stage.pending = true;
   if (shared) {
-    if (!sl.ev_uploaded) HIP_OK(c, hipEventCreateWithFlags(&sl.ev_uploaded, hipEventDisableTiming));
+    if (!sl.ev_uploaded.e) HIP_OK(c, sl.ev_uploaded.create(hipEventDisableTiming));
     HIP_OK(c, hipEventRecord(sl.ev_uploaded, st));
     sl.upload_pending = true;
     sl.upload_stream = st;
@@ -1533,7 +1433,7 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   // kernel carries the chain's completion event, as a compose on a caller's stream does (launch_compose): a later call
   // that reuses the slot or the chain's workspaces waits for it.
   const bool tracked = st != S || &sl != &ch.slot;
-  const hipEvent_t done = tracked ? ch.ev_done : nullptr;
+  const hipEvent_t done = tracked ? ch.ev_done.e : nullptr;
   const bool reduce = d_label0 || d_label1;
   DevObjectRow* const rows = reinterpret_cast<DevObjectRow*>(d_rows);
   const long long cells = (long long)n * rows_per_sample;
@@ -1601,30 +1501,13 @@ static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
   if (c->prm.mode == 9) OFDG_TRY(ensure_counter_croptab(c));
   OFDG_TRY(finalise_pool(c));
   OFDG_TRY(ensure_tex_table(c));
-  if (!c->pool && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
+  if (!c->pool.p && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
   if (n < 1 || n > 512) { c->err = "counter sampler: batch must be 1..512 samples"; return OFDG_EINVAL; }
-  const int W = c->prm.width, H = c->prm.height;
   // outline slots per sample: the worst case, so that no sample can run out (composites have up to 7 parts)
   const int max_objects = c->prm.num_objects > 0 ? std::min(c->prm.num_objects, kCsMaxObjects) : 24;
   const size_t shapes_cap = (size_t)n * (size_t)(c->prm.mode >= 6 ? max_objects * 7 : max_objects);
   const size_t n_obj = (size_t)n * (1 + kCsMaxObjects);
-  HIP_OK(c, sl.d_shapes.reserve(shapes_cap));
-  HIP_OK(c, sl.d_frames.reserve(shapes_cap * 2));
-  HIP_OK(c, sl.d_verts.reserve(shapes_cap * 2 * kMaxVerts));
-  HIP_OK(c, sl.d_objects.reserve(n_obj));
-  HIP_OK(c, sl.d_samples.reserve(n));
-  OFDG_TRY(reserve_workspaces(c, shapes_cap));
-  HIP_OK(c, sl.d_items.reserve(shapes_cap * 2 * (size_t)((H + kBandRows - 1) / kBandRows) * ((W + kChunkW - 1) / kChunkW) + 1));
-  OFDG_TRY(reserve_blockmask(c, sl, n));
-  if (c->prm.background_prep) {
-    HIP_OK(c, sl.d_bgprep.reserve(n));
-    HIP_OK(c, sl.d_bgtex.reserve((size_t)n * 4 * W * H));
-  }
-  if (!sl.d_item_count) {
-    HIP_OK(c, hipMalloc((void**)&sl.d_item_count, sizeof(int)));
-    HIP_OK(c, hipMemset(sl.d_item_count, 0, sizeof(int)));
-    HIP_OK(c, hipDeviceSynchronize());
-  }
+  OFDG_TRY(size_slot(c, sl, n, shapes_cap, n_obj));
   sl.res_samples = n;
   sl.res_shapes = (int)shapes_cap;
   sl.res_objects = (int)n_obj;
@@ -1708,7 +1591,7 @@ int ofdg_forward_counter_ex_fmt(ofdg_ctx* c, long long first_index, int n_sample
 int ofdg_num_chains(const ofdg_ctx* c) { return c ? c->n_chains : OFDG_EINVAL; }
 void* ofdg_stream(ofdg_ctx* c) {
   if (!c) return nullptr;
-  return (void*)c->chains[c->next_chain % (unsigned)c->n_chains].stream;
+  return (void*)c->chains[c->next_chain % (unsigned)c->n_chains].stream.s;
 }
 
 // Download the blueprints the counter sampler produces for samples first_index.. (tests):
@@ -1830,7 +1713,7 @@ int ofdg_synchronize(ofdg_ctx* c, void* stream) {
     if (c->chains[k].done_pending) HIP_OK(c, hipEventSynchronize(c->chains[k].ev_done));  // (a compose on another caller stream)
   }
   uint32_t words[ofdg_ctx::kErrWords];
-  HIP_OK(c, hipMemcpy(words, c->d_err, sizeof(words), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(words, c->d_err.p, sizeof(words), hipMemcpyDeviceToHost));
   uint32_t e = 0;
   long long first_bad = -1;
   for (int i = 0; i < ofdg_ctx::kErrWords; ++i)
@@ -1840,7 +1723,7 @@ int ofdg_synchronize(ofdg_ctx* c, void* stream) {
       const long long q = c->ticket - 1 - ((c->ticket - 1 - i) % ofdg_ctx::kErrWords + ofdg_ctx::kErrWords) % ofdg_ctx::kErrWords;
       if (first_bad < 0 || q < first_bad) first_bad = q;
     }
-  if (e) HIP_OK(c, hipMemset(c->d_err, 0, sizeof(words)));
+  if (e) HIP_OK(c, hipMemset(c->d_err.p, 0, sizeof(words)));
   if (c->word_reserved < 0) std::fill(c->word_clean, c->word_clean + ofdg_ctx::kErrWords, true);  // (nothing in flight, every word read)
   if (e) {
     c->err = err_text(e) + " (first in batch " + std::to_string(first_bad) + " of this context, or one " + std::to_string(ofdg_ctx::kErrWords) + " calls earlier)";
@@ -1852,16 +1735,16 @@ int ofdg_synchronize(ofdg_ctx* c, void* stream) {
 // The device-side error flags without waiting for anything in flight (a prefetch ring checks them when it hands
 // a finished batch over; flags of younger batches are reported at their own hand-over at the latest).
 static int poll_words(ofdg_ctx* c, int first, int n, uint32_t* flags) {
-  if (!c->h_err) HIP_OK(c, hipHostMalloc((void**)&c->h_err, sizeof(uint32_t), hipHostMallocMapped));
-  if (!c->err_stream) HIP_OK(c, hipStreamCreateWithFlags(&c->err_stream, hipStreamNonBlocking));
+  if (!c->h_err.p) HIP_OK(c, c->h_err.alloc(sizeof(uint32_t), hipHostMallocMapped));
+  if (!c->err_stream.s) HIP_OK(c, c->err_stream.create(hipStreamNonBlocking));
   // read AND clear in one atomic exchange per word (younger batches are still running and may raise a flag at any time: a
   // copy followed by a memset would lose what is raised in between)
   uint32_t* h_dev = nullptr;
-  HIP_OK(c, hipHostGetDevicePointer((void**)&h_dev, c->h_err, 0));
-  hipLaunchKernelGGL(err_exchange_kernel, dim3(1), dim3(64), 0, c->err_stream, c->d_err + first, n, h_dev);
+  HIP_OK(c, hipHostGetDevicePointer((void**)&h_dev, c->h_err.p, 0));
+  hipLaunchKernelGGL(err_exchange_kernel, dim3(1), dim3(64), 0, c->err_stream, c->d_err.p + first, n, h_dev);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipStreamSynchronize(c->err_stream));
-  *flags = *c->h_err;
+  *flags = *(const uint32_t*)c->h_err.p;
   return OFDG_OK;
 }
 int ofdg_poll_errors(ofdg_ctx* c) {
@@ -1892,11 +1775,9 @@ static int warp_alloc(ofdg_ctx* c, int n_crops) {
   const size_t crop_floats = (size_t)4 * (c->prm.width + 1) * (c->prm.height + 1);
   HIP_OK(c, hipDeviceSynchronize());
   drop_counter_croptab(c);
-  if (c->d_warp) { HIP_OK(c, hipFree(c->d_warp)); c->d_warp = nullptr; }
-  if (c->d_warp_max) { HIP_OK(c, hipFree(c->d_warp_max)); c->d_warp_max = nullptr; }
-  HIP_OK(c, hipMalloc((void**)&c->d_warp, (size_t)n_crops * crop_floats * sizeof(float)));
-  HIP_OK(c, hipMalloc((void**)&c->d_warp_max, (size_t)n_crops * sizeof(unsigned)));
-  HIP_OK(c, hipMemset(c->d_warp_max, 0, (size_t)n_crops * sizeof(unsigned)));
+  HIP_OK(c, c->d_warp.alloc((size_t)n_crops * crop_floats));
+  HIP_OK(c, c->d_warp_max.alloc((size_t)n_crops));
+  HIP_OK(c, hipMemset(c->d_warp_max.p, 0, (size_t)n_crops * sizeof(unsigned)));
   c->crop_server = CropServer();
   c->crop_server.n_crops = n_crops;
   return OFDG_OK;
@@ -1916,38 +1797,35 @@ int ofdg_warp_generate(ofdg_ctx* c, int n_fields, uint32_t seed) {
   if (org.empty()) { c->err = "frame too small for warp crops"; return OFDG_EINVAL; }
   OFDG_TRY(warp_alloc(c, n_fields * (int)org.size()));
   const size_t n = (size_t)S * S;
-  float *fa = nullptr, *fb = nullptr;
-  uint8_t* flagged = nullptr;
-  DevDisplacer* dd = nullptr;
-  HIP_OK(c, hipMalloc((void**)&fa, 4 * n * sizeof(float)));
-  HIP_OK(c, hipMalloc((void**)&fb, 4 * n * sizeof(float)));
-  HIP_OK(c, hipMalloc((void**)&flagged, 2 * n));
+  DevBuf<float> fa, fb;
+  DevBuf<uint8_t> flagged;
+  DevBuf<DevDisplacer> dd;
+  HIP_OK(c, fa.alloc(4 * n));
+  HIP_OK(c, fb.alloc(4 * n));
+  HIP_OK(c, flagged.alloc(2 * n));
   const int cw = W + 1, ch = H + 1;
   const size_t crop_floats = (size_t)4 * cw * ch;
   const int blocks = (int)((n + 255) / 256);
   for (int f = 0; f < n_fields; ++f) {
     std::vector<DevDisplacer> disp = make_device_displacers(make_displacer_params(W, H, seed + (uint32_t)f));
-    if (dd) { HIP_OK(c, hipFree(dd)); dd = nullptr; }
-    HIP_OK(c, hipMalloc((void**)&dd, std::max<size_t>(1, disp.size()) * sizeof(DevDisplacer)));
-    HIP_OK(c, hipMemcpy(dd, disp.data(), disp.size() * sizeof(DevDisplacer), hipMemcpyHostToDevice));
-    HIP_OK(c, hipMemset(flagged, 0, 2 * n));
-    hipLaunchKernelGGL(wf_sample_kernel, dim3(blocks), dim3(256), 0, 0, dd, (int)disp.size(), S, fa);
-    float *from = fa, *to = fb;
+    HIP_OK(c, dd.alloc(std::max<size_t>(1, disp.size())));
+    HIP_OK(c, hipMemcpy(dd.p, disp.data(), disp.size() * sizeof(DevDisplacer), hipMemcpyHostToDevice));
+    HIP_OK(c, hipMemset(flagged.p, 0, 2 * n));
+    hipLaunchKernelGGL(wf_sample_kernel, dim3(blocks), dim3(256), 0, 0, dd.p, (int)disp.size(), S, fa.p);
+    float *from = fa.p, *to = fb.p;
     for (int iter = 17; iter > 0; --iter) {  // WF:366, 406
-      hipLaunchKernelGGL(wf_compose_kernel, dim3(blocks, 2), dim3(256), 0, 0, from, to, S, flagged);
+      hipLaunchKernelGGL(wf_compose_kernel, dim3(blocks, 2), dim3(256), 0, 0, from, to, S, flagged.p);
       std::swap(from, to);
     }
-    hipLaunchKernelGGL(wf_finish_kernel, dim3(blocks, 2), dim3(256), 0, 0, from, S, flagged);
+    hipLaunchKernelGGL(wf_finish_kernel, dim3(blocks, 2), dim3(256), 0, 0, from, S, flagged.p);
     for (size_t k = 0; k < org.size(); ++k) {
       const size_t ci = (size_t)f * org.size() + k;
       hipLaunchKernelGGL(wf_crop_kernel, dim3((cw * ch + 255) / 256), dim3(256), 0, 0, from, S, org[k].first, org[k].second, cw, ch,
-                         c->d_warp + ci * crop_floats, c->d_warp_max + ci);
+                         c->d_warp.p + ci * crop_floats, c->d_warp_max.p + ci);
     }
     HIP_OK(c, hipGetLastError());
-    HIP_OK(c, hipDeviceSynchronize());
+    HIP_OK(c, hipDeviceSynchronize());  // (the field's temporaries are idle from here: `dd` is replaced, the others go with the scope)
   }
-  HIP_OK(c, hipFree(fa)); HIP_OK(c, hipFree(fb)); HIP_OK(c, hipFree(flagged));
-  if (dd) HIP_OK(c, hipFree(dd));
   return OFDG_OK;
 }
 
@@ -1965,7 +1843,7 @@ int ofdg_warp_upload(ofdg_ctx* c, const float* crops, int n) {
         float* dst = il.data() + (size_t)k * crop_floats + (size_t)(f >> 1) * 2 * plane + (f & 1);
         for (size_t i = 0; i < plane; ++i) dst[2 * i] = src[i];
       }
-    HIP_OK(c, hipMemcpy(c->d_warp, il.data(), il.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(c, hipMemcpy(c->d_warp.p, il.data(), il.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   std::vector<unsigned> mx(n, 0u);
   for (int k = 0; k < n; ++k) {
@@ -1974,7 +1852,7 @@ int ofdg_warp_upload(ofdg_ctx* c, const float* crops, int n) {
     for (size_t i = 0; i < 2 * plane; ++i) if (p[i] == p[i]) m = std::max(m, std::fabs(p[i]));
     std::memcpy(&mx[k], &m, sizeof(float));
   }
-  HIP_OK(c, hipMemcpy(c->d_warp_max, mx.data(), (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
+  HIP_OK(c, hipMemcpy(c->d_warp_max.p, mx.data(), (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice));
   return OFDG_OK;
 }
 
@@ -1991,7 +1869,7 @@ int ofdg_warp_download(ofdg_ctx* c, int index, float* crop) {
   const size_t crop_floats = (size_t)4 * (c->prm.width + 1) * (c->prm.height + 1);
   HIP_OK(c, hipDeviceSynchronize());
   std::vector<float> il(crop_floats);
-  HIP_OK(c, hipMemcpy(il.data(), c->d_warp + (size_t)index * crop_floats, crop_floats * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(il.data(), c->d_warp.p + (size_t)index * crop_floats, crop_floats * sizeof(float), hipMemcpyDeviceToHost));
   const size_t plane = crop_floats / 4;  // (device layout: interleaved pairs; the API's: four planes)
   for (int f = 0; f < 4; ++f) {
     const float* src = il.data() + (size_t)(f >> 1) * 2 * plane + (f & 1);
@@ -2039,14 +1917,14 @@ static int debug_rasterize_verts(ofdg_ctx* c, const std::vector<int2>& v, int n,
     for (int cx = 0; cx < W; cx += kChunkW) items.push_back(make_int4(0, b, cx, std::min(cx + kChunkW - 1, W - 1)));
   const int n_items = (int)items.size();
   HIP_OK(c, sl.d_items.reserve(items.size()));
-  if (!sl.d_item_count) HIP_OK(c, hipMalloc((void**)&sl.d_item_count, sizeof(int)));
+  OFDG_TRY(ensure_item_count(c, sl));
   HIP_OK(c, hipMemcpy(sl.d_items.p, items.data(), sizeof(int4) * items.size(), hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemcpy(sl.d_item_count, &n_items, sizeof(int), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(raster_kernel, dim3(64 * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, 0, sl.d_frames.p, sl.d_items.p, sl.d_item_count, sl.d_verts.p,
+  HIP_OK(c, hipMemcpy(sl.d_item_count.p, &n_items, sizeof(int), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(raster_kernel, dim3(64 * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, 0, sl.d_frames.p, sl.d_items.p, sl.d_item_count.p, sl.d_verts.p,
                      W, H, c->chains[0].cov.p, nullptr, 0, (unsigned long long*)nullptr);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipMemcpy(coverage_host, c->chains[0].cov.p, (size_t)W * H, hipMemcpyDeviceToHost));
-  HIP_OK(c, hipMemset(sl.d_item_count, 0, sizeof(int)));
+  HIP_OK(c, hipMemset(sl.d_item_count.p, 0, sizeof(int)));
   sl.res_samples = 0;  // (slot 0 served as scratch)
   c->last_slot = nullptr;
   return OFDG_OK;
@@ -2066,25 +1944,26 @@ int ofdg_debug_rasterize_path(ofdg_ctx* c, const double* xy, const int* types, i
   if (!c || !xy || !types || !coverage_host || n < 1 || n > 64) return OFDG_EINVAL;
   OFDG_TRY(discard_all_prepared(c));
   HIP_OK(c, hipDeviceSynchronize());
-  double* d_xy = nullptr; int* d_ty = nullptr; int2* d_v = nullptr; int* d_n = nullptr;
-  HIP_OK(c, hipMalloc((void**)&d_xy, sizeof(double) * 2 * n));
-  HIP_OK(c, hipMalloc((void**)&d_ty, sizeof(int) * n));
-  HIP_OK(c, hipMalloc((void**)&d_v, sizeof(int2) * kMaxVerts));
-  HIP_OK(c, hipMalloc((void**)&d_n, sizeof(int)));
-  HIP_OK(c, hipMemcpy(d_xy, xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemcpy(d_ty, types, sizeof(int) * n, hipMemcpyHostToDevice));
-  HIP_OK(c, hipMemset(d_v, 0, sizeof(int2) * kMaxVerts));
-  uint32_t* const dbg_err = c->d_err + ofdg_ctx::kErrWords;  // (the debug entry points' own word: no batch inherits it)
-  hipLaunchKernelGGL(debug_path_kernel, dim3(1), dim3(64), 0, 0, d_xy, d_ty, n, d_v, d_n, dbg_err);
+  DevBuf<double> d_xy;
+  DevBuf<int> d_ty, d_n;
+  DevBuf<int2> d_v;
+  HIP_OK(c, d_xy.alloc(2 * (size_t)n));
+  HIP_OK(c, d_ty.alloc(n));
+  HIP_OK(c, d_v.alloc(kMaxVerts));
+  HIP_OK(c, d_n.alloc(1));
+  HIP_OK(c, hipMemcpy(d_xy.p, xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+  HIP_OK(c, hipMemcpy(d_ty.p, types, sizeof(int) * n, hipMemcpyHostToDevice));
+  HIP_OK(c, hipMemset(d_v.p, 0, sizeof(int2) * kMaxVerts));
+  uint32_t* const dbg_err = c->d_err.p + ofdg_ctx::kErrWords;  // (the debug entry points' own word: no batch inherits it)
+  hipLaunchKernelGGL(debug_path_kernel, dim3(1), dim3(64), 0, 0, d_xy.p, d_ty.p, n, d_v.p, d_n.p, dbg_err);
   HIP_OK(c, hipGetLastError());
   uint32_t dbg_flags = 0;
   HIP_OK(c, hipMemcpy(&dbg_flags, dbg_err, sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (dbg_flags) HIP_OK(c, hipMemset(dbg_err, 0, sizeof(uint32_t)));
   std::vector<int2> v(kMaxVerts);
   int nv = 0;
-  HIP_OK(c, hipMemcpy(v.data(), d_v, sizeof(int2) * kMaxVerts, hipMemcpyDeviceToHost));
-  HIP_OK(c, hipMemcpy(&nv, d_n, sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(d_xy); (void)hipFree(d_ty); (void)hipFree(d_v); (void)hipFree(d_n);
+  HIP_OK(c, hipMemcpy(v.data(), d_v.p, sizeof(int2) * kMaxVerts, hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(&nv, d_n.p, sizeof(int), hipMemcpyDeviceToHost));
   if (dbg_flags) { c->err = "debug_rasterize_path: " + err_text(dbg_flags); return OFDG_ECAPACITY; }
   if (nv < 1 || nv > kMaxVerts) { c->err = "debug_rasterize_path: the flattened outline has " + std::to_string(nv) + " vertices"; return OFDG_ECAPACITY; }
   return debug_rasterize_verts(c, v, nv, coverage_host);
@@ -2094,13 +1973,12 @@ int ofdg_debug_rasterize_path(ofdg_ctx* c, const double* xy, const int* types, i
 // pixel of `rows` output rows of length `len` under the inverse affine inv[6] (AGG member order), before the -128.
 int ofdg_debug_dda_rows(ofdg_ctx* c, const double* inv, int rows, int len, int* out_xy) {
   if (!c || !inv || !out_xy || rows < 1 || len < 1 || (size_t)rows * len > (1u << 24)) return OFDG_EINVAL;
-  int2* d = nullptr;
-  HIP_OK(c, hipMalloc((void**)&d, sizeof(int2) * (size_t)rows * len));
+  DevBuf<int2> d;
+  HIP_OK(c, d.alloc((size_t)rows * len));
   const Mat m{inv[0], inv[1], inv[2], inv[3], inv[4], inv[5]};
-  hipLaunchKernelGGL(debug_dda_kernel, dim3((rows * len + 255) / 256), dim3(256), 0, 0, m, rows, len, d);
+  hipLaunchKernelGGL(debug_dda_kernel, dim3((rows * len + 255) / 256), dim3(256), 0, 0, m, rows, len, d.p);
   HIP_OK(c, hipGetLastError());
-  HIP_OK(c, hipMemcpy(out_xy, d, sizeof(int2) * (size_t)rows * len, hipMemcpyDeviceToHost));
-  (void)hipFree(d);
+  HIP_OK(c, hipMemcpy(out_xy, d.p, sizeof(int2) * (size_t)rows * len, hipMemcpyDeviceToHost));
   return OFDG_OK;
 }
 
@@ -2132,10 +2010,10 @@ int ofdg_debug_coverage(ofdg_ctx* c, int sample, int shape, int frame, uint8_t* 
 
 // number of raster work items left by the last launch (diagnostics)
 int ofdg_debug_item_count(ofdg_ctx* c) {
-  if (!c || !c->last_slot || !c->last_slot->d_item_count) return OFDG_EINVAL;
+  if (!c || !c->last_slot || !c->last_slot->d_item_count.p) return OFDG_EINVAL;
   int n = 0;
   if (hipDeviceSynchronize() != hipSuccess) return OFDG_EHIP;
-  if (hipMemcpy(&n, c->last_slot->d_item_count, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return OFDG_EHIP;
+  if (hipMemcpy(&n, c->last_slot->d_item_count.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return OFDG_EHIP;
   return n;
 }
 
@@ -2166,12 +2044,12 @@ int ofdg_debug_bgprep_tiles(ofdg_ctx* c, int* tiles, int* workgroups) {
 int ofdg_debug_bgprep_paths(ofdg_ctx* c, unsigned* counts9) {
   if (!c || !counts9) return OFDG_EINVAL;
   HIP_OK(c, hipDeviceSynchronize());
-  if (!c->d_prep_paths) {
-    HIP_OK(c, hipMalloc((void**)&c->d_prep_paths, 9 * sizeof(uint32_t)));
-    HIP_OK(c, hipMemset(c->d_prep_paths, 0, 9 * sizeof(uint32_t)));
+  if (!c->d_prep_paths.p) {
+    HIP_OK(c, c->d_prep_paths.alloc(9));
+    HIP_OK(c, hipMemset(c->d_prep_paths.p, 0, 9 * sizeof(uint32_t)));
   }
-  HIP_OK(c, hipMemcpy(counts9, c->d_prep_paths, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIP_OK(c, hipMemset(c->d_prep_paths, 0, 9 * sizeof(uint32_t)));
+  HIP_OK(c, hipMemcpy(counts9, c->d_prep_paths.p, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemset(c->d_prep_paths.p, 0, 9 * sizeof(uint32_t)));
   return OFDG_OK;
 }
 
@@ -2187,7 +2065,7 @@ int ofdg_set_profiling(ofdg_ctx* c, int mode) {
   if (mode && c->ev.empty()) {
     c->ev_sets = 256;
     c->ev.resize((size_t)c->ev_sets * 6);
-    for (auto& e : c->ev) HIP_OK(c, hipEventCreate(&e));
+    for (auto& e : c->ev) HIP_OK(c, e.create(hipEventDefault));
   }
   c->ev_composed.assign((size_t)c->ev_sets, 0);
   c->ev_bgprep.assign((size_t)c->ev_sets, 0);
@@ -2215,7 +2093,7 @@ int ofdg_kernel_ms(ofdg_ctx* c, const char* kernel, float* ms) {
     if (!c->ev_composed[(size_t)k]) continue;  // (never handed out, or its prepared batch was discarded before compose)
     if (i == 3 && !c->ev_bgprep[(size_t)k]) continue;
     ++n;
-    hipEvent_t* ev = &c->ev[(size_t)k * 6];
+    const Event* ev = &c->ev[(size_t)k * 6];
     HIP_OK(c, hipEventSynchronize(ev[5]));
     float t = 0;
     if (i == 3) {  // completion of raster .. completion of the (last) preparation kernel
@@ -2237,26 +2115,28 @@ int ofdg_kernel_ms(ofdg_ctx* c, const char* kernel, float* ms) {
 // aa [256], blend(d, s_fixed, m) [256*256] indexed d*256+m.
 int ofdg_debug_tables(ofdg_ctx* c, uint8_t* add_tbl, uint8_t* sub_tbl, uint8_t* aa_tbl, uint8_t* blend_tbl, int s_fixed) {
   if (!c) return OFDG_EINVAL;
-  uint8_t* d = nullptr;
-  HIP_OK(c, hipMalloc((void**)&d, 3 * 65536 + 256));
+  DevBuf<uint8_t> buf;
+  HIP_OK(c, buf.alloc(3 * 65536 + 256));
+  uint8_t* const d = buf.p;
   hipLaunchKernelGGL(tables_kernel, dim3(256), dim3(256), 0, 0, d, d + 65536, d + 3 * 65536, d + 2 * 65536, s_fixed);
   HIP_OK(c, hipGetLastError());
   HIP_OK(c, hipMemcpy(add_tbl, d, 65536, hipMemcpyDeviceToHost));
   HIP_OK(c, hipMemcpy(sub_tbl, d + 65536, 65536, hipMemcpyDeviceToHost));
   HIP_OK(c, hipMemcpy(blend_tbl, d + 2 * 65536, 65536, hipMemcpyDeviceToHost));
   HIP_OK(c, hipMemcpy(aa_tbl, d + 3 * 65536, 256, hipMemcpyDeviceToHost));
-  HIP_OK(c, hipFree(d));
   return OFDG_OK;
 }
 
 // include/ofdg_detmath.h on the device: n angles -> sin, cos; m floats -> expf (host arrays)
 int ofdg_debug_detmath(ofdg_ctx* c, const double* angles, int n, double* sin_out, double* cos_out, const float* x, int m, float* expf_out) {
   if (!c || n < 0 || m < 0 || (n > 0 && (!angles || !sin_out || !cos_out)) || (m > 0 && (!x || !expf_out))) return OFDG_EINVAL;
-  double* d = nullptr;
-  float* f = nullptr;
+  DevBuf<double> dbuf;
+  DevBuf<float> fbuf;
   const int k = std::max(std::max(n, m), 1);
-  HIP_OK(c, hipMalloc((void**)&d, (size_t)3 * k * sizeof(double)));
-  HIP_OK(c, hipMalloc((void**)&f, (size_t)2 * k * sizeof(float)));
+  HIP_OK(c, dbuf.alloc((size_t)3 * k));
+  HIP_OK(c, fbuf.alloc((size_t)2 * k));
+  double* const d = dbuf.p;
+  float* const f = fbuf.p;
   if (n) HIP_OK(c, hipMemcpy(d, angles, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   if (m) HIP_OK(c, hipMemcpy(f, x, (size_t)m * sizeof(float), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(detmath_kernel, dim3((k + 255) / 256), dim3(256), 0, 0, d, n, d + k, d + 2 * k, f, m, f + k);
@@ -2266,7 +2146,6 @@ int ofdg_debug_detmath(ofdg_ctx* c, const double* angles, int n, double* sin_out
     HIP_OK(c, hipMemcpy(cos_out, d + 2 * k, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   }
   if (m) HIP_OK(c, hipMemcpy(expf_out, f + k, (size_t)m * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_OK(c, hipFree(d)); HIP_OK(c, hipFree(f));
   return OFDG_OK;
 }
 
