@@ -1,0 +1,228 @@
+// C-ABI wrappers of the host-side pieces that never touch the GPU (declared in include/ofdg.h): no HIP header here.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <exception>
+#include <memory>
+
+#include "host_input.h"
+#include "realize.h"
+#include "sampler_ref.h"
+
+using namespace ofdg;
+
+struct ofdg_host_sampler {
+  RefSampler s;
+  ofdg_host_sampler(int m, int w, int h, int n) : s(m, w, h, n) {}
+};
+thread_local std::string ofdg::g_host_error;
+
+extern "C" {
+
+void ofdg_default_params(ofdg_params* p) {
+  std::memset(p, 0, sizeof(*p));
+  p->width = 512;               // DGEN_WIDTH
+  p->height = 384;              // DGEN_HEIGHT
+  p->mode = 1;                  // caffe.proto:7
+  p->use_antialiasing = 1;      // caffe.proto:11
+  p->batch_size = 1;
+  p->prefetch = 1;
+  p->first_level_threads = 16;  // caffe.proto:9
+  p->second_level_threads = 1;  // caffe.proto:10
+  p->sampler = OFDG_SAMPLER_REF;
+  p->world_size = 1;
+}
+
+const char* ofdg_host_last_error(void) { return g_host_error.c_str(); }
+
+int ofdg_host_decode_image(const char* path, uint8_t* planar_bgr, size_t capacity, int* width, int* height) {
+  if (!path || !width || !height) return OFDG_EINVAL;
+  try {
+    std::vector<uint8_t> img;
+    std::string why;
+    if (!read_image(path, planar_bgr ? &img : nullptr, width, height, &why)) { g_host_error = std::string("cannot read ") + path + ": " + why; return OFDG_ETEXTURES; }
+    if (planar_bgr) {
+      if (img.size() > capacity) { g_host_error = "image buffer too small"; return OFDG_ECAPACITY; }
+      std::memcpy(planar_bgr, img.data(), img.size());
+    }
+    return OFDG_OK;
+  } catch (const std::exception& e) {
+    g_host_error = e.what();
+    return OFDG_ETEXTURES;
+  }
+}
+
+int ofdg_host_sampler_create(int mode, int width, int height, int num_objects, ofdg_host_sampler** out) {
+  if (!out) return OFDG_EINVAL;
+  *out = nullptr;
+  std::unique_ptr<ofdg_host_sampler> s(new ofdg_host_sampler(mode, width, height, num_objects));
+  if (!s->s.ok()) { g_host_error = "BAD MODE"; return OFDG_EBADMODE; }
+  *out = s.release();
+  return OFDG_OK;
+}
+void ofdg_host_sampler_destroy(ofdg_host_sampler* s) { delete s; }
+int ofdg_host_sampler_next(ofdg_host_sampler* s, int n_tasks, ofdg_task* tasks, ofdg_blueprint* bps, int cap, int* n_bps) {
+  if (!s || !tasks || !bps || !n_bps) return OFDG_EINVAL;
+  std::vector<ofdg_blueprint> pool;
+  for (int i = 0; i < n_tasks; ++i) {
+    int rc = s->s.next_task(&pool, &tasks[i], &g_host_error);
+    if (rc != OFDG_OK) return rc;
+  }
+  *n_bps = (int)pool.size();
+  if ((int)pool.size() > cap) { g_host_error = "blueprint capacity exceeded"; return OFDG_ECAPACITY; }
+  std::memcpy(bps, pool.data(), pool.size() * sizeof(ofdg_blueprint));
+  return OFDG_OK;
+}
+
+int ofdg_host_realize(const ofdg_params* prm, int pool_n, int pool_w, int pool_h, const ofdg_task* tasks, int n_tasks,
+                      const ofdg_blueprint* bps, int n_bps, double* shape_mats, int shape_cap, int* n_shapes,
+                      double* object_mats, int object_cap, int* n_objects) {
+  if (!prm || !tasks || !bps || !n_shapes || !n_objects) return OFDG_EINVAL;
+  RealizeConfig cfg{prm->width, prm->height, prm->mode, pool_n, pool_w, pool_h};
+  RealizedBatch b;
+  int rc = realize_batch(cfg, tasks, n_tasks, bps, n_bps, &b, &g_host_error);
+  if (rc != OFDG_OK) return rc;
+  *n_shapes = (int)b.shapes.size();
+  *n_objects = (int)b.objects.size();
+  if ((int)b.shapes.size() > shape_cap || (int)b.objects.size() > object_cap) { g_host_error = "capacity"; return OFDG_ECAPACITY; }
+  for (size_t i = 0; i < b.shapes.size() && shape_mats; ++i) std::memcpy(shape_mats + 12 * i, b.shapes[i].m, sizeof(double) * 12);
+  for (size_t i = 0; i < b.objects.size() && object_mats; ++i) {
+    std::memcpy(object_mats + 12 * i, &b.objects[i].motion, sizeof(double) * 6);
+    std::memcpy(object_mats + 12 * i + 6, &b.objects[i].tex_inv, sizeof(double) * 6);
+  }
+  return OFDG_OK;
+}
+
+int ofdg_parse_prototxt(const char* text, ofdg_params* out, char* texture_dbases, int cap, int* n_top) {
+  if (!text || !out) return OFDG_EINVAL;
+  try {
+    LayerConfig cfg = parse_layer_prototxt(text);
+    *out = cfg.params;
+    if (texture_dbases && cap > 0) {
+      std::strncpy(texture_dbases, cfg.texture_dbases.c_str(), (size_t)cap - 1);
+      texture_dbases[cap - 1] = 0;
+    }
+    if (n_top) *n_top = (int)cfg.top.size();
+    return OFDG_OK;
+  } catch (const std::exception& e) {
+    g_host_error = e.what();
+    return OFDG_EINVAL;
+  }
+}
+
+// The background preparation record of getRandomizedCrop(2W, 2H, angle, zoom, shift) on a pool_w x pool_h image
+// (host logic, no GPU): f[8] = ca, sa, w2, h2, rw2, rh2, fx, fy; i[6] = x0, y0, cw, ch, shift_x, shift_y.
+int ofdg_host_bg_prep(int pool_w, int pool_h, int width, int height, float angle, float zoom, int shift_x, int shift_y, float* f,
+                      int* i) {
+  if (!f || !i || pool_w < 2 * width || pool_h < 2 * height || !(zoom > 0)) return OFDG_EINVAL;
+  const ofdg::DevBgPrep p = ofdg::make_bg_prep_host(pool_w, pool_h, width, height, angle, zoom, shift_x, shift_y, 0);
+  f[0] = p.ca; f[1] = p.sa; f[2] = p.w2; f[3] = p.h2; f[4] = p.rw2; f[5] = p.rh2; f[6] = p.fx; f[7] = p.fy;
+  i[0] = p.x0; i[1] = p.y0; i[2] = p.cw; i[3] = p.ch; i[4] = p.shx; i[5] = p.shy;
+  return OFDG_OK;
+}
+
+// ofdg_object_table's reduction on host label planes (no GPU): areas and boxes of the visible pixels of each label.
+static_assert(sizeof(ofdg_object_row) == 96 && offsetof(ofdg_object_row, box0) == 16 && offsetof(ofdg_object_row, motion) == 48,
+              "ofdg_object_row: 96 bytes, no padding");
+int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, int width, int height, const int32_t* counts,
+                           ofdg_object_row* rows, int rows_per_sample) {
+  if (!counts || !rows || n < 1 || width < 1 || height < 1 || rows_per_sample < 1) {
+    g_host_error = "ofdg_host_object_table: counts / rows NULL, or n, width, height or rows_per_sample below 1";
+    return OFDG_EINVAL;
+  }
+  const size_t plane = (size_t)width * height;
+  for (int s = 0; s < n; ++s) {
+    ofdg_object_row* const r = rows + (size_t)s * rows_per_sample;
+    const int limit = std::min(std::max(counts[s], 0), rows_per_sample);
+    for (int f = 0; f < 2; ++f) {
+      const uint8_t* const lab = f ? label1 : label0;
+      for (int k = 0; k < limit; ++k) {
+        int32_t* const box = f ? r[k].box1 : r[k].box0;
+        (f ? r[k].area1 : r[k].area0) = 0;
+        box[0] = width; box[1] = height; box[2] = -1; box[3] = -1;
+      }
+      if (!lab) continue;
+      const uint8_t* px = lab + (size_t)s * plane;
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x, ++px) {
+          const int k = *px;
+          if (k >= limit) continue;  // (no label of this sample, or a row the table does not hold)
+          int32_t* const box = f ? r[k].box1 : r[k].box0;
+          ++(f ? r[k].area1 : r[k].area0);
+          box[0] = std::min(box[0], x); box[1] = std::min(box[1], y);
+          box[2] = std::max(box[2], x); box[3] = std::max(box[3], y);
+        }
+    }
+  }
+  return OFDG_OK;
+}
+
+// ofdg_flow_stats on host buffers (no GPU): the definition of include/ofdg.h pixel by pixel.  This file is compiled with
+// -ffp-contract=off, so m2 is two products and one sum, each rounded to float32.
+static_assert(sizeof(ofdg_flow_stats_row) == 304 && offsetof(ofdg_flow_stats_row, n_counted) == 256 &&
+              offsetof(ofdg_flow_stats_row, sum_u_q8) == 272 && offsetof(ofdg_flow_stats_row, max_key) == 296,
+              "ofdg_flow_stats_row: 304 bytes, no padding");
+static float half_bits_to_float(uint16_t h) {  // binary16 -> float32, exact
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
+  uint32_t bits;
+  if (e == 31u) bits = sign | 0x7F800000u | (m << 13);
+  else if (e != 0u) bits = sign | ((e + 112u) << 23) | (m << 13);
+  else if (m == 0u) bits = sign;
+  else {  // subnormal: m * 2^-24
+    float f = (float)m * 5.9604644775390625e-8f;
+    std::memcpy(&bits, &f, 4);
+    bits |= sign;
+  }
+  float f;
+  std::memcpy(&f, &bits, 4);
+  return f;
+}
+int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height, float bin_px,
+                         int flags, ofdg_flow_stats_row* rows) {
+  if (const char* why = flow_stats_arg_error(flow, flow_fmt, occ, occ_fmt, n, width, height, bin_px, flags, rows)) {
+    g_host_error = std::string("ofdg_host_flow_stats: ") + why;
+    return OFDG_EINVAL;
+  }
+  const bool one_row = flags & OFDG_STATS_ONE_ROW, visible_only = flags & OFDG_STATS_VISIBLE_ONLY;
+  if (!(flags & OFDG_STATS_ACCUMULATE)) std::memset(rows, 0, sizeof(ofdg_flow_stats_row) * (one_row ? 1 : (size_t)n));
+  float edge2[OFDG_FLOW_HIST_BINS];
+  for (int k = 0; k < OFDG_FLOW_HIST_BINS; ++k) {
+    const float e = (float)k * bin_px;
+    edge2[k] = e * e;
+  }
+  const size_t plane = (size_t)width * height;
+  auto flow_at = [&](size_t i) {
+    return flow_fmt == OFDG_FMT_F16 ? half_bits_to_float(static_cast<const uint16_t*>(flow)[i]) : static_cast<const float*>(flow)[i];
+  };
+  for (int s = 0; s < n; ++s) {
+    ofdg_flow_stats_row& r = rows[one_row ? 0 : s];
+    for (size_t p = 0; p < plane; ++p) {
+      if (occ) {
+        const size_t o = (size_t)s * plane + p;
+        const bool hidden = occ_fmt == OFDG_FMT_U8 ? static_cast<const uint8_t*>(occ)[o] != 0 : static_cast<const float*>(occ)[o] != 0.0f;
+        if (hidden) {
+          ++r.n_occluded;
+          if (visible_only) continue;
+        }
+      }
+      const float u = flow_at((size_t)s * 2 * plane + p), v = flow_at(((size_t)s * 2 + 1) * plane + p);
+      if (!(std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f)) { ++r.n_bad; continue; }
+      ++r.n_counted;
+      const float uu = u * u, vv = v * v, m2 = uu + vv;
+      int b = 0;
+      for (int k = 1; k < OFDG_FLOW_HIST_BINS; ++k) b += edge2[k] <= m2;
+      ++r.hist[b];
+      r.sum_u_q8 += (int64_t)std::rint(u * 256.0f);
+      r.sum_v_q8 += (int64_t)std::rint(v * 256.0f);
+      r.sum_mag_q8 += (int64_t)std::rint(std::sqrt(m2) * 256.0f);
+      uint32_t bits;
+      std::memcpy(&bits, &m2, 4);
+      const uint32_t idx = (uint32_t)((one_row ? (size_t)s * plane : 0) + p);
+      r.max_key = std::max(r.max_key, ((uint64_t)bits << 32) | (uint64_t)(0xFFFFFFFFu - idx));
+    }
+  }
+  return OFDG_OK;
+}
+
+}  // extern "C"

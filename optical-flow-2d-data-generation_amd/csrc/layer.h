@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ofdg.h"
+#include "host_input.h"
 
 namespace ofdg {
 
@@ -36,19 +36,6 @@ class Blob {
   float* data_ = nullptr;
   bool external_ = false;
 };
-
-// What the prototxt subset parser extracts (src/caffe/proto/caffe.proto:6-12 and
-// the LMB data_param fields used at data_generation_layer.cpp:44, 109-113).
-struct LayerConfig {
-  std::string name, type;
-  std::vector<std::string> top;
-  ofdg_params params;
-  std::string texture_dbases;  // list file, or "synthetic:N:W:H[:seed]"
-};
-
-// Parses one `layer { ... }` block (protobuf text format subset: nested messages,
-// key: value, strings, numbers, true/false, '#' comments).  Throws std::runtime_error.
-LayerConfig parse_layer_prototxt(const std::string& text);
 
 class DataGenerationLayer {
  public:
@@ -99,8 +86,8 @@ class DataGenerationLayer {
   long long produced_ = 0, consumed_ = 0;
 };
 
-// Texture list loader: TextureCollection (DataGenerator.cpp:117-149) for binary PPM
-// (P6) files, or a synthetic pool.  Throws std::runtime_error("Could not open texture
+// Texture list loader: TextureCollection (DataGenerator.cpp:117-149) for binary PPM (P6) and PNG files, or a
+// synthetic pool: plan_texture_collection's plan, uploaded.  Throws std::runtime_error("Could not open texture
 // collection") like the reference.
 void load_texture_collection(ofdg_ctx* ctx, const std::string& spec);
 

@@ -261,20 +261,6 @@ static int texture_of_image(ofdg_ctx* c, const uint32_t* image, int w, int h, in
 
 extern "C" {
 
-void ofdg_default_params(ofdg_params* p) {
-  std::memset(p, 0, sizeof(*p));
-  p->width = 512;               // DGEN_WIDTH
-  p->height = 384;              // DGEN_HEIGHT
-  p->mode = 1;                  // caffe.proto:7
-  p->use_antialiasing = 1;      // caffe.proto:11
-  p->batch_size = 1;
-  p->prefetch = 1;
-  p->first_level_threads = 16;  // caffe.proto:9
-  p->second_level_threads = 1;  // caffe.proto:10
-  p->sampler = OFDG_SAMPLER_REF;
-  p->world_size = 1;
-}
-
 const char* ofdg_last_error(const ofdg_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
 int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {

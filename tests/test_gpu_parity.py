@@ -973,6 +973,63 @@ def test_layer_names_every_unreadable_texture_in_one_error(ofdg, tmp_path):
     layer.close()
 
 
+def _layer_equals_generator_fed_with(ofdg, lst, files):
+    """Forward() of the layer on list `lst` against a Generator whose pool holds decode_image(file) of every file, all of one size."""
+    import torch
+    layer = ofdg.DataGenerationLayer(LAYER_PROTOTXT % lst)
+    a, b, f = layer.Forward()
+    images = [ofdg.decode_image(p) for p in files]
+    g = ofdg.Generator(ofdg.default_params(width=128, height=96, mode=7, batch_size=3, background_prep=1))  # (the layer's default)
+    g.pool_alloc(len(images), images[0].shape[2], images[0].shape[1])
+    for k, im in enumerate(images):
+        g.pool_upload(k, im)
+    i0, i1, fl = ofdg.alloc_outputs(3, 96, 128)
+    g.forward(i0, i1, fl)
+    g.synchronize()
+    assert torch.equal(a, i0) and torch.equal(b, i1) and torch.equal(f, fl)
+    layer.close()
+
+
+def test_layer_names_unusable_ppms_with_the_other_unreadable_files(ofdg, tmp_path):
+    """PPMs whose header the reader refuses (maxval 65535, a payload one byte short, 2000000000 x 2000000000 with nothing
+    behind it) are named in the ONE error of the list, like PNGs; the good file alone then loads, and Forward() equals a
+    Generator whose pool is that file as decode_image gives it."""
+    rng = np.random.RandomState(13)
+    rgb = rng.randint(0, 256, (192, 256, 3)).astype(np.uint8)
+    good = tmp_path / "good.ppm"
+    good.write_bytes(b"P6\n256 192\n255\n" + rgb.tobytes())
+    bad = [tmp_path / n for n in ("maxval.ppm", "short.ppm", "huge.ppm")]
+    bad[0].write_bytes(b"P6\n256 192\n65535\n" + rgb.tobytes() * 2)
+    bad[1].write_bytes(b"P6\n256 192\n255\n" + rgb.tobytes()[:-1])
+    bad[2].write_bytes(b"P6\n2000000000 2000000000\n255\n")
+    lst = tmp_path / "database.txt"
+    lst.write_text("\n".join(str(p) for p in (bad[0], good, bad[1], bad[2])) + "\n")
+    with pytest.raises(ofdg.OfdgError) as e:
+        ofdg.DataGenerationLayer(LAYER_PROTOTXT % lst)
+    msg = str(e.value)
+    assert e.value.code == ofdg.ETEXTURES and "Could not open texture collection" in msg and "3 files" in msg
+    assert all(str(p) + ": neither a binary PPM (P6, maxval 255) nor a PNG" in msg for p in bad) and str(good) not in msg
+    lst.write_text(str(good) + "\n")
+    assert np.array_equal(ofdg.decode_image(good), np.stack([rgb[:, :, 2], rgb[:, :, 1], rgb[:, :, 0]]))
+    _layer_equals_generator_fed_with(ofdg, lst, [good])
+
+
+def test_layer_loads_a_uniform_list_of_ppm_and_png(ofdg, tmp_path):
+    """A list of one size that mixes formats - a PPM with two comment lines, an RGB PNG, a palette PNG - takes the uniform
+    pool (ofdg_pool_alloc / ofdg_pool_upload): Forward() equals the Generator fed with the three decode_image results."""
+    from PIL import Image
+    rng = np.random.RandomState(14)
+    rgb = [rng.randint(0, 256, (192, 256, 3)).astype(np.uint8) for _ in range(3)]
+    files = [tmp_path / n for n in ("tex0.ppm", "tex1.png", "tex2.png")]
+    files[0].write_bytes(b"P6\n# first comment\n# second comment\n256 192\n255\n" + rgb[0].tobytes())
+    Image.fromarray(rgb[1]).save(files[1])
+    Image.fromarray(rgb[2]).quantize(64).save(files[2])
+    assert np.array_equal(ofdg.decode_image(files[1]), np.stack([rgb[1][:, :, 2], rgb[1][:, :, 1], rgb[1][:, :, 0]]))
+    lst = tmp_path / "database.txt"
+    lst.write_text("\n".join(str(p) for p in files) + "\n")
+    _layer_equals_generator_fed_with(ofdg, lst, files)
+
+
 def test_pool_from_list_decodes_images_like_the_ppm_loader(ofdg, tmp_path):
     """Generator.pool_from_list (Pillow decode of any image format; the reference uses CImg::load) and
     tools/convert_textures.py + the layer's PPM loader fill the pool with the same texels, in B, G, R order;

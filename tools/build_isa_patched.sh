@@ -15,5 +15,5 @@ $LLVM/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=gfx950 -c $B/dev_p.s -o
 $LLVM/lld -flavor gnu -m elf64_amdgpu --no-undefined -shared -o $B/dev.out $B/dev.o
 $LLVM/clang-offload-bundler -type=o -bundle-align=4096 -targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950 -input=/dev/null -input=$B/dev.out -output=$B/dev.hipfb
 /opt/rocm/bin/hipcc $FLAGS "$@" --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang $B/dev.hipfb -c csrc/ofdg_api.hip -o $B/ofdg_api.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/libofdg_$name.so $B/ofdg_api.o build/realize.o build/sampler_ref.o build/layer.o build/warpfields.o build/comm.o -ldl
+make -s LIB=lib/libofdg_$name.so API_OBJ=$B/ofdg_api.o   # (the Makefile's link line and host objects)
 echo "built lib/libofdg_$name.so"

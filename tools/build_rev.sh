@@ -11,8 +11,9 @@ git -C $root archive $rev $pkg/csrc include | tar -x -C $tmp
 cd $tmp/$pkg
 objs=""
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -Wno-pass-failed -mllvm -amdgpu-kernarg-preload-count=16 -c csrc/ofdg_api.hip -o ofdg_api.o
-for f in realize sampler_ref layer warpfields comm; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -c csrc/$f.cpp -o $f.o; objs="$objs $f.o"
+for src in csrc/*.cpp; do   # (whatever host files that revision has)
+  f=$(basename $src .cpp)
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -c $src -o $f.o; objs="$objs $f.o"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $root/$pkg/lib/libofdg_$name.so ofdg_api.o $objs -ldl
 echo "built $pkg/lib/libofdg_$name.so from $rev"

@@ -1,0 +1,184 @@
+// The host code that reads untrusted input (csrc/host_input.cpp, csrc/host_api.cpp) as a program of its own, built with
+// -fsanitize=address,undefined by `make san` in the package directory.  No HIP, no GPU; CPU machines only.
+//
+//   host_input_check check <dir|file>   one line per file and query, through the C wrappers libofdg.so exports:
+//                                         *.prototxt  ofdg_parse_prototxt          *.txt  the texture list's plan
+//                                         any other   ofdg_host_decode_image, size only and decoded (FNV-1a of the planes)
+//   host_input_check mutate <dir> [-v]  every file of <dir> is a seed; four families of mutation, each case through the
+//                                       probe, the decode and the prototxt parser; -v prints every case's answers:
+//                                         t  every truncation length
+//                                         b  at every offset of the first kWindow bytes, each byte of kBytes
+//                                         p  every decimal field of a PPM header replaced by each of kNumbers
+//                                         c  every PNG chunk length replaced by 0, its value - 1, + 1, 0x7fffffff, 0xffffffff
+// Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
+#include <algorithm>
+#include <cctype>
+#include <cstdio>
+#include <cstring>
+#include <filesystem>
+#include <fstream>
+#include <iterator>
+#include <sstream>
+#include <stdexcept>
+
+#include "../optical-flow-2d-data-generation_amd/csrc/host_input.h"
+
+namespace {
+constexpr size_t kWindow = 64;  // covers the longest header of the seed set (tests/test_host_input.py: a PPM with two comment lines, 25 bytes)
+constexpr unsigned char kBytes[] = {0x00, 0x09, 0x0a, 0x20, 0x23, 0x2b, 0x2d, 0x30, 0x39, 0x7f, 0xff};
+const char* const kNumbers[] = {"0", "-1", "2147483647", "2147483648", "99999999999"};
+
+unsigned long long fnv1a(const uint8_t* p, size_t n) {
+  unsigned long long h = 14695981039346656037ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 1099511628211ull;
+  return h;
+}
+std::string slurp(const std::filesystem::path& p) {
+  std::ifstream f(p, std::ios::binary);
+  return std::string(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+}
+std::vector<std::filesystem::path> files_of(const char* dir) {
+  if (!std::filesystem::is_directory(dir)) return {dir};  // (one file, which need not exist: a missing list has an answer too)
+  std::vector<std::filesystem::path> v;
+  for (const auto& e : std::filesystem::directory_iterator(dir)) if (e.is_regular_file()) v.push_back(e.path());
+  std::sort(v.begin(), v.end());
+  return v;
+}
+std::string params_text(const ofdg_params& p) {
+  char b[256];
+  std::snprintf(b, sizeof b, "mode=%d batch=%d prefetch=%d threads=%d,%d aa=%d size=%dx%d objects=%d seed=%d chains=%d lookahead=%d prep=%d sampler=%d",
+                p.mode, p.batch_size, p.prefetch, p.first_level_threads, p.second_level_threads, p.use_antialiasing, p.width, p.height,
+                p.num_objects, p.seed, p.chains, p.lookahead, p.background_prep, p.sampler);
+  return b;
+}
+
+int check(const char* dir) {
+  for (const auto& path : files_of(dir)) {
+    const std::string name = path.filename().string(), ext = path.extension().string();
+    if (ext == ".prototxt") {
+      ofdg_params p;
+      std::memset(&p, 0, sizeof p);
+      char db[4096] = "";
+      int n_top = 0;
+      const int rc = ofdg_parse_prototxt(slurp(path).c_str(), &p, db, sizeof db, &n_top);
+      std::printf("prototxt %s rc=%d %s db=%s tops=%d msg=%s\n", name.c_str(), rc, params_text(p).c_str(), db, n_top, rc ? ofdg_host_last_error() : "");
+    } else if (ext == ".txt") {
+      const ofdg::TexturePlan plan = ofdg::plan_texture_collection(path.string());
+      std::printf("list %s files=%zu mixed=%s error=%s\n", name.c_str(), plan.paths.size(), plan.mixed ? "true" : "false", plan.error.c_str());
+      for (size_t i = 0; i < plan.widths.size(); ++i) std::printf("  %s %dx%d\n", plan.paths[i].c_str(), plan.widths[i], plan.heights[i]);
+    } else {
+      int w = 0, h = 0;
+      int rc = ofdg_host_decode_image(path.c_str(), nullptr, 0, &w, &h);
+      std::printf("image %s size rc=%d %dx%d msg=%s\n", name.c_str(), rc, w, h, rc ? ofdg_host_last_error() : "");
+      std::vector<uint8_t> planes(rc ? 1 : (size_t)3 * w * h);
+      w = h = 0;
+      rc = ofdg_host_decode_image(path.c_str(), planes.data(), planes.size(), &w, &h);
+      std::printf("image %s decode rc=%d %dx%d fnv=%016llx msg=%s\n", name.c_str(), rc, w, h, rc ? 0ull : fnv1a(planes.data(), planes.size()),
+                  rc ? ofdg_host_last_error() : "");
+    }
+  }
+  return 0;
+}
+
+struct Tally {
+  long long cases = 0, probe_refused = 0, decode_refused = 0, parser_refused = 0;
+  bool verbose = false;
+};
+// one mutated input through the probe, the decode and the parser; false: probe and decode contradict each other
+bool run_case(const std::string& bytes, const char* tag, Tally* t) {
+  int pw = 0, ph = 0, dw = 0, dh = 0;
+  std::string pwhy, dwhy, perr;
+  std::vector<uint8_t> planes;
+  std::istringstream f0(bytes), f1(bytes);
+  const bool probed = ofdg::read_image(f0, nullptr, &pw, &ph, &pwhy);
+  const bool decoded = ofdg::read_image(f1, &planes, &dw, &dh, &dwhy);
+  ofdg::LayerConfig cfg;
+  bool parsed = true;
+  try {
+    cfg = ofdg::parse_layer_prototxt(bytes);
+  } catch (const std::runtime_error& e) {  // (the parser's refusal; anything else escapes and ends the program)
+    parsed = false;
+    perr = e.what();
+  }
+  ++t->cases;
+  t->probe_refused += !probed;
+  t->decode_refused += !decoded;
+  t->parser_refused += !parsed;
+  if (t->verbose) {
+    std::printf("%s probe=%d %dx%d %s | decode=%d %dx%d %016llx %s | ", tag, probed, probed ? pw : 0, probed ? ph : 0, pwhy.c_str(), decoded,
+                decoded ? dw : 0, decoded ? dh : 0, decoded ? fnv1a(planes.data(), planes.size()) : 0ull, dwhy.c_str());
+    if (parsed) {
+      std::string tops;
+      for (const std::string& s : cfg.top) tops += s + ",";
+      std::printf("parse=1 %s name=%s type=%s tops=%s db=%s\n", params_text(cfg.params).c_str(), cfg.name.c_str(), cfg.type.c_str(), tops.c_str(),
+                  cfg.texture_dbases.c_str());
+    } else {
+      std::printf("parse=0 %s\n", perr.c_str());
+    }
+  }
+  if (decoded && (!probed || pw != dw || ph != dh || planes.size() != (size_t)3 * dw * dh)) {
+    std::printf("%s: the decode gives %dx%d (%zu bytes), the probe %s %dx%d\n", tag, dw, dh, planes.size(), probed ? "gives" : "refuses,", pw, ph);
+    return false;
+  }
+  return true;
+}
+
+int mutate(const char* dir, bool verbose) {
+  Tally t;
+  t.verbose = verbose;
+  bool ok = true;
+  char tag[128];
+  for (const auto& path : files_of(dir)) {
+    const std::string seed = slurp(path), name = path.filename().string();
+    for (size_t n = 0; n < seed.size(); ++n) {
+      std::snprintf(tag, sizeof tag, "%s t%zu", name.c_str(), n);
+      ok &= run_case(seed.substr(0, n), tag, &t);
+    }
+    for (size_t at = 0; at < std::min(kWindow, seed.size()); ++at)
+      for (unsigned char b : kBytes) {
+        std::string m = seed;
+        m[at] = (char)b;
+        std::snprintf(tag, sizeof tag, "%s b%zu=%02x", name.c_str(), at, b);
+        ok &= run_case(m, tag, &t);
+      }
+    if (seed.compare(0, 2, "P6") == 0) {
+      size_t i = 2;
+      for (int field = 0; field < 3 && i < seed.size();) {
+        if (seed[i] == '#') { while (i < seed.size() && seed[i] != '\n') ++i; continue; }
+        if (!std::isdigit((unsigned char)seed[i])) { ++i; continue; }
+        size_t end = i;
+        while (end < seed.size() && std::isdigit((unsigned char)seed[end])) ++end;
+        for (const char* number : kNumbers) {
+          std::snprintf(tag, sizeof tag, "%s p%d=%s", name.c_str(), field, number);
+          ok &= run_case(seed.substr(0, i) + number + seed.substr(end), tag, &t);
+        }
+        i = end;
+        ++field;
+      }
+      if (i > kWindow) { std::printf("%s: the header ends at byte %zu: widen kWindow (%zu)\n", name.c_str(), i, kWindow); return 1; }
+    }
+    if (seed.compare(0, 4, "\x89PNG") == 0) {
+      for (size_t i = 8; i + 12 <= seed.size();) {
+        const unsigned char* p = (const unsigned char*)&seed[i];
+        const uint32_t len = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+        for (uint32_t v : {0u, len - 1u, len + 1u, 0x7fffffffu, 0xffffffffu}) {
+          std::string m = seed;
+          for (int k = 0; k < 4; ++k) m[i + k] = (char)(v >> (24 - 8 * k));
+          std::snprintf(tag, sizeof tag, "%s c%zu=%08x", name.c_str(), i, v);
+          ok &= run_case(m, tag, &t);
+        }
+        i += 12 + (size_t)len;
+      }
+    }
+  }
+  std::printf("cases=%lld refused: probe=%lld decode=%lld parser=%lld\n", t.cases, t.probe_refused, t.decode_refused, t.parser_refused);
+  return ok ? 0 : 1;
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
+  if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v]\n", argv[0]);
+  return 2;
+}
