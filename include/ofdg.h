@@ -436,6 +436,63 @@ int ofdg_flow_stats(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const void*
 int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
                          float bin_px, int flags, ofdg_flow_stats_row* rows);
 
+/*
+ * Multi-scale ground-truth flow pyramid: the flow at 1/2 ... 1/64 resolution, as the losses of a coarse-to-fine network
+ * (FlowNet, PWC-Net and their successors) read it, with a defined treatment of occluded and non-finite pixels and a fixed
+ * order of summation - one launch behind the call that wrote the planes, the input read once, every level written in it.
+ *
+ * d_flow / d_occ: exactly as in the flow statistics above - any [n,2,H,W] flow tensor of the context's frame size (the
+ * forward flow or flow1 of ofdg_extras), float32 (flow_fmt = OFDG_FMT_F32, 16-byte aligned) or binary16 (OFDG_FMT_F16, 8-byte
+ * aligned); d_occ NULL, or the [n,1,H,W] map that goes with it, float32 (OFDG_FMT_F32, 16-byte aligned) or uint8 (OFDG_FMT_U8,
+ * 4-byte aligned); occ_fmt is not looked at when d_occ is NULL.  All 13 modes, both samplers.  The result is a pure function
+ * of the buffers: the context supplies W, H, the device and the stream only.
+ *
+ * pyr: where the levels go.  Level k = 1..levels is flow[k-1], [n,2,H>>k,W>>k] of out_fmt (OFDG_FMT_F32 or OFDG_FMT_F16), and -
+ * when asked for - weight[k-1], [n,1,H>>k,W>>k] uint16.  A row of a level is (W>>k) elements and nothing more is assumed of it
+ * (72 >> 3 = 9).  W and H must be multiples of 2^levels, so no cell straddles the frame's edge.  Entries at index >= levels are
+ * never read.
+ *
+ * Definition - a fixed summation tree in float32 without contraction, so every bit is the same on every run.  For sample i,
+ * u and v widened to float32 (exact for a binary16):
+ *   usable pixel: fabsf(u) < 1048576.0f && fabsf(v) < 1048576.0f (the rule of n_bad above: it leaves out NaN, +-inf and an
+ *                 overflowed half), and, when d_occ is given, occ == 0.
+ *   level 0:      S0(x,y) = usable ? (u,v) : (+0.0f,+0.0f);  c0(x,y) = usable ? 1 : 0.
+ *   level k >= 1, per component, over level k-1:
+ *                 Sk(X,Y) = fl32( fl32(S(2X,2Y) + S(2X+1,2Y)) + fl32(S(2X,2Y+1) + S(2X+1,2Y+1)) )
+ *                 (the left-right pairs first, then top and bottom);  ck = the integer sum of the four children.
+ *   output of level k: ck == 0: +0.0f;  otherwise fl32(Sk / (float)ck), a correctly rounded division, and with
+ *                 OFDG_PYR_SCALE then fl32(that * 2^-k) - the flow in pixels of level k.  Float32 denormals are kept.  For
+ *                 OFDG_FMT_F16 the result is then rounded once to nearest even (an overflow becomes +-inf).
+ *   weight[k-1](X,Y) = (uint16)ck: the usable pixels among the cell's 4^k, 0..4096.
+ *
+ * Asynchronous on `stream`, the stream the flow was written on; OFDG_STREAM_OWN: the internal stream the last render /
+ * forward call worked on, as in the flow statistics.  One kernel, no atomics; it reads no record of the context, so no
+ * completion bookkeeping is involved.
+ *
+ * OFDG_EINVAL, nothing enqueued, no output byte written, the field named in ofdg_last_error: d_flow or pyr NULL, levels
+ * outside 1..OFDG_PYR_MAX_LEVELS, W or H not a multiple of 2^levels, flow[k-1] NULL for a k <= levels, weight[] set for some
+ * levels <= levels and NULL for others, flow_fmt / occ_fmt / out_fmt not one of the codes above, n_samples < 1, unknown bits
+ * in flags, a misaligned pointer (flow[k-1] 16-byte, weight[k-1] 4-byte), OFDG_STREAM_OWN before any render / forward call on
+ * the context.
+ *
+ * The structure and the call share their name, as `struct stat` and stat do: say `struct ofdg_flow_pyramid` for the type.
+ */
+#define OFDG_PYR_MAX_LEVELS 6
+#define OFDG_PYR_SCALE 1              /* level k in level-k pixels: the mean times 2^-k */
+struct ofdg_flow_pyramid {
+  void* flow[OFDG_PYR_MAX_LEVELS];    /* flow[k-1] = level k: [n,2,H>>k,W>>k], element type out_fmt; 16-byte aligned base */
+  void* weight[OFDG_PYR_MAX_LEVELS];  /* all NULL, or weight[k-1] = [n,1,H>>k,W>>k] uint16: usable pixels of the cell, 0..4^k */
+  int32_t levels;                     /* 1..6 */
+  int32_t out_fmt;                    /* OFDG_FMT_F32 or OFDG_FMT_F16 */
+};
+int ofdg_flow_pyramid(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
+                      int n_samples, int flags, const struct ofdg_flow_pyramid* pyr, void* stream);
+/* The same on HOST buffers (no GPU), the definition cell by cell: flow [n,2,height,width], occ NULL or [n,1,height,width],
+ * any width / height >= 1 that are multiples of 2^levels, no alignment asked of any plane.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
+                           int flags, const struct ofdg_flow_pyramid* pyr);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -225,4 +225,96 @@ int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int oc
   return OFDG_OK;
 }
 
+// ofdg_flow_pyramid on host buffers (no GPU): the definition of include/ofdg.h cell by cell, level by level - the sums and
+// counts of level k are kept and level k + 1 is made of them.  -ffp-contract=off: every sum is its own float32 rounding.
+static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && offsetof(struct ofdg_flow_pyramid, levels) == 96 &&
+              offsetof(struct ofdg_flow_pyramid, out_fmt) == 100 && OFDG_PYR_MAX_LEVELS == kPyrMaxLevels && OFDG_PYR_SCALE == 1,
+              "struct ofdg_flow_pyramid: 104 bytes, the layout flow_pyramid_arg_error reads");
+static uint16_t float_to_half_bits(float f) {  // float32 -> binary16, to nearest even, an overflow becomes +-inf
+  uint32_t x;
+  std::memcpy(&x, &f, 4);
+  const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
+  x &= 0x7FFFFFFFu;
+  if (x > 0x7F800000u) return (uint16_t)(sign | 0x7E00u);
+  if (x >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // 65520 and above (inf too)
+  if (x >= 0x38800000u) {                                  // a normal half: 2^-14 and above
+    x -= 0x38000000u;
+    x += 0xFFFu + ((x >> 13) & 1u);
+    return (uint16_t)(sign | (x >> 13));
+  }
+  const int shift = 126 - (int)(x >> 23);  // a subnormal half: units of 2^-24
+  if (shift > 24) return sign;
+  const uint32_t m = (x & 0x7FFFFFu) | 0x800000u, h = m >> shift, rem = m & ((1u << shift) - 1u), mid = 1u << (shift - 1);
+  return (uint16_t)(sign | (h + ((rem > mid || (rem == mid && (h & 1u))) ? 1u : 0u)));
+}
+int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height, int flags,
+                           const struct ofdg_flow_pyramid* pyr) {
+  if (const char* why = flow_pyramid_arg_error(flow, flow_fmt, occ, occ_fmt, n, width, height, flags,
+                                               reinterpret_cast<const DevFlowPyramid*>(pyr))) {
+    g_host_error = std::string("ofdg_host_flow_pyramid: ") + why;
+    return OFDG_EINVAL;
+  }
+  const size_t plane = (size_t)width * height;
+  auto flow_at = [&](size_t i) {  // (memcpy: no alignment is asked of the planes)
+    if (flow_fmt == OFDG_FMT_F16) {
+      uint16_t h;
+      std::memcpy(&h, static_cast<const uint8_t*>(flow) + 2 * i, 2);
+      return half_bits_to_float(h);
+    }
+    float f;
+    std::memcpy(&f, static_cast<const uint8_t*>(flow) + 4 * i, 4);
+    return f;
+  };
+  auto hidden_at = [&](size_t i) {
+    if (occ_fmt == OFDG_FMT_U8) return static_cast<const uint8_t*>(occ)[i] != 0;
+    float f;
+    std::memcpy(&f, static_cast<const uint8_t*>(occ) + 4 * i, 4);
+    return f != 0.0f;
+  };
+  std::vector<float> su(plane), sv(plane), tu, tv;
+  std::vector<uint32_t> sc(plane), tc;
+  for (int s = 0; s < n; ++s) {
+    su.resize(plane); sv.resize(plane); sc.resize(plane);
+    for (size_t p = 0; p < plane; ++p) {
+      const float u = flow_at((size_t)s * 2 * plane + p), v = flow_at(((size_t)s * 2 + 1) * plane + p);
+      const bool usable = std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f && !(occ && hidden_at((size_t)s * plane + p));
+      su[p] = usable ? u : 0.0f;
+      sv[p] = usable ? v : 0.0f;
+      sc[p] = usable ? 1u : 0u;
+    }
+    for (int k = 1; k <= pyr->levels; ++k) {
+      const size_t w = (size_t)(width >> k), h = (size_t)(height >> k), pw = 2 * w;  // pw: the pitch of level k - 1
+      const float scale = (flags & OFDG_PYR_SCALE) ? 1.0f / (float)(1 << k) : 1.0f;
+      tu.assign(w * h, 0.0f); tv.assign(w * h, 0.0f); tc.assign(w * h, 0u);
+      for (size_t Y = 0; Y < h; ++Y)
+        for (size_t X = 0; X < w; ++X) {
+          const size_t a = 2 * Y * pw + 2 * X, b = a + pw, at = Y * w + X;
+          const float ut = su[a] + su[a + 1], ub = su[b] + su[b + 1], vt = sv[a] + sv[a + 1], vb = sv[b] + sv[b + 1];
+          const float cu = ut + ub, cv = vt + vb;
+          const uint32_t c = sc[a] + sc[a + 1] + sc[b] + sc[b + 1];
+          tu[at] = cu; tv[at] = cv; tc[at] = c;
+          float mu = 0.0f, mv = 0.0f;
+          if (c) {
+            const float qu = cu / (float)c, qv = cv / (float)c;
+            mu = qu * scale;
+            mv = qv * scale;
+          }
+          const size_t ou = (size_t)s * 2 * w * h + at, ov = ou + w * h;
+          if (pyr->out_fmt == OFDG_FMT_F16) {
+            uint16_t* const o = static_cast<uint16_t*>(pyr->flow[k - 1]);
+            o[ou] = float_to_half_bits(mu);
+            o[ov] = float_to_half_bits(mv);
+          } else {
+            float* const o = static_cast<float*>(pyr->flow[k - 1]);
+            o[ou] = mu;
+            o[ov] = mv;
+          }
+          if (pyr->weight[k - 1]) static_cast<uint16_t*>(pyr->weight[k - 1])[(size_t)s * w * h + at] = (uint16_t)c;
+        }
+      su.swap(tu); sv.swap(tv); sc.swap(tc);
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

@@ -3270,4 +3270,193 @@ __global__ __launch_bounds__(kStatsThreads) void flow_stats_kernel(const void* _
   }
 }
 
+// --------------------------------------------------------------------------
+// Multi-scale flow pyramid (ofdg_flow_pyramid): levels 1..L of the mean flow of the usable pixels of a [n,2,H,W] flow tensor,
+// float32 or binary16, with an optional [n,1,H,W] occlusion map, and optionally the usable-pixel counts.  One launch, the
+// input read once; the summation tree is the definition's (include/ofdg.h), so the result is the host twin's bit for bit.
+// --------------------------------------------------------------------------
+// One workgroup of four waves per (64x64 tile, sample).  A lane owns a 4x4 block of pixels: four 16-byte loads per plane (8
+// bytes for binary16, 4 or 16 bytes of map), all requested before the first is used; of a wave's load instruction every 16
+// lanes read 256 (128) contiguous bytes of one row.  Lane l of wave w holds block (bx, by) = (l & 15, 4w + (l >> 4)), so
+//   levels 1 and 2 (2x2 cells and the one cell of the block) are sums of the lane's own registers,
+//   level 3 adds the lanes 1 and 16 away, level 4 the lanes 2 and 32 away (__shfl_xor: both partners compute the same sum,
+//     float32 addition commutes bit for bit - the sums hold no NaN - so "left + right, then top + bottom" holds in every lane),
+//   the four level-4 sums and counts of each wave meet in LDS behind one barrier, and wave 0 finishes levels 5 and 6 from
+//     there in the order the definition fixes (only when levels >= 5: the test is uniform).
+// Pixels outside the frame (partial tiles; H may be 2 mod 4 when levels = 1) count as unusable and their lanes stay in the
+// shuffles; a cell is stored when it lies inside its level, and W, H are multiples of 2^levels, so such a cell never holds a
+// pixel outside.  Stores: level 1 is two adjacent cells per lane and row - one 8-byte (float32), 4-byte (binary16, weights)
+// store, aligned because W / 2 is a multiple of 4 -, 16 lanes fill 128 (64) contiguous bytes; the flow of level 1 is stored
+// non-temporally like the other output planes.  Everything narrower than a line - the weights, and the deeper levels, one
+// element per storing lane because their row pitch may be odd - is stored plainly, so that L2 merges the pieces of a line
+// (measured: non-temporal stores there cost 4 - 9 us per launch at 512x384x32).  No atomics, no scratch.
+constexpr int kPyrThreads = 256;
+constexpr int kPyrTile = 64;
+__device__ __forceinline__ void pyr_cell(float& su, float& sv, uint32_t c, float scale) {  // the sums of a cell -> its output
+  // c == 0: every pixel of the cell went in as +0, so the sums are +0 and +0 / 1 is the +0 the definition asks for - no test.
+  // A count that is a power of two (a cell without unusable pixels: the common case) divides exactly by a multiplication with
+  // 2^-log2(c) - the product is the correctly rounded quotient, denormals included - so the division's expansion runs only
+  // in a wave where some lane holds another count (the test is uniform: every lane takes the same, equally exact, path).
+  const uint32_t d = max(c, 1u);
+  if (__ballot((d & (d - 1u)) != 0u)) {
+    su = su / (float)d;
+    sv = sv / (float)d;
+  } else {
+    const float r = __uint_as_float((uint32_t)(96 + __clz((int)d)) << 23);  // 2^-log2(d): exponent 127 - (31 - clz)
+    su = __fmul_rn(su, r);
+    sv = __fmul_rn(sv, r);
+  }
+  su = __fmul_rn(su, scale);  // (1 or 2^-k: exact but for denormals)
+  sv = __fmul_rn(sv, scale);
+}
+template <typename OutT>
+__device__ __forceinline__ void pyr_store(const DevFlowPyramid& out, int k, int n_weights, int s, int W, int H, int X, int Y, float su, float sv,
+                                          uint32_t c, float scale) {  // one cell of level k (1-based)
+  const int w = W >> k, h = H >> k;
+  if (X >= w || Y >= h) return;
+  const size_t plane = (size_t)w * h, at = (size_t)Y * w + X;
+  OutT* const f = static_cast<OutT*>(out.flow[k - 1]) + (size_t)s * 2 * plane + at;
+  pyr_cell(su, sv, c, scale);
+  f[0] = (OutT)su;
+  f[plane] = (OutT)sv;
+  if (n_weights) (static_cast<uint16_t*>(out.weight[k - 1]) + (size_t)s * plane + at)[0] = (uint16_t)c;
+}
+template <bool kHalf, bool kHalfOut, int kOcc>  // kOcc: 0 no map, 1 float32, 2 uint8
+__global__ __launch_bounds__(kPyrThreads) void flow_pyramid_kernel(const void* __restrict__ flow, const void* __restrict__ occ, int n, int W,
+                                                                   int H, int scaled, int n_weights, const DevFlowPyramid out) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+  typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+  typedef typename std::conditional<kHalfOut, _Float16, float>::type OutT;
+  typedef typename std::conditional<kHalfOut, f16x2, f32x2>::type OutT2;
+  __shared__ float s_u[4][4], s_v[4][4];
+  __shared__ uint32_t s_c[4][4];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
+  const int x0 = (int)blockIdx.x * kPyrTile + bx * 4, y0 = (int)blockIdx.y * kPyrTile + by * 4;  // the block's first pixel
+  const int levels = out.levels;
+  const size_t plane = (size_t)W * H;
+  float scale[kPyrMaxLevels + 1];
+#pragma unroll
+  for (int k = 1; k <= kPyrMaxLevels; ++k) scale[k] = scaled ? 1.0f / (float)(1 << k) : 1.0f;
+  for (int s = (int)blockIdx.z; s < n; s += (int)gridDim.z) {
+    // level 0: the block's pixels, unusable ones as (+0, +0) with count 0
+    float u[4][4], v[4][4];
+    uint32_t hidden[4] = {0u, 0u, 0u, 0u};  // bit i of row j: the map says the pixel is occluded
+    bool in[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      in[j] = x0 < W && y0 + j < H;
+      const size_t q = in[j] ? ((size_t)(y0 + j) * W + x0) / 4 : 0;  // in quads of a plane (W % 4 == 0)
+      const size_t pu = (size_t)s * 2 * (plane / 4) + q, pv = pu + plane / 4, po = (size_t)s * (plane / 4) + q;
+      {  // (a row outside the frame reads the plane's first quad instead and is masked below: no branch around the loads)
+        if constexpr (kHalf) {
+          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu], b = reinterpret_cast<const f16x4*>(flow)[pv];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { u[j][i] = (float)a[i]; v[j][i] = (float)b[i]; }
+        } else {
+          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu], b = reinterpret_cast<const f32x4*>(flow)[pv];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { u[j][i] = a[i]; v[j][i] = b[i]; }
+        }
+        if constexpr (kOcc == 1) {
+          const f32x4 o = reinterpret_cast<const f32x4*>(occ)[po];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hidden[j] |= (o[i] != 0.0f ? 1u : 0u) << i;
+        } else if constexpr (kOcc == 2) {
+          const uint32_t o = reinterpret_cast<const uint32_t*>(occ)[po];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hidden[j] |= (((o >> (8 * i)) & 255u) != 0u ? 1u : 0u) << i;
+        }
+      }
+    }
+    uint32_t c0[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool usable = in[j] && fabsf(u[j][i]) < 1048576.0f && fabsf(v[j][i]) < 1048576.0f && !((hidden[j] >> i) & 1u);
+        u[j][i] = usable ? u[j][i] : 0.0f;
+        v[j][i] = usable ? v[j][i] : 0.0f;
+        c0[j][i] = usable ? 1u : 0u;
+      }
+    // level 1: 2x2 cells of the block, cell (a, b) = columns 2a, 2a+1 of rows 2b, 2b+1
+    float u1[2][2], v1[2][2];
+    uint32_t c1[2][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        u1[b][a] = __fadd_rn(__fadd_rn(u[2 * b][2 * a], u[2 * b][2 * a + 1]), __fadd_rn(u[2 * b + 1][2 * a], u[2 * b + 1][2 * a + 1]));
+        v1[b][a] = __fadd_rn(__fadd_rn(v[2 * b][2 * a], v[2 * b][2 * a + 1]), __fadd_rn(v[2 * b + 1][2 * a], v[2 * b + 1][2 * a + 1]));
+        c1[b][a] = c0[2 * b][2 * a] + c0[2 * b][2 * a + 1] + c0[2 * b + 1][2 * a] + c0[2 * b + 1][2 * a + 1];
+      }
+    {
+      const int w = W >> 1, h = H >> 1, X = x0 >> 1;
+      const size_t lp = (size_t)w * h;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int Y = (y0 >> 1) + b;
+        if (X < w && Y < h) {
+          const size_t at = (size_t)Y * w + X;
+          OutT* const f = static_cast<OutT*>(out.flow[0]) + (size_t)s * 2 * lp + at;
+          float mu[2] = {u1[b][0], u1[b][1]}, mv[2] = {v1[b][0], v1[b][1]};
+          pyr_cell(mu[0], mv[0], c1[b][0], scale[1]);
+          pyr_cell(mu[1], mv[1], c1[b][1], scale[1]);
+          const OutT2 pu = {(OutT)mu[0], (OutT)mu[1]};
+          const OutT2 pv = {(OutT)mv[0], (OutT)mv[1]};
+          __builtin_nontemporal_store(pu, reinterpret_cast<OutT2*>(f));
+          __builtin_nontemporal_store(pv, reinterpret_cast<OutT2*>(f + lp));
+          if (n_weights) {
+            const u16x2 pc = {(uint16_t)c1[b][0], (uint16_t)c1[b][1]};
+            *reinterpret_cast<u16x2*>(static_cast<uint16_t*>(out.weight[0]) + (size_t)s * lp + at) = pc;
+          }
+        }
+      }
+    }
+    // level 2: the block
+    float su = __fadd_rn(__fadd_rn(u1[0][0], u1[0][1]), __fadd_rn(u1[1][0], u1[1][1]));
+    float sv = __fadd_rn(__fadd_rn(v1[0][0], v1[0][1]), __fadd_rn(v1[1][0], v1[1][1]));
+    uint32_t c = c1[0][0] + c1[0][1] + c1[1][0] + c1[1][1];
+    if (levels >= 2) pyr_store<OutT>(out, 2, n_weights, s, W, H, x0 >> 2, y0 >> 2, su, sv, c, scale[2]);
+    // levels 3 and 4: across the wave (every lane takes part; a lane whose block leads the cell stores it)
+#pragma unroll
+    for (int k = 3; k <= 4; ++k) {
+      const int dx = k == 3 ? 1 : 2, dy = k == 3 ? 16 : 32;
+      su = __fadd_rn(su, __shfl_xor(su, dx, 64));
+      sv = __fadd_rn(sv, __shfl_xor(sv, dx, 64));
+      c += (uint32_t)__shfl_xor((int)c, dx, 64);
+      su = __fadd_rn(su, __shfl_xor(su, dy, 64));
+      sv = __fadd_rn(sv, __shfl_xor(sv, dy, 64));
+      c += (uint32_t)__shfl_xor((int)c, dy, 64);
+      const int m = (1 << (k - 2)) - 1;  // blocks per cell side, less one
+      if (levels >= k && !(bx & m) && !(by & m)) pyr_store<OutT>(out, k, n_weights, s, W, H, x0 >> k, y0 >> k, su, sv, c, scale[k]);
+    }
+    // levels 5 and 6: the tile's 4x4 level-4 cells through LDS, [row = wave][column]
+    if (levels >= 5) {
+      if ((lane & 0x33) == 0) { s_u[wave][bx >> 2] = su; s_v[wave][bx >> 2] = sv; s_c[wave][bx >> 2] = c; }
+      __syncthreads();
+      if (wave == 0) {
+        const int X = lane & 1, Y = (lane >> 1) & 1;  // (lanes 0..3 hold the tile's 2x2 level-5 cells; the others repeat them)
+        float tu = __fadd_rn(__fadd_rn(s_u[2 * Y][2 * X], s_u[2 * Y][2 * X + 1]), __fadd_rn(s_u[2 * Y + 1][2 * X], s_u[2 * Y + 1][2 * X + 1]));
+        float tv = __fadd_rn(__fadd_rn(s_v[2 * Y][2 * X], s_v[2 * Y][2 * X + 1]), __fadd_rn(s_v[2 * Y + 1][2 * X], s_v[2 * Y + 1][2 * X + 1]));
+        uint32_t tc = s_c[2 * Y][2 * X] + s_c[2 * Y][2 * X + 1] + s_c[2 * Y + 1][2 * X] + s_c[2 * Y + 1][2 * X + 1];
+        if (lane < 4) pyr_store<OutT>(out, 5, n_weights, s, W, H, (int)blockIdx.x * 2 + X, (int)blockIdx.y * 2 + Y, tu, tv, tc, scale[5]);
+        if (levels >= 6) {
+          tu = __fadd_rn(tu, __shfl_xor(tu, 1, 64));
+          tv = __fadd_rn(tv, __shfl_xor(tv, 1, 64));
+          tc += (uint32_t)__shfl_xor((int)tc, 1, 64);
+          tu = __fadd_rn(tu, __shfl_xor(tu, 2, 64));
+          tv = __fadd_rn(tv, __shfl_xor(tv, 2, 64));
+          tc += (uint32_t)__shfl_xor((int)tc, 2, 64);
+          if (lane == 0) pyr_store<OutT>(out, 6, n_weights, s, W, H, (int)blockIdx.x, (int)blockIdx.y, tu, tv, tc, scale[6]);
+        }
+      }
+      __syncthreads();  // (the next sample of this workgroup writes the table again)
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -1481,6 +1481,53 @@ int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d
   return OFDG_OK;
 }
 
+// Flow pyramid of caller-given planes: one kernel on `stream`.  Like the statistics it reads nothing of the context's own, so
+// no completion bookkeeping is needed on any stream.
+static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && OFDG_PYR_MAX_LEVELS == kPyrMaxLevels &&
+              offsetof(struct ofdg_flow_pyramid, weight) == offsetof(DevFlowPyramid, weight) &&
+              offsetof(struct ofdg_flow_pyramid, levels) == offsetof(DevFlowPyramid, levels) &&
+              offsetof(struct ofdg_flow_pyramid, out_fmt) == offsetof(DevFlowPyramid, out_fmt) && OFDG_PYR_SCALE == 1,
+              "struct ofdg_flow_pyramid: the layout the kernel takes; flow_pyramid_arg_error spells the flag out");
+int ofdg_flow_pyramid(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int flags,
+                      const struct ofdg_flow_pyramid* pyr, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  auto fail = [&](const std::string& why) { c->err = "ofdg_flow_pyramid: " + why; return OFDG_EINVAL; };
+  const int W = c->prm.width, H = c->prm.height;
+  const DevFlowPyramid* const out = reinterpret_cast<const DevFlowPyramid*>(pyr);
+  if (const char* why = flow_pyramid_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, flags, out)) return fail(why);
+  const bool half = flow_fmt == OFDG_FMT_F16, half_out = pyr->out_fmt == OFDG_FMT_F16;
+  if ((uintptr_t)d_flow & (half ? 7 : 15)) return fail(half ? "d_flow must be 8-byte aligned (binary16)" : "d_flow must be 16-byte aligned (float32)");
+  if (d_occ && ((uintptr_t)d_occ & (occ_fmt == OFDG_FMT_U8 ? 3 : 15)))
+    return fail(occ_fmt == OFDG_FMT_U8 ? "d_occ must be 4-byte aligned (uint8)" : "d_occ must be 16-byte aligned (float32)");
+  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
+  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+  DevFlowPyramid arg = *out;
+  for (int k = arg.levels; k < kPyrMaxLevels; ++k) arg.flow[k] = arg.weight[k] = nullptr;  // (never read: nothing of them travels)
+  const dim3 grid((unsigned)((W + kPyrTile - 1) / kPyrTile), (unsigned)((H + kPyrTile - 1) / kPyrTile), (unsigned)std::min(n_samples, 65535));
+  const int kind = (half ? 6 : 0) + (half_out ? 3 : 0) + (d_occ ? (occ_fmt == OFDG_FMT_U8 ? 2 : 1) : 0);
+  const int scaled = (flags & OFDG_PYR_SCALE) ? 1 : 0, n_weights = arg.weight[0] ? 1 : 0;
+#define OFDG_PYR_LAUNCH(HALF, HALF_OUT, OCC)                                                                                          \
+  hipLaunchKernelGGL((flow_pyramid_kernel<HALF, HALF_OUT, OCC>), grid, dim3(kPyrThreads), 0, st, d_flow, d_occ, n_samples, W, H, scaled, \
+                     n_weights, arg)
+  switch (kind) {
+    case 0: OFDG_PYR_LAUNCH(false, false, 0); break;
+    case 1: OFDG_PYR_LAUNCH(false, false, 1); break;
+    case 2: OFDG_PYR_LAUNCH(false, false, 2); break;
+    case 3: OFDG_PYR_LAUNCH(false, true, 0); break;
+    case 4: OFDG_PYR_LAUNCH(false, true, 1); break;
+    case 5: OFDG_PYR_LAUNCH(false, true, 2); break;
+    case 6: OFDG_PYR_LAUNCH(true, false, 0); break;
+    case 7: OFDG_PYR_LAUNCH(true, false, 1); break;
+    case 8: OFDG_PYR_LAUNCH(true, false, 2); break;
+    case 9: OFDG_PYR_LAUNCH(true, true, 0); break;
+    case 10: OFDG_PYR_LAUNCH(true, true, 1); break;
+    default: OFDG_PYR_LAUNCH(true, true, 2); break;
+  }
+#undef OFDG_PYR_LAUNCH
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
 static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {

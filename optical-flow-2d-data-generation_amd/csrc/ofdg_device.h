@@ -133,6 +133,43 @@ inline const char* flow_stats_arg_error(const void* flow, int flow_fmt, const vo
   return nullptr;
 }
 
+// Where the levels of a flow pyramid go (struct ofdg_flow_pyramid of include/ofdg.h, field for field): passed to the kernel
+// by value.
+constexpr int kPyrMaxLevels = 6;  // OFDG_PYR_MAX_LEVELS
+struct DevFlowPyramid {
+  void* flow[kPyrMaxLevels];
+  void* weight[kPyrMaxLevels];
+  int32_t levels, out_fmt;
+};
+static_assert(sizeof(DevFlowPyramid) == 104, "struct ofdg_flow_pyramid is 104 bytes");
+// The argument rules ofdg_flow_pyramid and ofdg_host_flow_pyramid share (format codes as above; OFDG_PYR_SCALE 1): the first
+// rule broken, or nullptr.  The planes of the input are aligned by the device entry only.
+inline const char* flow_pyramid_arg_error(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
+                                          int flags, const DevFlowPyramid* pyr) {
+  if (!flow) return "d_flow is NULL";
+  if (!pyr) return "pyr is NULL";
+  if (flow_fmt != 0 && flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (occ && occ_fmt != 0 && occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (pyr->out_fmt != 0 && pyr->out_fmt != 2) return "pyr->out_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (n < 1) return "n_samples must be at least 1";
+  if (width < 1 || height < 1) return "width and height must be at least 1";
+  if (flags & ~1) return "flags holds unknown bits";
+  if (pyr->levels < 1 || pyr->levels > kPyrMaxLevels) return "pyr->levels must lie in 1..6";
+  const int cell = 1 << pyr->levels;
+  if (width % cell || height % cell) return "pyr->levels: width and height must be multiples of 2^levels";
+  int with_weight = 0;
+  for (int k = 0; k < pyr->levels; ++k) {
+    if (!pyr->flow[k]) return "pyr->flow holds NULL for a level <= levels";
+    with_weight += pyr->weight[k] ? 1 : 0;
+  }
+  if (with_weight != 0 && with_weight != pyr->levels) return "pyr->weight must be set for every level <= levels or for none";
+  for (int k = 0; k < pyr->levels; ++k) {
+    if ((uintptr_t)pyr->flow[k] & 15) return "pyr->flow: every level must be 16-byte aligned";
+    if ((uintptr_t)pyr->weight[k] & 3) return "pyr->weight: every level must be 4-byte aligned";
+  }
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
