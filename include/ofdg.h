@@ -493,6 +493,86 @@ int ofdg_flow_pyramid(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const voi
 int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
                            int flags, const struct ofdg_flow_pyramid* pyr);
 
+/* The two reductions above on planes of another size than the context's frame - the planes ofdg_crop below wrote, for one.
+ * ofdg_flow_stats_sized / ofdg_flow_pyramid_sized are ofdg_flow_stats / ofdg_flow_pyramid in every respect (definition,
+ * stream, refusals, the same kernels) with [n,2,height,width] and [n,1,height,width] planes; the plane size follows the
+ * context's own rule - width a multiple of 8 and at least 8, height even and at least 2 -, and the pyramid's rule that both
+ * are multiples of 2^levels.  OFDG_EINVAL with the field named otherwise. */
+int ofdg_flow_stats_sized(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples,
+                          int width, int height, float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream);
+int ofdg_flow_pyramid_sized(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples,
+                            int width, int height, int flags, const struct ofdg_flow_pyramid* pyr, void* stream);
+
+/*
+ * Training crop: a crop_w x crop_h window of every output of a batch - frames, both flows, both occlusion maps, both label
+ * planes -, each sample at its own position, optionally mirrored left-right and / or top-bottom, in ONE launch behind the
+ * call that wrote the planes.  The window is a pure function of (seed, global sample index), so a resumed or sharded run
+ * cuts the same windows.  Bits are moved; nothing is converted, scaled or rotated.
+ *
+ * Planes: src[k] is the [n,C,H,W] tensor of the context's frame size, dst[k] the [n,C,crop_h,crop_w] tensor of the same
+ * element type; C = 3, 3, 2, 2, 1, 1, 1, 1 in the order of the enumerators.  image_fmt (image0, image1): OFDG_FMT_F32 or
+ * OFDG_FMT_U8; flow_fmt (flow, flow1): OFDG_FMT_F32 or OFDG_FMT_F16; occ_fmt (occ0, occ1): OFDG_FMT_F32 or OFDG_FMT_U8; the
+ * labels are uint8.  Every plane is optional on its own: src[k] and dst[k] both NULL.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_crop_draw(seed, first_index + i, W, H, crop_w, crop_h, flags).
+ * Either way it is sanitised before use - x0 clamped to [0, W - crop_w], y0 to [0, H - crop_h], flags &= 3, reserved = 0 -,
+ * so no record makes the kernel read outside a plane; the sanitised record is what recs_out[i] receives.
+ *
+ * Draw (ofdg_crop_draw): one block w of Philox4x32-10 with the counter sampler's key of global index g,
+ * {seed ^ (uint32)(g >> 32) * 0x9E3779B9, (uint32)g}, and the counter {0, 0, 0x0c70, 0} (the sampler's third counter word is
+ * always 0x0fd9: none of its streams is touched):  x0 = (uint32)(((uint64)w.x * (uint32)(W - crop_w + 1)) >> 32), y0 likewise
+ * from w.y and H - crop_h + 1, HFLIP = w.z & 1 with OFDG_CROP_RANDOM_HFLIP (else 0), VFLIP = (w.z >> 1) & 1 with
+ * OFDG_CROP_RANDOM_VFLIP (else 0).  No rejection loop: a position's probability is off by at most range / 2^32.
+ *
+ * Move, for destination pixel (X, Y) of channel c:  xs = x0 + (HFLIP ? crop_w - 1 - X : X), ys = y0 + (VFLIP ? crop_h - 1 - Y
+ * : Y);  dst[i,c,Y,X] = the bits of src[i,c,ys,xs], with the sign bit inverted (XOR 0x80000000, 0x8000 for binary16) in
+ * channel 0 of flow / flow1 under HFLIP and in channel 1 under VFLIP.  NaN payloads, -0.0 and infinities travel as bits.
+ *
+ * Occlusion with OFDG_CROP_OCC_WINDOW: a pixel whose flow target lies outside the window has no partner in the cropped
+ * pair.  In source coordinates, with u, v of the GIVEN flow plane (flow for occ0, flow1 for occ1) at (xs, ys) widened to
+ * float32:  tx = floorf(fl32(fl32((float)xs + u) + 0.5f)), ty likewise from ys and v;  inside iff tx >= (float)x0 && tx <=
+ * (float)(x0 + crop_w - 1) and the same for ty with y0 and crop_h (a NaN is outside).  The map's element becomes 1.0f / 1
+ * where the source element is non-zero (float32: compares unequal to zero - a NaN does, -0.0 does not) or the target is
+ * outside, and keeps the source's bits otherwise.  No contraction anywhere.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel for
+ * any n_samples, no atomics; it reads no record of the context, so no completion bookkeeping is involved.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, crop_w not a
+ * multiple of 8 in [8, W], crop_h not even in [2, H], unknown flag bits, non-zero reserved, another format code, no plane
+ * set, src[k] without dst[k] or the reverse, OFDG_CROP_OCC_WINDOW with occ0 but no flow (occ1 / flow1 likewise), a
+ * misaligned pointer (sources as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8; destinations and both
+ * record arrays 16-byte), a destination range (recs_out included) that overlaps any other range of the job (there is no
+ * in-place form), W * H of 2^31 and more, OFDG_STREAM_OWN before any render / forward call on the context.
+ */
+#define OFDG_CROP_HFLIP         1   /* record flag: columns mirrored, u negated   */
+#define OFDG_CROP_VFLIP         2   /* record flag: rows mirrored, v negated      */
+#define OFDG_CROP_RANDOM_HFLIP  4   /* job flag: drawn records may carry HFLIP    */
+#define OFDG_CROP_RANDOM_VFLIP  8   /* job flag: drawn records may carry VFLIP    */
+#define OFDG_CROP_OCC_WINDOW   16   /* job flag: see "occlusion" above            */
+typedef struct ofdg_crop_rec { int32_t x0, y0, flags, reserved; } ofdg_crop_rec;      /* 16 bytes */
+enum { OFDG_CROP_IMAGE0, OFDG_CROP_IMAGE1, OFDG_CROP_FLOW, OFDG_CROP_FLOW1,
+       OFDG_CROP_OCC0, OFDG_CROP_OCC1, OFDG_CROP_LABEL0, OFDG_CROP_LABEL1, OFDG_CROP_PLANES };
+struct ofdg_crop_job {
+  const void* src[OFDG_CROP_PLANES];   /* [n,C,H,W] of the context's frame, or NULL  */
+  void*       dst[OFDG_CROP_PLANES];   /* [n,C,crop_h,crop_w], same element type     */
+  const ofdg_crop_rec* recs;           /* DEVICE, n records, or NULL: drawn          */
+  ofdg_crop_rec*       recs_out;       /* DEVICE, n records, or NULL                 */
+  long long first_index;  uint32_t seed;
+  int32_t crop_w, crop_h, flags, image_fmt, flow_fmt, occ_fmt, reserved;
+};
+int ofdg_crop(ofdg_ctx* ctx, const struct ofdg_crop_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes [n,C,height,width], records in host memory, no
+ * alignment asked of any pointer.  Errors as above through ofdg_host_last_error. */
+int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (pure, no GPU).  OFDG_EINVAL (ofdg_host_last_error) for out NULL, crop_w outside
+ * [1, width], crop_h outside [1, height] or flags other than OFDG_CROP_RANDOM_HFLIP | OFDG_CROP_RANDOM_VFLIP |
+ * OFDG_CROP_OCC_WINDOW. */
+int ofdg_crop_draw(uint32_t seed, long long index, int width, int height, int crop_w, int crop_h, int flags, ofdg_crop_rec* out);
+/* The Philox4x32-10 block the draw is made of (pure, no GPU): out = Philox(counter, key) - the one definition the host draw and
+ * the kernel share, exposed so that it can be held to the published known answers.  OFDG_EINVAL for a NULL pointer. */
+int ofdg_crop_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

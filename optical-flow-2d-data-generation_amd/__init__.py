@@ -105,6 +105,7 @@ EXPORTS = [
     "ofdg_object_table", "ofdg_host_object_table",
     "ofdg_flow_stats", "ofdg_host_flow_stats",
     "ofdg_flow_pyramid", "ofdg_host_flow_pyramid",
+    "ofdg_flow_stats_sized", "ofdg_flow_pyramid_sized", "ofdg_crop", "ofdg_host_crop", "ofdg_crop_draw", "ofdg_crop_philox",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -348,6 +349,102 @@ def _pyramid_record(levels, out_code, flow_ptrs, weight_ptrs):
     return rec
 
 
+# the training crop (ofdg_crop_rec / struct ofdg_crop_job / ofdg_crop, include/ofdg.h)
+CROP_HFLIP, CROP_VFLIP, CROP_RANDOM_HFLIP, CROP_RANDOM_VFLIP, CROP_OCC_WINDOW = 1, 2, 4, 8, 16
+CROP_PLANES = ("image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1")  # the order of the OFDG_CROP_* enumerators
+_CROP_CHANNELS = (3, 3, 2, 2, 1, 1, 1, 1)
+
+
+class CropRec(C.Structure):
+    """ofdg_crop_rec: the window of one sample (16 bytes)."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CropJob(C.Structure):
+    """struct ofdg_crop_job (184 bytes)."""
+    _fields_ = [("src", C.c_void_p * 8), ("dst", C.c_void_p * 8), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("flags", C.c_int32),
+                ("image_fmt", C.c_int32), ("flow_fmt", C.c_int32), ("occ_fmt", C.c_int32), ("reserved", C.c_int32)]
+
+
+def crop_format(src, dst, height, width):
+    """(n, crop_h, crop_w, image code, flow code, occ code) of the planes of Generator.crop / host_crop: src and dst are dicts keyed
+    by CROP_PLANES; src[name] is [n,C,H,W] (the labels [n,H,W] or [n,1,H,W]) of the dtype its group allows - images float32 /
+    uint8, flows float32 / float16, occlusion maps float32 / uint8, labels uint8, one dtype per group -, dst[name] the same
+    with one crop_h x crop_w for all.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU
+    tensors and numpy arrays)."""
+    def name(t):
+        return str(t.dtype).replace("torch.", "")
+
+    if not src or not isinstance(src, dict) or not isinstance(dst, dict):
+        raise ValueError("src and dst must be dicts with at least one of %s" % (CROP_PLANES,))
+    for key in list(src) + list(dst):
+        if key not in CROP_PLANES:
+            raise ValueError("unknown plane %r (known: %s)" % (key, ", ".join(CROP_PLANES)))
+    if set(src) != set(dst):
+        raise ValueError("src and dst must hold the same planes, got %s and %s" % (sorted(src), sorted(dst)))
+    groups = {"image": ({"float32": FMT_F32, "uint8": FMT_U8}, None), "flow": ({"float32": FMT_F32, "float16": FMT_F16}, None),
+              "occ": ({"float32": FMT_F32, "uint8": FMT_U8}, None), "label": ({"uint8": FMT_U8}, None)}
+    n = crop = None
+    for k, key in enumerate(CROP_PLANES):
+        if key not in src:
+            continue
+        a, b, ch = src[key], dst[key], _CROP_CHANNELS[k]
+        group = key.rstrip("01") if not key.startswith("flow") else "flow"
+        codes, seen = groups[group]
+        if name(a) not in codes or (seen is not None and seen != name(a)):
+            raise ValueError("%s must be %s%s, got %s" % (key, " or ".join(codes), "" if seen is None else " like the other %s plane" % group, name(a)))
+        groups[group] = (codes, name(a))
+        lead = tuple(a.shape[:-2])
+        if len(a.shape) < 3 or tuple(a.shape[-2:]) != (height, width) or not (len(lead) == 2 and lead[1] == ch or (group == "label" and len(lead) == 1)):
+            raise ValueError("%s must be [n,%d,%d,%d], got %s" % (key, ch, height, width, tuple(a.shape)))
+        if lead[0] < 1 or (n is not None and lead[0] != n):
+            raise ValueError("%s holds %d samples, the other planes %s" % (key, lead[0], n))
+        n = int(lead[0])
+        if name(b) != name(a) or tuple(b.shape[:-2]) != lead or len(b.shape) != len(a.shape) or (crop is not None and tuple(b.shape[-2:]) != crop):
+            raise ValueError("dst[%s] must be %s %s, got %s %s" % (key, name(a), lead + (crop if crop else ("crop_h", "crop_w")), name(b), tuple(b.shape)))
+        crop = tuple(int(v) for v in b.shape[-2:])
+    if not 8 <= crop[1] <= width or crop[1] % 8 or not 2 <= crop[0] <= height or crop[0] % 2:
+        raise ValueError("the window must be a multiple of 8 wide, even high and inside %dx%d, got %dx%d" % (width, height, crop[1], crop[0]))
+    return n, crop[0], crop[1], groups["image"][0].get(groups["image"][1], FMT_F32), groups["flow"][0].get(groups["flow"][1], FMT_F32), \
+        groups["occ"][0].get(groups["occ"][1], FMT_F32)
+
+
+def _crop_flags(hflip, vflip, occ_window):
+    return (CROP_RANDOM_HFLIP if hflip else 0) | (CROP_RANDOM_VFLIP if vflip else 0) | (CROP_OCC_WINDOW if occ_window else 0)
+
+
+def _crop_job(src, dst, ptr, codes, crop_h, crop_w, recs, recs_out, first_index, seed, flags):
+    job = CropJob()
+    for k, key in enumerate(CROP_PLANES):
+        if key in src:
+            job.src[k], job.dst[k] = ptr(src[key]), ptr(dst[key])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed, job.crop_w, job.crop_h, job.flags = int(first_index), int(seed) & 0xFFFFFFFF, crop_w, crop_h, flags
+    job.image_fmt, job.flow_fmt, job.occ_fmt = codes
+    return job
+
+
+def crop_draw(seed, index, width, height, crop_w, crop_h, hflip=False, vflip=False):
+    """ofdg_crop_draw (pure, no GPU): the window (x0, y0, flags) of global sample `index` under `seed`; flags holds CROP_HFLIP /
+    CROP_VFLIP, drawn only when hflip / vflip allow them."""
+    r = CropRec()
+    rc = lib().ofdg_crop_draw(int(seed) & 0xFFFFFFFF, int(index), width, height, crop_w, crop_h, _crop_flags(hflip, vflip, False), C.byref(r))
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    return r.x0, r.y0, r.flags
+
+
+def crop_philox(counter, key):
+    """ofdg_crop_philox (pure, no GPU): the Philox4x32-10 block of a counter (4 words) under a key (2 words), as 4 words - the
+    function the draw of the crop's records is made of."""
+    out = (C.c_uint32 * 4)()
+    rc = lib().ofdg_crop_philox(C.byref((C.c_uint32 * 4)(*counter)), C.byref((C.c_uint32 * 2)(*key)), C.byref(out))
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    return tuple(int(v) for v in out)
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -423,6 +520,12 @@ def lib():
         L.ofdg_host_flow_stats.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.c_float, i32, vp]
         L.ofdg_flow_pyramid.argtypes = [vp, vp, i32, vp, i32, i32, i32, C.POINTER(FlowPyramid), vp]
         L.ofdg_host_flow_pyramid.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(FlowPyramid)]
+        L.ofdg_flow_stats_sized.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp]
+        L.ofdg_flow_pyramid_sized.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(FlowPyramid), vp]
+        L.ofdg_crop.argtypes = [vp, C.POINTER(CropJob), i32, vp]
+        L.ofdg_host_crop.argtypes = [C.POINTER(CropJob), i32, i32, i32]
+        L.ofdg_crop_draw.argtypes = [C.c_uint32, C.c_longlong, i32, i32, i32, i32, i32, C.POINTER(CropRec)]
+        L.ofdg_crop_philox.argtypes = [C.POINTER(C.c_uint32 * 4), C.POINTER(C.c_uint32 * 2), C.POINTER(C.c_uint32 * 4)]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -702,19 +805,22 @@ class Generator:
                                             _dptr(label1) if label1 is not None else None, _dptr(rows), per, _dptr(counts),
                                             C.c_void_p(stream)))
 
-    def flow_stats(self, flow, rows, occ=None, bin_px=2.0, accumulate=False, visible_only=False, one_row=False, stream=0):
+    def flow_stats(self, flow, rows, occ=None, bin_px=2.0, accumulate=False, visible_only=False, one_row=False, stream=0, size=None):
         """Per-sample statistics of a flow tensor (ofdg_flow_stats, include/ofdg.h) into rows (alloc_flow_stats): the histogram
         of |flow| in bins of bin_px pixels, counted / bad / occluded pixels, Q8 sums of u, v and |flow|, the largest |flow|^2
         and where it is.  flow: float32 or float16 [n,2,H,W] (the forward flow or flow1), occ: None or the float32 / uint8
         [n,1,H,W] map that goes with it; the formats come from the dtypes.  accumulate: add to the rows instead of overwriting
         them; visible_only: occluded pixels count in n_occluded only; one_row: all samples reduce into rows[0].  stream: the
         stream the flow was written on, or STREAM_OWN for the internal stream the last render / forward call worked on.
-        Asynchronous; read the rows with flow_stats_numpy after synchronising."""
-        n, fcode, ocode = flow_stats_format(flow, occ, rows, self.params.height, self.params.width, one_row)
-        self._check(lib().ofdg_flow_stats(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, float(bin_px),
-                                          _stats_flags(accumulate, visible_only, one_row), _dptr(rows), C.c_void_p(stream)))
+        Asynchronous; read the rows with flow_stats_numpy after synchronising.  size=(height, width): the planes are of that
+        size instead of the context's frame - a cropped flow (ofdg_flow_stats_sized)."""
+        height, width = (int(size[0]), int(size[1])) if size is not None else (self.params.height, self.params.width)
+        n, fcode, ocode = flow_stats_format(flow, occ, rows, height, width, one_row)
+        entry, plane = (lib().ofdg_flow_stats_sized, (width, height)) if size is not None else (lib().ofdg_flow_stats, ())
+        self._check(entry(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, *plane, float(bin_px),
+                          _stats_flags(accumulate, visible_only, one_row), _dptr(rows), C.c_void_p(stream)))
 
-    def flow_pyramid(self, flow, levels, occ=None, scale=True, out_dtype=None, weights=False, out=None, stream=0):
+    def flow_pyramid(self, flow, levels, occ=None, scale=True, out_dtype=None, weights=False, out=None, stream=0, size=None):
         """The ground truth at the resolutions a coarse-to-fine loss is taken at (ofdg_flow_pyramid, include/ofdg.h): level k =
         1..levels is [n,2,H>>k,W>>k], the mean flow of the usable pixels (finite, below 2^20, not occluded) of each 2^k x 2^k
         cell, summed in a fixed 2x2 tree, so bit for bit what host_flow_pyramid gives.  flow: float32 or float16 [n,2,H,W] (the
@@ -722,16 +828,40 @@ class Generator:
         (the mean times 2^-k).  out_dtype: torch.float32 / torch.float16, default the flow's.  weights: also the usable pixels
         of every cell (uint16 tensors [n,1,H>>k,W>>k]; 4096 at most).  out: what a former call or
         alloc_flow_pyramid returned, to write into (out_dtype and weights then follow it).  stream: the stream the flow was
-        written on, or STREAM_OWN.  Asynchronous.  Returns the list of levels, or (levels, weights) with weights."""
+        written on, or STREAM_OWN.  Asynchronous.  Returns the list of levels, or (levels, weights) with weights.
+        size=(height, width): the planes are of that size instead of the context's frame - a cropped flow
+        (ofdg_flow_pyramid_sized)."""
         n, height, width = int(flow.shape[0]), self.params.height, self.params.width
+        if size is not None:
+            height, width = int(size[0]), int(size[1])
         if out is None:
             out = alloc_flow_pyramid(n, height, width, levels, flow.dtype if out_dtype is None else out_dtype, weights, flow.device)
         lv, wt = out if isinstance(out, tuple) else (out, None)
         n, fcode, ocode, out_code = flow_pyramid_format(flow, occ, levels, lv, wt, height, width)
         rec = _pyramid_record(int(levels), out_code, [_dptr(t) for t in lv], None if wt is None else [_dptr(t) for t in wt])
-        self._check(lib().ofdg_flow_pyramid(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n,
-                                            PYR_SCALE if scale else 0, C.byref(rec), C.c_void_p(stream)))
+        entry, plane = (lib().ofdg_flow_pyramid_sized, (width, height)) if size is not None else (lib().ofdg_flow_pyramid, ())
+        self._check(entry(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, *plane,
+                          PYR_SCALE if scale else 0, C.byref(rec), C.c_void_p(stream)))
         return out
+
+    def crop(self, src, dst, recs=None, first_index=0, seed=None, hflip=False, vflip=False, occ_window=False, recs_out=None, stream=0):
+        """The training window of every plane of a batch in one launch (ofdg_crop, include/ofdg.h): src and dst are dicts keyed
+        by CROP_PLANES (image0, image1, flow, flow1, occ0, occ1, label0, label1; any subset), src[name] the [n,C,H,W] tensor a
+        render / forward call wrote, dst[name] the [n,C,crop_h,crop_w] tensor of the same dtype (alloc_crop).  recs: None - the
+        window of sample i is crop_draw(seed, first_index + i, ...) with flips drawn when hflip / vflip allow them - or an int32
+        device tensor [n,4] of (x0, y0, flags, 0), taken as given (sanitised: clamped into the frame, flags & 3).  seed: default
+        the context's.  A mirrored window has the sign of u (hflip) / v (vflip) inverted in both flows.  occ_window: occ0 /
+        occ1 also become 1 where the flow / flow1 target leaves the window.  recs_out: None or an int32 device tensor [n,4] that
+        receives the records used.  stream: the stream the planes were written on, or STREAM_OWN.  Asynchronous; there is no
+        in-place form.  Returns dst."""
+        n, crop_h, crop_w, *codes = crop_format(src, dst, self.params.height, self.params.width)
+        for t in (recs, recs_out):
+            if t is not None and (str(t.dtype) != "torch.int32" or tuple(t.shape) != (n, 4)):
+                raise ValueError("recs and recs_out must be int32 [%d,4], got %s %s" % (n, t.dtype, tuple(t.shape)))
+        job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, None if recs is None else _dptr(recs), None if recs_out is None else _dptr(recs_out),
+                        first_index, self.params.seed if seed is None else seed, _crop_flags(hflip, vflip, occ_window))
+        self._check(lib().ofdg_crop(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -1176,6 +1306,46 @@ def host_flow_pyramid(flow, levels, occ=None, scale=True, out_dtype=None, weight
     return (lv, wt) if weights else lv
 
 
+def alloc_crop(src, crop_h, crop_w, zero=True):
+    """The destination dict of Generator.crop for a source dict: every plane of src with its last two dimensions replaced by
+    crop_h x crop_w, same dtype and device (torch tensors or numpy arrays, as src holds), zeroed - on torch's current stream -
+    unless zero=False: the crop writes every element, and a buffer that is not filled needs no ordering against the stream
+    the crop runs on."""
+    out = {}
+    for key, t in src.items():
+        shape = tuple(t.shape[:-2]) + (int(crop_h), int(crop_w))
+        if hasattr(t, "new_zeros"):
+            out[key] = t.new_zeros(shape) if zero else t.new_empty(shape)
+        else:
+            import numpy as np
+            out[key] = np.zeros(shape, t.dtype)
+    return out
+
+
+def host_crop(src, crop_h, crop_w, recs=None, first_index=0, seed=0, hflip=False, vflip=False, occ_window=False):
+    """ofdg_host_crop (no GPU): the windows of HOST arrays - src a dict of numpy arrays keyed by CROP_PLANES, as Generator.crop
+    takes tensors; recs None (drawn from seed and first_index) or an int32 array [n,4].  Returns (dst, recs_used): the dict of
+    cropped arrays and the int32 [n,4] records after sanitising."""
+    import numpy as np
+    src = {k: np.ascontiguousarray(v) for k, v in src.items()}
+    if not src:
+        raise ValueError("src must hold at least one of %s" % (CROP_PLANES,))
+    height, width = next(iter(src.values())).shape[-2:]
+    dst = alloc_crop(src, crop_h, crop_w)
+    n, crop_h, crop_w, *codes = crop_format(src, dst, height, width)
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.int32 or recs.shape != (n, 4):
+            raise ValueError("recs must be int32 [%d,4], got %s %s" % (n, recs.dtype, recs.shape))
+    used = np.zeros((n, 4), np.int32)
+    job = _crop_job(src, dst, lambda a: a.ctypes.data, codes, crop_h, crop_w, None if recs is None else recs.ctypes.data, used.ctypes.data,
+                    first_index, seed, _crop_flags(hflip, vflip, occ_window))
+    rc = lib().ofdg_host_crop(C.byref(job), n, width, height)
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    return dst, used
+
+
 class HostSampler:
     """The reference-stream blueprint sampler on its own (host only, no GPU needed)."""
 
@@ -1312,12 +1482,21 @@ class FlowLoader:
     pyramid=L: the flow pyramid of every batch (Generator.flow_pyramid with levels=L, scale=pyramid_scale, in the flow's dtype,
     enqueued right behind the batch on the same internal stream; with "occ0" among extras= the map is passed) in levels cycled
     with the ring; every batch is then (image0, image1, flow, {...}) and the dict also holds "flow_pyramid" (the list of L
-    tensors [n,2,H>>k,W>>k]) and, with pyramid_weights=True, "flow_pyramid_weights" (the list of uint16 [n,1,H>>k,W>>k])."""
+    tensors [n,2,H>>k,W>>k]) and, with pyramid_weights=True, "flow_pyramid_weights" (the list of uint16 [n,1,H>>k,W>>k]).
+    crop=(crop_h, crop_w): every batch is cut to a training window per sample (Generator.crop into a second ring of buffers,
+    enqueued right behind the batch on the same internal stream; windows drawn from the context's seed and the batch's
+    first global index - shard_first_index of its step -, so start= resumes the same windows; crop_hflip / crop_vflip allow
+    drawn flips, crop_occ_window marks pixels whose target leaves the window in occ0 / occ1).  stats= and pyramid= then reduce
+    the CROPPED flow and occ0; the loader yields the cropped tensors and extras, every batch is (image0, image1, flow, {...})
+    and the dict also holds "crop" (int32 [n,4]: x0, y0, flags, 0).  objects=True with crop= raises: its boxes are of the
+    uncropped frame."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
-                 **kw):
+                 crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, **kw):
         import torch
+        if objects and crop is not None:
+            raise ValueError("objects=True does not combine with crop=: the table's boxes are of the uncropped frame")
         if objects and (extras is None or "label0" not in extras or "label1" not in extras):
             raise ValueError("objects=True needs the label planes it reduces: extras= must contain \"label0\" and \"label1\"")
         compact = image_dtype not in (None, torch.float32) or flow_dtype not in (None, torch.float32)
@@ -1345,7 +1524,18 @@ class FlowLoader:
         self.sbufs = [alloc_flow_stats(p.batch_size) if stats else None for _ in range(self.prefetch)]
         self.stats_bin_px = float(stats_bin_px)
         self.pyramid, self.pyramid_scale = int(pyramid), bool(pyramid_scale)
-        self.pbufs = [alloc_flow_pyramid(p.batch_size, p.height, p.width, self.pyramid, flow_dtype, bool(pyramid_weights))
+        self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
+        self.crop_flips, self.crop_occ_window = (bool(crop_hflip), bool(crop_vflip)), bool(crop_occ_window)
+        self.cbufs = [None] * self.prefetch     # (cropped planes by name, records) of each set
+        if self.crop is not None:
+            for j in range(self.prefetch):
+                planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
+                # (not filled: the crop writes every element and every record, and a fill on torch's stream would not be ordered
+                # against the internal stream the first crops run on)
+                self.cbufs[j] = (alloc_crop(planes, *self.crop, zero=False), torch.empty((p.batch_size, 4), dtype=torch.int32, device="cuda"))
+                crop_format(planes, self.cbufs[j][0], p.height, p.width)  # (raises for a window the frame does not allow)
+        ph, pw = self.crop if self.crop is not None else (p.height, p.width)
+        self.pbufs = [alloc_flow_pyramid(p.batch_size, ph, pw, self.pyramid, flow_dtype, bool(pyramid_weights))
                       if self.pyramid else None for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
@@ -1360,7 +1550,10 @@ class FlowLoader:
         chain = torch.cuda.ExternalStream(s)
         if self.released[j] is not None:
             chain.wait_event(self.released[j])
+        step = self.gen.step if self.crop is not None else 0
         self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
+        if self.crop is not None:
+            return self._enqueue_cropped(j, s, chain, step)
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         if self.sbufs[j] is not None:
@@ -1370,6 +1563,30 @@ class FlowLoader:
             occ = self.xbufs[j].get("occ0") if self.xbufs[j] is not None else None
             self.gen.flow_pyramid(self.bufs[j][2], self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s)
         self.ready[j].record(chain)
+
+    def _enqueue_cropped(self, j, s, chain, step):
+        """The window of batch `step` (just enqueued into set j on stream s), then the reductions on the cropped planes."""
+        p = self.gen.params
+        planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
+        out, recs = self.cbufs[j]
+        self.gen.crop(planes, out, first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank), hflip=self.crop_flips[0],
+                      vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
+        if self.sbufs[j] is not None:
+            self.gen.flow_stats(out["flow"], self.sbufs[j], occ=out.get("occ0"), bin_px=self.stats_bin_px, stream=s, size=self.crop)
+        if self.pbufs[j] is not None:
+            self.gen.flow_pyramid(out["flow"], self.pyramid, occ=out.get("occ0"), scale=self.pyramid_scale, out=self.pbufs[j], stream=s,
+                                  size=self.crop)
+        self.ready[j].record(chain)
+
+    def _add_reductions(self, more, j):
+        """the statistics and the pyramid of set j into the batch's dict"""
+        if self.sbufs[j] is not None:
+            more["flow_stats"] = self.sbufs[j]
+        if self.pbufs[j] is not None:
+            if isinstance(self.pbufs[j], tuple):
+                more["flow_pyramid"], more["flow_pyramid_weights"] = self.pbufs[j]
+            else:
+                more["flow_pyramid"] = self.pbufs[j]
 
     @property
     def consumed(self):
@@ -1393,17 +1610,17 @@ class FlowLoader:
             self._enqueue(f)
             self.head += 1
         self.k += 1
+        if self.crop is not None:
+            out, recs = self.cbufs[j]
+            more = {k: v for k, v in out.items() if k not in ("image0", "image1", "flow")}
+            more["crop"] = recs
+            self._add_reductions(more, j)
+            return (out["image0"], out["image1"], out["flow"], more)
         if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None:
             more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
             if self.obufs[j] is not None:
                 more.update(objects=self.obufs[j][0], object_counts=self.obufs[j][1])
-            if self.sbufs[j] is not None:
-                more["flow_stats"] = self.sbufs[j]
-            if self.pbufs[j] is not None:
-                if isinstance(self.pbufs[j], tuple):
-                    more["flow_pyramid"], more["flow_pyramid_weights"] = self.pbufs[j]
-                else:
-                    more["flow_pyramid"] = self.pbufs[j]
+            self._add_reductions(more, j)
             return self.bufs[j] + (more,)
         if self.extras is not None:
             return self.bufs[j] + (self.xbufs[j],)

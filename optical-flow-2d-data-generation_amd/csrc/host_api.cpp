@@ -317,4 +317,86 @@ int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int 
   return OFDG_OK;
 }
 
+// ofdg_crop on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising and the window
+// test are the functions the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy, so no alignment is asked.
+static_assert(sizeof(ofdg_crop_rec) == sizeof(DevCropRec) && sizeof(struct ofdg_crop_job) == sizeof(DevCropJob) &&
+              offsetof(struct ofdg_crop_job, recs) == 128 && offsetof(struct ofdg_crop_job, first_index) == 144 &&
+              offsetof(struct ofdg_crop_job, seed) == 152 && offsetof(struct ofdg_crop_job, crop_w) == 156 &&
+              offsetof(struct ofdg_crop_job, reserved) == 180 && OFDG_CROP_PLANES == kCropPlanes && OFDG_CROP_RANDOM_HFLIP == 4 &&
+              OFDG_CROP_RANDOM_VFLIP == 8 && OFDG_CROP_OCC_WINDOW == 16,
+              "struct ofdg_crop_job: 184 bytes, the layout crop_arg_error reads");
+int ofdg_crop_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
+  if (!counter || !key || !out) { g_host_error = "ofdg_crop_philox: counter, key or out is NULL"; return OFDG_EINVAL; }
+  const CropWords w = crop_philox(CropWords{counter[0], counter[1], counter[2], counter[3]}, key[0], key[1]);
+  out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w;
+  return OFDG_OK;
+}
+int ofdg_crop_draw(uint32_t seed, long long index, int width, int height, int crop_w, int crop_h, int flags, ofdg_crop_rec* out) {
+  const char* why = !out ? "out is NULL"
+                    : crop_w < 1 || crop_w > width ? "crop_w must lie in [1, width]"
+                    : crop_h < 1 || crop_h > height ? "crop_h must lie in [1, height]"
+                    : (flags & ~(OFDG_CROP_RANDOM_HFLIP | OFDG_CROP_RANDOM_VFLIP | OFDG_CROP_OCC_WINDOW)) ? "flags holds unknown bits" : nullptr;
+  if (why) { g_host_error = std::string("ofdg_crop_draw: ") + why; return OFDG_EINVAL; }
+  const DevCropRec r = crop_draw_rec(seed, (unsigned long long)index, width, height, crop_w, crop_h, flags);
+  *out = ofdg_crop_rec{r.x0, r.y0, r.flags, r.reserved};
+  return OFDG_OK;
+}
+int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, int height) {
+  const DevCropJob* const j = reinterpret_cast<const DevCropJob*>(job);
+  const char* why = (width < 1 || height < 1) ? "width and height must be at least 1" : crop_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_crop: ") + why; return OFDG_EINVAL; }
+  const int cw = j->crop_w, ch = j->crop_h;
+  const size_t frame = (size_t)width * height, window = (size_t)cw * ch;
+  auto flow_at = [&](const void* flow, size_t i) {
+    if (j->flow_fmt == OFDG_FMT_F16) {
+      uint16_t h;
+      std::memcpy(&h, static_cast<const uint8_t*>(flow) + 2 * i, 2);
+      return half_bits_to_float(h);
+    }
+    float f;
+    std::memcpy(&f, static_cast<const uint8_t*>(flow) + 4 * i, 4);
+    return f;
+  };
+  for (int i = 0; i < n_samples; ++i) {
+    DevCropRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + 16 * (size_t)i, 16);
+    else r = crop_draw_rec(j->seed, (unsigned long long)(j->first_index + i), width, height, cw, ch, j->flags);
+    r = crop_sanitise(r, width, height, cw, ch);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + 16 * (size_t)i, &r, 16);
+    const bool hflip = r.flags & OFDG_CROP_HFLIP, vflip = r.flags & OFDG_CROP_VFLIP;
+    for (int k = 0; k < kCropPlanes; ++k) {
+      if (!j->src[k]) continue;
+      const int C = crop_channels(k), es = crop_elem_bytes(*j, k);
+      const bool is_flow = k == OFDG_CROP_FLOW || k == OFDG_CROP_FLOW1, is_occ = k == OFDG_CROP_OCC0 || k == OFDG_CROP_OCC1;
+      const void* const flow = (is_occ && (j->flags & OFDG_CROP_OCC_WINDOW)) ? j->src[k - 2] : nullptr;
+      for (int c = 0; c < C; ++c) {
+        const uint8_t* const sp = static_cast<const uint8_t*>(j->src[k]) + ((size_t)i * C + c) * frame * es;
+        uint8_t* const dp = static_cast<uint8_t*>(j->dst[k]) + ((size_t)i * C + c) * window * es;
+        const bool negate = is_flow && (c == 0 ? hflip : vflip);
+        for (int Y = 0; Y < ch; ++Y)
+          for (int X = 0; X < cw; ++X) {
+            const int xs = r.x0 + (hflip ? cw - 1 - X : X), ys = r.y0 + (vflip ? ch - 1 - Y : Y);
+            const size_t at = (size_t)ys * width + xs;
+            uint8_t e[4];
+            std::memcpy(e, sp + at * es, es);
+            if (negate) e[es - 1] ^= 0x80u;  // (little-endian: the sign bit is in the element's last byte)
+            if (flow) {
+              const float u = flow_at(flow, (size_t)i * 2 * frame + at), v = flow_at(flow, ((size_t)i * 2 + 1) * frame + at);
+              const bool inside = crop_target_inside(xs, u, r.x0, cw) && crop_target_inside(ys, v, r.y0, ch);
+              if (es == 4) {
+                float f;
+                std::memcpy(&f, e, 4);
+                if (f != 0.0f || !inside) { f = 1.0f; std::memcpy(e, &f, 4); }
+              } else if (e[0] != 0 || !inside) {
+                e[0] = 1;
+              }
+            }
+            std::memcpy(dp + ((size_t)Y * cw + X) * es, e, es);
+          }
+      }
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

@@ -3459,4 +3459,225 @@ __global__ __launch_bounds__(kPyrThreads) void flow_pyramid_kernel(const void* _
   }
 }
 
+// --------------------------------------------------------------------------
+// Training crop (ofdg_crop): a window of every output plane of a batch, per sample its own, optionally mirrored, in one
+// launch.  Bits are moved; the only other operations are the sign-bit XOR of a mirrored flow component and the window test
+// of OFDG_CROP_OCC_WINDOW (include/ofdg.h), so the result is the host twin's bit for bit.
+// --------------------------------------------------------------------------
+// The destination of a (plane, channel, sample) is crop_w * crop_h elements without gaps, a whole number of 16-byte pieces
+// (crop_w % 8 == 0, crop_h even).  A piece is 4 float32, 8 binary16 - both inside one row - or 16 uint8: two halves of 8, each
+// inside one row (a row of uint8 is whole halves, two rows are whole pieces: the rows are paired).  A workgroup owns 1024
+// consecutive pieces of one channel, lane t the pieces t, t + 256, t + 512, t + 768 of them, so every store instruction of a
+// wave writes 1 KiB of consecutive, 16-byte aligned destination bytes: whole 128-byte lines.  blockIdx.x counts the
+// workgroups of all 14 channel slots of a sample (the table of their first blocks comes with the launch: absent planes own
+// none), blockIdx.y the samples.  Sources: x0 is arbitrary, so float32 is read by 4-byte loads, binary16 and uint8 by the
+// aligned 4-byte words that cover the run - one word more than the run is long when it starts inside a word, that index
+// clamped to the tensor's last word - and a byte funnel shift (v_alignbit); a mirrored run is read at its mirrored address and reversed in registers.  All loads
+// of a lane's four pieces are requested before the first is used.  Pieces past the channel's end (the last workgroup) read
+// pixel (0, 0) and are not stored.  The record is drawn or read, and sanitised, on uniform values once per (workgroup,
+// sample); workgroup 0 of a sample writes it back from lane 0 with a vector store.  The occlusion planes under
+// OFDG_CROP_OCC_WINDOW take a path of their own that also fetches both flow components of the piece's pixels, one piece at a
+// time.  No LDS, no atomics, no scratch.
+constexpr int kCropThreads = 256;
+constexpr int kCropPerLane = 4;  // 16-byte pieces a lane moves
+constexpr int kCropSlots = 14;   // channels of the eight planes: 3 3 2 2 1 1 1 1
+struct DevCropGrid {
+  uint32_t first_block[kCropSlots + 1];  // slot s owns blocks [first_block[s], first_block[s + 1]) of blockIdx.x
+};
+typedef uint32_t crop_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void crop_store(crop_u32x4* p, crop_u32x4 v) {
+  __builtin_nontemporal_store(v, p);  // (whole lines, read next by another kernel: measured against plain stores, CHANGELOG)
+}
+// kWords 32-bit words of destination: the kWords * 4 / kES elements that start at element `first` of the tensor at p (`last`:
+// index of its last whole word), in destination order - reversed element by element when the row is mirrored.
+template <int kES, int kWords>
+__device__ __forceinline__ void crop_fetch(const uint32_t* __restrict__ p, size_t last, size_t first, bool mirrored, uint32_t (&out)[kWords]) {
+  uint32_t t[kWords];
+  if constexpr (kES == 4) {
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) t[i] = p[first + i];
+  } else {
+    const size_t byte = first * kES, word = byte >> 2;
+    const uint32_t shift = ((uint32_t)byte & 3u) * 8u;
+    uint32_t w[kWords + 1];
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) w[i] = p[word + i];  // (the run lies inside the tensor, so these words do)
+    // the word behind them only when the run starts inside a word: an aligned run (the same for every lane of a sample: W, the
+    // window's width and a run's length are multiples of 8 elements) requests no byte it does not move
+    w[kWords] = shift ? p[word + kWords < last ? word + kWords : last] : 0u;
+#pragma unroll
+    for (int i = 0; i < kWords; ++i) t[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], shift);
+  }
+#pragma unroll
+  for (int i = 0; i < kWords; ++i) {
+    const uint32_t m = t[kWords - 1 - i];
+    const uint32_t r = kES == 4 ? m : kES == 2 ? (m >> 16) | (m << 16) : __builtin_bswap32(m);
+    out[i] = mirrored ? r : t[i];
+  }
+}
+// Position of a lane's pieces: piece q of a channel starts at pixel q * kPixels of the crop_w x crop_h window.
+struct CropAt {
+  uint32_t X, Y;
+};
+__device__ __forceinline__ CropAt crop_advance(CropAt a, uint32_t dX, uint32_t dY, uint32_t crop_w) {
+  a.X += dX;
+  a.Y += dY;
+  if (a.X >= crop_w) { a.X -= crop_w; ++a.Y; }
+  return a;
+}
+// First source element (relative to the channel's plane) of the run of `run` destination pixels that starts at (X, Y).
+__device__ __forceinline__ size_t crop_source(const DevCropRec& r, CropAt a, int run, int W, int crop_w, int crop_h) {
+  const uint32_t ys = (uint32_t)r.y0 + ((r.flags & 2) ? (uint32_t)crop_h - 1u - a.Y : a.Y);
+  const uint32_t xs = (uint32_t)r.x0 + ((r.flags & 1) ? (uint32_t)crop_w - a.X - (uint32_t)run : a.X);
+  return (size_t)ys * (uint32_t)W + xs;
+}
+// The plain move of one channel: src / dst are the tensors of the plane, `chan` = sample * C + channel, sign: the XOR of
+// every destination word (the sign bits of a mirrored flow component, else 0).
+template <int kES>
+__device__ __forceinline__ void crop_move(const void* __restrict__ src, void* __restrict__ dst, size_t chan, size_t tensor_words,
+                                          const DevCropRec& r, int W, int H, int crop_w, int crop_h, uint32_t block, uint32_t sign) {
+  constexpr int kPixels = 16 / kES;                       // of a piece
+  constexpr int kRun = kES == 1 ? 8 : kPixels;            // of one fetch: uint8 pieces are two runs
+  const uint32_t pieces = (uint32_t)crop_w * (uint32_t)crop_h / kPixels;
+  const uint32_t* const sp = static_cast<const uint32_t*>(src);
+  const size_t plane = chan * ((size_t)W * H), last = tensor_words - 1;
+  crop_u32x4* const dp = static_cast<crop_u32x4*>(dst) + chan * pieces;
+  const uint32_t q0 = block * (kCropThreads * kCropPerLane) + threadIdx.x;
+  const uint32_t dX = (kCropThreads * kPixels) % (uint32_t)crop_w, dY = (kCropThreads * kPixels) / (uint32_t)crop_w;
+  const bool mirrored = r.flags & 1;
+  CropAt a;
+  a.Y = (q0 * kPixels) / (uint32_t)crop_w;  // (q0 * kPixels < 2^31 + 2^14: crop_arg_error bounds the frame)
+  a.X = q0 * kPixels - a.Y * (uint32_t)crop_w;
+  uint32_t v[kCropPerLane][4];
+#pragma unroll
+  for (int j = 0; j < kCropPerLane; ++j) {
+    const bool ok = q0 + j * kCropThreads < pieces;
+    const CropAt at = ok ? a : CropAt{0u, 0u};
+    if constexpr (kES == 1) {
+      const CropAt b = crop_advance(at, 8u, 0u, (uint32_t)crop_w);
+      uint32_t lo[2], hi[2];
+      crop_fetch<1, 2>(sp, last, plane + crop_source(r, at, kRun, W, crop_w, crop_h), mirrored, lo);
+      crop_fetch<1, 2>(sp, last, plane + crop_source(r, ok ? b : at, kRun, W, crop_w, crop_h), mirrored, hi);
+      v[j][0] = lo[0]; v[j][1] = lo[1]; v[j][2] = hi[0]; v[j][3] = hi[1];
+    } else {
+      crop_fetch<kES, 4>(sp, last, plane + crop_source(r, at, kRun, W, crop_w, crop_h), mirrored, v[j]);
+    }
+    a = crop_advance(a, dX, dY, (uint32_t)crop_w);
+  }
+#pragma unroll
+  for (int j = 0; j < kCropPerLane; ++j) {
+    const uint32_t q = q0 + j * kCropThreads;
+    if (q < pieces) {
+      const crop_u32x4 o = {v[j][0] ^ sign, v[j][1] ^ sign, v[j][2] ^ sign, v[j][3] ^ sign};
+      crop_store(dp + q, o);
+    }
+  }
+}
+// An occlusion plane under OFDG_CROP_OCC_WINDOW: the map's elements (kES 4: float32, 1: uint8) with both components of the
+// flow that goes with it (kFES 4: float32, 2: binary16) at the same source pixels; an element becomes 1.0f / 1 where it is
+// non-zero (float32: compares unequal to 0, so a NaN does and -0.0 does not) or the flow target leaves the window.
+template <int kES, int kFES>
+__device__ __forceinline__ void crop_occ_window(const void* __restrict__ src, void* __restrict__ dst, const void* __restrict__ flow, size_t sample,
+                                                size_t n, const DevCropRec& r, int W, int H, int crop_w, int crop_h, uint32_t block) {
+  constexpr int kPixels = 16 / kES, kRun = kES == 1 ? 8 : 4, kRuns = kPixels / kRun;
+  constexpr int kOccWords = kRun * kES / 4, kFlowWords = kRun * kFES / 4;
+  const uint32_t pieces = (uint32_t)crop_w * (uint32_t)crop_h / kPixels;
+  const size_t frame = (size_t)W * H;
+  const uint32_t* const sp = static_cast<const uint32_t*>(src);
+  const uint32_t* const fp = static_cast<const uint32_t*>(flow);
+  const size_t last = n * frame * kES / 4 - 1, flow_last = n * 2 * frame * kFES / 4 - 1;
+  crop_u32x4* const dp = static_cast<crop_u32x4*>(dst) + sample * pieces;
+  const uint32_t q0 = block * (kCropThreads * kCropPerLane) + threadIdx.x;
+  const uint32_t dX = (kCropThreads * kPixels) % (uint32_t)crop_w, dY = (kCropThreads * kPixels) / (uint32_t)crop_w;
+  const bool mirrored = r.flags & 1;
+  CropAt a;
+  a.Y = (q0 * kPixels) / (uint32_t)crop_w;
+  a.X = q0 * kPixels - a.Y * (uint32_t)crop_w;
+#pragma unroll 1  // (one piece at a time: up to 34 loads each, and the registers of four would halve the occupancy of the whole kernel)
+  for (int j = 0; j < kCropPerLane; ++j) {
+    const uint32_t q = q0 + j * kCropThreads;
+    const bool ok = q < pieces;
+    uint32_t o[4];
+#pragma unroll
+    for (int g = 0; g < kRuns; ++g) {
+      CropAt at = ok ? a : CropAt{0u, 0u};
+      if (g == 1 && ok) at = crop_advance(at, 8u, 0u, (uint32_t)crop_w);
+      const size_t first = crop_source(r, at, kRun, W, crop_w, crop_h);
+      uint32_t m[kOccWords], u[kFlowWords], v[kFlowWords];
+      crop_fetch<kES, kOccWords>(sp, last, sample * frame + first, mirrored, m);
+      crop_fetch<kFES, kFlowWords>(fp, flow_last, sample * 2 * frame + first, mirrored, u);
+      crop_fetch<kFES, kFlowWords>(fp, flow_last, (sample * 2 + 1) * frame + first, mirrored, v);
+      const int ys = r.y0 + (int)((r.flags & 2) ? (uint32_t)crop_h - 1u - at.Y : at.Y);
+#pragma unroll
+      for (int p = 0; p < kRun; ++p) {
+        const int xs = r.x0 + (int)(mirrored ? (uint32_t)crop_w - 1u - (at.X + p) : at.X + p);
+        float fu, fv;
+        if constexpr (kFES == 4) {
+          fu = __uint_as_float(u[p]);
+          fv = __uint_as_float(v[p]);
+        } else {
+          fu = (float)__builtin_bit_cast(_Float16, (uint16_t)(u[p / 2] >> (16 * (p & 1))));
+          fv = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[p / 2] >> (16 * (p & 1))));
+        }
+        const bool inside = crop_target_inside(xs, fu, r.x0, crop_w) && crop_target_inside(ys, fv, r.y0, crop_h);
+        if constexpr (kES == 4) {
+          m[p] = (__uint_as_float(m[p]) != 0.0f || !inside) ? 0x3f800000u : m[p];
+        } else {
+          const uint32_t sh = 8u * (p & 3), b = (m[p / 4] >> sh) & 255u;
+          m[p / 4] = (m[p / 4] & ~(255u << sh)) | (((b != 0u || !inside) ? 1u : b) << sh);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < kOccWords; ++i) o[g * kOccWords + i] = m[i];
+    }
+    if (ok) {
+      const crop_u32x4 ov = {o[0], o[1], o[2], o[3]};
+      crop_store(dp + q, ov);
+    }
+    a = crop_advance(a, dX, dY, (uint32_t)crop_w);
+  }
+}
+template <bool kImageU8, bool kFlowHalf, bool kOccU8>
+__global__ __launch_bounds__(kCropThreads) void crop_kernel(const DevCropJob job, const DevCropGrid grid, int n, int W, int H) {
+  constexpr int kImageES = kImageU8 ? 1 : 4, kFlowES = kFlowHalf ? 2 : 4, kOccES = kOccU8 ? 1 : 4;
+  const uint32_t bx = blockIdx.x;
+  int slot = 0;
+#pragma unroll
+  for (int s = 1; s < kCropSlots; ++s) slot += bx >= grid.first_block[s] ? 1 : 0;
+  uint32_t first = 0;
+#pragma unroll
+  for (int s = 1; s < kCropSlots; ++s) first = slot == s ? grid.first_block[s] : first;
+  const uint32_t block = bx - first;
+  const int plane = slot < 6 ? slot / 3 : slot < 10 ? 2 + (slot - 6) / 2 : slot - 6;
+  const int channel = slot < 6 ? slot % 3 : slot < 10 ? (slot - 6) % 2 : 0;
+  const void* src = nullptr;
+  void* dst = nullptr;
+#pragma unroll
+  for (int k = 0; k < kCropPlanes; ++k) {  // (selects, not an indexed read of the argument)
+    src = plane == k ? job.src[k] : src;
+    dst = plane == k ? job.dst[k] : dst;
+  }
+  const int crop_w = job.crop_w, crop_h = job.crop_h, C = crop_channels(plane);
+  const size_t frame = (size_t)W * H;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    DevCropRec r;
+    if (job.recs) r = job.recs[i];
+    else r = crop_draw_rec(job.seed, (unsigned long long)(job.first_index + i), W, H, crop_w, crop_h, job.flags);
+    r = crop_sanitise(r, W, H, crop_w, crop_h);
+    if (job.recs_out && bx == 0u && threadIdx.x == 0u) *reinterpret_cast<int4*>(job.recs_out + i) = make_int4(r.x0, r.y0, r.flags, 0);
+    const size_t chan = (size_t)i * C + channel, elems = (size_t)n * C * frame;
+    if (plane < 2) {
+      crop_move<kImageES>(src, dst, chan, elems * kImageES / 4, r, W, H, crop_w, crop_h, block, 0u);
+    } else if (plane < 4) {
+      const bool negate = channel == 0 ? (r.flags & 1) : (r.flags & 2);
+      crop_move<kFlowES>(src, dst, chan, elems * kFlowES / 4, r, W, H, crop_w, crop_h, block, negate ? (kFlowHalf ? 0x80008000u : 0x80000000u) : 0u);
+    } else if (plane < 6) {
+      if (job.flags & 16) crop_occ_window<kOccES, kFlowES>(src, dst, plane == 4 ? job.src[2] : job.src[3], (size_t)i, (size_t)n, r, W, H, crop_w, crop_h, block);
+      else crop_move<kOccES>(src, dst, chan, elems * kOccES / 4, r, W, H, crop_w, crop_h, block, 0u);
+    } else {
+      crop_move<1>(src, dst, chan, elems / 4, r, W, H, crop_w, crop_h, block, 0u);
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -1444,11 +1444,10 @@ static_assert(sizeof(ofdg_flow_stats_row) == sizeof(DevFlowStatsRow) && OFDG_FLO
               "ofdg_flow_stats_row: 304 bytes without padding, the layout the kernel adds to");
 static_assert(OFDG_FMT_F32 == 0 && OFDG_FMT_U8 == 1 && OFDG_FMT_F16 == 2 && OFDG_STATS_ACCUMULATE == 1 && OFDG_STATS_VISIBLE_ONLY == 2 &&
               OFDG_STATS_ONE_ROW == 4, "flow_stats_arg_error spells these codes out");
-int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, float bin_px,
-                    int flags, ofdg_flow_stats_row* d_rows, void* stream) {
-  if (!c) return OFDG_EINVAL;
-  auto fail = [&](const std::string& why) { c->err = "ofdg_flow_stats: " + why; return OFDG_EINVAL; };
-  const int W = c->prm.width, H = c->prm.height;
+// (`who`: the entry's name in the error text; W, H: the context's frame, or the plane size a sized call gave and checked)
+static int flow_stats_on(ofdg_ctx* c, const char* who, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
+                         int n_samples, float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream) {
+  auto fail = [&](const std::string& why) { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; };
   if (const char* why = flow_stats_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, bin_px, flags, d_rows)) return fail(why);
   const bool half = flow_fmt == OFDG_FMT_F16;
   if ((uintptr_t)d_flow & (half ? 7 : 15)) return fail(half ? "d_flow must be 8-byte aligned (binary16)" : "d_flow must be 16-byte aligned (float32)");
@@ -1480,6 +1479,17 @@ int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }
+int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, float bin_px,
+                    int flags, ofdg_flow_stats_row* d_rows, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  return flow_stats_on(c, "ofdg_flow_stats", c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
+}
+int ofdg_flow_stats_sized(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int width, int height,
+                          float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  if (const char* why = plane_size_error(width, height)) { c->err = std::string("ofdg_flow_stats_sized: ") + why; return OFDG_EINVAL; }
+  return flow_stats_on(c, "ofdg_flow_stats_sized", width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
+}
 
 // Flow pyramid of caller-given planes: one kernel on `stream`.  Like the statistics it reads nothing of the context's own, so
 // no completion bookkeeping is needed on any stream.
@@ -1488,11 +1498,9 @@ static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && OFDG
               offsetof(struct ofdg_flow_pyramid, levels) == offsetof(DevFlowPyramid, levels) &&
               offsetof(struct ofdg_flow_pyramid, out_fmt) == offsetof(DevFlowPyramid, out_fmt) && OFDG_PYR_SCALE == 1,
               "struct ofdg_flow_pyramid: the layout the kernel takes; flow_pyramid_arg_error spells the flag out");
-int ofdg_flow_pyramid(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int flags,
-                      const struct ofdg_flow_pyramid* pyr, void* stream) {
-  if (!c) return OFDG_EINVAL;
-  auto fail = [&](const std::string& why) { c->err = "ofdg_flow_pyramid: " + why; return OFDG_EINVAL; };
-  const int W = c->prm.width, H = c->prm.height;
+static int flow_pyramid_on(ofdg_ctx* c, const char* who, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
+                           int n_samples, int flags, const struct ofdg_flow_pyramid* pyr, void* stream) {
+  auto fail = [&](const std::string& why) { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; };
   const DevFlowPyramid* const out = reinterpret_cast<const DevFlowPyramid*>(pyr);
   if (const char* why = flow_pyramid_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, flags, out)) return fail(why);
   const bool half = flow_fmt == OFDG_FMT_F16, half_out = pyr->out_fmt == OFDG_FMT_F16;
@@ -1524,6 +1532,76 @@ int ofdg_flow_pyramid(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void*
     default: OFDG_PYR_LAUNCH(true, true, 2); break;
   }
 #undef OFDG_PYR_LAUNCH
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+int ofdg_flow_pyramid(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int flags,
+                      const struct ofdg_flow_pyramid* pyr, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  return flow_pyramid_on(c, "ofdg_flow_pyramid", c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
+}
+int ofdg_flow_pyramid_sized(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int width, int height,
+                            int flags, const struct ofdg_flow_pyramid* pyr, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  if (const char* why = plane_size_error(width, height)) { c->err = std::string("ofdg_flow_pyramid_sized: ") + why; return OFDG_EINVAL; }
+  return flow_pyramid_on(c, "ofdg_flow_pyramid_sized", width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
+}
+
+// Training crop of caller-given planes: one kernel on `stream` for every plane and sample.  Like the two reductions above it
+// reads nothing of the context's own, so no completion bookkeeping is needed on any stream.
+static_assert(sizeof(ofdg_crop_rec) == sizeof(DevCropRec) && sizeof(struct ofdg_crop_job) == sizeof(DevCropJob) && OFDG_CROP_PLANES == kCropPlanes &&
+              offsetof(struct ofdg_crop_job, dst) == offsetof(DevCropJob, dst) && offsetof(struct ofdg_crop_job, recs) == offsetof(DevCropJob, recs) &&
+              offsetof(struct ofdg_crop_job, recs_out) == offsetof(DevCropJob, recs_out) &&
+              offsetof(struct ofdg_crop_job, first_index) == offsetof(DevCropJob, first_index) &&
+              offsetof(struct ofdg_crop_job, seed) == offsetof(DevCropJob, seed) && offsetof(struct ofdg_crop_job, crop_w) == offsetof(DevCropJob, crop_w) &&
+              offsetof(struct ofdg_crop_job, occ_fmt) == offsetof(DevCropJob, occ_fmt) && offsetof(struct ofdg_crop_job, reserved) == 180,
+              "struct ofdg_crop_job: the layout the kernel takes");
+static_assert(OFDG_CROP_HFLIP == 1 && OFDG_CROP_VFLIP == 2 && OFDG_CROP_RANDOM_HFLIP == 4 && OFDG_CROP_RANDOM_VFLIP == 8 && OFDG_CROP_OCC_WINDOW == 16 &&
+              OFDG_CROP_FLOW == 2 && OFDG_CROP_OCC0 == 4 && OFDG_CROP_LABEL0 == 6, "crop_arg_error and crop_kernel spell these codes out");
+int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  auto fail = [&](const std::string& why) { c->err = "ofdg_crop: " + why; return OFDG_EINVAL; };
+  const int W = c->prm.width, H = c->prm.height;
+  const DevCropJob* const j = reinterpret_cast<const DevCropJob*>(job);
+  if (const char* why = crop_arg_error(j, n_samples, W, H)) return fail(why);
+  static const char* const kPlane[kCropPlanes] = {"image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1"};
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const int es = crop_elem_bytes(*j, k), need = es == 4 ? 16 : es == 2 ? 8 : 4;
+    if ((uintptr_t)j->src[k] & (uintptr_t)(need - 1))
+      return fail(std::string("src[") + kPlane[k] + "] must be " + std::to_string(need) + "-byte aligned");
+    if ((uintptr_t)j->dst[k] & 15) return fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return fail("recs_out must be 16-byte aligned");
+  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
+  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+  DevCropGrid grid;
+  uint32_t blocks = 0;
+  for (int k = 0, slot = 0; k < kCropPlanes; ++k) {
+    const uint32_t pieces = (uint32_t)((size_t)j->crop_w * j->crop_h * crop_elem_bytes(*j, k) / 16);
+    const uint32_t per_channel = j->src[k] ? (pieces + kCropThreads * kCropPerLane - 1) / (kCropThreads * kCropPerLane) : 0u;
+    for (int ch = 0; ch < crop_channels(k); ++ch, ++slot) {
+      grid.first_block[slot] = blocks;
+      blocks += per_channel;
+    }
+  }
+  grid.first_block[kCropSlots] = blocks;
+  const dim3 g(blocks, (unsigned)std::min(n_samples, 65535));
+  const int kind = (j->image_fmt == OFDG_FMT_U8 ? 4 : 0) + (j->flow_fmt == OFDG_FMT_F16 ? 2 : 0) + (j->occ_fmt == OFDG_FMT_U8 ? 1 : 0);
+#define OFDG_CROP_LAUNCH(IMAGE_U8, FLOW_HALF, OCC_U8) \
+  hipLaunchKernelGGL((crop_kernel<IMAGE_U8, FLOW_HALF, OCC_U8>), g, dim3(kCropThreads), 0, st, *j, grid, n_samples, W, H)
+  switch (kind) {
+    case 0: OFDG_CROP_LAUNCH(false, false, false); break;
+    case 1: OFDG_CROP_LAUNCH(false, false, true); break;
+    case 2: OFDG_CROP_LAUNCH(false, true, false); break;
+    case 3: OFDG_CROP_LAUNCH(false, true, true); break;
+    case 4: OFDG_CROP_LAUNCH(true, false, false); break;
+    case 5: OFDG_CROP_LAUNCH(true, false, true); break;
+    case 6: OFDG_CROP_LAUNCH(true, true, false); break;
+    default: OFDG_CROP_LAUNCH(true, true, true); break;
+  }
+#undef OFDG_CROP_LAUNCH
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }

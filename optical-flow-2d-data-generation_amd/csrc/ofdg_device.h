@@ -1,6 +1,7 @@
 // Device-side records of the render pipeline (host realize -> geom -> raster ->
 // compose).  Plain PODs shared by host code and HIP kernels.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace ofdg {
@@ -167,6 +168,125 @@ inline const char* flow_pyramid_arg_error(const void* flow, int flow_fmt, const 
     if ((uintptr_t)pyr->flow[k] & 15) return "pyr->flow: every level must be 16-byte aligned";
     if ((uintptr_t)pyr->weight[k] & 3) return "pyr->weight: every level must be 4-byte aligned";
   }
+  return nullptr;
+}
+
+// The plane-size rule of the sized reductions (ofdg_flow_stats_sized, ofdg_flow_pyramid_sized): the context's own.
+inline const char* plane_size_error(int width, int height) {
+  if (width < 8 || height < 2 || (width % 8) != 0 || (height % 2) != 0) return "width must be a multiple of 8 and height even";
+  return nullptr;
+}
+
+// ---- Training crop (ofdg_crop, include/ofdg.h) -----------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the window test of the occlusion rule and the argument rules.  OFDG_HD_FN as in realize.h (the same tokens).
+#if defined(__HIPCC__) || defined(__HIP__)
+#define OFDG_HD_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define OFDG_HD_FN inline
+#endif
+constexpr int kCropPlanes = 8;  // OFDG_CROP_PLANES: image0, image1, flow, flow1, occ0, occ1, label0, label1
+struct DevCropRec {
+  int32_t x0, y0, flags, reserved;
+};
+struct DevCropJob {  // struct ofdg_crop_job, field for field
+  const void* src[kCropPlanes];
+  void* dst[kCropPlanes];
+  const DevCropRec* recs;
+  DevCropRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t crop_w, crop_h, flags, image_fmt, flow_fmt, occ_fmt, reserved;
+};
+static_assert(sizeof(DevCropRec) == 16 && sizeof(DevCropJob) == 184, "ofdg_crop_rec is 16 bytes, struct ofdg_crop_job 184");
+OFDG_HD_FN int crop_channels(int plane) { return plane < 2 ? 3 : plane < 4 ? 2 : 1; }
+// bytes of an element of plane k (format codes of include/ofdg.h: float32 0, uint8 1, binary16 2; labels are uint8)
+OFDG_HD_FN int crop_elem_bytes(const DevCropJob& j, int plane) {
+  const int fmt = plane < 2 ? j.image_fmt : plane < 4 ? j.flow_fmt : plane < 6 ? j.occ_fmt : 1;
+  return fmt == 0 ? 4 : fmt == 1 ? 1 : 2;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11), the function of csrc/sampler_counter.hip restated for host and device.  The sampler's
+// own device copy stays as it is; this one is held to the three published known answers through ofdg_crop_philox
+// (tests/test_crop.py), and host and kernel to each other through the drawn records (tests/test_gpu_crop.py).
+struct CropWords {
+  uint32_t x, y, z, w;
+};
+OFDG_HD_FN CropWords crop_philox(CropWords ctr, uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * ctr.x, p1 = 0xCD9E8D57ull * ctr.z;
+    ctr = CropWords{(uint32_t)(p1 >> 32) ^ ctr.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ ctr.w ^ k1, (uint32_t)p0};
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return ctr;
+}
+// The record of global sample g: one Philox block under the sampler's key of g (cs_key) and the counter {0, 0, 0x0c70, 0} -
+// the sampler's third counter word is always 0x0fd9, so no stream of the sampler is touched.  x0 = floor(w.x * range / 2^32):
+// no rejection loop, so a value's probability is off by at most range / 2^32 (below 2^-16 for any frame).  Needs
+// crop_w <= width and crop_h <= height.  flags: the job's (RANDOM_HFLIP 4, RANDOM_VFLIP 8).
+OFDG_HD_FN DevCropRec crop_draw_rec(uint32_t seed, unsigned long long g, int width, int height, int crop_w, int crop_h, int flags) {
+  const CropWords w = crop_philox(CropWords{0u, 0u, 0x0c70u, 0u}, seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, (uint32_t)g);
+  DevCropRec r;
+  r.x0 = (int32_t)(uint32_t)(((unsigned long long)w.x * (uint32_t)(width - crop_w + 1)) >> 32);
+  r.y0 = (int32_t)(uint32_t)(((unsigned long long)w.y * (uint32_t)(height - crop_h + 1)) >> 32);
+  r.flags = ((flags & 4) ? (int32_t)(w.z & 1u) : 0) | ((flags & 8) ? (int32_t)((w.z >> 1) & 1u) << 1 : 0);
+  r.reserved = 0;
+  return r;
+}
+// What is used of a record, given or drawn: the window inside the frame, the two flip bits, nothing else.
+OFDG_HD_FN DevCropRec crop_sanitise(DevCropRec r, int width, int height, int crop_w, int crop_h) {
+  r.x0 = r.x0 < 0 ? 0 : r.x0 > width - crop_w ? width - crop_w : r.x0;
+  r.y0 = r.y0 < 0 ? 0 : r.y0 > height - crop_h ? height - crop_h : r.y0;
+  r.flags &= 3;
+  r.reserved = 0;
+  return r;
+}
+// OFDG_CROP_OCC_WINDOW, one axis: does the flow target of source coordinate `at` (displacement d) lie in [lo, lo + len - 1]?
+// Three float32 roundings, no contraction; a NaN fails both comparisons.
+OFDG_HD_FN bool crop_target_inside(int at, float d, int lo, int len) {
+  const float s = (float)at + d;
+  const float h = s + 0.5f;
+  const float t = floorf(h);
+  return t >= (float)lo && t <= (float)(lo + len - 1);
+}
+// The argument rules ofdg_crop and ofdg_host_crop share (flag bits: RANDOM_HFLIP 4, RANDOM_VFLIP 8, OCC_WINDOW 16): the first
+// rule broken, or nullptr.  Alignment is asked by the device entry only.
+inline const char* crop_arg_error(const DevCropJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (j->crop_w < 8 || j->crop_w > width || (j->crop_w % 8) != 0) return "crop_w must be a multiple of 8 in [8, width]";
+  if (j->crop_h < 2 || j->crop_h > height || (j->crop_h % 2) != 0) return "crop_h must be even and in [2, height]";
+  if ((unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "width * height must be below 2^31";
+  if (j->flags & ~(4 | 8 | 16)) return "flags holds unknown bits";
+  if (j->reserved != 0) return "reserved must be 0";
+  if (j->image_fmt != 0 && j->image_fmt != 1) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flow_fmt != 0 && j->flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->occ_fmt != 0 && j->occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  int planes = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (j->src[k] && !j->dst[k]) return "dst: a plane has a source and no destination";
+    if (!j->src[k] && j->dst[k]) return "src: a plane has a destination and no source";
+    planes += j->src[k] ? 1 : 0;
+  }
+  if (!planes) return "src: no plane is set";
+  if ((j->flags & 16) && j->src[4] && !j->src[2]) return "flags: OFDG_CROP_OCC_WINDOW with occ0 needs flow";
+  if ((j->flags & 16) && j->src[5] && !j->src[3]) return "flags: OFDG_CROP_OCC_WINDOW with occ1 needs flow1";
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[2 * kCropPlanes + 2];
+  int nr = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const unsigned long long per = (unsigned long long)n * crop_channels(k) * crop_elem_bytes(*j, k);
+    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * width * height), false};
+    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * j->crop_w * j->crop_h), true};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * 16, false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * 16, true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
   return nullptr;
 }
 
