@@ -587,6 +587,15 @@ void* ofdg_stream(ofdg_ctx* ctx);
 /* How many internal streams take turns: a caller that cycles k * ofdg_num_chains output buffer sets and passes
  * ofdg_stream() finds every set always written by the same stream (no event needed between its writers). */
 int ofdg_num_chains(const ofdg_ctx* ctx);
+/* Counter sampler: how many batches of a chain ONE sampler -> geom -> raster launch serves.  2 (the default): a call that
+ * finds no front end ready on its chain runs those three latency-bound kernels for its own batch and for the batch that
+ * chain is asked for next (first_index + ofdg_num_chains x the stride of the caller's last two calls, else batch x
+ * world_size); that call then launches only its background preparation and compose.  A call for anything else - another
+ * first_index or n_samples, after ofdg_set_step or a change of the pool - forgets the second batch and prepares its own:
+ * nothing is rendered from a stale front end, and the bytes are those of n = 1, where every call launches its own front
+ * end.  It applies to the overlapped pipeline without look-ahead (serial = 0, lookahead = 0) and to batches of up to 256
+ * samples; a chain's workspaces hold two batches.  ofdg_ctx_info() ends in " front=N".  OFDG_EINVAL unless n is 1 or 2. */
+int ofdg_set_front_batches(ofdg_ctx* ctx, int n);
 
 /* Wait for `stream` and for everything the context has in flight, and report
  * device-side error flags raised by kernels. */

@@ -138,16 +138,25 @@ struct ofdg_ctx {
       hipStream_t stream = nullptr;  // where the preparation was enqueued
       long long ticket = -1;       // the batch's number (its error word)
       bool ahead = false;          // prepared by an EARLIER call (look-ahead): the end of its preparation says nothing about when compose could start
+      int base = 0;                // its first sample in the slot (a slot filled for two batches: the second one starts at n)
     } prep;
+    // The paired front end (ofdg_set_front_batches): the sampler -> geom -> raster launches of a counter-sampler call fill the
+    // private slot for TWO batches, the call's own and the one this chain is asked for next.  `half` is that second batch while
+    // it waits for its call: sampled, outlined and rasterised in samples [n, 2n) of the slot, its background preparation and
+    // its compose still to be enqueued (launch_second_half).  Everything that forgets `prep` forgets `half` (discard_prepared).
+    Prepared half;
   };
   static constexpr int kMaxChains = 8;
   Chain chains[kMaxChains];
   int lookahead = 0;      // counter sampler: batches prepared ahead of the call that composes them (0: none)
+  int front_batches = 2;  // counter sampler: batches of a chain one sampler -> geom -> raster launch serves (ofdg_set_front_batches)
+  std::string info_head;  // ofdg_ctx_info without its " front=N"
   long long last_first = -1;  // first index of the previous ofdg_forward_counter call (the stride of the caller's sequence)
   int n_chains = 3;       // one hardware queue each: HIP maps streams onto GPU_MAX_HW_QUEUES (4 by default) queues
   unsigned next_chain = 0;
   int last_chain = 0;     // the chain and the slot the last launch used (ofdg_render_resident, debug read-back)
   Slot* last_slot = nullptr;
+  int last_base = 0, last_n = 0;       // ... and the samples of that slot the last launch composed (a slot may hold two batches)
   Chain* last_ch = nullptr;            // the chain that composed the batch in last_slot ...
   hipStream_t last_stream = nullptr;   // ... and the internal stream that call worked on (ofdg_object_table: OFDG_STREAM_OWN)
   hipStream_t last_user_st = nullptr;  // serial mode: the caller's stream of the last launch
@@ -202,6 +211,7 @@ struct ofdg_ctx {
   long long ev_count = 0, ev_alloc = 0, launch_count = 0;  // event sets: composed / handed out (a prepared batch holds one)
   std::vector<char> ev_composed;  // per set: its compose was enqueued (a prepared batch that is discarded leaves its set incomplete)
   std::vector<char> ev_bgprep;    // per set: the batch's background preparation ran behind raster and is timed (ev[3] .. ev[2] or ev[4])
+  std::vector<char> ev_front;     // per set: geom and raster were launched for it (a batch served from a second half has neither)
   std::vector<ofdg_task> fw_tasks;
   std::vector<ofdg_blueprint> fw_bps;
 };
@@ -315,12 +325,13 @@ int ofdg_create(const ofdg_params* params, ofdg_ctx** out) {
   // with GPU_MAX_HW_QUEUES >= 8 gets four chains (+5-8 % throughput, profiles/r02_chains_vs_hw_queues.txt); four chains
   // on four queues share a queue with the caller's streams and are slower than three.
   c->n_chains = params->chains > 0 ? std::min(params->chains, (int)ofdg_ctx::kMaxChains) : (g_hw_queues_env >= 8 ? 4 : 3);
-  c->info = "chains=" + std::to_string(c->n_chains) +
+  c->info_head = "chains=" + std::to_string(c->n_chains) +
             (params->chains > 0 ? " (ofdg_params.chains)"
              : g_hw_queues_env >= 8 ? " (GPU_MAX_HW_QUEUES=" + std::to_string(g_hw_queues_env) + ": one hardware queue per chain)"
              : g_hw_queues_env > 0 ? " (GPU_MAX_HW_QUEUES=" + std::to_string(g_hw_queues_env) + " < 8: start the process with GPU_MAX_HW_QUEUES=8 for four chains, +5-8 %)"
                                    : " (GPU_MAX_HW_QUEUES was not set when the library was loaded: HIP's default of 4 hardware queues; start the process with GPU_MAX_HW_QUEUES=8 for four chains, +5-8 %)") +
             " lookahead=" + std::to_string(c->lookahead) + (c->overlap ? "" : " serial");
+  c->info = c->info_head + " front=" + std::to_string(c->front_batches);
   for (int i = 0; i < c->n_chains; ++i) {
     ofdg_ctx::Chain& ch = c->chains[i];
     if ((e = ch.stream.create(hipStreamNonBlocking)) != hipSuccess ||
@@ -794,15 +805,18 @@ static int size_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n_samples, size_t n_sh
 
 // ---- render -------------------------------------------------------------------------------
 // device counter sampler + device realize fill the slot's records (no host data)
-static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop = nullptr);
-static int launch_counter_sampler(ofdg_ctx* c, ofdg_ctx::Slot& sl, long long first_index, hipStream_t s, uint32_t* err) {
+static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop = nullptr,
+                               int base = 0, hipEvent_t start = nullptr);
+//   first_index2 >= 0: the slot is sized for two batches; samples [split, res_samples) are first_index2.. and flag in err2
+static int launch_counter_sampler(ofdg_ctx* c, ofdg_ctx::Slot& sl, long long first_index, hipStream_t s, uint32_t* err, int split,
+                                  long long first_index2, uint32_t* err2) {
   const int stride = sl.res_shapes / sl.res_samples;
   const int prep = c->prm.background_prep ? 1 : 0;
   CsRealizeDims D{c->prm.width, c->prm.height, c->pool_n, c->pool_w, c->pool_h, sl.res_samples, stride, prep,
                   c->prm.mode == 9 ? c->crop_server.n_crops : 0, c->fg_src.stride, c->fg_src.origin, c->bg_src.stride, c->bg_src.origin,
                   (unsigned long long)(uintptr_t)c->pool.p, c->d_tex_table.p, c->prm.mode == 9 ? c->d_cs_croptab.p : nullptr};
   hipLaunchKernelGGL(cs_sample_realize_kernel, dim3(sl.res_samples * kCsGroups), dim3(64), 0, s, c->cs_mode, D, first_index,
-                     sl.d_shapes.p, sl.d_objects.p, sl.d_samples.p, err, sl.d_bgprep.p);
+                     sl.d_shapes.p, sl.d_objects.p, sl.d_samples.p, err, sl.d_bgprep.p, split, first_index2, err2);
   HIP_OK(c, hipGetLastError());
   sl.bgprep_pending = prep != 0;  // (rendered behind raster: launch_prepare)
   return OFDG_OK;
@@ -822,17 +836,28 @@ static hipStream_t chain_stream(const ofdg_ctx* c, const ofdg_ctx::Chain& ch, hi
 
 // A prepared batch that will never be composed (the caller's sequence jumped, the pool changed, the chain's private slot is
 // needed for something else): forget it.  compose is what resets the slot's raster work list, so do that here.
+// what the kernels of a batch that is never handed over flagged is nobody's (its word must not speak for ticket + kErrWords,
+// nor make ofdg_synchronize report a batch that was never composed)
+static int clean_discarded_word(ofdg_ctx* c, const ofdg_ctx::Chain::Prepared& p) {
+  if (p.ticket >= 0 && p.ticket + ofdg_ctx::kErrWords > c->ticket) {
+    HIP_OK(c, hipMemsetAsync(err_word(c, p.ticket), 0, sizeof(uint32_t), p.stream));
+    c->word_clean[(size_t)(p.ticket % ofdg_ctx::kErrWords)] = true;
+  }
+  return OFDG_OK;
+}
+// The second half of a paired front end that its call will not come for.  Its raster items are consumed and the work list was
+// reset by the first half's compose (or is, by discard_prepared, if that compose never ran either): only its word is left.
+static int discard_half(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
+  if (!ch.half.valid) return OFDG_OK;
+  ch.half.valid = false;
+  return clean_discarded_word(c, ch.half);
+}
 static int discard_prepared(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
+  OFDG_TRY(discard_half(c, ch));
   if (!ch.prep.valid) return OFDG_OK;
   ch.prep.valid = false;
   if (ch.prep.slot && ch.prep.slot->d_item_count.p) HIP_OK(c, hipMemsetAsync(ch.prep.slot->d_item_count.p, 0, sizeof(int), ch.prep.stream));
-  // ... and what its kernels flagged is nobody's: the batch is never handed over (its word must not speak for ticket + kErrWords,
-  // nor make ofdg_synchronize report a batch that was never composed)
-  if (ch.prep.ticket >= 0 && ch.prep.ticket + ofdg_ctx::kErrWords > c->ticket) {
-    HIP_OK(c, hipMemsetAsync(err_word(c, ch.prep.ticket), 0, sizeof(uint32_t), ch.prep.stream));
-    c->word_clean[(size_t)(ch.prep.ticket % ofdg_ctx::kErrWords)] = true;
-  }
-  return OFDG_OK;
+  return clean_discarded_word(c, ch.prep);
 }
 static int discard_all_prepared(ofdg_ctx* c) {
   c->bg_cap_n = -1;  // (called by everything that changes the pool)
@@ -872,20 +897,31 @@ static void track_completion(ofdg_ctx::Slot& sl, ofdg_ctx::Chain& ch, hipStream_
 
 // The preparation kernels of the batch resident in `sl`, in order on chain `ch`: [counter sampler ->] geom -> raster
 //   `st` is the stream of the call the batch is prepared for (only the serial mode prepares on it).
+//   view_n > 0: the batch is samples [view_base, view_base + view_n) of the slot (ofdg_render_resident of a slot that was filled
+//   for two batches).  cs_first2 >= 0 (the paired front end): the slot is sized for 2 x n_first samples; the three launches
+//   serve both batches, the preparation behind them the first one only, and the second one is left in ch.half.
 static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, hipStream_t st, long long cs_first_index = -1,
-                          bool hand_over = true) {
+                          bool hand_over = true, int view_base = 0, int view_n = 0, long long cs_first2 = -1, int n_first = 0) {
   const int W = c->prm.width, H = c->prm.height;
   const int n_sf = sl.res_shapes * 2;
   const RenderDims dm = render_dims(c, sl);
+  const bool paired = cs_first_index >= 0 && cs_first2 >= 0;
   OFDG_TRY(discard_prepared(c, ch));
+  // (this launch rewrites the slot's outlines and flips its block masks: a second half another chain keeps in it is gone)
+  if (&sl != &ch.slot)
+    for (int k = 0; k < c->n_chains; ++k)
+      if (c->chains[k].half.valid && c->chains[k].half.slot == &sl) OFDG_TRY(discard_half(c, c->chains[k]));
   const long long ticket = c->ticket++;  // this batch's number: its kernels raise their flags in its own word
   uint32_t* const err = err_word(c, ticket);
+  const long long ticket2 = paired ? c->ticket++ : -1;  // ... and the second batch's: every kernel of the front end knows its sample
+  uint32_t* const err2 = paired ? err_word(c, ticket2) : err;
   Event* ev = nullptr;
   if (c->profiling && c->ev_sets > 0 && (c->launch_count % c->ev_stride) == 0) {
     const size_t set = (size_t)(c->ev_alloc++ % c->ev_sets);
     ev = &c->ev[set * 6];
     c->ev_composed[set] = 0;
     c->ev_bgprep[set] = 0;
+    c->ev_front[set] = 1;
   }
   c->launch_count++;
   if (!c->overlap) {
@@ -905,8 +941,9 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   // mode 9: the batch's own crop table (host path) or the static table of all crops (counter sampler)
   const DevCropRef* croptab = cs_first_index >= 0 ? c->d_cs_croptab.p : sl.d_croptab.p;
   HIP_OK(c, take_err_word(c, ticket, S));  // (nothing is enqueued unless this caller asks by ticket AND the word's last owner was never asked about)
+  if (paired) HIP_OK(c, take_err_word(c, ticket2, S));
   if (cs_first_index >= 0) {  // device counter sampler + device realize
-    OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, err));
+    OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, err, paired ? n_first : sl.res_samples, cs_first2, err2));
   }
   // (the background preparation of the batch goes LAST, right in front of compose: below)
   // geom: outlines, bounding boxes, per-object boxes (parity `bp`), raster work list
@@ -924,7 +961,8 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   // geom: outlines, boxes, raster work list -> raster: coverage slots + block masks (persistent waves over the list)
   hipExtLaunchKernelGGL(geom_kernel, dim3(std::max(1, (n_sf + kGeomWaves - 1) / kGeomWaves)), dim3(64 * kGeomWaves), 0, S,
                         prof_prep ? ev[0].e : nullptr, prof_prep ? ev[1].e : nullptr, 0, sl.d_shapes.p, sl.res_shapes, c->d_cs_tab.p, W, H,
-                        sl.d_frames.p, sl.d_verts.p, box_cur, err, sl.d_item_count.p, sl.d_items.p, croptab);
+                        sl.d_frames.p, sl.d_verts.p, box_cur, err, sl.d_item_count.p, sl.d_items.p, croptab,
+                        paired ? n_first * (sl.res_shapes / sl.res_samples) * 2 : 0x7fffffff, err2);
   HIP_OK(c, hipGetLastError());
   // The batch's last preparation kernel - raster, or the background preparation behind it - carries two things on its own
   // packet: the hand-over event of a compose on a caller's stream, or (profiling 1) the start of the compose launch's time.
@@ -934,19 +972,61 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   const bool prep_last = sl.bgprep_pending;
   hipEvent_t last_stop = ev ? (c->profiling == 2 ? nullptr : ev[4].e) : (hand_over ? ch.ev_prep.e : nullptr);
   // (a profiled batch with a preparation behind raster also takes raster's completion: the preparation is timed from there)
-  hipExtLaunchKernelGGL(raster_kernel, dim3(kRasterGrid * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, S, nullptr,
+  hipExtLaunchKernelGGL(raster_kernel, dim3((paired ? kRasterGridPaired : kRasterGrid) * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, S, nullptr,
                         (ev && (c->profiling == 2 || prep_last)) ? ev[3].e : (prep_last ? nullptr : last_stop), 0,
                         sl.d_frames.p, sl.d_items.p, sl.d_item_count.p, sl.d_verts.p, W, H, cov, box_next, n_mask_words, box_cur);
   HIP_OK(c, hipGetLastError());
   if (prep_last) {
-    OFDG_TRY(prepare_backgrounds(c, sl, sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2].e : last_stop));
+    // (of a pair: the first batch's only - the second one's goes in front of ITS compose, launch_second_half)
+    OFDG_TRY(prepare_backgrounds(c, sl, paired ? n_first : sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2].e : last_stop));
     sl.bgprep_pending = false;
     if (ev) c->ev_bgprep[(size_t)(ev - c->ev.data()) / 6] = 1;
   }
   if (ev && hand_over) HIP_OK(c, hipEventRecord(ch.ev_prep, S));
-  ch.prep.valid = true; ch.prep.slot = &sl; ch.prep.first_index = cs_first_index; ch.prep.n = sl.res_samples;
+  ch.prep.valid = true; ch.prep.slot = &sl; ch.prep.first_index = cs_first_index;
+  ch.prep.n = paired ? n_first : (view_n > 0 ? view_n : sl.res_samples);
+  ch.prep.base = view_n > 0 ? view_base : 0;
   ch.prep.box_cur = box_cur; ch.prep.croptab = croptab; ch.prep.ev = ev; ch.prep.stream = S; ch.prep.ticket = ticket;
   ch.prep.ahead = false;
+  if (paired) {
+    ch.half = ch.prep;
+    ch.half.first_index = cs_first2; ch.half.base = n_first; ch.half.ev = nullptr; ch.half.ticket = ticket2;
+  }
+  return OFDG_OK;
+}
+
+// The call the second half of a paired front end was made for has come: samples [n, 2n) of the chain's private slot are
+// sampled, outlined and rasterised.  What is left is the batch's own background preparation, on the chain's stream, and the
+// hand-over of a compose on a caller's stream - recorded behind THAT preparation.  No geom / raster launch: a profiled call's
+// event set says so (ev_front), and profiling 1 has a predecessor of compose on the chain only where there is a preparation.
+static int launch_second_half(ofdg_ctx* c, ofdg_ctx::Chain& ch, bool hand_over) {
+  ofdg_ctx::Chain::Prepared h = ch.half;
+  ofdg_ctx::Slot& sl = *h.slot;
+  const hipStream_t S = h.stream;
+  const bool prep = c->prm.background_prep != 0;
+  Event* ev = nullptr;
+  if (c->profiling && c->ev_sets > 0 && (c->launch_count % c->ev_stride) == 0 && (c->profiling == 2 || prep)) {
+    const size_t set = (size_t)(c->ev_alloc++ % c->ev_sets);
+    ev = &c->ev[set * 6];
+    c->ev_composed[set] = 0;
+    c->ev_bgprep[set] = 0;
+    c->ev_front[set] = 0;
+  }
+  c->launch_count++;
+  // the first half's compose may have run on a caller's stream: the chain's stream is ordered behind it from here on, as in
+  // launch_prepare (the event is about to be taken by this batch's compose)
+  if (ch.done_pending && ch.done_stream != S) OFDG_TRY(wait_unless_fired(c, S, ch.ev_done, &ch.done_pending, /*settles=*/true));
+  if (sl.compose_pending && sl.compose_stream != S) OFDG_TRY(wait_unless_fired(c, S, sl.compose_event, &sl.compose_pending));
+  ch.half.valid = false;  // (taken: a failure below leaves it to discard_prepared as `prep`)
+  h.ev = ev;
+  ch.prep = h;
+  if (prep) {
+    const bool prof2 = ev && c->profiling == 2;
+    const hipEvent_t stop = ev ? (prof2 ? ev[2].e : ev[4].e) : (hand_over ? ch.ev_prep.e : nullptr);
+    OFDG_TRY(prepare_backgrounds(c, sl, h.n, /*records_resident=*/true, S, err_word(c, h.ticket), stop, h.base, prof2 ? ev[3].e : nullptr));
+    if (prof2) c->ev_bgprep[(size_t)(ev - c->ev.data()) / 6] = 1;  // (its own start marker .. its end)
+  }
+  if (hand_over && (ev || !prep)) HIP_OK(c, hipEventRecord(ch.ev_prep, S));
   return OFDG_OK;
 }
 
@@ -1070,10 +1150,16 @@ static int compose_stream(ofdg_ctx* c, ofdg_ctx::Chain& ch, hipStream_t st, hipS
 //   completion of its predecessor on the chain (the last preparation kernel's own packet, ev[4], launch_prepare) to its own
 //   completion: its dispatch gap (1 - 2 us) is counted with it, and nothing is added to the stream.  profiling 2: the
 //   kernel's own start (a marker, ev[4]) and end.
+//   The batch is samples [ch.prep.base, + ch.prep.n) of the slot: the sample records and the block-mask rows are passed from
+//   there on (a kernel's sample 0 is the batch's first); shapes, objects, coverage slots and the prepared textures are
+//   addressed by what the records hold, which is slot-global.
 static int launch_compose_kernels(ofdg_ctx* c, const ofdg_ctx::Chain& ch, const ofdg_ctx::Slot& sl, const CallOut& o, const ComposeExtras& x,
                                   const uint32_t* fgpool, const uint32_t* bgpool, hipStream_t cs, hipEvent_t done) {
   const int W = c->prm.width, H = c->prm.height;
-  const RenderDims dm = render_dims(c, sl);
+  RenderDims dm = render_dims(c, sl);
+  dm.n_samples = ch.prep.n;
+  const DevSample* const samples = sl.d_samples.p + ch.prep.base;
+  const unsigned long long* const box = ch.prep.box_cur + (size_t)ch.prep.base * dm.tiles_x * ((H + kBandRows - 1) / kBandRows) * 2;
   const int grid = dm.tiles_x * dm.tiles_y * dm.n_samples * 4;  // one 64 x 4 strip per single-wave workgroup
   Event* const ev = ch.prep.ev;
   // the variant, decided here once (the optional outputs exist in the rigid modes only: check_extras)
@@ -1085,11 +1171,11 @@ static int launch_compose_kernels(ofdg_ctx* c, const ofdg_ctx::Chain& ch, const 
   // every family has a _pow2 and a general kernel of one function type: this is the one place a compose kernel is launched
   auto compose = [&](auto* k_pow2, auto* k, auto... args) { launch_kernel(lc, pow2 ? k_pow2 : k, args...); };
   auto rigid = [&](auto* k_pow2, auto* k, auto... tail) {
-    compose(k_pow2, k, sl.d_samples.p, ch.prep.box_cur, sl.d_objects.p, ch.cov.p, grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch,
+    compose(k_pow2, k, samples, box, sl.d_objects.p, ch.cov.p, grid, dm.tiles_x, dm.tiles_y, W, H, dm.use_aa, dm.bg_pitch,
             dm.fg_pitch, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p, sl.d_item_count.p, tail...);
   };
   auto deform = [&](auto* k_pow2, auto* k, auto... tail) {
-    compose(k_pow2, k, dm, sl.d_samples.p, sl.d_objects.p, ch.prep.box_cur, ch.cov.p, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p,
+    compose(k_pow2, k, dm, samples, sl.d_objects.p, box, ch.cov.p, fgpool, bgpool, o.img0, o.img1, o.flow, sl.d_frames.p,
             ch.prep.croptab, sl.d_item_count.p, tail...);
   };
   switch (kind) {
@@ -1139,11 +1225,12 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, const CallOut& o, hi
   if (!ch.prep.valid) { c->err = "internal: compose without a prepared batch"; return OFDG_EINVAL; }
   ofdg_ctx::Slot& sl = *ch.prep.slot;
   ComposeExtras x;
-  OFDG_TRY(plan_extras(c, ch, sl.res_samples, o, &x));
+  OFDG_TRY(plan_extras(c, ch, ch.prep.n, o, &x));
   const uint32_t* bgpool = c->prm.background_prep ? sl.d_bgtex.p : (c->pool_bg.p ? c->pool_bg.p : c->pool.p);  // (after the slot's buffers are final)
   const uint32_t* fgpool = c->pool_fg.p ? c->pool_fg.p : c->pool.p;
   if (c->prm.background_prep && !bgpool) { c->err = "background_prep: the slot has no prepared backgrounds"; return OFDG_EINVAL; }
   c->last_slot = &sl; c->last_ch = &ch;
+  c->last_base = ch.prep.base; c->last_n = ch.prep.n;
   c->last_stream = ch.prep.stream; c->last_ticket = ch.prep.ticket;
   ch.prep.valid = false;  // (consumed from here on; an argument error above leaves it to discard_prepared, which resets the work list)
   const bool foreign = ch.prep.stream != st;  // the caller's stream is not the chain's
@@ -1158,9 +1245,11 @@ static int launch_compose(ofdg_ctx* c, ofdg_ctx::Chain& ch, const CallOut& o, hi
 }
 
 // preparation + compose of the batch resident in `sl`, in order on chain `ch`
-static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, const CallOut& o, hipStream_t st, long long cs_first_index = -1) {
+//   view_n > 0: of its samples [view_base, view_base + view_n) only
+static int launch_resident(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, const CallOut& o, hipStream_t st, long long cs_first_index = -1,
+                           int view_base = 0, int view_n = 0) {
   // (the preparation's completion event is only needed when compose runs on another stream than the chain's)
-  OFDG_TRY(launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st));
+  OFDG_TRY(launch_prepare(c, ch, sl, st, cs_first_index, chain_stream(c, ch, st) != st, view_base, view_n));
   return launch_compose(c, ch, o, st);
 }
 
@@ -1191,11 +1280,17 @@ static int ensure_bgprep_tables(ofdg_ctx* c) {
 
 // background_prep: render the 2W x 2H background textures of n samples into the slot's buffer on stream `s`; their
 // records are in sl.d_bgprep already (written by the device sampler, or uploaded with the batch's other records)
-//   stop: an event for the completion of the LAST kernel launched here (on that kernel's own packet)
-static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop) {
+//   stop: an event for the completion of the LAST kernel launched here (on that kernel's own packet); start: a marker in front
+//   of the first one (profiling 2 of a batch that has no raster launch to be timed from)
+//   base: the slot's first sample of the n (the second batch of a slot filled for two: its records and textures start there)
+static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop, int base,
+                               hipEvent_t start) {
   const int W = c->prm.width, H = c->prm.height;
-  if (!records_resident || !sl.d_bgprep.p || sl.d_bgprep.cap < (size_t)n) { c->err = "internal: background preparation without its records"; return OFDG_EINVAL; }
-  HIP_OK(c, sl.d_bgtex.reserve((size_t)n * 4 * W * H));
+  if (!records_resident || !sl.d_bgprep.p || sl.d_bgprep.cap < (size_t)(base + n)) { c->err = "internal: background preparation without its records"; return OFDG_EINVAL; }
+  if (base == 0) HIP_OK(c, sl.d_bgtex.reserve((size_t)n * 4 * W * H));
+  else if (sl.d_bgtex.cap < (size_t)(base + n) * 4 * W * H) { c->err = "internal: background preparation of a second batch the slot was not sized for"; return OFDG_EINVAL; }
+  const DevBgPrep* const rec = sl.d_bgprep.p + base;
+  uint32_t* const tex = sl.d_bgtex.p + (size_t)base * 4 * W * H;
   int cap_cw, cap_ch;
   bool fusable;
   bgprep_caps(c, &cap_cw, &cap_ch, &fusable);
@@ -1205,22 +1300,22 @@ static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool reco
     OFDG_TRY(ensure_bgprep_tables(c));
   }
   if (!staged) {
-    hipExtLaunchKernelGGL(bgprep_kernel, dim3((W * H + 255) / 256, n), dim3(256), 0, s, nullptr, stop, 0, sl.d_bgprep.p, W, H, sl.d_bgtex.p);
+    hipExtLaunchKernelGGL(bgprep_kernel, dim3((W * H + 255) / 256, n), dim3(256), 0, s, start, stop, 0, rec, W, H, tex);
     HIP_OK(c, hipGetLastError());
     return OFDG_OK;
   }
   const DevResizeTabs T{c->d_bg_at_x.p, c->d_bg_alpha_x.p, c->d_bg_at_y.p, c->d_bg_alpha_y.p};
   if (fusable && n <= kPrepMaxSamples) {
-    hipExtLaunchKernelGGL(bgprep_stream_kernel, dim3(kPrepGrid), dim3(64), (size_t)(n + 1) * sizeof(int), s, nullptr, stop, 0, sl.d_bgprep.p, T, W, H, n, cap_cw, cap_ch, sl.d_bgtex.p, err,
+    hipExtLaunchKernelGGL(bgprep_stream_kernel, dim3(kPrepGrid), dim3(64), (size_t)(n + 1) * sizeof(int), s, start, stop, 0, rec, T, W, H, n, cap_cw, cap_ch, tex, err,
                           c->d_prep_paths.p);
     HIP_OK(c, hipGetLastError());
     return OFDG_OK;
   }
   HIP_OK(c, sl.d_bgC.reserve((size_t)n * cap_cw * cap_ch));
-  hipLaunchKernelGGL(bgprep_rotcrop_kernel, dim3(kBgPrepBlocks, n), dim3(256), 0, s, sl.d_bgprep.p, T, W, H, cap_cw, cap_ch, sl.d_bgC.p,
-                     err);
-  hipExtLaunchKernelGGL(bgprep_resize_kernel, dim3(kBgPrepBlocks, n), dim3(256), 0, s, nullptr, stop, 0, sl.d_bgprep.p, T, W, H, cap_cw, cap_ch, sl.d_bgC.p,
-                        sl.d_bgtex.p);
+  hipExtLaunchKernelGGL(bgprep_rotcrop_kernel, dim3(kBgPrepBlocks, n), dim3(256), 0, s, start, nullptr, 0, rec, T, W, H, cap_cw, cap_ch, sl.d_bgC.p,
+                        err);
+  hipExtLaunchKernelGGL(bgprep_resize_kernel, dim3(kBgPrepBlocks, n), dim3(256), 0, s, nullptr, stop, 0, rec, T, W, H, cap_cw, cap_ch, sl.d_bgC.p,
+                        tex);
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }
@@ -1385,7 +1480,10 @@ int ofdg_render_resident(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flo
   // a chain's private slot is not tracked by events while only that chain uses it: let its owner drain first
   for (int k = 0; k < c->n_chains; ++k)
     if (&c->chains[k].slot == c->last_slot && !c->last_slot->compose_pending) HIP_OK(c, hipStreamSynchronize(c->chains[k].stream));
-  return launch_resident(c, take_chain(c), *c->last_slot, CallOut{"ofdg_render_resident", d_img0, d_img1, d_flow, {}, 0}, (hipStream_t)stream);
+  // (the batch the last call composed: of a slot that was filled for two batches, that call's samples)
+  const int view_base = c->last_base, view_n = c->last_n;
+  return launch_resident(c, take_chain(c), *c->last_slot, CallOut{"ofdg_render_resident", d_img0, d_img1, d_flow, {}, 0}, (hipStream_t)stream, -1,
+                         view_base, view_n);
 }
 
 // The per-object annotation table of the batch the last render / forward call composed (c->last_slot): two small kernels on
@@ -1413,7 +1511,8 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   ofdg_ctx::Chain& ch = *c->last_ch;
   const hipStream_t S = c->last_stream;  // the internal stream that call worked on
   const hipStream_t st = stream == OFDG_STREAM_OWN ? S : (hipStream_t)stream;
-  const int W = c->prm.width, H = c->prm.height, n = sl.res_samples;
+  const int W = c->prm.width, H = c->prm.height, n = c->last_n;
+  const DevSample* const samples = sl.d_samples.p + c->last_base;  // (the batch that call composed: a slot may hold two)
   // The slot's records must outlive the kernels.  On the chain's own stream the order of the stream sees to that (a private
   // slot is rewritten there only); on a caller's stream - or for a caller's slot, which any stream may rewrite - the last
   // kernel carries the chain's completion event, as a compose on a caller's stream does (launch_compose): a later call
@@ -1424,11 +1523,11 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   DevObjectRow* const rows = reinterpret_cast<DevObjectRow*>(d_rows);
   const long long cells = (long long)n * rows_per_sample;
   hipExtLaunchKernelGGL(object_table_header_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, nullptr, reduce ? nullptr : done, 0,
-                        sl.d_samples.p, sl.d_objects.p, sl.d_shapes.p, n, rows_per_sample, W, H, rows, d_counts);
+                        samples, sl.d_objects.p, sl.d_shapes.p, n, rows_per_sample, W, H, rows, d_counts);
   HIP_OK(c, hipGetLastError());
   if (reduce) {
     hipExtLaunchKernelGGL(object_table_reduce_kernel, dim3((unsigned)((H + kTabBand - 1) / kTabBand), 2, (unsigned)n), dim3(64 * kTabWaves), 0,
-                          st, nullptr, done, 0, sl.d_samples.p, d_label0, d_label1, W, H, rows_per_sample, rows);
+                          st, nullptr, done, 0, samples, d_label0, d_label1, W, H, rows_per_sample, rows);
     HIP_OK(c, hipGetLastError());
   }
   if (tracked) track_completion(sl, ch, st, done);
@@ -1608,12 +1707,14 @@ int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void*
 
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
-static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n) {
+//   front = 2: the slot holds two such batches (the paired front end)
+static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, int front = 1) {
   if (c->prm.mode == 9) OFDG_TRY(ensure_counter_croptab(c));
   OFDG_TRY(finalise_pool(c));
   OFDG_TRY(ensure_tex_table(c));
   if (!c->pool.p && !c->pool_mixed) { c->err = "Could not open texture collection (no texture pool)"; return OFDG_ETEXTURES; }
   if (n < 1 || n > 512) { c->err = "counter sampler: batch must be 1..512 samples"; return OFDG_EINVAL; }
+  n *= front;
   // outline slots per sample: the worst case, so that no sample can run out (composites have up to 7 parts)
   const int max_objects = c->prm.num_objects > 0 ? std::min(c->prm.num_objects, kCsMaxObjects) : 24;
   const size_t shapes_cap = (size_t)n * (size_t)(c->prm.mode >= 6 ? max_objects * 7 : max_objects);
@@ -1644,14 +1745,31 @@ static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_sample
     OFDG_TRY(prepare_counter_slot(c, cj.slot, n_samples));
     return launch_prepare(c, cj, cj.slot, s_, first, hand_over);
   };
-  OFDG_TRY(prepare_on(ch, first_index, st, chain_stream(c, ch, st) != st));
+  const long long prev_first = c->last_first;
+  // the stride of the caller's sequence: that of its last two calls, else the sharding rule's
+  const long long stride = (prev_first >= 0 && first_index > prev_first) ? first_index - prev_first
+                                                                           : (long long)n_samples * std::max(1, c->prm.world_size);
+  const bool hand_over = chain_stream(c, ch, st) != st;
+  // The paired front end: sampler, geom and raster are latency-bound single-wave kernels whose launches last about as long
+  // for two batches as for one, so this chain runs them for the batch it will be asked for NEXT as well (n_chains calls on),
+  // and that call launches only its background preparation and compose.  Stream order and what runs beside what stay as
+  // they are.  A call for anything else than the second half forgets it and prepares its own pair.  (2 x n stays within
+  // the 512 samples a slot was ever sized for.)
+  if (c->front_batches == 2 && c->overlap && c->lookahead == 0 && 2 * n_samples <= 512) {
+    if (ch.half.valid && ch.half.slot == &ch.slot && ch.half.first_index == first_index && ch.half.n == n_samples && !ch.prep.valid) {
+      OFDG_TRY(launch_second_half(c, ch, hand_over));
+    } else {
+      OFDG_TRY(discard_prepared(c, ch));
+      OFDG_TRY(prepare_counter_slot(c, ch.slot, n_samples, 2));
+      OFDG_TRY(launch_prepare(c, ch, ch.slot, st, first_index, hand_over, 0, 0, first_index + (long long)c->n_chains * stride, n_samples));
+    }
+  } else {
+    OFDG_TRY(prepare_on(ch, first_index, st, hand_over));
+  }
   OFDG_TRY(launch_compose(c, ch, o, st));
   // (the caller's batch is composed: from here on the call has succeeded, whatever happens to the batches prepared ahead)
-  const long long prev_first = c->last_first;
   c->last_first = first_index;
   if (c->overlap && c->lookahead > 0) {
-    const long long stride = (prev_first >= 0 && first_index > prev_first) ? first_index - prev_first
-                                                                             : (long long)n_samples * std::max(1, c->prm.world_size);
     for (int d = 1; d <= std::min(c->lookahead, c->n_chains - 1); ++d) {
       ofdg_ctx::Chain& cj = c->chains[(k + d) % c->n_chains];
       // a preparation ahead that cannot be enqueued is dropped: the call that needs the batch prepares it itself and
@@ -1811,7 +1929,19 @@ int ofdg_set_step(ofdg_ctx* c, long long step) {
       }
     }
   }
+  // (a second half was sampled for the sequence the old counter was walking)
+  if (step != c->step) for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_half(c, c->chains[k]));
   c->step = step;
+  return OFDG_OK;
+}
+
+// Batches of a chain that one sampler -> geom -> raster launch serves on the counter-sampler path: 2 (the default, see
+// forward_counter_impl) or 1 (every call launches its own front end).  A scheduling choice: the bytes are the same.
+int ofdg_set_front_batches(ofdg_ctx* c, int n) {
+  if (!c || (n != 1 && n != 2)) { if (c) c->err = "ofdg_set_front_batches: n = " + std::to_string(n) + " (valid: 1, 2)"; return OFDG_EINVAL; }
+  for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_half(c, c->chains[k]));
+  c->front_batches = n;
+  c->info = c->info_head + " front=" + std::to_string(n);
   return OFDG_OK;
 }
 
@@ -2139,11 +2269,11 @@ int ofdg_debug_bgprep_tiles(ofdg_ctx* c, int* tiles, int* workgroups) {
   int cap_cw, cap_ch;
   bool fusable;
   bgprep_caps(c, &cap_cw, &cap_ch, &fusable);
-  const int n = sl.res_samples;
+  const int n = c->last_n;  // (the batch the last call composed: a slot may hold two)
   if (c->prm.background_prep != 1 || !fusable || n > kPrepMaxSamples || n < 1 || !sl.d_bgprep.p) return OFDG_OK;
   HIP_OK(c, hipDeviceSynchronize());
   std::vector<DevBgPrep> rec((size_t)n);
-  HIP_OK(c, hipMemcpy(rec.data(), sl.d_bgprep.p, rec.size() * sizeof(DevBgPrep), hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(rec.data(), sl.d_bgprep.p + c->last_base, rec.size() * sizeof(DevBgPrep), hipMemcpyDeviceToHost));
   for (const DevBgPrep& q : rec)
     if (prep_sample_fits(q, cap_cw, cap_ch)) *tiles += prep_tile_cols(q) * prep_tile_rows(q);
   return OFDG_OK;
@@ -2180,6 +2310,7 @@ int ofdg_set_profiling(ofdg_ctx* c, int mode) {
   }
   c->ev_composed.assign((size_t)c->ev_sets, 0);
   c->ev_bgprep.assign((size_t)c->ev_sets, 0);
+  c->ev_front.assign((size_t)c->ev_sets, 0);
   return OFDG_OK;
 }
 
@@ -2203,6 +2334,7 @@ int ofdg_kernel_ms(ofdg_ctx* c, const char* kernel, float* ms) {
   for (int k = 0; k < c->ev_sets; ++k) {
     if (!c->ev_composed[(size_t)k]) continue;  // (never handed out, or its prepared batch was discarded before compose)
     if (i == 3 && !c->ev_bgprep[(size_t)k]) continue;
+    if (i < 2 && !c->ev_front[(size_t)k]) continue;  // (served from a second half: no geom / raster launch, its ev[0 .. 3] are stale)
     ++n;
     const Event* ev = &c->ev[(size_t)k * 6];
     HIP_OK(c, hipEventSynchronize(ev[5]));

@@ -14,6 +14,11 @@ constexpr int kCurveMaxDepth = 16;  // DFS stack depth for curve3 subdivision
 constexpr int kBandRows = 8;        // scanlines one raster workgroup accumulates in LDS
 constexpr int kMaxFgObjects = 64;   // foreground objects per sample (bits of a tile mask)
 constexpr int kRasterGrid = 512;    // x4 persistent single-wave raster workgroups: enough to finish in time, few enough not to crowd compose
+// ... and of a launch that rasterises two batches of a chain (the paired front end; profiles/paired_front_raster_grid.txt)
+#ifndef OFDG_RASTER_GRID_PAIRED
+#define OFDG_RASTER_GRID_PAIRED 768
+#endif
+constexpr int kRasterGridPaired = OFDG_RASTER_GRID_PAIRED;
 
 // error bits raised by kernels (device word, read by ofdg_synchronize)
 constexpr uint32_t kErrVertCapacity = 1u;   // outline has more than kMaxVerts vertices
