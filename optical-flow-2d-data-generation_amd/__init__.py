@@ -120,6 +120,34 @@ class Extras(C.Structure):
 # the compact output formats (ofdg_out_format, include/ofdg.h)
 FMT_F32, FMT_U8, FMT_F16 = 0, 1, 2
 _FMT_NAMES = {"f32": FMT_F32, "u8": FMT_U8, "f16": FMT_F16}
+# dtype name -> format code, by what a plane holds
+_IMAGE_CODES = {"float32": FMT_F32, "uint8": FMT_U8}
+_FLOW_CODES = {"float32": FMT_F32, "float16": FMT_F16}
+_OCC_CODES = {"float32": FMT_F32, "uint8": FMT_U8}
+
+
+def _dtype_name(t):
+    """"float32" of a torch tensor or a numpy array"""
+    return str(t.dtype).replace("torch.", "")
+
+
+def _check_plane(what, t, dtypes, shape, says=None, note=""):
+    """Raises "<what> must be <dtypes> <shape><note>, got <dtype> <shape>" unless t has one of the dtype names and exactly that
+    shape.  says: how to name the dtypes, when not as "a or b"."""
+    if _dtype_name(t) not in dtypes or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be %s %s%s, got %s %s" % (what, says or " or ".join(dtypes), tuple(shape), note, _dtype_name(t), tuple(t.shape)))
+
+
+def _check_flow_occ(flow, occ, height, width, got="%s %s"):
+    """(n, flow code, occ code) of what the reductions read: flow float32 or float16 [n,2,H,W], occ None or float32 / uint8
+    [n,1,H,W].  got: how the message shows the dtype and shape of a flow that is neither."""
+    if flow is None or _dtype_name(flow) not in _FLOW_CODES or len(flow.shape) != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (2, height, width):
+        raise ValueError("flow must be float32 or float16 [n,2,%d,%d], got %s"
+                         % (height, width, None if flow is None else got % (_dtype_name(flow), tuple(flow.shape))))
+    n = int(flow.shape[0])
+    if occ is not None:
+        _check_plane("occ", occ, _OCC_CODES, (n, 1, height, width), says="None or float32 / uint8")
+    return n, _FLOW_CODES[_dtype_name(flow)], FMT_F32 if occ is None else _OCC_CODES[_dtype_name(occ)]
 
 
 class OutFormat(C.Structure):
@@ -131,16 +159,13 @@ def output_format(image0, image1, flow, n, height, width):
     """The format codes (image, flow) of three output tensors for n samples of height x width: uint8 or float32 frames (both
     alike), float16 or float32 flow.  Raises ValueError for anything else, or for a tensor with fewer elements than
     [n,3,H,W] / [n,2,H,W].  Looks at dtype and size only (works on CPU tensors)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
     if image0.dtype != image1.dtype:
-        raise ValueError("image0 and image1 must have one dtype, got %s and %s" % (name(image0), name(image1)))
+        raise ValueError("image0 and image1 must have one dtype, got %s and %s" % (_dtype_name(image0), _dtype_name(image1)))
     codes = []
-    for what, t, valid in (("image0", image0, {"float32": FMT_F32, "uint8": FMT_U8}), ("flow", flow, {"float32": FMT_F32, "float16": FMT_F16})):
-        if name(t) not in valid:
-            raise ValueError("%s must be %s, got %s" % (what, " or ".join(sorted(valid)), name(t)))
-        codes.append(valid[name(t)])
+    for what, t, valid in (("image0", image0, _IMAGE_CODES), ("flow", flow, _FLOW_CODES)):
+        if _dtype_name(t) not in valid:
+            raise ValueError("%s must be %s, got %s" % (what, " or ".join(sorted(valid)), _dtype_name(t)))
+        codes.append(valid[_dtype_name(t)])
     for what, t, ch in (("image0", image0, 3), ("image1", image1, 3), ("flow", flow, 2)):
         if t.numel() < n * ch * height * width:
             raise ValueError("%s holds %d elements, [%d,%d,%d,%d] needs %d" % (what, t.numel(), n, ch, height, width, n * ch * height * width))
@@ -159,9 +184,6 @@ def extras_format(extras, flow_code, n, height, width):
     flow_code (FMT_F32 | FMT_F16) for n samples of height x width: flow1 must have the flow's dtype, occ0 / occ1 one dtype,
     float32 or uint8, the labels are uint8, every tensor its shape ([n,2,H,W], [n,1,H,W], [n,H,W]).  Raises ValueError for
     anything else.  Looks at dtype and shape only (works on CPU tensors)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
     flow_dt = {FMT_F32: "float32", FMT_F16: "float16"}[flow_code]
     occ_dt = None
     for key, t in extras.items():
@@ -177,11 +199,10 @@ def extras_format(extras, flow_code, n, height, width):
             valid = ("float32", "uint8") if occ_dt is None else (occ_dt,)
         else:
             valid = ("uint8",)
-        if tuple(t.shape) != shape or name(t) not in valid:
-            why = " (the dtype of flow)" if key == "flow1" else " (occ0 and occ1 alike)" if key in ("occ0", "occ1") else ""
-            raise ValueError("extra %r must be %s %s%s, got %s %s" % (key, " or ".join(valid), shape, why, name(t), tuple(t.shape)))
+        why = " (the dtype of flow)" if key == "flow1" else " (occ0 and occ1 alike)" if key in ("occ0", "occ1") else ""
+        _check_plane("extra %r" % key, t, valid, shape, note=why)
         if key in ("occ0", "occ1"):
-            occ_dt = name(t)
+            occ_dt = _dtype_name(t)
     return FMT_U8 if occ_dt == "uint8" else FMT_F32
 
 
@@ -244,21 +265,17 @@ def object_table_format(label0, label1, rows, counts, height, width, n=None):
     """(n, rows_per_sample) of the arguments of Generator.object_table: rows uint8 [n, rows_per_sample, 96] with
     rows_per_sample >= 1, counts int32 [n], label0 / label1 None or uint8 [n,H,W]; n (the batch the table is of), when given,
     must be theirs.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
     if rows is None or counts is None:
         raise ValueError("object_table needs rows and counts (alloc_object_table)")
-    if name(rows) != "uint8" or len(rows.shape) != 3 or rows.shape[2] != C.sizeof(ObjectRow) or rows.shape[1] < 1 or rows.shape[0] < 1:
-        raise ValueError("rows must be uint8 [n, rows_per_sample >= 1, %d], got %s %s" % (C.sizeof(ObjectRow), name(rows), tuple(rows.shape)))
+    if _dtype_name(rows) != "uint8" or len(rows.shape) != 3 or rows.shape[2] != C.sizeof(ObjectRow) or rows.shape[1] < 1 or rows.shape[0] < 1:
+        raise ValueError("rows must be uint8 [n, rows_per_sample >= 1, %d], got %s %s" % (C.sizeof(ObjectRow), _dtype_name(rows), tuple(rows.shape)))
     nn, per = int(rows.shape[0]), int(rows.shape[1])
     if n is not None and nn != n:
         raise ValueError("rows holds %d samples, the batch the table is of has %d" % (nn, n))
-    if name(counts) != "int32" or tuple(counts.shape) != (nn,):
-        raise ValueError("counts must be int32 %s, got %s %s" % ((nn,), name(counts), tuple(counts.shape)))
+    _check_plane("counts", counts, ("int32",), (nn,))
     for key, t in (("label0", label0), ("label1", label1)):
-        if t is not None and (name(t) != "uint8" or tuple(t.shape) != (nn, height, width)):
-            raise ValueError("%s must be None or uint8 %s, got %s %s" % (key, (nn, height, width), name(t), tuple(t.shape)))
+        if t is not None:
+            _check_plane(key, t, ("uint8",), (nn, height, width), says="None or uint8")
     return nn, per
 
 
@@ -266,25 +283,11 @@ def flow_stats_format(flow, occ, rows, height, width, one_row=False):
     """(n, flow code, occ code) of the arguments of Generator.flow_stats / host_flow_stats: flow float32 or float16 [n,2,H,W],
     occ None or float32 / uint8 [n,1,H,W], rows uint8 [n, 304] ([1, 304] with one_row).  Raises ValueError for anything else.
     Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
     if flow is None or rows is None:
         raise ValueError("flow_stats needs flow and rows (alloc_flow_stats)")
-    codes = {"float32": FMT_F32, "float16": FMT_F16}
-    if name(flow) not in codes or len(flow.shape) != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (2, height, width):
-        raise ValueError("flow must be float32 or float16 [n,2,%d,%d], got %s %s" % (height, width, name(flow), tuple(flow.shape)))
-    n = int(flow.shape[0])
-    occ_code = FMT_F32
-    if occ is not None:
-        occ_codes = {"float32": FMT_F32, "uint8": FMT_U8}
-        if name(occ) not in occ_codes or tuple(occ.shape) != (n, 1, height, width):
-            raise ValueError("occ must be None or float32 / uint8 %s, got %s %s" % ((n, 1, height, width), name(occ), tuple(occ.shape)))
-        occ_code = occ_codes[name(occ)]
-    want = (1 if one_row else n, C.sizeof(FlowStatsRow))
-    if name(rows) != "uint8" or tuple(rows.shape) != want:
-        raise ValueError("rows must be uint8 %s, got %s %s" % (want, name(rows), tuple(rows.shape)))
-    return n, codes[name(flow)], occ_code
+    n, flow_code, occ_code = _check_flow_occ(flow, occ, height, width)
+    _check_plane("rows", rows, ("uint8",), (1 if one_row else n, C.sizeof(FlowStatsRow)))
+    return n, flow_code, occ_code
 
 
 def _stats_flags(accumulate, visible_only, one_row):
@@ -308,36 +311,20 @@ def flow_pyramid_format(flow, occ, levels, out, out_weights, height, width):
     tensors [n,2,H>>k,W>>k] of one dtype, float32 or float16, out_weights None or a list of `levels` uint16 tensors
     [n,1,H>>k,W>>k].  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and
     numpy arrays)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
-    codes = {"float32": FMT_F32, "float16": FMT_F16}
-    if flow is None or name(flow) not in codes or len(flow.shape) != 4 or flow.shape[0] < 1 or tuple(flow.shape[1:]) != (2, height, width):
-        raise ValueError("flow must be float32 or float16 [n,2,%d,%d], got %s" % (height, width, None if flow is None else (name(flow), tuple(flow.shape))))
-    n = int(flow.shape[0])
-    occ_code = FMT_F32
-    if occ is not None:
-        occ_codes = {"float32": FMT_F32, "uint8": FMT_U8}
-        if name(occ) not in occ_codes or tuple(occ.shape) != (n, 1, height, width):
-            raise ValueError("occ must be None or float32 / uint8 %s, got %s %s" % ((n, 1, height, width), name(occ), tuple(occ.shape)))
-        occ_code = occ_codes[name(occ)]
+    n, flow_code, occ_code = _check_flow_occ(flow, occ, height, width, got="(%r, %r)")  # (a flow of None: "got None", as it always has)
     levels = int(levels)
     if not 1 <= levels <= PYR_MAX_LEVELS or height % (1 << levels) or width % (1 << levels):
         raise ValueError("levels must lie in 1..%d with height and width multiples of 2^levels, got %d for %dx%d" % (PYR_MAX_LEVELS, levels, width, height))
-    if out is None or len(out) != levels or name(out[0]) not in codes:
+    if out is None or len(out) != levels or _dtype_name(out[0]) not in _FLOW_CODES:
         raise ValueError("out must be %d float32 or float16 tensors (alloc_flow_pyramid)" % levels)
     for k, t in enumerate(out, 1):
-        want = (n, 2, height >> k, width >> k)
-        if name(t) != name(out[0]) or tuple(t.shape) != want:
-            raise ValueError("level %d must be %s %s, got %s %s" % (k, name(out[0]), want, name(t), tuple(t.shape)))
+        _check_plane("level %d" % k, t, (_dtype_name(out[0]),), (n, 2, height >> k, width >> k))
     if out_weights is not None:
         if len(out_weights) != levels:
             raise ValueError("weights must be %d tensors (alloc_flow_pyramid(weights=True))" % levels)
         for k, t in enumerate(out_weights, 1):
-            want = (n, 1, height >> k, width >> k)
-            if name(t) != "uint16" or tuple(t.shape) != want:
-                raise ValueError("weight %d must be uint16 %s, got %s %s" % (k, want, name(t), tuple(t.shape)))
-    return n, codes[name(flow)], occ_code, codes[name(out[0])]
+            _check_plane("weight %d" % k, t, ("uint16",), (n, 1, height >> k, width >> k))
+    return n, flow_code, occ_code, _FLOW_CODES[_dtype_name(out[0])]
 
 
 def _pyramid_record(levels, out_code, flow_ptrs, weight_ptrs):
@@ -373,9 +360,6 @@ def crop_format(src, dst, height, width):
     uint8, flows float32 / float16, occlusion maps float32 / uint8, labels uint8, one dtype per group -, dst[name] the same
     with one crop_h x crop_w for all.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU
     tensors and numpy arrays)."""
-    def name(t):
-        return str(t.dtype).replace("torch.", "")
-
     if not src or not isinstance(src, dict) or not isinstance(dst, dict):
         raise ValueError("src and dst must be dicts with at least one of %s" % (CROP_PLANES,))
     for key in list(src) + list(dst):
@@ -383,8 +367,7 @@ def crop_format(src, dst, height, width):
             raise ValueError("unknown plane %r (known: %s)" % (key, ", ".join(CROP_PLANES)))
     if set(src) != set(dst):
         raise ValueError("src and dst must hold the same planes, got %s and %s" % (sorted(src), sorted(dst)))
-    groups = {"image": ({"float32": FMT_F32, "uint8": FMT_U8}, None), "flow": ({"float32": FMT_F32, "float16": FMT_F16}, None),
-              "occ": ({"float32": FMT_F32, "uint8": FMT_U8}, None), "label": ({"uint8": FMT_U8}, None)}
+    groups = {"image": (_IMAGE_CODES, None), "flow": (_FLOW_CODES, None), "occ": (_OCC_CODES, None), "label": ({"uint8": FMT_U8}, None)}
     n = crop = None
     for k, key in enumerate(CROP_PLANES):
         if key not in src:
@@ -392,17 +375,17 @@ def crop_format(src, dst, height, width):
         a, b, ch = src[key], dst[key], _CROP_CHANNELS[k]
         group = key.rstrip("01") if not key.startswith("flow") else "flow"
         codes, seen = groups[group]
-        if name(a) not in codes or (seen is not None and seen != name(a)):
-            raise ValueError("%s must be %s%s, got %s" % (key, " or ".join(codes), "" if seen is None else " like the other %s plane" % group, name(a)))
-        groups[group] = (codes, name(a))
+        if _dtype_name(a) not in codes or (seen is not None and seen != _dtype_name(a)):
+            raise ValueError("%s must be %s%s, got %s" % (key, " or ".join(codes), "" if seen is None else " like the other %s plane" % group, _dtype_name(a)))
+        groups[group] = (codes, _dtype_name(a))
         lead = tuple(a.shape[:-2])
         if len(a.shape) < 3 or tuple(a.shape[-2:]) != (height, width) or not (len(lead) == 2 and lead[1] == ch or (group == "label" and len(lead) == 1)):
             raise ValueError("%s must be [n,%d,%d,%d], got %s" % (key, ch, height, width, tuple(a.shape)))
         if lead[0] < 1 or (n is not None and lead[0] != n):
             raise ValueError("%s holds %d samples, the other planes %s" % (key, lead[0], n))
         n = int(lead[0])
-        if name(b) != name(a) or tuple(b.shape[:-2]) != lead or len(b.shape) != len(a.shape) or (crop is not None and tuple(b.shape[-2:]) != crop):
-            raise ValueError("dst[%s] must be %s %s, got %s %s" % (key, name(a), lead + (crop if crop else ("crop_h", "crop_w")), name(b), tuple(b.shape)))
+        if _dtype_name(b) != _dtype_name(a) or tuple(b.shape[:-2]) != lead or len(b.shape) != len(a.shape) or (crop is not None and tuple(b.shape[-2:]) != crop):
+            raise ValueError("dst[%s] must be %s %s, got %s %s" % (key, _dtype_name(a), lead + (crop if crop else ("crop_h", "crop_w")), _dtype_name(b), tuple(b.shape)))
         crop = tuple(int(v) for v in b.shape[-2:])
     if not 8 <= crop[1] <= width or crop[1] % 8 or not 2 <= crop[0] <= height or crop[0] % 2:
         raise ValueError("the window must be a multiple of 8 wide, even high and inside %dx%d, got %dx%d" % (width, height, crop[1], crop[0]))
@@ -425,13 +408,18 @@ def _crop_job(src, dst, ptr, codes, crop_h, crop_w, recs, recs_out, first_index,
     return job
 
 
+def _host_check(rc):
+    """Raises what an ofdg_host_* / pure entry left in the thread's error text."""
+    if rc != OK:
+        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+
+
 def crop_draw(seed, index, width, height, crop_w, crop_h, hflip=False, vflip=False):
     """ofdg_crop_draw (pure, no GPU): the window (x0, y0, flags) of global sample `index` under `seed`; flags holds CROP_HFLIP /
     CROP_VFLIP, drawn only when hflip / vflip allow them."""
     r = CropRec()
     rc = lib().ofdg_crop_draw(int(seed) & 0xFFFFFFFF, int(index), width, height, crop_w, crop_h, _crop_flags(hflip, vflip, False), C.byref(r))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    _host_check(rc)
     return r.x0, r.y0, r.flags
 
 
@@ -440,8 +428,7 @@ def crop_philox(counter, key):
     function the draw of the crop's records is made of."""
     out = (C.c_uint32 * 4)()
     rc = lib().ofdg_crop_philox(C.byref((C.c_uint32 * 4)(*counter)), C.byref((C.c_uint32 * 2)(*key)), C.byref(out))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    _host_check(rc)
     return tuple(int(v) for v in out)
 
 
@@ -802,9 +789,15 @@ class Generator:
         areas stay 0).  stream: the stream the labels were written on - the stream of that call, or STREAM_OWN for the
         internal stream it worked on.  Asynchronous; read the table with object_table_numpy after synchronising."""
         n, per = object_table_format(label0, label1, rows, counts, self.params.height, self.params.width, self._last_n)
-        self._check(lib().ofdg_object_table(self.h, _dptr(label0) if label0 is not None else None,
-                                            _dptr(label1) if label1 is not None else None, _dptr(rows), per, _dptr(counts),
-                                            C.c_void_p(stream)))
+        self._check(lib().ofdg_object_table(self.h, _optr(label0), _optr(label1), _dptr(rows), per, _dptr(counts), C.c_void_p(stream)))
+
+    def _sized(self, entry, size):
+        """(height, width, entry point, its extra arguments) of a reduction of planes of size=(height, width), or, with None,
+        of the context's frame: ofdg_<entry>_sized takes width and height behind n_samples."""
+        if size is None:
+            return self.params.height, self.params.width, getattr(lib(), entry), ()
+        height, width = int(size[0]), int(size[1])
+        return height, width, getattr(lib(), entry + "_sized"), (width, height)
 
     def flow_stats(self, flow, rows, occ=None, bin_px=2.0, accumulate=False, visible_only=False, one_row=False, stream=0, size=None):
         """Per-sample statistics of a flow tensor (ofdg_flow_stats, include/ofdg.h) into rows (alloc_flow_stats): the histogram
@@ -815,10 +808,9 @@ class Generator:
         stream the flow was written on, or STREAM_OWN for the internal stream the last render / forward call worked on.
         Asynchronous; read the rows with flow_stats_numpy after synchronising.  size=(height, width): the planes are of that
         size instead of the context's frame - a cropped flow (ofdg_flow_stats_sized)."""
-        height, width = (int(size[0]), int(size[1])) if size is not None else (self.params.height, self.params.width)
+        height, width, entry, plane = self._sized("ofdg_flow_stats", size)
         n, fcode, ocode = flow_stats_format(flow, occ, rows, height, width, one_row)
-        entry, plane = (lib().ofdg_flow_stats_sized, (width, height)) if size is not None else (lib().ofdg_flow_stats, ())
-        self._check(entry(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, *plane, float(bin_px),
+        self._check(entry(self.h, _dptr(flow), fcode, _optr(occ), ocode, n, *plane, float(bin_px),
                           _stats_flags(accumulate, visible_only, one_row), _dptr(rows), C.c_void_p(stream)))
 
     def flow_pyramid(self, flow, levels, occ=None, scale=True, out_dtype=None, weights=False, out=None, stream=0, size=None):
@@ -832,17 +824,13 @@ class Generator:
         written on, or STREAM_OWN.  Asynchronous.  Returns the list of levels, or (levels, weights) with weights.
         size=(height, width): the planes are of that size instead of the context's frame - a cropped flow
         (ofdg_flow_pyramid_sized)."""
-        n, height, width = int(flow.shape[0]), self.params.height, self.params.width
-        if size is not None:
-            height, width = int(size[0]), int(size[1])
+        height, width, entry, plane = self._sized("ofdg_flow_pyramid", size)
         if out is None:
-            out = alloc_flow_pyramid(n, height, width, levels, flow.dtype if out_dtype is None else out_dtype, weights, flow.device)
+            out = alloc_flow_pyramid(int(flow.shape[0]), height, width, levels, flow.dtype if out_dtype is None else out_dtype, weights, flow.device)
         lv, wt = out if isinstance(out, tuple) else (out, None)
         n, fcode, ocode, out_code = flow_pyramid_format(flow, occ, levels, lv, wt, height, width)
         rec = _pyramid_record(int(levels), out_code, [_dptr(t) for t in lv], None if wt is None else [_dptr(t) for t in wt])
-        entry, plane = (lib().ofdg_flow_pyramid_sized, (width, height)) if size is not None else (lib().ofdg_flow_pyramid, ())
-        self._check(entry(self.h, _dptr(flow), fcode, _dptr(occ) if occ is not None else None, ocode, n, *plane,
-                          PYR_SCALE if scale else 0, C.byref(rec), C.c_void_p(stream)))
+        self._check(entry(self.h, _dptr(flow), fcode, _optr(occ), ocode, n, *plane, PYR_SCALE if scale else 0, C.byref(rec), C.c_void_p(stream)))
         return out
 
     def crop(self, src, dst, recs=None, first_index=0, seed=None, hflip=False, vflip=False, occ_window=False, recs_out=None, stream=0):
@@ -859,8 +847,8 @@ class Generator:
         for t in (recs, recs_out):
             if t is not None and (str(t.dtype) != "torch.int32" or tuple(t.shape) != (n, 4)):
                 raise ValueError("recs and recs_out must be int32 [%d,4], got %s %s" % (n, t.dtype, tuple(t.shape)))
-        job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, None if recs is None else _dptr(recs), None if recs_out is None else _dptr(recs_out),
-                        first_index, self.params.seed if seed is None else seed, _crop_flags(hflip, vflip, occ_window))
+        job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, _optr(recs), _optr(recs_out), first_index,
+                        self.params.seed if seed is None else seed, _crop_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_crop(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
@@ -1019,12 +1007,10 @@ def decode_image(path):
     L.ofdg_host_decode_image.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.ofdg_host_last_error.restype = C.c_char_p
     rc = L.ofdg_host_decode_image(str(path).encode(), None, 0, C.byref(w), C.byref(h))
-    if rc != OK:
-        raise OfdgError(rc, L.ofdg_host_last_error().decode())
+    _host_check(rc)
     out = np.empty((3, h.value, w.value), dtype=np.uint8)
     rc = L.ofdg_host_decode_image(str(path).encode(), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w), C.byref(h))
-    if rc != OK:
-        raise OfdgError(rc, L.ofdg_host_last_error().decode())
+    _host_check(rc)
     return out
 
 
@@ -1125,6 +1111,16 @@ def _dptr(x):
     return C.c_void_p(int(x))
 
 
+def _optr(x):
+    """_dptr of an optional argument: None stays None (NULL)."""
+    return None if x is None else _dptr(x)
+
+
+def _hptr(a):
+    """The address of a host array as a ctypes pointer; None stays None (NULL)."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def device_pointers(tensors):
     """The device addresses of output tensors as ctypes pointers, checked once: what a loop that renders into the same buffer
     sets again and again passes instead of the tensors (the per-call checks of three tensors cost the host ~2 us)."""
@@ -1205,10 +1201,8 @@ def host_object_table(label0, label1, counts, rows_per_sample=MAX_OBJECT_ROWS, w
     if len(shape) != 3 or shape[0] != len(counts) or any(t is not None and t.shape != shape for t in planes):
         raise ValueError("label planes must be uint8 [n,H,W] with n = len(counts) = %d, got %s" % (len(counts), [None if t is None else t.shape for t in planes]))
     out = np.zeros((shape[0], rows_per_sample), _object_row_dtype())
-    rc = lib().ofdg_host_object_table(*(None if t is None else t.ctypes.data_as(C.c_void_p) for t in planes), shape[0], shape[2], shape[1],
-                                      counts.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), rows_per_sample)
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    rc = lib().ofdg_host_object_table(_hptr(planes[0]), _hptr(planes[1]), shape[0], shape[2], shape[1], _hptr(counts), _hptr(out), rows_per_sample)
+    _host_check(rc)
     return out
 
 
@@ -1260,11 +1254,9 @@ def host_flow_stats(flow, occ=None, bin_px=2.0, accumulate=False, visible_only=F
     elif rows.dtype != _flow_stats_dtype() or rows.shape != (m,) or not rows.flags["C_CONTIGUOUS"]:
         raise ValueError("rows must be a contiguous FLOW_STATS_DTYPE array of shape %s" % ((m,),))
     n, fcode, ocode = flow_stats_format(flow, occ, rows.view(np.uint8).reshape(m, -1), height, width, one_row)
-    rc = lib().ofdg_host_flow_stats(flow.ctypes.data_as(C.c_void_p), fcode, None if occ is None else occ.ctypes.data_as(C.c_void_p), ocode,
-                                    n, width, height, float(bin_px), _stats_flags(accumulate, visible_only, one_row),
-                                    rows.ctypes.data_as(C.c_void_p))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    rc = lib().ofdg_host_flow_stats(_hptr(flow), fcode, _hptr(occ), ocode, n, width, height, float(bin_px),
+                                    _stats_flags(accumulate, visible_only, one_row), _hptr(rows))
+    _host_check(rc)
     return rows
 
 
@@ -1304,10 +1296,8 @@ def host_flow_pyramid(flow, levels, occ=None, scale=True, out_dtype=None, weight
     wt = [np.zeros((n, 1, height >> k, width >> k), np.uint16) for k in range(1, levels + 1)] if weights else None
     n, fcode, ocode, out_code = flow_pyramid_format(flow, occ, levels, lv, wt, height, width)
     rec = _pyramid_record(levels, out_code, [t.ctypes.data for t in lv], None if wt is None else [t.ctypes.data for t in wt])
-    rc = lib().ofdg_host_flow_pyramid(flow.ctypes.data_as(C.c_void_p), fcode, None if occ is None else occ.ctypes.data_as(C.c_void_p), ocode,
-                                      n, width, height, PYR_SCALE if scale else 0, C.byref(rec))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    rc = lib().ofdg_host_flow_pyramid(_hptr(flow), fcode, _hptr(occ), ocode, n, width, height, PYR_SCALE if scale else 0, C.byref(rec))
+    _host_check(rc)
     return (lv, wt) if weights else lv
 
 
@@ -1346,8 +1336,7 @@ def host_crop(src, crop_h, crop_w, recs=None, first_index=0, seed=0, hflip=False
     job = _crop_job(src, dst, lambda a: a.ctypes.data, codes, crop_h, crop_w, None if recs is None else recs.ctypes.data, used.ctypes.data,
                     first_index, seed, _crop_flags(hflip, vflip, occ_window))
     rc = lib().ofdg_host_crop(C.byref(job), n, width, height)
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    _host_check(rc)
     return dst, used
 
 
@@ -1357,8 +1346,7 @@ class HostSampler:
     def __init__(self, mode, width=512, height=384, num_objects=0):
         h = C.c_void_p()
         rc = lib().ofdg_host_sampler_create(mode, width, height, num_objects, C.byref(h))
-        if rc != OK:
-            raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+        _host_check(rc)
         self.h = h
 
     def next(self, n_tasks, cap=None):
@@ -1367,8 +1355,7 @@ class HostSampler:
         bps = (Blueprint * cap)()
         n = C.c_int()
         rc = lib().ofdg_host_sampler_next(self.h, n_tasks, C.cast(tasks, C.c_void_p), C.cast(bps, C.c_void_p), cap, C.byref(n))
-        if rc != OK:
-            raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+        _host_check(rc)
         return tasks, bps, n.value
 
     def __del__(self):
@@ -1389,8 +1376,7 @@ def host_realize(params, pool_n, pool_w, pool_h, tasks, n_tasks, bps, n_bps, cap
     rc = lib().ofdg_host_realize(C.byref(params), pool_n, pool_w, pool_h, C.cast(tasks, C.c_void_p), n_tasks,
                                  C.cast(bps, C.c_void_p), n_bps, sm.ctypes.data_as(C.c_void_p), cap, C.byref(ns),
                                  om.ctypes.data_as(C.c_void_p), cap, C.byref(no))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    _host_check(rc)
     return sm[:ns.value].copy(), om[:no.value].copy()
 
 
@@ -1409,8 +1395,7 @@ def parse_prototxt(text):
     buf = C.create_string_buffer(4096)
     ntop = C.c_int()
     rc = lib().ofdg_parse_prototxt(text.encode(), C.byref(p), buf, 4096, C.byref(ntop))
-    if rc != OK:
-        raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+    _host_check(rc)
     return p, buf.value.decode(), ntop.value
 
 
@@ -1422,8 +1407,7 @@ class DataGenerationLayer:
     def __init__(self, prototxt, comm=None):
         h = C.c_void_p()
         rc = lib().ofdg_layer_create_dist(prototxt.encode(), comm.h if comm is not None else None, C.byref(h))
-        if rc != OK:
-            raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+        _host_check(rc)
         self.h = h
 
     def type(self):
@@ -1434,8 +1418,7 @@ class DataGenerationLayer:
         p0, p1, p2 = C.c_void_p(), C.c_void_p(), C.c_void_p()
         shape = (C.c_int * 4)()
         rc = lib().ofdg_layer_forward(self.h, C.byref(p0), C.byref(p1), C.byref(p2), C.byref(shape))
-        if rc != OK:
-            raise OfdgError(rc, lib().ofdg_host_last_error().decode())
+        _host_check(rc)
         n, _, hh, ww = list(shape)
         outs = []
         for ptr, ch in ((p0, 3), (p1, 3), (p2, 2)):
@@ -1561,12 +1544,7 @@ class FlowLoader:
             return self._enqueue_cropped(j, s, chain, step)
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
-        if self.sbufs[j] is not None:
-            occ = self.xbufs[j].get("occ0") if self.xbufs[j] is not None else None
-            self.gen.flow_stats(self.bufs[j][2], self.sbufs[j], occ=occ, bin_px=self.stats_bin_px, stream=s)
-        if self.pbufs[j] is not None:
-            occ = self.xbufs[j].get("occ0") if self.xbufs[j] is not None else None
-            self.gen.flow_pyramid(self.bufs[j][2], self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s)
+        self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
         self.ready[j].record(chain)
 
     def _enqueue_cropped(self, j, s, chain, step):
@@ -1576,12 +1554,16 @@ class FlowLoader:
         out, recs = self.cbufs[j]
         self.gen.crop(planes, out, first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank), hflip=self.crop_flips[0],
                       vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
-        if self.sbufs[j] is not None:
-            self.gen.flow_stats(out["flow"], self.sbufs[j], occ=out.get("occ0"), bin_px=self.stats_bin_px, stream=s, size=self.crop)
-        if self.pbufs[j] is not None:
-            self.gen.flow_pyramid(out["flow"], self.pyramid, occ=out.get("occ0"), scale=self.pyramid_scale, out=self.pbufs[j], stream=s,
-                                  size=self.crop)
+        self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
         self.ready[j].record(chain)
+
+    def _enqueue_reductions(self, j, flow, occ, s, size):
+        """The statistics and the pyramid of set j, as far as the loader makes them, of a flow and its map (None: no map) of
+        size=(height, width) (None: the frame) on stream s."""
+        if self.sbufs[j] is not None:
+            self.gen.flow_stats(flow, self.sbufs[j], occ=occ, bin_px=self.stats_bin_px, stream=s, size=size)
+        if self.pbufs[j] is not None:
+            self.gen.flow_pyramid(flow, self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s, size=size)
 
     def _add_reductions(self, more, j):
         """the statistics and the pyramid of set j into the batch's dict"""

@@ -123,8 +123,6 @@ int ofdg_host_bg_prep(int pool_w, int pool_h, int width, int height, float angle
 }
 
 // ofdg_object_table's reduction on host label planes (no GPU): areas and boxes of the visible pixels of each label.
-static_assert(sizeof(ofdg_object_row) == 96 && offsetof(ofdg_object_row, box0) == 16 && offsetof(ofdg_object_row, motion) == 48,
-              "ofdg_object_row: 96 bytes, no padding");
 int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, int width, int height, const int32_t* counts,
                            ofdg_object_row* rows, int rows_per_sample) {
   if (!counts || !rows || n < 1 || width < 1 || height < 1 || rows_per_sample < 1) {
@@ -160,9 +158,6 @@ int ofdg_host_object_table(const uint8_t* label0, const uint8_t* label1, int n, 
 
 // ofdg_flow_stats on host buffers (no GPU): the definition of include/ofdg.h pixel by pixel.  This file is compiled with
 // -ffp-contract=off, so m2 is two products and one sum, each rounded to float32.
-static_assert(sizeof(ofdg_flow_stats_row) == 304 && offsetof(ofdg_flow_stats_row, n_counted) == 256 &&
-              offsetof(ofdg_flow_stats_row, sum_u_q8) == 272 && offsetof(ofdg_flow_stats_row, max_key) == 296,
-              "ofdg_flow_stats_row: 304 bytes, no padding");
 static float half_bits_to_float(uint16_t h) {  // binary16 -> float32, exact
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
   uint32_t bits;
@@ -178,6 +173,31 @@ static float half_bits_to_float(uint16_t h) {  // binary16 -> float32, exact
   std::memcpy(&f, &bits, 4);
   return f;
 }
+// How the host twins read a caller's plane: element by element through memcpy, so no alignment is asked of it.
+struct FlowPlane {  // binary16 or float32, widened to float32
+  const void* p;
+  int fmt;
+  float at(size_t i) const {
+    if (fmt == OFDG_FMT_F16) {
+      uint16_t h;
+      std::memcpy(&h, static_cast<const uint8_t*>(p) + 2 * i, 2);
+      return half_bits_to_float(h);
+    }
+    float f;
+    std::memcpy(&f, static_cast<const uint8_t*>(p) + 4 * i, 4);
+    return f;
+  }
+};
+struct OccPlane {  // uint8 or float32: is the element non-zero?
+  const void* p;
+  int fmt;
+  bool at(size_t i) const {
+    if (fmt == OFDG_FMT_U8) return static_cast<const uint8_t*>(p)[i] != 0;
+    float f;
+    std::memcpy(&f, static_cast<const uint8_t*>(p) + 4 * i, 4);
+    return f != 0.0f;
+  }
+};
 int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height, float bin_px,
                          int flags, ofdg_flow_stats_row* rows) {
   if (const char* why = flow_stats_arg_error(flow, flow_fmt, occ, occ_fmt, n, width, height, bin_px, flags, rows)) {
@@ -192,21 +212,16 @@ int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int oc
     edge2[k] = e * e;
   }
   const size_t plane = (size_t)width * height;
-  auto flow_at = [&](size_t i) {
-    return flow_fmt == OFDG_FMT_F16 ? half_bits_to_float(static_cast<const uint16_t*>(flow)[i]) : static_cast<const float*>(flow)[i];
-  };
+  const FlowPlane fl{flow, flow_fmt};
+  const OccPlane hidden{occ, occ_fmt};
   for (int s = 0; s < n; ++s) {
     ofdg_flow_stats_row& r = rows[one_row ? 0 : s];
     for (size_t p = 0; p < plane; ++p) {
-      if (occ) {
-        const size_t o = (size_t)s * plane + p;
-        const bool hidden = occ_fmt == OFDG_FMT_U8 ? static_cast<const uint8_t*>(occ)[o] != 0 : static_cast<const float*>(occ)[o] != 0.0f;
-        if (hidden) {
-          ++r.n_occluded;
-          if (visible_only) continue;
-        }
+      if (occ && hidden.at((size_t)s * plane + p)) {
+        ++r.n_occluded;
+        if (visible_only) continue;
       }
-      const float u = flow_at((size_t)s * 2 * plane + p), v = flow_at(((size_t)s * 2 + 1) * plane + p);
+      const float u = fl.at((size_t)s * 2 * plane + p), v = fl.at(((size_t)s * 2 + 1) * plane + p);
       if (!(std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f)) { ++r.n_bad; continue; }
       ++r.n_counted;
       const float uu = u * u, vv = v * v, m2 = uu + vv;
@@ -227,9 +242,6 @@ int ofdg_host_flow_stats(const void* flow, int flow_fmt, const void* occ, int oc
 
 // ofdg_flow_pyramid on host buffers (no GPU): the definition of include/ofdg.h cell by cell, level by level - the sums and
 // counts of level k are kept and level k + 1 is made of them.  -ffp-contract=off: every sum is its own float32 rounding.
-static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && offsetof(struct ofdg_flow_pyramid, levels) == 96 &&
-              offsetof(struct ofdg_flow_pyramid, out_fmt) == 100 && OFDG_PYR_MAX_LEVELS == kPyrMaxLevels && OFDG_PYR_SCALE == 1,
-              "struct ofdg_flow_pyramid: 104 bytes, the layout flow_pyramid_arg_error reads");
 static uint16_t float_to_half_bits(float f) {  // float32 -> binary16, to nearest even, an overflow becomes +-inf
   uint32_t x;
   std::memcpy(&x, &f, 4);
@@ -255,29 +267,15 @@ int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int 
     return OFDG_EINVAL;
   }
   const size_t plane = (size_t)width * height;
-  auto flow_at = [&](size_t i) {  // (memcpy: no alignment is asked of the planes)
-    if (flow_fmt == OFDG_FMT_F16) {
-      uint16_t h;
-      std::memcpy(&h, static_cast<const uint8_t*>(flow) + 2 * i, 2);
-      return half_bits_to_float(h);
-    }
-    float f;
-    std::memcpy(&f, static_cast<const uint8_t*>(flow) + 4 * i, 4);
-    return f;
-  };
-  auto hidden_at = [&](size_t i) {
-    if (occ_fmt == OFDG_FMT_U8) return static_cast<const uint8_t*>(occ)[i] != 0;
-    float f;
-    std::memcpy(&f, static_cast<const uint8_t*>(occ) + 4 * i, 4);
-    return f != 0.0f;
-  };
+  const FlowPlane fl{flow, flow_fmt};
+  const OccPlane hidden{occ, occ_fmt};
   std::vector<float> su(plane), sv(plane), tu, tv;
   std::vector<uint32_t> sc(plane), tc;
   for (int s = 0; s < n; ++s) {
     su.resize(plane); sv.resize(plane); sc.resize(plane);
     for (size_t p = 0; p < plane; ++p) {
-      const float u = flow_at((size_t)s * 2 * plane + p), v = flow_at(((size_t)s * 2 + 1) * plane + p);
-      const bool usable = std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f && !(occ && hidden_at((size_t)s * plane + p));
+      const float u = fl.at((size_t)s * 2 * plane + p), v = fl.at(((size_t)s * 2 + 1) * plane + p);
+      const bool usable = std::fabs(u) < 1048576.0f && std::fabs(v) < 1048576.0f && !(occ && hidden.at((size_t)s * plane + p));
       su[p] = usable ? u : 0.0f;
       sv[p] = usable ? v : 0.0f;
       sc[p] = usable ? 1u : 0u;
@@ -319,12 +317,6 @@ int ofdg_host_flow_pyramid(const void* flow, int flow_fmt, const void* occ, int 
 
 // ofdg_crop on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising and the window
 // test are the functions the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy, so no alignment is asked.
-static_assert(sizeof(ofdg_crop_rec) == sizeof(DevCropRec) && sizeof(struct ofdg_crop_job) == sizeof(DevCropJob) &&
-              offsetof(struct ofdg_crop_job, recs) == 128 && offsetof(struct ofdg_crop_job, first_index) == 144 &&
-              offsetof(struct ofdg_crop_job, seed) == 152 && offsetof(struct ofdg_crop_job, crop_w) == 156 &&
-              offsetof(struct ofdg_crop_job, reserved) == 180 && OFDG_CROP_PLANES == kCropPlanes && OFDG_CROP_RANDOM_HFLIP == 4 &&
-              OFDG_CROP_RANDOM_VFLIP == 8 && OFDG_CROP_OCC_WINDOW == 16,
-              "struct ofdg_crop_job: 184 bytes, the layout crop_arg_error reads");
 int ofdg_crop_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
   if (!counter || !key || !out) { g_host_error = "ofdg_crop_philox: counter, key or out is NULL"; return OFDG_EINVAL; }
   const CropWords w = crop_philox(CropWords{counter[0], counter[1], counter[2], counter[3]}, key[0], key[1]);
@@ -347,16 +339,6 @@ int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, in
   if (why) { g_host_error = std::string("ofdg_host_crop: ") + why; return OFDG_EINVAL; }
   const int cw = j->crop_w, ch = j->crop_h;
   const size_t frame = (size_t)width * height, window = (size_t)cw * ch;
-  auto flow_at = [&](const void* flow, size_t i) {
-    if (j->flow_fmt == OFDG_FMT_F16) {
-      uint16_t h;
-      std::memcpy(&h, static_cast<const uint8_t*>(flow) + 2 * i, 2);
-      return half_bits_to_float(h);
-    }
-    float f;
-    std::memcpy(&f, static_cast<const uint8_t*>(flow) + 4 * i, 4);
-    return f;
-  };
   for (int i = 0; i < n_samples; ++i) {
     DevCropRec r;
     if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + 16 * (size_t)i, 16);
@@ -368,7 +350,7 @@ int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, in
       if (!j->src[k]) continue;
       const int C = crop_channels(k), es = crop_elem_bytes(*j, k);
       const bool is_flow = k == OFDG_CROP_FLOW || k == OFDG_CROP_FLOW1, is_occ = k == OFDG_CROP_OCC0 || k == OFDG_CROP_OCC1;
-      const void* const flow = (is_occ && (j->flags & OFDG_CROP_OCC_WINDOW)) ? j->src[k - 2] : nullptr;
+      const FlowPlane fl{(is_occ && (j->flags & OFDG_CROP_OCC_WINDOW)) ? j->src[k - 2] : nullptr, j->flow_fmt};  // (of an occlusion map under the window rule)
       for (int c = 0; c < C; ++c) {
         const uint8_t* const sp = static_cast<const uint8_t*>(j->src[k]) + ((size_t)i * C + c) * frame * es;
         uint8_t* const dp = static_cast<uint8_t*>(j->dst[k]) + ((size_t)i * C + c) * window * es;
@@ -380,15 +362,13 @@ int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, in
             uint8_t e[4];
             std::memcpy(e, sp + at * es, es);
             if (negate) e[es - 1] ^= 0x80u;  // (little-endian: the sign bit is in the element's last byte)
-            if (flow) {
-              const float u = flow_at(flow, (size_t)i * 2 * frame + at), v = flow_at(flow, ((size_t)i * 2 + 1) * frame + at);
+            if (fl.p) {
+              const float u = fl.at((size_t)i * 2 * frame + at), v = fl.at(((size_t)i * 2 + 1) * frame + at);
               const bool inside = crop_target_inside(xs, u, r.x0, cw) && crop_target_inside(ys, v, r.y0, ch);
-              if (es == 4) {
-                float f;
-                std::memcpy(&f, e, 4);
-                if (f != 0.0f || !inside) { f = 1.0f; std::memcpy(e, &f, 4); }
-              } else if (e[0] != 0 || !inside) {
-                e[0] = 1;
+              if (OccPlane{e, j->occ_fmt}.at(0) || !inside) {
+                const float one = 1.0f;
+                if (es == 4) std::memcpy(e, &one, 4);
+                else e[0] = 1;
               }
             }
             std::memcpy(dp + ((size_t)Y * cw + X) * es, e, es);

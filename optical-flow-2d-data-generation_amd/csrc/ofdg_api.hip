@@ -266,6 +266,36 @@ static std::string err_text(uint32_t e) {
   return t;
 }
 
+// ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop ------------
+// How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
+struct PostOp {
+  ofdg_ctx* c;
+  const char* who;  // the entry's name in the error text
+  int fail(const std::string& why) const { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; }
+  // an input plane of element type fmt (NULL: not given) at the alignment the kernels read it with (plane_alignment)
+  int aligned(const std::string& name, const void* p, int fmt, bool say_fmt = true) const {
+    if (!plane_misaligned(p, fmt)) return OFDG_OK;
+    return fail(name + " must be " + std::to_string(plane_alignment(fmt)) + "-byte aligned" + (say_fmt ? std::string(" (") + fmt_name(fmt) + ")" : ""));
+  }
+  // `stream` of the call; OFDG_STREAM_OWN: the internal stream the last render / forward call worked on
+  int stream_of(void* stream, hipStream_t* st) const {
+    if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
+    *st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+    return OFDG_OK;
+  }
+};
+// A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
+// the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel.
+template <class T, T... Vs, class F>
+static void with_constant(T v, F&& f) {
+  (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
+}
+template <class F>
+static void with_bool(bool v, F&& f) { with_constant<bool, false, true>(v, f); }
+// the kernels' kOcc of an optional occlusion map: 0 no map, 1 float32, 2 uint8
+template <class F>
+static void with_occ_kind(const void* d_occ, int occ_fmt, F&& f) { with_constant<int, 0, 1, 2>(!d_occ ? 0 : occ_fmt == OFDG_FMT_U8 ? 2 : 1, f); }
+
 static int discard_all_prepared(ofdg_ctx* c);
 static int texture_of_image(ofdg_ctx* c, const uint32_t* image, int w, int h, int tw, int th, uint32_t* out);
 
@@ -1489,28 +1519,23 @@ int ofdg_render_resident(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flo
 // The per-object annotation table of the batch the last render / forward call composed (c->last_slot): two small kernels on
 // `stream` - the stream the labels were written on - that read the slot's records and the caller's label planes.  Nothing but
 // argument checks happens on the host.
-static_assert(sizeof(ofdg_object_row) == sizeof(DevObjectRow) && sizeof(ofdg_object_row) == 96 && offsetof(ofdg_object_row, area0) == 8 &&
-              offsetof(ofdg_object_row, area0) == offsetof(DevObjectRow, area) && offsetof(ofdg_object_row, box0) == 16 &&
-              offsetof(ofdg_object_row, box0) == offsetof(DevObjectRow, box) && offsetof(ofdg_object_row, box1) == 32 &&
-              offsetof(ofdg_object_row, motion) == 48 && offsetof(ofdg_object_row, motion) == offsetof(DevObjectRow, motion),
-              "ofdg_object_row: 96 bytes without padding, the layout the kernels write");
-static_assert(OFDG_MAX_OBJECT_ROWS == kObjectRows, "background + kMaxFgObjects");
 int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_label1, ofdg_object_row* d_rows, int rows_per_sample,
                       int32_t* d_counts, void* stream) {
   if (!c) return OFDG_EINVAL;
-  auto fail = [&](const std::string& why) { c->err = "ofdg_object_table: " + why; return OFDG_EINVAL; };
-  if (c->prm.mode == 9) return fail("the table restates the label planes, which are defined for the rigid modes only (mode 9)");
-  if (!d_rows) return fail("d_rows is NULL");
-  if (!d_counts) return fail("d_counts is NULL");
-  if (rows_per_sample < 1) return fail("rows_per_sample = " + std::to_string(rows_per_sample) + " (valid: >= 1)");
-  if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_counts & 3) || ((uintptr_t)d_label0 & 3) || ((uintptr_t)d_label1 & 3))
-    return fail("d_rows must be 8-byte aligned, d_counts and the label planes 4-byte aligned");
+  const PostOp op{c, "ofdg_object_table"};
+  if (c->prm.mode == 9) return op.fail("the table restates the label planes, which are defined for the rigid modes only (mode 9)");
+  if (!d_rows) return op.fail("d_rows is NULL");
+  if (!d_counts) return op.fail("d_counts is NULL");
+  if (rows_per_sample < 1) return op.fail("rows_per_sample = " + std::to_string(rows_per_sample) + " (valid: >= 1)");
+  if (((uintptr_t)d_rows & 7) || ((uintptr_t)d_counts & 3) || plane_misaligned(d_label0, OFDG_FMT_U8) || plane_misaligned(d_label1, OFDG_FMT_U8))
+    return op.fail("d_rows must be 8-byte aligned, d_counts and the label planes 4-byte aligned");
   if (!c->last_slot || !c->last_ch || c->last_slot->res_samples <= 0)
-    return fail("no render / forward call has been made yet on this context");
+    return op.fail("no render / forward call has been made yet on this context");
   ofdg_ctx::Slot& sl = *c->last_slot;
   ofdg_ctx::Chain& ch = *c->last_ch;
   const hipStream_t S = c->last_stream;  // the internal stream that call worked on
-  const hipStream_t st = stream == OFDG_STREAM_OWN ? S : (hipStream_t)stream;
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
   const int W = c->prm.width, H = c->prm.height, n = c->last_n;
   const DevSample* const samples = sl.d_samples.p + c->last_base;  // (the batch that call composed: a slot may hold two)
   // The slot's records must outlive the kernels.  On the chain's own stream the order of the stream sees to that (a private
@@ -1534,147 +1559,106 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   return OFDG_OK;
 }
 
-// Flow statistics of caller-given planes: the clearing of the rows and one kernel on `stream`.  It reads nothing of the
-// context's own (no slot record, no workspace), so no completion bookkeeping is needed on any stream.
-static_assert(sizeof(ofdg_flow_stats_row) == sizeof(DevFlowStatsRow) && OFDG_FLOW_HIST_BINS == kFlowHistBins &&
-              offsetof(ofdg_flow_stats_row, n_counted) == offsetof(DevFlowStatsRow, count) &&
-              offsetof(ofdg_flow_stats_row, sum_u_q8) == offsetof(DevFlowStatsRow, sum_q8) &&
-              offsetof(ofdg_flow_stats_row, max_key) == offsetof(DevFlowStatsRow, max_key) && offsetof(ofdg_flow_stats_row, max_key) == 296,
-              "ofdg_flow_stats_row: 304 bytes without padding, the layout the kernel adds to");
-static_assert(OFDG_FMT_F32 == 0 && OFDG_FMT_U8 == 1 && OFDG_FMT_F16 == 2 && OFDG_STATS_ACCUMULATE == 1 && OFDG_STATS_VISIBLE_ONLY == 2 &&
-              OFDG_STATS_ONE_ROW == 4, "flow_stats_arg_error spells these codes out");
-// (`who`: the entry's name in the error text; W, H: the context's frame, or the plane size a sized call gave and checked)
-static int flow_stats_on(ofdg_ctx* c, const char* who, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
-                         int n_samples, float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream) {
-  auto fail = [&](const std::string& why) { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; };
-  if (const char* why = flow_stats_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, bin_px, flags, d_rows)) return fail(why);
-  const bool half = flow_fmt == OFDG_FMT_F16;
-  if ((uintptr_t)d_flow & (half ? 7 : 15)) return fail(half ? "d_flow must be 8-byte aligned (binary16)" : "d_flow must be 16-byte aligned (float32)");
-  if (d_occ && ((uintptr_t)d_occ & (occ_fmt == OFDG_FMT_U8 ? 3 : 15)))
-    return fail(occ_fmt == OFDG_FMT_U8 ? "d_occ must be 4-byte aligned (uint8)" : "d_occ must be 16-byte aligned (float32)");
-  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
-  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+// The two reductions and the crop read nothing of the context's own (no slot record, no workspace), so no completion
+// bookkeeping is needed on any stream.  A flow with its optional occlusion map as they take it:
+static int flow_planes_aligned(const PostOp& op, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt) {
+  OFDG_TRY(op.aligned("d_flow", d_flow, flow_fmt));
+  return op.aligned("d_occ", d_occ, occ_fmt);
+}
+
+// Flow statistics of caller-given planes: the clearing of the rows and one kernel on `stream`.
+// (op.who: the entry's name; W, H: the context's frame, or the plane size a sized call gave and checked)
+static int flow_stats_on(const PostOp& op, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples,
+                         float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream) {
+  ofdg_ctx* const c = op.c;
+  if (const char* why = flow_stats_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, bin_px, flags, d_rows)) return op.fail(why);
+  OFDG_TRY(flow_planes_aligned(op, d_flow, flow_fmt, d_occ, occ_fmt));
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
   const bool one_row = flags & OFDG_STATS_ONE_ROW;
   if (!(flags & OFDG_STATS_ACCUMULATE))
     HIP_OK(c, hipMemsetAsync(d_rows, 0, sizeof(ofdg_flow_stats_row) * (one_row ? 1 : (size_t)n_samples), st));
   const uint32_t plane_quads = (uint32_t)((size_t)W * H / 4);  // (W % 8 == 0: whole quads)
   const dim3 grid((plane_quads + kStatsQuads - 1) / kStatsQuads, (unsigned)std::min(n_samples, 65535));
-  const int kind = (half ? 3 : 0) + (d_occ ? (occ_fmt == OFDG_FMT_U8 ? 2 : 1) : 0);
   DevFlowStatsRow* const rows = reinterpret_cast<DevFlowStatsRow*>(d_rows);
   const float inv_bin = 1.0f / bin_px;
   const int vis = (flags & OFDG_STATS_VISIBLE_ONLY) ? 1 : 0, one = one_row ? 1 : 0;
-#define OFDG_STATS_LAUNCH(HALF, OCC)                                                                                               \
-  hipLaunchKernelGGL((flow_stats_kernel<HALF, OCC>), grid, dim3(kStatsThreads), 0, st, d_flow, d_occ, n_samples, plane_quads, bin_px, \
-                     inv_bin, vis, one, rows)
-  switch (kind) {
-    case 0: OFDG_STATS_LAUNCH(false, 0); break;
-    case 1: OFDG_STATS_LAUNCH(false, 1); break;
-    case 2: OFDG_STATS_LAUNCH(false, 2); break;
-    case 3: OFDG_STATS_LAUNCH(true, 0); break;
-    case 4: OFDG_STATS_LAUNCH(true, 1); break;
-    default: OFDG_STATS_LAUNCH(true, 2); break;
-  }
-#undef OFDG_STATS_LAUNCH
+  with_bool(flow_fmt == OFDG_FMT_F16, [&](auto half) {
+    with_occ_kind(d_occ, occ_fmt, [&](auto occ) {
+      hipLaunchKernelGGL((flow_stats_kernel<decltype(half)::value, decltype(occ)::value>), grid, dim3(kStatsThreads), 0, st, d_flow, d_occ,
+                         n_samples, plane_quads, bin_px, inv_bin, vis, one, rows);
+    });
+  });
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }
 int ofdg_flow_stats(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, float bin_px,
                     int flags, ofdg_flow_stats_row* d_rows, void* stream) {
   if (!c) return OFDG_EINVAL;
-  return flow_stats_on(c, "ofdg_flow_stats", c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
+  return flow_stats_on(PostOp{c, "ofdg_flow_stats"}, c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
 }
 int ofdg_flow_stats_sized(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int width, int height,
                           float bin_px, int flags, ofdg_flow_stats_row* d_rows, void* stream) {
   if (!c) return OFDG_EINVAL;
-  if (const char* why = plane_size_error(width, height)) { c->err = std::string("ofdg_flow_stats_sized: ") + why; return OFDG_EINVAL; }
-  return flow_stats_on(c, "ofdg_flow_stats_sized", width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
+  const PostOp op{c, "ofdg_flow_stats_sized"};
+  if (const char* why = plane_size_error(width, height)) return op.fail(why);
+  return flow_stats_on(op, width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, bin_px, flags, d_rows, stream);
 }
 
-// Flow pyramid of caller-given planes: one kernel on `stream`.  Like the statistics it reads nothing of the context's own, so
-// no completion bookkeeping is needed on any stream.
-static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && OFDG_PYR_MAX_LEVELS == kPyrMaxLevels &&
-              offsetof(struct ofdg_flow_pyramid, weight) == offsetof(DevFlowPyramid, weight) &&
-              offsetof(struct ofdg_flow_pyramid, levels) == offsetof(DevFlowPyramid, levels) &&
-              offsetof(struct ofdg_flow_pyramid, out_fmt) == offsetof(DevFlowPyramid, out_fmt) && OFDG_PYR_SCALE == 1,
-              "struct ofdg_flow_pyramid: the layout the kernel takes; flow_pyramid_arg_error spells the flag out");
-static int flow_pyramid_on(ofdg_ctx* c, const char* who, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt,
-                           int n_samples, int flags, const struct ofdg_flow_pyramid* pyr, void* stream) {
-  auto fail = [&](const std::string& why) { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; };
+// Flow pyramid of caller-given planes: one kernel on `stream`.
+static int flow_pyramid_on(const PostOp& op, int W, int H, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples,
+                           int flags, const struct ofdg_flow_pyramid* pyr, void* stream) {
+  ofdg_ctx* const c = op.c;
   const DevFlowPyramid* const out = reinterpret_cast<const DevFlowPyramid*>(pyr);
-  if (const char* why = flow_pyramid_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, flags, out)) return fail(why);
-  const bool half = flow_fmt == OFDG_FMT_F16, half_out = pyr->out_fmt == OFDG_FMT_F16;
-  if ((uintptr_t)d_flow & (half ? 7 : 15)) return fail(half ? "d_flow must be 8-byte aligned (binary16)" : "d_flow must be 16-byte aligned (float32)");
-  if (d_occ && ((uintptr_t)d_occ & (occ_fmt == OFDG_FMT_U8 ? 3 : 15)))
-    return fail(occ_fmt == OFDG_FMT_U8 ? "d_occ must be 4-byte aligned (uint8)" : "d_occ must be 16-byte aligned (float32)");
-  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
-  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+  if (const char* why = flow_pyramid_arg_error(d_flow, flow_fmt, d_occ, occ_fmt, n_samples, W, H, flags, out)) return op.fail(why);
+  OFDG_TRY(flow_planes_aligned(op, d_flow, flow_fmt, d_occ, occ_fmt));
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
   DevFlowPyramid arg = *out;
   for (int k = arg.levels; k < kPyrMaxLevels; ++k) arg.flow[k] = arg.weight[k] = nullptr;  // (never read: nothing of them travels)
   const dim3 grid((unsigned)((W + kPyrTile - 1) / kPyrTile), (unsigned)((H + kPyrTile - 1) / kPyrTile), (unsigned)std::min(n_samples, 65535));
-  const int kind = (half ? 6 : 0) + (half_out ? 3 : 0) + (d_occ ? (occ_fmt == OFDG_FMT_U8 ? 2 : 1) : 0);
   const int scaled = (flags & OFDG_PYR_SCALE) ? 1 : 0, n_weights = arg.weight[0] ? 1 : 0;
-#define OFDG_PYR_LAUNCH(HALF, HALF_OUT, OCC)                                                                                          \
-  hipLaunchKernelGGL((flow_pyramid_kernel<HALF, HALF_OUT, OCC>), grid, dim3(kPyrThreads), 0, st, d_flow, d_occ, n_samples, W, H, scaled, \
-                     n_weights, arg)
-  switch (kind) {
-    case 0: OFDG_PYR_LAUNCH(false, false, 0); break;
-    case 1: OFDG_PYR_LAUNCH(false, false, 1); break;
-    case 2: OFDG_PYR_LAUNCH(false, false, 2); break;
-    case 3: OFDG_PYR_LAUNCH(false, true, 0); break;
-    case 4: OFDG_PYR_LAUNCH(false, true, 1); break;
-    case 5: OFDG_PYR_LAUNCH(false, true, 2); break;
-    case 6: OFDG_PYR_LAUNCH(true, false, 0); break;
-    case 7: OFDG_PYR_LAUNCH(true, false, 1); break;
-    case 8: OFDG_PYR_LAUNCH(true, false, 2); break;
-    case 9: OFDG_PYR_LAUNCH(true, true, 0); break;
-    case 10: OFDG_PYR_LAUNCH(true, true, 1); break;
-    default: OFDG_PYR_LAUNCH(true, true, 2); break;
-  }
-#undef OFDG_PYR_LAUNCH
+  with_bool(flow_fmt == OFDG_FMT_F16, [&](auto half) {
+    with_bool(pyr->out_fmt == OFDG_FMT_F16, [&](auto half_out) {
+      with_occ_kind(d_occ, occ_fmt, [&](auto occ) {
+        hipLaunchKernelGGL((flow_pyramid_kernel<decltype(half)::value, decltype(half_out)::value, decltype(occ)::value>), grid, dim3(kPyrThreads), 0,
+                           st, d_flow, d_occ, n_samples, W, H, scaled, n_weights, arg);
+      });
+    });
+  });
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }
 int ofdg_flow_pyramid(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int flags,
                       const struct ofdg_flow_pyramid* pyr, void* stream) {
   if (!c) return OFDG_EINVAL;
-  return flow_pyramid_on(c, "ofdg_flow_pyramid", c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
+  return flow_pyramid_on(PostOp{c, "ofdg_flow_pyramid"}, c->prm.width, c->prm.height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
 }
 int ofdg_flow_pyramid_sized(ofdg_ctx* c, const void* d_flow, int flow_fmt, const void* d_occ, int occ_fmt, int n_samples, int width, int height,
                             int flags, const struct ofdg_flow_pyramid* pyr, void* stream) {
   if (!c) return OFDG_EINVAL;
-  if (const char* why = plane_size_error(width, height)) { c->err = std::string("ofdg_flow_pyramid_sized: ") + why; return OFDG_EINVAL; }
-  return flow_pyramid_on(c, "ofdg_flow_pyramid_sized", width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
+  const PostOp op{c, "ofdg_flow_pyramid_sized"};
+  if (const char* why = plane_size_error(width, height)) return op.fail(why);
+  return flow_pyramid_on(op, width, height, d_flow, flow_fmt, d_occ, occ_fmt, n_samples, flags, pyr, stream);
 }
 
-// Training crop of caller-given planes: one kernel on `stream` for every plane and sample.  Like the two reductions above it
-// reads nothing of the context's own, so no completion bookkeeping is needed on any stream.
-static_assert(sizeof(ofdg_crop_rec) == sizeof(DevCropRec) && sizeof(struct ofdg_crop_job) == sizeof(DevCropJob) && OFDG_CROP_PLANES == kCropPlanes &&
-              offsetof(struct ofdg_crop_job, dst) == offsetof(DevCropJob, dst) && offsetof(struct ofdg_crop_job, recs) == offsetof(DevCropJob, recs) &&
-              offsetof(struct ofdg_crop_job, recs_out) == offsetof(DevCropJob, recs_out) &&
-              offsetof(struct ofdg_crop_job, first_index) == offsetof(DevCropJob, first_index) &&
-              offsetof(struct ofdg_crop_job, seed) == offsetof(DevCropJob, seed) && offsetof(struct ofdg_crop_job, crop_w) == offsetof(DevCropJob, crop_w) &&
-              offsetof(struct ofdg_crop_job, occ_fmt) == offsetof(DevCropJob, occ_fmt) && offsetof(struct ofdg_crop_job, reserved) == 180,
-              "struct ofdg_crop_job: the layout the kernel takes");
-static_assert(OFDG_CROP_HFLIP == 1 && OFDG_CROP_VFLIP == 2 && OFDG_CROP_RANDOM_HFLIP == 4 && OFDG_CROP_RANDOM_VFLIP == 8 && OFDG_CROP_OCC_WINDOW == 16 &&
-              OFDG_CROP_FLOW == 2 && OFDG_CROP_OCC0 == 4 && OFDG_CROP_LABEL0 == 6, "crop_arg_error and crop_kernel spell these codes out");
+// Training crop of caller-given planes: one kernel on `stream` for every plane and sample.
 int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void* stream) {
   if (!c) return OFDG_EINVAL;
-  auto fail = [&](const std::string& why) { c->err = "ofdg_crop: " + why; return OFDG_EINVAL; };
+  const PostOp op{c, "ofdg_crop"};
   const int W = c->prm.width, H = c->prm.height;
   const DevCropJob* const j = reinterpret_cast<const DevCropJob*>(job);
-  if (const char* why = crop_arg_error(j, n_samples, W, H)) return fail(why);
+  if (const char* why = crop_arg_error(j, n_samples, W, H)) return op.fail(why);
   static const char* const kPlane[kCropPlanes] = {"image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1"};
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
-    const int es = crop_elem_bytes(*j, k), need = es == 4 ? 16 : es == 2 ? 8 : 4;
-    if ((uintptr_t)j->src[k] & (uintptr_t)(need - 1))
-      return fail(std::string("src[") + kPlane[k] + "] must be " + std::to_string(need) + "-byte aligned");
-    if ((uintptr_t)j->dst[k] & 15) return fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+    OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], crop_plane_fmt(*j, k), /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
   }
-  if ((uintptr_t)j->recs & 15) return fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return fail("recs_out must be 16-byte aligned");
-  if (stream == OFDG_STREAM_OWN && !c->last_ch) return fail("stream: OFDG_STREAM_OWN before any render / forward call on this context");
-  const hipStream_t st = stream == OFDG_STREAM_OWN ? c->last_stream : (hipStream_t)stream;
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
   DevCropGrid grid;
   uint32_t blocks = 0;
   for (int k = 0, slot = 0; k < kCropPlanes; ++k) {
@@ -1687,20 +1671,14 @@ int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void*
   }
   grid.first_block[kCropSlots] = blocks;
   const dim3 g(blocks, (unsigned)std::min(n_samples, 65535));
-  const int kind = (j->image_fmt == OFDG_FMT_U8 ? 4 : 0) + (j->flow_fmt == OFDG_FMT_F16 ? 2 : 0) + (j->occ_fmt == OFDG_FMT_U8 ? 1 : 0);
-#define OFDG_CROP_LAUNCH(IMAGE_U8, FLOW_HALF, OCC_U8) \
-  hipLaunchKernelGGL((crop_kernel<IMAGE_U8, FLOW_HALF, OCC_U8>), g, dim3(kCropThreads), 0, st, *j, grid, n_samples, W, H)
-  switch (kind) {
-    case 0: OFDG_CROP_LAUNCH(false, false, false); break;
-    case 1: OFDG_CROP_LAUNCH(false, false, true); break;
-    case 2: OFDG_CROP_LAUNCH(false, true, false); break;
-    case 3: OFDG_CROP_LAUNCH(false, true, true); break;
-    case 4: OFDG_CROP_LAUNCH(true, false, false); break;
-    case 5: OFDG_CROP_LAUNCH(true, false, true); break;
-    case 6: OFDG_CROP_LAUNCH(true, true, false); break;
-    default: OFDG_CROP_LAUNCH(true, true, true); break;
-  }
-#undef OFDG_CROP_LAUNCH
+  with_bool(j->image_fmt == OFDG_FMT_U8, [&](auto image_u8) {
+    with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto flow_half) {
+      with_bool(j->occ_fmt == OFDG_FMT_U8, [&](auto occ_u8) {
+        hipLaunchKernelGGL((crop_kernel<decltype(image_u8)::value, decltype(flow_half)::value, decltype(occ_u8)::value>), g, dim3(kCropThreads), 0,
+                           st, *j, grid, n_samples, W, H);
+      });
+    });
+  });
   HIP_OK(c, hipGetLastError());
   return OFDG_OK;
 }

@@ -2,7 +2,19 @@
 // compose).  Plain PODs shared by host code and HIP kernels.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "../../include/ofdg.h"  // the ABI: each Dev* record below that restates one of its structs is held to it next to its definition
+
+// Marks a function shared by host code and kernels (this header, realize.h): the pattern of OFDG_DM_FN
+// (include/ofdg_detmath.h); plain inline in a C++ translation unit.  always_inline: the device code then is what it was when
+// the device had copies of its own, written inline (profiles/shared_realize_device_code.txt).
+#if defined(__HIPCC__) || defined(__HIP__)
+#define OFDG_HD_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define OFDG_HD_FN inline
+#endif
 
 namespace ofdg {
 
@@ -107,8 +119,31 @@ struct DevObjectRow {
   int32_t box[2][4];  // [frame]{x0, y0, x1, y1}
   double motion[6];
 };
-static_assert(sizeof(DevObjectRow) == 96, "ofdg_object_row is 96 bytes without padding");
 constexpr int kObjectRows = kMaxFgObjects + 1;  // OFDG_MAX_OBJECT_ROWS: background + foreground objects
+static_assert(sizeof(ofdg_object_row) == sizeof(DevObjectRow) && sizeof(DevObjectRow) == 96 && offsetof(ofdg_object_row, area0) == offsetof(DevObjectRow, area) &&
+              offsetof(ofdg_object_row, box0) == offsetof(DevObjectRow, box) && offsetof(ofdg_object_row, box1) == offsetof(DevObjectRow, box) + 16 &&
+              offsetof(ofdg_object_row, motion) == offsetof(DevObjectRow, motion) && OFDG_MAX_OBJECT_ROWS == kObjectRows,
+              "ofdg_object_row: 96 bytes without padding, the layout the kernels write; background + kMaxFgObjects rows");
+
+// ---- Caller-given planes (ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop and their host twins) ------------------------------
+// The element types are the codes of include/ofdg.h: OFDG_FMT_F32, OFDG_FMT_U8, OFDG_FMT_F16.
+OFDG_HD_FN int fmt_elem_bytes(int fmt) { return fmt == OFDG_FMT_F32 ? 4 : fmt == OFDG_FMT_U8 ? 1 : 2; }
+inline const char* fmt_name(int fmt) { return fmt == OFDG_FMT_F32 ? "float32" : fmt == OFDG_FMT_U8 ? "uint8" : "binary16"; }
+// What the device entries ask of an input plane's base: a lane reads four elements at once (16, 4 or 8 bytes).
+inline int plane_alignment(int fmt) { return 4 * fmt_elem_bytes(fmt); }
+inline bool plane_misaligned(const void* p, int fmt) { return (uintptr_t)p & (uintptr_t)(plane_alignment(fmt) - 1); }
+// The rules of a flow with its optional occlusion map that the reductions share, in two parts (the entries have rules of
+// their own between them): the format codes, then the batch and the plane.  The first rule broken, or nullptr.
+inline const char* flow_occ_fmt_error(int flow_fmt, bool with_occ, int occ_fmt) {
+  if (flow_fmt != OFDG_FMT_F32 && flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (with_occ && occ_fmt != OFDG_FMT_F32 && occ_fmt != OFDG_FMT_U8) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  return nullptr;
+}
+inline const char* batch_plane_error(int n, int width, int height) {
+  if (n < 1) return "n_samples must be at least 1";
+  if (width < 1 || height < 1) return "width and height must be at least 1";
+  return nullptr;
+}
 
 // One row of the flow statistics (ofdg_flow_stats_row of include/ofdg.h, field for field): the kernel adds to the counts and
 // the Q8 sums with unsigned atomics (two's complement: the sums are int64 to the caller), so they are arrays here.
@@ -119,21 +154,21 @@ struct DevFlowStatsRow {
   unsigned long long sum_q8[3];   // sum_u_q8, sum_v_q8, sum_mag_q8
   unsigned long long max_key;
 };
-static_assert(sizeof(DevFlowStatsRow) == 304, "ofdg_flow_stats_row is 304 bytes without padding");
-// The argument rules ofdg_flow_stats and ofdg_host_flow_stats share (format codes and flag bits are those of include/ofdg.h:
-// float32 0, uint8 1, binary16 2; ACCUMULATE 1, VISIBLE_ONLY 2, ONE_ROW 4): the first rule broken, or nullptr.
+static_assert(sizeof(ofdg_flow_stats_row) == sizeof(DevFlowStatsRow) && sizeof(DevFlowStatsRow) == 304 && OFDG_FLOW_HIST_BINS == kFlowHistBins &&
+              offsetof(ofdg_flow_stats_row, n_counted) == offsetof(DevFlowStatsRow, count) && offsetof(ofdg_flow_stats_row, sum_u_q8) == offsetof(DevFlowStatsRow, sum_q8) &&
+              offsetof(ofdg_flow_stats_row, max_key) == offsetof(DevFlowStatsRow, max_key) && offsetof(DevFlowStatsRow, max_key) == 296,
+              "ofdg_flow_stats_row: 304 bytes without padding, the layout the kernel adds to");
+// The argument rules ofdg_flow_stats and ofdg_host_flow_stats share: the first rule broken, or nullptr.
 inline const char* flow_stats_arg_error(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
                                         float bin_px, int flags, const void* rows) {
   if (!flow) return "d_flow is NULL";
   if (!rows) return "d_rows is NULL";
-  if (flow_fmt != 0 && flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
-  if (occ && occ_fmt != 0 && occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (n < 1) return "n_samples must be at least 1";
-  if (width < 1 || height < 1) return "width and height must be at least 1";
+  if (const char* why = flow_occ_fmt_error(flow_fmt, occ != nullptr, occ_fmt)) return why;
+  if (const char* why = batch_plane_error(n, width, height)) return why;
   if (!(bin_px >= 0.0009765625f && bin_px <= 16384.0f)) return "bin_px must lie in [2^-10, 2^14]";
-  if (flags & ~7) return "flags holds unknown bits";
-  if ((flags & 2) && !occ) return "flags: OFDG_STATS_VISIBLE_ONLY needs d_occ";
-  if ((flags & 4) && (unsigned long long)n * (unsigned long long)width * (unsigned long long)height >= (1ull << 32))
+  if (flags & ~(OFDG_STATS_ACCUMULATE | OFDG_STATS_VISIBLE_ONLY | OFDG_STATS_ONE_ROW)) return "flags holds unknown bits";
+  if ((flags & OFDG_STATS_VISIBLE_ONLY) && !occ) return "flags: OFDG_STATS_VISIBLE_ONLY needs d_occ";
+  if ((flags & OFDG_STATS_ONE_ROW) && (unsigned long long)n * (unsigned long long)width * (unsigned long long)height >= (1ull << 32))
     return "flags: OFDG_STATS_ONE_ROW needs n*H*W below 2^32";
   if ((uintptr_t)rows & 7) return "d_rows must be 8-byte aligned";
   return nullptr;
@@ -147,19 +182,20 @@ struct DevFlowPyramid {
   void* weight[kPyrMaxLevels];
   int32_t levels, out_fmt;
 };
-static_assert(sizeof(DevFlowPyramid) == 104, "struct ofdg_flow_pyramid is 104 bytes");
-// The argument rules ofdg_flow_pyramid and ofdg_host_flow_pyramid share (format codes as above; OFDG_PYR_SCALE 1): the first
-// rule broken, or nullptr.  The planes of the input are aligned by the device entry only.
+static_assert(sizeof(struct ofdg_flow_pyramid) == sizeof(DevFlowPyramid) && sizeof(DevFlowPyramid) == 104 && OFDG_PYR_MAX_LEVELS == kPyrMaxLevels &&
+              offsetof(struct ofdg_flow_pyramid, weight) == offsetof(DevFlowPyramid, weight) && offsetof(struct ofdg_flow_pyramid, levels) == offsetof(DevFlowPyramid, levels) &&
+              offsetof(struct ofdg_flow_pyramid, out_fmt) == offsetof(DevFlowPyramid, out_fmt) && offsetof(DevFlowPyramid, out_fmt) == 100,
+              "struct ofdg_flow_pyramid: 104 bytes, the layout the kernel takes");
+// The argument rules ofdg_flow_pyramid and ofdg_host_flow_pyramid share: the first rule broken, or nullptr.  The planes of
+// the input are aligned by the device entry only.
 inline const char* flow_pyramid_arg_error(const void* flow, int flow_fmt, const void* occ, int occ_fmt, int n, int width, int height,
                                           int flags, const DevFlowPyramid* pyr) {
   if (!flow) return "d_flow is NULL";
   if (!pyr) return "pyr is NULL";
-  if (flow_fmt != 0 && flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
-  if (occ && occ_fmt != 0 && occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (pyr->out_fmt != 0 && pyr->out_fmt != 2) return "pyr->out_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
-  if (n < 1) return "n_samples must be at least 1";
-  if (width < 1 || height < 1) return "width and height must be at least 1";
-  if (flags & ~1) return "flags holds unknown bits";
+  if (const char* why = flow_occ_fmt_error(flow_fmt, occ != nullptr, occ_fmt)) return why;
+  if (pyr->out_fmt != OFDG_FMT_F32 && pyr->out_fmt != OFDG_FMT_F16) return "pyr->out_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (const char* why = batch_plane_error(n, width, height)) return why;
+  if (flags & ~OFDG_PYR_SCALE) return "flags holds unknown bits";
   if (pyr->levels < 1 || pyr->levels > kPyrMaxLevels) return "pyr->levels must lie in 1..6";
   const int cell = 1 << pyr->levels;
   if (width % cell || height % cell) return "pyr->levels: width and height must be multiples of 2^levels";
@@ -184,12 +220,7 @@ inline const char* plane_size_error(int width, int height) {
 
 // ---- Training crop (ofdg_crop, include/ofdg.h) -----------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
-// sanitising, the window test of the occlusion rule and the argument rules.  OFDG_HD_FN as in realize.h (the same tokens).
-#if defined(__HIPCC__) || defined(__HIP__)
-#define OFDG_HD_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define OFDG_HD_FN inline
-#endif
+// sanitising, the window test of the occlusion rule and the argument rules.
 constexpr int kCropPlanes = 8;  // OFDG_CROP_PLANES: image0, image1, flow, flow1, occ0, occ1, label0, label1
 struct DevCropRec {
   int32_t x0, y0, flags, reserved;
@@ -203,13 +234,19 @@ struct DevCropJob {  // struct ofdg_crop_job, field for field
   uint32_t seed;
   int32_t crop_w, crop_h, flags, image_fmt, flow_fmt, occ_fmt, reserved;
 };
-static_assert(sizeof(DevCropRec) == 16 && sizeof(DevCropJob) == 184, "ofdg_crop_rec is 16 bytes, struct ofdg_crop_job 184");
+static_assert(sizeof(ofdg_crop_rec) == sizeof(DevCropRec) && sizeof(DevCropRec) == 16 && sizeof(struct ofdg_crop_job) == sizeof(DevCropJob) &&
+              sizeof(DevCropJob) == 184 && OFDG_CROP_PLANES == kCropPlanes && offsetof(struct ofdg_crop_job, dst) == offsetof(DevCropJob, dst) &&
+              offsetof(struct ofdg_crop_job, recs) == offsetof(DevCropJob, recs) && offsetof(struct ofdg_crop_job, recs_out) == offsetof(DevCropJob, recs_out) &&
+              offsetof(struct ofdg_crop_job, first_index) == offsetof(DevCropJob, first_index) && offsetof(struct ofdg_crop_job, seed) == offsetof(DevCropJob, seed) &&
+              offsetof(struct ofdg_crop_job, crop_w) == offsetof(DevCropJob, crop_w) && offsetof(struct ofdg_crop_job, occ_fmt) == offsetof(DevCropJob, occ_fmt) &&
+              offsetof(struct ofdg_crop_job, reserved) == offsetof(DevCropJob, reserved) && offsetof(DevCropJob, reserved) == 180,
+              "ofdg_crop_rec: 16 bytes; struct ofdg_crop_job: 184 bytes, the layout the kernel takes");
+static_assert(OFDG_CROP_HFLIP == 1 && OFDG_CROP_VFLIP == 2 && OFDG_CROP_RANDOM_HFLIP == 4 && OFDG_CROP_RANDOM_VFLIP == 8 && OFDG_CROP_FLOW == 2 &&
+              OFDG_CROP_OCC0 == 4 && OFDG_CROP_LABEL0 == 6, "crop_draw_rec, crop_sanitise, crop_channels and crop_kernel spell these codes out");
 OFDG_HD_FN int crop_channels(int plane) { return plane < 2 ? 3 : plane < 4 ? 2 : 1; }
-// bytes of an element of plane k (format codes of include/ofdg.h: float32 0, uint8 1, binary16 2; labels are uint8)
-OFDG_HD_FN int crop_elem_bytes(const DevCropJob& j, int plane) {
-  const int fmt = plane < 2 ? j.image_fmt : plane < 4 ? j.flow_fmt : plane < 6 ? j.occ_fmt : 1;
-  return fmt == 0 ? 4 : fmt == 1 ? 1 : 2;
-}
+// the element type of plane k (the labels are uint8) and its bytes
+OFDG_HD_FN int crop_plane_fmt(const DevCropJob& j, int plane) { return plane < 2 ? j.image_fmt : plane < 4 ? j.flow_fmt : plane < 6 ? j.occ_fmt : OFDG_FMT_U8; }
+OFDG_HD_FN int crop_elem_bytes(const DevCropJob& j, int plane) { return fmt_elem_bytes(crop_plane_fmt(j, plane)); }
 
 // Philox4x32-10 (Salmon et al., SC'11), the function of csrc/sampler_counter.hip restated for host and device.  The sampler's
 // own device copy stays as it is; this one is held to the three published known answers through ofdg_crop_philox
@@ -255,19 +292,18 @@ OFDG_HD_FN bool crop_target_inside(int at, float d, int lo, int len) {
   const float t = floorf(h);
   return t >= (float)lo && t <= (float)(lo + len - 1);
 }
-// The argument rules ofdg_crop and ofdg_host_crop share (flag bits: RANDOM_HFLIP 4, RANDOM_VFLIP 8, OCC_WINDOW 16): the first
-// rule broken, or nullptr.  Alignment is asked by the device entry only.
+// The argument rules ofdg_crop and ofdg_host_crop share: the first rule broken, or nullptr.  Alignment is asked by the device
+// entry only.
 inline const char* crop_arg_error(const DevCropJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (n < 1) return "n_samples must be at least 1";
   if (j->crop_w < 8 || j->crop_w > width || (j->crop_w % 8) != 0) return "crop_w must be a multiple of 8 in [8, width]";
   if (j->crop_h < 2 || j->crop_h > height || (j->crop_h % 2) != 0) return "crop_h must be even and in [2, height]";
   if ((unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "width * height must be below 2^31";
-  if (j->flags & ~(4 | 8 | 16)) return "flags holds unknown bits";
+  if (j->flags & ~(OFDG_CROP_RANDOM_HFLIP | OFDG_CROP_RANDOM_VFLIP | OFDG_CROP_OCC_WINDOW)) return "flags holds unknown bits";
   if (j->reserved != 0) return "reserved must be 0";
-  if (j->image_fmt != 0 && j->image_fmt != 1) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->flow_fmt != 0 && j->flow_fmt != 2) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
-  if (j->occ_fmt != 0 && j->occ_fmt != 1) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->image_fmt != OFDG_FMT_F32 && j->image_fmt != OFDG_FMT_U8) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = flow_occ_fmt_error(j->flow_fmt, true, j->occ_fmt)) return why;  // (the job's occ_fmt is checked with or without a map)
   int planes = 0;
   for (int k = 0; k < kCropPlanes; ++k) {
     if (j->src[k] && !j->dst[k]) return "dst: a plane has a source and no destination";
@@ -275,8 +311,8 @@ inline const char* crop_arg_error(const DevCropJob* j, int n, int width, int hei
     planes += j->src[k] ? 1 : 0;
   }
   if (!planes) return "src: no plane is set";
-  if ((j->flags & 16) && j->src[4] && !j->src[2]) return "flags: OFDG_CROP_OCC_WINDOW with occ0 needs flow";
-  if ((j->flags & 16) && j->src[5] && !j->src[3]) return "flags: OFDG_CROP_OCC_WINDOW with occ1 needs flow1";
+  if ((j->flags & OFDG_CROP_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_CROP_OCC_WINDOW with occ0 needs flow";
+  if ((j->flags & OFDG_CROP_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_CROP_OCC_WINDOW with occ1 needs flow1";
   // no in-place form: a destination range may meet no other range of the job
   struct Range { uintptr_t lo, hi; bool dst; };
   Range r[2 * kCropPlanes + 2];

@@ -1,6 +1,6 @@
 // Host "realize" step: blueprints -> device records (fp64 affines in the
 // reference's operation order, texture placement, z-order), and the pieces it
-// shares with the device realize (OFDG_HD_FN below).
+// shares with the device realize (OFDG_HD_FN of ofdg_device.h).
 //
 // Mirrors DataGenerator::RealizeObjectBlueprint and the object set-up half of
 // Process_TaskBucket (reference src/caffe/DataGenerator.cpp:1065-1173, 1183-1211)
@@ -13,16 +13,7 @@
 #include <vector>
 
 #include "../../include/ofdg.h"
-#include "ofdg_device.h"
-
-// Marks a function shared by the host realize and the device realize (sampler_counter.hip, kernels.hip): the pattern of
-// OFDG_DM_FN (include/ofdg_detmath.h); plain inline in a C++ translation unit.  always_inline: the device code then is
-// what it was when the device had copies of its own, written inline (profiles/shared_realize_device_code.txt).
-#if defined(__HIPCC__) || defined(__HIP__)
-#define OFDG_HD_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define OFDG_HD_FN inline
-#endif
+#include "ofdg_device.h"  // (OFDG_HD_FN too)
 
 namespace ofdg {
 

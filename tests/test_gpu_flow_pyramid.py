@@ -231,6 +231,28 @@ def test_flowloader_pyramid(ofdg):
         assert occ.any()
 
 
+def test_flowloader_statistics_and_pyramid_of_the_uncropped_batch(ofdg):
+    """stats=True with pyramid=3 and no crop=: both reductions of a set are enqueued by one method of the loader (the cropped
+    form is tests/test_gpu_crop.py::test_flowloader_crop); each against its host twin, the batch what a plain loader yields."""
+    import torch
+    import flow_stats_reference as fsr
+    W, H, B = 128, 96, 2
+    kw = dict(width=W, height=H, mode=7, batch_size=B, sampler=1, seed=21)
+    pool = lambda g: g.pool_synthetic(3, 2 * W, 2 * H, 11)  # noqa: E731
+    it = iter(ofdg.FlowLoader(ofdg.default_params(**kw), pool=pool, prefetch=3, extras=("occ0",), stats=True, pyramid=3))
+    pit = iter(ofdg.FlowLoader(ofdg.default_params(**kw), pool=pool, prefetch=3, extras=("occ0",)))
+    for _ in range(2):
+        i0, i1, fl, more = next(it)
+        p = next(pit)
+        torch.cuda.current_stream().synchronize()
+        assert set(more) == {"occ0", "flow_stats", "flow_pyramid"} and len(more["flow_pyramid"]) == 3
+        assert torch.equal(i0, p[0]) and torch.equal(i1, p[1]) and torch.equal(fl, p[2]) and torch.equal(more["occ0"], p[3]["occ0"])
+        flow, occ = fl.cpu().numpy(), more["occ0"].cpu().numpy()
+        fpr.expect_equal(host_arrays(more["flow_pyramid"]), ofdg.host_flow_pyramid(flow, 3, occ))
+        assert ofdg.flow_stats_numpy(more["flow_stats"])["rows"].tobytes() == ofdg.host_flow_stats(flow, occ, 2.0).tobytes()
+        fsr.expect_equal(ofdg.flow_stats_numpy(more["flow_stats"])["rows"], fsr.flow_stats(flow, occ, 2.0))
+
+
 def test_refusals_enqueue_nothing(ofdg):
     import torch
     W, H, B, L = 128, 96, 2, 3

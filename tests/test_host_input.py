@@ -114,6 +114,12 @@ def run_san(program, mode, d):
     return r.stdout.split("\n")[:-1]
 
 
+def test_host_twins_read_planes_at_an_odd_address_under_the_sanitizers(san_program, tmp_path):
+    """ofdg_host_flow_stats, ofdg_host_flow_pyramid and ofdg_host_crop ask no alignment of their inputs: a binary16 flow and a
+    float32 map one byte off give the bytes of the aligned planes, with no ASan / UBSan report (exit 0)."""
+    assert run_san(san_program, "planes", tmp_path)[-1].endswith("odd=same")
+
+
 def test_sanitizer_build_agrees_with_the_library_and_survives_the_mutations(ofdg, san_program, tmp_path):
     """Two builds of one source agree: every line of `check` equals what libofdg.so answers through ctypes; `mutate` ends with
     exit 0 (no ASan / UBSan report, no escaped exception) and refuses most, not all, of what it made."""

@@ -7,7 +7,7 @@ root="$(cd "$(dirname "$0")/.." && pwd)"
 pkg=optical-flow-2d-data-generation_amd
 tmp=${TMPDIR:-/tmp}/ofdg_rev_$name   # (outside the package: the snapshot that travels to the GPU box holds no second copy of the sources)
 rm -rf $tmp; mkdir -p $tmp
-git -C $root archive $rev $pkg/csrc include | tar -x -C $tmp
+git -C $root archive $rev $pkg/csrc $pkg/__init__.py include | tar -x -C $tmp   # (__init__.py: $tmp is a root the revision's package imports from)
 cd $tmp/$pkg
 objs=""
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -Wno-pass-failed -mllvm -amdgpu-kernarg-preload-count=16 -c csrc/ofdg_api.hip -o ofdg_api.o

@@ -10,6 +10,9 @@
 //                                         b  at every offset of the first kWindow bytes, each byte of kBytes
 //                                         p  every decimal field of a PPM header replaced by each of kNumbers
 //                                         c  every PNG chunk length replaced by 0, its value - 1, + 1, 0x7fffffff, 0xffffffff
+//   host_input_check planes             ofdg_host_flow_stats, ofdg_host_flow_pyramid and ofdg_host_crop on a binary16 flow and a
+//                                       float32 occlusion map that start at an ODD address (the twins ask no alignment of
+//                                       their inputs), against the same planes at an aligned one
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -174,11 +177,92 @@ int mutate(const char* dir, bool verbose) {
   std::printf("cases=%lld refused: probe=%lld decode=%lld parser=%lld\n", t.cases, t.probe_refused, t.decode_refused, t.parser_refused);
   return ok ? 0 : 1;
 }
+
+// a copy of `bytes` that starts one byte behind an allocation's (aligned) start
+struct OddCopy {
+  std::vector<uint8_t> raw;
+  explicit OddCopy(const std::vector<uint8_t>& bytes) : raw(bytes.size() + 1) { std::memcpy(raw.data() + 1, bytes.data(), bytes.size()); }
+  const void* p() const { return raw.data() + 1; }
+};
+int planes() {
+  const int n = 2, W = 16, H = 8, cw = 8, ch = 4, levels = 2;
+  const size_t px = (size_t)W * H;
+  std::vector<uint16_t> flow(n * 2 * px);
+  std::vector<float> occ(n * px);
+  uint32_t x = 12345u;
+  for (uint16_t& h : flow) {  // finite halves of either sign, 2^-5 .. 2^5 (some targets leave the window), and a few zeros
+    x = x * 1664525u + 1013904223u;
+    h = (x >> 28) == 0 ? 0 : (uint16_t)(((x >> 16) & 0x8000u) | ((10u + (x >> 20) % 11u) << 10) | ((x >> 8) & 0x3FFu));
+  }
+  for (float& f : occ) {
+    x = x * 1664525u + 1013904223u;
+    f = (x >> 30) == 0 ? 1.0f : 0.0f;
+  }
+  std::vector<uint8_t> flow_bytes(flow.size() * 2), occ_bytes(occ.size() * 4);
+  std::memcpy(flow_bytes.data(), flow.data(), flow_bytes.size());
+  std::memcpy(occ_bytes.data(), occ.data(), occ_bytes.size());
+  const OddCopy flow_odd(flow_bytes), occ_odd(occ_bytes);
+  bool ok = true;
+  unsigned long long sums[3] = {0, 0, 0};
+  std::vector<uint8_t> first[3];
+  for (int odd = 0; odd < 2; ++odd) {
+    const void* const fp = odd ? flow_odd.p() : (const void*)flow.data();
+    const void* const op = odd ? occ_odd.p() : (const void*)occ.data();
+    std::vector<uint8_t> got[3];
+    std::vector<ofdg_flow_stats_row> rows(n);
+    int rc = ofdg_host_flow_stats(fp, OFDG_FMT_F16, op, OFDG_FMT_F32, n, W, H, 2.0f, 0, rows.data());
+    if (rc) { std::printf("planes: flow_stats rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+    got[0].assign((const uint8_t*)rows.data(), (const uint8_t*)(rows.data() + n));
+    std::vector<uint16_t> lv[2], wt[2];
+    struct ofdg_flow_pyramid pyr;
+    std::memset(&pyr, 0, sizeof pyr);
+    pyr.levels = levels;
+    pyr.out_fmt = OFDG_FMT_F16;
+    for (int k = 0; k < levels; ++k) {
+      lv[k].assign((size_t)n * 2 * (px >> (2 * k + 2)) + 8, 0);  // (+ 8: room to start at a 16-byte boundary)
+      wt[k].assign((size_t)n * (px >> (2 * k + 2)), 0);
+      pyr.flow[k] = lv[k].data() + ((16 - ((uintptr_t)lv[k].data() & 15)) & 15) / 2;
+      pyr.weight[k] = wt[k].data();
+    }
+    rc = ofdg_host_flow_pyramid(fp, OFDG_FMT_F16, op, OFDG_FMT_F32, n, W, H, OFDG_PYR_SCALE, &pyr);
+    if (rc) { std::printf("planes: flow_pyramid rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+    for (int k = 0; k < levels; ++k) {
+      const size_t cells = (size_t)n * (px >> (2 * k + 2));
+      got[1].insert(got[1].end(), (const uint8_t*)pyr.flow[k], (const uint8_t*)pyr.flow[k] + cells * 4);
+      got[1].insert(got[1].end(), (const uint8_t*)wt[k].data(), (const uint8_t*)(wt[k].data() + cells));
+    }
+    std::vector<uint8_t> cflow((size_t)n * 2 * cw * ch * 2), cocc((size_t)n * cw * ch * 4), recs((size_t)n * 16);
+    struct ofdg_crop_job job;
+    std::memset(&job, 0, sizeof job);
+    job.src[OFDG_CROP_FLOW] = fp;
+    job.dst[OFDG_CROP_FLOW] = cflow.data();
+    job.src[OFDG_CROP_OCC0] = op;
+    job.dst[OFDG_CROP_OCC0] = cocc.data();
+    job.recs_out = (ofdg_crop_rec*)recs.data();
+    job.seed = 7;
+    job.crop_w = cw;
+    job.crop_h = ch;
+    job.flags = OFDG_CROP_RANDOM_HFLIP | OFDG_CROP_RANDOM_VFLIP | OFDG_CROP_OCC_WINDOW;
+    job.flow_fmt = OFDG_FMT_F16;
+    rc = ofdg_host_crop(&job, n, W, H);
+    if (rc) { std::printf("planes: crop rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+    got[2] = cflow;
+    got[2].insert(got[2].end(), cocc.begin(), cocc.end());
+    got[2].insert(got[2].end(), recs.begin(), recs.end());
+    for (int e = 0; e < 3; ++e) {
+      if (!odd) { first[e] = got[e]; sums[e] = fnv1a(got[e].data(), got[e].size()); }
+      else if (got[e] != first[e]) { std::printf("planes: entry %d differs between the aligned and the odd planes\n", e); ok = false; }
+    }
+  }
+  std::printf("planes stats=%016llx pyramid=%016llx crop=%016llx odd=%s\n", sums[0], sums[1], sums[2], ok ? "same" : "DIFFERENT");
+  return ok ? 0 : 1;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v]\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes\n", argv[0]);
   return 2;
 }
