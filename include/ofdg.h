@@ -573,6 +573,91 @@ int ofdg_crop_draw(uint32_t seed, long long index, int width, int height, int cr
  * the kernel share, exposed so that it can be held to the published known answers.  OFDG_EINVAL for a NULL pointer. */
 int ofdg_crop_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 
+/*
+ * Photometric augmentation: gamma, contrast, brightness, per-channel colour gain and additive noise on image0 and image1 of
+ * a batch, each sample by a record of its own and frame 1 slightly apart from frame 0, in ONE launch behind the call that
+ * wrote the frames.  The record is a pure function of (seed, global sample index), the noise of (seed, global sample index,
+ * frame, element), so a resumed or sharded run makes the same pixels.  Everything below is exact: the kernel, ofdg_host_photo
+ * and the numpy restatement of the tests give the same bits.  float32 and fp64 operations are IEEE, each rounded on its own
+ * (no contraction); fl32(.) marks a float32 rounding where the text would otherwise leave it open.
+ *
+ * Planes: src[f] is image f as [n,3,height,width] of src_fmt, dst[f] the same shape of dst_fmt; OFDG_FMT_F32 or OFDG_FMT_U8,
+ * chosen independently.  A frame is optional on its own (src[f] and dst[f] both NULL).  width = height = 0: the context's
+ * frame; otherwise any size the context's rule allows (width a multiple of 8 and at least 8, height even and at least 2) - the
+ * frames ofdg_crop wrote, for one.  dst[f] == src[f] with src_fmt == dst_fmt is the in-place form.  The float32 frames of the
+ * render / forward calls hold the blended BYTE values (compose blends in integers and stores (float)byte; the uint8 format
+ * stores "the byte itself - the value whose float is what the plain call stores"), so both element types name a table index.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_photo_draw(seed, first_index + i, the job's ranges).  Either way
+ * it is sanitised before use, and the sanitised record is what recs_out[i] receives.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g,
+ *    {seed ^ (uint32)(g >> 32) * 0x9E3779B9, (uint32)g}, blocks j = 0, 1, 2 at the counters {j, 0, 0x0c71, 0} (the sampler's
+ *    third counter word is 0x0fd9, the crop's 0x0c70).  u(w) = (float)(w >> 8) * 2^-24 (exact);  sym(w, a) = fl32(a *
+ *    fl32(fl32(2 u(w)) - 1)), and a zero of either sign counts as +0.
+ *      block 0:  lg0 = sym(.x, gamma_log)   lc0 = sym(.y, contrast_log)   b0 = sym(.z, brightness)   sigma = fl32(sigma_max * u(.w))
+ *      block 1:  lB = sym(.x, colour_log)   lG = sym(.y, colour_log)      lR = sym(.z, colour_log)
+ *      block 2:  dg = sym(.x, pair_gamma_log)  dc = sym(.y, pair_contrast_log)  db = sym(.z, pair_brightness)  dcol = sym(.w, pair_colour_log)
+ *    Frame 1: lg1 = fl32(lg0 + dg), lc1 = fl32(lc0 + dc), b1 = fl32(b0 + db), and dcol is added to each of lB, lG, lR.  Every
+ *    logarithm l becomes (float)EXP((double)l) - EXP and LOG: ofdg_det_exp, ofdg_det_log of include/ofdg_detmath.h -: gamma[f], contrast[f], gain[f][c];
+ *    brightness[f] = b_f; sigma[1] = sigma[0] = sigma.  All ranges 0 give the identity record: gamma, contrast, gain 1.0f,
+ *    brightness, sigma +0.
+ * 2. Sanitise, field by field:  x is NaN ? identity : x < lo ? lo : x > hi ? hi : x  with  gamma [1/8, 8] identity 1,
+ *    contrast [0, 4] identity 1, gain [0, 8] identity 1, brightness [-1, 1] identity 0, sigma [0, 64] identity 0; an infinity
+ *    lands on a bound, -0.0 stays.  reserved = 0.  No record makes the kernel read or write outside a plane.
+ * 3. Table, in fp64, for frame f, channel c (B, G, R) and k = 0..255:  x = k / 255.0;  p = 0 for k = 0, p = x for gamma[f] ==
+ *    1.0f, else p = EXP((double)gamma[f] * LOG(x));  t = 255.0 * ((((p * gain[f][c]) - 0.5) * contrast[f] + 0.5)
+ *    + brightness[f]), the float32 fields widened, evaluated in that order, six roundings;  t = t > 0 ? t : 0, then t = t < 255
+ *    ? t : 255;  T[f][c][k] = (float)t.  The identity record gives T[f][c][k] = k.
+ * 4. Pixel (y, x) of channel c of frame f of sample i.  k: the uint8 element; for float32 the element e with e = e > 0 ? e : 0
+ *    (a NaN becomes 0), e = e < 255 ? e : 255, k = (int)rintf(e) (ties to even).  v = T[f][c][k].  Where sigma[f] > 0: with the
+ *    element number m = (c * height + y) * width + x, w = word (m & 3) of the Philox block under the sample's key at the counter
+ *    {m >> 2, f, 0x0c72, 0}, s = the sum of w's four bytes (0..1020, mean 510, variance 4 * (256^2 - 1) / 12 = 147.80054^2):
+ *    v = fl32(v + fl32(fl32(sigma[f] / 147.80054f) * (float)(s - 510))), then v = v > 0 ? v : 0, v = v < 255 ? v : 255 - an
+ *    Irwin-Hall normal of unit variance in 1021 levels, made of integers only.  sigma[f] == 0 draws nothing and leaves v as it
+ *    is.  Output: float32 stores v, uint8 stores rintf(v) (ties to even).
+ *
+ * Asynchronous on `stream`, the stream the frames were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel for any
+ * n_samples, both frames and all channels, no atomics, no table in global memory; it reads no record of the context.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, one of width /
+ * height 0 or a size that breaks the rule above, 3 * width * height of 2^32 and more, another format code, non-zero flags or
+ * reserved, a range that is negative, NaN or infinite, no frame set, src[f] without dst[f] or the reverse, a misaligned pointer
+ * (sources as the render calls ask: 16-byte float32, 4-byte uint8; destinations and both record arrays 16-byte), a destination
+ * range (recs_out included) that overlaps any other range of the job - but for dst[f] == src[f] with src_fmt == dst_fmt -,
+ * OFDG_STREAM_OWN before any render / forward call on the context.
+ */
+typedef struct ofdg_photo_rec {          /* 64 bytes; index [f] = frame 0 / 1, gain[f][c] c = B,G,R */
+  float gamma[2], contrast[2], brightness[2], gain[2][3], sigma[2];
+  int32_t reserved[2];
+} ofdg_photo_rec;
+struct ofdg_photo_job {
+  const void* src[2]; void* dst[2];      /* image0, image1: [n,3,height,width]; each frame optional (src and dst both NULL) */
+  const ofdg_photo_rec* recs;            /* DEVICE, n records, or NULL: drawn */
+  ofdg_photo_rec*       recs_out;        /* DEVICE, n records, or NULL */
+  long long first_index; uint32_t seed;
+  int32_t width, height;                 /* 0, 0: the context's frame */
+  int32_t src_fmt, dst_fmt;              /* OFDG_FMT_F32 or OFDG_FMT_U8, independently */
+  int32_t flags, reserved;               /* no flag yet: both must be 0 */
+  float gamma_log, contrast_log, brightness, colour_log, sigma_max;                 /* ranges of the draw, all >= 0 */
+  float pair_gamma_log, pair_contrast_log, pair_brightness, pair_colour_log;        /* frame 1 against frame 0 */
+};
+int ofdg_photo(ofdg_ctx* ctx, const struct ofdg_photo_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes [n,3,height,width], records in host memory, no
+ * alignment asked of any pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_photo(const struct ofdg_photo_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (step 1 alone: not sanitised; pure, no GPU).  Of `ranges` only the nine ranges are
+ * read.  OFDG_EINVAL (ofdg_host_last_error) for a NULL pointer or a range that is negative, NaN or infinite. */
+int ofdg_photo_draw(uint32_t seed, long long index, const struct ofdg_photo_job* ranges, ofdg_photo_rec* out);
+/* The table [2][3][256] (frame, channel, k) of a HOST record after sanitising: as the DEVICE computes it (one small launch, waited
+ * for), and as the host does.  Bit for bit the same.  OFDG_EINVAL for a NULL pointer. */
+int ofdg_debug_photo_table(ofdg_ctx* ctx, const ofdg_photo_rec* rec_host, float* table_host);
+int ofdg_host_photo_table(const ofdg_photo_rec* rec, float* table);
+/* The function ofdg_det_log of include/ofdg_detmath.h on n numbers as this library was compiled (pure, no GPU): what the table's gamma is
+ * made of, exposed so that its stated error bound can be held to libm.  OFDG_EINVAL for a NULL pointer or n < 0. */
+int ofdg_host_det_log(const double* x, int n, double* log_out);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -13,6 +13,9 @@
  * host.  Accuracy: < 1 ULP (sin, cos; checked against libm in tests/test_host_logic.py), expf is the
  * fp64 result rounded once (equal to the correctly rounded float except within 2^-50 of a tie).
  *
+ * ofdg_det_log (the gamma tables of ofdg_photo are defined with it) adds one IEEE fp64 division, which is correctly rounded
+ * on both sides as well; its bound is stated where it is defined and held to libm in tests/test_photo.py.
+ *
  * Algorithms: Cody-Waite three-part pi/2 reduction + the classical degree-13/14 minimax kernels on
  * [-pi/4, pi/4] (fdlibm's k_sin / k_cos coefficients); exp by ln2 reduction + degree-11 Taylor-minimax.
  */
@@ -116,5 +119,49 @@ OFDG_DM_FN double ofdg_det_exp(double x) {
 }
 /* expf as the reference's Gaussian supports use it: the fp64 value rounded once to float. */
 OFDG_DM_FN float ofdg_det_expf(float x) { return (float)ofdg_det_exp((double)x); }
+
+/* log(x) in fp64 for finite x > 0 (subnormals included), relative error < 2^-50; -inf for +-0, NaN below 0 and for NaN, +inf
+ * for +inf.  The exponent is split off, x = 2^e * m with m in [sqrt(1/2), sqrt(2)), and with s = (m - 1) / (m + 1) - the one
+ * IEEE division; m - 1 is exact - log(m) = 2 s (1 + z/3 + z^2/5 + ... + z^11/23), z = s^2 <= 0.02944 (the first term left out
+ * is below 2^-60 of the sum).  log(x) = e * ln2_hi + (e * ln2_lo + log(m)): e * ln2_hi is exact (33 x 11 bits), and for e != 0
+ * the sum is at least 0.34 in size, so nothing cancels.  Error: s carries two roundings, the Horner chain about one, the
+ * products and sums behind it two more - under 3 ulp, stated as 2^-50; tests/test_photo.py holds it to libm. */
+OFDG_DM_FN double ofdg_det_log(double x) {
+  const double ln2_hi = 6.93147180369123816490e-01; /* 33 bits */
+  const double ln2_lo = 1.90821492927058770002e-10;
+  const uint64_t inf_bits = 0x7FF0000000000000ull;
+  if (x != x) return x;
+  if (x < 0.0) return (x - x) / (x - x);
+  double inf;
+  memcpy(&inf, &inf_bits, 8);
+  if (x == 0.0) return -inf;
+  if (x == inf) return x;
+  int e = 0;
+  if (x < 2.2250738585072014e-308) { x = x * 18014398509481984.0; e = -54; } /* subnormal: times 2^54, exact */
+  uint64_t b;
+  memcpy(&b, &x, 8);
+  e += (int)(b >> 52) - 1023;
+  b = (b & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
+  double m;
+  memcpy(&m, &b, 8); /* [1, 2) */
+  if (m >= 1.41421356237309514547) { m = m * 0.5; e += 1; }
+  const double s = (m - 1.0) / (m + 1.0);
+  const double z = s * s;
+  double p = 1.0 / 23.0;
+  p = p * z + 1.0 / 21.0;
+  p = p * z + 1.0 / 19.0;
+  p = p * z + 1.0 / 17.0;
+  p = p * z + 1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + 1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + 1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + 1.0 / 3.0;
+  p = p * z + 1.0;
+  const double lm = (2.0 * s) * p;
+  const double fe = (double)e;
+  return fe * ln2_hi + (fe * ln2_lo + lm);
+}
 
 #endif /* OFDG_DETMATH_H_ */

@@ -106,6 +106,7 @@ EXPORTS = [
     "ofdg_flow_stats", "ofdg_host_flow_stats",
     "ofdg_flow_pyramid", "ofdg_host_flow_pyramid",
     "ofdg_flow_stats_sized", "ofdg_flow_pyramid_sized", "ofdg_crop", "ofdg_host_crop", "ofdg_crop_draw", "ofdg_crop_philox",
+    "ofdg_photo", "ofdg_host_photo", "ofdg_photo_draw", "ofdg_debug_photo_table", "ofdg_host_photo_table", "ofdg_host_det_log",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -432,6 +433,133 @@ def crop_philox(counter, key):
     return tuple(int(v) for v in out)
 
 
+# the photometric augmentation (ofdg_photo_rec / struct ofdg_photo_job / ofdg_photo, include/ofdg.h)
+PHOTO_RANGES = ("gamma_log", "contrast_log", "brightness", "colour_log", "sigma_max",
+                "pair_gamma_log", "pair_contrast_log", "pair_brightness", "pair_colour_log")
+# A starting point, in the spirit of the FlowNet / PWC-Net recipes for FlyingChairs-like data: gamma in [0.7, 1.5] (log 0.4 wide
+# either way), contrast in [0.55, 1.8], brightness +-0.1 of full scale, each colour channel by [0.67, 1.5], noise of up to 10
+# grey levels; frame 1 within a few per cent of frame 0.  Not a tuned recipe: every field is a range to be chosen per data set.
+PHOTO_FLOWNET = dict(gamma_log=0.4, contrast_log=0.6, brightness=0.1, colour_log=0.4, sigma_max=10.0,
+                     pair_gamma_log=0.05, pair_contrast_log=0.05, pair_brightness=0.02, pair_colour_log=0.03)
+PHOTO_REC_FLOATS = 16  # a record as float32 [16]: gamma[2] contrast[2] brightness[2] gain[2][3] sigma[2], then the two reserved words
+
+
+class PhotoRec(C.Structure):
+    """ofdg_photo_rec: the transform of one sample (64 bytes)."""
+    _fields_ = [("gamma", C.c_float * 2), ("contrast", C.c_float * 2), ("brightness", C.c_float * 2), ("gain", (C.c_float * 3) * 2),
+                ("sigma", C.c_float * 2), ("reserved", C.c_int32 * 2)]
+
+
+class PhotoJob(C.Structure):
+    """struct ofdg_photo_job (120 bytes)."""
+    _fields_ = [("src", C.c_void_p * 2), ("dst", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)] + \
+               [(name, C.c_float) for name in PHOTO_RANGES]
+
+
+def _photo_ranges(job, ranges):
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in PHOTO_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(PHOTO_RANGES)))
+    for key in PHOTO_RANGES:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    return job
+
+
+def photo_format(src, dst, height=None, width=None):
+    """(n, height, width, src code, dst code) of the frames of Generator.photo / host_photo: src and dst are pairs (image0,
+    image1), either member None in both; a frame is float32 or uint8 [n,3,height,width], one dtype for src and one for dst.
+    Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    if len(src) != 2 or len(dst) != 2 or all(t is None for t in src):
+        raise ValueError("src and dst must be pairs (image0, image1) with at least one frame")
+    shape = next(tuple(t.shape) for t in src if t is not None)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 3 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a frame must be [n,3,%s,%s], got %s" % (height or "height", width or "width", shape))
+    codes = []
+    for what, pair in (("src", src), ("dst", dst)):
+        names = {_dtype_name(t) for t in pair if t is not None}
+        if len(names) != 1 or not names <= set(_IMAGE_CODES):
+            raise ValueError("%s must be float32 or uint8, one dtype for both frames, got %s" % (what, sorted(names)))
+        codes.append(_IMAGE_CODES[names.pop()])
+    for f in range(2):
+        if (src[f] is None) != (dst[f] is None):
+            raise ValueError("image%d must be set in both src and dst or in neither" % f)
+        for what, t in (("src", src[f]), ("dst", dst[f])):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError("%s[image%d] must be %s, got %s" % (what, f, shape, tuple(t.shape)))
+    return int(shape[0]), int(shape[2]), int(shape[3]), codes[0], codes[1]
+
+
+def _photo_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
+    job = _photo_ranges(PhotoJob(), ranges)
+    for f in range(2):
+        if src[f] is not None:
+            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt = codes
+    return job
+
+
+def photo_draw(seed, index, ranges=None):
+    """ofdg_photo_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (PHOTO_RANGES; a
+    missing one is 0), before sanitising, as float32 [16] (PHOTO_REC_FLOATS)."""
+    import numpy as np
+    out = np.zeros((PHOTO_REC_FLOATS,), np.float32)
+    job = _photo_ranges(PhotoJob(), ranges)
+    _host_check(lib().ofdg_photo_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), _hptr(out)))
+    return out
+
+
+def host_det_log(x):
+    """ofdg_host_det_log (pure, no GPU): ofdg_det_log of a float64 array."""
+    import numpy as np
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros(x.shape, np.float64)
+    _host_check(lib().ofdg_host_det_log(_hptr(x), x.size, _hptr(out)))
+    return out
+
+
+def host_photo_table(rec):
+    """ofdg_host_photo_table (no GPU): the table float32 [2,3,256] (frame, channel B G R, k) of a record float32 [16], sanitised
+    first."""
+    import numpy as np
+    rec = np.ascontiguousarray(rec, np.float32).reshape(PHOTO_REC_FLOATS)
+    out = np.zeros((2, 3, 256), np.float32)
+    _host_check(lib().ofdg_host_photo_table(_hptr(rec), _hptr(out)))
+    return out
+
+
+def host_photo(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None, in_place=False):
+    """ofdg_host_photo (no GPU): the augmentation of HOST arrays - src a pair (image0, image1) of float32 or uint8 arrays
+    [n,3,H,W], either None; recs None (drawn from seed, first_index and ranges) or a float32 array [n,16].  dst_dtype: np.float32
+    / np.uint8, default the source's.  in_place: the sources themselves are written (they must be contiguous and of dst_dtype).
+    Returns ((image0, image1), recs_used): the augmented arrays (None for an absent frame) and the float32 [n,16] records after
+    sanitising."""
+    import numpy as np
+    src = tuple(src)
+    if not in_place:
+        src = tuple(None if t is None else np.ascontiguousarray(t) for t in src)
+    given = [t for t in src if t is not None]
+    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
+    dst = src if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in src)
+    n, height, width, *codes = photo_format(src, dst)
+    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
+        raise ValueError("in_place needs contiguous sources of dst_dtype")
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.float32 or recs.shape != (n, PHOTO_REC_FLOATS):
+            raise ValueError("recs must be float32 [%d,%d], got %s %s" % (n, PHOTO_REC_FLOATS, recs.dtype, recs.shape))
+    used = np.zeros((n, PHOTO_REC_FLOATS), np.float32)
+    job = _photo_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                     first_index, seed, ranges)
+    _host_check(lib().ofdg_host_photo(C.byref(job), n, width, height))
+    return dst, used
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -513,6 +641,12 @@ def lib():
         L.ofdg_host_crop.argtypes = [C.POINTER(CropJob), i32, i32, i32]
         L.ofdg_crop_draw.argtypes = [C.c_uint32, C.c_longlong, i32, i32, i32, i32, i32, C.POINTER(CropRec)]
         L.ofdg_crop_philox.argtypes = [C.POINTER(C.c_uint32 * 4), C.POINTER(C.c_uint32 * 2), C.POINTER(C.c_uint32 * 4)]
+        L.ofdg_photo.argtypes = [vp, C.POINTER(PhotoJob), i32, vp]
+        L.ofdg_host_photo.argtypes = [C.POINTER(PhotoJob), i32, i32, i32]
+        L.ofdg_photo_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(PhotoJob), vp]
+        L.ofdg_debug_photo_table.argtypes = [vp, vp, vp]
+        L.ofdg_host_photo_table.argtypes = [vp, vp]
+        L.ofdg_host_det_log.argtypes = [vp, i32, vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -851,6 +985,37 @@ class Generator:
                         self.params.seed if seed is None else seed, _crop_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_crop(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
+
+    def photo(self, src, dst=None, recs=None, first_index=0, seed=None, ranges=None, recs_out=None, stream=0, size=None):
+        """The photometric augmentation of both frames of a batch in one launch (ofdg_photo, include/ofdg.h): gamma, contrast,
+        brightness, colour gain and noise, each sample by its own record, frame 1 slightly apart from frame 0.  src: the pair
+        (image0, image1) of float32 or uint8 tensors [n,3,H,W] a render / forward call (or crop) wrote, either member None.
+        dst: the pair to write, float32 or uint8 independently of src; None: in place.  recs: None - the record of sample i is
+        photo_draw(seed, first_index + i, ranges) - or a float32 device tensor [n,16], taken as given; either is sanitised.
+        ranges: a dict of PHOTO_RANGES (a missing one is 0; PHOTO_FLOWNET is a starting point).  seed: default the context's.
+        recs_out: None or a float32 device tensor [n,16] that receives the records used.  stream: the stream the frames were
+        written on, or STREAM_OWN.  size=(height, width): frames of that size instead of the context's.  Asynchronous.
+        Returns dst."""
+        src = tuple(src)
+        dst = src if dst is None else tuple(dst)
+        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        n, _, _, *codes = photo_format(src, dst, height, width)
+        for t in (recs, recs_out):
+            if t is not None and (str(t.dtype) != "torch.float32" or tuple(t.shape) != (n, PHOTO_REC_FLOATS)):
+                raise ValueError("recs and recs_out must be float32 [%d,%d], got %s %s" % (n, PHOTO_REC_FLOATS, t.dtype, tuple(t.shape)))
+        job = _photo_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), _optr(recs), _optr(recs_out),
+                         first_index, self.params.seed if seed is None else seed, ranges)
+        self._check(lib().ofdg_photo(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
+
+    def debug_photo_table(self, rec):
+        """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
+        host_photo_table)."""
+        import numpy as np
+        rec = np.ascontiguousarray(rec, np.float32).reshape(PHOTO_REC_FLOATS)
+        out = np.zeros((2, 3, 256), np.float32)
+        self._check(lib().ofdg_debug_photo_table(self.h, _hptr(rec), _hptr(out)))
+        return out
 
     def sample_counter(self, first_index, n):
         """Blueprints of the device counter sampler: (tasks, bps, n_bps) in the fixed layout."""
@@ -1477,12 +1642,19 @@ class FlowLoader:
     drawn flips, crop_occ_window marks pixels whose target leaves the window in occ0 / occ1).  stats= and pyramid= then reduce
     the CROPPED flow and occ0; the loader yields the cropped tensors and extras, every batch is (image0, image1, flow, {...})
     and the dict also holds "crop" (int32 [n,4]: x0, y0, flags, 0).  objects=True with crop= raises: its boxes are of the
-    uncropped frame."""
+    uncropped frame.
+    photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames of every batch are augmented in place
+    (Generator.photo, enqueued on the same internal stream right behind the batch - behind the crop when there is one, on the
+    cropped frames; records drawn from the context's seed and the batch's first global index, so start= and sharding make the
+    same pixels); every batch is then (image0, image1, flow, {...}) and the dict also holds "photo" (float32 [n,16], the
+    records used)."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
-                 crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, **kw):
+                 crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, **kw):
         import torch
+        self.photo = None if photo is None else dict(photo)
+        _photo_ranges(PhotoJob(), self.photo)  # (raises for a name that is no range)
         if objects and crop is not None:
             raise ValueError("objects=True does not combine with crop=: the table's boxes are of the uncropped frame")
         if objects and (extras is None or "label0" not in extras or "label1" not in extras):
@@ -1525,6 +1697,9 @@ class FlowLoader:
         ph, pw = self.crop if self.crop is not None else (p.height, p.width)
         self.pbufs = [alloc_flow_pyramid(p.batch_size, ph, pw, self.pyramid, flow_dtype, bool(pyramid_weights))
                       if self.pyramid else None for _ in range(self.prefetch)]
+        # (not filled: the augmentation writes every record; see the crop's buffers above)
+        self.rbufs = [torch.empty((p.batch_size, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
+                      for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -1538,10 +1713,11 @@ class FlowLoader:
         chain = torch.cuda.ExternalStream(s)
         if self.released[j] is not None:
             chain.wait_event(self.released[j])
-        step = self.gen.step if self.crop is not None else 0
+        step = self.gen.step if self.crop is not None or self.photo is not None else 0
         self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
         if self.crop is not None:
             return self._enqueue_cropped(j, s, chain, step)
+        self._enqueue_photo(j, self.bufs[j][:2], s, step, None)
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
@@ -1554,8 +1730,16 @@ class FlowLoader:
         out, recs = self.cbufs[j]
         self.gen.crop(planes, out, first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank), hflip=self.crop_flips[0],
                       vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
+        self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
         self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
         self.ready[j].record(chain)
+
+    def _enqueue_photo(self, j, frames, s, step, size):
+        """The augmentation of the frames of batch `step` (set j, on stream s) in place, when the loader makes one."""
+        if self.photo is not None:
+            p = self.gen.params
+            self.gen.photo(frames, recs_out=self.rbufs[j], first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank),
+                           ranges=self.photo, stream=s, size=size)
 
     def _enqueue_reductions(self, j, flow, occ, s, size):
         """The statistics and the pyramid of set j, as far as the loader makes them, of a flow and its map (None: no map) of
@@ -1601,10 +1785,14 @@ class FlowLoader:
             out, recs = self.cbufs[j]
             more = {k: v for k, v in out.items() if k not in ("image0", "image1", "flow")}
             more["crop"] = recs
+            if self.rbufs[j] is not None:
+                more["photo"] = self.rbufs[j]
             self._add_reductions(more, j)
             return (out["image0"], out["image1"], out["flow"], more)
-        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None:
+        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None:
             more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
+            if self.rbufs[j] is not None:
+                more["photo"] = self.rbufs[j]
             if self.obufs[j] is not None:
                 more.update(objects=self.obufs[j][0], object_counts=self.obufs[j][1])
             self._add_reductions(more, j)

@@ -379,4 +379,83 @@ int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, in
   return OFDG_OK;
 }
 
+// ofdg_photo on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the table
+// entry, the index and the noise are the functions the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.
+static void photo_table_of(const DevPhotoRec& r, float* table) {
+  for (int f = 0; f < 2; ++f)
+    for (int c = 0; c < 3; ++c)
+      for (int k = 0; k < 256; ++k) table[(f * 3 + c) * 256 + k] = photo_table_entry(r.gamma[f], r.gain[f][c], r.contrast[f], r.brightness[f], k);
+}
+int ofdg_host_det_log(const double* x, int n, double* log_out) {
+  if (n < 0 || (n > 0 && (!x || !log_out))) { g_host_error = "ofdg_host_det_log: x or log_out is NULL, or n below 0"; return OFDG_EINVAL; }
+  for (int i = 0; i < n; ++i) log_out[i] = ofdg_det_log(x[i]);
+  return OFDG_OK;
+}
+int ofdg_host_photo_table(const ofdg_photo_rec* rec, float* table) {
+  if (!rec || !table) { g_host_error = "ofdg_host_photo_table: rec or table is NULL"; return OFDG_EINVAL; }
+  DevPhotoRec r;
+  std::memcpy(&r, rec, sizeof(r));
+  photo_table_of(photo_sanitise(r), table);
+  return OFDG_OK;
+}
+int ofdg_photo_draw(uint32_t seed, long long index, const struct ofdg_photo_job* ranges, ofdg_photo_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_photo_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevPhotoJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = photo_ranges_error(j)) { g_host_error = std::string("ofdg_photo_draw: ") + why; return OFDG_EINVAL; }
+  const DevPhotoRec r = photo_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_photo(const struct ofdg_photo_job* job, int n_samples, int width, int height) {
+  const DevPhotoJob* const j = reinterpret_cast<const DevPhotoJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = photo_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_photo: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  std::vector<float> table(2 * 3 * 256);
+  for (int i = 0; i < n_samples; ++i) {
+    const unsigned long long g = (unsigned long long)(j->first_index + i);
+    DevPhotoRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + 64 * (size_t)i, 64);
+    else r = photo_draw_rec(j->seed, g, *j);
+    r = photo_sanitise(r);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + 64 * (size_t)i, &r, 64);
+    photo_table_of(r, table.data());
+    const uint32_t k0 = j->seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const bool noisy = r.sigma[f] > 0.0f;
+      const float scale = photo_noise_scale(r.sigma[f]);
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t* const sp = static_cast<const uint8_t*>(j->src[f]) + ((size_t)i * 3 + c) * plane * ses;
+        uint8_t* const dp = static_cast<uint8_t*>(j->dst[f]) + ((size_t)i * 3 + c) * plane * des;
+        const float* const T = table.data() + (f * 3 + c) * 256;
+        CropWords block{0u, 0u, 0u, 0u};
+        for (size_t p = 0; p < plane; ++p) {
+          int k = sp[p];
+          if (ses == 4) {
+            float e;
+            std::memcpy(&e, sp + 4 * p, 4);
+            k = photo_index(e);
+          }
+          float v = T[k];
+          if (noisy) {
+            const uint32_t m = (uint32_t)((size_t)c * plane + p);
+            if ((m & 3u) == 0u || p == 0) block = crop_philox(CropWords{m >> 2, (uint32_t)f, 0x0c72u, 0u}, k0, k1);
+            const uint32_t word = (m & 3u) == 0u ? block.x : (m & 3u) == 1u ? block.y : (m & 3u) == 2u ? block.z : block.w;
+            v = photo_add_noise(v, scale, word);
+          }
+          if (des == 4) std::memcpy(dp + 4 * p, &v, 4);
+          else dp[p] = (uint8_t)rintf(v);
+        }
+      }
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

@@ -3681,4 +3681,114 @@ __global__ __launch_bounds__(kCropThreads) void crop_kernel(const DevCropJob job
   }
 }
 
+// --------------------------------------------------------------------------
+// Photometric augmentation (ofdg_photo): a 256-entry table per (sample, frame, channel), a lookup per element and, where the
+// sample's sigma is above 0, the noise of one Philox word per element, in one launch.  The functions of the definition are
+// the host twin's (csrc/ofdg_device.h), so the result is the twin's bit for bit.
+// --------------------------------------------------------------------------
+// A channel of a sample is width * height elements without gaps, a whole number of 16-element runs (width % 8 == 0, height
+// even).  A workgroup serves kPhotoBlockPixels consecutive elements of one (sample, frame, channel): each thread first makes
+// one entry of that table in LDS (one fp64 log and exp), then the workgroup moves pieces - what one 16-byte store holds of the
+// destination: 4 float32 or 16 uint8 - lane t the pieces t, t + 256, ... of the block, so a wave's store instruction writes
+// 1 KiB of consecutive bytes.  A piece of a uint8 source is read as 4-byte words (the alignment asked of it), of a float32
+// source as 16-byte ones.  A piece starts at an element number that is a multiple of 4, so the noise of its elements is whole
+// Philox blocks: one per 4 elements.  A piece is read whole before it is written and by the same lane, which is all the
+// in-place form needs.  The lookup is a ds_read_b32 at a data-dependent index (neighbouring pixels: mostly the same or
+// nearby entries, so few lanes of a half-wave meet on a bank with different addresses).  blockIdx.x counts the blocks of the
+// channels of the frames that are set, blockIdx.y the samples.  The record is drawn or read, and sanitised, on uniform
+// values once per (workgroup, sample); workgroup 0 writes it back from lane 0 with vector stores.  The noise branch is
+// uniform per (sample, frame).  No atomics, no scratch, 1 KiB of LDS.
+constexpr int kPhotoThreads = 256;
+#ifndef OFDG_PHOTO_BLOCK_PIXELS
+#define OFDG_PHOTO_BLOCK_PIXELS 32768
+#endif
+constexpr int kPhotoBlockPixels = OFDG_PHOTO_BLOCK_PIXELS;  // 6 workgroups per channel of a 512 x 384 frame, a table entry per 128 elements (measured against 4096 .. 65536: CHANGELOG)
+static_assert(kPhotoBlockPixels % (kPhotoThreads * 16) == 0, "whole rounds of pieces of either kind");
+template <bool kSrcU8, bool kDstU8>
+__global__ __launch_bounds__(kPhotoThreads) void photo_kernel(const DevPhotoJob job, int n, int W, int H, uint32_t per_channel) {
+  constexpr int kP = kDstU8 ? 16 : 4;  // elements of a piece
+  __shared__ float table[256];
+  const uint32_t slot = blockIdx.x / per_channel, block = blockIdx.x - slot * per_channel;
+  const int f = (int)(slot / 3u) + (job.src[0] ? 0 : 1), c = (int)(slot % 3u);
+  const void* const src = f ? job.src[1] : job.src[0];
+  void* const dst = f ? job.dst[1] : job.dst[0];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: photo_arg_error)
+  const uint32_t first = block * (uint32_t)kPhotoBlockPixels;
+  const uint32_t end = first + (uint32_t)kPhotoBlockPixels < plane ? first + (uint32_t)kPhotoBlockPixels : plane;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const unsigned long long g = (unsigned long long)(job.first_index + i);
+    DevPhotoRec r;
+    if (job.recs) r = job.recs[i];
+    else r = photo_draw_rec(job.seed, g, job);
+    r = photo_sanitise(r);
+    if (job.recs_out && blockIdx.x == 0u && threadIdx.x == 0u) {
+      float4* const o = reinterpret_cast<float4*>(job.recs_out + i);
+      o[0] = make_float4(r.gamma[0], r.gamma[1], r.contrast[0], r.contrast[1]);
+      o[1] = make_float4(r.brightness[0], r.brightness[1], r.gain[0][0], r.gain[0][1]);
+      o[2] = make_float4(r.gain[0][2], r.gain[1][0], r.gain[1][1], r.gain[1][2]);
+      o[3] = make_float4(r.sigma[0], r.sigma[1], 0.0f, 0.0f);
+    }
+    const float gamma = f ? r.gamma[1] : r.gamma[0], contrast = f ? r.contrast[1] : r.contrast[0];
+    const float brightness = f ? r.brightness[1] : r.brightness[0], sigma = f ? r.sigma[1] : r.sigma[0];
+    const float gain = f ? (c == 0 ? r.gain[1][0] : c == 1 ? r.gain[1][1] : r.gain[1][2]) : (c == 0 ? r.gain[0][0] : c == 1 ? r.gain[0][1] : r.gain[0][2]);
+    table[threadIdx.x] = photo_table_entry(gamma, gain, contrast, brightness, (int)threadIdx.x);
+    __syncthreads();
+    const bool noisy = sigma > 0.0f;
+    const float scale = photo_noise_scale(sigma);
+    const uint32_t k0 = job.seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+    const size_t chan = ((size_t)i * 3 + (size_t)c) * plane;  // first element of the channel in the tensor
+    for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kPhotoThreads * kP)) {
+      int k[kP];
+      if constexpr (kSrcU8) {
+        const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + chan + at);
+#pragma unroll
+        for (int q = 0; q < kP / 4; ++q) {
+          const uint32_t w = sp[q];
+          k[4 * q] = (int)(w & 255u); k[4 * q + 1] = (int)((w >> 8) & 255u); k[4 * q + 2] = (int)((w >> 16) & 255u); k[4 * q + 3] = (int)(w >> 24);
+        }
+      } else {
+        const float4* const sp = reinterpret_cast<const float4*>(static_cast<const float*>(src) + chan + at);
+#pragma unroll
+        for (int q = 0; q < kP / 4; ++q) {
+          const float4 e = sp[q];
+          k[4 * q] = photo_index(e.x); k[4 * q + 1] = photo_index(e.y); k[4 * q + 2] = photo_index(e.z); k[4 * q + 3] = photo_index(e.w);
+        }
+      }
+      float v[kP];
+#pragma unroll
+      for (int q = 0; q < kP; ++q) v[q] = table[k[q]];
+      if (noisy) {
+        const uint32_t m = (uint32_t)c * plane + at;  // element number of the piece's first element: a multiple of 4
+#pragma unroll
+        for (int q = 0; q < kP / 4; ++q) {
+          const CropWords w = crop_philox(CropWords{(m >> 2) + (uint32_t)q, (uint32_t)f, 0x0c72u, 0u}, k0, k1);
+          v[4 * q] = photo_add_noise(v[4 * q], scale, w.x);
+          v[4 * q + 1] = photo_add_noise(v[4 * q + 1], scale, w.y);
+          v[4 * q + 2] = photo_add_noise(v[4 * q + 2], scale, w.z);
+          v[4 * q + 3] = photo_add_noise(v[4 * q + 3], scale, w.w);
+        }
+      }
+      crop_u32x4 o;
+      if constexpr (kDstU8) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          o[q] = (uint32_t)rintf(v[4 * q]) | ((uint32_t)rintf(v[4 * q + 1]) << 8) | ((uint32_t)rintf(v[4 * q + 2]) << 16) | ((uint32_t)rintf(v[4 * q + 3]) << 24);
+        crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + chan + at), o);
+      } else {
+        o = crop_u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        crop_store(reinterpret_cast<crop_u32x4*>(static_cast<float*>(dst) + chan + at), o);
+      }
+    }
+    __syncthreads();  // (the next sample of this workgroup writes the table again)
+  }
+}
+// ofdg_debug_photo_table: the table [2][3][256] of one record as the device computes its entries - workgroup b = f * 3 + c.
+__global__ __launch_bounds__(256) void photo_table_kernel(const DevPhotoRec* __restrict__ rec, float* __restrict__ out) {
+  const DevPhotoRec r = photo_sanitise(*rec);
+  const int f = (int)blockIdx.x / 3, c = (int)blockIdx.x % 3;
+  const float gain = f ? (c == 0 ? r.gain[1][0] : c == 1 ? r.gain[1][1] : r.gain[1][2]) : (c == 0 ? r.gain[0][0] : c == 1 ? r.gain[0][1] : r.gain[0][2]);
+  out[blockIdx.x * 256u + threadIdx.x] =
+      photo_table_entry(f ? r.gamma[1] : r.gamma[0], gain, f ? r.contrast[1] : r.contrast[0], f ? r.brightness[1] : r.brightness[0], (int)threadIdx.x);
+}
+
 }  // namespace ofdg

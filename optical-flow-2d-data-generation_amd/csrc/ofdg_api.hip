@@ -266,7 +266,7 @@ static std::string err_text(uint32_t e) {
   return t;
 }
 
-// ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop ------------
+// ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -285,7 +285,7 @@ struct PostOp {
   }
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
-// the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel.
+// the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1683,6 +1683,36 @@ int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void*
   return OFDG_OK;
 }
 
+// Photometric augmentation of caller-given frames: one kernel on `stream` for both frames, every channel and sample.
+int ofdg_photo(ofdg_ctx* c, const struct ofdg_photo_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_photo"};
+  const DevPhotoJob* const j = reinterpret_cast<const DevPhotoJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = photo_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = photo_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const uint32_t per_channel = (plane + kPhotoBlockPixels - 1) / kPhotoBlockPixels;
+  const dim3 g(per_channel * 3u * ((j->src[0] ? 1u : 0u) + (j->src[1] ? 1u : 0u)), (unsigned)std::min(n_samples, 65535));
+  with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
+      hipLaunchKernelGGL((photo_kernel<decltype(src_u8)::value, decltype(dst_u8)::value>), g, dim3(kPhotoThreads), 0, st, *j, n_samples, W, H, per_channel);
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
 //   front = 2: the slot holds two such batches (the paired front end)
@@ -2367,6 +2397,20 @@ int ofdg_debug_detmath(ofdg_ctx* c, const double* angles, int n, double* sin_out
     HIP_OK(c, hipMemcpy(cos_out, d + 2 * k, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   }
   if (m) HIP_OK(c, hipMemcpy(expf_out, f + k, (size_t)m * sizeof(float), hipMemcpyDeviceToHost));
+  return OFDG_OK;
+}
+
+int ofdg_debug_photo_table(ofdg_ctx* c, const ofdg_photo_rec* rec_host, float* table_host) {
+  if (!c) return OFDG_EINVAL;
+  if (!rec_host || !table_host) { c->err = "ofdg_debug_photo_table: rec_host or table_host is NULL"; return OFDG_EINVAL; }
+  DevBuf<DevPhotoRec> rec;
+  DevBuf<float> table;
+  HIP_OK(c, rec.alloc(1));
+  HIP_OK(c, table.alloc((size_t)2 * 3 * 256));
+  HIP_OK(c, hipMemcpy(rec.p, rec_host, sizeof(DevPhotoRec), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(photo_table_kernel, dim3(6), dim3(256), 0, 0, rec.p, table.p);
+  HIP_OK(c, hipGetLastError());
+  HIP_OK(c, hipMemcpy(table_host, table.p, (size_t)2 * 3 * 256 * sizeof(float), hipMemcpyDeviceToHost));
   return OFDG_OK;
 }
 

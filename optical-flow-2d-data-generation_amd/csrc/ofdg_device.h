@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/ofdg_detmath.h"
 #include "../../include/ofdg.h"  // the ABI: each Dev* record below that restates one of its structs is held to it next to its definition
 
 // Marks a function shared by host code and kernels (this header, realize.h): the pattern of OFDG_DM_FN
@@ -328,6 +329,172 @@ inline const char* crop_arg_error(const DevCropJob* j, int n, int width, int hei
   for (int a = 0; a < nr; ++a)
     for (int b = 0; b < nr; ++b)
       if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
+  return nullptr;
+}
+
+// ---- Photometric augmentation (ofdg_photo, include/ofdg.h) -----------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, one table entry, the element's index, the noise and the argument rules.  Everything here is compiled without
+// contraction, so every operation below is its own rounding.
+struct DevPhotoRec {  // ofdg_photo_rec, field for field
+  float gamma[2], contrast[2], brightness[2], gain[2][3], sigma[2];
+  int32_t reserved[2];
+};
+struct DevPhotoJob {  // struct ofdg_photo_job, field for field
+  const void* src[2];
+  void* dst[2];
+  const DevPhotoRec* recs;
+  DevPhotoRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, src_fmt, dst_fmt, flags, reserved;
+  float gamma_log, contrast_log, brightness, colour_log, sigma_max;
+  float pair_gamma_log, pair_contrast_log, pair_brightness, pair_colour_log;
+};
+static_assert(sizeof(ofdg_photo_rec) == sizeof(DevPhotoRec) && sizeof(DevPhotoRec) == 64 && offsetof(ofdg_photo_rec, gain) == offsetof(DevPhotoRec, gain) &&
+              offsetof(DevPhotoRec, gain) == 24 && offsetof(ofdg_photo_rec, sigma) == offsetof(DevPhotoRec, sigma) && offsetof(DevPhotoRec, sigma) == 48 &&
+              offsetof(ofdg_photo_rec, reserved) == offsetof(DevPhotoRec, reserved), "ofdg_photo_rec: 64 bytes without padding, the layout the kernel reads and writes");
+static_assert(sizeof(struct ofdg_photo_job) == sizeof(DevPhotoJob) && sizeof(DevPhotoJob) == 120 && offsetof(struct ofdg_photo_job, dst) == offsetof(DevPhotoJob, dst) &&
+              offsetof(struct ofdg_photo_job, recs) == offsetof(DevPhotoJob, recs) && offsetof(struct ofdg_photo_job, recs_out) == offsetof(DevPhotoJob, recs_out) &&
+              offsetof(struct ofdg_photo_job, first_index) == offsetof(DevPhotoJob, first_index) && offsetof(struct ofdg_photo_job, seed) == offsetof(DevPhotoJob, seed) &&
+              offsetof(struct ofdg_photo_job, width) == offsetof(DevPhotoJob, width) && offsetof(struct ofdg_photo_job, src_fmt) == offsetof(DevPhotoJob, src_fmt) &&
+              offsetof(struct ofdg_photo_job, reserved) == offsetof(DevPhotoJob, reserved) && offsetof(struct ofdg_photo_job, gamma_log) == offsetof(DevPhotoJob, gamma_log) &&
+              offsetof(DevPhotoJob, gamma_log) == 84 && offsetof(struct ofdg_photo_job, pair_colour_log) == offsetof(DevPhotoJob, pair_colour_log) &&
+              offsetof(DevPhotoJob, pair_colour_log) == 116, "struct ofdg_photo_job: 120 bytes, the layout the kernel takes");
+// u(w) = (w >> 8) * 2^-24 in [0, 1), exact; sym(w, a) = a * (2 u - 1) in [-a, a), one rounding (2 u and 2 u - 1 are exact); a
+// zero of either sign is +0, so the ranges 0 give the identity record bit for bit.
+OFDG_HD_FN float photo_unit(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }
+OFDG_HD_FN float photo_sym(uint32_t w, float a) {
+  const float t = 2.0f * photo_unit(w) - 1.0f;
+  const float r = a * t;
+  return r == 0.0f ? 0.0f : r;
+}
+OFDG_HD_FN float photo_exp(float l) { return (float)ofdg_det_exp((double)l); }
+// The record of global sample g: Philox blocks 0, 1, 2 under the sampler's key of g and the counters {j, 0, 0x0c71, 0} (the
+// sampler's third counter word is 0x0fd9, the crop's 0x0c70).  `j` supplies the nine ranges.
+OFDG_HD_FN DevPhotoRec photo_draw_rec(uint32_t seed, unsigned long long g, const DevPhotoJob& j) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords a = crop_philox(CropWords{0u, 0u, 0x0c71u, 0u}, k0, k1);
+  const CropWords b = crop_philox(CropWords{1u, 0u, 0x0c71u, 0u}, k0, k1);
+  const CropWords d = crop_philox(CropWords{2u, 0u, 0x0c71u, 0u}, k0, k1);
+  const float lg0 = photo_sym(a.x, j.gamma_log), lc0 = photo_sym(a.y, j.contrast_log), b0 = photo_sym(a.z, j.brightness);
+  const float sigma = j.sigma_max * photo_unit(a.w);
+  const float col0 = photo_sym(b.x, j.colour_log), col1 = photo_sym(b.y, j.colour_log), col2 = photo_sym(b.z, j.colour_log);
+  const float dg = photo_sym(d.x, j.pair_gamma_log), dc = photo_sym(d.y, j.pair_contrast_log), db = photo_sym(d.z, j.pair_brightness);
+  const float dcol = photo_sym(d.w, j.pair_colour_log);
+  const float lg1 = lg0 + dg, lc1 = lc0 + dc, b1 = b0 + db, col0b = col0 + dcol, col1b = col1 + dcol, col2b = col2 + dcol;
+  DevPhotoRec r;
+  r.gamma[0] = photo_exp(lg0); r.gamma[1] = photo_exp(lg1);
+  r.contrast[0] = photo_exp(lc0); r.contrast[1] = photo_exp(lc1);
+  r.brightness[0] = b0; r.brightness[1] = b1;
+  r.gain[0][0] = photo_exp(col0); r.gain[0][1] = photo_exp(col1); r.gain[0][2] = photo_exp(col2);
+  r.gain[1][0] = photo_exp(col0b); r.gain[1][1] = photo_exp(col1b); r.gain[1][2] = photo_exp(col2b);
+  r.sigma[0] = sigma; r.sigma[1] = sigma;
+  r.reserved[0] = 0; r.reserved[1] = 0;
+  return r;
+}
+// What is used of a record, given or drawn: a NaN becomes the identity value, then the lower bound, then the upper one (an
+// infinity lands on a bound; -0.0 passes as it is).
+OFDG_HD_FN float photo_clamp(float x, float lo, float hi, float identity) { return x != x ? identity : x < lo ? lo : x > hi ? hi : x; }
+OFDG_HD_FN DevPhotoRec photo_sanitise(DevPhotoRec r) {
+  for (int f = 0; f < 2; ++f) {
+    r.gamma[f] = photo_clamp(r.gamma[f], 0.125f, 8.0f, 1.0f);
+    r.contrast[f] = photo_clamp(r.contrast[f], 0.0f, 4.0f, 1.0f);
+    r.brightness[f] = photo_clamp(r.brightness[f], -1.0f, 1.0f, 0.0f);
+    for (int c = 0; c < 3; ++c) r.gain[f][c] = photo_clamp(r.gain[f][c], 0.0f, 8.0f, 1.0f);
+    r.sigma[f] = photo_clamp(r.sigma[f], 0.0f, 64.0f, 0.0f);
+    r.reserved[f] = 0;
+  }
+  return r;
+}
+// Entry k of the table of one (frame, channel) of a sanitised record: fp64, every operation rounded on its own, the sums
+// from left to right; below 0 (or NaN, which a sanitised record cannot give) becomes 0, then above 255 becomes 255.
+OFDG_HD_FN float photo_table_entry(float gamma, float gain, float contrast, float brightness, int k) {
+  const double x = (double)k / 255.0;
+  double p = x;
+  if (k == 0) p = 0.0;
+  else if (gamma != 1.0f) p = ofdg_det_exp((double)gamma * ofdg_det_log(x));
+  const double a = p * (double)gain;
+  const double b = a - 0.5;
+  const double c = b * (double)contrast;
+  const double d = c + 0.5;
+  const double e = d + (double)brightness;
+  double t = 255.0 * e;
+  t = t > 0.0 ? t : 0.0;
+  t = t < 255.0 ? t : 255.0;
+  return (float)t;
+}
+// The table index of a float32 element: clamped to [0, 255] (a NaN becomes 0), then rounded to nearest even.
+OFDG_HD_FN int photo_index(float x) {
+  x = x > 0.0f ? x : 0.0f;
+  x = x < 255.0f ? x : 255.0f;
+  return (int)rintf(x);
+}
+// sigma / sqrt(4 * (256^2 - 1) / 12): what one unit of the centred byte sum is worth
+OFDG_HD_FN float photo_noise_scale(float sigma) { return sigma / 147.80054f; }
+// v with the noise of one Philox word: the word's four bytes summed (0..1020, mean 510), two float32 products / sums, clamped.
+OFDG_HD_FN float photo_add_noise(float v, float scale, uint32_t word) {
+  const int s = (int)((word & 255u) + ((word >> 8) & 255u) + ((word >> 16) & 255u) + (word >> 24));
+  const float d = scale * (float)(s - 510);
+  float o = v + d;
+  o = o > 0.0f ? o : 0.0f;
+  o = o < 255.0f ? o : 255.0f;
+  return o;
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* photo_plane_size(const DevPhotoJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The nine ranges of the draw: the first that is negative, NaN or infinite, or nullptr.
+inline const char* photo_ranges_error(const DevPhotoJob& job) {
+  const DevPhotoJob* const j = &job;
+  const struct { float v; const char* why; } ranges[9] = {
+      {j->gamma_log, "gamma_log must be finite and not negative"}, {j->contrast_log, "contrast_log must be finite and not negative"},
+      {j->brightness, "brightness must be finite and not negative"}, {j->colour_log, "colour_log must be finite and not negative"},
+      {j->sigma_max, "sigma_max must be finite and not negative"}, {j->pair_gamma_log, "pair_gamma_log must be finite and not negative"},
+      {j->pair_contrast_log, "pair_contrast_log must be finite and not negative"}, {j->pair_brightness, "pair_brightness must be finite and not negative"},
+      {j->pair_colour_log, "pair_colour_log must be finite and not negative"}};
+  for (int k = 0; k < 9; ++k)
+    if (!(ranges[k].v >= 0.0f && ranges[k].v <= 3.4028234663852886e38f)) return ranges[k].why;
+  return nullptr;
+}
+// The argument rules ofdg_photo and ofdg_host_photo share: the first rule broken, or nullptr.  width, height: what
+// photo_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* photo_arg_error(const DevPhotoJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags != 0) return "flags must be 0";
+  if (j->reserved != 0) return "reserved must be 0";
+  if (const char* why = photo_ranges_error(*j)) return why;
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
+    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
+    frames += j->src[f] ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  // a destination range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
+  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
+  Range r[6];
+  int nr = 0;
+  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
+    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
+    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
+    nr += 2;
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * 64, false, -1};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * 64, true, -1};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
   return nullptr;
 }
 

@@ -1,7 +1,8 @@
 """Compare the device code of two builds function by function: python tools/device_code_diff.py PARENT.s BRANCH.s, where each
 file is the gfx950 assembly of csrc/ofdg_api.hip (the Makefile's flags plus --offload-device-only -S -cuid=ofdg).  A function
 is its instruction stream (label to .Lfunc_end) and its .amdhsa_kernel block, with the numbers of local labels (.LBB<n>_,
-.Lfunc_end<n>, .Ltmp<n>) taken out: they count functions, so appending one renumbers the rest.  Prints how many functions of
+.Lfunc_end<n>, .Ltmp<n>; BB<n>_ in the loop comments too) taken out: they count functions, so a new one renumbers those
+behind it.  Prints how many functions of
 the parent are identical in the branch, which differ or are missing, and which are new."""
 import re, sys, hashlib
 def functions(path):
@@ -26,7 +27,7 @@ def functions(path):
             while ".end_amdhsa_kernel" not in lines[j]: j += 1
             kd[m.group(1)] = "\n".join(lines[i:j + 1]); i = j
         i += 1
-    norm = lambda t: re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", re.sub(r"\.Ltmp\d+", ".Ltmp", t)))
+    norm = lambda t: re.sub(r"BB\d+_", "BB_",re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", re.sub(r"\.Ltmp\d+", ".Ltmp", t)))
     return {k: hashlib.sha256((norm(v) + "\n" + norm(kd.get(k, ""))).encode()).hexdigest() for k, v in out.items()}, {k: v.count("\n") + 1 for k, v in out.items()}
 a, la = functions(sys.argv[1]); b, lb = functions(sys.argv[2])
 same = [k for k in a if k in b and a[k] == b[k]]
