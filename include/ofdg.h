@@ -507,7 +507,8 @@ int ofdg_flow_pyramid_sized(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, con
  * Training crop: a crop_w x crop_h window of every output of a batch - frames, both flows, both occlusion maps, both label
  * planes -, each sample at its own position, optionally mirrored left-right and / or top-bottom, in ONE launch behind the
  * call that wrote the planes.  The window is a pure function of (seed, global sample index), so a resumed or sharded run
- * cuts the same windows.  Bits are moved; nothing is converted, scaled or rotated.
+ * cuts the same windows.  Bits are moved and nothing is converted; a window that is also zoomed, rotated or squeezed is
+ * ofdg_spatial below.
  *
  * Planes: src[k] is the [n,C,H,W] tensor of the context's frame size, dst[k] the [n,C,crop_h,crop_w] tensor of the same
  * element type; C = 3, 3, 2, 2, 1, 1, 1, 1 in the order of the enumerators.  image_fmt (image0, image1): OFDG_FMT_F32 or
@@ -657,6 +658,117 @@ int ofdg_host_photo_table(const ofdg_photo_rec* rec, float* table);
 /* The function ofdg_det_log of include/ofdg_detmath.h on n numbers as this library was compiled (pure, no GPU): what the table's gamma is
  * made of, exposed so that its stated error bound can be held to libm.  OFDG_EINVAL for a NULL pointer or n < 0. */
 int ofdg_host_det_log(const double* x, int n, double* log_out);
+
+/*
+ * Spatial augmentation: every output of a batch - frames, both flows, both occlusion maps, both label planes - resampled
+ * through an affine map per sample and per frame (zoom, rotation, squeeze, translation, flips; frame 1 slightly apart from
+ * frame 0) into an out_w x out_h window, the ground-truth flow transformed to match, in ONE launch behind the call that wrote
+ * the planes.  The record is a pure function of (seed, global sample index), so a resumed or sharded run makes the same warps.
+ * Everything below is exact: the kernel, ofdg_host_spatial and the numpy restatement of the tests give the same bits.  All
+ * arithmetic is IEEE, each operation rounded on its own (no contraction); fl64(.) / fl32(.) mark a rounding where the text
+ * would otherwise leave it open.
+ *
+ * Planes: the eight planes, their order and their formats are ofdg_crop's (OFDG_CROP_IMAGE0 .. OFDG_CROP_LABEL1, image_fmt,
+ * flow_fmt, occ_fmt).  src[k] is [n,C,H,W] of the source size, dst[k] [n,C,out_h,out_w] of the same element type.  width =
+ * height = 0: the source is the context's frame.  Source and output size each obey the context's rule (width a multiple of 8
+ * and at least 8, height even and at least 2) and no side exceeds 2^20; the output may be smaller or larger than the source.
+ * Every plane is optional on its own: src[k] and dst[k] both NULL.
+ *
+ * Record: m[f] = {a, b, c, d, e, g} maps destination pixel index (X, Y) of frame f to source pixel coordinates,
+ *   qx = fl64(fl64(fl64(a * X) + fl64(b * Y)) + c),   qy = fl64(fl64(fl64(d * X) + fl64(e * Y)) + g).
+ * The record of sample i is recs[i] when recs is given, else ofdg_spatial_draw(seed, first_index + i, ...).  Either way it is
+ * sanitised before use, and the sanitised record is what recs_out[i] receives.  Sanitising, per frame f: when one of the six
+ * entries is not finite, or one of |a|, |b|, |d|, |e| exceeds 64, or |c| or |g| exceeds 2^20, or det = fl64(fl64(a * e) -
+ * fl64(b * d)) has |det| outside [2^-12, 2^12], m[f] becomes the centred integer window {1, 0, (W - out_w) / 2, 0, 1,
+ * (H - out_h) / 2} (the quotients rounded toward -inf).  reserved = 0.  No record makes the kernel touch memory outside a plane.
+ *
+ * Tap of a pixel: Qx = (int)t, t = floor(fl64(fl64(qx * 256) + 0.5)) - 24.8 fixed point, as in the span interpolator of the
+ * render path -; t below -2^30 counts as -2^30, above 2^30 as 2^30.  Qy likewise.  The pixel is inside when 0 <= Qx <= (W - 1)
+ * * 256 && 0 <= Qy <= (H - 1) * 256.  ix = Qx >> 8, fx = Qx & 255 (arithmetic shift), likewise y; the four taps (ix, ix + 1) x
+ * (iy, iy + 1) are each clamped to the frame, which replicates the border.  The nearest tap is nx = (Qx + 128) >> 8, ny
+ * likewise, clamped.
+ *
+ * Frames: each element is widened to float32, both element types by the same expressions.  With the float32 weights w00 =
+ * (256 - fx)(256 - fy), w10 = fx (256 - fy), w01 = (256 - fx) fy, w11 = fx fy and the elements e00 (ix, iy), e10 (ix + 1, iy),
+ * e01 (ix, iy + 1), e11:
+ *   v = fl32(fl32(fl32(fl32(w00 * e00) + fl32(w10 * e10)) + fl32(fl32(w01 * e01) + fl32(w11 * e11))) * 2^-16).
+ * Every partial result is an integer below 2^24 when the elements are bytes, so the rendered frames (byte values in either
+ * format) are interpolated exactly.  float32 stores v (a NaN as 0x7FC00000); uint8 stores rintf of v clamped to [0, 255] (ties
+ * to even, a NaN becomes 0).
+ *
+ * Flow, at destination pixel (X, Y) of frame 0: (u, v) is the source flow at the NEAREST tap of m[0], widened to float32 -
+ * interpolating it would mix the motions of two objects at every boundary.  The target in source frame 1 is tx = fl64(qx +
+ * (double)u), ty likewise; it is mapped back through the inverse of m[1], made once per sample in fp64 with det as above:
+ * ia = e / det, ib = -b / det, id = -d / det, ie = a / det;
+ *   px = fl64(fl64(ia * fl64(tx - c)) + fl64(ib * fl64(ty - g))),   py = fl64(fl64(id * fl64(tx - c)) + fl64(ie * fl64(ty - g)))
+ * with c, g of m[1];  u' = (float)fl64(px - X), v' = (float)fl64(py - Y); binary16 is then rounded once to nearest even.  A
+ * non-finite source flow gives what that arithmetic gives, a NaN stored as 0x7FC00000 / 0x7E00 (the statistics and the pyramid
+ * leave such pixels out).  flow1 is the same with the frames exchanged: taps of m[1], inverse of m[0].
+ *
+ * Labels: the element at the nearest tap of its frame.
+ *
+ * Occlusion maps: the element becomes 1.0f / 1 when the source element at the nearest tap is non-zero (the crop's rule: a NaN
+ * is, -0.0 is not), or the pixel is not inside, or - with OFDG_SPATIAL_OCC_WINDOW - floor(fl64(px + 0.5)) lies outside [0,
+ * out_w - 1] or floor(fl64(py + 0.5)) outside [0, out_h - 1], px, py from that frame's flow (occ0: flow, occ1: flow1; a NaN is
+ * outside).  Otherwise it becomes +0.0f / 0.
+ *
+ * Draw (ofdg_spatial_draw): Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, blocks j = 0,
+ * 1, 2 at the counters {j, 0, 0x0c73, 0} (0x0c70 .. 0x0c72 and 0x0fd9 are taken); u(w) and sym(w, a) are ofdg_photo's.
+ *   block 0:  lz = sym(.x, zoom_log)  th = sym(.y, rot)  lq = sym(.z, squeeze_log);  h = -1 with OFDG_SPATIAL_RANDOM_HFLIP and
+ *             .w & 1, else 1;  v = -1 with OFDG_SPATIAL_RANDOM_VFLIP and (.w >> 1) & 1, else 1
+ *   block 1:  tfx = fl32(fl32(2 u(.x)) - 1)   tfy likewise from .y
+ *   block 2:  dlz = sym(.x, pair_zoom_log)  dth = sym(.y, pair_rot)  dtx = sym(.z, pair_translate)  dty = sym(.w, pair_translate)
+ * The map, in fp64 with EXP = ofdg_det_exp and sincos = ofdg_det_sincos of include/ofdg_detmath.h, for frame 0: gx = EXP(-(double)fl32(lz
+ * + lq)), gy = EXP(-(double)fl32(lz - lq)), (s, c) = sincos((double)th);  a = c * gx * h, b = -(s * gy) * v, d = s * gx * h, e =
+ * c * gy * v, each from left to right, a zero of either sign counting as +0.  The centre keeps the window inside the frame
+ * where it fits: hw = (out_w - 1) / 2.0, hh = (out_h - 1) / 2.0, ex = |a| * hw + |b| * hh, slack = max((W - 1) / 2.0 - ex, 0), cx
+ * = (W - 1) / 2.0 + ((double)tfx * translate) * slack, c = cx - (a * hw + b * hh); y the same with d, e, H, tfy: cy and g.
+ * Frame 1: the same formulas with fl32(lz + dlz) for lz, fl32(th + dth) for th and the centre (cx + dtx, cy + dty).  No
+ * rejection loop.  All ranges 0 give the centred identity window, frame 1 as frame 0.  translate is a fraction of the slack
+ * in [0, 1], rot and pair_rot are radians, pair_translate is in source pixels.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_crop.  One kernel for any
+ * n_samples, all planes and both frames, no atomics; it reads no record of the context.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, only one of
+ * width / height 0, a source or output size that breaks the rule above, W * H or out_w * out_h of 2^31 and more, unknown flag
+ * bits, non-zero reserved, another format code, a range that is negative, NaN or infinite, translate above 1, no plane set,
+ * src[k] without dst[k] or the reverse, OFDG_SPATIAL_OCC_WINDOW with occ0 but no flow (occ1 / flow1 likewise), a misaligned
+ * pointer (sources as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8; destinations and both record arrays
+ * 16-byte), a destination range (recs_out included) that overlaps any other range of the job (there is no in-place form),
+ * OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: bilinear sampling of the flow, mapping the boxes of the object table, non-affine (mode-9-style) augmentation
+ * warps, an in-place form.
+ */
+#define OFDG_SPATIAL_RANDOM_HFLIP  4   /* job flag: drawn maps may mirror the columns */
+#define OFDG_SPATIAL_RANDOM_VFLIP  8   /* job flag: drawn maps may mirror the rows    */
+#define OFDG_SPATIAL_OCC_WINDOW   16   /* job flag: see "occlusion maps" above        */
+typedef struct ofdg_spatial_rec {        /* 112 bytes; m[f] = {a, b, c, d, e, g} of frame f */
+  double m[2][6];
+  int32_t reserved[4];
+} ofdg_spatial_rec;
+struct ofdg_spatial_job {
+  const void* src[OFDG_CROP_PLANES];     /* [n,C,height,width], or NULL                */
+  void*       dst[OFDG_CROP_PLANES];     /* [n,C,out_h,out_w], same element type       */
+  const ofdg_spatial_rec* recs;          /* DEVICE, n records, or NULL: drawn          */
+  ofdg_spatial_rec*       recs_out;      /* DEVICE, n records, or NULL                 */
+  long long first_index;  uint32_t seed;
+  int32_t width, height;                 /* the source size; 0, 0: the context's frame */
+  int32_t out_w, out_h, flags, image_fmt, flow_fmt, occ_fmt;
+  int32_t reserved[2];
+  float zoom_log, rot, squeeze_log, translate;            /* ranges of the draw, all >= 0 */
+  float pair_zoom_log, pair_rot, pair_translate;          /* frame 1 against frame 0      */
+};
+int ofdg_spatial(ofdg_ctx* ctx, const struct ofdg_spatial_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes [n,C,height,width], records in host memory, no
+ * alignment asked of any pointer.  width, height: the source size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (the draw alone: not sanitised; pure, no GPU).  Of `ranges` the seven ranges, flags,
+ * width, height, out_w and out_h are read; the sizes must be set.  OFDG_EINVAL (ofdg_host_last_error) for a NULL pointer, a
+ * size that breaks the rule, unknown flag bits or a range ofdg_spatial refuses. */
+int ofdg_spatial_draw(uint32_t seed, long long index, const struct ofdg_spatial_job* ranges, ofdg_spatial_rec* out);
 
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).

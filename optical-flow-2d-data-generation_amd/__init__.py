@@ -107,6 +107,7 @@ EXPORTS = [
     "ofdg_flow_pyramid", "ofdg_host_flow_pyramid",
     "ofdg_flow_stats_sized", "ofdg_flow_pyramid_sized", "ofdg_crop", "ofdg_host_crop", "ofdg_crop_draw", "ofdg_crop_philox",
     "ofdg_photo", "ofdg_host_photo", "ofdg_photo_draw", "ofdg_debug_photo_table", "ofdg_host_photo_table", "ofdg_host_det_log",
+    "ofdg_spatial", "ofdg_host_spatial", "ofdg_spatial_draw",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -361,6 +362,15 @@ def crop_format(src, dst, height, width):
     uint8, flows float32 / float16, occlusion maps float32 / uint8, labels uint8, one dtype per group -, dst[name] the same
     with one crop_h x crop_w for all.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU
     tensors and numpy arrays)."""
+    n, crop, codes = _plane_dicts(src, dst, height, width)
+    if not 8 <= crop[1] <= width or crop[1] % 8 or not 2 <= crop[0] <= height or crop[0] % 2:
+        raise ValueError("the window must be a multiple of 8 wide, even high and inside %dx%d, got %dx%d" % (width, height, crop[1], crop[0]))
+    return (n, crop[0], crop[1]) + codes
+
+
+def _plane_dicts(src, dst, height, width):
+    """What crop_format and spatial_format share: (n, (out_h, out_w), (image code, flow code, occ code)) of two dicts of planes,
+    whatever the output size."""
     if not src or not isinstance(src, dict) or not isinstance(dst, dict):
         raise ValueError("src and dst must be dicts with at least one of %s" % (CROP_PLANES,))
     for key in list(src) + list(dst):
@@ -388,10 +398,8 @@ def crop_format(src, dst, height, width):
         if _dtype_name(b) != _dtype_name(a) or tuple(b.shape[:-2]) != lead or len(b.shape) != len(a.shape) or (crop is not None and tuple(b.shape[-2:]) != crop):
             raise ValueError("dst[%s] must be %s %s, got %s %s" % (key, _dtype_name(a), lead + (crop if crop else ("crop_h", "crop_w")), _dtype_name(b), tuple(b.shape)))
         crop = tuple(int(v) for v in b.shape[-2:])
-    if not 8 <= crop[1] <= width or crop[1] % 8 or not 2 <= crop[0] <= height or crop[0] % 2:
-        raise ValueError("the window must be a multiple of 8 wide, even high and inside %dx%d, got %dx%d" % (width, height, crop[1], crop[0]))
-    return n, crop[0], crop[1], groups["image"][0].get(groups["image"][1], FMT_F32), groups["flow"][0].get(groups["flow"][1], FMT_F32), \
-        groups["occ"][0].get(groups["occ"][1], FMT_F32)
+    return n, crop, (groups["image"][0].get(groups["image"][1], FMT_F32), groups["flow"][0].get(groups["flow"][1], FMT_F32),
+                     groups["occ"][0].get(groups["occ"][1], FMT_F32))
 
 
 def _crop_flags(hflip, vflip, occ_window):
@@ -560,6 +568,110 @@ def host_photo(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=Non
     return dst, used
 
 
+# the spatial augmentation (ofdg_spatial_rec / struct ofdg_spatial_job / ofdg_spatial, include/ofdg.h)
+SPATIAL_RANDOM_HFLIP, SPATIAL_RANDOM_VFLIP, SPATIAL_OCC_WINDOW = 4, 8, 16
+SPATIAL_RANGES = ("zoom_log", "rot", "squeeze_log", "translate", "pair_zoom_log", "pair_rot", "pair_translate")
+# A starting point after the augmentation of FlowNet (Dosovitskiy, Fischer, Ilg et al., "FlowNet: Learning Optical Flow with
+# Convolutional Networks", ICCV 2015, section 5.1: translation, rotation of +-17 degrees and scaling of 0.9 .. 2.0 per pair,
+# with a smaller relative transform between the two frames; FlowNet 2.0 and PWC-Net keep the scheme and add a squeeze).  Here:
+# zoom by exp(+-0.4) = 0.67 .. 1.49, +-0.3 rad = 17 degrees, squeeze by exp(+-0.15), the window anywhere it fits; frame 1 within
+# 3 per cent, 0.03 rad and 2 source pixels of frame 0.  Not a tuned recipe: every field is a range to be chosen per data set.
+SPATIAL_FLOWNET = dict(zoom_log=0.4, rot=0.3, squeeze_log=0.15, translate=1.0, pair_zoom_log=0.03, pair_rot=0.03, pair_translate=2.0)
+SPATIAL_REC_DOUBLES = 14  # a record as float64 [14]: m[0] = a b c d e g, m[1] likewise, then the 16 reserved bytes
+
+
+class SpatialRec(C.Structure):
+    """ofdg_spatial_rec: the two maps of one sample (112 bytes)."""
+    _fields_ = [("m", (C.c_double * 6) * 2), ("reserved", C.c_int32 * 4)]
+
+
+class SpatialJob(C.Structure):
+    """struct ofdg_spatial_job (224 bytes)."""
+    _fields_ = [("src", C.c_void_p * 8), ("dst", C.c_void_p * 8), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("flags", C.c_int32), ("image_fmt", C.c_int32), ("flow_fmt", C.c_int32),
+                ("occ_fmt", C.c_int32), ("reserved", C.c_int32 * 2)] + [(name, C.c_float) for name in SPATIAL_RANGES]
+
+
+def _spatial_ranges(job, ranges):
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in SPATIAL_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(SPATIAL_RANGES)))
+    for key in SPATIAL_RANGES:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    return job
+
+
+def _spatial_flags(hflip, vflip, occ_window):
+    return (SPATIAL_RANDOM_HFLIP if hflip else 0) | (SPATIAL_RANDOM_VFLIP if vflip else 0) | (SPATIAL_OCC_WINDOW if occ_window else 0)
+
+
+def spatial_format(src, dst, height, width):
+    """(n, out_h, out_w, image code, flow code, occ code) of the planes of Generator.spatial / host_spatial: src and dst are dicts
+    keyed by CROP_PLANES as crop_format takes them, src[name] of the source size height x width, dst[name] of one output size
+    for all, smaller or larger than the source; either size a multiple of 8 wide and even high.  Raises ValueError for
+    anything else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    n, out, codes = _plane_dicts(src, dst, height, width)
+    for what, (h, w) in (("source", (height, width)), ("output", out)):
+        if w < 8 or w % 8 or h < 2 or h % 2:
+            raise ValueError("the %s must be a multiple of 8 wide and even high, got %dx%d" % (what, w, h))
+    return (n, out[0], out[1]) + codes
+
+
+def _spatial_job(src, dst, ptr, codes, size, out_h, out_w, recs, recs_out, first_index, seed, ranges, flags):
+    job = _spatial_ranges(SpatialJob(), ranges)
+    for k, key in enumerate(CROP_PLANES):
+        if key in src:
+            job.src[k], job.dst[k] = ptr(src[key]), ptr(dst[key])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.out_h, job.out_w, job.flags = out_h, out_w, flags
+    job.image_fmt, job.flow_fmt, job.occ_fmt = codes
+    return job
+
+
+def spatial_draw(seed, index, width, height, out_w, out_h, ranges=None, hflip=False, vflip=False):
+    """ofdg_spatial_draw (pure, no GPU): the record of global sample `index` under `seed` for a width x height source, an
+    out_w x out_h window and a dict of ranges (SPATIAL_RANGES; a missing one is 0), before sanitising, as float64 [14]
+    (SPATIAL_REC_DOUBLES: the maps of frame 0 and frame 1, a b c d e g each, then the reserved bytes)."""
+    import numpy as np
+    out = np.zeros((SPATIAL_REC_DOUBLES,), np.float64)
+    job = _spatial_ranges(SpatialJob(), ranges)
+    job.width, job.height, job.out_w, job.out_h, job.flags = int(width), int(height), int(out_w), int(out_h), _spatial_flags(hflip, vflip, False)
+    _host_check(lib().ofdg_spatial_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), _hptr(out)))
+    return out
+
+
+def alloc_spatial(src, out_h, out_w, zero=True):
+    """The destination dict of Generator.spatial for a source dict: every plane of src with its last two dimensions replaced by
+    out_h x out_w (alloc_crop: the output may also be larger than the source)."""
+    return alloc_crop(src, out_h, out_w, zero)
+
+
+def host_spatial(src, out_h, out_w, recs=None, first_index=0, seed=0, ranges=None, hflip=False, vflip=False, occ_window=False):
+    """ofdg_host_spatial (no GPU): the augmentation of HOST arrays - src a dict of numpy arrays keyed by CROP_PLANES, as
+    Generator.spatial takes tensors; recs None (drawn from seed, first_index and ranges) or a float64 array [n,14].  Returns
+    (dst, recs_used): the dict of warped arrays and the float64 [n,14] records after sanitising."""
+    import numpy as np
+    src = {k: np.ascontiguousarray(v) for k, v in src.items()}
+    if not src:
+        raise ValueError("src must hold at least one of %s" % (CROP_PLANES,))
+    height, width = next(iter(src.values())).shape[-2:]
+    dst = alloc_spatial(src, out_h, out_w)
+    n, out_h, out_w, *codes = spatial_format(src, dst, height, width)
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.float64 or recs.shape != (n, SPATIAL_REC_DOUBLES):
+            raise ValueError("recs must be float64 [%d,%d], got %s %s" % (n, SPATIAL_REC_DOUBLES, recs.dtype, recs.shape))
+    used = np.zeros((n, SPATIAL_REC_DOUBLES), np.float64)
+    job = _spatial_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), out_h, out_w, None if recs is None else recs.ctypes.data,
+                       used.ctypes.data, first_index, seed, ranges, _spatial_flags(hflip, vflip, occ_window))
+    _host_check(lib().ofdg_host_spatial(C.byref(job), n, width, height))
+    return dst, used
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -647,6 +759,9 @@ def lib():
         L.ofdg_debug_photo_table.argtypes = [vp, vp, vp]
         L.ofdg_host_photo_table.argtypes = [vp, vp]
         L.ofdg_host_det_log.argtypes = [vp, i32, vp]
+        L.ofdg_spatial.argtypes = [vp, C.POINTER(SpatialJob), i32, vp]
+        L.ofdg_host_spatial.argtypes = [C.POINTER(SpatialJob), i32, i32, i32]
+        L.ofdg_spatial_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(SpatialJob), vp]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1006,6 +1121,29 @@ class Generator:
         job = _photo_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), _optr(recs), _optr(recs_out),
                          first_index, self.params.seed if seed is None else seed, ranges)
         self._check(lib().ofdg_photo(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
+
+    def spatial(self, src, dst, recs=None, first_index=0, seed=None, ranges=None, hflip=False, vflip=False, occ_window=False,
+                recs_out=None, stream=0, size=None):
+        """The spatial augmentation of every plane of a batch in one launch (ofdg_spatial, include/ofdg.h): each sample warped by
+        an affine map of its own - zoom, rotation, squeeze, translation, flips -, frame 1 slightly apart from frame 0, and both
+        flows transformed to match.  src and dst are dicts keyed by CROP_PLANES (any subset), src[name] the [n,C,H,W] tensor a
+        render / forward call wrote, dst[name] the [n,C,out_h,out_w] tensor of the same dtype (alloc_spatial); the output may
+        be smaller or larger than the source.  recs: None - the record of sample i is spatial_draw(seed, first_index + i, ...)
+        with flips drawn when hflip / vflip allow them - or a float64 device tensor [n,14], taken as given; either is
+        sanitised.  ranges: a dict of SPATIAL_RANGES (a missing one is 0; SPATIAL_FLOWNET is a starting point).  seed: default
+        the context's.  occ_window: occ0 / occ1 also become 1 where the flow / flow1 target leaves the output window.
+        recs_out: None or a float64 device tensor [n,14] that receives the records used.  stream: the stream the planes were
+        written on, or STREAM_OWN.  size=(height, width): sources of that size instead of the context's frame.  Asynchronous;
+        there is no in-place form.  Returns dst."""
+        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        n, out_h, out_w, *codes = spatial_format(src, dst, height, width)
+        for t in (recs, recs_out):
+            if t is not None and (str(t.dtype) != "torch.float64" or tuple(t.shape) != (n, SPATIAL_REC_DOUBLES)):
+                raise ValueError("recs and recs_out must be float64 [%d,%d], got %s %s" % (n, SPATIAL_REC_DOUBLES, t.dtype, tuple(t.shape)))
+        job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), out_h, out_w, _optr(recs),
+                           _optr(recs_out), first_index, self.params.seed if seed is None else seed, ranges, _spatial_flags(hflip, vflip, occ_window))
+        self._check(lib().ofdg_spatial(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
     def debug_photo_table(self, rec):
@@ -1647,12 +1785,29 @@ class FlowLoader:
     (Generator.photo, enqueued on the same internal stream right behind the batch - behind the crop when there is one, on the
     cropped frames; records drawn from the context's seed and the batch's first global index, so start= and sharding make the
     same pixels); every batch is then (image0, image1, flow, {...}) and the dict also holds "photo" (float32 [n,16], the
-    records used)."""
+    records used).
+    spatial=ranges (a dict of SPATIAL_RANGES, SPATIAL_FLOWNET for one) with spatial_size=(out_h, out_w): every batch is warped
+    per sample into an out_h x out_w window (Generator.spatial into a second ring of buffers, enqueued right behind the batch
+    on the same internal stream, exactly where the crop would go; records drawn from the context's seed and the batch's first
+    global index - shard_first_index of its step -, so start= and sharding reproduce the same warps; spatial_hflip /
+    spatial_vflip allow drawn flips, spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  photo=,
+    stats= and pyramid= then work on the WARPED planes; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and
+    frame 1, a b c d e g each, then padding).  crop= with spatial= raises - the spatial step contains the window -, and so
+    does objects=True: its boxes are of the unwarped frame."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
-                 crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, **kw):
+                 crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
+                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, **kw):
         import torch
+        self.spatial = None if spatial is None else dict(spatial)
+        _spatial_ranges(SpatialJob(), self.spatial)  # (raises for a name that is no range)
+        if self.spatial is not None and crop is not None:
+            raise ValueError("crop= does not combine with spatial=: the spatial step contains the window (spatial_size=)")
+        if self.spatial is not None and objects:
+            raise ValueError("objects=True does not combine with spatial=: the table's boxes are of the unwarped frame")
+        if self.spatial is not None and spatial_size is None:
+            raise ValueError("spatial= needs spatial_size=(out_h, out_w)")
         self.photo = None if photo is None else dict(photo)
         _photo_ranges(PhotoJob(), self.photo)  # (raises for a name that is no range)
         if objects and crop is not None:
@@ -1694,6 +1849,14 @@ class FlowLoader:
                 # against the internal stream the first crops run on)
                 self.cbufs[j] = (alloc_crop(planes, *self.crop, zero=False), torch.empty((p.batch_size, 4), dtype=torch.int32, device="cuda"))
                 crop_format(planes, self.cbufs[j][0], p.height, p.width)  # (raises for a window the frame does not allow)
+        self.spatial_flags = (bool(spatial_hflip), bool(spatial_vflip), bool(spatial_occ_window))
+        if self.spatial is not None:            # the warped planes and their records take the crop's place: the same second ring
+            self.crop = (int(spatial_size[0]), int(spatial_size[1]))
+            for j in range(self.prefetch):
+                planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
+                self.cbufs[j] = (alloc_spatial(planes, *self.crop, zero=False),
+                                 torch.empty((p.batch_size, SPATIAL_REC_DOUBLES), dtype=torch.float64, device="cuda"))
+                spatial_format(planes, self.cbufs[j][0], p.height, p.width)  # (raises for a size the rule does not allow)
         ph, pw = self.crop if self.crop is not None else (p.height, p.width)
         self.pbufs = [alloc_flow_pyramid(p.batch_size, ph, pw, self.pyramid, flow_dtype, bool(pyramid_weights))
                       if self.pyramid else None for _ in range(self.prefetch)]
@@ -1728,8 +1891,13 @@ class FlowLoader:
         p = self.gen.params
         planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
         out, recs = self.cbufs[j]
-        self.gen.crop(planes, out, first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank), hflip=self.crop_flips[0],
-                      vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
+        first = shard_first_index(step, p.batch_size, p.world_size, p.rank)
+        if self.spatial is not None:
+            self.gen.spatial(planes, out, first_index=first, ranges=self.spatial, hflip=self.spatial_flags[0], vflip=self.spatial_flags[1],
+                             occ_window=self.spatial_flags[2], recs_out=recs, stream=s)
+        else:
+            self.gen.crop(planes, out, first_index=first, hflip=self.crop_flips[0],
+                          vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
         self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
         self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
         self.ready[j].record(chain)
@@ -1784,7 +1952,7 @@ class FlowLoader:
         if self.crop is not None:
             out, recs = self.cbufs[j]
             more = {k: v for k, v in out.items() if k not in ("image0", "image1", "flow")}
-            more["crop"] = recs
+            more["spatial" if self.spatial is not None else "crop"] = recs
             if self.rbufs[j] is not None:
                 more["photo"] = self.rbufs[j]
             self._add_reductions(more, j)

@@ -458,4 +458,115 @@ int ofdg_host_photo(const struct ofdg_photo_job* job, int n_samples, int width, 
   return OFDG_OK;
 }
 
+// ofdg_spatial on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
+// inverse, the tap, the blend, the flow's transform and the occlusion rule are the functions the kernel runs
+// (csrc/ofdg_device.h); elements are moved with memcpy, so no alignment is asked.
+int ofdg_spatial_draw(uint32_t seed, long long index, const struct ofdg_spatial_job* ranges, ofdg_spatial_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_spatial_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevSpatialJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  int W = 0, H = 0;
+  const char* why = j.width == 0 && j.height == 0 ? "width and height must be set" : spatial_plane_size(j, &W, &H);
+  if (!why) why = spatial_draw_error(j);
+  if (why) { g_host_error = std::string("ofdg_spatial_draw: ") + why; return OFDG_EINVAL; }
+  const DevSpatialRec r = spatial_draw_rec(seed, (unsigned long long)index, j, W, H);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+struct SpatialElems {  // a plane's elements widened to float32: float32, binary16 or uint8
+  const uint8_t* p;
+  int es;
+  bool half;
+  float at(size_t i) const {
+    if (es == 1) return (float)p[i];
+    if (half) return FlowPlane{p, OFDG_FMT_F16}.at(i);
+    float f;
+    std::memcpy(&f, p + 4 * i, 4);
+    return f;
+  }
+};
+int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int width, int height) {
+  const DevSpatialJob* const j = reinterpret_cast<const DevSpatialJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why && (width > kSpatialMaxSide || height > kSpatialMaxSide)) why = "width and height must not exceed 2^20";
+  if (!why) why = spatial_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_spatial: ") + why; return OFDG_EINVAL; }
+  const int W = width, H = height, ow = j->out_w, oh = j->out_h;
+  const size_t frame = (size_t)W * H, window = (size_t)ow * oh;
+  const bool occ_window = j->flags & OFDG_SPATIAL_OCC_WINDOW;
+  const int ies = fmt_elem_bytes(j->image_fmt), fes = fmt_elem_bytes(j->flow_fmt), oes = fmt_elem_bytes(j->occ_fmt);
+  for (int i = 0; i < n_samples; ++i) {
+    DevSpatialRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = spatial_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j, W, H);
+    r = spatial_sanitise(r, W, H, ow, oh);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    for (int f = 0; f < 2; ++f) {
+      const double* const m = r.m[f];
+      const SpatialInv other = spatial_inverse(r.m[1 - f]);
+      const void* const s_img = j->src[OFDG_CROP_IMAGE0 + f];
+      const void* const s_flow = j->src[OFDG_CROP_FLOW + f];
+      const void* const s_occ = j->src[OFDG_CROP_OCC0 + f];
+      const void* const s_lab = j->src[OFDG_CROP_LABEL0 + f];
+      uint8_t* const d_img = static_cast<uint8_t*>(j->dst[OFDG_CROP_IMAGE0 + f]);
+      uint8_t* const d_flow = static_cast<uint8_t*>(j->dst[OFDG_CROP_FLOW + f]);
+      uint8_t* const d_occ = static_cast<uint8_t*>(j->dst[OFDG_CROP_OCC0 + f]);
+      uint8_t* const d_lab = static_cast<uint8_t*>(j->dst[OFDG_CROP_LABEL0 + f]);
+      if (!s_img && !s_flow && !s_occ && !s_lab) continue;
+      const SpatialElems img{static_cast<const uint8_t*>(s_img), ies, false};
+      const SpatialElems flow{static_cast<const uint8_t*>(s_flow), fes, fes == 2};
+      for (int Y = 0; Y < oh; ++Y) {
+        const double rowx = spatial_row_term(m[1], Y), rowy = spatial_row_term(m[4], Y);
+        for (int X = 0; X < ow; ++X) {
+          const double qx = spatial_coord(m[0], X, rowx, m[2]), qy = spatial_coord(m[3], X, rowy, m[5]);
+          const int Qx = spatial_fixed(qx), Qy = spatial_fixed(qy);
+          const size_t to = (size_t)Y * ow + X;
+          const size_t near = (size_t)spatial_clamp((Qy + 128) >> 8, H) * W + spatial_clamp((Qx + 128) >> 8, W);
+          if (s_img) {
+            const int fx = Qx & 255, fy = Qy & 255;
+            const size_t x0 = spatial_clamp(Qx >> 8, W), x1 = spatial_clamp((Qx >> 8) + 1, W);
+            const size_t y0 = (size_t)spatial_clamp(Qy >> 8, H) * W, y1 = (size_t)spatial_clamp((Qy >> 8) + 1, H) * W;
+            for (int c = 0; c < 3; ++c) {
+              const size_t base = ((size_t)i * 3 + c) * frame;
+              const float v = spatial_blend(img.at(base + y0 + x0), img.at(base + y0 + x1), img.at(base + y1 + x0), img.at(base + y1 + x1), fx, fy);
+              uint8_t* const o = d_img + (((size_t)i * 3 + c) * window + to) * ies;
+              if (ies == 4) std::memcpy(o, &v, 4);
+              else *o = (uint8_t)spatial_to_byte(v);
+            }
+          }
+          double px = 0.0, py = 0.0;
+          if (s_flow) {
+            const float u = flow.at((size_t)i * 2 * frame + near), v = flow.at(((size_t)i * 2 + 1) * frame + near);
+            spatial_partner(qx, qy, u, v, other, &px, &py);
+            const float ou = spatial_flow_of(px, X), ov = spatial_flow_of(py, Y);
+            uint8_t* const o0 = d_flow + ((size_t)i * 2 * window + to) * fes;
+            uint8_t* const o1 = d_flow + (((size_t)i * 2 + 1) * window + to) * fes;
+            if (fes == 4) {
+              std::memcpy(o0, &ou, 4);
+              std::memcpy(o1, &ov, 4);
+            } else {
+              const uint16_t hu = (uint16_t)spatial_half_bits(ou), hv = (uint16_t)spatial_half_bits(ov);
+              std::memcpy(o0, &hu, 2);
+              std::memcpy(o1, &hv, 2);
+            }
+          }
+          if (s_occ) {
+            bool hidden = OccPlane{static_cast<const uint8_t*>(s_occ) + ((size_t)i * frame + near) * oes, j->occ_fmt}.at(0);
+            hidden = hidden || !spatial_inside(Qx, Qy, W, H);
+            if (occ_window) hidden = hidden || !(spatial_partner_inside(px, ow) && spatial_partner_inside(py, oh));
+            uint8_t* const o = d_occ + ((size_t)i * window + to) * oes;
+            const float one = hidden ? 1.0f : 0.0f;
+            if (oes == 4) std::memcpy(o, &one, 4);
+            else *o = hidden ? 1 : 0;
+          }
+          if (s_lab) d_lab[(size_t)i * window + to] = static_cast<const uint8_t*>(s_lab)[(size_t)i * frame + near];
+        }
+      }
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

@@ -3791,4 +3791,188 @@ __global__ __launch_bounds__(256) void photo_table_kernel(const DevPhotoRec* __r
       photo_table_entry(f ? r.gamma[1] : r.gamma[0], gain, f ? r.contrast[1] : r.contrast[0], f ? r.brightness[1] : r.brightness[0], (int)threadIdx.x);
 }
 
+// --------------------------------------------------------------------------
+// Spatial augmentation (ofdg_spatial): every plane of a batch resampled through an affine map per (sample, frame) - a gather
+// with bilinear interpolation for the frames, the nearest tap for flow, maps and labels -, the flow transformed to match, in
+// one launch.  The functions of the definition are the host twin's (csrc/ofdg_device.h), so the result is the twin's bit for
+// bit.
+// --------------------------------------------------------------------------
+// The destination of a (plane, channel, sample) is out_w * out_h elements without gaps; 16 consecutive elements - a unit - are
+// one 16-byte piece of a uint8 plane, two of a binary16 and four of a float32 one.  A unit is two runs of 8 pixels, each
+// inside one row (out_w % 8 == 0; where out_w / 8 is odd every other unit has its runs in two rows, which is why units are
+// counted in row PAIRS: rows 2P and 2P + 1 together are out_w / 8 whole units).  Four neighbouring lanes own a unit, a lane
+// four consecutive pixels of it, so the lanes of a wave read neighbouring source pixels in the same instruction: a line
+// fetched serves its lanes at once and the next three pixels right behind (a lane that walked 16 pixels on its own asked for
+// every line 16 times, from L2: CHANGELOG).  The coordinates, the taps and the weights of a pixel are computed once and serve
+// every plane of the frame: three image channels, two flow components, the map and the label.  Every store is one 16-byte
+// piece: a float32 piece is a lane's own; a binary16 piece is gathered by the even lane of a pair, a uint8 piece by the
+// first lane of the four (wave shuffles, no LDS allocated), so a wave's store instruction writes whole consecutive rows of
+// the tile.  A workgroup owns a 2-D tile of kSpatialTileQ units x (64 / kSpatialTileQ) * kSpatialPasses row pairs - a compact
+// footprint in the source also when the map rotates - and walks it in kSpatialPasses passes; blockIdx.x counts the tiles,
+// blockIdx.y the samples, blockIdx.z the frames that have a plane.  Sources are read element by element at computed, clamped
+// indices (dword / ushort / ubyte loads: nothing is asked of x), so no record reaches outside a plane.  The record is drawn
+// or read, sanitised and inverted on uniform values once per (workgroup, sample); workgroup 0 writes it back from lane 0
+// with vector stores.  No LDS, no atomics, no scratch.
+constexpr int kSpatialThreads = 256;
+#ifndef OFDG_SPATIAL_TILE_Q
+#define OFDG_SPATIAL_TILE_Q 8
+#endif
+#ifndef OFDG_SPATIAL_PASSES
+#define OFDG_SPATIAL_PASSES 2
+#endif
+constexpr int kSpatialTileQ = OFDG_SPATIAL_TILE_Q;                   // units of 16 pixels across a tile (measured against 4 and 16: CHANGELOG)
+constexpr int kSpatialRowPairs = kSpatialThreads / 4 / kSpatialTileQ;  // row pairs of one pass
+constexpr int kSpatialPasses = OFDG_SPATIAL_PASSES;                  // 8 pixels a lane: the record's draw is paid once for them (measured against 4 and 8: CHANGELOG)
+constexpr int kSpatialTileP = kSpatialRowPairs * kSpatialPasses;     // row pairs of a tile
+static_assert(kSpatialTileQ * kSpatialRowPairs * 4 == kSpatialThreads, "four lanes per unit of a pass");
+__device__ __forceinline__ void spatial_store(void* p, crop_u32x4 v) {
+  crop_store(static_cast<crop_u32x4*>(p), v);  // (whole pieces, read next by another kernel: measured against plain stores, CHANGELOG)
+}
+template <bool kImageU8, bool kFlowHalf, bool kOccU8>
+__global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpatialJob job, int n, int W, int H, uint32_t tiles_x) {
+  constexpr int kImageES = kImageU8 ? 1 : 4, kFlowES = kFlowHalf ? 2 : 4, kOccES = kOccU8 ? 1 : 4;
+  const int ow = job.out_w, oh = job.out_h;
+  const uint32_t R = (uint32_t)ow / 8u, pairs = (uint32_t)oh / 2u;  // units per row pair, row pairs
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const uint32_t j = threadIdx.x & 3u, u = threadIdx.x >> 2;  // the lane's four pixels of its unit; the unit of the pass
+  const uint32_t q = tx * kSpatialTileQ + u % kSpatialTileQ, P0 = ty * kSpatialTileP + u / kSpatialTileQ;
+  const uint32_t t = 2u * q + (j >> 1);  // the run of 8 among the 2 R runs of a row pair
+  const bool second = t >= R;
+  const int X0 = (int)((t - (second ? R : 0u)) * 8u + (j & 1u) * 4u);
+  const bool frame0 = job.src[0] || job.src[2] || job.src[4] || job.src[6];
+  const int f = (blockIdx.z != 0u || !frame0) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.src[1] : job.src[0]);
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.src[3] : job.src[2]);
+  const uint8_t* const s_occ = static_cast<const uint8_t*>(f ? job.src[5] : job.src[4]);
+  const uint8_t* const s_lab = static_cast<const uint8_t*>(f ? job.src[7] : job.src[6]);
+  uint8_t* const d_img = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+  uint8_t* const d_flow = static_cast<uint8_t*>(f ? job.dst[3] : job.dst[2]);
+  uint8_t* const d_occ = static_cast<uint8_t*>(f ? job.dst[5] : job.dst[4]);
+  uint8_t* const d_lab = static_cast<uint8_t*>(f ? job.dst[7] : job.dst[6]);
+  const bool occ_window = job.flags & 16;
+  const size_t frame = (size_t)W * H, window = (size_t)ow * oh;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    DevSpatialRec r;
+    if (job.recs) r = job.recs[i];
+    else r = spatial_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job, W, H);
+    r = spatial_sanitise(r, W, H, ow, oh);
+    if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u) {
+      double2* const o = reinterpret_cast<double2*>(job.recs_out + i);
+      o[0] = make_double2(r.m[0][0], r.m[0][1]); o[1] = make_double2(r.m[0][2], r.m[0][3]); o[2] = make_double2(r.m[0][4], r.m[0][5]);
+      o[3] = make_double2(r.m[1][0], r.m[1][1]); o[4] = make_double2(r.m[1][2], r.m[1][3]); o[5] = make_double2(r.m[1][4], r.m[1][5]);
+      *reinterpret_cast<int4*>(o + 6) = make_int4(0, 0, 0, 0);
+    }
+    if (q >= R) continue;  // (a whole unit, its four lanes together)
+    const double ma = f ? r.m[1][0] : r.m[0][0], mb = f ? r.m[1][1] : r.m[0][1], mc = f ? r.m[1][2] : r.m[0][2];
+    const double md = f ? r.m[1][3] : r.m[0][3], me = f ? r.m[1][4] : r.m[0][4], mg = f ? r.m[1][5] : r.m[0][5];
+    const double om[6] = {f ? r.m[0][0] : r.m[1][0], f ? r.m[0][1] : r.m[1][1], f ? r.m[0][2] : r.m[1][2],
+                          f ? r.m[0][3] : r.m[1][3], f ? r.m[0][4] : r.m[1][4], f ? r.m[0][5] : r.m[1][5]};
+    const SpatialInv other = spatial_inverse(om);
+    const uint8_t* const si = s_img + (size_t)i * 3 * frame * kImageES;
+    const uint8_t* const sf = s_flow + (size_t)i * 2 * frame * kFlowES;
+    const uint8_t* const so = s_occ + (size_t)i * frame * kOccES;
+    const uint8_t* const sl = s_lab + (size_t)i * frame;
+#pragma unroll 1
+    for (int pass = 0; pass < kSpatialPasses; ++pass) {
+      const uint32_t P = P0 + (uint32_t)pass * kSpatialRowPairs;
+      if (P >= pairs) break;  // (whole units again)
+      const int Y = (int)(2u * P + (second ? 1u : 0u));
+      const size_t at = ((size_t)P * R + q) * 16u + 4u * j;  // the lane's first element in a channel of the destination
+      const double rowx = spatial_row_term(mb, Y), rowy = spatial_row_term(me, Y);
+      float img[3][4], fu[4], fv[4];
+      uint32_t hid[4], lab[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int X = X0 + p;
+        const double qx = spatial_coord(ma, X, rowx, mc), qy = spatial_coord(md, X, rowy, mg);
+        const int Qx = spatial_fixed(qx), Qy = spatial_fixed(qy);
+        const uint32_t near = (uint32_t)spatial_clamp((Qy + 128) >> 8, H) * (uint32_t)W + (uint32_t)spatial_clamp((Qx + 128) >> 8, W);
+        if (s_img) {
+          const int fx = Qx & 255, fy = Qy & 255;
+          const uint32_t x0 = (uint32_t)spatial_clamp(Qx >> 8, W), x1 = (uint32_t)spatial_clamp((Qx >> 8) + 1, W);
+          const uint32_t y0 = (uint32_t)spatial_clamp(Qy >> 8, H) * (uint32_t)W, y1 = (uint32_t)spatial_clamp((Qy >> 8) + 1, H) * (uint32_t)W;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            float e00, e10, e01, e11;
+            if constexpr (kImageU8) {
+              const uint8_t* const pc = si + (size_t)c * frame;
+              e00 = (float)pc[y0 + x0]; e10 = (float)pc[y0 + x1]; e01 = (float)pc[y1 + x0]; e11 = (float)pc[y1 + x1];
+            } else {
+              const float* const pc = reinterpret_cast<const float*>(si) + (size_t)c * frame;
+              e00 = pc[y0 + x0]; e10 = pc[y0 + x1]; e01 = pc[y1 + x0]; e11 = pc[y1 + x1];
+            }
+            img[c][p] = spatial_blend(e00, e10, e01, e11, fx, fy);
+          }
+        }
+        double px = 0.0, py = 0.0;
+        if (s_flow) {
+          float su, sv;
+          if constexpr (kFlowHalf) {
+            const _Float16* const pf = reinterpret_cast<const _Float16*>(sf);
+            su = (float)pf[near]; sv = (float)pf[frame + near];
+          } else {
+            const float* const pf = reinterpret_cast<const float*>(sf);
+            su = pf[near]; sv = pf[frame + near];
+          }
+          spatial_partner(qx, qy, su, sv, other, &px, &py);
+          fu[p] = spatial_flow_of(px, X);
+          fv[p] = spatial_flow_of(py, Y);
+        }
+        if (s_occ) {
+          bool hidden;
+          if constexpr (kOccU8) hidden = so[near] != 0;
+          else hidden = reinterpret_cast<const float*>(so)[near] != 0.0f;
+          hidden = hidden || !spatial_inside(Qx, Qy, W, H);
+          if (occ_window) hidden = hidden || !(spatial_partner_inside(px, ow) && spatial_partner_inside(py, oh));
+          hid[p] = hidden ? 1u : 0u;
+        }
+        if (s_lab) lab[p] = sl[near];
+      }
+      // (the lanes of a unit are all here: q and P are the unit's)
+      if (s_img) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (kImageU8) {
+            const uint32_t w = spatial_to_byte(img[c][0]) | (spatial_to_byte(img[c][1]) << 8) | (spatial_to_byte(img[c][2]) << 16) | (spatial_to_byte(img[c][3]) << 24);
+            const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+            if (j == 0u) spatial_store(d_img + ((size_t)i * 3 + c) * window + at, o);
+          } else {
+            const crop_u32x4 o = {__float_as_uint(img[c][0]), __float_as_uint(img[c][1]), __float_as_uint(img[c][2]), __float_as_uint(img[c][3])};
+            spatial_store(d_img + (((size_t)i * 3 + c) * window + at) * 4u, o);
+          }
+        }
+      }
+      if (s_flow) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const float* const v = c ? fv : fu;
+          if constexpr (kFlowHalf) {
+            const uint32_t w0 = spatial_half_bits(v[0]) | (spatial_half_bits(v[1]) << 16), w1 = spatial_half_bits(v[2]) | (spatial_half_bits(v[3]) << 16);
+            const crop_u32x4 o = {w0, w1, (uint32_t)__shfl_down((int)w0, 1), (uint32_t)__shfl_down((int)w1, 1)};
+            if ((j & 1u) == 0u) spatial_store(d_flow + (((size_t)i * 2 + c) * window + at) * 2u, o);
+          } else {
+            const crop_u32x4 o = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+            spatial_store(d_flow + (((size_t)i * 2 + c) * window + at) * 4u, o);
+          }
+        }
+      }
+      if (s_occ) {
+        if constexpr (kOccU8) {
+          const uint32_t w = hid[0] | (hid[1] << 8) | (hid[2] << 16) | (hid[3] << 24);
+          const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+          if (j == 0u) spatial_store(d_occ + (size_t)i * window + at, o);
+        } else {
+          const crop_u32x4 o = {hid[0] ? 0x3f800000u : 0u, hid[1] ? 0x3f800000u : 0u, hid[2] ? 0x3f800000u : 0u, hid[3] ? 0x3f800000u : 0u};
+          spatial_store(d_occ + ((size_t)i * window + at) * 4u, o);
+        }
+      }
+      if (s_lab) {
+        const uint32_t w = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+        const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+        if (j == 0u) spatial_store(d_lab + (size_t)i * window + at, o);
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -498,6 +498,250 @@ inline const char* photo_arg_error(const DevPhotoJob* j, int n, int width, int h
   return nullptr;
 }
 
+// ---- Spatial augmentation (ofdg_spatial, include/ofdg.h) -------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the inverse, the tap, the blend, the flow's transform, the occlusion rule and the argument rules.  Compiled
+// without contraction, so every operation below is its own rounding.
+struct DevSpatialRec {  // ofdg_spatial_rec, field for field
+  double m[2][6];       // [frame]{a, b, c, d, e, g}
+  int32_t reserved[4];
+};
+struct DevSpatialJob {  // struct ofdg_spatial_job, field for field
+  const void* src[kCropPlanes];
+  void* dst[kCropPlanes];
+  const DevSpatialRec* recs;
+  DevSpatialRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, out_w, out_h, flags, image_fmt, flow_fmt, occ_fmt;
+  int32_t reserved[2];
+  float zoom_log, rot, squeeze_log, translate, pair_zoom_log, pair_rot, pair_translate;
+};
+static_assert(sizeof(ofdg_spatial_rec) == sizeof(DevSpatialRec) && sizeof(DevSpatialRec) == 112 && offsetof(ofdg_spatial_rec, reserved) == offsetof(DevSpatialRec, reserved) &&
+              offsetof(DevSpatialRec, reserved) == 96, "ofdg_spatial_rec: 112 bytes without padding, the layout the kernel reads and writes");
+static_assert(sizeof(struct ofdg_spatial_job) == sizeof(DevSpatialJob) && sizeof(DevSpatialJob) == 224 && offsetof(struct ofdg_spatial_job, dst) == offsetof(DevSpatialJob, dst) &&
+              offsetof(struct ofdg_spatial_job, recs) == offsetof(DevSpatialJob, recs) && offsetof(struct ofdg_spatial_job, recs_out) == offsetof(DevSpatialJob, recs_out) &&
+              offsetof(struct ofdg_spatial_job, first_index) == offsetof(DevSpatialJob, first_index) && offsetof(struct ofdg_spatial_job, seed) == offsetof(DevSpatialJob, seed) &&
+              offsetof(struct ofdg_spatial_job, width) == offsetof(DevSpatialJob, width) && offsetof(struct ofdg_spatial_job, out_w) == offsetof(DevSpatialJob, out_w) &&
+              offsetof(struct ofdg_spatial_job, occ_fmt) == offsetof(DevSpatialJob, occ_fmt) && offsetof(struct ofdg_spatial_job, reserved) == offsetof(DevSpatialJob, reserved) &&
+              offsetof(DevSpatialJob, reserved) == 188 && offsetof(struct ofdg_spatial_job, zoom_log) == offsetof(DevSpatialJob, zoom_log) &&
+              offsetof(struct ofdg_spatial_job, pair_translate) == offsetof(DevSpatialJob, pair_translate) && offsetof(DevSpatialJob, pair_translate) == 220,
+              "struct ofdg_spatial_job: 224 bytes, the layout the kernel takes");
+static_assert(OFDG_SPATIAL_RANDOM_HFLIP == 4 && OFDG_SPATIAL_RANDOM_VFLIP == 8 && OFDG_SPATIAL_OCC_WINDOW == 16, "spatial_draw_rec and spatial_kernel spell these codes out");
+constexpr int kSpatialMaxSide = 1 << 20;  // of a source or output plane: (side - 1) * 256 stays far inside an int
+OFDG_HD_FN double spatial_abs(double x) { return x < 0.0 ? -x : x; }
+OFDG_HD_FN double spatial_plus_zero(double x) { return x == 0.0 ? 0.0 : x; }
+// a, b, d, e of one frame into m[0], m[1], m[3], m[4]: zoom exp(lz), squeeze exp(lq), rotation th, flips h, v = +-1
+OFDG_HD_FN void spatial_linear(float lz, float th, float lq, double h, double v, double* m) {
+  const float lx = lz + lq, ly = lz - lq;
+  const double gx = ofdg_det_exp(-(double)lx), gy = ofdg_det_exp(-(double)ly);
+  double s, c;
+  ofdg_det_sincos((double)th, &s, &c);
+  m[0] = spatial_plus_zero(c * gx * h);
+  m[1] = spatial_plus_zero(-(s * gy) * v);
+  m[3] = spatial_plus_zero(s * gx * h);
+  m[4] = spatial_plus_zero(c * gy * v);
+}
+// c (or g) of a frame: the centre `at` of the window minus where the linear part puts the window's centre
+OFDG_HD_FN double spatial_offset(double at, double p, double q, double hw, double hh) {
+  const double t0 = p * hw, t1 = q * hh;
+  return at - (t0 + t1);
+}
+// the centre of frame 0 on one axis of a source of `side` pixels: (side - 1) / 2 + (tf * translate) * slack
+OFDG_HD_FN double spatial_centre(int side, double p, double q, double hw, double hh, float tf, float translate) {
+  const double mid = (double)(side - 1) / 2.0;
+  const double t0 = spatial_abs(p) * hw, t1 = spatial_abs(q) * hh;
+  const double ex = t0 + t1;
+  double slack = mid - ex;
+  slack = slack > 0.0 ? slack : 0.0;
+  const double f = (double)tf * (double)translate;
+  return mid + f * slack;
+}
+// The record of global sample g for a W x H source: Philox blocks 0, 1, 2 under the sampler's key of g at the counters {j, 0,
+// 0x0c73, 0}.  `j` supplies the seven ranges, the flags and the output size.
+OFDG_HD_FN DevSpatialRec spatial_draw_rec(uint32_t seed, unsigned long long g, const DevSpatialJob& j, int W, int H) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords w0 = crop_philox(CropWords{0u, 0u, 0x0c73u, 0u}, k0, k1);
+  const CropWords w1 = crop_philox(CropWords{1u, 0u, 0x0c73u, 0u}, k0, k1);
+  const CropWords w2 = crop_philox(CropWords{2u, 0u, 0x0c73u, 0u}, k0, k1);
+  const float lz = photo_sym(w0.x, j.zoom_log), th = photo_sym(w0.y, j.rot), lq = photo_sym(w0.z, j.squeeze_log);
+  const double h = ((j.flags & 4) && (w0.w & 1u)) ? -1.0 : 1.0, v = ((j.flags & 8) && ((w0.w >> 1) & 1u)) ? -1.0 : 1.0;
+  const float tfx = 2.0f * photo_unit(w1.x) - 1.0f, tfy = 2.0f * photo_unit(w1.y) - 1.0f;
+  const float dlz = photo_sym(w2.x, j.pair_zoom_log), dth = photo_sym(w2.y, j.pair_rot);
+  const float dtx = photo_sym(w2.z, j.pair_translate), dty = photo_sym(w2.w, j.pair_translate);
+  const double hw = (double)(j.out_w - 1) / 2.0, hh = (double)(j.out_h - 1) / 2.0;
+  DevSpatialRec r;
+  spatial_linear(lz, th, lq, h, v, r.m[0]);
+  const double cx = spatial_centre(W, r.m[0][0], r.m[0][1], hw, hh, tfx, j.translate);
+  const double cy = spatial_centre(H, r.m[0][3], r.m[0][4], hw, hh, tfy, j.translate);
+  r.m[0][2] = spatial_offset(cx, r.m[0][0], r.m[0][1], hw, hh);
+  r.m[0][5] = spatial_offset(cy, r.m[0][3], r.m[0][4], hw, hh);
+  const float lz1 = lz + dlz, th1 = th + dth;
+  spatial_linear(lz1, th1, lq, h, v, r.m[1]);
+  r.m[1][2] = spatial_offset(cx + (double)dtx, r.m[1][0], r.m[1][1], hw, hh);
+  r.m[1][5] = spatial_offset(cy + (double)dty, r.m[1][3], r.m[1][4], hw, hh);
+  for (int k = 0; k < 4; ++k) r.reserved[k] = 0;
+  return r;
+}
+OFDG_HD_FN double spatial_det(const double* m) {
+  const double p = m[0] * m[4], q = m[1] * m[3];
+  return p - q;
+}
+// What is used of a record, given or drawn: a frame whose map is not finite, out of bounds or (nearly) singular becomes the
+// centred integer window.  (A comparison with a NaN fails, so a NaN fails its bound.)
+OFDG_HD_FN DevSpatialRec spatial_sanitise(DevSpatialRec r, int W, int H, int out_w, int out_h) {
+  for (int f = 0; f < 2; ++f) {
+    double* const m = r.m[f];
+    bool ok = spatial_abs(m[0]) <= 64.0 && spatial_abs(m[1]) <= 64.0 && spatial_abs(m[3]) <= 64.0 && spatial_abs(m[4]) <= 64.0;
+    ok = ok && spatial_abs(m[2]) <= 1048576.0 && spatial_abs(m[5]) <= 1048576.0;
+    const double det = spatial_abs(spatial_det(m));
+    ok = ok && det >= 0.000244140625 && det <= 4096.0;
+    if (!ok) {
+      m[0] = 1.0; m[1] = 0.0; m[2] = (double)((W - out_w) >> 1);
+      m[3] = 0.0; m[4] = 1.0; m[5] = (double)((H - out_h) >> 1);
+    }
+  }
+  for (int k = 0; k < 4; ++k) r.reserved[k] = 0;
+  return r;
+}
+// The inverse of a sanitised frame's map (its linear part, and the offsets the target is taken against), made once per sample.
+struct SpatialInv {
+  double ia, ib, id, ie, c, g;
+};
+OFDG_HD_FN SpatialInv spatial_inverse(const double* m) {
+  const double det = spatial_det(m);
+  SpatialInv v;
+  v.ia = m[4] / det; v.ib = -m[1] / det; v.id = -m[3] / det; v.ie = m[0] / det;
+  v.c = m[2]; v.g = m[5];
+  return v;
+}
+// One coordinate of a destination pixel: q = (p * X + r * Y) + o, three roundings.  `row` = fl64(r * Y) is the same for a row.
+OFDG_HD_FN double spatial_row_term(double r, int Y) { return r * (double)Y; }
+OFDG_HD_FN double spatial_coord(double p, int X, double row, double o) {
+  const double t = p * (double)X;
+  const double s = t + row;
+  return s + o;
+}
+// 24.8 fixed point of a coordinate, saturating at +-2^30
+OFDG_HD_FN int spatial_fixed(double q) {
+  const double s = q * 256.0;
+  double t = floor(s + 0.5);
+  t = t < -1073741824.0 ? -1073741824.0 : t;
+  t = t > 1073741824.0 ? 1073741824.0 : t;
+  return (int)t;
+}
+OFDG_HD_FN int spatial_clamp(int i, int side) { return i < 0 ? 0 : i > side - 1 ? side - 1 : i; }
+OFDG_HD_FN bool spatial_inside(int Qx, int Qy, int W, int H) { return Qx >= 0 && Qx <= (W - 1) * 256 && Qy >= 0 && Qy <= (H - 1) * 256; }
+OFDG_HD_FN float spatial_quiet(float v) {  // a NaN as 0x7FC00000
+  const uint32_t bits = 0x7FC00000u;
+  float nan;
+  memcpy(&nan, &bits, 4);
+  return v != v ? nan : v;
+}
+// The bilinear blend of four elements widened to float32, with the fractions fx, fy in 0..255
+OFDG_HD_FN float spatial_blend(float e00, float e10, float e01, float e11, int fx, int fy) {
+  const float w00 = (float)((256 - fx) * (256 - fy)), w10 = (float)(fx * (256 - fy)), w01 = (float)((256 - fx) * fy), w11 = (float)(fx * fy);
+  const float p00 = w00 * e00, p10 = w10 * e10, p01 = w01 * e01, p11 = w11 * e11;
+  const float top = p00 + p10, bottom = p01 + p11;
+  const float sum = top + bottom;
+  return spatial_quiet(sum * 1.52587890625e-05f);
+}
+OFDG_HD_FN uint32_t spatial_to_byte(float v) { return (uint32_t)photo_index(v); }  // clamped to [0, 255] (a NaN becomes 0), then to nearest even
+// Where the pixel at (qx, qy) of its own frame's source, moving by (u, v), lands in the OTHER frame's destination
+OFDG_HD_FN void spatial_partner(double qx, double qy, float u, float v, const SpatialInv& o, double* px, double* py) {
+  const double tx = qx + (double)u, ty = qy + (double)v;
+  const double dx = tx - o.c, dy = ty - o.g;
+  const double xa = o.ia * dx, xb = o.ib * dy, ya = o.id * dx, yb = o.ie * dy;
+  *px = xa + xb;
+  *py = ya + yb;
+}
+OFDG_HD_FN float spatial_flow_of(double p, int at) { return spatial_quiet((float)(p - (double)at)); }
+// OFDG_SPATIAL_OCC_WINDOW, one axis: floor(p + 0.5) in [0, len - 1]; a NaN fails both comparisons
+OFDG_HD_FN bool spatial_partner_inside(double p, int len) {
+  const double t = floor(p + 0.5);
+  return t >= 0.0 && t <= (double)(len - 1);
+}
+// float32 -> binary16 to nearest even; an overflow becomes +-inf, a NaN 0x7E00
+OFDG_HD_FN uint32_t spatial_half_bits(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint32_t sign = (x >> 16) & 0x8000u;
+  x &= 0x7FFFFFFFu;
+  if (x > 0x7F800000u) return 0x7E00u;
+  if (x >= 0x477FF000u) return sign | 0x7C00u;
+  if (x >= 0x38800000u) {
+    x -= 0x38000000u;
+    x += 0xFFFu + ((x >> 13) & 1u);
+    return sign | (x >> 13);
+  }
+  const int shift = 126 - (int)(x >> 23);
+  if (shift > 24) return sign;
+  const uint32_t m = (x & 0x7FFFFFu) | 0x800000u, h = m >> shift, rem = m & ((1u << shift) - 1u), mid = 1u << (shift - 1);
+  return sign | (h + ((rem > mid || (rem == mid && (h & 1u))) ? 1u : 0u));
+}
+// The source size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* spatial_plane_size(const DevSpatialJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  if (const char* why = plane_size_error(*width, *height)) return why;
+  if (*width > kSpatialMaxSide || *height > kSpatialMaxSide) return "width and height must not exceed 2^20";
+  return nullptr;
+}
+// What the draw reads of a job besides the source size: the output size, the flags and the seven ranges.
+inline const char* spatial_draw_error(const DevSpatialJob& job) {
+  const DevSpatialJob* const j = &job;
+  if (j->out_w < 8 || (j->out_w % 8) != 0 || j->out_w > kSpatialMaxSide) return "out_w must be a multiple of 8 in [8, 2^20]";
+  if (j->out_h < 2 || (j->out_h % 2) != 0 || j->out_h > kSpatialMaxSide) return "out_h must be even and in [2, 2^20]";
+  if (j->flags & ~(OFDG_SPATIAL_RANDOM_HFLIP | OFDG_SPATIAL_RANDOM_VFLIP | OFDG_SPATIAL_OCC_WINDOW)) return "flags holds unknown bits";
+  const struct { float v; const char* why; } ranges[7] = {
+      {j->zoom_log, "zoom_log must be finite and not negative"}, {j->rot, "rot must be finite and not negative"},
+      {j->squeeze_log, "squeeze_log must be finite and not negative"}, {j->translate, "translate must lie in [0, 1]"},
+      {j->pair_zoom_log, "pair_zoom_log must be finite and not negative"}, {j->pair_rot, "pair_rot must be finite and not negative"},
+      {j->pair_translate, "pair_translate must be finite and not negative"}};
+  for (int k = 0; k < 7; ++k)
+    if (!(ranges[k].v >= 0.0f && ranges[k].v <= 3.4028234663852886e38f)) return ranges[k].why;
+  if (j->translate > 1.0f) return "translate must lie in [0, 1]";
+  return nullptr;
+}
+// The argument rules ofdg_spatial and ofdg_host_spatial share: the first rule broken, or nullptr.  width, height: what
+// spatial_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* spatial_arg_error(const DevSpatialJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (const char* why = spatial_draw_error(*j)) return why;
+  if ((unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "width * height must be below 2^31";
+  if ((unsigned long long)j->out_w * (unsigned long long)j->out_h >= (1ull << 31)) return "out_w * out_h must be below 2^31";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (j->image_fmt != OFDG_FMT_F32 && j->image_fmt != OFDG_FMT_U8) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = flow_occ_fmt_error(j->flow_fmt, true, j->occ_fmt)) return why;
+  int planes = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (j->src[k] && !j->dst[k]) return "dst: a plane has a source and no destination";
+    if (!j->src[k] && j->dst[k]) return "src: a plane has a destination and no source";
+    planes += j->src[k] ? 1 : 0;
+  }
+  if (!planes) return "src: no plane is set";
+  if ((j->flags & OFDG_SPATIAL_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_SPATIAL_OCC_WINDOW with occ0 needs flow";
+  if ((j->flags & OFDG_SPATIAL_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_SPATIAL_OCC_WINDOW with occ1 needs flow1";
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[2 * kCropPlanes + 2];
+  int nr = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const int es = fmt_elem_bytes(k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8);
+    const unsigned long long per = (unsigned long long)n * crop_channels(k) * es;
+    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * width * height), false};
+    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * j->out_w * j->out_h), true};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevSpatialRec), false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevSpatialRec), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
