@@ -770,6 +770,72 @@ int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int wid
  * size that breaks the rule, unknown flag bits or a range ofdg_spatial refuses. */
 int ofdg_spatial_draw(uint32_t seed, long long index, const struct ofdg_spatial_job* ranges, ofdg_spatial_rec* out);
 
+/* ---- network-ready frames and flow: ofdg_pack ----------------------------------------------------------------------------
+ * The last stage of a data recipe in one launch: planar B,G,R frames holding 0..255 and a flow in pixels become what a network
+ * reads - every channel scaled and shifted, optionally reordered to R,G,B, cast to the training element type, in planar or
+ * channels-last memory, both frames optionally concatenated into one 6-channel tensor, the flow multiplied by a constant.
+ *
+ * Planes: src[OFDG_PACK_IMAGE0], src[OFDG_PACK_IMAGE1] are [n,3,height,width] of image_src_fmt (OFDG_FMT_F32 or OFDG_FMT_U8),
+ * src[OFDG_PACK_FLOW] is [n,2,height,width] of flow_src_fmt (OFDG_FMT_F32 or OFDG_FMT_F16); any subset, a plane that is NULL
+ * in src is NULL in dst.  width, height: 0, 0 for the context's frame, or a width that is a multiple of 8 (at least 8) with an
+ * even height (at least 2) - the planes ofdg_crop and ofdg_spatial wrote.  Destinations are of image_dst_fmt / flow_dst_fmt:
+ * OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16, chosen independently of each other and of the sources.
+ *
+ * Value.  Every float32 operation is IEEE, rounded on its own (no fused multiply-add), denormals kept.  A frame element x of
+ * SOURCE channel c - (float)byte of a uint8 source, the element itself of a float32 one - gives y = fl32(fl32(x * scale[c]) +
+ * bias[c]); scale and bias are per source channel B, G, R and serve both frames.  A flow element u - the float32 element, or
+ * the binary16 one widened exactly - gives y = fl32(u * flow_scale).  What is stored of y:
+ *   OFDG_FMT_F32   its bits
+ *   OFDG_FMT_F16   y rounded once to nearest even: an overflow becomes +-inf, subnormals are kept (the conversion of the
+ *                  compact formats above)
+ *   OFDG_FMT_BF16  with b = the bits of y: (uint16_t)((b + 0x7FFF + ((b >> 16) & 1)) >> 16), i.e. round to nearest even on the
+ *                  upper 16 bits; what is above 0x7F7F7FFF in magnitude becomes +-inf; a float32 denormal keeps its upper bits
+ *   a NaN y        0x7FC00000 / 0x7E00 / 0x7FC0, whatever its sign and payload were (ofdg_spatial's rule)
+ * -0.0 stays -0.0 in every format.  Which products overflow is the caller's business: with scale = 1/255 nothing does.
+ *
+ * Placement.  C = 3 for a frame, 6 with OFDG_PACK_CONCAT, 2 for the flow.  Source channel c of frame f goes to destination
+ * channel cd = (OFDG_PACK_CONCAT ? 3 * f : 0) + (OFDG_PACK_RGB ? 2 - c : c) of dst[f] (of dst[0] with OFDG_PACK_CONCAT); the
+ * flow's channels keep their order.  Element (i, cd, y, x) of a destination sits at element index
+ *   OFDG_PACK_NCHW  ((i * C + cd) * height + y) * width + x
+ *   OFDG_PACK_NHWC  ((i * height + y) * width + x) * C + cd      (what torch calls channels_last memory of a [n,C,H,W] tensor)
+ * `layout` holds for the frames and the flow alike.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  ONE kernel for any
+ * n_samples and every plane given, no atomics; it reads no record of the context.  Sources are left as they are.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, only one of
+ * width / height 0, a size that breaks the rule above, 6 * width * height of 2^31 and more, a format code not listed for its
+ * field, a layout other than 0 / 1, unknown flag bits, non-zero reserved, a scale, bias or flow_scale that is NaN or infinite,
+ * no plane set, src[k] without dst[k] or the reverse, OFDG_PACK_CONCAT without both frames or with dst[1] set, a misaligned
+ * pointer (sources as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8; destinations 16-byte), a
+ * destination range that meets any other range of the job (there is no in-place form; a range is the n * C * height * width
+ * elements of its plane), OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: a validity mask output, packing the levels of the flow pyramid, an in-place form; labels and occlusion maps
+ * are left as they are.
+ */
+#define OFDG_FMT_BF16 3            /* ofdg_pack destinations only: bfloat16, the float32 value rounded to nearest even, once */
+#define OFDG_PACK_NCHW 0           /* layout: [n,C,height,width] */
+#define OFDG_PACK_NHWC 1           /* layout: [n,height,width,C] (torch channels_last memory) */
+#define OFDG_PACK_CONCAT 1         /* flag: dst[0] holds both frames, C = 6 (image0's three channels, then image1's); dst[1] NULL */
+#define OFDG_PACK_RGB    2         /* flag: destination channel c of a frame is source channel 2 - c (R,G,B instead of B,G,R) */
+enum { OFDG_PACK_IMAGE0, OFDG_PACK_IMAGE1, OFDG_PACK_FLOW, OFDG_PACK_PLANES };
+struct ofdg_pack_job {                       /* 112 bytes */
+  const void* src[OFDG_PACK_PLANES];         /* image0, image1 [n,3,height,width]; flow [n,2,height,width]; each optional */
+  void*       dst[OFDG_PACK_PLANES];
+  int32_t width, height;                     /* 0, 0: the context's frame */
+  int32_t image_src_fmt, flow_src_fmt;       /* F32 | U8;  F32 | F16 */
+  int32_t image_dst_fmt, flow_dst_fmt;       /* F32 | F16 | BF16, independently */
+  int32_t layout, flags;
+  float scale[3], bias[3];                   /* per SOURCE channel B, G, R; both frames */
+  float flow_scale;
+  int32_t reserved;
+};
+int ofdg_pack(ofdg_ctx* ctx, const struct ofdg_pack_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition element by element: no alignment asked of any pointer.  width, height: the
+ * plane size; the job's own must be 0, 0 or the same.  Errors as above through ofdg_host_last_error. */
+int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, int height);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

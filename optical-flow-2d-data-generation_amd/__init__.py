@@ -108,6 +108,7 @@ EXPORTS = [
     "ofdg_flow_stats_sized", "ofdg_flow_pyramid_sized", "ofdg_crop", "ofdg_host_crop", "ofdg_crop_draw", "ofdg_crop_philox",
     "ofdg_photo", "ofdg_host_photo", "ofdg_photo_draw", "ofdg_debug_photo_table", "ofdg_host_photo_table", "ofdg_host_det_log",
     "ofdg_spatial", "ofdg_host_spatial", "ofdg_spatial_draw",
+    "ofdg_pack", "ofdg_host_pack",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -672,6 +673,144 @@ def host_spatial(src, out_h, out_w, recs=None, first_index=0, seed=0, ranges=Non
     return dst, used
 
 
+# network-ready packing (struct ofdg_pack_job / ofdg_pack, include/ofdg.h)
+FMT_BF16 = 3
+PACK_NCHW, PACK_NHWC = 0, 1
+PACK_CONCAT, PACK_RGB = 1, 2
+PACK_PLANES = ("image0", "image1", "flow")
+# dtype name -> format code of a packed destination; a numpy array holds bfloat16 as uint16 bit patterns
+_PACK_DST_CODES = {"float32": FMT_F32, "float16": FMT_F16, "bfloat16": FMT_BF16, "uint16": FMT_BF16}
+
+
+class PackJob(C.Structure):
+    """struct ofdg_pack_job (112 bytes)."""
+    _fields_ = [("src", C.c_void_p * 3), ("dst", C.c_void_p * 3), ("width", C.c_int32), ("height", C.c_int32),
+                ("image_src_fmt", C.c_int32), ("flow_src_fmt", C.c_int32), ("image_dst_fmt", C.c_int32), ("flow_dst_fmt", C.c_int32),
+                ("layout", C.c_int32), ("flags", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3),
+                ("flow_scale", C.c_float), ("reserved", C.c_int32)]
+
+
+def pack_norm(mean, std, unit=255.0):
+    """(scale, bias) of ofdg_pack for (x / unit - mean) / std: scale = 1 / (unit * std), bias = -mean / std, computed in float64
+    and rounded to float32; mean and std per channel in the SOURCE's order B, G, R.  Two float32 arrays [3]."""
+    import numpy as np
+    mean, std = np.asarray(mean, np.float64).reshape(3), np.asarray(std, np.float64).reshape(3)
+    return (1.0 / (float(unit) * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def pack_format(src, dst, layout, concat, height=None, width=None):
+    """(n, height, width, image source code, flow source code, image destination code, flow destination code) of the planes of
+    Generator.pack / host_pack: src and dst are dicts keyed by PACK_PLANES (any subset, the same in both; with concat both
+    frames in src and image0 alone in dst).  A source frame is float32 or uint8 [n,3,H,W], a source flow float32 or float16
+    [n,2,H,W]; a destination is float32, float16 or bfloat16 (uint16 for a numpy array) of the LOGICAL shape [n,C,H,W], C = 3, 6
+    with concat, or 2 - with PACK_NHWC its memory is [n,H,W,C] (alloc_pack).  A format that no plane sets is FMT_F32.  Raises
+    ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    if layout not in (PACK_NCHW, PACK_NHWC):
+        raise ValueError("layout must be PACK_NCHW or PACK_NHWC, got %r" % (layout,))
+    if not src or not isinstance(src, dict) or not isinstance(dst, dict):
+        raise ValueError("src and dst must be dicts with at least one of %s" % (PACK_PLANES,))
+    for key in list(src) + list(dst):
+        if key not in PACK_PLANES:
+            raise ValueError("unknown plane %r (known: %s)" % (key, ", ".join(PACK_PLANES)))
+    if concat and not ("image0" in src and "image1" in src):
+        raise ValueError("concat needs image0 and image1 in src")
+    want = set(src) - ({"image1"} if concat else set())
+    if set(dst) != want:
+        raise ValueError("dst must hold %s, got %s" % (sorted(want), sorted(dst)))
+    shape = tuple(next(iter(src.values())).shape)
+    if len(shape) != 4 or shape[0] < 1 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a source plane must be [n,C,%s,%s], got %s" % (height or "height", width or "width", shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    if width < 8 or width % 8 or height < 2 or height % 2:
+        raise ValueError("the planes must be a multiple of 8 wide and even high, got %dx%d" % (width, height))
+    codes = {"image_src": set(), "flow_src": set(), "image_dst": set(), "flow_dst": set()}
+    for key, t in src.items():
+        flow = key == "flow"
+        _check_plane("src[%s]" % key, t, _FLOW_CODES if flow else _IMAGE_CODES, (n, 2 if flow else 3, height, width))
+        codes["flow_src" if flow else "image_src"].add((_FLOW_CODES if flow else _IMAGE_CODES)[_dtype_name(t)])
+    for key, t in dst.items():
+        flow = key == "flow"
+        _check_plane("dst[%s]" % key, t, _PACK_DST_CODES, (n, 2 if flow else 6 if concat else 3, height, width), says="float32, float16 or bfloat16")
+        codes["flow_dst" if flow else "image_dst"].add(_PACK_DST_CODES[_dtype_name(t)])
+    for what, got in codes.items():
+        if len(got) > 1:
+            raise ValueError("both frames must have one dtype in src and one in dst (%s)" % what)
+    return (n, height, width) + tuple(got.pop() if got else FMT_F32 for got in (codes[k] for k in ("image_src", "flow_src", "image_dst", "flow_dst")))
+
+
+def alloc_pack(n, height, width, image_dtype=None, flow_dtype=None, layout=PACK_NCHW, concat=False, planes=PACK_PLANES, device="cuda",
+               zero=True):
+    """The destination dict of Generator.pack: for each of `planes` (with concat, image0 stands for both frames and image1 is
+    left out) a tensor of the logical shape [n,C,height,width], C = 3, 6 (concat) or 2 (flow), of image_dtype / flow_dtype
+    (torch.float32 - the default -, torch.float16 or torch.bfloat16).  With PACK_NHWC a buffer is allocated as [n,H,W,C] and
+    returned as buf.permute(0, 3, 1, 2): is_contiguous(memory_format=torch.channels_last) holds.  zero=False: not filled (the
+    pack writes every element)."""
+    import torch
+    make = torch.zeros if zero else torch.empty
+    out = {}
+    for key in planes:
+        if key not in PACK_PLANES:
+            raise ValueError("unknown plane %r (known: %s)" % (key, ", ".join(PACK_PLANES)))
+        if concat and key == "image1":
+            continue
+        flow = key == "flow"
+        dtype = (flow_dtype if flow else image_dtype) or torch.float32
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("%s must be torch.float32, torch.float16 or torch.bfloat16, got %s" % ("flow_dtype" if flow else "image_dtype", dtype))
+        c = 2 if flow else 6 if concat else 3
+        if layout == PACK_NHWC:
+            out[key] = make((n, height, width, c), dtype=dtype, device=device).permute(0, 3, 1, 2)
+        elif layout == PACK_NCHW:
+            out[key] = make((n, c, height, width), dtype=dtype, device=device)
+        else:
+            raise ValueError("layout must be PACK_NCHW or PACK_NHWC, got %r" % (layout,))
+    return out
+
+
+def _pack_job(src, dst, ptr, dptr, codes, size, scale, bias, flow_scale, layout, concat, rgb):
+    job = PackJob()
+    for k, key in enumerate(PACK_PLANES):
+        if key in src:
+            job.src[k] = ptr(src[key])
+        if key in dst:
+            job.dst[k] = dptr(dst[key])
+    job.height, job.width = size
+    job.image_src_fmt, job.flow_src_fmt, job.image_dst_fmt, job.flow_dst_fmt = codes
+    job.layout, job.flags = layout, (PACK_CONCAT if concat else 0) | (PACK_RGB if rgb else 0)
+    scale, bias = tuple(float(v) for v in scale), tuple(float(v) for v in bias)
+    if len(scale) != 3 or len(bias) != 3:
+        raise ValueError("scale and bias must hold three values (source channels B, G, R)")
+    job.scale[:], job.bias[:] = scale, bias
+    job.flow_scale = float(flow_scale)
+    return job
+
+
+def host_pack(src, image_dtype=None, flow_dtype=None, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), flow_scale=1.0, layout=PACK_NCHW,
+              concat=False, rgb=False):
+    """ofdg_host_pack (no GPU): the packing of HOST arrays - src a dict of numpy arrays keyed by PACK_PLANES as Generator.pack takes
+    tensors.  image_dtype / flow_dtype: np.float32 (the default), np.float16 or "bfloat16" - returned as uint16 bit patterns,
+    numpy having no such type.  Returns the dict of packed arrays in the logical shape [n,C,H,W] (with PACK_NHWC a transposed
+    view of an [n,H,W,C] array; with concat image0 holds both frames)."""
+    import numpy as np
+    src = {k: np.ascontiguousarray(v) for k, v in src.items()}
+    if not src or layout not in (PACK_NCHW, PACK_NHWC):
+        pack_format(src, {}, layout, concat)
+    n, _, height, width = next(iter(src.values())).shape
+    dst = {}
+    for key in src:
+        if concat and key == "image1":
+            continue
+        flow = key == "flow"
+        dtype = (flow_dtype if flow else image_dtype) or np.float32
+        dtype = np.dtype(np.uint16 if isinstance(dtype, str) and dtype == "bfloat16" else dtype)
+        c = 2 if flow else 6 if concat else 3
+        dst[key] = np.zeros((n, height, width, c), dtype).transpose(0, 3, 1, 2) if layout == PACK_NHWC else np.zeros((n, c, height, width), dtype)
+    n, height, width, *codes = pack_format(src, dst, layout, concat)
+    job = _pack_job(src, dst, lambda a: a.ctypes.data, lambda a: a.ctypes.data, codes, (0, 0), scale, bias, flow_scale, layout, concat, rgb)
+    _host_check(lib().ofdg_host_pack(C.byref(job), n, width, height))
+    return dst
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -762,6 +901,8 @@ def lib():
         L.ofdg_spatial.argtypes = [vp, C.POINTER(SpatialJob), i32, vp]
         L.ofdg_host_spatial.argtypes = [C.POINTER(SpatialJob), i32, i32, i32]
         L.ofdg_spatial_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(SpatialJob), vp]
+        L.ofdg_pack.argtypes = [vp, C.POINTER(PackJob), i32, vp]
+        L.ofdg_host_pack.argtypes = [C.POINTER(PackJob), i32, i32, i32]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1144,6 +1285,30 @@ class Generator:
         job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), out_h, out_w, _optr(recs),
                            _optr(recs_out), first_index, self.params.seed if seed is None else seed, ranges, _spatial_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_spatial(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
+
+    def pack(self, src, dst, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), flow_scale=1.0, layout=PACK_NCHW, concat=False, rgb=False,
+             stream=0, size=None):
+        """Network-ready frames and flow in one launch (ofdg_pack, include/ofdg.h): every frame element becomes x * scale[c] +
+        bias[c] (per SOURCE channel B, G, R; pack_norm makes the pair from a mean and a std), every flow element u * flow_scale,
+        cast to the destinations' dtypes.  src and dst are dicts keyed by PACK_PLANES (image0, image1, flow; any subset): src[name]
+        the float32 / uint8 frames and the float32 / float16 flow a render / forward call (or crop, spatial, photo) wrote, dst
+        what alloc_pack made with the same layout and concat - torch.float32, torch.float16 or torch.bfloat16, planar (PACK_NCHW)
+        or channels-last memory (PACK_NHWC).  concat: dst["image0"] takes both frames as 6 channels, dst holds no image1.  rgb:
+        the channels of a frame are written in the order R, G, B.  stream: the stream the planes were written on, or
+        STREAM_OWN.  size=(height, width): planes of that size instead of the context's frame.  Asynchronous; there is no
+        in-place form.  Returns dst."""
+        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        n, _, _, *codes = pack_format(src, dst, layout, concat, height, width)
+
+        def dptr(t):  # a destination: dense in the memory order of the layout
+            import torch
+            if not t.is_cuda or not t.is_contiguous(memory_format=torch.channels_last if layout == PACK_NHWC else torch.contiguous_format):
+                raise ValueError("dst tensors must be device tensors as alloc_pack makes them for this layout")
+            return t.data_ptr()
+        job = _pack_job(src, dst, lambda t: _dptr(t).value, dptr, codes, (0, 0) if size is None else (height, width), scale, bias, flow_scale,
+                        layout, concat, rgb)
+        self._check(lib().ofdg_pack(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
     def debug_photo_table(self, rec):
@@ -1793,13 +1958,23 @@ class FlowLoader:
     spatial_vflip allow drawn flips, spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  photo=,
     stats= and pyramid= then work on the WARPED planes; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and
     frame 1, a b c d e g each, then padding).  crop= with spatial= raises - the spatial step contains the window -, and so
-    does objects=True: its boxes are of the unwarped frame."""
+    does objects=True: its boxes are of the unwarped frame.
+    pack=dict(image_dtype=, flow_dtype=, layout=, concat=, rgb=, scale=, bias=, flow_scale=) (every key optional: alloc_pack and
+    Generator.pack): the frames and the flow of every batch are packed for the network into a further ring of buffers
+    (Generator.pack, enqueued on the same internal stream as the LAST step of the batch: behind crop / spatial and photo, on
+    their outputs; stats= and pyramid= keep reading the unpacked, unscaled flow).  The loader then yields the packed tensors in
+    the places of image0, image1 and flow - with concat the 6-channel tensor first and None second -; extras, objects, stats
+    and pyramid are untouched.  The pyramid's levels, labels and occlusion maps are not packed."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
-                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, **kw):
+                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, **kw):
         import torch
+        self.pack = None if pack is None else dict(pack)
+        unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
+        if unknown:
+            raise ValueError("unknown pack option(s) %s" % sorted(unknown))
         self.spatial = None if spatial is None else dict(spatial)
         _spatial_ranges(SpatialJob(), self.spatial)  # (raises for a name that is no range)
         if self.spatial is not None and crop is not None:
@@ -1863,6 +2038,11 @@ class FlowLoader:
         # (not filled: the augmentation writes every record; see the crop's buffers above)
         self.rbufs = [torch.empty((p.batch_size, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
                       for _ in range(self.prefetch)]
+        # (not filled: the pack writes every element; see the crop's buffers above)
+        self.kbufs = [None if self.pack is None else
+                      alloc_pack(p.batch_size, ph, pw, image_dtype=self.pack.get("image_dtype"), flow_dtype=self.pack.get("flow_dtype"),
+                                 layout=self.pack.get("layout", PACK_NCHW), concat=bool(self.pack.get("concat", False)), zero=False)
+                      for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -1884,6 +2064,7 @@ class FlowLoader:
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
+        self._enqueue_pack(j, self.bufs[j], s, None)
         self.ready[j].record(chain)
 
     def _enqueue_cropped(self, j, s, chain, step):
@@ -1900,6 +2081,7 @@ class FlowLoader:
                           vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
         self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
         self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
+        self._enqueue_pack(j, (out["image0"], out["image1"], out["flow"]), s, self.crop)
         self.ready[j].record(chain)
 
     def _enqueue_photo(self, j, frames, s, step, size):
@@ -1908,6 +2090,14 @@ class FlowLoader:
             p = self.gen.params
             self.gen.photo(frames, recs_out=self.rbufs[j], first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank),
                            ranges=self.photo, stream=s, size=size)
+
+    def _enqueue_pack(self, j, planes, s, size):
+        """The packing of (image0, image1, flow) of set j into its packed buffers on stream s, when the loader makes one."""
+        if self.pack is not None:
+            o = self.pack
+            self.gen.pack(dict(zip(PACK_PLANES, planes)), self.kbufs[j], scale=o.get("scale", (1.0, 1.0, 1.0)), bias=o.get("bias", (0.0, 0.0, 0.0)),
+                          flow_scale=o.get("flow_scale", 1.0), layout=o.get("layout", PACK_NCHW), concat=bool(o.get("concat", False)),
+                          rgb=bool(o.get("rgb", False)), stream=s, size=size)
 
     def _enqueue_reductions(self, j, flow, occ, s, size):
         """The statistics and the pyramid of set j, as far as the loader makes them, of a flow and its map (None: no map) of
@@ -1949,6 +2139,14 @@ class FlowLoader:
             self._enqueue(f)
             self.head += 1
         self.k += 1
+        batch = self._batch(j)
+        if self.kbufs[j] is not None:
+            k = self.kbufs[j]
+            batch = (k["image0"], k.get("image1"), k["flow"]) + tuple(batch[3:])
+        return batch
+
+    def _batch(self, j):
+        """what set j hands out, before the packed tensors take the places of image0, image1 and flow"""
         if self.crop is not None:
             out, recs = self.cbufs[j]
             more = {k: v for k, v in out.items() if k not in ("image0", "image1", "flow")}

@@ -569,4 +569,38 @@ int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int wid
   return OFDG_OK;
 }
 
+// ofdg_pack on host arrays (no GPU): the definition of include/ofdg.h element by element.  The value, the roundings, the
+// placement and the argument rules are the functions the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy,
+// so no alignment is asked.
+int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, int height) {
+  const DevPackJob* const j = reinterpret_cast<const DevPackJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = pack_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_pack: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  for (int k = 0; k < kPackPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const bool flow = k == OFDG_PACK_FLOW;
+    const int sfmt = flow ? j->flow_src_fmt : j->image_src_fmt, dfmt = flow ? j->flow_dst_fmt : j->image_dst_fmt;
+    const int Cs = flow ? 2 : 3, Cd = pack_channels(k, j->flags), des = fmt_elem_bytes(dfmt);
+    const SpatialElems src{static_cast<const uint8_t*>(j->src[k]), fmt_elem_bytes(sfmt), sfmt == OFDG_FMT_F16};
+    uint8_t* const dst = static_cast<uint8_t*>(j->dst[(j->flags & OFDG_PACK_CONCAT) && !flow ? OFDG_PACK_IMAGE0 : k]);
+    for (int i = 0; i < n_samples; ++i)
+      for (int c = 0; c < Cs; ++c) {
+        const int cd = flow ? c : pack_dst_channel(k, c, j->flags);
+        for (int y = 0; y < height; ++y)
+          for (int x = 0; x < width; ++x) {
+            const float e = src.at(((size_t)i * Cs + c) * plane + (size_t)y * width + x);
+            const float v = flow ? pack_flow_value(e, j->flow_scale) : pack_value(e, j->scale[c], j->bias[c]);
+            const uint32_t bits = pack_stored_bits(v, dfmt);
+            std::memcpy(dst + pack_dst_index(j->layout, Cd, i, cd, y, x, width, height) * des, &bits, des);
+          }
+      }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

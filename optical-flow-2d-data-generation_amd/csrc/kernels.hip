@@ -3975,4 +3975,189 @@ __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpati
   }
 }
 
+// --------------------------------------------------------------------------
+// Network-ready packing (ofdg_pack): scale and shift, channel order, element type, layout and the concatenation of both
+// frames, and the flow times a constant, in one launch.  The functions of the definition are the host twin's
+// (csrc/ofdg_device.h), so the result is the twin's bit for bit.
+// --------------------------------------------------------------------------
+// A streaming kernel: its bound is bytes.  A channel of a sample is width * height elements without gaps, whole units of 8
+// consecutive pixels of one row (width % 8 == 0).  A lane owns one unit of one plane group - a frame (3 channels), both frames
+// (6, OFDG_PACK_CONCAT) or the flow (2) - and all of its channels: per channel it reads 8 bytes of a uint8 source as two
+// 4-byte words, 16 bytes of a binary16 one as two 8-byte pieces, 32 bytes of a float32 one as two 16-byte pieces (the
+// alignments the entry asks of a source), every load requested before the first value is used, and converts in registers.
+// What a lane then holds is kP consecutive 16-byte pieces of a run of 64 * kP pieces that the wave's 64 units fill without
+// gaps: one piece per channel of a planar 16-bit destination, two per channel of a planar float32 one, the unit's 8 * C
+// interleaved elements - 8 * C * es / 16 = 2, 3, 4, 6 or 12 pieces - of a channels-last one.  Where kP > 1 a store
+// instruction that wrote each lane's m-th piece would touch 16 bytes out of every kP * 16 (measured: CHANGELOG), so the
+// lanes of a wave exchange their pieces through the wave's own LDS slots and store instruction m writes pieces 64 m .. 64 m +
+// 63 of the run, 1 KiB of consecutive bytes.  The exchange stays inside a wave (its LDS instructions execute in order), so
+// it needs no workgroup barrier and lanes past the last unit take part without storing.  Every store is a whole 16-byte
+// piece, non-temporal, as in crop_kernel.  blockIdx.x counts the workgroups of the plane groups that are set (frames, then
+// the flow), blockIdx.y the samples.  Lanes past the last unit read unit 0.  The frames' formats, the layout and the
+// concatenation are template arguments; the flow's two formats, the channel order and every constant are uniform at run
+// time (the flow's six forms are in every instantiation, behind uniform branches).  The bfloat16 rounding is the integer
+// form of the definition.  LDS: 16 bytes * 256 * the largest kP of the instantiation (8 - 48 KiB); no atomics, no scratch.
+constexpr int kPackThreads = 256;
+constexpr int kPackSrcF32 = 0, kPackSrcU8 = 1, kPackSrcF16 = 2;  // how pack_unit reads a source
+struct PackRun {          // the wave's units
+  crop_u32x4* lds;        // the wave's 64 * kP slots
+  uint32_t first_unit;    // the unit of its lane 0
+  uint32_t units;         // units of a channel: those from here on do not exist
+};
+__device__ __forceinline__ void pack_wave_sync() {  // the wave's LDS accesses so far before those that follow
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// The wave's run of 64 * kP pieces from `dp` on, lane l holding pieces l * kP .. l * kP + kP - 1 of it.
+template <int kP>
+__device__ __forceinline__ void pack_store_run(const crop_u32x4 (&piece)[kP], uint8_t* dp, const PackRun& run) {
+  const uint32_t lane = threadIdx.x & 63u;
+  crop_u32x4* const d = reinterpret_cast<crop_u32x4*>(dp);
+  if constexpr (kP == 1) {
+    if (run.first_unit + lane < run.units) crop_store(d + lane, piece[0]);
+  } else {
+#pragma unroll
+    for (int m = 0; m < kP; ++m) run.lds[lane * kP + m] = piece[m];
+    pack_wave_sync();
+#pragma unroll
+    for (int m = 0; m < kP; ++m) {
+      const uint32_t idx = (uint32_t)m * 64u + lane;
+      if (run.first_unit + idx / kP < run.units) crop_store(d + idx, run.lds[idx]);
+    }
+    pack_wave_sync();  // (the slots are written again by the next channel, plane group or sample)
+  }
+}
+template <int kDst>
+__device__ __forceinline__ uint32_t pack_device_bits(float y) {
+  if constexpr (kDst == OFDG_FMT_F32) return __float_as_uint(spatial_quiet(y));
+  else if constexpr (kDst == OFDG_FMT_BF16) return pack_bf16_bits(y);
+  else return y != y ? 0x7E00u : (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)y);  // (v_cvt_f16_f32: to nearest even, denormals kept)
+}
+// One unit per lane: sp[cd] the 8 source elements of destination channel cd; dp the first destination byte of the wave's
+// first unit (planar: in channel 0, the channels chan_bytes apart; channels-last: of its 8 * kC elements).
+template <int kC, int kSrc, int kDst, bool kNhwc, bool kBias>
+__device__ __forceinline__ void pack_unit(const uint8_t* const (&sp)[kC], const float (&scale)[kC], const float (&bias)[kC], uint8_t* dp, size_t chan_bytes,
+                                          const PackRun& run) {
+  constexpr int kSW = kSrc == kPackSrcU8 ? 2 : kSrc == kPackSrcF16 ? 4 : 8;  // 32-bit words of 8 source elements
+  constexpr bool kWide = kDst == OFDG_FMT_F32;
+  uint32_t raw[kC][kSW];
+#pragma unroll
+  for (int c = 0; c < kC; ++c) {
+    if constexpr (kSrc == kPackSrcU8) {
+      const uint32_t* const p = reinterpret_cast<const uint32_t*>(sp[c]);
+      raw[c][0] = p[0]; raw[c][1] = p[1];
+    } else if constexpr (kSrc == kPackSrcF16) {
+      const uint2* const p = reinterpret_cast<const uint2*>(sp[c]);
+      const uint2 a = p[0], b = p[1];
+      raw[c][0] = a.x; raw[c][1] = a.y; raw[c][2] = b.x; raw[c][3] = b.y;
+    } else {
+      const uint4* const p = reinterpret_cast<const uint4*>(sp[c]);
+      const uint4 a = p[0], b = p[1];
+      raw[c][0] = a.x; raw[c][1] = a.y; raw[c][2] = a.z; raw[c][3] = a.w;
+      raw[c][4] = b.x; raw[c][5] = b.y; raw[c][6] = b.z; raw[c][7] = b.w;
+    }
+  }
+  uint32_t o[kC][8];  // what is stored of each element (the low 16 bits of a 16-bit format)
+#pragma unroll
+  for (int c = 0; c < kC; ++c) {
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      float x;
+      if constexpr (kSrc == kPackSrcU8) x = (float)((raw[c][p / 4] >> (8 * (p & 3))) & 255u);
+      else if constexpr (kSrc == kPackSrcF16) x = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw[c][p / 2] >> (16 * (p & 1))));
+      else x = __uint_as_float(raw[c][p]);
+      float y;
+      if constexpr (kBias) y = pack_value(x, scale[c], bias[c]);
+      else y = pack_flow_value(x, scale[c]);
+      o[c][p] = pack_device_bits<kDst>(y);
+    }
+  }
+  if constexpr (!kNhwc) {
+#pragma unroll
+    for (int c = 0; c < kC; ++c) {
+      if constexpr (kWide) {
+        const crop_u32x4 piece[2] = {crop_u32x4{o[c][0], o[c][1], o[c][2], o[c][3]}, crop_u32x4{o[c][4], o[c][5], o[c][6], o[c][7]}};
+        pack_store_run<2>(piece, dp + (size_t)c * chan_bytes, run);
+      } else {
+        const crop_u32x4 piece[1] = {crop_u32x4{o[c][0] | (o[c][1] << 16), o[c][2] | (o[c][3] << 16), o[c][4] | (o[c][5] << 16), o[c][6] | (o[c][7] << 16)}};
+        pack_store_run<1>(piece, dp + (size_t)c * chan_bytes, run);
+      }
+    }
+  } else {
+    // element e = pixel * kC + channel of the unit is o[e % kC][e / kC]
+    constexpr int kP = kWide ? 2 * kC : kC;
+    crop_u32x4 piece[kP];
+    if constexpr (kWide) {
+#pragma unroll
+      for (int m = 0; m < kP; ++m) {
+        const int e = 4 * m;
+        piece[m] = crop_u32x4{o[e % kC][e / kC], o[(e + 1) % kC][(e + 1) / kC], o[(e + 2) % kC][(e + 2) / kC], o[(e + 3) % kC][(e + 3) / kC]};
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < kP; ++m) {
+        const int e = 8 * m;
+        piece[m] = crop_u32x4{o[e % kC][e / kC] | (o[(e + 1) % kC][(e + 1) / kC] << 16), o[(e + 2) % kC][(e + 2) / kC] | (o[(e + 3) % kC][(e + 3) / kC] << 16),
+                              o[(e + 4) % kC][(e + 4) / kC] | (o[(e + 5) % kC][(e + 5) / kC] << 16),
+                              o[(e + 6) % kC][(e + 6) / kC] | (o[(e + 7) % kC][(e + 7) / kC] << 16)};
+      }
+    }
+    pack_store_run<kP>(piece, dp, run);
+  }
+}
+template <bool kImgU8, int kImgDst, bool kNhwc, bool kConcat>
+__global__ __launch_bounds__(kPackThreads) void pack_kernel(const DevPackJob job, int n, int W, int H, uint32_t per_group) {
+  constexpr int kImgSrc = kImgU8 ? kPackSrcU8 : kPackSrcF32, kImgC = kConcat ? 6 : 3;
+  constexpr uint32_t kImgSES = kImgU8 ? 1 : 4, kImgDES = kImgDst == OFDG_FMT_F32 ? 4 : 2;
+  // the largest kP: planar 2 (a float32 channel); channels-last the frames' 8 * C * es / 16, or a float32 flow's 4
+  constexpr int kImgP = kImgC * (int)kImgDES / 2, kMaxP = !kNhwc ? 2 : kImgP > 4 ? kImgP : 4;
+  __shared__ crop_u32x4 slots[kPackThreads * kMaxP];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (6 * plane < 2^31: pack_arg_error)
+  const uint32_t units = plane / 8u;
+  const uint32_t group = blockIdx.x / per_group;
+  const uint32_t mine = (blockIdx.x - group * per_group) * (uint32_t)kPackThreads + threadIdx.x;
+  const uint32_t at = mine < units ? mine * 8u : 0u;  // the unit's first pixel in a channel; past the end: unit 0, read and not stored
+  const PackRun run{slots + (threadIdx.x >> 6) * (uint32_t)(64 * kMaxP), mine - (threadIdx.x & 63u), units};
+  const size_t run_at = (size_t)run.first_unit * 8u;  // first pixel of the wave's run (its lane 0 exists, or nothing is stored)
+  const uint32_t frame_groups = kConcat ? 1u : (job.src[0] ? 1u : 0u) + (job.src[1] ? 1u : 0u);
+  const bool rgb = job.flags & 2;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    if (group < frame_groups) {
+      const int f = (!kConcat && (group != 0u || !job.src[0])) ? 1 : 0;
+      const float s3[3] = {rgb ? job.scale[2] : job.scale[0], job.scale[1], rgb ? job.scale[0] : job.scale[2]};  // by destination channel
+      const float b3[3] = {rgb ? job.bias[2] : job.bias[0], job.bias[1], rgb ? job.bias[0] : job.bias[2]};
+      const uint8_t* sp[kImgC];
+      float scale[kImgC], bias[kImgC];
+#pragma unroll
+      for (int cd = 0; cd < kImgC; ++cd) {
+        const uint8_t* const s = static_cast<const uint8_t*>((kConcat ? cd >= 3 : f != 0) ? job.src[1] : job.src[0]);
+        const uint32_t c = rgb ? 2u - (uint32_t)(cd % 3) : (uint32_t)(cd % 3);  // the source channel
+        sp[cd] = s + ((size_t)i * 3u * plane + c * plane + at) * kImgSES;
+        scale[cd] = s3[cd % 3]; bias[cd] = b3[cd % 3];
+      }
+      uint8_t* const d = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+      uint8_t* const dp = d + (kNhwc ? ((size_t)i * plane + run_at) * kImgC : (size_t)i * kImgC * plane + run_at) * kImgDES;
+      pack_unit<kImgC, kImgSrc, kImgDst, kNhwc, true>(sp, scale, bias, dp, (size_t)plane * kImgDES, run);
+    } else {
+      const bool half = job.flow_src_fmt == OFDG_FMT_F16;
+      const uint32_t ses = half ? 2u : 4u, des = job.flow_dst_fmt == OFDG_FMT_F32 ? 4u : 2u;
+      const uint8_t* const s = static_cast<const uint8_t*>(job.src[2]);
+      const uint8_t* const sp[2] = {s + ((size_t)i * 2u * plane + at) * ses, s + ((size_t)i * 2u * plane + plane + at) * ses};
+      const float scale[2] = {job.flow_scale, job.flow_scale}, bias[2] = {0.0f, 0.0f};
+      uint8_t* const dp = static_cast<uint8_t*>(job.dst[2]) + (kNhwc ? ((size_t)i * plane + run_at) * 2u : (size_t)i * 2u * plane + run_at) * des;
+      const size_t chan_bytes = (size_t)plane * des;
+      if (half) {
+        if (job.flow_dst_fmt == OFDG_FMT_F32) pack_unit<2, kPackSrcF16, OFDG_FMT_F32, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+        else if (job.flow_dst_fmt == OFDG_FMT_F16) pack_unit<2, kPackSrcF16, OFDG_FMT_F16, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+        else pack_unit<2, kPackSrcF16, OFDG_FMT_BF16, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+      } else {
+        if (job.flow_dst_fmt == OFDG_FMT_F32) pack_unit<2, kPackSrcF32, OFDG_FMT_F32, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+        else if (job.flow_dst_fmt == OFDG_FMT_F16) pack_unit<2, kPackSrcF32, OFDG_FMT_F16, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+        else pack_unit<2, kPackSrcF32, OFDG_FMT_BF16, kNhwc, false>(sp, scale, bias, dp, chan_bytes, run);
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

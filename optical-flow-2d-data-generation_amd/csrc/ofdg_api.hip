@@ -267,7 +267,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial
+// ofdg_spatial, ofdg_pack
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -287,7 +287,7 @@ struct PostOp {
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
-// 8 spatial_kernel.
+// 8 spatial_kernel, 24 pack_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1744,6 +1744,41 @@ int ofdg_spatial(ofdg_ctx* c, const struct ofdg_spatial_job* job, int n_samples,
       with_bool(j->occ_fmt == OFDG_FMT_U8, [&](auto occ_u8) {
         hipLaunchKernelGGL((spatial_kernel<decltype(image_u8)::value, decltype(flow_half)::value, decltype(occ_u8)::value>), g, dim3(kSpatialThreads), 0,
                            st, *j, n_samples, W, H, tiles_x);
+      });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Network-ready packing of caller-given planes: one kernel on `stream` for both frames, the flow and every sample.
+int ofdg_pack(ofdg_ctx* c, const struct ofdg_pack_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_pack"};
+  const DevPackJob* const j = reinterpret_cast<const DevPackJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = pack_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = pack_arg_error(j, n_samples, W, H)) return op.fail(why);
+  static const char* const kPlane[kPackPlanes] = {"image0", "image1", "flow"};
+  for (int k = 0; k < kPackPlanes; ++k) {
+    if (!j->src[k]) continue;
+    OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], k == OFDG_PACK_FLOW ? j->flow_src_fmt : j->image_src_fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+  }
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const bool concat = j->flags & OFDG_PACK_CONCAT;
+  const uint32_t units = (uint32_t)W * (uint32_t)H / 8u, per_group = (units + kPackThreads - 1) / kPackThreads;
+  const uint32_t groups = (concat ? 1u : (j->src[OFDG_PACK_IMAGE0] ? 1u : 0u) + (j->src[OFDG_PACK_IMAGE1] ? 1u : 0u)) + (j->src[OFDG_PACK_FLOW] ? 1u : 0u);
+  const dim3 g(per_group * groups, (unsigned)std::min(n_samples, 65535));
+  with_bool(j->image_src_fmt == OFDG_FMT_U8, [&](auto image_u8) {
+    with_constant<int, OFDG_FMT_F32, OFDG_FMT_F16, OFDG_FMT_BF16>(j->image_dst_fmt, [&](auto image_dst) {
+      with_bool(j->layout == OFDG_PACK_NHWC, [&](auto nhwc) {
+        with_bool(concat, [&](auto both) {
+          hipLaunchKernelGGL((pack_kernel<decltype(image_u8)::value, decltype(image_dst)::value, decltype(nhwc)::value, decltype(both)::value>), g,
+                             dim3(kPackThreads), 0, st, *j, n_samples, W, H, per_group);
+        });
       });
     });
   });

@@ -742,6 +742,111 @@ inline const char* spatial_arg_error(const DevSpatialJob* j, int n, int width, i
   return nullptr;
 }
 
+// ---- Network-ready packing (ofdg_pack, include/ofdg.h) ---------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the value, the bfloat16
+// rounding, the placement and the argument rules.  Compiled without contraction, so a product and a sum are two roundings.
+constexpr int kPackPlanes = 3;  // OFDG_PACK_PLANES: image0, image1, flow
+struct DevPackJob {             // struct ofdg_pack_job, field for field
+  const void* src[kPackPlanes];
+  void* dst[kPackPlanes];
+  int32_t width, height, image_src_fmt, flow_src_fmt, image_dst_fmt, flow_dst_fmt, layout, flags;
+  float scale[3], bias[3];
+  float flow_scale;
+  int32_t reserved;
+};
+static_assert(sizeof(struct ofdg_pack_job) == sizeof(DevPackJob) && sizeof(DevPackJob) == 112 && OFDG_PACK_PLANES == kPackPlanes &&
+              offsetof(struct ofdg_pack_job, dst) == offsetof(DevPackJob, dst) && offsetof(struct ofdg_pack_job, width) == offsetof(DevPackJob, width) &&
+              offsetof(struct ofdg_pack_job, image_src_fmt) == offsetof(DevPackJob, image_src_fmt) && offsetof(struct ofdg_pack_job, flow_dst_fmt) == offsetof(DevPackJob, flow_dst_fmt) &&
+              offsetof(struct ofdg_pack_job, layout) == offsetof(DevPackJob, layout) && offsetof(struct ofdg_pack_job, flags) == offsetof(DevPackJob, flags) &&
+              offsetof(DevPackJob, flags) == 76 && offsetof(struct ofdg_pack_job, scale) == offsetof(DevPackJob, scale) && offsetof(struct ofdg_pack_job, bias) == offsetof(DevPackJob, bias) &&
+              offsetof(struct ofdg_pack_job, flow_scale) == offsetof(DevPackJob, flow_scale) && offsetof(struct ofdg_pack_job, reserved) == offsetof(DevPackJob, reserved) &&
+              offsetof(DevPackJob, reserved) == 108 && OFDG_FMT_BF16 == 3 && OFDG_PACK_NHWC == 1 && OFDG_PACK_CONCAT == 1 && OFDG_PACK_RGB == 2,
+              "struct ofdg_pack_job: 112 bytes, the layout the kernel takes; pack_kernel spells the codes out");
+// y of a frame element x under its source channel's constants, and of a flow element u: each operation its own rounding
+OFDG_HD_FN float pack_value(float x, float scale, float bias) {
+  const float p = x * scale;
+  return p + bias;
+}
+OFDG_HD_FN float pack_flow_value(float u, float flow_scale) { return u * flow_scale; }
+// float32 -> bfloat16 to nearest even on the upper 16 bits; a NaN becomes 0x7FC0.  (b <= 0xFF800000 here: the sum stays
+// inside 32 bits.)
+OFDG_HD_FN uint32_t pack_bf16_bits(float y) {
+  uint32_t b;
+  memcpy(&b, &y, 4);
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
+}
+// What is stored of y in a destination of `fmt`: 32 bits of float32, else 16
+OFDG_HD_FN uint32_t pack_stored_bits(float y, int fmt) {
+  if (fmt == OFDG_FMT_BF16) return pack_bf16_bits(y);
+  if (fmt == OFDG_FMT_F16) return spatial_half_bits(y);
+  const float q = spatial_quiet(y);
+  uint32_t b;
+  memcpy(&b, &q, 4);
+  return b;
+}
+// channels of a destination plane; the destination channel of source channel c of frame f
+OFDG_HD_FN int pack_channels(int plane, int flags) { return plane == OFDG_PACK_FLOW ? 2 : (flags & OFDG_PACK_CONCAT) ? 6 : 3; }
+OFDG_HD_FN int pack_dst_channel(int f, int c, int flags) { return ((flags & OFDG_PACK_CONCAT) ? 3 * f : 0) + ((flags & OFDG_PACK_RGB) ? 2 - c : c); }
+// element index of (sample i, destination channel cd, row y, column x) in a destination of C channels
+OFDG_HD_FN size_t pack_dst_index(int layout, int C, int i, int cd, int y, int x, int width, int height) {
+  if (layout == OFDG_PACK_NHWC) return (((size_t)i * height + y) * width + x) * C + cd;
+  return (((size_t)i * C + cd) * height + y) * width + x;
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* pack_plane_size(const DevPackJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+inline bool pack_finite(float v) { return v >= -3.4028234663852886e38f && v <= 3.4028234663852886e38f; }
+// The argument rules ofdg_pack and ofdg_host_pack share: the first rule broken, or nullptr.  width, height: what
+// pack_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* pack_arg_error(const DevPackJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (6ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "6 * width * height must be below 2^31";
+  if (j->image_src_fmt != OFDG_FMT_F32 && j->image_src_fmt != OFDG_FMT_U8) return "image_src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flow_src_fmt != OFDG_FMT_F32 && j->flow_src_fmt != OFDG_FMT_F16) return "flow_src_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->image_dst_fmt != OFDG_FMT_F32 && j->image_dst_fmt != OFDG_FMT_F16 && j->image_dst_fmt != OFDG_FMT_BF16)
+    return "image_dst_fmt must be OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16";
+  if (j->flow_dst_fmt != OFDG_FMT_F32 && j->flow_dst_fmt != OFDG_FMT_F16 && j->flow_dst_fmt != OFDG_FMT_BF16)
+    return "flow_dst_fmt must be OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16";
+  if (j->layout != OFDG_PACK_NCHW && j->layout != OFDG_PACK_NHWC) return "layout must be OFDG_PACK_NCHW or OFDG_PACK_NHWC";
+  if (j->flags & ~(OFDG_PACK_CONCAT | OFDG_PACK_RGB)) return "flags holds unknown bits";
+  if (j->reserved != 0) return "reserved must be 0";
+  for (int c = 0; c < 3; ++c) {
+    if (!pack_finite(j->scale[c])) return "scale must be finite";
+    if (!pack_finite(j->bias[c])) return "bias must be finite";
+  }
+  if (!pack_finite(j->flow_scale)) return "flow_scale must be finite";
+  const bool concat = j->flags & OFDG_PACK_CONCAT;
+  int planes = 0;
+  for (int k = 0; k < kPackPlanes; ++k) {
+    if (concat && k == OFDG_PACK_IMAGE1) continue;
+    if (j->src[k] && !j->dst[k]) return "dst: a plane has a source and no destination";
+    if (!j->src[k] && j->dst[k]) return "src: a plane has a destination and no source";
+    planes += j->src[k] ? 1 : 0;
+  }
+  if (concat && (!j->src[OFDG_PACK_IMAGE0] || !j->src[OFDG_PACK_IMAGE1])) return "flags: OFDG_PACK_CONCAT needs both frames";
+  if (concat && j->dst[OFDG_PACK_IMAGE1]) return "flags: OFDG_PACK_CONCAT takes dst[image1] NULL";
+  if (!planes) return "src: no plane is set";
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[2 * kPackPlanes];
+  int nr = 0;
+  const unsigned long long per = (unsigned long long)n * width * height;
+  for (int k = 0; k < kPackPlanes; ++k) {
+    const bool flow = k == OFDG_PACK_FLOW;
+    if (j->src[k]) r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * (flow ? 2 : 3) * fmt_elem_bytes(flow ? j->flow_src_fmt : j->image_src_fmt)), false};
+    if (j->dst[k]) r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * pack_channels(k, j->flags) * fmt_elem_bytes(flow ? j->flow_dst_fmt : j->image_dst_fmt)), true};
+  }
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
