@@ -850,15 +850,23 @@ void* ofdg_stream(ofdg_ctx* ctx);
 /* How many internal streams take turns: a caller that cycles k * ofdg_num_chains output buffer sets and passes
  * ofdg_stream() finds every set always written by the same stream (no event needed between its writers). */
 int ofdg_num_chains(const ofdg_ctx* ctx);
-/* Counter sampler: how many batches of a chain ONE sampler -> geom -> raster launch serves.  2 (the default): a call that
- * finds no front end ready on its chain runs those three latency-bound kernels for its own batch and for the batch that
- * chain is asked for next (first_index + ofdg_num_chains x the stride of the caller's last two calls, else batch x
- * world_size); that call then launches only its background preparation and compose.  A call for anything else - another
- * first_index or n_samples, after ofdg_set_step or a change of the pool - forgets the second batch and prepares its own:
- * nothing is rendered from a stale front end, and the bytes are those of n = 1, where every call launches its own front
- * end.  It applies to the overlapped pipeline without look-ahead (serial = 0, lookahead = 0) and to batches of up to 256
- * samples; a chain's workspaces hold two batches.  ofdg_ctx_info() ends in " front=N".  OFDG_EINVAL unless n is 1 or 2. */
+/* Counter sampler: how many batches of a chain ONE sampler -> geom -> raster launch serves, n = 1 .. 4 (the default is 4).
+ * A call that finds no front end ready on its chain runs those three latency-bound kernels for a GROUP: its own batch and
+ * the n - 1 batches that chain is asked for next (first_index + k x ofdg_num_chains x the stride of the caller's last two
+ * calls, else batch x world_size; k = 1 .. n - 1); each of those calls then launches only its background preparation and
+ * compose.  A call for anything else than the group's next batch - another first_index or n_samples, after ofdg_set_step,
+ * ofdg_set_front_batches or a change of the pool - forgets the rest of the group and prepares its own: nothing is rendered
+ * from a stale front end, and the bytes are those of n = 1, where every call launches its own front end.  It applies to the
+ * overlapped pipeline without look-ahead (serial = 0, lookahead = 0); a chain's workspaces hold n batches, and a call whose
+ * n x n_samples exceeds 512 samples gets the largest group that fits (ofdg_front_batches_for).  ofdg_ctx_info() ends in
+ * " front=N".  OFDG_EINVAL unless n is 1 .. 4. */
 int ofdg_set_front_batches(ofdg_ctx* ctx, int n);
+/* The group a call for n_samples samples gets under the setting `front`: the largest N <= front with N x n_samples <= 512,
+ * at least 1; OFDG_EINVAL unless front is 1 .. 4.  Needs no context and no device. */
+int ofdg_front_batches_for(int front, int n_samples);
+/* How many batches the chains hold ready for calls that have not come yet (the remaining parts of their groups): what the next
+ * call for something else forgets.  OFDG_EINVAL for a NULL context. */
+int ofdg_front_pending(const ofdg_ctx* ctx);
 
 /* Wait for `stream` and for everything the context has in flight, and report
  * device-side error flags raised by kernels. */

@@ -95,7 +95,7 @@ EXPORTS = [
     "ofdg_forward_counter", "ofdg_sample_counter", "ofdg_warp_generate", "ofdg_warp_upload", "ofdg_warp_info", "ofdg_warp_download", "ofdg_host_displacers",
     "ofdg_host_sampler_create", "ofdg_host_sampler_next", "ofdg_host_sampler_destroy", "ofdg_host_realize",
     "ofdg_parse_prototxt", "ofdg_host_last_error", "ofdg_host_decode_image", "ofdg_layer_create", "ofdg_layer_forward", "ofdg_layer_destroy",
-    "ofdg_layer_in_flight", "ofdg_poll_errors", "ofdg_poll_errors_of", "ofdg_last_ticket", "ofdg_num_chains", "ofdg_set_front_batches",
+    "ofdg_layer_in_flight", "ofdg_poll_errors", "ofdg_poll_errors_of", "ofdg_last_ticket", "ofdg_num_chains", "ofdg_set_front_batches", "ofdg_front_batches_for", "ofdg_front_pending",
     "ofdg_comm_unique_id", "ofdg_comm_init", "ofdg_comm_adopt", "ofdg_comm_destroy", "ofdg_comm_rank", "ofdg_comm_world_size",
     "ofdg_comm_last_error", "ofdg_comm_bcast_setup", "ofdg_comm_bcast_abort", "ofdg_comm_nccl_count", "ofdg_comm_bcast_pool", "ofdg_comm_agree", "ofdg_setup_of", "ofdg_setup_params",
     "ofdg_setup_alloc_pool", "ofdg_pool_device_mixed", "ofdg_pool_device_image", "ofdg_layer_create_dist",
@@ -928,6 +928,8 @@ def lib():
         L.ofdg_last_ticket.restype = C.c_longlong
         L.ofdg_num_chains.argtypes = [vp]
         L.ofdg_set_front_batches.argtypes = [vp, i32]
+        L.ofdg_front_batches_for.argtypes = [i32, i32]
+        L.ofdg_front_pending.argtypes = [vp]
         L.ofdg_comm_unique_id.argtypes = [vp]
         L.ofdg_comm_init.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
         L.ofdg_comm_adopt.argtypes = [vp, i32, i32, i32, C.POINTER(vp)]
@@ -1355,8 +1357,12 @@ class Generator:
         return lib().ofdg_num_chains(self.h)
 
     def set_front_batches(self, n):
-        """Counter sampler: batches of a chain one sampler -> geom -> raster launch serves, 2 (default) or 1 (include/ofdg.h)."""
+        """Counter sampler: batches of a chain one sampler -> geom -> raster launch serves, 1 .. 4 (include/ofdg.h)."""
         self._check(lib().ofdg_set_front_batches(self.h, int(n)))
+
+    def front_pending(self):
+        """Batches the chains hold ready for calls that have not come yet (include/ofdg.h)."""
+        return lib().ofdg_front_pending(self.h)
 
     def next_stream(self):
         """The internal hipStream_t (int) the next render / forward call works on; pass it as that call's

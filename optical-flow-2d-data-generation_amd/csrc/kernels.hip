@@ -316,13 +316,15 @@ __global__ __launch_bounds__(64 * kGeomWaves) void geom_kernel(const DevShape* _
                                                    DevShapeFrame* __restrict__ frames, int2* __restrict__ verts,
                                                    unsigned long long* __restrict__ blockmask, uint32_t* __restrict__ err,
                                                    int* __restrict__ item_count, int4* __restrict__ items,
-                                                   const DevCropRef* __restrict__ crops, int split_sf, uint32_t* __restrict__ err2) {
+                                                   const DevCropRef* __restrict__ crops, int part_sf, uint32_t* __restrict__ err1,
+                                                   uint32_t* __restrict__ err2, uint32_t* __restrict__ err3) {
   __shared__ GeomWs s_ws[kGeomWaves];
   step_kernel_priority();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sf = __builtin_amdgcn_readfirstlane(blockIdx.x * kGeomWaves + wave);
-  // (a slot that holds two batches of a chain: the outlines from split_sf on belong to the second one and flag in ITS word)
-  geom_wave(s_ws[wave], sf, lane, shapes, n_shapes, cs_tab, W, H, frames, verts, blockmask, sf >= split_sf ? err2 : err, item_count, items, crops);
+  // (a slot that holds up to four batches of a chain in parts of part_sf outlines: an outline flags in ITS batch's word)
+  geom_wave(s_ws[wave], sf, lane, shapes, n_shapes, cs_tab, W, H, frames, verts, blockmask,
+            front_pick(sf, part_sf, err, err1, err2, err3), item_count, items, crops);
 }
 
 // --------------------------------------------------------------------------

@@ -138,25 +138,29 @@ struct ofdg_ctx {
       hipStream_t stream = nullptr;  // where the preparation was enqueued
       long long ticket = -1;       // the batch's number (its error word)
       bool ahead = false;          // prepared by an EARLIER call (look-ahead): the end of its preparation says nothing about when compose could start
-      int base = 0;                // its first sample in the slot (a slot filled for two batches: the second one starts at n)
+      int base = 0;                // its first sample in the slot (a slot filled for N batches: part k starts at k x n)
     } prep;
-    // The paired front end (ofdg_set_front_batches): the sampler -> geom -> raster launches of a counter-sampler call fill the
-    // private slot for TWO batches, the call's own and the one this chain is asked for next.  `half` is that second batch while
-    // it waits for its call: sampled, outlined and rasterised in samples [n, 2n) of the slot, its background preparation and
-    // its compose still to be enqueued (launch_second_half).  Everything that forgets `prep` forgets `half` (discard_prepared).
-    Prepared half;
+    // The shared front end (ofdg_set_front_batches): the sampler -> geom -> raster launches of a counter-sampler call fill the
+    // private slot for a GROUP of N batches, the call's own (part 0) and the ones this chain is asked for next.  `rest` are the
+    // parts 1 .. N - 1 that still wait for their calls, in the order they will be asked for (rest_next is the next one): sampled,
+    // outlined and rasterised in samples [k n, (k + 1) n) of the slot, their background preparation and their compose still to
+    // be enqueued (launch_next_part).  Everything that forgets `prep` forgets them all (discard_prepared).
+    Prepared rest[kMaxFrontBatches - 1];
+    int rest_next = 0;
+    bool fresh = true;  // no group since the start or since parts were discarded: the next group is a first one (kFrontFirstGroup)
+    Prepared* next_part() { return rest_next < kMaxFrontBatches - 1 && rest[rest_next].valid ? &rest[rest_next] : nullptr; }
   };
   static constexpr int kMaxChains = 8;
   Chain chains[kMaxChains];
   int lookahead = 0;      // counter sampler: batches prepared ahead of the call that composes them (0: none)
-  int front_batches = 2;  // counter sampler: batches of a chain one sampler -> geom -> raster launch serves (ofdg_set_front_batches)
+  int front_batches = kFrontDefault;  // counter sampler: batches of a chain one sampler -> geom -> raster launch serves (ofdg_set_front_batches)
   std::string info_head;  // ofdg_ctx_info without its " front=N"
   long long last_first = -1;  // first index of the previous ofdg_forward_counter call (the stride of the caller's sequence)
   int n_chains = 3;       // one hardware queue each: HIP maps streams onto GPU_MAX_HW_QUEUES (4 by default) queues
   unsigned next_chain = 0;
   int last_chain = 0;     // the chain and the slot the last launch used (ofdg_render_resident, debug read-back)
   Slot* last_slot = nullptr;
-  int last_base = 0, last_n = 0;       // ... and the samples of that slot the last launch composed (a slot may hold two batches)
+  int last_base = 0, last_n = 0;       // ... and the samples of that slot the last launch composed (a slot may hold several batches)
   Chain* last_ch = nullptr;            // the chain that composed the batch in last_slot ...
   hipStream_t last_stream = nullptr;   // ... and the internal stream that call worked on (ofdg_object_table: OFDG_STREAM_OWN)
   hipStream_t last_user_st = nullptr;  // serial mode: the caller's stream of the last launch
@@ -211,7 +215,7 @@ struct ofdg_ctx {
   long long ev_count = 0, ev_alloc = 0, launch_count = 0;  // event sets: composed / handed out (a prepared batch holds one)
   std::vector<char> ev_composed;  // per set: its compose was enqueued (a prepared batch that is discarded leaves its set incomplete)
   std::vector<char> ev_bgprep;    // per set: the batch's background preparation ran behind raster and is timed (ev[3] .. ev[2] or ev[4])
-  std::vector<char> ev_front;     // per set: geom and raster were launched for it (a batch served from a second half has neither)
+  std::vector<char> ev_front;     // per set: geom and raster were launched for it (a batch served from a later part of a group has neither)
   std::vector<ofdg_task> fw_tasks;
   std::vector<ofdg_blueprint> fw_bps;
 };
@@ -839,16 +843,16 @@ static int size_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n_samples, size_t n_sh
 // device counter sampler + device realize fill the slot's records (no host data)
 static int prepare_backgrounds(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, bool records_resident, hipStream_t s, uint32_t* err, hipEvent_t stop = nullptr,
                                int base = 0, hipEvent_t start = nullptr);
-//   first_index2 >= 0: the slot is sized for two batches; samples [split, res_samples) are first_index2.. and flag in err2
-static int launch_counter_sampler(ofdg_ctx* c, ofdg_ctx::Slot& sl, long long first_index, hipStream_t s, uint32_t* err, int split,
-                                  long long first_index2, uint32_t* err2) {
+//   the slot is sized for res_samples / part batches: samples [k part, (k + 1) part) are first_index + k x part_stride .. and flag in err[k]
+static int launch_counter_sampler(ofdg_ctx* c, ofdg_ctx::Slot& sl, long long first_index, hipStream_t s, uint32_t* const err[kMaxFrontBatches],
+                                  int part, long long part_stride) {
   const int stride = sl.res_shapes / sl.res_samples;
   const int prep = c->prm.background_prep ? 1 : 0;
   CsRealizeDims D{c->prm.width, c->prm.height, c->pool_n, c->pool_w, c->pool_h, sl.res_samples, stride, prep,
                   c->prm.mode == 9 ? c->crop_server.n_crops : 0, c->fg_src.stride, c->fg_src.origin, c->bg_src.stride, c->bg_src.origin,
                   (unsigned long long)(uintptr_t)c->pool.p, c->d_tex_table.p, c->prm.mode == 9 ? c->d_cs_croptab.p : nullptr};
   hipLaunchKernelGGL(cs_sample_realize_kernel, dim3(sl.res_samples * kCsGroups), dim3(64), 0, s, c->cs_mode, D, first_index,
-                     sl.d_shapes.p, sl.d_objects.p, sl.d_samples.p, err, sl.d_bgprep.p, split, first_index2, err2);
+                     sl.d_shapes.p, sl.d_objects.p, sl.d_samples.p, err[0], sl.d_bgprep.p, part, part_stride, err[1], err[2], err[3]);
   HIP_OK(c, hipGetLastError());
   sl.bgprep_pending = prep != 0;  // (rendered behind raster: launch_prepare)
   return OFDG_OK;
@@ -877,17 +881,22 @@ static int clean_discarded_word(ofdg_ctx* c, const ofdg_ctx::Chain::Prepared& p)
   }
   return OFDG_OK;
 }
-// The second half of a paired front end that its call will not come for.  Its raster items are consumed and the work list was
-// reset by the first half's compose (or is, by discard_prepared, if that compose never ran either): only its word is left.
-static int discard_half(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
-  if (!ch.half.valid) return OFDG_OK;
-  ch.half.valid = false;
-  return clean_discarded_word(c, ch.half);
+// The remaining parts of a group that their calls will not come for.  Their raster items are consumed and the work list was
+// reset by part 0's compose (or is, by discard_prepared, if that compose never ran either): only their words are left.
+static int discard_rest(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
+  for (ofdg_ctx::Chain::Prepared& p : ch.rest) {
+    if (!p.valid) continue;
+    p.valid = false;
+    ch.fresh = true;
+    OFDG_TRY(clean_discarded_word(c, p));
+  }
+  return OFDG_OK;
 }
 static int discard_prepared(ofdg_ctx* c, ofdg_ctx::Chain& ch) {
-  OFDG_TRY(discard_half(c, ch));
+  OFDG_TRY(discard_rest(c, ch));
   if (!ch.prep.valid) return OFDG_OK;
   ch.prep.valid = false;
+  ch.fresh = true;
   if (ch.prep.slot && ch.prep.slot->d_item_count.p) HIP_OK(c, hipMemsetAsync(ch.prep.slot->d_item_count.p, 0, sizeof(int), ch.prep.stream));
   return clean_discarded_word(c, ch.prep);
 }
@@ -930,23 +939,28 @@ static void track_completion(ofdg_ctx::Slot& sl, ofdg_ctx::Chain& ch, hipStream_
 // The preparation kernels of the batch resident in `sl`, in order on chain `ch`: [counter sampler ->] geom -> raster
 //   `st` is the stream of the call the batch is prepared for (only the serial mode prepares on it).
 //   view_n > 0: the batch is samples [view_base, view_base + view_n) of the slot (ofdg_render_resident of a slot that was filled
-//   for two batches).  cs_first2 >= 0 (the paired front end): the slot is sized for 2 x n_first samples; the three launches
-//   serve both batches, the preparation behind them the first one only, and the second one is left in ch.half.
+//   for several batches).  group > 1 (the shared front end, counter sampler): the slot is sized for group x n_first samples, part k
+//   holding the batch of first index cs_first_index + k x part_stride; the three launches serve them all, the preparation behind
+//   them part 0 only, and parts 1 .. group - 1 are left in ch.rest.
 static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, hipStream_t st, long long cs_first_index = -1,
-                          bool hand_over = true, int view_base = 0, int view_n = 0, long long cs_first2 = -1, int n_first = 0) {
+                          bool hand_over = true, int view_base = 0, int view_n = 0, int group = 1, long long part_stride = 0, int n_first = 0) {
   const int W = c->prm.width, H = c->prm.height;
   const int n_sf = sl.res_shapes * 2;
   const RenderDims dm = render_dims(c, sl);
-  const bool paired = cs_first_index >= 0 && cs_first2 >= 0;
+  const bool grouped = cs_first_index >= 0 && group > 1;
+  if (!grouped) group = 1;
   OFDG_TRY(discard_prepared(c, ch));
-  // (this launch rewrites the slot's outlines and flips its block masks: a second half another chain keeps in it is gone)
+  // (this launch rewrites the slot's outlines and flips its block masks: the parts another chain keeps in it are gone)
   if (&sl != &ch.slot)
     for (int k = 0; k < c->n_chains; ++k)
-      if (c->chains[k].half.valid && c->chains[k].half.slot == &sl) OFDG_TRY(discard_half(c, c->chains[k]));
-  const long long ticket = c->ticket++;  // this batch's number: its kernels raise their flags in its own word
-  uint32_t* const err = err_word(c, ticket);
-  const long long ticket2 = paired ? c->ticket++ : -1;  // ... and the second batch's: every kernel of the front end knows its sample
-  uint32_t* const err2 = paired ? err_word(c, ticket2) : err;
+      if (c->chains[k].next_part() && c->chains[k].next_part()->slot == &sl) OFDG_TRY(discard_rest(c, c->chains[k]));
+  // this batch's number: its kernels raise their flags in its own word ... and the later parts': every kernel of the front end
+  // knows its sample (words past the group are part 0's: no sample selects them)
+  const long long ticket = c->ticket;
+  c->ticket += group;
+  uint32_t* errs[kMaxFrontBatches];
+  for (int k = 0; k < kMaxFrontBatches; ++k) errs[k] = err_word(c, ticket + (k < group ? k : 0));
+  uint32_t* const err = errs[0];
   Event* ev = nullptr;
   if (c->profiling && c->ev_sets > 0 && (c->launch_count % c->ev_stride) == 0) {
     const size_t set = (size_t)(c->ev_alloc++ % c->ev_sets);
@@ -973,9 +987,9 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   // mode 9: the batch's own crop table (host path) or the static table of all crops (counter sampler)
   const DevCropRef* croptab = cs_first_index >= 0 ? c->d_cs_croptab.p : sl.d_croptab.p;
   HIP_OK(c, take_err_word(c, ticket, S));  // (nothing is enqueued unless this caller asks by ticket AND the word's last owner was never asked about)
-  if (paired) HIP_OK(c, take_err_word(c, ticket2, S));
+  for (int k = 1; k < group; ++k) HIP_OK(c, take_err_word(c, ticket + k, S));
   if (cs_first_index >= 0) {  // device counter sampler + device realize
-    OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, err, paired ? n_first : sl.res_samples, cs_first2, err2));
+    OFDG_TRY(launch_counter_sampler(c, sl, cs_first_index, S, errs, grouped ? n_first : sl.res_samples, grouped ? part_stride : 0));
   }
   // (the background preparation of the batch goes LAST, right in front of compose: below)
   // geom: outlines, bounding boxes, per-object boxes (parity `bp`), raster work list
@@ -994,7 +1008,7 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   hipExtLaunchKernelGGL(geom_kernel, dim3(std::max(1, (n_sf + kGeomWaves - 1) / kGeomWaves)), dim3(64 * kGeomWaves), 0, S,
                         prof_prep ? ev[0].e : nullptr, prof_prep ? ev[1].e : nullptr, 0, sl.d_shapes.p, sl.res_shapes, c->d_cs_tab.p, W, H,
                         sl.d_frames.p, sl.d_verts.p, box_cur, err, sl.d_item_count.p, sl.d_items.p, croptab,
-                        paired ? n_first * (sl.res_shapes / sl.res_samples) * 2 : 0x7fffffff, err2);
+                        grouped ? n_first * (sl.res_shapes / sl.res_samples) * 2 : std::max(n_sf, 1), errs[1], errs[2], errs[3]);
   HIP_OK(c, hipGetLastError());
   // The batch's last preparation kernel - raster, or the background preparation behind it - carries two things on its own
   // packet: the hand-over event of a compose on a caller's stream, or (profiling 1) the start of the compose launch's time.
@@ -1004,35 +1018,38 @@ static int launch_prepare(ofdg_ctx* c, ofdg_ctx::Chain& ch, ofdg_ctx::Slot& sl, 
   const bool prep_last = sl.bgprep_pending;
   hipEvent_t last_stop = ev ? (c->profiling == 2 ? nullptr : ev[4].e) : (hand_over ? ch.ev_prep.e : nullptr);
   // (a profiled batch with a preparation behind raster also takes raster's completion: the preparation is timed from there)
-  hipExtLaunchKernelGGL(raster_kernel, dim3((paired ? kRasterGridPaired : kRasterGrid) * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, S, nullptr,
+  hipExtLaunchKernelGGL(raster_kernel, dim3(kRasterGridFront[group] * 4 / kRasterWaves), dim3(64 * kRasterWaves), 0, S, nullptr,
                         (ev && (c->profiling == 2 || prep_last)) ? ev[3].e : (prep_last ? nullptr : last_stop), 0,
                         sl.d_frames.p, sl.d_items.p, sl.d_item_count.p, sl.d_verts.p, W, H, cov, box_next, n_mask_words, box_cur);
   HIP_OK(c, hipGetLastError());
   if (prep_last) {
-    // (of a pair: the first batch's only - the second one's goes in front of ITS compose, launch_second_half)
-    OFDG_TRY(prepare_backgrounds(c, sl, paired ? n_first : sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2].e : last_stop));
+    // (of a group: part 0's only - a later part's goes in front of ITS compose, launch_next_part)
+    OFDG_TRY(prepare_backgrounds(c, sl, grouped ? n_first : sl.res_samples, /*records_resident=*/true, S, err, (ev && c->profiling == 2) ? ev[2].e : last_stop));
     sl.bgprep_pending = false;
     if (ev) c->ev_bgprep[(size_t)(ev - c->ev.data()) / 6] = 1;
   }
   if (ev && hand_over) HIP_OK(c, hipEventRecord(ch.ev_prep, S));
   ch.prep.valid = true; ch.prep.slot = &sl; ch.prep.first_index = cs_first_index;
-  ch.prep.n = paired ? n_first : (view_n > 0 ? view_n : sl.res_samples);
+  ch.prep.n = grouped ? n_first : (view_n > 0 ? view_n : sl.res_samples);
   ch.prep.base = view_n > 0 ? view_base : 0;
   ch.prep.box_cur = box_cur; ch.prep.croptab = croptab; ch.prep.ev = ev; ch.prep.stream = S; ch.prep.ticket = ticket;
   ch.prep.ahead = false;
-  if (paired) {
-    ch.half = ch.prep;
-    ch.half.first_index = cs_first2; ch.half.base = n_first; ch.half.ev = nullptr; ch.half.ticket = ticket2;
+  ch.rest_next = 0;
+  for (int k = 1; k < group; ++k) {
+    ofdg_ctx::Chain::Prepared& p = ch.rest[k - 1];
+    p = ch.prep;
+    p.first_index = cs_first_index + k * part_stride; p.base = k * n_first; p.ev = nullptr; p.ticket = ticket + k;
   }
+  ch.fresh = false;
   return OFDG_OK;
 }
 
-// The call the second half of a paired front end was made for has come: samples [n, 2n) of the chain's private slot are
+// The call the next part of a group was made for has come: samples [k n, (k + 1) n) of the chain's private slot are
 // sampled, outlined and rasterised.  What is left is the batch's own background preparation, on the chain's stream, and the
 // hand-over of a compose on a caller's stream - recorded behind THAT preparation.  No geom / raster launch: a profiled call's
 // event set says so (ev_front), and profiling 1 has a predecessor of compose on the chain only where there is a preparation.
-static int launch_second_half(ofdg_ctx* c, ofdg_ctx::Chain& ch, bool hand_over) {
-  ofdg_ctx::Chain::Prepared h = ch.half;
+static int launch_next_part(ofdg_ctx* c, ofdg_ctx::Chain& ch, bool hand_over) {
+  ofdg_ctx::Chain::Prepared h = *ch.next_part();
   ofdg_ctx::Slot& sl = *h.slot;
   const hipStream_t S = h.stream;
   const bool prep = c->prm.background_prep != 0;
@@ -1045,11 +1062,11 @@ static int launch_second_half(ofdg_ctx* c, ofdg_ctx::Chain& ch, bool hand_over) 
     c->ev_front[set] = 0;
   }
   c->launch_count++;
-  // the first half's compose may have run on a caller's stream: the chain's stream is ordered behind it from here on, as in
+  // the previous part's compose may have run on a caller's stream: the chain's stream is ordered behind it from here on, as in
   // launch_prepare (the event is about to be taken by this batch's compose)
   if (ch.done_pending && ch.done_stream != S) OFDG_TRY(wait_unless_fired(c, S, ch.ev_done, &ch.done_pending, /*settles=*/true));
   if (sl.compose_pending && sl.compose_stream != S) OFDG_TRY(wait_unless_fired(c, S, sl.compose_event, &sl.compose_pending));
-  ch.half.valid = false;  // (taken: a failure below leaves it to discard_prepared as `prep`)
+  ch.rest[ch.rest_next++].valid = false;  // (taken: a failure below leaves it to discard_prepared as `prep`)
   h.ev = ev;
   ch.prep = h;
   if (prep) {
@@ -1512,7 +1529,7 @@ int ofdg_render_resident(ofdg_ctx* c, float* d_img0, float* d_img1, float* d_flo
   // a chain's private slot is not tracked by events while only that chain uses it: let its owner drain first
   for (int k = 0; k < c->n_chains; ++k)
     if (&c->chains[k].slot == c->last_slot && !c->last_slot->compose_pending) HIP_OK(c, hipStreamSynchronize(c->chains[k].stream));
-  // (the batch the last call composed: of a slot that was filled for two batches, that call's samples)
+  // (the batch the last call composed: of a slot that was filled for a group of batches, that call's samples)
   const int view_base = c->last_base, view_n = c->last_n;
   return launch_resident(c, take_chain(c), *c->last_slot, CallOut{"ofdg_render_resident", d_img0, d_img1, d_flow, {}, 0}, (hipStream_t)stream, -1,
                          view_base, view_n);
@@ -1539,7 +1556,7 @@ int ofdg_object_table(ofdg_ctx* c, const uint8_t* d_label0, const uint8_t* d_lab
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const int W = c->prm.width, H = c->prm.height, n = c->last_n;
-  const DevSample* const samples = sl.d_samples.p + c->last_base;  // (the batch that call composed: a slot may hold two)
+  const DevSample* const samples = sl.d_samples.p + c->last_base;  // (the batch that call composed: a slot may hold several)
   // The slot's records must outlive the kernels.  On the chain's own stream the order of the stream sees to that (a private
   // slot is rewritten there only); on a caller's stream - or for a caller's slot, which any stream may rewrite - the last
   // kernel carries the chain's completion event, as a compose on a caller's stream does (launch_compose): a later call
@@ -1788,7 +1805,7 @@ int ofdg_pack(ofdg_ctx* c, const struct ofdg_pack_job* job, int n_samples, void*
 
 // size slot `sl` for n device-sampled samples: a fixed number of shape slots per sample
 // (unused ones are typed 0 and produce no outline)
-//   front = 2: the slot holds two such batches (the paired front end)
+//   front = N: the slot holds N such batches (a group of the shared front end)
 static int prepare_counter_slot(ofdg_ctx* c, ofdg_ctx::Slot& sl, int n, int front = 1) {
   if (c->prm.mode == 9) OFDG_TRY(ensure_counter_croptab(c));
   OFDG_TRY(finalise_pool(c));
@@ -1831,18 +1848,23 @@ static int forward_counter_impl(ofdg_ctx* c, long long first_index, int n_sample
   const long long stride = (prev_first >= 0 && first_index > prev_first) ? first_index - prev_first
                                                                            : (long long)n_samples * std::max(1, c->prm.world_size);
   const bool hand_over = chain_stream(c, ch, st) != st;
-  // The paired front end: sampler, geom and raster are latency-bound single-wave kernels whose launches last about as long
-  // for two batches as for one, so this chain runs them for the batch it will be asked for NEXT as well (n_chains calls on),
-  // and that call launches only its background preparation and compose.  Stream order and what runs beside what stay as
-  // they are.  A call for anything else than the second half forgets it and prepares its own pair.  (2 x n stays within
-  // the 512 samples a slot was ever sized for.)
-  if (c->front_batches == 2 && c->overlap && c->lookahead == 0 && 2 * n_samples <= 512) {
-    if (ch.half.valid && ch.half.slot == &ch.slot && ch.half.first_index == first_index && ch.half.n == n_samples && !ch.prep.valid) {
-      OFDG_TRY(launch_second_half(c, ch, hand_over));
+  // The shared front end: sampler, geom and raster are latency-bound single-wave kernels whose launches last little longer
+  // for several batches than for one, so this chain runs them for a GROUP: its batch and the N - 1 it will be asked for NEXT
+  // (n_chains calls on each), and those calls launch only their background preparation and compose.  Stream order and what
+  // runs beside what stay as they are.  A call for anything else than the group's next part forgets the rest of it and
+  // prepares a group of its own.  (N x n stays within the kPrepMaxSamples a slot was ever sized for: the largest N that does.)
+  const int front = (c->overlap && c->lookahead == 0) ? ofdg_front_batches_for(c->front_batches, n_samples) : 1;
+  if (front > 1) {
+    const ofdg_ctx::Chain::Prepared* const nx = ch.next_part();
+    if (nx && nx->slot == &ch.slot && nx->first_index == first_index && nx->n == n_samples && !ch.prep.valid) {
+      OFDG_TRY(launch_next_part(c, ch, hand_over));
     } else {
       OFDG_TRY(discard_prepared(c, ch));
-      OFDG_TRY(prepare_counter_slot(c, ch.slot, n_samples, 2));
-      OFDG_TRY(launch_prepare(c, ch, ch.slot, st, first_index, hand_over, 0, 0, first_index + (long long)c->n_chains * stride, n_samples));
+      const int group = ch.fresh ? std::min(front, kFrontFirstGroup) : front;
+      // (a shorter first group reserves what the whole ones behind it need: growing a workspace waits for the device)
+      if (group < front) OFDG_TRY(prepare_counter_slot(c, ch.slot, n_samples, front));
+      OFDG_TRY(prepare_counter_slot(c, ch.slot, n_samples, group));
+      OFDG_TRY(launch_prepare(c, ch, ch.slot, st, first_index, hand_over, 0, 0, group, (long long)c->n_chains * stride, n_samples));
     }
   } else {
     OFDG_TRY(prepare_on(ch, first_index, st, hand_over));
@@ -2010,17 +2032,35 @@ int ofdg_set_step(ofdg_ctx* c, long long step) {
       }
     }
   }
-  // (a second half was sampled for the sequence the old counter was walking)
-  if (step != c->step) for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_half(c, c->chains[k]));
+  // (the remaining parts of a group were sampled for the sequence the old counter was walking)
+  if (step != c->step) for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_rest(c, c->chains[k]));
   c->step = step;
   return OFDG_OK;
 }
 
-// Batches of a chain that one sampler -> geom -> raster launch serves on the counter-sampler path: 2 (the default, see
-// forward_counter_impl) or 1 (every call launches its own front end).  A scheduling choice: the bytes are the same.
+// Batches of a chain that one sampler -> geom -> raster launch serves on the counter-sampler path: 1 (every call launches its
+// own front end) .. kMaxFrontBatches (see forward_counter_impl).  A scheduling choice: the bytes are the same.
+// ... and how many of them a call for n_samples samples gets: the largest N <= front with N x n_samples <= kPrepMaxSamples
+// (OFDG_EINVAL: front is out of range).  No context, no device.
+int ofdg_front_batches_for(int front, int n_samples) {
+  if (front < 1 || front > kMaxFrontBatches) return OFDG_EINVAL;
+  while (front > 1 && (long long)front * n_samples > kPrepMaxSamples) --front;
+  return front;
+}
+// How many batches are sampled, outlined and rasterised and still wait for their calls, over all chains.
+int ofdg_front_pending(const ofdg_ctx* c) {
+  if (!c) return OFDG_EINVAL;
+  int n = 0;
+  for (int k = 0; k < c->n_chains; ++k)
+    for (const ofdg_ctx::Chain::Prepared& p : c->chains[k].rest) n += p.valid ? 1 : 0;
+  return n;
+}
 int ofdg_set_front_batches(ofdg_ctx* c, int n) {
-  if (!c || (n != 1 && n != 2)) { if (c) c->err = "ofdg_set_front_batches: n = " + std::to_string(n) + " (valid: 1, 2)"; return OFDG_EINVAL; }
-  for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_half(c, c->chains[k]));
+  if (!c || ofdg_front_batches_for(n, 1) < 1) {
+    if (c) c->err = "ofdg_set_front_batches: n = " + std::to_string(n) + " (valid: 1 .. " + std::to_string(kMaxFrontBatches) + ")";
+    return OFDG_EINVAL;
+  }
+  for (int k = 0; k < c->n_chains; ++k) OFDG_TRY(discard_rest(c, c->chains[k]));
   c->front_batches = n;
   c->info = c->info_head + " front=" + std::to_string(n);
   return OFDG_OK;
@@ -2350,7 +2390,7 @@ int ofdg_debug_bgprep_tiles(ofdg_ctx* c, int* tiles, int* workgroups) {
   int cap_cw, cap_ch;
   bool fusable;
   bgprep_caps(c, &cap_cw, &cap_ch, &fusable);
-  const int n = c->last_n;  // (the batch the last call composed: a slot may hold two)
+  const int n = c->last_n;  // (the batch the last call composed: a slot may hold several)
   if (c->prm.background_prep != 1 || !fusable || n > kPrepMaxSamples || n < 1 || !sl.d_bgprep.p) return OFDG_OK;
   HIP_OK(c, hipDeviceSynchronize());
   std::vector<DevBgPrep> rec((size_t)n);
@@ -2415,7 +2455,7 @@ int ofdg_kernel_ms(ofdg_ctx* c, const char* kernel, float* ms) {
   for (int k = 0; k < c->ev_sets; ++k) {
     if (!c->ev_composed[(size_t)k]) continue;  // (never handed out, or its prepared batch was discarded before compose)
     if (i == 3 && !c->ev_bgprep[(size_t)k]) continue;
-    if (i < 2 && !c->ev_front[(size_t)k]) continue;  // (served from a second half: no geom / raster launch, its ev[0 .. 3] are stale)
+    if (i < 2 && !c->ev_front[(size_t)k]) continue;  // (served from a later part of a group: no geom / raster launch, its ev[0 .. 3] are stale)
     ++n;
     const Event* ev = &c->ev[(size_t)k * 6];
     HIP_OK(c, hipEventSynchronize(ev[5]));

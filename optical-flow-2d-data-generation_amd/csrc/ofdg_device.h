@@ -32,12 +32,41 @@ constexpr int kRasterGrid = 512;    // x4 persistent single-wave raster workgrou
 #define OFDG_RASTER_GRID_PAIRED 768
 #endif
 constexpr int kRasterGridPaired = OFDG_RASTER_GRID_PAIRED;
+// ... and three or four (ofdg_set_front_batches; profiles/front_n_raster_grid.txt).  15 waves of 10.2 KB LDS fit a
+// CU, 960 x 4 on the device: the waves beyond them start as the first ones finish their share of the list.
+#ifndef OFDG_RASTER_GRID_3
+#define OFDG_RASTER_GRID_3 1536
+#endif
+#ifndef OFDG_RASTER_GRID_4
+#define OFDG_RASTER_GRID_4 1536
+#endif
+constexpr int kMaxFrontBatches = 4;  // batches of a chain one sampler -> geom -> raster launch may serve
+constexpr int kRasterGridFront[kMaxFrontBatches + 1] = {kRasterGrid, kRasterGrid, kRasterGridPaired, OFDG_RASTER_GRID_3, OFDG_RASTER_GRID_4};
+// ... of which the FIRST group a chain launches after a start or a discard holds at most this many.  4: every group is N.  2
+// ("first a pair": a shorter fill, fewer parts nobody asks for at the end of a short run) measured worse at N = 4 in a 20-step
+// run and better at N = 3 (profiles/front_n_ab.txt).
+#ifndef OFDG_FRONT_FIRST_GROUP
+#define OFDG_FRONT_FIRST_GROUP 4
+#endif
+constexpr int kFrontFirstGroup = OFDG_FRONT_FIRST_GROUP;
+// ... and a new context's setting (profiles/front_n_ab.txt)
+#ifndef OFDG_FRONT_DEFAULT
+#define OFDG_FRONT_DEFAULT 4
+#endif
+constexpr int kFrontDefault = OFDG_FRONT_DEFAULT;
 
 // error bits raised by kernels (device word, read by ofdg_synchronize)
 constexpr uint32_t kErrVertCapacity = 1u;   // outline has more than kMaxVerts vertices
 constexpr uint32_t kErrCurveCapacity = 2u;  // a curve exceeded kCurveMaxPts / kCurveMaxDepth
 constexpr uint32_t kErrDxLimit = 4u;        // an edge spans >= 16384 px (AGG dx_limit)
 constexpr uint32_t kErrBgPrepCapacity = 8u; // background_prep: a crop of the rotated image exceeds the workspace (zoom < 0.75)
+
+// A slot filled for up to kMaxFrontBatches batches of a chain in equal parts: what belongs to the part element i is in (its
+// error word, its offset).  Compares and selects, no division: i and part are wave-uniform where this is used, so it stays scalar.
+template <typename T>
+OFDG_HD_FN T front_pick(int i, int part, T p0, T p1, T p2, T p3) {
+  return i < part ? p0 : (i < 2 * part ? p1 : (i < 3 * part ? p2 : p3));
+}
 
 // 2x3 affine in AGG's member order (sx, shy, shx, sy, tx, ty), fp64.
 struct Mat {
