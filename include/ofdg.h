@@ -836,6 +836,66 @@ int ofdg_pack(ofdg_ctx* ctx, const struct ofdg_pack_job* job, int n_samples, voi
  * plane size; the job's own must be 0, 0 or the same.  Errors as above through ofdg_host_last_error. */
 int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, int height);
 
+/* ---- motion boundaries: ofdg_boundaries --------------------------------------------------------------------------------------
+ * The ground truth FlyingThings3D ships next to its occlusion masks and Sintel evaluates in bands of (d0-10, d10-60, d60-140):
+ * a mask of the pixels on either side of a step in the flow, and the squared distance of every pixel to the nearest of them,
+ * of both frames and every sample in ONE launch behind the call that wrote the flow.  Everything below is exact: the kernel,
+ * ofdg_host_boundaries and the numpy restatement of the tests give the same bytes.
+ *
+ * Frames.  Frame f is processed when flow[f] is set and must then have at least one of edge[f] and dist2[f].  Frame 0 takes
+ * flow (and label0), frame 1 flow1 (and label1); of a frame that is absent the label is not looked at.  flow[f] is
+ * [n,2,height,width] of flow_fmt (OFDG_FMT_F32 or OFDG_FMT_F16), label[f] [n,height,width] uint8, edge[f] and dist2[f]
+ * [n,1,height,width] uint8.  width, height: 0, 0 for the context's frame, or a width that is a multiple of 8 (at least 8) with
+ * an even height (at least 2) - the planes ofdg_crop and ofdg_spatial wrote.
+ *
+ * Edge.  u and v are widened to float32 (exact for binary16).  Two 4-neighbours p, q (one apart in x or in y), both inside the
+ * plane, are a STEP when - with OFDG_BND_LABELS - label[p] != label[q], and d2 > t2, where du = fl32(u_p - u_q), dv = fl32(v_p
+ * - v_q), d2 = fl32(fl32(du * du) + fl32(dv * dv)) and t2 = fl32(min_step * min_step): IEEE float32, every operation rounded
+ * on its own (no contraction), denormals kept.  A NaN d2 compares false, so inf - inf and anything beside a NaN is no step; an
+ * infinite d2 is one (inf beside a finite value; +-65504 beside its negation in float32 is finite and compares as such).  With
+ * min_step 0 a difference whose square underflows to 0 is no step.  The rule is symmetric in p and q.  edge(p) = 1 when p
+ * belongs to at least one step, else 0: a boundary is two pixels thick, one on each side.  Without OFDG_BND_LABELS label[f]
+ * is not read and may be NULL or set (left open by the issue: fixed here).
+ *
+ * Distance.  dist2(x, y) is the smallest (x - x')^2 + (y - y')^2 over the edge pixels (x', y') of the same sample and frame
+ * for which that value is <= radius^2, or OFDG_BND_FAR when there is none: at most 225, 0 on the edge itself, and the Sintel
+ * bands are thresholds on it (d < 10 is dist2 < 100).  Nothing wraps across samples, frames or the plane's border.  radius is
+ * read only when a dist2 plane is set and must then lie in 1 .. OFDG_BND_MAX_RADIUS.
+ *
+ * All 13 modes: mode 9 renders no labels and works without OFDG_BND_LABELS (min_step then decides alone).
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_crop.  One kernel for any
+ * n_samples, both frames and both outputs, no atomics; it reads no record of the context.  Sources are left as they are.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, only one of
+ * width / height 0, a size that breaks the rule above, width * height of 2^31 and more, unknown flag bits, non-zero reserved,
+ * another flow_fmt, no frame present, an output of a frame without its flow, a frame with a flow and no output,
+ * OFDG_BND_LABELS with a present frame that lacks its label, a min_step that is NaN, negative or infinite, a radius outside 1
+ * .. 15 with a dist2 set, a misaligned pointer (flow 16-byte float32 / 8-byte binary16, labels 4-byte, outputs 16-byte), an
+ * output range that overlaps any other range of the job (a range is the n * C * height * width elements of its plane; the label
+ * of a present frame counts when set, used or not), OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: an 8-neighbour rule, radii above 15 or a float distance, per-sample boundary counts, packing these planes in
+ * ofdg_pack, mapping them through ofdg_spatial other than by calling this entry on the warped planes, an in-place form.
+ */
+#define OFDG_BND_LABELS 1       /* a neighbour pair counts only where its labels differ; label[f] required */
+#define OFDG_BND_MAX_RADIUS 15
+#define OFDG_BND_FAR 255
+struct ofdg_boundary_job {      /* 96 bytes */
+  const void*    flow[2];       /* [n,2,H,W] flow / flow1, element type flow_fmt, or NULL: frame absent */
+  const uint8_t* label[2];      /* [n,H,W] label0 / label1, or NULL */
+  uint8_t*       edge[2];       /* [n,1,H,W] uint8 1 / 0, or NULL */
+  uint8_t*       dist2[2];      /* [n,1,H,W] uint8, or NULL */
+  int32_t width, height;        /* 0, 0: the context's frame */
+  int32_t flow_fmt, flags, radius;
+  float   min_step;
+  int32_t reserved[2];
+};
+int ofdg_boundaries(ofdg_ctx* ctx, const struct ofdg_boundary_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: no alignment asked of any pointer.  width, height: the plane
+ * size; the job's own must be 0, 0 or the same.  Errors as above through ofdg_host_last_error. */
+int ofdg_host_boundaries(const struct ofdg_boundary_job* job, int n_samples, int width, int height);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -109,6 +109,7 @@ EXPORTS = [
     "ofdg_photo", "ofdg_host_photo", "ofdg_photo_draw", "ofdg_debug_photo_table", "ofdg_host_photo_table", "ofdg_host_det_log",
     "ofdg_spatial", "ofdg_host_spatial", "ofdg_spatial_draw",
     "ofdg_pack", "ofdg_host_pack",
+    "ofdg_boundaries", "ofdg_host_boundaries",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -811,6 +812,114 @@ def host_pack(src, image_dtype=None, flow_dtype=None, scale=(1.0, 1.0, 1.0), bia
     return dst
 
 
+# motion boundaries (struct ofdg_boundary_job / ofdg_boundaries, include/ofdg.h)
+BND_LABELS = 1       # OFDG_BND_LABELS
+BND_MAX_RADIUS = 15  # OFDG_BND_MAX_RADIUS
+BND_FAR = 255        # OFDG_BND_FAR
+
+
+class BoundaryJob(C.Structure):
+    """struct ofdg_boundary_job (96 bytes)."""
+    _fields_ = [("flow", C.c_void_p * 2), ("label", C.c_void_p * 2), ("edge", C.c_void_p * 2), ("dist2", C.c_void_p * 2),
+                ("width", C.c_int32), ("height", C.c_int32), ("flow_fmt", C.c_int32), ("flags", C.c_int32), ("radius", C.c_int32),
+                ("min_step", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def boundaries_format(flow, edge=None, dist2=None, label=None, flow1=None, edge1=None, dist2_1=None, label1=None, height=None, width=None):
+    """(n, height, width, flow code) of the planes of Generator.boundaries / host_boundaries: flow / flow1 float32 or float16
+    [n,2,H,W] (one dtype for both; a frame is present when its flow is given, and at least one must be), label / label1 None or
+    uint8 [n,H,W], edge / edge1 and dist2 / dist2_1 None or uint8 [n,1,H,W], at least one of the two for a frame that is present
+    and none for one that is not.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and
+    numpy arrays)."""
+    frames = ((flow, edge, dist2, label, ""), (flow1, edge1, dist2_1, label1, "1"))
+    first = flow if flow is not None else flow1
+    if first is None:
+        raise ValueError("flow or flow1 must be given: no frame is present")
+    shape = tuple(first.shape)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 2 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a flow must be float32 or float16 [n,2,%s,%s], got %s %s" % (height or "height", width or "width", _dtype_name(first), shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    if width < 8 or width % 8 or height < 2 or height % 2:
+        raise ValueError("the planes must be a multiple of 8 wide and even high, got %dx%d" % (width, height))
+    codes = set()
+    for fl, e, d, lab, tag in frames:
+        names = ("flow" + tag, "edge" + tag, "dist2" + ("_1" if tag else ""), "label" + tag)
+        if fl is None:
+            if e is not None or d is not None:
+                raise ValueError("%s / %s need %s" % (names[1], names[2], names[0]))
+            continue
+        _check_plane(names[0], fl, _FLOW_CODES, (n, 2, height, width))
+        codes.add(_FLOW_CODES[_dtype_name(fl)])
+        if e is None and d is None:
+            raise ValueError("%s needs at least one of %s and %s" % names[:3])
+        for name, t in ((names[1], e), (names[2], d)):
+            if t is not None:
+                _check_plane(name, t, ("uint8",), (n, 1, height, width))
+        if lab is not None:
+            _check_plane(names[3], lab, ("uint8",), (n, height, width))
+    if len(codes) > 1:
+        raise ValueError("flow and flow1 must have one dtype")
+    return n, height, width, codes.pop()
+
+
+def _boundary_job(planes, ptr, code, size, radius, min_step, labels):
+    """planes: (flow, edge, dist2, label, flow1, edge1, dist2_1, label1); labels None: used when a label plane is given"""
+    if labels is None:
+        labels = any(planes[4 * f] is not None and planes[4 * f + 3] is not None for f in range(2))
+    job = BoundaryJob()
+    for f in range(2):
+        fl, e, d, lab = planes[4 * f:4 * f + 4]
+        if labels and fl is not None and lab is None:
+            raise ValueError("labels=True needs the label plane of every frame that is present")
+        for field, t in ((job.flow, fl), (job.edge, e), (job.dist2, d), (job.label, lab if labels else None)):
+            if t is not None:
+                field[f] = ptr(t)
+    job.height, job.width = size
+    job.flow_fmt, job.flags, job.radius, job.min_step = code, BND_LABELS if labels else 0, int(radius), float(min_step)
+    return job
+
+
+def alloc_boundaries(n, height, width, frames=(0,), edge=True, dist=True, device="cuda", zero=True):
+    """The outputs of Generator.boundaries as a dict: "edge0" / "dist0" (and "edge1" / "dist1" with 1 among frames), uint8
+    [n,1,height,width] each.  zero=False: not filled (the call writes every element)."""
+    import torch
+    make = torch.zeros if zero else torch.empty
+    out = {}
+    for f in frames:
+        if f not in (0, 1):
+            raise ValueError("frames must hold 0 and / or 1, got %r" % (f,))
+        if edge:
+            out["edge%d" % f] = make((n, 1, height, width), dtype=torch.uint8, device=device)
+        if dist:
+            out["dist%d" % f] = make((n, 1, height, width), dtype=torch.uint8, device=device)
+    if not out:
+        raise ValueError("alloc_boundaries needs a frame and at least one of edge and dist")
+    return out
+
+
+def host_boundaries(flow=None, label=None, flow1=None, label1=None, radius=10, min_step=0.0, labels=None, edge=True, dist=True):
+    """ofdg_host_boundaries (no GPU) on numpy arrays: flow / flow1 float32 or float16 [n,2,H,W], label / label1 None or uint8
+    [n,H,W]; labels None: used when a label plane is given.  Returns the dict alloc_boundaries describes - "edge0", "dist0" for
+    flow, "edge1", "dist1" for flow1, uint8 [n,1,H,W], as far as edge / dist ask for them."""
+    import numpy as np
+    src = [None if a is None else np.ascontiguousarray(a) for a in (flow, label, flow1, label1)]
+    first = src[0] if src[0] is not None else src[2]
+    out = {}
+    if first is not None and first.ndim == 4:
+        n, _, height, width = first.shape
+        for f in range(2):
+            if src[2 * f] is not None:
+                if edge:
+                    out["edge%d" % f] = np.zeros((n, 1, height, width), np.uint8)
+                if dist:
+                    out["dist%d" % f] = np.zeros((n, 1, height, width), np.uint8)
+    planes = (src[0], out.get("edge0"), out.get("dist0"), src[1], src[2], out.get("edge1"), out.get("dist1"), src[3])
+    n, height, width, code = boundaries_format(planes[0], planes[1], planes[2], planes[3], planes[4], planes[5], planes[6], planes[7])
+    job = _boundary_job(planes, lambda a: a.ctypes.data, code, (0, 0), radius, min_step, labels)
+    _host_check(lib().ofdg_host_boundaries(C.byref(job), n, width, height))
+    return out
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -903,6 +1012,8 @@ def lib():
         L.ofdg_spatial_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(SpatialJob), vp]
         L.ofdg_pack.argtypes = [vp, C.POINTER(PackJob), i32, vp]
         L.ofdg_host_pack.argtypes = [C.POINTER(PackJob), i32, i32, i32]
+        L.ofdg_boundaries.argtypes = [vp, C.POINTER(BoundaryJob), i32, vp]
+        L.ofdg_host_boundaries.argtypes = [C.POINTER(BoundaryJob), i32, i32, i32]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1312,6 +1423,22 @@ class Generator:
                         layout, concat, rgb)
         self._check(lib().ofdg_pack(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
+
+    def boundaries(self, flow, edge=None, dist2=None, label=None, flow1=None, edge1=None, dist2_1=None, label1=None, radius=10, min_step=0.0,
+                   labels=None, stream=0, size=None):
+        """Motion-boundary masks and squared distances to the nearest boundary in one launch (ofdg_boundaries, include/ofdg.h).
+        flow / flow1: the float32 / float16 [n,2,H,W] flow of frame 0 / frame 1 (either may be None: that frame is left out);
+        edge / edge1: uint8 [n,1,H,W], 1 on the two pixels of every step of the flow; dist2 / dist2_1: uint8 [n,1,H,W], the
+        squared distance to the nearest edge pixel within `radius` (1..15), BND_FAR beyond (alloc_boundaries makes all four);
+        label / label1: the uint8 [n,H,W] label planes.  labels: a neighbour pair counts only where its labels differ - None:
+        when a label plane is given.  min_step: a pair is a step when its flow difference exceeds it (pixels).  stream: the
+        stream the planes were written on, or STREAM_OWN.  size=(height, width): planes of that size instead of the context's
+        frame.  Asynchronous."""
+        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        n, _, _, code = boundaries_format(flow, edge, dist2, label, flow1, edge1, dist2_1, label1, height, width)
+        job = _boundary_job((flow, edge, dist2, label, flow1, edge1, dist2_1, label1), lambda t: _dptr(t).value, code,
+                            (0, 0) if size is None else (height, width), radius, min_step, labels)
+        self._check(lib().ofdg_boundaries(self.h, C.byref(job), n, C.c_void_p(stream)))
 
     def debug_photo_table(self, rec):
         """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
@@ -1970,13 +2097,22 @@ class FlowLoader:
     (Generator.pack, enqueued on the same internal stream as the LAST step of the batch: behind crop / spatial and photo, on
     their outputs; stats= and pyramid= keep reading the unpacked, unscaled flow).  The loader then yields the packed tensors in
     the places of image0, image1 and flow - with concat the 6-channel tensor first and None second -; extras, objects, stats
-    and pyramid are untouched.  The pyramid's levels, labels and occlusion maps are not packed."""
+    and pyramid are untouched.  The pyramid's levels, labels and occlusion maps are not packed.
+    boundaries=dict(radius=, min_step=, labels=, frames=, edge=, dist=) (every key optional: radius 10, min_step 0, labels None -
+    used when the frame's label plane is among extras= -, frames (0,), edge and dist True): the motion-boundary masks and the
+    distance-to-boundary maps of every batch (Generator.boundaries into a further ring of buffers, enqueued on the same
+    internal stream behind the batch - behind crop / spatial, on their flow and label planes -, ahead of the pack; the
+    photometric step does not touch what it reads).  Every batch is then (image0, image1, flow, {...}) and the dict also holds
+    "edge0" and "dist0" (uint8 [n,1,H,W]), and "edge1" and "dist1" when frame 1 is asked, as far as edge / dist ask for them.
+    labels=True needs "label0" ("label1" for frame 1) among extras=, frame 1 needs "flow1" there, and labels=False needs an
+    explicit min_step > 0: without labels a min_step of 0 marks every pixel whose flow differs from a neighbour's at all."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
-                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, **kw):
+                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, **kw):
         import torch
+        self.boundaries = self._boundary_options(boundaries, extras)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -2049,12 +2185,56 @@ class FlowLoader:
                       alloc_pack(p.batch_size, ph, pw, image_dtype=self.pack.get("image_dtype"), flow_dtype=self.pack.get("flow_dtype"),
                                  layout=self.pack.get("layout", PACK_NCHW), concat=bool(self.pack.get("concat", False)), zero=False)
                       for _ in range(self.prefetch)]
+        # (not filled: the call writes every element; see the crop's buffers above)
+        self.ebufs = [None if self.boundaries is None else
+                      alloc_boundaries(p.batch_size, ph, pw, frames=self.boundaries["frames"], edge=self.boundaries["edge"],
+                                       dist=self.boundaries["dist"], zero=False) for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
         for j in range(self.prefetch - 1):      # fill the ring
             self._enqueue(j)
         self.head = self.prefetch - 1
+
+    @staticmethod
+    def _boundary_options(boundaries, extras):
+        """boundaries= with its defaults filled in, or None; raises for what the loader cannot serve"""
+        if boundaries is None:
+            return None
+        o = dict(radius=10, min_step=None, labels=None, frames=(0,), edge=True, dist=True)
+        unknown = set(boundaries) - set(o)
+        if unknown:
+            raise ValueError("unknown boundaries option(s) %s" % sorted(unknown))
+        o.update(boundaries)
+        o["frames"] = tuple(sorted(set(int(f) for f in o["frames"])))
+        if not o["frames"] or any(f not in (0, 1) for f in o["frames"]) or not (o["edge"] or o["dist"]):
+            raise ValueError("boundaries= needs frames of 0 and / or 1 and at least one of edge and dist")
+        extras = tuple(extras or ())
+        if 1 in o["frames"] and "flow1" not in extras:
+            raise ValueError("boundaries= of frame 1 reads flow1: extras= must contain \"flow1\"")
+        have = all("label%d" % f in extras for f in o["frames"])
+        if o["labels"] and not have:
+            raise ValueError("boundaries= with labels=True needs the label planes of its frames: extras= must contain %s"
+                             % " and ".join("\"label%d\"" % f for f in o["frames"]))
+        if o["labels"] is None:
+            o["labels"] = have
+        if not o["labels"] and not (o["min_step"] is not None and float(o["min_step"]) > 0.0):
+            raise ValueError("boundaries= without labels needs an explicit min_step > 0")
+        o["min_step"] = float(o["min_step"] or 0.0)
+        return o
+
+    def _enqueue_boundaries(self, j, planes, s, size):
+        """The boundary planes of set j from the flows and labels among `planes` (by name) on stream s, when the loader makes them."""
+        if self.boundaries is not None:
+            o, out = self.boundaries, self.ebufs[j]
+            args = {}
+            for f in o["frames"]:
+                tag = "1" if f else ""
+                args["flow" + tag] = planes["flow" + tag]
+                args["edge" + tag], args["dist2_1" if f else "dist2"] = out.get("edge%d" % f), out.get("dist%d" % f)
+                args["label" + tag] = planes["label%d" % f] if o["labels"] else None
+            args.setdefault("flow", None)
+            self.gen.boundaries(radius=o["radius"], min_step=o["min_step"], labels=o["labels"], stream=s, size=size, **args)
 
     def _enqueue(self, j):
         import torch
@@ -2070,6 +2250,7 @@ class FlowLoader:
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
+        self._enqueue_boundaries(j, dict(self.xbufs[j] or {}, flow=self.bufs[j][2]), s, None)
         self._enqueue_pack(j, self.bufs[j], s, None)
         self.ready[j].record(chain)
 
@@ -2087,6 +2268,7 @@ class FlowLoader:
                           vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
         self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
         self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
+        self._enqueue_boundaries(j, out, s, self.crop)
         self._enqueue_pack(j, (out["image0"], out["image1"], out["flow"]), s, self.crop)
         self.ready[j].record(chain)
 
@@ -2114,7 +2296,7 @@ class FlowLoader:
             self.gen.flow_pyramid(flow, self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s, size=size)
 
     def _add_reductions(self, more, j):
-        """the statistics and the pyramid of set j into the batch's dict"""
+        """the statistics, the pyramid and the boundary planes of set j into the batch's dict"""
         if self.sbufs[j] is not None:
             more["flow_stats"] = self.sbufs[j]
         if self.pbufs[j] is not None:
@@ -2122,6 +2304,8 @@ class FlowLoader:
                 more["flow_pyramid"], more["flow_pyramid_weights"] = self.pbufs[j]
             else:
                 more["flow_pyramid"] = self.pbufs[j]
+        if self.ebufs[j] is not None:
+            more.update(self.ebufs[j])
 
     @property
     def consumed(self):
@@ -2161,7 +2345,7 @@ class FlowLoader:
                 more["photo"] = self.rbufs[j]
             self._add_reductions(more, j)
             return (out["image0"], out["image1"], out["flow"], more)
-        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None:
+        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None or self.ebufs[j] is not None:
             more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
             if self.rbufs[j] is not None:
                 more["photo"] = self.rbufs[j]

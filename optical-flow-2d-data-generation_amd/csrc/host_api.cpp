@@ -5,6 +5,7 @@
 #include <cstring>
 #include <exception>
 #include <memory>
+#include <vector>
 
 #include "host_input.h"
 #include "realize.h"
@@ -599,6 +600,58 @@ int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, in
             std::memcpy(dst + pack_dst_index(j->layout, Cd, i, cd, y, x, width, height) * des, &bits, des);
           }
       }
+  }
+  return OFDG_OK;
+}
+
+// ofdg_boundaries on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The pair rule and the argument
+// rules are the functions the kernel runs (csrc/ofdg_device.h); the distance is the minimum over the offsets of the disc.
+int ofdg_host_boundaries(const struct ofdg_boundary_job* job, int n_samples, int width, int height) {
+  const DevBoundaryJob* const j = reinterpret_cast<const DevBoundaryJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = boundary_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_boundaries: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const bool labels = j->flags & OFDG_BND_LABELS;
+  const float t2 = boundary_threshold(j->min_step);
+  std::vector<uint8_t> edge(plane);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->flow[f]) continue;
+    const FlowPlane flow{j->flow[f], j->flow_fmt};
+    const int R = j->dist2[f] ? j->radius : 0;
+    for (int i = 0; i < n_samples; ++i) {
+      const size_t fu = (size_t)i * 2 * plane, fv = fu + plane;
+      const uint8_t* const lab = labels ? j->label[f] + (size_t)i * plane : nullptr;
+      auto step = [&](size_t p, size_t q) {
+        if (lab && lab[p] == lab[q]) return false;
+        return boundary_step(flow.at(fu + p), flow.at(fv + p), flow.at(fu + q), flow.at(fv + q), t2);
+      };
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          const size_t p = (size_t)y * width + x;
+          edge[p] = (x > 0 && step(p, p - 1)) || (x + 1 < width && step(p, p + 1)) || (y > 0 && step(p, p - width)) ||
+                    (y + 1 < height && step(p, p + width)) ? 1 : 0;
+        }
+      if (j->edge[f]) std::memcpy(j->edge[f] + (size_t)i * plane, edge.data(), plane);
+      if (!j->dist2[f]) continue;
+      uint8_t* const out = j->dist2[f] + (size_t)i * plane;
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          // every offset of the disc, the near ones first: ay = |dy|, ax = |dx|, both signs of each
+          int best = OFDG_BND_FAR;
+          for (int ay = 0; ay <= R && ay * ay < best; ++ay)
+            for (int ax = 0; ax * ax + ay * ay <= R * R && ax * ax + ay * ay < best; ++ax)
+              for (int s = 0; s < 4; ++s) {
+                const int px = x + ((s & 1) ? -ax : ax), py = y + ((s & 2) ? -ay : ay);
+                if (px < 0 || px >= width || py < 0 || py >= height) continue;
+                if (edge[(size_t)py * width + px]) best = ax * ax + ay * ay;
+              }
+          out[(size_t)y * width + x] = (uint8_t)best;
+        }
+    }
   }
   return OFDG_OK;
 }

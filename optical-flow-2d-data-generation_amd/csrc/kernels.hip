@@ -4162,4 +4162,162 @@ __global__ __launch_bounds__(kPackThreads) void pack_kernel(const DevPackJob job
   }
 }
 
+// ---- Motion boundaries (ofdg_boundaries, include/ofdg.h) -------------------------------------------------------------------
+// A workgroup owns a kBndTileW x kBndTileH tile of one frame of one sample; blockIdx.x counts the tiles, blockIdx.y the
+// samples, blockIdx.z the frames that are present.  Its REGION is the tile and a halo of R = radius pixels (0 when the frame
+// has no dist2 plane), one more row above and one more column to the left for the steps that reach into it; what lies outside
+// the plane holds no step, so nothing wraps.  Four passes, a workgroup barrier between them:
+//   1. steps.   A wave takes 64 consecutive columns of a region row at a time: a lane decides whether its pixel and the one to
+//               its right, and its pixel and the one below, are a step (boundary_step, the labels compared first: where they
+//               agree the flow is not read), and __ballot makes the two 64-bit words of the run.  A region row is kBndWords words.
+//   2. edge.    edge word = right | right << 1 (the carry from the word before) | down | down of the row above.
+//   3. across.  For four tile columns of a region row at a time: the row's words shifted into a 31-bit window centred on the
+//               column, the nearest set bit on either side by count-leading / count-trailing zeros, g^2 (or 255: none within
+//               R) as a byte in LDS.
+//   4. down.    A lane owns 8 consecutive columns of kBndOwn vertically adjacent rows: dist2 = min over |dy| <= R of dy^2 +
+//               g^2(x, y + dy), kept where <= R^2; edge is the window's centre bit.  8 bytes per lane and plane, non-temporal.
+// Element loads at checked indices only; no atomics, no scratch.  LDS: 12 KiB at 128 x 32.
+constexpr int kBndThreads = 256;
+#ifndef OFDG_BND_TILE_W
+#define OFDG_BND_TILE_W 128
+#endif
+#ifndef OFDG_BND_TILE_H
+#define OFDG_BND_TILE_H 32
+#endif
+constexpr int kBndTileW = OFDG_BND_TILE_W, kBndTileH = OFDG_BND_TILE_H;  // (measured against 64 x 32 and 128 x 64: CHANGELOG)
+constexpr int kBndPad = kBndMaxRadius + 1;                             // region columns left of the tile
+constexpr int kBndWords = (kBndTileW + 2 * kBndPad + 63) / 64;         // 64-column words of a region row
+constexpr int kBndRows = kBndTileH + 2 * kBndMaxRadius;                // region rows at the largest radius
+constexpr int kBndOwn = kBndTileW * kBndTileH / (8 * kBndThreads);     // rows of 8 columns a lane owns in pass 4
+static_assert(kBndTileW % 64 == 0 && kBndOwn >= 1 && kBndOwn * 8 * kBndThreads == kBndTileW * kBndTileH && kBndThreads % (kBndTileW / 8) == 0 &&
+              kBndTileW + kBndPad + kBndMaxRadius <= 64 * kBndWords, "a lane owns whole runs of 8 columns; the region fits its words");
+typedef uint32_t bnd_u32x2 __attribute__((ext_vector_type(2)));
+template <bool kHalf>
+__device__ __forceinline__ float bnd_flow(const uint8_t* __restrict__ flow, size_t at) {
+  if constexpr (kHalf) return (float)reinterpret_cast<const _Float16*>(flow)[at];
+  else return reinterpret_cast<const float*>(flow)[at];
+}
+// 8 bits -> 8 bytes of 1 / 0, the lowest bit in the lowest byte
+__device__ __forceinline__ bnd_u32x2 bnd_spread(uint32_t bits) {
+  return bnd_u32x2{((bits & 15u) * 0x00204081u) & 0x01010101u, (((bits >> 4) & 15u) * 0x00204081u) & 0x01010101u};
+}
+template <bool kHalf, bool kLabels>
+__global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundaryJob job, int n, int W, int H, uint32_t tiles_x) {
+  __shared__ unsigned long long s_right[kBndRows + 1][kBndWords], s_down[kBndRows + 1][kBndWords];  // row 0: the row above the region
+  __shared__ unsigned long long s_edge[kBndRows][kBndWords];
+  __shared__ uint32_t s_g2[kBndRows][kBndTileW / 4];
+  const int f = (blockIdx.z != 0u || !job.flow[0]) ? 1 : 0;
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.flow[1] : job.flow[0]);
+  const uint8_t* const s_lab = f ? job.label[1] : job.label[0];
+  uint8_t* const d_edge = f ? job.edge[1] : job.edge[0];
+  uint8_t* const d_dist = f ? job.dist2[1] : job.dist2[0];
+  const int R = d_dist ? job.radius : 0;
+  const float t2 = boundary_threshold(job.min_step);
+  const int x0 = (int)(blockIdx.x % tiles_x) * kBndTileW, y0 = (int)(blockIdx.x / tiles_x) * kBndTileH;
+  const int lane = (int)(threadIdx.x & 63u), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int rows = kBndTileH + 2 * R;  // region rows: row e is row y0 - R + e of the plane
+  const int x_lo = max(x0 - R - 1, 0), x_hi = min(x0 + kBndTileW + R, W);  // columns whose steps the tile can see
+  const size_t plane = (size_t)W * H;
+  constexpr int kPerRow = kBndTileW / 8;
+  const int col8 = (int)threadIdx.x % kPerRow, cy0 = (int)threadIdx.x / kPerRow * kBndOwn;  // pass 4: the lane's columns and first row
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const uint8_t* const fl = s_flow + (size_t)i * 2 * plane * (kHalf ? 2 : 4);
+    const uint8_t* const lab = s_lab + (size_t)i * plane;  // (read with kLabels only)
+    for (int unit = wave; unit < (rows + 1) * kBndWords; unit += kBndThreads / 64) {
+      const int ry = unit / kBndWords, w = unit - ry * kBndWords;
+      const int y = y0 - R - 1 + ry, x = x0 - kBndPad + 64 * w + lane;
+      unsigned long long right = 0ull, down = 0ull;
+      if (y >= 0 && y < H) {
+        const bool in = x >= x_lo && x < x_hi;
+        bool want_r = in && x + 1 < W, want_d = in && y + 1 < H, step_r = false, step_d = false;
+        const size_t p = (size_t)y * W + (size_t)(in ? x : 0);
+        if constexpr (kLabels) {
+          if (in) {
+            const uint8_t l = lab[p];
+            want_r = want_r && lab[p + 1] != l;
+            want_d = want_d && lab[p + W] != l;
+          }
+        }
+        if (want_r || want_d) {
+          const float u = bnd_flow<kHalf>(fl, p), v = bnd_flow<kHalf>(fl, plane + p);
+          if (want_r) step_r = boundary_step(u, v, bnd_flow<kHalf>(fl, p + 1), bnd_flow<kHalf>(fl, plane + p + 1), t2);
+          if (want_d) step_d = boundary_step(u, v, bnd_flow<kHalf>(fl, p + W), bnd_flow<kHalf>(fl, plane + p + W), t2);
+        }
+        right = __ballot(step_r);
+        down = __ballot(step_d);
+      }
+      if (lane == 0) { s_right[ry][w] = right; s_down[ry][w] = down; }
+    }
+    __syncthreads();
+    for (int t = (int)threadIdx.x; t < rows * kBndWords; t += kBndThreads) {
+      const int e = t / kBndWords, w = t - e * kBndWords;
+      const unsigned long long r = s_right[e + 1][w];
+      s_edge[e][w] = r | (r << 1) | (w ? s_right[e + 1][w - 1] >> 63 : 0ull) | s_down[e + 1][w] | s_down[e][w];
+    }
+    __syncthreads();
+    if (d_dist) {
+      for (int t = (int)threadIdx.x; t < rows * (kBndTileW / 4); t += kBndThreads) {
+        const int e = t / (kBndTileW / 4), c4 = t - e * (kBndTileW / 4);
+        const int first = 4 * c4 + kBndPad - kBndMaxRadius;  // the window of the first of the four columns starts at this bit
+        const int w0 = first >> 6, sh = first & 63;
+        unsigned long long chunk = s_edge[e][w0] >> sh;
+        if (sh != 0 && w0 + 1 < kBndWords) chunk |= s_edge[e][w0 + 1] << (64 - sh);
+        uint32_t g2 = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const uint32_t win = (uint32_t)(chunk >> b) & 0x7FFFFFFFu;  // bit 15: the column itself
+          const uint32_t hi = win >> kBndMaxRadius, lo = win & 0x7FFFu;
+          const int dr = hi ? __builtin_ctz(hi) : 64, dl = lo ? __builtin_clz(lo) - 16 : 64;
+          const int g = min(dr, dl);
+          g2 |= (g <= R ? (uint32_t)(g * g) : 255u) << (8 * b);
+        }
+        s_g2[e][c4] = g2;
+      }
+      __syncthreads();
+    }
+    const int X = x0 + 8 * col8;
+    if (X < W) {  // (W is a multiple of 8: the lane's 8 columns exist or none does)
+      if (d_dist) {
+        uint32_t best[kBndOwn][8];
+#pragma unroll
+        for (int k = 0; k < kBndOwn; ++k)
+#pragma unroll
+          for (int b = 0; b < 8; ++b) best[k][b] = 255u;
+        for (int r = 0; r < kBndOwn + 2 * R; ++r) {
+          const uint2 g = *reinterpret_cast<const uint2*>(&s_g2[cy0 + r][2 * col8]);
+#pragma unroll
+          for (int k = 0; k < kBndOwn; ++k) {
+            const int dy = r - R - k;  // region row cy0 + r against the lane's row cy0 + k
+            const uint32_t dy2 = (dy < -R || dy > R) ? 255u : (uint32_t)(dy * dy);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) best[k][b] = min(best[k][b], (((b < 4 ? g.x : g.y) >> (8 * (b & 3))) & 255u) + dy2);
+          }
+        }
+        const uint32_t r2 = (uint32_t)(R * R);
+#pragma unroll
+        for (int k = 0; k < kBndOwn; ++k) {
+          const int Y = y0 + cy0 + k;
+          if (Y >= H) break;
+          uint32_t o[8];
+#pragma unroll
+          for (int b = 0; b < 8; ++b) o[b] = best[k][b] <= r2 ? best[k][b] : 255u;
+          __builtin_nontemporal_store(bnd_u32x2{o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24), o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24)},
+                                      reinterpret_cast<bnd_u32x2*>(d_dist + (size_t)i * plane + (size_t)Y * W + X));
+        }
+      }
+      if (d_edge) {
+        const int bit = 8 * col8 + kBndPad;
+#pragma unroll
+        for (int k = 0; k < kBndOwn; ++k) {
+          const int Y = y0 + cy0 + k;
+          if (Y >= H) break;
+          const uint32_t bits = (uint32_t)(s_edge[cy0 + k + R][bit >> 6] >> (bit & 63)) & 255u;
+          __builtin_nontemporal_store(bnd_spread(bits), reinterpret_cast<bnd_u32x2*>(d_edge + (size_t)i * plane + (size_t)Y * W + X));
+        }
+      }
+    }
+    __syncthreads();  // (the words are written again for the next sample)
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack
+// ofdg_spatial, ofdg_pack, ofdg_boundaries
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -291,7 +291,7 @@ struct PostOp {
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
-// 8 spatial_kernel, 24 pack_kernel.
+// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1797,6 +1797,36 @@ int ofdg_pack(ofdg_ctx* c, const struct ofdg_pack_job* job, int n_samples, void*
                              dim3(kPackThreads), 0, st, *j, n_samples, W, H, per_group);
         });
       });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Motion boundaries of caller-given flows: one kernel on `stream` for both frames, both outputs and every sample.
+int ofdg_boundaries(ofdg_ctx* c, const struct ofdg_boundary_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_boundaries"};
+  const DevBoundaryJob* const j = reinterpret_cast<const DevBoundaryJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = boundary_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = boundary_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const bool labels = j->flags & OFDG_BND_LABELS;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->flow[f]) continue;
+    OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
+    OFDG_TRY(op.aligned(f ? "label[1]" : "label[0]", j->label[f], OFDG_FMT_U8, /*say_fmt=*/false));
+    if ((uintptr_t)j->edge[f] & 15) return op.fail(std::string(f ? "edge[1]" : "edge[0]") + " must be 16-byte aligned");
+    if ((uintptr_t)j->dist2[f] & 15) return op.fail(std::string(f ? "dist2[1]" : "dist2[0]") + " must be 16-byte aligned");
+  }
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t tiles_x = ((uint32_t)W + kBndTileW - 1) / kBndTileW, tiles_y = ((uint32_t)H + kBndTileH - 1) / kBndTileH;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), (j->flow[0] ? 1u : 0u) + (j->flow[1] ? 1u : 0u));
+  with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
+    with_bool(labels, [&](auto with_labels) {
+      hipLaunchKernelGGL((boundary_kernel<decltype(half)::value, decltype(with_labels)::value>), g, dim3(kBndThreads), 0, st, *j, n_samples, W, H, tiles_x);
     });
   });
   HIP_OK(c, hipGetLastError());

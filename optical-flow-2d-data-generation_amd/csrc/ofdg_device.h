@@ -876,6 +876,78 @@ inline const char* pack_arg_error(const DevPackJob* j, int n, int width, int hei
   return nullptr;
 }
 
+// ---- Motion boundaries (ofdg_boundaries, include/ofdg.h) -------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the pair rule and the argument
+// rules.  Compiled without contraction, so the two squares and their sum are three roundings.
+constexpr int kBndMaxRadius = 15;  // OFDG_BND_MAX_RADIUS
+struct DevBoundaryJob {            // struct ofdg_boundary_job, field for field
+  const void* flow[2];
+  const uint8_t* label[2];
+  uint8_t* edge[2];
+  uint8_t* dist2[2];
+  int32_t width, height, flow_fmt, flags, radius;
+  float min_step;
+  int32_t reserved[2];
+};
+static_assert(sizeof(struct ofdg_boundary_job) == sizeof(DevBoundaryJob) && sizeof(DevBoundaryJob) == 96 && OFDG_BND_MAX_RADIUS == kBndMaxRadius &&
+              offsetof(struct ofdg_boundary_job, label) == offsetof(DevBoundaryJob, label) && offsetof(struct ofdg_boundary_job, edge) == offsetof(DevBoundaryJob, edge) &&
+              offsetof(struct ofdg_boundary_job, dist2) == offsetof(DevBoundaryJob, dist2) && offsetof(struct ofdg_boundary_job, width) == offsetof(DevBoundaryJob, width) &&
+              offsetof(DevBoundaryJob, width) == 64 && offsetof(struct ofdg_boundary_job, flow_fmt) == offsetof(DevBoundaryJob, flow_fmt) &&
+              offsetof(struct ofdg_boundary_job, flags) == offsetof(DevBoundaryJob, flags) && offsetof(struct ofdg_boundary_job, radius) == offsetof(DevBoundaryJob, radius) &&
+              offsetof(struct ofdg_boundary_job, min_step) == offsetof(DevBoundaryJob, min_step) && offsetof(DevBoundaryJob, min_step) == 84 &&
+              offsetof(struct ofdg_boundary_job, reserved) == offsetof(DevBoundaryJob, reserved) && OFDG_BND_LABELS == 1 && OFDG_BND_FAR == 255,
+              "struct ofdg_boundary_job: 96 bytes, the layout the kernel takes; boundary_kernel spells the codes out");
+// Are the 4-neighbours p and q a step?  (u, v) of each widened to float32, t2 = fl32(min_step * min_step); with kLabels the
+// caller has compared the labels.  A NaN d2 compares false.
+OFDG_HD_FN bool boundary_step(float up, float vp, float uq, float vq, float t2) {
+  const float du = up - uq, dv = vp - vq;
+  const float a = du * du, b = dv * dv;
+  const float d2 = a + b;
+  return d2 > t2;
+}
+OFDG_HD_FN float boundary_threshold(float min_step) { return min_step * min_step; }
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* boundary_plane_size(const DevBoundaryJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The argument rules ofdg_boundaries and ofdg_host_boundaries share: the first rule broken, or nullptr.  width, height: what
+// boundary_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* boundary_arg_error(const DevBoundaryJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (const char* why = batch_plane_error(n, width, height)) return why;
+  if ((unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "width * height must be below 2^31";
+  if (j->flags & ~OFDG_BND_LABELS) return "flags holds unknown bits";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (!j->flow[0] && !j->flow[1]) return "flow: no frame is present";
+  for (int f = 0; f < 2; ++f) {
+    if (!j->flow[f] && j->edge[f]) return "edge: an output of a frame without its flow";
+    if (!j->flow[f] && j->dist2[f]) return "dist2: an output of a frame without its flow";
+    if (j->flow[f] && !j->edge[f] && !j->dist2[f]) return "edge, dist2: a frame has a flow and no output";
+    if (j->flow[f] && (j->flags & OFDG_BND_LABELS) && !j->label[f]) return "label: OFDG_BND_LABELS needs the label plane of every frame present";
+  }
+  if (!(j->min_step >= 0.0f && j->min_step <= 3.4028234663852886e38f)) return "min_step must be finite and not negative";
+  if ((j->dist2[0] || j->dist2[1]) && (j->radius < 1 || j->radius > kBndMaxRadius)) return "radius must lie in 1..15";
+  // an output may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[8];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->flow[f]) continue;
+    r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
+    if (j->label[f]) r[nr++] = Range{(uintptr_t)j->label[f], (uintptr_t)j->label[f] + (uintptr_t)plane, false};
+    if (j->edge[f]) r[nr++] = Range{(uintptr_t)j->edge[f], (uintptr_t)j->edge[f] + (uintptr_t)plane, true};
+    if (j->dist2[f]) r[nr++] = Range{(uintptr_t)j->dist2[f], (uintptr_t)j->dist2[f] + (uintptr_t)plane, true};
+  }
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "edge, dist2: an output range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
