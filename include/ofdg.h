@@ -896,6 +896,114 @@ int ofdg_boundaries(ofdg_ctx* ctx, const struct ofdg_boundary_job* job, int n_sa
  * size; the job's own must be 0, 0 or the same.  Errors as above through ofdg_host_last_error. */
 int ofdg_host_boundaries(const struct ofdg_boundary_job* job, int n_samples, int width, int height);
 
+/*
+ * Occluder rectangles ("eraser" of the RAFT-style recipes): up to OFDG_ERASE_MAX_RECTS rectangles of image0 and / or image1 of
+ * every sample are painted over IN PLACE - with the frame's mean colour, a constant or noise - and, with OFDG_ERASE_OCC, the
+ * occlusion maps are extended by what the rectangles hide.  The record is a pure function of (seed, global sample index), the
+ * noise of (seed, global sample index, frame, element), so a resumed or sharded run makes the same pixels.  Everything below
+ * is exact: the kernels, ofdg_host_erase and the numpy restatement of the tests give the same bytes.  fl32(.) marks a float32
+ * rounding (no contraction).
+ *
+ * Planes, all written in place: image[f] is image f as [n,3,height,width] of image_fmt (OFDG_FMT_F32 or OFDG_FMT_U8; the
+ * float32 frames hold byte values, see ofdg_photo); occ[f] the occlusion map of frame f, [n,1,height,width] of occ_fmt (F32 or
+ * U8), or NULL; flow[0] the forward flow, flow[1] flow1, [n,2,height,width] of flow_fmt (F32 or F16), read only, or NULL.
+ * width = height = 0: the context's frame; otherwise any size the context's rule allows (the planes ofdg_crop / ofdg_spatial
+ * wrote, for one).  flags: OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1, the frames that may hold rectangles - at least one, and
+ * image[f] of each must be given; an image[f] of a frame that is not flagged is not looked at -, and OFDG_ERASE_OCC.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_erase_draw(seed, first_index + i, width, height, the job).  Either
+ * way it is sanitised before use, and the sanitised record, with the fill bytes, is what recs_out[i] receives.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, {seed ^ (uint32)(g >> 32) *
+ *    0x9E3779B9, (uint32)g}, blocks j = 0..4 at the counters {j, 0, 0x0c74, 0} (taken: 0x0fd9 the sampler, 0x0c70 crop, 0x0c71 and
+ *    0x0c72 photo, 0x0c73 spatial; 0x0c75 is the noise fill below).  u(w) = (float)(w >> 8) * 2^-24 as in ofdg_photo;
+ *    pick(w, lo, hi) = lo + (int)(((uint64)w * (uint32)(hi - lo + 1)) >> 32), the multiply-shift of the crop's draw.
+ *      block 0:  erased = u(.x) < prob;  count = pick(.y, min_rects, max_rects);  frame of rectangle k = bit k of .z when both
+ *                frames are flagged, else the flagged frame.
+ *      block k + 1 (k = 0..3):  w = pick(.x, min_size, max_size)  h = pick(.y, min_size, max_size)
+ *                x0 = pick(.z, 0, width - 1)  y0 = pick(.w, 0, height - 1)  - the top-left corner anywhere in the frame, the
+ *                rectangle then clipped by step 2, as the RAFT recipe places it.  No rejection loop.
+ *    Not erased: count 0.  Rectangles k >= count, fill and reserved are 0.
+ * 2. Sanitise.  count = count < 0 ? 0 : count > 4 ? 4 : count.  For k < count in order: frame &= 1; the rectangle is dropped
+ *    when its frame is not flagged, when w < 1 or h < 1, or when the clipped rectangle [max(x0, 0), min(x0 + w, width)) x
+ *    [max(y0, 0), min(y0 + h, height)) (the sums in 64 bits) is empty; else it is kept, clipped.  The kept rectangles move to
+ *    the front in their order, count becomes their number, every other rectangle, fill and reserved become 0.  No record makes
+ *    a kernel touch a byte outside a plane.
+ * 3. Fill byte of frame f, channel c (B, G, R), for every frame f that has a rectangle after step 2 (else fill[f][c] = 0):
+ *      OFDG_ERASE_MEAN   the mean of that channel of the sample's frame BEFORE any rectangle is painted, in integers:
+ *                        q = 256 * b for a uint8 element b; for a float32 element v:  v = v > 0 ? v : 0 (a NaN becomes 0),
+ *                        v = v < 255 ? v : 255,  q = (uint32)rintf(fl32(v * 256.0f)) (ties to even).  S = the sum of q over
+ *                        the P = width * height elements (64 bits),  mean_q8 = (2 S + P) / (2 P) by integer division,
+ *                        m = (mean_q8 + 128) >> 8.  The same frame in either format gets the same m.
+ *      OFDG_ERASE_CONST  m = color[c], each in 0..255.
+ *      OFDG_ERASE_NOISE  fill[f][c] = 0; the element e = c * P + y * width + x of the frame gets the top byte (>> 24) of
+ *                        word (e & 3) of the Philox block under the sample's key at the counter {e >> 2, f, 0x0c75, 0}.
+ *    Every element inside a rectangle of frame f becomes m (the noise byte): a uint8 frame stores the byte, a float32 frame
+ *    (float)byte.  A painted value does not depend on the rectangle, so overlapping rectangles need no order.  Elements
+ *    outside keep their bits.
+ * 4. Occlusion, with OFDG_ERASE_OCC, for each occ[f] given: element (y, x) becomes 1.0f / 1 when it lies inside a rectangle of
+ *    frame f, or - when frame 1 - f is flagged - when its target lies inside a rectangle of frame 1 - f: with (u, v) the
+ *    element's flow[f] widened to float32, tx = floorf(fl32(fl32((float)x + u) + 0.5f)), ty likewise from y and v (the
+ *    formula of OFDG_CROP_OCC_WINDOW), inside when x0 <= tx <= x0 + w - 1 and y0 <= ty <= y0 + h - 1, compared as float32 (a
+ *    NaN is in no rectangle).  All other elements keep their bits.  When frame 1 - f is flagged, occ[f] needs flow[f].
+ *    Without the flag occ and flow are not looked at; nor is a flow[f] that no given map needs.
+ *
+ * work: DEVICE memory of n_samples * OFDG_ERASE_WORK_BYTES, 16-byte aligned, required for OFDG_ERASE_MEAN only (else not looked
+ * at); contents unspecified before and after.  Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN
+ * as in ofdg_flow_stats.  At most one clearing of `work` and two kernels per call, integer atomics only.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, a size that
+ * breaks the rule above, 3 * width * height of 2^31 and more, another format code (occ_fmt and flow_fmt count with
+ * OFDG_ERASE_OCC only), unknown flag bits, non-zero reserved, no frame flag, a flagged frame without its image, another fill
+ * code, a colour outside 0..255 (OFDG_ERASE_CONST), prob outside [0, 1] or NaN, min_rects <= max_rects outside 0..4, 1 <=
+ * min_size <= max_size <= 32767 broken (the ranges count when recs is NULL), OFDG_ERASE_OCC with no map or with a map
+ * that lacks its flow, work NULL under OFDG_ERASE_MEAN, a misaligned pointer (images, maps and flows as the render calls ask:
+ * 16-byte float32, 8-byte binary16, 4-byte uint8; work and both record arrays 16-byte), a written range (images, maps, work,
+ * recs_out) that overlaps any other range of the job, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: textured occluders from the pool, shapes other than rectangles, a copying form, label planes, the object table
+ * and boundary planes (they stay those of the un-erased sample), mode 9 beyond painting (it has no maps to mark).
+ */
+#define OFDG_ERASE_MAX_RECTS 4
+#define OFDG_ERASE_FRAME0 1          /* job flag: frame 0 may hold rectangles */
+#define OFDG_ERASE_FRAME1 2          /* job flag: frame 1 may hold rectangles */
+#define OFDG_ERASE_OCC    4          /* job flag: step 4 */
+#define OFDG_ERASE_MEAN  0           /* job->fill */
+#define OFDG_ERASE_CONST 1
+#define OFDG_ERASE_NOISE 2
+#define OFDG_ERASE_WORK_BYTES 64     /* of job->work per sample */
+typedef struct ofdg_erase_rect { int32_t x0, y0, w, h, frame; } ofdg_erase_rect;
+typedef struct ofdg_erase_rec {      /* 96 bytes */
+  int32_t count;                     /* 0..OFDG_ERASE_MAX_RECTS */
+  ofdg_erase_rect rect[OFDG_ERASE_MAX_RECTS];
+  uint8_t fill[2][3];                /* [frame][B,G,R]: written into recs_out, never read */
+  uint8_t reserved[6];
+} ofdg_erase_rec;
+struct ofdg_erase_job {              /* 152 bytes */
+  void* image[2];                    /* [n,3,height,width] of image_fmt, in place */
+  void* occ[2];                      /* [n,1,height,width] of occ_fmt, in place, or NULL */
+  const void* flow[2];               /* [n,2,height,width] of flow_fmt: flow, flow1, or NULL */
+  const ofdg_erase_rec* recs;        /* DEVICE, n records, or NULL: drawn */
+  ofdg_erase_rec*       recs_out;    /* DEVICE, n records, or NULL */
+  void* work;                        /* DEVICE, n * OFDG_ERASE_WORK_BYTES (OFDG_ERASE_MEAN) */
+  long long first_index; uint32_t seed;
+  int32_t width, height;             /* 0, 0: the context's frame */
+  int32_t image_fmt, occ_fmt, flow_fmt, flags, fill;
+  int32_t min_rects, max_rects, min_size, max_size;   /* ranges of the draw */
+  float   prob;
+  int32_t color[3];                  /* B, G, R of OFDG_ERASE_CONST */
+  int32_t reserved[2];
+};
+int ofdg_erase(ofdg_ctx* ctx, const struct ofdg_erase_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and records in host memory, no alignment asked of any
+ * pointer, work not looked at.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` for a width x height plane (step 1 alone: not sanitised; pure, no GPU).  Of `ranges`
+ * only flags, prob and the four ranges are read.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer, width or
+ * height outside 1..32768, no frame flag, unknown flag bits or a range that breaks the rules above. */
+int ofdg_erase_draw(uint32_t seed, long long index, int width, int height, const struct ofdg_erase_job* ranges, ofdg_erase_rec* out);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

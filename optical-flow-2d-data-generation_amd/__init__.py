@@ -110,6 +110,7 @@ EXPORTS = [
     "ofdg_spatial", "ofdg_host_spatial", "ofdg_spatial_draw",
     "ofdg_pack", "ofdg_host_pack",
     "ofdg_boundaries", "ofdg_host_boundaries",
+    "ofdg_erase", "ofdg_host_erase", "ofdg_erase_draw",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -920,6 +921,175 @@ def host_boundaries(flow=None, label=None, flow1=None, label1=None, radius=10, m
     return out
 
 
+# occluder rectangles (ofdg_erase_rec / struct ofdg_erase_job / ofdg_erase, include/ofdg.h)
+ERASE_MAX_RECTS = 4    # OFDG_ERASE_MAX_RECTS
+ERASE_FRAME0, ERASE_FRAME1, ERASE_OCC = 1, 2, 4      # OFDG_ERASE_FRAME0 / FRAME1 / OCC (job flags)
+ERASE_MEAN, ERASE_CONST, ERASE_NOISE = 0, 1, 2       # OFDG_ERASE_MEAN / CONST / NOISE (job fill)
+ERASE_WORK_BYTES = 64  # OFDG_ERASE_WORK_BYTES
+ERASE_REC_WORDS = 24   # a record as int32 [24]: count, rect[4] = x0 y0 w h frame, then fill[2][3] and the six reserved bytes
+ERASE_RANGES = ("prob", "min_rects", "max_rects", "min_size", "max_size")
+_ERASE_DEFAULTS = dict(prob=0.0, min_rects=0, max_rects=0, min_size=1, max_size=1)
+# A starting point, the eraser transform of the RAFT recipes: every second sample gets one or two rectangles of 50..99 pixels
+# a side; with the defaults of Generator.erase they go into frame 1 and take its mean colour.  Not a tuned recipe.
+ERASE_RAFT = dict(prob=0.5, min_rects=1, max_rects=2, min_size=50, max_size=99)
+
+
+class EraseRect(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("frame", C.c_int32)]
+
+
+class EraseRec(C.Structure):
+    """ofdg_erase_rec: the rectangles of one sample (96 bytes)."""
+    _fields_ = [("count", C.c_int32), ("rect", EraseRect * ERASE_MAX_RECTS), ("fill", (C.c_uint8 * 3) * 2), ("reserved", C.c_uint8 * 6)]
+
+
+class EraseJob(C.Structure):
+    """struct ofdg_erase_job (152 bytes)."""
+    _fields_ = [("image", C.c_void_p * 2), ("occ", C.c_void_p * 2), ("flow", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("work", C.c_void_p), ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("image_fmt", C.c_int32), ("occ_fmt", C.c_int32), ("flow_fmt", C.c_int32), ("flags", C.c_int32), ("fill", C.c_int32),
+                ("min_rects", C.c_int32), ("max_rects", C.c_int32), ("min_size", C.c_int32), ("max_size", C.c_int32), ("prob", C.c_float),
+                ("color", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
+
+
+def _erase_rec_dtype():
+    import numpy as np
+    return np.dtype([("count", "<i4"), ("rect", "<i4", (ERASE_MAX_RECTS, 5)), ("fill", "u1", (2, 3)), ("reserved", "u1", (6,))])
+
+
+def erase_numpy(recs):
+    """Records of Generator.erase / host_erase - a torch tensor or numpy array of int32 [n,24] (or any array of 96 bytes a
+    record) - as a numpy structured array [n] with the fields count, rect [4,5] (x0, y0, w, h, frame), fill [2,3] and reserved [6]."""
+    import numpy as np
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _erase_rec_dtype():
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % 96:
+        raise ValueError("records must be 96 bytes each, got %d bytes" % raw.size)
+    return raw.view(_erase_rec_dtype())
+
+
+def _erase_ranges(job, ranges):
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in ERASE_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(ERASE_RANGES)))
+    for key in ERASE_RANGES:
+        setattr(job, key, (float if key == "prob" else int)(ranges.get(key, _ERASE_DEFAULTS[key])))
+    return job
+
+
+def _erase_frames(frames):
+    frames = tuple(sorted(set(int(f) for f in frames)))
+    if not frames or any(f not in (0, 1) for f in frames):
+        raise ValueError("frames must hold 0 and / or 1, got %r" % (frames,))
+    return frames
+
+
+def erase_format(images, occ=None, flow=None, height=None, width=None):
+    """(n, height, width, image code, occ code, flow code) of the planes of Generator.erase / host_erase: images the pair
+    (image0, image1) of float32 or uint8 [n,3,H,W], either None; occ None or the pair (occ0, occ1) of float32 or uint8 [n,1,H,W],
+    either None; flow None or the pair (flow, flow1) of float32 or float16 [n,2,H,W], either None; one dtype per pair.  Raises
+    ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    occ = (None, None) if occ is None else tuple(occ)
+    flow = (None, None) if flow is None else tuple(flow)
+    if len(images) != 2 or len(occ) != 2 or len(flow) != 2 or all(t is None for t in images):
+        raise ValueError("images, occ and flow must be pairs, images with at least one frame")
+    shape = next(tuple(t.shape) for t in images if t is not None)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 3 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a frame must be [n,3,%s,%s], got %s" % (height or "height", width or "width", shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    codes = []
+    for what, pair, table, ch in (("image", images, _IMAGE_CODES, 3), ("occ", occ, _OCC_CODES, 1), ("flow", flow, _FLOW_CODES, 2)):
+        names = set()
+        for f, t in enumerate(pair):
+            if t is not None:
+                _check_plane("%s[%d]" % (what, f), t, tuple(table), (n, ch, height, width))
+                names.add(_dtype_name(t))
+        if len(names) > 1:
+            raise ValueError("%s must have one dtype for both frames, got %s" % (what, sorted(names)))
+        codes.append(table[names.pop()] if names else FMT_F32)
+    return (n, height, width) + tuple(codes)
+
+
+def _erase_job(images, occ, flow, ptr, codes, size, recs, recs_out, work, first_index, seed, ranges, fill, color, frames, mark_occ):
+    occ = (None, None) if occ is None else tuple(occ)
+    flow = (None, None) if flow is None else tuple(flow)
+    frames = _erase_frames(frames)
+    if mark_occ is None:
+        mark_occ = any(t is not None for t in occ)
+    if mark_occ and all(t is None for t in occ):
+        raise ValueError("mark_occ=True needs an occlusion map")
+    if fill not in (ERASE_MEAN, ERASE_CONST, ERASE_NOISE):
+        raise ValueError("fill must be ERASE_MEAN, ERASE_CONST or ERASE_NOISE, got %r" % (fill,))
+    if len(color) != 3:
+        raise ValueError("color must be (B, G, R), got %r" % (color,))
+    job = _erase_ranges(EraseJob(), ranges)
+    for f in range(2):
+        if f in frames and images[f] is None:
+            raise ValueError("frames holds %d and image%d is None" % (f, f))
+        if images[f] is not None:
+            job.image[f] = ptr(images[f])
+        if mark_occ and occ[f] is not None:
+            job.occ[f] = ptr(occ[f])
+            if (1 - f) in frames:
+                if flow[f] is None:
+                    raise ValueError("occ%d is marked for the rectangles of frame %d through %s: flow[%d] is None" % (f, 1 - f, "flow1" if f else "flow", f))
+                job.flow[f] = ptr(flow[f])
+    job.recs, job.recs_out, job.work = recs, recs_out, work
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.image_fmt, job.occ_fmt, job.flow_fmt = codes
+    job.flags = sum(ERASE_FRAME1 if f else ERASE_FRAME0 for f in frames) | (ERASE_OCC if mark_occ else 0)
+    job.fill = int(fill)
+    for c in range(3):
+        job.color[c] = int(color[c])
+    return job
+
+
+def erase_draw(seed, index, width, height, ranges=None, frames=(1,)):
+    """ofdg_erase_draw (pure, no GPU): the record of global sample `index` under `seed` for a width x height plane, a dict of
+    ERASE_RANGES (a missing one: prob 0, no rectangle, size 1) and the frames that may hold rectangles, before sanitising, as one
+    element of the structured array erase_numpy describes."""
+    job = _erase_ranges(EraseJob(), ranges)
+    job.flags = sum(ERASE_FRAME1 if f else ERASE_FRAME0 for f in _erase_frames(frames))
+    out = EraseRec()
+    _host_check(lib().ofdg_erase_draw(int(seed) & 0xFFFFFFFF, int(index), int(width), int(height), C.byref(job), C.byref(out)))
+    return erase_numpy(bytearray(out))[0]
+
+
+def alloc_erase(n, device="cuda"):
+    """(work, recs) of Generator.erase for n samples: the uint8 [n,64] workspace of the mean fill and the int32 [n,24] records
+    (recs_out).  Not filled: the call clears the first and writes every record."""
+    import torch
+    return (torch.empty((n, ERASE_WORK_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((n, ERASE_REC_WORDS), dtype=torch.int32, device=device))
+
+
+def host_erase(images, occ=None, flow=None, recs=None, first_index=0, seed=0, ranges=None, fill=ERASE_MEAN, color=(0, 0, 0), frames=(1,),
+               mark_occ=None):
+    """ofdg_host_erase (no GPU) on numpy arrays, IN PLACE (they must be C-contiguous): images the pair (image0, image1) of
+    float32 or uint8 [n,3,H,W], occ None or the pair of maps, flow None or the pair (flow, flow1); recs None (drawn from seed,
+    first_index and ranges) or n records (erase_numpy's array, or int32 [n,24]).  mark_occ None: on when a map is given.
+    Returns the records used, after sanitising and with the fill bytes, as erase_numpy's array."""
+    import numpy as np
+    n, height, width, *codes = erase_format(images, occ, flow)
+    for t in tuple(images) + tuple(occ or ()) + tuple(flow or ()):
+        if t is not None and not t.flags["C_CONTIGUOUS"]:
+            raise ValueError("host_erase works in place: every array must be C-contiguous")
+    if recs is not None:
+        recs = erase_numpy(recs).copy()
+        if recs.shape != (n,):
+            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
+    used = np.zeros((n,), _erase_rec_dtype())
+    job = _erase_job(images, occ, flow, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                     None, first_index, seed, ranges, fill, color, frames, mark_occ)
+    _host_check(lib().ofdg_host_erase(C.byref(job), n, width, height))
+    return used
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -1014,6 +1184,9 @@ def lib():
         L.ofdg_host_pack.argtypes = [C.POINTER(PackJob), i32, i32, i32]
         L.ofdg_boundaries.argtypes = [vp, C.POINTER(BoundaryJob), i32, vp]
         L.ofdg_host_boundaries.argtypes = [C.POINTER(BoundaryJob), i32, i32, i32]
+        L.ofdg_erase.argtypes = [vp, C.POINTER(EraseJob), i32, vp]
+        L.ofdg_host_erase.argtypes = [C.POINTER(EraseJob), i32, i32, i32]
+        L.ofdg_erase_draw.argtypes = [C.c_uint32, C.c_longlong, i32, i32, C.POINTER(EraseJob), C.POINTER(EraseRec)]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1439,6 +1612,33 @@ class Generator:
         job = _boundary_job((flow, edge, dist2, label, flow1, edge1, dist2_1, label1), lambda t: _dptr(t).value, code,
                             (0, 0) if size is None else (height, width), radius, min_step, labels)
         self._check(lib().ofdg_boundaries(self.h, C.byref(job), n, C.c_void_p(stream)))
+
+    def erase(self, images, occ=None, flow=None, recs=None, first_index=0, seed=None, ranges=None, fill=ERASE_MEAN, color=(0, 0, 0), frames=(1,),
+              mark_occ=None, recs_out=None, stream=0, size=None, work=None):
+        """Occluder rectangles, in place (ofdg_erase, include/ofdg.h): up to four rectangles of the frames among `frames` of every
+        sample are painted over - fill ERASE_MEAN: the frame's mean colour, ERASE_CONST: color (B, G, R), ERASE_NOISE - and the
+        occlusion maps extended by what they hide.  images: the pair (image0, image1) of float32 or uint8 tensors [n,3,H,W] (a
+        frame not among `frames` may be None); occ: None or the pair (occ0, occ1) of float32 or uint8 maps, either None; flow:
+        None or the pair (flow, flow1), read only - occ0 needs flow when frame 1 is erased, occ1 needs flow1 when frame 0 is.
+        mark_occ: None - on when a map is given.  recs: None - the record of sample i is erase_draw(seed, first_index + i, W, H,
+        ranges, frames) - or an int32 device tensor [n,24], taken as given; either is sanitised.  ranges: a dict of ERASE_RANGES
+        (ERASE_RAFT is a starting point).  seed: default the context's.  recs_out: None or an int32 device tensor [n,24] that
+        receives the records used with the fill bytes (erase_numpy reads it).  work: the uint8 [n,64] workspace ERASE_MEAN needs
+        (alloc_erase makes both); one per call in flight.  stream: the stream the planes were written on, or STREAM_OWN.
+        size=(height, width): planes of that size instead of the context's.  Asynchronous.  Returns images."""
+        images = tuple(images)
+        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        n, _, _, *codes = erase_format(images, occ, flow, height, width)
+        for t in (recs, recs_out):
+            if t is not None and (str(t.dtype) != "torch.int32" or tuple(t.shape) != (n, ERASE_REC_WORDS)):
+                raise ValueError("recs and recs_out must be int32 [%d,%d], got %s %s" % (n, ERASE_REC_WORDS, t.dtype, tuple(t.shape)))
+        if fill == ERASE_MEAN and (work is None or str(work.dtype) != "torch.uint8" or work.numel() < n * ERASE_WORK_BYTES):
+            raise ValueError("fill=ERASE_MEAN needs work=, a uint8 device tensor of at least [%d,%d] (alloc_erase)" % (n, ERASE_WORK_BYTES))
+        job = _erase_job(images, occ, flow, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), _optr(recs),
+                         _optr(recs_out), _optr(work) if fill == ERASE_MEAN else None, first_index, self.params.seed if seed is None else seed,
+                         ranges, fill, color, frames, mark_occ)
+        self._check(lib().ofdg_erase(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return images
 
     def debug_photo_table(self, rec):
         """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
@@ -2105,14 +2305,23 @@ class FlowLoader:
     photometric step does not touch what it reads).  Every batch is then (image0, image1, flow, {...}) and the dict also holds
     "edge0" and "dist0" (uint8 [n,1,H,W]), and "edge1" and "dist1" when frame 1 is asked, as far as edge / dist ask for them.
     labels=True needs "label0" ("label1" for frame 1) among extras=, frame 1 needs "flow1" there, and labels=False needs an
-    explicit min_step > 0: without labels a min_step of 0 marks every pixel whose flow differs from a neighbour's at all."""
+    explicit min_step > 0: without labels a min_step of 0 marks every pixel whose flow differs from a neighbour's at all.
+    erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
+    takes them): occluder rectangles are painted into the frames of every batch in place and the occlusion maps among extras=
+    extended (Generator.erase, enqueued on the same internal stream behind crop / spatial and behind photo, on their planes,
+    and ahead of stats=, pyramid=, boundaries= and pack=, so the reductions see the extended occ0; records drawn from the
+    context's seed and the batch's first global index).  Every batch is then (image0, image1, flow, {...}) and the dict also
+    holds "erase" (int32 [n,24], the records used: erase_numpy).  mark_occ=True needs a map among extras=; marking occ1 for
+    rectangles of frame 0 needs "flow1" there.  Labels, the object table and the boundary planes stay those of the un-erased
+    sample."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
-                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, **kw):
+                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, **kw):
         import torch
         self.boundaries = self._boundary_options(boundaries, extras)
+        self.erase = self._erase_options(erase, extras)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -2189,6 +2398,8 @@ class FlowLoader:
         self.ebufs = [None if self.boundaries is None else
                       alloc_boundaries(p.batch_size, ph, pw, frames=self.boundaries["frames"], edge=self.boundaries["edge"],
                                        dist=self.boundaries["dist"], zero=False) for _ in range(self.prefetch)]
+        # (not filled: the call clears the workspace on its stream and writes every record)
+        self.wbufs = [None if self.erase is None else alloc_erase(p.batch_size) for _ in range(self.prefetch)]
         self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
         self.released = [None] * self.prefetch                               # consumer done with the set
         self.k = 0
@@ -2223,6 +2434,39 @@ class FlowLoader:
         o["min_step"] = float(o["min_step"] or 0.0)
         return o
 
+    @staticmethod
+    def _erase_options(erase, extras):
+        """erase= split into (ranges, the other arguments of Generator.erase), or None; raises for what the loader cannot serve"""
+        if erase is None:
+            return None
+        o = dict(fill=ERASE_MEAN, color=(0, 0, 0), frames=(1,), mark_occ=None)
+        unknown = set(erase) - set(o) - set(ERASE_RANGES)
+        if unknown:
+            raise ValueError("unknown erase option(s) %s" % sorted(unknown))
+        o.update({k: v for k, v in erase.items() if k in o})
+        o["frames"] = _erase_frames(o["frames"])
+        extras = tuple(extras or ())
+        maps = [f for f in range(2) if "occ%d" % f in extras]
+        if o["mark_occ"] and not maps:
+            raise ValueError("erase= with mark_occ=True needs an occlusion map: extras= must contain \"occ0\" or \"occ1\"")
+        if o["mark_occ"] is None:
+            o["mark_occ"] = bool(maps)
+        if o["mark_occ"] and 1 in maps and 0 in o["frames"] and "flow1" not in extras:
+            raise ValueError("erase= marks the rectangles of frame 0 into occ1 through flow1: extras= must contain \"flow1\"")
+        return {k: v for k, v in erase.items() if k in ERASE_RANGES}, o
+
+    def _enqueue_erase(self, j, planes, s, step, size):
+        """The rectangles of batch `step` into the frames and maps among `planes` (by name) of set j on stream s, in place, when
+        the loader makes them."""
+        if self.erase is not None:
+            ranges, o = self.erase
+            p = self.gen.params
+            work, recs = self.wbufs[j]
+            self.gen.erase((planes["image0"], planes["image1"]), occ=(planes.get("occ0"), planes.get("occ1")) if o["mark_occ"] else None,
+                           flow=(planes["flow"], planes.get("flow1")), first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank),
+                           ranges=ranges, fill=o["fill"], color=o["color"], frames=o["frames"], mark_occ=o["mark_occ"], recs_out=recs, stream=s,
+                           size=size, work=work)
+
     def _enqueue_boundaries(self, j, planes, s, size):
         """The boundary planes of set j from the flows and labels among `planes` (by name) on stream s, when the loader makes them."""
         if self.boundaries is not None:
@@ -2242,11 +2486,12 @@ class FlowLoader:
         chain = torch.cuda.ExternalStream(s)
         if self.released[j] is not None:
             chain.wait_event(self.released[j])
-        step = self.gen.step if self.crop is not None or self.photo is not None else 0
+        step = self.gen.step if self.crop is not None or self.photo is not None or self.erase is not None else 0
         self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
         if self.crop is not None:
             return self._enqueue_cropped(j, s, chain, step)
         self._enqueue_photo(j, self.bufs[j][:2], s, step, None)
+        self._enqueue_erase(j, dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {})), s, step, None)
         if self.obufs[j] is not None:
             self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
         self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
@@ -2267,6 +2512,7 @@ class FlowLoader:
             self.gen.crop(planes, out, first_index=first, hflip=self.crop_flips[0],
                           vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
         self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
+        self._enqueue_erase(j, out, s, step, self.crop)
         self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
         self._enqueue_boundaries(j, out, s, self.crop)
         self._enqueue_pack(j, (out["image0"], out["image1"], out["flow"]), s, self.crop)
@@ -2296,7 +2542,7 @@ class FlowLoader:
             self.gen.flow_pyramid(flow, self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s, size=size)
 
     def _add_reductions(self, more, j):
-        """the statistics, the pyramid and the boundary planes of set j into the batch's dict"""
+        """the statistics, the pyramid, the boundary planes and the eraser's records of set j into the batch's dict"""
         if self.sbufs[j] is not None:
             more["flow_stats"] = self.sbufs[j]
         if self.pbufs[j] is not None:
@@ -2306,6 +2552,8 @@ class FlowLoader:
                 more["flow_pyramid"] = self.pbufs[j]
         if self.ebufs[j] is not None:
             more.update(self.ebufs[j])
+        if self.wbufs[j] is not None:
+            more["erase"] = self.wbufs[j][1]
 
     @property
     def consumed(self):
@@ -2345,7 +2593,7 @@ class FlowLoader:
                 more["photo"] = self.rbufs[j]
             self._add_reductions(more, j)
             return (out["image0"], out["image1"], out["flow"], more)
-        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None or self.ebufs[j] is not None:
+        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None or self.ebufs[j] is not None or self.wbufs[j] is not None:
             more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
             if self.rbufs[j] is not None:
                 more["photo"] = self.rbufs[j]

@@ -656,4 +656,93 @@ int ofdg_host_boundaries(const struct ofdg_boundary_job* job, int n_samples, int
   return OFDG_OK;
 }
 
+// ofdg_erase on host arrays (no GPU): the definition of include/ofdg.h element by element.  The draw, the sanitising, the Q8
+// value, the mean byte, the noise byte, the marking rule and the argument rules are the functions the kernels run
+// (csrc/ofdg_device.h); elements are moved with memcpy.
+int ofdg_erase_draw(uint32_t seed, long long index, int width, int height, const struct ofdg_erase_job* ranges, ofdg_erase_rec* out) {
+  const char* why = !ranges || !out ? "ranges or out is NULL" : width < 1 || width > 32768 || height < 1 || height > 32768 ? "width and height must lie in 1..32768" : nullptr;
+  DevEraseJob j;
+  if (!why) {
+    std::memcpy(&j, ranges, sizeof(j));
+    why = erase_ranges_error(j);
+  }
+  if (why) { g_host_error = std::string("ofdg_erase_draw: ") + why; return OFDG_EINVAL; }
+  const DevEraseRec r = erase_draw_rec(seed, (unsigned long long)index, width, height, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, int height) {
+  const DevEraseJob* const j = reinterpret_cast<const DevEraseJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = erase_arg_error(j, n_samples, width, height, /*with_work=*/false);
+  if (why) { g_host_error = std::string("ofdg_host_erase: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int es = fmt_elem_bytes(j->image_fmt);
+  const bool occ = j->flags & OFDG_ERASE_OCC;
+  for (int i = 0; i < n_samples; ++i) {
+    const unsigned long long g = (unsigned long long)(j->first_index + i);
+    DevEraseRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = erase_draw_rec(j->seed, g, width, height, *j);
+    r = erase_sanitise(r, width, height, j->flags);
+    const int frames = erase_frames_of(r);
+    const uint32_t k0 = j->seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+    for (int f = 0; f < 2; ++f) {
+      if (!((frames >> f) & 1)) continue;
+      uint8_t* const img = static_cast<uint8_t*>(j->image[f]) + (size_t)i * 3 * plane * es;
+      for (int c = 0; c < 3; ++c) {  // the fill bytes first: of the frame before any rectangle is painted
+        uint32_t m = 0;
+        if (j->fill == OFDG_ERASE_CONST) m = (uint32_t)j->color[c];
+        else if (j->fill == OFDG_ERASE_MEAN) {
+          unsigned long long S = 0;
+          for (size_t p = 0; p < plane; ++p) {
+            if (es == 1) S += 256u * img[(size_t)c * plane + p];
+            else {
+              float v;
+              std::memcpy(&v, img + 4 * ((size_t)c * plane + p), 4);
+              S += erase_q8(v);
+            }
+          }
+          m = erase_mean_byte(S, plane);
+        }
+        r.fill[f][c] = (uint8_t)m;
+      }
+      for (int k = 0; k < r.count; ++k) {
+        const DevEraseRect& q = r.rect[k];
+        if (q.frame != f) continue;
+        for (int c = 0; c < 3; ++c)
+          for (int y = q.y0; y < q.y0 + q.h; ++y)
+            for (int x = q.x0; x < q.x0 + q.w; ++x) {
+              const uint32_t e = (uint32_t)((size_t)c * plane + (size_t)y * width + x);
+              const uint32_t b = j->fill == OFDG_ERASE_NOISE ? erase_noise_byte(k0, k1, f, e) : r.fill[f][c];
+              const float v = (float)b;
+              if (es == 1) img[e] = (uint8_t)b;
+              else std::memcpy(img + 4 * (size_t)e, &v, 4);
+            }
+      }
+    }
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    for (int f = 0; f < 2 && occ; ++f) {
+      if (!j->occ[f] || !r.count) continue;
+      const bool cross = erase_cross(*j, f);
+      const FlowPlane flow{j->flow[f], j->flow_fmt};
+      const size_t fu = (size_t)i * 2 * plane, fv = fu + plane;
+      uint8_t* const map = static_cast<uint8_t*>(j->occ[f]) + (size_t)i * plane * fmt_elem_bytes(j->occ_fmt);
+      const float one = 1.0f;
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          const size_t p = (size_t)y * width + x;
+          const float u = cross ? flow.at(fu + p) : 0.0f, v = cross ? flow.at(fv + p) : 0.0f;
+          if (!erase_marks(r, f, cross, x, y, u, v)) continue;
+          if (j->occ_fmt == OFDG_FMT_U8) map[p] = 1;
+          else std::memcpy(map + 4 * p, &one, 4);
+        }
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

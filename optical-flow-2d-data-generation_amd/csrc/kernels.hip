@@ -4320,4 +4320,232 @@ __global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundary
   }
 }
 
+// ---- Occluder rectangles (ofdg_erase, include/ofdg.h) ----------------------------------------------------------------------
+// Two launches on the caller's stream, behind the clearing of `work` under OFDG_ERASE_MEAN: erase_mean_kernel adds the Q8 sums
+// of the frames that have a rectangle, erase_apply_kernel paints the rectangles and extends the maps.  In place: the second
+// launch starts after the first has ended - the order of the stream, nothing a workgroup waits for -, so no rectangle of a
+// frame is painted before that frame's sum is complete, and no workgroup waits or spins for another.  Both kernels get the
+// record of a sample the same way: read or drawn, and sanitised, on wave-uniform values (erase_record), so every workgroup of
+// a sample holds the same rectangles in scalar registers.  The functions of the definition are the host twin's
+// (csrc/ofdg_device.h), so the result is the twin's byte for byte.
+constexpr int kEraseThreads = 256;
+constexpr int kEraseMeanPixels = 32768;  // elements of a channel per reduction workgroup, as photo_kernel's: 6 per channel of a 512 x 384 frame
+constexpr int kEraseFillSplit = 4;       // workgroups that share the rows of one (rectangle, plane): 16 rows in flight
+constexpr int kEraseFillBlocks = kEraseMaxRects * 4 * kEraseFillSplit;  // planes of a rectangle: B, G, R and the map of its frame
+constexpr int kEraseOccQuads = 1024;     // quads of a map per workgroup of the pass over flow and map, as flow_stats_kernel's
+static_assert(kEraseMeanPixels % (kEraseThreads * 16) == 0 && (unsigned long long)kEraseMeanPixels * 65280ull < (1ull << 32),
+              "whole rounds of pieces of either kind; a workgroup's Q8 sum fits 32 bits");
+__device__ __forceinline__ DevEraseRec erase_record(const DevEraseJob& job, int i, int W, int H) {
+  DevEraseRec r;
+  if (job.recs) r = job.recs[i];
+  else r = erase_draw_rec(job.seed, (unsigned long long)(job.first_index + i), W, H, job);
+  return erase_sanitise(r, W, H, job.flags);
+}
+// rectangle k of a record for a wave-uniform k, through selects (no indexed access: the record stays in registers), pinned
+// to scalar registers
+// (arguments by value: a conditional between members would select their addresses and pin the record to memory)
+__device__ __forceinline__ int erase_pick4(int k, int v0, int v1, int v2, int v3) { return k == 0 ? v0 : k == 1 ? v1 : k == 2 ? v2 : v3; }
+__device__ __forceinline__ DevEraseRect erase_rect_at(const DevEraseRec& r, int k) {
+#define OFDG_ERASE_PICK(field) __builtin_amdgcn_readfirstlane(erase_pick4(k, r.rect[0].field, r.rect[1].field, r.rect[2].field, r.rect[3].field))
+  return DevEraseRect{OFDG_ERASE_PICK(x0), OFDG_ERASE_PICK(y0), OFDG_ERASE_PICK(w), OFDG_ERASE_PICK(h), OFDG_ERASE_PICK(frame)};
+#undef OFDG_ERASE_PICK
+}
+
+// The mean's reduction.  blockIdx.x counts the kEraseMeanPixels-element blocks of the channels of the flagged frames,
+// blockIdx.y the samples.  A sample whose record has no rectangle in the workgroup's frame is left before any load.  A lane
+// reads pieces - 16 bytes of float32, four 4-byte words of uint8 - as photo_kernel does, sums Q8 values in 32 bits (at most
+// 128 elements of 65280), the wave adds across with __shfl_xor, the workgroup through LDS, and one 64-bit integer atomicAdd
+// per workgroup goes to the sample's sum of (frame, channel) in `work`.  Integers only: no bit depends on arrival order.
+template <bool kU8>
+__global__ __launch_bounds__(kEraseThreads) void erase_mean_kernel(const DevEraseJob job, int n, int W, int H, uint32_t per_channel) {
+  constexpr int kP = kU8 ? 16 : 4;  // elements of a piece
+  __shared__ uint32_t s_part[kEraseThreads / 64];
+  const uint32_t slot = blockIdx.x / per_channel, block = blockIdx.x - slot * per_channel;
+  const int f = (job.flags & 3) == 3 ? (int)(slot / 3u) : (job.flags & 3) == 2 ? 1 : 0, c = (int)(slot % 3u);
+  const void* const src = f ? job.image[1] : job.image[0];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^31: erase_arg_error)
+  const uint32_t first = block * (uint32_t)kEraseMeanPixels;
+  const uint32_t end = first + (uint32_t)kEraseMeanPixels < plane ? first + (uint32_t)kEraseMeanPixels : plane;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const DevEraseRec r = erase_record(job, i, W, H);
+    if (!((erase_frames_of(r) >> f) & 1)) continue;  // (uniform over the workgroup)
+    const size_t chan = ((size_t)i * 3 + (size_t)c) * plane;
+    uint32_t sum = 0;
+    for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kEraseThreads * kP)) {
+      if constexpr (kU8) {
+        const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + chan + at);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t w = sp[q];
+          sum += (w & 255u) + ((w >> 8) & 255u) + ((w >> 16) & 255u) + (w >> 24);
+        }
+      } else {
+        const float4 e = *reinterpret_cast<const float4*>(static_cast<const float*>(src) + chan + at);
+        sum += erase_q8(e.x) + erase_q8(e.y) + erase_q8(e.z) + erase_q8(e.w);
+      }
+    }
+    if constexpr (kU8) sum *= 256u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+#pragma unroll
+      for (int w = 0; w < kEraseThreads / 64; ++w) total += s_part[w];
+      atomicAdd(f ? &job.work[i].sum[1][c] : &job.work[i].sum[0][c], total);
+    }
+    __syncthreads();  // (the next sample of this workgroup writes the parts again)
+  }
+}
+
+// One row piece of a rectangle: w elements of kB bytes from element number e0 of the sample's plane `base`, by one wave.  The
+// row starts anywhere, so the elements up to the first 16-byte boundary and those behind the last whole piece are stored
+// singly and the pieces between with 16-byte non-temporal stores.  A piece starts at an element number that is a multiple of
+// 4 (the plane's base is 4-byte aligned at least and a sample's planes are multiples of 16 elements), so the noise of a piece
+// is whole Philox blocks.
+template <int kB>
+__device__ __forceinline__ void erase_fill_row(uint8_t* base, uint32_t e0, int w, int lane, bool noise, uint32_t k0, uint32_t k1, int f, uint32_t byte) {
+  constexpr int kP = 16 / kB;  // elements of a piece
+  const uint32_t addr = (uint32_t)(uintptr_t)(base + (size_t)e0 * kB);
+  const int to_boundary = (int)(((16u - (addr & 15u)) & 15u) / (uint32_t)kB);
+  const int head = to_boundary < w ? to_boundary : w;
+  const int pieces = (w - head) / kP;
+  const int tail0 = head + pieces * kP;
+  const int singles = head + (w - tail0);
+  for (int t = lane; t < singles; t += 64) {
+    const uint32_t e = e0 + (uint32_t)(t < head ? t : tail0 + (t - head));
+    const uint32_t b = noise ? erase_noise_byte(k0, k1, f, e) : byte;
+    if constexpr (kB == 1) base[e] = (uint8_t)b;
+    else reinterpret_cast<float*>(base)[e] = (float)b;
+  }
+  for (int p = lane; p < pieces; p += 64) {
+    const uint32_t e = e0 + (uint32_t)(head + p * kP);
+    crop_u32x4 o;
+    if (noise) {
+#pragma unroll
+      for (int q = 0; q < kP / 4; ++q) {
+        const CropWords nw = crop_philox(CropWords{(e >> 2) + (uint32_t)q, (uint32_t)f, 0x0c75u, 0u}, k0, k1);
+        if constexpr (kB == 1) o[q] = (nw.x >> 24) | ((nw.y >> 24) << 8) | ((nw.z >> 24) << 16) | ((nw.w >> 24) << 24);
+        else o = crop_u32x4{__float_as_uint((float)(nw.x >> 24)), __float_as_uint((float)(nw.y >> 24)), __float_as_uint((float)(nw.z >> 24)), __float_as_uint((float)(nw.w >> 24))};
+      }
+    } else {
+      const uint32_t v = kB == 1 ? byte * 0x01010101u : __float_as_uint((float)byte);
+      o = crop_u32x4{v, v, v, v};
+    }
+    crop_store(reinterpret_cast<crop_u32x4*>(base + (size_t)e * kB), o);
+  }
+}
+
+// Painting and marking.  blockIdx.y counts the samples; blockIdx.x first the kEraseFillBlocks fill workgroups - (rectangle k,
+// plane B / G / R / the map of the rectangle's frame, one of kEraseFillSplit shares of its rows), a wave per row, so only the
+// rectangles' rows are touched and a sample without rectangles does no memory traffic - and then, per map given under
+// OFDG_ERASE_OCC, the workgroups of a pass over flow[f] and occ[f] in quads as flow_stats_kernel reads them.  That pass runs
+// only for a sample with a rectangle in frame 1 - f (and that frame flagged); it then also makes the direct marks of the
+// rectangles of frame f, and the fill workgroups leave that map alone - so every element of a map has one writer.  A quad of
+// the map is read and written back only where a mark falls into it.  The fill byte of the mean comes from the sums the first
+// launch left in `work`; workgroup 0 writes the sanitised record with the fill bytes from lane 0 with six vector stores.
+template <bool kU8, bool kOccU8, bool kHalf>
+__global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEraseJob job, int n, int W, int H, uint32_t occ_blocks) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  constexpr int kB = kU8 ? 1 : 4, kOB = kOccU8 ? 1 : 4;
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const bool mark = job.flags & OFDG_ERASE_OCC;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const DevEraseRec r = erase_record(job, i, W, H);
+    const int frames = erase_frames_of(r);
+    const unsigned long long g = (unsigned long long)(job.first_index + i);
+    const uint32_t k0 = job.seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+    if (job.recs_out && blockIdx.x == 0u && threadIdx.x == 0u) {
+      uint32_t fb[6];
+#pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        const int f = s / 3, c = s % 3;
+        fb[s] = !((frames >> f) & 1) || job.fill == OFDG_ERASE_NOISE ? 0u
+                : job.fill == OFDG_ERASE_CONST ? (uint32_t)job.color[c] : erase_mean_byte(job.work[i].sum[f][c], plane);
+      }
+      crop_u32x4* const o = reinterpret_cast<crop_u32x4*>(job.recs_out + i);
+      const DevEraseRect q0 = r.rect[0], q1 = r.rect[1], q2 = r.rect[2], q3 = r.rect[3];
+      o[0] = crop_u32x4{(uint32_t)r.count, (uint32_t)q0.x0, (uint32_t)q0.y0, (uint32_t)q0.w};
+      o[1] = crop_u32x4{(uint32_t)q0.h, (uint32_t)q0.frame, (uint32_t)q1.x0, (uint32_t)q1.y0};
+      o[2] = crop_u32x4{(uint32_t)q1.w, (uint32_t)q1.h, (uint32_t)q1.frame, (uint32_t)q2.x0};
+      o[3] = crop_u32x4{(uint32_t)q2.y0, (uint32_t)q2.w, (uint32_t)q2.h, (uint32_t)q2.frame};
+      o[4] = crop_u32x4{(uint32_t)q3.x0, (uint32_t)q3.y0, (uint32_t)q3.w, (uint32_t)q3.h};
+      o[5] = crop_u32x4{(uint32_t)q3.frame, fb[0] | (fb[1] << 8) | (fb[2] << 16) | (fb[3] << 24), fb[4] | (fb[5] << 8), 0u};
+    }
+    if (blockIdx.x < (uint32_t)kEraseFillBlocks) {
+      const int k = (int)blockIdx.x / (4 * kEraseFillSplit), pl = ((int)blockIdx.x / kEraseFillSplit) % 4, part = (int)blockIdx.x % kEraseFillSplit;
+      if (k >= r.count) continue;
+      const DevEraseRect q = erase_rect_at(r, k);
+      const int f = q.frame;
+      if (pl == 3) {  // the direct marks of the rectangle, unless the pass below serves this map
+        uint8_t* const map = static_cast<uint8_t*>(f ? job.occ[1] : job.occ[0]);
+        if (!mark || !map || (erase_cross(job, f) && ((frames >> (1 - f)) & 1))) continue;
+        uint8_t* const base = map + (size_t)i * plane * kOB;
+        for (int y = q.y0 + part * 4 + wave; y < q.y0 + q.h; y += 4 * kEraseFillSplit)
+          erase_fill_row<kOB>(base, (uint32_t)y * (uint32_t)W + (uint32_t)q.x0, q.w, lane, false, 0u, 0u, 0, 1u);
+      } else {
+        const bool noise = job.fill == OFDG_ERASE_NOISE;
+        const uint32_t byte = noise ? 0u : job.fill == OFDG_ERASE_CONST ? (uint32_t)(pl == 0 ? job.color[0] : pl == 1 ? job.color[1] : job.color[2])
+                                         : erase_mean_byte(f ? job.work[i].sum[1][pl] : job.work[i].sum[0][pl], plane);
+        uint8_t* const base = static_cast<uint8_t*>(f ? job.image[1] : job.image[0]) + (size_t)i * 3 * plane * kB;
+        for (int y = q.y0 + part * 4 + wave; y < q.y0 + q.h; y += 4 * kEraseFillSplit)
+          erase_fill_row<kB>(base, (uint32_t)pl * plane + (uint32_t)y * (uint32_t)W + (uint32_t)q.x0, q.w, lane, noise, k0, k1, f, byte);
+      }
+    } else {
+      const uint32_t b = blockIdx.x - (uint32_t)kEraseFillBlocks;
+      const int f = job.occ[0] && job.occ[1] ? (int)(b / occ_blocks) : job.occ[0] ? 0 : 1;
+      if (!erase_cross(job, f) || !((frames >> (1 - f)) & 1)) continue;
+      DevEraseRec rs;  // the four rectangles in scalar registers (fill and reserved are not read)
+      rs.rect[0] = erase_rect_at(r, 0);
+      rs.rect[1] = erase_rect_at(r, 1);
+      rs.rect[2] = erase_rect_at(r, 2);
+      rs.rect[3] = erase_rect_at(r, 3);
+      rs.count = __builtin_amdgcn_readfirstlane(r.count);
+      const uint32_t plane_quads = plane / 4u;
+      const uint32_t q_begin = (b % occ_blocks) * (uint32_t)kEraseOccQuads;
+      const uint32_t q_end = min(q_begin + (uint32_t)kEraseOccQuads, plane_quads);
+      const void* const flow = f ? job.flow[1] : job.flow[0];
+      void* const map = f ? job.occ[1] : job.occ[0];
+      const size_t pu = (size_t)i * 2 * plane_quads, pv = pu + plane_quads, po = (size_t)i * plane_quads;  // in quads
+      for (uint32_t qd = q_begin + threadIdx.x; qd < q_end; qd += (uint32_t)kEraseThreads) {
+        float u[4], v[4];
+        if constexpr (kHalf) {
+          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu + qd], c = reinterpret_cast<const f16x4*>(flow)[pv + qd];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) { u[s] = (float)a[s]; v[s] = (float)c[s]; }
+        } else {
+          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu + qd], c = reinterpret_cast<const f32x4*>(flow)[pv + qd];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) { u[s] = a[s]; v[s] = c[s]; }
+        }
+        const uint32_t at = qd * 4u;
+        const int y = (int)(at / (uint32_t)W), x = (int)(at - (uint32_t)y * (uint32_t)W);  // (W % 8 == 0: a quad lies in one row)
+        uint32_t hits = 0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) hits |= (erase_marks(rs, f, true, x + s, y, u[s], v[s]) ? 1u : 0u) << s;
+        if (!hits) continue;
+        if constexpr (kOccU8) {
+          uint32_t* const p = reinterpret_cast<uint32_t*>(map) + po + qd;
+          uint32_t o = *p;
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            if ((hits >> s) & 1u) o = (o & ~(255u << (8 * s))) | (1u << (8 * s));
+          *p = o;
+        } else {
+          f32x4* const p = reinterpret_cast<f32x4*>(map) + po + qd;
+          f32x4 o = *p;
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            if ((hits >> s) & 1u) o[s] = 1.0f;
+          *p = o;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -291,7 +291,7 @@ struct PostOp {
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
-// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel.
+// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1827,6 +1827,53 @@ int ofdg_boundaries(ofdg_ctx* c, const struct ofdg_boundary_job* job, int n_samp
   with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
     with_bool(labels, [&](auto with_labels) {
       hipLaunchKernelGGL((boundary_kernel<decltype(half)::value, decltype(with_labels)::value>), g, dim3(kBndThreads), 0, st, *j, n_samples, W, H, tiles_x);
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Occluder rectangles on caller-given planes, in place: under OFDG_ERASE_MEAN the clearing of `work` and the reduction, then
+// one kernel that paints and marks, all on `stream`.
+int ofdg_erase(ofdg_ctx* c, const struct ofdg_erase_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_erase"};
+  const DevEraseJob* const j = reinterpret_cast<const DevEraseJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = erase_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = erase_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const bool mark = j->flags & OFDG_ERASE_OCC, mean = j->fill == OFDG_ERASE_MEAN;
+  for (int f = 0; f < 2; ++f) {
+    if ((j->flags >> f) & 1) OFDG_TRY(op.aligned(f ? "image[1]" : "image[0]", j->image[f], j->image_fmt));
+    if (mark) OFDG_TRY(op.aligned(f ? "occ[1]" : "occ[0]", j->occ[f], j->occ_fmt));
+    if (erase_cross(*j, f)) OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  if (mean && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const unsigned ny = (unsigned)std::min(n_samples, 65535);
+  if (mean) {
+    HIP_OK(c, hipMemsetAsync(j->work, 0, sizeof(DevEraseWork) * (size_t)n_samples, st));
+    const uint32_t per_channel = (plane + kEraseMeanPixels - 1) / kEraseMeanPixels;
+    const dim3 g(per_channel * 3u * ((j->flags & 3) == 3 ? 2u : 1u), ny);
+    with_bool(j->image_fmt == OFDG_FMT_U8, [&](auto image_u8) {
+      hipLaunchKernelGGL((erase_mean_kernel<decltype(image_u8)::value>), g, dim3(kEraseThreads), 0, st, *j, n_samples, W, H, per_channel);
+    });
+    HIP_OK(c, hipGetLastError());
+  }
+  const uint32_t occ_blocks = (plane / 4u + kEraseOccQuads - 1) / kEraseOccQuads;
+  const uint32_t maps = mark ? (j->occ[0] ? 1u : 0u) + (j->occ[1] ? 1u : 0u) : 0u;
+  const dim3 g((uint32_t)kEraseFillBlocks + occ_blocks * maps, ny);
+  with_bool(j->image_fmt == OFDG_FMT_U8, [&](auto image_u8) {
+    with_bool(mark && j->occ_fmt == OFDG_FMT_U8, [&](auto occ_u8) {
+      with_bool(mark && j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
+        hipLaunchKernelGGL((erase_apply_kernel<decltype(image_u8)::value, decltype(occ_u8)::value, decltype(half)::value>), g, dim3(kEraseThreads), 0, st,
+                           *j, n_samples, W, H, occ_blocks);
+      });
     });
   });
   HIP_OK(c, hipGetLastError());

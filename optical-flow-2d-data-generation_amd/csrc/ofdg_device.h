@@ -948,6 +948,222 @@ inline const char* boundary_arg_error(const DevBoundaryJob* j, int n, int width,
   return nullptr;
 }
 
+// ---- Occluder rectangles (ofdg_erase, include/ofdg.h) ----------------------------------------------------------------------
+// What the device entry, the kernels and the host twin share: the job as the kernels take it, the record's draw and its
+// sanitising, the integer mean, the noise byte, the target test of the occlusion rule and the argument rules.
+constexpr int kEraseMaxRects = 4;  // OFDG_ERASE_MAX_RECTS
+struct DevEraseRect {
+  int32_t x0, y0, w, h, frame;
+};
+struct DevEraseRec {  // ofdg_erase_rec, field for field
+  int32_t count;
+  DevEraseRect rect[kEraseMaxRects];
+  uint8_t fill[2][3];
+  uint8_t reserved[6];
+};
+struct DevEraseWork {  // one sample's part of job->work: the Q8 sums of the frames that have a rectangle
+  unsigned long long sum[2][3];
+  unsigned long long pad[2];
+};
+struct DevEraseJob {  // struct ofdg_erase_job, field for field
+  void* image[2];
+  void* occ[2];
+  const void* flow[2];
+  const DevEraseRec* recs;
+  DevEraseRec* recs_out;
+  DevEraseWork* work;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, image_fmt, occ_fmt, flow_fmt, flags, fill;
+  int32_t min_rects, max_rects, min_size, max_size;
+  float prob;
+  int32_t color[3];
+  int32_t reserved[2];
+};
+static_assert(sizeof(ofdg_erase_rec) == sizeof(DevEraseRec) && sizeof(DevEraseRec) == 96 && sizeof(ofdg_erase_rect) == sizeof(DevEraseRect) &&
+              offsetof(ofdg_erase_rec, rect) == offsetof(DevEraseRec, rect) && offsetof(DevEraseRec, rect) == 4 && offsetof(ofdg_erase_rec, fill) == offsetof(DevEraseRec, fill) &&
+              offsetof(DevEraseRec, fill) == 84 && offsetof(ofdg_erase_rec, reserved) == offsetof(DevEraseRec, reserved) && offsetof(DevEraseRec, reserved) == 90 &&
+              OFDG_ERASE_MAX_RECTS == kEraseMaxRects && sizeof(DevEraseWork) == OFDG_ERASE_WORK_BYTES,
+              "ofdg_erase_rec: 96 bytes, the layout the kernels read and write as six 16-byte pieces; a sample's workspace");
+static_assert(sizeof(struct ofdg_erase_job) == sizeof(DevEraseJob) && sizeof(DevEraseJob) == 152 && offsetof(struct ofdg_erase_job, occ) == offsetof(DevEraseJob, occ) &&
+              offsetof(struct ofdg_erase_job, flow) == offsetof(DevEraseJob, flow) && offsetof(struct ofdg_erase_job, recs) == offsetof(DevEraseJob, recs) &&
+              offsetof(struct ofdg_erase_job, recs_out) == offsetof(DevEraseJob, recs_out) && offsetof(struct ofdg_erase_job, work) == offsetof(DevEraseJob, work) &&
+              offsetof(struct ofdg_erase_job, first_index) == offsetof(DevEraseJob, first_index) && offsetof(struct ofdg_erase_job, seed) == offsetof(DevEraseJob, seed) &&
+              offsetof(DevEraseJob, seed) == 80 && offsetof(struct ofdg_erase_job, width) == offsetof(DevEraseJob, width) &&
+              offsetof(struct ofdg_erase_job, image_fmt) == offsetof(DevEraseJob, image_fmt) && offsetof(struct ofdg_erase_job, fill) == offsetof(DevEraseJob, fill) &&
+              offsetof(struct ofdg_erase_job, min_rects) == offsetof(DevEraseJob, min_rects) && offsetof(DevEraseJob, min_rects) == 112 &&
+              offsetof(struct ofdg_erase_job, prob) == offsetof(DevEraseJob, prob) && offsetof(struct ofdg_erase_job, color) == offsetof(DevEraseJob, color) &&
+              offsetof(struct ofdg_erase_job, reserved) == offsetof(DevEraseJob, reserved) && offsetof(DevEraseJob, reserved) == 144 && OFDG_ERASE_FRAME0 == 1 &&
+              OFDG_ERASE_FRAME1 == 2 && OFDG_ERASE_OCC == 4 && OFDG_ERASE_MEAN == 0 && OFDG_ERASE_CONST == 1 && OFDG_ERASE_NOISE == 2,
+              "struct ofdg_erase_job: 152 bytes, the layout the kernels take; the helpers below spell the codes out");
+// lo + floor(w * (hi - lo + 1) / 2^32): the multiply-shift of the crop's draw
+OFDG_HD_FN int32_t erase_pick(uint32_t w, int32_t lo, int32_t hi) { return lo + (int32_t)(uint32_t)(((unsigned long long)w * (uint32_t)(hi - lo + 1)) >> 32); }
+// The record of global sample g for a width x height plane: Philox blocks 0..4 under the sampler's key of g at the counters
+// {j, 0, 0x0c74, 0}.  `j` supplies flags, prob and the four ranges (erase_ranges_error has passed).  Not sanitised.  Here and
+// below the four rectangles are spelled out one by one, never indexed by a variable: a kernel then keeps the record in
+// registers.
+OFDG_HD_FN DevEraseRect erase_draw_rect(int k, int count, uint32_t frame_bits, uint32_t k0, uint32_t k1, int width, int height, const DevEraseJob& j) {
+  const CropWords b = crop_philox(CropWords{(uint32_t)k + 1u, 0u, 0x0c74u, 0u}, k0, k1);
+  const int frames = j.flags & 3;
+  const bool on = k < count;
+  DevEraseRect q;
+  q.x0 = on ? erase_pick(b.z, 0, width - 1) : 0;
+  q.y0 = on ? erase_pick(b.w, 0, height - 1) : 0;
+  q.w = on ? erase_pick(b.x, j.min_size, j.max_size) : 0;
+  q.h = on ? erase_pick(b.y, j.min_size, j.max_size) : 0;
+  q.frame = on ? (frames == 3 ? (int32_t)((frame_bits >> k) & 1u) : frames == 2 ? 1 : 0) : 0;
+  return q;
+}
+OFDG_HD_FN DevEraseRec erase_draw_rec(uint32_t seed, unsigned long long g, int width, int height, const DevEraseJob& j) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords a = crop_philox(CropWords{0u, 0u, 0x0c74u, 0u}, k0, k1);
+  DevEraseRec r;
+  const bool erased = photo_unit(a.x) < j.prob;
+  r.count = erased ? erase_pick(a.y, j.min_rects, j.max_rects) : 0;
+  r.rect[0] = erase_draw_rect(0, r.count, a.z, k0, k1, width, height, j);
+  r.rect[1] = erase_draw_rect(1, r.count, a.z, k0, k1, width, height, j);
+  r.rect[2] = erase_draw_rect(2, r.count, a.z, k0, k1, width, height, j);
+  r.rect[3] = erase_draw_rect(3, r.count, a.z, k0, k1, width, height, j);
+  r.fill[0][0] = r.fill[0][1] = r.fill[0][2] = r.fill[1][0] = r.fill[1][1] = r.fill[1][2] = 0;
+  r.reserved[0] = r.reserved[1] = r.reserved[2] = r.reserved[3] = r.reserved[4] = r.reserved[5] = 0;
+  return r;
+}
+// What is used of a record, given or drawn: the rectangles of flagged frames, clipped to the plane, the empty ones dropped
+// and the kept ones moved to the front in their order; everything else 0.
+OFDG_HD_FN DevEraseRect erase_clip(const DevEraseRect& q, bool counted, int width, int height, int flags, bool* keep) {
+  const int f = q.frame & 1;
+  const long long x0 = q.x0 < 0 ? 0 : q.x0, y0 = q.y0 < 0 ? 0 : q.y0;
+  const long long xe = (long long)q.x0 + q.w, ye = (long long)q.y0 + q.h;
+  const long long x1 = xe < width ? xe : width, y1 = ye < height ? ye : height;
+  *keep = counted && ((flags >> f) & 1) && q.w >= 1 && q.h >= 1 && x1 > x0 && y1 > y0;
+  return DevEraseRect{(int32_t)x0, (int32_t)y0, (int32_t)(x1 - x0), (int32_t)(y1 - y0), f};
+}
+// a if on, else b - field by field and on values: a conditional between members would select their addresses
+OFDG_HD_FN int32_t erase_select_int(bool on, int32_t a, int32_t b) { return on ? a : b; }
+OFDG_HD_FN DevEraseRect erase_select(bool on, const DevEraseRect& a, const DevEraseRect& b) {
+  return DevEraseRect{erase_select_int(on, a.x0, b.x0), erase_select_int(on, a.y0, b.y0), erase_select_int(on, a.w, b.w), erase_select_int(on, a.h, b.h),
+                      erase_select_int(on, a.frame, b.frame)};
+}
+OFDG_HD_FN DevEraseRec erase_sanitise(const DevEraseRec& in, int width, int height, int flags) {
+  const int count = in.count < 0 ? 0 : in.count > kEraseMaxRects ? kEraseMaxRects : in.count;
+  bool k0, k1, k2, k3;
+  const DevEraseRect o0 = erase_clip(in.rect[0], count > 0, width, height, flags, &k0), o1 = erase_clip(in.rect[1], count > 1, width, height, flags, &k1);
+  const DevEraseRect o2 = erase_clip(in.rect[2], count > 2, width, height, flags, &k2), o3 = erase_clip(in.rect[3], count > 3, width, height, flags, &k3);
+  const int p1 = k0 ? 1 : 0, p2 = p1 + (k1 ? 1 : 0), p3 = p2 + (k2 ? 1 : 0);  // the kept ones in front of rectangle 1, 2, 3
+  const DevEraseRect none = DevEraseRect{0, 0, 0, 0, 0};
+  DevEraseRec r;
+  r.count = p3 + (k3 ? 1 : 0);
+  r.rect[0] = erase_select(k0, o0, erase_select(k1 && p1 == 0, o1, erase_select(k2 && p2 == 0, o2, erase_select(k3 && p3 == 0, o3, none))));
+  r.rect[1] = erase_select(k1 && p1 == 1, o1, erase_select(k2 && p2 == 1, o2, erase_select(k3 && p3 == 1, o3, none)));
+  r.rect[2] = erase_select(k2 && p2 == 2, o2, erase_select(k3 && p3 == 2, o3, none));
+  r.rect[3] = erase_select(k3 && p3 == 3, o3, none);
+  r.fill[0][0] = r.fill[0][1] = r.fill[0][2] = r.fill[1][0] = r.fill[1][1] = r.fill[1][2] = 0;
+  r.reserved[0] = r.reserved[1] = r.reserved[2] = r.reserved[3] = r.reserved[4] = r.reserved[5] = 0;
+  return r;
+}
+// bit f: frame f has a rectangle (of a sanitised record)
+OFDG_HD_FN int erase_frames_of(const DevEraseRec& r) {
+  return (r.count > 0 ? 1 << r.rect[0].frame : 0) | (r.count > 1 ? 1 << r.rect[1].frame : 0) | (r.count > 2 ? 1 << r.rect[2].frame : 0) |
+         (r.count > 3 ? 1 << r.rect[3].frame : 0);
+}
+// The Q8 value of a float32 element: clamped to [0, 255] (a NaN becomes 0), times 256, to nearest even.
+OFDG_HD_FN uint32_t erase_q8(float v) {
+  v = v > 0.0f ? v : 0.0f;
+  v = v < 255.0f ? v : 255.0f;
+  return (uint32_t)rintf(v * 256.0f);
+}
+// The fill byte of a channel whose P elements sum to S in Q8: the mean rounded half up to Q8, then half up to a byte.
+OFDG_HD_FN uint32_t erase_mean_byte(unsigned long long S, unsigned long long P) {
+  const unsigned long long mean_q8 = (2ull * S + P) / (2ull * P);
+  return (uint32_t)((mean_q8 + 128ull) >> 8);
+}
+// The noise byte of element e of frame f: the top byte of word e & 3 of the block {e >> 2, f, 0x0c75, 0}.
+OFDG_HD_FN uint32_t erase_noise_word(const CropWords& w, uint32_t e) { return ((e & 3u) == 0u ? w.x : (e & 3u) == 1u ? w.y : (e & 3u) == 2u ? w.z : w.w) >> 24; }
+OFDG_HD_FN uint32_t erase_noise_byte(uint32_t k0, uint32_t k1, int f, uint32_t e) {
+  return erase_noise_word(crop_philox(CropWords{e >> 2, (uint32_t)f, 0x0c75u, 0u}, k0, k1), e);
+}
+// Does the flow target of (x, y) with displacement (u, v) lie inside rectangle q?  The crop's formula per axis.
+OFDG_HD_FN bool erase_target_inside(int x, int y, float u, float v, const DevEraseRect& q) {
+  return crop_target_inside(x, u, q.x0, q.w) && crop_target_inside(y, v, q.y0, q.h);
+}
+OFDG_HD_FN bool erase_inside(int x, int y, const DevEraseRect& q) { return x >= q.x0 && x < q.x0 + q.w && y >= q.y0 && y < q.y0 + q.h; }
+OFDG_HD_FN bool erase_marks_one(const DevEraseRect& q, int f, bool cross, int x, int y, float u, float v) {
+  return q.frame == f ? erase_inside(x, y, q) : cross && erase_target_inside(x, y, u, v, q);
+}
+// Is element (x, y) of the map of frame f marked by a sanitised record?  cross: frame 1 - f is flagged and (u, v) is the
+// element's flow[f].
+OFDG_HD_FN bool erase_marks(const DevEraseRec& r, int f, bool cross, int x, int y, float u, float v) {
+  // (spelled out rectangle by rectangle: no indexed access, so a kernel keeps the record in registers)
+  return (r.count > 0 && erase_marks_one(r.rect[0], f, cross, x, y, u, v)) || (r.count > 1 && erase_marks_one(r.rect[1], f, cross, x, y, u, v)) ||
+         (r.count > 2 && erase_marks_one(r.rect[2], f, cross, x, y, u, v)) || (r.count > 3 && erase_marks_one(r.rect[3], f, cross, x, y, u, v));
+}
+// does the map of frame f need its flow?  (OFDG_ERASE_OCC, the map given, frame 1 - f flagged)
+OFDG_HD_FN bool erase_cross(const DevEraseJob& j, int f) { return (j.flags & OFDG_ERASE_OCC) && j.occ[f] && ((j.flags >> (1 - f)) & 1); }
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* erase_plane_size(const DevEraseJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// What the draw reads of a job: the first rule broken, or nullptr.
+inline const char* erase_ranges_error(const DevEraseJob& j) {
+  if (j.flags & ~(OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1 | OFDG_ERASE_OCC)) return "flags holds unknown bits";
+  if (!(j.flags & (OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1))) return "flags: OFDG_ERASE_FRAME0 or OFDG_ERASE_FRAME1 must be set";
+  if (!(j.prob >= 0.0f && j.prob <= 1.0f)) return "prob must lie in [0, 1]";
+  if (j.min_rects < 0 || j.max_rects > kEraseMaxRects || j.min_rects > j.max_rects) return "min_rects <= max_rects must lie in 0..4";
+  if (j.min_size < 1 || j.max_size > 32767 || j.min_size > j.max_size) return "min_size <= max_size must lie in 1..32767";
+  return nullptr;
+}
+// The argument rules ofdg_erase and ofdg_host_erase share: the first rule broken, or nullptr.  width, height: what
+// erase_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+inline const char* erase_arg_error(const DevEraseJob* j, int n, int width, int height, bool with_work) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "3 * width * height must be below 2^31";
+  if (j->image_fmt != OFDG_FMT_F32 && j->image_fmt != OFDG_FMT_U8) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags & ~(OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1 | OFDG_ERASE_OCC)) return "flags holds unknown bits";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (!(j->flags & (OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1))) return "flags: OFDG_ERASE_FRAME0 or OFDG_ERASE_FRAME1 must be set";
+  if (!j->image[0] && !j->image[1]) return "image: no frame is set";
+  for (int f = 0; f < 2; ++f)
+    if (((j->flags >> f) & 1) && !j->image[f]) return "image: a flagged frame has no image";
+  if (j->fill != OFDG_ERASE_MEAN && j->fill != OFDG_ERASE_CONST && j->fill != OFDG_ERASE_NOISE) return "fill must be OFDG_ERASE_MEAN, OFDG_ERASE_CONST or OFDG_ERASE_NOISE";
+  if (j->fill == OFDG_ERASE_CONST)
+    for (int c = 0; c < 3; ++c)
+      if (j->color[c] < 0 || j->color[c] > 255) return "color must lie in 0..255";
+  if (!j->recs)
+    if (const char* why = erase_ranges_error(*j)) return why;
+  const bool occ = j->flags & OFDG_ERASE_OCC;
+  if (occ) {
+    if (!j->occ[0] && !j->occ[1]) return "occ: OFDG_ERASE_OCC needs a map";
+    if (j->occ_fmt != OFDG_FMT_F32 && j->occ_fmt != OFDG_FMT_U8) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+    for (int f = 0; f < 2; ++f)
+      if (erase_cross(*j, f)) {
+        if (!j->flow[f]) return "flow: a map needs its flow when the other frame is flagged";
+        if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+      }
+  }
+  const bool work = with_work && j->fill == OFDG_ERASE_MEAN;
+  if (work && !j->work) return "work is NULL under OFDG_ERASE_MEAN";
+  // a written range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[10];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (((j->flags >> f) & 1)) r[nr++] = Range{(uintptr_t)j->image[f], (uintptr_t)j->image[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->image_fmt)), true};
+    if (occ && j->occ[f]) r[nr++] = Range{(uintptr_t)j->occ[f], (uintptr_t)j->occ[f] + (uintptr_t)(plane * fmt_elem_bytes(j->occ_fmt)), true};
+    if (erase_cross(*j, f)) r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevEraseRec), false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevEraseRec), true};
+  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(DevEraseWork), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.
