@@ -1509,6 +1509,24 @@ class Generator:
         self._check(entry(self.h, _dptr(flow), fcode, _optr(occ), ocode, n, *plane, PYR_SCALE if scale else 0, C.byref(rec), C.c_void_p(stream)))
         return out
 
+    def _job_size(self, size):
+        """(height, width, the size a job states) of planes of size=(height, width), or, with None, of the context's frame,
+        which a job states as (0, 0)."""
+        if size is None:
+            return self.params.height, self.params.width, (0, 0)
+        height, width = int(size[0]), int(size[1])
+        return height, width, (height, width)
+
+    @staticmethod
+    def _check_recs(recs, recs_out, dtype, shape):
+        """recs and recs_out of a post-processing call: each None or a tensor of torch.<dtype> and of that shape"""
+        for t in (recs, recs_out):
+            if t is not None and (str(t.dtype) != "torch." + dtype or tuple(t.shape) != shape):
+                raise ValueError("recs and recs_out must be %s [%s], got %s %s" % (dtype, ",".join(map(str, shape)), t.dtype, tuple(t.shape)))
+
+    def _seed(self, seed):
+        return self.params.seed if seed is None else seed
+
     def crop(self, src, dst, recs=None, first_index=0, seed=None, hflip=False, vflip=False, occ_window=False, recs_out=None, stream=0):
         """The training window of every plane of a batch in one launch (ofdg_crop, include/ofdg.h): src and dst are dicts keyed
         by CROP_PLANES (image0, image1, flow, flow1, occ0, occ1, label0, label1; any subset), src[name] the [n,C,H,W] tensor a
@@ -1520,11 +1538,9 @@ class Generator:
         receives the records used.  stream: the stream the planes were written on, or STREAM_OWN.  Asynchronous; there is no
         in-place form.  Returns dst."""
         n, crop_h, crop_w, *codes = crop_format(src, dst, self.params.height, self.params.width)
-        for t in (recs, recs_out):
-            if t is not None and (str(t.dtype) != "torch.int32" or tuple(t.shape) != (n, 4)):
-                raise ValueError("recs and recs_out must be int32 [%d,4], got %s %s" % (n, t.dtype, tuple(t.shape)))
-        job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, _optr(recs), _optr(recs_out), first_index,
-                        self.params.seed if seed is None else seed, _crop_flags(hflip, vflip, occ_window))
+        self._check_recs(recs, recs_out, "int32", (n, 4))
+        job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
+                        _crop_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_crop(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
@@ -1540,13 +1556,10 @@ class Generator:
         Returns dst."""
         src = tuple(src)
         dst = src if dst is None else tuple(dst)
-        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        height, width, job_size = self._job_size(size)
         n, _, _, *codes = photo_format(src, dst, height, width)
-        for t in (recs, recs_out):
-            if t is not None and (str(t.dtype) != "torch.float32" or tuple(t.shape) != (n, PHOTO_REC_FLOATS)):
-                raise ValueError("recs and recs_out must be float32 [%d,%d], got %s %s" % (n, PHOTO_REC_FLOATS, t.dtype, tuple(t.shape)))
-        job = _photo_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), _optr(recs), _optr(recs_out),
-                         first_index, self.params.seed if seed is None else seed, ranges)
+        self._check_recs(recs, recs_out, "float32", (n, PHOTO_REC_FLOATS))
+        job = _photo_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
         self._check(lib().ofdg_photo(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
@@ -1563,13 +1576,11 @@ class Generator:
         recs_out: None or a float64 device tensor [n,14] that receives the records used.  stream: the stream the planes were
         written on, or STREAM_OWN.  size=(height, width): sources of that size instead of the context's frame.  Asynchronous;
         there is no in-place form.  Returns dst."""
-        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        height, width, job_size = self._job_size(size)
         n, out_h, out_w, *codes = spatial_format(src, dst, height, width)
-        for t in (recs, recs_out):
-            if t is not None and (str(t.dtype) != "torch.float64" or tuple(t.shape) != (n, SPATIAL_REC_DOUBLES)):
-                raise ValueError("recs and recs_out must be float64 [%d,%d], got %s %s" % (n, SPATIAL_REC_DOUBLES, t.dtype, tuple(t.shape)))
-        job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), out_h, out_w, _optr(recs),
-                           _optr(recs_out), first_index, self.params.seed if seed is None else seed, ranges, _spatial_flags(hflip, vflip, occ_window))
+        self._check_recs(recs, recs_out, "float64", (n, SPATIAL_REC_DOUBLES))
+        job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, job_size, out_h, out_w, _optr(recs), _optr(recs_out), first_index,
+                           self._seed(seed), ranges, _spatial_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_spatial(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
@@ -1584,7 +1595,7 @@ class Generator:
         the channels of a frame are written in the order R, G, B.  stream: the stream the planes were written on, or
         STREAM_OWN.  size=(height, width): planes of that size instead of the context's frame.  Asynchronous; there is no
         in-place form.  Returns dst."""
-        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        height, width, job_size = self._job_size(size)
         n, _, _, *codes = pack_format(src, dst, layout, concat, height, width)
 
         def dptr(t):  # a destination: dense in the memory order of the layout
@@ -1592,8 +1603,7 @@ class Generator:
             if not t.is_cuda or not t.is_contiguous(memory_format=torch.channels_last if layout == PACK_NHWC else torch.contiguous_format):
                 raise ValueError("dst tensors must be device tensors as alloc_pack makes them for this layout")
             return t.data_ptr()
-        job = _pack_job(src, dst, lambda t: _dptr(t).value, dptr, codes, (0, 0) if size is None else (height, width), scale, bias, flow_scale,
-                        layout, concat, rgb)
+        job = _pack_job(src, dst, lambda t: _dptr(t).value, dptr, codes, job_size, scale, bias, flow_scale, layout, concat, rgb)
         self._check(lib().ofdg_pack(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
@@ -1607,10 +1617,10 @@ class Generator:
         when a label plane is given.  min_step: a pair is a step when its flow difference exceeds it (pixels).  stream: the
         stream the planes were written on, or STREAM_OWN.  size=(height, width): planes of that size instead of the context's
         frame.  Asynchronous."""
-        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        height, width, job_size = self._job_size(size)
         n, _, _, code = boundaries_format(flow, edge, dist2, label, flow1, edge1, dist2_1, label1, height, width)
-        job = _boundary_job((flow, edge, dist2, label, flow1, edge1, dist2_1, label1), lambda t: _dptr(t).value, code,
-                            (0, 0) if size is None else (height, width), radius, min_step, labels)
+        job = _boundary_job((flow, edge, dist2, label, flow1, edge1, dist2_1, label1), lambda t: _dptr(t).value, code, job_size, radius,
+                            min_step, labels)
         self._check(lib().ofdg_boundaries(self.h, C.byref(job), n, C.c_void_p(stream)))
 
     def erase(self, images, occ=None, flow=None, recs=None, first_index=0, seed=None, ranges=None, fill=ERASE_MEAN, color=(0, 0, 0), frames=(1,),
@@ -1627,16 +1637,13 @@ class Generator:
         (alloc_erase makes both); one per call in flight.  stream: the stream the planes were written on, or STREAM_OWN.
         size=(height, width): planes of that size instead of the context's.  Asynchronous.  Returns images."""
         images = tuple(images)
-        height, width = (self.params.height, self.params.width) if size is None else (int(size[0]), int(size[1]))
+        height, width, job_size = self._job_size(size)
         n, _, _, *codes = erase_format(images, occ, flow, height, width)
-        for t in (recs, recs_out):
-            if t is not None and (str(t.dtype) != "torch.int32" or tuple(t.shape) != (n, ERASE_REC_WORDS)):
-                raise ValueError("recs and recs_out must be int32 [%d,%d], got %s %s" % (n, ERASE_REC_WORDS, t.dtype, tuple(t.shape)))
+        self._check_recs(recs, recs_out, "int32", (n, ERASE_REC_WORDS))
         if fill == ERASE_MEAN and (work is None or str(work.dtype) != "torch.uint8" or work.numel() < n * ERASE_WORK_BYTES):
             raise ValueError("fill=ERASE_MEAN needs work=, a uint8 device tensor of at least [%d,%d] (alloc_erase)" % (n, ERASE_WORK_BYTES))
-        job = _erase_job(images, occ, flow, lambda t: _dptr(t).value, codes, (0, 0) if size is None else (height, width), _optr(recs),
-                         _optr(recs_out), _optr(work) if fill == ERASE_MEAN else None, first_index, self.params.seed if seed is None else seed,
-                         ranges, fill, color, frames, mark_occ)
+        job = _erase_job(images, occ, flow, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out),
+                         _optr(work) if fill == ERASE_MEAN else None, first_index, self._seed(seed), ranges, fill, color, frames, mark_occ)
         self._check(lib().ofdg_erase(self.h, C.byref(job), n, C.c_void_p(stream)))
         return images
 
@@ -2246,6 +2253,27 @@ class DataGenerationLayer:
             pass
 
 
+class _RingSlot:
+    """One ring set of FlowLoader: everything one batch in flight is written into, and the two events of its hand-over.  A
+    buffer of a stage the loader does not run is None."""
+    __slots__ = ("outs",         # (image0, image1, flow): what forward writes ...
+                 "extras",       # ... and its extras dict (None without extras=)
+                 "frame",        # both by name: the source of the window
+                 "planes",       # the planes every stage behind the window works on, by name: the window's, or `frame` itself
+                 "window_recs",  # the records of crop= / spatial=
+                 "objects",      # (rows, counts) of objects=True
+                 "stats",        # the rows of stats=True
+                 "pyramid",      # the levels of pyramid=, or (levels, weights)
+                 "photo",        # the records of photo=
+                 "erase",        # (workspace, records) of erase=
+                 "edges",        # the planes of boundaries= by name ...
+                 "edge_args",    # ... and the plane arguments of Generator.boundaries that fill them
+                 "packed",       # the tensors of pack= by name
+                 "ready",        # event: the batch is rendered (recorded on the internal stream)
+                 "released",     # event: the consumer is done with the set (None until it has been handed out once)
+                 "batch")        # what the set hands out
+
+
 class FlowLoader:
     """Endless iterator of (image0, image1, flow) CUDA tensors - the role of the reference's prefetch
     thread + blocking queue (data_generation_layer.cpp:36-56, 141-172, 266-282; data_param.prefetch).
@@ -2257,63 +2285,62 @@ class FlowLoader:
     and a buffer set is re-rendered only after the consumer work enqueued up to the next `next()` is done.
     Use the tensors on the consumer stream, or synchronise before touching them elsewhere.  Samples shard
     over ranks by global index (params.rank / params.world_size): no communication.
-    extras=("flow1", "occ0", ...): the optional outputs are rendered too, into buffers cycled with the ring, and every
-    batch is (image0, image1, flow, {name: tensor}).
+
+    A batch is made by these stages, each only when its option asks for it, all enqueued on the batch's internal stream in
+    this order, every buffer cycled with the ring:
+
+        1. forward          the frames, the flow and the extras=
+        2. spatial= / crop= the window, into planes of its own: every later stage works on the window's planes and size
+        3. photo=           in place, on both frames
+        4. erase=           in place, on the frames and the occlusion maps
+        5. objects=True     the table, of the label planes of stage 1
+        6. stats=, pyramid= the reductions of flow and occ0
+        7. boundaries=      of the flows and label planes
+        8. pack=            of image0, image1 and flow, into tensors of its own
+
+    So the eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
+    unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
+    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 to 4 are drawn from the
+    context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
+    same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
+    as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
+
+    extras=("flow1", "occ0", ...): the optional outputs are rendered too; the dict holds them by name.
     image_dtype=torch.uint8 / flow_dtype=torch.float16: the ring's buffers are allocated and rendered in the compact formats.
     With extras= that takes extras_compact=True: flow1 then has flow_dtype and the occlusion maps are uint8 (1 / 0); without
     it the extras are float32 and a compact format with them raises.
-    objects=True (needs label0 and label1 among extras=): the per-object annotation table of every batch (Generator.object_table,
-    enqueued right behind the batch on the same internal stream) in buffers cycled with the ring; the batch's extras dict then
-    also holds "objects" (uint8 [n, 65, 96], see object_table_numpy) and "object_counts" (int32 [n]).
-    stats=True: the flow statistics of every batch (Generator.flow_stats with bin_px=stats_bin_px, enqueued right behind the
-    batch on the same internal stream; with "occ0" among extras= the map is passed) in rows cycled with the ring; every batch
-    is then (image0, image1, flow, {...}) and the dict also holds "flow_stats" (uint8 [n, 304], see flow_stats_numpy).
-    pyramid=L: the flow pyramid of every batch (Generator.flow_pyramid with levels=L, scale=pyramid_scale, in the flow's dtype,
-    enqueued right behind the batch on the same internal stream; with "occ0" among extras= the map is passed) in levels cycled
-    with the ring; every batch is then (image0, image1, flow, {...}) and the dict also holds "flow_pyramid" (the list of L
-    tensors [n,2,H>>k,W>>k]) and, with pyramid_weights=True, "flow_pyramid_weights" (the list of uint16 [n,1,H>>k,W>>k]).
-    crop=(crop_h, crop_w): every batch is cut to a training window per sample (Generator.crop into a second ring of buffers,
-    enqueued right behind the batch on the same internal stream; windows drawn from the context's seed and the batch's
-    first global index - shard_first_index of its step -, so start= resumes the same windows; crop_hflip / crop_vflip allow
-    drawn flips, crop_occ_window marks pixels whose target leaves the window in occ0 / occ1).  stats= and pyramid= then reduce
-    the CROPPED flow and occ0; the loader yields the cropped tensors and extras, every batch is (image0, image1, flow, {...})
-    and the dict also holds "crop" (int32 [n,4]: x0, y0, flags, 0).  objects=True with crop= raises: its boxes are of the
-    uncropped frame.
-    photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames of every batch are augmented in place
-    (Generator.photo, enqueued on the same internal stream right behind the batch - behind the crop when there is one, on the
-    cropped frames; records drawn from the context's seed and the batch's first global index, so start= and sharding make the
-    same pixels); every batch is then (image0, image1, flow, {...}) and the dict also holds "photo" (float32 [n,16], the
-    records used).
+    crop=(crop_h, crop_w): every batch is cut to a training window per sample (Generator.crop; crop_hflip / crop_vflip allow
+    drawn flips, crop_occ_window marks pixels whose target leaves the window in occ0 / occ1).  The loader yields the cropped
+    tensors and extras; the dict also holds "crop" (int32 [n,4]: x0, y0, flags, 0).
     spatial=ranges (a dict of SPATIAL_RANGES, SPATIAL_FLOWNET for one) with spatial_size=(out_h, out_w): every batch is warped
-    per sample into an out_h x out_w window (Generator.spatial into a second ring of buffers, enqueued right behind the batch
-    on the same internal stream, exactly where the crop would go; records drawn from the context's seed and the batch's first
-    global index - shard_first_index of its step -, so start= and sharding reproduce the same warps; spatial_hflip /
-    spatial_vflip allow drawn flips, spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  photo=,
-    stats= and pyramid= then work on the WARPED planes; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and
-    frame 1, a b c d e g each, then padding).  crop= with spatial= raises - the spatial step contains the window -, and so
-    does objects=True: its boxes are of the unwarped frame.
-    pack=dict(image_dtype=, flow_dtype=, layout=, concat=, rgb=, scale=, bias=, flow_scale=) (every key optional: alloc_pack and
-    Generator.pack): the frames and the flow of every batch are packed for the network into a further ring of buffers
-    (Generator.pack, enqueued on the same internal stream as the LAST step of the batch: behind crop / spatial and photo, on
-    their outputs; stats= and pyramid= keep reading the unpacked, unscaled flow).  The loader then yields the packed tensors in
-    the places of image0, image1 and flow - with concat the 6-channel tensor first and None second -; extras, objects, stats
-    and pyramid are untouched.  The pyramid's levels, labels and occlusion maps are not packed.
+    per sample into an out_h x out_w window (Generator.spatial; spatial_hflip / spatial_vflip allow drawn flips,
+    spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  The loader yields the warped tensors and
+    extras; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and frame 1, a b c d e g each, then padding).
+    Raises without spatial_size= and with crop=: the spatial step contains the window.
+    photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
+    holds "photo" (float32 [n,16], the records used).
+    erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
+    takes them): occluder rectangles are painted into the frames and the occlusion maps among extras= extended; the dict also
+    holds "erase" (int32 [n,24], the records used: erase_numpy).  mark_occ=True needs a map among extras=; marking occ1 for
+    rectangles of frame 0 needs "flow1" there.
+    objects=True (needs "label0" and "label1" among extras=): the per-object annotation table (Generator.object_table); the
+    dict also holds "objects" (uint8 [n, 65, 96], see object_table_numpy) and "object_counts" (int32 [n]).  Raises with crop=
+    and with spatial=: its boxes are of the uncropped, unwarped frame.
+    stats=True: the flow statistics (Generator.flow_stats with bin_px=stats_bin_px; with "occ0" among extras= the map is
+    passed); the dict also holds "flow_stats" (uint8 [n, 304], see flow_stats_numpy).
+    pyramid=L: the flow pyramid (Generator.flow_pyramid with levels=L, scale=pyramid_scale, in the flow's dtype; with "occ0"
+    among extras= the map is passed); the dict also holds "flow_pyramid" (the list of L tensors [n,2,H>>k,W>>k]) and, with
+    pyramid_weights=True, "flow_pyramid_weights" (the list of uint16 [n,1,H>>k,W>>k]).
     boundaries=dict(radius=, min_step=, labels=, frames=, edge=, dist=) (every key optional: radius 10, min_step 0, labels None -
     used when the frame's label plane is among extras= -, frames (0,), edge and dist True): the motion-boundary masks and the
-    distance-to-boundary maps of every batch (Generator.boundaries into a further ring of buffers, enqueued on the same
-    internal stream behind the batch - behind crop / spatial, on their flow and label planes -, ahead of the pack; the
-    photometric step does not touch what it reads).  Every batch is then (image0, image1, flow, {...}) and the dict also holds
-    "edge0" and "dist0" (uint8 [n,1,H,W]), and "edge1" and "dist1" when frame 1 is asked, as far as edge / dist ask for them.
-    labels=True needs "label0" ("label1" for frame 1) among extras=, frame 1 needs "flow1" there, and labels=False needs an
-    explicit min_step > 0: without labels a min_step of 0 marks every pixel whose flow differs from a neighbour's at all.
-    erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
-    takes them): occluder rectangles are painted into the frames of every batch in place and the occlusion maps among extras=
-    extended (Generator.erase, enqueued on the same internal stream behind crop / spatial and behind photo, on their planes,
-    and ahead of stats=, pyramid=, boundaries= and pack=, so the reductions see the extended occ0; records drawn from the
-    context's seed and the batch's first global index).  Every batch is then (image0, image1, flow, {...}) and the dict also
-    holds "erase" (int32 [n,24], the records used: erase_numpy).  mark_occ=True needs a map among extras=; marking occ1 for
-    rectangles of frame 0 needs "flow1" there.  Labels, the object table and the boundary planes stay those of the un-erased
-    sample."""
+    distance-to-boundary maps (Generator.boundaries); the dict also holds "edge0" and "dist0" (uint8 [n,1,H,W]), and "edge1"
+    and "dist1" when frame 1 is asked, as far as edge / dist ask for them.  labels=True needs "label0" ("label1" for frame 1)
+    among extras=, frame 1 needs "flow1" there, and labels=False needs an explicit min_step > 0: without labels a min_step of
+    0 marks every pixel whose flow differs from a neighbour's at all.
+    pack=dict(image_dtype=, flow_dtype=, layout=, concat=, rgb=, scale=, bias=, flow_scale=) (every key optional: alloc_pack and
+    Generator.pack): the frames and the flow are packed for the network.  The loader yields the packed tensors in the places
+    of image0, image1 and flow - with concat the 6-channel tensor first and None second -; the dict is untouched: the
+    pyramid's levels, labels and occlusion maps are not packed."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
@@ -2355,53 +2382,58 @@ class FlowLoader:
         self.start = int(start)
         self.prefetch = max(2, int(prefetch))
         self.consumer = torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(int(stream))
-        self.bufs = [alloc_outputs(p.batch_size, p.height, p.width, image_dtype=image_dtype, flow_dtype=flow_dtype)
-                     for _ in range(self.prefetch)]
         self.extras = tuple(extras) if extras is not None else None
-        xfmt = dict(flow_dtype=flow_dtype, occ_dtype=torch.uint8) if extras_compact else {}
-        self.xbufs = [alloc_extras(p.batch_size, p.height, p.width, self.extras, **xfmt) if self.extras is not None else None
-                      for _ in range(self.prefetch)]
-        self.obufs = [alloc_object_table(p.batch_size) if objects else None for _ in range(self.prefetch)]
-        self.sbufs = [alloc_flow_stats(p.batch_size) if stats else None for _ in range(self.prefetch)]
         self.stats_bin_px = float(stats_bin_px)
         self.pyramid, self.pyramid_scale = int(pyramid), bool(pyramid_scale)
         self.crop = None if crop is None else (int(crop[0]), int(crop[1]))
         self.crop_flips, self.crop_occ_window = (bool(crop_hflip), bool(crop_vflip)), bool(crop_occ_window)
-        self.cbufs = [None] * self.prefetch     # (cropped planes by name, records) of each set
-        if self.crop is not None:
-            for j in range(self.prefetch):
-                planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
-                # (not filled: the crop writes every element and every record, and a fill on torch's stream would not be ordered
-                # against the internal stream the first crops run on)
-                self.cbufs[j] = (alloc_crop(planes, *self.crop, zero=False), torch.empty((p.batch_size, 4), dtype=torch.int32, device="cuda"))
-                crop_format(planes, self.cbufs[j][0], p.height, p.width)  # (raises for a window the frame does not allow)
         self.spatial_flags = (bool(spatial_hflip), bool(spatial_vflip), bool(spatial_occ_window))
-        if self.spatial is not None:            # the warped planes and their records take the crop's place: the same second ring
-            self.crop = (int(spatial_size[0]), int(spatial_size[1]))
-            for j in range(self.prefetch):
-                planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
-                self.cbufs[j] = (alloc_spatial(planes, *self.crop, zero=False),
-                                 torch.empty((p.batch_size, SPATIAL_REC_DOUBLES), dtype=torch.float64, device="cuda"))
-                spatial_format(planes, self.cbufs[j][0], p.height, p.width)  # (raises for a size the rule does not allow)
-        ph, pw = self.crop if self.crop is not None else (p.height, p.width)
-        self.pbufs = [alloc_flow_pyramid(p.batch_size, ph, pw, self.pyramid, flow_dtype, bool(pyramid_weights))
-                      if self.pyramid else None for _ in range(self.prefetch)]
-        # (not filled: the augmentation writes every record; see the crop's buffers above)
-        self.rbufs = [torch.empty((p.batch_size, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
-                      for _ in range(self.prefetch)]
-        # (not filled: the pack writes every element; see the crop's buffers above)
-        self.kbufs = [None if self.pack is None else
-                      alloc_pack(p.batch_size, ph, pw, image_dtype=self.pack.get("image_dtype"), flow_dtype=self.pack.get("flow_dtype"),
-                                 layout=self.pack.get("layout", PACK_NCHW), concat=bool(self.pack.get("concat", False)), zero=False)
-                      for _ in range(self.prefetch)]
-        # (not filled: the call writes every element; see the crop's buffers above)
-        self.ebufs = [None if self.boundaries is None else
-                      alloc_boundaries(p.batch_size, ph, pw, frames=self.boundaries["frames"], edge=self.boundaries["edge"],
-                                       dist=self.boundaries["dist"], zero=False) for _ in range(self.prefetch)]
-        # (not filled: the call clears the workspace on its stream and writes every record)
-        self.wbufs = [None if self.erase is None else alloc_erase(p.batch_size) for _ in range(self.prefetch)]
-        self.ready = [torch.cuda.Event() for _ in range(self.prefetch)]      # batch rendered (internal stream)
-        self.released = [None] * self.prefetch                               # consumer done with the set
+        # (height, width) of the planes behind stage 2, None: the frame's
+        self.window = self.crop if self.spatial is None else (int(spatial_size[0]), int(spatial_size[1]))
+        xfmt = dict(flow_dtype=flow_dtype, occ_dtype=torch.uint8) if extras_compact else {}
+        n, (ph, pw) = p.batch_size, self.window or (p.height, p.width)
+
+        def slot():
+            t = _RingSlot()
+            t.outs = alloc_outputs(n, p.height, p.width, image_dtype=image_dtype, flow_dtype=flow_dtype)
+            t.extras = alloc_extras(n, p.height, p.width, self.extras, **xfmt) if self.extras is not None else None
+            t.frame = t.planes = dict(zip(PACK_PLANES, t.outs), **(t.extras or {}))
+            # Behind forward's buffers nothing is filled where the stage writes every element and every record itself (the eraser
+            # clears its workspace on its stream): a fill on torch's stream would not be ordered against the internal stream the
+            # first batches run on.
+            t.window_recs = None
+            if self.spatial is not None:
+                t.planes = alloc_spatial(t.frame, ph, pw, zero=False)
+                t.window_recs = torch.empty((n, SPATIAL_REC_DOUBLES), dtype=torch.float64, device="cuda")
+                spatial_format(t.frame, t.planes, p.height, p.width)  # (raises for a size the rule does not allow)
+            elif self.crop is not None:
+                t.planes = alloc_crop(t.frame, ph, pw, zero=False)
+                t.window_recs = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+                crop_format(t.frame, t.planes, p.height, p.width)  # (raises for a window the frame does not allow)
+            t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
+            t.erase = alloc_erase(n) if self.erase is not None else None
+            t.objects = alloc_object_table(n) if objects else None
+            t.stats = alloc_flow_stats(n) if stats else None
+            t.pyramid = alloc_flow_pyramid(n, ph, pw, self.pyramid, flow_dtype, bool(pyramid_weights)) if self.pyramid else None
+            t.edges = t.edge_args = t.packed = None
+            if self.boundaries is not None:
+                o = self.boundaries
+                t.edges = alloc_boundaries(n, ph, pw, frames=o["frames"], edge=o["edge"], dist=o["dist"], zero=False)
+                t.edge_args = dict(flow=None)
+                for f in o["frames"]:
+                    tag = "1" if f else ""
+                    t.edge_args.update({"flow" + tag: t.planes["flow" + tag], "edge" + tag: t.edges.get("edge%d" % f),
+                                        "dist2_1" if f else "dist2": t.edges.get("dist%d" % f),
+                                        "label" + tag: t.planes["label%d" % f] if o["labels"] else None})
+            if self.pack is not None:
+                o = self.pack
+                t.packed = alloc_pack(n, ph, pw, image_dtype=o.get("image_dtype"), flow_dtype=o.get("flow_dtype"),
+                                      layout=o.get("layout", PACK_NCHW), concat=bool(o.get("concat", False)), zero=False)
+            t.ready, t.released = torch.cuda.Event(), None
+            t.batch = self._batch(t)
+            return t
+
+        self.slots = [slot() for _ in range(self.prefetch)]
         self.k = 0
         for j in range(self.prefetch - 1):      # fill the ring
             self._enqueue(j)
@@ -2455,105 +2487,72 @@ class FlowLoader:
             raise ValueError("erase= marks the rectangles of frame 0 into occ1 through flow1: extras= must contain \"flow1\"")
         return {k: v for k, v in erase.items() if k in ERASE_RANGES}, o
 
-    def _enqueue_erase(self, j, planes, s, step, size):
-        """The rectangles of batch `step` into the frames and maps among `planes` (by name) of set j on stream s, in place, when
-        the loader makes them."""
+    def _enqueue(self, j):
+        """The next batch into set j: the stages of the class docstring, in its order, on the stream next_stream() gives."""
+        import torch
+        t, g, p = self.slots[j], self.gen, self.gen.params
+        s = g.next_stream()
+        chain = torch.cuda.ExternalStream(s)
+        if t.released is not None:
+            chain.wait_event(t.released)
+        first = 0                               # the first global index of the batch forward is about to render ...
+        if self.window is not None or self.photo is not None or self.erase is not None:  # ... for the stages that draw records
+            first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
+        g.forward(*t.outs, s, extras=t.extras)
+        planes, size = t.planes, self.window
+        if self.spatial is not None:
+            hflip, vflip, occ_window = self.spatial_flags
+            g.spatial(t.frame, planes, first_index=first, ranges=self.spatial, hflip=hflip, vflip=vflip, occ_window=occ_window,
+                      recs_out=t.window_recs, stream=s)
+        elif self.crop is not None:
+            g.crop(t.frame, planes, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
+                   recs_out=t.window_recs, stream=s)
+        if self.photo is not None:
+            g.photo((planes["image0"], planes["image1"]), recs_out=t.photo, first_index=first, ranges=self.photo, stream=s, size=size)
         if self.erase is not None:
             ranges, o = self.erase
-            p = self.gen.params
-            work, recs = self.wbufs[j]
-            self.gen.erase((planes["image0"], planes["image1"]), occ=(planes.get("occ0"), planes.get("occ1")) if o["mark_occ"] else None,
-                           flow=(planes["flow"], planes.get("flow1")), first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank),
-                           ranges=ranges, fill=o["fill"], color=o["color"], frames=o["frames"], mark_occ=o["mark_occ"], recs_out=recs, stream=s,
-                           size=size, work=work)
-
-    def _enqueue_boundaries(self, j, planes, s, size):
-        """The boundary planes of set j from the flows and labels among `planes` (by name) on stream s, when the loader makes them."""
+            work, recs = t.erase
+            g.erase((planes["image0"], planes["image1"]), occ=(planes.get("occ0"), planes.get("occ1")) if o["mark_occ"] else None,
+                    flow=(planes["flow"], planes.get("flow1")), first_index=first, ranges=ranges, fill=o["fill"], color=o["color"],
+                    frames=o["frames"], mark_occ=o["mark_occ"], recs_out=recs, stream=s, size=size, work=work)
+        if t.objects is not None:               # (only without a window: of the frame's own label planes)
+            g.object_table(t.extras["label0"], t.extras["label1"], *t.objects, stream=s)
+        if t.stats is not None:
+            g.flow_stats(planes["flow"], t.stats, occ=planes.get("occ0"), bin_px=self.stats_bin_px, stream=s, size=size)
+        if t.pyramid is not None:
+            g.flow_pyramid(planes["flow"], self.pyramid, occ=planes.get("occ0"), scale=self.pyramid_scale, out=t.pyramid, stream=s, size=size)
         if self.boundaries is not None:
-            o, out = self.boundaries, self.ebufs[j]
-            args = {}
-            for f in o["frames"]:
-                tag = "1" if f else ""
-                args["flow" + tag] = planes["flow" + tag]
-                args["edge" + tag], args["dist2_1" if f else "dist2"] = out.get("edge%d" % f), out.get("dist%d" % f)
-                args["label" + tag] = planes["label%d" % f] if o["labels"] else None
-            args.setdefault("flow", None)
-            self.gen.boundaries(radius=o["radius"], min_step=o["min_step"], labels=o["labels"], stream=s, size=size, **args)
-
-    def _enqueue(self, j):
-        import torch
-        s = self.gen.next_stream()
-        chain = torch.cuda.ExternalStream(s)
-        if self.released[j] is not None:
-            chain.wait_event(self.released[j])
-        step = self.gen.step if self.crop is not None or self.photo is not None or self.erase is not None else 0
-        self.gen.forward(*self.bufs[j], s, extras=self.xbufs[j])
-        if self.crop is not None:
-            return self._enqueue_cropped(j, s, chain, step)
-        self._enqueue_photo(j, self.bufs[j][:2], s, step, None)
-        self._enqueue_erase(j, dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {})), s, step, None)
-        if self.obufs[j] is not None:
-            self.gen.object_table(self.xbufs[j]["label0"], self.xbufs[j]["label1"], *self.obufs[j], stream=s)
-        self._enqueue_reductions(j, self.bufs[j][2], (self.xbufs[j] or {}).get("occ0"), s, None)
-        self._enqueue_boundaries(j, dict(self.xbufs[j] or {}, flow=self.bufs[j][2]), s, None)
-        self._enqueue_pack(j, self.bufs[j], s, None)
-        self.ready[j].record(chain)
-
-    def _enqueue_cropped(self, j, s, chain, step):
-        """The window of batch `step` (just enqueued into set j on stream s), then the reductions on the cropped planes."""
-        p = self.gen.params
-        planes = dict(zip(("image0", "image1", "flow"), self.bufs[j]), **(self.xbufs[j] or {}))
-        out, recs = self.cbufs[j]
-        first = shard_first_index(step, p.batch_size, p.world_size, p.rank)
-        if self.spatial is not None:
-            self.gen.spatial(planes, out, first_index=first, ranges=self.spatial, hflip=self.spatial_flags[0], vflip=self.spatial_flags[1],
-                             occ_window=self.spatial_flags[2], recs_out=recs, stream=s)
-        else:
-            self.gen.crop(planes, out, first_index=first, hflip=self.crop_flips[0],
-                          vflip=self.crop_flips[1], occ_window=self.crop_occ_window, recs_out=recs, stream=s)
-        self._enqueue_photo(j, (out["image0"], out["image1"]), s, step, self.crop)
-        self._enqueue_erase(j, out, s, step, self.crop)
-        self._enqueue_reductions(j, out["flow"], out.get("occ0"), s, self.crop)
-        self._enqueue_boundaries(j, out, s, self.crop)
-        self._enqueue_pack(j, (out["image0"], out["image1"], out["flow"]), s, self.crop)
-        self.ready[j].record(chain)
-
-    def _enqueue_photo(self, j, frames, s, step, size):
-        """The augmentation of the frames of batch `step` (set j, on stream s) in place, when the loader makes one."""
-        if self.photo is not None:
-            p = self.gen.params
-            self.gen.photo(frames, recs_out=self.rbufs[j], first_index=shard_first_index(step, p.batch_size, p.world_size, p.rank),
-                           ranges=self.photo, stream=s, size=size)
-
-    def _enqueue_pack(self, j, planes, s, size):
-        """The packing of (image0, image1, flow) of set j into its packed buffers on stream s, when the loader makes one."""
+            o = self.boundaries
+            g.boundaries(radius=o["radius"], min_step=o["min_step"], labels=o["labels"], stream=s, size=size, **t.edge_args)
         if self.pack is not None:
             o = self.pack
-            self.gen.pack(dict(zip(PACK_PLANES, planes)), self.kbufs[j], scale=o.get("scale", (1.0, 1.0, 1.0)), bias=o.get("bias", (0.0, 0.0, 0.0)),
-                          flow_scale=o.get("flow_scale", 1.0), layout=o.get("layout", PACK_NCHW), concat=bool(o.get("concat", False)),
-                          rgb=bool(o.get("rgb", False)), stream=s, size=size)
+            g.pack({k: planes[k] for k in PACK_PLANES}, t.packed, scale=o.get("scale", (1.0, 1.0, 1.0)), bias=o.get("bias", (0.0, 0.0, 0.0)),
+                   flow_scale=o.get("flow_scale", 1.0), layout=o.get("layout", PACK_NCHW), concat=bool(o.get("concat", False)),
+                   rgb=bool(o.get("rgb", False)), stream=s, size=size)
+        t.ready.record(chain)
 
-    def _enqueue_reductions(self, j, flow, occ, s, size):
-        """The statistics and the pyramid of set j, as far as the loader makes them, of a flow and its map (None: no map) of
-        size=(height, width) (None: the frame) on stream s."""
-        if self.sbufs[j] is not None:
-            self.gen.flow_stats(flow, self.sbufs[j], occ=occ, bin_px=self.stats_bin_px, stream=s, size=size)
-        if self.pbufs[j] is not None:
-            self.gen.flow_pyramid(flow, self.pyramid, occ=occ, scale=self.pyramid_scale, out=self.pbufs[j], stream=s, size=size)
-
-    def _add_reductions(self, more, j):
-        """the statistics, the pyramid, the boundary planes and the eraser's records of set j into the batch's dict"""
-        if self.sbufs[j] is not None:
-            more["flow_stats"] = self.sbufs[j]
-        if self.pbufs[j] is not None:
-            if isinstance(self.pbufs[j], tuple):
-                more["flow_pyramid"], more["flow_pyramid_weights"] = self.pbufs[j]
-            else:
-                more["flow_pyramid"] = self.pbufs[j]
-        if self.ebufs[j] is not None:
-            more.update(self.ebufs[j])
-        if self.wbufs[j] is not None:
-            more["erase"] = self.wbufs[j][1]
+    def _batch(self, t):
+        """What slot t hands out: (image0, image1, flow) - the packed tensors when there are any, None for image1 with concat -
+        and, unless it would be empty and there is no extras= either, the dict of everything else its stages write."""
+        more = {k: v for k, v in t.planes.items() if k not in PACK_PLANES}
+        if t.window_recs is not None:
+            more["spatial" if self.spatial is not None else "crop"] = t.window_recs
+        if t.photo is not None:
+            more["photo"] = t.photo
+        if t.objects is not None:
+            more["objects"], more["object_counts"] = t.objects
+        if t.stats is not None:
+            more["flow_stats"] = t.stats
+        if isinstance(t.pyramid, tuple):
+            more["flow_pyramid"], more["flow_pyramid_weights"] = t.pyramid
+        elif t.pyramid is not None:
+            more["flow_pyramid"] = t.pyramid
+        if t.edges is not None:
+            more.update(t.edges)
+        if t.erase is not None:
+            more["erase"] = t.erase[1]
+        top = t.planes if t.packed is None else t.packed
+        return (top["image0"], top.get("image1"), top["flow"]) + ((more,) if more or self.extras is not None else ())
 
     @property
     def consumed(self):
@@ -2566,44 +2565,19 @@ class FlowLoader:
     def __next__(self):
         import torch
         j = self.k % self.prefetch
-        self.consumer.wait_event(self.ready[j])
+        self.consumer.wait_event(self.slots[j].ready)
         # the set handed out last time is free once the consumer work enqueued so far is done: render the
         # batch that will be consumed prefetch-1 iterations from now into it
         f = self.head % self.prefetch
         if f != j:
             ev = torch.cuda.Event()
             ev.record(self.consumer)
-            self.released[f] = ev
+            self.slots[f].released = ev
             self._enqueue(f)
             self.head += 1
         self.k += 1
-        batch = self._batch(j)
-        if self.kbufs[j] is not None:
-            k = self.kbufs[j]
-            batch = (k["image0"], k.get("image1"), k["flow"]) + tuple(batch[3:])
-        return batch
-
-    def _batch(self, j):
-        """what set j hands out, before the packed tensors take the places of image0, image1 and flow"""
-        if self.crop is not None:
-            out, recs = self.cbufs[j]
-            more = {k: v for k, v in out.items() if k not in ("image0", "image1", "flow")}
-            more["spatial" if self.spatial is not None else "crop"] = recs
-            if self.rbufs[j] is not None:
-                more["photo"] = self.rbufs[j]
-            self._add_reductions(more, j)
-            return (out["image0"], out["image1"], out["flow"], more)
-        if self.obufs[j] is not None or self.sbufs[j] is not None or self.pbufs[j] is not None or self.rbufs[j] is not None or self.ebufs[j] is not None or self.wbufs[j] is not None:
-            more = dict(self.xbufs[j]) if self.xbufs[j] is not None else {}
-            if self.rbufs[j] is not None:
-                more["photo"] = self.rbufs[j]
-            if self.obufs[j] is not None:
-                more.update(objects=self.obufs[j][0], object_counts=self.obufs[j][1])
-            self._add_reductions(more, j)
-            return self.bufs[j] + (more,)
-        if self.extras is not None:
-            return self.bufs[j] + (self.xbufs[j],)
-        return self.bufs[j]
+        batch = self.slots[j].batch
+        return batch if len(batch) == 3 else batch[:3] + (dict(batch[3]),)  # (a dict of the caller's own)
 
 
 def _as_tensor(ptr, shape):
