@@ -1004,6 +1004,93 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
  * height outside 1..32768, no frame flag, unknown flag bits or a range that breaks the rules above. */
 int ofdg_erase_draw(uint32_t seed, long long index, int width, int height, const struct ofdg_erase_job* ranges, ofdg_erase_rec* out);
 
+/*
+ * Motion blur: every pixel of image0 and / or image1 becomes a weighted mean of its frame along a short segment through the
+ * pixel, whose direction and length are the pixel's own flow times the sample's shutter - the fraction of the inter-frame
+ * interval the exposure lasts.  The exposure is centred on the frame's instant, so the segment is symmetric about the pixel
+ * and the sign of the flow does not matter: flow1 serves frame 1 as it is.  Flow, occlusion maps and labels are not touched:
+ * the ground truth is the motion of the sharp frames.  NOT in place (a pixel reads its neighbours).  The record is a pure
+ * function of (seed, global sample index), so a resumed or sharded run makes the same pixels.  Everything is integers once
+ * the half-displacement is rounded: the kernel, ofdg_host_motion_blur and the numpy restatement of the tests give the same
+ * bytes.  fl32(.) marks a float32 rounding (no contraction).
+ *
+ * Planes: src[f] and dst[f] are image f as [n,3,height,width] of src_fmt / dst_fmt (OFDG_FMT_F32 or OFDG_FMT_U8, chosen
+ * independently; float32 frames hold byte values, see ofdg_photo); flow[f] is [n,2,height,width] of flow_fmt (OFDG_FMT_F32 or
+ * OFDG_FMT_F16), read only: flow[0] the forward flow, flow[1] flow1.  A frame is absent (src[f], dst[f], flow[f] all NULL) or
+ * complete (all three set).  width = height = 0: the context's frame; otherwise any size the context's rule allows, as in
+ * ofdg_photo.  Mode 9 has no flow1: there only frame 0 can be blurred.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_motion_blur_draw(seed, first_index + i, the job).  Either way it
+ * is sanitised before use, and the sanitised record is what recs_out[i] receives.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, {seed ^ (uint32)(g >> 32) *
+ *    0x9E3779B9, (uint32)g}, block 0 at the counter {0, 0, 0x0c76, 0} (taken: 0x0fd9 the sampler, 0x0c70 crop, 0x0c71 and 0x0c72
+ *    photo, 0x0c73 spatial, 0x0c74 and 0x0c75 erase).  u(w) and sym(w, a) are ofdg_photo's.  on = u(.x) < prob;
+ *    s0 = fl32(shutter_min + fl32(fl32(shutter_max - shutter_min) * u(.y)));  s1 = fl32(s0 + sym(.z, pair_shutter)).
+ *    shutter = {s0, s1}; without `on` both are +0.  reserved = 0.  (.w is not used.)
+ * 2. Sanitise, per frame: a NaN becomes 0, a value below 0 becomes 0 (-0.0 becomes +0), a value above OFDG_MBLUR_MAX_SHUTTER
+ *    (2) becomes 2.  reserved = 0.
+ * 3. Pixel (x, y) of frame f, s = shutter[f]:
+ *    a. Half-displacement in 24.8.  (u, v) = the element of flow[f] widened to float32.  When u or v is not finite, Dx = Dy =
+ *       0.  Otherwise Dx = (int)rintf(clamp(fl32(fl32(u * s) * 128.0f), -8192.0f, 8192.0f)), Dy likewise from v (ties to
+ *       even; each component clamped on its own: a streak is at most 64 px long, OFDG_MBLUR_MAX_HALF_PX 32 each way).
+ *    b. Taps.  L = max(|Dx|, |Dy|);  m = min(taps_side, (L + 255) >> 8) - one tap per pixel of half-extent on the major axis,
+ *       no gaps until the cap taps_side (1..OFDG_MBLUR_MAX_TAPS_SIDE);  N = 2 m + 1.  For m > 0:  sx = (int)rintf(fl32((float)Dx
+ *       / (float)m)), sy likewise (IEEE division).  Taps k = -m..m at Qx = clamp(256 x + k sx, 0, 256 (width - 1)), Qy =
+ *       clamp(256 y + k sy, 0, 256 (height - 1)): a streak that leaves the frame repeats the border.
+ *    c. Tap value, per channel.  The byte of an element: itself for uint8; for float32 the index rule of ofdg_photo (clamped
+ *       to [0, 255], a NaN becomes 0, then rintf).  ix = Qx >> 8, fx = Qx & 255, iy and fy likewise; e00, e10, e01, e11 the
+ *       bytes at (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1), each index clamped into the plane as ofdg_spatial
+ *       does.  T = (256 - fx)(256 - fy) e00 + fx (256 - fy) e10 + (256 - fx) fy e01 + fx fy e11, an integer;  t = (T + 128)
+ *       >> 8.
+ *    d. Mean.  w = 65536 / N by integer division; the centre tap weighs 65536 - 2 m w, every other tap w.  S = the sum of
+ *       weight_k * t_k (below 2^32 - 2^23: uint32 suffices).  b = (S + 2^23) >> 24.  A uint8 destination stores b, a float32
+ *       one (float)b.  m = 0 gives the source byte: zero shutter, zero or non-finite flow, a sample the draw left out.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel for any
+ * n and both frames; no atomics.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, a size that
+ * breaks the rule above, 3 * width * height of 2^32 and more, another format code, non-zero flags or reserved, taps_side
+ * outside 1..16, an incomplete frame or no frame at all, - when recs is NULL, as in ofdg_erase - prob outside [0, 1] or NaN,
+ * shutter_min or shutter_max negative, NaN, infinite or above 2, shutter_min > shutter_max, pair_shutter negative, NaN or
+ * infinite; a misaligned pointer (sources and flows as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8;
+ * destinations and both record arrays 16-byte), a destination range (dst[f], recs_out) that overlaps any other range of the
+ * job, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: layered blur at occlusion boundaries (a pixel is smeared along its own motion only, so a moving object does
+ * not bleed over a still background), blur of the ground-truth planes, an in-place form, frame 1 in mode 9, streaks above
+ * 64 px.
+ */
+#define OFDG_MBLUR_MAX_SHUTTER 2.0f
+#define OFDG_MBLUR_MAX_HALF_PX 32      /* |Dx|, |Dy| <= 256 * 32 */
+#define OFDG_MBLUR_MAX_TAPS_SIDE 16
+typedef struct ofdg_mblur_rec {        /* 16 bytes */
+  float   shutter[2];                  /* [frame], 0..OFDG_MBLUR_MAX_SHUTTER */
+  int32_t reserved[2];
+} ofdg_mblur_rec;
+struct ofdg_mblur_job {                /* 128 bytes */
+  const void* src[2];                  /* [n,3,height,width] of src_fmt: image0, image1, or NULL */
+  void*       dst[2];                  /* [n,3,height,width] of dst_fmt */
+  const void* flow[2];                 /* [n,2,height,width] of flow_fmt: flow, flow1 */
+  const ofdg_mblur_rec* recs;          /* DEVICE, n records, or NULL: drawn */
+  ofdg_mblur_rec*       recs_out;      /* DEVICE, n records, or NULL */
+  long long first_index; uint32_t seed;
+  int32_t width, height;               /* 0, 0: the context's frame */
+  int32_t src_fmt, dst_fmt, flow_fmt, flags, taps_side;
+  float   prob, shutter_min, shutter_max, pair_shutter;   /* ranges of the draw */
+  int32_t reserved[2];
+};
+int ofdg_motion_blur(ofdg_ctx* ctx, const struct ofdg_mblur_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and records in host memory, no alignment asked of any
+ * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (step 1 alone: not sanitised; pure, no GPU).  Of `ranges` only prob, shutter_min,
+ * shutter_max and pair_shutter are read.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer or a range
+ * that breaks the rules above. */
+int ofdg_motion_blur_draw(uint32_t seed, long long index, const struct ofdg_mblur_job* ranges, ofdg_mblur_rec* out);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -111,6 +111,7 @@ EXPORTS = [
     "ofdg_pack", "ofdg_host_pack",
     "ofdg_boundaries", "ofdg_host_boundaries",
     "ofdg_erase", "ofdg_host_erase", "ofdg_erase_draw",
+    "ofdg_motion_blur", "ofdg_host_motion_blur", "ofdg_motion_blur_draw",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1090,6 +1091,129 @@ def host_erase(images, occ=None, flow=None, recs=None, first_index=0, seed=0, ra
     return used
 
 
+# motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
+MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
+MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
+MBLUR_MAX_TAPS_SIDE = 16   # OFDG_MBLUR_MAX_TAPS_SIDE
+MBLUR_REC_FLOATS = 4       # a record as float32 [4]: shutter[2], then the two reserved words
+MBLUR_RANGES = ("prob", "shutter_min", "shutter_max", "pair_shutter")
+# A starting point: every second sample is blurred, its exposure up to half the inter-frame interval (a 180-degree shutter),
+# frame 1 within a tenth of frame 0, eight taps either side of the pixel (no gaps up to a half-extent of 8 px).  Not a tuned
+# recipe: every field is a range to be chosen per data set.  (taps_side is no range of the draw: Generator.motion_blur,
+# host_motion_blur and FlowLoader take it from the dict when their own argument is None.)
+MBLUR_DEFAULT = dict(prob=0.5, shutter_min=0.0, shutter_max=0.5, pair_shutter=0.1, taps_side=8)
+
+
+class MblurRec(C.Structure):
+    """ofdg_mblur_rec: the shutters of one sample (16 bytes)."""
+    _fields_ = [("shutter", C.c_float * 2), ("reserved", C.c_int32 * 2)]
+
+
+class MblurJob(C.Structure):
+    """struct ofdg_mblur_job (128 bytes)."""
+    _fields_ = [("src", C.c_void_p * 2), ("dst", C.c_void_p * 2), ("flow", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flow_fmt", C.c_int32), ("flags", C.c_int32), ("taps_side", C.c_int32)] + \
+               [(name, C.c_float) for name in MBLUR_RANGES] + [("reserved", C.c_int32 * 2)]
+
+
+def _mblur_ranges(job, ranges, taps_side=None):
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in MBLUR_RANGES and key != "taps_side":
+            raise ValueError("unknown range %r (known: %s, and taps_side)" % (key, ", ".join(MBLUR_RANGES)))
+    for key in MBLUR_RANGES:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    job.taps_side = int(ranges.get("taps_side", MBLUR_DEFAULT["taps_side"]) if taps_side is None else taps_side)
+    return job
+
+
+def motion_blur_format(images, out, flow, height=None, width=None):
+    """(n, height, width, src code, dst code, flow code) of the planes of Generator.motion_blur / host_motion_blur: images, out
+    and flow are pairs - (image0, image1), the frames to write, (flow, flow1) -; frame f is None in all three or set in all
+    three.  A frame is float32 or uint8 [n,3,height,width], one dtype for images and one for out; a flow float32 or float16
+    [n,2,height,width], one dtype.  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors
+    and numpy arrays)."""
+    if images is None or out is None or flow is None or len(images) != 2 or len(out) != 2 or len(flow) != 2:
+        raise ValueError("images, out and flow must be pairs (frame 0, frame 1)")
+    if all(t is None for t in images):
+        raise ValueError("images must hold at least one frame")
+    for f in range(2):
+        if len({images[f] is None, out[f] is None, flow[f] is None}) != 1:
+            raise ValueError("frame %d must be set in images, out and flow, or in none of them%s"
+                             % (f, " (without flow1 only frame 0 can be blurred)" if f and flow[f] is None else ""))
+    shape = next(tuple(t.shape) for t in images if t is not None)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 3 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a frame must be [n,3,%s,%s], got %s" % (height or "height", width or "width", shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    codes = []
+    for what, pair, table, ch in (("images", images, _IMAGE_CODES, 3), ("out", out, _IMAGE_CODES, 3), ("flow", flow, _FLOW_CODES, 2)):
+        names = set()
+        for f, t in enumerate(pair):
+            if t is not None:
+                _check_plane("%s[%d]" % (what, f), t, tuple(table), (n, ch, height, width))
+                names.add(_dtype_name(t))
+        if len(names) > 1:
+            raise ValueError("%s must have one dtype for both frames, got %s" % (what, sorted(names)))
+        codes.append(table[names.pop()])
+    return (n, height, width) + tuple(codes)
+
+
+def _mblur_job(images, out, flow, ptr, codes, size, recs, recs_out, first_index, seed, ranges, taps_side):
+    job = _mblur_ranges(MblurJob(), ranges, taps_side)
+    for f in range(2):
+        if images[f] is not None:
+            job.src[f], job.dst[f], job.flow[f] = ptr(images[f]), ptr(out[f]), ptr(flow[f])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt, job.flow_fmt = codes
+    return job
+
+
+def motion_blur_draw(seed, index, ranges=None):
+    """ofdg_motion_blur_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (MBLUR_RANGES;
+    a missing one is 0), before sanitising, as float32 [4] (MBLUR_REC_FLOATS): shutter of frame 0, of frame 1, 0, 0."""
+    import numpy as np
+    out = MblurRec()
+    job = _mblur_ranges(MblurJob(), ranges)
+    _host_check(lib().ofdg_motion_blur_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return np.frombuffer(bytearray(out), np.float32).copy()
+
+
+def alloc_motion_blur(n, height, width, image_dtype=None, frames=(0, 1), device="cuda"):
+    """((out0, out1), recs) of Generator.motion_blur for n samples: the frames to write - [n,3,height,width] of image_dtype
+    (default torch.float32), None for a frame not among `frames` - and the float32 [n,4] records (recs_out).  Not filled: the
+    call writes every element and every record."""
+    import torch
+    dt = torch.float32 if image_dtype is None else image_dtype
+    return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if f in frames else None for f in range(2)),
+            torch.empty((n, MBLUR_REC_FLOATS), dtype=torch.float32, device=device))
+
+
+def host_motion_blur(images, flow, recs=None, first_index=0, seed=0, ranges=None, taps_side=None, dst_dtype=None):
+    """ofdg_host_motion_blur (no GPU) on numpy arrays: images the pair (image0, image1) of float32 or uint8 [n,3,H,W], flow the
+    pair (flow, flow1) of float32 or float16 [n,2,H,W]; frame f None in both or set in both.  recs None (drawn from seed,
+    first_index and ranges) or a float32 array [n,4].  dst_dtype: np.float32 / np.uint8, default the source's.  Returns
+    ((out0, out1), recs_used): the blurred arrays (None for an absent frame) and the float32 [n,4] records after sanitising."""
+    import numpy as np
+    images = tuple(None if t is None else np.ascontiguousarray(t) for t in images)
+    flow = tuple(None if t is None else np.ascontiguousarray(t) for t in flow)
+    given = [t for t in images if t is not None]
+    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
+    out = tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
+    n, height, width, *codes = motion_blur_format(images, out, flow)
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.float32 or recs.shape != (n, MBLUR_REC_FLOATS):
+            raise ValueError("recs must be float32 [%d,%d], got %s %s" % (n, MBLUR_REC_FLOATS, recs.dtype, recs.shape))
+    used = np.zeros((n, MBLUR_REC_FLOATS), np.float32)
+    job = _mblur_job(images, out, flow, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                     first_index, seed, ranges, taps_side)
+    _host_check(lib().ofdg_host_motion_blur(C.byref(job), n, width, height))
+    return out, used
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -1187,6 +1311,9 @@ def lib():
         L.ofdg_erase.argtypes = [vp, C.POINTER(EraseJob), i32, vp]
         L.ofdg_host_erase.argtypes = [C.POINTER(EraseJob), i32, i32, i32]
         L.ofdg_erase_draw.argtypes = [C.c_uint32, C.c_longlong, i32, i32, C.POINTER(EraseJob), C.POINTER(EraseRec)]
+        L.ofdg_motion_blur.argtypes = [vp, C.POINTER(MblurJob), i32, vp]
+        L.ofdg_host_motion_blur.argtypes = [C.POINTER(MblurJob), i32, i32, i32]
+        L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1646,6 +1773,31 @@ class Generator:
                          _optr(work) if fill == ERASE_MEAN else None, first_index, self._seed(seed), ranges, fill, color, frames, mark_occ)
         self._check(lib().ofdg_erase(self.h, C.byref(job), n, C.c_void_p(stream)))
         return images
+
+    def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
+                    size=None):
+        """Motion blur of both frames of a batch in one launch (ofdg_motion_blur, include/ofdg.h): every pixel becomes the mean
+        of its frame along a segment through it, the pixel's own flow times the sample's shutter long, centred on the pixel.
+        images: the pair (image0, image1) of float32 or uint8 tensors [n,3,H,W] a render / forward call (or crop, spatial)
+        wrote; out: the pair to write, float32 or uint8 independently of images (alloc_motion_blur) - there is no in-place
+        form -; flow: the pair (flow, flow1) of float32 or float16 tensors [n,2,H,W], read only.  Frame f is None in all three
+        or set in all three: without flow1 only frame 0 can be blurred.  recs: None - the record of sample i is
+        motion_blur_draw(seed, first_index + i, ranges) - or a float32 device tensor [n,4] (shutter of frame 0, of frame 1, 0,
+        0), taken as given; either is sanitised.  ranges: a dict of MBLUR_RANGES (a missing one is 0; MBLUR_DEFAULT is a
+        starting point).  taps_side: taps either side of the pixel at most, 1..16; None: ranges["taps_side"], else 8.  seed:
+        default the context's.  recs_out: None or a float32 device tensor [n,4] that receives the records used.  stream: the
+        stream the planes were written on, or STREAM_OWN.  size=(height, width): planes of that size instead of the
+        context's.  Flow, maps and labels are not touched.  Asynchronous.  Returns out."""
+        if flow is None:
+            raise ValueError("flow= is required: the pair (flow, flow1), flow1 None when only frame 0 is blurred")
+        images, out, flow = tuple(images), tuple(out), tuple(flow)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = motion_blur_format(images, out, flow, height, width)
+        self._check_recs(recs, recs_out, "float32", (n, MBLUR_REC_FLOATS))
+        job = _mblur_job(images, out, flow, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
+                         ranges, taps_side)
+        self._check(lib().ofdg_motion_blur(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return out
 
     def debug_photo_table(self, rec):
         """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
@@ -2259,8 +2411,10 @@ class _RingSlot:
     __slots__ = ("outs",         # (image0, image1, flow): what forward writes ...
                  "extras",       # ... and its extras dict (None without extras=)
                  "frame",        # both by name: the source of the window
-                 "planes",       # the planes every stage behind the window works on, by name: the window's, or `frame` itself
+                 "sharp",        # the planes the window writes, by name, or `frame` itself: what motion_blur= reads
+                 "planes",       # the planes every stage behind the blur works on, by name: `sharp`, with the blurred frames in place
                  "window_recs",  # the records of crop= / spatial=
+                 "blur",         # the records of motion_blur=
                  "objects",      # (rows, counts) of objects=True
                  "stats",        # the rows of stats=True
                  "pyramid",      # the levels of pyramid=, or (levels, weights)
@@ -2291,16 +2445,19 @@ class FlowLoader:
 
         1. forward          the frames, the flow and the extras=
         2. spatial= / crop= the window, into planes of its own: every later stage works on the window's planes and size
-        3. photo=           in place, on both frames
-        4. erase=           in place, on the frames and the occlusion maps
-        5. objects=True     the table, of the label planes of stage 1
-        6. stats=, pyramid= the reductions of flow and occ0
-        7. boundaries=      of the flows and label planes
-        8. pack=            of image0, image1 and flow, into tensors of its own
+        3. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
+                            places of image0 / image1 for every later stage and in the batch
+        4. photo=           in place, on both frames
+        5. erase=           in place, on the frames and the occlusion maps
+        6. objects=True     the table, of the label planes of stage 1
+        7. stats=, pyramid= the reductions of flow and occ0
+        8. boundaries=      of the flows and label planes
+        9. pack=            of image0, image1 and flow, into tensors of its own
 
-    So the eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
+    So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
+    eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 to 4 are drawn from the
+    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 to 5 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -2317,6 +2474,11 @@ class FlowLoader:
     spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  The loader yields the warped tensors and
     extras; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and frame 1, a b c d e g each, then padding).
     Raises without spatial_size= and with crop=: the spatial step contains the window.
+    motion_blur=dict(...) (the MBLUR_RANGES and, optionally, taps_side= and frames=; MBLUR_DEFAULT for one): the frames are
+    blurred along their own flow (Generator.motion_blur) into a further ring of frame buffers, which the loader yields in the
+    places of image0 / image1; flow, maps and labels stay those of the sharp frames.  frames=None: both frames when "flow1"
+    is among extras=, else frame 0; frame 1 without "flow1" raises.  The dict also holds "motion_blur" (float32 [n,4], the
+    records used: the shutter of frame 0, of frame 1, 0, 0).
     photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
     holds "photo" (float32 [n,16], the records used).
     erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
@@ -2345,10 +2507,12 @@ class FlowLoader:
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
-                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, **kw):
+                 spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
+                 **kw):
         import torch
         self.boundaries = self._boundary_options(boundaries, extras)
         self.erase = self._erase_options(erase, extras)
+        self.motion_blur = self._motion_blur_options(motion_blur, extras)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -2410,6 +2574,10 @@ class FlowLoader:
                 t.planes = alloc_crop(t.frame, ph, pw, zero=False)
                 t.window_recs = torch.empty((n, 4), dtype=torch.int32, device="cuda")
                 crop_format(t.frame, t.planes, p.height, p.width)  # (raises for a window the frame does not allow)
+            t.sharp, t.blur = t.planes, None
+            if self.motion_blur is not None:
+                blurred, t.blur = alloc_motion_blur(n, ph, pw, t.sharp["image0"].dtype, self.motion_blur[1])
+                t.planes = dict(t.sharp, **{"image%d" % f: b for f, b in enumerate(blurred) if b is not None})
             t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
             t.erase = alloc_erase(n) if self.erase is not None else None
             t.objects = alloc_object_table(n) if objects else None
@@ -2487,6 +2655,23 @@ class FlowLoader:
             raise ValueError("erase= marks the rectangles of frame 0 into occ1 through flow1: extras= must contain \"flow1\"")
         return {k: v for k, v in erase.items() if k in ERASE_RANGES}, o
 
+    @staticmethod
+    def _motion_blur_options(motion_blur, extras):
+        """motion_blur= split into (ranges with taps_side, frames), or None; raises for what the loader cannot serve"""
+        if motion_blur is None:
+            return None
+        unknown = set(motion_blur) - set(MBLUR_RANGES) - {"taps_side", "frames"}
+        if unknown:
+            raise ValueError("unknown motion_blur option(s) %s" % sorted(unknown))
+        have_flow1 = "flow1" in tuple(extras or ())
+        frames = motion_blur.get("frames")
+        frames = ((0, 1) if have_flow1 else (0,)) if frames is None else tuple(sorted(set(int(f) for f in frames)))
+        if not frames or any(f not in (0, 1) for f in frames):
+            raise ValueError("motion_blur= needs frames of 0 and / or 1, got %r" % (frames,))
+        if 1 in frames and not have_flow1:
+            raise ValueError("motion_blur= of frame 1 reads flow1: extras= must contain \"flow1\", or pass frames=(0,)")
+        return {k: v for k, v in motion_blur.items() if k != "frames"}, frames
+
     def _enqueue(self, j):
         """The next batch into set j: the stages of the class docstring, in its order, on the stream next_stream() gives."""
         import torch
@@ -2496,17 +2681,22 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
         if self.spatial is not None:
             hflip, vflip, occ_window = self.spatial_flags
-            g.spatial(t.frame, planes, first_index=first, ranges=self.spatial, hflip=hflip, vflip=vflip, occ_window=occ_window,
+            g.spatial(t.frame, t.sharp, first_index=first, ranges=self.spatial, hflip=hflip, vflip=vflip, occ_window=occ_window,
                       recs_out=t.window_recs, stream=s)
         elif self.crop is not None:
-            g.crop(t.frame, planes, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
+            g.crop(t.frame, t.sharp, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
                    recs_out=t.window_recs, stream=s)
+        if self.motion_blur is not None:
+            ranges, frames = self.motion_blur
+            pick = lambda a, b: tuple(t_ if f in frames else None for f, t_ in enumerate((a, b)))  # noqa: E731
+            g.motion_blur(pick(t.sharp["image0"], t.sharp["image1"]), pick(planes["image0"], planes["image1"]),
+                          flow=pick(t.sharp["flow"], t.sharp.get("flow1")), first_index=first, ranges=ranges, recs_out=t.blur, stream=s, size=size)
         if self.photo is not None:
             g.photo((planes["image0"], planes["image1"]), recs_out=t.photo, first_index=first, ranges=self.photo, stream=s, size=size)
         if self.erase is not None:
@@ -2537,6 +2727,8 @@ class FlowLoader:
         more = {k: v for k, v in t.planes.items() if k not in PACK_PLANES}
         if t.window_recs is not None:
             more["spatial" if self.spatial is not None else "crop"] = t.window_recs
+        if t.blur is not None:
+            more["motion_blur"] = t.blur
         if t.photo is not None:
             more["photo"] = t.photo
         if t.objects is not None:

@@ -745,4 +745,72 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
   return OFDG_OK;
 }
 
+// ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
+// half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
+// the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.
+int ofdg_motion_blur_draw(uint32_t seed, long long index, const struct ofdg_mblur_job* ranges, ofdg_mblur_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_motion_blur_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevMblurJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = mblur_ranges_error(j)) { g_host_error = std::string("ofdg_motion_blur_draw: ") + why; return OFDG_EINVAL; }
+  const DevMblurRec r = mblur_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int width, int height) {
+  const DevMblurJob* const j = reinterpret_cast<const DevMblurJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = mblur_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_motion_blur: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  for (int i = 0; i < n_samples; ++i) {
+    DevMblurRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = mblur_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
+    r = mblur_sanitise(r);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const float s = r.shutter[f];
+      const FlowPlane flow{j->flow[f], j->flow_fmt};
+      const size_t fu = (size_t)i * 2 * plane, fv = fu + plane;
+      const uint8_t* const sp = static_cast<const uint8_t*>(j->src[f]) + (size_t)i * 3 * plane * ses;
+      uint8_t* const dp = static_cast<uint8_t*>(j->dst[f]) + (size_t)i * 3 * plane * des;
+      const auto byte_at = [&](int c, int x, int y) -> uint32_t {
+        const size_t e = (size_t)c * plane + (size_t)spatial_clamp(y, height) * width + spatial_clamp(x, width);
+        if (ses == 1) return sp[e];
+        float v;
+        std::memcpy(&v, sp + 4 * e, 4);
+        return (uint32_t)photo_index(v);
+      };
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          const size_t p = (size_t)y * width + x;
+          const float u = flow.at(fu + p), v = flow.at(fv + p);
+          const bool finite = mblur_finite(u) && mblur_finite(v);
+          const int Dx = finite ? mblur_half(u, s) : 0, Dy = finite ? mblur_half(v, s) : 0;
+          const int m = mblur_taps_side(Dx, Dy, j->taps_side);
+          const int sx = m ? mblur_step(Dx, m) : 0, sy = m ? mblur_step(Dy, m) : 0;
+          for (int c = 0; c < 3; ++c) {
+            uint32_t S = 0;
+            for (int k = -m; k <= m; ++k) {
+              const int Qx = mblur_coord(x, k, sx, width), Qy = mblur_coord(y, k, sy, height);
+              const int ix = Qx >> 8, iy = Qy >> 8;
+              S += mblur_weight(k, m) * mblur_tap(byte_at(c, ix, iy), byte_at(c, ix + 1, iy), byte_at(c, ix, iy + 1), byte_at(c, ix + 1, iy + 1), Qx & 255, Qy & 255);
+            }
+            const uint32_t b = mblur_byte(S);
+            const float o = (float)b;
+            if (des == 1) dp[(size_t)c * plane + p] = (uint8_t)b;
+            else std::memcpy(dp + 4 * ((size_t)c * plane + p), &o, 4);
+          }
+        }
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

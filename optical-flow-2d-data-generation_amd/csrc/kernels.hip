@@ -4548,4 +4548,180 @@ __global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEra
   }
 }
 
+// ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
+// One launch for both frames and every sample: blockIdx.x counts the kMblurTileW x kMblurTileH tiles of a frame, blockIdx.y
+// the samples, blockIdx.z the frames that are set.  A 4-wave workgroup owns a tile, a lane four consecutive pixels of one row
+// (width % 8 == 0: a lane's four pixels, and the eight of a pair of lanes, are whole or outside together), so a wave's loads
+// of the centre pieces and of the flow are whole consecutive rows of the tile.  The record is drawn or read, and sanitised,
+// on uniform values once per (workgroup, sample) and stays in scalar registers; workgroup 0 writes it back from lane 0 with
+// one vector store.  A frame whose shutter is 0 reads no flow.  The workgroup then takes one of three paths, agreed on
+// through one word of LDS per wave (two ballots packed into it, no atomics; eight words in all: a row of four per parity
+// of the sample's turn):
+//   copy    no pixel of the tile has a tap beside its centre (m = 0 everywhere): every lane stores the bytes of the centre
+//           piece it read whole; nothing is staged.
+//   window  every tap of the tile lies within kMblurHalo pixels of its pixel: the tile and that halo - (64 + 33) x (16 + 33)
+//           pixels, one dword each: B, G, R packed, the float32-to-byte rule applied once on the way in, the border
+//           replicated, so the clamp of ix + 1 and iy + 1 is the window's own - go to LDS (18.6 KiB), and a tap is four
+//           ds_read_b32 (two pairs of neighbours) for all three channels.
+//   gather  some streak is longer than the halo: every pixel of the tile gathers its taps from global memory at clamped
+//           indices (ubyte / dword loads), the coordinates of a tap computed once for the three channels.
+// With OFDG_MBLUR_WINDOW=0 the window path is compiled out (the all-global-gather variant: CHANGELOG).  No record or flow
+// reaches outside a plane or the window: every index is clamped, and the window path is taken only when m |step| <= 256
+// kMblurHalo on both axes for every pixel of the tile.  Stores are whole pieces, non-temporal: 16 bytes of float32 a lane,
+// 8 bytes of uint8 a pair of lanes (a row of uint8 starts at a multiple of 8 bytes only), gathered by the even lane with a
+// wave shuffle.  The functions of the definition are the host twin's (csrc/ofdg_device.h), so the result is the twin's byte
+// for byte.  No atomics, no scratch.
+constexpr int kMblurThreads = 256;
+constexpr int kMblurTileW = 64, kMblurTileH = 16;
+#ifndef OFDG_MBLUR_WINDOW
+#define OFDG_MBLUR_WINDOW 1
+#endif
+constexpr bool kMblurWindow = OFDG_MBLUR_WINDOW != 0;
+constexpr int kMblurHalo = 16;  // pixels of halo on every side of the tile (and one more column and row for ix + 1, iy + 1)
+constexpr int kMblurWinW = kMblurTileW + 2 * kMblurHalo + 1, kMblurWinH = kMblurTileH + 2 * kMblurHalo + 1;
+static_assert(kMblurTileW / 4 * kMblurTileH == kMblurThreads, "a lane per four pixels of the tile");
+template <bool kSrcU8>
+__device__ __forceinline__ uint32_t mblur_load_byte(const uint8_t* __restrict__ sp, uint32_t e) {
+  if constexpr (kSrcU8) return sp[e];
+  else return (uint32_t)photo_index(reinterpret_cast<const float*>(sp)[e]);
+}
+template <bool kSrcU8, bool kDstU8, bool kFlowHalf>
+__global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob job, int n, int W, int H, uint32_t tiles_x) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  constexpr int kSES = kSrcU8 ? 1 : 4, kDES = kDstU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
+  __shared__ uint32_t win[kMblurWindow ? kMblurWinW * kMblurWinH : 1];
+  __shared__ uint32_t paths[2][kMblurThreads / 64];  // [parity of the sample's turn][wave]: bit 0 a tap beside the centre, bit 1 one beyond the halo
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int X0 = (int)(tx * kMblurTileW + (threadIdx.x & 15u) * 4u), Y = (int)(ty * kMblurTileH + (threadIdx.x >> 4));
+  const int wx0 = (int)(tx * kMblurTileW) - kMblurHalo, wy0 = (int)(ty * kMblurTileH) - kMblurHalo;  // the window's first column and row in the frame
+  const int f = (blockIdx.z != 0u || !job.src[0]) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.src[1] : job.src[0]);
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.flow[1] : job.flow[0]);
+  uint8_t* const d_img = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: mblur_arg_error)
+  const bool inside = X0 < W && Y < H;
+  const uint32_t at = inside ? (uint32_t)Y * (uint32_t)W + (uint32_t)X0 : 0u;  // the lane's first pixel in a channel
+  const int cap = job.taps_side;
+  uint32_t turn = 0u;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y, turn ^= 1u) {
+    DevMblurRec r;
+    if (job.recs) r = job.recs[i];
+    else r = mblur_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
+    r = mblur_sanitise(r);
+    if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u)
+      *reinterpret_cast<crop_u32x4*>(job.recs_out + i) = crop_u32x4{__float_as_uint(r.shutter[0]), __float_as_uint(r.shutter[1]), 0u, 0u};
+    const float s = f ? r.shutter[1] : r.shutter[0];
+    const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
+    uint32_t out[3][4] = {};  // the bytes to store: the centre piece, unless taps say otherwise
+    float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (inside) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if constexpr (kSrcU8) {
+          const uint32_t w = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)c * plane + at);
+          out[c][0] = w & 255u; out[c][1] = (w >> 8) & 255u; out[c][2] = (w >> 16) & 255u; out[c][3] = w >> 24;
+        } else {
+          const f32x4 e = *reinterpret_cast<const f32x4*>(sp + ((size_t)c * plane + at) * 4u);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) out[c][p] = (uint32_t)photo_index(e[p]);
+        }
+      }
+      if (s > 0.0f) {  // (uniform: a frame with shutter 0 reads no flow)
+        const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
+        if constexpr (kFlowHalf) {
+          const f16x4 a = *reinterpret_cast<const f16x4*>(fp), b = *reinterpret_cast<const f16x4*>(fp + (size_t)plane * kFES);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) { u[p] = (float)a[p]; v[p] = (float)b[p]; }
+        } else {
+          const f32x4 a = *reinterpret_cast<const f32x4*>(fp), b = *reinterpret_cast<const f32x4*>(fp + (size_t)plane * kFES);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) { u[p] = a[p]; v[p] = b[p]; }
+        }
+      }
+    }
+    int m[4], sx[4], sy[4];
+    bool blurred = false, far = false;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool finite = mblur_finite(u[p]) && mblur_finite(v[p]);
+      const int Dx = finite ? mblur_half(u[p], s) : 0, Dy = finite ? mblur_half(v[p], s) : 0;
+      m[p] = mblur_taps_side(Dx, Dy, cap);
+      sx[p] = m[p] ? mblur_step(Dx, m[p]) : 0;
+      sy[p] = m[p] ? mblur_step(Dy, m[p]) : 0;
+      blurred = blurred || m[p] != 0;
+      far = far || m[p] * mblur_abs(sx[p]) > 256 * kMblurHalo || m[p] * mblur_abs(sy[p]) > 256 * kMblurHalo;
+    }
+    // the path of the workgroup (every lane is here: a lane outside the frame has m = 0)
+    const uint32_t mine = (__any(blurred) ? 1u : 0u) | (__any(far) ? 2u : 0u);
+    if ((threadIdx.x & 63u) == 0u) paths[turn][threadIdx.x >> 6] = mine;
+    __syncthreads();  // (a wave is at most one barrier ahead of another, and the next sample's words go to the other row)
+    const uint32_t path = paths[turn][0] | paths[turn][1] | paths[turn][2] | paths[turn][3];
+    if (kMblurWindow && path == 1u) {
+      for (int j = (int)threadIdx.x; j < kMblurWinW * kMblurWinH; j += kMblurThreads) {
+        const int wy = j / kMblurWinW, wx = j - wy * kMblurWinW;
+        const uint32_t e = (uint32_t)spatial_clamp(wy0 + wy, H) * (uint32_t)W + (uint32_t)spatial_clamp(wx0 + wx, W);
+        win[j] = mblur_load_byte<kSrcU8>(sp, e) | (mblur_load_byte<kSrcU8>(sp, plane + e) << 8) | (mblur_load_byte<kSrcU8>(sp, 2u * plane + e) << 16);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int mp = m[p];
+        if (mp == 0) continue;
+        uint32_t S0 = 0u, S1 = 0u, S2 = 0u;
+#pragma unroll 1
+        for (int k = -mp; k <= mp; ++k) {
+          const int Qx = mblur_coord(X0 + p, k, sx[p], W), Qy = mblur_coord(Y, k, sy[p], H);
+          const int fx = Qx & 255, fy = Qy & 255;
+          // (0 <= column <= 95, 0 <= row <= 47: the tap is within the halo of its pixel, and a clamp only moves it towards the tile)
+          const uint32_t* const q = win + ((Qy >> 8) - wy0) * kMblurWinW + ((Qx >> 8) - wx0);
+          const uint32_t w00 = q[0], w10 = q[1], w01 = q[kMblurWinW], w11 = q[kMblurWinW + 1];
+          const uint32_t wk = mblur_weight(k, mp);
+          S0 += wk * mblur_tap(w00 & 255u, w10 & 255u, w01 & 255u, w11 & 255u, fx, fy);
+          S1 += wk * mblur_tap((w00 >> 8) & 255u, (w10 >> 8) & 255u, (w01 >> 8) & 255u, (w11 >> 8) & 255u, fx, fy);
+          S2 += wk * mblur_tap(w00 >> 16, w10 >> 16, w01 >> 16, w11 >> 16, fx, fy);
+        }
+        out[0][p] = mblur_byte(S0); out[1][p] = mblur_byte(S1); out[2][p] = mblur_byte(S2);
+      }
+      __syncthreads();  // (the next sample of this workgroup stages the window again)
+    } else if (path != 0u) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int mp = m[p];
+        if (mp == 0) continue;
+        uint32_t S0 = 0u, S1 = 0u, S2 = 0u;
+#pragma unroll 1
+        for (int k = -mp; k <= mp; ++k) {
+          const int Qx = mblur_coord(X0 + p, k, sx[p], W), Qy = mblur_coord(Y, k, sy[p], H);
+          const int fx = Qx & 255, fy = Qy & 255;
+          const uint32_t xa = (uint32_t)spatial_clamp(Qx >> 8, W), xb = (uint32_t)spatial_clamp((Qx >> 8) + 1, W);
+          const uint32_t ya = (uint32_t)spatial_clamp(Qy >> 8, H) * (uint32_t)W, yb = (uint32_t)spatial_clamp((Qy >> 8) + 1, H) * (uint32_t)W;
+          const uint32_t wk = mblur_weight(k, mp);
+          S0 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, ya + xa), mblur_load_byte<kSrcU8>(sp, ya + xb), mblur_load_byte<kSrcU8>(sp, yb + xa),
+                               mblur_load_byte<kSrcU8>(sp, yb + xb), fx, fy);
+          S1 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, plane + ya + xa), mblur_load_byte<kSrcU8>(sp, plane + ya + xb),
+                               mblur_load_byte<kSrcU8>(sp, plane + yb + xa), mblur_load_byte<kSrcU8>(sp, plane + yb + xb), fx, fy);
+          S2 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, 2u * plane + ya + xa), mblur_load_byte<kSrcU8>(sp, 2u * plane + ya + xb),
+                               mblur_load_byte<kSrcU8>(sp, 2u * plane + yb + xa), mblur_load_byte<kSrcU8>(sp, 2u * plane + yb + xb), fx, fy);
+        }
+        out[0][p] = mblur_byte(S0); out[1][p] = mblur_byte(S1); out[2][p] = mblur_byte(S2);
+      }
+    }
+    // (the lanes of a pair are inside together: X0 of the even one is a multiple of 8)
+    uint8_t* const dp = d_img + (size_t)i * 3 * plane * kDES;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (kDstU8) {
+        const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
+        const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
+        if (inside && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
+      } else {
+        const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
+        if (inside) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -291,7 +291,7 @@ struct PostOp {
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
-// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel.
+// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1873,6 +1873,39 @@ int ofdg_erase(ofdg_ctx* c, const struct ofdg_erase_job* job, int n_samples, voi
       with_bool(mark && j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
         hipLaunchKernelGGL((erase_apply_kernel<decltype(image_u8)::value, decltype(occ_u8)::value, decltype(half)::value>), g, dim3(kEraseThreads), 0, st,
                            *j, n_samples, W, H, occ_blocks);
+      });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Motion blur of caller-given frames along their flows: one kernel on `stream` for both frames and every sample.
+int ofdg_motion_blur(ofdg_ctx* c, const struct ofdg_mblur_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_motion_blur"};
+  const DevMblurJob* const j = reinterpret_cast<const DevMblurJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = mblur_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = mblur_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    OFDG_TRY(op.aligned(f ? "src[1]" : "src[0]", j->src[f], j->src_fmt));
+    OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
+    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[1]" : "dst[0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t tiles_x = ((uint32_t)W + kMblurTileW - 1) / kMblurTileW, tiles_y = ((uint32_t)H + kMblurTileH - 1) / kMblurTileH;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), (j->src[0] ? 1u : 0u) + (j->src[1] ? 1u : 0u));
+  with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
+      with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
+        hipLaunchKernelGGL((mblur_kernel<decltype(src_u8)::value, decltype(dst_u8)::value, decltype(half)::value>), g, dim3(kMblurThreads), 0, st, *j,
+                           n_samples, W, H, tiles_x);
       });
     });
   });

@@ -1164,6 +1164,159 @@ inline const char* erase_arg_error(const DevEraseJob* j, int n, int width, int h
   return nullptr;
 }
 
+// ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the half-displacement, the tap count and step, the tap value, the mean and the argument rules.  Compiled
+// without contraction, so every float operation below is its own rounding; behind the half-displacement and the step
+// everything is integers.
+constexpr int kMblurMaxTapsSide = OFDG_MBLUR_MAX_TAPS_SIDE;
+static_assert(256 * OFDG_MBLUR_MAX_HALF_PX == 8192, "mblur_half spells the clamp out");
+struct DevMblurRec {  // ofdg_mblur_rec, field for field
+  float shutter[2];
+  int32_t reserved[2];
+};
+struct DevMblurJob {  // struct ofdg_mblur_job, field for field
+  const void* src[2];
+  void* dst[2];
+  const void* flow[2];
+  const DevMblurRec* recs;
+  DevMblurRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, src_fmt, dst_fmt, flow_fmt, flags, taps_side;
+  float prob, shutter_min, shutter_max, pair_shutter;
+  int32_t reserved[2];
+};
+static_assert(sizeof(ofdg_mblur_rec) == sizeof(DevMblurRec) && sizeof(DevMblurRec) == 16 && offsetof(ofdg_mblur_rec, reserved) == offsetof(DevMblurRec, reserved) &&
+              offsetof(DevMblurRec, reserved) == 8, "ofdg_mblur_rec: 16 bytes without padding, the layout the kernel reads and writes");
+static_assert(sizeof(struct ofdg_mblur_job) == sizeof(DevMblurJob) && sizeof(DevMblurJob) == 128 && offsetof(struct ofdg_mblur_job, dst) == offsetof(DevMblurJob, dst) &&
+              offsetof(struct ofdg_mblur_job, flow) == offsetof(DevMblurJob, flow) && offsetof(struct ofdg_mblur_job, recs) == offsetof(DevMblurJob, recs) &&
+              offsetof(struct ofdg_mblur_job, recs_out) == offsetof(DevMblurJob, recs_out) && offsetof(struct ofdg_mblur_job, first_index) == offsetof(DevMblurJob, first_index) &&
+              offsetof(struct ofdg_mblur_job, seed) == offsetof(DevMblurJob, seed) && offsetof(struct ofdg_mblur_job, width) == offsetof(DevMblurJob, width) &&
+              offsetof(struct ofdg_mblur_job, src_fmt) == offsetof(DevMblurJob, src_fmt) && offsetof(struct ofdg_mblur_job, taps_side) == offsetof(DevMblurJob, taps_side) &&
+              offsetof(DevMblurJob, taps_side) == 100 && offsetof(struct ofdg_mblur_job, prob) == offsetof(DevMblurJob, prob) &&
+              offsetof(struct ofdg_mblur_job, pair_shutter) == offsetof(DevMblurJob, pair_shutter) && offsetof(DevMblurJob, pair_shutter) == 116 &&
+              offsetof(struct ofdg_mblur_job, reserved) == offsetof(DevMblurJob, reserved), "struct ofdg_mblur_job: 128 bytes, the layout the kernel takes");
+// The record of global sample g: Philox block 0 under the sampler's key of g at the counter {0, 0, 0x0c76, 0}.  `j` supplies
+// prob and the three ranges.
+OFDG_HD_FN DevMblurRec mblur_draw_rec(uint32_t seed, unsigned long long g, const DevMblurJob& j) {
+  const CropWords w = crop_philox(CropWords{0u, 0u, 0x0c76u, 0u}, seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, (uint32_t)g);
+  const bool on = photo_unit(w.x) < j.prob;
+  const float span = j.shutter_max - j.shutter_min;
+  const float part = span * photo_unit(w.y);
+  const float s0 = j.shutter_min + part;
+  const float s1 = s0 + photo_sym(w.z, j.pair_shutter);
+  DevMblurRec r;
+  r.shutter[0] = on ? s0 : 0.0f;
+  r.shutter[1] = on ? s1 : 0.0f;
+  r.reserved[0] = 0; r.reserved[1] = 0;
+  return r;
+}
+// What is used of a record, given or drawn: a NaN, a negative value and -0.0 become +0, a value above 2 becomes 2.
+OFDG_HD_FN float mblur_shutter(float s) { return s > 0.0f ? (s > OFDG_MBLUR_MAX_SHUTTER ? OFDG_MBLUR_MAX_SHUTTER : s) : 0.0f; }
+OFDG_HD_FN DevMblurRec mblur_sanitise(DevMblurRec r) {
+  for (int f = 0; f < 2; ++f) {
+    r.shutter[f] = mblur_shutter(r.shutter[f]);
+    r.reserved[f] = 0;
+  }
+  return r;
+}
+// finite: neither NaN nor an infinity (on the bits: no comparison the compiler may fold)
+OFDG_HD_FN bool mblur_finite(float x) {
+  uint32_t b;
+  __builtin_memcpy(&b, &x, 4);
+  return (b & 0x7f800000u) != 0x7f800000u;
+}
+// One component of the half-displacement in 24.8 for a finite flow component d and a sanitised shutter s: two float32
+// products (an overflow to an infinity lands on the clamp), the clamp, ties to even.
+OFDG_HD_FN int mblur_half(float d, float s) {
+  const float a = d * s;
+  float h = a * 128.0f;
+  h = h < -8192.0f ? -8192.0f : h > 8192.0f ? 8192.0f : h;
+  return (int)rintf(h);
+}
+OFDG_HD_FN int mblur_abs(int v) { return v < 0 ? -v : v; }
+// taps on each side of the centre: one per pixel of half-extent on the major axis, up to the cap
+OFDG_HD_FN int mblur_taps_side(int Dx, int Dy, int cap) {
+  const int ax = mblur_abs(Dx), ay = mblur_abs(Dy), L = ax > ay ? ax : ay, m = (L + 255) >> 8;
+  return m < cap ? m : cap;
+}
+// the step between taps on one axis, for m > 0: an IEEE float32 division, ties to even
+OFDG_HD_FN int mblur_step(int D, int m) { return (int)rintf((float)D / (float)m); }
+// a tap's coordinate on one axis, clamped into the plane: side is the width or the height
+OFDG_HD_FN int mblur_coord(int at, int k, int step, int side) {
+  const int q = 256 * at + k * step, hi = 256 * (side - 1);
+  return q < 0 ? 0 : q > hi ? hi : q;
+}
+// the 24.8 bilinear tap of four bytes, the integer form of ofdg_spatial's: at most 65280
+OFDG_HD_FN uint32_t mblur_tap(uint32_t e00, uint32_t e10, uint32_t e01, uint32_t e11, int fx, int fy) {
+  const uint32_t ux = (uint32_t)fx, uy = (uint32_t)fy;
+  const uint32_t T = (256u - ux) * (256u - uy) * e00 + ux * (256u - uy) * e10 + (256u - ux) * uy * e01 + ux * uy * e11;
+  return (T + 128u) >> 8;
+}
+// the weight of tap k of N = 2 m + 1: 65536 / N, the centre takes what the division leaves
+OFDG_HD_FN uint32_t mblur_weight(int k, int m) {
+  const uint32_t w = 65536u / (uint32_t)(2 * m + 1);
+  return k == 0 ? 65536u - 2u * (uint32_t)m * w : w;
+}
+// the byte of a weighted sum of taps (the weights sum to 65536, a tap is at most 65280: no overflow)
+OFDG_HD_FN uint32_t mblur_byte(uint32_t S) { return (S + (1u << 23)) >> 24; }
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* mblur_plane_size(const DevMblurJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// What the draw reads of a job: the first rule broken, or nullptr.
+inline const char* mblur_ranges_error(const DevMblurJob& j) {
+  if (!(j.prob >= 0.0f && j.prob <= 1.0f)) return "prob must lie in [0, 1]";
+  if (!(j.shutter_min >= 0.0f && j.shutter_min <= OFDG_MBLUR_MAX_SHUTTER)) return "shutter_min must lie in [0, 2]";
+  if (!(j.shutter_max >= 0.0f && j.shutter_max <= OFDG_MBLUR_MAX_SHUTTER)) return "shutter_max must lie in [0, 2]";
+  if (j.shutter_min > j.shutter_max) return "shutter_min must not be above shutter_max";
+  if (!(j.pair_shutter >= 0.0f && j.pair_shutter <= 3.4028234663852886e38f)) return "pair_shutter must be finite and not negative";
+  return nullptr;
+}
+// The argument rules ofdg_motion_blur and ofdg_host_motion_blur share: the first rule broken, or nullptr.  width, height:
+// what mblur_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* mblur_arg_error(const DevMblurJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->flags != 0) return "flags must be 0";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (j->taps_side < 1 || j->taps_side > kMblurMaxTapsSide) return "taps_side must lie in 1..16";
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    const int set = (j->src[f] ? 1 : 0) + (j->dst[f] ? 1 : 0) + (j->flow[f] ? 1 : 0);
+    if (set != 0 && set != 3) return !j->src[f] ? "src: a frame is incomplete (src, dst and flow go together)" : !j->dst[f] ? "dst: a frame is incomplete (src, dst and flow go together)"
+                                                                                                                               : "flow: a frame is incomplete (src, dst and flow go together)";
+    frames += set ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  if (!j->recs)
+    if (const char* why = mblur_ranges_error(*j)) return why;
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[8];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    r[nr++] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->src_fmt)), false};
+    r[nr++] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->dst_fmt)), true};
+    r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevMblurRec), false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevMblurRec), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.

@@ -13,9 +13,12 @@
 //   host_input_check planes             ofdg_host_flow_stats, ofdg_host_flow_pyramid and ofdg_host_crop on a binary16 flow and a
 //                                       float32 occlusion map that start at an ODD address (the twins ask no alignment of
 //                                       their inputs), against the same planes at an aligned one
+//   host_input_check mblur              ofdg_host_motion_blur and ofdg_motion_blur_draw on exactly sized heap buffers: every
+//                                       format, extreme flows, given and drawn records, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <filesystem>
@@ -257,12 +260,114 @@ int planes() {
   std::printf("planes stats=%016llx pyramid=%016llx crop=%016llx odd=%s\n", sums[0], sums[1], sums[2], ok ? "same" : "DIFFERENT");
   return ok ? 0 : 1;
 }
+
+// ofdg_host_motion_blur and ofdg_motion_blur_draw on heap buffers of exactly the planes' sizes (a byte read or written beside
+// one is a report): every format, flows that hold NaN, infinities, +-3e38, +-65504 and streaks that leave every border, given
+// records beyond every bound and drawn ones, on 8x2 (a plane smaller than any streak) and 72x40; then every refusal.
+int mblur() {
+  const float extreme[] = {0.0f, 3.25f, -40.5f, 3e38f, -3e38f, 65504.0f, -65504.0f, 1e-40f, -0.0f, 100.0f, -7.125f, 0.0039f};
+  const uint16_t extreme16[] = {0x0000, 0x4280, 0xd110, 0x7c00, 0xfc00, 0x7bff, 0xfbff, 0x0001, 0x8000, 0x5640, 0xc720, 0x7e00};
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 2; ++size) {
+    const int W = size ? 72 : 8, H = size ? 40 : 2, n = 3;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 8; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32, ff = fmts & 4 ? OFDG_FMT_F16 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4), fb = n * 2 * px * (ff == OFDG_FMT_F16 ? 2 : 4);
+      std::vector<uint8_t> src[2], dst[2], flow[2];
+      uint32_t x = 12345u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        src[f].resize(sb); dst[f].assign(db, 0xA5); flow[f].resize(fb);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          const float v = (e % 11) == 0 ? (e % 22 ? NAN : 1e9f) : (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          if (sf == OFDG_FMT_U8) src[f][e] = (uint8_t)(x >> 24);
+          else std::memcpy(src[f].data() + 4 * e, &v, 4);
+        }
+        for (size_t e = 0; e < n * 2 * px; ++e) {
+          const size_t k = (e / 5 + f) % 12;
+          if (ff == OFDG_FMT_F16) std::memcpy(flow[f].data() + 2 * e, &extreme16[k], 2);
+          else if (k == 11 && (e & 1)) { const float q = NAN; std::memcpy(flow[f].data() + 4 * e, &q, 4); }
+          else std::memcpy(flow[f].data() + 4 * e, &extreme[k], 4);
+        }
+      }
+      const float given[3][4] = {{NAN, -1.0f, 0, 0}, {2.5f, INFINITY, 0, 0}, {0.5f, 1.25f, 0, 0}};
+      std::vector<uint8_t> recs(sizeof given), used((size_t)n * 16, 0xA5);
+      std::memcpy(recs.data(), given, sizeof given);
+      for (int drawn = 0; drawn < 2; ++drawn)
+        for (int frames = 1; frames < 4; ++frames) {
+          struct ofdg_mblur_job job;
+          std::memset(&job, 0, sizeof job);
+          for (int f = 0; f < 2; ++f)
+            if ((frames >> f) & 1) { job.src[f] = src[f].data(); job.dst[f] = dst[f].data(); job.flow[f] = flow[f].data(); }
+          job.recs = drawn ? nullptr : (const ofdg_mblur_rec*)recs.data();
+          job.recs_out = (ofdg_mblur_rec*)used.data();
+          job.first_index = (1ll << 32) - 1; job.seed = 7;
+          job.src_fmt = sf; job.dst_fmt = df; job.flow_fmt = ff;
+          job.taps_side = drawn ? 16 : 5;
+          job.prob = 1.0f; job.shutter_min = 0.25f; job.shutter_max = 2.0f; job.pair_shutter = 0.5f;
+          const int rc = ofdg_host_motion_blur(&job, n, W, H);
+          if (rc) { std::printf("mblur: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+          ++calls;
+          for (int f = 0; f < 2; ++f)
+            if ((frames >> f) & 1) sum = sum * 31 + fnv1a(dst[f].data(), dst[f].size());
+          sum = sum * 31 + fnv1a(used.data(), used.size());
+        }
+    }
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> src((size_t)n * 3 * W * H * 4, 0), dst((size_t)n * 3 * W * H * 4, 0xA5), flow((size_t)n * 2 * W * H * 4, 0), out((size_t)n * 16, 0xA5);
+    struct ofdg_mblur_job good;
+    std::memset(&good, 0, sizeof good);
+    good.src[0] = src.data(); good.dst[0] = dst.data(); good.flow[0] = flow.data(); good.recs_out = (ofdg_mblur_rec*)out.data();
+    good.taps_side = 8; good.prob = 0.5f; good.shutter_max = 1.0f;
+    const auto refuse = [&](struct ofdg_mblur_job j, int ns, int w, int h) {
+      if (ofdg_host_motion_blur(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_motion_blur: ", 23) == 0) ++refused;
+      else std::printf("mblur: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_mblur_job j;
+    if (ofdg_host_motion_blur(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.src_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.flags = 1; refuse(j, n, W, H);
+    j = good; j.reserved[1] = 1; refuse(j, n, W, H);
+    j = good; j.taps_side = 0; refuse(j, n, W, H);
+    j = good; j.taps_side = 17; refuse(j, n, W, H);
+    j = good; j.flow[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; j.flow[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.prob = NAN; refuse(j, n, W, H);
+    j = good; j.shutter_min = -1.0f; refuse(j, n, W, H);
+    j = good; j.shutter_max = 2.5f; refuse(j, n, W, H);
+    j = good; j.shutter_min = 1.5f; refuse(j, n, W, H);
+    j = good; j.pair_shutter = INFINITY; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data(); refuse(j, n, W, H);
+    j = good; j.recs_out = (ofdg_mblur_rec*)(dst.data() + 16); refuse(j, n, W, H);
+    ofdg_mblur_rec rec;
+    std::memset(&rec, 0xA5, sizeof rec);
+    j = good; j.prob = 2.0f;
+    if (ofdg_motion_blur_draw(1, 0, &j, &rec) == OFDG_EINVAL && ofdg_motion_blur_draw(1, 0, nullptr, &rec) == OFDG_EINVAL && ofdg_motion_blur_draw(1, 0, &good, nullptr) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; }) &&
+                       ((const uint8_t*)&rec)[0] == 0xA5 && ((const uint8_t*)&rec)[15] == 0xA5;
+    if (!clean) { std::printf("mblur: a refusal wrote something\n"); return 1; }
+    if (ofdg_motion_blur_draw(1, (1ll << 32) + 3, &good, &rec) != OFDG_OK || ofdg_host_motion_blur(&good, n, W, H) != OFDG_OK) { std::printf("mblur: the valid call failed\n"); return 1; }
+  }
+  std::printf("mblur calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 23 ? 0 : 1;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
+  if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur\n", argv[0]);
   return 2;
 }
