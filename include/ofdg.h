@@ -1091,6 +1091,108 @@ int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int w
  * that breaks the rules above. */
 int ofdg_motion_blur_draw(uint32_t seed, long long index, const struct ofdg_mblur_job* ranges, ofdg_mblur_rec* out);
 
+/*
+ * Reprojection: each frame pulled through its own ground-truth flow, with residuals.  For frame f in {0, 1} ("own"; frame
+ * 1 - f is "other") every pixel looks up the other frame where flow[f] says it went - flow[0] the forward flow, flow[1] flow1 -
+ * and reports the other frame's bilinear value there (warped), how far that is from its own byte (err), whether the target is
+ * in the frame (mask), and how far flow[1 - f], read at the target as the backward field, is from undoing the displacement
+ * (fb2, the squared forward-backward residual in px^2).  Per sample and frame a row of integer counts and sums splits the
+ * residuals by what occ[f] calls visible and hidden.  Every input is read only; NOT in place.  A pure function of the
+ * buffers.  Everything is integers once a displacement is rounded to 1/256 px: the kernel, ofdg_host_reproject and the numpy
+ * restatement of the tests give the same bytes and the same rows on every run.  fl32(.) marks a float32 rounding (no
+ * contraction).
+ *
+ * Inputs: img[f] is image f as [n,3,height,width] of img_fmt (OFDG_FMT_F32 or OFDG_FMT_U8; float32 frames hold byte values, see
+ * ofdg_photo); flow[f] is [n,2,height,width] of flow_fmt (OFDG_FMT_F32 or OFDG_FMT_F16); occ[f] is [n,1,height,width] of occ_fmt
+ * (OFDG_FMT_F32 or OFDG_FMT_U8) or NULL.  Outputs, each optional on its own, per frame: warped[f] [n,3,height,width] of dst_fmt
+ * (OFDG_FMT_F32 or OFDG_FMT_U8), err[f] and mask[f] uint8 [n,1,height,width], fb2[f] float32 [n,1,height,width]; rows:
+ * n ofdg_reproject_row.  flags holds OFDG_REPROJ_FRAME0 and / or OFDG_REPROJ_FRAME1, the frames that are worked on (an output of
+ * a frame that is not flagged must be NULL), and OFDG_REPROJ_ACCUMULATE.  width = height = 0: the context's frame; otherwise
+ * any size the context's rule allows, as in ofdg_photo.
+ *
+ * Pixel (x, y) of a flagged frame f, (u, v) the element of flow[f] widened to float32:
+ * 1. Bad.  u or v is not finite (exponent bits all set): the pixel is bad.
+ * 2. Displacement in 24.8.  Dx = (int)rintf(clamp(fl32(u * 256.0f), -2^30, 2^30)) (ties to even), Dy likewise from v.
+ *    Qx = 256 x + Dx, Qy = 256 y + Dy.
+ * 3. Rounded target.  rx = (Qx + 128) >> 8 (arithmetic shift), ry likewise.  The pixel is inside iff 0 <= rx <= width - 1 and
+ *    0 <= ry <= height - 1, else outside.
+ * 4. Bad or outside: every warped element is 0, err 0, mask 0, fb2 +0.0f; of the row only n_bad or n_outside counts the pixel.
+ * 5. Inside: mask 1.  Qx is clamped into [0, 256 (width - 1)], Qy into [0, 256 (height - 1)]; ix = Qx >> 8, fx = Qx & 255, iy
+ *    and fy likewise, ix + 1 and iy + 1 clamped into the plane - step 3c of ofdg_motion_blur, as is the byte of an element
+ *    (itself for uint8, the index rule of ofdg_photo for float32).  Per channel, e00, e10, e01, e11 the bytes of the OTHER frame
+ *    at (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1): T = (256 - fx)(256 - fy) e00 + fx (256 - fy) e10 + (256 - fx)
+ *    fy e01 + fx fy e11;  t = (T + 128) >> 8;  the warped byte w = (t + 128) >> 8.  A uint8 destination stores w, a float32 one
+ *    (float)w.  err = the largest |w - own byte| of the three channels.
+ * 6. Forward-backward residual, when flow[1 - f] is given.  Per component, b00, b10, b01, b11 the elements of flow[1 - f] at
+ *    the same four places, B = (int)rintf(clamp(fl32(b * 256.0f), -2^30, 2^30)) each;  T = (256 - fx)(256 - fy) B00 + fx (256 -
+ *    fy) B10 + (256 - fx) fy B01 + fx fy B11 in int64 (the weights sum to 65536);  bx = (T + 32768) >> 16 (arithmetic shift), by
+ *    likewise.  ex = clamp(Dx + bx, -2^23, 2^23), ey likewise;  e2 = ex ex + ey ey (int64, at most 2^47);  fb2 = fl32((float)e2)
+ *    * 2^-16 (exact).  When one of the eight elements is not finite, e2 = 2^47 and fb2 = +infinity.
+ * 7. Visibility.  An inside pixel is visible when occ[f] is NULL or its element there is zero (float32: compares equal to 0,
+ *    so -0.0 is and a NaN is not - ofdg_crop's rule), else hidden.
+ * 8. Row of sample i, block f (nothing is added to an unflagged frame's block).  n_bad, n_outside, n_visible, n_hidden count the
+ *    pixels; they sum to width * height.  With img[0] and img[1] both given: err_hist[err >> 4], sum_err_visible and
+ *    max_err_visible over visible pixels, sum_err_hidden over hidden ones.  With flow[1 - f] given: n_fb_over_visible and
+ *    n_fb_over_hidden count the pixels with e2 > (int64)fb_thresh_q8^2, sum_fb2_visible adds min(e2, 2^32 - 1) and
+ *    max_fb2_visible is the largest e2, over visible pixels (units of 2^-16 px^2).  Fields whose inputs are absent stay 0.
+ *    Without OFDG_REPROJ_ACCUMULATE the call first writes every byte of the n rows as zero on `stream`; with it the counts and
+ *    sums are added to and the maxima raised (as OFDG_STATS_ACCUMULATE).
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel for any
+ * n and both frames; integer atomics only, so no bit depends on the order of arrival.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, a size that
+ * breaks the rule above, 3 * width * height of 2^32 and more, another format code (occ_fmt counts only when a map is given),
+ * unknown bits in flags, non-zero reserved, fb_thresh_q8 outside 0..2^23, no frame flagged, an output of an unflagged frame,
+ * no output at all, a flagged frame without flow[f], warped / err / mask of frame f without img[1 - f], err without img[f], fb2
+ * without flow[1 - f]; a misaligned pointer (inputs as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8;
+ * destinations and rows 16-byte), a destination range (warped, err, mask, fb2, rows) that overlaps any other range of the job,
+ * OFDG_STREAM_OWN before any render / forward call on the context.  Mode 9 has no flow1 and no maps: there frame 0 can be
+ * reprojected, without fb2.
+ *
+ * Out of scope: sub-pixel affine-aware taps (affine-free: plain bilinear), the nearest label is not used to pick taps,
+ * splatting / a forward warp, an in-place form, one row for the whole batch, rows mapped through ofdg_pack, frame 1 and fb2 in
+ * mode 9.
+ */
+#define OFDG_REPROJ_FRAME0     1
+#define OFDG_REPROJ_FRAME1     2
+#define OFDG_REPROJ_ACCUMULATE 4   /* add to the rows instead of overwriting them */
+#define OFDG_REPROJ_ERR_BINS   16
+#define OFDG_REPROJ_MAX_FB_THRESH_Q8 (1 << 23)
+typedef struct ofdg_reproject_frame_row {   /* 128 bytes without padding */
+  uint32_t n_bad, n_outside, n_visible, n_hidden;
+  uint32_t err_hist[OFDG_REPROJ_ERR_BINS];  /* visible pixels, bin err >> 4 */
+  uint32_t max_err_visible;
+  uint32_t n_fb_over_visible, n_fb_over_hidden;
+  uint32_t reserved;
+  uint64_t sum_err_visible, sum_err_hidden;
+  uint64_t sum_fb2_visible;                 /* of min(e2, 2^32 - 1), units of 2^-16 px^2 */
+  uint64_t max_fb2_visible;                 /* the largest e2 */
+} ofdg_reproject_frame_row;
+typedef struct ofdg_reproject_row {         /* 256 bytes without padding: a block per frame */
+  ofdg_reproject_frame_row frame[2];
+} ofdg_reproject_row;
+struct ofdg_reproject_job {                 /* 160 bytes */
+  const void* img[2];                       /* [n,3,height,width] of img_fmt: image0, image1, or NULL */
+  const void* flow[2];                      /* [n,2,height,width] of flow_fmt: flow, flow1, or NULL */
+  const void* occ[2];                       /* [n,1,height,width] of occ_fmt: occ0, occ1, or NULL */
+  void* warped[2];                          /* [n,3,height,width] of dst_fmt, or NULL */
+  void* err[2];                             /* uint8 [n,1,height,width], or NULL */
+  void* mask[2];                            /* uint8 [n,1,height,width], or NULL */
+  void* fb2[2];                             /* float32 [n,1,height,width], or NULL */
+  ofdg_reproject_row* rows;                 /* DEVICE, n rows, or NULL */
+  int32_t width, height;                    /* 0, 0: the context's frame */
+  int32_t img_fmt, dst_fmt, flow_fmt, occ_fmt;
+  int32_t flags;                            /* OFDG_REPROJ_* */
+  int32_t fb_thresh_q8;                     /* 0..2^23, in 1/256 px */
+  int32_t reserved[2];
+};
+int ofdg_reproject(ofdg_ctx* ctx, const struct ofdg_reproject_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and rows in host memory, no alignment asked of any
+ * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int width, int height);
+
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).
  * ofdg_set_step(k) makes the next ofdg_forward produce batch k (counter sampler: at no cost; reference-stream

@@ -112,6 +112,7 @@ EXPORTS = [
     "ofdg_boundaries", "ofdg_host_boundaries",
     "ofdg_erase", "ofdg_host_erase", "ofdg_erase_draw",
     "ofdg_motion_blur", "ofdg_host_motion_blur", "ofdg_motion_blur_draw",
+    "ofdg_reproject", "ofdg_host_reproject",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1214,6 +1215,203 @@ def host_motion_blur(images, flow, recs=None, first_index=0, seed=0, ranges=None
     return out, used
 
 
+# reprojection (ofdg_reproject_row / struct ofdg_reproject_job / ofdg_reproject, include/ofdg.h)
+REPROJ_FRAME0 = 1            # OFDG_REPROJ_FRAME0
+REPROJ_FRAME1 = 2            # OFDG_REPROJ_FRAME1
+REPROJ_ACCUMULATE = 4        # OFDG_REPROJ_ACCUMULATE
+REPROJ_ERR_BINS = 16         # OFDG_REPROJ_ERR_BINS
+REPROJ_MAX_FB_THRESH_Q8 = 1 << 23   # OFDG_REPROJ_MAX_FB_THRESH_Q8
+REPROJ_PLANES = ("warped", "err", "mask", "fb2")   # the per-frame outputs; "rows" is the batch's
+REPROJ_OUTPUTS = REPROJ_PLANES + ("rows",)
+
+
+class ReprojectFrameRow(C.Structure):
+    """ofdg_reproject_frame_row: one frame's block of a row (128 bytes)."""
+    _fields_ = [("n_bad", C.c_uint32), ("n_outside", C.c_uint32), ("n_visible", C.c_uint32), ("n_hidden", C.c_uint32),
+                ("err_hist", C.c_uint32 * REPROJ_ERR_BINS), ("max_err_visible", C.c_uint32), ("n_fb_over_visible", C.c_uint32),
+                ("n_fb_over_hidden", C.c_uint32), ("reserved", C.c_uint32), ("sum_err_visible", C.c_uint64), ("sum_err_hidden", C.c_uint64),
+                ("sum_fb2_visible", C.c_uint64), ("max_fb2_visible", C.c_uint64)]
+
+
+class ReprojectRow(C.Structure):
+    """ofdg_reproject_row: the blocks of frame 0 and frame 1 of one sample (256 bytes)."""
+    _fields_ = [("frame", ReprojectFrameRow * 2)]
+
+
+class ReprojectJob(C.Structure):
+    """struct ofdg_reproject_job (160 bytes)."""
+    _fields_ = [("img", C.c_void_p * 2), ("flow", C.c_void_p * 2), ("occ", C.c_void_p * 2), ("warped", C.c_void_p * 2), ("err", C.c_void_p * 2),
+                ("mask", C.c_void_p * 2), ("fb2", C.c_void_p * 2), ("rows", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("img_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flow_fmt", C.c_int32), ("occ_fmt", C.c_int32), ("flags", C.c_int32),
+                ("fb_thresh_q8", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def _reproject_dtype():
+    """The numpy dtype of one frame's block: a row is two of them."""
+    import numpy as np
+    return np.dtype([("n_bad", "<u4"), ("n_outside", "<u4"), ("n_visible", "<u4"), ("n_hidden", "<u4"), ("err_hist", "<u4", (REPROJ_ERR_BINS,)),
+                     ("max_err_visible", "<u4"), ("n_fb_over_visible", "<u4"), ("n_fb_over_hidden", "<u4"), ("reserved", "<u4"),
+                     ("sum_err_visible", "<u8"), ("sum_err_hidden", "<u8"), ("sum_fb2_visible", "<u8"), ("max_fb2_visible", "<u8")])
+
+
+def reproject_key(name, f):
+    """The name of output `name` (REPROJ_PLANES) of frame f in the dicts of Generator.reproject, host_reproject and FlowLoader:
+    "warped0", "err1", "mask0", "fb2_1"."""
+    return "%s%s%d" % (name, "_" if name[-1].isdigit() else "", f)
+
+
+_REPROJ_KEYS = {reproject_key(name, f): (name, f) for name in REPROJ_PLANES for f in range(2)}
+
+
+def _fb_thresh_q8(fb_thresh):
+    q = int(round(float(fb_thresh) * 256.0))
+    if not 0 <= q <= REPROJ_MAX_FB_THRESH_Q8:
+        raise ValueError("fb_thresh must lie in [0, 32768] px, got %r" % (fb_thresh,))
+    return q
+
+
+def _reproject_frames(frames, flows, out):
+    """frames= of a reprojection as a sorted tuple; None: the frames `out` names, or, without any, those whose flow is given"""
+    if frames is None:
+        named = sorted({_REPROJ_KEYS[k][1] for k in out if k in _REPROJ_KEYS})
+        return tuple(named) if named else tuple(f for f in range(2) if flows[f] is not None)
+    frames = tuple(sorted(set(int(f) for f in frames)))
+    if not frames or any(f not in (0, 1) for f in frames):
+        raise ValueError("frames must hold 0 and / or 1, got %r" % (frames,))
+    return frames
+
+
+def reproject_format(images, flows, occ, out, height=None, width=None):
+    """(n, height, width, image code, dst code, flow code, occ code) of the planes of Generator.reproject / host_reproject:
+    images, flows and occ are pairs - (image0, image1), (flow, flow1), (occ0, occ1) -, any member None (occ itself may be
+    None); out a dict of reproject_key names.  A frame is float32 or uint8 [n,3,height,width], a flow float32 or float16
+    [n,2,height,width], a map float32 or uint8 [n,1,height,width], each kind of one dtype; "warped*" float32 or uint8 of one
+    dtype, "err*" and "mask*" uint8 [n,1,height,width], "fb2_*" float32 [n,1,height,width].  Raises ValueError for anything
+    else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    occ = (None, None) if occ is None else occ
+    if images is None or flows is None or len(images) != 2 or len(flows) != 2 or len(occ) != 2:
+        raise ValueError("images, flows and occ must be pairs (frame 0, frame 1)")
+    unknown = sorted(set(out) - set(_REPROJ_KEYS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(sorted(_REPROJ_KEYS))))
+    given = [t for t in flows if t is not None]
+    if not given:
+        raise ValueError("flows must hold at least one flow")
+    shape = tuple(given[0].shape)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 2 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a flow must be [n,2,%s,%s], got %s" % (height or "height", width or "width", shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    warped = tuple(out.get(reproject_key("warped", f)) for f in range(2))
+    codes = []
+    for what, pair, table, ch, default in (("images", images, _IMAGE_CODES, 3, FMT_F32), ("warped", warped, _IMAGE_CODES, 3, FMT_F32),
+                                           ("flows", flows, _FLOW_CODES, 2, FMT_F32), ("occ", occ, _OCC_CODES, 1, FMT_F32)):
+        names = set()
+        for f, t in enumerate(pair):
+            if t is not None:
+                _check_plane("%s[%d]" % (what, f), t, tuple(table), (n, ch, height, width))
+                names.add(_dtype_name(t))
+        if len(names) > 1:
+            raise ValueError("%s must have one dtype for both frames, got %s" % (what, sorted(names)))
+        codes.append(table[names.pop()] if names else default)
+    for key, t in out.items():
+        name = _REPROJ_KEYS[key][0]
+        if name in ("err", "mask"):
+            _check_plane(key, t, ("uint8",), (n, 1, height, width))
+        elif name == "fb2":
+            _check_plane(key, t, ("float32",), (n, 1, height, width))
+    return (n, height, width) + tuple(codes)
+
+
+def _reproject_job(images, flows, occ, out, rows, ptr, codes, size, frames, fb_thresh, accumulate):
+    job = ReprojectJob()
+    occ = (None, None) if occ is None else occ
+    for f in range(2):
+        job.img[f], job.flow[f], job.occ[f] = (None if t is None else ptr(t) for t in (images[f], flows[f], occ[f]))
+    for key, t in out.items():
+        name, f = _REPROJ_KEYS[key]
+        getattr(job, name)[f] = ptr(t)
+    job.rows = rows
+    job.height, job.width = size
+    job.img_fmt, job.dst_fmt, job.flow_fmt, job.occ_fmt = codes
+    job.flags = sum(1 << f for f in frames) | (REPROJ_ACCUMULATE if accumulate else 0)
+    job.fb_thresh_q8 = _fb_thresh_q8(fb_thresh)
+    return job
+
+
+def alloc_reproject(n, height, width, frames=(0,), outputs=("rows",), image_dtype=None, device="cuda"):
+    """(out, rows) of Generator.reproject for n samples: out the dict of the planes among `outputs` (REPROJ_OUTPUTS) for each
+    frame of `frames` under their reproject_key names - "warped*" [n,3,height,width] of image_dtype (default torch.float32),
+    "err*" and "mask*" uint8 and "fb2_*" float32 [n,1,height,width] -, rows the zeroed uint8 [n,256] rows when "rows" is
+    among outputs, else None.  The planes are not filled: the call writes every element."""
+    import torch
+    unknown = sorted(set(outputs) - set(REPROJ_OUTPUTS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(REPROJ_OUTPUTS)))
+    if n < 1:
+        raise ValueError("alloc_reproject needs n >= 1, got %d" % n)
+    shapes = {"warped": (3, torch.float32 if image_dtype is None else image_dtype), "err": (1, torch.uint8), "mask": (1, torch.uint8),
+              "fb2": (1, torch.float32)}
+    out = {reproject_key(name, f): torch.empty((n, shapes[name][0], height, width), dtype=shapes[name][1], device=device)
+           for f in _reproject_frames(frames, (None, None), {}) for name in REPROJ_PLANES if name in outputs}
+    rows = torch.zeros((n, C.sizeof(ReprojectRow)), dtype=torch.uint8, device=device) if "rows" in outputs else None
+    return out, rows
+
+
+def reproject_numpy(rows, fb_thresh=None):
+    """The rows Generator.reproject filled (a tensor or an array; synchronise first) as a dict: "rows" the structured array
+    [n,2] (sample, frame; the fields of ofdg_reproject_frame_row) and, float64 [n,2] each, NaN where the count is 0:
+    "mean_err_visible" and "mean_err_hidden" (grey levels), "share_fb_over_visible" and "share_fb_over_hidden" (of the visible /
+    hidden pixels, those whose forward-backward residual is above the call's fb_thresh), "mean_fb2_visible" and
+    "max_fb2_visible" (px^2)."""
+    import numpy as np
+    r = np.ascontiguousarray(rows.cpu().numpy() if hasattr(rows, "cpu") else rows)
+    t = r.view(np.uint8).reshape(-1, C.sizeof(ReprojectRow)).view(_reproject_dtype()).reshape(-1, 2).copy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vis, hid = t["n_visible"].astype(np.float64), t["n_hidden"].astype(np.float64)
+        per = lambda a, b: np.where(b > 0, a.astype(np.float64) / b, np.nan)  # noqa: E731
+        return {"rows": t, "mean_err_visible": per(t["sum_err_visible"], vis), "mean_err_hidden": per(t["sum_err_hidden"], hid),
+                "share_fb_over_visible": per(t["n_fb_over_visible"], vis), "share_fb_over_hidden": per(t["n_fb_over_hidden"], hid),
+                "mean_fb2_visible": per(t["sum_fb2_visible"], vis) / 65536.0, "max_fb2_visible": t["max_fb2_visible"].astype(np.float64) / 65536.0}
+
+
+def host_reproject(images, flows, occ=None, outputs=("rows",), frames=None, fb_thresh=1.0, dst_dtype=None, rows=None, accumulate=False):
+    """ofdg_host_reproject (no GPU) on numpy arrays: images the pair (image0, image1) of float32 or uint8 [n,3,H,W], flows the
+    pair (flow, flow1) of float32 or float16 [n,2,H,W], occ None or the pair (occ0, occ1) of float32 or uint8 [n,1,H,W]; any
+    member may be None.  outputs: which of REPROJ_OUTPUTS to make, for each frame of `frames` (None: those whose flow is given).
+    dst_dtype: np.float32 / np.uint8 of "warped*", default the images'.  rows: the array a former call returned, to add to with
+    accumulate=True.  Returns (out, rows): the dict of planes under their reproject_key names and the structured array [n,2]
+    (reproject_numpy's "rows"), None without "rows"."""
+    import numpy as np
+    con = lambda pair: (None, None) if pair is None else tuple(None if t is None else np.ascontiguousarray(t) for t in pair)  # noqa: E731
+    images, flows, occ = con(images), con(flows), con(occ)
+    unknown = sorted(set(outputs) - set(REPROJ_OUTPUTS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(REPROJ_OUTPUTS)))
+    given = [t for t in flows if t is not None]
+    if not given or given[0].ndim != 4:
+        raise ValueError("flows must hold at least one flow [n,2,H,W]")
+    n, _, height, width = given[0].shape
+    frames = _reproject_frames(frames, flows, {})
+    some = [t for t in images if t is not None]
+    dt = np.dtype(dst_dtype if dst_dtype is not None else some[0].dtype if some else np.float32)
+    kinds = {"warped": (3, dt), "err": (1, np.uint8), "mask": (1, np.uint8), "fb2": (1, np.float32)}
+    out = {reproject_key(name, f): np.zeros((n, kinds[name][0], height, width), kinds[name][1]) for f in frames for name in REPROJ_PLANES if name in outputs}
+    n, height, width, *codes = reproject_format(images, flows, occ, out)
+    if "rows" not in outputs:
+        if rows is not None or accumulate:
+            raise ValueError("rows= and accumulate=True need \"rows\" among outputs")
+    elif rows is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs rows= to add to")
+        rows = np.zeros((n, 2), _reproject_dtype())
+    elif rows.dtype != _reproject_dtype() or rows.shape != (n, 2) or not rows.flags["C_CONTIGUOUS"]:
+        raise ValueError("rows must be a contiguous structured array [%d,2] as a former call returned it" % n)
+    job = _reproject_job(images, flows, occ, out, None if rows is None else rows.ctypes.data, lambda a: a.ctypes.data, codes, (0, 0), frames, fb_thresh,
+                         accumulate)
+    _host_check(lib().ofdg_host_reproject(C.byref(job), n, width, height))
+    return out, rows
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -1314,6 +1512,8 @@ def lib():
         L.ofdg_motion_blur.argtypes = [vp, C.POINTER(MblurJob), i32, vp]
         L.ofdg_host_motion_blur.argtypes = [C.POINTER(MblurJob), i32, i32, i32]
         L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
+        L.ofdg_reproject.argtypes = [vp, C.POINTER(ReprojectJob), i32, vp]
+        L.ofdg_host_reproject.argtypes = [C.POINTER(ReprojectJob), i32, i32, i32]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -1798,6 +1998,30 @@ class Generator:
                          ranges, taps_side)
         self._check(lib().ofdg_motion_blur(self.h, C.byref(job), n, C.c_void_p(stream)))
         return out
+
+    def reproject(self, images, flows, occ=None, out=None, rows=None, fb_thresh=1.0, frames=None, accumulate=False, stream=0, size=None):
+        """Each frame pulled through its own flow, with residuals, in one launch (ofdg_reproject, include/ofdg.h): for frame f
+        the other frame is sampled bilinearly where flows[f] says each pixel went.  images: the pair (image0, image1) of
+        float32 or uint8 tensors [n,3,H,W]; flows: the pair (flow, flow1) of float32 or float16 tensors [n,2,H,W]; occ: None or
+        the pair (occ0, occ1) of float32 or uint8 tensors [n,1,H,W]; any member may be None (mode 9: flows=(flow, None)), all
+        read only.  out: a dict of the planes to write under their reproject_key names (alloc_reproject) - "warped0" the
+        other frame seen from frame 0, "err0" the largest channel residual against image0, "mask0" 1 where the target is in
+        the frame, "fb2_0" the squared forward-backward residual in px^2, and the same with 1.  rows: None or the uint8 device
+        tensor [n,256] that receives a row per sample (reproject_numpy), split by what occ calls visible and hidden;
+        accumulate=True adds to it.  fb_thresh: the residual in px above which a pixel counts in n_fb_over_*.  frames: None -
+        the frames out names, or, with rows alone, those whose flow is given.  stream: the stream the planes were written on,
+        or STREAM_OWN.  size=(height, width): planes of that size instead of the context's.  Asynchronous.  Returns
+        (out, rows)."""
+        images, flows, out = tuple(images), tuple(flows), dict(out or {})
+        occ = None if occ is None else tuple(occ)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = reproject_format(images, flows, occ, out, height, width)
+        if rows is not None and (str(rows.dtype) != "torch.uint8" or tuple(rows.shape) != (n, C.sizeof(ReprojectRow))):
+            raise ValueError("rows must be uint8 [%d,%d], got %s %s" % (n, C.sizeof(ReprojectRow), rows.dtype, tuple(rows.shape)))
+        job = _reproject_job(images, flows, occ, out, _optr(rows), lambda t: _dptr(t).value, codes, job_size, _reproject_frames(frames, flows, out),
+                             fb_thresh, accumulate)
+        self._check(lib().ofdg_reproject(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return out, rows
 
     def debug_photo_table(self, rec):
         """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
@@ -2415,6 +2639,7 @@ class _RingSlot:
                  "planes",       # the planes every stage behind the blur works on, by name: `sharp`, with the blurred frames in place
                  "window_recs",  # the records of crop= / spatial=
                  "blur",         # the records of motion_blur=
+                 "reproject",    # (planes by name, rows) of reproject=
                  "objects",      # (rows, counts) of objects=True
                  "stats",        # the rows of stats=True
                  "pyramid",      # the levels of pyramid=, or (levels, weights)
@@ -2445,19 +2670,21 @@ class FlowLoader:
 
         1. forward          the frames, the flow and the extras=
         2. spatial= / crop= the window, into planes of its own: every later stage works on the window's planes and size
-        3. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
+        3. reproject=       of the window's sharp frames, flows and maps as they are then (un-blurred, un-erased), into planes
+                            and rows of its own
+        4. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
                             places of image0 / image1 for every later stage and in the batch
-        4. photo=           in place, on both frames
-        5. erase=           in place, on the frames and the occlusion maps
-        6. objects=True     the table, of the label planes of stage 1
-        7. stats=, pyramid= the reductions of flow and occ0
-        8. boundaries=      of the flows and label planes
-        9. pack=            of image0, image1 and flow, into tensors of its own
+        5. photo=           in place, on both frames
+        6. erase=           in place, on the frames and the occlusion maps
+        7. objects=True     the table, of the label planes of stage 1
+        8. stats=, pyramid= the reductions of flow and occ0
+        9. boundaries=      of the flows and label planes
+        10. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
     eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 to 5 are drawn from the
+    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 and 4 to 6 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -2479,6 +2706,12 @@ class FlowLoader:
     places of image0 / image1; flow, maps and labels stay those of the sharp frames.  frames=None: both frames when "flow1"
     is among extras=, else frame 0; frame 1 without "flow1" raises.  The dict also holds "motion_blur" (float32 [n,4], the
     records used: the shutter of frame 0, of frame 1, 0, 0).
+    reproject=dict(frames=, fb_thresh=, outputs=) (all optional): each frame of frames= is pulled through its own flow
+    (Generator.reproject) right behind the window, so it reads the sharp frames and the maps before erase= extends them.
+    outputs= names what to make (REPROJ_OUTPUTS; default ("rows",)): the dict holds "reproject" (uint8 [n,256], a row per
+    sample: reproject_numpy) and the planes by name, "warped0", "err0", "mask0", "fb2_0" and the same with 1.  occ0 / occ1
+    split the rows into visible and hidden when they are among extras=.  frames=None: both frames when "flow1" is among
+    extras=, else frame 0; frame 1 or "fb2" without "flow1" raises.  fb_thresh: px, default 1.
     photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
     holds "photo" (float32 [n,16], the records used).
     erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
@@ -2508,11 +2741,12 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 **kw):
+                 reproject=None, **kw):
         import torch
         self.boundaries = self._boundary_options(boundaries, extras)
         self.erase = self._erase_options(erase, extras)
         self.motion_blur = self._motion_blur_options(motion_blur, extras)
+        self.reproject = self._reproject_options(reproject, extras)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -2575,6 +2809,9 @@ class FlowLoader:
                 t.window_recs = torch.empty((n, 4), dtype=torch.int32, device="cuda")
                 crop_format(t.frame, t.planes, p.height, p.width)  # (raises for a window the frame does not allow)
             t.sharp, t.blur = t.planes, None
+            t.reproject = None
+            if self.reproject is not None:
+                t.reproject = alloc_reproject(n, ph, pw, self.reproject[0], self.reproject[2], t.sharp["image0"].dtype)
             if self.motion_blur is not None:
                 blurred, t.blur = alloc_motion_blur(n, ph, pw, t.sharp["image0"].dtype, self.motion_blur[1])
                 t.planes = dict(t.sharp, **{"image%d" % f: b for f, b in enumerate(blurred) if b is not None})
@@ -2672,6 +2909,29 @@ class FlowLoader:
             raise ValueError("motion_blur= of frame 1 reads flow1: extras= must contain \"flow1\", or pass frames=(0,)")
         return {k: v for k, v in motion_blur.items() if k != "frames"}, frames
 
+    @staticmethod
+    def _reproject_options(reproject, extras):
+        """reproject= split into (frames, fb_thresh, outputs), or None; raises for what the loader cannot serve"""
+        if reproject is None:
+            return None
+        unknown = set(reproject) - {"frames", "fb_thresh", "outputs"}
+        if unknown:
+            raise ValueError("unknown reproject option(s) %s" % sorted(unknown))
+        have_flow1 = "flow1" in tuple(extras or ())
+        frames = reproject.get("frames")
+        frames = ((0, 1) if have_flow1 else (0,)) if frames is None else tuple(sorted(set(int(f) for f in frames)))
+        if not frames or any(f not in (0, 1) for f in frames):
+            raise ValueError("reproject= needs frames of 0 and / or 1, got %r" % (frames,))
+        if 1 in frames and not have_flow1:
+            raise ValueError("reproject= of frame 1 reads flow1: extras= must contain \"flow1\", or pass frames=(0,)")
+        outputs = tuple(reproject.get("outputs", ("rows",)))
+        bad = sorted(set(outputs) - set(REPROJ_OUTPUTS))
+        if bad or not outputs:
+            raise ValueError("reproject= needs outputs among %s, got %r" % (", ".join(REPROJ_OUTPUTS), outputs))
+        if "fb2" in outputs and not have_flow1:
+            raise ValueError("reproject= output \"fb2\" reads flow1: extras= must contain \"flow1\"")
+        return frames, _fb_thresh_q8(reproject.get("fb_thresh", 1.0)) / 256.0, outputs
+
     def _enqueue(self, j):
         """The next batch into set j: the stages of the class docstring, in its order, on the stream next_stream() gives."""
         import torch
@@ -2692,6 +2952,10 @@ class FlowLoader:
         elif self.crop is not None:
             g.crop(t.frame, t.sharp, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
                    recs_out=t.window_recs, stream=s)
+        if self.reproject is not None:
+            frames, fb_thresh, _ = self.reproject
+            g.reproject((t.sharp["image0"], t.sharp["image1"]), (t.sharp["flow"], t.sharp.get("flow1")), (t.sharp.get("occ0"), t.sharp.get("occ1")),
+                        out=t.reproject[0], rows=t.reproject[1], fb_thresh=fb_thresh, frames=frames, stream=s, size=size)
         if self.motion_blur is not None:
             ranges, frames = self.motion_blur
             pick = lambda a, b: tuple(t_ if f in frames else None for f, t_ in enumerate((a, b)))  # noqa: E731
@@ -2727,6 +2991,10 @@ class FlowLoader:
         more = {k: v for k, v in t.planes.items() if k not in PACK_PLANES}
         if t.window_recs is not None:
             more["spatial" if self.spatial is not None else "crop"] = t.window_recs
+        if t.reproject is not None:
+            more.update(t.reproject[0])
+            if t.reproject[1] is not None:
+                more["reproject"] = t.reproject[1]
         if t.blur is not None:
             more["motion_blur"] = t.blur
         if t.photo is not None:

@@ -813,4 +813,108 @@ int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int w
   return OFDG_OK;
 }
 
+// ofdg_reproject on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The displacement, the inside
+// test, the tap, the warped byte, the backward displacement, the residual and the argument rules are the functions the kernel
+// runs (csrc/ofdg_device.h); elements are moved with memcpy.
+int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int width, int height) {
+  const DevReprojJob* const j = reinterpret_cast<const DevReprojJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = reproj_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_reproject: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int ses = fmt_elem_bytes(j->img_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  const bool with_err = reproj_with_err(*j);
+  const long long thr2 = (long long)j->fb_thresh_q8 * j->fb_thresh_q8;
+  uint8_t* const rows = reinterpret_cast<uint8_t*>(j->rows);
+  if (rows && !(j->flags & OFDG_REPROJ_ACCUMULATE)) std::memset(rows, 0, sizeof(DevReprojRow) * (size_t)n_samples);
+  for (int i = 0; i < n_samples; ++i)
+    for (int f = 0; f < 2; ++f) {
+      if (!((j->flags >> f) & 1)) continue;
+      const bool with_fb = reproj_with_fb(*j, f), with_own = j->img[f] != nullptr, with_other = j->img[1 - f] != nullptr;
+      const FlowPlane flow{j->flow[f], j->flow_fmt}, back{j->flow[1 - f], j->flow_fmt};
+      const OccPlane occ{j->occ[f], j->occ_fmt};
+      const size_t fu = (size_t)i * 2 * plane, fv = fu + plane;
+      const auto byte_at = [&](int g, int c, int x, int y) -> uint32_t {
+        const uint8_t* const sp = static_cast<const uint8_t*>(j->img[g]) + (size_t)i * 3 * plane * ses;
+        const size_t e = (size_t)c * plane + (size_t)spatial_clamp(y, height) * width + spatial_clamp(x, width);
+        if (ses == 1) return sp[e];
+        float v;
+        std::memcpy(&v, sp + 4 * e, 4);
+        return (uint32_t)photo_index(v);
+      };
+      DevReprojFrameRow r;
+      if (rows) std::memcpy(&r, rows + sizeof(DevReprojRow) * (size_t)i + sizeof(r) * (size_t)f, sizeof(r));
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          const size_t p = (size_t)y * width + x;
+          const float u = flow.at(fu + p), v = flow.at(fv + p);
+          const bool bad = !(mblur_finite(u) && mblur_finite(v));
+          const int Dx = bad ? 0 : reproj_q8(u), Dy = bad ? 0 : reproj_q8(v);
+          const bool in = !bad && reproj_inside(256 * x + Dx, 256 * y + Dy, width, height);
+          uint32_t w[3] = {0u, 0u, 0u}, err = 0u;
+          long long e2 = 0;
+          float fb2 = 0.0f;
+          if (in) {
+            const int Qx = reproj_coord(256 * x + Dx, width), Qy = reproj_coord(256 * y + Dy, height);
+            const int ix = Qx >> 8, iy = Qy >> 8, fx = Qx & 255, fy = Qy & 255;
+            if (with_other)
+              for (int c = 0; c < 3; ++c) {
+                w[c] = reproj_byte(mblur_tap(byte_at(1 - f, c, ix, iy), byte_at(1 - f, c, ix + 1, iy), byte_at(1 - f, c, ix, iy + 1), byte_at(1 - f, c, ix + 1, iy + 1), fx, fy));
+                if (with_own) {
+                  const uint32_t own = byte_at(f, c, x, y), d = w[c] > own ? w[c] - own : own - w[c];
+                  err = d > err ? d : err;
+                }
+              }
+            if (with_fb) {
+              const size_t xa = (size_t)spatial_clamp(ix, width), xb = (size_t)spatial_clamp(ix + 1, width);
+              const size_t ya = (size_t)spatial_clamp(iy, height) * width, yb = (size_t)spatial_clamp(iy + 1, height) * width;
+              float b[2][4];
+              bool finite = true;
+              for (int k = 0; k < 2; ++k) {
+                const size_t o = fu + (size_t)k * plane;
+                b[k][0] = back.at(o + ya + xa); b[k][1] = back.at(o + ya + xb); b[k][2] = back.at(o + yb + xa); b[k][3] = back.at(o + yb + xb);
+                for (int t = 0; t < 4; ++t) finite = finite && mblur_finite(b[k][t]);
+              }
+              if (finite) {
+                e2 = reproj_e2(Dx, Dy, reproj_back(b[0][0], b[0][1], b[0][2], b[0][3], fx, fy), reproj_back(b[1][0], b[1][1], b[1][2], b[1][3], fx, fy));
+                fb2 = reproj_fb2(e2);
+              } else {
+                e2 = kReprojE2Sat;
+                fb2 = INFINITY;
+              }
+            }
+          }
+          for (int c = 0; c < 3 && j->warped[f]; ++c) {
+            uint8_t* const dp = static_cast<uint8_t*>(j->warped[f]) + (size_t)i * 3 * plane * des;
+            const float o = (float)w[c];
+            if (des == 1) dp[(size_t)c * plane + p] = (uint8_t)w[c];
+            else std::memcpy(dp + 4 * ((size_t)c * plane + p), &o, 4);
+          }
+          if (j->err[f]) static_cast<uint8_t*>(j->err[f])[(size_t)i * plane + p] = (uint8_t)err;
+          if (j->mask[f]) static_cast<uint8_t*>(j->mask[f])[(size_t)i * plane + p] = in ? 1 : 0;
+          if (j->fb2[f]) std::memcpy(static_cast<uint8_t*>(j->fb2[f]) + 4 * ((size_t)i * plane + p), &fb2, 4);
+          if (!rows) continue;
+          if (!in) { ++r.cnt[bad ? 0 : 1]; continue; }
+          const int hid = j->occ[f] && occ.at((size_t)i * plane + p) ? 1 : 0;
+          ++r.cnt[2 + hid];
+          if (with_err) {
+            r.sum_err[hid] += err;
+            if (!hid) { ++r.err_hist[err >> 4]; r.max_err_visible = err > r.max_err_visible ? err : r.max_err_visible; }
+          }
+          if (with_fb) {
+            if (e2 > thr2) ++r.n_fb_over[hid];
+            if (!hid) {
+              r.sum_fb2_visible += (unsigned long long)(e2 < 4294967295ll ? e2 : 4294967295ll);
+              r.max_fb2_visible = (unsigned long long)e2 > r.max_fb2_visible ? (unsigned long long)e2 : r.max_fb2_visible;
+            }
+          }
+        }
+      if (rows) std::memcpy(rows + sizeof(DevReprojRow) * (size_t)i + sizeof(r) * (size_t)f, &r, sizeof(r));
+    }
+  return OFDG_OK;
+}
+
 }  // extern "C"

@@ -4724,4 +4724,262 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
   }
 }
 
+// ---- Reprojection (ofdg_reproject, include/ofdg.h) -------------------------------------------------------------------------
+// One launch for both frames and every sample: blockIdx.x counts the kReprojTileW x kReprojTileH tiles of a frame, blockIdx.y
+// the samples, blockIdx.z the frames that are flagged.  A 4-wave workgroup owns a tile, a lane four consecutive pixels of one
+// row (width % 8 == 0: a lane's four pixels, and the eight of a pair of lanes, are whole or outside together), so the own
+// frame, the flow and the map are read as whole 16 / 8 / 4-byte pieces.  The other frame and the backward flow are gathered
+// from global memory at clamped indices (ubyte / ushort / dword loads), the coordinates of a target computed once for the
+// three channels and the two components: no index leaves a plane.  (A floating LDS window over the box of a tile's targets
+// lost to this gather by 1.2 to 1.6 times - one tap per pixel amortises no staging:
+// tools/patches/reproject_kernel_floating_window.patch, CHANGELOG.)  Stores are whole pieces, non-temporal: 16 bytes of
+// float32 a lane, 8 bytes of uint8 a pair of lanes, gathered by the even lane with a wave shuffle.  The presence of each
+// output, the destination format and the map's format are uniform run-time branches; the source format and the flow format
+// are template arguments (4 instantiations).
+// Rows: a lane sums its four pixels in registers (the six counts packed three to a word of 10-bit fields, the two error
+// sums two to a word: a wave holds 256 pixels), the wave reduces them with __shfl_xor and counts the histogram with ballots,
+// lane 0 (lanes 0..15 for the bins) writes the wave's slots in LDS - a row of slots per parity of the sample's turn, so one
+// barrier a sample suffices - and the workgroup issues one integer atomic per non-zero word of the (sample, frame) block:
+// atomicAdd on u32 / u64, atomicMax on u32 / u64.  No float atomics, so no bit depends on the order of arrival.  A launch
+// without rows runs none of this and no barrier.  The functions of the definition are the host twin's (csrc/ofdg_device.h).
+// No scratch.
+constexpr int kReprojThreads = 256;
+constexpr int kReprojTileW = 64, kReprojTileH = 16;
+constexpr int kReprojWords = 23;  // the 32-bit words of a frame's block ahead of `reserved`
+static_assert(kReprojTileW / 4 * kReprojTileH == kReprojThreads, "a lane per four pixels of the tile");
+static_assert(offsetof(DevReprojFrameRow, reserved) == 4 * kReprojWords && offsetof(DevReprojFrameRow, sum_err) == 96, "the words and the 64-bit sums the kernel adds to");
+template <bool kHalf>
+__device__ __forceinline__ float reproj_load_flow(const uint8_t* __restrict__ fp, uint32_t e) {
+  if constexpr (kHalf) return (float)reinterpret_cast<const _Float16*>(fp)[e];
+  else return reinterpret_cast<const float*>(fp)[e];
+}
+template <bool kSrcU8, bool kFlowHalf>
+__global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevReprojJob job, int n, int W, int H, uint32_t tiles_x) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  constexpr int kSES = kSrcU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
+  __shared__ uint32_t s_words[2][kReprojThreads / 64][kReprojWords];  // [parity of the sample's turn][wave]
+  __shared__ unsigned long long s_sums[2][kReprojThreads / 64][4];    // sum_err visible, hidden, sum_fb2_visible, max_fb2_visible
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int X0 = (int)(tx * kReprojTileW + (threadIdx.x & 15u) * 4u), Y = (int)(ty * kReprojTileH + (threadIdx.x >> 4));
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int f = (blockIdx.z != 0u || !(job.flags & OFDG_REPROJ_FRAME0)) ? 1 : 0;
+  const uint8_t* const s_own = static_cast<const uint8_t*>(f ? job.img[1] : job.img[0]);
+  const uint8_t* const s_other = static_cast<const uint8_t*>(f ? job.img[0] : job.img[1]);
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.flow[1] : job.flow[0]);
+  const uint8_t* const s_back = static_cast<const uint8_t*>(f ? job.flow[0] : job.flow[1]);
+  const uint8_t* const s_occ = static_cast<const uint8_t*>(f ? job.occ[1] : job.occ[0]);
+  uint8_t* const d_warped = static_cast<uint8_t*>(f ? job.warped[1] : job.warped[0]);
+  uint8_t* const d_err = static_cast<uint8_t*>(f ? job.err[1] : job.err[0]);
+  uint8_t* const d_mask = static_cast<uint8_t*>(f ? job.mask[1] : job.mask[0]);
+  float* const d_fb2 = static_cast<float*>(f ? job.fb2[1] : job.fb2[0]);
+  // what the launch has to compute: the taps of the other frame for warped, err and the rows' residuals, the backward taps
+  // for fb2 and the rows' counts (uniform)
+  const bool with_err = s_own && s_other && (d_err || job.rows), with_other = s_other && (d_warped || with_err);
+  const bool with_fb = s_back && (d_fb2 || job.rows);
+  const bool dst_u8 = job.dst_fmt == OFDG_FMT_U8, occ_u8 = job.occ_fmt == OFDG_FMT_U8;
+  const long long thr2 = (long long)job.fb_thresh_q8 * job.fb_thresh_q8;
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: reproj_arg_error)
+  const bool act = X0 < W && Y < H;
+  const uint32_t at = act ? (uint32_t)Y * (uint32_t)W + (uint32_t)X0 : 0u;  // the lane's first pixel in a channel
+  uint32_t turn = 0u;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y, turn ^= 1u) {
+    const uint8_t* const op = s_other + (size_t)i * 3 * plane * kSES;
+    const uint8_t* const bp = s_back + (size_t)i * 2 * plane * kFES;
+    float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t own[3][4] = {};
+    uint32_t hidden = 0u;  // bit p: the map says pixel p is hidden
+    if (act) {
+      const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
+      if constexpr (kFlowHalf) {
+        const f16x4 a = *reinterpret_cast<const f16x4*>(fp), b = *reinterpret_cast<const f16x4*>(fp + (size_t)plane * kFES);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { u[p] = (float)a[p]; v[p] = (float)b[p]; }
+      } else {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(fp), b = *reinterpret_cast<const f32x4*>(fp + (size_t)plane * kFES);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) { u[p] = a[p]; v[p] = b[p]; }
+      }
+      if (with_err) {
+        const uint8_t* const sp = s_own + (size_t)i * 3 * plane * kSES;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (kSrcU8) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)c * plane + at);
+            own[c][0] = w & 255u; own[c][1] = (w >> 8) & 255u; own[c][2] = (w >> 16) & 255u; own[c][3] = w >> 24;
+          } else {
+            const f32x4 e = *reinterpret_cast<const f32x4*>(sp + ((size_t)c * plane + at) * 4u);
+#pragma unroll
+            for (int p = 0; p < 4; ++p) own[c][p] = (uint32_t)photo_index(e[p]);
+          }
+        }
+      }
+      if (s_occ) {
+        if (occ_u8) {
+          const uint32_t o = *reinterpret_cast<const uint32_t*>(s_occ + (size_t)i * plane + at);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) hidden |= (((o >> (8 * p)) & 255u) != 0u ? 1u : 0u) << p;
+        } else {
+          const f32x4 o = *reinterpret_cast<const f32x4*>(s_occ + ((size_t)i * plane + at) * 4u);
+#pragma unroll
+          for (int p = 0; p < 4; ++p) hidden |= (o[p] != 0.0f ? 1u : 0u) << p;
+        }
+      }
+    }
+    uint32_t out[3][4] = {};
+    uint32_t errs = 0u, masks = 0u;  // a byte per pixel
+    float fb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    // the lane's part of the row
+    uint32_t cnt_a = 0u, cnt_b = 0u;  // 10-bit fields: bad, outside, visible | hidden, over visible, over hidden
+    uint32_t sum_err = 0u, max_err = 0u;  // 16-bit fields: visible, hidden
+    int bin[4] = {kReprojErrBins, kReprojErrBins, kReprojErrBins, kReprojErrBins};
+    unsigned long long sum_fb2 = 0ull, max_fb2 = 0ull;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+      const int Dx = bad ? 0 : reproj_q8(u[p]), Dy = bad ? 0 : reproj_q8(v[p]);
+      const int Qx0 = 256 * (X0 + p) + Dx, Qy0 = 256 * Y + Dy;
+      const bool in = act && !bad && reproj_inside(Qx0, Qy0, W, H);
+      uint32_t err = 0u;
+      long long e2 = 0;
+      if (in) {
+        const int Qx = reproj_coord(Qx0, W), Qy = reproj_coord(Qy0, H);
+        const int fx = Qx & 255, fy = Qy & 255;
+        const uint32_t xa = (uint32_t)spatial_clamp(Qx >> 8, W), xb = (uint32_t)spatial_clamp((Qx >> 8) + 1, W);
+        const uint32_t ya = (uint32_t)spatial_clamp(Qy >> 8, H) * (uint32_t)W, yb = (uint32_t)spatial_clamp((Qy >> 8) + 1, H) * (uint32_t)W;
+        masks |= 1u << (8 * p);
+        if (with_other) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const uint32_t o = (uint32_t)c * plane;
+            const uint32_t w = reproj_byte(mblur_tap(mblur_load_byte<kSrcU8>(op, o + ya + xa), mblur_load_byte<kSrcU8>(op, o + ya + xb),
+                                                     mblur_load_byte<kSrcU8>(op, o + yb + xa), mblur_load_byte<kSrcU8>(op, o + yb + xb), fx, fy));
+            out[c][p] = w;
+            const uint32_t d = w > own[c][p] ? w - own[c][p] : own[c][p] - w;
+            err = d > err ? d : err;
+          }
+          err = with_err ? err : 0u;
+          errs |= err << (8 * p);
+        }
+        if (with_fb) {
+          const float b0 = reproj_load_flow<kFlowHalf>(bp, ya + xa), b1 = reproj_load_flow<kFlowHalf>(bp, ya + xb);
+          const float b2 = reproj_load_flow<kFlowHalf>(bp, yb + xa), b3 = reproj_load_flow<kFlowHalf>(bp, yb + xb);
+          const float c0 = reproj_load_flow<kFlowHalf>(bp, plane + ya + xa), c1 = reproj_load_flow<kFlowHalf>(bp, plane + ya + xb);
+          const float c2 = reproj_load_flow<kFlowHalf>(bp, plane + yb + xa), c3 = reproj_load_flow<kFlowHalf>(bp, plane + yb + xb);
+          const bool finite = mblur_finite(b0) && mblur_finite(b1) && mblur_finite(b2) && mblur_finite(b3) && mblur_finite(c0) && mblur_finite(c1) &&
+                              mblur_finite(c2) && mblur_finite(c3);
+          if (finite) {
+            e2 = reproj_e2(Dx, Dy, reproj_back(b0, b1, b2, b3, fx, fy), reproj_back(c0, c1, c2, c3, fx, fy));
+            fb[p] = reproj_fb2(e2);
+          } else {
+            e2 = kReprojE2Sat;
+            fb[p] = __uint_as_float(0x7f800000u);
+          }
+        }
+      }
+      if (job.rows) {  // (uniform)
+        const bool hid = (hidden >> p) & 1u;
+        const bool vis = in && !hid;
+        const bool over = in && with_fb && e2 > thr2;
+        cnt_a += (act && bad ? 1u : 0u) | ((act && !bad && !in ? 1u : 0u) << 10) | ((vis ? 1u : 0u) << 20);
+        cnt_b += (in && hid ? 1u : 0u) | ((over && !hid ? 1u : 0u) << 10) | ((over && hid ? 1u : 0u) << 20);
+        if (with_err) {
+          sum_err += in ? (hid ? err << 16 : err) : 0u;
+          max_err = vis && err > max_err ? err : max_err;
+          bin[p] = vis ? (int)(err >> 4) : kReprojErrBins;
+        }
+        if (with_fb && vis) {
+          sum_fb2 += (unsigned long long)(e2 < 4294967295ll ? e2 : 4294967295ll);
+          max_fb2 = (unsigned long long)e2 > max_fb2 ? (unsigned long long)e2 : max_fb2;
+        }
+      }
+    }
+    // (the lanes of a pair are inside together: X0 of the even one is a multiple of 8)
+    if (d_warped) {
+      if (dst_u8) {
+        uint8_t* const dp = d_warped + (size_t)i * 3 * plane;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
+          const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
+          if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
+        }
+      } else {
+        uint8_t* const dp = d_warped + (size_t)i * 3 * plane * 4u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
+          if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
+        }
+      }
+    }
+    if (d_err) {
+      const u32x2 o = {errs, (uint32_t)__shfl_down((int)errs, 1)};
+      if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_err + (size_t)i * plane + at));
+    }
+    if (d_mask) {
+      const u32x2 o = {masks, (uint32_t)__shfl_down((int)masks, 1)};
+      if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_mask + (size_t)i * plane + at));
+    }
+    if (d_fb2) {
+      const f32x4 o = {fb[0], fb[1], fb[2], fb[3]};
+      if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(d_fb2 + (size_t)i * plane + at));
+    }
+    if (job.rows) {  // (uniform: every lane of the workgroup is here)
+      uint32_t hist = 0u;  // lane b: the wave's count of bin b
+      if (with_err) {
+#pragma unroll
+        for (int b = 0; b < kReprojErrBins; ++b) {
+          const uint32_t k = (uint32_t)(__popcll(__ballot(bin[0] == b)) + __popcll(__ballot(bin[1] == b)) + __popcll(__ballot(bin[2] == b)) + __popcll(__ballot(bin[3] == b)));
+          hist = lane == b ? k : hist;
+        }
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        cnt_a += (uint32_t)__shfl_xor((int)cnt_a, d, 64);
+        cnt_b += (uint32_t)__shfl_xor((int)cnt_b, d, 64);
+        sum_err += (uint32_t)__shfl_xor((int)sum_err, d, 64);
+        const uint32_t me = (uint32_t)__shfl_xor((int)max_err, d, 64);
+        max_err = me > max_err ? me : max_err;
+        sum_fb2 += (unsigned long long)__shfl_xor((long long)sum_fb2, d, 64);
+        const unsigned long long mf = (unsigned long long)__shfl_xor((long long)max_fb2, d, 64);
+        max_fb2 = mf > max_fb2 ? mf : max_fb2;
+      }
+      uint32_t* const sw = s_words[turn][wave];
+      if (lane < kReprojErrBins) sw[4 + lane] = hist;
+      if (lane == 0) {
+        sw[0] = cnt_a & 1023u; sw[1] = (cnt_a >> 10) & 1023u; sw[2] = cnt_a >> 20; sw[3] = cnt_b & 1023u;
+        sw[20] = max_err; sw[21] = (cnt_b >> 10) & 1023u; sw[22] = cnt_b >> 20;
+        s_sums[turn][wave][0] = sum_err & 65535u; s_sums[turn][wave][1] = sum_err >> 16;
+        s_sums[turn][wave][2] = sum_fb2; s_sums[turn][wave][3] = max_fb2;
+      }
+      __syncthreads();  // (a wave is at most one barrier ahead of another, and the next sample's slots are the other row's)
+      DevReprojFrameRow* const fr = &job.rows[i].frame[f];
+      if (threadIdx.x < (uint32_t)kReprojWords) {
+        const uint32_t t = threadIdx.x, a = s_words[turn][0][t], b = s_words[turn][1][t], c = s_words[turn][2][t], d = s_words[turn][3][t];
+        uint32_t* const word = reinterpret_cast<uint32_t*>(fr) + t;
+        if (t == 20u) {
+          const uint32_t m = max(max(a, b), max(c, d));
+          if (m) atomicMax(word, m);
+        } else {
+          const uint32_t s = a + b + c + d;
+          if (s) atomicAdd(word, s);
+        }
+      } else if (threadIdx.x >= 64u && threadIdx.x < 68u) {
+        const uint32_t t = threadIdx.x - 64u;
+        const unsigned long long a = s_sums[turn][0][t], b = s_sums[turn][1][t], c = s_sums[turn][2][t], d = s_sums[turn][3][t];
+        unsigned long long* const word = reinterpret_cast<unsigned long long*>(fr) + 12 + t;
+        if (t == 3u) {
+          const unsigned long long m = max(max(a, b), max(c, d));
+          if (m) atomicMax(word, m);
+        } else {
+          const unsigned long long s = a + b + c + d;
+          if (s) atomicAdd(word, s);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur, ofdg_reproject
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -291,7 +291,8 @@ struct PostOp {
 };
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
-// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel.
+// 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
+// 4 reproject_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1907,6 +1908,40 @@ int ofdg_motion_blur(ofdg_ctx* c, const struct ofdg_mblur_job* job, int n_sample
         hipLaunchKernelGGL((mblur_kernel<decltype(src_u8)::value, decltype(dst_u8)::value, decltype(half)::value>), g, dim3(kMblurThreads), 0, st, *j,
                            n_samples, W, H, tiles_x);
       });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Reprojection of caller-given frames through their flows: the rows cleared on `stream` unless they accumulate, then one kernel
+// for both frames and every sample.
+int ofdg_reproject(ofdg_ctx* c, const struct ofdg_reproject_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_reproject"};
+  const DevReprojJob* const j = reinterpret_cast<const DevReprojJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = reproj_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = reproj_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    OFDG_TRY(op.aligned(f ? "img[1]" : "img[0]", j->img[f], j->img_fmt));
+    OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
+    if (j->occ[f]) OFDG_TRY(op.aligned(f ? "occ[1]" : "occ[0]", j->occ[f], j->occ_fmt));
+    if ((uintptr_t)j->warped[f] & 15) return op.fail(std::string(f ? "warped[1]" : "warped[0]") + " must be 16-byte aligned");
+    if ((uintptr_t)j->err[f] & 15) return op.fail(std::string(f ? "err[1]" : "err[0]") + " must be 16-byte aligned");
+    if ((uintptr_t)j->mask[f] & 15) return op.fail(std::string(f ? "mask[1]" : "mask[0]") + " must be 16-byte aligned");
+    if ((uintptr_t)j->fb2[f] & 15) return op.fail(std::string(f ? "fb2[1]" : "fb2[0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->rows & 15) return op.fail("rows must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  if (j->rows && !(j->flags & OFDG_REPROJ_ACCUMULATE)) HIP_OK(c, hipMemsetAsync(j->rows, 0, sizeof(DevReprojRow) * (size_t)n_samples, st));
+  const uint32_t tiles_x = ((uint32_t)W + kReprojTileW - 1) / kReprojTileW, tiles_y = ((uint32_t)H + kReprojTileH - 1) / kReprojTileH;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), ((j->flags & OFDG_REPROJ_FRAME0) ? 1u : 0u) + ((j->flags & OFDG_REPROJ_FRAME1) ? 1u : 0u));
+  with_bool(j->img_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
+      hipLaunchKernelGGL((reproject_kernel<decltype(src_u8)::value, decltype(half)::value>), g, dim3(kReprojThreads), 0, st, *j, n_samples, W, H, tiles_x);
     });
   });
   HIP_OK(c, hipGetLastError());

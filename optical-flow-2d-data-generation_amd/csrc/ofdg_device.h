@@ -1317,6 +1317,149 @@ inline const char* mblur_arg_error(const DevMblurJob* j, int n, int width, int h
   return nullptr;
 }
 
+// ---- Reprojection (ofdg_reproject, include/ofdg.h) -------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job and the row as the kernel takes them, the 24.8
+// displacement, the inside test, the warped byte, the backward displacement at the target, the residual and the argument
+// rules.  The tap is mblur_tap, the finite test mblur_finite, the clamps spatial_clamp, the byte of a float32 photo_index.
+// Behind the two float32 products everything is integers.
+constexpr int kReprojErrBins = OFDG_REPROJ_ERR_BINS;
+constexpr long long kReprojE2Sat = 1ll << 47;  // e2 of a non-finite backward tap: ex = ey = 2^23
+struct DevReprojFrameRow {  // ofdg_reproject_frame_row, field for field: the kernel adds to the words with unsigned atomics
+  uint32_t cnt[4];          // n_bad, n_outside, n_visible, n_hidden
+  uint32_t err_hist[kReprojErrBins];
+  uint32_t max_err_visible;
+  uint32_t n_fb_over[2];    // visible, hidden
+  uint32_t reserved;
+  unsigned long long sum_err[2];  // visible, hidden
+  unsigned long long sum_fb2_visible, max_fb2_visible;
+};
+struct DevReprojRow { DevReprojFrameRow frame[2]; };
+struct DevReprojJob {  // struct ofdg_reproject_job, field for field
+  const void* img[2];
+  const void* flow[2];
+  const void* occ[2];
+  void* warped[2];
+  void* err[2];
+  void* mask[2];
+  void* fb2[2];
+  DevReprojRow* rows;
+  int32_t width, height, img_fmt, dst_fmt, flow_fmt, occ_fmt, flags, fb_thresh_q8;
+  int32_t reserved[2];
+};
+static_assert(sizeof(ofdg_reproject_frame_row) == sizeof(DevReprojFrameRow) && sizeof(DevReprojFrameRow) == 128 &&
+              offsetof(ofdg_reproject_frame_row, n_bad) == offsetof(DevReprojFrameRow, cnt) && offsetof(ofdg_reproject_frame_row, err_hist) == offsetof(DevReprojFrameRow, err_hist) &&
+              offsetof(ofdg_reproject_frame_row, max_err_visible) == offsetof(DevReprojFrameRow, max_err_visible) && offsetof(DevReprojFrameRow, max_err_visible) == 80 &&
+              offsetof(ofdg_reproject_frame_row, n_fb_over_visible) == offsetof(DevReprojFrameRow, n_fb_over) &&
+              offsetof(ofdg_reproject_frame_row, sum_err_visible) == offsetof(DevReprojFrameRow, sum_err) && offsetof(DevReprojFrameRow, sum_err) == 96 &&
+              offsetof(ofdg_reproject_frame_row, sum_fb2_visible) == offsetof(DevReprojFrameRow, sum_fb2_visible) &&
+              offsetof(ofdg_reproject_frame_row, max_fb2_visible) == offsetof(DevReprojFrameRow, max_fb2_visible) && offsetof(DevReprojFrameRow, max_fb2_visible) == 120,
+              "ofdg_reproject_frame_row: 128 bytes without padding, the layout the kernel adds to");
+static_assert(sizeof(ofdg_reproject_row) == sizeof(DevReprojRow) && sizeof(DevReprojRow) == 256 && offsetof(ofdg_reproject_row, frame) == 0,
+              "ofdg_reproject_row: 256 bytes without padding, a block per frame");
+static_assert(sizeof(struct ofdg_reproject_job) == sizeof(DevReprojJob) && sizeof(DevReprojJob) == 160 && offsetof(struct ofdg_reproject_job, flow) == offsetof(DevReprojJob, flow) &&
+              offsetof(struct ofdg_reproject_job, occ) == offsetof(DevReprojJob, occ) && offsetof(struct ofdg_reproject_job, warped) == offsetof(DevReprojJob, warped) &&
+              offsetof(struct ofdg_reproject_job, err) == offsetof(DevReprojJob, err) && offsetof(struct ofdg_reproject_job, mask) == offsetof(DevReprojJob, mask) &&
+              offsetof(struct ofdg_reproject_job, fb2) == offsetof(DevReprojJob, fb2) && offsetof(struct ofdg_reproject_job, rows) == offsetof(DevReprojJob, rows) &&
+              offsetof(DevReprojJob, rows) == 112 && offsetof(struct ofdg_reproject_job, width) == offsetof(DevReprojJob, width) &&
+              offsetof(struct ofdg_reproject_job, img_fmt) == offsetof(DevReprojJob, img_fmt) && offsetof(struct ofdg_reproject_job, occ_fmt) == offsetof(DevReprojJob, occ_fmt) &&
+              offsetof(struct ofdg_reproject_job, flags) == offsetof(DevReprojJob, flags) && offsetof(struct ofdg_reproject_job, fb_thresh_q8) == offsetof(DevReprojJob, fb_thresh_q8) &&
+              offsetof(DevReprojJob, fb_thresh_q8) == 148 && offsetof(struct ofdg_reproject_job, reserved) == offsetof(DevReprojJob, reserved),
+              "struct ofdg_reproject_job: 160 bytes, the layout the kernel takes");
+// A finite displacement component in 24.8: one float32 product (an overflow to an infinity lands on the clamp), the clamp,
+// ties to even.
+OFDG_HD_FN int reproj_q8(float d) {
+  float h = d * 256.0f;
+  h = h < -1073741824.0f ? -1073741824.0f : h > 1073741824.0f ? 1073741824.0f : h;
+  return (int)rintf(h);
+}
+// Is the rounded target of the 24.8 coordinate (Qx, Qy) a pixel of the plane?
+OFDG_HD_FN bool reproj_inside(int Qx, int Qy, int W, int H) {
+  const int rx = (Qx + 128) >> 8, ry = (Qy + 128) >> 8;
+  return rx >= 0 && rx <= W - 1 && ry >= 0 && ry <= H - 1;
+}
+// a 24.8 coordinate clamped into the plane: side is the width or the height
+OFDG_HD_FN int reproj_coord(int Q, int side) {
+  const int hi = 256 * (side - 1);
+  return Q < 0 ? 0 : Q > hi ? hi : Q;
+}
+// the warped byte of a tap (mblur_tap: at most 65280)
+OFDG_HD_FN uint32_t reproj_byte(uint32_t t) { return (t + 128u) >> 8; }
+// One component of the backward displacement at the target, in 24.8: the four finite elements in Q8 under the tap's
+// weights, in int64.
+OFDG_HD_FN int reproj_back(float b00, float b10, float b01, float b11, int fx, int fy) {
+  const long long T = (long long)((256 - fx) * (256 - fy)) * reproj_q8(b00) + (long long)(fx * (256 - fy)) * reproj_q8(b10) +
+                      (long long)((256 - fx) * fy) * reproj_q8(b01) + (long long)(fx * fy) * reproj_q8(b11);
+  return (int)((T + 32768) >> 16);
+}
+// the squared forward-backward residual in units of 2^-16 px^2: each component clamped to 2^23 on its own
+OFDG_HD_FN long long reproj_e2(int Dx, int Dy, int bx, int by) {
+  long long ex = (long long)Dx + bx, ey = (long long)Dy + by;
+  ex = ex < -8388608 ? -8388608 : ex > 8388608 ? 8388608 : ex;
+  ey = ey < -8388608 ? -8388608 : ey > 8388608 ? 8388608 : ey;
+  return ex * ex + ey * ey;
+}
+OFDG_HD_FN float reproj_fb2(long long e2) { return (float)e2 * 1.52587890625e-05f; }
+// what a frame's block of the row can hold, from the inputs that are given
+OFDG_HD_FN bool reproj_with_err(const DevReprojJob& j) { return j.img[0] && j.img[1]; }
+OFDG_HD_FN bool reproj_with_fb(const DevReprojJob& j, int f) { return j.flow[1 - f] != nullptr; }
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* reproj_plane_size(const DevReprojJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The argument rules ofdg_reproject and ofdg_host_reproject share: the first rule broken, or nullptr.  width, height: what
+// reproj_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* reproj_arg_error(const DevReprojJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->img_fmt != OFDG_FMT_F32 && j->img_fmt != OFDG_FMT_U8) return "img_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if ((j->occ[0] || j->occ[1]) && j->occ_fmt != OFDG_FMT_F32 && j->occ_fmt != OFDG_FMT_U8) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags & ~(OFDG_REPROJ_FRAME0 | OFDG_REPROJ_FRAME1 | OFDG_REPROJ_ACCUMULATE)) return "flags holds unknown bits";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (j->fb_thresh_q8 < 0 || j->fb_thresh_q8 > OFDG_REPROJ_MAX_FB_THRESH_Q8) return "fb_thresh_q8 must lie in 0..2^23";
+  if (!(j->flags & (OFDG_REPROJ_FRAME0 | OFDG_REPROJ_FRAME1))) return "flags: no frame is flagged";
+  bool any = j->rows != nullptr;
+  for (int f = 0; f < 2; ++f) {
+    const bool planes = j->warped[f] || j->err[f] || j->mask[f];
+    if (!((j->flags >> f) & 1)) {
+      if (planes || j->fb2[f]) return f ? "flags: frame 1 has an output but is not flagged" : "flags: frame 0 has an output but is not flagged";
+      continue;
+    }
+    any = any || planes || j->fb2[f];
+    if (!j->flow[f]) return f ? "flow[1]: a flagged frame needs its flow" : "flow[0]: a flagged frame needs its flow";
+    if (planes && !j->img[1 - f]) return f ? "img[0]: warped, err and mask of frame 1 need the other frame" : "img[1]: warped, err and mask of frame 0 need the other frame";
+    if (j->err[f] && !j->img[f]) return f ? "img[1]: err of frame 1 needs its own frame" : "img[0]: err of frame 0 needs its own frame";
+    if (j->fb2[f] && !j->flow[1 - f]) return f ? "flow[0]: fb2 of frame 1 needs both flows" : "flow[1]: fb2 of frame 0 needs both flows";
+  }
+  if (!any) return "rows: no output is given";
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[16];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  const auto add = [&](const void* p, unsigned long long bytes, bool dst) {
+    if (p) r[nr++] = Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, dst};
+  };
+  for (int f = 0; f < 2; ++f) {
+    add(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
+    add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
+    add(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
+    add(j->warped[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
+    add(j->err[f], plane, true);
+    add(j->mask[f], plane, true);
+    add(j->fb2[f], plane * 4, true);
+  }
+  add(j->rows, (unsigned long long)n * sizeof(DevReprojRow), true);
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a destination range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.

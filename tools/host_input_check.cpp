@@ -15,6 +15,8 @@
 //                                       their inputs), against the same planes at an aligned one
 //   host_input_check mblur              ofdg_host_motion_blur and ofdg_motion_blur_draw on exactly sized heap buffers: every
 //                                       format, extreme flows, given and drawn records, every refusal
+//   host_input_check reproject          ofdg_host_reproject on exactly sized heap buffers: every format pair, every presence
+//                                       subset of the outputs and of the frames, extreme flows and frames, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -361,13 +363,128 @@ int mblur() {
   std::printf("mblur calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
   return refused == 23 ? 0 : 1;
 }
+
+// ofdg_host_reproject on heap buffers of exactly the planes' sizes (a byte read or written beside one is a report): the 16
+// format combinations (frames, destination, flow, map), every subset of warped / err / mask / fb2 / rows for frame 0, frame 1
+// and both, flows that hold NaN, infinities, +-3e38, +-65504 and targets beyond every border, float32 frames with NaN and
+// 1e9, on 8x2 (a plane smaller than most displacements) and 72x40; then every refusal.
+int reproject() {
+  const float extreme[] = {0.0f, 3.25f, -40.5f, 3e38f, -3e38f, 65504.0f, -65504.0f, 1e-40f, -0.0f, 100.0f, -7.125f, 0.0039f, 0.5f, -0.5f};
+  const uint16_t extreme16[] = {0x0000, 0x4280, 0xd110, 0x7c00, 0xfc00, 0x7bff, 0xfbff, 0x0001, 0x8000, 0x5640, 0xc720, 0x7e00, 0x3800, 0xb800};
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 2; ++size) {
+    const int W = size ? 72 : 8, H = size ? 40 : 2, n = 3;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 16; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32, ff = fmts & 4 ? OFDG_FMT_F16 : OFDG_FMT_F32,
+                of = fmts & 8 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4), fb = n * 2 * px * (ff == OFDG_FMT_F16 ? 2 : 4),
+                   ob = n * px * (of == OFDG_FMT_U8 ? 1 : 4);
+      std::vector<uint8_t> img[2], flow[2], occ[2], warped[2], err[2], mask[2], fb2[2], rows((size_t)n * sizeof(ofdg_reproject_row), 0xA5);
+      uint32_t x = 4321u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        img[f].resize(sb); flow[f].resize(fb); occ[f].resize(ob);
+        warped[f].assign(db, 0xA5); err[f].assign(n * px, 0xA5); mask[f].assign(n * px, 0xA5); fb2[f].assign(n * px * 4, 0xA5);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          const float v = (e % 11) == 0 ? (e % 22 ? NAN : 1e9f) : (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          if (sf == OFDG_FMT_U8) img[f][e] = (uint8_t)(x >> 24);
+          else std::memcpy(img[f].data() + 4 * e, &v, 4);
+        }
+        for (size_t e = 0; e < n * 2 * px; ++e) {
+          const size_t k = (e / 3 + f) % 14;
+          if (ff == OFDG_FMT_F16) std::memcpy(flow[f].data() + 2 * e, &extreme16[k], 2);
+          else if (k == 11 && (e & 1)) { const float q = NAN; std::memcpy(flow[f].data() + 4 * e, &q, 4); }
+          else std::memcpy(flow[f].data() + 4 * e, &extreme[k], 4);
+        }
+        for (size_t e = 0; e < n * px; ++e) {
+          const float v = (e % 7) == 0 ? NAN : (e % 3) == 0 ? 1.0f : (e % 5) == 0 ? -0.0f : 0.0f;
+          if (of == OFDG_FMT_U8) occ[f][e] = (e % 3) == 0 ? 255 : 0;
+          else std::memcpy(occ[f].data() + 4 * e, &v, 4);
+        }
+      }
+      for (int frames = 1; frames < 4; ++frames)
+        for (int outs = 1; outs < 32; ++outs)
+          for (int maps = 0; maps < 2; ++maps) {
+            if (maps && (outs & 15) != 15) continue;  // (without maps: with every plane only)
+            struct ofdg_reproject_job job;
+            std::memset(&job, 0, sizeof job);
+            for (int f = 0; f < 2; ++f) {
+              job.img[f] = img[f].data(); job.flow[f] = flow[f].data();
+              if (!maps) job.occ[f] = occ[f].data();
+              if (!((frames >> f) & 1)) continue;
+              if (outs & 1) job.warped[f] = warped[f].data();
+              if (outs & 2) job.err[f] = err[f].data();
+              if (outs & 4) job.mask[f] = mask[f].data();
+              if (outs & 8) job.fb2[f] = fb2[f].data();
+            }
+            if (outs & 16) job.rows = (ofdg_reproject_row*)rows.data();
+            job.img_fmt = sf; job.dst_fmt = df; job.flow_fmt = ff; job.occ_fmt = of;
+            job.flags = frames | ((outs & 16) && (frames & 2) ? OFDG_REPROJ_ACCUMULATE : 0);
+            job.fb_thresh_q8 = outs & 1 ? 256 : OFDG_REPROJ_MAX_FB_THRESH_Q8;
+            const int rc = ofdg_host_reproject(&job, n, W, H);
+            if (rc) { std::printf("reproject: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+            ++calls;
+            for (int f = 0; f < 2; ++f)
+              sum = sum * 31 + fnv1a(warped[f].data(), warped[f].size()) + fnv1a(err[f].data(), err[f].size()) + fnv1a(mask[f].data(), mask[f].size()) + fnv1a(fb2[f].data(), fb2[f].size());
+            sum = sum * 31 + fnv1a(rows.data(), rows.size());
+          }
+    }
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    const size_t px = (size_t)n * W * H;
+    std::vector<uint8_t> img0(px * 12, 0), img1(px * 12, 0), flow0(px * 8, 0), flow1(px * 8, 0), occ0(px * 4, 0), warped(px * 12, 0xA5), err(px, 0xA5), mask(px, 0xA5), fb2(px * 4, 0xA5),
+        rows((size_t)n * sizeof(ofdg_reproject_row), 0xA5);
+    struct ofdg_reproject_job good;
+    std::memset(&good, 0, sizeof good);
+    good.img[0] = img0.data(); good.img[1] = img1.data(); good.flow[0] = flow0.data(); good.flow[1] = flow1.data(); good.occ[0] = occ0.data();
+    good.warped[0] = warped.data(); good.err[0] = err.data(); good.mask[0] = mask.data(); good.fb2[0] = fb2.data(); good.rows = (ofdg_reproject_row*)rows.data();
+    good.flags = OFDG_REPROJ_FRAME0; good.fb_thresh_q8 = 256;
+    const auto refuse = [&](struct ofdg_reproject_job j, int ns, int w, int h) {
+      if (ofdg_host_reproject(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_reproject: ", 21) == 0) ++refused;
+      else std::printf("reproject: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_reproject_job j;
+    if (ofdg_host_reproject(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.img_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.occ_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.flags = 9; refuse(j, n, W, H);
+    j = good; j.flags = OFDG_REPROJ_ACCUMULATE; refuse(j, n, W, H);
+    j = good; j.flags = OFDG_REPROJ_FRAME1; refuse(j, n, W, H);
+    j = good; j.reserved[1] = 1; refuse(j, n, W, H);
+    j = good; j.fb_thresh_q8 = -1; refuse(j, n, W, H);
+    j = good; j.fb_thresh_q8 = OFDG_REPROJ_MAX_FB_THRESH_Q8 + 1; refuse(j, n, W, H);
+    j = good; j.flow[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.flow[1] = nullptr; refuse(j, n, W, H);
+    j = good; j.img[1] = nullptr; refuse(j, n, W, H);
+    j = good; j.img[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.warped[0] = nullptr; j.err[0] = nullptr; j.mask[0] = nullptr; j.fb2[0] = nullptr; j.rows = nullptr; refuse(j, n, W, H);
+    j = good; j.warped[0] = img1.data(); refuse(j, n, W, H);
+    j = good; j.rows = (ofdg_reproject_row*)(fb2.data() + 16); refuse(j, n, W, H);
+    j = good; j.mask[0] = err.data() + px - 1; refuse(j, n, W, H);
+    const auto untouched = [](const std::vector<uint8_t>& v) { return std::all_of(v.begin(), v.end(), [](uint8_t b) { return b == 0xA5; }); };
+    if (!(untouched(warped) && untouched(err) && untouched(mask) && untouched(fb2) && untouched(rows))) { std::printf("reproject: a refusal wrote something\n"); return 1; }
+    if (ofdg_host_reproject(&good, n, W, H) != OFDG_OK) { std::printf("reproject: the valid call failed\n"); return 1; }
+  }
+  std::printf("reproject calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 24 ? 0 : 1;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
+  if (argc >= 2 && std::strcmp(argv[1], "reproject") == 0) return reproject();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject\n", argv[0]);
   return 2;
 }
