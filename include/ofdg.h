@@ -1151,7 +1151,7 @@ int ofdg_motion_blur_draw(uint32_t seed, long long index, const struct ofdg_mblu
  * reprojected, without fb2.
  *
  * Out of scope: sub-pixel affine-aware taps (affine-free: plain bilinear), the nearest label is not used to pick taps,
- * splatting / a forward warp, an in-place form, one row for the whole batch, rows mapped through ofdg_pack, frame 1 and fb2 in
+ * splatting / a forward warp (ofdg_splat below), an in-place form, one row for the whole batch, rows mapped through ofdg_pack, frame 1 and fb2 in
  * mode 9.
  */
 #define OFDG_REPROJ_FRAME0     1
@@ -1192,6 +1192,131 @@ int ofdg_reproject(ofdg_ctx* ctx, const struct ofdg_reproject_job* job, int n_sa
  * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
  * ofdg_host_last_error. */
 int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int width, int height);
+
+/*
+ * Splat: each frame pushed along its own ground-truth flow to the instant t in [0, 1] - the forward warp, the counterpart
+ * of ofdg_reproject's gather.  For frame f in {0, 1} ("own"; frame 1 - f is "other") every source pixel goes where the
+ * fraction t_q8[f] / 256 of flow[f] takes it - flow[0] the forward flow, flow[1] flow1 -, and where several land on one
+ * target pixel the generator's own order decides: the higher label (later in painter's order) wins, among equal labels the
+ * lowest source index.  Frame 0 pushed by t and frame 1 by 1 - t show the same instant, with the exact flows from it to both
+ * end frames; the targets nobody reached are the disocclusion holes, the sources that lost are the pixels covered at that
+ * instant.  The winner is an integer maximum per target, so the scatter gives the same bits on every run: the kernels,
+ * ofdg_host_splat and the numpy restatement of the tests agree byte for byte.  Every input is read only; NOT in place.
+ * fl32(.) marks a float32 rounding (no contraction).
+ *
+ * Inputs: img[f] is image f as [n,3,height,width] of img_fmt (OFDG_FMT_F32 or OFDG_FMT_U8; float32 frames hold byte values, see
+ * ofdg_photo) or NULL; flow[f] is [n,2,height,width] of flow_fmt (OFDG_FMT_F32 or OFDG_FMT_F16); label[f] is uint8
+ * [n,height,width] (label0 / label1) or NULL: every priority 0; occ[f] is [n,1,height,width] of occ_fmt (OFDG_FMT_F32 or
+ * OFDG_FMT_U8) or NULL, read by the rows only.  keys[f], uint32 [n,height,width] on the TARGET grid, is REQUIRED for a flagged
+ * frame: workspace and output, what it held before the call does not matter (the call clears it on `stream`), after the call
+ * it holds the winning keys.  Outputs, each optional on its own, per frame: image[f] [n,3,height,width] of dst_fmt (OFDG_FMT_F32
+ * or OFDG_FMT_U8), to_own[f] and to_other[f] [n,2,height,width] of oflow_fmt (OFDG_FMT_F32 or OFDG_FMT_F16), mask[f] uint8
+ * [n,1,height,width] on the TARGET grid, fate[f] uint8 [n,1,height,width] on the SOURCE grid; rows: n ofdg_splat_row.  flags
+ * holds OFDG_SPLAT_FRAME0 and / or OFDG_SPLAT_FRAME1, the frames that are worked on, and OFDG_SPLAT_ACCUMULATE.  width = height
+ * = 0: the context's frame; otherwise any size the context's rule allows, as in ofdg_photo, of at most OFDG_SPLAT_MAX_PIXELS
+ * pixels.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_splat_draw(seed, first_index + i, the job).  Either way it is
+ * sanitised before use, and the sanitised record is what recs_out[i] and the row's t_q8 receive.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, {seed ^ (uint32)(g >> 32) *
+ *    0x9E3779B9, (uint32)g}, block 0 at the counter {0, 0, 0x0c77, 0} (taken: 0x0fd9 the sampler, 0x0c70 crop, 0x0c71 and 0x0c72
+ *    photo, 0x0c73 spatial, 0x0c74 and 0x0c75 erase, 0x0c76 motion blur).  t = t_min_q8 + (int)(((uint64).x * (uint64)(t_max_q8
+ *    - t_min_q8 + 1)) >> 32);  t_q8 = {t, 256 - t}: frame 0 goes forward by t, frame 1 comes back by the rest, so both land
+ *    on the same instant.  reserved = 0.  (.y, .z, .w are not used.)
+ * 2. Sanitise.  Each t_q8[f] is clamped into 0..256; reserved = 0.
+ * 3. Source pixel s = (x, y) of a flagged frame f, T = t_q8[f], (u, v) the element of flow[f] widened to float32:
+ *    a. Bad.  u or v is not finite (exponent bits all set): the fate is 3.
+ *    b. Displacement in 24.8.  Dx = (int)rintf(clamp(fl32(u * 256.0f), -2^30, 2^30)) (ties to even), Dy likewise from v:
+ *       ofdg_reproject's step 2, bit for bit.
+ *    c. Scaled displacement.  Sx = (int)(((int64)Dx * T + 128) >> 8) (arithmetic shift);  Qx = 256 x + Sx;  rx = (Qx + 128)
+ *       >> 8 (arithmetic shift).  Sy, Qy, ry likewise.
+ *    d. Inside iff 0 <= rx < width and 0 <= ry < height; otherwise the fate is 2.
+ *    e. Key.  key = (L << 24) | (2^24 - 1 - (y * width + x)), L the label byte at s, 0 without a label plane.  Never 0, because
+ *       width * height <= 2^24 - 1.
+ *    f. Scatter.  keys[f][i][ry][rx] = max(itself, key) over all inside sources of sample i; the plane starts at 0.
+ * 4. Target pixel p = (px, py), K its final key.  K = 0, a hole: mask 0, every element of image, to_own and to_other there is
+ *    0 / +0.0.  Otherwise mask 1; the winner is the source s = 2^24 - 1 - (K & 0xFFFFFF) at (x, y) = (s % width, s / width).
+ *    image holds the three bytes of img[f] at s (the byte of an element: itself for uint8, the index rule of ofdg_photo for
+ *    float32); a uint8 destination stores the byte, a float32 one (float)byte.  to_own = ((float)(x - px), (float)(y - py)).
+ *    to_other = (fl32((float)(256 (x - px) + Dx)) * 2^-8, likewise y), Dx and Dy the winner's.  An OFDG_FMT_F16 oflow_fmt rounds
+ *    the float32 value once, to nearest even (an overflow becomes an infinity).  What p shows sat at p + to_own in frame f and
+ *    sits at p + to_other in frame 1 - f.
+ * 5. Fate of an inside source: 0 (shown) when the key at its target equals its own, else 1 (covered).
+ * 6. Row of sample i, block f (nothing is written to an unflagged frame's block).  n_bad, n_outside, n_inside count the source
+ *    pixels; n_filled and n_holes the target pixels; each triple / pair sums to width * height.  n_covered counts the sources
+ *    of fate 1 and equals n_inside - n_filled.  With occ[f]: n_covered_visible / n_covered_hidden split the covered sources
+ *    by occ[f] at the source.  With occ[1 - f]: n_hole_other_visible / n_hole_other_hidden split the holes by occ[1 - f] at the
+ *    hole.  An element is visible when it is zero (float32: compares equal to 0 - ofdg_reproject's rule 7), else hidden;
+ *    without the map both counts stay 0.  t_q8 = T.  Without OFDG_SPLAT_ACCUMULATE the call first writes every byte of the n
+ *    rows as zero on `stream`; with it the counts are added to and t_q8 is overwritten.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  A fixed number of
+ * launches for any n and both frames: the clears, splat_scatter_kernel, splat_resolve_kernel (left out when nothing but keys
+ * is asked for).  Integer atomics only, so no bit depends on the order of arrival.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, a size that
+ * breaks the rule above, width * height above OFDG_SPLAT_MAX_PIXELS, another format code (occ_fmt counts only when a map is
+ * given), unknown bits in flags, non-zero reserved, no frame flagged, a flagged frame without flow[f] or without keys[f], any
+ * pointer of an unflagged frame (but occ[f], which the other frame's holes are set against), image[f] without img[f]; with
+ * recs NULL, t_min_q8 or t_max_q8 outside 0..256 or t_min_q8 > t_max_q8; a misaligned pointer (inputs as the render calls ask:
+ * 16-byte float32, 8-byte binary16, 4-byte uint8; keys, outputs, rows and records 16-byte), a written range (keys, image,
+ * to_own, to_other, mask, fate, rows, recs_out) that overlaps any other range of the job, OFDG_STREAM_OWN before any render /
+ * forward call on the context.  Mode 9 has no flow1, no labels and no maps: there frame 0 can be splatted, every priority 0.
+ *
+ * Out of scope: bilinear / summation / softmax splatting, sub-pixel-closest tie-breaks, hole filling, per-pixel hit counts,
+ * an in-place form, planes of more than 2^24 - 1 pixels, frame 1 in mode 9.
+ */
+#define OFDG_SPLAT_FRAME0     1
+#define OFDG_SPLAT_FRAME1     2
+#define OFDG_SPLAT_ACCUMULATE 4   /* add to the rows instead of overwriting them */
+#define OFDG_SPLAT_MAX_PIXELS ((1 << 24) - 1)   /* width * height at most */
+typedef struct ofdg_splat_rec {             /* 16 bytes */
+  int32_t t_q8[2];                          /* the fraction of flow[f] frame f is pushed by, in 1/256 */
+  int32_t reserved[2];
+} ofdg_splat_rec;
+typedef struct ofdg_splat_frame_row {       /* 64 bytes without padding */
+  uint32_t n_bad, n_outside, n_inside;      /* source pixels; sum = width * height */
+  uint32_t n_filled, n_holes;               /* target pixels; sum = width * height */
+  uint32_t n_covered;                       /* = n_inside - n_filled */
+  uint32_t n_covered_visible, n_covered_hidden;       /* by occ[f] at the source; 0 without occ[f] */
+  uint32_t n_hole_other_visible, n_hole_other_hidden; /* by occ[1 - f] at the hole; 0 without occ[1 - f] */
+  uint32_t t_q8;                            /* the sanitised fraction used (overwritten, never added) */
+  uint32_t reserved[5];
+} ofdg_splat_frame_row;
+typedef struct ofdg_splat_row {             /* 128 bytes without padding: a block per frame */
+  ofdg_splat_frame_row frame[2];
+} ofdg_splat_row;
+struct ofdg_splat_job {                     /* 248 bytes (4 of padding at the end) */
+  const void* img[2];                       /* [n,3,height,width] of img_fmt: image0, image1, or NULL */
+  const void* flow[2];                      /* [n,2,height,width] of flow_fmt: flow, flow1 */
+  const uint8_t* label[2];                  /* [n,height,width]: label0, label1, or NULL: every priority 0 */
+  const void* occ[2];                       /* [n,1,height,width] of occ_fmt: occ0, occ1, or NULL: rows only */
+  uint32_t* keys[2];                        /* [n,height,width] DEVICE: REQUIRED for a flagged frame; workspace AND output */
+  void* image[2];                           /* [n,3,height,width] of dst_fmt, or NULL */
+  void* to_own[2];                          /* [n,2,height,width] of oflow_fmt, or NULL */
+  void* to_other[2];                        /* [n,2,height,width] of oflow_fmt, or NULL */
+  void* mask[2];                            /* uint8 [n,1,height,width] on the TARGET grid: 1 filled, 0 hole */
+  void* fate[2];                            /* uint8 [n,1,height,width] on the SOURCE grid: 0 shown, 1 covered, 2 outside, 3 bad */
+  ofdg_splat_row* rows;                     /* DEVICE, n rows, or NULL */
+  const ofdg_splat_rec* recs;               /* DEVICE, n records, or NULL: drawn */
+  ofdg_splat_rec* recs_out;                 /* DEVICE, n records, or NULL */
+  long long first_index;                    /* global index of sample 0 (the draw) */
+  uint32_t seed;                            /* (the draw) */
+  int32_t width, height;                    /* 0, 0: the context's frame */
+  int32_t img_fmt, dst_fmt, flow_fmt, oflow_fmt, occ_fmt;
+  int32_t flags;                            /* OFDG_SPLAT_* */
+  int32_t t_min_q8, t_max_q8;               /* range of the draw, 0..256 */
+  int32_t reserved[2];
+};
+int ofdg_splat(ofdg_ctx* ctx, const struct ofdg_splat_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes, keys, rows and records in host memory, no
+ * alignment asked of any pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_splat(const struct ofdg_splat_job* job, int n_samples, int width, int height);
+/* The record of global sample `index` under `seed` (step 1; pure, no GPU): of `ranges` only t_min_q8 and t_max_q8 are read.
+ * Not sanitised.  OFDG_EINVAL for a NULL argument or a range that breaks the rule above. */
+int ofdg_splat_draw(uint32_t seed, long long index, const struct ofdg_splat_job* ranges, ofdg_splat_rec* out);
 
 /* Checkpoint / resume of ofdg_forward: the number of batches this context has produced is its whole sampler
  * state (the reference cannot resume: a restarted job replays its 45 streams from their seeds).

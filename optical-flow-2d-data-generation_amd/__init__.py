@@ -113,6 +113,7 @@ EXPORTS = [
     "ofdg_erase", "ofdg_host_erase", "ofdg_erase_draw",
     "ofdg_motion_blur", "ofdg_host_motion_blur", "ofdg_motion_blur_draw",
     "ofdg_reproject", "ofdg_host_reproject",
+    "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1412,6 +1413,259 @@ def host_reproject(images, flows, occ=None, outputs=("rows",), frames=None, fb_t
     return out, rows
 
 
+# splat (ofdg_splat_rec / ofdg_splat_row / struct ofdg_splat_job / ofdg_splat, include/ofdg.h)
+SPLAT_FRAME0 = 1             # OFDG_SPLAT_FRAME0
+SPLAT_FRAME1 = 2             # OFDG_SPLAT_FRAME1
+SPLAT_ACCUMULATE = 4         # OFDG_SPLAT_ACCUMULATE
+SPLAT_MAX_PIXELS = (1 << 24) - 1   # OFDG_SPLAT_MAX_PIXELS
+SPLAT_REC_INTS = 4           # a record as int32 [4]: t_q8 of frame 0, of frame 1, then the two reserved words
+SPLAT_PLANES = ("image", "to_own", "to_other", "mask", "fate")   # the optional per-frame outputs
+SPLAT_OUTPUTS = ("keys",) + SPLAT_PLANES + ("rows",)   # "keys" is made for every frame whether it is named or not
+SPLAT_FATES = ("shown", "covered", "outside", "bad")   # the values 0..3 of a fate plane
+
+
+class SplatRec(C.Structure):
+    """ofdg_splat_rec: the fractions of one sample (16 bytes)."""
+    _fields_ = [("t_q8", C.c_int32 * 2), ("reserved", C.c_int32 * 2)]
+
+
+class SplatFrameRow(C.Structure):
+    """ofdg_splat_frame_row: one frame's block of a row (64 bytes)."""
+    _fields_ = [(name, C.c_uint32) for name in ("n_bad", "n_outside", "n_inside", "n_filled", "n_holes", "n_covered", "n_covered_visible",
+                                                "n_covered_hidden", "n_hole_other_visible", "n_hole_other_hidden", "t_q8")] + [("reserved", C.c_uint32 * 5)]
+
+
+class SplatRow(C.Structure):
+    """ofdg_splat_row: the blocks of frame 0 and frame 1 of one sample (128 bytes)."""
+    _fields_ = [("frame", SplatFrameRow * 2)]
+
+
+class SplatJob(C.Structure):
+    """struct ofdg_splat_job (248 bytes)."""
+    _fields_ = [(name, C.c_void_p * 2) for name in ("img", "flow", "label", "occ", "keys", "image", "to_own", "to_other", "mask", "fate")] + \
+               [("rows", C.c_void_p), ("recs", C.c_void_p), ("recs_out", C.c_void_p), ("first_index", C.c_longlong), ("seed", C.c_uint32)] + \
+               [(name, C.c_int32) for name in ("width", "height", "img_fmt", "dst_fmt", "flow_fmt", "oflow_fmt", "occ_fmt", "flags", "t_min_q8", "t_max_q8")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
+def _splat_dtype():
+    """The numpy dtype of one frame's block: a row is two of them."""
+    import numpy as np
+    return np.dtype([(name, "<u4") for name, _ in SplatFrameRow._fields_[:-1]] + [("reserved", "<u4", (5,))])
+
+
+def splat_key(name, f):
+    """The name of plane `name` ("keys" or one of SPLAT_PLANES) of frame f in the dicts of Generator.splat, host_splat and
+    FlowLoader: "keys0", "image1", "to_own0", "to_other1", "mask0", "fate1"."""
+    return "%s%d" % (name, f)
+
+
+_SPLAT_KEYS = {splat_key(name, f): (name, f) for name in SPLAT_PLANES for f in range(2)}
+
+
+def _splat_t_range(t):
+    """t= of a splat as (t_min_q8, t_max_q8): None - the whole range 0..256 -, a fraction in [0, 1] - fixed -, or a pair
+    (min, max) of fractions"""
+    lo, hi = (0.0, 1.0) if t is None else tuple(t) if isinstance(t, (tuple, list)) else (t, t)
+    lo, hi = int(round(float(lo) * 256.0)), int(round(float(hi) * 256.0))
+    if not 0 <= lo <= hi <= 256:
+        raise ValueError("t must be a fraction in [0, 1] or a pair (min, max) of them with min <= max, got %r" % (t,))
+    return lo, hi
+
+
+def _splat_frames(frames, flows, out, keys):
+    """frames= of a splat as a sorted tuple; None: the frames `out` and `keys` name, or, without any, those whose flow is given"""
+    if frames is None:
+        named = sorted({_SPLAT_KEYS[k][1] for k in out if k in _SPLAT_KEYS} | {f for f in range(2) if keys[f] is not None})
+        return tuple(named) if named else tuple(f for f in range(2) if flows[f] is not None)
+    frames = tuple(sorted(set(int(f) for f in frames)))
+    if not frames or any(f not in (0, 1) for f in frames):
+        raise ValueError("frames must hold 0 and / or 1, got %r" % (frames,))
+    return frames
+
+
+def splat_format(images, flows, labels, occ, out, keys, height=None, width=None):
+    """(n, height, width, image code, dst code, flow code, oflow code, occ code) of the planes of Generator.splat / host_splat:
+    images, flows, labels, occ and keys are pairs - (image0, image1), (flow, flow1), (label0, label1), (occ0, occ1), (keys0,
+    keys1) -, any member None (images, labels and occ themselves may be None); out a dict of splat_key names.  A frame is
+    float32 or uint8 [n,3,height,width], a flow float32 or float16 [n,2,height,width], a label plane uint8 [n,height,width], a
+    map float32 or uint8 [n,1,height,width], each kind of one dtype; a key plane int32 or uint32 [n,height,width]; "image*"
+    float32 or uint8 of one dtype, "to_own*" and "to_other*" float32 or float16 [n,2,height,width] of one dtype, "mask*" and
+    "fate*" uint8 [n,1,height,width].  Raises ValueError for anything else.  Looks at dtype and shape only (works on CPU
+    tensors and numpy arrays)."""
+    images, labels, occ = ((None, None) if pair is None else pair for pair in (images, labels, occ))
+    if flows is None or keys is None or any(len(pair) != 2 for pair in (images, flows, labels, occ, keys)):
+        raise ValueError("images, flows, labels, occ and keys must be pairs (frame 0, frame 1)")
+    unknown = sorted(set(out) - set(_SPLAT_KEYS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(sorted(_SPLAT_KEYS))))
+    given = [t for t in flows if t is not None]
+    if not given:
+        raise ValueError("flows must hold at least one flow")
+    shape = tuple(given[0].shape)
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 2 or (height is not None and shape[2:] != (height, width)):
+        raise ValueError("a flow must be [n,2,%s,%s], got %s" % (height or "height", width or "width", shape))
+    n, height, width = int(shape[0]), int(shape[2]), int(shape[3])
+    if height * width > SPLAT_MAX_PIXELS:
+        raise ValueError("a plane of a splat holds at most 2^24 - 1 pixels, got %d x %d" % (height, width))
+    image = tuple(out.get(splat_key("image", f)) for f in range(2))
+    oflow = tuple(out.get(splat_key(name, f)) for name in ("to_own", "to_other") for f in range(2))
+    codes = []
+    for what, group, table, ch, default in (("images", images, _IMAGE_CODES, 3, FMT_F32), ("image", image, _IMAGE_CODES, 3, FMT_F32),
+                                            ("flows", flows, _FLOW_CODES, 2, FMT_F32), ("to_own / to_other", oflow, _FLOW_CODES, 2, FMT_F32),
+                                            ("occ", occ, _OCC_CODES, 1, FMT_F32)):
+        names = set()
+        for f, t in enumerate(group):
+            if t is not None:
+                _check_plane("%s[%d]" % (what, f % 2), t, tuple(table), (n, ch, height, width))
+                names.add(_dtype_name(t))
+        if len(names) > 1:
+            raise ValueError("%s must have one dtype for both frames, got %s" % (what, sorted(names)))
+        codes.append(table[names.pop()] if names else default)
+    for f in range(2):
+        if labels[f] is not None:
+            _check_plane("labels[%d]" % f, labels[f], ("uint8",), (n, height, width))
+        if keys[f] is not None:
+            _check_plane("keys[%d]" % f, keys[f], ("int32", "uint32"), (n, height, width))
+    for key, t in out.items():
+        if _SPLAT_KEYS[key][0] in ("mask", "fate"):
+            _check_plane(key, t, ("uint8",), (n, 1, height, width))
+    return (n, height, width) + tuple(codes)
+
+
+def _splat_job(images, flows, labels, occ, out, keys, rows, ptr, codes, size, frames, t_range, recs, recs_out, first_index, seed, accumulate):
+    job = SplatJob()
+    images, labels, occ = ((None, None) if pair is None else pair for pair in (images, labels, occ))
+    for f in range(2):
+        job.img[f], job.flow[f], job.label[f], job.occ[f], job.keys[f] = (None if t is None else ptr(t) for t in (images[f], flows[f], labels[f], occ[f], keys[f]))
+    for key, t in out.items():
+        name, f = _SPLAT_KEYS[key]
+        getattr(job, name)[f] = ptr(t)
+    job.rows, job.recs, job.recs_out = rows, recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.img_fmt, job.dst_fmt, job.flow_fmt, job.oflow_fmt, job.occ_fmt = codes
+    job.flags = sum(1 << f for f in frames) | (SPLAT_ACCUMULATE if accumulate else 0)
+    job.t_min_q8, job.t_max_q8 = t_range
+    return job
+
+
+def _splat_only(pair, frames):
+    """a pair of inputs with the members of the frames that are not worked on left out (the call refuses them)"""
+    return None if pair is None else tuple(t if f in frames else None for f, t in enumerate(pair))
+
+
+def splat_draw(seed, index, t=None):
+    """ofdg_splat_draw (pure, no GPU): the record of global sample `index` under `seed` for t= (None: 0..1; a fraction; a pair
+    (min, max)), before sanitising, as int32 [4] (SPLAT_REC_INTS): t_q8 of frame 0, of frame 1 (their sum is 256), 0, 0."""
+    import numpy as np
+    out, job = SplatRec(), SplatJob()
+    job.t_min_q8, job.t_max_q8 = _splat_t_range(t)
+    _host_check(lib().ofdg_splat_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return np.frombuffer(bytearray(out), np.int32).copy()
+
+
+def alloc_splat(n, height, width, frames=(0,), outputs=SPLAT_OUTPUTS, image_dtype=None, flow_dtype=None, device="cuda"):
+    """(out, keys, rows, recs) of Generator.splat for n samples: out the dict of the planes among `outputs` (SPLAT_OUTPUTS) for
+    each frame of `frames` under their splat_key names - "image*" [n,3,height,width] of image_dtype (default torch.float32),
+    "to_own*" and "to_other*" [n,2,height,width] of flow_dtype (default torch.float32), "mask*" and "fate*" uint8
+    [n,1,height,width] -, keys the pair of int32 [n,height,width] key planes (None for a frame not among `frames`; made whether
+    "keys" is among outputs or not: the call needs them), rows the zeroed uint8 [n,128] rows when "rows" is among outputs,
+    else None, recs the int32 [n,4] records (recs_out).  The planes are not filled: the call writes every element."""
+    import torch
+    unknown = sorted(set(outputs) - set(SPLAT_OUTPUTS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(SPLAT_OUTPUTS)))
+    if n < 1:
+        raise ValueError("alloc_splat needs n >= 1, got %d" % n)
+    frames = _splat_frames(frames, (None, None), {}, (None, None))
+    idt, fdt = torch.float32 if image_dtype is None else image_dtype, torch.float32 if flow_dtype is None else flow_dtype
+    shapes = {"image": (3, idt), "to_own": (2, fdt), "to_other": (2, fdt), "mask": (1, torch.uint8), "fate": (1, torch.uint8)}
+    out = {splat_key(name, f): torch.empty((n, shapes[name][0], height, width), dtype=shapes[name][1], device=device)
+           for f in frames for name in SPLAT_PLANES if name in outputs}
+    keys = tuple(torch.empty((n, height, width), dtype=torch.int32, device=device) if f in frames else None for f in range(2))
+    rows = torch.zeros((n, C.sizeof(SplatRow)), dtype=torch.uint8, device=device) if "rows" in outputs else None
+    return out, keys, rows, torch.empty((n, SPLAT_REC_INTS), dtype=torch.int32, device=device)
+
+
+def splat_numpy(rows=None, keys=None):
+    """What Generator.splat / host_splat filled (tensors or arrays; synchronise first), decoded, as a dict.  rows (uint8 [n,128]
+    or the structured array): "rows" the structured array [n,2] (sample, frame; the fields of ofdg_splat_frame_row) and, float64
+    [n,2] each, NaN where the count is 0: "share_holes" (of the target pixels), "share_covered" (of the inside sources),
+    "share_covered_hidden" (of the covered sources the frame's own map speaks of, those it calls hidden) and
+    "share_holes_other_hidden" (of the holes the other frame's map speaks of, those it calls hidden); "t" = t_q8 / 256.  keys (one
+    key plane [n,H,W]): "source" int32, the index y * W + x of the source that won each target, -1 for a hole, and "label"
+    uint8, the winner's label (0 for a hole)."""
+    import numpy as np
+    res = {}
+    if rows is not None:
+        r = np.ascontiguousarray(rows.cpu().numpy() if hasattr(rows, "cpu") else rows)
+        t = r.view(np.uint8).reshape(-1, C.sizeof(SplatRow)).view(_splat_dtype()).reshape(-1, 2).copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            per = lambda a, b: np.where(b > 0, a.astype(np.float64) / b, np.nan)  # noqa: E731
+            res.update({"rows": t, "t": t["t_q8"] / 256.0, "share_holes": per(t["n_holes"], t["n_filled"].astype(np.int64) + t["n_holes"]),
+                        "share_covered": per(t["n_covered"], t["n_inside"]),
+                        "share_covered_hidden": per(t["n_covered_hidden"], t["n_covered_visible"].astype(np.int64) + t["n_covered_hidden"]),
+                        "share_holes_other_hidden": per(t["n_hole_other_hidden"], t["n_hole_other_visible"].astype(np.int64) + t["n_hole_other_hidden"])})
+    if keys is not None:
+        k = np.ascontiguousarray(keys.cpu().numpy() if hasattr(keys, "cpu") else keys).view(np.uint32)
+        res["source"] = np.where(k != 0, SPLAT_MAX_PIXELS - (k & SPLAT_MAX_PIXELS).astype(np.int64), -1).astype(np.int32)
+        res["label"] = (k >> 24).astype(np.uint8)
+    return res
+
+
+def host_splat(images, flows, labels=None, occ=None, t=None, recs=None, outputs=SPLAT_OUTPUTS, frames=None, dst_dtype=None, oflow_dtype=None, rows=None,
+               accumulate=False, seed=0, first_index=0):
+    """ofdg_host_splat (no GPU) on numpy arrays: images None or the pair (image0, image1) of float32 or uint8 [n,3,H,W], flows
+    the pair (flow, flow1) of float32 or float16 [n,2,H,W], labels None or the pair (label0, label1) of uint8 [n,H,W], occ None
+    or the pair (occ0, occ1) of float32 or uint8 [n,1,H,W]; any member may be None.  t: None, a fraction or a pair (min, max) -
+    the record of sample i is splat_draw(seed, first_index + i, t) -, or recs: an int32 array [n,4] taken as given; either is
+    sanitised.  outputs: which of SPLAT_OUTPUTS to make, for each frame of `frames` (None: those whose flow is given); inputs of
+    the other frame are left out, but its map, which the holes are set against.  dst_dtype: np.float32 / np.uint8 of "image*",
+    default the images'; oflow_dtype: np.float32 / np.float16 of "to_own*" / "to_other*", default float32.  rows: the array a
+    former call returned, to add to with accumulate=True.  Returns (out, keys, rows, recs_used): the dict of planes under their
+    splat_key names, the pair of uint32 [n,H,W] key planes (None for a frame not worked on), the structured array [n,2]
+    (splat_numpy's "rows"; None without "rows") and the int32 [n,4] records after sanitising."""
+    import numpy as np
+    con = lambda pair: None if pair is None else tuple(None if a is None else np.ascontiguousarray(a) for a in pair)  # noqa: E731
+    images, flows, labels, occ = con(images), con(flows), con(labels), con(occ)
+    unknown = sorted(set(outputs) - set(SPLAT_OUTPUTS))
+    if unknown:
+        raise ValueError("unknown output(s) %s (known: %s)" % (unknown, ", ".join(SPLAT_OUTPUTS)))
+    given = [a for a in (flows or ()) if a is not None]
+    if not given or given[0].ndim != 4:
+        raise ValueError("flows must hold at least one flow [n,2,H,W]")
+    n, _, height, width = given[0].shape
+    frames = _splat_frames(frames, flows, {}, (None, None))
+    images, flows, labels = _splat_only(images, frames), _splat_only(flows, frames), _splat_only(labels, frames)
+    some = [a for a in (images or ()) if a is not None]
+    idt = np.dtype(dst_dtype if dst_dtype is not None else some[0].dtype if some else np.float32)
+    fdt = np.dtype(np.float32 if oflow_dtype is None else oflow_dtype)
+    kinds = {"image": (3, idt), "to_own": (2, fdt), "to_other": (2, fdt), "mask": (1, np.uint8), "fate": (1, np.uint8)}
+    out = {splat_key(name, f): np.zeros((n, kinds[name][0], height, width), kinds[name][1]) for f in frames for name in SPLAT_PLANES if name in outputs
+           and (name != "image" or (images is not None and images[f] is not None))}
+    keys = tuple(np.zeros((n, height, width), np.uint32) if f in frames else None for f in range(2))
+    n, height, width, *codes = splat_format(images, flows, labels, occ, out, keys)
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.int32 or recs.shape != (n, SPLAT_REC_INTS):
+            raise ValueError("recs must be int32 [%d,%d], got %s %s" % (n, SPLAT_REC_INTS, recs.dtype, recs.shape))
+    if "rows" not in outputs:
+        if rows is not None or accumulate:
+            raise ValueError("rows= and accumulate=True need \"rows\" among outputs")
+    elif rows is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs rows= to add to")
+        rows = np.zeros((n, 2), _splat_dtype())
+    elif rows.dtype != _splat_dtype() or rows.shape != (n, 2) or not rows.flags["C_CONTIGUOUS"]:
+        raise ValueError("rows must be a contiguous structured array [%d,2] as a former call returned it" % n)
+    used = np.zeros((n, SPLAT_REC_INTS), np.int32)
+    job = _splat_job(images, flows, labels, occ, out, keys, None if rows is None else rows.ctypes.data, lambda a: a.ctypes.data, codes, (0, 0), frames,
+                     _splat_t_range(t), None if recs is None else recs.ctypes.data, used.ctypes.data, first_index, seed, accumulate)
+    _host_check(lib().ofdg_host_splat(C.byref(job), n, width, height))
+    return out, keys, rows, used
+
+
 def build(verbose=False):
     """Compile libofdg.so for gfx950 with hipcc (in-tree, optical-flow-2d-data-generation_amd/lib)."""
     cmd = ["make", "-C", HERE] + ([] if verbose else ["-s"])
@@ -1514,6 +1768,9 @@ def lib():
         L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
         L.ofdg_reproject.argtypes = [vp, C.POINTER(ReprojectJob), i32, vp]
         L.ofdg_host_reproject.argtypes = [C.POINTER(ReprojectJob), i32, i32, i32]
+        L.ofdg_splat.argtypes = [vp, C.POINTER(SplatJob), i32, vp]
+        L.ofdg_host_splat.argtypes = [C.POINTER(SplatJob), i32, i32, i32]
+        L.ofdg_splat_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(SplatJob), C.POINTER(SplatRec)]
         L.ofdg_sample_counter.argtypes = [vp, C.c_longlong, i32, vp, vp]
         L.ofdg_warp_generate.argtypes = [vp, i32, C.c_uint32]
         L.ofdg_warp_upload.argtypes = [vp, vp, i32]
@@ -2022,6 +2279,42 @@ class Generator:
                              fb_thresh, accumulate)
         self._check(lib().ofdg_reproject(self.h, C.byref(job), n, C.c_void_p(stream)))
         return out, rows
+
+    def splat(self, images, flows, labels=None, occ=None, t=None, recs=None, out=None, keys=None, rows=None, accumulate=False, size=None, seed=None,
+              first_index=0, frames=None, recs_out=None, stream=0):
+        """Each frame pushed along its own flow to the instant t - the forward warp, with holes and covered pixels
+        (ofdg_splat, include/ofdg.h): frame 0 goes forward by t, frame 1 comes back by 1 - t, and where several sources land on
+        one pixel the higher label wins, among equal labels the lowest source index.  images: None or the pair (image0,
+        image1) of float32 or uint8 tensors [n,3,H,W]; flows: the pair (flow, flow1) of float32 or float16 tensors [n,2,H,W];
+        labels: None or the pair (label0, label1) of uint8 tensors [n,H,W]; occ: None or the pair (occ0, occ1) of float32 or
+        uint8 tensors [n,1,H,W] (the rows only); any member may be None (mode 9: flows=(flow, None)), all read only.  Inputs of
+        a frame that is not worked on are left out, but its map.  t: None - drawn from 0..1 -, a fraction - fixed -, or a
+        pair (min, max): the record of sample i is splat_draw(seed, first_index + i, t); or recs: an int32 device tensor [n,4]
+        (t_q8 of frame 0, of frame 1, 0, 0), taken as given; either is sanitised.  keys: the pair (keys0, keys1) of int32
+        device tensors [n,H,W] (alloc_splat), REQUIRED for every frame worked on: workspace and output, the winning keys
+        (splat_numpy decodes them).  out: a dict of the planes to write under their splat_key names - "image0" the frame at
+        t, "to_own0" / "to_other0" the flows from a pixel at t to frame 0 / frame 1, "mask0" 1 where a source arrived, "fate0"
+        per source pixel of frame 0 one of SPLAT_FATES, and the same with 1.  rows: None or the uint8 device tensor [n,128] that
+        receives a row per sample (splat_numpy); accumulate=True adds to it.  frames: None - the frames out and keys name.
+        seed: default the context's.  recs_out: None or an int32 device tensor [n,4] that receives the records used.  stream:
+        the stream the planes were written on, or STREAM_OWN.  size=(height, width): planes of that size instead of the
+        context's.  Asynchronous.  Returns (out, keys, rows)."""
+        flows, out = tuple(flows), dict(out or {})
+        keys = (None, None) if keys is None else tuple(keys)
+        frames = _splat_frames(frames, flows, out, keys)
+        images, labels, keys = _splat_only(images, frames), _splat_only(labels, frames), _splat_only(keys, frames)
+        flows, occ = _splat_only(flows, frames), None if occ is None else tuple(occ)
+        if recs is not None and t is not None:
+            raise ValueError("t= and recs= exclude each other")
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = splat_format(images, flows, labels, occ, out, keys, height, width)
+        self._check_recs(recs, recs_out, "int32", (n, SPLAT_REC_INTS))
+        if rows is not None and (str(rows.dtype) != "torch.uint8" or tuple(rows.shape) != (n, C.sizeof(SplatRow))):
+            raise ValueError("rows must be uint8 [%d,%d], got %s %s" % (n, C.sizeof(SplatRow), rows.dtype, tuple(rows.shape)))
+        job = _splat_job(images, flows, labels, occ, out, keys, _optr(rows), lambda x: _dptr(x).value, codes, job_size, frames, _splat_t_range(t),
+                         _optr(recs), _optr(recs_out), first_index, self._seed(seed), accumulate)
+        self._check(lib().ofdg_splat(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return out, keys, rows
 
     def debug_photo_table(self, rec):
         """ofdg_debug_photo_table: the table float32 [2,3,256] of a record float32 [16] as the DEVICE computes it (the twin:
@@ -2640,6 +2933,7 @@ class _RingSlot:
                  "window_recs",  # the records of crop= / spatial=
                  "blur",         # the records of motion_blur=
                  "reproject",    # (planes by name, rows) of reproject=
+                 "splat",        # (planes by name, keys, rows, records) of splat=
                  "objects",      # (rows, counts) of objects=True
                  "stats",        # the rows of stats=True
                  "pyramid",      # the levels of pyramid=, or (levels, weights)
@@ -2672,19 +2966,21 @@ class FlowLoader:
         2. spatial= / crop= the window, into planes of its own: every later stage works on the window's planes and size
         3. reproject=       of the window's sharp frames, flows and maps as they are then (un-blurred, un-erased), into planes
                             and rows of its own
-        4. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
+        4. splat=           of the same sharp planes, and the label planes, pushed to an instant between the frames, into
+                            planes, keys and rows of its own
+        5. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
                             places of image0 / image1 for every later stage and in the batch
-        5. photo=           in place, on both frames
-        6. erase=           in place, on the frames and the occlusion maps
-        7. objects=True     the table, of the label planes of stage 1
-        8. stats=, pyramid= the reductions of flow and occ0
-        9. boundaries=      of the flows and label planes
-        10. pack=           of image0, image1 and flow, into tensors of its own
+        6. photo=           in place, on both frames
+        7. erase=           in place, on the frames and the occlusion maps
+        8. objects=True     the table, of the label planes of stage 1
+        9. stats=, pyramid= the reductions of flow and occ0
+        10. boundaries=     of the flows and label planes
+        11. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
     eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 and 4 to 6 are drawn from the
+    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 and 4 to 7 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -2712,6 +3008,14 @@ class FlowLoader:
     sample: reproject_numpy) and the planes by name, "warped0", "err0", "mask0", "fb2_0" and the same with 1.  occ0 / occ1
     split the rows into visible and hidden when they are among extras=.  frames=None: both frames when "flow1" is among
     extras=, else frame 0; frame 1 or "fb2" without "flow1" raises.  fb_thresh: px, default 1.
+    splat=dict(t=, frames=, outputs=) (all optional): each frame of frames= is pushed along its own flow to an instant
+    between the frames (Generator.splat) right behind reproject=, so it reads the sharp frames, the flows, the label planes and
+    the maps before erase= touches them.  t=(min, max) draws the instant per sample from the context's seed and the sample's
+    global index (splat_draw), a fraction fixes it; default 0.5.  outputs= names what to make (SPLAT_OUTPUTS; default all): the
+    dict holds "splat", itself a dict of the planes by name - "keys0", "image0", "to_own0", "to_other0", "mask0", "fate0" and the
+    same with 1 -, "rows" (uint8 [n,128], a row per sample: splat_numpy) and "recs" (int32 [n,4], the records used).  label0 /
+    label1 decide who wins a pixel and occ0 / occ1 split the rows when they are among extras=; without labels the lowest source
+    index wins.  frames=None: both frames when "flow1" is among extras=, else frame 0; frame 1 without "flow1" raises.
     photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
     holds "photo" (float32 [n,16], the records used).
     erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
@@ -2741,12 +3045,13 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, **kw):
+                 reproject=None, splat=None, **kw):
         import torch
         self.boundaries = self._boundary_options(boundaries, extras)
         self.erase = self._erase_options(erase, extras)
         self.motion_blur = self._motion_blur_options(motion_blur, extras)
         self.reproject = self._reproject_options(reproject, extras)
+        self.splat = self._splat_options(splat, extras)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -2812,6 +3117,9 @@ class FlowLoader:
             t.reproject = None
             if self.reproject is not None:
                 t.reproject = alloc_reproject(n, ph, pw, self.reproject[0], self.reproject[2], t.sharp["image0"].dtype)
+            t.splat = None
+            if self.splat is not None:
+                t.splat = alloc_splat(n, ph, pw, self.splat[0], self.splat[2], t.sharp["image0"].dtype, t.sharp["flow"].dtype)
             if self.motion_blur is not None:
                 blurred, t.blur = alloc_motion_blur(n, ph, pw, t.sharp["image0"].dtype, self.motion_blur[1])
                 t.planes = dict(t.sharp, **{"image%d" % f: b for f, b in enumerate(blurred) if b is not None})
@@ -2932,6 +3240,27 @@ class FlowLoader:
             raise ValueError("reproject= output \"fb2\" reads flow1: extras= must contain \"flow1\"")
         return frames, _fb_thresh_q8(reproject.get("fb_thresh", 1.0)) / 256.0, outputs
 
+    @staticmethod
+    def _splat_options(splat, extras):
+        """splat= split into (frames, (t_min_q8, t_max_q8), outputs), or None; raises for what the loader cannot serve"""
+        if splat is None:
+            return None
+        unknown = set(splat) - {"t", "frames", "outputs"}
+        if unknown:
+            raise ValueError("unknown splat option(s) %s" % sorted(unknown))
+        have_flow1 = "flow1" in tuple(extras or ())
+        frames = splat.get("frames")
+        frames = ((0, 1) if have_flow1 else (0,)) if frames is None else tuple(sorted(set(int(f) for f in frames)))
+        if not frames or any(f not in (0, 1) for f in frames):
+            raise ValueError("splat= needs frames of 0 and / or 1, got %r" % (frames,))
+        if 1 in frames and not have_flow1:
+            raise ValueError("splat= of frame 1 reads flow1: extras= must contain \"flow1\", or pass frames=(0,)")
+        outputs = tuple(splat.get("outputs", SPLAT_OUTPUTS))
+        bad = sorted(set(outputs) - set(SPLAT_OUTPUTS))
+        if bad or not outputs:
+            raise ValueError("splat= needs outputs among %s, got %r" % (", ".join(SPLAT_OUTPUTS), outputs))
+        return frames, _splat_t_range(splat.get("t", 0.5)), outputs
+
     def _enqueue(self, j):
         """The next batch into set j: the stages of the class docstring, in its order, on the stream next_stream() gives."""
         import torch
@@ -2941,7 +3270,7 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
@@ -2956,6 +3285,12 @@ class FlowLoader:
             frames, fb_thresh, _ = self.reproject
             g.reproject((t.sharp["image0"], t.sharp["image1"]), (t.sharp["flow"], t.sharp.get("flow1")), (t.sharp.get("occ0"), t.sharp.get("occ1")),
                         out=t.reproject[0], rows=t.reproject[1], fb_thresh=fb_thresh, frames=frames, stream=s, size=size)
+        if self.splat is not None:
+            frames, t_range, _ = self.splat
+            out, keys, rows, recs = t.splat
+            g.splat((t.sharp["image0"], t.sharp["image1"]), (t.sharp["flow"], t.sharp.get("flow1")), (t.sharp.get("label0"), t.sharp.get("label1")),
+                    (t.sharp.get("occ0"), t.sharp.get("occ1")), t=(t_range[0] / 256.0, t_range[1] / 256.0), out=out, keys=keys, rows=rows, frames=frames,
+                    first_index=first, recs_out=recs, stream=s, size=size)
         if self.motion_blur is not None:
             ranges, frames = self.motion_blur
             pick = lambda a, b: tuple(t_ if f in frames else None for f, t_ in enumerate((a, b)))  # noqa: E731
@@ -2995,6 +3330,11 @@ class FlowLoader:
             more.update(t.reproject[0])
             if t.reproject[1] is not None:
                 more["reproject"] = t.reproject[1]
+        if t.splat is not None:
+            out, keys, rows, recs = t.splat
+            more["splat"] = dict(out, recs=recs, **{splat_key("keys", f): k for f, k in enumerate(keys) if k is not None})
+            if rows is not None:
+                more["splat"]["rows"] = rows
         if t.blur is not None:
             more["motion_blur"] = t.blur
         if t.photo is not None:

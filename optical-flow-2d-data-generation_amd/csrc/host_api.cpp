@@ -917,4 +917,132 @@ int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int
   return OFDG_OK;
 }
 
+// ofdg_splat on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel - the scatter over the sources, then
+// the targets, then the fates.  The draw, the sanitising, the displacement, its scaling, the rounded target, the key and the
+// argument rules are the functions the kernels run (csrc/ofdg_device.h); elements are moved with memcpy.
+int ofdg_splat_draw(uint32_t seed, long long index, const struct ofdg_splat_job* ranges, ofdg_splat_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_splat_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevSplatJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = splat_ranges_error(j)) { g_host_error = std::string("ofdg_splat_draw: ") + why; return OFDG_EINVAL; }
+  const DevSplatRec r = splat_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_splat(const struct ofdg_splat_job* job, int n_samples, int width, int height) {
+  const DevSplatJob* const j = reinterpret_cast<const DevSplatJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = splat_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_splat: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int ses = fmt_elem_bytes(j->img_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  uint8_t* const rows = reinterpret_cast<uint8_t*>(j->rows);
+  if (rows && !(j->flags & OFDG_SPLAT_ACCUMULATE)) std::memset(rows, 0, sizeof(DevSplatRow) * (size_t)n_samples);
+  const auto put_flow = [&](void* base, size_t e, float v) {
+    if (j->oflow_fmt == OFDG_FMT_F16) {
+      const uint16_t h = float_to_half_bits(v);
+      std::memcpy(static_cast<uint8_t*>(base) + 2 * e, &h, 2);
+    } else std::memcpy(static_cast<uint8_t*>(base) + 4 * e, &v, 4);
+  };
+  for (int i = 0; i < n_samples; ++i) {
+    DevSplatRec rec;
+    if (j->recs) std::memcpy(&rec, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(rec) * (size_t)i, sizeof(rec));
+    else rec = splat_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
+    rec = splat_sanitise(rec);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(rec) * (size_t)i, &rec, sizeof(rec));
+    for (int f = 0; f < 2; ++f) {
+      if (!((j->flags >> f) & 1)) continue;
+      const int T = rec.t_q8[f];
+      const FlowPlane flow{j->flow[f], j->flow_fmt};
+      const OccPlane own_occ{j->occ[f], j->occ_fmt}, other_occ{j->occ[1 - f], j->occ_fmt};
+      const size_t fu = (size_t)i * 2 * plane, fv = fu + plane;
+      uint8_t* const keys = reinterpret_cast<uint8_t*>(j->keys[f]) + 4 * (size_t)i * plane;
+      const auto key_at = [&](size_t p) { uint32_t k; std::memcpy(&k, keys + 4 * p, 4); return k; };
+      // where source s goes: 3 bad, 2 outside, else 0 with its target in *tp and its key in *key
+      const auto aim = [&](int x, int y, size_t* tp, uint32_t* key, int* Dx, int* Dy) -> int {
+        const size_t s = (size_t)y * width + x;
+        const float u = flow.at(fu + s), v = flow.at(fv + s);
+        if (!(mblur_finite(u) && mblur_finite(v))) return 3;
+        *Dx = reproj_q8(u); *Dy = reproj_q8(v);
+        const int rx = splat_round(x, splat_scale(*Dx, T)), ry = splat_round(y, splat_scale(*Dy, T));
+        if (!splat_inside(rx, ry, width, height)) return 2;
+        *tp = (size_t)ry * width + rx;
+        *key = splat_key(j->label[f] ? j->label[f][(size_t)i * plane + s] : 0u, (uint32_t)s);
+        return 0;
+      };
+      DevSplatFrameRow r{};
+      if (rows) std::memcpy(&r, rows + sizeof(DevSplatRow) * (size_t)i + sizeof(r) * (size_t)f, sizeof(r));
+      std::memset(keys, 0, 4 * plane);
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          size_t tp = 0;
+          uint32_t key = 0;
+          int Dx = 0, Dy = 0;
+          const int fate = aim(x, y, &tp, &key, &Dx, &Dy);
+          ++r.src[fate == 3 ? 0 : fate == 2 ? 1 : 2];
+          if (fate == 0 && key > key_at(tp)) std::memcpy(keys + 4 * tp, &key, 4);
+        }
+      for (int py = 0; py < height; ++py)
+        for (int px = 0; px < width; ++px) {
+          const size_t p = (size_t)py * width + px;
+          const uint32_t K = key_at(p);
+          uint32_t byte[3] = {0u, 0u, 0u};
+          float own[2] = {0.0f, 0.0f}, other[2] = {0.0f, 0.0f};
+          if (K) {
+            const size_t s = splat_source(K);
+            const int x = (int)(s % (size_t)width), y = (int)(s / (size_t)width);
+            own[0] = (float)(x - px); own[1] = (float)(y - py);
+            other[0] = splat_to_other(x - px, reproj_q8(flow.at(fu + s)));
+            other[1] = splat_to_other(y - py, reproj_q8(flow.at(fv + s)));
+            for (int c = 0; c < 3 && j->img[f]; ++c) {
+              const uint8_t* const sp = static_cast<const uint8_t*>(j->img[f]) + (size_t)i * 3 * plane * ses;
+              const size_t e = (size_t)c * plane + s;
+              if (ses == 1) byte[c] = sp[e];
+              else {
+                float v;
+                std::memcpy(&v, sp + 4 * e, 4);
+                byte[c] = (uint32_t)photo_index(v);
+              }
+            }
+            ++r.dst[0];
+          } else {
+            ++r.dst[1];
+            if (j->occ[1 - f]) ++r.hole_other[other_occ.at((size_t)i * plane + p) ? 1 : 0];
+          }
+          for (int c = 0; c < 3 && j->image[f]; ++c) {
+            uint8_t* const dp = static_cast<uint8_t*>(j->image[f]) + (size_t)i * 3 * plane * des;
+            const float o = (float)byte[c];
+            if (des == 1) dp[(size_t)c * plane + p] = (uint8_t)byte[c];
+            else std::memcpy(dp + 4 * ((size_t)c * plane + p), &o, 4);
+          }
+          for (int c = 0; c < 2; ++c) {
+            if (j->to_own[f]) put_flow(j->to_own[f], fu + (size_t)c * plane + p, own[c]);
+            if (j->to_other[f]) put_flow(j->to_other[f], fu + (size_t)c * plane + p, other[c]);
+          }
+          if (j->mask[f]) static_cast<uint8_t*>(j->mask[f])[(size_t)i * plane + p] = K ? 1 : 0;
+        }
+      for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+          const size_t s = (size_t)y * width + x;
+          size_t tp = 0;
+          uint32_t key = 0;
+          int Dx = 0, Dy = 0;
+          int fate = aim(x, y, &tp, &key, &Dx, &Dy);
+          if (fate == 0 && key_at(tp) != key) {
+            fate = 1;
+            ++r.n_covered;
+            if (j->occ[f]) ++r.covered[own_occ.at((size_t)i * plane + s) ? 1 : 0];
+          }
+          if (j->fate[f]) static_cast<uint8_t*>(j->fate[f])[(size_t)i * plane + s] = (uint8_t)fate;
+        }
+      r.t_q8 = (uint32_t)T;
+      if (rows) std::memcpy(rows + sizeof(DevSplatRow) * (size_t)i + sizeof(r) * (size_t)f, &r, sizeof(r));
+    }
+  }
+  return OFDG_OK;
+}
+
 }  // extern "C"

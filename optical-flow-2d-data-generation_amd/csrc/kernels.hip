@@ -4982,4 +4982,296 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
   }
 }
 
+// ---- Splat (ofdg_splat, include/ofdg.h) ------------------------------------------------------------------------------------
+// Two launches behind the clears, each for both frames and every sample, on reproject_kernel's layout: blockIdx.x counts
+// the kSplatTileW x kSplatTileH tiles of a frame, blockIdx.y the samples, blockIdx.z the frames that are flagged; a 4-wave
+// workgroup owns a tile, a lane four consecutive pixels of one row (width % 8 == 0: a lane's four pixels, and the eight of a
+// pair of lanes, are whole or outside together), so the flow, the label, the maps and the keys are read as whole 16 / 8 / 4-byte
+// pieces and every plane is written as whole pieces.
+// splat_scatter_kernel: a lane's pixels as SOURCES.  Targets of a tile mostly land near it: an LDS key window - the tile and
+// a halo of 16 pixels, 96 x 48 cells, 18 432 bytes - takes the maxima of the targets inside it on chip (ds_max_u32), and behind
+// a barrier the workgroup flushes it, a thread 18 cells, with one relaxed agent-scope atomic max without a return value per
+// touched cell: a wave's flush is 256 contiguous bytes of a row, where the per-pixel form issued four atomics a lane 16 bytes
+// apart.  A target outside the window goes straight to global memory with the same atomic.  Every target is tested against
+// the plane first, and a flushed cell again, so no index leaves it.  (The form without the window - one global atomic per
+// inside pixel - passed the same tests and took 1.3 to 2.4 times as long: tools/patches/splat_scatter_atomics_only.patch,
+// CHANGELOG.)  Thread 0 of the first tile writes the sanitised record and the row's t_q8.
+// splat_resolve_kernel: a lane's pixels in both roles.  As TARGETS it decodes the four keys, gathers the winner's bytes and
+// flow (ubyte / ushort / dword loads at an index below the plane's size: the keys were cleared and raised by this call only,
+// and an index is tested all the same) and stores image, to_own, to_other and mask; as SOURCES it aims again, reads the key
+// at the target and stores the fate.  Stores are non-temporal: 16 bytes of float32 a lane, 8 bytes of binary16 a lane, 8
+// bytes of uint8 a pair of lanes, gathered by the even lane with a wave shuffle.
+// Rows: a lane counts its four pixels in 10-bit fields three to a word (a wave holds 256 pixels), the wave reduces them
+// with __shfl_xor, lane 0 writes the wave's slots in LDS - a row of slots per parity of the sample's turn, so one barrier a
+// sample suffices - and the workgroup issues one atomicAdd per non-zero count.  Integer atomics only: no bit depends on the
+// order of arrival.  A launch without rows runs none of this and no barrier.  The presence of each output, the destination
+// formats and the maps' format are uniform run-time branches; the flow format (both kernels) and the source format
+// (resolve) are template arguments: 2 + 4 instantiations.  The functions of the definition are the host twin's
+// (csrc/ofdg_device.h).  No scratch.
+constexpr int kSplatThreads = 256;
+constexpr int kSplatTileW = 64, kSplatTileH = 16;
+constexpr int kSplatResolveWords = 7;  // n_filled .. n_hole_other_hidden: the words the resolve adds to
+static_assert(kSplatTileW / 4 * kSplatTileH == kSplatThreads, "a lane per four pixels of the tile");
+static_assert(offsetof(DevSplatFrameRow, dst) == 12 && offsetof(DevSplatFrameRow, t_q8) == 12 + 4 * kSplatResolveWords, "the words the two kernels add to");
+__device__ __forceinline__ DevSplatRec splat_rec_of(const DevSplatJob& job, int i) {
+  DevSplatRec r;
+  if (job.recs) r = job.recs[i];
+  else r = splat_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
+  return splat_sanitise(r);
+}
+// the four flow elements of a lane, widened
+template <bool kHalf>
+__device__ __forceinline__ void splat_load_flow4(const uint8_t* __restrict__ fp, float (&o)[4]) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  if constexpr (kHalf) {
+    const f16x4 a = *reinterpret_cast<const f16x4*>(fp);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = (float)a[p];
+  } else {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(fp);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = a[p];
+  }
+}
+// bit p: element p of the lane's four of a map is non-zero
+__device__ __forceinline__ uint32_t splat_load_hidden4(const uint8_t* __restrict__ op, size_t e, bool occ_u8) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  uint32_t hidden = 0u;
+  if (occ_u8) {
+    const uint32_t o = *reinterpret_cast<const uint32_t*>(op + e);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) hidden |= (((o >> (8 * p)) & 255u) != 0u ? 1u : 0u) << p;
+  } else {
+    const f32x4 o = *reinterpret_cast<const f32x4*>(op + e * 4u);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) hidden |= (o[p] != 0.0f ? 1u : 0u) << p;
+  }
+  return hidden;
+}
+template <bool kFlowHalf>
+__global__ __launch_bounds__(kSplatThreads) void splat_scatter_kernel(const DevSplatJob job, int n, int W, int H, uint32_t tiles_x) {
+  constexpr int kFES = kFlowHalf ? 2 : 4;
+  __shared__ uint32_t s_cnt[2][kSplatThreads / 64];  // [parity of the sample's turn][wave]: bad, outside, inside in 10-bit fields
+  // the LDS key window: the tile and a halo of kSplatHalo pixels; the maxima of the targets that land in it are taken on chip
+  // and flushed with one global atomic per touched cell, the others go straight to global memory
+  constexpr int kSplatHalo = 16, kWinW = kSplatTileW + 2 * kSplatHalo, kWinH = kSplatTileH + 2 * kSplatHalo, kWinCells = kWinW * kWinH;
+  static_assert(kWinCells % kSplatThreads == 0, "a thread clears and flushes a whole number of cells");
+  __shared__ uint32_t s_win[kWinCells];
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int X0 = (int)(tx * kSplatTileW + (threadIdx.x & 15u) * 4u), Y = (int)(ty * kSplatTileH + (threadIdx.x >> 4));
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int f = (blockIdx.z != 0u || !(job.flags & OFDG_SPLAT_FRAME0)) ? 1 : 0;
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.flow[1] : job.flow[0]);
+  const uint8_t* const s_label = f ? job.label[1] : job.label[0];
+  uint32_t* const d_keys = f ? job.keys[1] : job.keys[0];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (below 2^24: splat_arg_error)
+  const bool act = X0 < W && Y < H;
+  const uint32_t at = act ? (uint32_t)Y * (uint32_t)W + (uint32_t)X0 : 0u;  // the lane's first pixel in a plane
+  const int wx0 = (int)(tx * kSplatTileW) - kSplatHalo, wy0 = (int)(ty * kSplatTileH) - kSplatHalo;  // the window's first column and row in the frame
+  uint32_t turn = 0u;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y, turn ^= 1u) {
+    const DevSplatRec r = splat_rec_of(job, i);
+    const int T = f ? r.t_q8[1] : r.t_q8[0];
+#pragma unroll
+    for (int k = 0; k < kWinCells / kSplatThreads; ++k) s_win[(uint32_t)k * kSplatThreads + threadIdx.x] = 0u;
+    __syncthreads();
+    if (blockIdx.x == 0u && threadIdx.x == 0u) {
+      if (job.recs_out && blockIdx.z == 0u) *reinterpret_cast<crop_u32x4*>(job.recs_out + i) = crop_u32x4{(uint32_t)r.t_q8[0], (uint32_t)r.t_q8[1], 0u, 0u};
+      if (job.rows) job.rows[i].frame[f].t_q8 = (uint32_t)T;
+    }
+    float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t labels = 0u;  // a byte per pixel
+    if (act) {
+      const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
+      splat_load_flow4<kFlowHalf>(fp, u);
+      splat_load_flow4<kFlowHalf>(fp + (size_t)plane * kFES, v);
+      if (s_label) labels = *reinterpret_cast<const uint32_t*>(s_label + (size_t)i * plane + at);
+    }
+    uint32_t* const kp = d_keys + (size_t)i * plane;
+    uint32_t cnt = 0u;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+      const int rx = splat_round(X0 + p, splat_scale(bad ? 0 : reproj_q8(u[p]), T)), ry = splat_round(Y, splat_scale(bad ? 0 : reproj_q8(v[p]), T));
+      const bool in = act && !bad && splat_inside(rx, ry, W, H);
+      if (in) {
+        const uint32_t key = splat_key((labels >> (8 * p)) & 255u, at + (uint32_t)p);
+        const int cx = rx - wx0, cy = ry - wy0;
+        if (cx >= 0 && cx < kWinW && cy >= 0 && cy < kWinH) atomicMax(&s_win[cy * kWinW + cx], key);
+        else __hip_atomic_fetch_max(kp + ((uint32_t)ry * (uint32_t)W + (uint32_t)rx), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      cnt += (act && bad ? 1u : 0u) | ((act && !bad && !in ? 1u : 0u) << 10) | ((in ? 1u : 0u) << 20);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kWinCells / kSplatThreads; ++k) {
+      const uint32_t c = (uint32_t)k * kSplatThreads + threadIdx.x, key = s_win[c];
+      const int gx = wx0 + (int)(c % (uint32_t)kWinW), gy = wy0 + (int)(c / (uint32_t)kWinW);
+      if (key != 0u && splat_inside(gx, gy, W, H)) __hip_atomic_fetch_max(kp + ((uint32_t)gy * (uint32_t)W + (uint32_t)gx), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();  // (the window is cleared again for the next sample only behind its flush)
+    if (job.rows) {  // (uniform: every lane of the workgroup is here)
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d, 64);
+      if (lane == 0) s_cnt[turn][wave] = cnt;
+      __syncthreads();  // (a wave is at most one barrier ahead of another, and the next sample's slots are the other row's)
+      if (threadIdx.x < 3u) {
+        const uint32_t sh = 10u * threadIdx.x;
+        const uint32_t s = ((s_cnt[turn][0] >> sh) & 1023u) + ((s_cnt[turn][1] >> sh) & 1023u) + ((s_cnt[turn][2] >> sh) & 1023u) + ((s_cnt[turn][3] >> sh) & 1023u);
+        if (s) atomicAdd(&job.rows[i].frame[f].src[threadIdx.x], s);
+      }
+    }
+  }
+}
+template <bool kSrcU8, bool kFlowHalf>
+__global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevSplatJob job, int n, int W, int H, uint32_t tiles_x) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  constexpr int kSES = kSrcU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
+  __shared__ uint32_t s_cnt[2][kSplatThreads / 64][3];  // [parity of the sample's turn][wave]: the seven counts in 10-bit fields
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int X0 = (int)(tx * kSplatTileW + (threadIdx.x & 15u) * 4u), Y = (int)(ty * kSplatTileH + (threadIdx.x >> 4));
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int f = (blockIdx.z != 0u || !(job.flags & OFDG_SPLAT_FRAME0)) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.img[1] : job.img[0]);
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.flow[1] : job.flow[0]);
+  const uint8_t* const s_label = f ? job.label[1] : job.label[0];
+  const uint8_t* const s_occ = static_cast<const uint8_t*>(f ? job.occ[1] : job.occ[0]);
+  const uint8_t* const s_occ_other = static_cast<const uint8_t*>(f ? job.occ[0] : job.occ[1]);
+  const uint32_t* const s_keys = f ? job.keys[1] : job.keys[0];
+  uint8_t* const d_image = static_cast<uint8_t*>(f ? job.image[1] : job.image[0]);
+  uint8_t* const d_own = static_cast<uint8_t*>(f ? job.to_own[1] : job.to_own[0]);
+  uint8_t* const d_other = static_cast<uint8_t*>(f ? job.to_other[1] : job.to_other[0]);
+  uint8_t* const d_mask = static_cast<uint8_t*>(f ? job.mask[1] : job.mask[0]);
+  uint8_t* const d_fate = static_cast<uint8_t*>(f ? job.fate[1] : job.fate[0]);
+  // what the launch has to do (uniform)
+  const bool as_target = d_image || d_own || d_other || d_mask || job.rows, as_source = d_fate || job.rows;
+  const bool dst_u8 = job.dst_fmt == OFDG_FMT_U8, occ_u8 = job.occ_fmt == OFDG_FMT_U8, oflow_half = job.oflow_fmt == OFDG_FMT_F16;
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (below 2^24: splat_arg_error)
+  const bool act = X0 < W && Y < H;
+  const uint32_t at = act ? (uint32_t)Y * (uint32_t)W + (uint32_t)X0 : 0u;  // the lane's first pixel in a plane
+  uint32_t turn = 0u;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y, turn ^= 1u) {
+    const uint32_t* const kp = s_keys + (size_t)i * plane;
+    const uint8_t* const fp = s_flow + (size_t)i * 2 * plane * kFES;
+    uint32_t cnt_a = 0u, cnt_b = 0u, cnt_c = 0u;  // filled, holes, covered | covered visible, covered hidden, hole other visible | hole other hidden
+    if (as_target) {
+      crop_u32x4 K = {0u, 0u, 0u, 0u};
+      uint32_t hidden = 0u;  // bit p: the other frame's map says pixel p is hidden
+      if (act) {
+        K = *reinterpret_cast<const crop_u32x4*>(kp + at);
+        if (s_occ_other && job.rows) hidden = splat_load_hidden4(s_occ_other, (size_t)i * plane + at, occ_u8);
+      }
+      uint32_t out[3][4] = {};
+      uint32_t masks = 0u;  // a byte per pixel
+      float own[2][4] = {}, other[2][4] = {};
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const uint32_t s = splat_source(K[p]);
+        const bool filled = K[p] != 0u && s < plane;
+        if (filled) {
+          const uint32_t y = s / (uint32_t)W, x = s - y * (uint32_t)W;
+          const int dx = (int)x - (X0 + p), dy = (int)y - Y;
+          masks |= 1u << (8 * p);
+          own[0][p] = (float)dx; own[1][p] = (float)dy;
+          if (d_other) {
+            other[0][p] = splat_to_other(dx, reproj_q8(reproj_load_flow<kFlowHalf>(fp, s)));
+            other[1][p] = splat_to_other(dy, reproj_q8(reproj_load_flow<kFlowHalf>(fp, plane + s)));
+          }
+          if (d_image) {
+            const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c][p] = mblur_load_byte<kSrcU8>(sp, (uint32_t)c * plane + s);
+          }
+        }
+        const bool hole = act && !filled, hid = (hidden >> p) & 1u;
+        cnt_a += (filled ? 1u : 0u) | ((hole ? 1u : 0u) << 10);
+        cnt_b += (hole && s_occ_other && !hid ? 1u : 0u) << 20;
+        cnt_c += hole && s_occ_other && hid ? 1u : 0u;
+      }
+      // (the lanes of a pair are inside together: X0 of the even one is a multiple of 8)
+      if (d_image) {
+        if (dst_u8) {
+          uint8_t* const dp = d_image + (size_t)i * 3 * plane;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
+            const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
+            if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
+          }
+        } else {
+          uint8_t* const dp = d_image + (size_t)i * 3 * plane * 4u;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
+            if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
+          }
+        }
+      }
+#pragma unroll
+      for (int which = 0; which < 2; ++which) {
+        uint8_t* const dq = which ? d_other : d_own;
+        if (!dq || !act) continue;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const float* const e = which ? other[c] : own[c];
+          const size_t o = (size_t)i * 2 * plane + (size_t)c * plane + at;
+          if (oflow_half) __builtin_nontemporal_store(f16x4{(_Float16)e[0], (_Float16)e[1], (_Float16)e[2], (_Float16)e[3]}, reinterpret_cast<f16x4*>(dq + o * 2u));
+          else __builtin_nontemporal_store(f32x4{e[0], e[1], e[2], e[3]}, reinterpret_cast<f32x4*>(dq + o * 4u));
+        }
+      }
+      if (d_mask) {
+        const u32x2 o = {masks, (uint32_t)__shfl_down((int)masks, 1)};
+        if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_mask + (size_t)i * plane + at));
+      }
+    }
+    if (as_source) {
+      const DevSplatRec r = splat_rec_of(job, i);
+      const int T = f ? r.t_q8[1] : r.t_q8[0];
+      float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      uint32_t labels = 0u, hidden = 0u;
+      if (act) {
+        splat_load_flow4<kFlowHalf>(fp + (size_t)at * kFES, u);
+        splat_load_flow4<kFlowHalf>(fp + ((size_t)plane + at) * kFES, v);
+        if (s_label) labels = *reinterpret_cast<const uint32_t*>(s_label + (size_t)i * plane + at);
+        if (s_occ && job.rows) hidden = splat_load_hidden4(s_occ, (size_t)i * plane + at, occ_u8);
+      }
+      uint32_t fates = 0u;  // a byte per pixel
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+        const int rx = splat_round(X0 + p, splat_scale(bad ? 0 : reproj_q8(u[p]), T)), ry = splat_round(Y, splat_scale(bad ? 0 : reproj_q8(v[p]), T));
+        const bool in = act && !bad && splat_inside(rx, ry, W, H);
+        bool covered = false;
+        if (in) covered = kp[(uint32_t)ry * (uint32_t)W + (uint32_t)rx] != splat_key((labels >> (8 * p)) & 255u, at + (uint32_t)p);
+        fates |= (bad ? 3u : !in ? 2u : covered ? 1u : 0u) << (8 * p);
+        const bool hid = (hidden >> p) & 1u;
+        cnt_a += (covered ? 1u : 0u) << 20;
+        cnt_b += (covered && s_occ && !hid ? 1u : 0u) | ((covered && s_occ && hid ? 1u : 0u) << 10);
+      }
+      if (d_fate) {
+        const u32x2 o = {fates, (uint32_t)__shfl_down((int)fates, 1)};
+        if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_fate + (size_t)i * plane + at));
+      }
+    }
+    if (job.rows) {  // (uniform: every lane of the workgroup is here)
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        cnt_a += (uint32_t)__shfl_xor((int)cnt_a, d, 64);
+        cnt_b += (uint32_t)__shfl_xor((int)cnt_b, d, 64);
+        cnt_c += (uint32_t)__shfl_xor((int)cnt_c, d, 64);
+      }
+      if (lane == 0) { s_cnt[turn][wave][0] = cnt_a; s_cnt[turn][wave][1] = cnt_b; s_cnt[turn][wave][2] = cnt_c; }
+      __syncthreads();  // (a wave is at most one barrier ahead of another, and the next sample's slots are the other row's)
+      if (threadIdx.x < (uint32_t)kSplatResolveWords) {
+        const uint32_t w = threadIdx.x / 3u, sh = 10u * (threadIdx.x % 3u);
+        const uint32_t s = ((s_cnt[turn][0][w] >> sh) & 1023u) + ((s_cnt[turn][1][w] >> sh) & 1023u) + ((s_cnt[turn][2][w] >> sh) & 1023u) + ((s_cnt[turn][3][w] >> sh) & 1023u);
+        if (s) atomicAdd(reinterpret_cast<uint32_t*>(&job.rows[i].frame[f]) + 3u + threadIdx.x, s);
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

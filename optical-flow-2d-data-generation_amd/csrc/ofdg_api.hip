@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur, ofdg_reproject
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur, ofdg_reproject, ofdg_splat
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -292,7 +292,7 @@ struct PostOp {
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
-// 4 reproject_kernel.
+// 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1942,6 +1942,49 @@ int ofdg_reproject(ofdg_ctx* c, const struct ofdg_reproject_job* job, int n_samp
   with_bool(j->img_fmt == OFDG_FMT_U8, [&](auto src_u8) {
     with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
       hipLaunchKernelGGL((reproject_kernel<decltype(src_u8)::value, decltype(half)::value>), g, dim3(kReprojThreads), 0, st, *j, n_samples, W, H, tiles_x);
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Splat of caller-given frames along their flows: the key planes (and, unless they accumulate, the rows) cleared on `stream`,
+// then the scatter and the resolve, each one kernel for both frames and every sample.
+int ofdg_splat(ofdg_ctx* c, const struct ofdg_splat_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_splat"};
+  const DevSplatJob* const j = reinterpret_cast<const DevSplatJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = splat_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = splat_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    const std::string at = f ? "[1]" : "[0]";
+    OFDG_TRY(op.aligned("img" + at, j->img[f], j->img_fmt));
+    OFDG_TRY(op.aligned("flow" + at, j->flow[f], j->flow_fmt));
+    OFDG_TRY(op.aligned("label" + at, j->label[f], OFDG_FMT_U8, false));
+    if (j->occ[f]) OFDG_TRY(op.aligned("occ" + at, j->occ[f], j->occ_fmt));
+    const std::pair<const char*, const void*> outs[] = {{"keys", j->keys[f]}, {"image", j->image[f]}, {"to_own", j->to_own[f]}, {"to_other", j->to_other[f]},
+                                                         {"mask", j->mask[f]}, {"fate", j->fate[f]}};
+    for (const auto& o : outs)
+      if ((uintptr_t)o.second & 15) return op.fail(o.first + at + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->rows & 15) return op.fail("rows must be 16-byte aligned");
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const size_t plane = (size_t)W * (size_t)H;
+  for (int f = 0; f < 2; ++f)
+    if (j->keys[f]) HIP_OK(c, hipMemsetAsync(j->keys[f], 0, 4 * plane * (size_t)n_samples, st));
+  if (j->rows && !(j->flags & OFDG_SPLAT_ACCUMULATE)) HIP_OK(c, hipMemsetAsync(j->rows, 0, sizeof(DevSplatRow) * (size_t)n_samples, st));
+  const uint32_t tiles_x = ((uint32_t)W + kSplatTileW - 1) / kSplatTileW, tiles_y = ((uint32_t)H + kSplatTileH - 1) / kSplatTileH;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), ((j->flags & OFDG_SPLAT_FRAME0) ? 1u : 0u) + ((j->flags & OFDG_SPLAT_FRAME1) ? 1u : 0u));
+  with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto half) {
+    hipLaunchKernelGGL((splat_scatter_kernel<decltype(half)::value>), g, dim3(kSplatThreads), 0, st, *j, n_samples, W, H, tiles_x);
+    if (!splat_resolves(*j)) return;
+    with_bool(j->img_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+      hipLaunchKernelGGL((splat_resolve_kernel<decltype(src_u8)::value, decltype(half)::value>), g, dim3(kSplatThreads), 0, st, *j, n_samples, W, H, tiles_x);
     });
   });
   HIP_OK(c, hipGetLastError());

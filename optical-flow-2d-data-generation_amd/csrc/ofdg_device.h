@@ -1460,6 +1460,168 @@ inline const char* reproj_arg_error(const DevReprojJob* j, int n, int width, int
   return nullptr;
 }
 
+// ---- Splat (ofdg_splat, include/ofdg.h) ------------------------------------------------------------------------------------
+// What the device entry, the kernels and the host twin share: the job, the record and the row as the kernels take them, the
+// record's draw and its sanitising, the scaled displacement, the rounded target, the key and its decoding, the flow to the
+// other frame and the argument rules.  The displacement is reproj_q8, the finite test mblur_finite, the byte of a float32
+// photo_index.  Behind the one float32 product per component everything is integers.
+constexpr uint32_t kSplatIndexMask = (1u << 24) - 1u;
+static_assert(OFDG_SPLAT_MAX_PIXELS == (int)kSplatIndexMask, "a key holds a source index in 24 bits and is never 0");
+struct DevSplatRec {  // ofdg_splat_rec, field for field
+  int32_t t_q8[2];
+  int32_t reserved[2];
+};
+struct DevSplatFrameRow {  // ofdg_splat_frame_row, field for field: the kernels add to the words with unsigned atomics
+  uint32_t src[3];         // n_bad, n_outside, n_inside
+  uint32_t dst[2];         // n_filled, n_holes
+  uint32_t n_covered;
+  uint32_t covered[2];     // visible, hidden
+  uint32_t hole_other[2];  // visible, hidden
+  uint32_t t_q8;
+  uint32_t reserved[5];
+};
+struct DevSplatRow { DevSplatFrameRow frame[2]; };
+struct DevSplatJob {  // struct ofdg_splat_job, field for field
+  const void* img[2];
+  const void* flow[2];
+  const uint8_t* label[2];
+  const void* occ[2];
+  uint32_t* keys[2];
+  void* image[2];
+  void* to_own[2];
+  void* to_other[2];
+  void* mask[2];
+  void* fate[2];
+  DevSplatRow* rows;
+  const DevSplatRec* recs;
+  DevSplatRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, img_fmt, dst_fmt, flow_fmt, oflow_fmt, occ_fmt, flags, t_min_q8, t_max_q8;
+  int32_t reserved[2];
+};
+static_assert(sizeof(ofdg_splat_rec) == sizeof(DevSplatRec) && sizeof(DevSplatRec) == 16 && offsetof(ofdg_splat_rec, reserved) == offsetof(DevSplatRec, reserved) &&
+              offsetof(DevSplatRec, reserved) == 8, "ofdg_splat_rec: 16 bytes without padding, the layout the kernels read and write");
+static_assert(sizeof(ofdg_splat_frame_row) == sizeof(DevSplatFrameRow) && sizeof(DevSplatFrameRow) == 64 && offsetof(ofdg_splat_frame_row, n_bad) == offsetof(DevSplatFrameRow, src) &&
+              offsetof(ofdg_splat_frame_row, n_filled) == offsetof(DevSplatFrameRow, dst) && offsetof(ofdg_splat_frame_row, n_covered) == offsetof(DevSplatFrameRow, n_covered) &&
+              offsetof(DevSplatFrameRow, n_covered) == 20 && offsetof(ofdg_splat_frame_row, n_covered_visible) == offsetof(DevSplatFrameRow, covered) &&
+              offsetof(ofdg_splat_frame_row, n_hole_other_visible) == offsetof(DevSplatFrameRow, hole_other) && offsetof(ofdg_splat_frame_row, t_q8) == offsetof(DevSplatFrameRow, t_q8) &&
+              offsetof(DevSplatFrameRow, t_q8) == 40 && offsetof(ofdg_splat_frame_row, reserved) == offsetof(DevSplatFrameRow, reserved),
+              "ofdg_splat_frame_row: 64 bytes without padding, the layout the kernels add to");
+static_assert(sizeof(ofdg_splat_row) == sizeof(DevSplatRow) && sizeof(DevSplatRow) == 128 && offsetof(ofdg_splat_row, frame) == 0, "ofdg_splat_row: 128 bytes without padding, a block per frame");
+static_assert(sizeof(struct ofdg_splat_job) == sizeof(DevSplatJob) && sizeof(DevSplatJob) == 248 && offsetof(struct ofdg_splat_job, flow) == offsetof(DevSplatJob, flow) &&
+              offsetof(struct ofdg_splat_job, label) == offsetof(DevSplatJob, label) && offsetof(struct ofdg_splat_job, occ) == offsetof(DevSplatJob, occ) &&
+              offsetof(struct ofdg_splat_job, keys) == offsetof(DevSplatJob, keys) && offsetof(struct ofdg_splat_job, image) == offsetof(DevSplatJob, image) &&
+              offsetof(struct ofdg_splat_job, to_own) == offsetof(DevSplatJob, to_own) && offsetof(struct ofdg_splat_job, to_other) == offsetof(DevSplatJob, to_other) &&
+              offsetof(struct ofdg_splat_job, mask) == offsetof(DevSplatJob, mask) && offsetof(struct ofdg_splat_job, fate) == offsetof(DevSplatJob, fate) &&
+              offsetof(struct ofdg_splat_job, rows) == offsetof(DevSplatJob, rows) && offsetof(DevSplatJob, rows) == 160 && offsetof(struct ofdg_splat_job, recs) == offsetof(DevSplatJob, recs) &&
+              offsetof(struct ofdg_splat_job, recs_out) == offsetof(DevSplatJob, recs_out) && offsetof(struct ofdg_splat_job, first_index) == offsetof(DevSplatJob, first_index) &&
+              offsetof(struct ofdg_splat_job, seed) == offsetof(DevSplatJob, seed) && offsetof(DevSplatJob, seed) == 192 && offsetof(struct ofdg_splat_job, width) == offsetof(DevSplatJob, width) &&
+              offsetof(struct ofdg_splat_job, img_fmt) == offsetof(DevSplatJob, img_fmt) && offsetof(struct ofdg_splat_job, occ_fmt) == offsetof(DevSplatJob, occ_fmt) &&
+              offsetof(struct ofdg_splat_job, flags) == offsetof(DevSplatJob, flags) && offsetof(struct ofdg_splat_job, t_min_q8) == offsetof(DevSplatJob, t_min_q8) &&
+              offsetof(struct ofdg_splat_job, t_max_q8) == offsetof(DevSplatJob, t_max_q8) && offsetof(DevSplatJob, t_max_q8) == 232 &&
+              offsetof(struct ofdg_splat_job, reserved) == offsetof(DevSplatJob, reserved), "struct ofdg_splat_job: 248 bytes, the layout the kernels take");
+// The record of global sample g: Philox block 0 under the sampler's key of g at the counter {0, 0, 0x0c77, 0}.  `j` supplies
+// the range (splat_ranges_error has passed).
+OFDG_HD_FN DevSplatRec splat_draw_rec(uint32_t seed, unsigned long long g, const DevSplatJob& j) {
+  const CropWords w = crop_philox(CropWords{0u, 0u, 0x0c77u, 0u}, seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, (uint32_t)g);
+  const int t = j.t_min_q8 + (int)(((unsigned long long)w.x * (unsigned long long)(j.t_max_q8 - j.t_min_q8 + 1)) >> 32);
+  DevSplatRec r;
+  r.t_q8[0] = t; r.t_q8[1] = 256 - t;
+  r.reserved[0] = 0; r.reserved[1] = 0;
+  return r;
+}
+// what is used of a record, given or drawn: each fraction clamped into 0..256
+OFDG_HD_FN DevSplatRec splat_sanitise(DevSplatRec r) {
+  for (int f = 0; f < 2; ++f) {
+    r.t_q8[f] = r.t_q8[f] < 0 ? 0 : r.t_q8[f] > 256 ? 256 : r.t_q8[f];
+    r.reserved[f] = 0;
+  }
+  return r;
+}
+// the 24.8 displacement D (reproj_q8) scaled by T / 256, T in 0..256
+OFDG_HD_FN int splat_scale(int D, int T) { return (int)(((long long)D * T + 128) >> 8); }
+// the rounded target on one axis of pixel `at` displaced by the scaled S (int64: 256 at + S may pass 2^31 on a very wide plane)
+OFDG_HD_FN int splat_round(int at, int S) { return (int)((256ll * at + S + 128) >> 8); }
+OFDG_HD_FN bool splat_inside(int rx, int ry, int W, int H) { return rx >= 0 && rx < W && ry >= 0 && ry < H; }
+// the key of source index s (below 2^24 - 1) under label L: never 0
+OFDG_HD_FN uint32_t splat_key(uint32_t L, uint32_t s) { return (L << 24) | (kSplatIndexMask - s); }
+// the source index of a non-zero key
+OFDG_HD_FN uint32_t splat_source(uint32_t K) { return kSplatIndexMask - (K & kSplatIndexMask); }
+// one component of the flow from the target to the other frame: d = source - target in pixels, D the winner's displacement
+OFDG_HD_FN float splat_to_other(int d, int D) { return (float)(256ll * d + D) * 0.00390625f; }
+// does the launch of splat_resolve_kernel have anything to do?
+OFDG_HD_FN bool splat_resolves(const DevSplatJob& j) {
+  return j.rows || j.image[0] || j.image[1] || j.to_own[0] || j.to_own[1] || j.to_other[0] || j.to_other[1] || j.mask[0] || j.mask[1] || j.fate[0] || j.fate[1];
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* splat_plane_size(const DevSplatJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// What the draw reads of a job: the first rule broken, or nullptr.
+inline const char* splat_ranges_error(const DevSplatJob& j) {
+  if (j.t_min_q8 < 0 || j.t_min_q8 > 256) return "t_min_q8 must lie in 0..256";
+  if (j.t_max_q8 < 0 || j.t_max_q8 > 256) return "t_max_q8 must lie in 0..256";
+  if (j.t_min_q8 > j.t_max_q8) return "t_min_q8 must not be above t_max_q8";
+  return nullptr;
+}
+// The argument rules ofdg_splat and ofdg_host_splat share: the first rule broken, or nullptr.  width, height: what
+// splat_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* splat_arg_error(const DevSplatJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if ((unsigned long long)width * (unsigned long long)height > (unsigned long long)OFDG_SPLAT_MAX_PIXELS) return "width * height must be at most 2^24 - 1";
+  if (j->img_fmt != OFDG_FMT_F32 && j->img_fmt != OFDG_FMT_U8) return "img_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->oflow_fmt != OFDG_FMT_F32 && j->oflow_fmt != OFDG_FMT_F16) return "oflow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if ((j->occ[0] || j->occ[1]) && j->occ_fmt != OFDG_FMT_F32 && j->occ_fmt != OFDG_FMT_U8) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags & ~(OFDG_SPLAT_FRAME0 | OFDG_SPLAT_FRAME1 | OFDG_SPLAT_ACCUMULATE)) return "flags holds unknown bits";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (!(j->flags & (OFDG_SPLAT_FRAME0 | OFDG_SPLAT_FRAME1))) return "flags: no frame is flagged";
+  for (int f = 0; f < 2; ++f) {
+    if (!((j->flags >> f) & 1)) {
+      if (j->img[f] || j->flow[f] || j->label[f] || j->keys[f] || j->image[f] || j->to_own[f] || j->to_other[f] || j->mask[f] || j->fate[f])
+        return f ? "flags: frame 1 has a pointer but is not flagged" : "flags: frame 0 has a pointer but is not flagged";
+      continue;
+    }
+    if (!j->flow[f]) return f ? "flow[1]: a flagged frame needs its flow" : "flow[0]: a flagged frame needs its flow";
+    if (!j->keys[f]) return f ? "keys[1]: a flagged frame needs its key plane" : "keys[0]: a flagged frame needs its key plane";
+    if (j->image[f] && !j->img[f]) return f ? "img[1]: image of frame 1 needs its frame" : "img[0]: image of frame 0 needs its frame";
+  }
+  if (!j->recs)
+    if (const char* why = splat_ranges_error(*j)) return why;
+  // no in-place form: a written range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[24];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  const auto add = [&](const void* p, unsigned long long bytes, bool dst) {
+    if (p) r[nr++] = Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, dst};
+  };
+  for (int f = 0; f < 2; ++f) {
+    add(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
+    add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
+    add(j->label[f], plane, false);
+    add(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
+    add(j->keys[f], plane * 4, true);
+    add(j->image[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
+    add(j->to_own[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
+    add(j->to_other[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
+    add(j->mask[f], plane, true);
+    add(j->fate[f], plane, true);
+  }
+  add(j->rows, (unsigned long long)n * sizeof(DevSplatRow), true);
+  add(j->recs, (unsigned long long)n * sizeof(DevSplatRec), false);
+  add(j->recs_out, (unsigned long long)n * sizeof(DevSplatRec), true);
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.

@@ -17,6 +17,9 @@
 //                                       format, extreme flows, given and drawn records, every refusal
 //   host_input_check reproject          ofdg_host_reproject on exactly sized heap buffers: every format pair, every presence
 //                                       subset of the outputs and of the frames, extreme flows and frames, every refusal
+//   host_input_check splat              ofdg_host_splat and ofdg_splat_draw on exactly sized heap buffers: every format, every
+//                                       presence subset of the outputs and of the frames, with and without labels and maps,
+//                                       extreme flows and frames, given and drawn records, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -477,14 +480,167 @@ int reproject() {
   std::printf("reproject calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
   return refused == 24 ? 0 : 1;
 }
+
+// ofdg_host_splat and ofdg_splat_draw on heap buffers of exactly the planes' sizes (a byte read or written beside one is a
+// report): the 32 format combinations (frames, destination, flow, flows out, map), every subset of image / to_own / to_other /
+// mask / fate / rows for frame 0, frame 1 and both, with and without labels and maps, records given (with fractions out of
+// range) and drawn, flows that hold NaN, infinities, +-3e38, +-65504 and targets beyond every border, float32 frames with NaN
+// and 1e9, on 8x2 (a plane smaller than most displacements) and 72x40; then every refusal.
+int splat() {
+  const float extreme[] = {0.0f, 3.25f, -40.5f, 3e38f, -3e38f, 65504.0f, -65504.0f, 1e-40f, -0.0f, 100.0f, -7.125f, 0.0039f, 0.5f, -0.5f};
+  const uint16_t extreme16[] = {0x0000, 0x4280, 0xd110, 0x7c00, 0xfc00, 0x7bff, 0xfbff, 0x0001, 0x8000, 0x5640, 0xc720, 0x7e00, 0x3800, 0xb800};
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 2; ++size) {
+    const int W = size ? 72 : 8, H = size ? 40 : 2, n = 3;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 32; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32, ff = fmts & 4 ? OFDG_FMT_F16 : OFDG_FMT_F32,
+                of = fmts & 8 ? OFDG_FMT_U8 : OFDG_FMT_F32, qf = fmts & 16 ? OFDG_FMT_F16 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4), fb = n * 2 * px * (ff == OFDG_FMT_F16 ? 2 : 4),
+                   ob = n * px * (of == OFDG_FMT_U8 ? 1 : 4), qb = n * 2 * px * (qf == OFDG_FMT_F16 ? 2 : 4);
+      std::vector<uint8_t> img[2], flow[2], label[2], occ[2], keys[2], image[2], own[2], other[2], mask[2], fate[2], rows((size_t)n * sizeof(ofdg_splat_row), 0xA5);
+      std::vector<uint8_t> recs((size_t)n * sizeof(ofdg_splat_rec)), used((size_t)n * sizeof(ofdg_splat_rec), 0xA5);
+      const int32_t given[3][4] = {{256, 0, 0, 0}, {77, 400, 5, -5}, {-3, 128, 0, 0}};
+      std::memcpy(recs.data(), given, sizeof given);
+      uint32_t x = 9876u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        img[f].resize(sb); flow[f].resize(fb); occ[f].resize(ob); label[f].resize(n * px);
+        keys[f].assign(n * px * 4, 0xA5); image[f].assign(db, 0xA5); own[f].assign(qb, 0xA5); other[f].assign(qb, 0xA5); mask[f].assign(n * px, 0xA5); fate[f].assign(n * px, 0xA5);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          const float v = (e % 11) == 0 ? (e % 22 ? NAN : 1e9f) : (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          if (sf == OFDG_FMT_U8) img[f][e] = (uint8_t)(x >> 24);
+          else std::memcpy(img[f].data() + 4 * e, &v, 4);
+        }
+        for (size_t e = 0; e < n * 2 * px; ++e) {
+          const size_t k = (e / 3 + f) % 14;
+          if (ff == OFDG_FMT_F16) std::memcpy(flow[f].data() + 2 * e, &extreme16[k], 2);
+          else if (k == 11 && (e & 1)) { const float q = NAN; std::memcpy(flow[f].data() + 4 * e, &q, 4); }
+          else std::memcpy(flow[f].data() + 4 * e, &extreme[k], 4);
+        }
+        for (size_t e = 0; e < n * px; ++e) {
+          const float v = (e % 7) == 0 ? NAN : (e % 3) == 0 ? 1.0f : (e % 5) == 0 ? -0.0f : 0.0f;
+          if (of == OFDG_FMT_U8) occ[f][e] = (e % 3) == 0 ? 255 : 0;
+          else std::memcpy(occ[f].data() + 4 * e, &v, 4);
+          label[f][e] = (uint8_t)((e % 13) == 0 ? 255 : (e / 5) % 4);
+        }
+      }
+      for (int frames = 1; frames < 4; ++frames)
+        for (int outs = 0; outs < 64; ++outs)
+          for (int lean = 0; lean < 2; ++lean) {
+            if (lean && (outs & 31) != 31) continue;  // (without labels and maps, with drawn records: with every plane only)
+            if (fmts != 0 && fmts != 31 && (outs & 31) != 31 && (outs & (outs - 1))) continue;  // (every subset in two formats; else none, one, all)
+            struct ofdg_splat_job job;
+            std::memset(&job, 0, sizeof job);
+            for (int f = 0; f < 2; ++f) {
+              if (!lean) job.occ[f] = occ[f].data();
+              if (!((frames >> f) & 1)) continue;
+              job.img[f] = img[f].data(); job.flow[f] = flow[f].data(); job.keys[f] = (uint32_t*)keys[f].data();
+              if (!lean) job.label[f] = label[f].data();
+              if (outs & 1) job.image[f] = image[f].data();
+              if (outs & 2) job.to_own[f] = own[f].data();
+              if (outs & 4) job.to_other[f] = other[f].data();
+              if (outs & 8) job.mask[f] = mask[f].data();
+              if (outs & 16) job.fate[f] = fate[f].data();
+            }
+            if (outs & 32) job.rows = (ofdg_splat_row*)rows.data();
+            if (!lean) job.recs = (const ofdg_splat_rec*)recs.data();
+            job.recs_out = (ofdg_splat_rec*)used.data();
+            job.first_index = (1ll << 33) + outs; job.seed = 7u + (uint32_t)fmts; job.t_min_q8 = 0; job.t_max_q8 = lean ? 256 : 999;
+            job.img_fmt = sf; job.dst_fmt = df; job.flow_fmt = ff; job.oflow_fmt = qf; job.occ_fmt = of;
+            job.flags = frames | ((outs & 32) && (frames & 2) ? OFDG_SPLAT_ACCUMULATE : 0);
+            const int rc = ofdg_host_splat(&job, n, W, H);
+            if (rc) { std::printf("splat: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+            ++calls;
+            for (int f = 0; f < 2; ++f)
+              sum = sum * 31 + fnv1a(keys[f].data(), keys[f].size()) + fnv1a(image[f].data(), image[f].size()) + fnv1a(own[f].data(), own[f].size()) +
+                    fnv1a(other[f].data(), other[f].size()) + fnv1a(mask[f].data(), mask[f].size()) + fnv1a(fate[f].data(), fate[f].size());
+            sum = sum * 31 + fnv1a(rows.data(), rows.size()) + fnv1a(used.data(), used.size());
+          }
+    }
+  }
+  // the draw: its range is kept, and an index above 2^32 has a key of its own
+  {
+    struct ofdg_splat_job ranges;
+    std::memset(&ranges, 0, sizeof ranges);
+    ranges.t_min_q8 = 64; ranges.t_max_q8 = 192;
+    ofdg_splat_rec r;
+    for (long long g = 0; g < 64; ++g) {
+      if (ofdg_splat_draw(5, (g & 1 ? 1ll << 32 : 0) + g, &ranges, &r) != OFDG_OK || r.t_q8[0] < 64 || r.t_q8[0] > 192 || r.t_q8[0] + r.t_q8[1] != 256 || r.reserved[0] || r.reserved[1]) {
+        std::printf("splat: the draw left its range\n");
+        return 1;
+      }
+      sum = sum * 31 + (unsigned)r.t_q8[0];
+    }
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    const size_t px = (size_t)n * W * H;
+    std::vector<uint8_t> img0(px * 12, 0), flow0(px * 8, 0), flow1(px * 8, 0), label0(px, 0), occ0(px * 4, 0), occ1(px * 4, 0), keys(px * 4, 0xA5), keys1(px * 4, 0xA5), image(px * 12, 0xA5),
+        own(px * 8, 0xA5), other(px * 8, 0xA5), mask(px, 0xA5), fate(px, 0xA5), rows((size_t)n * sizeof(ofdg_splat_row), 0xA5), recs((size_t)n * sizeof(ofdg_splat_rec), 0),
+        used((size_t)n * sizeof(ofdg_splat_rec), 0xA5);
+    struct ofdg_splat_job good;
+    std::memset(&good, 0, sizeof good);
+    good.img[0] = img0.data(); good.flow[0] = flow0.data(); good.label[0] = label0.data(); good.occ[0] = occ0.data(); good.occ[1] = occ1.data();
+    good.keys[0] = (uint32_t*)keys.data(); good.image[0] = image.data(); good.to_own[0] = own.data(); good.to_other[0] = other.data(); good.mask[0] = mask.data();
+    good.fate[0] = fate.data(); good.rows = (ofdg_splat_row*)rows.data(); good.recs = (const ofdg_splat_rec*)recs.data(); good.recs_out = (ofdg_splat_rec*)used.data();
+    good.flags = OFDG_SPLAT_FRAME0;
+    const auto refuse = [&](struct ofdg_splat_job j, int ns, int w, int h) {
+      if (ofdg_host_splat(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_splat: ", 17) == 0) ++refused;
+      else std::printf("splat: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_splat_job j;
+    ofdg_splat_rec r;
+    if (ofdg_host_splat(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 4096, 4096);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.img_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.oflow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.occ_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.flags = 9; refuse(j, n, W, H);
+    j = good; j.flags = OFDG_SPLAT_ACCUMULATE; refuse(j, n, W, H);
+    j = good; j.flags = OFDG_SPLAT_FRAME1; refuse(j, n, W, H);
+    j = good; j.reserved[1] = 1; refuse(j, n, W, H);
+    j = good; j.flow[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.keys[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.img[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.flow[1] = flow1.data(); refuse(j, n, W, H);
+    j = good; j.keys[1] = (uint32_t*)keys1.data(); refuse(j, n, W, H);
+    j = good; j.flags = 3; j.flow[1] = flow1.data(); refuse(j, n, W, H);
+    j = good; j.recs = nullptr; j.t_min_q8 = -1; refuse(j, n, W, H);
+    j = good; j.recs = nullptr; j.t_max_q8 = 257; refuse(j, n, W, H);
+    j = good; j.recs = nullptr; j.t_min_q8 = 2; j.t_max_q8 = 1; refuse(j, n, W, H);
+    j = good; j.image[0] = img0.data(); refuse(j, n, W, H);
+    j = good; j.keys[0] = (uint32_t*)(own.data() + 16); refuse(j, n, W, H);
+    j = good; j.rows = (ofdg_splat_row*)(other.data() + 16); refuse(j, n, W, H);
+    j = good; j.mask[0] = fate.data() + px - 1; refuse(j, n, W, H);
+    j = good; j.recs_out = (ofdg_splat_rec*)recs.data(); refuse(j, n, W, H);
+    j = good; j.t_min_q8 = 9; j.t_max_q8 = 8;
+    if (ofdg_splat_draw(1, 0, &j, &r) == OFDG_EINVAL && ofdg_splat_draw(1, 0, nullptr, &r) == OFDG_EINVAL && ofdg_splat_draw(1, 0, &good, nullptr) == OFDG_EINVAL) ++refused;
+    const auto untouched = [](const std::vector<uint8_t>& v) { return std::all_of(v.begin(), v.end(), [](uint8_t b) { return b == 0xA5; }); };
+    if (!(untouched(keys) && untouched(keys1) && untouched(image) && untouched(own) && untouched(other) && untouched(mask) && untouched(fate) && untouched(rows) && untouched(used))) {
+      std::printf("splat: a refusal wrote something\n");
+      return 1;
+    }
+    if (ofdg_splat_draw(1, (1ll << 32) + 3, &good, &r) != OFDG_OK || ofdg_host_splat(&good, n, W, H) != OFDG_OK) { std::printf("splat: the valid call failed\n"); return 1; }
+  }
+  std::printf("splat calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 30 ? 0 : 1;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
   if (argc >= 2 && std::strcmp(argv[1], "reproject") == 0) return reproject();
+  if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat\n", argv[0]);
   return 2;
 }
