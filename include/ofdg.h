@@ -1005,6 +1005,113 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
 int ofdg_erase_draw(uint32_t seed, long long index, int width, int height, const struct ofdg_erase_job* ranges, ofdg_erase_rec* out);
 
 /*
+ * Colour jitter ("ColorJitter" of the RAFT-family recipes): brightness, contrast about the frame's own mean luminance,
+ * saturation and hue on image0 and / or image1 of a batch, each sample by a record of its own, the four operations in the
+ * sample's own order, both frames alike or - with a drawn probability - each on its own.  What ofdg_photo's one table per
+ * channel cannot hold: saturation and hue mix the three channels of a pixel, the contrast needs a reduction over the frame at
+ * its place in the chain.  The record is a pure function of (seed, global sample index).  Everything below is integers: the
+ * kernels, ofdg_host_jitter and the numpy restatement of the tests give the same bytes.  >> is the arithmetic (floor) shift.
+ *
+ * Planes, formats, sizes and aliasing as in ofdg_photo: src[f] is image f as [n,3,height,width] planar B, G, R of src_fmt, dst[f]
+ * the same shape of dst_fmt; OFDG_FMT_F32 or OFDG_FMT_U8, chosen independently.  A frame is present when both its pointers are
+ * given (src[f] and dst[f] both NULL: absent).  width = height = 0: the context's frame; otherwise any size the context's rule
+ * allows.  dst[f] == src[f] with src_fmt == dst_fmt is the in-place form.  The byte of a uint8 element is itself, of a float32
+ * element the index rule of ofdg_photo (clamped to [0, 255], a NaN 0, to nearest even); a uint8 destination stores the byte, a
+ * float32 one (float)byte.
+ *
+ * Record of sample i: recs[i] when recs is given, else ofdg_jitter_draw(seed, first_index + i, the job's ranges).  Either way
+ * it is sanitised before use, and the sanitised record, with the means, is what recs_out[i] receives.  Per frame f:
+ * brightness[f], contrast[f], saturation[f] in Q16 (65536: no change), hue[f] in units of 1 / 393216 of a turn (65536 per
+ * 60-degree sector), order[f] in 0..23: the index of the permutation of (brightness, contrast, saturation, hue) in
+ * lexicographic order - 0: b c s h, 1: b c h s, ... 23: h s c b.  shared: the contrast's mean is taken over both frames together.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, {seed ^ (uint32)(g >> 32) *
+ *    0x9E3779B9, (uint32)g}, blocks j = 0, 1, 2 at the counters {j, 0, 0x0c78, 0} (taken: 0x0fd9 the sampler, 0x0c70 crop, 0x0c71
+ *    and 0x0c72 photo, 0x0c73 spatial, 0x0c74 and 0x0c75 erase, 0x0c76 motion blur, 0x0c77 splat).  A = (int)lrintf(range *
+ *    65536.0f) for brightness, contrast and saturation, (int)lrintf(range * 393216.0f) for hue (to nearest even);  isym(w, A) =
+ *    (int)(((uint64)w * (uint32)(2 A + 1)) >> 32) - A, uniform on [-A, A];  u(w) = (float)(w >> 8) * 2^-24 as in ofdg_photo.
+ *      block f (f = 0, 1):  brightness[f] = 65536 + isym(.x, A_b)   contrast[f] = 65536 + isym(.y, A_c)
+ *                           saturation[f] = 65536 + isym(.z, A_s)   hue[f] = isym(.w, A_h)
+ *      block 2:  asymmetric = u(.x) < asym_prob;  order[0] = (int)(((w.y >> 8) * 24) >> 24);  order[1] likewise from .z
+ *    Not asymmetric: frame 1 takes frame 0's five fields and shared = 1; asymmetric: shared = 0.  mean = {-1, -1}, reserved 0.
+ *    All ranges 0 give an identity record: every factor 65536, both hues 0 (the order is drawn all the same; it then changes
+ *    nothing).
+ * 2. Sanitise.  Factors clamp to [0, 4 * 65536], hue to [-196608, 196608] (half a turn either way), order to 0..23; shared
+ *    becomes 1 where it is non-zero and the two frames' five fields are equal, else 0; mean = {-1, -1}; reserved = 0.
+ * 3. The operations, on the three bytes (B, G, R) of a pixel; each ends in bytes, as the recipe's uint8 pipeline does.
+ *      lum = (7471 B + 38470 G + 19595 R + 32768) >> 16                        (Rec.601; the weights sum to 65536)
+ *      mix(a, m, q) = clamp((q a + (65536 - q) m + 32768) >> 16, 0, 255)        (fits 32 bits; mix(a, m, 65536) == a)
+ *      brightness:  c = mix(c, 0, brightness[f])        saturation:  c = mix(c, lum of the pixel, saturation[f])
+ *      contrast:    c = mix(c, mean, contrast[f]), mean of step 4
+ *      hue: the HSV hue shift without leaving integers.  mx, mn: the largest and smallest of the three, d = mx - mn.  d == 0:
+ *        unchanged.  Else the sector s of the hexagon is the first of  0: max R min B,  1: max G min B,  2: max G min R,
+ *        3: max B min R,  4: max B min G,  5: max R min G  that holds (mid: the third channel), and the distance into it
+ *        t = mid - mn in even sectors, d - (mid - mn) in odd ones.  Hq = (65536 s + (65536 t) / d + hue[f]) mod 393216, the
+ *        division floored, the modulus non-negative;  s' = Hq >> 16, f' = Hq & 65535;  the new third channel is
+ *        mn + ((d f' + 32768) >> 16) in even s', mn + ((d (65536 - f') + 32768) >> 16) in odd s'; mx and mn go where sector
+ *        s' has its largest and smallest.  A hue of 0 changes nothing, one of 131072 is (R, G, B) -> (B, R, G); against a float
+ *        HSV round trip a channel is off by less than 0.5 + 255 / 65536.
+ *    The four run in the order order[f] names.  A frame whose three factors are 65536 and whose hue is 0 is copied - bit for
+ *    bit where src_fmt == dst_fmt (in place: not touched at all), else through its bytes.
+ * 4. Mean, for a frame with contrast[f] != 65536 (else none is computed and mean[f] = -1):  S = the sum of lum over the N =
+ *    width * height pixels of the frame AFTER the operations that stand before the contrast in order[f], in 64 bits;
+ *    mean[f] = (2 S + N) / (2 N) by integer division: a byte.  With shared set and both frames present S and N are those of
+ *    both frames together (the frames' fields are equal then), and mean[1] = mean[0]; with one frame present, that frame's.
+ *    An absent frame has mean[f] = -1.
+ *
+ * work: DEVICE memory of n_samples * OFDG_JITTER_WORK_BYTES, 16-byte aligned; contents unspecified before and after (the call
+ * clears it).  Required whenever recs is given, and with drawn records unless A_c = 0 (a contrast range of at most 2^-17: no
+ * drawn record has a contrast then, so no mean is taken and `work` is not looked at).  Asynchronous on `stream`, the stream
+ * the frames were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  At most one clearing of `work` and two kernels per
+ * call, integer atomics only; it reads no record of the context and works in every mode.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, one of width /
+ * height 0 or a size that breaks the rule, 3 * width * height of 2^32 and more, another format code, non-zero flags or
+ * reserved, a range that is negative, NaN, infinite or above its bound (brightness, contrast, saturation 3, hue 0.5,
+ * asym_prob 1), no frame set, src[f] without dst[f] or the reverse, work NULL where it is required, a misaligned pointer
+ * (sources as the render calls ask: 16-byte float32, 4-byte uint8; destinations, work and both record arrays 16-byte), a
+ * written range (destinations, work, recs_out) that overlaps any other range of the job - but for dst[f] == src[f] with
+ * src_fmt == dst_fmt -, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: bit parity with any framework's ColorJitter (those truncate where this rounds, and keep a float mean), a
+ * probability per operation, gamma and noise (ofdg_photo).
+ */
+#define OFDG_JITTER_WORK_BYTES 16    /* of job->work per sample */
+typedef struct ofdg_jitter_rec {     /* 64 bytes; index [f] = frame 0 / 1 */
+  int32_t brightness[2], contrast[2], saturation[2];   /* Q16 */
+  int32_t hue[2];                    /* 1 / 393216 of a turn */
+  int32_t order[2];                  /* 0..23 */
+  int32_t shared;                    /* 0 / 1 */
+  int32_t mean[2];                   /* written into recs_out, never read: the byte the contrast pivots on, or -1 */
+  int32_t reserved[3];
+} ofdg_jitter_rec;
+struct ofdg_jitter_job {             /* 112 bytes */
+  const void* src[2]; void* dst[2];  /* image0, image1: [n,3,height,width]; each frame optional (src and dst both NULL) */
+  const ofdg_jitter_rec* recs;       /* DEVICE, n records, or NULL: drawn */
+  ofdg_jitter_rec*       recs_out;   /* DEVICE, n records, or NULL */
+  void* work;                        /* DEVICE, n * OFDG_JITTER_WORK_BYTES */
+  long long first_index; uint32_t seed;
+  int32_t width, height;             /* 0, 0: the context's frame */
+  int32_t src_fmt, dst_fmt;          /* OFDG_FMT_F32 or OFDG_FMT_U8, independently */
+  int32_t flags, reserved;           /* no flag yet: both must be 0 */
+  float brightness, contrast, saturation, hue, asym_prob;   /* ranges of the draw: <= 3, 3, 3, 0.5 (turns), 1 */
+};
+int ofdg_jitter(ofdg_ctx* ctx, const struct ofdg_jitter_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and records in host memory, no alignment asked of any
+ * pointer, work not looked at.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_jitter(const struct ofdg_jitter_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (step 1 alone: not sanitised; pure, no GPU).  Of `ranges` only the five ranges are
+ * read.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer or a range that is negative, NaN, infinite
+ * or above its bound. */
+int ofdg_jitter_draw(uint32_t seed, long long index, const struct ofdg_jitter_job* ranges, ofdg_jitter_rec* out);
+/* The hue operation of step 3 alone on `pixels` pixels of planar bytes (pure, no GPU): bgr and out are [3][pixels], B, G, R; out
+ * may be bgr.  hue is taken as it is, not sanitised, anywhere in [-393216, 393216] - exposed so that the operation's identities
+ * (a whole turn either way, the channel rotation) can be held over the whole colour cube.  OFDG_EINVAL for a NULL pointer or a
+ * hue outside that range. */
+int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hue);
+
+/*
  * Motion blur: every pixel of image0 and / or image1 becomes a weighted mean of its frame along a short segment through the
  * pixel, whose direction and length are the pixel's own flow times the sample's shutter - the fraction of the inter-frame
  * interval the exposure lasts.  The exposure is centred on the frame's instant, so the segment is symmetric about the pixel

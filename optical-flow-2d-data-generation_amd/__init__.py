@@ -114,6 +114,7 @@ EXPORTS = [
     "ofdg_motion_blur", "ofdg_host_motion_blur", "ofdg_motion_blur_draw",
     "ofdg_reproject", "ofdg_host_reproject",
     "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
+    "ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw", "ofdg_host_jitter_hue",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1093,6 +1094,130 @@ def host_erase(images, occ=None, flow=None, recs=None, first_index=0, seed=0, ra
     return used
 
 
+# colour jitter (ofdg_jitter_rec / struct ofdg_jitter_job / ofdg_jitter, include/ofdg.h)
+JITTER_WORK_BYTES = 16  # OFDG_JITTER_WORK_BYTES
+JITTER_REC_WORDS = 16   # a record as int32 [16]: brightness[2] contrast[2] saturation[2] hue[2] order[2] shared mean[2], then 3 reserved words
+JITTER_ONE = 65536      # the Q16 factor that changes nothing; the hue units of one 60-degree sector
+JITTER_TURN = 393216    # the hue units of a whole turn
+JITTER_RANGES = ("brightness", "contrast", "saturation", "hue", "asym_prob")
+# The ColorJitter of the RAFT-family recipes (RAFT, GMA, GMFlow, FlowFormer): brightness, contrast and saturation by [0.6, 1.4],
+# the hue by up to 0.5 / 3.14 of a turn either way, every fifth sample with each frame on its own.
+JITTER_RAFT = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.5 / 3.14, asym_prob=0.2)
+
+
+class JitterRec(C.Structure):
+    """ofdg_jitter_rec: the transform of one sample (64 bytes)."""
+    _fields_ = [("brightness", C.c_int32 * 2), ("contrast", C.c_int32 * 2), ("saturation", C.c_int32 * 2), ("hue", C.c_int32 * 2),
+                ("order", C.c_int32 * 2), ("shared", C.c_int32), ("mean", C.c_int32 * 2), ("reserved", C.c_int32 * 3)]
+
+
+class JitterJob(C.Structure):
+    """struct ofdg_jitter_job (112 bytes)."""
+    _fields_ = [("src", C.c_void_p * 2), ("dst", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p), ("work", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)] + \
+               [(name, C.c_float) for name in JITTER_RANGES]
+
+
+def _jitter_rec_dtype():
+    import numpy as np
+    return np.dtype([("brightness", "<i4", (2,)), ("contrast", "<i4", (2,)), ("saturation", "<i4", (2,)), ("hue", "<i4", (2,)), ("order", "<i4", (2,)),
+                     ("shared", "<i4"), ("mean", "<i4", (2,)), ("reserved", "<i4", (3,))])
+
+
+def jitter_numpy(recs):
+    """Records of Generator.jitter / host_jitter - a torch tensor or numpy array of int32 [n,16] (or any array of 64 bytes a
+    record) - as a numpy structured array [n] with the fields brightness, contrast, saturation, hue, order, mean (each [2]: frame
+    0, frame 1), shared and reserved [3]."""
+    import numpy as np
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _jitter_rec_dtype():
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % 64:
+        raise ValueError("records must be 64 bytes each, got %d bytes" % raw.size)
+    return raw.view(_jitter_rec_dtype())
+
+
+def _jitter_ranges(job, ranges):
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in JITTER_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(JITTER_RANGES)))
+    for key in JITTER_RANGES:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    return job
+
+
+def _jitter_job(src, dst, ptr, codes, size, recs, recs_out, work, first_index, seed, ranges):
+    job = _jitter_ranges(JitterJob(), ranges)
+    for f in range(2):
+        if src[f] is not None:
+            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
+    job.recs, job.recs_out, job.work = recs, recs_out, work
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt = codes
+    return job
+
+
+def jitter_draw(seed, index, ranges=None):
+    """ofdg_jitter_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (JITTER_RANGES; a
+    missing one is 0; JITTER_RAFT for one), before sanitising, as one element of the structured array jitter_numpy describes."""
+    job = _jitter_ranges(JitterJob(), ranges)
+    out = JitterRec()
+    _host_check(lib().ofdg_jitter_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return jitter_numpy(bytearray(out))[0]
+
+
+def host_jitter_hue(bgr, hue):
+    """ofdg_host_jitter_hue (pure, no GPU): the hue operation alone on a uint8 array [3, ...] (B, G, R planes), hue in
+    [-JITTER_TURN, JITTER_TURN] as it is, not sanitised.  Returns the shifted array."""
+    import numpy as np
+    bgr = np.ascontiguousarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim < 1 or bgr.shape[0] != 3:
+        raise ValueError("bgr must be uint8 [3, ...], got %s %s" % (bgr.dtype, bgr.shape))
+    out = np.zeros(bgr.shape, np.uint8)
+    _host_check(lib().ofdg_host_jitter_hue(_hptr(bgr), _hptr(out), bgr.size // 3, int(hue)))
+    return out
+
+
+def alloc_jitter(n, device="cuda"):
+    """(work, recs) of Generator.jitter for n samples: the uint8 [n,16] workspace of the contrast's mean and the int32 [n,16]
+    records (recs_out).  Not filled: the call clears the first and writes every record."""
+    import torch
+    return (torch.empty((n, JITTER_WORK_BYTES), dtype=torch.uint8, device=device),
+            torch.empty((n, JITTER_REC_WORDS), dtype=torch.int32, device=device))
+
+
+def host_jitter(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None, in_place=False):
+    """ofdg_host_jitter (no GPU): the colour jitter of HOST arrays - src a pair (image0, image1) of float32 or uint8 arrays
+    [n,3,H,W] (planar B, G, R), either None; recs None (drawn from seed, first_index and ranges) or n records (jitter_numpy's
+    array, or int32 [n,16]).  dst_dtype: np.float32 / np.uint8, default the source's.  in_place: the sources themselves are
+    written (they must be contiguous and of dst_dtype).  Returns ((image0, image1), recs_used): the jittered arrays (None for
+    an absent frame) and the records after sanitising, with the means, as jitter_numpy's array."""
+    import numpy as np
+    src = tuple(src)
+    if not in_place:
+        src = tuple(None if t is None else np.ascontiguousarray(t) for t in src)
+    given = [t for t in src if t is not None]
+    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
+    dst = src if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in src)
+    n, height, width, *codes = photo_format(src, dst)
+    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
+        raise ValueError("in_place needs contiguous sources of dst_dtype")
+    if recs is not None:
+        recs = jitter_numpy(recs).copy()
+        if recs.shape != (n,):
+            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
+    used = np.zeros((n,), _jitter_rec_dtype())
+    job = _jitter_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data, None,
+                      first_index, seed, ranges)
+    _host_check(lib().ofdg_host_jitter(C.byref(job), n, width, height))
+    return dst, used
+
+
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
 MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
 MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
@@ -1763,6 +1888,10 @@ def lib():
         L.ofdg_erase.argtypes = [vp, C.POINTER(EraseJob), i32, vp]
         L.ofdg_host_erase.argtypes = [C.POINTER(EraseJob), i32, i32, i32]
         L.ofdg_erase_draw.argtypes = [C.c_uint32, C.c_longlong, i32, i32, C.POINTER(EraseJob), C.POINTER(EraseRec)]
+        L.ofdg_jitter.argtypes = [vp, C.POINTER(JitterJob), i32, vp]
+        L.ofdg_host_jitter.argtypes = [C.POINTER(JitterJob), i32, i32, i32]
+        L.ofdg_jitter_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(JitterJob), C.POINTER(JitterRec)]
+        L.ofdg_host_jitter_hue.argtypes = [vp, vp, C.c_size_t, i32]
         L.ofdg_motion_blur.argtypes = [vp, C.POINTER(MblurJob), i32, vp]
         L.ofdg_host_motion_blur.argtypes = [C.POINTER(MblurJob), i32, i32, i32]
         L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
@@ -2230,6 +2359,30 @@ class Generator:
                          _optr(work) if fill == ERASE_MEAN else None, first_index, self._seed(seed), ranges, fill, color, frames, mark_occ)
         self._check(lib().ofdg_erase(self.h, C.byref(job), n, C.c_void_p(stream)))
         return images
+
+    def jitter(self, src, dst=None, recs=None, first_index=0, seed=None, ranges=None, recs_out=None, stream=0, size=None, work=None):
+        """Colour jitter of both frames of a batch (ofdg_jitter, include/ofdg.h): brightness, contrast about the frame's own mean
+        luminance, saturation and hue, in the sample's own order, both frames alike or - with probability asym_prob - each on
+        its own.  src: the pair (image0, image1) of float32 or uint8 tensors [n,3,H,W] a render / forward call (or crop, spatial,
+        motion_blur, photo) wrote, either member None.  dst: the pair to write, float32 or uint8 independently of src; None: in
+        place.  recs: None - the record of sample i is jitter_draw(seed, first_index + i, ranges) - or an int32 device tensor
+        [n,16], taken as given; either is sanitised.  ranges: a dict of JITTER_RANGES (a missing one is 0; JITTER_RAFT is the
+        recipe's).  seed: default the context's.  recs_out: None or an int32 device tensor [n,16] that receives the records used,
+        with the means (jitter_numpy reads it).  work: the uint8 [n,16] workspace of the contrast's mean (alloc_jitter makes
+        both), one per call in flight; needed with recs= and whenever ranges holds a contrast.  stream: the stream the frames
+        were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of the context's.  Asynchronous.
+        Returns dst."""
+        src = tuple(src)
+        dst = src if dst is None else tuple(dst)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = photo_format(src, dst, height, width)
+        self._check_recs(recs, recs_out, "int32", (n, JITTER_REC_WORDS))
+        if work is not None and (str(work.dtype) != "torch.uint8" or work.numel() < n * JITTER_WORK_BYTES):
+            raise ValueError("work must be a uint8 device tensor of at least [%d,%d] (alloc_jitter)" % (n, JITTER_WORK_BYTES))
+        job = _jitter_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), _optr(work), first_index,
+                          self._seed(seed), ranges)
+        self._check(lib().ofdg_jitter(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
                     size=None):
@@ -2938,6 +3091,7 @@ class _RingSlot:
                  "stats",        # the rows of stats=True
                  "pyramid",      # the levels of pyramid=, or (levels, weights)
                  "photo",        # the records of photo=
+                 "jitter",       # (workspace, records) of jitter=
                  "erase",        # (workspace, records) of erase=
                  "edges",        # the planes of boundaries= by name ...
                  "edge_args",    # ... and the plane arguments of Generator.boundaries that fill them
@@ -2971,16 +3125,18 @@ class FlowLoader:
         5. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
                             places of image0 / image1 for every later stage and in the batch
         6. photo=           in place, on both frames
-        7. erase=           in place, on the frames and the occlusion maps
-        8. objects=True     the table, of the label planes of stage 1
-        9. stats=, pyramid= the reductions of flow and occ0
-        10. boundaries=     of the flows and label planes
-        11. pack=           of image0, image1 and flow, into tensors of its own
+        7. jitter=          in place, on both frames
+        8. erase=           in place, on the frames and the occlusion maps
+        9. objects=True     the table, of the label planes of stage 1
+        10. stats=, pyramid= the reductions of flow and occ0
+        11. boundaries=     of the flows and label planes
+        12. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
-    eraser's mean fill is that of the augmented frame, the reductions see the occ0 the eraser extended and the unpacked,
+    colour jitter and the eraser's mean fill see the augmented frame - the fill is the mean colour of the jittered frame, as in
+    the RAFT recipe -, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (neither photo= nor erase= touches what they read).  The records of stages 2 and 4 to 7 are drawn from the
+    the un-erased sample (none of photo=, jitter= and erase= touches what they read).  The records of stages 2 and 4 to 8 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -3018,6 +3174,9 @@ class FlowLoader:
     index wins.  frames=None: both frames when "flow1" is among extras=, else frame 0; frame 1 without "flow1" raises.
     photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
     holds "photo" (float32 [n,16], the records used).
+    jitter=ranges (a dict of JITTER_RANGES, JITTER_RAFT for the recipe's): the ColorJitter of the RAFT-family recipes on both
+    frames (Generator.jitter), behind photo= and in front of erase=; the dict also holds "jitter" (int32 [n,16], the records used
+    with the means: jitter_numpy).
     erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
     takes them): occluder rectangles are painted into the frames and the occlusion maps among extras= extended; the dict also
     holds "erase" (int32 [n,24], the records used: erase_numpy).  mark_occ=True needs a map among extras=; marking occ1 for
@@ -3045,13 +3204,14 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, splat=None, **kw):
+                 reproject=None, splat=None, jitter=None, **kw):
         import torch
         self.boundaries = self._boundary_options(boundaries, extras)
         self.erase = self._erase_options(erase, extras)
         self.motion_blur = self._motion_blur_options(motion_blur, extras)
         self.reproject = self._reproject_options(reproject, extras)
         self.splat = self._splat_options(splat, extras)
+        self.jitter = self._jitter_options(jitter)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -3124,6 +3284,7 @@ class FlowLoader:
                 blurred, t.blur = alloc_motion_blur(n, ph, pw, t.sharp["image0"].dtype, self.motion_blur[1])
                 t.planes = dict(t.sharp, **{"image%d" % f: b for f, b in enumerate(blurred) if b is not None})
             t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
+            t.jitter = alloc_jitter(n) if self.jitter is not None else None
             t.erase = alloc_erase(n) if self.erase is not None else None
             t.objects = alloc_object_table(n) if objects else None
             t.stats = alloc_flow_stats(n) if stats else None
@@ -3201,6 +3362,14 @@ class FlowLoader:
         return {k: v for k, v in erase.items() if k in ERASE_RANGES}, o
 
     @staticmethod
+    def _jitter_options(jitter):
+        """jitter= as a dict of its own, or None; raises for a name that is no range"""
+        if jitter is None:
+            return None
+        _jitter_ranges(JitterJob(), jitter)
+        return dict(jitter)
+
+    @staticmethod
     def _motion_blur_options(motion_blur, extras):
         """motion_blur= split into (ranges with taps_side, frames), or None; raises for what the loader cannot serve"""
         if motion_blur is None:
@@ -3270,7 +3439,7 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
@@ -3298,6 +3467,9 @@ class FlowLoader:
                           flow=pick(t.sharp["flow"], t.sharp.get("flow1")), first_index=first, ranges=ranges, recs_out=t.blur, stream=s, size=size)
         if self.photo is not None:
             g.photo((planes["image0"], planes["image1"]), recs_out=t.photo, first_index=first, ranges=self.photo, stream=s, size=size)
+        if self.jitter is not None:
+            work, recs = t.jitter
+            g.jitter((planes["image0"], planes["image1"]), recs_out=recs, first_index=first, ranges=self.jitter, stream=s, size=size, work=work)
         if self.erase is not None:
             ranges, o = self.erase
             work, recs = t.erase
@@ -3339,6 +3511,8 @@ class FlowLoader:
             more["motion_blur"] = t.blur
         if t.photo is not None:
             more["photo"] = t.photo
+        if t.jitter is not None:
+            more["jitter"] = t.jitter[1]
         if t.objects is not None:
             more["objects"], more["object_counts"] = t.objects
         if t.stats is not None:

@@ -745,6 +745,96 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
   return OFDG_OK;
 }
 
+// ofdg_jitter on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the order's
+// decoding, the operations and the mean are the functions the kernels run (csrc/ofdg_device.h); elements are moved with memcpy.
+int ofdg_jitter_draw(uint32_t seed, long long index, const struct ofdg_jitter_job* ranges, ofdg_jitter_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_jitter_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevJitterJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = jitter_ranges_error(j)) { g_host_error = std::string("ofdg_jitter_draw: ") + why; return OFDG_EINVAL; }
+  const DevJitterRec r = jitter_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hue) {
+  if (!bgr || !out || hue < -kJitterTurn || hue > kJitterTurn) { g_host_error = "ofdg_host_jitter_hue: bgr or out is NULL, or hue outside [-393216, 393216]"; return OFDG_EINVAL; }
+  for (size_t k = 0; k < pixels; ++k) {
+    int B = bgr[k], G = bgr[pixels + k], R = bgr[2 * pixels + k];
+    jitter_hue(B, G, R, hue);
+    out[k] = (uint8_t)B; out[pixels + k] = (uint8_t)G; out[2 * pixels + k] = (uint8_t)R;
+  }
+  return OFDG_OK;
+}
+int ofdg_host_jitter(const struct ofdg_jitter_job* job, int n_samples, int width, int height) {
+  const DevJitterJob* const j = reinterpret_cast<const DevJitterJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = jitter_arg_error(j, n_samples, width, height, /*with_work=*/false);
+  if (why) { g_host_error = std::string("ofdg_host_jitter: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  std::vector<uint8_t> px[2];  // the bytes of a sample's frame, pixel by pixel: B G R
+  for (int i = 0; i < n_samples; ++i) {
+    DevJitterRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = jitter_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
+    r = jitter_sanitise(r);
+    unsigned long long S[2] = {0, 0};
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const JitterFrame p = jitter_frame(r, f);
+      px[f].resize(3 * plane);
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t* const sp = static_cast<const uint8_t*>(j->src[f]) + ((size_t)i * 3 + c) * plane * ses;
+        for (size_t k = 0; k < plane; ++k) {
+          int b = sp[k];
+          if (ses == 4) {
+            float e;
+            std::memcpy(&e, sp + 4 * k, 4);
+            b = photo_index(e);
+          }
+          px[f][3 * k + c] = (uint8_t)b;
+        }
+      }
+      if (p.contrast == kJitterOne) continue;
+      const uint32_t ops = jitter_ops(p.order);
+      const int places = jitter_contrast_place(ops);
+      for (size_t k = 0; k < plane; ++k) {
+        int B = px[f][3 * k], G = px[f][3 * k + 1], R = px[f][3 * k + 2];
+        for (int place = 0; place < places; ++place) jitter_op(jitter_op_at(ops, place), p, 0, B, G, R);
+        S[f] += (unsigned long long)jitter_lum(B, G, R);
+      }
+    }
+    const bool joint = r.shared && j->src[0] && j->src[1];
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const JitterFrame p = jitter_frame(r, f);
+      const int mean = p.contrast == kJitterOne ? -1 : jitter_mean_byte(joint ? S[0] + S[1] : S[f], joint ? 2ull * plane : (unsigned long long)plane);
+      r.mean[f] = mean;
+      const bool same_fmt = j->src_fmt == j->dst_fmt;
+      if (jitter_identity(p) && same_fmt) {  // copied bit for bit; in place: not touched
+        if (j->dst[f] != j->src[f])
+          std::memmove(static_cast<uint8_t*>(j->dst[f]) + (size_t)i * 3 * plane * des, static_cast<const uint8_t*>(j->src[f]) + (size_t)i * 3 * plane * ses, 3 * plane * ses);
+        continue;
+      }
+      const uint32_t ops = jitter_ops(p.order);
+      for (size_t k = 0; k < plane; ++k) {
+        int v[3] = {px[f][3 * k], px[f][3 * k + 1], px[f][3 * k + 2]};
+        for (int place = 0; place < 4; ++place) jitter_op(jitter_op_at(ops, place), p, mean, v[0], v[1], v[2]);
+        for (int c = 0; c < 3; ++c) {
+          uint8_t* const dp = static_cast<uint8_t*>(j->dst[f]) + (((size_t)i * 3 + c) * plane + k) * des;
+          const float e = (float)v[c];
+          if (des == 4) std::memcpy(dp, &e, 4);
+          else *dp = (uint8_t)v[c];
+        }
+      }
+    }
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+  }
+  return OFDG_OK;
+}
+
 // ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.

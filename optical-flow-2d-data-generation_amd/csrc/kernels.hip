@@ -4548,6 +4548,214 @@ __global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEra
   }
 }
 
+// ---- Colour jitter (ofdg_jitter, include/ofdg.h) ---------------------------------------------------------------------------
+// Two launches on the caller's stream, behind the clearing of `work` where a record may hold a contrast: jitter_mean_kernel
+// adds the luminance sums of the frames whose contrast needs a mean, jitter_apply_kernel runs the four operations.  The second
+// launch starts after the first has ended - the order of the stream -, so no pixel is written before its frame's sum is
+// complete (the in-place form reads the un-jittered frame in both launches), and no workgroup waits for another.  A
+// workgroup serves kJitterBlockPixels consecutive pixels of one (sample, frame), all three channels: a lane takes the same
+// piece of the B, G and R plane, reads the three whole, works on the bytes in registers and - in the second launch - writes the
+// three back, which is all the in-place form needs.  The record is read or drawn, and sanitised, on wave-uniform values once
+// per (workgroup, sample); the frame's five fields are pinned to scalar registers, so the switch over the operation at a place
+// of the order does not diverge, and an operation at its identity is stepped over.  The functions of the definition are the
+// host twin's (csrc/ofdg_device.h), so the result is the twin's byte for byte.  No scratch; 16 bytes of LDS in the reduction.
+constexpr int kJitterThreads = 256;
+#ifndef OFDG_JITTER_BLOCK_PIXELS
+#define OFDG_JITTER_BLOCK_PIXELS 8192
+#endif
+constexpr int kJitterBlockPixels = OFDG_JITTER_BLOCK_PIXELS;  // 24 workgroups per 512 x 384 frame: two rounds of 16-pixel pieces, eight of 4-pixel ones
+static_assert(kJitterBlockPixels % (kJitterThreads * 16) == 0 && (unsigned long long)kJitterBlockPixels * 255ull < (1ull << 32),
+              "whole rounds of pieces of either kind; a workgroup's luminance sum fits 32 bits");
+__device__ __forceinline__ DevJitterRec jitter_record(const DevJitterJob& job, int i) {
+  DevJitterRec r;
+  if (job.recs) r = job.recs[i];
+  else r = jitter_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
+  return jitter_sanitise(r);
+}
+__device__ __forceinline__ JitterFrame jitter_frame_uniform(const DevJitterRec& r, int f) {
+  const JitterFrame p = jitter_frame(r, f);
+  return JitterFrame{__builtin_amdgcn_readfirstlane(p.brightness), __builtin_amdgcn_readfirstlane(p.contrast), __builtin_amdgcn_readfirstlane(p.saturation),
+                     __builtin_amdgcn_readfirstlane(p.hue), __builtin_amdgcn_readfirstlane(p.order)};
+}
+// the bytes of kP consecutive elements from element `at` of one channel: uint8 as 4-byte words (the alignment asked of a
+// source), float32 as 16-byte ones through the index rule
+template <bool kU8, int kP>
+__device__ __forceinline__ void jitter_load_channel(const void* src, size_t at, int (&v)[kP]) {
+  if constexpr (kU8) {
+    const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + at);
+#pragma unroll
+    for (int q = 0; q < kP / 4; ++q) {
+      const uint32_t w = sp[q];
+      v[4 * q] = (int)(w & 255u); v[4 * q + 1] = (int)((w >> 8) & 255u); v[4 * q + 2] = (int)((w >> 16) & 255u); v[4 * q + 3] = (int)(w >> 24);
+    }
+  } else {
+    const float4* const sp = reinterpret_cast<const float4*>(static_cast<const float*>(src) + at);
+#pragma unroll
+    for (int q = 0; q < kP / 4; ++q) {
+      const float4 e = sp[q];
+      v[4 * q] = photo_index(e.x); v[4 * q + 1] = photo_index(e.y); v[4 * q + 2] = photo_index(e.z); v[4 * q + 3] = photo_index(e.w);
+    }
+  }
+}
+// one 16-byte piece of a destination channel: 16 bytes, or 4 times (float)byte
+template <bool kU8, int kP>
+__device__ __forceinline__ void jitter_store_channel(void* dst, size_t at, const int (&v)[kP]) {
+  crop_u32x4 o;
+  if constexpr (kU8) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = (uint32_t)v[4 * q] | ((uint32_t)v[4 * q + 1] << 8) | ((uint32_t)v[4 * q + 2] << 16) | ((uint32_t)v[4 * q + 3] << 24);
+    crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + at), o);
+  } else {
+    o = crop_u32x4{__float_as_uint((float)v[0]), __float_as_uint((float)v[1]), __float_as_uint((float)v[2]), __float_as_uint((float)v[3])};
+    crop_store(reinterpret_cast<crop_u32x4*>(static_cast<float*>(dst) + at), o);
+  }
+}
+// The operations at the places [0, places) of `ops` on kP pixels.  The place loop stays a loop, its switch is uniform; the
+// pixels of a case are unrolled, so the arrays are registers.
+template <int kP>
+__device__ __forceinline__ void jitter_run(uint32_t ops, int places, const JitterFrame& p, int mean, int (&B)[kP], int (&G)[kP], int (&R)[kP]) {
+#pragma unroll 1
+  for (int place = 0; place < places; ++place) {
+    switch (jitter_op_at(ops, place)) {
+      case kJitterBrightness:
+        if (p.brightness == kJitterOne) break;
+#pragma unroll
+        for (int q = 0; q < kP; ++q) { B[q] = jitter_mix(B[q], 0, p.brightness); G[q] = jitter_mix(G[q], 0, p.brightness); R[q] = jitter_mix(R[q], 0, p.brightness); }
+        break;
+      case kJitterContrast:
+        if (p.contrast == kJitterOne) break;
+#pragma unroll
+        for (int q = 0; q < kP; ++q) { B[q] = jitter_mix(B[q], mean, p.contrast); G[q] = jitter_mix(G[q], mean, p.contrast); R[q] = jitter_mix(R[q], mean, p.contrast); }
+        break;
+      case kJitterSaturation:
+        if (p.saturation == kJitterOne) break;
+#pragma unroll
+        for (int q = 0; q < kP; ++q) {
+          const int l = jitter_lum(B[q], G[q], R[q]);
+          B[q] = jitter_mix(B[q], l, p.saturation); G[q] = jitter_mix(G[q], l, p.saturation); R[q] = jitter_mix(R[q], l, p.saturation);
+        }
+        break;
+      default:
+        if (p.hue == 0) break;
+#pragma unroll
+        for (int q = 0; q < kP; ++q) jitter_hue(B[q], G[q], R[q], p.hue);
+        break;
+    }
+  }
+}
+
+// The mean's reduction.  blockIdx.x counts the kJitterBlockPixels-pixel blocks of the frames that are set, blockIdx.y the
+// samples.  A workgroup whose (sample, frame) has no contrast leaves before any load.  A lane reads pieces of the source - 16
+// bytes of float32, four 4-byte words of uint8 - of all three channels, runs the operations that stand before the contrast,
+// sums the luminances in 32 bits (at most 32 pixels of 255), the wave adds across with __shfl_xor, the workgroup through LDS,
+// and one 64-bit integer atomicAdd per workgroup goes to the frame's sum in `work`.  Integers only: no bit depends on arrival
+// order.
+template <bool kU8>
+__global__ __launch_bounds__(kJitterThreads) void jitter_mean_kernel(const DevJitterJob job, int n, int W, int H, uint32_t per_frame) {
+  constexpr int kP = kU8 ? 16 : 4;  // pixels of a piece
+  __shared__ uint32_t s_part[kJitterThreads / 64];
+  const uint32_t slot = blockIdx.x / per_frame, block = blockIdx.x - slot * per_frame;
+  const int f = (int)slot + (job.src[0] ? 0 : 1);
+  const void* const src = f ? job.src[1] : job.src[0];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: jitter_arg_error)
+  const uint32_t first = block * (uint32_t)kJitterBlockPixels;
+  const uint32_t end = first + (uint32_t)kJitterBlockPixels < plane ? first + (uint32_t)kJitterBlockPixels : plane;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const DevJitterRec r = jitter_record(job, i);
+    const JitterFrame p = jitter_frame_uniform(r, f);
+    if (p.contrast == kJitterOne) continue;  // (uniform over the workgroup)
+    const uint32_t ops = jitter_ops(p.order);
+    const int places = jitter_contrast_place(ops);
+    const size_t base = (size_t)i * 3 * plane;
+    uint32_t sum = 0;
+    for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kJitterThreads * kP)) {
+      int B[kP], G[kP], R[kP];
+      jitter_load_channel<kU8, kP>(src, base + at, B);
+      jitter_load_channel<kU8, kP>(src, base + plane + at, G);
+      jitter_load_channel<kU8, kP>(src, base + 2 * (size_t)plane + at, R);
+      jitter_run<kP>(ops, places, p, 0, B, G, R);
+#pragma unroll
+      for (int q = 0; q < kP; ++q) sum += (uint32_t)jitter_lum(B[q], G[q], R[q]);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
+    if (lane == 0) s_part[wave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+#pragma unroll
+      for (int w = 0; w < kJitterThreads / 64; ++w) total += s_part[w];
+      atomicAdd(f ? &job.work[i].sum[1] : &job.work[i].sum[0], total);
+    }
+    __syncthreads();  // (the next sample of this workgroup writes the parts again)
+  }
+}
+
+// The byte the contrast of frame f of sample i pivots on, from the sums the first launch left in `work`; -1 for an absent
+// frame and for one without a contrast (`work` is not read then: it may be NULL where no record can hold a contrast).
+__device__ __forceinline__ int jitter_mean_of(const DevJitterJob& job, const DevJitterRec& r, int i, int f, uint32_t plane) {
+  if (!(f ? job.src[1] : job.src[0]) || (f ? r.contrast[1] : r.contrast[0]) == kJitterOne) return -1;
+  const bool joint = r.shared && job.src[0] && job.src[1];
+  const unsigned long long s0 = job.work[i].sum[0], s1 = job.work[i].sum[1];
+  return jitter_mean_byte(joint ? s0 + s1 : f ? s1 : s0, joint ? 2ull * plane : (unsigned long long)plane);
+}
+
+// The operations.  The grid is jitter_mean_kernel's; a piece is what one 16-byte store holds of the destination - 4 float32 or
+// 16 uint8 -, lane t takes the pieces t, t + 256, ... of the block, so a wave's store instruction writes 1 KiB of consecutive
+// bytes per channel.  A frame at the identity is copied bit for bit where the formats agree - and left alone in place -, and
+// goes through its bytes where they differ.  Workgroup 0 of a sample writes the sanitised record with both means from lane 0
+// with four vector stores.
+template <bool kSrcU8, bool kDstU8>
+__global__ __launch_bounds__(kJitterThreads) void jitter_apply_kernel(const DevJitterJob job, int n, int W, int H, uint32_t per_frame) {
+  constexpr int kP = kDstU8 ? 16 : 4;  // pixels of a piece
+  const uint32_t slot = blockIdx.x / per_frame, block = blockIdx.x - slot * per_frame;
+  const int f = (int)slot + (job.src[0] ? 0 : 1);
+  const void* const src = f ? job.src[1] : job.src[0];
+  void* const dst = f ? job.dst[1] : job.dst[0];
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: jitter_arg_error)
+  const uint32_t first = block * (uint32_t)kJitterBlockPixels;
+  const uint32_t end = first + (uint32_t)kJitterBlockPixels < plane ? first + (uint32_t)kJitterBlockPixels : plane;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const DevJitterRec r = jitter_record(job, i);
+    if (job.recs_out && blockIdx.x == 0u && threadIdx.x == 0u) {
+      const int m0 = jitter_mean_of(job, r, i, 0, plane), m1 = jitter_mean_of(job, r, i, 1, plane);
+      crop_u32x4* const o = reinterpret_cast<crop_u32x4*>(job.recs_out + i);
+      o[0] = crop_u32x4{(uint32_t)r.brightness[0], (uint32_t)r.brightness[1], (uint32_t)r.contrast[0], (uint32_t)r.contrast[1]};
+      o[1] = crop_u32x4{(uint32_t)r.saturation[0], (uint32_t)r.saturation[1], (uint32_t)r.hue[0], (uint32_t)r.hue[1]};
+      o[2] = crop_u32x4{(uint32_t)r.order[0], (uint32_t)r.order[1], (uint32_t)r.shared, (uint32_t)m0};
+      o[3] = crop_u32x4{(uint32_t)m1, 0u, 0u, 0u};
+    }
+    const JitterFrame p = jitter_frame_uniform(r, f);
+    const size_t base = (size_t)i * 3 * plane;
+    if (jitter_identity(p)) {  // (uniform over the workgroup)
+      if constexpr (kSrcU8 == kDstU8) {
+        if (src == dst) continue;
+        constexpr int kB = kSrcU8 ? 1 : 4;
+        for (int c = 0; c < 3; ++c)
+          for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kJitterThreads * kP)) {
+            const size_t e = (base + (size_t)c * plane + at) * kB;
+            const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + e);
+            crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + e), crop_u32x4{sp[0], sp[1], sp[2], sp[3]});
+          }
+        continue;
+      }
+    }
+    const int mean = __builtin_amdgcn_readfirstlane(jitter_mean_of(job, r, i, f, plane));
+    const uint32_t ops = jitter_ops(p.order);
+    for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kJitterThreads * kP)) {
+      int B[kP], G[kP], R[kP];
+      jitter_load_channel<kSrcU8, kP>(src, base + at, B);
+      jitter_load_channel<kSrcU8, kP>(src, base + plane + at, G);
+      jitter_load_channel<kSrcU8, kP>(src, base + 2 * (size_t)plane + at, R);
+      jitter_run<kP>(ops, 4, p, mean, B, G, R);
+      jitter_store_channel<kDstU8, kP>(dst, base + at, B);
+      jitter_store_channel<kDstU8, kP>(dst, base + plane + at, G);
+      jitter_store_channel<kDstU8, kP>(dst, base + 2 * (size_t)plane + at, R);
+    }
+  }
+}
+
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
 // One launch for both frames and every sample: blockIdx.x counts the kMblurTileW x kMblurTileH tiles of a frame, blockIdx.y
 // the samples, blockIdx.z the frames that are set.  A 4-wave workgroup owns a tile, a lane four consecutive pixels of one row

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_motion_blur, ofdg_reproject, ofdg_splat
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -292,7 +292,7 @@ struct PostOp {
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
-// 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel.
+// 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1875,6 +1875,46 @@ int ofdg_erase(ofdg_ctx* c, const struct ofdg_erase_job* job, int n_samples, voi
         hipLaunchKernelGGL((erase_apply_kernel<decltype(image_u8)::value, decltype(occ_u8)::value, decltype(half)::value>), g, dim3(kEraseThreads), 0, st,
                            *j, n_samples, W, H, occ_blocks);
       });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Colour jitter of caller-given frames: where a record may hold a contrast the clearing of `work` and the reduction, then one
+// kernel for both frames and every sample, all on `stream`.
+int ofdg_jitter(ofdg_ctx* c, const struct ofdg_jitter_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_jitter"};
+  const DevJitterJob* const j = reinterpret_cast<const DevJitterJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = jitter_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = jitter_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const bool mean = jitter_needs_work(*j);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  if (mean && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const uint32_t per_frame = (plane + kJitterBlockPixels - 1) / kJitterBlockPixels;
+  const dim3 g(per_frame * ((j->src[0] ? 1u : 0u) + (j->src[1] ? 1u : 0u)), (unsigned)std::min(n_samples, 65535));
+  if (mean) {
+    HIP_OK(c, hipMemsetAsync(j->work, 0, sizeof(DevJitterWork) * (size_t)n_samples, st));
+    with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+      hipLaunchKernelGGL((jitter_mean_kernel<decltype(src_u8)::value>), g, dim3(kJitterThreads), 0, st, *j, n_samples, W, H, per_frame);
+    });
+    HIP_OK(c, hipGetLastError());
+  }
+  with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
+      hipLaunchKernelGGL((jitter_apply_kernel<decltype(src_u8)::value, decltype(dst_u8)::value>), g, dim3(kJitterThreads), 0, st, *j, n_samples, W, H, per_frame);
     });
   });
   HIP_OK(c, hipGetLastError());

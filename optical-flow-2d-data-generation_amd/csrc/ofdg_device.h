@@ -1164,6 +1164,220 @@ inline const char* erase_arg_error(const DevEraseJob* j, int n, int width, int h
   return nullptr;
 }
 
+// ---- Colour jitter (ofdg_jitter, include/ofdg.h) ---------------------------------------------------------------------------
+// What the device entry, the kernels and the host twin share: the job as the kernels take it, the record's draw and its
+// sanitising, the order's decoding, the four operations on the bytes of a pixel, the mean and the argument rules.  Integers
+// throughout; >> of a negative int is the arithmetic shift on every compiler this builds with.
+struct DevJitterRec {  // ofdg_jitter_rec, field for field
+  int32_t brightness[2], contrast[2], saturation[2], hue[2], order[2], shared, mean[2], reserved[3];
+};
+struct DevJitterWork {  // one sample's part of job->work: the luminance sums of the frames whose contrast needs a mean
+  unsigned long long sum[2];
+};
+struct DevJitterJob {  // struct ofdg_jitter_job, field for field
+  const void* src[2];
+  void* dst[2];
+  const DevJitterRec* recs;
+  DevJitterRec* recs_out;
+  DevJitterWork* work;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, src_fmt, dst_fmt, flags, reserved;
+  float brightness, contrast, saturation, hue, asym_prob;
+};
+static_assert(sizeof(ofdg_jitter_rec) == sizeof(DevJitterRec) && sizeof(DevJitterRec) == 64 && offsetof(ofdg_jitter_rec, hue) == offsetof(DevJitterRec, hue) &&
+              offsetof(DevJitterRec, hue) == 24 && offsetof(ofdg_jitter_rec, order) == offsetof(DevJitterRec, order) && offsetof(ofdg_jitter_rec, shared) == offsetof(DevJitterRec, shared) &&
+              offsetof(DevJitterRec, shared) == 40 && offsetof(ofdg_jitter_rec, mean) == offsetof(DevJitterRec, mean) && offsetof(ofdg_jitter_rec, reserved) == offsetof(DevJitterRec, reserved) &&
+              offsetof(DevJitterRec, reserved) == 52 && sizeof(DevJitterWork) == OFDG_JITTER_WORK_BYTES,
+              "ofdg_jitter_rec: 64 bytes, the layout the kernels read and write as four 16-byte pieces; a sample's workspace");
+static_assert(sizeof(struct ofdg_jitter_job) == sizeof(DevJitterJob) && sizeof(DevJitterJob) == 112 && offsetof(struct ofdg_jitter_job, dst) == offsetof(DevJitterJob, dst) &&
+              offsetof(struct ofdg_jitter_job, recs) == offsetof(DevJitterJob, recs) && offsetof(struct ofdg_jitter_job, recs_out) == offsetof(DevJitterJob, recs_out) &&
+              offsetof(struct ofdg_jitter_job, work) == offsetof(DevJitterJob, work) && offsetof(struct ofdg_jitter_job, first_index) == offsetof(DevJitterJob, first_index) &&
+              offsetof(struct ofdg_jitter_job, seed) == offsetof(DevJitterJob, seed) && offsetof(DevJitterJob, seed) == 64 && offsetof(struct ofdg_jitter_job, width) == offsetof(DevJitterJob, width) &&
+              offsetof(struct ofdg_jitter_job, src_fmt) == offsetof(DevJitterJob, src_fmt) && offsetof(struct ofdg_jitter_job, reserved) == offsetof(DevJitterJob, reserved) &&
+              offsetof(struct ofdg_jitter_job, brightness) == offsetof(DevJitterJob, brightness) && offsetof(DevJitterJob, brightness) == 92 &&
+              offsetof(struct ofdg_jitter_job, asym_prob) == offsetof(DevJitterJob, asym_prob) && offsetof(DevJitterJob, asym_prob) == 108,
+              "struct ofdg_jitter_job: 112 bytes, the layout the kernels take");
+constexpr int kJitterOne = 65536;      // a Q16 factor that changes nothing; the hue units of one sector
+constexpr int kJitterTurn = 393216;    // the hue units of a whole turn
+enum { kJitterBrightness = 0, kJitterContrast = 1, kJitterSaturation = 2, kJitterHue = 3 };  // the operations as order[f] permutes them
+// The five fields of one frame of a record (by value: a conditional between members would select their addresses).
+struct JitterFrame {
+  int32_t brightness, contrast, saturation, hue, order;
+};
+OFDG_HD_FN JitterFrame jitter_frame(const DevJitterRec& r, int f) {
+  return JitterFrame{f ? r.brightness[1] : r.brightness[0], f ? r.contrast[1] : r.contrast[0], f ? r.saturation[1] : r.saturation[0], f ? r.hue[1] : r.hue[0],
+                     f ? r.order[1] : r.order[0]};
+}
+OFDG_HD_FN bool jitter_same(const JitterFrame& a, const JitterFrame& b) {
+  return a.brightness == b.brightness && a.contrast == b.contrast && a.saturation == b.saturation && a.hue == b.hue && a.order == b.order;
+}
+// does nothing to any pixel: the frame is copied
+OFDG_HD_FN bool jitter_identity(const JitterFrame& p) { return p.brightness == kJitterOne && p.contrast == kJitterOne && p.saturation == kJitterOne && p.hue == 0; }
+// A = lrintf(range * unit), to nearest even; isym(w, A) uniform on [-A, A] by the multiply-shift of the crop's draw
+OFDG_HD_FN int32_t jitter_amp(float range, float unit) { return (int32_t)lrintf(range * unit); }
+OFDG_HD_FN int32_t jitter_isym(uint32_t w, int32_t A) { return (int32_t)(uint32_t)(((unsigned long long)w * (uint32_t)(2 * A + 1)) >> 32) - A; }
+// The record of global sample g: Philox blocks 0, 1, 2 under the sampler's key of g and the counters {j, 0, 0x0c78, 0}.  `j`
+// supplies the five ranges (jitter_ranges_error has passed).  Not sanitised.
+OFDG_HD_FN DevJitterRec jitter_draw_rec(uint32_t seed, unsigned long long g, const DevJitterJob& j) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords a = crop_philox(CropWords{0u, 0u, 0x0c78u, 0u}, k0, k1);
+  const CropWords b = crop_philox(CropWords{1u, 0u, 0x0c78u, 0u}, k0, k1);
+  const CropWords d = crop_philox(CropWords{2u, 0u, 0x0c78u, 0u}, k0, k1);
+  const int32_t Ab = jitter_amp(j.brightness, 65536.0f), Ac = jitter_amp(j.contrast, 65536.0f), As = jitter_amp(j.saturation, 65536.0f);
+  const int32_t Ah = jitter_amp(j.hue, 393216.0f);
+  const bool asym = photo_unit(d.x) < j.asym_prob;
+  DevJitterRec r;
+  r.brightness[0] = kJitterOne + jitter_isym(a.x, Ab); r.contrast[0] = kJitterOne + jitter_isym(a.y, Ac);
+  r.saturation[0] = kJitterOne + jitter_isym(a.z, As); r.hue[0] = jitter_isym(a.w, Ah);
+  r.order[0] = (int32_t)(((d.y >> 8) * 24u) >> 24);
+  r.brightness[1] = asym ? kJitterOne + jitter_isym(b.x, Ab) : r.brightness[0]; r.contrast[1] = asym ? kJitterOne + jitter_isym(b.y, Ac) : r.contrast[0];
+  r.saturation[1] = asym ? kJitterOne + jitter_isym(b.z, As) : r.saturation[0]; r.hue[1] = asym ? jitter_isym(b.w, Ah) : r.hue[0];
+  r.order[1] = asym ? (int32_t)(((d.z >> 8) * 24u) >> 24) : r.order[0];
+  r.shared = asym ? 0 : 1;
+  r.mean[0] = -1; r.mean[1] = -1;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+OFDG_HD_FN int32_t jitter_clamp(int32_t x, int32_t lo, int32_t hi) { return x < lo ? lo : x > hi ? hi : x; }
+// What is used of a record, given or drawn.  No record makes a kernel touch a byte outside a plane.
+OFDG_HD_FN DevJitterRec jitter_sanitise(DevJitterRec r) {
+  for (int f = 0; f < 2; ++f) {
+    r.brightness[f] = jitter_clamp(r.brightness[f], 0, 4 * kJitterOne);
+    r.contrast[f] = jitter_clamp(r.contrast[f], 0, 4 * kJitterOne);
+    r.saturation[f] = jitter_clamp(r.saturation[f], 0, 4 * kJitterOne);
+    r.hue[f] = jitter_clamp(r.hue[f], -kJitterTurn / 2, kJitterTurn / 2);
+    r.order[f] = jitter_clamp(r.order[f], 0, 23);
+    r.mean[f] = -1;
+  }
+  r.shared = (r.shared != 0 && jitter_same(jitter_frame(r, 0), jitter_frame(r, 1))) ? 1 : 0;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+// The permutation number `order` names, as four nibbles: the operation at place p is (ops >> 4 p) & 15.  The factorial
+// digits of order pick, place by place, among the operations still left (kept as nibbles too, in rising order).
+OFDG_HD_FN uint32_t jitter_pop(uint32_t* left, int i) {
+  const uint32_t sh = 4u * (uint32_t)i, v = (*left >> sh) & 15u;
+  *left = (*left & ((1u << sh) - 1u)) | ((*left >> (sh + 4u)) << sh);
+  return v;
+}
+OFDG_HD_FN uint32_t jitter_ops(int order) {
+  const int i0 = order / 6, rest = order - 6 * i0, i1 = rest / 2, i2 = rest - 2 * i1;
+  uint32_t left = 0x3210u;
+  const uint32_t o0 = jitter_pop(&left, i0), o1 = jitter_pop(&left, i1), o2 = jitter_pop(&left, i2);
+  return o0 | (o1 << 4) | (o2 << 8) | ((left & 15u) << 12);
+}
+OFDG_HD_FN int jitter_op_at(uint32_t ops, int place) { return (int)((ops >> (4 * place)) & 15u); }
+// the place of the contrast: the operations in front of it shape the image its mean is taken of
+OFDG_HD_FN int jitter_contrast_place(uint32_t ops) {
+  return jitter_op_at(ops, 0) == kJitterContrast ? 0 : jitter_op_at(ops, 1) == kJitterContrast ? 1 : jitter_op_at(ops, 2) == kJitterContrast ? 2 : 3;
+}
+OFDG_HD_FN int jitter_lum(int B, int G, int R) { return (7471 * B + 38470 * G + 19595 * R + 32768) >> 16; }
+OFDG_HD_FN int jitter_mix(int a, int m, int q) {
+  const int v = (q * a + (kJitterOne - q) * m + 32768) >> 16;
+  return v < 0 ? 0 : v > 255 ? 255 : v;
+}
+// floor(num / d) for 0 <= num < 2^24 and 1 <= d <= 255, exact.  On the device: the product with the hardware's reciprocal
+// (off by less than 2^-6 here, so its integer part is the quotient or a neighbour) and one correction step either way,
+// measured against the compiler's integer division (CHANGELOG; tools/patches/jitter_integer_division.patch).
+OFDG_HD_FN int jitter_div(int num, int d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int q = (int)((float)num * __builtin_amdgcn_rcpf((float)d));
+  const int r = num - q * d;
+  return q + (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
+#else
+  return num / d;
+#endif
+}
+// The hue shift of one pixel.  A grey pixel (d = 0) falls out unchanged: t = 0 and every channel becomes mn + 0.
+OFDG_HD_FN void jitter_hue(int& B, int& G, int& R, int hue) {
+  const int mx = R > G ? (R > B ? R : B) : (G > B ? G : B), mn = R < G ? (R < B ? R : B) : (G < B ? G : B), d = mx - mn;
+  const int s = (R == mx && B == mn) ? 0 : (G == mx && B == mn) ? 1 : (G == mx && R == mn) ? 2 : (B == mx && R == mn) ? 3 : (B == mx && G == mn) ? 4 : 5;
+  const int mid = (s == 0 || s == 3) ? G : (s == 1 || s == 4) ? R : B;
+  const int t = (s & 1) ? d - (mid - mn) : mid - mn;
+  int hq = kJitterOne * s + jitter_div(kJitterOne * t, d > 0 ? d : 1) + hue;  // within a turn of [0, kJitterTurn) for any hue in [-kJitterTurn, kJitterTurn]
+  hq += hq < 0 ? kJitterTurn : 0;
+  hq -= hq >= kJitterTurn ? kJitterTurn : 0;
+  const int s2 = hq >> 16, f2 = hq & 65535;
+  const int nm = mn + ((d * ((s2 & 1) ? kJitterOne - f2 : f2) + 32768) >> 16);
+  R = (s2 == 0 || s2 == 5) ? mx : (s2 == 2 || s2 == 3) ? mn : nm;
+  G = (s2 == 1 || s2 == 2) ? mx : (s2 == 4 || s2 == 5) ? mn : nm;
+  B = (s2 == 3 || s2 == 4) ? mx : (s2 == 0 || s2 == 1) ? mn : nm;
+}
+// One operation on one pixel; `mean` is looked at by the contrast only.
+OFDG_HD_FN void jitter_op(int op, const JitterFrame& p, int mean, int& B, int& G, int& R) {
+  if (op == kJitterBrightness) {
+    B = jitter_mix(B, 0, p.brightness); G = jitter_mix(G, 0, p.brightness); R = jitter_mix(R, 0, p.brightness);
+  } else if (op == kJitterContrast) {
+    B = jitter_mix(B, mean, p.contrast); G = jitter_mix(G, mean, p.contrast); R = jitter_mix(R, mean, p.contrast);
+  } else if (op == kJitterSaturation) {
+    const int l = jitter_lum(B, G, R);
+    B = jitter_mix(B, l, p.saturation); G = jitter_mix(G, l, p.saturation); R = jitter_mix(R, l, p.saturation);
+  } else {
+    jitter_hue(B, G, R, p.hue);
+  }
+}
+// (2 S + N) / (2 N): the mean of N luminances, to nearest, a tie upwards
+OFDG_HD_FN int32_t jitter_mean_byte(unsigned long long S, unsigned long long N) { return (int32_t)((2ull * S + N) / (2ull * N)); }
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* jitter_plane_size(const DevJitterJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The five ranges of the draw: the first that is negative, NaN, infinite or above its bound, or nullptr.
+inline const char* jitter_ranges_error(const DevJitterJob& j) {
+  if (!(j.brightness >= 0.0f && j.brightness <= 3.0f)) return "brightness must lie in [0, 3]";
+  if (!(j.contrast >= 0.0f && j.contrast <= 3.0f)) return "contrast must lie in [0, 3]";
+  if (!(j.saturation >= 0.0f && j.saturation <= 3.0f)) return "saturation must lie in [0, 3]";
+  if (!(j.hue >= 0.0f && j.hue <= 0.5f)) return "hue must lie in [0, 0.5]";
+  if (!(j.asym_prob >= 0.0f && j.asym_prob <= 1.0f)) return "asym_prob must lie in [0, 1]";
+  return nullptr;
+}
+// Can a record of this job have a contrast, so that the device entry needs `work`?  Given records are not looked at on the
+// host: they always can.
+inline bool jitter_needs_work(const DevJitterJob& j) { return j.recs || jitter_amp(j.contrast, 65536.0f) != 0; }
+// The argument rules ofdg_jitter and ofdg_host_jitter share: the first rule broken, or nullptr.  width, height: what
+// jitter_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+inline const char* jitter_arg_error(const DevJitterJob* j, int n, int width, int height, bool with_work) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags != 0) return "flags must be 0";
+  if (j->reserved != 0) return "reserved must be 0";
+  if (const char* why = jitter_ranges_error(*j)) return why;
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
+    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
+    frames += j->src[f] ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  const bool work = with_work && jitter_needs_work(*j);
+  if (work && !j->work) return "work is NULL where a record may hold a contrast";
+  // a written range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
+  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
+  Range r[7];
+  int nr = 0;
+  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
+    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
+    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
+    nr += 2;
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevJitterRec), false, -1};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevJitterRec), true, -1};
+  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(DevJitterWork), true, -1};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
 // sanitising, the half-displacement, the tap count and step, the tap value, the mean and the argument rules.  Compiled

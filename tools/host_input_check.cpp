@@ -20,6 +20,9 @@
 //   host_input_check splat              ofdg_host_splat and ofdg_splat_draw on exactly sized heap buffers: every format, every
 //                                       presence subset of the outputs and of the frames, with and without labels and maps,
 //                                       extreme flows and frames, given and drawn records, every refusal
+//   host_input_check jitter             ofdg_host_jitter, ofdg_jitter_draw and ofdg_host_jitter_hue on exactly sized heap buffers:
+//                                       every format pair, copying and in place, one frame and both, odd sizes, hostile given
+//                                       records and drawn ones, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -634,13 +637,140 @@ int splat() {
 }
 }  // namespace
 
+// ofdg_host_jitter, ofdg_jitter_draw and ofdg_host_jitter_hue on heap buffers of exactly the planes' sizes (a byte read or
+// written beside one is a report): the four format pairs, copying and - where the formats agree - in place, frame 0, frame 1
+// and both, given records whose every field sits at and beyond the ends of int32 (a signed overflow in the clamps, the mix or
+// the hue's modulus is a report), every order with every operation away from its identity, and drawn records at the widest
+// ranges, on 8x2, 24x6 and 72x40; float32 frames with NaN, 1e9 and halves; the hue alone at both ends of its range; then every
+// refusal.
+int jitter() {
+  const int32_t hostile[] = {INT32_MIN, INT32_MIN + 1, -393217, -196609, -65537, -1, 0, 1, 65535, 65536, 65537, 196608, 196609, 262144, 262145, 393216, INT32_MAX - 1, INT32_MAX};
+  const int n_hostile = (int)(sizeof hostile / sizeof hostile[0]);
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 3; ++size) {
+    const int W = size == 0 ? 8 : size == 1 ? 24 : 72, H = size == 0 ? 2 : size == 1 ? 6 : 40, n = 28;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 4; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4);
+      std::vector<uint8_t> src[2], dst[2];
+      uint32_t x = 777u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        src[f].resize(sb); dst[f].assign(db, 0xA5);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          const float v = (e % 11) == 0 ? (e % 22 ? NAN : 1e9f) : (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          if (sf == OFDG_FMT_U8) src[f][e] = (e % 7) == 0 ? (uint8_t)(e % 3 ? 255 : 0) : (uint8_t)(x >> 24);
+          else std::memcpy(src[f].data() + 4 * e, &v, 4);
+        }
+      }
+      // records 0..23: every order, everything away from the identity; 24..27: every field walks the hostile values
+      std::vector<ofdg_jitter_rec> recs(n), used(n);
+      for (int i = 0; i < n; ++i) {
+        ofdg_jitter_rec& r = recs[i];
+        std::memset(&r, 0x5A, sizeof r);
+        for (int f = 0; f < 2; ++f) {
+          if (i < 24) { r.brightness[f] = 75000; r.contrast[f] = 110000 - 90000 * f * (i & 1); r.saturation[f] = 20000; r.hue[f] = 40000 - 99999 * f; r.order[f] = i; }
+          else {
+            const int k = (i - 24) * 5 + f * 2 + fmts + size;
+            r.brightness[f] = hostile[k % n_hostile]; r.contrast[f] = hostile[(k + 5) % n_hostile]; r.saturation[f] = hostile[(k + 9) % n_hostile];
+            r.hue[f] = hostile[(k + 13) % n_hostile]; r.order[f] = hostile[(k + 3) % n_hostile];
+          }
+        }
+        r.shared = hostile[i % n_hostile];
+      }
+      for (int drawn = 0; drawn < 2; ++drawn)
+        for (int frames = 1; frames < 4; ++frames)
+          for (int in_place = 0; in_place < (sf == df ? 2 : 1); ++in_place) {
+            std::vector<uint8_t> own[2] = {src[0], src[1]};  // (the in-place form writes its sources)
+            struct ofdg_jitter_job job;
+            std::memset(&job, 0, sizeof job);
+            for (int f = 0; f < 2; ++f)
+              if ((frames >> f) & 1) { job.src[f] = own[f].data(); job.dst[f] = in_place ? own[f].data() : dst[f].data(); }
+            job.recs = drawn ? nullptr : recs.data();
+            job.recs_out = used.data();
+            job.first_index = (1ll << 32) - 1; job.seed = 7;
+            job.src_fmt = sf; job.dst_fmt = df;
+            job.brightness = 3.0f; job.contrast = 3.0f; job.saturation = 3.0f; job.hue = 0.5f; job.asym_prob = 0.5f;
+            const int rc = ofdg_host_jitter(&job, n, W, H);
+            if (rc) { std::printf("jitter: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+            ++calls;
+            for (int f = 0; f < 2; ++f)
+              if ((frames >> f) & 1) sum = sum * 31 + (in_place ? fnv1a(own[f].data(), own[f].size()) : fnv1a(dst[f].data(), dst[f].size()));
+            sum = sum * 31 + fnv1a((const uint8_t*)used.data(), used.size() * sizeof(ofdg_jitter_rec));
+            for (int i = 0; i < n; ++i)
+              for (int f = 0; f < 2; ++f)
+                if (used[i].brightness[f] < 0 || used[i].brightness[f] > 262144 || used[i].hue[f] < -196608 || used[i].hue[f] > 196608 || used[i].order[f] < 0 ||
+                    used[i].order[f] > 23 || used[i].mean[f] < -1 || used[i].mean[f] > 255 || used[i].reserved[f] != 0) { std::printf("jitter: a record left its bounds\n"); return 1; }
+          }
+    }
+  }
+  {  // the hue alone, at both ends of its range and in the middle, in place, on a buffer of exactly 3 * 333 bytes
+    std::vector<uint8_t> bgr(3 * 333);
+    for (size_t e = 0; e < bgr.size(); ++e) bgr[e] = (uint8_t)(e * 37u + (e >> 3));
+    for (const int hue : {-393216, -196608, -1, 0, 1, 131072, 393216}) {
+      if (ofdg_host_jitter_hue(bgr.data(), bgr.data(), 333, hue) != OFDG_OK) { std::printf("jitter: the hue call failed\n"); return 1; }
+      ++calls;
+      sum = sum * 31 + fnv1a(bgr.data(), bgr.size());
+    }
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> src((size_t)n * 3 * W * H * 4, 0), dst((size_t)n * 3 * W * H * 4 + 64, 0xA5), out((size_t)n * 64, 0xA5);
+    struct ofdg_jitter_job good;
+    std::memset(&good, 0, sizeof good);
+    good.src[0] = src.data(); good.dst[0] = dst.data(); good.recs_out = (ofdg_jitter_rec*)out.data();
+    good.brightness = 0.4f; good.contrast = 0.4f; good.saturation = 0.4f; good.hue = 0.16f; good.asym_prob = 0.2f;
+    const auto refuse = [&](struct ofdg_jitter_job j, int ns, int w, int h) {
+      if (ofdg_host_jitter(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_jitter: ", 18) == 0) ++refused;
+      else std::printf("jitter: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_jitter_job j;
+    if (ofdg_host_jitter(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.width = W + 8; j.height = H; refuse(j, n, W, H);
+    j = good; j.src_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flags = 1; refuse(j, n, W, H);
+    j = good; j.reserved = 1; refuse(j, n, W, H);
+    j = good; j.brightness = NAN; refuse(j, n, W, H);
+    j = good; j.contrast = -0.5f; refuse(j, n, W, H);
+    j = good; j.saturation = 3.5f; refuse(j, n, W, H);
+    j = good; j.hue = 0.51f; refuse(j, n, W, H);
+    j = good; j.asym_prob = INFINITY; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[1] = nullptr; j.dst[1] = dst.data(); j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data() + 16; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data(); j.dst_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.recs_out = (ofdg_jitter_rec*)(dst.data() + 16); refuse(j, n, W, H);
+    ofdg_jitter_rec rec;
+    std::memset(&rec, 0xA5, sizeof rec);
+    j = good; j.hue = 2.0f;
+    if (ofdg_jitter_draw(1, 0, &j, &rec) == OFDG_EINVAL && ofdg_jitter_draw(1, 0, nullptr, &rec) == OFDG_EINVAL && ofdg_jitter_draw(1, 0, &good, nullptr) == OFDG_EINVAL) ++refused;
+    if (ofdg_host_jitter_hue(nullptr, dst.data(), 4, 0) == OFDG_EINVAL && ofdg_host_jitter_hue(src.data(), nullptr, 4, 0) == OFDG_EINVAL &&
+        ofdg_host_jitter_hue(src.data(), dst.data(), 4, 393217) == OFDG_EINVAL && ofdg_host_jitter_hue(src.data(), dst.data(), 4, INT32_MIN) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; }) &&
+                       ((const uint8_t*)&rec)[0] == 0xA5 && ((const uint8_t*)&rec)[63] == 0xA5;
+    if (!clean) { std::printf("jitter: a refusal wrote something\n"); return 1; }
+    if (ofdg_jitter_draw(1, (1ll << 32) + 3, &good, &rec) != OFDG_OK || ofdg_host_jitter(&good, n, W, H) != OFDG_OK) { std::printf("jitter: the valid call failed\n"); return 1; }
+  }
+  std::printf("jitter calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 24 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
   if (argc >= 2 && std::strcmp(argv[1], "reproject") == 0) return reproject();
   if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
+  if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter\n", argv[0]);
   return 2;
 }
