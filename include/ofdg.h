@@ -1112,6 +1112,91 @@ int ofdg_jitter_draw(uint32_t seed, long long index, const struct ofdg_jitter_jo
 int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hue);
 
 /*
+ * Flow visualisation: the Middlebury colour wheel (Baker et al., "A Database and Evaluation Methodology for Optical Flow") of
+ * any [n,2,height,width] flow tensor - the forward flow, flow1, a cropped, warped or splat flow, a residual - as a uint8
+ * picture: the direction is the hue, the length the saturation, zero flow white.  Behind the producing call on the same
+ * stream, so that a ready picture and no float plane goes to an image writer.  Everything below is integers behind one
+ * rounding of each flow component: the kernels, ofdg_host_flow_vis and the numpy restatement of the tests give the same bytes.
+ * >> is the arithmetic shift; divisions are floored, on non-negative operands.
+ *
+ * flow: [n,2,height,width] of flow_fmt, OFDG_FMT_F32 (16-byte aligned) or OFDG_FMT_F16 (8-byte).  occ: NULL, or the
+ * [n,1,height,width] map of occ_fmt that goes with it, OFDG_FMT_U8 (4-byte) or OFDG_FMT_F32 (16-byte), as in ofdg_flow_stats;
+ * read only under OFDG_VIS_DIM_OCC.  dst: 16-byte aligned, [n,3,height,width] (OFDG_VIS_PLANAR_BGR) or [n,height,width,3]
+ * (OFDG_VIS_HWC_RGB).  width = height = 0: the context's frame; otherwise width a multiple of 8 and at least 8, height even
+ * and at least 2.
+ *
+ * 1. Usable.  u, v are widened to float32.  The pixel is usable when fabsf(u) < 1048576.0f && fabsf(v) < 1048576.0f (rule 2
+ *    of ofdg_flow_stats).  An unusable pixel is written as (0, 0, 0) and takes no part in any maximum.
+ * 2. Fixed point.  U = (int)rintf(u * 256.0f), V likewise (to nearest even; |U| <= 2^28).  R2 = U U + V V in 64 bits.
+ *    Rq = isqrt(R2) (floor).
+ * 3. Scale M (Q8 pixels).  OFDG_VIS_NORM_FIXED: M = (int)lrintf(max_flow * 256.0f).  OFDG_VIS_NORM_SAMPLE: M = max(1,
+ *    isqrt(the largest R2 of the sample's usable pixels)), occluded ones included.  OFDG_VIS_NORM_BATCH: the same over all
+ *    n_samples.  rows_out[i] = { that largest R2 (0 under FIXED: none is taken), M, 0 }.
+ * 4. Radius.  rho = min((Rq << 16) / M, 65537), in 64 bits.
+ * 5. Angle, as a turn fraction in Q16: the angle of (u, v) with y pointing down, which is what Middlebury's
+ *    atan2(-v, -u) / pi mapped to [0, 1] is.  ax = |U|, ay = |V|, mx = max(ax, ay), mn = min(ax, ay);
+ *    t = mx ? (mn << 16) / mx : 0 (0..65536);  i = t >> 8, fr = t & 255;
+ *    a24 = A[i] + (((A[min(i + 1, 256)] - A[i]) fr + 128) >> 8);  o = (a24 + 128) >> 8 (0..8192);
+ *    b = ax >= ay ? o : 16384 - o;  U < 0: b = 32768 - b;  V < 0: b = (65536 - b) & 65535.
+ *    A[k] = lrint(atan(k / 256) / (2 pi) 2^24), k = 0..256, a literal table (A[1] = 10430, A[128] = 1238021,
+ *    A[255] = 2091927, A[256] = 2097152; the 257 entries sum to 301013384).
+ * 6. Wheel: the 55 entries (R, G, B) of Baker et al., a literal table too (its 165 bytes sum to 21038, entry 54 is
+ *    (255, 0, 43)); i counts from 0 within a segment:
+ *      RY, 15 entries: (255, 255 i / 15, 0)        YG, 6: (255 - 255 i / 6, 255, 0)      GC, 4: (0, 255, 255 i / 4)
+ *      CB, 11: (0, 255 - 255 i / 11, 255)          BM, 13: (255 i / 13, 0, 255)          MR, 6: (255, 0, 255 - 255 i / 6)
+ *    fk = 54 b, k0 = fk >> 16 (0..53), f = fk & 65535;  per channel c16 = wheel[k0][c] (65536 - f) + wheel[k0 + 1][c] f.
+ *    The seam between entry 54 and entry 0 is Middlebury's own and is kept.
+ * 7. Colour.  rho <= 65536: out = (int)(((16711680 << 16) - rho (16711680 - c16)) >> 32), in 64 bits - zero flow is white,
+ *    radius 1 the pure wheel colour, floored as Middlebury floors.  rho > 65536: out = (3 c16) >> 18, Middlebury's 0.75 for
+ *    vectors out of range.
+ * 8. Dimming.  With OFDG_VIS_DIM_OCC and occ != 0: out >>= 1.  A float32 map is compared with != 0.0f; a NaN counts as
+ *    occluded.
+ * With max_flow = 8, as (R, G, B): (8, 0) is (255, 0, 0), (0, 8) (255, 229, 0), (-8, 0) (0, 209, 255), (0, -8) (88, 0, 255),
+ * (0, 0) (255, 255, 255), (8, 8) - out of range - (191, 86, 0), (-8, 8) (24, 191, 0).  Against the float code of the paper a
+ * channel differs by at most 1 away from radius 1 and from the wheel's seam, the two places where the code itself jumps
+ * (DESIGN.md).
+ *
+ * work: DEVICE memory of n_samples * OFDG_FLOW_VIS_WORK_BYTES, 16-byte aligned, contents unspecified before and after (the
+ * call clears it); required unless norm is FIXED, which does not look at it.  Asynchronous on `stream`, the stream the flow
+ * was written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  At most one clearing of `work` and two kernels per call (FIXED: one
+ * kernel); the only atomic is a 64-bit integer maximum; it reads no record of the context and works in every mode.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, flow or dst, n_samples < 1, a
+ * size that breaks the rule, 3 * width * height of 2^32 and more, another format, layout or norm code, unknown flag bits, a
+ * non-zero reserved field, OFDG_VIS_DIM_OCC without occ, max_flow NaN or outside [2^-8, 2^20] under FIXED, work NULL where
+ * it is required, a misaligned pointer (rows_out: 16-byte), a written range (dst, work, rows_out) that overlaps any other
+ * range of the job, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: arrows and quiver plots, an HSV (OpenCV-style) code, error maps against a second flow, percentile
+ * normalisation, a float output, montages with the frames, an in-place form.
+ */
+#define OFDG_VIS_PLANAR_BGR 0   /* dst [n,3,height,width] uint8, planes B, G, R: the frames' own layout */
+#define OFDG_VIS_HWC_RGB    1   /* dst [n,height,width,3] uint8, R, G, B: what image writers and TensorBoard take */
+#define OFDG_VIS_NORM_FIXED  0  /* radius 1 is max_flow pixels */
+#define OFDG_VIS_NORM_SAMPLE 1  /* radius 1 is the sample's own largest usable displacement */
+#define OFDG_VIS_NORM_BATCH  2  /* ... the largest of the whole call */
+#define OFDG_VIS_DIM_OCC 1      /* flag: pixels with occ != 0 at half brightness; occ required */
+#define OFDG_FLOW_VIS_WORK_BYTES 8   /* of job->work per sample */
+typedef struct ofdg_flow_vis_row { uint64_t max_r2_q16; uint32_t scale_q8; uint32_t reserved; } ofdg_flow_vis_row;  /* 16 bytes */
+struct ofdg_flow_vis_job {       /* 96 bytes */
+  const void* flow;              /* [n,2,height,width], OFDG_FMT_F32 (16-byte aligned) or OFDG_FMT_F16 (8-byte) */
+  const void* occ;               /* NULL, or [n,1,height,width] OFDG_FMT_U8 (4-byte) / OFDG_FMT_F32 (16-byte), as in ofdg_flow_stats */
+  void* dst;                     /* 16-byte aligned */
+  ofdg_flow_vis_row* rows_out;   /* DEVICE, n rows, or NULL */
+  void* work;                    /* DEVICE, n * OFDG_FLOW_VIS_WORK_BYTES, 16-byte aligned; required unless norm is FIXED */
+  int32_t width, height, flow_fmt, occ_fmt, layout, norm, flags, reserved;
+  float max_flow;                /* NORM_FIXED only: in [2^-8, 2^20]; otherwise not looked at */
+  int32_t reserved2[5];
+};
+int ofdg_flow_vis(ofdg_ctx* ctx, const struct ofdg_flow_vis_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and rows in host memory, no alignment asked of any
+ * pointer, work not looked at.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_flow_vis(const struct ofdg_flow_vis_job* job, int n_samples, int width, int height);
+/* The two constant tables of steps 5 and 6, copied out (pure, no GPU).  OFDG_EINVAL for a NULL pointer. */
+int ofdg_host_flow_vis_tables(int32_t atan_q24[257], uint8_t wheel_rgb[55][3]);
+
+/*
  * Motion blur: every pixel of image0 and / or image1 becomes a weighted mean of its frame along a short segment through the
  * pixel, whose direction and length are the pixel's own flow times the sample's shutter - the fraction of the inter-frame
  * interval the exposure lasts.  The exposure is centred on the frame's instant, so the segment is symmetric about the pixel

@@ -115,6 +115,7 @@ EXPORTS = [
     "ofdg_reproject", "ofdg_host_reproject",
     "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
     "ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw", "ofdg_host_jitter_hue",
+    "ofdg_flow_vis", "ofdg_host_flow_vis", "ofdg_host_flow_vis_tables",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1218,6 +1219,129 @@ def host_jitter(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=No
     return dst, used
 
 
+# flow visualisation (ofdg_flow_vis_row / struct ofdg_flow_vis_job / ofdg_flow_vis, include/ofdg.h)
+VIS_PLANAR_BGR, VIS_HWC_RGB = 0, 1                         # OFDG_VIS_PLANAR_BGR, OFDG_VIS_HWC_RGB
+VIS_NORM_FIXED, VIS_NORM_SAMPLE, VIS_NORM_BATCH = 0, 1, 2  # OFDG_VIS_NORM_*
+VIS_DIM_OCC = 1                                            # OFDG_VIS_DIM_OCC
+FLOW_VIS_WORK_BYTES = 8                                    # OFDG_FLOW_VIS_WORK_BYTES
+FLOW_VIS_ROW_WORDS = 4                                     # a row as int32 [4]: max_r2_q16 (two words), scale_q8, reserved
+VIS_LAYOUTS = {"planar_bgr": VIS_PLANAR_BGR, "hwc_rgb": VIS_HWC_RGB}
+VIS_NORMS = {"fixed": VIS_NORM_FIXED, "sample": VIS_NORM_SAMPLE, "batch": VIS_NORM_BATCH}
+
+
+class FlowVisRow(C.Structure):
+    """ofdg_flow_vis_row: the scale of one sample's picture (16 bytes)."""
+    _fields_ = [("max_r2_q16", C.c_uint64), ("scale_q8", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FlowVisJob(C.Structure):
+    """struct ofdg_flow_vis_job (96 bytes)."""
+    _fields_ = [("flow", C.c_void_p), ("occ", C.c_void_p), ("dst", C.c_void_p), ("rows_out", C.c_void_p), ("work", C.c_void_p),
+                ("width", C.c_int32), ("height", C.c_int32), ("flow_fmt", C.c_int32), ("occ_fmt", C.c_int32), ("layout", C.c_int32),
+                ("norm", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("max_flow", C.c_float), ("reserved2", C.c_int32 * 5)]
+
+
+def _flow_vis_row_dtype():
+    import numpy as np
+    return np.dtype([("max_r2_q16", "<u8"), ("scale_q8", "<u4"), ("reserved", "<u4")])
+
+
+def flow_vis_numpy(rows):
+    """Rows of Generator.flow_vis / host_flow_vis - a torch tensor or numpy array of int32 [n,4] (or any array of 16 bytes a
+    row) - as a numpy structured array [n] with the fields max_r2_q16 (the largest squared displacement, in units of 2^-16
+    px^2; 0 under norm="fixed"), scale_q8 (the displacement at radius 1, in 1/256 px) and reserved."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if hasattr(rows, "detach") else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _flow_vis_row_dtype():
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % 16:
+        raise ValueError("rows must be 16 bytes each, got %d bytes" % raw.size)
+    return raw.view(_flow_vis_row_dtype())
+
+
+def flow_vis_shape(n, height, width, layout="planar_bgr"):
+    """The shape of the picture of n samples: [n,3,H,W] (planar_bgr) or [n,H,W,3] (hwc_rgb)."""
+    if layout not in VIS_LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (", ".join(VIS_LAYOUTS), layout))
+    return (n, 3, height, width) if VIS_LAYOUTS[layout] == VIS_PLANAR_BGR else (n, height, width, 3)
+
+
+def _flow_vis_job(flow, occ, dst, rows_out, work, ptr, size, codes, norm, max_flow, layout, dim_occ):
+    """The job of Generator.flow_vis / host_flow_vis; raises ValueError for a name that is no norm or layout, and for
+    norm="fixed" without max_flow"""
+    if norm not in VIS_NORMS:
+        raise ValueError("norm must be one of %s, got %r" % (", ".join(VIS_NORMS), norm))
+    if layout not in VIS_LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (", ".join(VIS_LAYOUTS), layout))
+    if norm == "fixed" and max_flow is None:
+        raise ValueError("norm=\"fixed\" needs max_flow= (pixels at radius 1)")
+    job = FlowVisJob()
+    job.flow, job.occ, job.dst, job.rows_out, job.work = ptr(flow), ptr(occ), ptr(dst), ptr(rows_out), ptr(work)
+    job.height, job.width = size
+    job.flow_fmt, job.occ_fmt = codes
+    job.layout, job.norm, job.flags = VIS_LAYOUTS[layout], VIS_NORMS[norm], VIS_DIM_OCC if dim_occ else 0
+    job.max_flow = 0.0 if max_flow is None else float(max_flow)
+    return job
+
+
+def alloc_flow_vis(n, size, layout="planar_bgr", norm="sample", device="cuda"):
+    """(dst, rows, work) of Generator.flow_vis for n samples of size=(height, width): the uint8 picture in `layout`, the int32
+    [n,4] rows (rows_out; flow_vis_numpy reads them) and the uint8 [n,8] workspace of the maximum - None under norm="fixed",
+    which needs none.  Not filled: the call clears the workspace and writes every byte of the other two."""
+    import torch
+    if norm not in VIS_NORMS:
+        raise ValueError("norm must be one of %s, got %r" % (", ".join(VIS_NORMS), norm))
+    shape = flow_vis_shape(n, int(size[0]), int(size[1]), layout)
+    return (torch.empty(shape, dtype=torch.uint8, device=device), torch.empty((n, FLOW_VIS_ROW_WORDS), dtype=torch.int32, device=device),
+            None if norm == "fixed" else torch.empty((n, FLOW_VIS_WORK_BYTES), dtype=torch.uint8, device=device))
+
+
+def host_flow_vis(flow, occ=None, norm="sample", max_flow=None, layout="planar_bgr", dim_occ=False):
+    """ofdg_host_flow_vis (no GPU): the colour-wheel picture of a HOST flow - float32 or float16 [n,2,H,W], occ None or the
+    float32 / uint8 [n,1,H,W] map that goes with it (looked at with dim_occ only).  Returns (picture, rows): uint8 [n,3,H,W]
+    (planar B, G, R) or [n,H,W,3] (R, G, B) and the rows as flow_vis_numpy's array."""
+    import numpy as np
+    flow = np.ascontiguousarray(flow)
+    occ = None if occ is None else np.ascontiguousarray(occ)
+    if flow.ndim != 4:
+        raise ValueError("flow must be [n,2,H,W], got %s" % (flow.shape,))
+    height, width = flow.shape[2:]
+    n, *codes = _check_flow_occ(flow, occ, height, width)
+    dst = np.zeros(flow_vis_shape(n, height, width, layout), np.uint8)
+    rows = np.zeros((n,), _flow_vis_row_dtype())
+    job = _flow_vis_job(flow, occ, dst, rows, None, lambda a: None if a is None else a.ctypes.data, (0, 0), codes, norm, max_flow, layout, dim_occ)
+    _host_check(lib().ofdg_host_flow_vis(C.byref(job), n, width, height))
+    return dst, rows
+
+
+def host_flow_vis_tables():
+    """ofdg_host_flow_vis_tables (pure, no GPU): (the int32 [257] arctangent table in Q24 turns, the uint8 [55,3] colour wheel
+    as R, G, B) of the definition."""
+    import numpy as np
+    atan, wheel = np.zeros(257, np.int32), np.zeros((55, 3), np.uint8)
+    _host_check(lib().ofdg_host_flow_vis_tables(_hptr(atan), _hptr(wheel)))
+    return atan, wheel
+
+
+def flow_vis_legend(size=151):
+    """The wheel disc to put beside a picture, uint8 [size,size,3] (R, G, B): host_flow_vis of u = x - c, v = y - c, c = size //
+    2, under norm="fixed" with max_flow = c - so the disc of radius c holds every direction at every length, white in the
+    centre, and the corners show the colours of vectors out of range.  Computed at the next size the rule allows, then cut."""
+    import numpy as np
+    size = int(size)
+    if size < 3:
+        raise ValueError("size must be at least 3, got %d" % size)
+    c = size // 2
+    height, width = size + (size & 1), (size + 7) // 8 * 8
+    flow = np.zeros((1, 2, height, width), np.float32)
+    flow[0, 0] = np.arange(width, dtype=np.float32)[None, :] - c
+    flow[0, 1] = np.arange(height, dtype=np.float32)[:, None] - c
+    picture, _ = host_flow_vis(flow, norm="fixed", max_flow=float(c), layout="hwc_rgb")
+    return np.ascontiguousarray(picture[0, :size, :size])
+
+
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
 MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
 MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
@@ -1892,6 +2016,9 @@ def lib():
         L.ofdg_host_jitter.argtypes = [C.POINTER(JitterJob), i32, i32, i32]
         L.ofdg_jitter_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(JitterJob), C.POINTER(JitterRec)]
         L.ofdg_host_jitter_hue.argtypes = [vp, vp, C.c_size_t, i32]
+        L.ofdg_flow_vis.argtypes = [vp, C.POINTER(FlowVisJob), i32, vp]
+        L.ofdg_host_flow_vis.argtypes = [C.POINTER(FlowVisJob), i32, i32, i32]
+        L.ofdg_host_flow_vis_tables.argtypes = [vp, vp]
         L.ofdg_motion_blur.argtypes = [vp, C.POINTER(MblurJob), i32, vp]
         L.ofdg_host_motion_blur.argtypes = [C.POINTER(MblurJob), i32, i32, i32]
         L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
@@ -2382,6 +2509,32 @@ class Generator:
         job = _jitter_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), _optr(work), first_index,
                           self._seed(seed), ranges)
         self._check(lib().ofdg_jitter(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
+
+    def flow_vis(self, flow, dst=None, occ=None, norm="sample", max_flow=None, layout="planar_bgr", dim_occ=False, rows_out=None, work=None,
+                 stream=0, size=None):
+        """The Middlebury colour-wheel picture of a flow tensor (ofdg_flow_vis, include/ofdg.h): the direction is the hue, the
+        length the saturation, zero flow white, unusable pixels black.  flow: float32 or float16 [n,2,H,W] - the forward flow,
+        flow1, a cropped, warped or splat flow; the formats come from the dtypes.  dst: the uint8 tensor to write, [n,3,H,W]
+        (layout "planar_bgr": planes B, G, R, as the frames) or [n,H,W,3] ("hwc_rgb": what image writers take); None: a new
+        one.  norm: "fixed" - radius 1 is max_flow pixels -, "sample" - the sample's own largest displacement - or "batch" -
+        the largest of the call.  dim_occ: pixels where occ (the float32 / uint8 [n,1,H,W] map that goes with the flow) is
+        non-zero at half brightness.  rows_out: None or an int32 device tensor [n,4] that receives the scales used
+        (flow_vis_numpy reads it).  work: the uint8 [n,8] workspace of the maximum (alloc_flow_vis makes all three), one per
+        call in flight; needed unless norm is "fixed".  stream: the stream the flow was written on, or STREAM_OWN.
+        size=(height, width): planes of that size instead of the context's.  Asynchronous.  Returns dst."""
+        import torch
+        height, width, job_size = self._job_size(size)
+        n, *codes = _check_flow_occ(flow, occ, height, width)
+        if dst is None:
+            dst = torch.empty(flow_vis_shape(n, height, width, layout), dtype=torch.uint8, device=flow.device)
+        _check_plane("dst", dst, ("uint8",), flow_vis_shape(n, height, width, layout))
+        self._check_recs(None, rows_out, "int32", (n, FLOW_VIS_ROW_WORDS))
+        if work is not None and (str(work.dtype) != "torch.uint8" or work.numel() < n * FLOW_VIS_WORK_BYTES):
+            raise ValueError("work must be a uint8 device tensor of at least [%d,%d] (alloc_flow_vis)" % (n, FLOW_VIS_WORK_BYTES))
+        job = _flow_vis_job(flow, occ, dst, rows_out, work, lambda t: None if t is None else _dptr(t).value, job_size, codes, norm, max_flow,
+                            layout, dim_occ)
+        self._check(lib().ofdg_flow_vis(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
@@ -3095,6 +3248,7 @@ class _RingSlot:
                  "erase",        # (workspace, records) of erase=
                  "edges",        # the planes of boundaries= by name ...
                  "edge_args",    # ... and the plane arguments of Generator.boundaries that fill them
+                 "vis",          # (picture, rows, workspace) of vis= by the name of the flow
                  "packed",       # the tensors of pack= by name
                  "ready",        # event: the batch is rendered (recorded on the internal stream)
                  "released",     # event: the consumer is done with the set (None until it has been handed out once)
@@ -3130,7 +3284,8 @@ class FlowLoader:
         9. objects=True     the table, of the label planes of stage 1
         10. stats=, pyramid= the reductions of flow and occ0
         11. boundaries=     of the flows and label planes
-        12. pack=           of image0, image1 and flow, into tensors of its own
+        12. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
+        13. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
     colour jitter and the eraser's mean fill see the augmented frame - the fill is the mean colour of the jittered frame, as in
@@ -3198,14 +3353,20 @@ class FlowLoader:
     pack=dict(image_dtype=, flow_dtype=, layout=, concat=, rgb=, scale=, bias=, flow_scale=) (every key optional: alloc_pack and
     Generator.pack): the frames and the flow are packed for the network.  The loader yields the packed tensors in the places
     of image0, image1 and flow - with concat the 6-channel tensor first and None second -; the dict is untouched: the
-    pyramid's levels, labels and occlusion maps are not packed."""
+    pyramid's levels, labels and occlusion maps are not packed.
+    vis=dict(which=, norm=, max_flow=, layout=, dim_occ=) (every key optional: which ("flow",), norm "sample", layout
+    "planar_bgr", dim_occ False; Generator.flow_vis): the colour-wheel picture of the batch's final flow - behind the window,
+    in front of pack=, which may rescale it; the dict also holds "flow_vis" (uint8, [n,3,H,W] or [n,H,W,3]) and "flow_vis_rows"
+    (int32 [n,4]: flow_vis_numpy), and "flow1_vis" / "flow1_vis_rows" when which names "flow1", which must be among extras=.
+    dim_occ=True dims by "occ0" (for flow1: "occ1") as the eraser left it, and needs that map among extras=."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, splat=None, jitter=None, **kw):
+                 reproject=None, splat=None, jitter=None, vis=None, **kw):
         import torch
+        self.vis = self._vis_options(vis, extras)
         self.boundaries = self._boundary_options(boundaries, extras)
         self.erase = self._erase_options(erase, extras)
         self.motion_blur = self._motion_blur_options(motion_blur, extras)
@@ -3299,6 +3460,9 @@ class FlowLoader:
                     t.edge_args.update({"flow" + tag: t.planes["flow" + tag], "edge" + tag: t.edges.get("edge%d" % f),
                                         "dist2_1" if f else "dist2": t.edges.get("dist%d" % f),
                                         "label" + tag: t.planes["label%d" % f] if o["labels"] else None})
+            t.vis = None
+            if self.vis is not None:
+                t.vis = {name: alloc_flow_vis(n, (ph, pw), self.vis["layout"], self.vis["norm"]) for name in self.vis["which"]}
             if self.pack is not None:
                 o = self.pack
                 t.packed = alloc_pack(n, ph, pw, image_dtype=o.get("image_dtype"), flow_dtype=o.get("flow_dtype"),
@@ -3360,6 +3524,30 @@ class FlowLoader:
         if o["mark_occ"] and 1 in maps and 0 in o["frames"] and "flow1" not in extras:
             raise ValueError("erase= marks the rectangles of frame 0 into occ1 through flow1: extras= must contain \"flow1\"")
         return {k: v for k, v in erase.items() if k in ERASE_RANGES}, o
+
+    @staticmethod
+    def _vis_options(vis, extras):
+        """vis= with its defaults filled in, or None; raises for what the loader cannot serve"""
+        if vis is None:
+            return None
+        o = dict(which=("flow",), norm="sample", max_flow=None, layout="planar_bgr", dim_occ=False)
+        unknown = set(vis) - set(o)
+        if unknown:
+            raise ValueError("unknown vis option(s) %s" % sorted(unknown))
+        o.update(vis)
+        o["which"] = (o["which"],) if isinstance(o["which"], str) else tuple(o["which"])
+        o["dim_occ"] = bool(o["dim_occ"])
+        extras = tuple(extras or ())
+        if not o["which"] or any(name not in ("flow", "flow1") for name in o["which"]) or len(set(o["which"])) != len(o["which"]):
+            raise ValueError("vis= needs which of \"flow\" and / or \"flow1\", got %r" % (o["which"],))
+        if "flow1" in o["which"] and "flow1" not in extras:
+            raise ValueError("vis= of flow1 reads a flow the loader was not asked for: extras= must contain \"flow1\"")
+        for name in o["which"]:
+            occ = "occ1" if name == "flow1" else "occ0"
+            if o["dim_occ"] and occ not in extras:
+                raise ValueError("vis= with dim_occ=True dims %s by %s: extras= must contain \"%s\"" % (name, occ, occ))
+        _flow_vis_job(None, None, None, None, None, lambda a: None, (0, 0), (FMT_F32, FMT_F32), o["norm"], o["max_flow"], o["layout"], o["dim_occ"])
+        return o
 
     @staticmethod
     def _jitter_options(jitter):
@@ -3485,6 +3673,11 @@ class FlowLoader:
         if self.boundaries is not None:
             o = self.boundaries
             g.boundaries(radius=o["radius"], min_step=o["min_step"], labels=o["labels"], stream=s, size=size, **t.edge_args)
+        if self.vis is not None:
+            o = self.vis
+            for name, (dst, rows, work) in t.vis.items():
+                g.flow_vis(planes[name], dst, occ=planes["occ1" if name == "flow1" else "occ0"] if o["dim_occ"] else None, norm=o["norm"],
+                           max_flow=o["max_flow"], layout=o["layout"], dim_occ=o["dim_occ"], rows_out=rows, work=work, stream=s, size=size)
         if self.pack is not None:
             o = self.pack
             g.pack({k: planes[k] for k in PACK_PLANES}, t.packed, scale=o.get("scale", (1.0, 1.0, 1.0)), bias=o.get("bias", (0.0, 0.0, 0.0)),
@@ -3525,6 +3718,9 @@ class FlowLoader:
             more.update(t.edges)
         if t.erase is not None:
             more["erase"] = t.erase[1]
+        if t.vis is not None:
+            for name, (dst, rows, _) in t.vis.items():
+                more[name + "_vis"], more[name + "_vis_rows"] = dst, rows
         top = t.planes if t.packed is None else t.packed
         return (top["image0"], top.get("image1"), top["flow"]) + ((more,) if more or self.extras is not None else ())
 

@@ -835,6 +835,60 @@ int ofdg_host_jitter(const struct ofdg_jitter_job* job, int n_samples, int width
   return OFDG_OK;
 }
 
+// ofdg_flow_vis on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The usable rule, the Q8 components,
+// the roots, the scale, the angle, the wheel and the colour are the functions the kernels run (csrc/ofdg_device.h) on the two
+// tables of that header; elements are moved with memcpy.
+int ofdg_host_flow_vis_tables(int32_t atan_q24[257], uint8_t wheel_rgb[55][3]) {
+  if (!atan_q24 || !wheel_rgb) { g_host_error = "ofdg_host_flow_vis_tables: atan_q24 or wheel_rgb is NULL"; return OFDG_EINVAL; }
+  for (int k = 0; k < kVisAtanEntries; ++k) atan_q24[k] = kVisAtan[k];
+  for (int k = 0; k < kVisWheelEntries; ++k)
+    for (int c = 0; c < 3; ++c) wheel_rgb[k][c] = (uint8_t)(kVisWheel[k] >> (8 * c));
+  return OFDG_OK;
+}
+int ofdg_host_flow_vis(const struct ofdg_flow_vis_job* job, int n_samples, int width, int height) {
+  const DevVisJob* const j = reinterpret_cast<const DevVisJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = vis_arg_error(j, n_samples, width, height, /*with_work=*/false);
+  if (why) { g_host_error = std::string("ofdg_host_flow_vis: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const FlowPlane fl{j->flow, j->flow_fmt};
+  const OccPlane hidden{j->occ, j->occ_fmt};
+  const bool dim = j->flags & OFDG_VIS_DIM_OCC, hwc = j->layout == OFDG_VIS_HWC_RGB;
+  // the largest R2 of each sample's usable pixels, occluded ones included; BATCH: the largest of them all
+  std::vector<unsigned long long> max_r2((size_t)n_samples, 0ull);
+  if (j->norm != OFDG_VIS_NORM_FIXED) {
+    unsigned long long all = 0;
+    for (int i = 0; i < n_samples; ++i) {
+      for (size_t k = 0; k < plane; ++k) {
+        const float u = fl.at((size_t)i * 2 * plane + k), v = fl.at(((size_t)i * 2 + 1) * plane + k);
+        if (vis_usable(u, v)) max_r2[i] = std::max(max_r2[i], vis_r2(vis_fixed(u), vis_fixed(v)));
+      }
+      all = std::max(all, max_r2[i]);
+    }
+    if (j->norm == OFDG_VIS_NORM_BATCH) std::fill(max_r2.begin(), max_r2.end(), all);
+  }
+  uint8_t* const dst = static_cast<uint8_t*>(j->dst);
+  for (int i = 0; i < n_samples; ++i) {
+    const uint32_t M = j->norm == OFDG_VIS_NORM_FIXED ? vis_scale_fixed(j->max_flow) : vis_scale_of(max_r2[i]);
+    if (j->rows_out) {
+      const DevVisRow row{max_r2[i], M, 0u};
+      std::memcpy(reinterpret_cast<uint8_t*>(j->rows_out) + sizeof(row) * (size_t)i, &row, sizeof(row));
+    }
+    for (size_t k = 0; k < plane; ++k) {
+      const float u = fl.at((size_t)i * 2 * plane + k), v = fl.at(((size_t)i * 2 + 1) * plane + k);
+      const uint32_t rgb = vis_usable(u, v) ? vis_pixel(u, v, M, vis_inv(M), dim && hidden.at((size_t)i * plane + k), kVisAtan, kVisWheel) : 0u;
+      for (int c = 0; c < 3; ++c) {  // c: R, G, B
+        const uint8_t byte = (uint8_t)(rgb >> (8 * c));
+        if (hwc) dst[((size_t)i * plane + k) * 3 + c] = byte;
+        else dst[((size_t)i * 3 + (2 - c)) * plane + k] = byte;
+      }
+    }
+  }
+  return OFDG_OK;
+}
+
 // ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.

@@ -5482,4 +5482,142 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
   }
 }
 
+// ---- Flow visualisation (ofdg_flow_vis, include/ofdg.h) --------------------------------------------------------------------
+// Under OFDG_VIS_NORM_FIXED one launch, else two behind the clearing of `work`: flow_vis_max_kernel leaves the largest R2 of
+// each sample (BATCH: of the call, in slot 0) in `work`, flow_vis_colour_kernel - which starts after the first has ended, the
+// order of the stream - takes the scale from it and writes the picture.  blockIdx.x counts the kVisBlockPixels-pixel blocks
+// of a plane, blockIdx.y the samples (strided beyond 65535 of them, as in the jitter: no test runs that many).  A lane takes 4
+// consecutive pixels - 16 bytes of each float32 flow plane, 8 of a
+// binary16 one, 16 or 4 of the map - in rounds of 1024 pixels per workgroup; H * W is a multiple of 16, so a plane is whole
+// pieces and rows never split one.  The steps of the definition are the host twin's functions (csrc/ofdg_device.h), so the
+// bytes are the twin's.  No scratch; the colour kernel holds the two tables in 1260 bytes of LDS.
+constexpr int kVisThreads = 256;
+constexpr int kVisBlockPixels = 4096;  // 48 workgroups per 512 x 384 plane, four rounds each
+static_assert(kVisBlockPixels % (kVisThreads * 4) == 0, "whole rounds of 4-pixel pieces");
+#ifndef OFDG_VIS_READ_FIRST
+#define OFDG_VIS_READ_FIRST 1
+#endif
+constexpr int kVisReadFirst = OFDG_VIS_READ_FIRST;  // which slots of `work` the reduction reads before its atomic: 0 none, 1 BATCH's one slot, 2 every slot
+template <bool kHalf>
+__device__ __forceinline__ void vis_load_flow4(const void* flow, size_t at, float (&e)[4]) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  if constexpr (kHalf) {
+    const f16x4 a = *reinterpret_cast<const f16x4*>(static_cast<const _Float16*>(flow) + at);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = (float)a[q];
+  } else {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(static_cast<const float*>(flow) + at);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = a[q];
+  }
+}
+
+// The maximum's reduction: a running 64-bit maximum of R2 per lane over the usable pixels, across the wave with __shfl_xor,
+// across the workgroup through LDS, and at most one 64-bit integer atomicMax per workgroup (none where nothing is usable: the
+// slot is cleared to 0 before the launch).  No bit depends on arrival order.
+template <bool kHalf>
+__global__ __launch_bounds__(kVisThreads) void flow_vis_max_kernel(const DevVisJob job, int n, uint32_t plane) {
+  __shared__ unsigned long long s_part[kVisThreads / 64];
+  const uint32_t first = blockIdx.x * (uint32_t)kVisBlockPixels;
+  const uint32_t end = first + (uint32_t)kVisBlockPixels < plane ? first + (uint32_t)kVisBlockPixels : plane;
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    const size_t base = (size_t)i * 2 * plane;
+    unsigned long long best = 0;
+    for (uint32_t at = first + threadIdx.x * 4u; at < end; at += (uint32_t)(kVisThreads * 4)) {
+      float u[4], v[4];
+      vis_load_flow4<kHalf>(job.flow, base + at, u);
+      vis_load_flow4<kHalf>(job.flow, base + plane + at, v);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const unsigned long long r2 = vis_usable(u[q], v[q]) ? vis_r2(vis_fixed(u[q]), vis_fixed(v[q])) : 0ull;
+        best = r2 > best ? r2 : best;
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const unsigned long long other = (unsigned long long)__shfl_xor((long long)best, d, 64);
+      best = other > best ? other : best;
+    }
+    if (lane == 0) s_part[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+#pragma unroll
+      for (int w = 0; w < kVisThreads / 64; ++w) total = s_part[w] > total ? s_part[w] : total;
+      // BATCH: every workgroup of the call meets on slot 0, which only grows - one that reads a value no smaller than its own
+      // has nothing to add (a stale, smaller reading costs an atomic that changes nothing), which spares the slot most of
+      // the atomics.  A sample's own slot has 1 / n of them, and there the reading's round trip costs more than it saves
+      // (the three forms measured: CHANGELOG; kVisReadFirst 0: no slot is read first, 2: every slot is).
+      unsigned long long* const slot = job.work + (job.norm == OFDG_VIS_NORM_BATCH ? 0 : i);
+      const bool read_first = kVisReadFirst == 2 || (kVisReadFirst == 1 && job.norm == OFDG_VIS_NORM_BATCH);
+      if (read_first ? total > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : total != 0ull) atomicMax(slot, total);
+    }
+    __syncthreads();  // (the next sample of this workgroup writes the parts again)
+  }
+}
+
+// The picture.  The grid is flow_vis_max_kernel's.  The tables are copied to LDS once per workgroup; the scale is read or
+// rounded on wave-uniform values once per (workgroup, sample).  Planar: a lane stores one dword of each of the B, G and R
+// planes, a wave 256 consecutive bytes per plane; HWC: a lane stores the 12 bytes of its 4 pixels as three dwords, a wave 768
+// consecutive bytes.  Workgroup 0 of a sample writes its row from lane 0 with one 16-byte store.
+template <bool kHalf, int kOcc, bool kHwc>  // kOcc: 0 no dimming, 1 by a float32 map, 2 by a uint8 one
+__global__ __launch_bounds__(kVisThreads) void flow_vis_colour_kernel(const DevVisJob job, int n, uint32_t plane) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  __shared__ int32_t s_atan[kVisAtanEntries];
+  __shared__ uint32_t s_wheel[kVisWheelEntries];
+  for (int k = (int)threadIdx.x; k < kVisAtanEntries; k += kVisThreads) s_atan[k] = kVisAtan[k];
+  if (threadIdx.x < (uint32_t)kVisWheelEntries) s_wheel[threadIdx.x] = kVisWheel[threadIdx.x];
+  __syncthreads();
+  const uint32_t first = blockIdx.x * (uint32_t)kVisBlockPixels;
+  const uint32_t end = first + (uint32_t)kVisBlockPixels < plane ? first + (uint32_t)kVisBlockPixels : plane;
+  uint8_t* const dst = static_cast<uint8_t*>(job.dst);
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    unsigned long long max_r2 = 0;
+    uint32_t M;
+    if (job.norm == OFDG_VIS_NORM_FIXED) M = vis_scale_fixed(job.max_flow);
+    else {
+      max_r2 = job.work[job.norm == OFDG_VIS_NORM_BATCH ? 0 : i];
+      M = vis_scale_of(max_r2);
+    }
+    M = (uint32_t)__builtin_amdgcn_readfirstlane((int)M);
+    const float inv_m = vis_inv(M);
+    if (job.rows_out && blockIdx.x == 0u && threadIdx.x == 0u)
+      *reinterpret_cast<crop_u32x4*>(job.rows_out + i) = crop_u32x4{(uint32_t)max_r2, (uint32_t)(max_r2 >> 32), M, 0u};
+    const size_t base = (size_t)i * 2 * plane;
+    for (uint32_t at = first + threadIdx.x * 4u; at < end; at += (uint32_t)(kVisThreads * 4)) {
+      float u[4], v[4];
+      vis_load_flow4<kHalf>(job.flow, base + at, u);
+      vis_load_flow4<kHalf>(job.flow, base + plane + at, v);
+      uint32_t hidden = 0;  // bit q: pixel q is dimmed
+      if constexpr (kOcc == 1) {
+        const f32x4 o = *reinterpret_cast<const f32x4*>(static_cast<const float*>(job.occ) + (size_t)i * plane + at);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) hidden |= (o[q] != 0.0f ? 1u : 0u) << q;
+      } else if constexpr (kOcc == 2) {
+        const uint32_t o = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(job.occ) + (size_t)i * plane + at);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) hidden |= (((o >> (8 * q)) & 255u) != 0u ? 1u : 0u) << q;
+      }
+      uint32_t px[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) px[q] = vis_usable(u[q], v[q]) ? vis_pixel(u[q], v[q], M, inv_m, (hidden >> q) & 1u, s_atan, s_wheel) : 0u;
+      if constexpr (kHwc) {
+        uint32_t* const dp = reinterpret_cast<uint32_t*>(dst + ((size_t)i * plane + at) * 3);
+        dp[0] = px[0] | (px[1] << 24);
+        dp[1] = (px[1] >> 8) | (px[2] << 16);
+        dp[2] = (px[2] >> 16) | (px[3] << 8);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {  // c: R, G, B of a pixel's word; plane 2 - c
+          const uint32_t sh = 8u * (uint32_t)c;
+          const uint32_t w = ((px[0] >> sh) & 255u) | (((px[1] >> sh) & 255u) << 8) | (((px[2] >> sh) & 255u) << 16) | (((px[3] >> sh) & 255u) << 24);
+          *reinterpret_cast<uint32_t*>(dst + ((size_t)i * 3 + (size_t)(2 - c)) * plane + at) = w;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -292,7 +292,8 @@ struct PostOp {
 // A run-time value as a template argument: f(std::integral_constant<T, V>) for the V among Vs that v equals.  The lists at
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
-// 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel.
+// 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel,
+// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -2025,6 +2026,44 @@ int ofdg_splat(ofdg_ctx* c, const struct ofdg_splat_job* job, int n_samples, voi
     if (!splat_resolves(*j)) return;
     with_bool(j->img_fmt == OFDG_FMT_U8, [&](auto src_u8) {
       hipLaunchKernelGGL((splat_resolve_kernel<decltype(src_u8)::value, decltype(half)::value>), g, dim3(kSplatThreads), 0, st, *j, n_samples, W, H, tiles_x);
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// The colour-wheel picture of a caller-given flow: unless the scale is fixed the clearing of `work` and the maximum's
+// reduction, then one kernel for every sample, all on `stream`.
+int ofdg_flow_vis(ofdg_ctx* c, const struct ofdg_flow_vis_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_flow_vis"};
+  const DevVisJob* const j = reinterpret_cast<const DevVisJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = vis_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = vis_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const bool maxima = vis_needs_work(*j);
+  OFDG_TRY(op.aligned("flow", j->flow, j->flow_fmt));
+  if (j->occ) OFDG_TRY(op.aligned("occ", j->occ, j->occ_fmt));
+  if ((uintptr_t)j->dst & 15) return op.fail("dst must be 16-byte aligned");
+  if ((uintptr_t)j->rows_out & 15) return op.fail("rows_out must be 16-byte aligned");
+  if (maxima && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const dim3 g((plane + kVisBlockPixels - 1) / kVisBlockPixels, (unsigned)std::min(n_samples, 65535));
+  const bool half = j->flow_fmt == OFDG_FMT_F16;
+  if (maxima) {
+    HIP_OK(c, hipMemsetAsync(j->work, 0, sizeof(unsigned long long) * (size_t)n_samples, st));
+    with_bool(half, [&](auto h) { hipLaunchKernelGGL((flow_vis_max_kernel<decltype(h)::value>), g, dim3(kVisThreads), 0, st, *j, n_samples, plane); });
+    HIP_OK(c, hipGetLastError());
+  }
+  with_bool(half, [&](auto h) {
+    with_occ_kind((j->flags & OFDG_VIS_DIM_OCC) ? j->occ : nullptr, j->occ_fmt, [&](auto occ_kind) {
+      with_bool(j->layout == OFDG_VIS_HWC_RGB, [&](auto hwc) {
+        hipLaunchKernelGGL((flow_vis_colour_kernel<decltype(h)::value, decltype(occ_kind)::value, decltype(hwc)::value>), g, dim3(kVisThreads), 0, st, *j,
+                           n_samples, plane);
+      });
     });
   });
   HIP_OK(c, hipGetLastError());

@@ -1836,6 +1836,191 @@ inline const char* splat_arg_error(const DevSplatJob* j, int n, int width, int h
   return nullptr;
 }
 
+// ---- Flow visualisation (ofdg_flow_vis, include/ofdg.h) --------------------------------------------------------------------
+// What the device entry, the kernels and the host twin share: the job as the kernels take it, the two constant tables, the
+// steps of the definition on one pixel and the argument rules.  Behind the rounding of u and v to Q8 everything is integers.
+struct DevVisRow {  // ofdg_flow_vis_row, field for field
+  unsigned long long max_r2;
+  uint32_t scale_q8, reserved;
+};
+struct DevVisJob {  // struct ofdg_flow_vis_job, field for field
+  const void* flow;
+  const void* occ;
+  void* dst;
+  DevVisRow* rows_out;
+  unsigned long long* work;  // one 64-bit maximum per sample
+  int32_t width, height, flow_fmt, occ_fmt, layout, norm, flags, reserved;
+  float max_flow;
+  int32_t reserved2[5];
+};
+static_assert(sizeof(ofdg_flow_vis_row) == sizeof(DevVisRow) && sizeof(DevVisRow) == 16 && offsetof(ofdg_flow_vis_row, scale_q8) == offsetof(DevVisRow, scale_q8) &&
+              offsetof(DevVisRow, scale_q8) == 8 && sizeof(unsigned long long) == OFDG_FLOW_VIS_WORK_BYTES,
+              "ofdg_flow_vis_row: 16 bytes, written as one piece; a sample's workspace");
+static_assert(sizeof(struct ofdg_flow_vis_job) == sizeof(DevVisJob) && sizeof(DevVisJob) == 96 && offsetof(struct ofdg_flow_vis_job, occ) == offsetof(DevVisJob, occ) &&
+              offsetof(struct ofdg_flow_vis_job, dst) == offsetof(DevVisJob, dst) && offsetof(struct ofdg_flow_vis_job, rows_out) == offsetof(DevVisJob, rows_out) &&
+              offsetof(struct ofdg_flow_vis_job, work) == offsetof(DevVisJob, work) && offsetof(struct ofdg_flow_vis_job, width) == offsetof(DevVisJob, width) &&
+              offsetof(DevVisJob, width) == 40 && offsetof(struct ofdg_flow_vis_job, norm) == offsetof(DevVisJob, norm) && offsetof(DevVisJob, norm) == 60 &&
+              offsetof(struct ofdg_flow_vis_job, max_flow) == offsetof(DevVisJob, max_flow) && offsetof(DevVisJob, max_flow) == 72 &&
+              offsetof(struct ofdg_flow_vis_job, reserved2) == offsetof(DevVisJob, reserved2),
+              "struct ofdg_flow_vis_job: 96 bytes, the layout the kernels take");
+constexpr int kVisAtanEntries = 257, kVisWheelEntries = 55;
+// A[k] = lrint(atan(k / 256) / (2 pi) * 2^24): the angle of slope k / 256 as a turn fraction in Q24
+constexpr int32_t kVisAtan[kVisAtanEntries] = {
+    0, 10430, 20860, 31290, 41718, 52145, 62571, 72994, 83416, 93835, 104251, 114664, 125073, 135479, 145880, 156277,
+    166669, 177056, 187438, 197815, 208185, 218549, 228906, 239256, 249600, 259935, 270263, 280583, 290894, 301197, 311491, 321775,
+    332050, 342315, 352570, 362814, 373047, 383270, 393481, 403681, 413869, 424044, 434208, 444358, 454496, 464620, 474731, 484829,
+    494912, 504981, 515035, 525075, 535100, 545109, 555103, 565081, 575043, 584989, 594918, 604831, 614727, 624606, 634467, 644311,
+    654136, 663944, 673734, 683505, 693257, 702990, 712705, 722400, 732076, 741732, 751368, 760984, 770579, 780155, 789709, 799243,
+    808756, 818248, 827718, 837168, 846595, 856001, 865384, 874746, 884085, 893402, 902696, 911968, 921217, 930443, 939645, 948825,
+    957981, 967114, 976223, 985308, 994370, 1003407, 1012421, 1021410, 1030375, 1039316, 1048232, 1057123, 1065990, 1074832, 1083649, 1092442,
+    1101209, 1109951, 1118668, 1127359, 1136026, 1144667, 1153282, 1161872, 1170436, 1178975, 1187488, 1195975, 1204436, 1212871, 1221280, 1229664,
+    1238021, 1246352, 1254658, 1262937, 1271189, 1279416, 1287616, 1295790, 1303938, 1312059, 1320154, 1328223, 1336265, 1344281, 1352271, 1360234,
+    1368170, 1376081, 1383964, 1391822, 1399652, 1407457, 1415234, 1422986, 1430711, 1438409, 1446081, 1453727, 1461346, 1468939, 1476505, 1484045,
+    1491559, 1499046, 1506507, 1513942, 1521350, 1528733, 1536089, 1543419, 1550722, 1558000, 1565251, 1572477, 1579676, 1586849, 1593997, 1601118,
+    1608214, 1615284, 1622328, 1629346, 1636338, 1643305, 1650246, 1657162, 1664052, 1670917, 1677757, 1684570, 1691359, 1698123, 1704861, 1711574,
+    1718262, 1724925, 1731563, 1738176, 1744764, 1751327, 1757866, 1764380, 1770869, 1777334, 1783774, 1790190, 1796582, 1802949, 1809292, 1815611,
+    1821906, 1828177, 1834423, 1840646, 1846846, 1853021, 1859173, 1865301, 1871405, 1877486, 1883544, 1889578, 1895590, 1901578, 1907542, 1913484,
+    1919403, 1925299, 1931173, 1937023, 1942851, 1948656, 1954439, 1960199, 1965938, 1971653, 1977347, 1983018, 1988668, 1994295, 1999901, 2005485,
+    2011047, 2016588, 2022107, 2027604, 2033080, 2038535, 2043968, 2049381, 2054772, 2060142, 2065491, 2070820, 2076127, 2081414, 2086681, 2091927,
+    2097152};
+// The colour wheel of Baker et al., entry k as R | G << 8 | B << 16: RY 15, YG 6, GC 4, CB 11, BM 13, MR 6 entries
+#define VIS_RGB(r, g, b) ((uint32_t)(r) | ((uint32_t)(g) << 8) | ((uint32_t)(b) << 16))
+constexpr uint32_t kVisWheel[kVisWheelEntries] = {
+    VIS_RGB(255, 0, 0), VIS_RGB(255, 17, 0), VIS_RGB(255, 34, 0), VIS_RGB(255, 51, 0), VIS_RGB(255, 68, 0), VIS_RGB(255, 85, 0),
+    VIS_RGB(255, 102, 0), VIS_RGB(255, 119, 0), VIS_RGB(255, 136, 0), VIS_RGB(255, 153, 0), VIS_RGB(255, 170, 0), VIS_RGB(255, 187, 0),
+    VIS_RGB(255, 204, 0), VIS_RGB(255, 221, 0), VIS_RGB(255, 238, 0), VIS_RGB(255, 255, 0), VIS_RGB(213, 255, 0), VIS_RGB(170, 255, 0),
+    VIS_RGB(128, 255, 0), VIS_RGB(85, 255, 0), VIS_RGB(43, 255, 0), VIS_RGB(0, 255, 0), VIS_RGB(0, 255, 63), VIS_RGB(0, 255, 127),
+    VIS_RGB(0, 255, 191), VIS_RGB(0, 255, 255), VIS_RGB(0, 232, 255), VIS_RGB(0, 209, 255), VIS_RGB(0, 186, 255), VIS_RGB(0, 163, 255),
+    VIS_RGB(0, 140, 255), VIS_RGB(0, 116, 255), VIS_RGB(0, 93, 255), VIS_RGB(0, 70, 255), VIS_RGB(0, 47, 255), VIS_RGB(0, 24, 255),
+    VIS_RGB(0, 0, 255), VIS_RGB(19, 0, 255), VIS_RGB(39, 0, 255), VIS_RGB(58, 0, 255), VIS_RGB(78, 0, 255), VIS_RGB(98, 0, 255),
+    VIS_RGB(117, 0, 255), VIS_RGB(137, 0, 255), VIS_RGB(156, 0, 255), VIS_RGB(176, 0, 255), VIS_RGB(196, 0, 255), VIS_RGB(215, 0, 255),
+    VIS_RGB(235, 0, 255), VIS_RGB(255, 0, 255), VIS_RGB(255, 0, 213), VIS_RGB(255, 0, 170), VIS_RGB(255, 0, 128), VIS_RGB(255, 0, 85),
+    VIS_RGB(255, 0, 43)};
+#undef VIS_RGB
+constexpr uint32_t kVisRhoOut = 65537u;  // the radius of every vector out of range
+// steps 1 and 2: the usable pixel and its Q8 components
+OFDG_HD_FN bool vis_usable(float u, float v) { return fabsf(u) < 1048576.0f && fabsf(v) < 1048576.0f; }
+OFDG_HD_FN int vis_fixed(float u) { return (int)rintf(u * 256.0f); }
+OFDG_HD_FN unsigned long long vis_r2(int U, int V) { return (unsigned long long)((long long)U * U) + (unsigned long long)((long long)V * V); }
+// floor(sqrt(x)) for x < 2^58, exact.  On the device: the hardware's float root, one Newton step in double (the error falls
+// from 2^-22 of the root to far below 1) and one correction step either way; on the host the double root and the same step.
+OFDG_HD_FN uint32_t vis_isqrt(unsigned long long x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double xd = (double)x;
+  const float s = __builtin_amdgcn_sqrtf((float)xd);
+  const double g = (double)s;
+  const double g1 = g + __builtin_fma(-g, g, xd) * (double)(0.5f * __builtin_amdgcn_rcpf(s > 0.0f ? s : 1.0f));
+  uint32_t r = (uint32_t)g1;
+#else
+  uint32_t r = (uint32_t)sqrt((double)x);
+#endif
+  const unsigned long long rr = (unsigned long long)r * r;
+  return rr > x ? r - 1u : rr + 2ull * r + 1ull <= x ? r + 1u : r;
+}
+// floor((a << 16) / d) for a < 2^29 and 1 <= d < 2^30: exact where the quotient is at most `cap` (<= 65536), some value above
+// `cap` where it is larger.  On the device: the float quotient (off by less than 2^-21 of itself, so by less than 1 up to the
+// cap) and one correction step either way, as jitter_div; inv: the float reciprocal of d, which the caller may keep.
+OFDG_HD_FN uint32_t vis_div16(uint32_t a, uint32_t d, float inv, uint32_t cap) {
+  const unsigned long long num = (unsigned long long)a << 16;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float qf = (float)a * inv * 65536.0f;
+  const uint32_t q = (uint32_t)(qf < (float)(cap + 1u) ? qf : (float)(cap + 1u));
+  const long long r = (long long)num - (long long)((unsigned long long)q * d);
+  return q + (r >= (long long)d ? 1u : 0u) - (r < 0 ? 1u : 0u);
+#else
+  (void)inv;
+  const unsigned long long q = num / d;
+  return q > cap + 1u ? cap + 1u : (uint32_t)q;
+#endif
+}
+OFDG_HD_FN float vis_inv(uint32_t d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcpf((float)d);
+#else
+  (void)d;
+  return 0.0f;
+#endif
+}
+// step 3: M of a largest R2, and of max_flow
+OFDG_HD_FN uint32_t vis_scale_of(unsigned long long max_r2) {
+  const uint32_t m = vis_isqrt(max_r2);
+  return m > 1u ? m : 1u;
+}
+OFDG_HD_FN uint32_t vis_scale_fixed(float max_flow) { return (uint32_t)lrintf(max_flow * 256.0f); }
+// step 5: the angle of (U, V) as a turn fraction in Q16, y pointing down; A: the 257 entries of kVisAtan where they lie
+OFDG_HD_FN uint32_t vis_angle(int U, int V, const int32_t* A) {
+  const uint32_t ax = (uint32_t)(U < 0 ? -U : U), ay = (uint32_t)(V < 0 ? -V : V);
+  const uint32_t mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax, div = mx ? mx : 1u;
+  const uint32_t t = vis_div16(mn, div, vis_inv(div), 65536u);  // (mn <= mx: at most 65536)
+  const uint32_t i = t >> 8, fr = t & 255u, i1 = i < 256u ? i + 1u : 256u;
+  const int32_t a24 = A[i] + (((A[i1] - A[i]) * (int32_t)fr + 128) >> 8);
+  const int32_t o = (a24 + 128) >> 8;
+  int32_t b = ax >= ay ? o : 16384 - o;
+  b = U < 0 ? 32768 - b : b;
+  b = V < 0 ? (65536 - b) & 65535 : b;
+  return (uint32_t)b;
+}
+// steps 6 and 7 for one channel: w0, w1 the two wheel entries' bytes, f the fraction between them in Q16
+OFDG_HD_FN uint32_t vis_channel(uint32_t w0, uint32_t w1, uint32_t f, uint32_t rho) {
+  const uint32_t c16 = w0 * (65536u - f) + w1 * f;
+  if (rho > 65536u) return (3u * c16) >> 18;
+  return (uint32_t)(((16711680ll << 16) - (long long)rho * (long long)(16711680u - c16)) >> 32);
+}
+// Steps 2 and 4 to 8 of a usable pixel: R | G << 8 | B << 16.  M: the scale, inv_m: vis_inv(M); wheel: the 55 entries of
+// kVisWheel where they lie.
+OFDG_HD_FN uint32_t vis_pixel(float u, float v, uint32_t M, float inv_m, bool dim, const int32_t* A, const uint32_t* wheel) {
+  const int U = vis_fixed(u), V = vis_fixed(v);
+  const uint32_t Rq = vis_isqrt(vis_r2(U, V));
+  const uint32_t q = vis_div16(Rq, M, inv_m, 65536u);
+  const uint32_t rho = q > kVisRhoOut ? kVisRhoOut : q;
+  const uint32_t fk = vis_angle(U, V, A) * 54u, k0 = fk >> 16, f = fk & 65535u;
+  const uint32_t e0 = wheel[k0], e1 = wheel[k0 + 1u];
+  uint32_t R = vis_channel(e0 & 255u, e1 & 255u, f, rho), G = vis_channel((e0 >> 8) & 255u, (e1 >> 8) & 255u, f, rho), B = vis_channel(e0 >> 16, e1 >> 16, f, rho);
+  if (dim) { R >>= 1; G >>= 1; B >>= 1; }
+  return R | (G << 8) | (B << 16);
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* vis_plane_size(const DevVisJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+inline bool vis_needs_work(const DevVisJob& j) { return j.norm != OFDG_VIS_NORM_FIXED; }
+// The argument rules ofdg_flow_vis and ofdg_host_flow_vis share: the first rule broken, or nullptr.  width, height: what
+// vis_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+inline const char* vis_arg_error(const DevVisJob* j, int n, int width, int height, bool with_work) {
+  if (!j) return "job is NULL";
+  if (!j->flow) return "flow is NULL";
+  if (!j->dst) return "dst is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (const char* why = flow_occ_fmt_error(j->flow_fmt, j->occ != nullptr, j->occ_fmt)) return why;
+  if (j->layout != OFDG_VIS_PLANAR_BGR && j->layout != OFDG_VIS_HWC_RGB) return "layout must be OFDG_VIS_PLANAR_BGR or OFDG_VIS_HWC_RGB";
+  if (j->norm != OFDG_VIS_NORM_FIXED && j->norm != OFDG_VIS_NORM_SAMPLE && j->norm != OFDG_VIS_NORM_BATCH)
+    return "norm must be OFDG_VIS_NORM_FIXED, OFDG_VIS_NORM_SAMPLE or OFDG_VIS_NORM_BATCH";
+  if (j->flags & ~OFDG_VIS_DIM_OCC) return "flags holds unknown bits";
+  if (j->reserved != 0) return "reserved must be 0";
+  for (int k = 0; k < 5; ++k)
+    if (j->reserved2[k] != 0) return "reserved2 must be 0";
+  if ((j->flags & OFDG_VIS_DIM_OCC) && !j->occ) return "flags: OFDG_VIS_DIM_OCC needs occ";
+  if (j->norm == OFDG_VIS_NORM_FIXED && !(j->max_flow >= 0.00390625f && j->max_flow <= 1048576.0f)) return "max_flow must lie in [2^-8, 2^20]";
+  const bool work = with_work && vis_needs_work(*j);
+  if (work && !j->work) return "work is NULL where norm is not OFDG_VIS_NORM_FIXED";
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[5];
+  int nr = 0;
+  const unsigned long long plane = (unsigned long long)n * width * height;
+  r[nr++] = Range{(uintptr_t)j->flow, (uintptr_t)j->flow + (uintptr_t)(2ull * plane * fmt_elem_bytes(j->flow_fmt)), false};
+  if (j->occ) r[nr++] = Range{(uintptr_t)j->occ, (uintptr_t)j->occ + (uintptr_t)(plane * fmt_elem_bytes(j->occ_fmt)), false};
+  r[nr++] = Range{(uintptr_t)j->dst, (uintptr_t)j->dst + (uintptr_t)(3ull * plane), true};
+  if (j->rows_out) r[nr++] = Range{(uintptr_t)j->rows_out, (uintptr_t)j->rows_out + (uintptr_t)n * sizeof(DevVisRow), true};
+  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(unsigned long long), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.

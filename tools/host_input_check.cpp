@@ -23,6 +23,9 @@
 //   host_input_check jitter             ofdg_host_jitter, ofdg_jitter_draw and ofdg_host_jitter_hue on exactly sized heap buffers:
 //                                       every format pair, copying and in place, one frame and both, odd sizes, hostile given
 //                                       records and drawn ones, every refusal
+//   host_input_check flow_vis           ofdg_host_flow_vis and ofdg_host_flow_vis_tables on exactly sized heap buffers: the test
+//                                       sizes, both flow formats and layouts, the three norms and both ends of max_flow, with
+//                                       and without dimming, extreme flows and any bit pattern, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -763,14 +766,124 @@ int jitter() {
   return refused == 24 ? 0 : 1;
 }
 
+// ofdg_host_flow_vis and ofdg_host_flow_vis_tables on heap buffers of exactly the planes' sizes (a byte read or written beside
+// one is a report): float32 and binary16 flows that hold zeros, every octant, NaN, both infinities, +-2^20, the largest usable
+// value and random bit patterns (a signed overflow in the Q8 components, the roots or the colour is a report), both layouts,
+// the three norms and both ends of max_flow, without a map and dimmed by a uint8 and a float32 one, on 8x2, 24x6, 72x40 and
+// 264x200 with three samples; then every refusal.
+int flow_vis() {
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 4; ++size) {
+    const int W = size == 0 ? 8 : size == 1 ? 24 : size == 2 ? 72 : 264, H = size == 0 ? 2 : size == 1 ? 6 : size == 2 ? 40 : 200, n = 3;
+    const size_t px = (size_t)W * H;
+    for (int half = 0; half < 2; ++half) {
+      std::vector<uint8_t> flow(n * 2 * px * (half ? 2 : 4));
+      uint32_t x = 4242u + (uint32_t)size;
+      const float special[] = {0.0f, -0.0f, 3.0f, -3.0f, NAN, INFINITY, -INFINITY, 1048576.0f, -1048576.0f, 1048575.9375f, -1048575.9375f, 0.001953125f, 65504.0f, 1e-30f, 3.4e38f};
+      const uint16_t special_h[] = {0x0000, 0x8000, 0x4200, 0xC200, 0x7E00, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF, 0x0001, 0x8001, 0x1800, 0x3C00, 0x03FF, 0xFE00};
+      for (size_t e = 0; e < n * 2 * px; ++e) {
+        x = x * 1664525u + 1013904223u;
+        if (half) {
+          const uint16_t h = (e % 3) == 0 ? special_h[(x >> 20) % 15] : (uint16_t)(x >> 16);
+          std::memcpy(flow.data() + 2 * e, &h, 2);
+        } else {
+          float v = (e % 3) == 0 ? special[(x >> 20) % 15] : (e % 3) == 1 ? (float)(int)(x >> 20) * 0.37f - 700.0f : 0.0f;
+          if ((e % 7) == 3) std::memcpy(&v, &x, 4);  // any bit pattern
+          std::memcpy(flow.data() + 4 * e, &v, 4);
+        }
+      }
+      if (size == 1) std::memset(flow.data() + flow.size() / 3, 0xFF, flow.size() / 3);  // sample 1: all NaN, M = 1
+      for (int occ_kind = 0; occ_kind < 3; ++occ_kind) {
+        std::vector<uint8_t> occ(occ_kind == 1 ? n * px : occ_kind == 2 ? n * px * 4 : 0);
+        for (size_t e = 0; e < occ.size(); ++e) { x = x * 1664525u + 1013904223u; occ[e] = (x >> 24) & 1 ? (uint8_t)(x >> 16) : 0; }  // (float32: any pattern, NaN among them)
+        for (int layout = 0; layout < 2; ++layout)
+          for (int norm = 0; norm < 4; ++norm) {
+            std::vector<uint8_t> dst(n * 3 * px, 0xA5);
+            std::vector<ofdg_flow_vis_row> rows(n);
+            struct ofdg_flow_vis_job job;
+            std::memset(&job, 0, sizeof job);
+            job.flow = flow.data(); job.occ = occ_kind ? occ.data() : nullptr; job.dst = dst.data(); job.rows_out = rows.data();
+            job.flow_fmt = half ? OFDG_FMT_F16 : OFDG_FMT_F32; job.occ_fmt = occ_kind == 1 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+            job.layout = layout; job.norm = norm == 3 ? OFDG_VIS_NORM_FIXED : norm; job.flags = occ_kind ? OFDG_VIS_DIM_OCC : 0;
+            job.max_flow = norm == 3 ? 1048576.0f : norm == 0 ? 0.00390625f : NAN;
+            const int rc = ofdg_host_flow_vis(&job, n, W, H);
+            if (rc) { std::printf("flow_vis: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+            ++calls;
+            sum = sum * 31 + fnv1a(dst.data(), dst.size());
+            sum = sum * 31 + fnv1a((const uint8_t*)rows.data(), rows.size() * sizeof(ofdg_flow_vis_row));
+            for (int i = 0; i < n; ++i)
+              if (rows[i].scale_q8 < 1u || rows[i].scale_q8 > (1u << 29) || rows[i].reserved != 0u || (job.norm == OFDG_VIS_NORM_FIXED && rows[i].max_r2_q16 != 0u)) {
+                std::printf("flow_vis: a row left its bounds\n");
+                return 1;
+              }
+          }
+      }
+    }
+  }
+  {  // the tables, into arrays of exactly their sizes
+    std::vector<int32_t> atan_q24(257);
+    std::vector<uint8_t> wheel(55 * 3);
+    if (ofdg_host_flow_vis_tables(atan_q24.data(), reinterpret_cast<uint8_t(*)[3]>(wheel.data())) != OFDG_OK || atan_q24[256] != 2097152 || wheel[164] != 43) {
+      std::printf("flow_vis: the tables\n");
+      return 1;
+    }
+    ++calls;
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> flow((size_t)n * 2 * W * H * 4, 0), occ((size_t)n * W * H, 1), dst((size_t)n * 3 * W * H + 64, 0xA5), out((size_t)n * 16, 0xA5);
+    struct ofdg_flow_vis_job good;
+    std::memset(&good, 0, sizeof good);
+    good.flow = flow.data(); good.occ = occ.data(); good.dst = dst.data(); good.rows_out = (ofdg_flow_vis_row*)out.data();
+    good.flow_fmt = OFDG_FMT_F32; good.occ_fmt = OFDG_FMT_U8; good.norm = OFDG_VIS_NORM_SAMPLE; good.flags = OFDG_VIS_DIM_OCC;
+    const auto refuse = [&](struct ofdg_flow_vis_job j, int ns, int w, int h) {
+      if (ofdg_host_flow_vis(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_flow_vis: ", 20) == 0) ++refused;
+      else std::printf("flow_vis: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_flow_vis_job j;
+    if (ofdg_host_flow_vis(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.width = W + 8; j.height = H; refuse(j, n, W, H);
+    j = good; j.flow = nullptr; refuse(j, n, W, H);
+    j = good; j.dst = nullptr; refuse(j, n, W, H);
+    j = good; j.flow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.occ_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.layout = 2; refuse(j, n, W, H);
+    j = good; j.norm = 3; refuse(j, n, W, H);
+    j = good; j.flags = 2; refuse(j, n, W, H);
+    j = good; j.reserved = 1; refuse(j, n, W, H);
+    j = good; j.reserved2[4] = 1; refuse(j, n, W, H);
+    j = good; j.occ = nullptr; refuse(j, n, W, H);
+    j = good; j.norm = OFDG_VIS_NORM_FIXED; j.max_flow = NAN; refuse(j, n, W, H);
+    j = good; j.norm = OFDG_VIS_NORM_FIXED; j.max_flow = 0.0f; refuse(j, n, W, H);
+    j = good; j.norm = OFDG_VIS_NORM_FIXED; j.max_flow = 2097152.0f; refuse(j, n, W, H);
+    j = good; j.dst = flow.data() + 16; refuse(j, n, W, H);
+    j = good; j.dst = occ.data(); refuse(j, n, W, H);
+    j = good; j.rows_out = (ofdg_flow_vis_row*)(dst.data() + 16); refuse(j, n, W, H);
+    uint8_t wheel[55][3];
+    int32_t atan_q24[257];
+    if (ofdg_host_flow_vis_tables(nullptr, wheel) == OFDG_EINVAL && ofdg_host_flow_vis_tables(atan_q24, nullptr) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; });
+    if (!clean) { std::printf("flow_vis: a refusal wrote something\n"); return 1; }
+    if (ofdg_host_flow_vis(&good, n, W, H) != OFDG_OK) { std::printf("flow_vis: the valid call failed\n"); return 1; }
+  }
+  std::printf("flow_vis calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 24 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
   if (argc >= 2 && std::strcmp(argv[1], "reproject") == 0) return reproject();
   if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
   if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
+  if (argc >= 2 && std::strcmp(argv[1], "flow_vis") == 0) return flow_vis();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | flow_vis\n", argv[0]);
   return 2;
 }
