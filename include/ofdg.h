@@ -1197,6 +1197,102 @@ int ofdg_host_flow_vis(const struct ofdg_flow_vis_job* job, int n_samples, int w
 int ofdg_host_flow_vis_tables(int32_t atan_q24[257], uint8_t wheel_rgb[55][3]);
 
 /*
+ * Flow error: the end-point error (EPE) of an estimated flow against the ground truth, split the way Sintel and KITTI report
+ * it - matched / unmatched pixels by the occlusion map, three bands of ground-truth speed, three bands of distance to the next
+ * motion boundary (the dist2 plane of ofdg_boundaries) -, with the 1 / 3 / 5 px and KITTI Fl outlier counts, a histogram of
+ * the error, the worst pixel, and optionally the error as a plane and as the KITTI devkit's colour picture.  Behind the call
+ * that made the ground truth, on the same stream.  Everything below is integers behind one rounding of each flow component:
+ * the kernel, ofdg_host_flow_error and the numpy restatement of the tests give the same bytes, and the rows are the same bits
+ * on every run, so that curves compare across runs and ranks and an epoch accumulates on the device.
+ *
+ * gt: [n,2,height,width] of gt_fmt, OFDG_FMT_F32 (16-byte aligned) or OFDG_FMT_F16 (8-byte).  est: the same shape of est_fmt,
+ * OFDG_FMT_F32 (16-byte), OFDG_FMT_F16 or OFDG_FMT_BF16 (8-byte).  occ: NULL, or the [n,1,height,width] map of occ_fmt,
+ * OFDG_FMT_U8 (4-byte) or OFDG_FMT_F32 (16-byte), as in ofdg_flow_stats.  dist2: NULL, or the uint8 [n,1,height,width] dist2
+ * plane of ofdg_boundaries of this flow (4-byte).  At least one of rows, epe and picture is set.  width = height = 0: the
+ * context's frame; otherwise width a multiple of 8 and at least 8, height even and at least 2.
+ *
+ * A pixel is (x, y) of sample i; idx = y * width + x, under OFDG_ERR_ONE_ROW idx = (i * height + y) * width + x.
+ * 1. Widen and scale.  ug, vg are widened to float32.  The components of est are widened to float32 (exact for binary16 and
+ *    bfloat16), then each is fl32(e * est_scale).
+ * 2. Unusable ground truth.  Not (fabsf(ug) < 1048576.0f && fabsf(vg) < 1048576.0f): n_bad_gt += 1 and nothing else (rule 2
+ *    of ofdg_flow_stats: NaN, +-inf, an overflowed half).
+ * 3. Unusable estimate.  Otherwise, the scaled estimate fails the same test: n_bad_est += 1 and nothing else - a diverged
+ *    network is a count, not NaN metrics.
+ * 4. An unusable pixel of either kind writes epe = -1 and the picture (0, 0, 0).
+ * 5. Fixed point.  Ug = (int)rintf(ug * 256.0f), likewise Vg, Ue, Ve (|.| <= 2^28).  E2 = (Ue - Ug)^2 + (Ve - Vg)^2 in 64
+ *    bits, Eq = isqrt(E2) (floor; Q8 pixels, below 2^30).  G2 = Ug^2 + Vg^2, Gq = isqrt(G2).
+ * 6. Cell.  hidden = 1 when occ is given and occ != 0, else 0 (a float32 map is compared with != 0.0f; a NaN counts as
+ *    hidden).  Speed band: the number of k in {0, 1} with Gq >= S_k, S_k = lrintf(speed_px[k] * 256.0f).  Distance band: the
+ *    number of k in {0, 1} with dist2 >= dist2_edge[k]; without a dist2 plane band 0.  OFDG_BND_FAR is in the last band.
+ * 7. cell[hidden][speed][distance]: n += 1, sum_epe_q8 += Eq, n_1px += (Eq > 256), n_3px += (Eq > 768), n_5px += (Eq > 1280),
+ *    n_fl += (Eq > 768 && 20 Eq > Gq) - KITTI's Fl outlier: more than 3 px and more than 5 % of the true length.
+ * 8. Row.  hist[b] += 1, b the number of k in 0..14 with Eq >= (16 << k) (edges 1/16, 1/8, ... 1024 px);
+ *    max_key = max(max_key, ((uint64)Eq << 32) | (0xFFFFFFFFu - idx)): the worst pixel, the first of equals.  max_key == 0:
+ *    nothing was counted.
+ * 9. epe.  OFDG_FMT_F32: fl32((float)Eq * 0.00390625f), the conversion to nearest even; OFDG_FMT_F16: that float32 rounded once
+ *    to nearest even (inf above 65504).
+ * 10. picture, the KITTI devkit's error colours.  bin = the number of j in 0..8 with Eq >= (48 << j) && 320 Eq >= (Gq << j), in
+ *    64 bits - the devkit's min(E / 3, 20 E / |gt|) against its edges 1/16 ... 16; Gq = 0 leaves E / 3 alone.  (R, G, B) of
+ *    bins 0..9, a literal table whose 30 bytes sum to 4523: (49,54,149) (69,117,180) (116,173,209) (171,217,233) (224,243,248)
+ *    (254,224,144) (253,174,97) (244,109,67) (215,48,39) (165,0,38).  With OFDG_ERR_DIM_OCC and a hidden pixel every channel
+ *    is shifted right by 1.  A pixel is an Fl outlier exactly when its bin is 5 or more, except at equality on an edge: Fl
+ *    is strict, the bins are not.
+ * With est_scale 1: gt (10, 0), est (10, 0) is Eq 0, bin 0; gt (0, 0), est (3, 0) Eq 768, bin 5, no outlier, not in n_3px;
+ * gt (100, 0), est (104, 0) Eq 1024, bin 4, in n_3px, not in n_fl; gt (100, 0), est (106, 0) in n_fl, bin 5.  Eq / 256 is
+ * within 2.5 / 256 px of the float64 EPE of the same inputs.
+ *
+ * Without OFDG_ERR_ACCUMULATE the call first writes every byte of its rows as zero on `stream`, then reduces; with it the rows
+ * are added to (the key: the maximum), and an all-zero row is the identity.  Asynchronous on `stream`; OFDG_STREAM_OWN as in
+ * ofdg_flow_stats.  At most one clearing and one kernel; integer atomics only, so no bit depends on arrival order.  It reads
+ * no record of the context and works in every mode.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, gt or est; no output set;
+ * n_samples < 1; a size that breaks the rule; 3 * width * height of 2^32 and more; OFDG_ERR_ONE_ROW with n * height * width of
+ * 2^32 and more; another gt_fmt, est_fmt, occ_fmt (where occ is set), epe_fmt (where epe is set), layout or flag bit; a
+ * non-zero reserved field; OFDG_ERR_DIM_OCC without occ or without picture; est_scale NaN or |est_scale| outside [2^-10,
+ * 2^10]; speed_px not 0 < speed_px[0] <= speed_px[1] <= 2^20 (a NaN fails); where dist2 is set, dist2_edge not 1 <=
+ * dist2_edge[0] <= dist2_edge[1] <= 255; a misaligned pointer (rows: 8-byte; epe, picture: 16-byte); a written range (rows,
+ * epe, picture) that overlaps any other range of the job; OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: an estimate at another resolution, angular error, an outlier mask plane, radii above 15 for the distance
+ * bands (the limit of ofdg_boundaries), percentiles, flow1's estimate in the same call, packing these planes, an in-place
+ * form.
+ */
+#define OFDG_ERR_ACCUMULATE 1   /* add to the rows instead of overwriting them (max for the key) */
+#define OFDG_ERR_ONE_ROW    2   /* all n samples reduce into rows[0] */
+#define OFDG_ERR_DIM_OCC    4   /* picture: pixels with occ != 0 at half brightness, as the KITTI devkit draws them; occ required */
+#define OFDG_FLOW_ERROR_HIST_BINS 16
+typedef struct ofdg_flow_error_cell { uint64_t sum_epe_q8; uint32_t n, n_1px, n_3px, n_5px, n_fl, reserved; } ofdg_flow_error_cell;  /* 32 bytes */
+typedef struct ofdg_flow_error_row {      /* 672 bytes, no padding, 8-byte aligned */
+  ofdg_flow_error_cell cell[2][3][3];     /* [hidden][speed band][distance band] */
+  uint32_t hist[OFDG_FLOW_ERROR_HIST_BINS];
+  uint64_t max_key;
+  uint32_t n_bad_gt, n_bad_est;
+  uint32_t reserved[4];
+} ofdg_flow_error_row;
+struct ofdg_flow_error_job {              /* 128 bytes */
+  const void* gt;                         /* [n,2,H,W], gt_fmt: OFDG_FMT_F32 (16-byte aligned) or OFDG_FMT_F16 (8-byte) */
+  const void* est;                        /* [n,2,H,W], est_fmt: OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16 (what autocast nets emit) */
+  const void* occ;                        /* NULL, or [n,1,H,W], occ_fmt OFDG_FMT_U8 (4-byte) / OFDG_FMT_F32 (16-byte), as in ofdg_flow_stats */
+  const uint8_t* dist2;                   /* NULL, or [n,1,H,W] uint8: the dist2 plane of ofdg_boundaries for this flow (4-byte) */
+  ofdg_flow_error_row* rows;              /* DEVICE, n rows (one with ONE_ROW), 8-byte aligned, or NULL */
+  void* epe;                              /* NULL, or [n,1,H,W] of epe_fmt OFDG_FMT_F32 / OFDG_FMT_F16, 16-byte aligned */
+  void* picture;                          /* NULL, or uint8 [n,3,H,W] (OFDG_VIS_PLANAR_BGR) / [n,H,W,3] (OFDG_VIS_HWC_RGB), 16-byte aligned */
+  int32_t width, height, gt_fmt, est_fmt, occ_fmt, epe_fmt, layout, flags;
+  float   est_scale;                      /* the estimate is multiplied by it first (networks that predict flow / 20); 1.0f: as is */
+  float   speed_px[2];                    /* edges of the speed bands, pixels */
+  int32_t dist2_edge[2];                  /* edges of the distance bands, in units of dist2 */
+  int32_t reserved[5];
+};
+int ofdg_flow_error(ofdg_ctx* ctx, const struct ofdg_flow_error_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and rows in host memory, no alignment asked of any
+ * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_flow_error(const struct ofdg_flow_error_job* job, int n_samples, int width, int height);
+/* The colour table of step 10 as (R, G, B), copied out (pure, no GPU).  OFDG_EINVAL for a NULL pointer. */
+int ofdg_host_flow_error_colours(uint8_t rgb[10][3]);
+
+/*
  * Motion blur: every pixel of image0 and / or image1 becomes a weighted mean of its frame along a short segment through the
  * pixel, whose direction and length are the pixel's own flow times the sample's shutter - the fraction of the inter-frame
  * interval the exposure lasts.  The exposure is centred on the frame's instant, so the segment is symmetric about the pixel

@@ -116,6 +116,7 @@ EXPORTS = [
     "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
     "ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw", "ofdg_host_jitter_hue",
     "ofdg_flow_vis", "ofdg_host_flow_vis", "ofdg_host_flow_vis_tables",
+    "ofdg_flow_error", "ofdg_host_flow_error", "ofdg_host_flow_error_colours",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -1342,6 +1343,218 @@ def flow_vis_legend(size=151):
     return np.ascontiguousarray(picture[0, :size, :size])
 
 
+# flow error (ofdg_flow_error_row / struct ofdg_flow_error_job / ofdg_flow_error, include/ofdg.h)
+ERR_ACCUMULATE, ERR_ONE_ROW, ERR_DIM_OCC = 1, 2, 4         # OFDG_ERR_*
+FLOW_ERROR_HIST_BINS = 16                                  # OFDG_FLOW_ERROR_HIST_BINS
+FLOW_ERROR_OUTPUTS = ("rows", "epe", "picture")
+# dtype name -> format code of an estimate; a numpy array holds bfloat16 as uint16 bit patterns
+_EST_CODES = {"float32": FMT_F32, "float16": FMT_F16, "bfloat16": FMT_BF16, "uint16": FMT_BF16}
+_EPE_CODES = {"float32": FMT_F32, "float16": FMT_F16}
+
+
+class FlowErrorCell(C.Structure):
+    """ofdg_flow_error_cell (32 bytes)."""
+    _fields_ = [("sum_epe_q8", C.c_uint64), ("n", C.c_uint32), ("n_1px", C.c_uint32), ("n_3px", C.c_uint32), ("n_5px", C.c_uint32),
+                ("n_fl", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FlowErrorRow(C.Structure):
+    """ofdg_flow_error_row (672 bytes): cell[hidden][speed band][distance band], the histogram, the worst pixel's key and the
+    unusable counts."""
+    _fields_ = [("cell", FlowErrorCell * 3 * 3 * 2), ("hist", C.c_uint32 * FLOW_ERROR_HIST_BINS), ("max_key", C.c_uint64),
+                ("n_bad_gt", C.c_uint32), ("n_bad_est", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class FlowErrorJob(C.Structure):
+    """struct ofdg_flow_error_job (128 bytes)."""
+    _fields_ = [("gt", C.c_void_p), ("est", C.c_void_p), ("occ", C.c_void_p), ("dist2", C.c_void_p), ("rows", C.c_void_p), ("epe", C.c_void_p),
+                ("picture", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("gt_fmt", C.c_int32), ("est_fmt", C.c_int32),
+                ("occ_fmt", C.c_int32), ("epe_fmt", C.c_int32), ("layout", C.c_int32), ("flags", C.c_int32), ("est_scale", C.c_float),
+                ("speed_px", C.c_float * 2), ("dist2_edge", C.c_int32 * 2), ("reserved", C.c_int32 * 5)]
+
+
+def _flow_error_row_dtype():
+    import numpy as np
+    cell = np.dtype([("sum_epe_q8", "<u8"), ("n", "<u4"), ("n_1px", "<u4"), ("n_3px", "<u4"), ("n_5px", "<u4"), ("n_fl", "<u4"), ("reserved", "<u4")])
+    return np.dtype([("cell", cell, (2, 3, 3)), ("hist", "<u4", (FLOW_ERROR_HIST_BINS,)), ("max_key", "<u8"), ("n_bad_gt", "<u4"),
+                     ("n_bad_est", "<u4"), ("reserved", "<u4", (4,))])
+
+
+def flow_error_numpy(rows):
+    """Rows of Generator.flow_error / host_flow_error - a torch tensor or numpy array of uint8 [m,672] (or any array of 672
+    bytes a row; synchronise first) - as a numpy structured array [m]: cell[hidden][speed band][distance band] with
+    sum_epe_q8 (1/256 px), n, n_1px, n_3px, n_5px, n_fl; hist [16]; max_key; n_bad_gt; n_bad_est."""
+    import numpy as np
+    a = rows.detach().cpu().numpy() if hasattr(rows, "detach") else np.asarray(rows)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _flow_error_row_dtype():
+        return a.reshape(-1)
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % C.sizeof(FlowErrorRow):
+        raise ValueError("rows must be %d bytes each, got %d bytes" % (C.sizeof(FlowErrorRow), raw.size))
+    return raw.view(_flow_error_row_dtype())
+
+
+def flow_error_format(gt, est, occ=None, dist2=None, rows=None, epe=None, picture=None, height=None, width=None, layout="planar_bgr",
+                      one_row=False):
+    """(n, gt code, est code, occ code, epe code) of the planes of Generator.flow_error / host_flow_error for planes of height
+    x width: gt float32 or float16 [n,2,H,W], est float32, float16 or bfloat16 (uint16 for a numpy array) of that shape, occ
+    None or float32 / uint8 [n,1,H,W], dist2 None or uint8 [n,1,H,W], rows None or uint8 [n,672] ([1,672] with one_row), epe
+    None or float32 / float16 [n,1,H,W], picture None or uint8 in `layout`.  Raises ValueError for anything else.  Looks at
+    dtype and shape only (works on CPU tensors)."""
+    n, gcode, ocode = _check_flow_occ(gt, occ, height, width)
+    _check_plane("est", est, _EST_CODES, (n, 2, height, width), says="float32, float16 or bfloat16")
+    if dist2 is not None:
+        _check_plane("dist2", dist2, ("uint8",), (n, 1, height, width))
+    if rows is not None:
+        _check_plane("rows", rows, ("uint8",), (1 if one_row else n, C.sizeof(FlowErrorRow)))
+    if epe is not None:
+        _check_plane("epe", epe, _EPE_CODES, (n, 1, height, width))
+    if picture is not None:
+        _check_plane("picture", picture, ("uint8",), flow_vis_shape(n, height, width, layout))
+    return n, gcode, _EST_CODES[_dtype_name(est)], ocode, FMT_F32 if epe is None else _EPE_CODES[_dtype_name(epe)]
+
+
+def _flow_error_job(planes, ptr, size, codes, est_scale, speed_px, dist2_edges, layout, dim_occ, accumulate, one_row):
+    """The job of Generator.flow_error / host_flow_error; planes: (gt, est, occ, dist2, rows, epe, picture).  Raises ValueError
+    for a name that is no layout."""
+    if layout not in VIS_LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (", ".join(VIS_LAYOUTS), layout))
+    job = FlowErrorJob()
+    job.gt, job.est, job.occ, job.dist2, job.rows, job.epe, job.picture = (ptr(t) for t in planes)
+    job.height, job.width = size
+    job.gt_fmt, job.est_fmt, job.occ_fmt, job.epe_fmt = codes
+    job.layout = VIS_LAYOUTS[layout]
+    job.flags = (ERR_ACCUMULATE if accumulate else 0) | (ERR_ONE_ROW if one_row else 0) | (ERR_DIM_OCC if dim_occ else 0)
+    job.est_scale = float(est_scale)
+    job.speed_px[0], job.speed_px[1] = float(speed_px[0]), float(speed_px[1])
+    job.dist2_edge[0], job.dist2_edge[1] = int(dist2_edges[0]), int(dist2_edges[1])
+    return job
+
+
+def _flow_error_outputs(outputs):
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in FLOW_ERROR_OUTPUTS for o in outputs):
+        raise ValueError("outputs must name some of %s, got %r" % (", ".join(FLOW_ERROR_OUTPUTS), outputs))
+    return outputs
+
+
+def alloc_flow_error(n, height, width, outputs=("rows",), epe_dtype=None, layout="planar_bgr", one_row=False, device="cuda"):
+    """The outputs of Generator.flow_error for n samples of height x width, as a dict by the names in outputs: "rows" uint8
+    [n,672] ([1,672] with one_row), zeroed - an all-zero row is what accumulate=True starts from; flow_error_numpy reads them
+    -, "epe" [n,1,H,W] of epe_dtype (torch.float32, the default, or torch.float16) and "picture" uint8 [n,3,H,W] ("planar_bgr")
+    or [n,H,W,3] ("hwc_rgb"), not filled: the call writes every element."""
+    import torch
+    outputs = _flow_error_outputs(outputs)
+    epe_dtype = torch.float32 if epe_dtype is None else epe_dtype
+    if epe_dtype not in (torch.float32, torch.float16):
+        raise ValueError("epe_dtype must be torch.float32 or torch.float16, got %s" % epe_dtype)
+    if n < 1:
+        raise ValueError("alloc_flow_error needs n >= 1, got %d" % n)
+    out = {}
+    if "rows" in outputs:
+        out["rows"] = torch.zeros((1 if one_row else n, C.sizeof(FlowErrorRow)), dtype=torch.uint8, device=device)
+    if "epe" in outputs:
+        out["epe"] = torch.empty((n, 1, height, width), dtype=epe_dtype, device=device)
+    if "picture" in outputs:
+        out["picture"] = torch.empty(flow_vis_shape(n, height, width, layout), dtype=torch.uint8, device=device)
+    return out
+
+
+def host_flow_error(gt, est, occ=None, dist2=None, outputs=("rows",), rows=None, epe_dtype=None, est_scale=1.0, speed_px=(10, 40),
+                    dist2_edges=(26, 101), layout="planar_bgr", dim_occ=False, accumulate=False, one_row=False):
+    """ofdg_host_flow_error (no GPU): the error of a HOST estimate - float32, float16 or, as uint16 bit patterns, bfloat16
+    [n,2,H,W] - against the ground truth gt, float32 or float16 of that shape; occ None or the float32 / uint8 [n,1,H,W] map,
+    dist2 None or the uint8 [n,1,H,W] dist2 plane of host_boundaries.  Returns a dict by the names in outputs: "rows" the
+    structured array of flow_error_numpy ([n], [1] with one_row), "epe" float32 (or np.float16 with epe_dtype) [n,1,H,W],
+    "picture" uint8 in `layout`.  rows: the array a former call returned, to add to with accumulate=True."""
+    import numpy as np
+    outputs = _flow_error_outputs(outputs)
+    gt, est = np.ascontiguousarray(gt), np.ascontiguousarray(est)
+    occ = None if occ is None else np.ascontiguousarray(occ)
+    dist2 = None if dist2 is None else np.ascontiguousarray(dist2)
+    if gt.ndim != 4:
+        raise ValueError("gt must be [n,2,H,W], got %s" % (gt.shape,))
+    height, width = gt.shape[2:]
+    n, m = gt.shape[0], 1 if one_row else gt.shape[0]
+    if rows is not None:
+        if rows.dtype != _flow_error_row_dtype() or rows.shape != (m,) or not rows.flags["C_CONTIGUOUS"]:
+            raise ValueError("rows must be a contiguous array of flow_error_numpy's dtype and shape %s" % ((m,),))
+        if "rows" not in outputs:
+            outputs += ("rows",)
+    elif accumulate:
+        raise ValueError("accumulate=True needs rows= to add to")
+    elif "rows" in outputs:
+        rows = np.zeros((m,), _flow_error_row_dtype())
+    epe = np.zeros((n, 1, height, width), np.float32 if epe_dtype is None else epe_dtype) if "epe" in outputs else None
+    picture = np.zeros(flow_vis_shape(n, height, width, layout), np.uint8) if "picture" in outputs else None
+    n, *codes = flow_error_format(gt, est, occ, dist2, None if rows is None else rows.view(np.uint8).reshape(m, -1), epe, picture, height, width,
+                                  layout, one_row)
+    job = _flow_error_job((gt, est, occ, dist2, rows, epe, picture), lambda a: None if a is None else a.ctypes.data, (0, 0), codes, est_scale,
+                          speed_px, dist2_edges, layout, dim_occ, accumulate, one_row)
+    _host_check(lib().ofdg_host_flow_error(C.byref(job), n, width, height))
+    return {k: v for k, v in (("rows", rows), ("epe", epe), ("picture", picture)) if v is not None}
+
+
+def flow_error_summary(rows):
+    """The metrics of rows of Generator.flow_error / host_flow_error (a tensor or an array; synchronise first), all rows added
+    up, as a dict of float64 computed from the integers: "n", "epe" (mean end-point error, pixels), "px1", "px3", "px5" (the
+    fractions of pixels whose error is above 1, 3 and 5 px) and "fl" (KITTI's Fl outlier fraction) over all counted pixels;
+    "visible" and "hidden" (Sintel's matched / unmatched), "speed" (a list: the three bands of ground-truth speed) and
+    "distance" (the three bands of distance to a motion boundary), each a dict of the same six or None where its n is 0 - as
+    are the overall five; "n_bad_gt", "n_bad_est", "hist" (int64 [16]); "worst_epe" (pixels), "worst_index" (the pixel's idx)
+    and "worst_row" (the row that holds it), None where nothing was counted."""
+    import numpy as np
+    r = flow_error_numpy(rows)
+    cells = {k: r["cell"][k].astype(np.uint64).sum(axis=0, dtype=np.uint64) for k in ("sum_epe_q8", "n", "n_1px", "n_3px", "n_5px", "n_fl")}  # [2,3,3]
+
+    def group(index):
+        s = {k: int(v[index].sum(dtype=np.uint64)) for k, v in cells.items()}
+        if s["n"] == 0:
+            return None
+        n = float(s["n"])
+        return {"n": s["n"], "epe": s["sum_epe_q8"] / 256.0 / n, "px1": s["n_1px"] / n, "px3": s["n_3px"] / n, "px5": s["n_5px"] / n, "fl": s["n_fl"] / n}
+
+    out = group(Ellipsis) or {"n": 0, "epe": None, "px1": None, "px3": None, "px5": None, "fl": None}
+    out["visible"], out["hidden"] = group((0,)), group((1,))
+    out["speed"] = [group((slice(None), k)) for k in range(3)]
+    out["distance"] = [group((slice(None), slice(None), k)) for k in range(3)]
+    out["n_bad_gt"], out["n_bad_est"] = int(r["n_bad_gt"].sum(dtype=np.uint64)), int(r["n_bad_est"].sum(dtype=np.uint64))
+    out["hist"] = r["hist"].astype(np.int64).sum(axis=0)
+    key = r["max_key"]
+    out["worst_epe"] = out["worst_index"] = out["worst_row"] = None
+    if len(key) and int(key.max()) != 0:
+        eq = key >> np.uint64(32)
+        idx = 0xFFFFFFFF - (key & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        w = min((k for k in range(len(key)) if key[k] != 0), key=lambda k: (-int(eq[k]), k))  # the largest error, the first row of equals
+        out["worst_epe"], out["worst_index"], out["worst_row"] = int(eq[w]) / 256.0, int(idx[w]), int(w)
+    return out
+
+
+def host_flow_error_colours():
+    """ofdg_host_flow_error_colours (pure, no GPU): the uint8 [10,3] colour table of the error picture as R, G, B."""
+    import numpy as np
+    rgb = np.zeros((10, 3), np.uint8)
+    _host_check(lib().ofdg_host_flow_error_colours(_hptr(rgb)))
+    return rgb
+
+
+def flow_error_legend(cell=None):
+    """The colour bar to put beside an error picture (no GPU): (colours, edges) - the ten colours of the KITTI devkit as uint8
+    [10,3] (R, G, B), bin 0 first, and the nine edges between them as float64 [9], 1/16 ... 16: bin k holds min(E / 3 px,
+    E / (5 % of |gt|)) in [edges[k-1], edges[k]), so a pixel from bin 5 on is an Fl outlier.  cell=(height, width): the colours
+    as a picture instead, uint8 [height, 10 * width, 3]."""
+    import numpy as np
+    colours = host_flow_error_colours()
+    edges = 2.0 ** np.arange(-4, 5, dtype=np.float64)
+    if cell is not None:
+        h, w = int(cell[0]), int(cell[1])
+        if h < 1 or w < 1:
+            raise ValueError("cell must be (height, width) of at least 1 x 1, got %r" % (cell,))
+        colours = np.ascontiguousarray(np.broadcast_to(np.repeat(colours, w, axis=0)[None], (h, 10 * w, 3)))
+    return colours, edges
+
+
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
 MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
 MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
@@ -2019,6 +2232,9 @@ def lib():
         L.ofdg_flow_vis.argtypes = [vp, C.POINTER(FlowVisJob), i32, vp]
         L.ofdg_host_flow_vis.argtypes = [C.POINTER(FlowVisJob), i32, i32, i32]
         L.ofdg_host_flow_vis_tables.argtypes = [vp, vp]
+        L.ofdg_flow_error.argtypes = [vp, C.POINTER(FlowErrorJob), i32, vp]
+        L.ofdg_host_flow_error.argtypes = [C.POINTER(FlowErrorJob), i32, i32, i32]
+        L.ofdg_host_flow_error_colours.argtypes = [vp]
         L.ofdg_motion_blur.argtypes = [vp, C.POINTER(MblurJob), i32, vp]
         L.ofdg_host_motion_blur.argtypes = [C.POINTER(MblurJob), i32, i32, i32]
         L.ofdg_motion_blur_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(MblurJob), C.POINTER(MblurRec)]
@@ -2536,6 +2752,27 @@ class Generator:
                             layout, dim_occ)
         self._check(lib().ofdg_flow_vis(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
+
+    def flow_error(self, gt, est, occ=None, dist2=None, rows=None, epe=None, picture=None, est_scale=1.0, speed_px=(10, 40),
+                   dist2_edges=(26, 101), layout="planar_bgr", dim_occ=False, accumulate=False, one_row=False, stream=0, size=None):
+        """The end-point error of an estimated flow against the ground truth (ofdg_flow_error, include/ofdg.h), in integers, the
+        same bits on every run.  gt: float32 or float16 [n,2,H,W]; est: float32, float16 or bfloat16 of that shape, multiplied
+        by est_scale first (a network that predicts flow / 20: est_scale=20).  occ: None or the float32 / uint8 [n,1,H,W] map
+        that goes with gt - Sintel's matched / unmatched split; dist2: None or the uint8 [n,1,H,W] dist2 plane
+        Generator.boundaries made of gt - the bands of distance to a motion boundary, split at dist2_edges (the default: within
+        5 px, within 10 px, beyond); speed_px: the edges of the bands of ground-truth speed.  Outputs, at least one
+        (alloc_flow_error makes them): rows, uint8 [n,672] ([1,672] with one_row: every sample into one row) - read them with
+        flow_error_numpy / flow_error_summary -, epe, float32 or float16 [n,1,H,W] (-1 where gt or est is unusable), picture,
+        uint8 in `layout`, the KITTI devkit's error colours (flow_error_legend; dim_occ: hidden pixels at half brightness).
+        accumulate: add to the rows - a validation epoch on the device.  stream: the stream the planes were written on, or
+        STREAM_OWN.  size=(height, width): planes of that size instead of the context's.  Asynchronous.  Returns the dict of
+        the outputs given, by name."""
+        height, width, job_size = self._job_size(size)
+        n, *codes = flow_error_format(gt, est, occ, dist2, rows, epe, picture, height, width, layout, one_row)
+        job = _flow_error_job((gt, est, occ, dist2, rows, epe, picture), lambda t: None if t is None else _dptr(t).value, job_size, codes, est_scale,
+                              speed_px, dist2_edges, layout, dim_occ, accumulate, one_row)
+        self._check(lib().ofdg_flow_error(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return {k: v for k, v in (("rows", rows), ("epe", epe), ("picture", picture)) if v is not None}
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
                     size=None):
@@ -3358,7 +3595,9 @@ class FlowLoader:
     "planar_bgr", dim_occ False; Generator.flow_vis): the colour-wheel picture of the batch's final flow - behind the window,
     in front of pack=, which may rescale it; the dict also holds "flow_vis" (uint8, [n,3,H,W] or [n,H,W,3]) and "flow_vis_rows"
     (int32 [n,4]: flow_vis_numpy), and "flow1_vis" / "flow1_vis_rows" when which names "flow1", which must be among extras=.
-    dim_occ=True dims by "occ0" (for flow1: "occ1") as the eraser left it, and needs that map among extras=."""
+    dim_occ=True dims by "occ0" (for flow1: "occ1") as the eraser left it, and needs that map among extras=.
+    flow_error(est, ...) is no stage: a method that scores a network's estimate against the batch handed out last
+    (Generator.flow_error), on the consumer stream."""
 
     def __init__(self, params=None, pool=None, prefetch=3, stream=None, start=0, extras=None, image_dtype=None, flow_dtype=None,
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
@@ -3723,6 +3962,46 @@ class FlowLoader:
                 more[name + "_vis"], more[name + "_vis_rows"] = dst, rows
         top = t.planes if t.packed is None else t.packed
         return (top["image0"], top.get("image1"), top["flow"]) + ((more,) if more or self.extras is not None else ())
+
+    def flow_error(self, est, rows=None, accumulate=False, one_row=False, outputs=("rows",), est_scale=None, **options):
+        """Scores an estimate against the batch handed out last (Generator.flow_error), on the consumer stream: the ground truth
+        is that batch's final flow as the stages left it - not the packed one -, with "occ0" when it is among extras= and the
+        distance plane "dist0" when boundaries= made it for frame 0; the ring keeps that set alive until the next next().
+        est: a float32, float16 or bfloat16 device tensor of the flow's shape.  est_scale: None - 1, or 1 / flow_scale when
+        pack= rescales the flow, so that a network trained on the packed flow is scored in pixels.  rows: None - new, zeroed
+        rows - or the rows of a former call, to add to with accumulate=True (three batches: one row of an epoch).  outputs:
+        which of "rows", "epe" and "picture" to make.  options: speed_px, dist2_edges, layout, dim_occ, epe_dtype.  Returns the
+        dict of the rows and the planes asked for, by name.  Raises before the first batch, and for an est of another shape,
+        dtype or device."""
+        import torch
+        if self.k == 0:
+            raise RuntimeError("flow_error scores the batch handed out last: call next() first")
+        unknown = set(options) - {"speed_px", "dist2_edges", "layout", "dim_occ", "epe_dtype"}
+        if unknown:
+            raise ValueError("unknown flow_error option(s) %s" % sorted(unknown))
+        t = self.slots[(self.k - 1) % self.prefetch]
+        gt = t.planes["flow"]
+        if not hasattr(est, "is_cuda") or not est.is_cuda or est.device != gt.device:
+            raise ValueError("est must be a tensor on %s, the device of the batch" % (gt.device,))
+        if _dtype_name(est) not in ("float32", "float16", "bfloat16") or tuple(est.shape) != tuple(gt.shape):
+            raise ValueError("est must be float32, float16 or bfloat16 %s, got %s %s" % (tuple(gt.shape), _dtype_name(est), tuple(est.shape)))
+        n, _, ph, pw = gt.shape
+        outputs = _flow_error_outputs(outputs)
+        layout = options.get("layout", "planar_bgr")
+        if est_scale is None:
+            est_scale = 1.0 if self.pack is None else 1.0 / float(self.pack.get("flow_scale", 1.0))
+        if rows is None and accumulate:
+            raise ValueError("accumulate=True needs rows= to add to")
+        new = [o for o in outputs if o != "rows" or rows is None]  # (rows= given: those are the rows)
+        with torch.cuda.stream(self.consumer):      # (the zeroing of new rows runs on the stream of the call)
+            out = alloc_flow_error(n, ph, pw, new, options.get("epe_dtype"), layout, one_row, gt.device) if new else {}
+        if rows is not None:
+            out["rows"] = rows
+        self.gen.flow_error(gt, est, occ=t.planes.get("occ0"), dist2=None if t.edges is None else t.edges.get("dist0"), rows=out.get("rows"),
+                            epe=out.get("epe"), picture=out.get("picture"), est_scale=est_scale, speed_px=options.get("speed_px", (10, 40)),
+                            dist2_edges=options.get("dist2_edges", (26, 101)), layout=layout, dim_occ=bool(options.get("dim_occ", False)),
+                            accumulate=accumulate, one_row=one_row, stream=self.consumer.cuda_stream, size=self.window)
+        return out
 
     @property
     def consumed(self):

@@ -889,6 +889,83 @@ int ofdg_host_flow_vis(const struct ofdg_flow_vis_job* job, int n_samples, int w
   return OFDG_OK;
 }
 
+// ofdg_flow_error on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The usable rule, the Q8
+// components, the roots, the cell, the flags, the bins, the key, epe and the colour are the functions the kernel runs
+// (csrc/ofdg_device.h); elements are moved with memcpy, the rows are added to field by field.
+int ofdg_host_flow_error_colours(uint8_t rgb[10][3]) {
+  if (!rgb) { g_host_error = "ofdg_host_flow_error_colours: rgb is NULL"; return OFDG_EINVAL; }
+  for (int k = 0; k < kErrColours; ++k)
+    for (int c = 0; c < 3; ++c) rgb[k][c] = (uint8_t)(kErrColour[k] >> (8 * c));
+  return OFDG_OK;
+}
+int ofdg_host_flow_error(const struct ofdg_flow_error_job* job, int n_samples, int width, int height) {
+  const DevErrJob* const j = reinterpret_cast<const DevErrJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = err_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_flow_error: ") + why; return OFDG_EINVAL; }
+  const size_t plane = (size_t)width * height;
+  const FlowPlane gt{j->gt, j->gt_fmt}, est_f{j->est, j->est_fmt};
+  const auto est = [&](size_t i) {
+    if (j->est_fmt != OFDG_FMT_BF16) return est_f.at(i);
+    uint16_t h;
+    std::memcpy(&h, static_cast<const uint8_t*>(j->est) + 2 * i, 2);
+    return err_bf16(h);
+  };
+  const OccPlane hidden{j->occ, j->occ_fmt};
+  const bool one_row = j->flags & OFDG_ERR_ONE_ROW, dim = j->flags & OFDG_ERR_DIM_OCC, hwc = j->layout == OFDG_VIS_HWC_RGB;
+  const ErrBands bands = err_bands(*j);
+  uint8_t* const rows = reinterpret_cast<uint8_t*>(j->rows);
+  if (rows && !(j->flags & OFDG_ERR_ACCUMULATE)) std::memset(rows, 0, sizeof(DevErrRow) * (one_row ? 1 : (size_t)n_samples));
+  uint8_t* const picture = static_cast<uint8_t*>(j->picture);
+  for (int i = 0; i < n_samples; ++i) {
+    DevErrRow row{};
+    if (rows) std::memcpy(&row, rows + sizeof(row) * (one_row ? 0 : (size_t)i), sizeof(row));
+    for (size_t k = 0; k < plane; ++k) {
+      const float ug = gt.at((size_t)i * 2 * plane + k), vg = gt.at(((size_t)i * 2 + 1) * plane + k);
+      const float ue = err_scaled(est((size_t)i * 2 * plane + k), j->est_scale), ve = err_scaled(est(((size_t)i * 2 + 1) * plane + k), j->est_scale);
+      const bool gt_ok = vis_usable(ug, vg), ok = gt_ok && vis_usable(ue, ve);
+      float epe = -1.0f;
+      uint32_t rgb = 0u;
+      if (!gt_ok) ++row.n_bad[0];
+      else if (!ok) ++row.n_bad[1];
+      else {
+        const ErrPixel e = err_pixel(ug, vg, ue, ve);
+        const bool hid = j->occ && hidden.at((size_t)i * plane + k);
+        DevErrCell& cell = row.cell[err_cell(hid, e.Gq, j->dist2 ? j->dist2[(size_t)i * plane + k] : 0u, j->dist2 != nullptr, bands)];
+        const uint32_t flags = err_flags(e.Eq, e.Gq);
+        ++cell.n;
+        cell.sum_epe_q8 += e.Eq;
+        cell.n_1px += flags & 1u;
+        cell.n_3px += (flags >> 1) & 1u;
+        cell.n_5px += (flags >> 2) & 1u;
+        cell.n_fl += (flags >> 3) & 1u;
+        ++row.hist[err_hist_bin(e.Eq)];
+        row.max_key = std::max(row.max_key, err_key(e.Eq, (uint32_t)((one_row ? (size_t)i * plane : 0) + k)));
+        epe = err_epe(e.Eq);
+        rgb = err_colour(e.Eq, e.Gq, dim && hid, kErrColour);
+      }
+      if (j->epe) {
+        if (j->epe_fmt == OFDG_FMT_F16) {
+          const uint16_t h = float_to_half_bits(epe);
+          std::memcpy(static_cast<uint8_t*>(j->epe) + 2 * ((size_t)i * plane + k), &h, 2);
+        } else {
+          std::memcpy(static_cast<uint8_t*>(j->epe) + 4 * ((size_t)i * plane + k), &epe, 4);
+        }
+      }
+      if (picture)
+        for (int c = 0; c < 3; ++c) {  // c: R, G, B
+          const uint8_t byte = (uint8_t)(rgb >> (8 * c));
+          if (hwc) picture[((size_t)i * plane + k) * 3 + c] = byte;
+          else picture[((size_t)i * 3 + (2 - c)) * plane + k] = byte;
+        }
+    }
+    if (rows) std::memcpy(rows + sizeof(row) * (one_row ? 0 : (size_t)i), &row, sizeof(row));
+  }
+  return OFDG_OK;
+}
+
 // ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.

@@ -5620,4 +5620,200 @@ __global__ __launch_bounds__(kVisThreads) void flow_vis_colour_kernel(const DevV
   }
 }
 
+// ---- Flow error (ofdg_flow_error, include/ofdg.h) --------------------------------------------------------------------------
+// One launch behind the optional clearing of the rows.  The grid is the colour-wheel's: blockIdx.x counts the
+// kErrBlockPixels-pixel blocks of a plane, blockIdx.y the samples (strided beyond 65535 of them).  A lane takes 4 consecutive
+// pixels - 16 bytes of each float32 plane, 8 of a binary16 / bfloat16 one, 16 or 4 of the map, 4 of dist2 - in rounds of 1024
+// pixels per workgroup; the steps of the definition are the host twin's functions (csrc/ofdg_device.h).
+// The row is 168 words, too many to keep per lane, so each wave keeps a copy in LDS, packed: a workgroup sees at most
+// kErrBlockPixels = 4096 pixels of a sample, so a cell is two 64-bit words - sum_epe_q8 (below 2^42) with n above bit 48, and
+// the four outlier counts in 16 bits each - and a pixel costs at most two 64-bit LDS atomics.  Neighbouring pixels mostly fall
+// into one cell and one histogram bin, so a lane first adds in registers and goes to LDS only when the cell (the bin) changes
+// and at the end of the sample.  The key and the two unusable counts stay in registers and cross the wave with __shfl_xor.
+// Then the workgroup unpacks and issues one global integer atomic per non-zero word of the row and one 64-bit atomicMax for
+// the key.  Integer atomics only: no bit depends on arrival order.  kPlanes: epe or the picture is written - the rows-only
+// form holds none of that code.  No scratch.
+constexpr int kErrThreads = 256;
+constexpr int kErrBlockPixels = 4096;
+constexpr int kErrWaves = kErrThreads / 64;
+static_assert(kErrBlockPixels % (kErrThreads * 4) == 0 && kErrBlockPixels <= 4096, "whole rounds of 4-pixel pieces; the packed counters hold 4096 pixels");
+template <int kFmt>  // OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16
+__device__ __forceinline__ void err_load4(const void* p, size_t at, float (&e)[4]) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  if constexpr (kFmt == OFDG_FMT_F16) {
+    const f16x4 a = *reinterpret_cast<const f16x4*>(static_cast<const _Float16*>(p) + at);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = (float)a[q];
+  } else if constexpr (kFmt == OFDG_FMT_BF16) {
+    const u32x2 a = *reinterpret_cast<const u32x2*>(static_cast<const uint16_t*>(p) + at);
+    e[0] = err_bf16(a[0] & 0xFFFFu);
+    e[1] = err_bf16(a[0] >> 16);
+    e[2] = err_bf16(a[1] & 0xFFFFu);
+    e[3] = err_bf16(a[1] >> 16);
+  } else {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(static_cast<const float*>(p) + at);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = a[q];
+  }
+}
+template <bool kGtHalf, int kEst, bool kPlanes>
+__global__ __launch_bounds__(kErrThreads) void flow_error_kernel(const DevErrJob job, int n, uint32_t plane) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  __shared__ unsigned long long s_sum_n[kErrWaves][kErrCells];  // sum_epe_q8 | n << 48
+  __shared__ unsigned long long s_out[kErrWaves][kErrCells];    // n_1px | n_3px << 16 | n_5px << 32 | n_fl << 48
+  __shared__ uint32_t s_hist[kErrWaves][kErrHistBins];
+  __shared__ unsigned long long s_key;
+  __shared__ uint32_t s_bad[2];
+  __shared__ uint32_t s_colour[kErrColours];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (kPlanes) {
+    if (tid < kErrColours) s_colour[tid] = kErrColour[tid];  // (the first barrier of the sample loop orders it)
+  }
+  const uint32_t first = blockIdx.x * (uint32_t)kErrBlockPixels;
+  const uint32_t end = first + (uint32_t)kErrBlockPixels < plane ? first + (uint32_t)kErrBlockPixels : plane;
+  const ErrBands bands = err_bands(job);
+  const bool with_rows = job.rows != nullptr, with_dist = job.dist2 != nullptr, one_row = job.flags & OFDG_ERR_ONE_ROW;
+  const bool dim_occ = job.flags & OFDG_ERR_DIM_OCC, occ_u8 = job.occ_fmt == OFDG_FMT_U8;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    for (int k = tid; k < kErrWaves * kErrCells; k += kErrThreads) { (&s_sum_n[0][0])[k] = 0ull; (&s_out[0][0])[k] = 0ull; }
+    if (tid < kErrWaves * kErrHistBins) (&s_hist[0][0])[tid] = 0u;
+    if (tid == 64) s_key = 0ull;
+    if (tid == 65 || tid == 66) s_bad[tid - 65] = 0u;
+    __syncthreads();
+    const size_t base = (size_t)i * 2 * plane, base1 = (size_t)i * plane;
+    const uint32_t idx_base = one_row ? (uint32_t)i * plane : 0u;
+    uint32_t cur_cell = 0, cur_bin = 0, bin_count = 0, n_bad_gt = 0, n_bad_est = 0;
+    unsigned long long acc_sum_n = 0, acc_out = 0, key = 0;
+    for (uint32_t at = first + (uint32_t)tid * 4u; at < end; at += (uint32_t)(kErrThreads * 4)) {
+      float ug[4], vg[4], ue[4], ve[4];
+      err_load4<kGtHalf ? OFDG_FMT_F16 : OFDG_FMT_F32>(job.gt, base + at, ug);
+      err_load4<kGtHalf ? OFDG_FMT_F16 : OFDG_FMT_F32>(job.gt, base + plane + at, vg);
+      err_load4<kEst>(job.est, base + at, ue);
+      err_load4<kEst>(job.est, base + plane + at, ve);
+      uint32_t hidden = 0, d2 = 0;  // bit q: pixel q is hidden; byte q: its dist2
+      if (job.occ) {
+        if (occ_u8) {
+          const uint32_t o = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(job.occ) + base1 + at);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hidden |= (((o >> (8 * q)) & 255u) != 0u ? 1u : 0u) << q;
+        } else {
+          const f32x4 o = *reinterpret_cast<const f32x4*>(static_cast<const float*>(job.occ) + base1 + at);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hidden |= (o[q] != 0.0f ? 1u : 0u) << q;
+        }
+      }
+      if (with_dist) d2 = *reinterpret_cast<const uint32_t*>(job.dist2 + base1 + at);
+      float out_epe[4];
+      uint32_t px[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float se = err_scaled(ue[q], job.est_scale), te = err_scaled(ve[q], job.est_scale);
+        const bool gt_ok = vis_usable(ug[q], vg[q]), ok = gt_ok && vis_usable(se, te);
+        n_bad_gt += gt_ok ? 0u : 1u;
+        n_bad_est += (gt_ok && !ok) ? 1u : 0u;
+        if constexpr (kPlanes) { out_epe[q] = -1.0f; px[q] = 0u; }
+        if (ok) {
+          const ErrPixel e = err_pixel(ug[q], vg[q], se, te);
+          const bool hid = (hidden >> q) & 1u;
+          if (with_rows) {
+            const uint32_t cell = err_cell(hid, e.Gq, (d2 >> (8 * q)) & 255u, with_dist, bands), flags = err_flags(e.Eq, e.Gq), bin = err_hist_bin(e.Eq);
+            if (cell != cur_cell) {
+              if (acc_sum_n) atomicAdd(&s_sum_n[wave][cur_cell], acc_sum_n);
+              if (acc_out) atomicAdd(&s_out[wave][cur_cell], acc_out);
+              acc_sum_n = acc_out = 0ull;
+              cur_cell = cell;
+            }
+            acc_sum_n += (unsigned long long)e.Eq | (1ull << 48);
+            acc_out += (unsigned long long)(flags & 1u) | ((unsigned long long)((flags >> 1) & 1u) << 16) | ((unsigned long long)((flags >> 2) & 1u) << 32) |
+                       ((unsigned long long)((flags >> 3) & 1u) << 48);
+            if (bin != cur_bin) {
+              if (bin_count) atomicAdd(&s_hist[wave][cur_bin], bin_count);
+              bin_count = 0u;
+              cur_bin = bin;
+            }
+            ++bin_count;
+            const unsigned long long k = err_key(e.Eq, idx_base + at + (uint32_t)q);
+            key = k > key ? k : key;
+          }
+          if constexpr (kPlanes) {
+            out_epe[q] = err_epe(e.Eq);
+            if (job.picture) px[q] = err_colour(e.Eq, e.Gq, dim_occ && hid, s_colour);
+          }
+        }
+      }
+      if constexpr (kPlanes) {
+        if (job.epe) {
+          if (job.epe_fmt == OFDG_FMT_F16)
+            *reinterpret_cast<f16x4*>(static_cast<_Float16*>(job.epe) + base1 + at) = f16x4{(_Float16)out_epe[0], (_Float16)out_epe[1], (_Float16)out_epe[2], (_Float16)out_epe[3]};
+          else
+            *reinterpret_cast<f32x4*>(static_cast<float*>(job.epe) + base1 + at) = f32x4{out_epe[0], out_epe[1], out_epe[2], out_epe[3]};
+        }
+        if (job.picture) {
+          uint8_t* const dst = static_cast<uint8_t*>(job.picture);
+          if (job.layout == OFDG_VIS_HWC_RGB) {
+            uint32_t* const dp = reinterpret_cast<uint32_t*>(dst + (base1 + at) * 3);
+            dp[0] = px[0] | (px[1] << 24);
+            dp[1] = (px[1] >> 8) | (px[2] << 16);
+            dp[2] = (px[2] >> 16) | (px[3] << 8);
+          } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {  // c: R, G, B of a pixel's word; plane 2 - c
+              const uint32_t sh = 8u * (uint32_t)c;
+              const uint32_t w = ((px[0] >> sh) & 255u) | (((px[1] >> sh) & 255u) << 8) | (((px[2] >> sh) & 255u) << 16) | (((px[3] >> sh) & 255u) << 24);
+              *reinterpret_cast<uint32_t*>(dst + ((size_t)i * 3 + (size_t)(2 - c)) * plane + at) = w;
+            }
+          }
+        }
+      }
+    }
+    if (with_rows) {
+      if (acc_sum_n) atomicAdd(&s_sum_n[wave][cur_cell], acc_sum_n);
+      if (acc_out) atomicAdd(&s_out[wave][cur_cell], acc_out);
+      if (bin_count) atomicAdd(&s_hist[wave][cur_bin], bin_count);
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        n_bad_gt += (uint32_t)__shfl_xor((int)n_bad_gt, d, 64);
+        n_bad_est += (uint32_t)__shfl_xor((int)n_bad_est, d, 64);
+        const unsigned long long other = (unsigned long long)__shfl_xor((long long)key, d, 64);
+        key = other > key ? other : key;
+      }
+      if (lane == 0) {
+        if (n_bad_gt) atomicAdd(&s_bad[0], n_bad_gt);
+        if (n_bad_est) atomicAdd(&s_bad[1], n_bad_est);
+        if (key) atomicMax(&s_key, key);
+      }
+      __syncthreads();
+      DevErrRow* const out = job.rows + (one_row ? 0 : i);
+      if (tid < kErrCells * 6) {  // word f of cell c: the sum, then n, n_1px, n_3px, n_5px, n_fl
+        const int c = tid / 6, f = tid - c * 6;
+        unsigned long long a = 0, b = 0;
+#pragma unroll
+        for (int w = 0; w < kErrWaves; ++w) { a += s_sum_n[w][c]; b += s_out[w][c]; }
+        if (f == 0) {
+          const unsigned long long sum = a & ((1ull << 48) - 1ull);
+          if (sum) atomicAdd(&out->cell[c].sum_epe_q8, sum);
+        } else {
+          const uint32_t v = f == 1 ? (uint32_t)(a >> 48) : (uint32_t)(b >> (16 * (f - 2))) & 0xFFFFu;
+          if (v) atomicAdd(&out->cell[c].n + (f - 1), v);
+        }
+      } else if (tid < kErrCells * 6 + kErrHistBins) {
+        const int b = tid - kErrCells * 6;
+        uint32_t h = 0;
+#pragma unroll
+        for (int w = 0; w < kErrWaves; ++w) h += s_hist[w][b];
+        if (h) atomicAdd(&out->hist[b], h);
+      } else if (tid < kErrCells * 6 + kErrHistBins + 2) {
+        const int k = tid - (kErrCells * 6 + kErrHistBins);
+        if (s_bad[k]) atomicAdd(&out->n_bad[k], s_bad[k]);
+      } else if (tid == kErrCells * 6 + kErrHistBins + 2 && s_key) {
+        atomicMax(&out->max_key, s_key);
+      }
+    }
+    __syncthreads();  // (the next sample of this workgroup clears the tables)
+  }
+}
+
 }  // namespace ofdg

@@ -271,7 +271,8 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
+// ofdg_flow_error
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -293,7 +294,7 @@ struct PostOp {
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
 // 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel,
-// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel.
+// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -2062,6 +2063,41 @@ int ofdg_flow_vis(ofdg_ctx* c, const struct ofdg_flow_vis_job* job, int n_sample
     with_occ_kind((j->flags & OFDG_VIS_DIM_OCC) ? j->occ : nullptr, j->occ_fmt, [&](auto occ_kind) {
       with_bool(j->layout == OFDG_VIS_HWC_RGB, [&](auto hwc) {
         hipLaunchKernelGGL((flow_vis_colour_kernel<decltype(h)::value, decltype(occ_kind)::value, decltype(hwc)::value>), g, dim3(kVisThreads), 0, st, *j,
+                           n_samples, plane);
+      });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// The error of a caller-given estimate against a caller-given ground truth: unless the rows are added to their clearing,
+// then one kernel for every sample, all on `stream`.
+int ofdg_flow_error(ofdg_ctx* c, const struct ofdg_flow_error_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_flow_error"};
+  const DevErrJob* const j = reinterpret_cast<const DevErrJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = err_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = err_arg_error(j, n_samples, W, H)) return op.fail(why);
+  OFDG_TRY(op.aligned("gt", j->gt, j->gt_fmt));
+  OFDG_TRY(op.aligned("est", j->est, j->est_fmt, /*say_fmt=*/false));
+  if (j->occ) OFDG_TRY(op.aligned("occ", j->occ, j->occ_fmt));
+  if ((uintptr_t)j->dist2 & 3) return op.fail("dist2 must be 4-byte aligned");
+  if ((uintptr_t)j->rows & 7) return op.fail("rows must be 8-byte aligned");
+  if ((uintptr_t)j->epe & 15) return op.fail("epe must be 16-byte aligned");
+  if ((uintptr_t)j->picture & 15) return op.fail("picture must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  if (j->rows && !(j->flags & OFDG_ERR_ACCUMULATE))
+    HIP_OK(c, hipMemsetAsync(j->rows, 0, sizeof(DevErrRow) * ((j->flags & OFDG_ERR_ONE_ROW) ? 1 : (size_t)n_samples), st));
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;
+  const dim3 g((plane + kErrBlockPixels - 1) / kErrBlockPixels, (unsigned)std::min(n_samples, 65535));
+  with_bool(j->gt_fmt == OFDG_FMT_F16, [&](auto half) {
+    with_constant<int, OFDG_FMT_F32, OFDG_FMT_F16, OFDG_FMT_BF16>(j->est_fmt, [&](auto est) {
+      with_bool(j->epe || j->picture, [&](auto planes) {
+        hipLaunchKernelGGL((flow_error_kernel<decltype(half)::value, decltype(est)::value, decltype(planes)::value>), g, dim3(kErrThreads), 0, st, *j,
                            n_samples, plane);
       });
     });

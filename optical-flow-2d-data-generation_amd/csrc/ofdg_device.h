@@ -2021,6 +2021,161 @@ inline const char* vis_arg_error(const DevVisJob* j, int n, int width, int heigh
   return nullptr;
 }
 
+// ---- Flow error (ofdg_flow_error, include/ofdg.h) --------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job and the row as the kernel takes them, the colour table,
+// the steps of the definition on one pixel and the argument rules.  Behind the rounding of the four components to Q8
+// (vis_fixed) everything is integers; the roots are vis_isqrt, whose correction step is exact for every x below 2^60 (r < 2^30:
+// r r + 2 r + 1 stays in 64 bits) - E2 is below 2^59.
+struct DevErrCell {  // ofdg_flow_error_cell, field for field
+  unsigned long long sum_epe_q8;
+  uint32_t n, n_1px, n_3px, n_5px, n_fl, reserved;
+};
+constexpr int kErrCells = 18, kErrHistBins = OFDG_FLOW_ERROR_HIST_BINS, kErrColours = 10;
+struct DevErrRow {  // ofdg_flow_error_row, field for field
+  DevErrCell cell[kErrCells];  // [hidden][speed band][distance band]
+  uint32_t hist[kErrHistBins];
+  unsigned long long max_key;
+  uint32_t n_bad[2];  // n_bad_gt, n_bad_est
+  uint32_t reserved[4];
+};
+struct DevErrJob {  // struct ofdg_flow_error_job, field for field
+  const void* gt;
+  const void* est;
+  const void* occ;
+  const uint8_t* dist2;
+  DevErrRow* rows;
+  void* epe;
+  void* picture;
+  int32_t width, height, gt_fmt, est_fmt, occ_fmt, epe_fmt, layout, flags;
+  float est_scale;
+  float speed_px[2];
+  int32_t dist2_edge[2];
+  int32_t reserved[5];
+};
+static_assert(sizeof(ofdg_flow_error_cell) == sizeof(DevErrCell) && sizeof(DevErrCell) == 32 && offsetof(ofdg_flow_error_cell, n) == offsetof(DevErrCell, n) &&
+              offsetof(DevErrCell, n) == 8 && offsetof(ofdg_flow_error_cell, n_fl) == offsetof(DevErrCell, n_fl) && offsetof(DevErrCell, n_fl) == 24,
+              "ofdg_flow_error_cell: 32 bytes");
+static_assert(sizeof(ofdg_flow_error_row) == sizeof(DevErrRow) && sizeof(DevErrRow) == 672 && offsetof(ofdg_flow_error_row, hist) == offsetof(DevErrRow, hist) &&
+              offsetof(DevErrRow, hist) == 576 && offsetof(ofdg_flow_error_row, max_key) == offsetof(DevErrRow, max_key) && offsetof(DevErrRow, max_key) == 640 &&
+              offsetof(ofdg_flow_error_row, n_bad_gt) == offsetof(DevErrRow, n_bad) && offsetof(ofdg_flow_error_row, n_bad_est) == offsetof(DevErrRow, n_bad) + 4 &&
+              offsetof(ofdg_flow_error_row, reserved) == offsetof(DevErrRow, reserved),
+              "ofdg_flow_error_row: 672 bytes, no padding");
+static_assert(sizeof(struct ofdg_flow_error_job) == sizeof(DevErrJob) && sizeof(DevErrJob) == 128 && offsetof(struct ofdg_flow_error_job, dist2) == offsetof(DevErrJob, dist2) &&
+              offsetof(struct ofdg_flow_error_job, rows) == offsetof(DevErrJob, rows) && offsetof(struct ofdg_flow_error_job, picture) == offsetof(DevErrJob, picture) &&
+              offsetof(struct ofdg_flow_error_job, width) == offsetof(DevErrJob, width) && offsetof(DevErrJob, width) == 56 &&
+              offsetof(struct ofdg_flow_error_job, flags) == offsetof(DevErrJob, flags) && offsetof(DevErrJob, flags) == 84 &&
+              offsetof(struct ofdg_flow_error_job, est_scale) == offsetof(DevErrJob, est_scale) && offsetof(DevErrJob, est_scale) == 88 &&
+              offsetof(struct ofdg_flow_error_job, speed_px) == offsetof(DevErrJob, speed_px) &&
+              offsetof(struct ofdg_flow_error_job, dist2_edge) == offsetof(DevErrJob, dist2_edge) && offsetof(DevErrJob, dist2_edge) == 100 &&
+              offsetof(struct ofdg_flow_error_job, reserved) == offsetof(DevErrJob, reserved) && OFDG_ERR_ACCUMULATE == 1 && OFDG_ERR_ONE_ROW == 2 && OFDG_ERR_DIM_OCC == 4,
+              "struct ofdg_flow_error_job: 128 bytes, the layout the kernel takes");
+// The KITTI devkit's error colours, bin k as R | G << 8 | B << 16
+#define ERR_RGB(r, g, b) ((uint32_t)(r) | ((uint32_t)(g) << 8) | ((uint32_t)(b) << 16))
+constexpr uint32_t kErrColour[kErrColours] = {ERR_RGB(49, 54, 149),   ERR_RGB(69, 117, 180), ERR_RGB(116, 173, 209), ERR_RGB(171, 217, 233),
+                                              ERR_RGB(224, 243, 248), ERR_RGB(254, 224, 144), ERR_RGB(253, 174, 97),  ERR_RGB(244, 109, 67),
+                                              ERR_RGB(215, 48, 39),   ERR_RGB(165, 0, 38)};
+#undef ERR_RGB
+// step 1: bfloat16 bits widened (exact), and the estimate's scaling - one float32 product
+OFDG_HD_FN float err_bf16(uint32_t bits) {
+  const uint32_t w = bits << 16;
+  float f;
+  __builtin_memcpy(&f, &w, 4);
+  return f;
+}
+OFDG_HD_FN float err_scaled(float e, float est_scale) { return e * est_scale; }
+// what a call keeps of the job's bands: S_0, S_1 in Q8 pixels and the two edges of dist2
+struct ErrBands {
+  uint32_t speed[2];
+  uint32_t dist[2];
+};
+OFDG_HD_FN ErrBands err_bands(const DevErrJob& j) {
+  return ErrBands{{(uint32_t)lrintf(j.speed_px[0] * 256.0f), (uint32_t)lrintf(j.speed_px[1] * 256.0f)}, {(uint32_t)j.dist2_edge[0], (uint32_t)j.dist2_edge[1]}};
+}
+// step 5 of a pixel whose four components are usable
+struct ErrPixel {
+  uint32_t Eq, Gq;
+};
+OFDG_HD_FN ErrPixel err_pixel(float ug, float vg, float ue, float ve) {
+  const int Ug = vis_fixed(ug), Vg = vis_fixed(vg), Ue = vis_fixed(ue), Ve = vis_fixed(ve);
+  return ErrPixel{vis_isqrt(vis_r2(Ue - Ug, Ve - Vg)), vis_isqrt(vis_r2(Ug, Vg))};
+}
+// step 6: the cell's index, (hidden * 3 + speed band) * 3 + distance band; d2: the pixel's dist2, 0 without a plane
+OFDG_HD_FN uint32_t err_cell(bool hidden, uint32_t Gq, uint32_t d2, bool with_dist, const ErrBands& b) {
+  const uint32_t sb = (Gq >= b.speed[0] ? 1u : 0u) + (Gq >= b.speed[1] ? 1u : 0u);
+  const uint32_t db = with_dist ? (d2 >= b.dist[0] ? 1u : 0u) + (d2 >= b.dist[1] ? 1u : 0u) : 0u;
+  return ((hidden ? 3u : 0u) + sb) * 3u + db;
+}
+// step 7: the four flags of a pixel, bit 0 n_1px, 1 n_3px, 2 n_5px, 3 n_fl
+OFDG_HD_FN uint32_t err_flags(uint32_t Eq, uint32_t Gq) {
+  return (Eq > 256u ? 1u : 0u) | (Eq > 768u ? 2u : 0u) | (Eq > 1280u ? 4u : 0u) | ((Eq > 768u && 20ull * Eq > (unsigned long long)Gq) ? 8u : 0u);
+}
+// step 8: the number of k in 0..14 with Eq >= (16 << k): 0 below 16, else floor(log2(Eq)) - 3, at most 15
+OFDG_HD_FN uint32_t err_hist_bin(uint32_t Eq) {
+  if (Eq < 16u) return 0u;
+  const uint32_t b = (uint32_t)(31 - __builtin_clz(Eq)) - 3u;
+  return b < 15u ? b : 15u;
+}
+OFDG_HD_FN unsigned long long err_key(uint32_t Eq, uint32_t idx) { return ((unsigned long long)Eq << 32) | (unsigned long long)(0xFFFFFFFFu - idx); }
+// step 9: the float32 of Eq / 256 (the conversion rounds to nearest even, the product is exact)
+OFDG_HD_FN float err_epe(uint32_t Eq) { return (float)Eq * 0.00390625f; }
+// step 10: the bin - both conditions only get harder with j, so the count stops at the first that fails - and the colour
+OFDG_HD_FN uint32_t err_colour_bin(uint32_t Eq, uint32_t Gq) {
+  uint32_t bin = 0;
+  for (int j = 0; j < 9; ++j) bin += (Eq >= (48u << j) && 320ull * Eq >= ((unsigned long long)Gq << j)) ? 1u : 0u;
+  return bin;
+}
+OFDG_HD_FN uint32_t err_colour(uint32_t Eq, uint32_t Gq, bool dim, const uint32_t* table) {
+  const uint32_t c = table[err_colour_bin(Eq, Gq)];
+  return dim ? (c >> 1) & 0x7F7F7Fu : c;
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* err_plane_size(const DevErrJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The argument rules ofdg_flow_error and ofdg_host_flow_error share: the first rule broken, or nullptr.  width, height: what
+// err_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* err_arg_error(const DevErrJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (!j->gt) return "gt is NULL";
+  if (!j->est) return "est is NULL";
+  if (!j->rows && !j->epe && !j->picture) return "rows, epe and picture are all NULL: no output";
+  if (n < 1) return "n_samples must be at least 1";
+  const unsigned long long plane = (unsigned long long)width * (unsigned long long)height;
+  if (3ull * plane >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->flags & ~(OFDG_ERR_ACCUMULATE | OFDG_ERR_ONE_ROW | OFDG_ERR_DIM_OCC)) return "flags holds unknown bits";
+  if ((j->flags & OFDG_ERR_ONE_ROW) && (unsigned long long)n * plane >= (1ull << 32)) return "flags: OFDG_ERR_ONE_ROW needs n_samples * height * width below 2^32";
+  if (j->gt_fmt != OFDG_FMT_F32 && j->gt_fmt != OFDG_FMT_F16) return "gt_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->est_fmt != OFDG_FMT_F32 && j->est_fmt != OFDG_FMT_F16 && j->est_fmt != OFDG_FMT_BF16) return "est_fmt must be OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16";
+  if (j->occ && j->occ_fmt != OFDG_FMT_F32 && j->occ_fmt != OFDG_FMT_U8) return "occ_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->epe && j->epe_fmt != OFDG_FMT_F32 && j->epe_fmt != OFDG_FMT_F16) return "epe_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
+  if (j->layout != OFDG_VIS_PLANAR_BGR && j->layout != OFDG_VIS_HWC_RGB) return "layout must be OFDG_VIS_PLANAR_BGR or OFDG_VIS_HWC_RGB";
+  for (int k = 0; k < 5; ++k)
+    if (j->reserved[k] != 0) return "reserved must be 0";
+  if ((j->flags & OFDG_ERR_DIM_OCC) && !j->occ) return "flags: OFDG_ERR_DIM_OCC needs occ";
+  if ((j->flags & OFDG_ERR_DIM_OCC) && !j->picture) return "flags: OFDG_ERR_DIM_OCC needs picture";
+  if (!(fabsf(j->est_scale) >= 0.0009765625f && fabsf(j->est_scale) <= 1024.0f)) return "est_scale: its magnitude must lie in [2^-10, 2^10]";
+  if (!(j->speed_px[0] > 0.0f && j->speed_px[0] <= j->speed_px[1] && j->speed_px[1] <= 1048576.0f)) return "speed_px must be 0 < speed_px[0] <= speed_px[1] <= 2^20";
+  if (j->dist2 && !(1 <= j->dist2_edge[0] && j->dist2_edge[0] <= j->dist2_edge[1] && j->dist2_edge[1] <= 255))
+    return "dist2_edge must be 1 <= dist2_edge[0] <= dist2_edge[1] <= 255";
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[7];
+  int nr = 0;
+  const unsigned long long all = (unsigned long long)n * plane;
+  r[nr++] = Range{(uintptr_t)j->gt, (uintptr_t)j->gt + (uintptr_t)(2ull * all * fmt_elem_bytes(j->gt_fmt)), false};
+  r[nr++] = Range{(uintptr_t)j->est, (uintptr_t)j->est + (uintptr_t)(2ull * all * fmt_elem_bytes(j->est_fmt)), false};
+  if (j->occ) r[nr++] = Range{(uintptr_t)j->occ, (uintptr_t)j->occ + (uintptr_t)(all * fmt_elem_bytes(j->occ_fmt)), false};
+  if (j->dist2) r[nr++] = Range{(uintptr_t)j->dist2, (uintptr_t)j->dist2 + (uintptr_t)all, false};
+  if (j->rows) r[nr++] = Range{(uintptr_t)j->rows, (uintptr_t)j->rows + sizeof(DevErrRow) * (uintptr_t)((j->flags & OFDG_ERR_ONE_ROW) ? 1 : n), true};
+  if (j->epe) r[nr++] = Range{(uintptr_t)j->epe, (uintptr_t)j->epe + (uintptr_t)(all * fmt_elem_bytes(j->epe_fmt)), true};
+  if (j->picture) r[nr++] = Range{(uintptr_t)j->picture, (uintptr_t)j->picture + (uintptr_t)(3ull * all), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):
 // Texture::getRandomizedCrop(2W, 2H, rot, zoom, shift), DG:87-109 - the CImg chain
 // get_shift -> rotate -> crop -> resize as ONE resampling along its composed coordinate map.

@@ -26,6 +26,10 @@
 //   host_input_check flow_vis           ofdg_host_flow_vis and ofdg_host_flow_vis_tables on exactly sized heap buffers: the test
 //                                       sizes, both flow formats and layouts, the three norms and both ends of max_flow, with
 //                                       and without dimming, extreme flows and any bit pattern, every refusal
+//   host_input_check flow_error         ofdg_host_flow_error and ofdg_host_flow_error_colours on exactly sized heap buffers: the
+//                                       test sizes, both ground-truth and all three estimate formats, the maps, dist2, every
+//                                       subset of the outputs, both layouts and epe formats, extreme flows and any bit pattern,
+//                                       both ends of est_scale, accumulation, every refusal
 // Deterministic and counted by cases.  Exit 0: no sanitizer report, no escaped exception, probe and decode agree.
 #include <algorithm>
 #include <cctype>
@@ -875,6 +879,139 @@ int flow_vis() {
   return refused == 24 ? 0 : 1;
 }
 
+// ofdg_host_flow_error and ofdg_host_flow_error_colours on heap buffers of exactly the planes' sizes (a byte read or written
+// beside one is a report): float32 and binary16 ground truth, float32, binary16 and bfloat16 estimates that hold zeros, NaN, both
+// infinities, +-2^20, the largest usable value and random bit patterns (a signed overflow in the Q8 components, their
+// differences, the roots, the sums or the bins is a report), both ends of est_scale, no map and a uint8 and a float32 one, without
+// and with dist2, every non-empty subset of the outputs, both layouts and epe formats, per-sample rows, accumulated rows and one
+// row, on 8x2, 24x6, 72x40 and 264x200 with three samples; then every refusal.
+int flow_error() {
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 4; ++size) {
+    const int W = size == 0 ? 8 : size == 1 ? 24 : size == 2 ? 72 : 264, H = size == 0 ? 2 : size == 1 ? 6 : size == 2 ? 40 : 200, n = 3;
+    const size_t px = (size_t)W * H;
+    uint32_t x = 777u + (uint32_t)size;
+    const float special[] = {0.0f, -0.0f, 3.0f, -3.0f, NAN, INFINITY, -INFINITY, 1048576.0f, -1048576.0f, 1048575.9375f, -1048575.9375f, 0.001953125f, 65504.0f, 1e-30f, 3.4e38f};
+    const uint16_t special_h[] = {0x0000, 0x8000, 0x4200, 0xC200, 0x7E00, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF, 0x0001, 0x8001, 0x1800, 0x3C00, 0x03FF, 0xFE00};
+    const auto fill = [&](std::vector<uint8_t>& plane, int bytes) {  // bytes 4: float32; 2: binary16 or bfloat16 bit patterns
+      for (size_t e = 0; e < plane.size() / bytes; ++e) {
+        x = x * 1664525u + 1013904223u;
+        if (bytes == 2) {
+          const uint16_t h = (e % 3) == 0 ? special_h[(x >> 20) % 15] : (uint16_t)(x >> 16);
+          std::memcpy(plane.data() + 2 * e, &h, 2);
+        } else {
+          float v = (e % 3) == 0 ? special[(x >> 20) % 15] : (e % 3) == 1 ? (float)(int)(x >> 20) * 0.37f - 700.0f : 0.0f;
+          if ((e % 7) == 3) std::memcpy(&v, &x, 4);  // any bit pattern
+          std::memcpy(plane.data() + 4 * e, &v, 4);
+        }
+      }
+    };
+    for (int gt_half = 0; gt_half < 2; ++gt_half)
+      for (int est_fmt = 0; est_fmt < 3; ++est_fmt) {
+        std::vector<uint8_t> gt(n * 2 * px * (gt_half ? 2 : 4)), est(n * 2 * px * (est_fmt ? 2 : 4));
+        fill(gt, gt_half ? 2 : 4);
+        fill(est, est_fmt ? 2 : 4);
+        for (int occ_kind = 0; occ_kind < 3; ++occ_kind) {
+          std::vector<uint8_t> occ(occ_kind == 1 ? n * px : occ_kind == 2 ? n * px * 4 : 0), dist2(n * px);
+          for (size_t e = 0; e < occ.size(); ++e) { x = x * 1664525u + 1013904223u; occ[e] = (x >> 24) & 1 ? (uint8_t)(x >> 16) : 0; }  // (float32: any pattern, NaN among them)
+          for (size_t e = 0; e < dist2.size(); ++e) { x = x * 1664525u + 1013904223u; dist2[e] = (uint8_t)(x >> 24); }
+          for (int outputs = 1; outputs < 8; ++outputs) {  // bit 0 rows, 1 epe, 2 picture
+            const int layout = outputs & 1, epe_half = (outputs >> 1) & (occ_kind & 1), with_dist = (outputs + occ_kind) & 1, one_row = occ_kind == 2;
+            std::vector<ofdg_flow_error_row> rows(outputs & 1 ? (one_row ? 1 : n) : 0);
+            std::vector<uint8_t> epe(outputs & 2 ? n * px * (epe_half ? 2 : 4) : 0, 0xA5), picture(outputs & 4 ? n * 3 * px : 0, 0xA5);
+            if (!rows.empty()) std::memset(rows.data(), 0xA5, rows.size() * sizeof(ofdg_flow_error_row));
+            struct ofdg_flow_error_job job;
+            std::memset(&job, 0, sizeof job);
+            job.gt = gt.data(); job.est = est.data(); job.occ = occ_kind ? occ.data() : nullptr; job.dist2 = with_dist ? dist2.data() : nullptr;
+            job.rows = rows.empty() ? nullptr : rows.data(); job.epe = epe.empty() ? nullptr : epe.data(); job.picture = picture.empty() ? nullptr : picture.data();
+            job.gt_fmt = gt_half ? OFDG_FMT_F16 : OFDG_FMT_F32; job.est_fmt = est_fmt == 0 ? OFDG_FMT_F32 : est_fmt == 1 ? OFDG_FMT_F16 : OFDG_FMT_BF16;
+            job.occ_fmt = occ_kind == 1 ? OFDG_FMT_U8 : OFDG_FMT_F32; job.epe_fmt = epe_half ? OFDG_FMT_F16 : OFDG_FMT_F32; job.layout = layout;
+            job.flags = (one_row ? OFDG_ERR_ONE_ROW : 0) | ((occ_kind && (outputs & 4)) ? OFDG_ERR_DIM_OCC : 0);
+            job.est_scale = outputs == 3 ? 1024.0f : outputs == 5 ? -0.0009765625f : 1.0f;
+            job.speed_px[0] = outputs == 7 ? 1e-30f : 10.0f; job.speed_px[1] = outputs == 7 ? 1048576.0f : 40.0f;
+            job.dist2_edge[0] = with_dist ? 1 + outputs : -5; job.dist2_edge[1] = with_dist ? 255 - outputs : 999;
+            for (int pass = 0; pass < (rows.empty() ? 1 : 2); ++pass) {  // the second pass adds to the rows of the first
+              if (pass) job.flags |= OFDG_ERR_ACCUMULATE;
+              const int rc = ofdg_host_flow_error(&job, n, W, H);
+              if (rc) { std::printf("flow_error: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+              ++calls;
+            }
+            sum = sum * 31 + fnv1a((const uint8_t*)rows.data(), rows.size() * sizeof(ofdg_flow_error_row));
+            sum = sum * 31 + fnv1a(epe.data(), epe.size());
+            sum = sum * 31 + fnv1a(picture.data(), picture.size());
+            unsigned long long counted = 0;
+            for (const ofdg_flow_error_row& r : rows) {
+              unsigned long long cells = 0, hist = 0;
+              for (int c = 0; c < 18; ++c) cells += (&r.cell[0][0][0])[c].n;
+              for (int b = 0; b < OFDG_FLOW_ERROR_HIST_BINS; ++b) hist += r.hist[b];
+              if (cells != hist) { std::printf("flow_error: the cells and the histogram disagree\n"); return 1; }
+              counted += cells + r.n_bad_gt + r.n_bad_est;
+            }
+            if (!rows.empty() && counted != 2ull * n * px) { std::printf("flow_error: pixels lost\n"); return 1; }
+          }
+        }
+      }
+  }
+  {
+    std::vector<uint8_t> rgb(30);
+    unsigned total = 0;
+    if (ofdg_host_flow_error_colours(reinterpret_cast<uint8_t(*)[3]>(rgb.data())) != OFDG_OK) { std::printf("flow_error: the colours\n"); return 1; }
+    for (uint8_t b : rgb) total += b;
+    if (total != 4523u) { std::printf("flow_error: the colours sum to %u\n", total); return 1; }
+    ++calls;
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    const size_t px = (size_t)W * H;
+    std::vector<uint8_t> gt(n * 2 * px * 4, 0), est(n * 2 * px * 4, 0), occ(n * px, 1), dist2(n * px, 255), out(n * 672 + n * px * 4 + n * px * 3, 0xA5);
+    struct ofdg_flow_error_job good;
+    std::memset(&good, 0, sizeof good);
+    good.gt = gt.data(); good.est = est.data(); good.occ = occ.data(); good.dist2 = dist2.data();
+    good.rows = (ofdg_flow_error_row*)out.data(); good.epe = out.data() + n * 672; good.picture = out.data() + n * 672 + n * px * 4;
+    good.occ_fmt = OFDG_FMT_U8; good.flags = OFDG_ERR_DIM_OCC; good.est_scale = 1.0f; good.speed_px[0] = 10.0f; good.speed_px[1] = 40.0f;
+    good.dist2_edge[0] = 26; good.dist2_edge[1] = 101;
+    const auto refuse = [&](struct ofdg_flow_error_job j, int ns, int w, int h) {
+      if (ofdg_host_flow_error(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_flow_error: ", 22) == 0) ++refused;
+      else std::printf("flow_error: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_flow_error_job j;
+    if (ofdg_host_flow_error(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.flags |= OFDG_ERR_ONE_ROW; refuse(j, 4, 65536, 21844);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.gt = nullptr; refuse(j, n, W, H);
+    j = good; j.est = nullptr; refuse(j, n, W, H);
+    j = good; j.rows = nullptr; j.epe = nullptr; j.picture = nullptr; j.flags = 0; refuse(j, n, W, H);
+    j = good; j.gt_fmt = OFDG_FMT_BF16; refuse(j, n, W, H);
+    j = good; j.est_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.occ_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.epe_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.layout = 2; refuse(j, n, W, H);
+    j = good; j.flags = 8; refuse(j, n, W, H);
+    j = good; j.reserved[4] = 1; refuse(j, n, W, H);
+    j = good; j.occ = nullptr; refuse(j, n, W, H);
+    j = good; j.picture = nullptr; refuse(j, n, W, H);
+    j = good; j.est_scale = NAN; refuse(j, n, W, H);
+    j = good; j.est_scale = 2048.0f; refuse(j, n, W, H);
+    j = good; j.speed_px[0] = 0.0f; refuse(j, n, W, H);
+    j = good; j.speed_px[1] = NAN; refuse(j, n, W, H);
+    j = good; j.dist2_edge[0] = 0; refuse(j, n, W, H);
+    j = good; j.dist2_edge[1] = 256; refuse(j, n, W, H);
+    j = good; j.epe = gt.data() + 16; refuse(j, n, W, H);
+    j = good; j.picture = occ.data(); refuse(j, n, W, H);
+    j = good; j.rows = (ofdg_flow_error_row*)(out.data() + n * 672 + 16); refuse(j, n, W, H);
+    if (ofdg_host_flow_error_colours(nullptr) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; });
+    if (!clean) { std::printf("flow_error: a refusal wrote something\n"); return 1; }
+    if (ofdg_host_flow_error(&good, n, W, H) != OFDG_OK) { std::printf("flow_error: the valid call failed\n"); return 1; }
+  }
+  std::printf("flow_error calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 29 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "planes") == 0) return planes();
   if (argc >= 2 && std::strcmp(argv[1], "mblur") == 0) return mblur();
@@ -882,8 +1019,9 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
   if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
   if (argc >= 2 && std::strcmp(argv[1], "flow_vis") == 0) return flow_vis();
+  if (argc >= 2 && std::strcmp(argv[1], "flow_error") == 0) return flow_error();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | flow_vis\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | flow_vis | flow_error\n", argv[0]);
   return 2;
 }
