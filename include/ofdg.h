@@ -59,7 +59,8 @@ extern "C" {
  * instead of owning heap pointers (DG:934-940).
  */
 typedef struct ofdg_blueprint {
-  int32_t obj_id;
+  int32_t obj_id;       /* top-level foreground blueprints of one task: distinct and > OFDG_BACKGROUND_ID, in any order (they are
+                           rendered in ascending obj_id); a repeated id is refused with OFDG_EINVAL */
   int32_t obj_type;
   float   init_rot, init_scale, init_trans_x, init_trans_y;
   float   rot, scale, trans_x, trans_y;
@@ -249,7 +250,8 @@ int ofdg_sample_counter(ofdg_ctx* ctx, long long first_index, int n_samples,
  *   label0  uint8   [n,H,W]    index_image0 / index_image1 of blitObject (DG:762-775) as the painter's position of the owner:
  *   label1                     0 = background, k = the k-th top-level foreground object in ascending obj_id; an object owns a
  *                              pixel where its non-AA mask of that frame is 255 (a composite: its composed mask, DG:591-646),
- *                              the last owner in painter's order wins
+ *                              the last owner in painter's order wins.  The ids of a task's foreground blueprints must be
+ *                              distinct and > OFDG_BACKGROUND_ID (else OFDG_EINVAL); their order in the array is free
  *   occ0    float32 [n,1,H,W]  1.0f where the forward flow, rounded as xr = (int)floorf((float)x + u + 0.5f) (likewise y), leaves
  *                              the frame or lands on a frame-1 pixel of another label (label1[yr][xr] != label0[y][x]), else 0.0f
  *   occ1    float32 [n,1,H,W]  the same for frame-1 pixels with flow1, label1 at (x, y) and label0 at the target
@@ -343,7 +345,8 @@ int ofdg_forward_counter_ex_fmt(ofdg_ctx* ctx, long long first_index, int n_samp
  * ofdg_object_table annotates the batch of the LAST render / forward call of this context (the batch ofdg_render_resident
  * and ofdg_debug_coverage speak of).  Row k of sample i is d_rows[i * rows_per_sample + k] and describes the object whose
  * label is k in the numbering of ofdg_extras: row 0 the background, row k the k-th top-level foreground object in ascending
- * obj_id.  d_counts[i] = 1 + n_objects of sample i whatever rows_per_sample is; rows k >= d_counts[i] inside the table are
+ * obj_id (ids within a task are distinct and > OFDG_BACKGROUND_ID, whatever their order in the blueprint array: a task that
+ * repeats one is refused when it is rendered).  d_counts[i] = 1 + n_objects of sample i whatever rows_per_sample is; rows k >= d_counts[i] inside the table are
  * all-zero bytes; objects k >= rows_per_sample are not reported (the count shows the truncation; no error flag is raised).
  * Areas and boxes are of VISIBLE pixels - those whose label is the row's index, i.e. after the painter's order has hidden
  * what lies below: an object wholly covered or moved out of the frame has area 0 and the empty box.

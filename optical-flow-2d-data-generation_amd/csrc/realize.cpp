@@ -151,6 +151,14 @@ int realize_batch(const RealizeConfig& cfg, const ofdg_task* tasks, int n_tasks,
     for (int i = 0; i < task.n_objects; ++i) order[i] = task.first_object + i;
     for (size_t i = 1; i < order.size(); ++i)  // insertion sort by id (already sorted when sampled)
       for (size_t j = i; j > 0 && bps[order[j]].obj_id < bps[order[j - 1]].obj_id; --j) std::swap(order[j], order[j - 1]);
+    // The reference's objects_map keeps the last blueprint of an id (DataGenerator.cpp:1210); labels, occlusion maps and
+    // the object table number objects by their place in this order, so a dropped one would shift every later row: refuse.
+    for (size_t i = 1; i < order.size(); ++i)
+      if (bps[order[i]].obj_id == bps[order[i - 1]].obj_id) {
+        *msg = "foreground object id " + std::to_string(bps[order[i]].obj_id) + " appears more than once in task " + std::to_string(t) +
+               " (ids within a task must be distinct)";
+        return OFDG_EINVAL;
+      }
     for (int bi : order) {
       const ofdg_blueprint& p = bps[bi];
       if (p.obj_id <= OFDG_BACKGROUND_ID) {

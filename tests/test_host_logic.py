@@ -118,6 +118,116 @@ def test_realize_matrices(ofdg):
     assert si == len(sm) and oi == len(om)
 
 
+def _motions(b, bgm, W, H):
+    """(intrinsic, motion) of a blueprint as object_motion composes them (realize.cpp: setIntrinsicTransform, setMotion,
+    addBackgroundMotion)."""
+    ident = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+    intrinsic = mul(mul(ident, rot(b.init_rot)), (1, 0, 0, 1, b.init_trans_x, b.init_trans_y))
+    motion = mul(mul(mul(ident, rot(b.rot)), (b.scale, 0, 0, b.scale, 0, 0)), (1, 0, 0, 1, b.trans_x, b.trans_y))
+    bg_n = mul(mul((1, 0, 0, 1, -W / 2., -H / 2.), bgm), (1, 0, 0, 1, W / 2., H / 2.))
+    return intrinsic, mul(motion, bg_n)
+
+
+def test_realize_matrices_of_composites(ofdg):
+    """Mode 7: an object's matrices come from its own (the composite's) blueprint; a composite's shape rows are its components',
+    each from the component's own init_* / rot / scale / trans composed with the background motion (push_shape); a simple
+    object has one shape row, its own."""
+    W, H, B = 512, 384, 3
+    ident = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+    tasks, bps, n = ofdg.HostSampler(7, W, H).next(B)
+    sm, om = ofdg.host_realize(ofdg.default_params(width=W, height=H, mode=7), 7, 1024, 768, tasks, B, bps, n)
+    si = oi = composites = 0
+    for t in tasks:
+        bg = bps[t.background]
+        bgm = mul(mul(mul(ident, rot(bg.rot)), (bg.scale, 0, 0, bg.scale, 0, 0)), (1, 0, 0, 1, bg.trans_x, bg.trans_y))
+        assert tuple(om[oi][0]) == bgm
+        oi += 1
+        for k in range(t.n_objects):
+            b = bps[t.first_object + k]
+            _, motion = _motions(b, bgm, W, H)
+            assert tuple(om[oi][0]) == motion and tuple(om[oi][1]) == inv(motion)
+            oi += 1
+            parts = [bps[b.first_component + j] for j in range(b.n_components)] if b.obj_type == 3 else [b]
+            composites += b.obj_type == 3
+            for c in parts:
+                c_intrinsic, c_motion = _motions(c, bgm, W, H)
+                assert tuple(sm[si][0]) == c_intrinsic and tuple(sm[si][1]) == mul(c_intrinsic, c_motion)
+                si += 1
+    assert composites >= 10
+    assert oi == len(om) and si == len(sm)
+    assert len(sm) == sum(max(1, bps[t.first_object + k].n_components) for t in tasks for k in range(t.n_objects))
+
+
+def _realize(ofdg, W, H, mode, tasks, n_tasks, bps, n):
+    return ofdg.host_realize(ofdg.default_params(width=W, height=H, mode=mode), 3, 2 * W, 2 * H, tasks, n_tasks, bps, n)
+
+
+def test_realize_counts_at_the_capacity_limits(ofdg):
+    """64 foreground objects (kMaxFgObjects) and 8 components (kMaxComponents) are taken, 65 and 9 are not."""
+    import capacity_scenes as cs
+    W, H, B = 128, 96, 2
+    tasks, bps, n = ofdg.HostSampler(7, W, H, 64).next(B, cap=B * 1024)
+    assert all(t.n_objects == 64 for t in tasks)
+    sm, om = _realize(ofdg, W, H, 7, tasks, B, bps, n)
+    assert len(om) == B * 65
+    assert len(sm) == sum(max(1, bps[t.first_object + k].n_components) for t in tasks for k in range(t.n_objects)) > 2 * 64
+    # 65: the range runs one blueprint into the task's components, still inside the array
+    more = cs.clone_tasks(tasks, B)
+    more[0].n_objects = 65
+    assert more[0].first_object + 65 <= n
+    with pytest.raises(ofdg.OfdgError) as e:
+        _realize(ofdg, W, H, 7, more, B, bps, n)
+    assert e.value.code == ofdg.ECAPACITY and "more than 64" in str(e.value)
+    # 8 components are realised (one more shape row, the last one's own matrices), 9 and 0 are not
+    one, bps1, n1, ci = cs.seven_component_composite(ofdg.HostSampler, W, H)
+    sm7, om7 = _realize(ofdg, W, H, 7, one, 1, bps1, n1)
+    t8, b8, n8 = cs.with_component_added(one, 1, bps1, n1, ci, source=3)
+    sm8, om8 = _realize(ofdg, W, H, 7, t8, 1, b8, n8)
+    assert np.array_equal(om7, om8) and len(sm8) == len(sm7) + 1 and np.array_equal(sm7, sm8[:-1])
+    bg = b8[t8[0].background]
+    bgm = mul(mul(mul((1.0, 0.0, 0.0, 1.0, 0.0, 0.0), rot(bg.rot)), (bg.scale, 0, 0, bg.scale, 0, 0)), (1, 0, 0, 1, bg.trans_x, bg.trans_y))
+    c_intrinsic, c_motion = _motions(b8[b8[ci].first_component + 7], bgm, W, H)
+    assert tuple(sm8[-1][0]) == c_intrinsic and tuple(sm8[-1][1]) == mul(c_intrinsic, c_motion)
+    t9, b9, n9 = cs.with_component_added(t8, 1, b8, n8, ci, source=3)
+    for bad_bps, bad_n, count in ((b9, n9, 9), (cs.clone(bps1, n1), n1, 0)):
+        bad_bps[ci].n_components = count
+        with pytest.raises(ofdg.OfdgError) as e:
+            _realize(ofdg, W, H, 7, one if count == 0 else t9, 1, bad_bps, bad_n)
+        assert e.value.code == ofdg.ECAPACITY and "component range outside [1, 8]" in str(e.value), count
+    # a component run that leaves the array
+    past = cs.clone(bps1, n1)
+    past[ci].first_component = n1 - past[ci].n_components + 1
+    with pytest.raises(ofdg.OfdgError) as e:
+        _realize(ofdg, W, H, 7, one, 1, past, n1)
+    assert e.value.code == ofdg.ECAPACITY and "the array" in str(e.value)
+    past[ci].first_component = n1 - past[ci].n_components  # (the last run that fits is taken)
+    _realize(ofdg, W, H, 7, one, 1, past, n1)
+
+
+def test_realize_sorts_by_id_and_refuses_duplicates(ofdg):
+    """Foreground blueprints may come in any order: objects and shapes are realised in ascending obj_id.  Two blueprints of a
+    task with one id are refused (the reference would keep the last, DG:1210, and every later label / table row would shift)."""
+    import capacity_scenes as cs
+    W, H = 128, 96
+    tasks, bps, n = ofdg.HostSampler(7, W, H, 64).next(1, cap=1024)
+    sm, om = _realize(ofdg, W, H, 7, tasks, 1, bps, n)
+    pt, pb, pn = cs.permuted(tasks, bps, n)  # (a composite's first_component is an index into the array: nothing to fix up)
+    ids = [pb[pt[0].first_object + k].obj_id for k in range(64)]
+    assert ids != sorted(ids) and sorted(ids) == [bps[tasks[0].first_object + k].obj_id for k in range(64)]
+    sm_p, om_p = _realize(ofdg, W, H, 7, pt, 1, pb, pn)
+    assert np.array_equal(om, om_p) and np.array_equal(sm, sm_p)
+    assert len({tuple(m[0]) for m in om}) == 65  # (every object has a motion of its own: the order is visible in the rows)
+    two, bps2, n2 = ofdg.HostSampler(7, W, H, 64).next(2, cap=2048)
+    bps2[two[1].first_object + 63].obj_id = bps2[two[1].first_object + 7].obj_id
+    with pytest.raises(ofdg.OfdgError) as e:
+        _realize(ofdg, W, H, 7, two, 2, bps2, n2)
+    assert e.value.code == ofdg.EINVAL and "object id 17 " in str(e.value) and "task 1" in str(e.value)
+    bps2[two[1].first_object + 63].obj_id = 9  # (below the sampler's ids, distinct: accepted, and realised first)
+    sm2, om2 = _realize(ofdg, W, H, 7, two, 2, bps2, n2)
+    _, motion = _motions(bps2[two[1].first_object + 63], tuple(om2[65][0]), W, H)
+    assert tuple(om2[66][0]) == motion
+
+
 def test_realize_rejects_bad_blueprints(ofdg):
     hs = ofdg.HostSampler(5, 128, 96)
     tasks, bps, n = hs.next(1)
