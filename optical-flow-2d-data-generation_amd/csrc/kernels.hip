@@ -24,6 +24,15 @@
 
 namespace ofdg {
 
+// The file's vector types: what one 4-, 8- or 16-byte load or store instruction moves.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
 // --------------------------------------------------------------------------
 // small helpers
 // --------------------------------------------------------------------------
@@ -762,13 +771,12 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
 }
 // ... and the loads through it name the GLOBAL address space (a pointer rebuilt from integers is generic: flat_load with a
 // 64-bit address per lane; as global memory it is global_load v, voffset32, s[base])
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) const u32x2_t g_uint2;
+typedef __attribute__((address_space(1))) const u32x2 g_uint2;
 typedef __attribute__((address_space(1))) const uint32_t g_uint32;
 typedef __attribute__((address_space(1))) const char g_char;
 __device__ __forceinline__ uint2 gload2(const char* base, uint32_t off) {
   asm("" : "+v"(off));  // (the offset stays a 32-bit VGPR: a select folded into a 64-bit phi would defeat the saddr form)
-  const u32x2_t v = *(g_uint2*)((g_char*)base + off);
+  const u32x2 v = *(g_uint2*)((g_char*)base + off);
   return make_uint2(v.x, v.y);
 }
 __device__ __forceinline__ uint32_t gload1(const char* base, uint32_t off) { return *(g_uint32*)((g_char*)base + off); }
@@ -927,7 +935,6 @@ __device__ __forceinline__ int lerp_u8(const Taps& t, float Icc, float Inc, floa
 // Warp crops as the kernels read them: two interleaved planes of w*h float pairs - (flow x, flow y), then
 // (iflow x, iflow y) - so that a pixel's displacement is ONE 8-byte load.
 __device__ __forceinline__ float2 crop_pair(const DevCropRef& C, int plane_pair, int x, int y) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   const f32x2 v = *(OFDG_GLOBAL const f32x2*)(C.data + ((size_t)plane_pair * C.w * C.h + (size_t)y * C.w + x) * 2);
   return make_float2(v.x, v.y);
 }
@@ -1223,8 +1230,7 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
   {
     uint32_t boff = inside ? (uint32_t)(yy * gb.pitch + xx) * 4u : 0u;
     asm("" : "+v"(boff));
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x4_t v = *(__attribute__((address_space(1))) const u32x4_t*)((g_char*)reinterpret_cast<const char*>(btex) + boff);  // frame 0: identity warp == copy (DG:667-668, 680)
+    const u32x4 v = *(__attribute__((address_space(1))) const u32x4*)((g_char*)reinterpret_cast<const char*>(btex) + boff);  // frame 0: identity warp == copy (DG:667-668, 680)
     bq = make_uint4(v.x, v.y, v.z, v.w);
   }
   uint32_t pre_c0[kPre], pre_c1[kPre], pre_rec[kPre];
@@ -1573,8 +1579,6 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
     // dword per plane (v_perm_b32, no conversion), 4-byte streaming stores (a row of a plane is 8-byte aligned: W % 8 == 0).
     // fp16 flow: the float32 flow converted once, round to nearest even (v_cvt_f16_f32 under the default rounding mode - not
     // v_cvt_pkrtz, which rounds towards zero), 8-byte stores.  Offsets in pixels, scaled by the element size of each output.
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     const size_t plane = (size_t)W * H;
     uint32_t op = (uint32_t)y * (uint32_t)W + (uint32_t)x0;
     asm volatile("" : "+v"(op));
@@ -1647,7 +1651,6 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
       // __fadd_rn / floorf / float compares), sends each of the lane's four pixels - the linear index yr * W + xr of the other
       // frame's pixel, kOccOutside when it leaves the frame.  Taken here, from the registers: the stored flow may be binary16,
       // and an occlusion bit must not depend on that.  One 16-byte vector store per frame into the chain's workspace.
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
       auto targets = [&](const float (&uu)[kPx], const float (&vv)[kPx]) {
         uint32_t t[kPx];
 #pragma unroll
@@ -1668,7 +1671,6 @@ __device__ __forceinline__ void compose_rigid(const DevSample* __restrict__ samp
   // u8 -> float planes (DG:1229-1245); streaming 16-byte stores, never re-read.  Every plane is a wave-uniform base
   // (SGPR pair) + one 32-bit byte offset per lane; the offset is made opaque so that no address arithmetic is
   // hoisted above the object loop (it would hold registers there).
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   const size_t plane = (size_t)W * H;
   uint32_t ob = ((uint32_t)y * (uint32_t)W + (uint32_t)x0) * 4u;
   asm volatile("" : "+v"(ob));
@@ -1779,8 +1781,7 @@ __global__ __launch_bounds__(64) void compose_rigid_fmt_pow2_kernel(
 // of frame f is occluded (1.0f) when its flow, rounded as (int)floorf((float)x + u + 0.5f), leaves the frame or lands on a
 // pixel of the other frame with another label.  A lane takes 4 adjacent pixels: 16-byte flow loads, one 4-byte label load,
 // 4 byte gathers of the other frame's label (local: mostly L2 hits), 16-byte stores.  occ0 / occ1 NULL: not computed.
-typedef float occ_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ occ_f32x4 occlusion_quad(const float* __restrict__ u_plane, const float* __restrict__ v_plane,
+__device__ __forceinline__ f32x4 occlusion_quad(const float* __restrict__ u_plane, const float* __restrict__ v_plane,
                                                  const uint8_t* __restrict__ own, const uint8_t* __restrict__ other, int x0, int y,
                                                  int W, int H) {
   const float4 u = *reinterpret_cast<const float4*>(u_plane);
@@ -1798,7 +1799,7 @@ __device__ __forceinline__ occ_f32x4 occlusion_quad(const float* __restrict__ u_
     const uint32_t t = in ? (uint32_t)other[off] : 0u;
     o[p] = (in && t == ((l >> (8 * p)) & 255u)) ? 0.f : 1.f;
   }
-  const occ_f32x4 r = {o[0], o[1], o[2], o[3]};
+  const f32x4 r = {o[0], o[1], o[2], o[3]};
   return r;
 }
 __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict__ flow, const float* __restrict__ flow1,
@@ -1814,13 +1815,13 @@ __global__ __launch_bounds__(256) void occlusion_kernel(const float* __restrict_
   const size_t pix = (size_t)y * W + x0;
   if (occ0) {
     const float* f = flow + (size_t)s * 2 * plane + pix;
-    const occ_f32x4 o = occlusion_quad(f, f + plane, label0 + s * plane + pix, label1 + s * plane + pix, x0, y, W, H);
-    __builtin_nontemporal_store(o, reinterpret_cast<occ_f32x4*>(occ0 + s * plane + pix));
+    const f32x4 o = occlusion_quad(f, f + plane, label0 + s * plane + pix, label1 + s * plane + pix, x0, y, W, H);
+    __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(occ0 + s * plane + pix));
   }
   if (occ1) {
     const float* f = flow1 + (size_t)s * 2 * plane + pix;
-    const occ_f32x4 o = occlusion_quad(f, f + plane, label1 + s * plane + pix, label0 + s * plane + pix, x0, y, W, H);
-    __builtin_nontemporal_store(o, reinterpret_cast<occ_f32x4*>(occ1 + s * plane + pix));
+    const f32x4 o = occlusion_quad(f, f + plane, label1 + s * plane + pix, label0 + s * plane + pix, x0, y, W, H);
+    __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(occ1 + s * plane + pix));
   }
 }
 
@@ -1880,8 +1881,8 @@ __global__ __launch_bounds__(256) void occlusion_fmt_kernel(const uint32_t* __re
     if (out_fmt & kOutOccU8) {
       __builtin_nontemporal_store(o, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(dst) + pix));
     } else {
-      const occ_f32x4 f = {(float)(o & 1u), (float)((o >> 8) & 1u), (float)((o >> 16) & 1u), (float)(o >> 24)};
-      __builtin_nontemporal_store(f, reinterpret_cast<occ_f32x4*>(static_cast<float*>(dst) + pix));
+      const f32x4 f = {(float)(o & 1u), (float)((o >> 8) & 1u), (float)((o >> 16) & 1u), (float)(o >> 24)};
+      __builtin_nontemporal_store(f, reinterpret_cast<f32x4*>(static_cast<float*>(dst) + pix));
     }
   };
   if (occ0) store(occ0, occlusion_fmt_quad(tgt0 + pix, label0 + pix, label1 + sp, (uint32_t)plane));
@@ -2272,7 +2273,6 @@ __device__ __forceinline__ bool bgprep_region(const DevBgPrep& p, const DevResiz
 // strict-fp32 operations per texel, evaluated on float pairs (v_pk_mul_f32 / v_pk_add_f32: one instruction for both), and
 // - when no lane of the wave leaves the image (no mirroring, no clamping: the usual case, the rotation is a few degrees) -
 // without the wrap logic.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct RotPair { f32x2 mx, my; };
 // mx = (w2 + xc * ca) + yc * sa;  my = (h2 - xc * sa) + yc * ca   (element-wise: exactly the scalar sequence)
 __device__ __forceinline__ RotPair bgprep_rot_coords(const DevBgPrep& p, float xc0, float xc1, float yc) {
@@ -3122,6 +3122,99 @@ __global__ void tables_kernel(uint8_t* add_tbl, uint8_t* sub_tbl, uint8_t* aa_tb
 }
 
 // --------------------------------------------------------------------------
+// Plane accessors of the post-processing kernels below: how a lane reads and writes its QUAD - four adjacent pixels of one
+// row of one plane - in each storage format.  The format rules, stated once (the host twins in csrc/ofdg_device.h and
+// csrc/host_api.cpp hold the same):
+//   flow       float32 (16 bytes a quad), binary16 (8 bytes) or - flow_error's estimate only - bfloat16 (8 bytes, err_bf16),
+//              widened to float32; usable where both components are below 2^20 in magnitude (flow_usable: a NaN is not),
+//              finite where the exponent is not all ones (flow_finite).
+//   image      uint8 (one 4-byte word, pixel p in byte p) or float32 (16 bytes) taken to a byte by photo_index: clamped to
+//              [0, 255], a NaN to 0, ties to even.  A byte goes back as itself or as (float)byte.
+//   occlusion  uint8 (4 bytes) or float32 (16 bytes): a pixel is hidden where its element is NON-ZERO (a NaN is hidden, -0.0
+//              is not).
+// A quad_* function takes a ready pointer to the lane's first element - the address arithmetic, 32-bit or size_t, stays with
+// the kernel, which knows its guard - and issues one load or store instruction of the quad's size; the elem_* forms read one
+// element at the caller's index, in the caller's index type.  Stores of whole pieces are non-temporal: the planes are read
+// next by another kernel.  A new op reads and writes its planes through these.
+// --------------------------------------------------------------------------
+constexpr int quad_fmt(bool half) { return half ? OFDG_FMT_F16 : OFDG_FMT_F32; }
+template <int kFmt> struct FlowFmt;  // the element and the quad of a flow format, for the kernel's pointer arithmetic
+template <> struct FlowFmt<OFDG_FMT_F32> { typedef float elem; typedef f32x4 quad; };
+template <> struct FlowFmt<OFDG_FMT_F16> { typedef _Float16 elem; typedef f16x4 quad; };
+template <> struct FlowFmt<OFDG_FMT_BF16> { typedef uint16_t elem; typedef u32x2 quad; };
+__device__ __forceinline__ bool flow_finite(float x) { return mblur_finite(x); }            // (the twins' names, as the
+__device__ __forceinline__ bool flow_usable(float u, float v) { return vis_usable(u, v); }  // ops that came first left them)
+template <int kFmt>  // OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16
+__device__ __forceinline__ void quad_load(const void* p4, float (&o)[4]) {
+  if constexpr (kFmt == OFDG_FMT_F16) {
+    const f16x4 a = *static_cast<const f16x4*>(p4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = (float)a[p];
+  } else if constexpr (kFmt == OFDG_FMT_BF16) {
+    const u32x2 a = *static_cast<const u32x2*>(p4);
+    o[0] = err_bf16(a[0] & 0xFFFFu);
+    o[1] = err_bf16(a[0] >> 16);
+    o[2] = err_bf16(a[1] & 0xFFFFu);
+    o[3] = err_bf16(a[1] >> 16);
+  } else {
+    static_assert(kFmt == OFDG_FMT_F32, "a flow format");
+    const f32x4 a = *static_cast<const f32x4*>(p4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = a[p];
+  }
+}
+template <int kFmt, typename Index>  // OFDG_FMT_F32 or OFDG_FMT_F16: element e of the plane(s) at base
+__device__ __forceinline__ float elem_load(const uint8_t* __restrict__ base, Index e) {
+  static_assert(kFmt == OFDG_FMT_F32 || kFmt == OFDG_FMT_F16, "a flow format of a source plane");
+  return (float)reinterpret_cast<const typename FlowFmt<kFmt>::elem*>(base)[e];
+}
+template <bool kU8, typename T>  // T: uint32_t or int; o[0..3] are the quad's bytes
+__device__ __forceinline__ void quad_load_bytes(const void* p4, T* o) {
+  if constexpr (kU8) {
+    const uint32_t w = *static_cast<const uint32_t*>(p4);
+    o[0] = (T)(w & 255u); o[1] = (T)((w >> 8) & 255u); o[2] = (T)((w >> 16) & 255u); o[3] = (T)(w >> 24);
+  } else {
+    const f32x4 e = *static_cast<const f32x4*>(p4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = (T)photo_index(e[p]);
+  }
+}
+template <bool kU8>
+__device__ __forceinline__ uint32_t elem_load_byte(const uint8_t* __restrict__ base, uint32_t e) {
+  if constexpr (kU8) return base[e];
+  else return (uint32_t)photo_index(reinterpret_cast<const float*>(base)[e]);
+}
+template <bool kU8>  // bit p: pixel p of the quad is hidden
+__device__ __forceinline__ uint32_t quad_load_hidden(const void* p4) {
+  uint32_t hidden = 0u;
+  if constexpr (kU8) {
+    const uint32_t o = *static_cast<const uint32_t*>(p4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) hidden |= (((o >> (8 * p)) & 255u) != 0u ? 1u : 0u) << p;
+  } else {
+    const f32x4 o = *static_cast<const f32x4*>(p4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) hidden |= (o[p] != 0.0f ? 1u : 0u) << p;
+  }
+  return hidden;
+}
+__device__ __forceinline__ uint32_t quad_word(const uint32_t (&b)[4]) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
+// The quads of a pair of lanes - 8 bytes of a uint8 plane, whose rows start at multiples of 8 bytes only - stored by the even
+// lane, the odd lane's word fetched with a wave shuffle: every lane of the wave calls this, `on` says whether the lane's
+// quad exists (the lanes of a pair agree).  dst8: the lane's own quad.
+__device__ __forceinline__ void quad_store_bytes_pair(void* dst8, uint32_t word, bool on) {
+  const u32x2 o = {word, (uint32_t)__shfl_down((int)word, 1)};
+  if (on && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, static_cast<u32x2*>(dst8));
+}
+__device__ __forceinline__ void quad_store_bytes_f32(void* dst, const uint32_t (&b)[4], bool on) {
+  const f32x4 o = {(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
+  if (on) __builtin_nontemporal_store(o, static_cast<f32x4*>(dst));
+}
+__device__ __forceinline__ void quad_store_u32x4(u32x4* p, u32x4 v) {
+  __builtin_nontemporal_store(v, p);  // (whole lines, read next by another kernel: measured against plain stores, CHANGELOG)
+}
+
+// --------------------------------------------------------------------------
 // Per-sample flow statistics (ofdg_flow_stats): displacement histogram, counts, Q8 sums and the largest |flow|^2 of a
 // [n,2,H,W] flow tensor, float32 or binary16, with an optional [n,1,H,W] occlusion map (float32 or uint8).  One launch
 // behind the call that wrote the planes; a pure function of the buffers.
@@ -3151,8 +3244,7 @@ template <bool kHalf, int kOcc>  // kOcc: 0 no map, 1 float32, 2 uint8
 __global__ __launch_bounds__(kStatsThreads) void flow_stats_kernel(const void* __restrict__ flow, const void* __restrict__ occ, int n,
                                                                    uint32_t plane_quads, float bin_px, float inv_bin, int visible_only,
                                                                    int one_row, DevFlowStatsRow* __restrict__ rows) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef typename FlowFmt<quad_fmt(kHalf)>::quad FlowQuad;
   __shared__ uint32_t s_hist[kStatsThreads / 64][kFlowHistBins];
   __shared__ uint32_t s_cnt[3];
   __shared__ unsigned long long s_sum[3];
@@ -3176,31 +3268,17 @@ __global__ __launch_bounds__(kStatsThreads) void flow_stats_kernel(const void* _
       float u[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
       uint32_t hidden = 0;  // bit j: the map says pixel j is occluded
       if (act) {
-        if constexpr (kHalf) {
-          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu + q], b = reinterpret_cast<const f16x4*>(flow)[pv + q];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { u[j] = (float)a[j]; v[j] = (float)b[j]; }
-        } else {
-          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu + q], b = reinterpret_cast<const f32x4*>(flow)[pv + q];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { u[j] = a[j]; v[j] = b[j]; }
-        }
-        if constexpr (kOcc == 1) {
-          const f32x4 o = reinterpret_cast<const f32x4*>(occ)[po + q];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) hidden |= (o[j] != 0.0f ? 1u : 0u) << j;
-        } else if constexpr (kOcc == 2) {
-          const uint32_t o = reinterpret_cast<const uint32_t*>(occ)[po + q];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) hidden |= (((o >> (8 * j)) & 255u) != 0u ? 1u : 0u) << j;
-        }
+        quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + (pu + q), u);
+        quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + (pv + q), v);
+        if constexpr (kOcc == 1) hidden = quad_load_hidden<false>(static_cast<const f32x4*>(occ) + (po + q));
+        else if constexpr (kOcc == 2) hidden = quad_load_hidden<true>(static_cast<const uint32_t*>(occ) + (po + q));
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool occluded = (hidden >> j) & 1u;
         n_occ += occluded ? 1u : 0u;
         const bool look = act && !(occluded && visible_only);
-        const bool good = fabsf(u[j]) < 1048576.0f && fabsf(v[j]) < 1048576.0f;
+        const bool good = flow_usable(u[j], v[j]);
         n_bad += (look && !good) ? 1u : 0u;
         const bool counted = look && good;
         int b = -1;
@@ -3327,11 +3405,7 @@ __device__ __forceinline__ void pyr_store(const DevFlowPyramid& out, int k, int 
 template <bool kHalf, bool kHalfOut, int kOcc>  // kOcc: 0 no map, 1 float32, 2 uint8
 __global__ __launch_bounds__(kPyrThreads) void flow_pyramid_kernel(const void* __restrict__ flow, const void* __restrict__ occ, int n, int W,
                                                                    int H, int scaled, int n_weights, const DevFlowPyramid out) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+  typedef typename FlowFmt<quad_fmt(kHalf)>::quad FlowQuad;
   typedef typename std::conditional<kHalfOut, _Float16, float>::type OutT;
   typedef typename std::conditional<kHalfOut, f16x2, f32x2>::type OutT2;
   __shared__ float s_u[4][4], s_v[4][4];
@@ -3354,32 +3428,18 @@ __global__ __launch_bounds__(kPyrThreads) void flow_pyramid_kernel(const void* _
       in[j] = x0 < W && y0 + j < H;
       const size_t q = in[j] ? ((size_t)(y0 + j) * W + x0) / 4 : 0;  // in quads of a plane (W % 4 == 0)
       const size_t pu = (size_t)s * 2 * (plane / 4) + q, pv = pu + plane / 4, po = (size_t)s * (plane / 4) + q;
-      {  // (a row outside the frame reads the plane's first quad instead and is masked below: no branch around the loads)
-        if constexpr (kHalf) {
-          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu], b = reinterpret_cast<const f16x4*>(flow)[pv];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { u[j][i] = (float)a[i]; v[j][i] = (float)b[i]; }
-        } else {
-          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu], b = reinterpret_cast<const f32x4*>(flow)[pv];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { u[j][i] = a[i]; v[j][i] = b[i]; }
-        }
-        if constexpr (kOcc == 1) {
-          const f32x4 o = reinterpret_cast<const f32x4*>(occ)[po];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) hidden[j] |= (o[i] != 0.0f ? 1u : 0u) << i;
-        } else if constexpr (kOcc == 2) {
-          const uint32_t o = reinterpret_cast<const uint32_t*>(occ)[po];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) hidden[j] |= (((o >> (8 * i)) & 255u) != 0u ? 1u : 0u) << i;
-        }
-      }
+      // (a row outside the frame reads the plane's first quad instead and is masked below: no branch around the loads)
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + pu, u[j]);
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + pv, v[j]);
+      if constexpr (kOcc == 1) hidden[j] = quad_load_hidden<false>(static_cast<const f32x4*>(occ) + po);
+      else if constexpr (kOcc == 2) hidden[j] = quad_load_hidden<true>(static_cast<const uint32_t*>(occ) + po);
     }
     uint32_t c0[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
+        // (flow_usable, spelled out: as a call in this chain of && the kernel compiled to half as many basic blocks again)
         const bool usable = in[j] && fabsf(u[j][i]) < 1048576.0f && fabsf(v[j][i]) < 1048576.0f && !((hidden[j] >> i) & 1u);
         u[j][i] = usable ? u[j][i] : 0.0f;
         v[j][i] = usable ? v[j][i] : 0.0f;
@@ -3487,10 +3547,6 @@ constexpr int kCropSlots = 14;   // channels of the eight planes: 3 3 2 2 1 1 1 
 struct DevCropGrid {
   uint32_t first_block[kCropSlots + 1];  // slot s owns blocks [first_block[s], first_block[s + 1]) of blockIdx.x
 };
-typedef uint32_t crop_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void crop_store(crop_u32x4* p, crop_u32x4 v) {
-  __builtin_nontemporal_store(v, p);  // (whole lines, read next by another kernel: measured against plain stores, CHANGELOG)
-}
 // kWords 32-bit words of destination: the kWords * 4 / kES elements that start at element `first` of the tensor at p (`last`:
 // index of its last whole word), in destination order - reversed element by element when the row is mirrored.
 template <int kES, int kWords>
@@ -3544,7 +3600,7 @@ __device__ __forceinline__ void crop_move(const void* __restrict__ src, void* __
   const uint32_t pieces = (uint32_t)crop_w * (uint32_t)crop_h / kPixels;
   const uint32_t* const sp = static_cast<const uint32_t*>(src);
   const size_t plane = chan * ((size_t)W * H), last = tensor_words - 1;
-  crop_u32x4* const dp = static_cast<crop_u32x4*>(dst) + chan * pieces;
+  u32x4* const dp = static_cast<u32x4*>(dst) + chan * pieces;
   const uint32_t q0 = block * (kCropThreads * kCropPerLane) + threadIdx.x;
   const uint32_t dX = (kCropThreads * kPixels) % (uint32_t)crop_w, dY = (kCropThreads * kPixels) / (uint32_t)crop_w;
   const bool mirrored = r.flags & 1;
@@ -3571,8 +3627,8 @@ __device__ __forceinline__ void crop_move(const void* __restrict__ src, void* __
   for (int j = 0; j < kCropPerLane; ++j) {
     const uint32_t q = q0 + j * kCropThreads;
     if (q < pieces) {
-      const crop_u32x4 o = {v[j][0] ^ sign, v[j][1] ^ sign, v[j][2] ^ sign, v[j][3] ^ sign};
-      crop_store(dp + q, o);
+      const u32x4 o = {v[j][0] ^ sign, v[j][1] ^ sign, v[j][2] ^ sign, v[j][3] ^ sign};
+      quad_store_u32x4(dp + q, o);
     }
   }
 }
@@ -3589,7 +3645,7 @@ __device__ __forceinline__ void crop_occ_window(const void* __restrict__ src, vo
   const uint32_t* const sp = static_cast<const uint32_t*>(src);
   const uint32_t* const fp = static_cast<const uint32_t*>(flow);
   const size_t last = n * frame * kES / 4 - 1, flow_last = n * 2 * frame * kFES / 4 - 1;
-  crop_u32x4* const dp = static_cast<crop_u32x4*>(dst) + sample * pieces;
+  u32x4* const dp = static_cast<u32x4*>(dst) + sample * pieces;
   const uint32_t q0 = block * (kCropThreads * kCropPerLane) + threadIdx.x;
   const uint32_t dX = (kCropThreads * kPixels) % (uint32_t)crop_w, dY = (kCropThreads * kPixels) / (uint32_t)crop_w;
   const bool mirrored = r.flags & 1;
@@ -3634,8 +3690,8 @@ __device__ __forceinline__ void crop_occ_window(const void* __restrict__ src, vo
       for (int i = 0; i < kOccWords; ++i) o[g * kOccWords + i] = m[i];
     }
     if (ok) {
-      const crop_u32x4 ov = {o[0], o[1], o[2], o[3]};
-      crop_store(dp + q, ov);
+      const u32x4 ov = {o[0], o[1], o[2], o[3]};
+      quad_store_u32x4(dp + q, ov);
     }
     a = crop_advance(a, dX, dY, (uint32_t)crop_w);
   }
@@ -3709,6 +3765,7 @@ static_assert(kPhotoBlockPixels % (kPhotoThreads * 16) == 0, "whole rounds of pi
 template <bool kSrcU8, bool kDstU8>
 __global__ __launch_bounds__(kPhotoThreads) void photo_kernel(const DevPhotoJob job, int n, int W, int H, uint32_t per_channel) {
   constexpr int kP = kDstU8 ? 16 : 4;  // elements of a piece
+  typedef typename std::conditional<kSrcU8, uint8_t, float>::type SrcT;
   __shared__ float table[256];
   const uint32_t slot = blockIdx.x / per_channel, block = blockIdx.x - slot * per_channel;
   const int f = (int)(slot / 3u) + (job.src[0] ? 0 : 1), c = (int)(slot % 3u);
@@ -3741,21 +3798,9 @@ __global__ __launch_bounds__(kPhotoThreads) void photo_kernel(const DevPhotoJob 
     const size_t chan = ((size_t)i * 3 + (size_t)c) * plane;  // first element of the channel in the tensor
     for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kPhotoThreads * kP)) {
       int k[kP];
-      if constexpr (kSrcU8) {
-        const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + chan + at);
+      const SrcT* const sp = static_cast<const SrcT*>(src) + chan + at;
 #pragma unroll
-        for (int q = 0; q < kP / 4; ++q) {
-          const uint32_t w = sp[q];
-          k[4 * q] = (int)(w & 255u); k[4 * q + 1] = (int)((w >> 8) & 255u); k[4 * q + 2] = (int)((w >> 16) & 255u); k[4 * q + 3] = (int)(w >> 24);
-        }
-      } else {
-        const float4* const sp = reinterpret_cast<const float4*>(static_cast<const float*>(src) + chan + at);
-#pragma unroll
-        for (int q = 0; q < kP / 4; ++q) {
-          const float4 e = sp[q];
-          k[4 * q] = photo_index(e.x); k[4 * q + 1] = photo_index(e.y); k[4 * q + 2] = photo_index(e.z); k[4 * q + 3] = photo_index(e.w);
-        }
-      }
+      for (int q = 0; q < kP / 4; ++q) quad_load_bytes<kSrcU8>(sp + 4 * q, k + 4 * q);
       float v[kP];
 #pragma unroll
       for (int q = 0; q < kP; ++q) v[q] = table[k[q]];
@@ -3770,15 +3815,15 @@ __global__ __launch_bounds__(kPhotoThreads) void photo_kernel(const DevPhotoJob 
           v[4 * q + 3] = photo_add_noise(v[4 * q + 3], scale, w.w);
         }
       }
-      crop_u32x4 o;
+      u32x4 o;
       if constexpr (kDstU8) {
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           o[q] = (uint32_t)rintf(v[4 * q]) | ((uint32_t)rintf(v[4 * q + 1]) << 8) | ((uint32_t)rintf(v[4 * q + 2]) << 16) | ((uint32_t)rintf(v[4 * q + 3]) << 24);
-        crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + chan + at), o);
+        quad_store_u32x4(reinterpret_cast<u32x4*>(static_cast<uint8_t*>(dst) + chan + at), o);
       } else {
-        o = crop_u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-        crop_store(reinterpret_cast<crop_u32x4*>(static_cast<float*>(dst) + chan + at), o);
+        o = u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        quad_store_u32x4(reinterpret_cast<u32x4*>(static_cast<float*>(dst) + chan + at), o);
       }
     }
     __syncthreads();  // (the next sample of this workgroup writes the table again)
@@ -3827,8 +3872,8 @@ constexpr int kSpatialRowPairs = kSpatialThreads / 4 / kSpatialTileQ;  // row pa
 constexpr int kSpatialPasses = OFDG_SPATIAL_PASSES;                  // 8 pixels a lane: the record's draw is paid once for them (measured against 4 and 8: CHANGELOG)
 constexpr int kSpatialTileP = kSpatialRowPairs * kSpatialPasses;     // row pairs of a tile
 static_assert(kSpatialTileQ * kSpatialRowPairs * 4 == kSpatialThreads, "four lanes per unit of a pass");
-__device__ __forceinline__ void spatial_store(void* p, crop_u32x4 v) {
-  crop_store(static_cast<crop_u32x4*>(p), v);  // (whole pieces, read next by another kernel: measured against plain stores, CHANGELOG)
+__device__ __forceinline__ void spatial_store(void* p, u32x4 v) {
+  quad_store_u32x4(static_cast<u32x4*>(p), v);  // (whole pieces, read next by another kernel: measured against plain stores, CHANGELOG)
 }
 template <bool kImageU8, bool kFlowHalf, bool kOccU8>
 __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpatialJob job, int n, int W, int H, uint32_t tiles_x) {
@@ -3936,10 +3981,10 @@ __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpati
         for (int c = 0; c < 3; ++c) {
           if constexpr (kImageU8) {
             const uint32_t w = spatial_to_byte(img[c][0]) | (spatial_to_byte(img[c][1]) << 8) | (spatial_to_byte(img[c][2]) << 16) | (spatial_to_byte(img[c][3]) << 24);
-            const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+            const u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
             if (j == 0u) spatial_store(d_img + ((size_t)i * 3 + c) * window + at, o);
           } else {
-            const crop_u32x4 o = {__float_as_uint(img[c][0]), __float_as_uint(img[c][1]), __float_as_uint(img[c][2]), __float_as_uint(img[c][3])};
+            const u32x4 o = {__float_as_uint(img[c][0]), __float_as_uint(img[c][1]), __float_as_uint(img[c][2]), __float_as_uint(img[c][3])};
             spatial_store(d_img + (((size_t)i * 3 + c) * window + at) * 4u, o);
           }
         }
@@ -3950,10 +3995,10 @@ __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpati
           const float* const v = c ? fv : fu;
           if constexpr (kFlowHalf) {
             const uint32_t w0 = spatial_half_bits(v[0]) | (spatial_half_bits(v[1]) << 16), w1 = spatial_half_bits(v[2]) | (spatial_half_bits(v[3]) << 16);
-            const crop_u32x4 o = {w0, w1, (uint32_t)__shfl_down((int)w0, 1), (uint32_t)__shfl_down((int)w1, 1)};
+            const u32x4 o = {w0, w1, (uint32_t)__shfl_down((int)w0, 1), (uint32_t)__shfl_down((int)w1, 1)};
             if ((j & 1u) == 0u) spatial_store(d_flow + (((size_t)i * 2 + c) * window + at) * 2u, o);
           } else {
-            const crop_u32x4 o = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+            const u32x4 o = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
             spatial_store(d_flow + (((size_t)i * 2 + c) * window + at) * 4u, o);
           }
         }
@@ -3961,16 +4006,16 @@ __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpati
       if (s_occ) {
         if constexpr (kOccU8) {
           const uint32_t w = hid[0] | (hid[1] << 8) | (hid[2] << 16) | (hid[3] << 24);
-          const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+          const u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
           if (j == 0u) spatial_store(d_occ + (size_t)i * window + at, o);
         } else {
-          const crop_u32x4 o = {hid[0] ? 0x3f800000u : 0u, hid[1] ? 0x3f800000u : 0u, hid[2] ? 0x3f800000u : 0u, hid[3] ? 0x3f800000u : 0u};
+          const u32x4 o = {hid[0] ? 0x3f800000u : 0u, hid[1] ? 0x3f800000u : 0u, hid[2] ? 0x3f800000u : 0u, hid[3] ? 0x3f800000u : 0u};
           spatial_store(d_occ + ((size_t)i * window + at) * 4u, o);
         }
       }
       if (s_lab) {
         const uint32_t w = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-        const crop_u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+        const u32x4 o = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
         if (j == 0u) spatial_store(d_lab + (size_t)i * window + at, o);
       }
     }
@@ -4002,7 +4047,7 @@ __global__ __launch_bounds__(kSpatialThreads) void spatial_kernel(const DevSpati
 constexpr int kPackThreads = 256;
 constexpr int kPackSrcF32 = 0, kPackSrcU8 = 1, kPackSrcF16 = 2;  // how pack_unit reads a source
 struct PackRun {          // the wave's units
-  crop_u32x4* lds;        // the wave's 64 * kP slots
+  u32x4* lds;        // the wave's 64 * kP slots
   uint32_t first_unit;    // the unit of its lane 0
   uint32_t units;         // units of a channel: those from here on do not exist
 };
@@ -4013,11 +4058,11 @@ __device__ __forceinline__ void pack_wave_sync() {  // the wave's LDS accesses s
 }
 // The wave's run of 64 * kP pieces from `dp` on, lane l holding pieces l * kP .. l * kP + kP - 1 of it.
 template <int kP>
-__device__ __forceinline__ void pack_store_run(const crop_u32x4 (&piece)[kP], uint8_t* dp, const PackRun& run) {
+__device__ __forceinline__ void pack_store_run(const u32x4 (&piece)[kP], uint8_t* dp, const PackRun& run) {
   const uint32_t lane = threadIdx.x & 63u;
-  crop_u32x4* const d = reinterpret_cast<crop_u32x4*>(dp);
+  u32x4* const d = reinterpret_cast<u32x4*>(dp);
   if constexpr (kP == 1) {
-    if (run.first_unit + lane < run.units) crop_store(d + lane, piece[0]);
+    if (run.first_unit + lane < run.units) quad_store_u32x4(d + lane, piece[0]);
   } else {
 #pragma unroll
     for (int m = 0; m < kP; ++m) run.lds[lane * kP + m] = piece[m];
@@ -4025,7 +4070,7 @@ __device__ __forceinline__ void pack_store_run(const crop_u32x4 (&piece)[kP], ui
 #pragma unroll
     for (int m = 0; m < kP; ++m) {
       const uint32_t idx = (uint32_t)m * 64u + lane;
-      if (run.first_unit + idx / kP < run.units) crop_store(d + idx, run.lds[idx]);
+      if (run.first_unit + idx / kP < run.units) quad_store_u32x4(d + idx, run.lds[idx]);
     }
     pack_wave_sync();  // (the slots are written again by the next channel, plane group or sample)
   }
@@ -4079,28 +4124,28 @@ __device__ __forceinline__ void pack_unit(const uint8_t* const (&sp)[kC], const 
 #pragma unroll
     for (int c = 0; c < kC; ++c) {
       if constexpr (kWide) {
-        const crop_u32x4 piece[2] = {crop_u32x4{o[c][0], o[c][1], o[c][2], o[c][3]}, crop_u32x4{o[c][4], o[c][5], o[c][6], o[c][7]}};
+        const u32x4 piece[2] = {u32x4{o[c][0], o[c][1], o[c][2], o[c][3]}, u32x4{o[c][4], o[c][5], o[c][6], o[c][7]}};
         pack_store_run<2>(piece, dp + (size_t)c * chan_bytes, run);
       } else {
-        const crop_u32x4 piece[1] = {crop_u32x4{o[c][0] | (o[c][1] << 16), o[c][2] | (o[c][3] << 16), o[c][4] | (o[c][5] << 16), o[c][6] | (o[c][7] << 16)}};
+        const u32x4 piece[1] = {u32x4{o[c][0] | (o[c][1] << 16), o[c][2] | (o[c][3] << 16), o[c][4] | (o[c][5] << 16), o[c][6] | (o[c][7] << 16)}};
         pack_store_run<1>(piece, dp + (size_t)c * chan_bytes, run);
       }
     }
   } else {
     // element e = pixel * kC + channel of the unit is o[e % kC][e / kC]
     constexpr int kP = kWide ? 2 * kC : kC;
-    crop_u32x4 piece[kP];
+    u32x4 piece[kP];
     if constexpr (kWide) {
 #pragma unroll
       for (int m = 0; m < kP; ++m) {
         const int e = 4 * m;
-        piece[m] = crop_u32x4{o[e % kC][e / kC], o[(e + 1) % kC][(e + 1) / kC], o[(e + 2) % kC][(e + 2) / kC], o[(e + 3) % kC][(e + 3) / kC]};
+        piece[m] = u32x4{o[e % kC][e / kC], o[(e + 1) % kC][(e + 1) / kC], o[(e + 2) % kC][(e + 2) / kC], o[(e + 3) % kC][(e + 3) / kC]};
       }
     } else {
 #pragma unroll
       for (int m = 0; m < kP; ++m) {
         const int e = 8 * m;
-        piece[m] = crop_u32x4{o[e % kC][e / kC] | (o[(e + 1) % kC][(e + 1) / kC] << 16), o[(e + 2) % kC][(e + 2) / kC] | (o[(e + 3) % kC][(e + 3) / kC] << 16),
+        piece[m] = u32x4{o[e % kC][e / kC] | (o[(e + 1) % kC][(e + 1) / kC] << 16), o[(e + 2) % kC][(e + 2) / kC] | (o[(e + 3) % kC][(e + 3) / kC] << 16),
                               o[(e + 4) % kC][(e + 4) / kC] | (o[(e + 5) % kC][(e + 5) / kC] << 16),
                               o[(e + 6) % kC][(e + 6) / kC] | (o[(e + 7) % kC][(e + 7) / kC] << 16)};
       }
@@ -4114,7 +4159,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_kernel(const DevPackJob job
   constexpr uint32_t kImgSES = kImgU8 ? 1 : 4, kImgDES = kImgDst == OFDG_FMT_F32 ? 4 : 2;
   // the largest kP: planar 2 (a float32 channel); channels-last the frames' 8 * C * es / 16, or a float32 flow's 4
   constexpr int kImgP = kImgC * (int)kImgDES / 2, kMaxP = !kNhwc ? 2 : kImgP > 4 ? kImgP : 4;
-  __shared__ crop_u32x4 slots[kPackThreads * kMaxP];
+  __shared__ u32x4 slots[kPackThreads * kMaxP];
   const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (6 * plane < 2^31: pack_arg_error)
   const uint32_t units = plane / 8u;
   const uint32_t group = blockIdx.x / per_group;
@@ -4191,15 +4236,9 @@ constexpr int kBndRows = kBndTileH + 2 * kBndMaxRadius;                // region
 constexpr int kBndOwn = kBndTileW * kBndTileH / (8 * kBndThreads);     // rows of 8 columns a lane owns in pass 4
 static_assert(kBndTileW % 64 == 0 && kBndOwn >= 1 && kBndOwn * 8 * kBndThreads == kBndTileW * kBndTileH && kBndThreads % (kBndTileW / 8) == 0 &&
               kBndTileW + kBndPad + kBndMaxRadius <= 64 * kBndWords, "a lane owns whole runs of 8 columns; the region fits its words");
-typedef uint32_t bnd_u32x2 __attribute__((ext_vector_type(2)));
-template <bool kHalf>
-__device__ __forceinline__ float bnd_flow(const uint8_t* __restrict__ flow, size_t at) {
-  if constexpr (kHalf) return (float)reinterpret_cast<const _Float16*>(flow)[at];
-  else return reinterpret_cast<const float*>(flow)[at];
-}
 // 8 bits -> 8 bytes of 1 / 0, the lowest bit in the lowest byte
-__device__ __forceinline__ bnd_u32x2 bnd_spread(uint32_t bits) {
-  return bnd_u32x2{((bits & 15u) * 0x00204081u) & 0x01010101u, (((bits >> 4) & 15u) * 0x00204081u) & 0x01010101u};
+__device__ __forceinline__ u32x2 bnd_spread(uint32_t bits) {
+  return u32x2{((bits & 15u) * 0x00204081u) & 0x01010101u, (((bits >> 4) & 15u) * 0x00204081u) & 0x01010101u};
 }
 template <bool kHalf, bool kLabels>
 __global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundaryJob job, int n, int W, int H, uint32_t tiles_x) {
@@ -4239,9 +4278,9 @@ __global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundary
           }
         }
         if (want_r || want_d) {
-          const float u = bnd_flow<kHalf>(fl, p), v = bnd_flow<kHalf>(fl, plane + p);
-          if (want_r) step_r = boundary_step(u, v, bnd_flow<kHalf>(fl, p + 1), bnd_flow<kHalf>(fl, plane + p + 1), t2);
-          if (want_d) step_d = boundary_step(u, v, bnd_flow<kHalf>(fl, p + W), bnd_flow<kHalf>(fl, plane + p + W), t2);
+          const float u = elem_load<quad_fmt(kHalf)>(fl, p), v = elem_load<quad_fmt(kHalf)>(fl, plane + p);
+          if (want_r) step_r = boundary_step(u, v, elem_load<quad_fmt(kHalf)>(fl, p + 1), elem_load<quad_fmt(kHalf)>(fl, plane + p + 1), t2);
+          if (want_d) step_d = boundary_step(u, v, elem_load<quad_fmt(kHalf)>(fl, p + W), elem_load<quad_fmt(kHalf)>(fl, plane + p + W), t2);
         }
         right = __ballot(step_r);
         down = __ballot(step_d);
@@ -4301,8 +4340,8 @@ __global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundary
           uint32_t o[8];
 #pragma unroll
           for (int b = 0; b < 8; ++b) o[b] = best[k][b] <= r2 ? best[k][b] : 255u;
-          __builtin_nontemporal_store(bnd_u32x2{o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24), o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24)},
-                                      reinterpret_cast<bnd_u32x2*>(d_dist + (size_t)i * plane + (size_t)Y * W + X));
+          __builtin_nontemporal_store(u32x2{o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24), o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24)},
+                                      reinterpret_cast<u32x2*>(d_dist + (size_t)i * plane + (size_t)Y * W + X));
         }
       }
       if (d_edge) {
@@ -4312,7 +4351,7 @@ __global__ __launch_bounds__(kBndThreads) void boundary_kernel(const DevBoundary
           const int Y = y0 + cy0 + k;
           if (Y >= H) break;
           const uint32_t bits = (uint32_t)(s_edge[cy0 + k + R][bit >> 6] >> (bit & 63)) & 255u;
-          __builtin_nontemporal_store(bnd_spread(bits), reinterpret_cast<bnd_u32x2*>(d_edge + (size_t)i * plane + (size_t)Y * W + X));
+          __builtin_nontemporal_store(bnd_spread(bits), reinterpret_cast<u32x2*>(d_edge + (size_t)i * plane + (size_t)Y * W + X));
         }
       }
     }
@@ -4422,19 +4461,19 @@ __device__ __forceinline__ void erase_fill_row(uint8_t* base, uint32_t e0, int w
   }
   for (int p = lane; p < pieces; p += 64) {
     const uint32_t e = e0 + (uint32_t)(head + p * kP);
-    crop_u32x4 o;
+    u32x4 o;
     if (noise) {
 #pragma unroll
       for (int q = 0; q < kP / 4; ++q) {
         const CropWords nw = crop_philox(CropWords{(e >> 2) + (uint32_t)q, (uint32_t)f, 0x0c75u, 0u}, k0, k1);
         if constexpr (kB == 1) o[q] = (nw.x >> 24) | ((nw.y >> 24) << 8) | ((nw.z >> 24) << 16) | ((nw.w >> 24) << 24);
-        else o = crop_u32x4{__float_as_uint((float)(nw.x >> 24)), __float_as_uint((float)(nw.y >> 24)), __float_as_uint((float)(nw.z >> 24)), __float_as_uint((float)(nw.w >> 24))};
+        else o = u32x4{__float_as_uint((float)(nw.x >> 24)), __float_as_uint((float)(nw.y >> 24)), __float_as_uint((float)(nw.z >> 24)), __float_as_uint((float)(nw.w >> 24))};
       }
     } else {
       const uint32_t v = kB == 1 ? byte * 0x01010101u : __float_as_uint((float)byte);
-      o = crop_u32x4{v, v, v, v};
+      o = u32x4{v, v, v, v};
     }
-    crop_store(reinterpret_cast<crop_u32x4*>(base + (size_t)e * kB), o);
+    quad_store_u32x4(reinterpret_cast<u32x4*>(base + (size_t)e * kB), o);
   }
 }
 
@@ -4448,9 +4487,8 @@ __device__ __forceinline__ void erase_fill_row(uint8_t* base, uint32_t e0, int w
 // launch left in `work`; workgroup 0 writes the sanitised record with the fill bytes from lane 0 with six vector stores.
 template <bool kU8, bool kOccU8, bool kHalf>
 __global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEraseJob job, int n, int W, int H, uint32_t occ_blocks) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
   constexpr int kB = kU8 ? 1 : 4, kOB = kOccU8 ? 1 : 4;
+  typedef typename FlowFmt<quad_fmt(kHalf)>::quad FlowQuad;
   const uint32_t plane = (uint32_t)W * (uint32_t)H;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const bool mark = job.flags & OFDG_ERASE_OCC;
@@ -4467,14 +4505,14 @@ __global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEra
         fb[s] = !((frames >> f) & 1) || job.fill == OFDG_ERASE_NOISE ? 0u
                 : job.fill == OFDG_ERASE_CONST ? (uint32_t)job.color[c] : erase_mean_byte(job.work[i].sum[f][c], plane);
       }
-      crop_u32x4* const o = reinterpret_cast<crop_u32x4*>(job.recs_out + i);
+      u32x4* const o = reinterpret_cast<u32x4*>(job.recs_out + i);
       const DevEraseRect q0 = r.rect[0], q1 = r.rect[1], q2 = r.rect[2], q3 = r.rect[3];
-      o[0] = crop_u32x4{(uint32_t)r.count, (uint32_t)q0.x0, (uint32_t)q0.y0, (uint32_t)q0.w};
-      o[1] = crop_u32x4{(uint32_t)q0.h, (uint32_t)q0.frame, (uint32_t)q1.x0, (uint32_t)q1.y0};
-      o[2] = crop_u32x4{(uint32_t)q1.w, (uint32_t)q1.h, (uint32_t)q1.frame, (uint32_t)q2.x0};
-      o[3] = crop_u32x4{(uint32_t)q2.y0, (uint32_t)q2.w, (uint32_t)q2.h, (uint32_t)q2.frame};
-      o[4] = crop_u32x4{(uint32_t)q3.x0, (uint32_t)q3.y0, (uint32_t)q3.w, (uint32_t)q3.h};
-      o[5] = crop_u32x4{(uint32_t)q3.frame, fb[0] | (fb[1] << 8) | (fb[2] << 16) | (fb[3] << 24), fb[4] | (fb[5] << 8), 0u};
+      o[0] = u32x4{(uint32_t)r.count, (uint32_t)q0.x0, (uint32_t)q0.y0, (uint32_t)q0.w};
+      o[1] = u32x4{(uint32_t)q0.h, (uint32_t)q0.frame, (uint32_t)q1.x0, (uint32_t)q1.y0};
+      o[2] = u32x4{(uint32_t)q1.w, (uint32_t)q1.h, (uint32_t)q1.frame, (uint32_t)q2.x0};
+      o[3] = u32x4{(uint32_t)q2.y0, (uint32_t)q2.w, (uint32_t)q2.h, (uint32_t)q2.frame};
+      o[4] = u32x4{(uint32_t)q3.x0, (uint32_t)q3.y0, (uint32_t)q3.w, (uint32_t)q3.h};
+      o[5] = u32x4{(uint32_t)q3.frame, fb[0] | (fb[1] << 8) | (fb[2] << 16) | (fb[3] << 24), fb[4] | (fb[5] << 8), 0u};
     }
     if (blockIdx.x < (uint32_t)kEraseFillBlocks) {
       const int k = (int)blockIdx.x / (4 * kEraseFillSplit), pl = ((int)blockIdx.x / kEraseFillSplit) % 4, part = (int)blockIdx.x % kEraseFillSplit;
@@ -4513,15 +4551,8 @@ __global__ __launch_bounds__(kEraseThreads) void erase_apply_kernel(const DevEra
       const size_t pu = (size_t)i * 2 * plane_quads, pv = pu + plane_quads, po = (size_t)i * plane_quads;  // in quads
       for (uint32_t qd = q_begin + threadIdx.x; qd < q_end; qd += (uint32_t)kEraseThreads) {
         float u[4], v[4];
-        if constexpr (kHalf) {
-          const f16x4 a = reinterpret_cast<const f16x4*>(flow)[pu + qd], c = reinterpret_cast<const f16x4*>(flow)[pv + qd];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) { u[s] = (float)a[s]; v[s] = (float)c[s]; }
-        } else {
-          const f32x4 a = reinterpret_cast<const f32x4*>(flow)[pu + qd], c = reinterpret_cast<const f32x4*>(flow)[pv + qd];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) { u[s] = a[s]; v[s] = c[s]; }
-        }
+        quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + (pu + qd), u);
+        quad_load<quad_fmt(kHalf)>(static_cast<const FlowQuad*>(flow) + (pv + qd), v);
         const uint32_t at = qd * 4u;
         const int y = (int)(at / (uint32_t)W), x = (int)(at - (uint32_t)y * (uint32_t)W);  // (W % 8 == 0: a quad lies in one row)
         uint32_t hits = 0;
@@ -4581,33 +4612,22 @@ __device__ __forceinline__ JitterFrame jitter_frame_uniform(const DevJitterRec& 
 // source), float32 as 16-byte ones through the index rule
 template <bool kU8, int kP>
 __device__ __forceinline__ void jitter_load_channel(const void* src, size_t at, int (&v)[kP]) {
-  if constexpr (kU8) {
-    const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + at);
+  typedef typename std::conditional<kU8, uint8_t, float>::type SrcT;
+  const SrcT* const sp = static_cast<const SrcT*>(src) + at;
 #pragma unroll
-    for (int q = 0; q < kP / 4; ++q) {
-      const uint32_t w = sp[q];
-      v[4 * q] = (int)(w & 255u); v[4 * q + 1] = (int)((w >> 8) & 255u); v[4 * q + 2] = (int)((w >> 16) & 255u); v[4 * q + 3] = (int)(w >> 24);
-    }
-  } else {
-    const float4* const sp = reinterpret_cast<const float4*>(static_cast<const float*>(src) + at);
-#pragma unroll
-    for (int q = 0; q < kP / 4; ++q) {
-      const float4 e = sp[q];
-      v[4 * q] = photo_index(e.x); v[4 * q + 1] = photo_index(e.y); v[4 * q + 2] = photo_index(e.z); v[4 * q + 3] = photo_index(e.w);
-    }
-  }
+  for (int q = 0; q < kP / 4; ++q) quad_load_bytes<kU8>(sp + 4 * q, v + 4 * q);
 }
 // one 16-byte piece of a destination channel: 16 bytes, or 4 times (float)byte
 template <bool kU8, int kP>
 __device__ __forceinline__ void jitter_store_channel(void* dst, size_t at, const int (&v)[kP]) {
-  crop_u32x4 o;
+  u32x4 o;
   if constexpr (kU8) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) o[q] = (uint32_t)v[4 * q] | ((uint32_t)v[4 * q + 1] << 8) | ((uint32_t)v[4 * q + 2] << 16) | ((uint32_t)v[4 * q + 3] << 24);
-    crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + at), o);
+    quad_store_u32x4(reinterpret_cast<u32x4*>(static_cast<uint8_t*>(dst) + at), o);
   } else {
-    o = crop_u32x4{__float_as_uint((float)v[0]), __float_as_uint((float)v[1]), __float_as_uint((float)v[2]), __float_as_uint((float)v[3])};
-    crop_store(reinterpret_cast<crop_u32x4*>(static_cast<float*>(dst) + at), o);
+    o = u32x4{__float_as_uint((float)v[0]), __float_as_uint((float)v[1]), __float_as_uint((float)v[2]), __float_as_uint((float)v[3])};
+    quad_store_u32x4(reinterpret_cast<u32x4*>(static_cast<float*>(dst) + at), o);
   }
 }
 // The operations at the places [0, places) of `ops` on kP pixels.  The place loop stays a loop, its switch is uniform; the
@@ -4720,11 +4740,11 @@ __global__ __launch_bounds__(kJitterThreads) void jitter_apply_kernel(const DevJ
     const DevJitterRec r = jitter_record(job, i);
     if (job.recs_out && blockIdx.x == 0u && threadIdx.x == 0u) {
       const int m0 = jitter_mean_of(job, r, i, 0, plane), m1 = jitter_mean_of(job, r, i, 1, plane);
-      crop_u32x4* const o = reinterpret_cast<crop_u32x4*>(job.recs_out + i);
-      o[0] = crop_u32x4{(uint32_t)r.brightness[0], (uint32_t)r.brightness[1], (uint32_t)r.contrast[0], (uint32_t)r.contrast[1]};
-      o[1] = crop_u32x4{(uint32_t)r.saturation[0], (uint32_t)r.saturation[1], (uint32_t)r.hue[0], (uint32_t)r.hue[1]};
-      o[2] = crop_u32x4{(uint32_t)r.order[0], (uint32_t)r.order[1], (uint32_t)r.shared, (uint32_t)m0};
-      o[3] = crop_u32x4{(uint32_t)m1, 0u, 0u, 0u};
+      u32x4* const o = reinterpret_cast<u32x4*>(job.recs_out + i);
+      o[0] = u32x4{(uint32_t)r.brightness[0], (uint32_t)r.brightness[1], (uint32_t)r.contrast[0], (uint32_t)r.contrast[1]};
+      o[1] = u32x4{(uint32_t)r.saturation[0], (uint32_t)r.saturation[1], (uint32_t)r.hue[0], (uint32_t)r.hue[1]};
+      o[2] = u32x4{(uint32_t)r.order[0], (uint32_t)r.order[1], (uint32_t)r.shared, (uint32_t)m0};
+      o[3] = u32x4{(uint32_t)m1, 0u, 0u, 0u};
     }
     const JitterFrame p = jitter_frame_uniform(r, f);
     const size_t base = (size_t)i * 3 * plane;
@@ -4736,7 +4756,7 @@ __global__ __launch_bounds__(kJitterThreads) void jitter_apply_kernel(const DevJ
           for (uint32_t at = first + threadIdx.x * (uint32_t)kP; at < end; at += (uint32_t)(kJitterThreads * kP)) {
             const size_t e = (base + (size_t)c * plane + at) * kB;
             const uint32_t* const sp = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src) + e);
-            crop_store(reinterpret_cast<crop_u32x4*>(static_cast<uint8_t*>(dst) + e), crop_u32x4{sp[0], sp[1], sp[2], sp[3]});
+            quad_store_u32x4(reinterpret_cast<u32x4*>(static_cast<uint8_t*>(dst) + e), u32x4{sp[0], sp[1], sp[2], sp[3]});
           }
         continue;
       }
@@ -4788,16 +4808,8 @@ constexpr bool kMblurWindow = OFDG_MBLUR_WINDOW != 0;
 constexpr int kMblurHalo = 16;  // pixels of halo on every side of the tile (and one more column and row for ix + 1, iy + 1)
 constexpr int kMblurWinW = kMblurTileW + 2 * kMblurHalo + 1, kMblurWinH = kMblurTileH + 2 * kMblurHalo + 1;
 static_assert(kMblurTileW / 4 * kMblurTileH == kMblurThreads, "a lane per four pixels of the tile");
-template <bool kSrcU8>
-__device__ __forceinline__ uint32_t mblur_load_byte(const uint8_t* __restrict__ sp, uint32_t e) {
-  if constexpr (kSrcU8) return sp[e];
-  else return (uint32_t)photo_index(reinterpret_cast<const float*>(sp)[e]);
-}
 template <bool kSrcU8, bool kDstU8, bool kFlowHalf>
 __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob job, int n, int W, int H, uint32_t tiles_x) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   constexpr int kSES = kSrcU8 ? 1 : 4, kDES = kDstU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
   __shared__ uint32_t win[kMblurWindow ? kMblurWinW * kMblurWinH : 1];
   __shared__ uint32_t paths[2][kMblurThreads / 64];  // [parity of the sample's turn][wave]: bit 0 a tap beside the centre, bit 1 one beyond the halo
@@ -4819,14 +4831,15 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
     else r = mblur_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
     r = mblur_sanitise(r);
     if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u)
-      *reinterpret_cast<crop_u32x4*>(job.recs_out + i) = crop_u32x4{__float_as_uint(r.shutter[0]), __float_as_uint(r.shutter[1]), 0u, 0u};
+      *reinterpret_cast<u32x4*>(job.recs_out + i) = u32x4{__float_as_uint(r.shutter[0]), __float_as_uint(r.shutter[1]), 0u, 0u};
     const float s = f ? r.shutter[1] : r.shutter[0];
     const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
     uint32_t out[3][4] = {};  // the bytes to store: the centre piece, unless taps say otherwise
     float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (inside) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
+      for (int c = 0; c < 3; ++c) {  // (quad_load_bytes, spelled out: through the call the float32-source kernels were scheduled
+                                     // otherwise, 27 instructions longer, and the copy path measured 1 - 2 % slower)
         if constexpr (kSrcU8) {
           const uint32_t w = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)c * plane + at);
           out[c][0] = w & 255u; out[c][1] = (w >> 8) & 255u; out[c][2] = (w >> 16) & 255u; out[c][3] = w >> 24;
@@ -4838,22 +4851,15 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
       }
       if (s > 0.0f) {  // (uniform: a frame with shutter 0 reads no flow)
         const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
-        if constexpr (kFlowHalf) {
-          const f16x4 a = *reinterpret_cast<const f16x4*>(fp), b = *reinterpret_cast<const f16x4*>(fp + (size_t)plane * kFES);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) { u[p] = (float)a[p]; v[p] = (float)b[p]; }
-        } else {
-          const f32x4 a = *reinterpret_cast<const f32x4*>(fp), b = *reinterpret_cast<const f32x4*>(fp + (size_t)plane * kFES);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) { u[p] = a[p]; v[p] = b[p]; }
-        }
+        quad_load<quad_fmt(kFlowHalf)>(fp, u);
+        quad_load<quad_fmt(kFlowHalf)>(fp + (size_t)plane * kFES, v);
       }
     }
     int m[4], sx[4], sy[4];
     bool blurred = false, far = false;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const bool finite = mblur_finite(u[p]) && mblur_finite(v[p]);
+      const bool finite = flow_finite(u[p]) && flow_finite(v[p]);
       const int Dx = finite ? mblur_half(u[p], s) : 0, Dy = finite ? mblur_half(v[p], s) : 0;
       m[p] = mblur_taps_side(Dx, Dy, cap);
       sx[p] = m[p] ? mblur_step(Dx, m[p]) : 0;
@@ -4870,7 +4876,7 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
       for (int j = (int)threadIdx.x; j < kMblurWinW * kMblurWinH; j += kMblurThreads) {
         const int wy = j / kMblurWinW, wx = j - wy * kMblurWinW;
         const uint32_t e = (uint32_t)spatial_clamp(wy0 + wy, H) * (uint32_t)W + (uint32_t)spatial_clamp(wx0 + wx, W);
-        win[j] = mblur_load_byte<kSrcU8>(sp, e) | (mblur_load_byte<kSrcU8>(sp, plane + e) << 8) | (mblur_load_byte<kSrcU8>(sp, 2u * plane + e) << 16);
+        win[j] = elem_load_byte<kSrcU8>(sp, e) | (elem_load_byte<kSrcU8>(sp, plane + e) << 8) | (elem_load_byte<kSrcU8>(sp, 2u * plane + e) << 16);
       }
       __syncthreads();
 #pragma unroll
@@ -4906,12 +4912,12 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
           const uint32_t xa = (uint32_t)spatial_clamp(Qx >> 8, W), xb = (uint32_t)spatial_clamp((Qx >> 8) + 1, W);
           const uint32_t ya = (uint32_t)spatial_clamp(Qy >> 8, H) * (uint32_t)W, yb = (uint32_t)spatial_clamp((Qy >> 8) + 1, H) * (uint32_t)W;
           const uint32_t wk = mblur_weight(k, mp);
-          S0 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, ya + xa), mblur_load_byte<kSrcU8>(sp, ya + xb), mblur_load_byte<kSrcU8>(sp, yb + xa),
-                               mblur_load_byte<kSrcU8>(sp, yb + xb), fx, fy);
-          S1 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, plane + ya + xa), mblur_load_byte<kSrcU8>(sp, plane + ya + xb),
-                               mblur_load_byte<kSrcU8>(sp, plane + yb + xa), mblur_load_byte<kSrcU8>(sp, plane + yb + xb), fx, fy);
-          S2 += wk * mblur_tap(mblur_load_byte<kSrcU8>(sp, 2u * plane + ya + xa), mblur_load_byte<kSrcU8>(sp, 2u * plane + ya + xb),
-                               mblur_load_byte<kSrcU8>(sp, 2u * plane + yb + xa), mblur_load_byte<kSrcU8>(sp, 2u * plane + yb + xb), fx, fy);
+          S0 += wk * mblur_tap(elem_load_byte<kSrcU8>(sp, ya + xa), elem_load_byte<kSrcU8>(sp, ya + xb), elem_load_byte<kSrcU8>(sp, yb + xa),
+                               elem_load_byte<kSrcU8>(sp, yb + xb), fx, fy);
+          S1 += wk * mblur_tap(elem_load_byte<kSrcU8>(sp, plane + ya + xa), elem_load_byte<kSrcU8>(sp, plane + ya + xb),
+                               elem_load_byte<kSrcU8>(sp, plane + yb + xa), elem_load_byte<kSrcU8>(sp, plane + yb + xb), fx, fy);
+          S2 += wk * mblur_tap(elem_load_byte<kSrcU8>(sp, 2u * plane + ya + xa), elem_load_byte<kSrcU8>(sp, 2u * plane + ya + xb),
+                               elem_load_byte<kSrcU8>(sp, 2u * plane + yb + xa), elem_load_byte<kSrcU8>(sp, 2u * plane + yb + xb), fx, fy);
         }
         out[0][p] = mblur_byte(S0); out[1][p] = mblur_byte(S1); out[2][p] = mblur_byte(S2);
       }
@@ -4920,14 +4926,8 @@ __global__ __launch_bounds__(kMblurThreads) void mblur_kernel(const DevMblurJob 
     uint8_t* const dp = d_img + (size_t)i * 3 * plane * kDES;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      if constexpr (kDstU8) {
-        const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
-        const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
-        if (inside && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
-      } else {
-        const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
-        if (inside) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
-      }
+      if constexpr (kDstU8) quad_store_bytes_pair(dp + (uint32_t)c * plane + at, quad_word(out[c]), inside);
+      else quad_store_bytes_f32(dp + ((size_t)c * plane + at) * 4u, out[c], inside);
     }
   }
 }
@@ -4956,16 +4956,8 @@ constexpr int kReprojTileW = 64, kReprojTileH = 16;
 constexpr int kReprojWords = 23;  // the 32-bit words of a frame's block ahead of `reserved`
 static_assert(kReprojTileW / 4 * kReprojTileH == kReprojThreads, "a lane per four pixels of the tile");
 static_assert(offsetof(DevReprojFrameRow, reserved) == 4 * kReprojWords && offsetof(DevReprojFrameRow, sum_err) == 96, "the words and the 64-bit sums the kernel adds to");
-template <bool kHalf>
-__device__ __forceinline__ float reproj_load_flow(const uint8_t* __restrict__ fp, uint32_t e) {
-  if constexpr (kHalf) return (float)reinterpret_cast<const _Float16*>(fp)[e];
-  else return reinterpret_cast<const float*>(fp)[e];
-}
 template <bool kSrcU8, bool kFlowHalf>
 __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevReprojJob job, int n, int W, int H, uint32_t tiles_x) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   constexpr int kSES = kSrcU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
   __shared__ uint32_t s_words[2][kReprojThreads / 64][kReprojWords];  // [parity of the sample's turn][wave]
   __shared__ unsigned long long s_sums[2][kReprojThreads / 64][4];    // sum_err visible, hidden, sum_fb2_visible, max_fb2_visible
@@ -5000,39 +4992,19 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
     uint32_t hidden = 0u;  // bit p: the map says pixel p is hidden
     if (act) {
       const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
-      if constexpr (kFlowHalf) {
-        const f16x4 a = *reinterpret_cast<const f16x4*>(fp), b = *reinterpret_cast<const f16x4*>(fp + (size_t)plane * kFES);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { u[p] = (float)a[p]; v[p] = (float)b[p]; }
-      } else {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(fp), b = *reinterpret_cast<const f32x4*>(fp + (size_t)plane * kFES);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { u[p] = a[p]; v[p] = b[p]; }
-      }
+      quad_load<quad_fmt(kFlowHalf)>(fp, u);
+      quad_load<quad_fmt(kFlowHalf)>(fp + (size_t)plane * kFES, v);
       if (with_err) {
         const uint8_t* const sp = s_own + (size_t)i * 3 * plane * kSES;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          if constexpr (kSrcU8) {
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(sp + (uint32_t)c * plane + at);
-            own[c][0] = w & 255u; own[c][1] = (w >> 8) & 255u; own[c][2] = (w >> 16) & 255u; own[c][3] = w >> 24;
-          } else {
-            const f32x4 e = *reinterpret_cast<const f32x4*>(sp + ((size_t)c * plane + at) * 4u);
-#pragma unroll
-            for (int p = 0; p < 4; ++p) own[c][p] = (uint32_t)photo_index(e[p]);
-          }
+          if constexpr (kSrcU8) quad_load_bytes<true>(sp + (uint32_t)c * plane + at, own[c]);
+          else quad_load_bytes<false>(sp + ((size_t)c * plane + at) * 4u, own[c]);
         }
       }
       if (s_occ) {
-        if (occ_u8) {
-          const uint32_t o = *reinterpret_cast<const uint32_t*>(s_occ + (size_t)i * plane + at);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) hidden |= (((o >> (8 * p)) & 255u) != 0u ? 1u : 0u) << p;
-        } else {
-          const f32x4 o = *reinterpret_cast<const f32x4*>(s_occ + ((size_t)i * plane + at) * 4u);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) hidden |= (o[p] != 0.0f ? 1u : 0u) << p;
-        }
+        if (occ_u8) hidden = quad_load_hidden<true>(s_occ + (size_t)i * plane + at);
+        else hidden = quad_load_hidden<false>(s_occ + ((size_t)i * plane + at) * 4u);
       }
     }
     uint32_t out[3][4] = {};
@@ -5045,7 +5017,7 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
     unsigned long long sum_fb2 = 0ull, max_fb2 = 0ull;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+      const bool bad = !(flow_finite(u[p]) && flow_finite(v[p]));
       const int Dx = bad ? 0 : reproj_q8(u[p]), Dy = bad ? 0 : reproj_q8(v[p]);
       const int Qx0 = 256 * (X0 + p) + Dx, Qy0 = 256 * Y + Dy;
       const bool in = act && !bad && reproj_inside(Qx0, Qy0, W, H);
@@ -5061,8 +5033,8 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             const uint32_t o = (uint32_t)c * plane;
-            const uint32_t w = reproj_byte(mblur_tap(mblur_load_byte<kSrcU8>(op, o + ya + xa), mblur_load_byte<kSrcU8>(op, o + ya + xb),
-                                                     mblur_load_byte<kSrcU8>(op, o + yb + xa), mblur_load_byte<kSrcU8>(op, o + yb + xb), fx, fy));
+            const uint32_t w = reproj_byte(mblur_tap(elem_load_byte<kSrcU8>(op, o + ya + xa), elem_load_byte<kSrcU8>(op, o + ya + xb),
+                                                     elem_load_byte<kSrcU8>(op, o + yb + xa), elem_load_byte<kSrcU8>(op, o + yb + xb), fx, fy));
             out[c][p] = w;
             const uint32_t d = w > own[c][p] ? w - own[c][p] : own[c][p] - w;
             err = d > err ? d : err;
@@ -5071,12 +5043,12 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
           errs |= err << (8 * p);
         }
         if (with_fb) {
-          const float b0 = reproj_load_flow<kFlowHalf>(bp, ya + xa), b1 = reproj_load_flow<kFlowHalf>(bp, ya + xb);
-          const float b2 = reproj_load_flow<kFlowHalf>(bp, yb + xa), b3 = reproj_load_flow<kFlowHalf>(bp, yb + xb);
-          const float c0 = reproj_load_flow<kFlowHalf>(bp, plane + ya + xa), c1 = reproj_load_flow<kFlowHalf>(bp, plane + ya + xb);
-          const float c2 = reproj_load_flow<kFlowHalf>(bp, plane + yb + xa), c3 = reproj_load_flow<kFlowHalf>(bp, plane + yb + xb);
-          const bool finite = mblur_finite(b0) && mblur_finite(b1) && mblur_finite(b2) && mblur_finite(b3) && mblur_finite(c0) && mblur_finite(c1) &&
-                              mblur_finite(c2) && mblur_finite(c3);
+          const float b0 = elem_load<quad_fmt(kFlowHalf)>(bp, ya + xa), b1 = elem_load<quad_fmt(kFlowHalf)>(bp, ya + xb);
+          const float b2 = elem_load<quad_fmt(kFlowHalf)>(bp, yb + xa), b3 = elem_load<quad_fmt(kFlowHalf)>(bp, yb + xb);
+          const float c0 = elem_load<quad_fmt(kFlowHalf)>(bp, plane + ya + xa), c1 = elem_load<quad_fmt(kFlowHalf)>(bp, plane + ya + xb);
+          const float c2 = elem_load<quad_fmt(kFlowHalf)>(bp, plane + yb + xa), c3 = elem_load<quad_fmt(kFlowHalf)>(bp, plane + yb + xb);
+          const bool finite = flow_finite(b0) && flow_finite(b1) && flow_finite(b2) && flow_finite(b3) && flow_finite(c0) && flow_finite(c1) &&
+                              flow_finite(c2) && flow_finite(c3);
           if (finite) {
             e2 = reproj_e2(Dx, Dy, reproj_back(b0, b1, b2, b3, fx, fy), reproj_back(c0, c1, c2, c3, fx, fy));
             fb[p] = reproj_fb2(e2);
@@ -5108,28 +5080,15 @@ __global__ __launch_bounds__(kReprojThreads) void reproject_kernel(const DevRepr
       if (dst_u8) {
         uint8_t* const dp = d_warped + (size_t)i * 3 * plane;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
-          const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
-          if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
-        }
+        for (int c = 0; c < 3; ++c) quad_store_bytes_pair(dp + (uint32_t)c * plane + at, quad_word(out[c]), act);
       } else {
         uint8_t* const dp = d_warped + (size_t)i * 3 * plane * 4u;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
-          if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
-        }
+        for (int c = 0; c < 3; ++c) quad_store_bytes_f32(dp + ((size_t)c * plane + at) * 4u, out[c], act);
       }
     }
-    if (d_err) {
-      const u32x2 o = {errs, (uint32_t)__shfl_down((int)errs, 1)};
-      if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_err + (size_t)i * plane + at));
-    }
-    if (d_mask) {
-      const u32x2 o = {masks, (uint32_t)__shfl_down((int)masks, 1)};
-      if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_mask + (size_t)i * plane + at));
-    }
+    if (d_err) quad_store_bytes_pair(d_err + (size_t)i * plane + at, errs, act);
+    if (d_mask) quad_store_bytes_pair(d_mask + (size_t)i * plane + at, masks, act);
     if (d_fb2) {
       const f32x4 o = {fb[0], fb[1], fb[2], fb[3]};
       if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(d_fb2 + (size_t)i * plane + at));
@@ -5227,36 +5186,6 @@ __device__ __forceinline__ DevSplatRec splat_rec_of(const DevSplatJob& job, int 
   else r = splat_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
   return splat_sanitise(r);
 }
-// the four flow elements of a lane, widened
-template <bool kHalf>
-__device__ __forceinline__ void splat_load_flow4(const uint8_t* __restrict__ fp, float (&o)[4]) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  if constexpr (kHalf) {
-    const f16x4 a = *reinterpret_cast<const f16x4*>(fp);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) o[p] = (float)a[p];
-  } else {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(fp);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) o[p] = a[p];
-  }
-}
-// bit p: element p of the lane's four of a map is non-zero
-__device__ __forceinline__ uint32_t splat_load_hidden4(const uint8_t* __restrict__ op, size_t e, bool occ_u8) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  uint32_t hidden = 0u;
-  if (occ_u8) {
-    const uint32_t o = *reinterpret_cast<const uint32_t*>(op + e);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) hidden |= (((o >> (8 * p)) & 255u) != 0u ? 1u : 0u) << p;
-  } else {
-    const f32x4 o = *reinterpret_cast<const f32x4*>(op + e * 4u);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) hidden |= (o[p] != 0.0f ? 1u : 0u) << p;
-  }
-  return hidden;
-}
 template <bool kFlowHalf>
 __global__ __launch_bounds__(kSplatThreads) void splat_scatter_kernel(const DevSplatJob job, int n, int W, int H, uint32_t tiles_x) {
   constexpr int kFES = kFlowHalf ? 2 : 4;
@@ -5285,22 +5214,22 @@ __global__ __launch_bounds__(kSplatThreads) void splat_scatter_kernel(const DevS
     for (int k = 0; k < kWinCells / kSplatThreads; ++k) s_win[(uint32_t)k * kSplatThreads + threadIdx.x] = 0u;
     __syncthreads();
     if (blockIdx.x == 0u && threadIdx.x == 0u) {
-      if (job.recs_out && blockIdx.z == 0u) *reinterpret_cast<crop_u32x4*>(job.recs_out + i) = crop_u32x4{(uint32_t)r.t_q8[0], (uint32_t)r.t_q8[1], 0u, 0u};
+      if (job.recs_out && blockIdx.z == 0u) *reinterpret_cast<u32x4*>(job.recs_out + i) = u32x4{(uint32_t)r.t_q8[0], (uint32_t)r.t_q8[1], 0u, 0u};
       if (job.rows) job.rows[i].frame[f].t_q8 = (uint32_t)T;
     }
     float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     uint32_t labels = 0u;  // a byte per pixel
     if (act) {
       const uint8_t* const fp = s_flow + ((size_t)i * 2 * plane + at) * kFES;
-      splat_load_flow4<kFlowHalf>(fp, u);
-      splat_load_flow4<kFlowHalf>(fp + (size_t)plane * kFES, v);
+      quad_load<quad_fmt(kFlowHalf)>(fp, u);
+      quad_load<quad_fmt(kFlowHalf)>(fp + (size_t)plane * kFES, v);
       if (s_label) labels = *reinterpret_cast<const uint32_t*>(s_label + (size_t)i * plane + at);
     }
     uint32_t* const kp = d_keys + (size_t)i * plane;
     uint32_t cnt = 0u;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+      const bool bad = !(flow_finite(u[p]) && flow_finite(v[p]));
       const int rx = splat_round(X0 + p, splat_scale(bad ? 0 : reproj_q8(u[p]), T)), ry = splat_round(Y, splat_scale(bad ? 0 : reproj_q8(v[p]), T));
       const bool in = act && !bad && splat_inside(rx, ry, W, H);
       if (in) {
@@ -5334,9 +5263,6 @@ __global__ __launch_bounds__(kSplatThreads) void splat_scatter_kernel(const DevS
 }
 template <bool kSrcU8, bool kFlowHalf>
 __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevSplatJob job, int n, int W, int H, uint32_t tiles_x) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   constexpr int kSES = kSrcU8 ? 1 : 4, kFES = kFlowHalf ? 2 : 4;
   __shared__ uint32_t s_cnt[2][kSplatThreads / 64][3];  // [parity of the sample's turn][wave]: the seven counts in 10-bit fields
   const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
@@ -5366,11 +5292,14 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
     const uint8_t* const fp = s_flow + (size_t)i * 2 * plane * kFES;
     uint32_t cnt_a = 0u, cnt_b = 0u, cnt_c = 0u;  // filled, holes, covered | covered visible, covered hidden, hole other visible | hole other hidden
     if (as_target) {
-      crop_u32x4 K = {0u, 0u, 0u, 0u};
+      u32x4 K = {0u, 0u, 0u, 0u};
       uint32_t hidden = 0u;  // bit p: the other frame's map says pixel p is hidden
       if (act) {
-        K = *reinterpret_cast<const crop_u32x4*>(kp + at);
-        if (s_occ_other && job.rows) hidden = splat_load_hidden4(s_occ_other, (size_t)i * plane + at, occ_u8);
+        K = *reinterpret_cast<const u32x4*>(kp + at);
+        if (s_occ_other && job.rows) {
+          if (occ_u8) hidden = quad_load_hidden<true>(s_occ_other + (size_t)i * plane + at);
+          else hidden = quad_load_hidden<false>(s_occ_other + ((size_t)i * plane + at) * 4u);
+        }
       }
       uint32_t out[3][4] = {};
       uint32_t masks = 0u;  // a byte per pixel
@@ -5385,13 +5314,13 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
           masks |= 1u << (8 * p);
           own[0][p] = (float)dx; own[1][p] = (float)dy;
           if (d_other) {
-            other[0][p] = splat_to_other(dx, reproj_q8(reproj_load_flow<kFlowHalf>(fp, s)));
-            other[1][p] = splat_to_other(dy, reproj_q8(reproj_load_flow<kFlowHalf>(fp, plane + s)));
+            other[0][p] = splat_to_other(dx, reproj_q8(elem_load<quad_fmt(kFlowHalf)>(fp, s)));
+            other[1][p] = splat_to_other(dy, reproj_q8(elem_load<quad_fmt(kFlowHalf)>(fp, plane + s)));
           }
           if (d_image) {
             const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) out[c][p] = mblur_load_byte<kSrcU8>(sp, (uint32_t)c * plane + s);
+            for (int c = 0; c < 3; ++c) out[c][p] = elem_load_byte<kSrcU8>(sp, (uint32_t)c * plane + s);
           }
         }
         const bool hole = act && !filled, hid = (hidden >> p) & 1u;
@@ -5404,18 +5333,11 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
         if (dst_u8) {
           uint8_t* const dp = d_image + (size_t)i * 3 * plane;
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const uint32_t w = out[c][0] | (out[c][1] << 8) | (out[c][2] << 16) | (out[c][3] << 24);
-            const u32x2 o = {w, (uint32_t)__shfl_down((int)w, 1)};
-            if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(dp + (uint32_t)c * plane + at));
-          }
+          for (int c = 0; c < 3; ++c) quad_store_bytes_pair(dp + (uint32_t)c * plane + at, quad_word(out[c]), act);
         } else {
           uint8_t* const dp = d_image + (size_t)i * 3 * plane * 4u;
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const f32x4 o = {(float)out[c][0], (float)out[c][1], (float)out[c][2], (float)out[c][3]};
-            if (act) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(dp + ((size_t)c * plane + at) * 4u));
-          }
+          for (int c = 0; c < 3; ++c) quad_store_bytes_f32(dp + ((size_t)c * plane + at) * 4u, out[c], act);
         }
       }
 #pragma unroll
@@ -5430,10 +5352,7 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
           else __builtin_nontemporal_store(f32x4{e[0], e[1], e[2], e[3]}, reinterpret_cast<f32x4*>(dq + o * 4u));
         }
       }
-      if (d_mask) {
-        const u32x2 o = {masks, (uint32_t)__shfl_down((int)masks, 1)};
-        if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_mask + (size_t)i * plane + at));
-      }
+      if (d_mask) quad_store_bytes_pair(d_mask + (size_t)i * plane + at, masks, act);
     }
     if (as_source) {
       const DevSplatRec r = splat_rec_of(job, i);
@@ -5441,15 +5360,18 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
       float u[4] = {0.0f, 0.0f, 0.0f, 0.0f}, v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       uint32_t labels = 0u, hidden = 0u;
       if (act) {
-        splat_load_flow4<kFlowHalf>(fp + (size_t)at * kFES, u);
-        splat_load_flow4<kFlowHalf>(fp + ((size_t)plane + at) * kFES, v);
+        quad_load<quad_fmt(kFlowHalf)>(fp + (size_t)at * kFES, u);
+        quad_load<quad_fmt(kFlowHalf)>(fp + ((size_t)plane + at) * kFES, v);
         if (s_label) labels = *reinterpret_cast<const uint32_t*>(s_label + (size_t)i * plane + at);
-        if (s_occ && job.rows) hidden = splat_load_hidden4(s_occ, (size_t)i * plane + at, occ_u8);
+        if (s_occ && job.rows) {
+          if (occ_u8) hidden = quad_load_hidden<true>(s_occ + (size_t)i * plane + at);
+          else hidden = quad_load_hidden<false>(s_occ + ((size_t)i * plane + at) * 4u);
+        }
       }
       uint32_t fates = 0u;  // a byte per pixel
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
-        const bool bad = !(mblur_finite(u[p]) && mblur_finite(v[p]));
+        const bool bad = !(flow_finite(u[p]) && flow_finite(v[p]));
         const int rx = splat_round(X0 + p, splat_scale(bad ? 0 : reproj_q8(u[p]), T)), ry = splat_round(Y, splat_scale(bad ? 0 : reproj_q8(v[p]), T));
         const bool in = act && !bad && splat_inside(rx, ry, W, H);
         bool covered = false;
@@ -5459,10 +5381,7 @@ __global__ __launch_bounds__(kSplatThreads) void splat_resolve_kernel(const DevS
         cnt_a += (covered ? 1u : 0u) << 20;
         cnt_b += (covered && s_occ && !hid ? 1u : 0u) | ((covered && s_occ && hid ? 1u : 0u) << 10);
       }
-      if (d_fate) {
-        const u32x2 o = {fates, (uint32_t)__shfl_down((int)fates, 1)};
-        if (act && (threadIdx.x & 1u) == 0u) __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(d_fate + (size_t)i * plane + at));
-      }
+      if (d_fate) quad_store_bytes_pair(d_fate + (size_t)i * plane + at, fates, act);
     }
     if (job.rows) {  // (uniform: every lane of the workgroup is here)
 #pragma unroll
@@ -5498,26 +5417,13 @@ static_assert(kVisBlockPixels % (kVisThreads * 4) == 0, "whole rounds of 4-pixel
 #define OFDG_VIS_READ_FIRST 1
 #endif
 constexpr int kVisReadFirst = OFDG_VIS_READ_FIRST;  // which slots of `work` the reduction reads before its atomic: 0 none, 1 BATCH's one slot, 2 every slot
-template <bool kHalf>
-__device__ __forceinline__ void vis_load_flow4(const void* flow, size_t at, float (&e)[4]) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  if constexpr (kHalf) {
-    const f16x4 a = *reinterpret_cast<const f16x4*>(static_cast<const _Float16*>(flow) + at);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e[q] = (float)a[q];
-  } else {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(static_cast<const float*>(flow) + at);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e[q] = a[q];
-  }
-}
 
 // The maximum's reduction: a running 64-bit maximum of R2 per lane over the usable pixels, across the wave with __shfl_xor,
 // across the workgroup through LDS, and at most one 64-bit integer atomicMax per workgroup (none where nothing is usable: the
 // slot is cleared to 0 before the launch).  No bit depends on arrival order.
 template <bool kHalf>
 __global__ __launch_bounds__(kVisThreads) void flow_vis_max_kernel(const DevVisJob job, int n, uint32_t plane) {
+  typedef typename FlowFmt<quad_fmt(kHalf)>::elem FlowElem;
   __shared__ unsigned long long s_part[kVisThreads / 64];
   const uint32_t first = blockIdx.x * (uint32_t)kVisBlockPixels;
   const uint32_t end = first + (uint32_t)kVisBlockPixels < plane ? first + (uint32_t)kVisBlockPixels : plane;
@@ -5527,11 +5433,11 @@ __global__ __launch_bounds__(kVisThreads) void flow_vis_max_kernel(const DevVisJ
     unsigned long long best = 0;
     for (uint32_t at = first + threadIdx.x * 4u; at < end; at += (uint32_t)(kVisThreads * 4)) {
       float u[4], v[4];
-      vis_load_flow4<kHalf>(job.flow, base + at, u);
-      vis_load_flow4<kHalf>(job.flow, base + plane + at, v);
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowElem*>(job.flow) + (base + at), u);
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowElem*>(job.flow) + (base + plane + at), v);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const unsigned long long r2 = vis_usable(u[q], v[q]) ? vis_r2(vis_fixed(u[q]), vis_fixed(v[q])) : 0ull;
+        const unsigned long long r2 = flow_usable(u[q], v[q]) ? vis_r2(vis_fixed(u[q]), vis_fixed(v[q])) : 0ull;
         best = r2 > best ? r2 : best;
       }
     }
@@ -5564,7 +5470,7 @@ __global__ __launch_bounds__(kVisThreads) void flow_vis_max_kernel(const DevVisJ
 // consecutive bytes.  Workgroup 0 of a sample writes its row from lane 0 with one 16-byte store.
 template <bool kHalf, int kOcc, bool kHwc>  // kOcc: 0 no dimming, 1 by a float32 map, 2 by a uint8 one
 __global__ __launch_bounds__(kVisThreads) void flow_vis_colour_kernel(const DevVisJob job, int n, uint32_t plane) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  typedef typename FlowFmt<quad_fmt(kHalf)>::elem FlowElem;
   __shared__ int32_t s_atan[kVisAtanEntries];
   __shared__ uint32_t s_wheel[kVisWheelEntries];
   for (int k = (int)threadIdx.x; k < kVisAtanEntries; k += kVisThreads) s_atan[k] = kVisAtan[k];
@@ -5584,25 +5490,18 @@ __global__ __launch_bounds__(kVisThreads) void flow_vis_colour_kernel(const DevV
     M = (uint32_t)__builtin_amdgcn_readfirstlane((int)M);
     const float inv_m = vis_inv(M);
     if (job.rows_out && blockIdx.x == 0u && threadIdx.x == 0u)
-      *reinterpret_cast<crop_u32x4*>(job.rows_out + i) = crop_u32x4{(uint32_t)max_r2, (uint32_t)(max_r2 >> 32), M, 0u};
+      *reinterpret_cast<u32x4*>(job.rows_out + i) = u32x4{(uint32_t)max_r2, (uint32_t)(max_r2 >> 32), M, 0u};
     const size_t base = (size_t)i * 2 * plane;
     for (uint32_t at = first + threadIdx.x * 4u; at < end; at += (uint32_t)(kVisThreads * 4)) {
       float u[4], v[4];
-      vis_load_flow4<kHalf>(job.flow, base + at, u);
-      vis_load_flow4<kHalf>(job.flow, base + plane + at, v);
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowElem*>(job.flow) + (base + at), u);
+      quad_load<quad_fmt(kHalf)>(static_cast<const FlowElem*>(job.flow) + (base + plane + at), v);
       uint32_t hidden = 0;  // bit q: pixel q is dimmed
-      if constexpr (kOcc == 1) {
-        const f32x4 o = *reinterpret_cast<const f32x4*>(static_cast<const float*>(job.occ) + (size_t)i * plane + at);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) hidden |= (o[q] != 0.0f ? 1u : 0u) << q;
-      } else if constexpr (kOcc == 2) {
-        const uint32_t o = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(job.occ) + (size_t)i * plane + at);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) hidden |= (((o >> (8 * q)) & 255u) != 0u ? 1u : 0u) << q;
-      }
+      if constexpr (kOcc == 1) hidden = quad_load_hidden<false>(static_cast<const float*>(job.occ) + (size_t)i * plane + at);
+      else if constexpr (kOcc == 2) hidden = quad_load_hidden<true>(static_cast<const uint8_t*>(job.occ) + (size_t)i * plane + at);
       uint32_t px[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) px[q] = vis_usable(u[q], v[q]) ? vis_pixel(u[q], v[q], M, inv_m, (hidden >> q) & 1u, s_atan, s_wheel) : 0u;
+      for (int q = 0; q < 4; ++q) px[q] = flow_usable(u[q], v[q]) ? vis_pixel(u[q], v[q], M, inv_m, (hidden >> q) & 1u, s_atan, s_wheel) : 0u;
       if constexpr (kHwc) {
         uint32_t* const dp = reinterpret_cast<uint32_t*>(dst + ((size_t)i * plane + at) * 3);
         dp[0] = px[0] | (px[1] << 24);
@@ -5637,31 +5536,10 @@ constexpr int kErrThreads = 256;
 constexpr int kErrBlockPixels = 4096;
 constexpr int kErrWaves = kErrThreads / 64;
 static_assert(kErrBlockPixels % (kErrThreads * 4) == 0 && kErrBlockPixels <= 4096, "whole rounds of 4-pixel pieces; the packed counters hold 4096 pixels");
-template <int kFmt>  // OFDG_FMT_F32, OFDG_FMT_F16 or OFDG_FMT_BF16
-__device__ __forceinline__ void err_load4(const void* p, size_t at, float (&e)[4]) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  if constexpr (kFmt == OFDG_FMT_F16) {
-    const f16x4 a = *reinterpret_cast<const f16x4*>(static_cast<const _Float16*>(p) + at);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e[q] = (float)a[q];
-  } else if constexpr (kFmt == OFDG_FMT_BF16) {
-    const u32x2 a = *reinterpret_cast<const u32x2*>(static_cast<const uint16_t*>(p) + at);
-    e[0] = err_bf16(a[0] & 0xFFFFu);
-    e[1] = err_bf16(a[0] >> 16);
-    e[2] = err_bf16(a[1] & 0xFFFFu);
-    e[3] = err_bf16(a[1] >> 16);
-  } else {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(static_cast<const float*>(p) + at);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e[q] = a[q];
-  }
-}
 template <bool kGtHalf, int kEst, bool kPlanes>
 __global__ __launch_bounds__(kErrThreads) void flow_error_kernel(const DevErrJob job, int n, uint32_t plane) {
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef typename FlowFmt<quad_fmt(kGtHalf)>::elem GtElem;
+  typedef typename FlowFmt<kEst>::elem EstElem;
   __shared__ unsigned long long s_sum_n[kErrWaves][kErrCells];  // sum_epe_q8 | n << 48
   __shared__ unsigned long long s_out[kErrWaves][kErrCells];    // n_1px | n_3px << 16 | n_5px << 32 | n_fl << 48
   __shared__ uint32_t s_hist[kErrWaves][kErrHistBins];
@@ -5689,21 +5567,14 @@ __global__ __launch_bounds__(kErrThreads) void flow_error_kernel(const DevErrJob
     unsigned long long acc_sum_n = 0, acc_out = 0, key = 0;
     for (uint32_t at = first + (uint32_t)tid * 4u; at < end; at += (uint32_t)(kErrThreads * 4)) {
       float ug[4], vg[4], ue[4], ve[4];
-      err_load4<kGtHalf ? OFDG_FMT_F16 : OFDG_FMT_F32>(job.gt, base + at, ug);
-      err_load4<kGtHalf ? OFDG_FMT_F16 : OFDG_FMT_F32>(job.gt, base + plane + at, vg);
-      err_load4<kEst>(job.est, base + at, ue);
-      err_load4<kEst>(job.est, base + plane + at, ve);
+      quad_load<quad_fmt(kGtHalf)>(static_cast<const GtElem*>(job.gt) + (base + at), ug);
+      quad_load<quad_fmt(kGtHalf)>(static_cast<const GtElem*>(job.gt) + (base + plane + at), vg);
+      quad_load<kEst>(static_cast<const EstElem*>(job.est) + (base + at), ue);
+      quad_load<kEst>(static_cast<const EstElem*>(job.est) + (base + plane + at), ve);
       uint32_t hidden = 0, d2 = 0;  // bit q: pixel q is hidden; byte q: its dist2
       if (job.occ) {
-        if (occ_u8) {
-          const uint32_t o = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(job.occ) + base1 + at);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) hidden |= (((o >> (8 * q)) & 255u) != 0u ? 1u : 0u) << q;
-        } else {
-          const f32x4 o = *reinterpret_cast<const f32x4*>(static_cast<const float*>(job.occ) + base1 + at);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) hidden |= (o[q] != 0.0f ? 1u : 0u) << q;
-        }
+        if (occ_u8) hidden = quad_load_hidden<true>(static_cast<const uint8_t*>(job.occ) + base1 + at);
+        else hidden = quad_load_hidden<false>(static_cast<const float*>(job.occ) + base1 + at);
       }
       if (with_dist) d2 = *reinterpret_cast<const uint32_t*>(job.dist2 + base1 + at);
       float out_epe[4];
@@ -5711,7 +5582,7 @@ __global__ __launch_bounds__(kErrThreads) void flow_error_kernel(const DevErrJob
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float se = err_scaled(ue[q], job.est_scale), te = err_scaled(ve[q], job.est_scale);
-        const bool gt_ok = vis_usable(ug[q], vg[q]), ok = gt_ok && vis_usable(se, te);
+        const bool gt_ok = flow_usable(ug[q], vg[q]), ok = gt_ok && flow_usable(se, te);
         n_bad_gt += gt_ok ? 0u : 1u;
         n_bad_est += (gt_ok && !ok) ? 1u : 0u;
         if constexpr (kPlanes) { out_epe[q] = -1.0f; px[q] = 0u; }
