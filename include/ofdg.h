@@ -1115,6 +1115,117 @@ int ofdg_jitter_draw(uint32_t seed, long long index, const struct ofdg_jitter_jo
 int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hue);
 
 /*
+ * Camera: the optics and the sensor on image0 and / or image1 of a batch - a Gaussian lens blur and the artefacts of a Bayer
+ * mosaic that is interpolated back (the two camera effects Mayer et al., IJCV 2018, found to help on real data), each sample
+ * by a record of its own.  ofdg_motion_blur is the exposure; this is what stands behind it and in front of the sensor noise
+ * of ofdg_photo.  The record is a pure function of (seed, global sample index).  Everything below is integers on bytes but
+ * for the tap table, which is fp64 through ofdg_det_exp of include/ofdg_detmath.h, and therefore the same bits on host and
+ * device: the kernel, ofdg_host_camera and the numpy restatement of the tests give the same bytes.
+ *
+ * Planes, formats and sizes as in ofdg_jitter: src[f] is image f as [n,3,height,width] planar B, G, R of src_fmt, dst[f] the
+ * same shape of dst_fmt; OFDG_FMT_F32 or OFDG_FMT_U8, chosen independently.  A frame is present when both its pointers are
+ * given (src[f] and dst[f] both NULL: absent).  width = height = 0: the context's frame; otherwise any size the context's
+ * rule allows (width a multiple of 8 and at least 8, height even and at least 2).  There is NO in-place form - a pixel reads
+ * its neighbours -: dst[f] == src[f] is an overlap and is refused.  The byte of a uint8 element is itself, of a float32
+ * element the index rule of ofdg_photo (clamped to [0, 255], a NaN 0, to nearest even); a uint8 destination stores the byte,
+ * a float32 one (float)byte.  It reads no record of the context and works in every mode.
+ *
+ * Record of sample i: recs[i] (DEVICE memory) when recs is given, else ofdg_camera_draw(seed, first_index + i, the job's
+ * ranges).  Either way it is sanitised before use, and the sanitised record, with the radii, is what recs_out[i] receives.
+ * sigma_q8[f]: the lens blur's sigma of frame f in 1 / 256 px, 0..1024 (0: none).  bayer: -1 none, 0..3 the pattern.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, {seed ^ (uint32)(g >> 32) *
+ *    0x9E3779B9, (uint32)g}, blocks j = 0, 1 at the counters {j, 0, 0x0c79, 0} (taken: 0x0c70 .. 0x0c78 and 0x0fd9, see
+ *    ofdg_jitter).  u() and isym() as in ofdg_jitter.  lo = lrintf(sigma_min * 256), hi = lrintf(sigma_max * 256),
+ *    D = lrintf(sigma_delta * 256) (to nearest even).
+ *      block 0:  blurred = u(.x) < blur_prob
+ *                s0 = lo + (int)(((uint64).y * (uint32)(hi - lo + 1)) >> 32)         uniform on [lo, hi]
+ *                s1 = s0 + isym(.z, D)
+ *                mosaic = u(.w) < bayer_prob
+ *      block 1:  p = pattern >= 0 ? pattern : (int)(.x >> 30)
+ *    sigma_q8 = blurred ? {s0, s1} : {0, 0};  bayer = mosaic ? p : -1;  radius = {0, 0};  reserved = 0.  Both frames share
+ *    the pattern - it is one camera -, frame 1's focus is up to sigma_delta apart, as the other stages keep frame 1 slightly
+ *    apart.
+ * 2. Sanitise.  sigma_q8 clamps to [0, 1024]; a bayer outside -1..3 becomes -1; radius[f] = min(12, (3 sigma_q8[f] + 255)
+ *    >> 8): three sigma, rounded up; reserved = 0.
+ * 3. Taps, for s = sigma_q8[f] > 0 and R = radius[f], exp being ofdg_det_exp of include/ofdg_detmath.h in fp64:
+ *      e[k] = (uint32)llrint(exp(-(double)(k k) * 32768.0 / (double)(s s)) * 16777216.0)       k = 0..R
+ *      E    = e[0] + 2 (e[1] + .. + e[R])
+ *      w[k] = (e[k] * 65536 + E / 2) / E        k >= 1, in 64-bit integers, the division floored
+ *      w[0] = 65536 - 2 (w[1] + .. + w[R])
+ *    The weights sum to exactly 65536, do not increase outward, and w[0] > 0, for every s.  ofdg_camera_taps exports the
+ *    table.  Known answers: s = 85: 64160, 688;  s = 256: 26152, 15862, 3539, 291.
+ * 4. Blur, per channel, on the bytes a(x, y); coordinates are clamped to the plane (the edge is replicated):
+ *      h8(x, y)  = (sum_k w[|k|] a(x + k, y) + 128) >> 8                     at most 65280
+ *      out(x, y) = (sum_k w[|k|] h8(x, y + k) + 8388608) >> 24
+ *    Both sums fit unsigned 32 bits (the largest is 65280 * 65536 + 2^23).  A constant plane is unchanged.  s = 0: no blur.
+ *    Against the float64 separable convolution with the same truncated, normalised Gaussian a byte is off by at most 0.75
+ *    (0.5 the last rounding, 1 / 512 that of h8, under 0.19 the quantised taps over two passes).
+ * 5. Mosaic and demosaic, on the blurred bytes P_B, P_G, P_R, for bayer = p >= 0.  The site of (x, y) is a = (x + (p & 1)) & 1,
+ *    b = (y + (p >> 1)) & 1:  (0, 0) is R, (1, 1) is B, the other two are G - p = 0 is RGGB.  m(x, y) = P_site(x, y)(x, y), the one
+ *    sample the sensor has there.  Coordinates are reflected without repeating the edge (-1 -> 1, W -> W - 2), which keeps the
+ *    parity, so a reflected neighbour has the colour the pattern expects there (W >= 8, H >= 2 by the size rule).  With
+ *      hz = (m(x-1,y) + m(x+1,y) + 1) >> 1     vt = (m(x,y-1) + m(x,y+1) + 1) >> 1
+ *      cr = (the four edge neighbours + 2) >> 2     dg = (the four diagonal neighbours + 2) >> 2     c = m(x, y)
+ *                                        R     G     B
+ *      R site                            c     cr    dg
+ *      B site                            dg    cr    c
+ *      G site on an R row (b = 0)        hz    c     vt
+ *      G site on a B row  (b = 1)        vt    c     hz
+ *    - the classic bilinear demosaic.  Planes that are each constant come back unchanged.
+ * 6. Identity.  A frame with sigma_q8[f] = 0 and bayer = -1 is copied - bit for bit where src_fmt == dst_fmt, else through its
+ *    bytes.
+ *
+ * Asynchronous on `stream`, the stream the frames were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel per
+ * call, no atomics, no workspace.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, one of width /
+ * height 0 or a size that breaks the rule, 3 * width * height of 2^32 and more, another format code, non-zero flags or
+ * reserved, a range that is negative, NaN, infinite or above its bound (sigma_min, sigma_max, sigma_delta 4, blur_prob,
+ * bayer_prob 1), sigma_min > sigma_max, pattern outside -1..3, no frame set, src[f] without dst[f] or the reverse, a
+ * misaligned pointer (sources as the render calls ask: 16-byte float32, 4-byte uint8; destinations and both record arrays
+ * 16-byte), a written range (destinations, recs_out) that overlaps any other range of the job - dst[f] == src[f] included -,
+ * OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: noise between mosaic and demosaic (ofdg_photo's noise stays per element), any demosaicer but bilinear, white
+ * balance, gamma, sharpening, lens distortion and chromatic aberration (they move pixels, so they change the flow),
+ * vignetting, depth of field by label, a sigma above 4 px, a pattern per frame, an in-place form.  The flow, maps, labels,
+ * splat and reprojection planes are not touched.
+ */
+#define OFDG_CAMERA_MAX_SIGMA_Q8 1024  /* 4 px */
+#define OFDG_CAMERA_MAX_RADIUS 12      /* taps on each side of the centre */
+typedef struct ofdg_camera_rec {     /* 32 bytes; index [f] = frame 0 / 1 */
+  int32_t sigma_q8[2];               /* 1 / 256 px, 0..1024 */
+  int32_t bayer;                     /* -1: none; 0..3: the pattern */
+  int32_t radius[2];                 /* written into recs_out, never read */
+  int32_t reserved[3];
+} ofdg_camera_rec;
+struct ofdg_camera_job {             /* 112 bytes */
+  const void* src[2]; void* dst[2];  /* image0, image1: [n,3,height,width]; each frame optional (src and dst both NULL) */
+  const ofdg_camera_rec* recs;       /* DEVICE, n records, or NULL: drawn */
+  ofdg_camera_rec*       recs_out;   /* DEVICE, n records, or NULL */
+  long long first_index; uint32_t seed;
+  int32_t width, height;             /* 0, 0: the context's frame */
+  int32_t src_fmt, dst_fmt;          /* OFDG_FMT_F32 or OFDG_FMT_U8, independently */
+  int32_t flags;                     /* no flag yet: must be 0 */
+  int32_t pattern;                   /* of the draw: -1 drawn per sample, 0..3 fixed */
+  float sigma_min, sigma_max, sigma_delta, blur_prob, bayer_prob;   /* ranges of the draw: <= 4, 4, 4 (px), 1, 1 */
+  int32_t reserved;                  /* must be 0 */
+};
+int ofdg_camera(ofdg_ctx* ctx, const struct ofdg_camera_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes and records in host memory, no alignment asked of any
+ * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (step 1 alone: not sanitised; pure, no GPU).  Of `ranges` only the five ranges and
+ * pattern are read.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer, a range that is negative, NaN,
+ * infinite or above its bound, sigma_min > sigma_max or a pattern outside -1..3. */
+int ofdg_camera_draw(uint32_t seed, long long index, const struct ofdg_camera_job* ranges, ofdg_camera_rec* out);
+/* The tap table of step 3 for sigma_q8 in 1..1024 (pure, no GPU): out[0..R] the weights, out[R+1..12] zero.  OFDG_EINVAL
+ * (ofdg_host_last_error) for out NULL or a sigma_q8 outside 1..1024. */
+int ofdg_camera_taps(int sigma_q8, uint32_t out[13]);
+
+/*
  * Flow visualisation: the Middlebury colour wheel (Baker et al., "A Database and Evaluation Methodology for Optical Flow") of
  * any [n,2,height,width] flow tensor - the forward flow, flow1, a cropped, warped or splat flow, a residual - as a uint8
  * picture: the direction is the hue, the length the saturation, zero flow white.  Behind the producing call on the same

@@ -115,6 +115,7 @@ EXPORTS = [
     "ofdg_reproject", "ofdg_host_reproject",
     "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
     "ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw", "ofdg_host_jitter_hue",
+    "ofdg_camera", "ofdg_host_camera", "ofdg_camera_draw", "ofdg_camera_taps",
     "ofdg_flow_vis", "ofdg_host_flow_vis", "ofdg_host_flow_vis_tables",
     "ofdg_flow_error", "ofdg_host_flow_error", "ofdg_host_flow_error_colours",
 ]
@@ -1555,6 +1556,126 @@ def flow_error_legend(cell=None):
     return colours, edges
 
 
+# the camera: lens blur, Bayer mosaic and demosaic (ofdg_camera_rec / struct ofdg_camera_job / ofdg_camera, include/ofdg.h)
+CAMERA_REC_WORDS = 8        # a record as int32 [8]: sigma_q8[2] bayer radius[2], then 3 reserved words
+CAMERA_MAX_SIGMA_Q8 = 1024  # OFDG_CAMERA_MAX_SIGMA_Q8: 4 px
+CAMERA_MAX_RADIUS = 12      # OFDG_CAMERA_MAX_RADIUS
+CAMERA_RANGES = ("sigma_min", "sigma_max", "sigma_delta", "blur_prob", "bayer_prob", "pattern")
+# A starting point: four samples in five pass a lens of sigma 0.3 to 1.5 px, frame 1 focused within 0.1 px of frame 0, and
+# every second sample a Bayer sensor of a drawn pattern.  Not a tuned recipe: every field is a range to be chosen per data set
+# and target camera.
+CAMERA_DEFAULT = dict(sigma_min=0.3, sigma_max=1.5, sigma_delta=0.1, blur_prob=0.8, bayer_prob=0.5, pattern=-1)
+
+
+class CameraRec(C.Structure):
+    """ofdg_camera_rec: the lens and the sensor of one sample (32 bytes)."""
+    _fields_ = [("sigma_q8", C.c_int32 * 2), ("bayer", C.c_int32), ("radius", C.c_int32 * 2), ("reserved", C.c_int32 * 3)]
+
+
+class CameraJob(C.Structure):
+    """struct ofdg_camera_job (112 bytes)."""
+    _fields_ = [("src", C.c_void_p * 2), ("dst", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flags", C.c_int32), ("pattern", C.c_int32)] + \
+               [(name, C.c_float) for name in CAMERA_RANGES[:5]] + [("reserved", C.c_int32)]
+
+
+def _camera_rec_dtype():
+    import numpy as np
+    return np.dtype([("sigma_q8", "<i4", (2,)), ("bayer", "<i4"), ("radius", "<i4", (2,)), ("reserved", "<i4", (3,))])
+
+
+def camera_numpy(recs):
+    """Records of Generator.camera / host_camera - a torch tensor or numpy array of int32 [n,8] (or any array of 32 bytes a
+    record) - as a numpy structured array [n] with the fields sigma_q8 and radius (each [2]: frame 0, frame 1), bayer and
+    reserved [3]."""
+    import numpy as np
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _camera_rec_dtype():
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % 32:
+        raise ValueError("records must be 32 bytes each, got %d bytes" % raw.size)
+    return raw.view(_camera_rec_dtype())
+
+
+def _camera_ranges(job, ranges):
+    """the ranges of a dict in a job: a missing range is 0, a missing pattern -1 (drawn per sample)"""
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in CAMERA_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(CAMERA_RANGES)))
+    for key in CAMERA_RANGES[:5]:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    job.pattern = int(ranges.get("pattern", -1))
+    return job
+
+
+def _camera_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
+    job = _camera_ranges(CameraJob(), ranges)
+    for f in range(2):
+        if src[f] is not None:
+            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt = codes
+    return job
+
+
+def camera_draw(seed, index, ranges=None):
+    """ofdg_camera_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (CAMERA_RANGES; a
+    missing range is 0, a missing pattern -1; CAMERA_DEFAULT for one), before sanitising, as one element of the structured
+    array camera_numpy describes."""
+    job = _camera_ranges(CameraJob(), ranges)
+    out = CameraRec()
+    _host_check(lib().ofdg_camera_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return camera_numpy(bytearray(out))[0]
+
+
+def host_camera_taps(sigma_q8):
+    """ofdg_camera_taps (pure, no GPU): the tap table of a sigma in 1 / 256 px, 1..1024, as uint32 [13] - the weights w[0..R], R =
+    min(12, (3 sigma_q8 + 255) >> 8), which sum to 65536 as w[0] + 2 (w[1] + ..), then zeros."""
+    import numpy as np
+    out = (C.c_uint32 * (CAMERA_MAX_RADIUS + 1))()
+    _host_check(lib().ofdg_camera_taps(int(sigma_q8), out))
+    return np.frombuffer(bytearray(out), np.uint32).copy()
+
+
+def alloc_camera(n, height, width, image_dtype=None, frames=(0, 1), device="cuda"):
+    """((out0, out1), recs) of Generator.camera for n samples: the frames to write - [n,3,height,width] of image_dtype
+    (default torch.float32), None for a frame not among `frames` - and the int32 [n,8] records (recs_out).  Not filled: the
+    call writes every element and every record."""
+    import torch
+    dt = torch.float32 if image_dtype is None else image_dtype
+    return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if f in frames else None for f in range(2)),
+            torch.empty((n, CAMERA_REC_WORDS), dtype=torch.int32, device=device))
+
+
+def host_camera(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None):
+    """ofdg_host_camera (no GPU): the lens blur, mosaic and demosaic of HOST arrays - images a pair (image0, image1) of float32 or
+    uint8 arrays [n,3,H,W] (planar B, G, R), either None; recs None (drawn from seed, first_index and ranges) or n records
+    (camera_numpy's array, or int32 [n,8]).  dst_dtype: np.float32 / np.uint8, default the source's.  Returns ((out0, out1),
+    recs_used): the new arrays (None for an absent frame) and the records after sanitising, with the radii, as camera_numpy's
+    array."""
+    import numpy as np
+    images = tuple(None if t is None else np.ascontiguousarray(t) for t in images)
+    given = [t for t in images if t is not None]
+    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
+    out = tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
+    n, height, width, *codes = photo_format(images, out)
+    if recs is not None:
+        recs = camera_numpy(recs).copy()
+        if recs.shape != (n,):
+            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
+    used = np.zeros((n,), _camera_rec_dtype())
+    job = _camera_job(images, out, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                      first_index, seed, ranges)
+    _host_check(lib().ofdg_host_camera(C.byref(job), n, width, height))
+    return out, used
+
+
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
 MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
 MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
@@ -2229,6 +2350,10 @@ def lib():
         L.ofdg_host_jitter.argtypes = [C.POINTER(JitterJob), i32, i32, i32]
         L.ofdg_jitter_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(JitterJob), C.POINTER(JitterRec)]
         L.ofdg_host_jitter_hue.argtypes = [vp, vp, C.c_size_t, i32]
+        L.ofdg_camera.argtypes = [vp, C.POINTER(CameraJob), i32, vp]
+        L.ofdg_host_camera.argtypes = [C.POINTER(CameraJob), i32, i32, i32]
+        L.ofdg_camera_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(CameraJob), C.POINTER(CameraRec)]
+        L.ofdg_camera_taps.argtypes = [i32, C.POINTER(C.c_uint32)]
         L.ofdg_flow_vis.argtypes = [vp, C.POINTER(FlowVisJob), i32, vp]
         L.ofdg_host_flow_vis.argtypes = [C.POINTER(FlowVisJob), i32, i32, i32]
         L.ofdg_host_flow_vis_tables.argtypes = [vp, vp]
@@ -2773,6 +2898,25 @@ class Generator:
                               speed_px, dist2_edges, layout, dim_occ, accumulate, one_row)
         self._check(lib().ofdg_flow_error(self.h, C.byref(job), n, C.c_void_p(stream)))
         return {k: v for k, v in (("rows", rows), ("epe", epe), ("picture", picture)) if v is not None}
+
+    def camera(self, images, out, recs=None, first_index=0, seed=None, ranges=None, recs_out=None, stream=0, size=None):
+        """The camera of both frames of a batch in one launch (ofdg_camera, include/ofdg.h): a Gaussian lens blur of a sigma per
+        sample and frame, then - with a drawn probability - the Bayer mosaic of the sample's pattern interpolated back
+        bilinearly.  images: the pair (image0, image1) of float32 or uint8 tensors [n,3,H,W] a render / forward call (or crop,
+        spatial, motion_blur) wrote, either member None; out: the pair to write, float32 or uint8 independently of images
+        (alloc_camera) - there is no in-place form.  recs: None - the record of sample i is camera_draw(seed, first_index + i,
+        ranges) - or an int32 device tensor [n,8], taken as given; either is sanitised.  ranges: a dict of CAMERA_RANGES (a
+        missing range is 0, a missing pattern -1: drawn; CAMERA_DEFAULT is a starting point).  seed: default the context's.
+        recs_out: None or an int32 device tensor [n,8] that receives the records used, with the radii (camera_numpy reads it).
+        stream: the stream the frames were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of
+        the context's.  Flow, maps and labels are not touched.  Asynchronous.  Returns out."""
+        images, out = tuple(images), tuple(out)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = photo_format(images, out, height, width)
+        self._check_recs(recs, recs_out, "int32", (n, CAMERA_REC_WORDS))
+        job = _camera_job(images, out, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
+        self._check(lib().ofdg_camera(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return out
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
                     size=None):
@@ -3475,6 +3619,8 @@ class _RingSlot:
                  "planes",       # the planes every stage behind the blur works on, by name: `sharp`, with the blurred frames in place
                  "window_recs",  # the records of crop= / spatial=
                  "blur",         # the records of motion_blur=
+                 "optics",       # with camera=: the planes in front of the camera (what motion_blur= writes, else the sharp ones)
+                 "camera",       # the records of camera=
                  "reproject",    # (planes by name, rows) of reproject=
                  "splat",        # (planes by name, keys, rows, records) of splat=
                  "objects",      # (rows, counts) of objects=True
@@ -3515,20 +3661,23 @@ class FlowLoader:
                             planes, keys and rows of its own
         5. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
                             places of image0 / image1 for every later stage and in the batch
-        6. photo=           in place, on both frames
-        7. jitter=          in place, on both frames
-        8. erase=           in place, on the frames and the occlusion maps
-        9. objects=True     the table, of the label planes of stage 1
-        10. stats=, pyramid= the reductions of flow and occ0
-        11. boundaries=     of the flows and label planes
-        12. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
-        13. pack=           of image0, image1 and flow, into tensors of its own
+        6. camera=          lens blur, Bayer mosaic and demosaic of the frames as they are then, into frame buffers of its own,
+                            which take the places of image0 / image1 for every later stage and in the batch
+        7. photo=           in place, on both frames
+        8. jitter=          in place, on both frames
+        9. erase=           in place, on the frames and the occlusion maps
+        10. objects=True    the table, of the label planes of stage 1
+        11. stats=, pyramid= the reductions of flow and occ0
+        12. boundaries=     of the flows and label planes
+        13. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
+        14. pack=           of image0, image1 and flow, into tensors of its own
 
-    So the blur follows the flow the batch hands out, the photometric noise stays sharp on top of it as a sensor's does, the
+    So the blur follows the flow the batch hands out, the optics act behind the exposure and in front of the sensor noise, the
+    photometric noise stays sharp on top of both as a sensor's does, the
     colour jitter and the eraser's mean fill see the augmented frame - the fill is the mean colour of the jittered frame, as in
     the RAFT recipe -, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (none of photo=, jitter= and erase= touches what they read).  The records of stages 2 and 4 to 8 are drawn from the
+    the un-erased sample (none of camera=, photo=, jitter= and erase= touches what they read).  The records of stages 2 and 4 to 9 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -3566,6 +3715,9 @@ class FlowLoader:
     index wins.  frames=None: both frames when "flow1" is among extras=, else frame 0; frame 1 without "flow1" raises.
     photo=ranges (a dict of PHOTO_RANGES, PHOTO_FLOWNET for one): both frames are augmented (Generator.photo); the dict also
     holds "photo" (float32 [n,16], the records used).
+    camera=dict(...) (the CAMERA_RANGES, CAMERA_DEFAULT for a starting point): the lens blur and the Bayer artefacts of
+    Generator.camera on both frames, behind motion_blur= and in front of photo=, into frame buffers of its own; the dict also
+    holds "camera" (int32 [n,8], the records used with the radii: camera_numpy).  An unknown key raises.
     jitter=ranges (a dict of JITTER_RANGES, JITTER_RAFT for the recipe's): the ColorJitter of the RAFT-family recipes on both
     frames (Generator.jitter), behind photo= and in front of erase=; the dict also holds "jitter" (int32 [n,16], the records used
     with the means: jitter_numpy).
@@ -3603,7 +3755,7 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, splat=None, jitter=None, vis=None, **kw):
+                 reproject=None, splat=None, jitter=None, vis=None, camera=None, **kw):
         import torch
         self.vis = self._vis_options(vis, extras)
         self.boundaries = self._boundary_options(boundaries, extras)
@@ -3612,6 +3764,7 @@ class FlowLoader:
         self.reproject = self._reproject_options(reproject, extras)
         self.splat = self._splat_options(splat, extras)
         self.jitter = self._jitter_options(jitter)
+        self.camera = self._camera_options(camera)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -3683,6 +3836,11 @@ class FlowLoader:
             if self.motion_blur is not None:
                 blurred, t.blur = alloc_motion_blur(n, ph, pw, t.sharp["image0"].dtype, self.motion_blur[1])
                 t.planes = dict(t.sharp, **{"image%d" % f: b for f, b in enumerate(blurred) if b is not None})
+            t.optics = t.camera = None
+            if self.camera is not None:         # (the frames in front of the camera stay where they are: it has no in-place form)
+                t.optics = t.planes
+                shot, t.camera = alloc_camera(n, ph, pw, t.optics["image0"].dtype)
+                t.planes = dict(t.optics, image0=shot[0], image1=shot[1])
             t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
             t.jitter = alloc_jitter(n) if self.jitter is not None else None
             t.erase = alloc_erase(n) if self.erase is not None else None
@@ -3789,6 +3947,14 @@ class FlowLoader:
         return o
 
     @staticmethod
+    def _camera_options(camera):
+        """camera= as a dict of its own, or None; raises for a name that is no range"""
+        if camera is None:
+            return None
+        _camera_ranges(CameraJob(), camera)
+        return dict(camera)
+
+    @staticmethod
     def _jitter_options(jitter):
         """jitter= as a dict of its own, or None; raises for a name that is no range"""
         if jitter is None:
@@ -3866,7 +4032,7 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
@@ -3890,8 +4056,12 @@ class FlowLoader:
         if self.motion_blur is not None:
             ranges, frames = self.motion_blur
             pick = lambda a, b: tuple(t_ if f in frames else None for f, t_ in enumerate((a, b)))  # noqa: E731
-            g.motion_blur(pick(t.sharp["image0"], t.sharp["image1"]), pick(planes["image0"], planes["image1"]),
+            blurred = planes if t.optics is None else t.optics
+            g.motion_blur(pick(t.sharp["image0"], t.sharp["image1"]), pick(blurred["image0"], blurred["image1"]),
                           flow=pick(t.sharp["flow"], t.sharp.get("flow1")), first_index=first, ranges=ranges, recs_out=t.blur, stream=s, size=size)
+        if self.camera is not None:
+            g.camera((t.optics["image0"], t.optics["image1"]), (planes["image0"], planes["image1"]), recs_out=t.camera, first_index=first,
+                     ranges=self.camera, stream=s, size=size)
         if self.photo is not None:
             g.photo((planes["image0"], planes["image1"]), recs_out=t.photo, first_index=first, ranges=self.photo, stream=s, size=size)
         if self.jitter is not None:
@@ -3941,6 +4111,8 @@ class FlowLoader:
                 more["splat"]["rows"] = rows
         if t.blur is not None:
             more["motion_blur"] = t.blur
+        if t.camera is not None:
+            more["camera"] = t.camera
         if t.photo is not None:
             more["photo"] = t.photo
         if t.jitter is not None:

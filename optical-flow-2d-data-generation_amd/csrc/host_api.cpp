@@ -966,6 +966,106 @@ int ofdg_host_flow_error(const struct ofdg_flow_error_job* job, int n_samples, i
   return OFDG_OK;
 }
 
+// ofdg_camera on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the tap
+// table, the roundings, the sites and the demosaic are the functions the kernel runs (csrc/ofdg_device.h); elements are moved
+// with memcpy.
+int ofdg_camera_draw(uint32_t seed, long long index, const struct ofdg_camera_job* ranges, ofdg_camera_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_camera_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevCameraJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = camera_ranges_error(j)) { g_host_error = std::string("ofdg_camera_draw: ") + why; return OFDG_EINVAL; }
+  const DevCameraRec r = camera_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_camera_taps(int sigma_q8, uint32_t out[13]) {
+  if (!out || sigma_q8 < 1 || sigma_q8 > kCameraMaxSigma) { g_host_error = "ofdg_camera_taps: out is NULL, or sigma_q8 outside 1..1024"; return OFDG_EINVAL; }
+  uint32_t w[kCameraMaxRadius + 1];
+  camera_taps(sigma_q8, camera_radius(sigma_q8), w);
+  std::memcpy(out, w, sizeof(w));
+  return OFDG_OK;
+}
+int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width, int height) {
+  const DevCameraJob* const j = reinterpret_cast<const DevCameraJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = camera_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_camera: ") + why; return OFDG_EINVAL; }
+  const int W = width, H = height;
+  const size_t plane = (size_t)W * H;
+  const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  std::vector<uint8_t> px[3], out[3];   // the bytes of a sample's frame by channel: blurred, then demosaiced
+  std::vector<uint16_t> h8(plane);
+  for (int c = 0; c < 3; ++c) { px[c].resize(plane); out[c].resize(plane); }
+  for (int i = 0; i < n_samples; ++i) {
+    DevCameraRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = camera_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
+    r = camera_sanitise(r);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const int s = r.sigma_q8[f], R = r.radius[f], p = r.bayer;
+      const uint8_t* const sp = static_cast<const uint8_t*>(j->src[f]) + (size_t)i * 3 * plane * ses;
+      uint8_t* const dp = static_cast<uint8_t*>(j->dst[f]) + (size_t)i * 3 * plane * des;
+      if (s == 0 && p < 0 && j->src_fmt == j->dst_fmt) {  // copied bit for bit
+        std::memcpy(dp, sp, 3 * plane * ses);
+        continue;
+      }
+      uint32_t w[kCameraMaxRadius + 1] = {};
+      if (s > 0) camera_taps(s, R, w);
+      for (int c = 0; c < 3; ++c) {
+        for (size_t k = 0; k < plane; ++k) {
+          int b = sp[c * plane + k];
+          if (ses == 4) {
+            float e;
+            std::memcpy(&e, sp + (c * plane + k) * 4, 4);
+            b = photo_index(e);
+          }
+          px[c][k] = (uint8_t)b;
+        }
+        if (s == 0) continue;
+        for (int y = 0; y < H; ++y)
+          for (int x = 0; x < W; ++x) {
+            uint32_t S = 0;
+            for (int k = -R; k <= R; ++k) S += w[k < 0 ? -k : k] * px[c][(size_t)y * W + camera_clamp(x + k, W)];
+            h8[(size_t)y * W + x] = (uint16_t)camera_h8(S);
+          }
+        for (int y = 0; y < H; ++y)
+          for (int x = 0; x < W; ++x) {
+            uint32_t S = 0;
+            for (int k = -R; k <= R; ++k) S += w[k < 0 ? -k : k] * h8[(size_t)camera_clamp(y + k, H) * W + x];
+            px[c][(size_t)y * W + x] = (uint8_t)camera_byte(S);
+          }
+      }
+      for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+          uint32_t o[3] = {px[0][(size_t)y * W + x], px[1][(size_t)y * W + x], px[2][(size_t)y * W + x]};
+          if (p >= 0) {
+            const int a = camera_site_a(x, p), b = camera_site_b(y, p);
+            const size_t xm = camera_reflect(x - 1, W), xp = camera_reflect(x + 1, W);
+            const size_t ym = (size_t)camera_reflect(y - 1, H) * W, yp = (size_t)camera_reflect(y + 1, H) * W, y0 = (size_t)y * W;
+            const uint8_t* const ph = px[camera_site_channel(a ^ 1, b)].data();
+            const uint8_t* const pv = px[camera_site_channel(a, b ^ 1)].data();
+            const uint8_t* const pd = px[camera_site_channel(a ^ 1, b ^ 1)].data();
+            camera_demosaic(a, b, px[camera_site_channel(a, b)][y0 + x], (uint32_t)ph[y0 + xm] + ph[y0 + xp], (uint32_t)pv[ym + x] + pv[yp + x],
+                            (uint32_t)pd[ym + xm] + pd[ym + xp] + pd[yp + xm] + pd[yp + xp], o);
+          }
+          for (int c = 0; c < 3; ++c) out[c][(size_t)y * W + x] = (uint8_t)o[c];
+        }
+      for (int c = 0; c < 3; ++c)
+        for (size_t k = 0; k < plane; ++k) {
+          uint8_t* const q = dp + (c * plane + k) * des;
+          const float e = (float)out[c][k];
+          if (des == 4) std::memcpy(q, &e, 4);
+          else *q = out[c][k];
+        }
+    }
+  }
+  return OFDG_OK;
+}
+
 // ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.

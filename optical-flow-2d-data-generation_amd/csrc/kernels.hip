@@ -5687,4 +5687,233 @@ __global__ __launch_bounds__(kErrThreads) void flow_error_kernel(const DevErrJob
   }
 }
 
+// ---- Camera (ofdg_camera, include/ofdg.h) ----------------------------------------------------------------------------------
+// One launch for both frames and every sample: blockIdx.x counts the kCameraTileW x kCameraTileH tiles of a frame, blockIdx.y
+// the samples, blockIdx.z the frames that are set.  A 4-wave workgroup owns a tile, a lane four consecutive pixels of one row
+// (width % 8 == 0: a lane's four pixels, and the eight of a pair of lanes, are whole or outside together).  The record is read
+// or drawn, and sanitised, on uniform values once per (workgroup, sample); sigma, radius and pattern of the frame are pinned
+// to scalar registers, so the four cases are uniform branches:
+//   neither  the lane's own quad goes from source to destination: bit for bit (float32 to float32), else through its bytes.
+//            Nothing is staged.
+//   blur     channel by channel: the source bytes of the tile and a halo of R + 1 - rows clamped to the plane, columns as whole
+//            aligned quads, a quad outside the plane replicating the edge byte (width % 4 == 0: a quad is inside or outside
+//            whole) - go to LDS as bytes (`src`), the horizontal pass writes 16-bit rows (`h16`), the vertical pass the blurred
+//            bytes of the tile and one pixel around it (`blur`).  A lane computes four neighbouring sums at a time: the
+//            horizontal pass reads `src` a word at a time, unrolled over the words the radius needs, the weights in scalar
+//            registers; the vertical pass reads four 16-bit sums a time.  Products are 24-bit multiply-adds.  Every source
+//            element is read once per tile that needs it.
+//   Bayer    the demosaic reads the mosaic from `blur` - a neighbour's sample is the blurred byte of the channel its site
+//            has -, the coordinates reflected within the plane before they are made relative to the tile, so the entries of
+//            `blur` outside the plane are never looked at.  Without a blur the bytes go to `blur` straight from the source.
+// The taps are built once per (workgroup, sample): lane k makes e[k], lane k >= 1 then w[k], lane 0 w[0], through the
+// functions of the host twin (csrc/ofdg_device.h), as is all the arithmetic, so the result is the twin's byte for byte.
+// Every global index is clamped into the plane; every LDS index is bounded by the constants below (R <= 12).  13.7 KiB of
+// LDS, no atomics, no scratch.
+constexpr int kCameraThreads = 256;
+constexpr int kCameraTileW = 64, kCameraTileH = 16;
+constexpr int kCameraSrcHalo = 16;                                                   // columns of `src` left of the tile: R + 1 <= 13, rounded up to whole quads
+constexpr int kCameraSrcW = kCameraTileW + 2 * kCameraSrcHalo;                       // 96 bytes a row of `src`
+constexpr int kCameraRowsMax = kCameraTileH + 2 + 2 * kCameraMaxRadius;              // 42 rows of `src` and `h16`
+constexpr int kCameraOutHalo = 4;                                                    // columns of `h16` and `blur` left of the tile: 1, rounded up to a quad
+constexpr int kCameraOutW = kCameraTileW + 2 * kCameraOutHalo, kCameraOutH = kCameraTileH + 2;  // 72 x 18
+static_assert(kCameraTileW / 4 * kCameraTileH == kCameraThreads, "a lane per four pixels of the tile");
+static_assert(kCameraSrcHalo >= kCameraOutHalo + kCameraMaxRadius && kCameraThreads > kCameraMaxRadius, "the horizontal pass stays within `src`; a lane per tap");
+// a weight times a byte, an h8 or a sum of two h8: both below 2^24, so one 24-bit multiply-add gives the low 32 bits of the product
+__device__ __forceinline__ uint32_t camera_mad(uint32_t w, uint32_t v, uint32_t acc) { return __umul24(w, v) + acc; }
+// Four neighbouring sums of the horizontal pass: `at` is the word of `src` that holds the four centre bytes, w[d] the weight at
+// distance d (0 above the radius), kNW = ceil(R / 4) the words to look at on either side.  Unrolled: every distance is a constant.
+template <int kNW>
+__device__ __forceinline__ void camera_row_quad(const uint32_t* at, const uint32_t (&w)[kCameraMaxRadius + 1], uint32_t (&S)[4]) {
+#pragma unroll
+  for (int m = -kNW; m <= kNW; ++m) {
+    const uint32_t word = at[m];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t v = (word >> (8 * b)) & 255u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int d = 4 * m + b - q, ad = d < 0 ? -d : d;
+        if (ad <= 4 * kNW && ad <= kCameraMaxRadius) S[q] = camera_mad(w[ad], v, S[q]);
+      }
+    }
+  }
+}
+template <bool kSrcU8, bool kDstU8>
+__global__ __launch_bounds__(kCameraThreads) void camera_kernel(const DevCameraJob job, int n, int W, int H, uint32_t tiles_x) {
+  constexpr int kSES = kSrcU8 ? 1 : 4, kDES = kDstU8 ? 1 : 4;
+  __shared__ uint32_t s_src[kCameraRowsMax * kCameraSrcW / 4];
+  __shared__ uint16_t s_h16[kCameraRowsMax * kCameraOutW] __attribute__((aligned(8)));
+  __shared__ uint32_t s_blur[3 * kCameraOutH * kCameraOutW / 4];
+  __shared__ uint32_t s_e[kCameraMaxRadius + 1], s_w[kCameraMaxRadius + 1];
+  const uint8_t* const blur8 = reinterpret_cast<const uint8_t*>(s_blur);
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int TX = (int)(tx * kCameraTileW), TY = (int)(ty * kCameraTileH);  // the tile's first column and row in the frame
+  const int lx = (int)(threadIdx.x & 15u) * 4, ly = (int)(threadIdx.x >> 4);
+  const int X0 = TX + lx, Y = TY + ly;
+  const int f = (blockIdx.z != 0u || !job.src[0]) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.src[1] : job.src[0]);
+  uint8_t* const d_img = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: camera_arg_error)
+  const bool inside = X0 < W && Y < H;
+  const uint32_t at = inside ? (uint32_t)Y * (uint32_t)W + (uint32_t)X0 : 0u;  // the lane's first pixel in a channel
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    DevCameraRec r;
+    if (job.recs) r = job.recs[i];
+    else r = camera_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
+    r = camera_sanitise(r);
+    if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u) {
+      u32x4* const o = reinterpret_cast<u32x4*>(job.recs_out + i);
+      o[0] = u32x4{(uint32_t)r.sigma_q8[0], (uint32_t)r.sigma_q8[1], (uint32_t)r.bayer, (uint32_t)r.radius[0]};
+      o[1] = u32x4{(uint32_t)r.radius[1], 0u, 0u, 0u};
+    }
+    const int s = __builtin_amdgcn_readfirstlane(f ? r.sigma_q8[1] : r.sigma_q8[0]);
+    const int R = __builtin_amdgcn_readfirstlane(f ? r.radius[1] : r.radius[0]);
+    const int p = __builtin_amdgcn_readfirstlane(r.bayer);
+    const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
+    uint8_t* const dp = d_img + (size_t)i * 3 * plane * kDES;
+    if (s == 0 && p < 0) {  // neither (uniform): the copy
+      if constexpr (!kSrcU8 && !kDstU8) {
+        if (inside) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const size_t e = ((size_t)c * plane + at) * 4u;
+            quad_store_u32x4(reinterpret_cast<u32x4*>(dp + e), *reinterpret_cast<const u32x4*>(sp + e));
+          }
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          uint32_t own[4] = {0u, 0u, 0u, 0u};
+          if (inside) quad_load_bytes<kSrcU8>(sp + ((size_t)c * plane + at) * kSES, own);
+          if constexpr (kDstU8) quad_store_bytes_pair(dp + (uint32_t)c * plane + at, quad_word(own), inside);
+          else quad_store_bytes_f32(dp + ((size_t)c * plane + at) * 4u, own, inside);
+        }
+      }
+      continue;
+    }
+    if (s > 0) {  // the taps of this frame
+      if ((int)threadIdx.x <= R) s_e[threadIdx.x] = camera_tap_e(s, (int)threadIdx.x);
+      __syncthreads();
+      if ((int)threadIdx.x >= 1 && (int)threadIdx.x <= R) {
+        uint32_t E = s_e[0];
+        for (int k = 1; k <= R; ++k) E += 2u * s_e[k];
+        s_w[threadIdx.x] = camera_tap_w(s_e[threadIdx.x], E);
+      } else if ((int)threadIdx.x > R && (int)threadIdx.x <= kCameraMaxRadius) {
+        s_w[threadIdx.x] = 0u;
+      }
+      __syncthreads();
+      if (threadIdx.x == 0u) {
+        uint32_t side = 0u;
+        for (int k = 1; k <= R; ++k) side += s_w[k];
+        s_w[0] = 65536u - 2u * side;
+      }
+      // (the barrier behind the first staging stands between this and the first use of s_w[0])
+    }
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {
+      const uint8_t* const cp = sp + (size_t)c * plane * kSES;
+      uint32_t* const bl = s_blur + c * (kCameraOutH * kCameraOutW / 4);
+      if (s > 0) {
+        // `src`: row j is the frame's row TY - 1 - R + j, clamped; quad q its columns TX - 16 + 4 q ..
+        const int rows = kCameraOutH + 2 * R;
+        const int q0 = (kCameraSrcHalo - kCameraOutHalo - R) >> 2, nq = kCameraSrcW / 4 - 2 * q0;
+        for (int t = (int)threadIdx.x; t < rows * nq; t += kCameraThreads) {
+          const int j = t / nq, q = q0 + (t - j * nq);
+          const int gy = camera_clamp(TY - 1 - R + j, H), gx = TX - kCameraSrcHalo + 4 * q;
+          const int cx = gx < 0 ? 0 : gx >= W ? W - 4 : gx;
+          uint32_t b[4];
+          quad_load_bytes<kSrcU8>(cp + ((size_t)gy * (uint32_t)W + (uint32_t)cx) * kSES, b);
+          const uint32_t word = gx < 0 ? b[0] * 0x01010101u : gx >= W ? b[3] * 0x01010101u : quad_word(b);
+          s_src[j * (kCameraSrcW / 4) + q] = word;
+        }
+        __syncthreads();  // (also: the last channel's vertical pass has read `h16`, and s_w[0] is written)
+        // the horizontal pass: `h16` row j, columns TX - 4 + 4 g .. + 3.  The weights go to scalar registers (they are the
+        // workgroup's), the bytes are read a word at a time.
+        uint32_t w[kCameraMaxRadius + 1];
+#pragma unroll
+        for (int k = 0; k <= kCameraMaxRadius; ++k) w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_w[k]) & 0x1FFFFu;
+        const int words = (R + 3) >> 2;  // (uniform)
+        for (int t = (int)threadIdx.x; t < rows * (kCameraOutW / 4); t += kCameraThreads) {
+          const int j = t / (kCameraOutW / 4), g = t - j * (kCameraOutW / 4);
+          const uint32_t* const at = s_src + j * (kCameraSrcW / 4) + (kCameraSrcHalo - kCameraOutHalo) / 4 + g;
+          uint32_t S[4] = {0u, 0u, 0u, 0u};
+          if (words == 1) camera_row_quad<1>(at, w, S);
+          else if (words == 2) camera_row_quad<2>(at, w, S);
+          else camera_row_quad<3>(at, w, S);
+          const u32x2 o = {camera_h8(S[0]) | (camera_h8(S[1]) << 16), camera_h8(S[2]) | (camera_h8(S[3]) << 16)};
+          *reinterpret_cast<u32x2*>(s_h16 + j * kCameraOutW + 4 * g) = o;
+        }
+        __syncthreads();
+        // the vertical pass: `blur` row v is the frame's row TY - 1 + v, from the rows v .. v + 2 R of `h16`, four columns
+        // (8 bytes) a read
+        for (int t = (int)threadIdx.x; t < kCameraOutH * (kCameraOutW / 4); t += kCameraThreads) {
+          const int v = t / (kCameraOutW / 4), g = t - v * (kCameraOutW / 4);
+          const u32x2* const col = reinterpret_cast<const u32x2*>(s_h16 + (v + R) * kCameraOutW + 4 * g);
+          const u32x2 c = col[0];
+          uint32_t S0 = camera_mad(w[0], c[0] & 0xFFFFu, 0u), S1 = camera_mad(w[0], c[0] >> 16, 0u);
+          uint32_t S2 = camera_mad(w[0], c[1] & 0xFFFFu, 0u), S3 = camera_mad(w[0], c[1] >> 16, 0u);
+#pragma unroll 1
+          for (int k = 1; k <= R; ++k) {
+            const uint32_t wk = s_w[k] & 0x1FFFFu;
+            const u32x2 up = col[-k * (kCameraOutW / 4)], dn = col[k * (kCameraOutW / 4)];
+            S0 = camera_mad(wk, (up[0] & 0xFFFFu) + (dn[0] & 0xFFFFu), S0);
+            S1 = camera_mad(wk, (up[0] >> 16) + (dn[0] >> 16), S1);
+            S2 = camera_mad(wk, (up[1] & 0xFFFFu) + (dn[1] & 0xFFFFu), S2);
+            S3 = camera_mad(wk, (up[1] >> 16) + (dn[1] >> 16), S3);
+          }
+          bl[v * (kCameraOutW / 4) + g] = camera_byte(S0) | (camera_byte(S1) << 8) | (camera_byte(S2) << 16) | (camera_byte(S3) << 24);
+        }
+        // (the next channel's first barrier stands between this pass and the next writing of `h16`; `src` was last read
+        // in front of the barrier above)
+      } else {
+        // Bayer alone: the bytes of the tile and one pixel around it, as whole quads at clamped places (an entry outside the
+        // plane is not looked at)
+        for (int t = (int)threadIdx.x; t < kCameraOutH * (kCameraOutW / 4); t += kCameraThreads) {
+          const int v = t / (kCameraOutW / 4), g = t - v * (kCameraOutW / 4);
+          const int gy = camera_clamp(TY - 1 + v, H), gx = TX - kCameraOutHalo + 4 * g;
+          const int cx = gx < 0 ? 0 : gx >= W ? W - 4 : gx;
+          uint32_t b[4];
+          quad_load_bytes<kSrcU8>(cp + ((size_t)gy * (uint32_t)W + (uint32_t)cx) * kSES, b);
+          bl[v * (kCameraOutW / 4) + g] = quad_word(b);
+        }
+      }
+    }
+    __syncthreads();
+    uint32_t out[3][4] = {};
+    if (inside) {
+      const int at0 = (ly + 1) * kCameraOutW + kCameraOutHalo + lx;  // the lane's first pixel in a channel of `blur`
+      if (p < 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const uint32_t w = s_blur[(c * kCameraOutH * kCameraOutW + at0) >> 2];
+          out[c][0] = w & 255u; out[c][1] = (w >> 8) & 255u; out[c][2] = (w >> 16) & 255u; out[c][3] = w >> 24;
+        }
+      } else {
+        const int b = camera_site_b(Y, p);
+        const int rm = (camera_reflect(Y - 1, H) - TY + 1) * kCameraOutW, rp = (camera_reflect(Y + 1, H) - TY + 1) * kCameraOutW, r0 = (ly + 1) * kCameraOutW;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int x = X0 + q, a = camera_site_a(x, p);
+          const int x0 = kCameraOutHalo + lx + q, xm = camera_reflect(x - 1, W) - TX + kCameraOutHalo, xp = camera_reflect(x + 1, W) - TX + kCameraOutHalo;
+          const uint8_t* const pc = blur8 + camera_site_channel(a, b) * (kCameraOutH * kCameraOutW);
+          const uint8_t* const ph = blur8 + camera_site_channel(a ^ 1, b) * (kCameraOutH * kCameraOutW);
+          const uint8_t* const pv = blur8 + camera_site_channel(a, b ^ 1) * (kCameraOutH * kCameraOutW);
+          const uint8_t* const pd = blur8 + camera_site_channel(a ^ 1, b ^ 1) * (kCameraOutH * kCameraOutW);
+          uint32_t o[3];
+          camera_demosaic(a, b, pc[r0 + x0], (uint32_t)ph[r0 + xm] + ph[r0 + xp], (uint32_t)pv[rm + x0] + pv[rp + x0],
+                          (uint32_t)pd[rm + xm] + pd[rm + xp] + pd[rp + xm] + pd[rp + xp], o);
+          out[0][q] = o[0]; out[1][q] = o[1]; out[2][q] = o[2];
+        }
+      }
+    }
+    // (the lanes of a pair are inside together: X0 of the even one is a multiple of 8)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (kDstU8) quad_store_bytes_pair(dp + (uint32_t)c * plane + at, quad_word(out[c]), inside);
+      else quad_store_bytes_f32(dp + ((size_t)c * plane + at) * 4u, out[c], inside);
+    }
+    __syncthreads();  // (the next sample of this workgroup stages the tile again)
+  }
+}
+
 }  // namespace ofdg

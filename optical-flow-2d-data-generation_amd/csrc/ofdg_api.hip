@@ -271,7 +271,7 @@ static std::string err_text(uint32_t e) {
 }
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
-// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
+// ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_camera, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
 // ofdg_flow_error
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
@@ -294,7 +294,7 @@ struct PostOp {
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
 // 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel,
-// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel.
+// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel, 4 camera_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -1917,6 +1917,36 @@ int ofdg_jitter(ofdg_ctx* c, const struct ofdg_jitter_job* job, int n_samples, v
   with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
     with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
       hipLaunchKernelGGL((jitter_apply_kernel<decltype(src_u8)::value, decltype(dst_u8)::value>), g, dim3(kJitterThreads), 0, st, *j, n_samples, W, H, per_frame);
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// The camera of caller-given frames - lens blur, Bayer mosaic and demosaic -: one kernel on `stream` for both frames and every
+// sample.
+int ofdg_camera(ofdg_ctx* c, const struct ofdg_camera_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_camera"};
+  const DevCameraJob* const j = reinterpret_cast<const DevCameraJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = camera_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = camera_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t tiles_x = ((uint32_t)W + kCameraTileW - 1) / kCameraTileW, tiles_y = ((uint32_t)H + kCameraTileH - 1) / kCameraTileH;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), (j->src[0] ? 1u : 0u) + (j->src[1] ? 1u : 0u));
+  with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
+      hipLaunchKernelGGL((camera_kernel<decltype(src_u8)::value, decltype(dst_u8)::value>), g, dim3(kCameraThreads), 0, st, *j, n_samples, W, H, tiles_x);
     });
   });
   HIP_OK(c, hipGetLastError());

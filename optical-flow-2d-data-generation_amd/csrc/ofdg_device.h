@@ -1378,6 +1378,165 @@ inline const char* jitter_arg_error(const DevJitterJob* j, int n, int width, int
   return nullptr;
 }
 
+// ---- Camera (ofdg_camera, include/ofdg.h) ----------------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the tap table, the roundings of the two blur passes, the mosaic's sites, the demosaic's means and the argument
+// rules.  The taps are fp64 +, -, * through ofdg_det_exp (no contraction in any unit that includes this) and one rint;
+// everything else is integers.
+constexpr int kCameraMaxSigma = OFDG_CAMERA_MAX_SIGMA_Q8, kCameraMaxRadius = OFDG_CAMERA_MAX_RADIUS;
+struct DevCameraRec {  // ofdg_camera_rec, field for field
+  int32_t sigma_q8[2], bayer, radius[2], reserved[3];
+};
+struct DevCameraJob {  // struct ofdg_camera_job, field for field
+  const void* src[2];
+  void* dst[2];
+  const DevCameraRec* recs;
+  DevCameraRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, src_fmt, dst_fmt, flags, pattern;
+  float sigma_min, sigma_max, sigma_delta, blur_prob, bayer_prob;
+  int32_t reserved;
+};
+static_assert(sizeof(ofdg_camera_rec) == sizeof(DevCameraRec) && sizeof(DevCameraRec) == 32 && offsetof(ofdg_camera_rec, bayer) == offsetof(DevCameraRec, bayer) &&
+              offsetof(DevCameraRec, bayer) == 8 && offsetof(ofdg_camera_rec, radius) == offsetof(DevCameraRec, radius) && offsetof(DevCameraRec, radius) == 12 &&
+              offsetof(ofdg_camera_rec, reserved) == offsetof(DevCameraRec, reserved) && offsetof(DevCameraRec, reserved) == 20,
+              "ofdg_camera_rec: 32 bytes, the layout the kernel reads and writes as two 16-byte pieces");
+static_assert(sizeof(struct ofdg_camera_job) == sizeof(DevCameraJob) && sizeof(DevCameraJob) == 112 && offsetof(struct ofdg_camera_job, dst) == offsetof(DevCameraJob, dst) &&
+              offsetof(struct ofdg_camera_job, recs) == offsetof(DevCameraJob, recs) && offsetof(struct ofdg_camera_job, recs_out) == offsetof(DevCameraJob, recs_out) &&
+              offsetof(struct ofdg_camera_job, first_index) == offsetof(DevCameraJob, first_index) && offsetof(struct ofdg_camera_job, seed) == offsetof(DevCameraJob, seed) &&
+              offsetof(DevCameraJob, seed) == 56 && offsetof(struct ofdg_camera_job, width) == offsetof(DevCameraJob, width) &&
+              offsetof(struct ofdg_camera_job, src_fmt) == offsetof(DevCameraJob, src_fmt) && offsetof(struct ofdg_camera_job, pattern) == offsetof(DevCameraJob, pattern) &&
+              offsetof(DevCameraJob, pattern) == 80 && offsetof(struct ofdg_camera_job, sigma_min) == offsetof(DevCameraJob, sigma_min) && offsetof(DevCameraJob, sigma_min) == 84 &&
+              offsetof(struct ofdg_camera_job, bayer_prob) == offsetof(DevCameraJob, bayer_prob) && offsetof(struct ofdg_camera_job, reserved) == offsetof(DevCameraJob, reserved) &&
+              offsetof(DevCameraJob, reserved) == 104,
+              "struct ofdg_camera_job: 112 bytes, the layout the kernel takes");
+OFDG_HD_FN int32_t camera_q8(float px) { return (int32_t)lrintf(px * 256.0f); }
+// The record of global sample g: Philox blocks 0 and 1 under the sampler's key of g at the counters {j, 0, 0x0c79, 0}.  `j`
+// supplies the five ranges and the pattern (camera_ranges_error has passed).  Not sanitised.
+OFDG_HD_FN DevCameraRec camera_draw_rec(uint32_t seed, unsigned long long g, const DevCameraJob& j) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords a = crop_philox(CropWords{0u, 0u, 0x0c79u, 0u}, k0, k1);
+  const CropWords b = crop_philox(CropWords{1u, 0u, 0x0c79u, 0u}, k0, k1);
+  const int32_t lo = camera_q8(j.sigma_min), hi = camera_q8(j.sigma_max), D = camera_q8(j.sigma_delta);
+  const bool blurred = photo_unit(a.x) < j.blur_prob, mosaic = photo_unit(a.w) < j.bayer_prob;
+  const int32_t s0 = lo + (int32_t)(uint32_t)(((unsigned long long)a.y * (uint32_t)(hi - lo + 1)) >> 32);
+  const int32_t s1 = s0 + jitter_isym(a.z, D);
+  const int32_t p = j.pattern >= 0 ? j.pattern : (int32_t)(b.x >> 30);
+  DevCameraRec r;
+  r.sigma_q8[0] = blurred ? s0 : 0; r.sigma_q8[1] = blurred ? s1 : 0;
+  r.bayer = mosaic ? p : -1;
+  r.radius[0] = 0; r.radius[1] = 0;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+OFDG_HD_FN int32_t camera_radius(int32_t s) {
+  const int32_t R = (3 * s + 255) >> 8;
+  return R < kCameraMaxRadius ? R : kCameraMaxRadius;
+}
+// What is used of a record, given or drawn.  No record makes the kernel touch a byte outside a plane or its tile's window.
+OFDG_HD_FN DevCameraRec camera_sanitise(DevCameraRec r) {
+  for (int f = 0; f < 2; ++f) {
+    r.sigma_q8[f] = jitter_clamp(r.sigma_q8[f], 0, kCameraMaxSigma);
+    r.radius[f] = camera_radius(r.sigma_q8[f]);
+  }
+  r.bayer = (r.bayer < -1 || r.bayer > 3) ? -1 : r.bayer;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+// e[k] of the tap table: the Gaussian at distance k in 8.24, for s in 1..1024 and k in 0..12
+OFDG_HD_FN uint32_t camera_tap_e(int s, int k) {
+  const double x = -(double)(k * k) * 32768.0 / (double)(s * s);
+  return (uint32_t)(long long)rint(ofdg_det_exp(x) * 16777216.0);
+}
+// w[k], k >= 1: e[k] of the 65536 the taps sum to, to nearest (E < 2^29, e 65536 < 2^41)
+OFDG_HD_FN uint32_t camera_tap_w(uint32_t e, uint32_t E) { return (uint32_t)(((unsigned long long)e * 65536ull + (unsigned long long)(E / 2u)) / (unsigned long long)E); }
+// The table w[0..R] of sigma s (1..1024) and its radius R; entries above R are zeroed.
+OFDG_HD_FN void camera_taps(int s, int R, uint32_t (&w)[kCameraMaxRadius + 1]) {
+  uint32_t e[kCameraMaxRadius + 1], E = 0u, side = 0u;
+  for (int k = 0; k <= kCameraMaxRadius; ++k) {
+    e[k] = k <= R ? camera_tap_e(s, k) : 0u;
+    E += k ? 2u * e[k] : e[k];
+  }
+  for (int k = 1; k <= kCameraMaxRadius; ++k) {
+    w[k] = k <= R ? camera_tap_w(e[k], E) : 0u;
+    side += w[k];
+  }
+  w[0] = 65536u - 2u * side;
+}
+// the roundings of the two passes: a row sum to h8 (at most 65280), a column sum of h8 to the byte
+OFDG_HD_FN uint32_t camera_h8(uint32_t S) { return (S + 128u) >> 8; }
+OFDG_HD_FN uint32_t camera_byte(uint32_t S) { return (S + (1u << 23)) >> 24; }
+// edge replication, and reflection without repeating the edge (side >= 2; at is in [-1, side])
+OFDG_HD_FN int camera_clamp(int at, int side) { return at < 0 ? 0 : at >= side ? side - 1 : at; }
+OFDG_HD_FN int camera_reflect(int at, int side) { return at < 0 ? -at : at >= side ? 2 * side - 2 - at : at; }
+// The channel (0 B, 1 G, 2 R: the plane order) the mosaic of pattern p samples at the site (a, b) of a pixel.
+OFDG_HD_FN int camera_site_a(int x, int p) { return (x + (p & 1)) & 1; }
+OFDG_HD_FN int camera_site_b(int y, int p) { return (y + (p >> 1)) & 1; }
+OFDG_HD_FN int camera_site_channel(int a, int b) { return (a | b) == 0 ? 2 : (a & b) ? 0 : 1; }
+// The demosaiced pixel from its own sample c, the sums of its two horizontal (sh), two vertical (sv) and four diagonal (sd)
+// neighbours in the mosaic and its site: o[0..2] = B, G, R.
+OFDG_HD_FN void camera_demosaic(int a, int b, uint32_t c, uint32_t sh, uint32_t sv, uint32_t sd, uint32_t (&o)[3]) {
+  const uint32_t hz = (sh + 1u) >> 1, vt = (sv + 1u) >> 1, cr = (sh + sv + 2u) >> 2, dg = (sd + 2u) >> 2;
+  if (a == b) {  // an R site (0, 0) or a B site (1, 1)
+    o[a ? 0 : 2] = c; o[1] = cr; o[a ? 2 : 0] = dg;
+  } else {       // a G site: on an R row (b = 0) R lies beside it and B above and below, on a B row the reverse
+    o[1] = c; o[b ? 0 : 2] = hz; o[b ? 2 : 0] = vt;
+  }
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* camera_plane_size(const DevCameraJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The ranges of the draw and the pattern: the first rule broken, or nullptr.
+inline const char* camera_ranges_error(const DevCameraJob& j) {
+  if (!(j.sigma_min >= 0.0f && j.sigma_min <= 4.0f)) return "sigma_min must lie in [0, 4]";
+  if (!(j.sigma_max >= 0.0f && j.sigma_max <= 4.0f)) return "sigma_max must lie in [0, 4]";
+  if (j.sigma_min > j.sigma_max) return "sigma_min must not be above sigma_max";
+  if (!(j.sigma_delta >= 0.0f && j.sigma_delta <= 4.0f)) return "sigma_delta must lie in [0, 4]";
+  if (!(j.blur_prob >= 0.0f && j.blur_prob <= 1.0f)) return "blur_prob must lie in [0, 1]";
+  if (!(j.bayer_prob >= 0.0f && j.bayer_prob <= 1.0f)) return "bayer_prob must lie in [0, 1]";
+  if (j.pattern < -1 || j.pattern > 3) return "pattern must lie in -1..3";
+  return nullptr;
+}
+// The argument rules ofdg_camera and ofdg_host_camera share: the first rule broken, or nullptr.  width, height: what
+// camera_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* camera_arg_error(const DevCameraJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->flags != 0) return "flags must be 0";
+  if (j->reserved != 0) return "reserved must be 0";
+  if (const char* why = camera_ranges_error(*j)) return why;
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
+    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
+    frames += j->src[f] ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  // no in-place form: a written range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[6];
+  int nr = 0;
+  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    r[nr++] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false};
+    r[nr++] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevCameraRec), false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevCameraRec), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
 // sanitising, the half-displacement, the tap count and step, the tap value, the mean and the argument rules.  Compiled

@@ -23,6 +23,9 @@
 //   host_input_check jitter             ofdg_host_jitter, ofdg_jitter_draw and ofdg_host_jitter_hue on exactly sized heap buffers:
 //                                       every format pair, copying and in place, one frame and both, odd sizes, hostile given
 //                                       records and drawn ones, every refusal
+//   host_input_check camera             ofdg_host_camera, ofdg_camera_draw and ofdg_camera_taps on exactly sized heap buffers: the
+//                                       four test sizes, every format pair, one frame and both, every record case and hostile
+//                                       given records, drawn ones, frames of arbitrary bit patterns, every refusal
 //   host_input_check flow_vis           ofdg_host_flow_vis and ofdg_host_flow_vis_tables on exactly sized heap buffers: the test
 //                                       sizes, both flow formats and layouts, the three norms and both ends of max_flow, with
 //                                       and without dimming, extreme flows and any bit pattern, every refusal
@@ -770,6 +773,132 @@ int jitter() {
   return refused == 24 ? 0 : 1;
 }
 
+// ofdg_host_camera, ofdg_camera_draw and ofdg_camera_taps on heap buffers of exactly the planes' sizes (a byte read or written
+// beside one is a report - the blur's clamped taps and the mosaic's reflected neighbours at every edge of 8x2, 24x6, 72x40 and
+// 264x200): the four format pairs, frame 0, frame 1 and both, given records that hold the identity, Bayer alone, blur alone at
+// R = 1, 3 and 12, both, the frames apart, every pattern, and fields at and beyond the ends of int32 (a signed overflow in the
+// clamp or the radius is a report), drawn records at the widest ranges; float32 frames of arbitrary bit patterns (NaN,
+// infinities, denormals); every tap table; then every refusal.
+int camera() {
+  const int32_t hostile[] = {INT32_MIN, INT32_MIN + 1, -1025, -2, -1, 0, 1, 2, 3, 4, 85, 86, 256, 1023, 1024, 1025, 65536, INT32_MAX - 1, INT32_MAX};
+  const int n_hostile = (int)(sizeof hostile / sizeof hostile[0]);
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 4; ++size) {
+    const int W = size == 0 ? 8 : size == 1 ? 24 : size == 2 ? 72 : 264, H = size == 0 ? 2 : size == 1 ? 6 : size == 2 ? 40 : 200, n = 16;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 4; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4);
+      std::vector<uint8_t> src[2], dst[2];
+      uint32_t x = 4242u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        src[f].resize(sb); dst[f].assign(db, 0xA5);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          if (sf == OFDG_FMT_U8) { src[f][e] = (e % 7) == 0 ? (uint8_t)(e % 3 ? 255 : 0) : (uint8_t)(x >> 24); continue; }
+          const float v = (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          const uint32_t bits = x ^ (x << 13);  // (every third element: any bit pattern)
+          std::memcpy(src[f].data() + 4 * e, (e % 3) == 0 ? (const void*)&bits : (const void*)&v, 4);
+        }
+      }
+      // records 0..9: the cases by name; 10..15: every field walks the hostile values
+      std::vector<ofdg_camera_rec> recs(n), used(n);
+      const int32_t cases[10][3] = {{0, 0, -1}, {0, 0, 2}, {85, 85, -1}, {256, 256, -1}, {1024, 1024, -1}, {256, 256, 0}, {300, 0, 1}, {0, 700, 3}, {40, 1000, -1}, {1024, 1, 3}};
+      for (int i = 0; i < n; ++i) {
+        ofdg_camera_rec& r = recs[i];
+        std::memset(&r, 0x5A, sizeof r);
+        if (i < 10) { r.sigma_q8[0] = cases[i][0]; r.sigma_q8[1] = cases[i][1]; r.bayer = cases[i][2]; continue; }
+        const int k = (i - 10) * 3 + fmts + 5 * size;
+        r.sigma_q8[0] = hostile[k % n_hostile]; r.sigma_q8[1] = hostile[(k + 7) % n_hostile]; r.bayer = hostile[(k + 11) % n_hostile];
+        r.radius[0] = hostile[(k + 1) % n_hostile]; r.radius[1] = hostile[(k + 2) % n_hostile];
+      }
+      for (int drawn = 0; drawn < 2; ++drawn)
+        for (int frames = 1; frames < 4; ++frames) {
+          if (size == 3 && frames != 3) continue;  // (the largest size: both frames only)
+          struct ofdg_camera_job job;
+          std::memset(&job, 0, sizeof job);
+          for (int f = 0; f < 2; ++f)
+            if ((frames >> f) & 1) { job.src[f] = src[f].data(); job.dst[f] = dst[f].data(); }
+          job.recs = drawn ? nullptr : recs.data();
+          job.recs_out = used.data();
+          job.first_index = (1ll << 32) - 1; job.seed = 7;
+          job.src_fmt = sf; job.dst_fmt = df;
+          job.sigma_min = 0.0f; job.sigma_max = 4.0f; job.sigma_delta = 4.0f; job.blur_prob = 0.9f; job.bayer_prob = 0.7f; job.pattern = -1;
+          const int rc = ofdg_host_camera(&job, n, W, H);
+          if (rc) { std::printf("camera: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+          ++calls;
+          for (int f = 0; f < 2; ++f)
+            if ((frames >> f) & 1) sum = sum * 31 + fnv1a(dst[f].data(), dst[f].size());
+          sum = sum * 31 + fnv1a((const uint8_t*)used.data(), used.size() * sizeof(ofdg_camera_rec));
+          for (int i = 0; i < n; ++i)
+            for (int f = 0; f < 2; ++f)
+              if (used[i].sigma_q8[f] < 0 || used[i].sigma_q8[f] > 1024 || used[i].radius[f] < 0 || used[i].radius[f] > 12 || (used[i].sigma_q8[f] > 0) != (used[i].radius[f] > 0) ||
+                  used[i].bayer < -1 || used[i].bayer > 3 || used[i].reserved[f] != 0 || used[i].reserved[2] != 0) { std::printf("camera: a record left its bounds\n"); return 1; }
+        }
+    }
+  }
+  for (int s = 1; s <= 1024; ++s) {  // every table, into a buffer of exactly 13 words
+    std::vector<uint32_t> w(13, 0xA5A5A5A5u);
+    if (ofdg_camera_taps(s, w.data()) != OFDG_OK) { std::printf("camera: the taps call failed\n"); return 1; }
+    unsigned long long total = w[0];
+    for (int k = 1; k < 13; ++k) total += 2ull * w[k];
+    if (total != 65536ull) { std::printf("camera: the taps of %d sum to %llu\n", s, total); return 1; }
+    ++calls;
+    sum = sum * 31 + fnv1a((const uint8_t*)w.data(), 52);
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> src((size_t)n * 3 * W * H * 4, 0), dst((size_t)n * 3 * W * H * 4 + 64, 0xA5), out((size_t)n * 32, 0xA5);
+    struct ofdg_camera_job good;
+    std::memset(&good, 0, sizeof good);
+    good.src[0] = src.data(); good.dst[0] = dst.data(); good.recs_out = (ofdg_camera_rec*)out.data();
+    good.sigma_min = 0.3f; good.sigma_max = 1.5f; good.sigma_delta = 0.1f; good.blur_prob = 0.8f; good.bayer_prob = 0.5f; good.pattern = -1;
+    const auto refuse = [&](struct ofdg_camera_job j, int ns, int w, int h) {
+      if (ofdg_host_camera(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_camera: ", 18) == 0) ++refused;
+      else std::printf("camera: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_camera_job j;
+    if (ofdg_host_camera(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.width = W + 8; j.height = H; refuse(j, n, W, H);
+    j = good; j.src_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flags = 1; refuse(j, n, W, H);
+    j = good; j.reserved = 1; refuse(j, n, W, H);
+    j = good; j.sigma_min = NAN; refuse(j, n, W, H);
+    j = good; j.sigma_max = 4.5f; refuse(j, n, W, H);
+    j = good; j.sigma_min = 1.6f; refuse(j, n, W, H);
+    j = good; j.sigma_delta = -0.5f; refuse(j, n, W, H);
+    j = good; j.blur_prob = 1.5f; refuse(j, n, W, H);
+    j = good; j.bayer_prob = INFINITY; refuse(j, n, W, H);
+    j = good; j.pattern = 4; refuse(j, n, W, H);
+    j = good; j.pattern = -2; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[1] = nullptr; j.dst[1] = dst.data(); j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data() + 16; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data(); refuse(j, n, W, H);
+    j = good; j.recs_out = (ofdg_camera_rec*)(dst.data() + 16); refuse(j, n, W, H);
+    ofdg_camera_rec rec;
+    std::memset(&rec, 0xA5, sizeof rec);
+    j = good; j.sigma_delta = 5.0f;
+    if (ofdg_camera_draw(1, 0, &j, &rec) == OFDG_EINVAL && ofdg_camera_draw(1, 0, nullptr, &rec) == OFDG_EINVAL && ofdg_camera_draw(1, 0, &good, nullptr) == OFDG_EINVAL) ++refused;
+    uint32_t w[13];
+    std::memset(w, 0xA5, sizeof w);
+    if (ofdg_camera_taps(0, w) == OFDG_EINVAL && ofdg_camera_taps(1025, w) == OFDG_EINVAL && ofdg_camera_taps(INT32_MIN, w) == OFDG_EINVAL && ofdg_camera_taps(256, nullptr) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; }) &&
+                       ((const uint8_t*)&rec)[0] == 0xA5 && ((const uint8_t*)&rec)[31] == 0xA5 && w[0] == 0xA5A5A5A5u && w[12] == 0xA5A5A5A5u;
+    if (!clean) { std::printf("camera: a refusal wrote something\n"); return 1; }
+    if (ofdg_camera_draw(1, (1ll << 32) + 3, &good, &rec) != OFDG_OK || ofdg_host_camera(&good, n, W, H) != OFDG_OK) { std::printf("camera: the valid call failed\n"); return 1; }
+  }
+  std::printf("camera calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 27 ? 0 : 1;
+}
+
 // ofdg_host_flow_vis and ofdg_host_flow_vis_tables on heap buffers of exactly the planes' sizes (a byte read or written beside
 // one is a report): float32 and binary16 flows that hold zeros, every octant, NaN, both infinities, +-2^20, the largest usable
 // value and random bit patterns (a signed overflow in the Q8 components, the roots or the colour is a report), both layouts,
@@ -1018,10 +1147,11 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "reproject") == 0) return reproject();
   if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
   if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
+  if (argc >= 2 && std::strcmp(argv[1], "camera") == 0) return camera();
   if (argc >= 2 && std::strcmp(argv[1], "flow_vis") == 0) return flow_vis();
   if (argc >= 2 && std::strcmp(argv[1], "flow_error") == 0) return flow_error();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | flow_vis | flow_error\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | camera | flow_vis | flow_error\n", argv[0]);
   return 2;
 }
