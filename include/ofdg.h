@@ -1188,9 +1188,9 @@ int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hu
  * OFDG_STREAM_OWN before any render / forward call on the context.
  *
  * Out of scope: noise between mosaic and demosaic (ofdg_photo's noise stays per element), any demosaicer but bilinear, white
- * balance, gamma, sharpening, lens distortion and chromatic aberration (they move pixels, so they change the flow),
- * vignetting, depth of field by label, a sigma above 4 px, a pattern per frame, an in-place form.  The flow, maps, labels,
- * splat and reprojection planes are not touched.
+ * balance, gamma, sharpening, depth of field by label, a sigma above 4 px, a pattern per frame, an in-place form.  Lens
+ * distortion, lateral chromatic aberration and vignetting are ofdg_lens below: they move pixels, so they change the flow.
+ * The flow, maps, labels, splat and reprojection planes are not touched.
  */
 #define OFDG_CAMERA_MAX_SIGMA_Q8 1024  /* 4 px */
 #define OFDG_CAMERA_MAX_RADIUS 12      /* taps on each side of the centre */
@@ -1224,6 +1224,128 @@ int ofdg_camera_draw(uint32_t seed, long long index, const struct ofdg_camera_jo
 /* The tap table of step 3 for sigma_q8 in 1..1024 (pure, no GPU): out[0..R] the weights, out[R+1..12] zero.  OFDG_EINVAL
  * (ofdg_host_last_error) for out NULL or a sigma_q8 outside 1..1024. */
 int ofdg_camera_taps(int sigma_q8, uint32_t out[13]);
+
+/*
+ * Lens: every output of a batch - frames, both flows, both occlusion maps, both label planes - bent by a one-parameter radial
+ * distortion about a centre drawn per sample (ONE lens for both frames: it is one camera), the ground-truth flow carried
+ * through it exactly, the frames with lateral chromatic aberration (B and R sampled at a slightly different magnification
+ * than G) and vignetting, in ONE launch behind the call that wrote the planes.  The record is a pure function of (seed,
+ * global sample index).  Everything below is exact: the kernel, ofdg_host_lens and the numpy restatement of the tests give
+ * the same bits.  All arithmetic is IEEE, each operation rounded on its own (no contraction); fl64(.) / fl32(.) mark a
+ * rounding where the text would otherwise leave it open.
+ *
+ * Planes: the eight planes, their order and their formats are ofdg_crop's (OFDG_CROP_IMAGE0 .. OFDG_CROP_LABEL1, image_fmt,
+ * flow_fmt, occ_fmt).  src[k] and dst[k] are both [n,C,height,width]: the output has the source's size; a window is
+ * ofdg_crop's or ofdg_spatial's business.  width = height = 0: the context's frame; otherwise any size the context's rule
+ * allows (width a multiple of 8 and at least 8, height even and at least 2, no side above 2^20, W * H below 2^31).  Every
+ * plane is optional on its own: src[k] and dst[k] both NULL.  There is no in-place form.
+ *
+ * Record (ofdg_lens_rec, 64 bytes): doubles k1, z, ca_b, ca_r, vig, cx, cy, then int32 reserved[2].  Per sample, in fp64:
+ * hw = (W - 1) / 2.0, hh = (H - 1) / 2.0, inv = fl64(1 / fl64(fl64(hw * hw) + fl64(hh * hh))) - one over the squared
+ * half-diagonal -, and the magnification of channel ch, zc = fl64(z * fl64(1 + ca)) with ca = ca_b for B, 0 for G, ca_r for R.
+ * For destination pixel (X, Y):  dx = fl64(X - cx), dy = fl64(Y - cy), rho = fl64(fl64(fl64(dx * dx) + fl64(dy * dy)) * inv),
+ * L = fl64(1 + fl64(k1 * rho)).  The source position under magnification m is
+ *   qx = fl64(cx + fl64(fl64(m * L) * dx)),   qy = fl64(cy + fl64(fl64(m * L) * dy)).
+ * The GEOMETRIC map S uses m = z; frames use m = zc of their channel.  k1 > 0 is barrel, k1 < 0 pincushion distortion.
+ *
+ * The record of sample i is recs[i] when recs is given, else ofdg_lens_draw(seed, first_index + i, ...).  Either way it is
+ * sanitised before use, and the sanitised record is what recs_out[i] receives.  Sanitising: the record becomes the identity
+ * {0, 1, 0, 0, 0, hw, hh} when an entry is not finite, or |k1| > 0.125, or z is outside [0.5, 2], or |ca_b| or |ca_r| exceeds
+ * 1 / 64, or vig is outside [0, 0.5], or |fl64(cx - hw)| > hw / 4, or |fl64(cy - hh)| > hh / 4.  reserved = 0.  No record
+ * makes the kernel touch memory outside a plane.
+ *
+ * Taps: ofdg_spatial's, word for word, from (qx, qy) - 24.8 fixed point Qx, Qy with the same clamps, "inside" (decided on the
+ * geometric map), the four clamped bilinear taps, the nearest tap.
+ *
+ * Frames: each channel is interpolated at its own zc position by ofdg_spatial's bilinear expression (exact on byte values);
+ * the result v is multiplied by the vignette of the DESTINATION pixel, gain = (float)fl64(1 - fl64(vig * rho)) - positive for
+ * every sanitised record, rho <= 1.5625 given the centre limit -: v' = fl32(v * gain).  float32 stores v' (a NaN as
+ * 0x7FC00000); uint8 stores rintf(v') clamped to [0, 255] (ties to even, a NaN becomes 0).  With vig == 0 the multiplication
+ * is left out, so the identity record moves bytes only.
+ *
+ * Flow, at destination pixel (X, Y) of frame 0: (u, v) is the source flow at the NEAREST tap of S, widened to float32.  The
+ * target is tx = fl64(qx + (double)u), ty likewise, (qx, qy) of S.  The new flow needs P with S(P) = t.  Write P = c + s (t -
+ * c): dtx = fl64(tx - cx), dty likewise, ru = fl64(fl64(fl64(dtx * dtx) + fl64(dty * dty)) * inv), and s solves
+ * z s (1 + k1 ru s^2) = 1.
+ *   k1 == 0:  s = fl64(1 / z), and the pixel counts as solved.
+ *   k1 != 0 and ru <= 16 does not hold (a NaN does not):  the pixel is UNSOLVABLE.
+ *   otherwise s = fl64(1 / z), then exactly 8 Newton steps
+ *       a = fl64(fl64(ru * s) * s)
+ *       g = fl64(fl64(fl64(z * s) * fl64(1 + fl64(k1 * a))) - 1)
+ *       d = fl64(z * fl64(1 + fl64(fl64(3 * k1) * a)))
+ *       s = fl64(s - fl64(g / d))
+ *   then a, g and D = fl64(1 + fl64(fl64(3 * k1) * a)) once more from the final s; solved when |g| <= 2^-30 && D >= 0.25 && s >
+ *   0, else unsolvable.
+ * Solved: px = fl64(cx + fl64(s * dtx)), py likewise; u' = (float)fl64(px - X), v' = (float)fl64(py - Y) (a NaN as
+ * 0x7FC00000); binary16 is rounded once after that.  Unsolvable: both components are the canonical NaN (0x7FC00000 / 0x7E00),
+ * which the statistics and the pyramid leave out.  flow1 is the same from its own plane, through the same S.
+ * Why this is well defined (checked in numpy over 2 10^6 random (k1, z, ru) of the ranges above): for k1 > 0 the function is
+ * convex and the start lies right of the root, for k1 < 0 it is concave and the start - the first Newton step from 0 - lies
+ * left of it, so the iteration is monotone; 6 steps decide every case as 60 do, 8 is the margin.  D >= 0.25 keeps away from
+ * the fold of the pincushion branch (a = 1 / (3 |k1|)); a solution with a <= 1 / (4 |k1|) exists for every target inside the
+ * destination frame: 2 at |k1| = 0.125, against at most 1.5625 for an in-frame pixel given the centre limit.
+ *
+ * Labels: the element at the nearest tap of S.
+ *
+ * Occlusion maps: the element becomes 1.0f / 1 when the source element at the nearest tap of S is non-zero (the crop's rule),
+ * or the pixel is not inside, or that frame's flow plane is given and the pixel is unsolvable, or - with
+ * OFDG_LENS_OCC_WINDOW - floor(fl64(px + 0.5)) lies outside [0, W - 1] or floor(fl64(py + 0.5)) outside [0, H - 1] (a NaN is
+ * outside).  Otherwise it becomes +0.0f / 0.  OFDG_LENS_OCC_WINDOW needs the flow plane, as the spatial flag does.
+ *
+ * Draw (ofdg_lens_draw; pure, no GPU): Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g,
+ * blocks j = 0, 1 at the counters {j, 0, 0x0c7a, 0} (0x0c70 .. 0x0c79 and 0x0fd9 are taken); u(w) and sym(w, a) are
+ * ofdg_photo's.
+ *   block 0:  on = u(.x) < prob   k1 = sym(.y, k1_range)   ca_b = sym(.z, ca_range)   ca_r = sym(.w, ca_range)
+ *   block 1:  vig = fl32(u(.x) * vig_max)   ox = sym(.y, centre)   oy = sym(.z, centre)
+ * The record widens each float to double; cx = fl64(hw + fl64((double)ox * hw)), cy likewise with oy and hh.  z with
+ * OFDG_LENS_FILL: rc = the largest rho (as above, about (cx, cy)) of the four frame corners, Lc = fl64(1 + fl64(k1 * rc)), z =
+ * Lc > 1 ? fl64(1 / Lc) : 1 - with it every destination pixel is inside: for k1 > 0 L grows with rho, so the farthest corner
+ * is the worst pixel; for k1 <= 0 sources move inward.  Without the flag z = 1.  When !on the record is the identity.  Ranges
+ * and their limits: prob in [0, 1], k1_range <= 0.125, ca_range <= 1 / 64, vig_max <= 0.5, centre <= 0.25, none negative or
+ * NaN; they are checked even when records are given.  All ranges 0, or prob = 0, give the identity.
+ *
+ * Identity: under the identity record every destination plane has the source's bytes and a flow keeps its bits - for every
+ * finite flow below 2^20 px, qx = X exactly, s = 1, and cx + (t - cx) is exact -; a NaN flow is stored as the canonical NaN.
+ *
+ * Asynchronous on `stream`, the stream the planes were written on; OFDG_STREAM_OWN as in ofdg_crop.  One kernel for any
+ * n_samples, all planes and both frames, no atomics; it reads no record of the context.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, only one of
+ * width / height 0, a size that breaks the rule above, unknown flag bits, non-zero reserved, another format code, a range
+ * outside its limits, no plane set, src[k] without dst[k] or the reverse, OFDG_LENS_OCC_WINDOW with occ0 but no flow (occ1 /
+ * flow1 likewise), a misaligned pointer (sources as the render calls ask: 16-byte float32, 8-byte binary16, 4-byte uint8;
+ * destinations and both record arrays 16-byte), a destination range (recs_out included) that overlaps any other range of the
+ * job, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: higher radial terms or tangential distortion, a lens per frame, longitudinal aberration, interpolated flow,
+ * mapping the object table's boxes, a changed output size, an in-place form, vignetting other than linear in rho.
+ */
+#define OFDG_LENS_FILL         1   /* job flag: the drawn z keeps every destination pixel inside */
+#define OFDG_LENS_OCC_WINDOW  16   /* job flag: see "occlusion maps" above                        */
+typedef struct ofdg_lens_rec {           /* 64 bytes */
+  double k1, z, ca_b, ca_r, vig, cx, cy;
+  int32_t reserved[2];
+} ofdg_lens_rec;
+struct ofdg_lens_job {                   /* 208 bytes */
+  const void* src[OFDG_CROP_PLANES];     /* [n,C,height,width], or NULL                */
+  void*       dst[OFDG_CROP_PLANES];     /* the same shape and element type            */
+  const ofdg_lens_rec* recs;             /* DEVICE, n records, or NULL: drawn          */
+  ofdg_lens_rec*       recs_out;         /* DEVICE, n records, or NULL                 */
+  long long first_index;  uint32_t seed;
+  int32_t width, height;                 /* 0, 0: the context's frame                  */
+  int32_t flags, image_fmt, flow_fmt, occ_fmt;
+  int32_t reserved;                      /* must be 0 */
+  float prob, k1_range, ca_range, vig_max, centre;        /* ranges of the draw: <= 1, 0.125, 1 / 64, 0.5, 0.25 */
+};
+int ofdg_lens(ofdg_ctx* ctx, const struct ofdg_lens_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition pixel by pixel: planes [n,C,height,width], records in host memory, no
+ * alignment asked of any pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above
+ * through ofdg_host_last_error. */
+int ofdg_host_lens(const struct ofdg_lens_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (the draw alone: not sanitised; pure, no GPU).  Of `ranges` the five ranges, flags,
+ * width and height are read; the size must be set.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer,
+ * a size that breaks the rule, unknown flag bits or a range ofdg_lens refuses. */
+int ofdg_lens_draw(uint32_t seed, long long index, const struct ofdg_lens_job* ranges, ofdg_lens_rec* out);
 
 /*
  * Flow visualisation: the Middlebury colour wheel (Baker et al., "A Database and Evaluation Methodology for Optical Flow") of

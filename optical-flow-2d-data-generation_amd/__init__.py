@@ -118,6 +118,7 @@ EXPORTS = [
     "ofdg_camera", "ofdg_host_camera", "ofdg_camera_draw", "ofdg_camera_taps",
     "ofdg_flow_vis", "ofdg_host_flow_vis", "ofdg_host_flow_vis_tables",
     "ofdg_flow_error", "ofdg_host_flow_error", "ofdg_host_flow_error_colours",
+    "ofdg_lens", "ofdg_host_lens", "ofdg_lens_draw",
 ]
 
 # the optional outputs (ofdg_extras, include/ofdg.h): name -> (channels or None for [n,H,W], dtype name)
@@ -679,6 +680,121 @@ def host_spatial(src, out_h, out_w, recs=None, first_index=0, seed=0, ranges=Non
     job = _spatial_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), out_h, out_w, None if recs is None else recs.ctypes.data,
                        used.ctypes.data, first_index, seed, ranges, _spatial_flags(hflip, vflip, occ_window))
     _host_check(lib().ofdg_host_spatial(C.byref(job), n, width, height))
+    return dst, used
+
+
+# the lens: radial distortion with exact flow, colour fringes, vignetting (ofdg_lens_rec / struct ofdg_lens_job / ofdg_lens,
+# include/ofdg.h)
+LENS_FILL, LENS_OCC_WINDOW = 1, 16
+LENS_RANGES = ("prob", "k1_range", "ca_range", "vig_max", "centre")
+# A mild lens: every other sample bent, up to 5 per cent at the corners (consumer lenses distort a few per cent), fringes of up
+# to 0.2 per cent of the radius, corners up to a quarter darker, the centre within 5 per cent of the half-size; fill=True
+# zooms a barrel lens in until no destination pixel looks outside the frame.  Not a tuned recipe.
+LENS_DEFAULT = dict(prob=0.5, k1_range=0.05, ca_range=0.002, vig_max=0.25, centre=0.05, fill=True)
+LENS_REC_DOUBLES = 8  # a record as float64 [8]: k1 z ca_b ca_r vig cx cy, then the 8 reserved bytes
+
+
+class LensRec(C.Structure):
+    """ofdg_lens_rec: the lens of one sample (64 bytes)."""
+    _fields_ = [(name, C.c_double) for name in ("k1", "z", "ca_b", "ca_r", "vig", "cx", "cy")] + [("reserved", C.c_int32 * 2)]
+
+
+class LensJob(C.Structure):
+    """struct ofdg_lens_job (208 bytes)."""
+    _fields_ = [("src", C.c_void_p * 8), ("dst", C.c_void_p * 8), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("flags", C.c_int32), ("image_fmt", C.c_int32), ("flow_fmt", C.c_int32), ("occ_fmt", C.c_int32),
+                ("reserved", C.c_int32)] + [(name, C.c_float) for name in LENS_RANGES]
+
+
+def lens_numpy(recs):
+    """Records of Generator.lens / host_lens - a torch tensor or numpy array of float64 [n,8] - as a numpy structured array [n]
+    with the fields k1, z, ca_b, ca_r, vig, cx, cy (float64) and reserved (int32 [2])."""
+    import numpy as np
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, LENS_REC_DOUBLES)
+    dtype = np.dtype([(name, "<f8") for name in ("k1", "z", "ca_b", "ca_r", "vig", "cx", "cy")] + [("reserved", "<i4", (2,))])
+    return a.view(dtype).reshape(-1)
+
+
+def _lens_ranges(job, ranges):
+    """The five ranges of a dict into job; "fill" may ride along (LENS_DEFAULT holds it) and is returned."""
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in LENS_RANGES and key != "fill":
+            raise ValueError("unknown range %r (known: %s, fill)" % (key, ", ".join(LENS_RANGES)))
+    for key in LENS_RANGES:
+        setattr(job, key, float(ranges.get(key, 0.0)))
+    return job, bool(ranges.get("fill", False))
+
+
+def _lens_flags(fill, occ_window):
+    return (LENS_FILL if fill else 0) | (LENS_OCC_WINDOW if occ_window else 0)
+
+
+def lens_format(src, dst, height, width):
+    """(n, image code, flow code, occ code) of the planes of Generator.lens / host_lens: src and dst are dicts keyed by
+    CROP_PLANES as crop_format takes them, both of the size height x width, a multiple of 8 wide and even high.  Raises
+    ValueError for anything else.  Looks at dtype and shape only (works on CPU tensors and numpy arrays)."""
+    n, out, codes = _plane_dicts(src, dst, height, width)
+    if out != (height, width):
+        raise ValueError("the lens keeps the size: dst must be %dx%d like src, got %dx%d" % (width, height, out[1], out[0]))
+    if width < 8 or width % 8 or height < 2 or height % 2:
+        raise ValueError("the planes must be a multiple of 8 wide and even high, got %dx%d" % (width, height))
+    return (n,) + codes
+
+
+def _lens_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges, fill, occ_window):
+    job, with_fill = _lens_ranges(LensJob(), ranges)
+    for k, key in enumerate(CROP_PLANES):
+        if key in src:
+            job.src[k], job.dst[k] = ptr(src[key]), ptr(dst[key])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.flags = _lens_flags(with_fill if fill is None else fill, occ_window)
+    job.image_fmt, job.flow_fmt, job.occ_fmt = codes
+    return job
+
+
+def lens_draw(seed, index, width, height, ranges=None, fill=None):
+    """ofdg_lens_draw (pure, no GPU): the record of global sample `index` under `seed` for width x height planes and a dict of
+    ranges (LENS_RANGES; a missing one is 0; LENS_DEFAULT for one), before sanitising, as float64 [8] (LENS_REC_DOUBLES: k1 z
+    ca_b ca_r vig cx cy, then the reserved bytes).  fill: OFDG_LENS_FILL; None: what ranges holds under "fill", else off."""
+    import numpy as np
+    job, with_fill = _lens_ranges(LensJob(), ranges)
+    job.width, job.height, job.flags = int(width), int(height), _lens_flags(with_fill if fill is None else fill, False)
+    out = LensRec()
+    _host_check(lib().ofdg_lens_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return np.frombuffer(bytearray(out), np.float64).copy()
+
+
+def alloc_lens(src, zero=True):
+    """The destination dict of Generator.lens for a source dict: every plane of src once more, same shape, dtype and device
+    (alloc_crop)."""
+    first = next(iter(src.values()))
+    return alloc_crop(src, first.shape[-2], first.shape[-1], zero)
+
+
+def host_lens(src, recs=None, first_index=0, seed=0, ranges=None, fill=None, occ_window=False):
+    """ofdg_host_lens (no GPU): the lens on HOST arrays - src a dict of numpy arrays keyed by CROP_PLANES, as Generator.lens takes
+    tensors; recs None (drawn from seed, first_index and ranges) or a float64 array [n,8].  Returns (dst, recs_used): the dict
+    of bent arrays and the float64 [n,8] records after sanitising."""
+    import numpy as np
+    src = {k: np.ascontiguousarray(v) for k, v in src.items()}
+    if not src:
+        raise ValueError("src must hold at least one of %s" % (CROP_PLANES,))
+    height, width = next(iter(src.values())).shape[-2:]
+    dst = alloc_lens(src)
+    n, *codes = lens_format(src, dst, height, width)
+    if recs is not None:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.float64 or recs.shape != (n, LENS_REC_DOUBLES):
+            raise ValueError("recs must be float64 [%d,%d], got %s %s" % (n, LENS_REC_DOUBLES, recs.dtype, recs.shape))
+    used = np.zeros((n, LENS_REC_DOUBLES), np.float64)
+    job = _lens_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                    first_index, seed, ranges, fill, occ_window)
+    _host_check(lib().ofdg_host_lens(C.byref(job), n, width, height))
     return dst, used
 
 
@@ -2354,6 +2470,9 @@ def lib():
         L.ofdg_host_camera.argtypes = [C.POINTER(CameraJob), i32, i32, i32]
         L.ofdg_camera_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(CameraJob), C.POINTER(CameraRec)]
         L.ofdg_camera_taps.argtypes = [i32, C.POINTER(C.c_uint32)]
+        L.ofdg_lens.argtypes = [vp, C.POINTER(LensJob), i32, vp]
+        L.ofdg_host_lens.argtypes = [C.POINTER(LensJob), i32, i32, i32]
+        L.ofdg_lens_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(LensJob), C.POINTER(LensRec)]
         L.ofdg_flow_vis.argtypes = [vp, C.POINTER(FlowVisJob), i32, vp]
         L.ofdg_host_flow_vis.argtypes = [C.POINTER(FlowVisJob), i32, i32, i32]
         L.ofdg_host_flow_vis_tables.argtypes = [vp, vp]
@@ -2763,6 +2882,28 @@ class Generator:
         job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, job_size, out_h, out_w, _optr(recs), _optr(recs_out), first_index,
                            self._seed(seed), ranges, _spatial_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_spatial(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
+
+    def lens(self, src, dst, recs=None, first_index=0, seed=None, ranges=None, fill=None, occ_window=False, recs_out=None, stream=0,
+             size=None):
+        """The lens on every plane of a batch in one launch (ofdg_lens, include/ofdg.h): each sample bent by a radial distortion
+        of its own about a centre of its own - one lens for both frames -, both flows carried through it exactly (a pixel whose
+        target has no pre-image becomes NaN and is marked in its map), B and R sampled at a slightly different magnification
+        than G, the frames darkened towards the corners.  src and dst are dicts keyed by CROP_PLANES (any subset), src[name]
+        the [n,C,H,W] tensor a render / forward call (or crop, spatial) wrote, dst[name] a tensor of the same shape and dtype
+        (alloc_lens).  recs: None - the record of sample i is lens_draw(seed, first_index + i, ...) - or a float64 device
+        tensor [n,8], taken as given; either is sanitised.  ranges: a dict of LENS_RANGES (a missing one is 0; LENS_DEFAULT is
+        a starting point).  fill: the drawn zoom keeps every destination pixel inside the frame; None: what ranges holds under
+        "fill", else off.  seed: default the context's.  occ_window: occ0 / occ1 also become 1 where the flow / flow1 target
+        leaves the frame.  recs_out: None or a float64 device tensor [n,8] that receives the records used (lens_numpy reads
+        it).  stream: the stream the planes were written on, or STREAM_OWN.  size=(height, width): planes of that size instead
+        of the context's frame.  Asynchronous; there is no in-place form.  Returns dst."""
+        height, width, job_size = self._job_size(size)
+        n, *codes = lens_format(src, dst, height, width)
+        self._check_recs(recs, recs_out, "float64", (n, LENS_REC_DOUBLES))
+        job = _lens_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
+                        ranges, fill, occ_window)
+        self._check(lib().ofdg_lens(self.h, C.byref(job), n, C.c_void_p(stream)))
         return dst
 
     def pack(self, src, dst, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0), flow_scale=1.0, layout=PACK_NCHW, concat=False, rgb=False,
@@ -3615,7 +3756,9 @@ class _RingSlot:
     __slots__ = ("outs",         # (image0, image1, flow): what forward writes ...
                  "extras",       # ... and its extras dict (None without extras=)
                  "frame",        # both by name: the source of the window
-                 "sharp",        # the planes the window writes, by name, or `frame` itself: what motion_blur= reads
+                 "window",       # the planes the window writes, by name, or `frame` itself: what lens= reads
+                 "lens",         # the records of lens=
+                 "sharp",        # the planes lens= writes, by name, or `window` itself: what motion_blur= reads
                  "planes",       # the planes every stage behind the blur works on, by name: `sharp`, with the blurred frames in place
                  "window_recs",  # the records of crop= / spatial=
                  "blur",         # the records of motion_blur=
@@ -3655,29 +3798,32 @@ class FlowLoader:
 
         1. forward          the frames, the flow and the extras=
         2. spatial= / crop= the window, into planes of its own: every later stage works on the window's planes and size
-        3. reproject=       of the window's sharp frames, flows and maps as they are then (un-blurred, un-erased), into planes
+        3. lens=            every plane of the window (or the frame) bent by the sample's lens, into planes of its own on the
+                            window's size: every later stage and the batch see the bent planes
+        4. reproject=       of the window's sharp frames, flows and maps as they are then (un-blurred, un-erased), into planes
                             and rows of its own
-        4. splat=           of the same sharp planes, and the label planes, pushed to an instant between the frames, into
+        5. splat=           of the same sharp planes, and the label planes, pushed to an instant between the frames, into
                             planes, keys and rows of its own
-        5. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
+        6. motion_blur=     of the window's frames along the window's flows, into frame buffers of its own, which take the
                             places of image0 / image1 for every later stage and in the batch
-        6. camera=          lens blur, Bayer mosaic and demosaic of the frames as they are then, into frame buffers of its own,
+        7. camera=          lens blur, Bayer mosaic and demosaic of the frames as they are then, into frame buffers of its own,
                             which take the places of image0 / image1 for every later stage and in the batch
-        7. photo=           in place, on both frames
-        8. jitter=          in place, on both frames
-        9. erase=           in place, on the frames and the occlusion maps
-        10. objects=True    the table, of the label planes of stage 1
-        11. stats=, pyramid= the reductions of flow and occ0
-        12. boundaries=     of the flows and label planes
-        13. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
-        14. pack=           of image0, image1 and flow, into tensors of its own
+        8. photo=           in place, on both frames
+        9. jitter=          in place, on both frames
+        10. erase=           in place, on the frames and the occlusion maps
+        11. objects=True    the table, of the label planes of stage 1
+        12. stats=, pyramid= the reductions of flow and occ0
+        13. boundaries=     of the flows and label planes
+        14. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
+        15. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the optics act behind the exposure and in front of the sensor noise, the
     photometric noise stays sharp on top of both as a sensor's does, the
     colour jitter and the eraser's mean fill see the augmented frame - the fill is the mean colour of the jittered frame, as in
     the RAFT recipe -, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (none of camera=, photo=, jitter= and erase= touches what they read).  The records of stages 2 and 4 to 9 are drawn from the
+    the un-erased sample (none of camera=, photo=, jitter= and erase= touches what they read); with lens= the blur follows the bent
+    flow and the reductions count the bent one.  The records of stages 2, 3 and 5 to 10 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -3694,6 +3840,11 @@ class FlowLoader:
     spatial_occ_window marks pixels whose target leaves the window in occ0 / occ1).  The loader yields the warped tensors and
     extras; the dict also holds "spatial" (float64 [n,14]: the maps of frame 0 and frame 1, a b c d e g each, then padding).
     Raises without spatial_size= and with crop=: the spatial step contains the window.
+    lens=dict(...) (the LENS_RANGES and, optionally, fill=; LENS_DEFAULT for one): every plane of the window - of the frame
+    without one - is bent by a lens per sample (Generator.lens) into planes of its own, directly behind spatial= / crop= and in
+    front of reproject=; OFDG_LENS_OCC_WINDOW is on when an occlusion map is among extras= ("occ1" then needs "flow1" there).
+    The dict also holds "lens" (float64 [n,8], the records used: lens_numpy).  An unknown key raises; raises with
+    objects=True: the table's boxes are of the unbent frame.
     motion_blur=dict(...) (the MBLUR_RANGES and, optionally, taps_side= and frames=; MBLUR_DEFAULT for one): the frames are
     blurred along their own flow (Generator.motion_blur) into a further ring of frame buffers, which the loader yields in the
     places of image0 / image1; flow, maps and labels stay those of the sharp frames.  frames=None: both frames when "flow1"
@@ -3755,7 +3906,7 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, splat=None, jitter=None, vis=None, camera=None, **kw):
+                 reproject=None, splat=None, jitter=None, vis=None, camera=None, lens=None, **kw):
         import torch
         self.vis = self._vis_options(vis, extras)
         self.boundaries = self._boundary_options(boundaries, extras)
@@ -3765,6 +3916,7 @@ class FlowLoader:
         self.splat = self._splat_options(splat, extras)
         self.jitter = self._jitter_options(jitter)
         self.camera = self._camera_options(camera)
+        self.lens = self._lens_options(lens, extras, objects)
         self.pack = None if pack is None else dict(pack)
         unknown = set(self.pack or ()) - {"image_dtype", "flow_dtype", "layout", "concat", "rgb", "scale", "bias", "flow_scale"}
         if unknown:
@@ -3826,6 +3978,11 @@ class FlowLoader:
                 t.planes = alloc_crop(t.frame, ph, pw, zero=False)
                 t.window_recs = torch.empty((n, 4), dtype=torch.int32, device="cuda")
                 crop_format(t.frame, t.planes, p.height, p.width)  # (raises for a window the frame does not allow)
+            t.window, t.lens = t.planes, None
+            if self.lens is not None:
+                t.planes = alloc_lens(t.window, zero=False)
+                t.lens = torch.empty((n, LENS_REC_DOUBLES), dtype=torch.float64, device="cuda")
+                lens_format(t.window, t.planes, ph, pw)
             t.sharp, t.blur = t.planes, None
             t.reproject = None
             if self.reproject is not None:
@@ -3955,6 +4112,19 @@ class FlowLoader:
         return dict(camera)
 
     @staticmethod
+    def _lens_options(lens, extras, objects):
+        """lens= split into (the dict with its ranges and fill, occ_window), or None; raises for what the loader cannot serve"""
+        if lens is None:
+            return None
+        _lens_ranges(LensJob(), lens)
+        if objects:
+            raise ValueError("objects=True does not combine with lens=: the table's boxes are of the unbent frame")
+        extras = tuple(extras or ())
+        if "occ1" in extras and "flow1" not in extras:
+            raise ValueError("lens= marks occ1 where the flow1 target leaves the frame: extras= must contain \"flow1\"")
+        return dict(lens), "occ0" in extras or "occ1" in extras
+
+    @staticmethod
     def _jitter_options(jitter):
         """jitter= as a dict of its own, or None; raises for a name that is no range"""
         if jitter is None:
@@ -4032,17 +4202,20 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None or self.lens is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
         if self.spatial is not None:
             hflip, vflip, occ_window = self.spatial_flags
-            g.spatial(t.frame, t.sharp, first_index=first, ranges=self.spatial, hflip=hflip, vflip=vflip, occ_window=occ_window,
+            g.spatial(t.frame, t.window, first_index=first, ranges=self.spatial, hflip=hflip, vflip=vflip, occ_window=occ_window,
                       recs_out=t.window_recs, stream=s)
         elif self.crop is not None:
-            g.crop(t.frame, t.sharp, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
+            g.crop(t.frame, t.window, first_index=first, hflip=self.crop_flips[0], vflip=self.crop_flips[1], occ_window=self.crop_occ_window,
                    recs_out=t.window_recs, stream=s)
+        if self.lens is not None:
+            ranges, occ_window = self.lens
+            g.lens(t.window, t.sharp, first_index=first, ranges=ranges, occ_window=occ_window, recs_out=t.lens, stream=s, size=size)
         if self.reproject is not None:
             frames, fb_thresh, _ = self.reproject
             g.reproject((t.sharp["image0"], t.sharp["image1"]), (t.sharp["flow"], t.sharp.get("flow1")), (t.sharp.get("occ0"), t.sharp.get("occ1")),
@@ -4100,6 +4273,8 @@ class FlowLoader:
         more = {k: v for k, v in t.planes.items() if k not in PACK_PLANES}
         if t.window_recs is not None:
             more["spatial" if self.spatial is not None else "crop"] = t.window_recs
+        if t.lens is not None:
+            more["lens"] = t.lens
         if t.reproject is not None:
             more.update(t.reproject[0])
             if t.reproject[1] is not None:

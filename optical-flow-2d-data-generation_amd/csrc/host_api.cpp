@@ -570,6 +570,114 @@ int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int wid
   return OFDG_OK;
 }
 
+// ofdg_lens on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the set-up,
+// the forward map, the inverse and the vignette are the functions the kernel runs (csrc/ofdg_device.h), the taps and the
+// blend the spatial augmentation's; elements are moved with memcpy, so no alignment is asked.
+int ofdg_lens_draw(uint32_t seed, long long index, const struct ofdg_lens_job* ranges, ofdg_lens_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_lens_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevLensJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  int W = 0, H = 0;
+  const char* why = j.width == 0 && j.height == 0 ? "width and height must be set" : lens_plane_size(j, &W, &H);
+  if (!why) why = lens_draw_error(j);
+  if (why) { g_host_error = std::string("ofdg_lens_draw: ") + why; return OFDG_EINVAL; }
+  const DevLensRec r = lens_draw_rec(seed, (unsigned long long)index, j, W, H);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_host_lens(const struct ofdg_lens_job* job, int n_samples, int width, int height) {
+  const DevLensJob* const j = reinterpret_cast<const DevLensJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why && (width > kSpatialMaxSide || height > kSpatialMaxSide)) why = "width and height must not exceed 2^20";
+  if (!why && (unsigned long long)width * (unsigned long long)height >= (1ull << 31)) why = "width * height must be below 2^31";
+  if (!why) why = lens_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_lens: ") + why; return OFDG_EINVAL; }
+  const int W = width, H = height;
+  const size_t frame = (size_t)W * H;
+  const bool occ_window = j->flags & OFDG_LENS_OCC_WINDOW;
+  const int ies = fmt_elem_bytes(j->image_fmt), fes = fmt_elem_bytes(j->flow_fmt), oes = fmt_elem_bytes(j->occ_fmt);
+  for (int i = 0; i < n_samples; ++i) {
+    DevLensRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = lens_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j, W, H);
+    r = lens_sanitise(r, W, H);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    const LensSetup o = lens_setup(r, W, H);
+    for (int f = 0; f < 2; ++f) {
+      const void* const s_img = j->src[OFDG_CROP_IMAGE0 + f];
+      const void* const s_flow = j->src[OFDG_CROP_FLOW + f];
+      const void* const s_occ = j->src[OFDG_CROP_OCC0 + f];
+      const void* const s_lab = j->src[OFDG_CROP_LABEL0 + f];
+      uint8_t* const d_img = static_cast<uint8_t*>(j->dst[OFDG_CROP_IMAGE0 + f]);
+      uint8_t* const d_flow = static_cast<uint8_t*>(j->dst[OFDG_CROP_FLOW + f]);
+      uint8_t* const d_occ = static_cast<uint8_t*>(j->dst[OFDG_CROP_OCC0 + f]);
+      uint8_t* const d_lab = static_cast<uint8_t*>(j->dst[OFDG_CROP_LABEL0 + f]);
+      if (!s_img && !s_flow && !s_occ && !s_lab) continue;
+      const SpatialElems img{static_cast<const uint8_t*>(s_img), ies, false};
+      const SpatialElems flow{static_cast<const uint8_t*>(s_flow), fes, fes == 2};
+      for (int Y = 0; Y < H; ++Y) {
+        const double dy = (double)Y - o.cy;
+        for (int X = 0; X < W; ++X) {
+          const double dx = (double)X - o.cx;
+          const double rho = lens_rho(dx, dy, o.inv);
+          const double L = lens_L(o.k1, rho);
+          const double qx = lens_coord(o.cx, o.z, L, dx), qy = lens_coord(o.cy, o.z, L, dy);
+          const int Qx = spatial_fixed(qx), Qy = spatial_fixed(qy);
+          const size_t to = (size_t)Y * W + X;
+          const size_t near = (size_t)spatial_clamp((Qy + 128) >> 8, H) * W + spatial_clamp((Qx + 128) >> 8, W);
+          if (s_img) {
+            const float gain = lens_gain(o.vig, rho);
+            for (int c = 0; c < 3; ++c) {
+              const double zc = lens_channel_z(o, c);
+              const int Cx = spatial_fixed(lens_coord(o.cx, zc, L, dx)), Cy = spatial_fixed(lens_coord(o.cy, zc, L, dy));
+              const int fx = Cx & 255, fy = Cy & 255;
+              const size_t x0 = spatial_clamp(Cx >> 8, W), x1 = spatial_clamp((Cx >> 8) + 1, W);
+              const size_t y0 = (size_t)spatial_clamp(Cy >> 8, H) * W, y1 = (size_t)spatial_clamp((Cy >> 8) + 1, H) * W;
+              const size_t base = ((size_t)i * 3 + c) * frame;
+              float v = spatial_blend(img.at(base + y0 + x0), img.at(base + y0 + x1), img.at(base + y1 + x0), img.at(base + y1 + x1), fx, fy);
+              if (o.vig != 0.0) v = spatial_quiet(v * gain);
+              uint8_t* const d = d_img + (base + to) * ies;
+              if (ies == 4) std::memcpy(d, &v, 4);
+              else *d = (uint8_t)spatial_to_byte(v);
+            }
+          }
+          double px = 0.0, py = 0.0;
+          bool solved = true;
+          if (s_flow) {
+            const float u = flow.at((size_t)i * 2 * frame + near), v = flow.at(((size_t)i * 2 + 1) * frame + near);
+            const double tx = qx + (double)u, ty = qy + (double)v;
+            solved = lens_inverse(o, tx, ty, &px, &py);
+            const float ou = solved ? spatial_flow_of(px, X) : lens_nan(), ov = solved ? spatial_flow_of(py, Y) : lens_nan();
+            uint8_t* const o0 = d_flow + ((size_t)i * 2 * frame + to) * fes;
+            uint8_t* const o1 = d_flow + (((size_t)i * 2 + 1) * frame + to) * fes;
+            if (fes == 4) {
+              std::memcpy(o0, &ou, 4);
+              std::memcpy(o1, &ov, 4);
+            } else {
+              const uint16_t hu = (uint16_t)spatial_half_bits(ou), hv = (uint16_t)spatial_half_bits(ov);
+              std::memcpy(o0, &hu, 2);
+              std::memcpy(o1, &hv, 2);
+            }
+          }
+          if (s_occ) {
+            bool hidden = OccPlane{static_cast<const uint8_t*>(s_occ) + ((size_t)i * frame + near) * oes, j->occ_fmt}.at(0);
+            hidden = hidden || !spatial_inside(Qx, Qy, W, H) || !solved;
+            if (occ_window) hidden = hidden || !(spatial_partner_inside(px, W) && spatial_partner_inside(py, H));
+            uint8_t* const d = d_occ + ((size_t)i * frame + to) * oes;
+            const float one = hidden ? 1.0f : 0.0f;
+            if (oes == 4) std::memcpy(d, &one, 4);
+            else *d = hidden ? 1 : 0;
+          }
+          if (s_lab) d_lab[(size_t)i * frame + to] = static_cast<const uint8_t*>(s_lab)[(size_t)i * frame + near];
+        }
+      }
+    }
+  }
+  return OFDG_OK;
+}
+
 // ofdg_pack on host arrays (no GPU): the definition of include/ofdg.h element by element.  The value, the roundings, the
 // placement and the argument rules are the functions the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy,
 // so no alignment is asked.

@@ -5916,4 +5916,169 @@ __global__ __launch_bounds__(kCameraThreads) void camera_kernel(const DevCameraJ
   }
 }
 
+// --------------------------------------------------------------------------
+// Lens (ofdg_lens): every plane of a batch bent by one radial distortion per sample - the spatial augmentation's gather with
+// another map, a Newton inverse for the flow, a magnification per colour channel and a vignette.  The functions of the
+// definition are the host twin's (csrc/ofdg_device.h), so the result is the twin's bit for bit.
+// --------------------------------------------------------------------------
+// The walk is spatial_kernel's, with the output of the source's size: four neighbouring lanes own a unit of 16 elements, a
+// lane four consecutive pixels, a workgroup a tile of kSpatialTileQ units x kSpatialTileP row pairs; blockIdx.x counts the
+// tiles, blockIdx.y the samples, blockIdx.z the frames that have a plane.  The record is drawn or read, sanitised and turned
+// into the sample's constants (inv, both other magnifications, 1 / z, 3 k1) on uniform values once per (workgroup, sample);
+// rho, L, the geometric taps and the vignette of a pixel are computed once and serve the three channels, the flow, the map
+// and the label.  G is always sampled at the geometric position, B and R too where their aberration is 0 (a uniform branch).
+// The inverse - eight Newton steps, each with an fp64 division - is the only long fp64 chain, one per pixel of a frame that
+// has a flow.  Sources are read element by element at computed, clamped indices, so no record reaches outside a plane; every
+// store is one 16-byte piece.  No LDS, no atomics, no scratch.
+template <bool kImageU8, bool kFlowHalf, bool kOccU8>
+__global__ __launch_bounds__(kSpatialThreads) void lens_kernel(const DevLensJob job, int n, int W, int H, uint32_t tiles_x) {
+  constexpr int kImageES = kImageU8 ? 1 : 4, kFlowES = kFlowHalf ? 2 : 4, kOccES = kOccU8 ? 1 : 4;
+  const uint32_t R = (uint32_t)W / 8u, pairs = (uint32_t)H / 2u;  // units per row pair, row pairs
+  const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const uint32_t j = threadIdx.x & 3u, u = threadIdx.x >> 2;  // the lane's four pixels of its unit; the unit of the pass
+  const uint32_t q = tx * kSpatialTileQ + u % kSpatialTileQ, P0 = ty * kSpatialTileP + u / kSpatialTileQ;
+  const uint32_t t = 2u * q + (j >> 1);  // the run of 8 among the 2 R runs of a row pair
+  const bool second = t >= R;
+  const int X0 = (int)((t - (second ? R : 0u)) * 8u + (j & 1u) * 4u);
+  const bool frame0 = job.src[0] || job.src[2] || job.src[4] || job.src[6];
+  const int f = (blockIdx.z != 0u || !frame0) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.src[1] : job.src[0]);
+  const uint8_t* const s_flow = static_cast<const uint8_t*>(f ? job.src[3] : job.src[2]);
+  const uint8_t* const s_occ = static_cast<const uint8_t*>(f ? job.src[5] : job.src[4]);
+  const uint8_t* const s_lab = static_cast<const uint8_t*>(f ? job.src[7] : job.src[6]);
+  uint8_t* const d_img = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+  uint8_t* const d_flow = static_cast<uint8_t*>(f ? job.dst[3] : job.dst[2]);
+  uint8_t* const d_occ = static_cast<uint8_t*>(f ? job.dst[5] : job.dst[4]);
+  uint8_t* const d_lab = static_cast<uint8_t*>(f ? job.dst[7] : job.dst[6]);
+  const bool occ_window = job.flags & 16;
+  const size_t frame = (size_t)W * H;
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    DevLensRec r;
+    if (job.recs) r = job.recs[i];
+    else r = lens_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job, W, H);
+    r = lens_sanitise(r, W, H);
+    if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u) {
+      double2* const o = reinterpret_cast<double2*>(job.recs_out + i);
+      o[0] = make_double2(r.k1, r.z); o[1] = make_double2(r.ca_b, r.ca_r); o[2] = make_double2(r.vig, r.cx);
+      o[3] = make_double2(r.cy, 0.0);  // (the reserved words are the bits of +0.0)
+    }
+    if (q >= R) continue;  // (a whole unit, its four lanes together)
+    const LensSetup o = lens_setup(r, W, H);
+    const bool vignette = o.vig != 0.0;
+    const uint8_t* const si = s_img + (size_t)i * 3 * frame * kImageES;
+    const uint8_t* const sf = s_flow + (size_t)i * 2 * frame * kFlowES;
+    const uint8_t* const so = s_occ + (size_t)i * frame * kOccES;
+    const uint8_t* const sl = s_lab + (size_t)i * frame;
+#pragma unroll 1
+    for (int pass = 0; pass < kSpatialPasses; ++pass) {
+      const uint32_t P = P0 + (uint32_t)pass * kSpatialRowPairs;
+      if (P >= pairs) break;  // (whole units again)
+      const int Y = (int)(2u * P + (second ? 1u : 0u));
+      const size_t at = ((size_t)P * R + q) * 16u + 4u * j;  // the lane's first element in a channel of the destination
+      const double dy = (double)Y - o.cy;
+      float img[3][4], fu[4], fv[4];
+      uint32_t hid[4], lab[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int X = X0 + p;
+        const double dx = (double)X - o.cx;
+        const double rho = lens_rho(dx, dy, o.inv);
+        const double L = lens_L(o.k1, rho);
+        const double qx = lens_coord(o.cx, o.z, L, dx), qy = lens_coord(o.cy, o.z, L, dy);
+        const int Qx = spatial_fixed(qx), Qy = spatial_fixed(qy);
+        const uint32_t near = (uint32_t)spatial_clamp((Qy + 128) >> 8, H) * (uint32_t)W + (uint32_t)spatial_clamp((Qx + 128) >> 8, W);
+        if (s_img) {
+          const float gain = lens_gain(o.vig, rho);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const double zc = lens_channel_z(o, c);
+            int Cx = Qx, Cy = Qy;
+            if (zc != o.z) {  // (uniform: the sample's)
+              Cx = spatial_fixed(lens_coord(o.cx, zc, L, dx));
+              Cy = spatial_fixed(lens_coord(o.cy, zc, L, dy));
+            }
+            const int fx = Cx & 255, fy = Cy & 255;
+            const uint32_t x0 = (uint32_t)spatial_clamp(Cx >> 8, W), x1 = (uint32_t)spatial_clamp((Cx >> 8) + 1, W);
+            const uint32_t y0 = (uint32_t)spatial_clamp(Cy >> 8, H) * (uint32_t)W, y1 = (uint32_t)spatial_clamp((Cy >> 8) + 1, H) * (uint32_t)W;
+            float e00, e10, e01, e11;
+            if constexpr (kImageU8) {
+              const uint8_t* const pc = si + (size_t)c * frame;
+              e00 = (float)pc[y0 + x0]; e10 = (float)pc[y0 + x1]; e01 = (float)pc[y1 + x0]; e11 = (float)pc[y1 + x1];
+            } else {
+              const uint8_t* const pc = si + (size_t)c * frame * 4u;
+              e00 = elem_load<OFDG_FMT_F32>(pc, y0 + x0); e10 = elem_load<OFDG_FMT_F32>(pc, y0 + x1);
+              e01 = elem_load<OFDG_FMT_F32>(pc, y1 + x0); e11 = elem_load<OFDG_FMT_F32>(pc, y1 + x1);
+            }
+            float v = spatial_blend(e00, e10, e01, e11, fx, fy);
+            if (vignette) v = spatial_quiet(v * gain);
+            img[c][p] = v;
+          }
+        }
+        double px = 0.0, py = 0.0;
+        bool solved = true;
+        if (s_flow) {
+          const float su = elem_load<quad_fmt(kFlowHalf)>(sf, near), sv = elem_load<quad_fmt(kFlowHalf)>(sf, frame + near);
+          const double tx_ = qx + (double)su, ty_ = qy + (double)sv;
+          solved = lens_inverse(o, tx_, ty_, &px, &py);
+          fu[p] = solved ? spatial_flow_of(px, X) : lens_nan();
+          fv[p] = solved ? spatial_flow_of(py, Y) : lens_nan();
+        }
+        if (s_occ) {
+          bool hidden;
+          if constexpr (kOccU8) hidden = so[near] != 0;
+          else hidden = elem_load<OFDG_FMT_F32>(so, near) != 0.0f;
+          hidden = hidden || !spatial_inside(Qx, Qy, W, H) || !solved;
+          if (occ_window) hidden = hidden || !(spatial_partner_inside(px, W) && spatial_partner_inside(py, H));
+          hid[p] = hidden ? 1u : 0u;
+        }
+        if (s_lab) lab[p] = sl[near];
+      }
+      // (the lanes of a unit are all here: q and P are the unit's)
+      if (s_img) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (kImageU8) {
+            const uint32_t b[4] = {spatial_to_byte(img[c][0]), spatial_to_byte(img[c][1]), spatial_to_byte(img[c][2]), spatial_to_byte(img[c][3])};
+            const uint32_t w = quad_word(b);
+            const u32x4 v = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+            if (j == 0u) spatial_store(d_img + ((size_t)i * 3 + c) * frame + at, v);
+          } else {
+            const u32x4 v = {__float_as_uint(img[c][0]), __float_as_uint(img[c][1]), __float_as_uint(img[c][2]), __float_as_uint(img[c][3])};
+            spatial_store(d_img + (((size_t)i * 3 + c) * frame + at) * 4u, v);
+          }
+        }
+      }
+      if (s_flow) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const float* const v = c ? fv : fu;
+          if constexpr (kFlowHalf) {
+            const uint32_t w0 = spatial_half_bits(v[0]) | (spatial_half_bits(v[1]) << 16), w1 = spatial_half_bits(v[2]) | (spatial_half_bits(v[3]) << 16);
+            const u32x4 w = {w0, w1, (uint32_t)__shfl_down((int)w0, 1), (uint32_t)__shfl_down((int)w1, 1)};
+            if ((j & 1u) == 0u) spatial_store(d_flow + (((size_t)i * 2 + c) * frame + at) * 2u, w);
+          } else {
+            const u32x4 w = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+            spatial_store(d_flow + (((size_t)i * 2 + c) * frame + at) * 4u, w);
+          }
+        }
+      }
+      if (s_occ) {
+        if constexpr (kOccU8) {
+          const uint32_t w = quad_word(hid);
+          const u32x4 v = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+          if (j == 0u) spatial_store(d_occ + (size_t)i * frame + at, v);
+        } else {
+          const u32x4 v = {hid[0] ? 0x3f800000u : 0u, hid[1] ? 0x3f800000u : 0u, hid[2] ? 0x3f800000u : 0u, hid[3] ? 0x3f800000u : 0u};
+          spatial_store(d_occ + ((size_t)i * frame + at) * 4u, v);
+        }
+      }
+      if (s_lab) {
+        const uint32_t w = quad_word(lab);
+        const u32x4 v = {w, (uint32_t)__shfl_down((int)w, 1), (uint32_t)__shfl_down((int)w, 2), (uint32_t)__shfl_down((int)w, 3)};
+        if (j == 0u) spatial_store(d_lab + (size_t)i * frame + at, v);
+      }
+    }
+  }
+}
+
 }  // namespace ofdg

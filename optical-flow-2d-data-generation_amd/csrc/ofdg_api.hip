@@ -272,7 +272,7 @@ static std::string err_text(uint32_t e) {
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
 // ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_camera, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
-// ofdg_flow_error
+// ofdg_flow_error, ofdg_lens
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -294,7 +294,7 @@ struct PostOp {
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
 // 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel,
-// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel, 4 camera_kernel.
+// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel, 4 camera_kernel, 8 lens_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -2129,6 +2129,42 @@ int ofdg_flow_error(ofdg_ctx* c, const struct ofdg_flow_error_job* job, int n_sa
       with_bool(j->epe || j->picture, [&](auto planes) {
         hipLaunchKernelGGL((flow_error_kernel<decltype(half)::value, decltype(est)::value, decltype(planes)::value>), g, dim3(kErrThreads), 0, st, *j,
                            n_samples, plane);
+      });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// The lens on caller-given planes: one kernel on `stream` for every plane, both frames and every sample.
+int ofdg_lens(ofdg_ctx* c, const struct ofdg_lens_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_lens"};
+  const DevLensJob* const j = reinterpret_cast<const DevLensJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = lens_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = lens_arg_error(j, n_samples, W, H)) return op.fail(why);
+  static const char* const kPlane[kCropPlanes] = {"image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1"};
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const int fmt = k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8;
+    OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const bool frame0 = j->src[0] || j->src[2] || j->src[4] || j->src[6], frame1 = j->src[1] || j->src[3] || j->src[5] || j->src[7];
+  const uint32_t tiles_x = ((uint32_t)W / 8u + kSpatialTileQ - 1) / kSpatialTileQ;
+  const uint32_t tiles_y = ((uint32_t)H / 2u + kSpatialTileP - 1) / kSpatialTileP;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), (frame0 ? 1u : 0u) + (frame1 ? 1u : 0u));
+  with_bool(j->image_fmt == OFDG_FMT_U8, [&](auto image_u8) {
+    with_bool(j->flow_fmt == OFDG_FMT_F16, [&](auto flow_half) {
+      with_bool(j->occ_fmt == OFDG_FMT_U8, [&](auto occ_u8) {
+        hipLaunchKernelGGL((lens_kernel<decltype(image_u8)::value, decltype(flow_half)::value, decltype(occ_u8)::value>), g, dim3(kSpatialThreads), 0,
+                           st, *j, n_samples, W, H, tiles_x);
       });
     });
   });

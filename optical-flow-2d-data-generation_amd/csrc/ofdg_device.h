@@ -1537,6 +1537,219 @@ inline const char* camera_arg_error(const DevCameraJob* j, int n, int width, int
   return nullptr;
 }
 
+// ---- Lens (ofdg_lens, include/ofdg.h) --------------------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the per-sample set-up, the forward map, the 8-step inverse with its verdict, the vignette and the argument
+// rules.  The taps, the blend and the stores are the spatial augmentation's above.  Compiled without contraction, so every
+// operation below is its own rounding.
+struct DevLensRec {  // ofdg_lens_rec, field for field
+  double k1, z, ca_b, ca_r, vig, cx, cy;
+  int32_t reserved[2];
+};
+struct DevLensJob {  // struct ofdg_lens_job, field for field
+  const void* src[kCropPlanes];
+  void* dst[kCropPlanes];
+  const DevLensRec* recs;
+  DevLensRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, flags, image_fmt, flow_fmt, occ_fmt, reserved;
+  float prob, k1_range, ca_range, vig_max, centre;
+};
+static_assert(sizeof(ofdg_lens_rec) == sizeof(DevLensRec) && sizeof(DevLensRec) == 64 && offsetof(ofdg_lens_rec, cy) == offsetof(DevLensRec, cy) &&
+              offsetof(DevLensRec, cy) == 48 && offsetof(ofdg_lens_rec, reserved) == offsetof(DevLensRec, reserved) && offsetof(DevLensRec, reserved) == 56,
+              "ofdg_lens_rec: 64 bytes without padding, the layout the kernel reads and writes");
+static_assert(sizeof(struct ofdg_lens_job) == sizeof(DevLensJob) && sizeof(DevLensJob) == 208 && offsetof(struct ofdg_lens_job, dst) == offsetof(DevLensJob, dst) &&
+              offsetof(struct ofdg_lens_job, recs) == offsetof(DevLensJob, recs) && offsetof(struct ofdg_lens_job, recs_out) == offsetof(DevLensJob, recs_out) &&
+              offsetof(struct ofdg_lens_job, first_index) == offsetof(DevLensJob, first_index) && offsetof(struct ofdg_lens_job, seed) == offsetof(DevLensJob, seed) &&
+              offsetof(struct ofdg_lens_job, width) == offsetof(DevLensJob, width) && offsetof(struct ofdg_lens_job, flags) == offsetof(DevLensJob, flags) &&
+              offsetof(struct ofdg_lens_job, occ_fmt) == offsetof(DevLensJob, occ_fmt) && offsetof(struct ofdg_lens_job, reserved) == offsetof(DevLensJob, reserved) &&
+              offsetof(DevLensJob, reserved) == 180 && offsetof(struct ofdg_lens_job, prob) == offsetof(DevLensJob, prob) &&
+              offsetof(struct ofdg_lens_job, centre) == offsetof(DevLensJob, centre) && offsetof(DevLensJob, centre) == 200,
+              "struct ofdg_lens_job: 208 bytes, the layout the kernel takes");
+static_assert(OFDG_LENS_FILL == 1 && OFDG_LENS_OCC_WINDOW == 16, "lens_draw_rec and lens_kernel spell these codes out");
+OFDG_HD_FN DevLensRec lens_identity(int W, int H) {
+  DevLensRec r;
+  r.k1 = 0.0; r.z = 1.0; r.ca_b = 0.0; r.ca_r = 0.0; r.vig = 0.0;
+  r.cx = (double)(W - 1) / 2.0; r.cy = (double)(H - 1) / 2.0;
+  r.reserved[0] = 0; r.reserved[1] = 0;
+  return r;
+}
+// one over the squared half-diagonal of a W x H plane
+OFDG_HD_FN double lens_inv_diag2(int W, int H) {
+  const double hw = (double)(W - 1) / 2.0, hh = (double)(H - 1) / 2.0;
+  const double a = hw * hw, b = hh * hh;
+  const double s = a + b;
+  return 1.0 / s;
+}
+// rho of an offset (dx, dy) from the centre: the squared radius over the squared half-diagonal
+OFDG_HD_FN double lens_rho(double dx, double dy, double inv) {
+  const double a = dx * dx, b = dy * dy;
+  const double s = a + b;
+  return s * inv;
+}
+OFDG_HD_FN double lens_L(double k1, double rho) {
+  const double t = k1 * rho;
+  return 1.0 + t;
+}
+// one coordinate of the source position under magnification m: c + (m * L) * d
+OFDG_HD_FN double lens_coord(double c, double m, double L, double d) {
+  const double ml = m * L;
+  const double t = ml * d;
+  return c + t;
+}
+// The record of global sample g for a W x H plane: Philox blocks 0, 1 under the sampler's key of g at the counters {j, 0, 0x0c7a,
+// 0}.  `j` supplies the five ranges and the flags.  Not sanitised.
+OFDG_HD_FN DevLensRec lens_draw_rec(uint32_t seed, unsigned long long g, const DevLensJob& j, int W, int H) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords w0 = crop_philox(CropWords{0u, 0u, 0x0c7au, 0u}, k0, k1);
+  const CropWords w1 = crop_philox(CropWords{1u, 0u, 0x0c7au, 0u}, k0, k1);
+  DevLensRec r = lens_identity(W, H);
+  if (!(photo_unit(w0.x) < j.prob)) return r;
+  const float fk = photo_sym(w0.y, j.k1_range), fb = photo_sym(w0.z, j.ca_range), fr = photo_sym(w0.w, j.ca_range);
+  const float fv = photo_unit(w1.x) * j.vig_max;
+  const float ox = photo_sym(w1.y, j.centre), oy = photo_sym(w1.z, j.centre);
+  const double hw = r.cx, hh = r.cy;
+  r.k1 = (double)fk; r.ca_b = (double)fb; r.ca_r = (double)fr; r.vig = (double)fv;
+  const double sx = (double)ox * hw, sy = (double)oy * hh;
+  r.cx = hw + sx; r.cy = hh + sy;
+  if (j.flags & 1) {  // OFDG_LENS_FILL: the farthest corner's L, when above 1, is undone
+    const double inv = lens_inv_diag2(W, H);
+    const double x0 = 0.0 - r.cx, x1 = (double)(W - 1) - r.cx, y0 = 0.0 - r.cy, y1 = (double)(H - 1) - r.cy;
+    double rc = lens_rho(x0, y0, inv);
+    const double r1 = lens_rho(x1, y0, inv), r2 = lens_rho(x0, y1, inv), r3 = lens_rho(x1, y1, inv);
+    rc = r1 > rc ? r1 : rc; rc = r2 > rc ? r2 : rc; rc = r3 > rc ? r3 : rc;
+    const double Lc = lens_L(r.k1, rc);
+    r.z = Lc > 1.0 ? 1.0 / Lc : 1.0;
+  }
+  return r;
+}
+// What is used of a record, given or drawn: one that is not finite or out of its bounds becomes the identity.  (A comparison
+// with a NaN fails, so a NaN fails its bound; every entry has one.)
+OFDG_HD_FN DevLensRec lens_sanitise(DevLensRec r, int W, int H) {
+  const double hw = (double)(W - 1) / 2.0, hh = (double)(H - 1) / 2.0;
+  bool ok = spatial_abs(r.k1) <= 0.125 && r.z >= 0.5 && r.z <= 2.0 && spatial_abs(r.ca_b) <= 0.015625 && spatial_abs(r.ca_r) <= 0.015625;
+  ok = ok && r.vig >= 0.0 && r.vig <= 0.5 && spatial_abs(r.cx - hw) <= hw / 4.0 && spatial_abs(r.cy - hh) <= hh / 4.0;
+  if (!ok) return lens_identity(W, H);
+  r.reserved[0] = 0; r.reserved[1] = 0;
+  return r;
+}
+// What a sample's pixels share, made once from its sanitised record
+struct LensSetup {
+  double k1, k3, z, iz, zb, zr, vig, cx, cy, inv;  // k3 = 3 k1, iz = 1 / z, zb / zr: the magnification of B / R (G's is z)
+};
+OFDG_HD_FN LensSetup lens_setup(const DevLensRec& r, int W, int H) {
+  LensSetup s;
+  s.k1 = r.k1; s.k3 = 3.0 * r.k1; s.z = r.z; s.iz = 1.0 / r.z;
+  const double b = 1.0 + r.ca_b, c = 1.0 + r.ca_r;
+  s.zb = r.z * b; s.zr = r.z * c;
+  s.vig = r.vig; s.cx = r.cx; s.cy = r.cy;
+  s.inv = lens_inv_diag2(W, H);
+  return s;
+}
+OFDG_HD_FN double lens_channel_z(const LensSetup& s, int c) { return c == 0 ? s.zb : c == 2 ? s.zr : s.z; }
+// the vignette of a destination pixel
+OFDG_HD_FN float lens_gain(double vig, double rho) {
+  const double t = vig * rho;
+  return (float)(1.0 - t);
+}
+// a, g and the bracket of the derivative at s: g = z s (1 + k1 a) - 1 with a = ru s^2, D = 1 + 3 k1 a
+OFDG_HD_FN void lens_residual(const LensSetup& o, double ru, double s, double* g, double* D) {
+  const double rs = ru * s;
+  const double a = rs * s;
+  const double zs = o.z * s;
+  const double ka = o.k1 * a;
+  const double b = 1.0 + ka;
+  const double p = zs * b;
+  *g = p - 1.0;
+  const double k3a = o.k3 * a;
+  *D = 1.0 + k3a;
+}
+// P with S(P) = (tx, ty): eight Newton steps for s in P = c + s (t - c), then the verdict.  false: unsolvable.
+OFDG_HD_FN bool lens_inverse(const LensSetup& o, double tx, double ty, double* px, double* py) {
+  const double dtx = tx - o.cx, dty = ty - o.cy;
+  double s = o.iz;
+  bool solved = true;
+  if (o.k1 != 0.0) {
+    const double ru = lens_rho(dtx, dty, o.inv);
+    if (!(ru <= 16.0)) return false;
+    double g, D;
+    for (int k = 0; k < 8; ++k) {
+      lens_residual(o, ru, s, &g, &D);
+      const double d = o.z * D;
+      const double q = g / d;
+      s = s - q;
+    }
+    lens_residual(o, ru, s, &g, &D);
+    solved = spatial_abs(g) <= 9.31322574615478515625e-10 && D >= 0.25 && s > 0.0;
+  }
+  const double ax = s * dtx, ay = s * dty;
+  *px = o.cx + ax;
+  *py = o.cy + ay;
+  return solved;
+}
+OFDG_HD_FN float lens_nan() {  // 0x7FC00000: what an unsolvable pixel's flow holds
+  const uint32_t bits = 0x7FC00000u;
+  float nan;
+  memcpy(&nan, &bits, 4);
+  return nan;
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* lens_plane_size(const DevLensJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  if (const char* why = plane_size_error(*width, *height)) return why;
+  if (*width > kSpatialMaxSide || *height > kSpatialMaxSide) return "width and height must not exceed 2^20";
+  if ((unsigned long long)*width * (unsigned long long)*height >= (1ull << 31)) return "width * height must be below 2^31";
+  return nullptr;
+}
+// What the draw reads of a job besides the size: the flags and the five ranges.
+inline const char* lens_draw_error(const DevLensJob& j) {
+  if (j.flags & ~(OFDG_LENS_FILL | OFDG_LENS_OCC_WINDOW)) return "flags holds unknown bits";
+  if (!(j.prob >= 0.0f && j.prob <= 1.0f)) return "prob must lie in [0, 1]";
+  if (!(j.k1_range >= 0.0f && j.k1_range <= 0.125f)) return "k1_range must lie in [0, 0.125]";
+  if (!(j.ca_range >= 0.0f && j.ca_range <= 0.015625f)) return "ca_range must lie in [0, 1/64]";
+  if (!(j.vig_max >= 0.0f && j.vig_max <= 0.5f)) return "vig_max must lie in [0, 0.5]";
+  if (!(j.centre >= 0.0f && j.centre <= 0.25f)) return "centre must lie in [0, 0.25]";
+  return nullptr;
+}
+// The argument rules ofdg_lens and ofdg_host_lens share: the first rule broken, or nullptr.  width, height: what
+// lens_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* lens_arg_error(const DevLensJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (const char* why = lens_draw_error(*j)) return why;
+  if (j->reserved != 0) return "reserved must be 0";
+  if (j->image_fmt != OFDG_FMT_F32 && j->image_fmt != OFDG_FMT_U8) return "image_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = flow_occ_fmt_error(j->flow_fmt, true, j->occ_fmt)) return why;
+  int planes = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (j->src[k] && !j->dst[k]) return "dst: a plane has a source and no destination";
+    if (!j->src[k] && j->dst[k]) return "src: a plane has a destination and no source";
+    planes += j->src[k] ? 1 : 0;
+  }
+  if (!planes) return "src: no plane is set";
+  if ((j->flags & OFDG_LENS_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_LENS_OCC_WINDOW with occ0 needs flow";
+  if ((j->flags & OFDG_LENS_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_LENS_OCC_WINDOW with occ1 needs flow1";
+  // no in-place form: a destination range may meet no other range of the job
+  struct Range { uintptr_t lo, hi; bool dst; };
+  Range r[2 * kCropPlanes + 2];
+  int nr = 0;
+  for (int k = 0; k < kCropPlanes; ++k) {
+    if (!j->src[k]) continue;
+    const int es = fmt_elem_bytes(k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8);
+    const uintptr_t bytes = (uintptr_t)((unsigned long long)n * crop_channels(k) * es * width * height);
+    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + bytes, false};
+    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + bytes, true};
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevLensRec), false};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevLensRec), true};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
+  return nullptr;
+}
+
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
 // sanitising, the half-displacement, the tap count and step, the tap value, the mean and the argument rules.  Compiled

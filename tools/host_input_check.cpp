@@ -26,6 +26,9 @@
 //   host_input_check camera             ofdg_host_camera, ofdg_camera_draw and ofdg_camera_taps on exactly sized heap buffers: the
 //                                       four test sizes, every format pair, one frame and both, every record case and hostile
 //                                       given records, drawn ones, frames of arbitrary bit patterns, every refusal
+//   host_input_check lens               ofdg_host_lens and ofdg_lens_draw on exactly sized heap buffers: the test sizes, every
+//                                       format triple, one frame and both, every record case and hostile given records (NaN,
+//                                       infinities, beyond every limit), drawn ones, flows of any bit pattern, every refusal
 //   host_input_check flow_vis           ofdg_host_flow_vis and ofdg_host_flow_vis_tables on exactly sized heap buffers: the test
 //                                       sizes, both flow formats and layouts, the three norms and both ends of max_flow, with
 //                                       and without dimming, extreme flows and any bit pattern, every refusal
@@ -899,6 +902,132 @@ int camera() {
   return refused == 27 ? 0 : 1;
 }
 
+// ofdg_host_lens and ofdg_lens_draw on heap buffers of exactly the planes' sizes (a byte read or written beside one is a report -
+// the clamped taps at every edge of 8x2, 24x10, 72x34 and 136x18): every format triple, all eight planes and each frame alone,
+// given records that hold the identity, both signs of k1 at its bound, off-centre centres at their bound, fringes and a
+// vignette, and hostile records - NaN, infinities, values beyond every limit, every field in turn -, drawn records at the
+// widest ranges with and without OFDG_LENS_FILL; flows of arbitrary bit patterns (NaN, infinities, 1e30: an fp64 value that
+// does not fit the 24.8 fixed point, or a conversion of a NaN, is a report); then every refusal.
+int lens() {
+  const double hostile[] = {NAN, INFINITY, -INFINITY, 1e300, -1e300, 0.126, -0.126, 2.01, 0.49, 0.6, -0.0, 1e-310, 4e9, -4e9};
+  const int n_hostile = (int)(sizeof hostile / sizeof hostile[0]);
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 4; ++size) {
+    const int W = size == 0 ? 8 : size == 1 ? 24 : size == 2 ? 72 : 136, H = size == 0 ? 2 : size == 1 ? 10 : size == 2 ? 34 : 18, n = 24;
+    const size_t px = (size_t)W * H;
+    const double hw = (W - 1) / 2.0, hh = (H - 1) / 2.0;
+    for (int fmts = 0; fmts < 8; ++fmts) {
+      const int imf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, flf = fmts & 2 ? OFDG_FMT_F16 : OFDG_FMT_F32, ocf = fmts & 4 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+      const int es[8] = {imf == OFDG_FMT_U8 ? 1 : 4, imf == OFDG_FMT_U8 ? 1 : 4, flf == OFDG_FMT_F16 ? 2 : 4, flf == OFDG_FMT_F16 ? 2 : 4,
+                         ocf == OFDG_FMT_U8 ? 1 : 4, ocf == OFDG_FMT_U8 ? 1 : 4, 1, 1};
+      const int ch[8] = {3, 3, 2, 2, 1, 1, 1, 1};
+      std::vector<uint8_t> src[8], dst[8];
+      uint32_t x = 777u + (uint32_t)fmts;
+      for (int k = 0; k < 8; ++k) {
+        src[k].resize((size_t)n * ch[k] * px * es[k]); dst[k].assign(src[k].size(), 0xA5);
+        for (size_t e = 0; e < (size_t)n * ch[k] * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          if (es[k] == 1) { src[k][e] = (uint8_t)(x >> 24); continue; }
+          if (es[k] == 2) { const uint16_t h = (e % 5) == 0 ? (uint16_t)(x >> 16) : (uint16_t)(0x3800u + ((x >> 20) & 0x0FFFu) + ((x >> 3) & 0x8000u)); std::memcpy(src[k].data() + 2 * e, &h, 2); continue; }
+          float v = k < 2 ? (float)(x >> 24) : k < 4 ? ((float)(int)(x >> 20) - 2048.0f) / 64.0f : (x >> 29) == 0 ? 1.0f : 0.0f;
+          if (k >= 2 && k < 4 && (e % 97) == 0) v = 1e30f;
+          const uint32_t bits = x ^ (x << 13);  // (every seventh element: any bit pattern)
+          std::memcpy(src[k].data() + 4 * e, (e % 7) == 0 ? (const void*)&bits : (const void*)&v, 4);
+        }
+      }
+      // records 0..9: the cases by name; 10..23: every field in turn takes the hostile values
+      std::vector<ofdg_lens_rec> recs(n), used(n);
+      const double cases[10][7] = {{0, 1, 0, 0, 0, hw, hh}, {0.125, 1, 0, 0, 0, hw, hh}, {-0.125, 1, 0, 0, 0, hw, hh}, {0.125, 0.5, 0.015625, -0.015625, 0.5, hw + hw / 4, hh - hh / 4},
+                                   {-0.125, 2, -0.015625, 0.015625, 0.5, hw - hw / 4, hh + hh / 4}, {0.04, 0.9, 0.01, 0.002, 0.3, hw + 1, hh}, {-0.03, 1, 0, 0, 0.1, hw, hh + 0.5},
+                                   {0, 2, 0.01, 0.01, 0, hw, hh}, {0, 0.5, 0, 0, 0.5, hw / 1.3, hh}, {0.1, 0.8, 0, 0, 0, hw, hh * 1.2}};
+      for (int i = 0; i < n; ++i) {
+        ofdg_lens_rec& r = recs[i];
+        std::memset(&r, 0x5A, sizeof r);
+        double* const fld = &r.k1;
+        for (int k = 0; k < 7; ++k) fld[k] = cases[i < 10 ? i : 5][k];
+        if (i >= 10) fld[(i - 10) % 7] = hostile[((i - 10) * 3 + fmts + 5 * size) % n_hostile];
+      }
+      for (int drawn = 0; drawn < 3; ++drawn)
+        for (int frames = 1; frames < 4; ++frames) {
+          if (size == 3 && frames != 3) continue;  // (the largest size: both frames only)
+          struct ofdg_lens_job job;
+          std::memset(&job, 0, sizeof job);
+          for (int k = 0; k < 8; ++k)
+            if ((frames >> (k & 1)) & 1) { job.src[k] = src[k].data(); job.dst[k] = dst[k].data(); }
+          job.recs = drawn ? nullptr : recs.data();
+          job.recs_out = used.data();
+          job.first_index = (1ll << 32) - 1; job.seed = 7;
+          job.flags = OFDG_LENS_OCC_WINDOW | (drawn == 2 ? OFDG_LENS_FILL : 0);
+          job.image_fmt = imf; job.flow_fmt = flf; job.occ_fmt = ocf;
+          job.prob = 0.9f; job.k1_range = 0.125f; job.ca_range = 0.015625f; job.vig_max = 0.5f; job.centre = 0.25f;
+          const int rc = ofdg_host_lens(&job, n, W, H);
+          if (rc) { std::printf("lens: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+          ++calls;
+          for (int k = 0; k < 8; ++k)
+            if (job.src[k]) sum = sum * 31 + fnv1a(dst[k].data(), dst[k].size());
+          sum = sum * 31 + fnv1a((const uint8_t*)used.data(), used.size() * sizeof(ofdg_lens_rec));
+          for (int i = 0; i < n; ++i) {
+            const ofdg_lens_rec& u = used[i];
+            const bool in = std::fabs(u.k1) <= 0.125 && u.z >= 0.5 && u.z <= 2.0 && std::fabs(u.ca_b) <= 0.015625 && std::fabs(u.ca_r) <= 0.015625 && u.vig >= 0.0 && u.vig <= 0.5 &&
+                            std::fabs(u.cx - hw) <= hw / 4 && std::fabs(u.cy - hh) <= hh / 4 && u.reserved[0] == 0 && u.reserved[1] == 0;
+            if (!in) { std::printf("lens: a record left its bounds\n"); return 1; }
+          }
+        }
+    }
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> src((size_t)n * 3 * W * H * 4, 0), dst((size_t)n * 3 * W * H * 4 + 64, 0xA5), out((size_t)n * 64, 0xA5);
+    struct ofdg_lens_job good;
+    std::memset(&good, 0, sizeof good);
+    good.src[0] = src.data(); good.dst[0] = dst.data(); good.recs_out = (ofdg_lens_rec*)out.data();
+    good.prob = 0.5f; good.k1_range = 0.05f; good.ca_range = 0.002f; good.vig_max = 0.25f; good.centre = 0.05f; good.flags = OFDG_LENS_FILL;
+    const auto refuse = [&](struct ofdg_lens_job j, int ns, int w, int h) {
+      if (ofdg_host_lens(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_lens: ", 16) == 0) ++refused;
+      else std::printf("lens: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_lens_job j;
+    if (ofdg_host_lens(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 32768); refuse(good, 1, (1 << 20) + 8, 2);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.width = W + 8; j.height = H; refuse(j, n, W, H);
+    j = good; j.image_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.flow_fmt = OFDG_FMT_U8; refuse(j, n, W, H);
+    j = good; j.occ_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flags = 2; refuse(j, n, W, H);
+    j = good; j.reserved = 1; refuse(j, n, W, H);
+    j = good; j.prob = NAN; refuse(j, n, W, H);
+    j = good; j.prob = 1.5f; refuse(j, n, W, H);
+    j = good; j.k1_range = 0.126f; refuse(j, n, W, H);
+    j = good; j.ca_range = -0.001f; refuse(j, n, W, H);
+    j = good; j.vig_max = INFINITY; refuse(j, n, W, H);
+    j = good; j.centre = 0.3f; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; j.src[4] = src.data(); j.dst[4] = dst.data(); j.flags = OFDG_LENS_OCC_WINDOW; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data() + 16; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data(); refuse(j, n, W, H);
+    j = good; j.recs_out = (ofdg_lens_rec*)(dst.data() + 16); refuse(j, n, W, H);
+    ofdg_lens_rec rec;
+    std::memset(&rec, 0xA5, sizeof rec);
+    j = good; j.width = W; j.height = H; j.k1_range = 0.2f;
+    struct ofdg_lens_job sized = good;
+    sized.width = W; sized.height = H;
+    if (ofdg_lens_draw(1, 0, &j, &rec) == OFDG_EINVAL && ofdg_lens_draw(1, 0, nullptr, &rec) == OFDG_EINVAL && ofdg_lens_draw(1, 0, &sized, nullptr) == OFDG_EINVAL &&
+        ofdg_lens_draw(1, 0, &good, &rec) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; }) &&
+                       ((const uint8_t*)&rec)[0] == 0xA5 && ((const uint8_t*)&rec)[63] == 0xA5;
+    if (!clean) { std::printf("lens: a refusal wrote something\n"); return 1; }
+    if (ofdg_lens_draw(1, (1ll << 32) + 3, &sized, &rec) != OFDG_OK || ofdg_host_lens(&good, n, W, H) != OFDG_OK) { std::printf("lens: the valid call failed\n"); return 1; }
+  }
+  std::printf("lens calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 27 ? 0 : 1;
+}
+
 // ofdg_host_flow_vis and ofdg_host_flow_vis_tables on heap buffers of exactly the planes' sizes (a byte read or written beside
 // one is a report): float32 and binary16 flows that hold zeros, every octant, NaN, both infinities, +-2^20, the largest usable
 // value and random bit patterns (a signed overflow in the Q8 components, the roots or the colour is a report), both layouts,
@@ -1148,10 +1277,11 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "splat") == 0) return splat();
   if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
   if (argc >= 2 && std::strcmp(argv[1], "camera") == 0) return camera();
+  if (argc >= 2 && std::strcmp(argv[1], "lens") == 0) return lens();
   if (argc >= 2 && std::strcmp(argv[1], "flow_vis") == 0) return flow_vis();
   if (argc >= 2 && std::strcmp(argv[1], "flow_error") == 0) return flow_error();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | camera | flow_vis | flow_error\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | camera | lens | flow_vis | flow_error\n", argv[0]);
   return 2;
 }
