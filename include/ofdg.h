@@ -1348,6 +1348,120 @@ int ofdg_host_lens(const struct ofdg_lens_job* job, int n_samples, int width, in
 int ofdg_lens_draw(uint32_t seed, long long index, const struct ofdg_lens_job* ranges, ofdg_lens_rec* out);
 
 /*
+ * Block compression: what a baseline JFIF encoder followed by a decoder leaves in the pixels of image0 and / or image1 of a
+ * batch - 8x8 blocking, ringing at edges, chroma coarser than luma -, each sample by a record of its own.  It is the last
+ * physical step of the chain, behind the sensor noise and the colour response (ofdg_photo, ofdg_jitter): almost every real frame
+ * a flow network sees has been compressed.  This is NOT a codec: there is no entropy coding, no bit stream and no file.  The
+ * record is a pure function of (seed, global sample index).  Everything below is 32-bit integers on bytes (the largest
+ * intermediate over the extreme blocks is below 2^28; >> on a negative value is arithmetic): the kernel, ofdg_host_jpeg and the
+ * numpy restatement of the tests give the same bytes.
+ *
+ * Planes, formats, sizes, the byte of a float32 element and alignment as in ofdg_camera: src[f] is image f as
+ * [n,3,height,width] planar B, G, R of src_fmt, dst[f] the same shape of dst_fmt; OFDG_FMT_F32 or OFDG_FMT_U8, chosen
+ * independently.  A frame is present when both its pointers are given.  width = height = 0: the context's frame; otherwise any
+ * size the context's rule allows.  There IS an in-place form: dst[f] == src[f] is allowed when src_fmt == dst_fmt (a
+ * workgroup owns whole MCUs, reads all it needs and writes behind a barrier; see step 5).  It reads no record of the context
+ * and works in every mode.
+ *
+ * Record of sample i: recs[i] (DEVICE memory) when recs is given, else ofdg_jpeg_draw(seed, first_index + i, the job's ranges).
+ * Either way it is sanitised before use, and the sanitised record is what recs_out[i] receives.
+ *
+ * 1. Draw.  Philox4x32-10 (ofdg_crop_philox) under the counter sampler's key of global index g, blocks j = 0, 1 at the counters
+ *    {j, 0, 0x0c7b, 0} (taken: 0x0c70 .. 0x0c7a and 0x0fd9, see ofdg_jitter).  u() and isym() as in ofdg_jitter.
+ *      block 0:  on  = u(.x) < prob
+ *                q0  = quality_min + (int)(((uint64).y * (uint32)(quality_max - quality_min + 1)) >> 32)
+ *                q1  = clamp(q0 + isym(.z, quality_delta), 1, 100)
+ *                sub = subsample >= 0 ? subsample : (u(.w) < sub_prob)
+ *      block 1:  phase_x = .x >> 28, phase_y = .y >> 28 when OFDG_JPEG_PHASE is set, else 0
+ *    quality = on ? {q0, q1} : {0, 0};  subsample = sub;  reserved = 0.
+ * 2. Sanitise.  quality clamps to [0, 100]; a subsample other than 0 / 1 becomes 0; a phase outside 0..15 becomes 0;
+ *    reserved = 0.
+ * 3. Tables.  T.81 Annex K, Table K.1 (luminance) and K.2 (chrominance), as literals, under libjpeg's rule:
+ *      scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;   Q = clamp((base * scale + 50) / 100, 1, 255)
+ *    ofdg_jpeg_tables exports them; Pillow reports exactly these at quality 10, 50 and 90.
+ * 4. Colour, on the bytes, with libjpeg's 16-bit constants (each row sums to 65536 or 0):
+ *      Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *      Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *      Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ * 5. Geometry.  The plane is extended by replicating its edge on all four sides: coordinates are clamped.  The grid's origin
+ *    is (-phase_x, -phase_y) (4:4:4 uses phase & 7).  An MCU is 8x8 (4:4:4) or 16x16 (4:2:0: four Y blocks, one Cb, one Cr);
+ *    every MCU that meets the plane is processed, only pixels inside the plane are written.  4:2:0: a chroma sample is (the
+ *    four of its 2x2 cell + 2) >> 2, and on the way back each chroma sample is repeated over its cell.  A clamped coordinate of
+ *    an MCU always lands in that MCU's own part of the plane - that is what makes the in-place form sound.
+ * 6. Block, for p = sample - 128 and Q of step 3, with T[u][x] = lrint(4096 s(u) cos((2 x + 1) u pi / 16)), s(0) = 1 / sqrt 2,
+ *    else 1, as a literal (magnitudes 2896 and 4017, 3784, 3406, 2896, 2276, 1567, 799):
+ *      A[y][u] = sum_x T[u][x] p[y][x]      A1 = (A + 256) >> 9
+ *      F[v][u] = sum_y T[v][y] A1[y][u]     2^17 times the orthonormal coefficient
+ *      level   = sign(F) * ((|F| + Q * 65536) / (Q * 131072))      D = level * Q
+ *      B[y][u] = sum_v T[v][y] D[v][u]      B1 = (B + 256) >> 9
+ *      P[y][x] = sum_u T[u][x] B1[y][u]     out = clamp(((P + 65536) >> 17) + 128, 0, 255)
+ *    Against the orthonormal float64 DCT with round-half-away quantisation a level is off by at most 1 and under 3 % of them
+ *    are; where all levels of a block agree every byte is within 1 (tests/test_jpeg.py).
+ * 7. Back, with cb = Cb - 128 and cr = Cr - 128, each clamped to a byte:
+ *      R = Y + ((91881 cr + 32768) >> 16)
+ *      G = Y + ((-22554 cb - 46802 cr + 32768) >> 16)
+ *      B = Y + ((116130 cb + 32768) >> 16)
+ *    A uint8 destination stores the byte, a float32 one (float)byte.
+ * 8. Identity.  A frame with quality[f] = 0 is copied - bit for bit where src_fmt == dst_fmt, else through its bytes; in place
+ *    it is left untouched.  Quality 100 is NOT the identity: every Q is 1, yet the colour transform and the roundings of the
+ *    passes remain (a grey plane, B = G = R, does come back exactly at quality 100).
+ *
+ * Asynchronous on `stream`, the stream the frames were written on; OFDG_STREAM_OWN as in ofdg_flow_stats.  One kernel per
+ * call, no atomics, no workspace.
+ *
+ * OFDG_EINVAL, nothing enqueued, no byte written, the field named in ofdg_last_error: NULL job, n_samples < 1, one of width /
+ * height 0 or a size that breaks the rule, 3 * width * height of 2^32 and more, another format code, flags other than 0 /
+ * OFDG_JPEG_PHASE, non-zero reserved, quality_min / quality_max outside 1..100 or min > max, quality_delta outside 0..99, prob
+ * / sub_prob negative, NaN, infinite or above 1, subsample outside -1..1 (the ranges are checked even when records are given),
+ * no frame set, src[f] without dst[f] or the reverse, a misaligned pointer (sources as the render calls ask: 16-byte float32,
+ * 4-byte uint8; destinations and both record arrays 16-byte), a written range (destinations, recs_out) that overlaps any other
+ * range of the job - dst[f] == src[f] with src_fmt != dst_fmt and every partial overlap included, dst[f] == src[f] in one
+ * format excepted -, OFDG_STREAM_OWN before any render / forward call on the context.
+ *
+ * Out of scope: an entropy coder, a bit stream or a file size; triangle ("fancy") chroma upsampling across blocks - which is why
+ * 4:2:0 differs from libjpeg-turbo's decoder by several bytes on saturated edges, and which would end the in-place form -;
+ * 4:2:2 and other samplings; custom tables; progressive, arithmetic or 12-bit modes; deblocking filters and video codecs'
+ * inter-frame prediction; a quality per channel; compression of flow, maps, labels, splat or reprojection planes; packing of
+ * the records.
+ */
+#define OFDG_JPEG_PHASE 1            /* flags: the block grid's phase is drawn; without it the grid starts at (0, 0) */
+typedef struct ofdg_jpeg_rec {       /* 32 bytes; index [f] = frame 0 / 1 */
+  int32_t quality[2];                /* 0: frame f is not compressed; 1..100: libjpeg's quality */
+  int32_t subsample;                 /* 0: 4:4:4;  1: 4:2:0 */
+  int32_t phase_x, phase_y;          /* 0..15: the grid's origin is (-phase_x, -phase_y); 4:4:4 uses phase & 7 */
+  int32_t reserved[3];
+} ofdg_jpeg_rec;
+struct ofdg_jpeg_job {               /* 112 bytes */
+  const void* src[2]; void* dst[2];  /* as ofdg_camera; dst[f] == src[f] IS allowed when src_fmt == dst_fmt (in place) */
+  const ofdg_jpeg_rec* recs;         /* DEVICE, n records, or NULL: drawn */
+  ofdg_jpeg_rec*       recs_out;     /* DEVICE, n records, or NULL */
+  long long first_index; uint32_t seed;
+  int32_t width, height;             /* 0, 0: the context's frame */
+  int32_t src_fmt, dst_fmt;          /* OFDG_FMT_F32 or OFDG_FMT_U8, independently */
+  int32_t flags;                     /* 0 or OFDG_JPEG_PHASE */
+  int32_t subsample;                 /* of the draw: -1 drawn per sample, 0 / 1 fixed */
+  int32_t quality_min, quality_max, quality_delta;   /* 1..100, min <= max; delta 0..99 */
+  float prob, sub_prob;              /* 0..1 */
+  int32_t reserved[2];               /* must be 0 */
+};
+int ofdg_jpeg(ofdg_ctx* ctx, const struct ofdg_jpeg_job* job, int n_samples, void* stream);
+/* The same on HOST arrays (no GPU), the definition block by block: planes and records in host memory, no alignment asked of any
+ * pointer.  width, height: the plane size; the job's own must be 0, 0 or the same.  Errors as above through
+ * ofdg_host_last_error. */
+int ofdg_host_jpeg(const struct ofdg_jpeg_job* job, int n_samples, int width, int height);
+/* The drawn record of global sample `index` (step 1 alone: not sanitised; pure, no GPU).  Of `ranges` only the five ranges,
+ * subsample and flags are read.  OFDG_EINVAL (ofdg_host_last_error), `out` untouched, for a NULL pointer or a range, subsample
+ * or flags ofdg_jpeg refuses. */
+int ofdg_jpeg_draw(uint32_t seed, long long index, const struct ofdg_jpeg_job* ranges, ofdg_jpeg_rec* out);
+/* The tables of step 3 for a quality in 1..100 (pure, no GPU), row-major [v][u].  OFDG_EINVAL (ofdg_host_last_error) for a NULL
+ * pointer or a quality outside 1..100. */
+int ofdg_jpeg_tables(int quality, uint16_t luma[64], uint16_t chroma[64]);
+/* Steps 4-6 on one block (pure, no GPU): `in` the 64 samples row-major [y][x], q the table (each entry 1..255), levels the
+ * quantised coefficients [v][u] (may be NULL), out the decoded samples.  OFDG_EINVAL for a NULL in, q or out, or an entry of q
+ * outside 1..255. */
+int ofdg_host_jpeg_block(const uint8_t in[64], const uint16_t q[64], int32_t levels[64], uint8_t out[64]);
+
+/*
  * Flow visualisation: the Middlebury colour wheel (Baker et al., "A Database and Evaluation Methodology for Optical Flow") of
  * any [n,2,height,width] flow tensor - the forward flow, flow1, a cropped, warped or splat flow, a residual - as a uint8
  * picture: the direction is the hue, the length the saturation, zero flow white.  Behind the producing call on the same

@@ -116,6 +116,7 @@ EXPORTS = [
     "ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw",
     "ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw", "ofdg_host_jitter_hue",
     "ofdg_camera", "ofdg_host_camera", "ofdg_camera_draw", "ofdg_camera_taps",
+    "ofdg_jpeg", "ofdg_host_jpeg", "ofdg_jpeg_draw", "ofdg_jpeg_tables", "ofdg_host_jpeg_block",
     "ofdg_flow_vis", "ofdg_host_flow_vis", "ofdg_host_flow_vis_tables",
     "ofdg_flow_error", "ofdg_host_flow_error", "ofdg_host_flow_error_colours",
     "ofdg_lens", "ofdg_host_lens", "ofdg_lens_draw",
@@ -1792,6 +1793,148 @@ def host_camera(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype
     return out, used
 
 
+# block compression (ofdg_jpeg_rec / struct ofdg_jpeg_job / ofdg_jpeg, include/ofdg.h)
+JPEG_REC_WORDS = 8   # a record as int32 [8]: quality[2] subsample phase_x phase_y, then 3 reserved words
+JPEG_PHASE = 1       # OFDG_JPEG_PHASE
+JPEG_RANGES = ("quality_min", "quality_max", "quality_delta", "prob", "sub_prob", "subsample", "phase")
+# A starting point: every second sample is compressed at a quality of 30 to 95, frame 1 within 5 of frame 0, half of those
+# with 4:2:0 chroma, the block grid at a drawn phase (as after a crop of a compressed video).  Not a recipe from a paper:
+# every field is a range to be chosen per data set and target codec.
+JPEG_DEFAULT = dict(prob=0.5, quality_min=30, quality_max=95, quality_delta=5, subsample=-1, sub_prob=0.5, phase=True)
+
+
+class JpegRec(C.Structure):
+    """ofdg_jpeg_rec: the compression of one sample (32 bytes)."""
+    _fields_ = [("quality", C.c_int32 * 2), ("subsample", C.c_int32), ("phase_x", C.c_int32), ("phase_y", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class JpegJob(C.Structure):
+    """struct ofdg_jpeg_job (112 bytes)."""
+    _fields_ = [("src", C.c_void_p * 2), ("dst", C.c_void_p * 2), ("recs", C.c_void_p), ("recs_out", C.c_void_p),
+                ("first_index", C.c_longlong), ("seed", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("src_fmt", C.c_int32), ("dst_fmt", C.c_int32), ("flags", C.c_int32), ("subsample", C.c_int32),
+                ("quality_min", C.c_int32), ("quality_max", C.c_int32), ("quality_delta", C.c_int32),
+                ("prob", C.c_float), ("sub_prob", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def _jpeg_rec_dtype():
+    import numpy as np
+    return np.dtype([("quality", "<i4", (2,)), ("subsample", "<i4"), ("phase_x", "<i4"), ("phase_y", "<i4"), ("reserved", "<i4", (3,))])
+
+
+def jpeg_numpy(recs):
+    """Records of Generator.jpeg / host_jpeg - a torch tensor or numpy array of int32 [n,8] (or any array of 32 bytes a record)
+    - as a numpy structured array [n] with the fields quality ([2]: frame 0, frame 1), subsample, phase_x, phase_y and
+    reserved [3]."""
+    import numpy as np
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a)
+    if a.dtype == _jpeg_rec_dtype():
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % 32:
+        raise ValueError("records must be 32 bytes each, got %d bytes" % raw.size)
+    return raw.view(_jpeg_rec_dtype())
+
+
+def _jpeg_ranges(job, ranges):
+    """the ranges of a dict in a job: a missing probability or delta is 0, a missing quality_min / quality_max 75 (libjpeg's
+    default), a missing subsample -1 (drawn per sample), a missing phase False (the grid starts at (0, 0))"""
+    ranges = {} if ranges is None else ranges
+    for key in ranges:
+        if key not in JPEG_RANGES:
+            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(JPEG_RANGES)))
+    job.quality_min, job.quality_max = int(ranges.get("quality_min", 75)), int(ranges.get("quality_max", 75))
+    job.quality_delta = int(ranges.get("quality_delta", 0))
+    job.prob, job.sub_prob = float(ranges.get("prob", 0.0)), float(ranges.get("sub_prob", 0.0))
+    job.subsample = int(ranges.get("subsample", -1))
+    job.flags = JPEG_PHASE if ranges.get("phase", False) else 0
+    return job
+
+
+def _jpeg_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
+    job = _jpeg_ranges(JpegJob(), ranges)
+    for f in range(2):
+        if src[f] is not None:
+            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
+    job.recs, job.recs_out = recs, recs_out
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt = codes
+    return job
+
+
+def jpeg_draw(seed, index, ranges=None):
+    """ofdg_jpeg_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (JPEG_RANGES; a missing
+    probability or delta is 0, a missing quality 75, a missing subsample -1, a missing phase False; JPEG_DEFAULT for one),
+    before sanitising, as one element of the structured array jpeg_numpy describes."""
+    job = _jpeg_ranges(JpegJob(), ranges)
+    out = JpegRec()
+    _host_check(lib().ofdg_jpeg_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
+    return jpeg_numpy(bytearray(out))[0]
+
+
+def host_jpeg_tables(quality):
+    """ofdg_jpeg_tables (pure, no GPU): (luma, chroma), the quantisation tables of a quality in 1..100 as uint16 [8,8], [v][u] -
+    T.81's Tables K.1 and K.2 under libjpeg's scaling."""
+    import numpy as np
+    luma, chroma = np.zeros((8, 8), np.uint16), np.zeros((8, 8), np.uint16)
+    _host_check(lib().ofdg_jpeg_tables(int(quality), luma.ctypes.data, chroma.ctypes.data))
+    return luma, chroma
+
+
+def host_jpeg_block(block, q):
+    """ofdg_host_jpeg_block (pure, no GPU): one 8x8 block of uint8 samples [y][x] through the forward transform, the quantiser of
+    the table q (uint16 [8,8], entries 1..255) and back.  Returns (levels int32 [8,8] as [v][u], out uint8 [8,8])."""
+    import numpy as np
+    block = np.ascontiguousarray(block, np.uint8)
+    q = np.ascontiguousarray(q, np.uint16)
+    if block.shape != (8, 8) or q.shape != (8, 8):
+        raise ValueError("block and q must be [8,8], got %s and %s" % (block.shape, q.shape))
+    levels, out = np.zeros((8, 8), np.int32), np.zeros((8, 8), np.uint8)
+    _host_check(lib().ofdg_host_jpeg_block(block.ctypes.data, q.ctypes.data, levels.ctypes.data, out.ctypes.data))
+    return levels, out
+
+
+def alloc_jpeg(n, height=None, width=None, image_dtype=None, frames=(0, 1), device="cuda"):
+    """((out0, out1), recs) of Generator.jpeg for n samples: the int32 [n,8] records (recs_out) and - for the copying form, when
+    height and width are given - the frames to write, [n,3,height,width] of image_dtype (default torch.float32), None for a
+    frame not among `frames`; without a size (the in-place form) the pair is (None, None).  Not filled: the call writes every
+    element and every record."""
+    import torch
+    dt = torch.float32 if image_dtype is None else image_dtype
+    sized = height is not None and width is not None
+    return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if sized and f in frames else None for f in range(2)),
+            torch.empty((n, JPEG_REC_WORDS), dtype=torch.int32, device=device))
+
+
+def host_jpeg(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None, in_place=False):
+    """ofdg_host_jpeg (no GPU): the block compression of HOST arrays - images a pair (image0, image1) of float32 or uint8 arrays
+    [n,3,H,W] (planar B, G, R), either None; recs None (drawn from seed, first_index and ranges) or n records (jpeg_numpy's
+    array, or int32 [n,8]).  dst_dtype: np.float32 / np.uint8, default the source's.  in_place: the sources themselves are
+    written (they must be contiguous and of dst_dtype).  Returns ((out0, out1), recs_used): the arrays (None for an absent
+    frame) and the records after sanitising, as jpeg_numpy's array."""
+    import numpy as np
+    images = tuple(images)
+    if not in_place:
+        images = tuple(None if t is None else np.ascontiguousarray(t) for t in images)
+    given = [t for t in images if t is not None]
+    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
+    out = images if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
+    n, height, width, *codes = photo_format(images, out)
+    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
+        raise ValueError("in_place needs contiguous sources of dst_dtype")
+    if recs is not None:
+        recs = jpeg_numpy(recs).copy()
+        if recs.shape != (n,):
+            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
+    used = np.zeros((n,), _jpeg_rec_dtype())
+    job = _jpeg_job(images, out, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
+                    first_index, seed, ranges)
+    _host_check(lib().ofdg_host_jpeg(C.byref(job), n, width, height))
+    return out, used
+
+
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
 MBLUR_MAX_SHUTTER = 2.0    # OFDG_MBLUR_MAX_SHUTTER
 MBLUR_MAX_HALF_PX = 32     # OFDG_MBLUR_MAX_HALF_PX
@@ -2470,6 +2613,11 @@ def lib():
         L.ofdg_host_camera.argtypes = [C.POINTER(CameraJob), i32, i32, i32]
         L.ofdg_camera_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(CameraJob), C.POINTER(CameraRec)]
         L.ofdg_camera_taps.argtypes = [i32, C.POINTER(C.c_uint32)]
+        L.ofdg_jpeg.argtypes = [vp, C.POINTER(JpegJob), i32, vp]
+        L.ofdg_host_jpeg.argtypes = [C.POINTER(JpegJob), i32, i32, i32]
+        L.ofdg_jpeg_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(JpegJob), C.POINTER(JpegRec)]
+        L.ofdg_jpeg_tables.argtypes = [i32, vp, vp]
+        L.ofdg_host_jpeg_block.argtypes = [vp, vp, vp, vp]
         L.ofdg_lens.argtypes = [vp, C.POINTER(LensJob), i32, vp]
         L.ofdg_host_lens.argtypes = [C.POINTER(LensJob), i32, i32, i32]
         L.ofdg_lens_draw.argtypes = [C.c_uint32, C.c_longlong, C.POINTER(LensJob), C.POINTER(LensRec)]
@@ -3057,6 +3205,27 @@ class Generator:
         self._check_recs(recs, recs_out, "int32", (n, CAMERA_REC_WORDS))
         job = _camera_job(images, out, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
         self._check(lib().ofdg_camera(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return out
+
+    def jpeg(self, images, out=None, recs=None, first_index=0, seed=None, ranges=None, recs_out=None, stream=0, size=None):
+        """Block compression of both frames of a batch in one launch (ofdg_jpeg, include/ofdg.h): what a baseline JFIF encoder and
+        a decoder leave in the pixels - 8x8 blocking, ringing, with 4:2:0 coarser chroma - at a quality per sample and frame and
+        a block grid at the sample's phase.  No bit stream, no file.  images: the pair (image0, image1) of float32 or uint8
+        tensors [n,3,H,W] a render / forward call (or any stage up to jitter) wrote, either member None; out: the pair to write,
+        float32 or uint8 independently of images (alloc_jpeg), or None: in place.  recs: None - the record of sample i is
+        jpeg_draw(seed, first_index + i, ranges) - or an int32 device tensor [n,8], taken as given; either is sanitised.
+        ranges: a dict of JPEG_RANGES (jpeg_draw names the defaults; JPEG_DEFAULT is a starting point).  seed: default the
+        context's.  recs_out: None or an int32 device tensor [n,8] that receives the records used (jpeg_numpy reads it).
+        stream: the stream the frames were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of
+        the context's.  A frame of quality 0 is copied (in place: left alone); quality 100 is not the identity.  Flow, maps and
+        labels are not touched.  Asynchronous.  Returns out (in place: images)."""
+        images = tuple(images)
+        out = images if out is None else tuple(out)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = photo_format(images, out, height, width)
+        self._check_recs(recs, recs_out, "int32", (n, JPEG_REC_WORDS))
+        job = _jpeg_job(images, out, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
+        self._check(lib().ofdg_jpeg(self.h, C.byref(job), n, C.c_void_p(stream)))
         return out
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
@@ -3772,6 +3941,7 @@ class _RingSlot:
                  "photo",        # the records of photo=
                  "jitter",       # (workspace, records) of jitter=
                  "erase",        # (workspace, records) of erase=
+                 "jpeg",         # the records of jpeg= (the stage runs between jitter= and erase=)
                  "edges",        # the planes of boundaries= by name ...
                  "edge_args",    # ... and the plane arguments of Generator.boundaries that fill them
                  "vis",          # (picture, rows, workspace) of vis= by the name of the flow
@@ -3810,20 +3980,22 @@ class FlowLoader:
                             which take the places of image0 / image1 for every later stage and in the batch
         8. photo=           in place, on both frames
         9. jitter=          in place, on both frames
-        10. erase=           in place, on the frames and the occlusion maps
-        11. objects=True    the table, of the label planes of stage 1
-        12. stats=, pyramid= the reductions of flow and occ0
-        13. boundaries=     of the flows and label planes
-        14. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
-        15. pack=           of image0, image1 and flow, into tensors of its own
+        10. jpeg=           in place, on both frames
+        11. erase=           in place, on the frames and the occlusion maps
+        12. objects=True    the table, of the label planes of stage 1
+        13. stats=, pyramid= the reductions of flow and occ0
+        14. boundaries=     of the flows and label planes
+        15. vis=            the colour-wheel pictures of the flows as they are then, into tensors of its own
+        16. pack=           of image0, image1 and flow, into tensors of its own
 
     So the blur follows the flow the batch hands out, the optics act behind the exposure and in front of the sensor noise, the
     photometric noise stays sharp on top of both as a sensor's does, the
     colour jitter and the eraser's mean fill see the augmented frame - the fill is the mean colour of the jittered frame, as in
-    the RAFT recipe -, the reductions see the occ0 the eraser extended and the unpacked,
+    the RAFT recipe -, the block compression is the last physical step and the eraser paints on the finished, compressed
+    picture, the reductions see the occ0 the eraser extended and the unpacked,
     unscaled flow, and the pack sees the finished frames; the table, the label planes and the boundary planes are those of
-    the un-erased sample (none of camera=, photo=, jitter= and erase= touches what they read); with lens= the blur follows the bent
-    flow and the reductions count the bent one.  The records of stages 2, 3 and 5 to 10 are drawn from the
+    the un-erased sample (none of camera=, photo=, jitter=, jpeg= and erase= touches what they read); with lens= the blur follows the bent
+    flow and the reductions count the bent one.  The records of stages 2, 3 and 5 to 11 are drawn from the
     context's seed and the batch's first global index - shard_first_index of its step -, so start= and sharding reproduce the
     same windows, pixels and rectangles.  A batch is (image0, image1, flow), and (image0, image1, flow, {name: tensor}) as soon
     as extras= or any stage option but pack= is on; below, [H,W] is the size of the window when there is one.
@@ -3872,6 +4044,9 @@ class FlowLoader:
     jitter=ranges (a dict of JITTER_RANGES, JITTER_RAFT for the recipe's): the ColorJitter of the RAFT-family recipes on both
     frames (Generator.jitter), behind photo= and in front of erase=; the dict also holds "jitter" (int32 [n,16], the records used
     with the means: jitter_numpy).
+    jpeg=dict(...) (the JPEG_RANGES, JPEG_DEFAULT for a starting point): the block compression of Generator.jpeg in place on
+    both frames, directly behind jitter= and in front of erase=; the dict also holds "jpeg" (int32 [n,8], the records used:
+    jpeg_numpy).  An unknown key raises.
     erase=dict(...) (the ERASE_RANGES - ERASE_RAFT for one - and, optionally, fill=, color=, frames=, mark_occ= as Generator.erase
     takes them): occluder rectangles are painted into the frames and the occlusion maps among extras= extended; the dict also
     holds "erase" (int32 [n,24], the records used: erase_numpy).  mark_occ=True needs a map among extras=; marking occ1 for
@@ -3906,7 +4081,7 @@ class FlowLoader:
                  extras_compact=False, objects=False, stats=False, stats_bin_px=2.0, pyramid=0, pyramid_scale=True, pyramid_weights=False,
                  crop=None, crop_hflip=False, crop_vflip=False, crop_occ_window=True, photo=None, spatial=None, spatial_size=None,
                  spatial_hflip=False, spatial_vflip=False, spatial_occ_window=True, pack=None, boundaries=None, erase=None, motion_blur=None,
-                 reproject=None, splat=None, jitter=None, vis=None, camera=None, lens=None, **kw):
+                 reproject=None, splat=None, jitter=None, vis=None, camera=None, lens=None, jpeg=None, **kw):
         import torch
         self.vis = self._vis_options(vis, extras)
         self.boundaries = self._boundary_options(boundaries, extras)
@@ -3915,6 +4090,7 @@ class FlowLoader:
         self.reproject = self._reproject_options(reproject, extras)
         self.splat = self._splat_options(splat, extras)
         self.jitter = self._jitter_options(jitter)
+        self.jpeg = self._jpeg_options(jpeg)
         self.camera = self._camera_options(camera)
         self.lens = self._lens_options(lens, extras, objects)
         self.pack = None if pack is None else dict(pack)
@@ -4000,6 +4176,7 @@ class FlowLoader:
                 t.planes = dict(t.optics, image0=shot[0], image1=shot[1])
             t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
             t.jitter = alloc_jitter(n) if self.jitter is not None else None
+            t.jpeg = alloc_jpeg(n)[1] if self.jpeg is not None else None
             t.erase = alloc_erase(n) if self.erase is not None else None
             t.objects = alloc_object_table(n) if objects else None
             t.stats = alloc_flow_stats(n) if stats else None
@@ -4125,6 +4302,14 @@ class FlowLoader:
         return dict(lens), "occ0" in extras or "occ1" in extras
 
     @staticmethod
+    def _jpeg_options(jpeg):
+        """jpeg= as a dict of its own, or None; raises for a name that is no range"""
+        if jpeg is None:
+            return None
+        _jpeg_ranges(JpegJob(), jpeg)
+        return dict(jpeg)
+
+    @staticmethod
     def _jitter_options(jitter):
         """jitter= as a dict of its own, or None; raises for a name that is no range"""
         if jitter is None:
@@ -4202,7 +4387,7 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None or self.lens is not None:  # ... for the stages that draw records
+        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None or self.lens is not None or self.jpeg is not None:  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window
@@ -4240,6 +4425,8 @@ class FlowLoader:
         if self.jitter is not None:
             work, recs = t.jitter
             g.jitter((planes["image0"], planes["image1"]), recs_out=recs, first_index=first, ranges=self.jitter, stream=s, size=size, work=work)
+        if self.jpeg is not None:
+            g.jpeg((planes["image0"], planes["image1"]), recs_out=t.jpeg, first_index=first, ranges=self.jpeg, stream=s, size=size)
         if self.erase is not None:
             ranges, o = self.erase
             work, recs = t.erase
@@ -4292,6 +4479,8 @@ class FlowLoader:
             more["photo"] = t.photo
         if t.jitter is not None:
             more["jitter"] = t.jitter[1]
+        if t.jpeg is not None:
+            more["jpeg"] = t.jpeg
         if t.objects is not None:
             more["objects"], more["object_counts"] = t.objects
         if t.stats is not None:

@@ -1174,6 +1174,131 @@ int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width
   return OFDG_OK;
 }
 
+// ofdg_jpeg on host arrays (no GPU): the definition of include/ofdg.h MCU by MCU.  The draw, the sanitising, the tables, the
+// colour transforms, the block's passes and the argument rules are the functions the kernel runs (csrc/ofdg_device.h);
+// elements are moved with memcpy.  A frame is read whole before any of it is written, so the in-place form needs no care.
+int ofdg_jpeg_draw(uint32_t seed, long long index, const struct ofdg_jpeg_job* ranges, ofdg_jpeg_rec* out) {
+  if (!ranges || !out) { g_host_error = "ofdg_jpeg_draw: ranges or out is NULL"; return OFDG_EINVAL; }
+  DevJpegJob j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = jpeg_ranges_error(j)) { g_host_error = std::string("ofdg_jpeg_draw: ") + why; return OFDG_EINVAL; }
+  const DevJpegRec r = jpeg_draw_rec(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
+int ofdg_jpeg_tables(int quality, uint16_t luma[64], uint16_t chroma[64]) {
+  if (!luma || !chroma || quality < 1 || quality > 100) { g_host_error = "ofdg_jpeg_tables: luma or chroma is NULL, or quality outside 1..100"; return OFDG_EINVAL; }
+  for (int k = 0; k < 64; ++k) {
+    luma[k] = (uint16_t)jpeg_quant(kJpegBaseLuma[k], quality);
+    chroma[k] = (uint16_t)jpeg_quant(kJpegBaseChroma[k], quality);
+  }
+  return OFDG_OK;
+}
+int ofdg_host_jpeg_block(const uint8_t in[64], const uint16_t q[64], int32_t levels[64], uint8_t out[64]) {
+  if (!in || !q || !out) { g_host_error = "ofdg_host_jpeg_block: in, q or out is NULL"; return OFDG_EINVAL; }
+  for (int k = 0; k < 64; ++k)
+    if (q[k] < 1 || q[k] > 255) { g_host_error = "ofdg_host_jpeg_block: q: every entry must lie in 1..255"; return OFDG_EINVAL; }
+  uint8_t o[64];
+  jpeg_block(in, q, levels, o);
+  std::memcpy(out, o, sizeof(o));
+  return OFDG_OK;
+}
+int ofdg_host_jpeg(const struct ofdg_jpeg_job* job, int n_samples, int width, int height) {
+  const DevJpegJob* const j = reinterpret_cast<const DevJpegJob*>(job);
+  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = jpeg_arg_error(j, n_samples, width, height);
+  if (why) { g_host_error = std::string("ofdg_host_jpeg: ") + why; return OFDG_EINVAL; }
+  const int W = width, H = height;
+  const size_t plane = (size_t)W * H;
+  const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
+  std::vector<uint8_t> ycc[3], out[3];   // a sample's frame as Y, Cb, Cr; the decoded B, G, R
+  for (int c = 0; c < 3; ++c) { ycc[c].resize(plane); out[c].resize(plane); }
+  for (int i = 0; i < n_samples; ++i) {
+    DevJpegRec r;
+    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+    else r = jpeg_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
+    r = jpeg_sanitise(r);
+    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    for (int f = 0; f < 2; ++f) {
+      if (!j->src[f]) continue;
+      const int quality = r.quality[f];
+      const uint8_t* const sp = static_cast<const uint8_t*>(j->src[f]) + (size_t)i * 3 * plane * ses;
+      uint8_t* const dp = static_cast<uint8_t*>(j->dst[f]) + (size_t)i * 3 * plane * des;
+      if (quality == 0 && j->src_fmt == j->dst_fmt) {  // copied bit for bit; in place: left as it is
+        if (dp != sp) std::memcpy(dp, sp, 3 * plane * ses);
+        continue;
+      }
+      for (size_t k = 0; k < plane; ++k) {
+        int bgr[3];
+        for (int c = 0; c < 3; ++c) {
+          bgr[c] = sp[c * plane + k];
+          if (ses == 4) {
+            float e;
+            std::memcpy(&e, sp + (c * plane + k) * 4, 4);
+            bgr[c] = photo_index(e);
+          }
+        }
+        if (quality == 0) {
+          for (int c = 0; c < 3; ++c) out[c][k] = (uint8_t)bgr[c];
+        } else {
+          ycc[0][k] = (uint8_t)jpeg_luma(bgr[2], bgr[1], bgr[0]);
+          ycc[1][k] = (uint8_t)jpeg_cb(bgr[2], bgr[1], bgr[0]);
+          ycc[2][k] = (uint8_t)jpeg_cr(bgr[2], bgr[1], bgr[0]);
+        }
+      }
+      if (quality > 0) {
+        uint16_t q[2][64];
+        for (int k = 0; k < 64; ++k) {
+          q[0][k] = (uint16_t)jpeg_quant(kJpegBaseLuma[k], quality);
+          q[1][k] = (uint16_t)jpeg_quant(kJpegBaseChroma[k], quality);
+        }
+        const int sub = r.subsample, M = jpeg_mcu(sub);
+        const int px = jpeg_phase(r.phase_x, sub), py = jpeg_phase(r.phase_y, sub);
+        for (int oy = -py; oy < H; oy += M)
+          for (int ox = -px; ox < W; ox += M) {
+            uint8_t dec[3][256];  // the decoded Y, Cb, Cr of the MCU, [M][M]
+            for (int c = 0; c < 3; ++c) {
+              const bool coarse = sub && c > 0;
+              for (int b = 0; b < (sub && c == 0 ? 4 : 1); ++b) {
+                const int bx = 8 * (b & 1), by = 8 * (b >> 1);
+                uint8_t in[64], o[64];
+                for (int y = 0; y < 8; ++y)
+                  for (int x = 0; x < 8; ++x) {
+                    if (!coarse) {
+                      in[y * 8 + x] = ycc[c][(size_t)camera_clamp(oy + by + y, H) * W + camera_clamp(ox + bx + x, W)];
+                    } else {
+                      const size_t y0 = (size_t)camera_clamp(oy + 2 * y, H) * W, y1 = (size_t)camera_clamp(oy + 2 * y + 1, H) * W;
+                      const int x0 = camera_clamp(ox + 2 * x, W), x1 = camera_clamp(ox + 2 * x + 1, W);
+                      in[y * 8 + x] = (uint8_t)jpeg_cell((int32_t)ycc[c][y0 + x0] + ycc[c][y0 + x1] + ycc[c][y1 + x0] + ycc[c][y1 + x1]);
+                    }
+                  }
+                jpeg_block(in, q[c ? 1 : 0], nullptr, o);
+                for (int y = 0; y < (coarse ? 16 : 8); ++y)
+                  for (int x = 0; x < (coarse ? 16 : 8); ++x) dec[c][(by + y) * M + bx + x] = coarse ? o[(y >> 1) * 8 + (x >> 1)] : o[y * 8 + x];
+              }
+            }
+            for (int y = oy < 0 ? -oy : 0; y < M && oy + y < H; ++y)
+              for (int x = ox < 0 ? -ox : 0; x < M && ox + x < W; ++x) {
+                const int Y = dec[0][y * M + x], cb = dec[1][y * M + x], cr = dec[2][y * M + x];
+                const size_t k = (size_t)(oy + y) * W + (size_t)(ox + x);
+                out[0][k] = (uint8_t)jpeg_blue(Y, cb); out[1][k] = (uint8_t)jpeg_green(Y, cb, cr); out[2][k] = (uint8_t)jpeg_red(Y, cr);
+              }
+          }
+      }
+      for (int c = 0; c < 3; ++c)
+        for (size_t k = 0; k < plane; ++k) {
+          uint8_t* const q = dp + (c * plane + k) * des;
+          const float e = (float)out[c][k];
+          if (des == 4) std::memcpy(q, &e, 4);
+          else *q = out[c][k];
+        }
+    }
+  }
+  return OFDG_OK;
+}
+
 // ofdg_motion_blur on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.

@@ -6081,4 +6081,162 @@ __global__ __launch_bounds__(kSpatialThreads) void lens_kernel(const DevLensJob 
   }
 }
 
+// ---- Block compression (ofdg_jpeg, include/ofdg.h) -------------------------------------------------------------------------
+// One launch for both frames and every sample: blockIdx.x counts the 16x16 regions of the block grid, blockIdx.y the samples,
+// blockIdx.z the frames that are set.  A 4-wave workgroup owns one region at the sample's phase - one 4:2:0 MCU, or 2 x 2 MCUs
+// of 4:4:4 -, wave w its 8x8 quadrant, a lane one pixel: lane = 8 row + column.  The grid covers the largest phase (15); a
+// region that does not meet the plane at the sample's phase is skipped by its whole workgroup.  The record is read or drawn,
+// and sanitised, on uniform values once per (workgroup, sample); quality, subsampling and phase are pinned to scalar
+// registers, so every branch on them is uniform.
+//   A lane reads its pixel at clamped coordinates (the edge replicated), makes Y, Cb, Cr in registers, and a wave transforms one
+//   8x8 block at a time with a lane an element: the two passes of each transform exchange through the wave's own 64 words of
+//   LDS, a row read for the passes along x, a column read for those along y.  The pitch is 8 words: a 32-lane half (four rows of eight
+//   lanes) meets 4 addresses 8 banks apart in a row read and 8 consecutive words in a column read (the other lanes share one
+//   of them), and writes 32 consecutive words, so no access conflicts under the 32-bank rule of a one-word LDS read or write
+//   (profiles/jpeg_device_code.txt).  The lane's four slices of T stay
+//   in registers.  4:4:4: three blocks a wave (Y, Cb, Cr of its quadrant).  4:2:0: the four Y blocks, then Cb and Cr go
+//   through LDS as bytes, a lane averages one 2x2 cell, waves 0 and 1 transform the two chroma blocks (2 and 3 run along on
+//   the same values and drop them), and every lane picks up its cell's decoded pair.
+//   The two tables of the (sample, frame) are built once per workgroup by 128 lanes.  All the arithmetic is the host twin's
+//   (csrc/ofdg_device.h), so the result is the twin's byte for byte.
+// Every global read of a sample stands in front of the first barrier of the first transform and every write behind the last,
+// and a clamped coordinate of a region that meets the plane lies in that region: the in-place form (dst[f] == src[f]) reads
+// nothing another workgroup writes.  quality 0: three waves copy the region at phase 0, a channel each and a quad a lane (bit for
+// bit from float32 to float32, else through the bytes), or, in place, nothing.
+// Every global index is clamped into the plane or guarded by `inside`; every LDS index is below its array's bound by
+// construction (lane < 64; X, Y < 16).  2176 bytes of LDS, no atomics, no scratch.
+constexpr int kJpegThreads = 256, kJpegRegion = 16;
+// One block, a lane an element (lx, ly): step 6 of the definition.  xb: the wave's 64 words; q: the table; the lane's slices of
+// T: rx[k] = T[lx][k], ry[k] = T[ly][k], cx[k] = T[k][lx], cy[k] = T[k][ly].  Every lane of the workgroup calls it together.
+__device__ __forceinline__ int32_t jpeg_lane_block(int32_t sample, const uint16_t* q, int32_t* xb, int lx, int ly, const int32_t (&rx)[8],
+                                                   const int32_t (&ry)[8], const int32_t (&cx)[8], const int32_t (&cy)[8]) {
+  const int own = ly * 8 + lx;
+  int32_t s;
+  xb[own] = sample - 128;
+  __syncthreads();
+  s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += rx[k] * xb[ly * 8 + k];  // A[y][u]: y = ly, u = lx
+  s = jpeg_round9(s);
+  __syncthreads();
+  xb[own] = s;
+  __syncthreads();
+  s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += ry[k] * xb[k * 8 + lx];  // F[v][u]: v = ly, u = lx
+  const uint32_t Q = q[own];
+  s = jpeg_level(s, Q) * (int32_t)Q;
+  __syncthreads();
+  xb[own] = s;
+  __syncthreads();
+  s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += cy[k] * xb[k * 8 + lx];  // B[y][u]: y = ly, u = lx
+  s = jpeg_round9(s);
+  __syncthreads();
+  xb[own] = s;
+  __syncthreads();
+  s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += cx[k] * xb[ly * 8 + k];  // P[y][x]: y = ly, x = lx
+  __syncthreads();  // (the next block of this wave writes xb)
+  return jpeg_sample(s);
+}
+template <bool kSrcU8, bool kDstU8>
+__global__ __launch_bounds__(kJpegThreads) void jpeg_kernel(const DevJpegJob job, int n, int W, int H, uint32_t tiles_x) {
+  constexpr int kSES = kSrcU8 ? 1 : 4, kDES = kDstU8 ? 1 : 4;
+  __shared__ int32_t s_x[4][64];
+  __shared__ int32_t s_t[64];
+  __shared__ uint16_t s_q[2][64];
+  __shared__ uint8_t s_c[2][kJpegRegion * kJpegRegion];
+  __shared__ uint8_t s_d[2][64];
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int lx = lane & 7, ly = lane >> 3;
+  const int X = 8 * (wave & 1) + lx, Y = 8 * (wave >> 1) + ly;  // the lane's pixel in the region
+  const int TX = (int)(blockIdx.x % tiles_x) * kJpegRegion, TY = (int)(blockIdx.x / tiles_x) * kJpegRegion;
+  const int f = (blockIdx.z != 0u || !job.src[0]) ? 1 : 0;
+  const uint8_t* const s_img = static_cast<const uint8_t*>(f ? job.src[1] : job.src[0]);
+  uint8_t* const d_img = static_cast<uint8_t*>(f ? job.dst[1] : job.dst[0]);
+  const uint32_t plane = (uint32_t)W * (uint32_t)H;  // (3 * plane < 2^32: jpeg_arg_error)
+  if (threadIdx.x < 64u) s_t[threadIdx.x] = kJpegT[threadIdx.x];
+  __syncthreads();
+  int32_t t_rx[8], t_ry[8], t_cx[8], t_cy[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    t_rx[k] = s_t[lx * 8 + k]; t_ry[k] = s_t[ly * 8 + k];
+    t_cx[k] = s_t[k * 8 + lx]; t_cy[k] = s_t[k * 8 + ly];
+  }
+  int32_t* const xb = s_x[wave];
+  for (int i = (int)blockIdx.y; i < n; i += (int)gridDim.y) {
+    DevJpegRec r;
+    if (job.recs) r = job.recs[i];
+    else r = jpeg_draw_rec(job.seed, (unsigned long long)(job.first_index + i), job);
+    r = jpeg_sanitise(r);
+    if (job.recs_out && blockIdx.x == 0u && blockIdx.z == 0u && threadIdx.x == 0u) {
+      u32x4* const o = reinterpret_cast<u32x4*>(job.recs_out + i);
+      o[0] = u32x4{(uint32_t)r.quality[0], (uint32_t)r.quality[1], (uint32_t)r.subsample, (uint32_t)r.phase_x};
+      o[1] = u32x4{(uint32_t)r.phase_y, 0u, 0u, 0u};
+    }
+    const int quality = __builtin_amdgcn_readfirstlane(f ? r.quality[1] : r.quality[0]);
+    const int sub = __builtin_amdgcn_readfirstlane(r.subsample);
+    const uint8_t* const sp = s_img + (size_t)i * 3 * plane * kSES;
+    uint8_t* const dp = d_img + (size_t)i * 3 * plane * kDES;
+    if (quality == 0) {  // (uniform) the copy of the region at phase 0; in place: nothing
+      if (d_img != s_img) {
+        // as quads: wave c < 3 takes channel c, a lane four pixels of one row (W % 4 == 0: a quad is whole or outside)
+        const int gx = TX + 4 * (lane & 3), gy = TY + (lane >> 2);
+        const bool on = wave < 3 && gx < W && gy < H;
+        const uint32_t e = on ? (uint32_t)wave * plane + (uint32_t)gy * (uint32_t)W + (uint32_t)gx : 0u;
+        if constexpr (!kSrcU8 && !kDstU8) {
+          if (on) quad_store_u32x4(reinterpret_cast<u32x4*>(dp + (size_t)e * 4u), *reinterpret_cast<const u32x4*>(sp + (size_t)e * 4u));
+        } else {
+          uint32_t own[4] = {0u, 0u, 0u, 0u};
+          if (on) quad_load_bytes<kSrcU8>(sp + (size_t)e * kSES, own);
+          if constexpr (!kDstU8) quad_store_bytes_f32(dp + (size_t)e * 4u, own, on);
+          else if (on) *reinterpret_cast<uint32_t*>(dp + e) = quad_word(own);  // (the lane's own word: the pair store's shuffle costs this kernel a wave a SIMD)
+        }
+      }
+      continue;
+    }
+    const int ox = TX - __builtin_amdgcn_readfirstlane(jpeg_phase(r.phase_x, sub)), oy = TY - __builtin_amdgcn_readfirstlane(jpeg_phase(r.phase_y, sub));
+    if (ox >= W || oy >= H) continue;  // (uniform; ox + 16 > 0 and oy + 16 > 0 always) the region lies outside the plane
+    const int px = ox + X, py = oy + Y;
+    const bool inside = px >= 0 && px < W && py >= 0 && py < H;
+    const uint32_t at = (uint32_t)camera_clamp(py, H) * (uint32_t)W + (uint32_t)camera_clamp(px, W);
+    int32_t yv, cb, cr;
+    {
+      const int32_t b = (int32_t)elem_load_byte<kSrcU8>(sp, at), g = (int32_t)elem_load_byte<kSrcU8>(sp, plane + at), rr = (int32_t)elem_load_byte<kSrcU8>(sp, 2u * plane + at);
+      yv = jpeg_luma(rr, g, b); cb = jpeg_cb(rr, g, b); cr = jpeg_cr(rr, g, b);
+    }
+    if (threadIdx.x < 128u) s_q[wave][lane] = (uint16_t)jpeg_quant(wave ? kJpegBaseChroma[lane] : kJpegBaseLuma[lane], quality);
+    // (the barriers of the first pass stand between this and the first quantiser)
+    yv = jpeg_lane_block(yv, s_q[0], xb, lx, ly, t_rx, t_ry, t_cx, t_cy);
+    if (!sub) {
+      cb = jpeg_lane_block(cb, s_q[1], xb, lx, ly, t_rx, t_ry, t_cx, t_cy);
+      cr = jpeg_lane_block(cr, s_q[1], xb, lx, ly, t_rx, t_ry, t_cx, t_cy);
+    } else {
+      s_c[0][Y * kJpegRegion + X] = (uint8_t)cb;
+      s_c[1][Y * kJpegRegion + X] = (uint8_t)cr;
+      __syncthreads();
+      const uint8_t* const cell = s_c[wave & 1] + 2 * ly * kJpegRegion + 2 * lx;  // the cell (lx, ly) of Cb (even waves) or Cr
+      const int32_t mean = jpeg_cell((int32_t)cell[0] + cell[1] + cell[kJpegRegion] + cell[kJpegRegion + 1]);
+      const int32_t dec = jpeg_lane_block(mean, s_q[1], xb, lx, ly, t_rx, t_ry, t_cx, t_cy);
+      if (wave < 2) s_d[wave][lane] = (uint8_t)dec;
+      __syncthreads();
+      cb = s_d[0][(Y >> 1) * 8 + (X >> 1)];
+      cr = s_d[1][(Y >> 1) * 8 + (X >> 1)];
+    }
+    if (inside) {
+      const int32_t o[3] = {jpeg_blue(yv, cb), jpeg_green(yv, cb, cr), jpeg_red(yv, cr)};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const size_t e = (size_t)c * plane + at;
+        if constexpr (kDstU8) dp[e] = (uint8_t)o[c];
+        else reinterpret_cast<float*>(dp)[e] = (float)o[c];
+      }
+    }
+    __syncthreads();  // (the next sample of this workgroup writes the tables and the chroma bytes again)
+  }
+}
+
 }  // namespace ofdg

@@ -272,7 +272,7 @@ static std::string err_text(uint32_t e) {
 
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
 // ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_camera, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
-// ofdg_flow_error, ofdg_lens
+// ofdg_flow_error, ofdg_lens, ofdg_jpeg
 // How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
 struct PostOp {
   ofdg_ctx* c;
@@ -294,7 +294,7 @@ struct PostOp {
 // the call sites are the instantiations that exist: 6 flow_stats_kernel, 12 flow_pyramid_kernel, 8 crop_kernel, 4 photo_kernel,
 // 8 spatial_kernel, 24 pack_kernel, 4 boundary_kernel, 2 erase_mean_kernel, 8 erase_apply_kernel, 8 mblur_kernel,
 // 4 reproject_kernel, 2 splat_scatter_kernel, 4 splat_resolve_kernel, 2 jitter_mean_kernel, 4 jitter_apply_kernel,
-// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel, 4 camera_kernel, 8 lens_kernel.
+// 2 flow_vis_max_kernel, 12 flow_vis_colour_kernel, 12 flow_error_kernel, 4 camera_kernel, 8 lens_kernel, 4 jpeg_kernel.
 template <class T, T... Vs, class F>
 static void with_constant(T v, F&& f) {
   (void)(... || (v == Vs && (f(std::integral_constant<T, Vs>{}), true)));
@@ -2166,6 +2166,36 @@ int ofdg_lens(ofdg_ctx* c, const struct ofdg_lens_job* job, int n_samples, void*
         hipLaunchKernelGGL((lens_kernel<decltype(image_u8)::value, decltype(flow_half)::value, decltype(occ_u8)::value>), g, dim3(kSpatialThreads), 0,
                            st, *j, n_samples, W, H, tiles_x);
       });
+    });
+  });
+  HIP_OK(c, hipGetLastError());
+  return OFDG_OK;
+}
+
+// Block compression of caller-given frames, in place or into other frames: one kernel on `stream` for both frames and every
+// sample.  The grid covers the block grid at its largest phase (15 on either axis).
+int ofdg_jpeg(ofdg_ctx* c, const struct ofdg_jpeg_job* job, int n_samples, void* stream) {
+  if (!c) return OFDG_EINVAL;
+  const PostOp op{c, "ofdg_jpeg"};
+  const DevJpegJob* const j = reinterpret_cast<const DevJpegJob*>(job);
+  if (!j) return op.fail("job is NULL");
+  int W = c->prm.width, H = c->prm.height;
+  if (const char* why = jpeg_plane_size(*j, &W, &H)) return op.fail(why);
+  if (const char* why = jpeg_arg_error(j, n_samples, W, H)) return op.fail(why);
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
+    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
+  }
+  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
+  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  hipStream_t st;
+  OFDG_TRY(op.stream_of(stream, &st));
+  const uint32_t tiles_x = ((uint32_t)W + 15u + kJpegRegion - 1) / kJpegRegion, tiles_y = ((uint32_t)H + 15u + kJpegRegion - 1) / kJpegRegion;
+  const dim3 g(tiles_x * tiles_y, (unsigned)std::min(n_samples, 65535), (j->src[0] ? 1u : 0u) + (j->src[1] ? 1u : 0u));
+  with_bool(j->src_fmt == OFDG_FMT_U8, [&](auto src_u8) {
+    with_bool(j->dst_fmt == OFDG_FMT_U8, [&](auto dst_u8) {
+      hipLaunchKernelGGL((jpeg_kernel<decltype(src_u8)::value, decltype(dst_u8)::value>), g, dim3(kJpegThreads), 0, st, *j, n_samples, W, H, tiles_x);
     });
   });
   HIP_OK(c, hipGetLastError());

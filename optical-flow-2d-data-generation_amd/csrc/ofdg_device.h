@@ -1750,6 +1750,189 @@ inline const char* lens_arg_error(const DevLensJob* j, int n, int width, int hei
   return nullptr;
 }
 
+// ---- Block compression (ofdg_jpeg, include/ofdg.h) -------------------------------------------------------------------------
+// What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
+// sanitising, the quantisation tables, the colour transforms, the transform table, the roundings of the four passes, the
+// quantiser and the argument rules.  Everything is 32-bit integers; >> on a negative value is arithmetic.
+struct DevJpegRec {  // ofdg_jpeg_rec, field for field
+  int32_t quality[2], subsample, phase_x, phase_y, reserved[3];
+};
+struct DevJpegJob {  // struct ofdg_jpeg_job, field for field
+  const void* src[2];
+  void* dst[2];
+  const DevJpegRec* recs;
+  DevJpegRec* recs_out;
+  long long first_index;
+  uint32_t seed;
+  int32_t width, height, src_fmt, dst_fmt, flags, subsample, quality_min, quality_max, quality_delta;
+  float prob, sub_prob;
+  int32_t reserved[2];
+};
+static_assert(sizeof(ofdg_jpeg_rec) == sizeof(DevJpegRec) && sizeof(DevJpegRec) == 32 && offsetof(ofdg_jpeg_rec, subsample) == offsetof(DevJpegRec, subsample) &&
+              offsetof(DevJpegRec, subsample) == 8 && offsetof(ofdg_jpeg_rec, phase_x) == offsetof(DevJpegRec, phase_x) && offsetof(DevJpegRec, phase_x) == 12 &&
+              offsetof(ofdg_jpeg_rec, phase_y) == offsetof(DevJpegRec, phase_y) && offsetof(ofdg_jpeg_rec, reserved) == offsetof(DevJpegRec, reserved) &&
+              offsetof(DevJpegRec, reserved) == 20 && OFDG_JPEG_PHASE == 1,
+              "ofdg_jpeg_rec: 32 bytes, the layout the kernel reads and writes as two 16-byte pieces");
+static_assert(sizeof(struct ofdg_jpeg_job) == sizeof(DevJpegJob) && sizeof(DevJpegJob) == 112 && offsetof(struct ofdg_jpeg_job, dst) == offsetof(DevJpegJob, dst) &&
+              offsetof(struct ofdg_jpeg_job, recs) == offsetof(DevJpegJob, recs) && offsetof(struct ofdg_jpeg_job, recs_out) == offsetof(DevJpegJob, recs_out) &&
+              offsetof(struct ofdg_jpeg_job, first_index) == offsetof(DevJpegJob, first_index) && offsetof(struct ofdg_jpeg_job, seed) == offsetof(DevJpegJob, seed) &&
+              offsetof(DevJpegJob, seed) == 56 && offsetof(struct ofdg_jpeg_job, width) == offsetof(DevJpegJob, width) &&
+              offsetof(struct ofdg_jpeg_job, src_fmt) == offsetof(DevJpegJob, src_fmt) && offsetof(struct ofdg_jpeg_job, flags) == offsetof(DevJpegJob, flags) &&
+              offsetof(struct ofdg_jpeg_job, subsample) == offsetof(DevJpegJob, subsample) && offsetof(DevJpegJob, subsample) == 80 &&
+              offsetof(struct ofdg_jpeg_job, quality_min) == offsetof(DevJpegJob, quality_min) && offsetof(struct ofdg_jpeg_job, quality_delta) == offsetof(DevJpegJob, quality_delta) &&
+              offsetof(DevJpegJob, quality_delta) == 92 && offsetof(struct ofdg_jpeg_job, prob) == offsetof(DevJpegJob, prob) &&
+              offsetof(struct ofdg_jpeg_job, sub_prob) == offsetof(DevJpegJob, sub_prob) && offsetof(struct ofdg_jpeg_job, reserved) == offsetof(DevJpegJob, reserved) &&
+              offsetof(DevJpegJob, reserved) == 104,
+              "struct ofdg_jpeg_job: 112 bytes, the layout the kernel takes");
+// T.81 Annex K, Table K.1 (luminance) and Table K.2 (chrominance), row-major [v][u]
+constexpr uint8_t kJpegBaseLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
+                                       14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                       49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+constexpr uint8_t kJpegBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                         99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+// T[u][x] = lrint(4096 s(u) cos((2 x + 1) u pi / 16)), s(0) = 1 / sqrt 2, else 1: 8192 times the orthonormal DCT-II matrix
+constexpr int32_t kJpegT[64] = {2896, 2896,  2896,  2896,  2896,  2896,  2896,  2896,  4017, 3406,  2276,  799,   -799,  -2276, -3406, -4017,
+                                3784, 1567,  -1567, -3784, -3784, -1567, 1567,  3784,  3406, -799,  -4017, -2276, 2276,  4017,  799,   -3406,
+                                2896, -2896, -2896, 2896,  2896,  -2896, -2896, 2896,  2276, -4017, 799,   3406,  -3406, -799,  4017,  -2276,
+                                1567, -3784, 3784,  -1567, -1567, 3784,  -3784, 1567,  799,  -2276, 3406,  -4017, 4017,  -3406, 2276,  -799};
+// The record of global sample g: Philox blocks 0 and 1 under the sampler's key of g at the counters {j, 0, 0x0c7b, 0}.  `j`
+// supplies the ranges, subsample and flags (jpeg_ranges_error has passed).  Not sanitised.
+OFDG_HD_FN DevJpegRec jpeg_draw_rec(uint32_t seed, unsigned long long g, const DevJpegJob& j) {
+  const uint32_t k0 = seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
+  const CropWords a = crop_philox(CropWords{0u, 0u, 0x0c7bu, 0u}, k0, k1);
+  const CropWords b = crop_philox(CropWords{1u, 0u, 0x0c7bu, 0u}, k0, k1);
+  const bool on = photo_unit(a.x) < j.prob;
+  const int32_t q0 = j.quality_min + (int32_t)(uint32_t)(((unsigned long long)a.y * (uint32_t)(j.quality_max - j.quality_min + 1)) >> 32);
+  const int32_t q1 = jitter_clamp(q0 + jitter_isym(a.z, j.quality_delta), 1, 100);
+  const bool phase = (j.flags & OFDG_JPEG_PHASE) != 0;
+  DevJpegRec r;
+  r.quality[0] = on ? q0 : 0; r.quality[1] = on ? q1 : 0;
+  r.subsample = j.subsample >= 0 ? j.subsample : (photo_unit(a.w) < j.sub_prob ? 1 : 0);
+  r.phase_x = phase ? (int32_t)(b.x >> 28) : 0; r.phase_y = phase ? (int32_t)(b.y >> 28) : 0;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+// What is used of a record, given or drawn.  No record makes the kernel touch a byte outside a plane.
+OFDG_HD_FN DevJpegRec jpeg_sanitise(DevJpegRec r) {
+  r.quality[0] = jitter_clamp(r.quality[0], 0, 100); r.quality[1] = jitter_clamp(r.quality[1], 0, 100);
+  r.subsample = r.subsample == 1 ? 1 : 0;
+  r.phase_x = (r.phase_x < 0 || r.phase_x > 15) ? 0 : r.phase_x;
+  r.phase_y = (r.phase_y < 0 || r.phase_y > 15) ? 0 : r.phase_y;
+  r.reserved[0] = 0; r.reserved[1] = 0; r.reserved[2] = 0;
+  return r;
+}
+// the side of an MCU and the phase that counts: 4:4:4 uses phase & 7
+OFDG_HD_FN int jpeg_mcu(int subsample) { return subsample ? 16 : 8; }
+OFDG_HD_FN int jpeg_phase(int phase, int subsample) { return subsample ? phase : phase & 7; }
+// libjpeg's table entry of a quality in 1..100
+OFDG_HD_FN uint32_t jpeg_quant(uint32_t base, int quality) {
+  const uint32_t scale = quality < 50 ? 5000u / (uint32_t)quality : 200u - 2u * (uint32_t)quality;
+  const uint32_t q = (base * scale + 50u) / 100u;
+  return q < 1u ? 1u : q > 255u ? 255u : q;
+}
+// libjpeg's 16-bit colour constants, there and back; the results of the first three are bytes by construction
+OFDG_HD_FN int32_t jpeg_luma(int32_t r, int32_t g, int32_t b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+OFDG_HD_FN int32_t jpeg_cb(int32_t r, int32_t g, int32_t b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
+OFDG_HD_FN int32_t jpeg_cr(int32_t r, int32_t g, int32_t b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+OFDG_HD_FN int32_t jpeg_byte(int32_t v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+OFDG_HD_FN int32_t jpeg_red(int32_t y, int32_t cr) { return jpeg_byte(y + ((91881 * (cr - 128) + 32768) >> 16)); }
+OFDG_HD_FN int32_t jpeg_green(int32_t y, int32_t cb, int32_t cr) { return jpeg_byte(y + ((-22554 * (cb - 128) - 46802 * (cr - 128) + 32768) >> 16)); }
+OFDG_HD_FN int32_t jpeg_blue(int32_t y, int32_t cb) { return jpeg_byte(y + ((116130 * (cb - 128) + 32768) >> 16)); }
+// the mean of the four samples of a chroma cell
+OFDG_HD_FN int32_t jpeg_cell(int32_t s4) { return (s4 + 2) >> 2; }
+// the roundings: behind a first pass (forward and inverse), the quantiser and what it hands on, the byte behind the last pass
+OFDG_HD_FN int32_t jpeg_round9(int32_t a) { return (a + 256) >> 9; }
+OFDG_HD_FN int32_t jpeg_level(int32_t F, uint32_t Q) {
+  const uint32_t m = ((uint32_t)(F < 0 ? -F : F) + Q * 65536u) / (Q * 131072u);
+  return F < 0 ? -(int32_t)m : (int32_t)m;
+}
+OFDG_HD_FN int32_t jpeg_sample(int32_t P) { return jpeg_byte(((P + 65536) >> 17) + 128); }
+// Steps 4-6 of one block the plain way (the host twin's; the kernel runs the same passes a lane an element): in, q, levels and
+// out are row-major [8][8].
+inline void jpeg_block(const uint8_t* in, const uint16_t* q, int32_t* levels, uint8_t* out) {
+  int32_t a[64], d[64];
+  for (int y = 0; y < 8; ++y)
+    for (int u = 0; u < 8; ++u) {
+      int32_t s = 0;
+      for (int x = 0; x < 8; ++x) s += kJpegT[u * 8 + x] * ((int32_t)in[y * 8 + x] - 128);
+      a[y * 8 + u] = jpeg_round9(s);
+    }
+  for (int v = 0; v < 8; ++v)
+    for (int u = 0; u < 8; ++u) {
+      int32_t s = 0;
+      for (int y = 0; y < 8; ++y) s += kJpegT[v * 8 + y] * a[y * 8 + u];
+      const int32_t level = jpeg_level(s, q[v * 8 + u]);
+      if (levels) levels[v * 8 + u] = level;
+      d[v * 8 + u] = level * (int32_t)q[v * 8 + u];
+    }
+  for (int y = 0; y < 8; ++y)
+    for (int u = 0; u < 8; ++u) {
+      int32_t s = 0;
+      for (int v = 0; v < 8; ++v) s += kJpegT[v * 8 + y] * d[v * 8 + u];
+      a[y * 8 + u] = jpeg_round9(s);
+    }
+  for (int y = 0; y < 8; ++y)
+    for (int x = 0; x < 8; ++x) {
+      int32_t s = 0;
+      for (int u = 0; u < 8; ++u) s += kJpegT[u * 8 + x] * a[y * 8 + u];
+      out[y * 8 + x] = (uint8_t)jpeg_sample(s);
+    }
+}
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+inline const char* jpeg_plane_size(const DevJpegJob& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The ranges of the draw, subsample and flags: the first rule broken, or nullptr.
+inline const char* jpeg_ranges_error(const DevJpegJob& j) {
+  if (j.flags != 0 && j.flags != OFDG_JPEG_PHASE) return "flags must be 0 or OFDG_JPEG_PHASE";
+  if (j.quality_min < 1 || j.quality_min > 100) return "quality_min must lie in 1..100";
+  if (j.quality_max < 1 || j.quality_max > 100) return "quality_max must lie in 1..100";
+  if (j.quality_min > j.quality_max) return "quality_min must not be above quality_max";
+  if (j.quality_delta < 0 || j.quality_delta > 99) return "quality_delta must lie in 0..99";
+  if (!(j.prob >= 0.0f && j.prob <= 1.0f)) return "prob must lie in [0, 1]";
+  if (!(j.sub_prob >= 0.0f && j.sub_prob <= 1.0f)) return "sub_prob must lie in [0, 1]";
+  if (j.subsample < -1 || j.subsample > 1) return "subsample must lie in -1..1";
+  return nullptr;
+}
+// The argument rules ofdg_jpeg and ofdg_host_jpeg share: the first rule broken, or nullptr.  width, height: what
+// jpeg_plane_size gave.  Alignment is asked by the device entry only.
+inline const char* jpeg_arg_error(const DevJpegJob* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
+  if (const char* why = jpeg_ranges_error(*j)) return why;
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
+    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
+    frames += j->src[f] ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  // a written range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
+  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
+  Range r[6];
+  int nr = 0;
+  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
+    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
+    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
+    nr += 2;
+  }
+  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevJpegRec), false, -1};
+  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevJpegRec), true, -1};
+  for (int a = 0; a < nr; ++a)
+    for (int b = 0; b < nr; ++b)
+      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
+  return nullptr;
+}
+
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
 // sanitising, the half-displacement, the tap count and step, the tap value, the mean and the argument rules.  Compiled

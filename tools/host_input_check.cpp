@@ -29,6 +29,9 @@
 //   host_input_check lens               ofdg_host_lens and ofdg_lens_draw on exactly sized heap buffers: the test sizes, every
 //                                       format triple, one frame and both, every record case and hostile given records (NaN,
 //                                       infinities, beyond every limit), drawn ones, flows of any bit pattern, every refusal
+//   host_input_check jpeg               ofdg_host_jpeg, ofdg_jpeg_draw, ofdg_jpeg_tables and ofdg_host_jpeg_block on exactly sized heap
+//                                       buffers: the five test sizes, every format pair, copying and in place, both subsamplings,
+//                                       phases 0 and 15, hostile given records, drawn ones, every table, every refusal
 //   host_input_check flow_vis           ofdg_host_flow_vis and ofdg_host_flow_vis_tables on exactly sized heap buffers: the test
 //                                       sizes, both flow formats and layouts, the three norms and both ends of max_flow, with
 //                                       and without dimming, extreme flows and any bit pattern, every refusal
@@ -902,6 +905,165 @@ int camera() {
   return refused == 27 ? 0 : 1;
 }
 
+// ofdg_host_jpeg, ofdg_jpeg_draw, ofdg_jpeg_tables and ofdg_host_jpeg_block on heap buffers of exactly the planes' sizes (a byte
+// read or written beside one is a report - the clamped coordinates of the partial MCUs at every edge of 8x2, 24x10, 40x26, 72x34
+// and 136x18): the four format pairs, copying and in place, both subsamplings, the phases 0 and 15, given records whose fields
+// each walk INT_MIN / INT_MAX (a signed overflow in the clamp is a report), drawn records at the widest ranges; float32 frames of
+// arbitrary bit patterns; every table into 64 exact entries; the extreme blocks (a signed overflow in a pass is a report); then
+// every refusal.
+int jpeg() {
+  const int32_t hostile[] = {INT32_MIN, INT32_MIN + 1, -101, -16, -2, -1, 0, 1, 2, 7, 8, 15, 16, 50, 100, 101, 65536, INT32_MAX - 1, INT32_MAX};
+  const int n_hostile = (int)(sizeof hostile / sizeof hostile[0]);
+  const int sizes[5][2] = {{8, 2}, {24, 10}, {40, 26}, {72, 34}, {136, 18}};
+  unsigned long long sum = 0;
+  int calls = 0;
+  for (int size = 0; size < 5; ++size) {
+    const int W = sizes[size][0], H = sizes[size][1], n = 16;
+    const size_t px = (size_t)W * H;
+    for (int fmts = 0; fmts < 4; ++fmts) {
+      const int sf = fmts & 1 ? OFDG_FMT_U8 : OFDG_FMT_F32, df = fmts & 2 ? OFDG_FMT_U8 : OFDG_FMT_F32;
+      const size_t sb = n * 3 * px * (sf == OFDG_FMT_U8 ? 1 : 4), db = n * 3 * px * (df == OFDG_FMT_U8 ? 1 : 4);
+      std::vector<uint8_t> src[2], dst[2];
+      uint32_t x = 977u + (uint32_t)fmts;
+      for (int f = 0; f < 2; ++f) {
+        src[f].resize(sb); dst[f].assign(db, 0xA5);
+        for (size_t e = 0; e < n * 3 * px; ++e) {
+          x = x * 1664525u + 1013904223u;
+          if (sf == OFDG_FMT_U8) { src[f][e] = (e % 7) == 0 ? (uint8_t)(e % 3 ? 255 : 0) : (uint8_t)(x >> 24); continue; }
+          const float v = (float)(x >> 24) + ((e % 5) == 0 ? 0.5f : 0.0f);
+          const uint32_t bits = x ^ (x << 13);  // (every third element: any bit pattern)
+          std::memcpy(src[f].data() + 4 * e, (e % 3) == 0 ? (const void*)&bits : (const void*)&v, 4);
+        }
+      }
+      // records 0..7: subsampling x phase 0 / 15 x two qualities; 8..15: every field walks the hostile values
+      std::vector<ofdg_jpeg_rec> recs(n), used(n);
+      for (int i = 0; i < n; ++i) {
+        ofdg_jpeg_rec& r = recs[i];
+        std::memset(&r, 0x5A, sizeof r);
+        if (i < 8) {
+          r.quality[0] = i & 4 ? 100 : 1; r.quality[1] = i & 4 ? 0 : 50;
+          r.subsample = i & 1; r.phase_x = i & 2 ? 15 : 0; r.phase_y = i & 2 ? 15 : 0;
+          continue;
+        }
+        const int k = (i - 8) * 5 + fmts + 3 * size;
+        r.quality[0] = hostile[k % n_hostile]; r.quality[1] = hostile[(k + 7) % n_hostile]; r.subsample = hostile[(k + 11) % n_hostile];
+        r.phase_x = hostile[(k + 1) % n_hostile]; r.phase_y = hostile[(k + 2) % n_hostile];
+      }
+      for (int drawn = 0; drawn < 2; ++drawn)
+        for (int frames = 1; frames < 4; ++frames)
+          for (int in_place = 0; in_place < (sf == df ? 2 : 1); ++in_place) {
+            std::vector<uint8_t> own[2] = {src[0], src[1]};  // (the in-place form writes its sources: a copy a call)
+            struct ofdg_jpeg_job job;
+            std::memset(&job, 0, sizeof job);
+            for (int f = 0; f < 2; ++f)
+              if ((frames >> f) & 1) { job.src[f] = own[f].data(); job.dst[f] = in_place ? own[f].data() : dst[f].data(); }
+            job.recs = drawn ? nullptr : recs.data();
+            job.recs_out = used.data();
+            job.first_index = (1ll << 32) - 1; job.seed = 7;
+            job.src_fmt = sf; job.dst_fmt = df; job.flags = OFDG_JPEG_PHASE;
+            job.subsample = -1; job.quality_min = 1; job.quality_max = 100; job.quality_delta = 99; job.prob = 0.9f; job.sub_prob = 0.5f;
+            const int rc = ofdg_host_jpeg(&job, n, W, H);
+            if (rc) { std::printf("jpeg: rc=%d %s\n", rc, ofdg_host_last_error()); return 1; }
+            ++calls;
+            for (int f = 0; f < 2; ++f)
+              if ((frames >> f) & 1) sum = sum * 31 + (in_place ? fnv1a(own[f].data(), own[f].size()) : fnv1a(dst[f].data(), dst[f].size()));
+            sum = sum * 31 + fnv1a((const uint8_t*)used.data(), used.size() * sizeof(ofdg_jpeg_rec));
+            for (int i = 0; i < n; ++i)
+              if (used[i].quality[0] < 0 || used[i].quality[0] > 100 || used[i].quality[1] < 0 || used[i].quality[1] > 100 || used[i].subsample < 0 || used[i].subsample > 1 ||
+                  used[i].phase_x < 0 || used[i].phase_x > 15 || used[i].phase_y < 0 || used[i].phase_y > 15 || used[i].reserved[0] != 0 || used[i].reserved[1] != 0 ||
+                  used[i].reserved[2] != 0) { std::printf("jpeg: a record left its bounds\n"); return 1; }
+          }
+    }
+  }
+  for (int q = 1; q <= 100; ++q) {  // every table, into buffers of exactly 64 entries; the extreme blocks under each
+    std::vector<uint16_t> luma(64, 0xA5A5), chroma(64, 0xA5A5);
+    if (ofdg_jpeg_tables(q, luma.data(), chroma.data()) != OFDG_OK) { std::printf("jpeg: the tables call failed\n"); return 1; }
+    for (int k = 0; k < 64; ++k)
+      if (luma[k] < 1 || luma[k] > 255 || chroma[k] < 1 || chroma[k] > 255) { std::printf("jpeg: a table entry of quality %d left 1..255\n", q); return 1; }
+    for (int kind = 0; kind < 6; ++kind) {
+      std::vector<uint8_t> in(64), out(64, 0xA5);
+      std::vector<int32_t> levels(64);
+      for (int k = 0; k < 64; ++k) {
+        const int bx = k & 7, by = k >> 3;
+        in[k] = kind == 0 ? 0 : kind == 1 ? 255 : kind == 2 ? (uint8_t)(((bx + by) & 1) * 255) : kind == 3 ? (uint8_t)((bx & 1) * 255) : kind == 4 ? (uint8_t)((by >= 4) * 255) : (uint8_t)(k * 4);
+      }
+      if (ofdg_host_jpeg_block(in.data(), kind & 1 ? chroma.data() : luma.data(), kind & 2 ? nullptr : levels.data(), out.data()) != OFDG_OK) { std::printf("jpeg: the block call failed\n"); return 1; }
+      sum = sum * 31 + fnv1a(out.data(), 64);
+      ++calls;
+    }
+    sum = sum * 31 + fnv1a((const uint8_t*)luma.data(), 128) + fnv1a((const uint8_t*)chroma.data(), 128);
+  }
+  // the refusals: nothing is written
+  int refused = 0;
+  {
+    const int W = 16, H = 4, n = 2;
+    std::vector<uint8_t> src((size_t)n * 3 * W * H * 4, 0), dst((size_t)n * 3 * W * H * 4 + 64, 0xA5), out((size_t)n * 32, 0xA5);
+    struct ofdg_jpeg_job good;
+    std::memset(&good, 0, sizeof good);
+    good.src[0] = src.data(); good.dst[0] = dst.data(); good.recs_out = (ofdg_jpeg_rec*)out.data();
+    good.subsample = -1; good.quality_min = 30; good.quality_max = 95; good.quality_delta = 5; good.prob = 0.5f; good.sub_prob = 0.5f; good.flags = OFDG_JPEG_PHASE;
+    const auto refuse = [&](struct ofdg_jpeg_job j, int ns, int w, int h) {
+      if (ofdg_host_jpeg(&j, ns, w, h) == OFDG_EINVAL && std::strncmp(ofdg_host_last_error(), "ofdg_host_jpeg: ", 16) == 0) ++refused;
+      else std::printf("jpeg: a bad job was not refused (%s)\n", ofdg_host_last_error());
+    };
+    struct ofdg_jpeg_job j;
+    if (ofdg_host_jpeg(nullptr, n, W, H) == OFDG_EINVAL) ++refused;
+    refuse(good, 0, W, H); refuse(good, n, 12, H); refuse(good, n, W, 3); refuse(good, 1, 65536, 21846);
+    j = good; j.width = W; refuse(j, n, W, H);
+    j = good; j.width = W + 8; j.height = H; refuse(j, n, W, H);
+    j = good; j.src_fmt = OFDG_FMT_F16; refuse(j, n, W, H);
+    j = good; j.dst_fmt = 9; refuse(j, n, W, H);
+    j = good; j.flags = 2; refuse(j, n, W, H);
+    j = good; j.flags = INT32_MIN; refuse(j, n, W, H);
+    j = good; j.reserved[0] = 1; refuse(j, n, W, H);
+    j = good; j.reserved[1] = 1; refuse(j, n, W, H);
+    j = good; j.quality_min = 0; refuse(j, n, W, H);
+    j = good; j.quality_min = INT32_MIN; refuse(j, n, W, H);
+    j = good; j.quality_max = 101; refuse(j, n, W, H);
+    j = good; j.quality_max = INT32_MAX; refuse(j, n, W, H);
+    j = good; j.quality_min = 96; refuse(j, n, W, H);
+    j = good; j.quality_delta = -1; refuse(j, n, W, H);
+    j = good; j.quality_delta = 100; refuse(j, n, W, H);
+    j = good; j.prob = NAN; refuse(j, n, W, H);
+    j = good; j.prob = 1.5f; refuse(j, n, W, H);
+    j = good; j.sub_prob = INFINITY; refuse(j, n, W, H);
+    j = good; j.sub_prob = -0.5f; refuse(j, n, W, H);
+    j = good; j.subsample = 2; refuse(j, n, W, H);
+    j = good; j.subsample = -2; refuse(j, n, W, H);
+    j = good; j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.src[1] = nullptr; j.dst[1] = dst.data(); j.src[0] = nullptr; j.dst[0] = nullptr; refuse(j, n, W, H);
+    j = good; j.dst[0] = src.data() + 16; refuse(j, n, W, H);                         // a partial overlap
+    j = good; j.dst[0] = src.data(); j.dst_fmt = OFDG_FMT_U8; refuse(j, n, W, H);     // in place, in another format
+    j = good; j.recs_out = (ofdg_jpeg_rec*)(dst.data() + 16); refuse(j, n, W, H);
+    ofdg_jpeg_rec rec;
+    std::memset(&rec, 0xA5, sizeof rec);
+    j = good; j.quality_delta = 100;
+    if (ofdg_jpeg_draw(1, 0, &j, &rec) == OFDG_EINVAL && ofdg_jpeg_draw(1, 0, nullptr, &rec) == OFDG_EINVAL && ofdg_jpeg_draw(1, 0, &good, nullptr) == OFDG_EINVAL) ++refused;
+    uint16_t t[64], bad_q[64];
+    uint8_t blk[64] = {}, blk_out[64];
+    std::memset(t, 0xA5, sizeof t);
+    std::memset(blk_out, 0xA5, sizeof blk_out);
+    for (int k = 0; k < 64; ++k) bad_q[k] = k == 63 ? 256 : 1;
+    if (ofdg_jpeg_tables(0, t, t) == OFDG_EINVAL && ofdg_jpeg_tables(101, t, t) == OFDG_EINVAL && ofdg_jpeg_tables(INT32_MIN, t, t) == OFDG_EINVAL && ofdg_jpeg_tables(50, nullptr, t) == OFDG_EINVAL &&
+        ofdg_jpeg_tables(50, t, nullptr) == OFDG_EINVAL) ++refused;
+    if (ofdg_host_jpeg_block(blk, bad_q, nullptr, blk_out) == OFDG_EINVAL && ofdg_host_jpeg_block(nullptr, bad_q, nullptr, blk_out) == OFDG_EINVAL &&
+        ofdg_host_jpeg_block(blk, nullptr, nullptr, blk_out) == OFDG_EINVAL && ofdg_host_jpeg_block(blk, bad_q, nullptr, nullptr) == OFDG_EINVAL) ++refused;
+    bad_q[63] = 0;
+    if (ofdg_host_jpeg_block(blk, bad_q, nullptr, blk_out) == OFDG_EINVAL) ++refused;
+    const bool clean = std::all_of(dst.begin(), dst.end(), [](uint8_t b) { return b == 0xA5; }) && std::all_of(out.begin(), out.end(), [](uint8_t b) { return b == 0xA5; }) &&
+                       ((const uint8_t*)&rec)[0] == 0xA5 && ((const uint8_t*)&rec)[31] == 0xA5 && t[0] == 0xA5A5 && t[63] == 0xA5A5 && blk_out[0] == 0xA5 && blk_out[63] == 0xA5;
+    if (!clean) { std::printf("jpeg: a refusal wrote something\n"); return 1; }
+    j = good; j.dst[0] = src.data();  // in place in one format: accepted
+    if (ofdg_jpeg_draw(1, (1ll << 32) + 3, &good, &rec) != OFDG_OK || ofdg_host_jpeg(&good, n, W, H) != OFDG_OK || ofdg_host_jpeg(&j, n, W, H) != OFDG_OK) {
+      std::printf("jpeg: a valid call failed (%s)\n", ofdg_host_last_error());
+      return 1;
+    }
+  }
+  std::printf("jpeg calls=%d refused=%d sum=%016llx\n", calls, refused, sum);
+  return refused == 36 ? 0 : 1;
+}
+
 // ofdg_host_lens and ofdg_lens_draw on heap buffers of exactly the planes' sizes (a byte read or written beside one is a report -
 // the clamped taps at every edge of 8x2, 24x10, 72x34 and 136x18): every format triple, all eight planes and each frame alone,
 // given records that hold the identity, both signs of k1 at its bound, off-centre centres at their bound, fringes and a
@@ -1278,10 +1440,11 @@ int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "jitter") == 0) return jitter();
   if (argc >= 2 && std::strcmp(argv[1], "camera") == 0) return camera();
   if (argc >= 2 && std::strcmp(argv[1], "lens") == 0) return lens();
+  if (argc >= 2 && std::strcmp(argv[1], "jpeg") == 0) return jpeg();
   if (argc >= 2 && std::strcmp(argv[1], "flow_vis") == 0) return flow_vis();
   if (argc >= 2 && std::strcmp(argv[1], "flow_error") == 0) return flow_error();
   if (argc >= 3 && std::strcmp(argv[1], "check") == 0) return check(argv[2]);
   if (argc >= 3 && std::strcmp(argv[1], "mutate") == 0) return mutate(argv[2], argc > 3 && std::strcmp(argv[3], "-v") == 0);
-  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | camera | lens | flow_vis | flow_error\n", argv[0]);
+  std::fprintf(stderr, "usage: %s check <dir> | mutate <dir> [-v] | planes | mblur | reproject | splat | jitter | camera | lens | jpeg | flow_vis | flow_error\n", argv[0]);
   return 2;
 }
