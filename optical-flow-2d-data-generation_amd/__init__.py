@@ -435,6 +435,115 @@ def _host_check(rc):
         raise OfdgError(rc, lib().ofdg_host_last_error().decode())
 
 
+# What the operations with records share: everything below reads the record table (_RECORDS, behind the last operation's
+# classes), one entry per operation.
+def _ranges_into(op, job, ranges):
+    """The ranges of a dict (None: none) into the fields of a job, by the table's (name, int / float, missing-value default); the
+    table's `flags` are names the dict may hold besides that are no field.  Raises for any other name.  Returns the dict."""
+    r, ranges = _RECORDS[op], {} if ranges is None else ranges
+    for key in ranges:
+        if key not in r.flags and not any(key == name for name, _, _ in r.ranges):
+            known = ", ".join(name for name, _, _ in r.ranges)
+            raise ValueError("unknown range %r (known: %s)" % (key, r.says % known if r.says else ", ".join((known,) + r.flags)))
+    for name, kind, default in r.ranges:
+        setattr(job, name, kind(ranges.get(name, default)))
+    return ranges
+
+
+def _rec_dtype(op):
+    """the numpy structured dtype of an operation's record"""
+    import numpy as np
+    return np.dtype(_RECORDS[op].fields)
+
+
+def _rec_numpy(op, recs):
+    """X_numpy: a torch tensor or numpy array of whole records as the structured array [n]"""
+    import numpy as np
+    dtype = _rec_dtype(op)
+    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
+    a = np.ascontiguousarray(a)
+    if a.dtype == dtype:
+        return a
+    raw = a.view(np.uint8).reshape(-1)
+    if raw.size % dtype.itemsize:
+        raise ValueError("records must be %d bytes each, got %d bytes" % (dtype.itemsize, raw.size))
+    return raw.view(dtype)
+
+
+def _rec_given(op, recs, n):
+    """recs= of a host twin, not None: the n records as the array the C entry reads - the structured array where X_numpy
+    makes one (a copy), else rows of the table's dtype and width; raises ValueError for anything else"""
+    import numpy as np
+    r = _RECORDS[op]
+    if r.structured:
+        recs = _rec_numpy(op, recs).copy()
+        if recs.shape != (n,):
+            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
+    else:
+        recs = np.ascontiguousarray(recs)
+        if recs.dtype != np.dtype(r.dtype) or recs.shape != (n, r.width):
+            raise ValueError("recs must be %s [%d,%s], got %s %s" % (r.dtype, n, r.width, recs.dtype, recs.shape))
+    return recs
+
+
+def _rec_new(op, n):
+    """the zeroed host array a twin writes the records it used to"""
+    import numpy as np
+    r = _RECORDS[op]
+    return np.zeros((n,), _rec_dtype(op)) if r.structured else np.zeros((n, r.width), np.dtype(r.dtype))
+
+
+def _rec_alloc(op, n, device="cuda"):
+    """the device tensor [n, row width] of an operation's records (recs_out); not filled: the call writes every record"""
+    import torch
+    r = _RECORDS[op]
+    return torch.empty((n, r.width), dtype=getattr(torch, r.dtype), device=device)
+
+
+def _rec_draw(op, seed, index, job, *size):
+    """ofdg_X_draw of a job whose ranges are set (size: width, height where the entry takes them): the record's bytes"""
+    r = _RECORDS[op]
+    out = r.rec()
+    _host_check(getattr(lib(), r.draw)(int(seed) & 0xFFFFFFFF, int(index), *size, C.byref(job), C.byref(out)))
+    return bytearray(out)
+
+
+def _frame_pair_job(job, src, dst, ptr, codes, size, recs, recs_out, first_index, seed, work=None):
+    """the frames, records and formats of a photo / jitter / camera / jpeg job whose ranges are set; `work` where the job has it"""
+    for f in range(2):
+        if src[f] is not None:
+            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
+    job.recs, job.recs_out = recs, recs_out
+    if hasattr(job, "work"):
+        job.work = work
+    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
+    job.height, job.width = size
+    job.src_fmt, job.dst_fmt = codes
+    return job
+
+
+def _host_frame_pair(op, src, recs, dst_dtype, in_place, make_job):
+    """What host_photo, host_jitter, host_camera and host_jpeg share: contiguous sources, the destinations (the sources themselves
+    when in_place), photo_format, the given records, the job - make_job(src, dst, ptr, codes, size, recs, recs_out) - and the
+    call of the operation's host entry.  Returns (dst, records used)."""
+    import numpy as np
+    src = tuple(src)
+    if not in_place:
+        src = tuple(None if t is None else np.ascontiguousarray(t) for t in src)
+    present = [t for t in src if t is not None]
+    dt = np.dtype(present[0].dtype if dst_dtype is None and present else dst_dtype)
+    dst = src if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in src)
+    n, height, width, *codes = photo_format(src, dst)
+    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in present)):
+        raise ValueError("in_place needs contiguous sources of dst_dtype")
+    if recs is not None:
+        recs = _rec_given(op, recs, n)
+    used = _rec_new(op, n)
+    job = make_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data)
+    _host_check(getattr(lib(), _RECORDS[op].host)(C.byref(job), n, width, height))
+    return dst, used
+
+
 def crop_draw(seed, index, width, height, crop_w, crop_h, hflip=False, vflip=False):
     """ofdg_crop_draw (pure, no GPU): the window (x0, y0, flags) of global sample `index` under `seed`; flags holds CROP_HFLIP /
     CROP_VFLIP, drawn only when hflip / vflip allow them."""
@@ -479,12 +588,7 @@ class PhotoJob(C.Structure):
 
 
 def _photo_ranges(job, ranges):
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in PHOTO_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(PHOTO_RANGES)))
-    for key in PHOTO_RANGES:
-        setattr(job, key, float(ranges.get(key, 0.0)))
+    _ranges_into("photo", job, ranges)
     return job
 
 
@@ -513,25 +617,14 @@ def photo_format(src, dst, height=None, width=None):
 
 
 def _photo_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
-    job = _photo_ranges(PhotoJob(), ranges)
-    for f in range(2):
-        if src[f] is not None:
-            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
-    job.recs, job.recs_out = recs, recs_out
-    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
-    job.height, job.width = size
-    job.src_fmt, job.dst_fmt = codes
-    return job
+    return _frame_pair_job(_photo_ranges(PhotoJob(), ranges), src, dst, ptr, codes, size, recs, recs_out, first_index, seed)
 
 
 def photo_draw(seed, index, ranges=None):
     """ofdg_photo_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (PHOTO_RANGES; a
     missing one is 0), before sanitising, as float32 [16] (PHOTO_REC_FLOATS)."""
     import numpy as np
-    out = np.zeros((PHOTO_REC_FLOATS,), np.float32)
-    job = _photo_ranges(PhotoJob(), ranges)
-    _host_check(lib().ofdg_photo_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), _hptr(out)))
-    return out
+    return np.frombuffer(_rec_draw("photo", seed, index, _photo_ranges(PhotoJob(), ranges)), np.float32).copy()
 
 
 def host_det_log(x):
@@ -559,25 +652,7 @@ def host_photo(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=Non
     / np.uint8, default the source's.  in_place: the sources themselves are written (they must be contiguous and of dst_dtype).
     Returns ((image0, image1), recs_used): the augmented arrays (None for an absent frame) and the float32 [n,16] records after
     sanitising."""
-    import numpy as np
-    src = tuple(src)
-    if not in_place:
-        src = tuple(None if t is None else np.ascontiguousarray(t) for t in src)
-    given = [t for t in src if t is not None]
-    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
-    dst = src if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in src)
-    n, height, width, *codes = photo_format(src, dst)
-    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
-        raise ValueError("in_place needs contiguous sources of dst_dtype")
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.float32 or recs.shape != (n, PHOTO_REC_FLOATS):
-            raise ValueError("recs must be float32 [%d,%d], got %s %s" % (n, PHOTO_REC_FLOATS, recs.dtype, recs.shape))
-    used = np.zeros((n, PHOTO_REC_FLOATS), np.float32)
-    job = _photo_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
-                     first_index, seed, ranges)
-    _host_check(lib().ofdg_host_photo(C.byref(job), n, width, height))
-    return dst, used
+    return _host_frame_pair("photo", src, recs, dst_dtype, in_place, lambda *planes: _photo_job(*planes, first_index, seed, ranges))
 
 
 # the spatial augmentation (ofdg_spatial_rec / struct ofdg_spatial_job / ofdg_spatial, include/ofdg.h)
@@ -606,12 +681,7 @@ class SpatialJob(C.Structure):
 
 
 def _spatial_ranges(job, ranges):
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in SPATIAL_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(SPATIAL_RANGES)))
-    for key in SPATIAL_RANGES:
-        setattr(job, key, float(ranges.get(key, 0.0)))
+    _ranges_into("spatial", job, ranges)
     return job
 
 
@@ -649,11 +719,9 @@ def spatial_draw(seed, index, width, height, out_w, out_h, ranges=None, hflip=Fa
     out_w x out_h window and a dict of ranges (SPATIAL_RANGES; a missing one is 0), before sanitising, as float64 [14]
     (SPATIAL_REC_DOUBLES: the maps of frame 0 and frame 1, a b c d e g each, then the reserved bytes)."""
     import numpy as np
-    out = np.zeros((SPATIAL_REC_DOUBLES,), np.float64)
     job = _spatial_ranges(SpatialJob(), ranges)
     job.width, job.height, job.out_w, job.out_h, job.flags = int(width), int(height), int(out_w), int(out_h), _spatial_flags(hflip, vflip, False)
-    _host_check(lib().ofdg_spatial_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), _hptr(out)))
-    return out
+    return np.frombuffer(_rec_draw("spatial", seed, index, job), np.float64).copy()
 
 
 def alloc_spatial(src, out_h, out_w, zero=True):
@@ -673,11 +741,8 @@ def host_spatial(src, out_h, out_w, recs=None, first_index=0, seed=0, ranges=Non
     height, width = next(iter(src.values())).shape[-2:]
     dst = alloc_spatial(src, out_h, out_w)
     n, out_h, out_w, *codes = spatial_format(src, dst, height, width)
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.float64 or recs.shape != (n, SPATIAL_REC_DOUBLES):
-            raise ValueError("recs must be float64 [%d,%d], got %s %s" % (n, SPATIAL_REC_DOUBLES, recs.dtype, recs.shape))
-    used = np.zeros((n, SPATIAL_REC_DOUBLES), np.float64)
+    recs = None if recs is None else _rec_given("spatial", recs, n)
+    used = _rec_new("spatial", n)
     job = _spatial_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), out_h, out_w, None if recs is None else recs.ctypes.data,
                        used.ctypes.data, first_index, seed, ranges, _spatial_flags(hflip, vflip, occ_window))
     _host_check(lib().ofdg_host_spatial(C.byref(job), n, width, height))
@@ -714,19 +779,12 @@ def lens_numpy(recs):
     import numpy as np
     a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
     a = np.ascontiguousarray(a, np.float64).reshape(-1, LENS_REC_DOUBLES)
-    dtype = np.dtype([(name, "<f8") for name in ("k1", "z", "ca_b", "ca_r", "vig", "cx", "cy")] + [("reserved", "<i4", (2,))])
-    return a.view(dtype).reshape(-1)
+    return a.view(_rec_dtype("lens")).reshape(-1)
 
 
 def _lens_ranges(job, ranges):
     """The five ranges of a dict into job; "fill" may ride along (LENS_DEFAULT holds it) and is returned."""
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in LENS_RANGES and key != "fill":
-            raise ValueError("unknown range %r (known: %s, fill)" % (key, ", ".join(LENS_RANGES)))
-    for key in LENS_RANGES:
-        setattr(job, key, float(ranges.get(key, 0.0)))
-    return job, bool(ranges.get("fill", False))
+    return job, bool(_ranges_into("lens", job, ranges).get("fill", False))
 
 
 def _lens_flags(fill, occ_window):
@@ -765,9 +823,7 @@ def lens_draw(seed, index, width, height, ranges=None, fill=None):
     import numpy as np
     job, with_fill = _lens_ranges(LensJob(), ranges)
     job.width, job.height, job.flags = int(width), int(height), _lens_flags(with_fill if fill is None else fill, False)
-    out = LensRec()
-    _host_check(lib().ofdg_lens_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return np.frombuffer(bytearray(out), np.float64).copy()
+    return np.frombuffer(_rec_draw("lens", seed, index, job), np.float64).copy()
 
 
 def alloc_lens(src, zero=True):
@@ -788,11 +844,8 @@ def host_lens(src, recs=None, first_index=0, seed=0, ranges=None, fill=None, occ
     height, width = next(iter(src.values())).shape[-2:]
     dst = alloc_lens(src)
     n, *codes = lens_format(src, dst, height, width)
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.float64 or recs.shape != (n, LENS_REC_DOUBLES):
-            raise ValueError("recs must be float64 [%d,%d], got %s %s" % (n, LENS_REC_DOUBLES, recs.dtype, recs.shape))
-    used = np.zeros((n, LENS_REC_DOUBLES), np.float64)
+    recs = None if recs is None else _rec_given("lens", recs, n)
+    used = _rec_new("lens", n)
     job = _lens_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
                     first_index, seed, ranges, fill, occ_window)
     _host_check(lib().ofdg_host_lens(C.byref(job), n, width, height))
@@ -1077,31 +1130,17 @@ class EraseJob(C.Structure):
 
 
 def _erase_rec_dtype():
-    import numpy as np
-    return np.dtype([("count", "<i4"), ("rect", "<i4", (ERASE_MAX_RECTS, 5)), ("fill", "u1", (2, 3)), ("reserved", "u1", (6,))])
+    return _rec_dtype("erase")
 
 
 def erase_numpy(recs):
     """Records of Generator.erase / host_erase - a torch tensor or numpy array of int32 [n,24] (or any array of 96 bytes a
     record) - as a numpy structured array [n] with the fields count, rect [4,5] (x0, y0, w, h, frame), fill [2,3] and reserved [6]."""
-    import numpy as np
-    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
-    a = np.ascontiguousarray(a)
-    if a.dtype == _erase_rec_dtype():
-        return a
-    raw = a.view(np.uint8).reshape(-1)
-    if raw.size % 96:
-        raise ValueError("records must be 96 bytes each, got %d bytes" % raw.size)
-    return raw.view(_erase_rec_dtype())
+    return _rec_numpy("erase", recs)
 
 
 def _erase_ranges(job, ranges):
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in ERASE_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(ERASE_RANGES)))
-    for key in ERASE_RANGES:
-        setattr(job, key, (float if key == "prob" else int)(ranges.get(key, _ERASE_DEFAULTS[key])))
+    _ranges_into("erase", job, ranges)
     return job
 
 
@@ -1179,9 +1218,7 @@ def erase_draw(seed, index, width, height, ranges=None, frames=(1,)):
     element of the structured array erase_numpy describes."""
     job = _erase_ranges(EraseJob(), ranges)
     job.flags = sum(ERASE_FRAME1 if f else ERASE_FRAME0 for f in _erase_frames(frames))
-    out = EraseRec()
-    _host_check(lib().ofdg_erase_draw(int(seed) & 0xFFFFFFFF, int(index), int(width), int(height), C.byref(job), C.byref(out)))
-    return erase_numpy(bytearray(out))[0]
+    return erase_numpy(_rec_draw("erase", seed, index, job, int(width), int(height)))[0]
 
 
 def alloc_erase(n, device="cuda"):
@@ -1189,7 +1226,7 @@ def alloc_erase(n, device="cuda"):
     (recs_out).  Not filled: the call clears the first and writes every record."""
     import torch
     return (torch.empty((n, ERASE_WORK_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((n, ERASE_REC_WORDS), dtype=torch.int32, device=device))
+            _rec_alloc("erase", n, device))
 
 
 def host_erase(images, occ=None, flow=None, recs=None, first_index=0, seed=0, ranges=None, fill=ERASE_MEAN, color=(0, 0, 0), frames=(1,),
@@ -1203,11 +1240,8 @@ def host_erase(images, occ=None, flow=None, recs=None, first_index=0, seed=0, ra
     for t in tuple(images) + tuple(occ or ()) + tuple(flow or ()):
         if t is not None and not t.flags["C_CONTIGUOUS"]:
             raise ValueError("host_erase works in place: every array must be C-contiguous")
-    if recs is not None:
-        recs = erase_numpy(recs).copy()
-        if recs.shape != (n,):
-            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
-    used = np.zeros((n,), _erase_rec_dtype())
+    recs = None if recs is None else _rec_given("erase", recs, n)
+    used = _rec_new("erase", n)
     job = _erase_job(images, occ, flow, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
                      None, first_index, seed, ranges, fill, color, frames, mark_occ)
     _host_check(lib().ofdg_host_erase(C.byref(job), n, width, height))
@@ -1240,55 +1274,29 @@ class JitterJob(C.Structure):
 
 
 def _jitter_rec_dtype():
-    import numpy as np
-    return np.dtype([("brightness", "<i4", (2,)), ("contrast", "<i4", (2,)), ("saturation", "<i4", (2,)), ("hue", "<i4", (2,)), ("order", "<i4", (2,)),
-                     ("shared", "<i4"), ("mean", "<i4", (2,)), ("reserved", "<i4", (3,))])
+    return _rec_dtype("jitter")
 
 
 def jitter_numpy(recs):
     """Records of Generator.jitter / host_jitter - a torch tensor or numpy array of int32 [n,16] (or any array of 64 bytes a
     record) - as a numpy structured array [n] with the fields brightness, contrast, saturation, hue, order, mean (each [2]: frame
     0, frame 1), shared and reserved [3]."""
-    import numpy as np
-    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
-    a = np.ascontiguousarray(a)
-    if a.dtype == _jitter_rec_dtype():
-        return a
-    raw = a.view(np.uint8).reshape(-1)
-    if raw.size % 64:
-        raise ValueError("records must be 64 bytes each, got %d bytes" % raw.size)
-    return raw.view(_jitter_rec_dtype())
+    return _rec_numpy("jitter", recs)
 
 
 def _jitter_ranges(job, ranges):
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in JITTER_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(JITTER_RANGES)))
-    for key in JITTER_RANGES:
-        setattr(job, key, float(ranges.get(key, 0.0)))
+    _ranges_into("jitter", job, ranges)
     return job
 
 
 def _jitter_job(src, dst, ptr, codes, size, recs, recs_out, work, first_index, seed, ranges):
-    job = _jitter_ranges(JitterJob(), ranges)
-    for f in range(2):
-        if src[f] is not None:
-            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
-    job.recs, job.recs_out, job.work = recs, recs_out, work
-    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
-    job.height, job.width = size
-    job.src_fmt, job.dst_fmt = codes
-    return job
+    return _frame_pair_job(_jitter_ranges(JitterJob(), ranges), src, dst, ptr, codes, size, recs, recs_out, first_index, seed, work)
 
 
 def jitter_draw(seed, index, ranges=None):
     """ofdg_jitter_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (JITTER_RANGES; a
     missing one is 0; JITTER_RAFT for one), before sanitising, as one element of the structured array jitter_numpy describes."""
-    job = _jitter_ranges(JitterJob(), ranges)
-    out = JitterRec()
-    _host_check(lib().ofdg_jitter_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return jitter_numpy(bytearray(out))[0]
+    return jitter_numpy(_rec_draw("jitter", seed, index, _jitter_ranges(JitterJob(), ranges)))[0]
 
 
 def host_jitter_hue(bgr, hue):
@@ -1308,7 +1316,7 @@ def alloc_jitter(n, device="cuda"):
     records (recs_out).  Not filled: the call clears the first and writes every record."""
     import torch
     return (torch.empty((n, JITTER_WORK_BYTES), dtype=torch.uint8, device=device),
-            torch.empty((n, JITTER_REC_WORDS), dtype=torch.int32, device=device))
+            _rec_alloc("jitter", n, device))
 
 
 def host_jitter(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None, in_place=False):
@@ -1317,25 +1325,7 @@ def host_jitter(src, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=No
     array, or int32 [n,16]).  dst_dtype: np.float32 / np.uint8, default the source's.  in_place: the sources themselves are
     written (they must be contiguous and of dst_dtype).  Returns ((image0, image1), recs_used): the jittered arrays (None for
     an absent frame) and the records after sanitising, with the means, as jitter_numpy's array."""
-    import numpy as np
-    src = tuple(src)
-    if not in_place:
-        src = tuple(None if t is None else np.ascontiguousarray(t) for t in src)
-    given = [t for t in src if t is not None]
-    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
-    dst = src if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in src)
-    n, height, width, *codes = photo_format(src, dst)
-    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
-        raise ValueError("in_place needs contiguous sources of dst_dtype")
-    if recs is not None:
-        recs = jitter_numpy(recs).copy()
-        if recs.shape != (n,):
-            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
-    used = np.zeros((n,), _jitter_rec_dtype())
-    job = _jitter_job(src, dst, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data, None,
-                      first_index, seed, ranges)
-    _host_check(lib().ofdg_host_jitter(C.byref(job), n, width, height))
-    return dst, used
+    return _host_frame_pair("jitter", src, recs, dst_dtype, in_place, lambda *planes: _jitter_job(*planes, None, first_index, seed, ranges))
 
 
 # flow visualisation (ofdg_flow_vis_row / struct ofdg_flow_vis_job / ofdg_flow_vis, include/ofdg.h)
@@ -1698,57 +1688,31 @@ class CameraJob(C.Structure):
 
 
 def _camera_rec_dtype():
-    import numpy as np
-    return np.dtype([("sigma_q8", "<i4", (2,)), ("bayer", "<i4"), ("radius", "<i4", (2,)), ("reserved", "<i4", (3,))])
+    return _rec_dtype("camera")
 
 
 def camera_numpy(recs):
     """Records of Generator.camera / host_camera - a torch tensor or numpy array of int32 [n,8] (or any array of 32 bytes a
     record) - as a numpy structured array [n] with the fields sigma_q8 and radius (each [2]: frame 0, frame 1), bayer and
     reserved [3]."""
-    import numpy as np
-    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
-    a = np.ascontiguousarray(a)
-    if a.dtype == _camera_rec_dtype():
-        return a
-    raw = a.view(np.uint8).reshape(-1)
-    if raw.size % 32:
-        raise ValueError("records must be 32 bytes each, got %d bytes" % raw.size)
-    return raw.view(_camera_rec_dtype())
+    return _rec_numpy("camera", recs)
 
 
 def _camera_ranges(job, ranges):
     """the ranges of a dict in a job: a missing range is 0, a missing pattern -1 (drawn per sample)"""
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in CAMERA_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(CAMERA_RANGES)))
-    for key in CAMERA_RANGES[:5]:
-        setattr(job, key, float(ranges.get(key, 0.0)))
-    job.pattern = int(ranges.get("pattern", -1))
+    _ranges_into("camera", job, ranges)
     return job
 
 
 def _camera_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
-    job = _camera_ranges(CameraJob(), ranges)
-    for f in range(2):
-        if src[f] is not None:
-            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
-    job.recs, job.recs_out = recs, recs_out
-    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
-    job.height, job.width = size
-    job.src_fmt, job.dst_fmt = codes
-    return job
+    return _frame_pair_job(_camera_ranges(CameraJob(), ranges), src, dst, ptr, codes, size, recs, recs_out, first_index, seed)
 
 
 def camera_draw(seed, index, ranges=None):
     """ofdg_camera_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (CAMERA_RANGES; a
     missing range is 0, a missing pattern -1; CAMERA_DEFAULT for one), before sanitising, as one element of the structured
     array camera_numpy describes."""
-    job = _camera_ranges(CameraJob(), ranges)
-    out = CameraRec()
-    _host_check(lib().ofdg_camera_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return camera_numpy(bytearray(out))[0]
+    return camera_numpy(_rec_draw("camera", seed, index, _camera_ranges(CameraJob(), ranges)))[0]
 
 
 def host_camera_taps(sigma_q8):
@@ -1767,7 +1731,7 @@ def alloc_camera(n, height, width, image_dtype=None, frames=(0, 1), device="cuda
     import torch
     dt = torch.float32 if image_dtype is None else image_dtype
     return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if f in frames else None for f in range(2)),
-            torch.empty((n, CAMERA_REC_WORDS), dtype=torch.int32, device=device))
+            _rec_alloc("camera", n, device))
 
 
 def host_camera(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None):
@@ -1776,21 +1740,7 @@ def host_camera(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype
     (camera_numpy's array, or int32 [n,8]).  dst_dtype: np.float32 / np.uint8, default the source's.  Returns ((out0, out1),
     recs_used): the new arrays (None for an absent frame) and the records after sanitising, with the radii, as camera_numpy's
     array."""
-    import numpy as np
-    images = tuple(None if t is None else np.ascontiguousarray(t) for t in images)
-    given = [t for t in images if t is not None]
-    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
-    out = tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
-    n, height, width, *codes = photo_format(images, out)
-    if recs is not None:
-        recs = camera_numpy(recs).copy()
-        if recs.shape != (n,):
-            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
-    used = np.zeros((n,), _camera_rec_dtype())
-    job = _camera_job(images, out, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
-                      first_index, seed, ranges)
-    _host_check(lib().ofdg_host_camera(C.byref(job), n, width, height))
-    return out, used
+    return _host_frame_pair("camera", images, recs, dst_dtype, False, lambda *planes: _camera_job(*planes, first_index, seed, ranges))
 
 
 # block compression (ofdg_jpeg_rec / struct ofdg_jpeg_job / ofdg_jpeg, include/ofdg.h)
@@ -1818,60 +1768,32 @@ class JpegJob(C.Structure):
 
 
 def _jpeg_rec_dtype():
-    import numpy as np
-    return np.dtype([("quality", "<i4", (2,)), ("subsample", "<i4"), ("phase_x", "<i4"), ("phase_y", "<i4"), ("reserved", "<i4", (3,))])
+    return _rec_dtype("jpeg")
 
 
 def jpeg_numpy(recs):
     """Records of Generator.jpeg / host_jpeg - a torch tensor or numpy array of int32 [n,8] (or any array of 32 bytes a record)
     - as a numpy structured array [n] with the fields quality ([2]: frame 0, frame 1), subsample, phase_x, phase_y and
     reserved [3]."""
-    import numpy as np
-    a = recs.detach().cpu().numpy() if hasattr(recs, "detach") else np.asarray(recs)
-    a = np.ascontiguousarray(a)
-    if a.dtype == _jpeg_rec_dtype():
-        return a
-    raw = a.view(np.uint8).reshape(-1)
-    if raw.size % 32:
-        raise ValueError("records must be 32 bytes each, got %d bytes" % raw.size)
-    return raw.view(_jpeg_rec_dtype())
+    return _rec_numpy("jpeg", recs)
 
 
 def _jpeg_ranges(job, ranges):
     """the ranges of a dict in a job: a missing probability or delta is 0, a missing quality_min / quality_max 75 (libjpeg's
     default), a missing subsample -1 (drawn per sample), a missing phase False (the grid starts at (0, 0))"""
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in JPEG_RANGES:
-            raise ValueError("unknown range %r (known: %s)" % (key, ", ".join(JPEG_RANGES)))
-    job.quality_min, job.quality_max = int(ranges.get("quality_min", 75)), int(ranges.get("quality_max", 75))
-    job.quality_delta = int(ranges.get("quality_delta", 0))
-    job.prob, job.sub_prob = float(ranges.get("prob", 0.0)), float(ranges.get("sub_prob", 0.0))
-    job.subsample = int(ranges.get("subsample", -1))
-    job.flags = JPEG_PHASE if ranges.get("phase", False) else 0
+    job.flags = JPEG_PHASE if _ranges_into("jpeg", job, ranges).get("phase", False) else 0
     return job
 
 
 def _jpeg_job(src, dst, ptr, codes, size, recs, recs_out, first_index, seed, ranges):
-    job = _jpeg_ranges(JpegJob(), ranges)
-    for f in range(2):
-        if src[f] is not None:
-            job.src[f], job.dst[f] = ptr(src[f]), ptr(dst[f])
-    job.recs, job.recs_out = recs, recs_out
-    job.first_index, job.seed = int(first_index), int(seed) & 0xFFFFFFFF
-    job.height, job.width = size
-    job.src_fmt, job.dst_fmt = codes
-    return job
+    return _frame_pair_job(_jpeg_ranges(JpegJob(), ranges), src, dst, ptr, codes, size, recs, recs_out, first_index, seed)
 
 
 def jpeg_draw(seed, index, ranges=None):
     """ofdg_jpeg_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (JPEG_RANGES; a missing
     probability or delta is 0, a missing quality 75, a missing subsample -1, a missing phase False; JPEG_DEFAULT for one),
     before sanitising, as one element of the structured array jpeg_numpy describes."""
-    job = _jpeg_ranges(JpegJob(), ranges)
-    out = JpegRec()
-    _host_check(lib().ofdg_jpeg_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return jpeg_numpy(bytearray(out))[0]
+    return jpeg_numpy(_rec_draw("jpeg", seed, index, _jpeg_ranges(JpegJob(), ranges)))[0]
 
 
 def host_jpeg_tables(quality):
@@ -1905,7 +1827,7 @@ def alloc_jpeg(n, height=None, width=None, image_dtype=None, frames=(0, 1), devi
     dt = torch.float32 if image_dtype is None else image_dtype
     sized = height is not None and width is not None
     return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if sized and f in frames else None for f in range(2)),
-            torch.empty((n, JPEG_REC_WORDS), dtype=torch.int32, device=device))
+            _rec_alloc("jpeg", n, device))
 
 
 def host_jpeg(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=None, in_place=False):
@@ -1914,25 +1836,7 @@ def host_jpeg(images, recs=None, first_index=0, seed=0, ranges=None, dst_dtype=N
     array, or int32 [n,8]).  dst_dtype: np.float32 / np.uint8, default the source's.  in_place: the sources themselves are
     written (they must be contiguous and of dst_dtype).  Returns ((out0, out1), recs_used): the arrays (None for an absent
     frame) and the records after sanitising, as jpeg_numpy's array."""
-    import numpy as np
-    images = tuple(images)
-    if not in_place:
-        images = tuple(None if t is None else np.ascontiguousarray(t) for t in images)
-    given = [t for t in images if t is not None]
-    dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
-    out = images if in_place else tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
-    n, height, width, *codes = photo_format(images, out)
-    if in_place and (codes[0] != codes[1] or not all(t.flags["C_CONTIGUOUS"] for t in given)):
-        raise ValueError("in_place needs contiguous sources of dst_dtype")
-    if recs is not None:
-        recs = jpeg_numpy(recs).copy()
-        if recs.shape != (n,):
-            raise ValueError("recs must hold %d records, got %s" % (n, recs.shape))
-    used = np.zeros((n,), _jpeg_rec_dtype())
-    job = _jpeg_job(images, out, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
-                    first_index, seed, ranges)
-    _host_check(lib().ofdg_host_jpeg(C.byref(job), n, width, height))
-    return out, used
+    return _host_frame_pair("jpeg", images, recs, dst_dtype, in_place, lambda *planes: _jpeg_job(*planes, first_index, seed, ranges))
 
 
 # motion blur (ofdg_mblur_rec / struct ofdg_mblur_job / ofdg_motion_blur, include/ofdg.h)
@@ -1962,12 +1866,7 @@ class MblurJob(C.Structure):
 
 
 def _mblur_ranges(job, ranges, taps_side=None):
-    ranges = {} if ranges is None else ranges
-    for key in ranges:
-        if key not in MBLUR_RANGES and key != "taps_side":
-            raise ValueError("unknown range %r (known: %s, and taps_side)" % (key, ", ".join(MBLUR_RANGES)))
-    for key in MBLUR_RANGES:
-        setattr(job, key, float(ranges.get(key, 0.0)))
+    ranges = _ranges_into("motion_blur", job, ranges)
     job.taps_side = int(ranges.get("taps_side", MBLUR_DEFAULT["taps_side"]) if taps_side is None else taps_side)
     return job
 
@@ -2019,10 +1918,7 @@ def motion_blur_draw(seed, index, ranges=None):
     """ofdg_motion_blur_draw (pure, no GPU): the record of global sample `index` under `seed` for a dict of ranges (MBLUR_RANGES;
     a missing one is 0), before sanitising, as float32 [4] (MBLUR_REC_FLOATS): shutter of frame 0, of frame 1, 0, 0."""
     import numpy as np
-    out = MblurRec()
-    job = _mblur_ranges(MblurJob(), ranges)
-    _host_check(lib().ofdg_motion_blur_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return np.frombuffer(bytearray(out), np.float32).copy()
+    return np.frombuffer(_rec_draw("motion_blur", seed, index, _mblur_ranges(MblurJob(), ranges)), np.float32).copy()
 
 
 def alloc_motion_blur(n, height, width, image_dtype=None, frames=(0, 1), device="cuda"):
@@ -2032,7 +1928,7 @@ def alloc_motion_blur(n, height, width, image_dtype=None, frames=(0, 1), device=
     import torch
     dt = torch.float32 if image_dtype is None else image_dtype
     return (tuple(torch.empty((n, 3, height, width), dtype=dt, device=device) if f in frames else None for f in range(2)),
-            torch.empty((n, MBLUR_REC_FLOATS), dtype=torch.float32, device=device))
+            _rec_alloc("motion_blur", n, device))
 
 
 def host_motion_blur(images, flow, recs=None, first_index=0, seed=0, ranges=None, taps_side=None, dst_dtype=None):
@@ -2047,11 +1943,8 @@ def host_motion_blur(images, flow, recs=None, first_index=0, seed=0, ranges=None
     dt = np.dtype(given[0].dtype if dst_dtype is None and given else dst_dtype)
     out = tuple(None if t is None else np.zeros(t.shape, dt) for t in images)
     n, height, width, *codes = motion_blur_format(images, out, flow)
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.float32 or recs.shape != (n, MBLUR_REC_FLOATS):
-            raise ValueError("recs must be float32 [%d,%d], got %s %s" % (n, MBLUR_REC_FLOATS, recs.dtype, recs.shape))
-    used = np.zeros((n, MBLUR_REC_FLOATS), np.float32)
+    recs = None if recs is None else _rec_given("motion_blur", recs, n)
+    used = _rec_new("motion_blur", n)
     job = _mblur_job(images, out, flow, lambda a: a.ctypes.data, codes, (0, 0), None if recs is None else recs.ctypes.data, used.ctypes.data,
                      first_index, seed, ranges, taps_side)
     _host_check(lib().ofdg_host_motion_blur(C.byref(job), n, width, height))
@@ -2401,10 +2294,9 @@ def splat_draw(seed, index, t=None):
     """ofdg_splat_draw (pure, no GPU): the record of global sample `index` under `seed` for t= (None: 0..1; a fraction; a pair
     (min, max)), before sanitising, as int32 [4] (SPLAT_REC_INTS): t_q8 of frame 0, of frame 1 (their sum is 256), 0, 0."""
     import numpy as np
-    out, job = SplatRec(), SplatJob()
+    job = SplatJob()
     job.t_min_q8, job.t_max_q8 = _splat_t_range(t)
-    _host_check(lib().ofdg_splat_draw(int(seed) & 0xFFFFFFFF, int(index), C.byref(job), C.byref(out)))
-    return np.frombuffer(bytearray(out), np.int32).copy()
+    return np.frombuffer(_rec_draw("splat", seed, index, job), np.int32).copy()
 
 
 def alloc_splat(n, height, width, frames=(0,), outputs=SPLAT_OUTPUTS, image_dtype=None, flow_dtype=None, device="cuda"):
@@ -2427,7 +2319,7 @@ def alloc_splat(n, height, width, frames=(0,), outputs=SPLAT_OUTPUTS, image_dtyp
            for f in frames for name in SPLAT_PLANES if name in outputs}
     keys = tuple(torch.empty((n, height, width), dtype=torch.int32, device=device) if f in frames else None for f in range(2))
     rows = torch.zeros((n, C.sizeof(SplatRow)), dtype=torch.uint8, device=device) if "rows" in outputs else None
-    return out, keys, rows, torch.empty((n, SPLAT_REC_INTS), dtype=torch.int32, device=device)
+    return out, keys, rows, _rec_alloc("splat", n, device)
 
 
 def splat_numpy(rows=None, keys=None):
@@ -2488,10 +2380,7 @@ def host_splat(images, flows, labels=None, occ=None, t=None, recs=None, outputs=
            and (name != "image" or (images is not None and images[f] is not None))}
     keys = tuple(np.zeros((n, height, width), np.uint32) if f in frames else None for f in range(2))
     n, height, width, *codes = splat_format(images, flows, labels, occ, out, keys)
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.int32 or recs.shape != (n, SPLAT_REC_INTS):
-            raise ValueError("recs must be int32 [%d,%d], got %s %s" % (n, SPLAT_REC_INTS, recs.dtype, recs.shape))
+    recs = None if recs is None else _rec_given("splat", recs, n)
     if "rows" not in outputs:
         if rows is not None or accumulate:
             raise ValueError("rows= and accumulate=True need \"rows\" among outputs")
@@ -2501,11 +2390,64 @@ def host_splat(images, flows, labels=None, occ=None, t=None, recs=None, outputs=
         rows = np.zeros((n, 2), _splat_dtype())
     elif rows.dtype != _splat_dtype() or rows.shape != (n, 2) or not rows.flags["C_CONTIGUOUS"]:
         raise ValueError("rows must be a contiguous structured array [%d,2] as a former call returned it" % n)
-    used = np.zeros((n, SPLAT_REC_INTS), np.int32)
+    used = _rec_new("splat", n)
     job = _splat_job(images, flows, labels, occ, out, keys, None if rows is None else rows.ctypes.data, lambda a: a.ctypes.data, codes, (0, 0), frames,
                      _splat_t_range(t), None if recs is None else recs.ctypes.data, used.ctypes.data, first_index, seed, accumulate)
     _host_check(lib().ofdg_host_splat(C.byref(job), n, width, height))
     return out, keys, rows, used
+
+
+# ---- The record table: one description per operation that has records -------------------------------------------------------------
+# What _ranges_into, _rec_dtype, _rec_numpy, _rec_given, _rec_new, _rec_alloc, _rec_draw, Generator._rec_shape and the loader's
+# "does an enabled stage draw records" read.  A new operation with records adds ONE entry here and its written-out public functions.
+class _RecordOp:
+    """stage: the FlowLoader attribute that is not None when the stage is on.  rec, job: the ctypes classes.  fields: the numpy
+    field list of a record; structured: does X_numpy / host_X speak of records as that structured array (else as rows of
+    `dtype` [width], the torch view every operation's device tensors have).  ranges: ((name, int | float, missing-value
+    default), ...) of the job's fields a range dict fills; flags: names the dict may hold besides; says: the "known: ..." text
+    where it is not the plain list.  entries: the C entries (device, host twin, draw), by name."""
+    def __init__(self, stage, rec, job, fields, structured, dtype, width, entries, ranges=(), flags=(), says=None):
+        self.stage, self.rec, self.job, self.fields, self.structured, self.dtype, self.width = stage, rec, job, fields, structured, dtype, width
+        self.ranges, self.flags, self.says = tuple(ranges), tuple(flags), says
+        self.device, self.host, self.draw = entries
+
+
+def _floats(names):
+    return tuple((name, float, 0.0) for name in names)
+
+
+_PAIR = ("<i4", (2,))
+_RECORDS = {
+    "crop": _RecordOp("window", CropRec, CropJob, [("x0", "<i4"), ("y0", "<i4"), ("flags", "<i4"), ("reserved", "<i4")], False, "int32", 4,
+                      ("ofdg_crop", "ofdg_host_crop", None)),  # (ofdg_crop_draw takes no job: crop_draw calls it itself)
+    "photo": _RecordOp("photo", PhotoRec, PhotoJob,
+                       [("gamma", "<f4", (2,)), ("contrast", "<f4", (2,)), ("brightness", "<f4", (2,)), ("gain", "<f4", (2, 3)), ("sigma", "<f4", (2,)),
+                        ("reserved", "<i4", (2,))], False, "float32", PHOTO_REC_FLOATS,
+                       ("ofdg_photo", "ofdg_host_photo", "ofdg_photo_draw"), _floats(PHOTO_RANGES)),
+    "spatial": _RecordOp("window", SpatialRec, SpatialJob, [("m", "<f8", (2, 6)), ("reserved", "<i4", (4,))], False, "float64", SPATIAL_REC_DOUBLES,
+                         ("ofdg_spatial", "ofdg_host_spatial", "ofdg_spatial_draw"), _floats(SPATIAL_RANGES)),
+    "lens": _RecordOp("lens", LensRec, LensJob, [(name, "<f8") for name in ("k1", "z", "ca_b", "ca_r", "vig", "cx", "cy")] + [("reserved", "<i4", (2,))],
+                      False, "float64", LENS_REC_DOUBLES, ("ofdg_lens", "ofdg_host_lens", "ofdg_lens_draw"), _floats(LENS_RANGES), flags=("fill",)),
+    "erase": _RecordOp("erase", EraseRec, EraseJob, [("count", "<i4"), ("rect", "<i4", (ERASE_MAX_RECTS, 5)), ("fill", "u1", (2, 3)), ("reserved", "u1", (6,))],
+                       True, "int32", ERASE_REC_WORDS, ("ofdg_erase", "ofdg_host_erase", "ofdg_erase_draw"),
+                       tuple((k, float if k == "prob" else int, _ERASE_DEFAULTS[k]) for k in ERASE_RANGES)),
+    "jitter": _RecordOp("jitter", JitterRec, JitterJob,
+                        [("brightness",) + _PAIR, ("contrast",) + _PAIR, ("saturation",) + _PAIR, ("hue",) + _PAIR, ("order",) + _PAIR, ("shared", "<i4"),
+                         ("mean",) + _PAIR, ("reserved", "<i4", (3,))], True, "int32", JITTER_REC_WORDS,
+                        ("ofdg_jitter", "ofdg_host_jitter", "ofdg_jitter_draw"), _floats(JITTER_RANGES)),
+    "camera": _RecordOp("camera", CameraRec, CameraJob, [("sigma_q8",) + _PAIR, ("bayer", "<i4"), ("radius",) + _PAIR, ("reserved", "<i4", (3,))],
+                        True, "int32", CAMERA_REC_WORDS, ("ofdg_camera", "ofdg_host_camera", "ofdg_camera_draw"),
+                        _floats(CAMERA_RANGES[:5]) + (("pattern", int, -1),)),
+    "jpeg": _RecordOp("jpeg", JpegRec, JpegJob, [("quality",) + _PAIR, ("subsample", "<i4"), ("phase_x", "<i4"), ("phase_y", "<i4"), ("reserved", "<i4", (3,))],
+                      True, "int32", JPEG_REC_WORDS, ("ofdg_jpeg", "ofdg_host_jpeg", "ofdg_jpeg_draw"),
+                      (("quality_min", int, 75), ("quality_max", int, 75), ("quality_delta", int, 0), ("prob", float, 0.0), ("sub_prob", float, 0.0),
+                       ("subsample", int, -1)), flags=("phase",)),
+    "motion_blur": _RecordOp("motion_blur", MblurRec, MblurJob, [("shutter", "<f4", (2,)), ("reserved", "<i4", (2,))], False, "float32", MBLUR_REC_FLOATS,
+                             ("ofdg_motion_blur", "ofdg_host_motion_blur", "ofdg_motion_blur_draw"), _floats(MBLUR_RANGES), flags=("taps_side",),
+                             says="%s, and taps_side"),
+    "splat": _RecordOp("splat", SplatRec, SplatJob, [("t_q8",) + _PAIR, ("reserved", "<i4", (2,))], False, "int32", SPLAT_REC_INTS,
+                       ("ofdg_splat", "ofdg_host_splat", "ofdg_splat_draw")),
+}
 
 
 def build(verbose=False):
@@ -2966,6 +2908,11 @@ class Generator:
         return height, width, (height, width)
 
     @staticmethod
+    def _rec_shape(op, n):
+        """(torch dtype name, shape) of n records of an operation: what _check_recs takes"""
+        return _RECORDS[op].dtype, (n, _RECORDS[op].width)
+
+    @staticmethod
     def _check_recs(recs, recs_out, dtype, shape):
         """recs and recs_out of a post-processing call: each None or a tensor of torch.<dtype> and of that shape"""
         for t in (recs, recs_out):
@@ -2974,6 +2921,21 @@ class Generator:
 
     def _seed(self, seed):
         return self.params.seed if seed is None else seed
+
+    def _frame_pair(self, op, src, dst, recs, recs_out, size, stream, make_job, check=None):
+        """What photo, jitter, camera and jpeg share: the pairs (dst None: in place), photo_format, recs and recs_out against the record
+        table, check(n) where the operation has one, the job - make_job(src, dst, ptr, codes, size, recs,
+        recs_out) - and the call of the device entry.  Returns dst."""
+        src = tuple(src)
+        dst = src if dst is None else tuple(dst)
+        height, width, job_size = self._job_size(size)
+        n, _, _, *codes = photo_format(src, dst, height, width)
+        self._check_recs(recs, recs_out, *self._rec_shape(op, n))
+        if check is not None:
+            check(n)
+        job = make_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out))
+        self._check(getattr(lib(), _RECORDS[op].device)(self.h, C.byref(job), n, C.c_void_p(stream)))
+        return dst
 
     def crop(self, src, dst, recs=None, first_index=0, seed=None, hflip=False, vflip=False, occ_window=False, recs_out=None, stream=0):
         """The training window of every plane of a batch in one launch (ofdg_crop, include/ofdg.h): src and dst are dicts keyed
@@ -2986,7 +2948,7 @@ class Generator:
         receives the records used.  stream: the stream the planes were written on, or STREAM_OWN.  Asynchronous; there is no
         in-place form.  Returns dst."""
         n, crop_h, crop_w, *codes = crop_format(src, dst, self.params.height, self.params.width)
-        self._check_recs(recs, recs_out, "int32", (n, 4))
+        self._check_recs(recs, recs_out, *self._rec_shape("crop", n))
         job = _crop_job(src, dst, _dptr, codes, crop_h, crop_w, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
                         _crop_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_crop(self.h, C.byref(job), n, C.c_void_p(stream)))
@@ -3002,14 +2964,8 @@ class Generator:
         recs_out: None or a float32 device tensor [n,16] that receives the records used.  stream: the stream the frames were
         written on, or STREAM_OWN.  size=(height, width): frames of that size instead of the context's.  Asynchronous.
         Returns dst."""
-        src = tuple(src)
-        dst = src if dst is None else tuple(dst)
-        height, width, job_size = self._job_size(size)
-        n, _, _, *codes = photo_format(src, dst, height, width)
-        self._check_recs(recs, recs_out, "float32", (n, PHOTO_REC_FLOATS))
-        job = _photo_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
-        self._check(lib().ofdg_photo(self.h, C.byref(job), n, C.c_void_p(stream)))
-        return dst
+        return self._frame_pair("photo", src, dst, recs, recs_out, size, stream,
+                                lambda *planes: _photo_job(*planes, first_index, self._seed(seed), ranges))
 
     def spatial(self, src, dst, recs=None, first_index=0, seed=None, ranges=None, hflip=False, vflip=False, occ_window=False,
                 recs_out=None, stream=0, size=None):
@@ -3026,7 +2982,7 @@ class Generator:
         there is no in-place form.  Returns dst."""
         height, width, job_size = self._job_size(size)
         n, out_h, out_w, *codes = spatial_format(src, dst, height, width)
-        self._check_recs(recs, recs_out, "float64", (n, SPATIAL_REC_DOUBLES))
+        self._check_recs(recs, recs_out, *self._rec_shape("spatial", n))
         job = _spatial_job(src, dst, lambda t: _dptr(t).value, codes, job_size, out_h, out_w, _optr(recs), _optr(recs_out), first_index,
                            self._seed(seed), ranges, _spatial_flags(hflip, vflip, occ_window))
         self._check(lib().ofdg_spatial(self.h, C.byref(job), n, C.c_void_p(stream)))
@@ -3048,7 +3004,7 @@ class Generator:
         of the context's frame.  Asynchronous; there is no in-place form.  Returns dst."""
         height, width, job_size = self._job_size(size)
         n, *codes = lens_format(src, dst, height, width)
-        self._check_recs(recs, recs_out, "float64", (n, LENS_REC_DOUBLES))
+        self._check_recs(recs, recs_out, *self._rec_shape("lens", n))
         job = _lens_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
                         ranges, fill, occ_window)
         self._check(lib().ofdg_lens(self.h, C.byref(job), n, C.c_void_p(stream)))
@@ -3109,7 +3065,7 @@ class Generator:
         images = tuple(images)
         height, width, job_size = self._job_size(size)
         n, _, _, *codes = erase_format(images, occ, flow, height, width)
-        self._check_recs(recs, recs_out, "int32", (n, ERASE_REC_WORDS))
+        self._check_recs(recs, recs_out, *self._rec_shape("erase", n))
         if fill == ERASE_MEAN and (work is None or str(work.dtype) != "torch.uint8" or work.numel() < n * ERASE_WORK_BYTES):
             raise ValueError("fill=ERASE_MEAN needs work=, a uint8 device tensor of at least [%d,%d] (alloc_erase)" % (n, ERASE_WORK_BYTES))
         job = _erase_job(images, occ, flow, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out),
@@ -3129,17 +3085,11 @@ class Generator:
         both), one per call in flight; needed with recs= and whenever ranges holds a contrast.  stream: the stream the frames
         were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of the context's.  Asynchronous.
         Returns dst."""
-        src = tuple(src)
-        dst = src if dst is None else tuple(dst)
-        height, width, job_size = self._job_size(size)
-        n, _, _, *codes = photo_format(src, dst, height, width)
-        self._check_recs(recs, recs_out, "int32", (n, JITTER_REC_WORDS))
-        if work is not None and (str(work.dtype) != "torch.uint8" or work.numel() < n * JITTER_WORK_BYTES):
-            raise ValueError("work must be a uint8 device tensor of at least [%d,%d] (alloc_jitter)" % (n, JITTER_WORK_BYTES))
-        job = _jitter_job(src, dst, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), _optr(work), first_index,
-                          self._seed(seed), ranges)
-        self._check(lib().ofdg_jitter(self.h, C.byref(job), n, C.c_void_p(stream)))
-        return dst
+        def check_work(n):
+            if work is not None and (str(work.dtype) != "torch.uint8" or work.numel() < n * JITTER_WORK_BYTES):
+                raise ValueError("work must be a uint8 device tensor of at least [%d,%d] (alloc_jitter)" % (n, JITTER_WORK_BYTES))
+        return self._frame_pair("jitter", src, dst, recs, recs_out, size, stream,
+                                lambda *planes: _jitter_job(*planes, _optr(work), first_index, self._seed(seed), ranges), check_work)
 
     def flow_vis(self, flow, dst=None, occ=None, norm="sample", max_flow=None, layout="planar_bgr", dim_occ=False, rows_out=None, work=None,
                  stream=0, size=None):
@@ -3199,13 +3149,8 @@ class Generator:
         recs_out: None or an int32 device tensor [n,8] that receives the records used, with the radii (camera_numpy reads it).
         stream: the stream the frames were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of
         the context's.  Flow, maps and labels are not touched.  Asynchronous.  Returns out."""
-        images, out = tuple(images), tuple(out)
-        height, width, job_size = self._job_size(size)
-        n, _, _, *codes = photo_format(images, out, height, width)
-        self._check_recs(recs, recs_out, "int32", (n, CAMERA_REC_WORDS))
-        job = _camera_job(images, out, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
-        self._check(lib().ofdg_camera(self.h, C.byref(job), n, C.c_void_p(stream)))
-        return out
+        return self._frame_pair("camera", tuple(images), tuple(out), recs, recs_out, size, stream,
+                                lambda *planes: _camera_job(*planes, first_index, self._seed(seed), ranges))
 
     def jpeg(self, images, out=None, recs=None, first_index=0, seed=None, ranges=None, recs_out=None, stream=0, size=None):
         """Block compression of both frames of a batch in one launch (ofdg_jpeg, include/ofdg.h): what a baseline JFIF encoder and
@@ -3219,14 +3164,8 @@ class Generator:
         stream: the stream the frames were written on, or STREAM_OWN.  size=(height, width): frames of that size instead of
         the context's.  A frame of quality 0 is copied (in place: left alone); quality 100 is not the identity.  Flow, maps and
         labels are not touched.  Asynchronous.  Returns out (in place: images)."""
-        images = tuple(images)
-        out = images if out is None else tuple(out)
-        height, width, job_size = self._job_size(size)
-        n, _, _, *codes = photo_format(images, out, height, width)
-        self._check_recs(recs, recs_out, "int32", (n, JPEG_REC_WORDS))
-        job = _jpeg_job(images, out, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed), ranges)
-        self._check(lib().ofdg_jpeg(self.h, C.byref(job), n, C.c_void_p(stream)))
-        return out
+        return self._frame_pair("jpeg", images, out, recs, recs_out, size, stream,
+                                lambda *planes: _jpeg_job(*planes, first_index, self._seed(seed), ranges))
 
     def motion_blur(self, images, out, flow=None, recs=None, first_index=0, seed=None, ranges=None, taps_side=None, recs_out=None, stream=0,
                     size=None):
@@ -3247,7 +3186,7 @@ class Generator:
         images, out, flow = tuple(images), tuple(out), tuple(flow)
         height, width, job_size = self._job_size(size)
         n, _, _, *codes = motion_blur_format(images, out, flow, height, width)
-        self._check_recs(recs, recs_out, "float32", (n, MBLUR_REC_FLOATS))
+        self._check_recs(recs, recs_out, *self._rec_shape("motion_blur", n))
         job = _mblur_job(images, out, flow, lambda t: _dptr(t).value, codes, job_size, _optr(recs), _optr(recs_out), first_index, self._seed(seed),
                          ranges, taps_side)
         self._check(lib().ofdg_motion_blur(self.h, C.byref(job), n, C.c_void_p(stream)))
@@ -3305,7 +3244,7 @@ class Generator:
             raise ValueError("t= and recs= exclude each other")
         height, width, job_size = self._job_size(size)
         n, _, _, *codes = splat_format(images, flows, labels, occ, out, keys, height, width)
-        self._check_recs(recs, recs_out, "int32", (n, SPLAT_REC_INTS))
+        self._check_recs(recs, recs_out, *self._rec_shape("splat", n))
         if rows is not None and (str(rows.dtype) != "torch.uint8" or tuple(rows.shape) != (n, C.sizeof(SplatRow))):
             raise ValueError("rows must be uint8 [%d,%d], got %s %s" % (n, C.sizeof(SplatRow), rows.dtype, tuple(rows.shape)))
         job = _splat_job(images, flows, labels, occ, out, keys, _optr(rows), lambda x: _dptr(x).value, codes, job_size, frames, _splat_t_range(t),
@@ -3802,11 +3741,8 @@ def host_crop(src, crop_h, crop_w, recs=None, first_index=0, seed=0, hflip=False
     height, width = next(iter(src.values())).shape[-2:]
     dst = alloc_crop(src, crop_h, crop_w)
     n, crop_h, crop_w, *codes = crop_format(src, dst, height, width)
-    if recs is not None:
-        recs = np.ascontiguousarray(recs)
-        if recs.dtype != np.int32 or recs.shape != (n, 4):
-            raise ValueError("recs must be int32 [%d,4], got %s %s" % (n, recs.dtype, recs.shape))
-    used = np.zeros((n, 4), np.int32)
+    recs = None if recs is None else _rec_given("crop", recs, n)
+    used = _rec_new("crop", n)
     job = _crop_job(src, dst, lambda a: a.ctypes.data, codes, crop_h, crop_w, None if recs is None else recs.ctypes.data, used.ctypes.data,
                     first_index, seed, _crop_flags(hflip, vflip, occ_window))
     rc = lib().ofdg_host_crop(C.byref(job), n, width, height)
@@ -4148,16 +4084,16 @@ class FlowLoader:
             t.window_recs = None
             if self.spatial is not None:
                 t.planes = alloc_spatial(t.frame, ph, pw, zero=False)
-                t.window_recs = torch.empty((n, SPATIAL_REC_DOUBLES), dtype=torch.float64, device="cuda")
+                t.window_recs = _rec_alloc("spatial", n)
                 spatial_format(t.frame, t.planes, p.height, p.width)  # (raises for a size the rule does not allow)
             elif self.crop is not None:
                 t.planes = alloc_crop(t.frame, ph, pw, zero=False)
-                t.window_recs = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+                t.window_recs = _rec_alloc("crop", n)
                 crop_format(t.frame, t.planes, p.height, p.width)  # (raises for a window the frame does not allow)
             t.window, t.lens = t.planes, None
             if self.lens is not None:
                 t.planes = alloc_lens(t.window, zero=False)
-                t.lens = torch.empty((n, LENS_REC_DOUBLES), dtype=torch.float64, device="cuda")
+                t.lens = _rec_alloc("lens", n)
                 lens_format(t.window, t.planes, ph, pw)
             t.sharp, t.blur = t.planes, None
             t.reproject = None
@@ -4174,7 +4110,7 @@ class FlowLoader:
                 t.optics = t.planes
                 shot, t.camera = alloc_camera(n, ph, pw, t.optics["image0"].dtype)
                 t.planes = dict(t.optics, image0=shot[0], image1=shot[1])
-            t.photo = torch.empty((n, PHOTO_REC_FLOATS), dtype=torch.float32, device="cuda") if self.photo is not None else None
+            t.photo = _rec_alloc("photo", n) if self.photo is not None else None
             t.jitter = alloc_jitter(n) if self.jitter is not None else None
             t.jpeg = alloc_jpeg(n)[1] if self.jpeg is not None else None
             t.erase = alloc_erase(n) if self.erase is not None else None
@@ -4281,12 +4217,17 @@ class FlowLoader:
         return o
 
     @staticmethod
+    def _ranges_option(ranges, check, job):
+        """a stage's dict of ranges as a dict of its own, or None; raises for a name that is no range"""
+        if ranges is None:
+            return None
+        check(job(), ranges)
+        return dict(ranges)
+
+    @staticmethod
     def _camera_options(camera):
         """camera= as a dict of its own, or None; raises for a name that is no range"""
-        if camera is None:
-            return None
-        _camera_ranges(CameraJob(), camera)
-        return dict(camera)
+        return FlowLoader._ranges_option(camera, _camera_ranges, CameraJob)
 
     @staticmethod
     def _lens_options(lens, extras, objects):
@@ -4304,18 +4245,12 @@ class FlowLoader:
     @staticmethod
     def _jpeg_options(jpeg):
         """jpeg= as a dict of its own, or None; raises for a name that is no range"""
-        if jpeg is None:
-            return None
-        _jpeg_ranges(JpegJob(), jpeg)
-        return dict(jpeg)
+        return FlowLoader._ranges_option(jpeg, _jpeg_ranges, JpegJob)
 
     @staticmethod
     def _jitter_options(jitter):
         """jitter= as a dict of its own, or None; raises for a name that is no range"""
-        if jitter is None:
-            return None
-        _jitter_ranges(JitterJob(), jitter)
-        return dict(jitter)
+        return FlowLoader._ranges_option(jitter, _jitter_ranges, JitterJob)
 
     @staticmethod
     def _motion_blur_options(motion_blur, extras):
@@ -4387,7 +4322,7 @@ class FlowLoader:
         if t.released is not None:
             chain.wait_event(t.released)
         first = 0                               # the first global index of the batch forward is about to render ...
-        if self.window is not None or self.photo is not None or self.erase is not None or self.motion_blur is not None or self.splat is not None or self.jitter is not None or self.camera is not None or self.lens is not None or self.jpeg is not None:  # ... for the stages that draw records
+        if any(getattr(self, r.stage) is not None for r in _RECORDS.values()):  # ... for the stages that draw records
             first = shard_first_index(g.step, p.batch_size, p.world_size, p.rank)
         g.forward(*t.outs, s, extras=t.extras)
         planes, size = t.planes, self.window

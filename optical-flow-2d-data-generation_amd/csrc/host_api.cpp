@@ -5,6 +5,7 @@
 #include <cstring>
 #include <exception>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "host_input.h"
@@ -18,6 +19,49 @@ struct ofdg_host_sampler {
   ofdg_host_sampler(int m, int w, int h, int n) : s(m, w, h, n) {}
 };
 thread_local std::string ofdg::g_host_error;
+
+// How a host twin opens: the job's own width and height against the plane size given, the plane-size rule, then the rules the
+// twin shares with its device entry (arg_error(j, n, width, height): a function, or a lambda where the twin has rules of its
+// own in front).  pair_rule: does the twin refuse a job with one of width and height 0 before it compares them?  (Eight twins
+// do not; such a job is refused by the comparison.)  -> false with ofdg_host_last_error set.
+template <typename Job, typename Rules>
+static bool host_open(const char* who, const Job* j, int n, int width, int height, bool pair_rule, Rules arg_error) {
+  const char* why = !j ? "job is NULL" : pair_rule && (j->width == 0) != (j->height == 0) ? kPlanePairRule
+                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
+                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
+  if (!why) why = plane_size_error(width, height);
+  if (!why) why = arg_error(j, n, width, height);
+  if (why) g_host_error = std::string(who) + ": " + why;
+  return !why;
+}
+// Record i of a job as it is used: the caller's when recs is given, else draw(global index), then sanitised.  Bytes are moved
+// with memcpy, so no alignment is asked.  record_out: ... and handed back when recs_out is given.
+template <typename Job, typename Draw, typename Sanitise>
+static auto record_of(const Job* j, int i, Draw draw, Sanitise sanitise) {
+  std::remove_const_t<std::remove_pointer_t<decltype(j->recs)>> r;
+  if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
+  else r = draw((unsigned long long)(j->first_index + i));
+  return sanitise(r);
+}
+template <typename Job, typename Rec>
+static void record_out(const Job* j, int i, const Rec& r) {
+  if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+}
+
+// An ofdg_X_draw entry whose draw reads nothing but the job: its ranges checked, then the record of global sample `index`.
+// (crop and erase take a frame size, spatial and lens the job's own: those four are written out.)
+template <typename Dev, typename Rec, typename Job, typename Out>
+static int draw_entry(const char* who, const char* (*ranges_error)(const Dev&), Rec (*draw)(uint32_t, unsigned long long, const Dev&), uint32_t seed,
+                      long long index, const Job* ranges, Out* out) {
+  static_assert(sizeof(Dev) == sizeof(Job) && sizeof(Rec) == sizeof(Out), "the public structs, restated");
+  if (!ranges || !out) { g_host_error = std::string(who) + ": ranges or out is NULL"; return OFDG_EINVAL; }
+  Dev j;
+  std::memcpy(&j, ranges, sizeof(j));
+  if (const char* why = ranges_error(j)) { g_host_error = std::string(who) + ": " + why; return OFDG_EINVAL; }
+  const Rec r = draw(seed, (unsigned long long)index, j);
+  std::memcpy(out, &r, sizeof(r));
+  return OFDG_OK;
+}
 
 extern "C" {
 
@@ -341,11 +385,9 @@ int ofdg_host_crop(const struct ofdg_crop_job* job, int n_samples, int width, in
   const int cw = j->crop_w, ch = j->crop_h;
   const size_t frame = (size_t)width * height, window = (size_t)cw * ch;
   for (int i = 0; i < n_samples; ++i) {
-    DevCropRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + 16 * (size_t)i, 16);
-    else r = crop_draw_rec(j->seed, (unsigned long long)(j->first_index + i), width, height, cw, ch, j->flags);
-    r = crop_sanitise(r, width, height, cw, ch);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + 16 * (size_t)i, &r, 16);
+    DevCropRec r = record_of(j, i, [&](unsigned long long g) { return crop_draw_rec(j->seed, g, width, height, cw, ch, j->flags); },
+                             [&](const DevCropRec& r) { return crop_sanitise(r, width, height, cw, ch); });
+    record_out(j, i, r);
     const bool hflip = r.flags & OFDG_CROP_HFLIP, vflip = r.flags & OFDG_CROP_VFLIP;
     for (int k = 0; k < kCropPlanes; ++k) {
       if (!j->src[k]) continue;
@@ -400,31 +442,18 @@ int ofdg_host_photo_table(const ofdg_photo_rec* rec, float* table) {
   return OFDG_OK;
 }
 int ofdg_photo_draw(uint32_t seed, long long index, const struct ofdg_photo_job* ranges, ofdg_photo_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_photo_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevPhotoJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = photo_ranges_error(j)) { g_host_error = std::string("ofdg_photo_draw: ") + why; return OFDG_EINVAL; }
-  const DevPhotoRec r = photo_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_photo_draw", photo_ranges_error, photo_draw_rec, seed, index, ranges, out);
 }
 int ofdg_host_photo(const struct ofdg_photo_job* job, int n_samples, int width, int height) {
   const DevPhotoJob* const j = reinterpret_cast<const DevPhotoJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = photo_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_photo: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_photo", j, n_samples, width, height, /*pair_rule=*/false, photo_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
   std::vector<float> table(2 * 3 * 256);
   for (int i = 0; i < n_samples; ++i) {
     const unsigned long long g = (unsigned long long)(j->first_index + i);
-    DevPhotoRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + 64 * (size_t)i, 64);
-    else r = photo_draw_rec(j->seed, g, *j);
-    r = photo_sanitise(r);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + 64 * (size_t)i, &r, 64);
+    DevPhotoRec r = record_of(j, i, [&](unsigned long long g) { return photo_draw_rec(j->seed, g, *j); }, photo_sanitise);
+    record_out(j, i, r);
     photo_table_of(r, table.data());
     const uint32_t k0 = j->seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
     for (int f = 0; f < 2; ++f) {
@@ -488,22 +517,18 @@ struct SpatialElems {  // a plane's elements widened to float32: float32, binary
 };
 int ofdg_host_spatial(const struct ofdg_spatial_job* job, int n_samples, int width, int height) {
   const DevSpatialJob* const j = reinterpret_cast<const DevSpatialJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why && (width > kSpatialMaxSide || height > kSpatialMaxSide)) why = "width and height must not exceed 2^20";
-  if (!why) why = spatial_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_spatial: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_spatial", j, n_samples, width, height, /*pair_rule=*/false, [](const auto* j, int n, int width, int height) -> const char* {
+    if (width > kSpatialMaxSide || height > kSpatialMaxSide) return "width and height must not exceed 2^20";
+    return spatial_arg_error(j, n, width, height);
+  })) return OFDG_EINVAL;
   const int W = width, H = height, ow = j->out_w, oh = j->out_h;
   const size_t frame = (size_t)W * H, window = (size_t)ow * oh;
   const bool occ_window = j->flags & OFDG_SPATIAL_OCC_WINDOW;
   const int ies = fmt_elem_bytes(j->image_fmt), fes = fmt_elem_bytes(j->flow_fmt), oes = fmt_elem_bytes(j->occ_fmt);
   for (int i = 0; i < n_samples; ++i) {
-    DevSpatialRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = spatial_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j, W, H);
-    r = spatial_sanitise(r, W, H, ow, oh);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    DevSpatialRec r = record_of(j, i, [&](unsigned long long g) { return spatial_draw_rec(j->seed, g, *j, W, H); },
+                             [&](const DevSpatialRec& r) { return spatial_sanitise(r, W, H, ow, oh); });
+    record_out(j, i, r);
     for (int f = 0; f < 2; ++f) {
       const double* const m = r.m[f];
       const SpatialInv other = spatial_inverse(r.m[1 - f]);
@@ -587,23 +612,19 @@ int ofdg_lens_draw(uint32_t seed, long long index, const struct ofdg_lens_job* r
 }
 int ofdg_host_lens(const struct ofdg_lens_job* job, int n_samples, int width, int height) {
   const DevLensJob* const j = reinterpret_cast<const DevLensJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why && (width > kSpatialMaxSide || height > kSpatialMaxSide)) why = "width and height must not exceed 2^20";
-  if (!why && (unsigned long long)width * (unsigned long long)height >= (1ull << 31)) why = "width * height must be below 2^31";
-  if (!why) why = lens_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_lens: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_lens", j, n_samples, width, height, /*pair_rule=*/false, [](const auto* j, int n, int width, int height) -> const char* {
+    if (width > kSpatialMaxSide || height > kSpatialMaxSide) return "width and height must not exceed 2^20";
+    if ((unsigned long long)width * (unsigned long long)height >= (1ull << 31)) return "width * height must be below 2^31";
+    return lens_arg_error(j, n, width, height);
+  })) return OFDG_EINVAL;
   const int W = width, H = height;
   const size_t frame = (size_t)W * H;
   const bool occ_window = j->flags & OFDG_LENS_OCC_WINDOW;
   const int ies = fmt_elem_bytes(j->image_fmt), fes = fmt_elem_bytes(j->flow_fmt), oes = fmt_elem_bytes(j->occ_fmt);
   for (int i = 0; i < n_samples; ++i) {
-    DevLensRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = lens_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j, W, H);
-    r = lens_sanitise(r, W, H);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    DevLensRec r = record_of(j, i, [&](unsigned long long g) { return lens_draw_rec(j->seed, g, *j, W, H); },
+                             [&](const DevLensRec& r) { return lens_sanitise(r, W, H); });
+    record_out(j, i, r);
     const LensSetup o = lens_setup(r, W, H);
     for (int f = 0; f < 2; ++f) {
       const void* const s_img = j->src[OFDG_CROP_IMAGE0 + f];
@@ -683,12 +704,7 @@ int ofdg_host_lens(const struct ofdg_lens_job* job, int n_samples, int width, in
 // so no alignment is asked.
 int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, int height) {
   const DevPackJob* const j = reinterpret_cast<const DevPackJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = pack_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_pack: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_pack", j, n_samples, width, height, /*pair_rule=*/true, pack_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   for (int k = 0; k < kPackPlanes; ++k) {
     if (!j->src[k]) continue;
@@ -716,12 +732,7 @@ int ofdg_host_pack(const struct ofdg_pack_job* job, int n_samples, int width, in
 // rules are the functions the kernel runs (csrc/ofdg_device.h); the distance is the minimum over the offsets of the disc.
 int ofdg_host_boundaries(const struct ofdg_boundary_job* job, int n_samples, int width, int height) {
   const DevBoundaryJob* const j = reinterpret_cast<const DevBoundaryJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = boundary_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_boundaries: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_boundaries", j, n_samples, width, height, /*pair_rule=*/true, boundary_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const bool labels = j->flags & OFDG_BND_LABELS;
   const float t2 = boundary_threshold(j->min_step);
@@ -781,21 +792,16 @@ int ofdg_erase_draw(uint32_t seed, long long index, int width, int height, const
 }
 int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, int height) {
   const DevEraseJob* const j = reinterpret_cast<const DevEraseJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = erase_arg_error(j, n_samples, width, height, /*with_work=*/false);
-  if (why) { g_host_error = std::string("ofdg_host_erase: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_erase", j, n_samples, width, height, /*pair_rule=*/true,
+                 [](const auto* j, int n, int w, int h) { return erase_arg_error(j, n, w, h, /*with_work=*/false); }))
+    return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int es = fmt_elem_bytes(j->image_fmt);
   const bool occ = j->flags & OFDG_ERASE_OCC;
   for (int i = 0; i < n_samples; ++i) {
     const unsigned long long g = (unsigned long long)(j->first_index + i);
-    DevEraseRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = erase_draw_rec(j->seed, g, width, height, *j);
-    r = erase_sanitise(r, width, height, j->flags);
+    DevEraseRec r = record_of(j, i, [&](unsigned long long g) { return erase_draw_rec(j->seed, g, width, height, *j); },
+                             [&](const DevEraseRec& r) { return erase_sanitise(r, width, height, j->flags); });
     const int frames = erase_frames_of(r);
     const uint32_t k0 = j->seed ^ (uint32_t)(g >> 32) * 0x9E3779B9u, k1 = (uint32_t)g;
     for (int f = 0; f < 2; ++f) {
@@ -832,7 +838,7 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
             }
       }
     }
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    record_out(j, i, r);
     for (int f = 0; f < 2 && occ; ++f) {
       if (!j->occ[f] || !r.count) continue;
       const bool cross = erase_cross(*j, f);
@@ -856,13 +862,7 @@ int ofdg_host_erase(const struct ofdg_erase_job* job, int n_samples, int width, 
 // ofdg_jitter on host arrays (no GPU): the definition of include/ofdg.h pixel by pixel.  The draw, the sanitising, the order's
 // decoding, the operations and the mean are the functions the kernels run (csrc/ofdg_device.h); elements are moved with memcpy.
 int ofdg_jitter_draw(uint32_t seed, long long index, const struct ofdg_jitter_job* ranges, ofdg_jitter_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_jitter_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevJitterJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = jitter_ranges_error(j)) { g_host_error = std::string("ofdg_jitter_draw: ") + why; return OFDG_EINVAL; }
-  const DevJitterRec r = jitter_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_jitter_draw", jitter_ranges_error, jitter_draw_rec, seed, index, ranges, out);
 }
 int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hue) {
   if (!bgr || !out || hue < -kJitterTurn || hue > kJitterTurn) { g_host_error = "ofdg_host_jitter_hue: bgr or out is NULL, or hue outside [-393216, 393216]"; return OFDG_EINVAL; }
@@ -875,19 +875,14 @@ int ofdg_host_jitter_hue(const uint8_t* bgr, uint8_t* out, size_t pixels, int hu
 }
 int ofdg_host_jitter(const struct ofdg_jitter_job* job, int n_samples, int width, int height) {
   const DevJitterJob* const j = reinterpret_cast<const DevJitterJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = jitter_arg_error(j, n_samples, width, height, /*with_work=*/false);
-  if (why) { g_host_error = std::string("ofdg_host_jitter: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_jitter", j, n_samples, width, height, /*pair_rule=*/false,
+                 [](const auto* j, int n, int w, int h) { return jitter_arg_error(j, n, w, h, /*with_work=*/false); }))
+    return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
   std::vector<uint8_t> px[2];  // the bytes of a sample's frame, pixel by pixel: B G R
   for (int i = 0; i < n_samples; ++i) {
-    DevJitterRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = jitter_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
-    r = jitter_sanitise(r);
+    DevJitterRec r = record_of(j, i, [&](unsigned long long g) { return jitter_draw_rec(j->seed, g, *j); }, jitter_sanitise);
     unsigned long long S[2] = {0, 0};
     for (int f = 0; f < 2; ++f) {
       if (!j->src[f]) continue;
@@ -938,7 +933,7 @@ int ofdg_host_jitter(const struct ofdg_jitter_job* job, int n_samples, int width
         }
       }
     }
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    record_out(j, i, r);
   }
   return OFDG_OK;
 }
@@ -955,11 +950,9 @@ int ofdg_host_flow_vis_tables(int32_t atan_q24[257], uint8_t wheel_rgb[55][3]) {
 }
 int ofdg_host_flow_vis(const struct ofdg_flow_vis_job* job, int n_samples, int width, int height) {
   const DevVisJob* const j = reinterpret_cast<const DevVisJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = vis_arg_error(j, n_samples, width, height, /*with_work=*/false);
-  if (why) { g_host_error = std::string("ofdg_host_flow_vis: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_flow_vis", j, n_samples, width, height, /*pair_rule=*/false,
+                 [](const auto* j, int n, int w, int h) { return vis_arg_error(j, n, w, h, /*with_work=*/false); }))
+    return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const FlowPlane fl{j->flow, j->flow_fmt};
   const OccPlane hidden{j->occ, j->occ_fmt};
@@ -1008,11 +1001,7 @@ int ofdg_host_flow_error_colours(uint8_t rgb[10][3]) {
 }
 int ofdg_host_flow_error(const struct ofdg_flow_error_job* job, int n_samples, int width, int height) {
   const DevErrJob* const j = reinterpret_cast<const DevErrJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = err_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_flow_error: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_flow_error", j, n_samples, width, height, /*pair_rule=*/false, err_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const FlowPlane gt{j->gt, j->gt_fmt}, est_f{j->est, j->est_fmt};
   const auto est = [&](size_t i) {
@@ -1078,13 +1067,7 @@ int ofdg_host_flow_error(const struct ofdg_flow_error_job* job, int n_samples, i
 // table, the roundings, the sites and the demosaic are the functions the kernel runs (csrc/ofdg_device.h); elements are moved
 // with memcpy.
 int ofdg_camera_draw(uint32_t seed, long long index, const struct ofdg_camera_job* ranges, ofdg_camera_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_camera_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevCameraJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = camera_ranges_error(j)) { g_host_error = std::string("ofdg_camera_draw: ") + why; return OFDG_EINVAL; }
-  const DevCameraRec r = camera_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_camera_draw", camera_ranges_error, camera_draw_rec, seed, index, ranges, out);
 }
 int ofdg_camera_taps(int sigma_q8, uint32_t out[13]) {
   if (!out || sigma_q8 < 1 || sigma_q8 > kCameraMaxSigma) { g_host_error = "ofdg_camera_taps: out is NULL, or sigma_q8 outside 1..1024"; return OFDG_EINVAL; }
@@ -1095,11 +1078,7 @@ int ofdg_camera_taps(int sigma_q8, uint32_t out[13]) {
 }
 int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width, int height) {
   const DevCameraJob* const j = reinterpret_cast<const DevCameraJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = camera_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_camera: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_camera", j, n_samples, width, height, /*pair_rule=*/false, camera_arg_error)) return OFDG_EINVAL;
   const int W = width, H = height;
   const size_t plane = (size_t)W * H;
   const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
@@ -1107,11 +1086,8 @@ int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width
   std::vector<uint16_t> h8(plane);
   for (int c = 0; c < 3; ++c) { px[c].resize(plane); out[c].resize(plane); }
   for (int i = 0; i < n_samples; ++i) {
-    DevCameraRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = camera_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
-    r = camera_sanitise(r);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    DevCameraRec r = record_of(j, i, [&](unsigned long long g) { return camera_draw_rec(j->seed, g, *j); }, camera_sanitise);
+    record_out(j, i, r);
     for (int f = 0; f < 2; ++f) {
       if (!j->src[f]) continue;
       const int s = r.sigma_q8[f], R = r.radius[f], p = r.bayer;
@@ -1178,13 +1154,7 @@ int ofdg_host_camera(const struct ofdg_camera_job* job, int n_samples, int width
 // colour transforms, the block's passes and the argument rules are the functions the kernel runs (csrc/ofdg_device.h);
 // elements are moved with memcpy.  A frame is read whole before any of it is written, so the in-place form needs no care.
 int ofdg_jpeg_draw(uint32_t seed, long long index, const struct ofdg_jpeg_job* ranges, ofdg_jpeg_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_jpeg_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevJpegJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = jpeg_ranges_error(j)) { g_host_error = std::string("ofdg_jpeg_draw: ") + why; return OFDG_EINVAL; }
-  const DevJpegRec r = jpeg_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_jpeg_draw", jpeg_ranges_error, jpeg_draw_rec, seed, index, ranges, out);
 }
 int ofdg_jpeg_tables(int quality, uint16_t luma[64], uint16_t chroma[64]) {
   if (!luma || !chroma || quality < 1 || quality > 100) { g_host_error = "ofdg_jpeg_tables: luma or chroma is NULL, or quality outside 1..100"; return OFDG_EINVAL; }
@@ -1205,22 +1175,15 @@ int ofdg_host_jpeg_block(const uint8_t in[64], const uint16_t q[64], int32_t lev
 }
 int ofdg_host_jpeg(const struct ofdg_jpeg_job* job, int n_samples, int width, int height) {
   const DevJpegJob* const j = reinterpret_cast<const DevJpegJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = jpeg_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_jpeg: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_jpeg", j, n_samples, width, height, /*pair_rule=*/false, jpeg_arg_error)) return OFDG_EINVAL;
   const int W = width, H = height;
   const size_t plane = (size_t)W * H;
   const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
   std::vector<uint8_t> ycc[3], out[3];   // a sample's frame as Y, Cb, Cr; the decoded B, G, R
   for (int c = 0; c < 3; ++c) { ycc[c].resize(plane); out[c].resize(plane); }
   for (int i = 0; i < n_samples; ++i) {
-    DevJpegRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = jpeg_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
-    r = jpeg_sanitise(r);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    DevJpegRec r = record_of(j, i, [&](unsigned long long g) { return jpeg_draw_rec(j->seed, g, *j); }, jpeg_sanitise);
+    record_out(j, i, r);
     for (int f = 0; f < 2; ++f) {
       if (!j->src[f]) continue;
       const int quality = r.quality[f];
@@ -1303,30 +1266,16 @@ int ofdg_host_jpeg(const struct ofdg_jpeg_job* job, int n_samples, int width, in
 // half-displacement, the tap count, step and coordinate, the tap value, the weights and the argument rules are the functions
 // the kernel runs (csrc/ofdg_device.h); elements are moved with memcpy.
 int ofdg_motion_blur_draw(uint32_t seed, long long index, const struct ofdg_mblur_job* ranges, ofdg_mblur_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_motion_blur_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevMblurJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = mblur_ranges_error(j)) { g_host_error = std::string("ofdg_motion_blur_draw: ") + why; return OFDG_EINVAL; }
-  const DevMblurRec r = mblur_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_motion_blur_draw", mblur_ranges_error, mblur_draw_rec, seed, index, ranges, out);
 }
 int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int width, int height) {
   const DevMblurJob* const j = reinterpret_cast<const DevMblurJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = mblur_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_motion_blur: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_motion_blur", j, n_samples, width, height, /*pair_rule=*/true, mblur_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int ses = fmt_elem_bytes(j->src_fmt), des = fmt_elem_bytes(j->dst_fmt);
   for (int i = 0; i < n_samples; ++i) {
-    DevMblurRec r;
-    if (j->recs) std::memcpy(&r, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(r) * (size_t)i, sizeof(r));
-    else r = mblur_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
-    r = mblur_sanitise(r);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(r) * (size_t)i, &r, sizeof(r));
+    DevMblurRec r = record_of(j, i, [&](unsigned long long g) { return mblur_draw_rec(j->seed, g, *j); }, mblur_sanitise);
+    record_out(j, i, r);
     for (int f = 0; f < 2; ++f) {
       if (!j->src[f]) continue;
       const float s = r.shutter[f];
@@ -1372,12 +1321,7 @@ int ofdg_host_motion_blur(const struct ofdg_mblur_job* job, int n_samples, int w
 // runs (csrc/ofdg_device.h); elements are moved with memcpy.
 int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int width, int height) {
   const DevReprojJob* const j = reinterpret_cast<const DevReprojJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = reproj_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_reproject: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_reproject", j, n_samples, width, height, /*pair_rule=*/true, reproj_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int ses = fmt_elem_bytes(j->img_fmt), des = fmt_elem_bytes(j->dst_fmt);
   const bool with_err = reproj_with_err(*j);
@@ -1475,22 +1419,11 @@ int ofdg_host_reproject(const struct ofdg_reproject_job* job, int n_samples, int
 // the targets, then the fates.  The draw, the sanitising, the displacement, its scaling, the rounded target, the key and the
 // argument rules are the functions the kernels run (csrc/ofdg_device.h); elements are moved with memcpy.
 int ofdg_splat_draw(uint32_t seed, long long index, const struct ofdg_splat_job* ranges, ofdg_splat_rec* out) {
-  if (!ranges || !out) { g_host_error = "ofdg_splat_draw: ranges or out is NULL"; return OFDG_EINVAL; }
-  DevSplatJob j;
-  std::memcpy(&j, ranges, sizeof(j));
-  if (const char* why = splat_ranges_error(j)) { g_host_error = std::string("ofdg_splat_draw: ") + why; return OFDG_EINVAL; }
-  const DevSplatRec r = splat_draw_rec(seed, (unsigned long long)index, j);
-  std::memcpy(out, &r, sizeof(r));
-  return OFDG_OK;
+  return draw_entry("ofdg_splat_draw", splat_ranges_error, splat_draw_rec, seed, index, ranges, out);
 }
 int ofdg_host_splat(const struct ofdg_splat_job* job, int n_samples, int width, int height) {
   const DevSplatJob* const j = reinterpret_cast<const DevSplatJob*>(job);
-  const char* why = !j ? "job is NULL" : (j->width == 0) != (j->height == 0) ? "width and height must both be 0 or both be set"
-                        : (j->width != 0 || j->height != 0) && (j->width != width || j->height != height)
-                        ? "width and height of the job must be 0, 0 or the plane size given" : nullptr;
-  if (!why) why = plane_size_error(width, height);
-  if (!why) why = splat_arg_error(j, n_samples, width, height);
-  if (why) { g_host_error = std::string("ofdg_host_splat: ") + why; return OFDG_EINVAL; }
+  if (!host_open("ofdg_host_splat", j, n_samples, width, height, /*pair_rule=*/true, splat_arg_error)) return OFDG_EINVAL;
   const size_t plane = (size_t)width * height;
   const int ses = fmt_elem_bytes(j->img_fmt), des = fmt_elem_bytes(j->dst_fmt);
   uint8_t* const rows = reinterpret_cast<uint8_t*>(j->rows);
@@ -1502,11 +1435,8 @@ int ofdg_host_splat(const struct ofdg_splat_job* job, int n_samples, int width, 
     } else std::memcpy(static_cast<uint8_t*>(base) + 4 * e, &v, 4);
   };
   for (int i = 0; i < n_samples; ++i) {
-    DevSplatRec rec;
-    if (j->recs) std::memcpy(&rec, reinterpret_cast<const uint8_t*>(j->recs) + sizeof(rec) * (size_t)i, sizeof(rec));
-    else rec = splat_draw_rec(j->seed, (unsigned long long)(j->first_index + i), *j);
-    rec = splat_sanitise(rec);
-    if (j->recs_out) std::memcpy(reinterpret_cast<uint8_t*>(j->recs_out) + sizeof(rec) * (size_t)i, &rec, sizeof(rec));
+    DevSplatRec rec = record_of(j, i, [&](unsigned long long g) { return splat_draw_rec(j->seed, g, *j); }, splat_sanitise);
+    record_out(j, i, rec);
     for (int f = 0; f < 2; ++f) {
       if (!((j->flags >> f) & 1)) continue;
       const int T = rec.t_q8[f];

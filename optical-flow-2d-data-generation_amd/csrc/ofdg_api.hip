@@ -273,15 +273,44 @@ static std::string err_text(uint32_t e) {
 // ---- Post-processing of planes the caller holds: ofdg_object_table, ofdg_flow_stats, ofdg_flow_pyramid, ofdg_crop, ofdg_photo,
 // ofdg_spatial, ofdg_pack, ofdg_boundaries, ofdg_erase, ofdg_jitter, ofdg_camera, ofdg_motion_blur, ofdg_reproject, ofdg_splat, ofdg_flow_vis,
 // ofdg_flow_error, ofdg_lens, ofdg_jpeg
-// How each of them opens: the entry's name in front of every refusal, the alignment of its input planes, its stream.
+// How each of them opens: the entry's name in front of every refusal, the job and its plane size, the alignment of its
+// planes, its stream - in that order, which is the order of the refusals.
 struct PostOp {
   ofdg_ctx* c;
   const char* who;  // the entry's name in the error text
   int fail(const std::string& why) const { c->err = std::string(who) + ": " + why; return OFDG_EINVAL; }
+  // A job-struct entry's first lines: the context, the job as the kernels take it (Dev: what arg_error takes), its plane size
+  // (the job's own, else the context's frame) and the rules the entry shares with its host twin.  more: arg_error's with_work.
+  template <typename Dev, typename Job, typename... More>
+  int open(const Job* job, int n_samples, const char* (*plane_size)(const Dev&, int*, int*),
+           const char* (*arg_error)(const Dev*, int, int, int, More...), const Dev** j, int* W, int* H, More... more) const {
+    if (!c) return OFDG_EINVAL;
+    *j = reinterpret_cast<const Dev*>(job);
+    if (!*j) return fail("job is NULL");
+    *W = c->prm.width, *H = c->prm.height;
+    if (const char* why = plane_size(**j, W, H)) return fail(why);
+    if (const char* why = arg_error(*j, n_samples, *W, *H, more...)) return fail(why);
+    return OFDG_OK;
+  }
+  // a plane the kernels write, or a record array, in 16-byte pieces (NULL: not given); its name in up to three parts
+  int aligned16(const void* p, const char* name, const char* name2 = "", const char* name3 = "") const {
+    return ((uintptr_t)p & 15) ? fail(std::string(name) + name2 + name3 + " must be 16-byte aligned") : OFDG_OK;
+  }
   // an input plane of element type fmt (NULL: not given) at the alignment the kernels read it with (plane_alignment)
   int aligned(const std::string& name, const void* p, int fmt, bool say_fmt = true) const {
     if (!plane_misaligned(p, fmt)) return OFDG_OK;
     return fail(name + " must be " + std::to_string(plane_alignment(fmt)) + "-byte aligned" + (say_fmt ? std::string(" (") + fmt_name(fmt) + ")" : ""));
+  }
+  // the frames and records of a frame-pair job (photo, jitter, camera, jpeg) as those take them
+  template <typename Job>
+  int frame_pair_aligned(const Job& j) const {
+    for (int f = 0; f < 2; ++f) {
+      if (!j.src[f]) continue;
+      OFDG_TRY(aligned(f ? "src[image1]" : "src[image0]", j.src[f], j.src_fmt, /*say_fmt=*/false));
+      OFDG_TRY(aligned16(j.dst[f], f ? "dst[image1]" : "dst[image0]"));
+    }
+    OFDG_TRY(aligned16(j.recs, "recs"));
+    return aligned16(j.recs_out, "recs_out");
   }
   // `stream` of the call; OFDG_STREAM_OWN: the internal stream the last render / forward call worked on
   int stream_of(void* stream, hipStream_t* st) const {
@@ -1675,10 +1704,10 @@ int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void*
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], crop_plane_fmt(*j, k), /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->dst[k], "dst[", kPlane[k], "]"));
   }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   DevCropGrid grid;
@@ -1707,20 +1736,11 @@ int ofdg_crop(ofdg_ctx* c, const struct ofdg_crop_job* job, int n_samples, void*
 
 // Photometric augmentation of caller-given frames: one kernel on `stream` for both frames, every channel and sample.
 int ofdg_photo(ofdg_ctx* c, const struct ofdg_photo_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_photo"};
-  const DevPhotoJob* const j = reinterpret_cast<const DevPhotoJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = photo_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = photo_arg_error(j, n_samples, W, H)) return op.fail(why);
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
-  }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  const DevPhotoJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevPhotoJob>, photo_arg_error, &j, &W, &H));
+  OFDG_TRY(op.frame_pair_aligned(*j));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t plane = (uint32_t)W * (uint32_t)H;
@@ -1737,22 +1757,19 @@ int ofdg_photo(ofdg_ctx* c, const struct ofdg_photo_job* job, int n_samples, voi
 
 // Spatial augmentation of caller-given planes: one kernel on `stream` for every plane, both frames and every sample.
 int ofdg_spatial(ofdg_ctx* c, const struct ofdg_spatial_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_spatial"};
-  const DevSpatialJob* const j = reinterpret_cast<const DevSpatialJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = spatial_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = spatial_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevSpatialJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, spatial_plane_size, spatial_arg_error, &j, &W, &H));
   static const char* const kPlane[kCropPlanes] = {"image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1"};
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     const int fmt = k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8;
     OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->dst[k], "dst[", kPlane[k], "]"));
   }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const bool frame0 = j->src[0] || j->src[2] || j->src[4] || j->src[6], frame1 = j->src[1] || j->src[3] || j->src[5] || j->src[7];
@@ -1773,18 +1790,15 @@ int ofdg_spatial(ofdg_ctx* c, const struct ofdg_spatial_job* job, int n_samples,
 
 // Network-ready packing of caller-given planes: one kernel on `stream` for both frames, the flow and every sample.
 int ofdg_pack(ofdg_ctx* c, const struct ofdg_pack_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_pack"};
-  const DevPackJob* const j = reinterpret_cast<const DevPackJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = pack_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = pack_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevPackJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevPackJob>, pack_arg_error, &j, &W, &H));
   static const char* const kPlane[kPackPlanes] = {"image0", "image1", "flow"};
   for (int k = 0; k < kPackPlanes; ++k) {
     if (!j->src[k]) continue;
     OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], k == OFDG_PACK_FLOW ? j->flow_src_fmt : j->image_src_fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->dst[k], "dst[", kPlane[k], "]"));
   }
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
@@ -1808,20 +1822,17 @@ int ofdg_pack(ofdg_ctx* c, const struct ofdg_pack_job* job, int n_samples, void*
 
 // Motion boundaries of caller-given flows: one kernel on `stream` for both frames, both outputs and every sample.
 int ofdg_boundaries(ofdg_ctx* c, const struct ofdg_boundary_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_boundaries"};
-  const DevBoundaryJob* const j = reinterpret_cast<const DevBoundaryJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = boundary_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = boundary_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevBoundaryJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevBoundaryJob>, boundary_arg_error, &j, &W, &H));
   const bool labels = j->flags & OFDG_BND_LABELS;
   for (int f = 0; f < 2; ++f) {
     if (!j->flow[f]) continue;
     OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
     OFDG_TRY(op.aligned(f ? "label[1]" : "label[0]", j->label[f], OFDG_FMT_U8, /*say_fmt=*/false));
-    if ((uintptr_t)j->edge[f] & 15) return op.fail(std::string(f ? "edge[1]" : "edge[0]") + " must be 16-byte aligned");
-    if ((uintptr_t)j->dist2[f] & 15) return op.fail(std::string(f ? "dist2[1]" : "dist2[0]") + " must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->edge[f], f ? "edge[1]" : "edge[0]"));
+    OFDG_TRY(op.aligned16(j->dist2[f], f ? "dist2[1]" : "dist2[0]"));
   }
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
@@ -1839,22 +1850,19 @@ int ofdg_boundaries(ofdg_ctx* c, const struct ofdg_boundary_job* job, int n_samp
 // Occluder rectangles on caller-given planes, in place: under OFDG_ERASE_MEAN the clearing of `work` and the reduction, then
 // one kernel that paints and marks, all on `stream`.
 int ofdg_erase(ofdg_ctx* c, const struct ofdg_erase_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_erase"};
-  const DevEraseJob* const j = reinterpret_cast<const DevEraseJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = erase_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = erase_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const DevEraseJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevEraseJob>, erase_arg_error, &j, &W, &H, /*with_work=*/true));
   const bool mark = j->flags & OFDG_ERASE_OCC, mean = j->fill == OFDG_ERASE_MEAN;
   for (int f = 0; f < 2; ++f) {
     if ((j->flags >> f) & 1) OFDG_TRY(op.aligned(f ? "image[1]" : "image[0]", j->image[f], j->image_fmt));
     if (mark) OFDG_TRY(op.aligned(f ? "occ[1]" : "occ[0]", j->occ[f], j->occ_fmt));
     if (erase_cross(*j, f)) OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
   }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
-  if (mean && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
+  if (mean) OFDG_TRY(op.aligned16(j->work, "work"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t plane = (uint32_t)W * (uint32_t)H;
@@ -1886,22 +1894,13 @@ int ofdg_erase(ofdg_ctx* c, const struct ofdg_erase_job* job, int n_samples, voi
 // Colour jitter of caller-given frames: where a record may hold a contrast the clearing of `work` and the reduction, then one
 // kernel for both frames and every sample, all on `stream`.
 int ofdg_jitter(ofdg_ctx* c, const struct ofdg_jitter_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_jitter"};
-  const DevJitterJob* const j = reinterpret_cast<const DevJitterJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = jitter_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = jitter_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const DevJitterJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevJitterJob>, jitter_arg_error, &j, &W, &H, /*with_work=*/true));
   const bool mean = jitter_needs_work(*j);
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
-  }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
-  if (mean && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  OFDG_TRY(op.frame_pair_aligned(*j));
+  if (mean) OFDG_TRY(op.aligned16(j->work, "work"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t plane = (uint32_t)W * (uint32_t)H;
@@ -1926,20 +1925,11 @@ int ofdg_jitter(ofdg_ctx* c, const struct ofdg_jitter_job* job, int n_samples, v
 // The camera of caller-given frames - lens blur, Bayer mosaic and demosaic -: one kernel on `stream` for both frames and every
 // sample.
 int ofdg_camera(ofdg_ctx* c, const struct ofdg_camera_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_camera"};
-  const DevCameraJob* const j = reinterpret_cast<const DevCameraJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = camera_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = camera_arg_error(j, n_samples, W, H)) return op.fail(why);
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
-  }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  const DevCameraJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevCameraJob>, camera_arg_error, &j, &W, &H));
+  OFDG_TRY(op.frame_pair_aligned(*j));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t tiles_x = ((uint32_t)W + kCameraTileW - 1) / kCameraTileW, tiles_y = ((uint32_t)H + kCameraTileH - 1) / kCameraTileH;
@@ -1955,21 +1945,18 @@ int ofdg_camera(ofdg_ctx* c, const struct ofdg_camera_job* job, int n_samples, v
 
 // Motion blur of caller-given frames along their flows: one kernel on `stream` for both frames and every sample.
 int ofdg_motion_blur(ofdg_ctx* c, const struct ofdg_mblur_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_motion_blur"};
-  const DevMblurJob* const j = reinterpret_cast<const DevMblurJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = mblur_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = mblur_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevMblurJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevMblurJob>, mblur_arg_error, &j, &W, &H));
   for (int f = 0; f < 2; ++f) {
     if (!j->src[f]) continue;
     OFDG_TRY(op.aligned(f ? "src[1]" : "src[0]", j->src[f], j->src_fmt));
     OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
-    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[1]" : "dst[0]") + " must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->dst[f], f ? "dst[1]" : "dst[0]"));
   }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t tiles_x = ((uint32_t)W + kMblurTileW - 1) / kMblurTileW, tiles_y = ((uint32_t)H + kMblurTileH - 1) / kMblurTileH;
@@ -1989,23 +1976,20 @@ int ofdg_motion_blur(ofdg_ctx* c, const struct ofdg_mblur_job* job, int n_sample
 // Reprojection of caller-given frames through their flows: the rows cleared on `stream` unless they accumulate, then one kernel
 // for both frames and every sample.
 int ofdg_reproject(ofdg_ctx* c, const struct ofdg_reproject_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_reproject"};
-  const DevReprojJob* const j = reinterpret_cast<const DevReprojJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = reproj_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = reproj_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevReprojJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, reproj_plane_size, reproj_arg_error, &j, &W, &H));
   for (int f = 0; f < 2; ++f) {
     OFDG_TRY(op.aligned(f ? "img[1]" : "img[0]", j->img[f], j->img_fmt));
     OFDG_TRY(op.aligned(f ? "flow[1]" : "flow[0]", j->flow[f], j->flow_fmt));
     if (j->occ[f]) OFDG_TRY(op.aligned(f ? "occ[1]" : "occ[0]", j->occ[f], j->occ_fmt));
-    if ((uintptr_t)j->warped[f] & 15) return op.fail(std::string(f ? "warped[1]" : "warped[0]") + " must be 16-byte aligned");
-    if ((uintptr_t)j->err[f] & 15) return op.fail(std::string(f ? "err[1]" : "err[0]") + " must be 16-byte aligned");
-    if ((uintptr_t)j->mask[f] & 15) return op.fail(std::string(f ? "mask[1]" : "mask[0]") + " must be 16-byte aligned");
-    if ((uintptr_t)j->fb2[f] & 15) return op.fail(std::string(f ? "fb2[1]" : "fb2[0]") + " must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->warped[f], f ? "warped[1]" : "warped[0]"));
+    OFDG_TRY(op.aligned16(j->err[f], f ? "err[1]" : "err[0]"));
+    OFDG_TRY(op.aligned16(j->mask[f], f ? "mask[1]" : "mask[0]"));
+    OFDG_TRY(op.aligned16(j->fb2[f], f ? "fb2[1]" : "fb2[0]"));
   }
-  if ((uintptr_t)j->rows & 15) return op.fail("rows must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->rows, "rows"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   if (j->rows && !(j->flags & OFDG_REPROJ_ACCUMULATE)) HIP_OK(c, hipMemsetAsync(j->rows, 0, sizeof(DevReprojRow) * (size_t)n_samples, st));
@@ -2023,13 +2007,10 @@ int ofdg_reproject(ofdg_ctx* c, const struct ofdg_reproject_job* job, int n_samp
 // Splat of caller-given frames along their flows: the key planes (and, unless they accumulate, the rows) cleared on `stream`,
 // then the scatter and the resolve, each one kernel for both frames and every sample.
 int ofdg_splat(ofdg_ctx* c, const struct ofdg_splat_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_splat"};
-  const DevSplatJob* const j = reinterpret_cast<const DevSplatJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = splat_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = splat_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevSplatJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, splat_plane_size, splat_arg_error, &j, &W, &H));
   for (int f = 0; f < 2; ++f) {
     const std::string at = f ? "[1]" : "[0]";
     OFDG_TRY(op.aligned("img" + at, j->img[f], j->img_fmt));
@@ -2038,12 +2019,11 @@ int ofdg_splat(ofdg_ctx* c, const struct ofdg_splat_job* job, int n_samples, voi
     if (j->occ[f]) OFDG_TRY(op.aligned("occ" + at, j->occ[f], j->occ_fmt));
     const std::pair<const char*, const void*> outs[] = {{"keys", j->keys[f]}, {"image", j->image[f]}, {"to_own", j->to_own[f]}, {"to_other", j->to_other[f]},
                                                          {"mask", j->mask[f]}, {"fate", j->fate[f]}};
-    for (const auto& o : outs)
-      if ((uintptr_t)o.second & 15) return op.fail(o.first + at + " must be 16-byte aligned");
+    for (const auto& o : outs) OFDG_TRY(op.aligned16(o.second, o.first, at.c_str()));
   }
-  if ((uintptr_t)j->rows & 15) return op.fail("rows must be 16-byte aligned");
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->rows, "rows"));
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const size_t plane = (size_t)W * (size_t)H;
@@ -2066,19 +2046,16 @@ int ofdg_splat(ofdg_ctx* c, const struct ofdg_splat_job* job, int n_samples, voi
 // The colour-wheel picture of a caller-given flow: unless the scale is fixed the clearing of `work` and the maximum's
 // reduction, then one kernel for every sample, all on `stream`.
 int ofdg_flow_vis(ofdg_ctx* c, const struct ofdg_flow_vis_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_flow_vis"};
-  const DevVisJob* const j = reinterpret_cast<const DevVisJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = vis_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = vis_arg_error(j, n_samples, W, H, /*with_work=*/true)) return op.fail(why);
+  const DevVisJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevVisJob>, vis_arg_error, &j, &W, &H, /*with_work=*/true));
   const bool maxima = vis_needs_work(*j);
   OFDG_TRY(op.aligned("flow", j->flow, j->flow_fmt));
   if (j->occ) OFDG_TRY(op.aligned("occ", j->occ, j->occ_fmt));
-  if ((uintptr_t)j->dst & 15) return op.fail("dst must be 16-byte aligned");
-  if ((uintptr_t)j->rows_out & 15) return op.fail("rows_out must be 16-byte aligned");
-  if (maxima && ((uintptr_t)j->work & 15)) return op.fail("work must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->dst, "dst"));
+  OFDG_TRY(op.aligned16(j->rows_out, "rows_out"));
+  if (maxima) OFDG_TRY(op.aligned16(j->work, "work"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t plane = (uint32_t)W * (uint32_t)H;
@@ -2104,20 +2081,17 @@ int ofdg_flow_vis(ofdg_ctx* c, const struct ofdg_flow_vis_job* job, int n_sample
 // The error of a caller-given estimate against a caller-given ground truth: unless the rows are added to their clearing,
 // then one kernel for every sample, all on `stream`.
 int ofdg_flow_error(ofdg_ctx* c, const struct ofdg_flow_error_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_flow_error"};
-  const DevErrJob* const j = reinterpret_cast<const DevErrJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = err_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = err_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevErrJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevErrJob>, err_arg_error, &j, &W, &H));
   OFDG_TRY(op.aligned("gt", j->gt, j->gt_fmt));
   OFDG_TRY(op.aligned("est", j->est, j->est_fmt, /*say_fmt=*/false));
   if (j->occ) OFDG_TRY(op.aligned("occ", j->occ, j->occ_fmt));
   if ((uintptr_t)j->dist2 & 3) return op.fail("dist2 must be 4-byte aligned");
   if ((uintptr_t)j->rows & 7) return op.fail("rows must be 8-byte aligned");
-  if ((uintptr_t)j->epe & 15) return op.fail("epe must be 16-byte aligned");
-  if ((uintptr_t)j->picture & 15) return op.fail("picture must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->epe, "epe"));
+  OFDG_TRY(op.aligned16(j->picture, "picture"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   if (j->rows && !(j->flags & OFDG_ERR_ACCUMULATE))
@@ -2138,22 +2112,19 @@ int ofdg_flow_error(ofdg_ctx* c, const struct ofdg_flow_error_job* job, int n_sa
 
 // The lens on caller-given planes: one kernel on `stream` for every plane, both frames and every sample.
 int ofdg_lens(ofdg_ctx* c, const struct ofdg_lens_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_lens"};
-  const DevLensJob* const j = reinterpret_cast<const DevLensJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = lens_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = lens_arg_error(j, n_samples, W, H)) return op.fail(why);
+  const DevLensJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, lens_plane_size, lens_arg_error, &j, &W, &H));
   static const char* const kPlane[kCropPlanes] = {"image0", "image1", "flow", "flow1", "occ0", "occ1", "label0", "label1"};
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     const int fmt = k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8;
     OFDG_TRY(op.aligned(std::string("src[") + kPlane[k] + "]", j->src[k], fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[k] & 15) return op.fail(std::string("dst[") + kPlane[k] + "] must be 16-byte aligned");
+    OFDG_TRY(op.aligned16(j->dst[k], "dst[", kPlane[k], "]"));
   }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  OFDG_TRY(op.aligned16(j->recs, "recs"));
+  OFDG_TRY(op.aligned16(j->recs_out, "recs_out"));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const bool frame0 = j->src[0] || j->src[2] || j->src[4] || j->src[6], frame1 = j->src[1] || j->src[3] || j->src[5] || j->src[7];
@@ -2175,20 +2146,11 @@ int ofdg_lens(ofdg_ctx* c, const struct ofdg_lens_job* job, int n_samples, void*
 // Block compression of caller-given frames, in place or into other frames: one kernel on `stream` for both frames and every
 // sample.  The grid covers the block grid at its largest phase (15 on either axis).
 int ofdg_jpeg(ofdg_ctx* c, const struct ofdg_jpeg_job* job, int n_samples, void* stream) {
-  if (!c) return OFDG_EINVAL;
   const PostOp op{c, "ofdg_jpeg"};
-  const DevJpegJob* const j = reinterpret_cast<const DevJpegJob*>(job);
-  if (!j) return op.fail("job is NULL");
-  int W = c->prm.width, H = c->prm.height;
-  if (const char* why = jpeg_plane_size(*j, &W, &H)) return op.fail(why);
-  if (const char* why = jpeg_arg_error(j, n_samples, W, H)) return op.fail(why);
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    OFDG_TRY(op.aligned(f ? "src[image1]" : "src[image0]", j->src[f], j->src_fmt, /*say_fmt=*/false));
-    if ((uintptr_t)j->dst[f] & 15) return op.fail(std::string(f ? "dst[image1]" : "dst[image0]") + " must be 16-byte aligned");
-  }
-  if ((uintptr_t)j->recs & 15) return op.fail("recs must be 16-byte aligned");
-  if ((uintptr_t)j->recs_out & 15) return op.fail("recs_out must be 16-byte aligned");
+  const DevJpegJob* j;
+  int W, H;
+  OFDG_TRY(op.open(job, n_samples, job_plane_size<DevJpegJob>, jpeg_arg_error, &j, &W, &H));
+  OFDG_TRY(op.frame_pair_aligned(*j));
   hipStream_t st;
   OFDG_TRY(op.stream_of(stream, &st));
   const uint32_t tiles_x = ((uint32_t)W + 15u + kJpegRegion - 1) / kJpegRegion, tiles_y = ((uint32_t)H + 15u + kJpegRegion - 1) / kJpegRegion;

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/ofdg_detmath.h"
 #include "../../include/ofdg.h"  // the ABI: each Dev* record below that restates one of its structs is held to it next to its definition
@@ -248,6 +249,76 @@ inline const char* plane_size_error(int width, int height) {
   return nullptr;
 }
 
+// ---- Argument rules every post-processing operation shares (host code only) ------------------------------------------------
+// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
+constexpr const char* kPlanePairRule = "width and height must both be 0 or both be set";  // (host_api.cpp's host_open says it too)
+template <typename Job>
+inline const char* job_plane_size(const Job& j, int* width, int* height) {
+  if ((j.width == 0) != (j.height == 0)) return kPlanePairRule;
+  if (j.width != 0) { *width = j.width; *height = j.height; }
+  return plane_size_error(*width, *height);
+}
+// The byte ranges a job names, at most N of them, and the rule on them: a written range may meet no other range of the job,
+// except the one it is in place with (dst[f] == src[f] in one format).  Ranges that touch (hi == lo) do not meet.
+struct Range { uintptr_t lo, hi; bool written; int in_place_with; };
+template <int N>
+struct RangeSet {
+  Range r[N];
+  int n = 0;
+  // -> the range's index, for a partner's in_place_with.  N is an operation's own count of pointers: one add too many is a
+  // mistake in that operation's rules, never a caller's input, and ends the process rather than write past r.
+  int add(const void* p, unsigned long long bytes, bool written, int in_place_with = -1) {
+    if (n >= N) abort();
+    r[n] = Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, written, in_place_with};
+    return n++;
+  }
+  void add_if(const void* p, unsigned long long bytes, bool written) {
+    if (p) add(p, bytes, written);
+  }
+  // `why` when a written range meets another one, in the order the ranges were added; else nullptr
+  const char* overlap(const char* why) const {
+    for (int a = 0; a < n; ++a)
+      for (int b = 0; b < n; ++b)
+        if (a != b && r[a].written && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return why;
+    return nullptr;
+  }
+};
+// The frame-pair jobs (photo, jitter, camera, jpeg; motion blur as far as frame_pair_fmt_error): src[2], dst[2], src_fmt,
+// dst_fmt, recs, recs_out under the same names.  Three pieces, since each operation has rules of its own between them.
+template <typename Job>
+inline const char* frame_pair_fmt_error(const Job* j, int n, int width, int height) {
+  if (!j) return "job is NULL";
+  if (n < 1) return "n_samples must be at least 1";
+  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
+  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  return nullptr;
+}
+template <typename Job>
+inline const char* frame_pair_frames_error(const Job* j) {
+  int frames = 0;
+  for (int f = 0; f < 2; ++f) {
+    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
+    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
+    frames += j->src[f] ? 1 : 0;
+  }
+  if (!frames) return "src: no frame is set";
+  return nullptr;
+}
+// src and dst of each frame set, then recs and recs_out: six ranges at most.  in_place_form: does the operation take dst[f] == src[f]?
+template <int N, typename Job>
+inline void frame_pair_ranges(RangeSet<N>& set, const Job* j, int n, int width, int height, bool in_place_form) {
+  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
+  for (int f = 0; f < 2; ++f) {
+    if (!j->src[f]) continue;
+    const bool in_place = in_place_form && j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
+    const int s = set.add(j->src[f], elems * fmt_elem_bytes(j->src_fmt), false);
+    set.add(j->dst[f], elems * fmt_elem_bytes(j->dst_fmt), true, in_place ? s : -1);
+  }
+  set.add_if(j->recs, (unsigned long long)n * sizeof(*j->recs), false);
+  set.add_if(j->recs_out, (unsigned long long)n * sizeof(*j->recs), true);
+}
+
 // ---- Training crop (ofdg_crop, include/ofdg.h) -----------------------------------------------------------------------------
 // What the device entry, the kernel and the host twin share: the job as the kernel takes it, the record's draw and its
 // sanitising, the window test of the occlusion rule and the argument rules.
@@ -344,21 +415,16 @@ inline const char* crop_arg_error(const DevCropJob* j, int n, int width, int hei
   if ((j->flags & OFDG_CROP_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_CROP_OCC_WINDOW with occ0 needs flow";
   if ((j->flags & OFDG_CROP_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_CROP_OCC_WINDOW with occ1 needs flow1";
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[2 * kCropPlanes + 2];
-  int nr = 0;
+  RangeSet<2 * kCropPlanes + 2> r;
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     const unsigned long long per = (unsigned long long)n * crop_channels(k) * crop_elem_bytes(*j, k);
-    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * width * height), false};
-    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * j->crop_w * j->crop_h), true};
+    r.add(j->src[k], per * width * height, false);
+    r.add(j->dst[k], per * j->crop_w * j->crop_h, true);
   }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * 16, false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * 16, true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->recs, (unsigned long long)n * 16, false);
+  r.add_if(j->recs_out, (unsigned long long)n * 16, true);
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Photometric augmentation (ofdg_photo, include/ofdg.h) -----------------------------------------------------------------
@@ -470,12 +536,6 @@ OFDG_HD_FN float photo_add_noise(float v, float scale, uint32_t word) {
   o = o < 255.0f ? o : 255.0f;
   return o;
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* photo_plane_size(const DevPhotoJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The nine ranges of the draw: the first that is negative, NaN or infinite, or nullptr.
 inline const char* photo_ranges_error(const DevPhotoJob& job) {
   const DevPhotoJob* const j = &job;
@@ -490,41 +550,16 @@ inline const char* photo_ranges_error(const DevPhotoJob& job) {
   return nullptr;
 }
 // The argument rules ofdg_photo and ofdg_host_photo share: the first rule broken, or nullptr.  width, height: what
-// photo_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* photo_arg_error(const DevPhotoJob* j, int n, int width, int height) {
-  if (!j) return "job is NULL";
-  if (n < 1) return "n_samples must be at least 1";
-  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
-  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = frame_pair_fmt_error(j, n, width, height)) return why;
   if (j->flags != 0) return "flags must be 0";
   if (j->reserved != 0) return "reserved must be 0";
   if (const char* why = photo_ranges_error(*j)) return why;
-  int frames = 0;
-  for (int f = 0; f < 2; ++f) {
-    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
-    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
-    frames += j->src[f] ? 1 : 0;
-  }
-  if (!frames) return "src: no frame is set";
-  // a destination range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
-  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
-  Range r[6];
-  int nr = 0;
-  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
-    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
-    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
-    nr += 2;
-  }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * 64, false, -1};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * 64, true, -1};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  if (const char* why = frame_pair_frames_error(j)) return why;
+  RangeSet<6> r;
+  frame_pair_ranges(r, j, n, width, height, true);
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Spatial augmentation (ofdg_spatial, include/ofdg.h) -------------------------------------------------------------------
@@ -710,9 +745,7 @@ OFDG_HD_FN uint32_t spatial_half_bits(float f) {
 }
 // The source size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
 inline const char* spatial_plane_size(const DevSpatialJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  if (const char* why = plane_size_error(*width, *height)) return why;
+  if (const char* why = job_plane_size(j, width, height)) return why;
   if (*width > kSpatialMaxSide || *height > kSpatialMaxSide) return "width and height must not exceed 2^20";
   return nullptr;
 }
@@ -753,22 +786,17 @@ inline const char* spatial_arg_error(const DevSpatialJob* j, int n, int width, i
   if ((j->flags & OFDG_SPATIAL_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_SPATIAL_OCC_WINDOW with occ0 needs flow";
   if ((j->flags & OFDG_SPATIAL_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_SPATIAL_OCC_WINDOW with occ1 needs flow1";
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[2 * kCropPlanes + 2];
-  int nr = 0;
+  RangeSet<2 * kCropPlanes + 2> r;
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     const int es = fmt_elem_bytes(k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8);
     const unsigned long long per = (unsigned long long)n * crop_channels(k) * es;
-    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * width * height), false};
-    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * j->out_w * j->out_h), true};
+    r.add(j->src[k], per * width * height, false);
+    r.add(j->dst[k], per * j->out_w * j->out_h, true);
   }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevSpatialRec), false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevSpatialRec), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->recs, (unsigned long long)n * sizeof(DevSpatialRec), false);
+  r.add_if(j->recs_out, (unsigned long long)n * sizeof(DevSpatialRec), true);
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Network-ready packing (ofdg_pack, include/ofdg.h) ---------------------------------------------------------------------
@@ -822,15 +850,9 @@ OFDG_HD_FN size_t pack_dst_index(int layout, int C, int i, int cd, int y, int x,
   if (layout == OFDG_PACK_NHWC) return (((size_t)i * height + y) * width + x) * C + cd;
   return (((size_t)i * C + cd) * height + y) * width + x;
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* pack_plane_size(const DevPackJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 inline bool pack_finite(float v) { return v >= -3.4028234663852886e38f && v <= 3.4028234663852886e38f; }
 // The argument rules ofdg_pack and ofdg_host_pack share: the first rule broken, or nullptr.  width, height: what
-// pack_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* pack_arg_error(const DevPackJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (n < 1) return "n_samples must be at least 1";
@@ -861,19 +883,14 @@ inline const char* pack_arg_error(const DevPackJob* j, int n, int width, int hei
   if (concat && j->dst[OFDG_PACK_IMAGE1]) return "flags: OFDG_PACK_CONCAT takes dst[image1] NULL";
   if (!planes) return "src: no plane is set";
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[2 * kPackPlanes];
-  int nr = 0;
+  RangeSet<2 * kPackPlanes> r;
   const unsigned long long per = (unsigned long long)n * width * height;
   for (int k = 0; k < kPackPlanes; ++k) {
     const bool flow = k == OFDG_PACK_FLOW;
-    if (j->src[k]) r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + (uintptr_t)(per * (flow ? 2 : 3) * fmt_elem_bytes(flow ? j->flow_src_fmt : j->image_src_fmt)), false};
-    if (j->dst[k]) r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + (uintptr_t)(per * pack_channels(k, j->flags) * fmt_elem_bytes(flow ? j->flow_dst_fmt : j->image_dst_fmt)), true};
+    r.add_if(j->src[k], per * (flow ? 2 : 3) * fmt_elem_bytes(flow ? j->flow_src_fmt : j->image_src_fmt), false);
+    r.add_if(j->dst[k], per * pack_channels(k, j->flags) * fmt_elem_bytes(flow ? j->flow_dst_fmt : j->image_dst_fmt), true);
   }
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Motion boundaries (ofdg_boundaries, include/ofdg.h) -------------------------------------------------------------------
@@ -906,14 +923,8 @@ OFDG_HD_FN bool boundary_step(float up, float vp, float uq, float vq, float t2) 
   return d2 > t2;
 }
 OFDG_HD_FN float boundary_threshold(float min_step) { return min_step * min_step; }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* boundary_plane_size(const DevBoundaryJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The argument rules ofdg_boundaries and ofdg_host_boundaries share: the first rule broken, or nullptr.  width, height: what
-// boundary_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* boundary_arg_error(const DevBoundaryJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (const char* why = batch_plane_error(n, width, height)) return why;
@@ -931,21 +942,16 @@ inline const char* boundary_arg_error(const DevBoundaryJob* j, int n, int width,
   if (!(j->min_step >= 0.0f && j->min_step <= 3.4028234663852886e38f)) return "min_step must be finite and not negative";
   if ((j->dist2[0] || j->dist2[1]) && (j->radius < 1 || j->radius > kBndMaxRadius)) return "radius must lie in 1..15";
   // an output may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[8];
-  int nr = 0;
+  RangeSet<8> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
   for (int f = 0; f < 2; ++f) {
     if (!j->flow[f]) continue;
-    r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
-    if (j->label[f]) r[nr++] = Range{(uintptr_t)j->label[f], (uintptr_t)j->label[f] + (uintptr_t)plane, false};
-    if (j->edge[f]) r[nr++] = Range{(uintptr_t)j->edge[f], (uintptr_t)j->edge[f] + (uintptr_t)plane, true};
-    if (j->dist2[f]) r[nr++] = Range{(uintptr_t)j->dist2[f], (uintptr_t)j->dist2[f] + (uintptr_t)plane, true};
+    r.add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
+    r.add_if(j->label[f], plane, false);
+    r.add_if(j->edge[f], plane, true);
+    r.add_if(j->dist2[f], plane, true);
   }
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "edge, dist2: an output range overlaps another range of the job";
-  return nullptr;
+  return r.overlap("edge, dist2: an output range overlaps another range of the job");
 }
 
 // ---- Occluder rectangles (ofdg_erase, include/ofdg.h) ----------------------------------------------------------------------
@@ -1099,12 +1105,6 @@ OFDG_HD_FN bool erase_marks(const DevEraseRec& r, int f, bool cross, int x, int 
 }
 // does the map of frame f need its flow?  (OFDG_ERASE_OCC, the map given, frame 1 - f flagged)
 OFDG_HD_FN bool erase_cross(const DevEraseJob& j, int f) { return (j.flags & OFDG_ERASE_OCC) && j.occ[f] && ((j.flags >> (1 - f)) & 1); }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* erase_plane_size(const DevEraseJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // What the draw reads of a job: the first rule broken, or nullptr.
 inline const char* erase_ranges_error(const DevEraseJob& j) {
   if (j.flags & ~(OFDG_ERASE_FRAME0 | OFDG_ERASE_FRAME1 | OFDG_ERASE_OCC)) return "flags holds unknown bits";
@@ -1115,7 +1115,7 @@ inline const char* erase_ranges_error(const DevEraseJob& j) {
   return nullptr;
 }
 // The argument rules ofdg_erase and ofdg_host_erase share: the first rule broken, or nullptr.  width, height: what
-// erase_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+// job_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
 inline const char* erase_arg_error(const DevEraseJob* j, int n, int width, int height, bool with_work) {
   if (!j) return "job is NULL";
   if (n < 1) return "n_samples must be at least 1";
@@ -1146,22 +1146,17 @@ inline const char* erase_arg_error(const DevEraseJob* j, int n, int width, int h
   const bool work = with_work && j->fill == OFDG_ERASE_MEAN;
   if (work && !j->work) return "work is NULL under OFDG_ERASE_MEAN";
   // a written range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[10];
-  int nr = 0;
+  RangeSet<9> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
   for (int f = 0; f < 2; ++f) {
-    if (((j->flags >> f) & 1)) r[nr++] = Range{(uintptr_t)j->image[f], (uintptr_t)j->image[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->image_fmt)), true};
-    if (occ && j->occ[f]) r[nr++] = Range{(uintptr_t)j->occ[f], (uintptr_t)j->occ[f] + (uintptr_t)(plane * fmt_elem_bytes(j->occ_fmt)), true};
-    if (erase_cross(*j, f)) r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
+    if (((j->flags >> f) & 1)) r.add(j->image[f], plane * 3 * fmt_elem_bytes(j->image_fmt), true);
+    if (occ && j->occ[f]) r.add(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), true);
+    if (erase_cross(*j, f)) r.add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
   }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevEraseRec), false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevEraseRec), true};
-  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(DevEraseWork), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->recs, (unsigned long long)n * sizeof(DevEraseRec), false);
+  r.add_if(j->recs_out, (unsigned long long)n * sizeof(DevEraseRec), true);
+  if (work) r.add(j->work, (unsigned long long)n * sizeof(DevEraseWork), true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Colour jitter (ofdg_jitter, include/ofdg.h) ---------------------------------------------------------------------------
@@ -1319,12 +1314,6 @@ OFDG_HD_FN void jitter_op(int op, const JitterFrame& p, int mean, int& B, int& G
 }
 // (2 S + N) / (2 N): the mean of N luminances, to nearest, a tie upwards
 OFDG_HD_FN int32_t jitter_mean_byte(unsigned long long S, unsigned long long N) { return (int32_t)((2ull * S + N) / (2ull * N)); }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* jitter_plane_size(const DevJitterJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The five ranges of the draw: the first that is negative, NaN, infinite or above its bound, or nullptr.
 inline const char* jitter_ranges_error(const DevJitterJob& j) {
   if (!(j.brightness >= 0.0f && j.brightness <= 3.0f)) return "brightness must lie in [0, 3]";
@@ -1338,44 +1327,19 @@ inline const char* jitter_ranges_error(const DevJitterJob& j) {
 // host: they always can.
 inline bool jitter_needs_work(const DevJitterJob& j) { return j.recs || jitter_amp(j.contrast, 65536.0f) != 0; }
 // The argument rules ofdg_jitter and ofdg_host_jitter share: the first rule broken, or nullptr.  width, height: what
-// jitter_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+// job_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
 inline const char* jitter_arg_error(const DevJitterJob* j, int n, int width, int height, bool with_work) {
-  if (!j) return "job is NULL";
-  if (n < 1) return "n_samples must be at least 1";
-  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
-  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = frame_pair_fmt_error(j, n, width, height)) return why;
   if (j->flags != 0) return "flags must be 0";
   if (j->reserved != 0) return "reserved must be 0";
   if (const char* why = jitter_ranges_error(*j)) return why;
-  int frames = 0;
-  for (int f = 0; f < 2; ++f) {
-    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
-    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
-    frames += j->src[f] ? 1 : 0;
-  }
-  if (!frames) return "src: no frame is set";
+  if (const char* why = frame_pair_frames_error(j)) return why;
   const bool work = with_work && jitter_needs_work(*j);
   if (work && !j->work) return "work is NULL where a record may hold a contrast";
-  // a written range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
-  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
-  Range r[7];
-  int nr = 0;
-  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
-    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
-    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
-    nr += 2;
-  }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevJitterRec), false, -1};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevJitterRec), true, -1};
-  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(DevJitterWork), true, -1};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  RangeSet<7> r;
+  frame_pair_ranges(r, j, n, width, height, true);
+  if (work) r.add(j->work, (unsigned long long)n * sizeof(DevJitterWork), true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Camera (ofdg_camera, include/ofdg.h) ----------------------------------------------------------------------------------
@@ -1484,12 +1448,6 @@ OFDG_HD_FN void camera_demosaic(int a, int b, uint32_t c, uint32_t sh, uint32_t 
     o[1] = c; o[b ? 0 : 2] = hz; o[b ? 2 : 0] = vt;
   }
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* camera_plane_size(const DevCameraJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The ranges of the draw and the pattern: the first rule broken, or nullptr.
 inline const char* camera_ranges_error(const DevCameraJob& j) {
   if (!(j.sigma_min >= 0.0f && j.sigma_min <= 4.0f)) return "sigma_min must lie in [0, 4]";
@@ -1502,39 +1460,16 @@ inline const char* camera_ranges_error(const DevCameraJob& j) {
   return nullptr;
 }
 // The argument rules ofdg_camera and ofdg_host_camera share: the first rule broken, or nullptr.  width, height: what
-// camera_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* camera_arg_error(const DevCameraJob* j, int n, int width, int height) {
-  if (!j) return "job is NULL";
-  if (n < 1) return "n_samples must be at least 1";
-  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
-  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = frame_pair_fmt_error(j, n, width, height)) return why;
   if (j->flags != 0) return "flags must be 0";
   if (j->reserved != 0) return "reserved must be 0";
   if (const char* why = camera_ranges_error(*j)) return why;
-  int frames = 0;
-  for (int f = 0; f < 2; ++f) {
-    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
-    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
-    frames += j->src[f] ? 1 : 0;
-  }
-  if (!frames) return "src: no frame is set";
-  // no in-place form: a written range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[6];
-  int nr = 0;
-  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    r[nr++] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false};
-    r[nr++] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true};
-  }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevCameraRec), false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevCameraRec), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  if (const char* why = frame_pair_frames_error(j)) return why;
+  RangeSet<6> r;
+  frame_pair_ranges(r, j, n, width, height, false);  // no in-place form: a pixel reads its neighbours
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Lens (ofdg_lens, include/ofdg.h) --------------------------------------------------------------------------------------
@@ -1696,9 +1631,7 @@ OFDG_HD_FN float lens_nan() {  // 0x7FC00000: what an unsolvable pixel's flow ho
 }
 // The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
 inline const char* lens_plane_size(const DevLensJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  if (const char* why = plane_size_error(*width, *height)) return why;
+  if (const char* why = job_plane_size(j, width, height)) return why;
   if (*width > kSpatialMaxSide || *height > kSpatialMaxSide) return "width and height must not exceed 2^20";
   if ((unsigned long long)*width * (unsigned long long)*height >= (1ull << 31)) return "width * height must be below 2^31";
   return nullptr;
@@ -1732,22 +1665,17 @@ inline const char* lens_arg_error(const DevLensJob* j, int n, int width, int hei
   if ((j->flags & OFDG_LENS_OCC_WINDOW) && j->src[OFDG_CROP_OCC0] && !j->src[OFDG_CROP_FLOW]) return "flags: OFDG_LENS_OCC_WINDOW with occ0 needs flow";
   if ((j->flags & OFDG_LENS_OCC_WINDOW) && j->src[OFDG_CROP_OCC1] && !j->src[OFDG_CROP_FLOW1]) return "flags: OFDG_LENS_OCC_WINDOW with occ1 needs flow1";
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[2 * kCropPlanes + 2];
-  int nr = 0;
+  RangeSet<2 * kCropPlanes + 2> r;
   for (int k = 0; k < kCropPlanes; ++k) {
     if (!j->src[k]) continue;
     const int es = fmt_elem_bytes(k < 2 ? j->image_fmt : k < 4 ? j->flow_fmt : k < 6 ? j->occ_fmt : OFDG_FMT_U8);
-    const uintptr_t bytes = (uintptr_t)((unsigned long long)n * crop_channels(k) * es * width * height);
-    r[nr++] = Range{(uintptr_t)j->src[k], (uintptr_t)j->src[k] + bytes, false};
-    r[nr++] = Range{(uintptr_t)j->dst[k], (uintptr_t)j->dst[k] + bytes, true};
+    const unsigned long long bytes = (unsigned long long)n * crop_channels(k) * es * width * height;
+    r.add(j->src[k], bytes, false);
+    r.add(j->dst[k], bytes, true);
   }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevLensRec), false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevLensRec), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->recs, (unsigned long long)n * sizeof(DevLensRec), false);
+  r.add_if(j->recs_out, (unsigned long long)n * sizeof(DevLensRec), true);
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Block compression (ofdg_jpeg, include/ofdg.h) -------------------------------------------------------------------------
@@ -1878,12 +1806,6 @@ inline void jpeg_block(const uint8_t* in, const uint16_t* q, int32_t* levels, ui
       out[y * 8 + x] = (uint8_t)jpeg_sample(s);
     }
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* jpeg_plane_size(const DevJpegJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The ranges of the draw, subsample and flags: the first rule broken, or nullptr.
 inline const char* jpeg_ranges_error(const DevJpegJob& j) {
   if (j.flags != 0 && j.flags != OFDG_JPEG_PHASE) return "flags must be 0 or OFDG_JPEG_PHASE";
@@ -1897,40 +1819,15 @@ inline const char* jpeg_ranges_error(const DevJpegJob& j) {
   return nullptr;
 }
 // The argument rules ofdg_jpeg and ofdg_host_jpeg share: the first rule broken, or nullptr.  width, height: what
-// jpeg_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* jpeg_arg_error(const DevJpegJob* j, int n, int width, int height) {
-  if (!j) return "job is NULL";
-  if (n < 1) return "n_samples must be at least 1";
-  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
-  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = frame_pair_fmt_error(j, n, width, height)) return why;
   if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
   if (const char* why = jpeg_ranges_error(*j)) return why;
-  int frames = 0;
-  for (int f = 0; f < 2; ++f) {
-    if (j->src[f] && !j->dst[f]) return "dst: a frame has a source and no destination";
-    if (!j->src[f] && j->dst[f]) return "src: a frame has a destination and no source";
-    frames += j->src[f] ? 1 : 0;
-  }
-  if (!frames) return "src: no frame is set";
-  // a written range may meet no other range of the job, but for the in-place form: dst[f] == src[f] in one format
-  struct Range { uintptr_t lo, hi; bool dst; int in_place_with; };
-  Range r[6];
-  int nr = 0;
-  const unsigned long long elems = 3ull * (unsigned long long)n * width * height;
-  for (int f = 0; f < 2; ++f) {
-    if (!j->src[f]) continue;
-    const bool in_place = j->dst[f] == j->src[f] && j->src_fmt == j->dst_fmt;
-    r[nr] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(elems * fmt_elem_bytes(j->src_fmt)), false, -1};
-    r[nr + 1] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(elems * fmt_elem_bytes(j->dst_fmt)), true, in_place ? nr : -1};
-    nr += 2;
-  }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevJpegRec), false, -1};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevJpegRec), true, -1};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].in_place_with != b && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  if (const char* why = frame_pair_frames_error(j)) return why;
+  RangeSet<6> r;
+  frame_pair_ranges(r, j, n, width, height, true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Motion blur (ofdg_motion_blur, include/ofdg.h) ------------------------------------------------------------------------
@@ -2030,12 +1927,6 @@ OFDG_HD_FN uint32_t mblur_weight(int k, int m) {
 }
 // the byte of a weighted sum of taps (the weights sum to 65536, a tap is at most 65280: no overflow)
 OFDG_HD_FN uint32_t mblur_byte(uint32_t S) { return (S + (1u << 23)) >> 24; }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* mblur_plane_size(const DevMblurJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // What the draw reads of a job: the first rule broken, or nullptr.
 inline const char* mblur_ranges_error(const DevMblurJob& j) {
   if (!(j.prob >= 0.0f && j.prob <= 1.0f)) return "prob must lie in [0, 1]";
@@ -2046,13 +1937,9 @@ inline const char* mblur_ranges_error(const DevMblurJob& j) {
   return nullptr;
 }
 // The argument rules ofdg_motion_blur and ofdg_host_motion_blur share: the first rule broken, or nullptr.  width, height:
-// what mblur_plane_size gave.  Alignment is asked by the device entry only.
+// what job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* mblur_arg_error(const DevMblurJob* j, int n, int width, int height) {
-  if (!j) return "job is NULL";
-  if (n < 1) return "n_samples must be at least 1";
-  if (3ull * (unsigned long long)width * (unsigned long long)height >= (1ull << 32)) return "3 * width * height must be below 2^32";
-  if (j->src_fmt != OFDG_FMT_F32 && j->src_fmt != OFDG_FMT_U8) return "src_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
-  if (j->dst_fmt != OFDG_FMT_F32 && j->dst_fmt != OFDG_FMT_U8) return "dst_fmt must be OFDG_FMT_F32 or OFDG_FMT_U8";
+  if (const char* why = frame_pair_fmt_error(j, n, width, height)) return why;  // (as far as the rules coincide: a frame here has a flow)
   if (j->flow_fmt != OFDG_FMT_F32 && j->flow_fmt != OFDG_FMT_F16) return "flow_fmt must be OFDG_FMT_F32 or OFDG_FMT_F16";
   if (j->flags != 0) return "flags must be 0";
   if (j->reserved[0] != 0 || j->reserved[1] != 0) return "reserved must be 0";
@@ -2068,22 +1955,17 @@ inline const char* mblur_arg_error(const DevMblurJob* j, int n, int width, int h
   if (!j->recs)
     if (const char* why = mblur_ranges_error(*j)) return why;
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[8];
-  int nr = 0;
+  RangeSet<8> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
   for (int f = 0; f < 2; ++f) {
     if (!j->src[f]) continue;
-    r[nr++] = Range{(uintptr_t)j->src[f], (uintptr_t)j->src[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->src_fmt)), false};
-    r[nr++] = Range{(uintptr_t)j->dst[f], (uintptr_t)j->dst[f] + (uintptr_t)(plane * 3 * fmt_elem_bytes(j->dst_fmt)), true};
-    r[nr++] = Range{(uintptr_t)j->flow[f], (uintptr_t)j->flow[f] + (uintptr_t)(plane * 2 * fmt_elem_bytes(j->flow_fmt)), false};
+    r.add(j->src[f], plane * 3 * fmt_elem_bytes(j->src_fmt), false);
+    r.add(j->dst[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
+    r.add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
   }
-  if (j->recs) r[nr++] = Range{(uintptr_t)j->recs, (uintptr_t)j->recs + (uintptr_t)n * sizeof(DevMblurRec), false};
-  if (j->recs_out) r[nr++] = Range{(uintptr_t)j->recs_out, (uintptr_t)j->recs_out + (uintptr_t)n * sizeof(DevMblurRec), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "dst: a destination range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->recs, (unsigned long long)n * sizeof(DevMblurRec), false);
+  r.add_if(j->recs_out, (unsigned long long)n * sizeof(DevMblurRec), true);
+  return r.overlap("dst: a destination range overlaps another range of the job");
 }
 
 // ---- Reprojection (ofdg_reproject, include/ofdg.h) -------------------------------------------------------------------------
@@ -2171,14 +2053,9 @@ OFDG_HD_FN float reproj_fb2(long long e2) { return (float)e2 * 1.52587890625e-05
 // what a frame's block of the row can hold, from the inputs that are given
 OFDG_HD_FN bool reproj_with_err(const DevReprojJob& j) { return j.img[0] && j.img[1]; }
 OFDG_HD_FN bool reproj_with_fb(const DevReprojJob& j, int f) { return j.flow[1 - f] != nullptr; }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* reproj_plane_size(const DevReprojJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
+inline const char* reproj_plane_size(const DevReprojJob& j, int* width, int* height) { return job_plane_size(j, width, height); }  // (the name tests/test_reproject.py asks for)
 // The argument rules ofdg_reproject and ofdg_host_reproject share: the first rule broken, or nullptr.  width, height: what
-// reproj_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* reproj_arg_error(const DevReprojJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (n < 1) return "n_samples must be at least 1";
@@ -2206,27 +2083,19 @@ inline const char* reproj_arg_error(const DevReprojJob* j, int n, int width, int
   }
   if (!any) return "rows: no output is given";
   // no in-place form: a destination range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[16];
-  int nr = 0;
+  RangeSet<15> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
-  const auto add = [&](const void* p, unsigned long long bytes, bool dst) {
-    if (p) r[nr++] = Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, dst};
-  };
   for (int f = 0; f < 2; ++f) {
-    add(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
-    add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
-    add(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
-    add(j->warped[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
-    add(j->err[f], plane, true);
-    add(j->mask[f], plane, true);
-    add(j->fb2[f], plane * 4, true);
+    r.add_if(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
+    r.add_if(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
+    r.add_if(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
+    r.add_if(j->warped[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
+    r.add_if(j->err[f], plane, true);
+    r.add_if(j->mask[f], plane, true);
+    r.add_if(j->fb2[f], plane * 4, true);
   }
-  add(j->rows, (unsigned long long)n * sizeof(DevReprojRow), true);
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a destination range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->rows, (unsigned long long)n * sizeof(DevReprojRow), true);
+  return r.overlap("a destination range overlaps another range of the job");
 }
 
 // ---- Splat (ofdg_splat, include/ofdg.h) ------------------------------------------------------------------------------------
@@ -2323,12 +2192,7 @@ OFDG_HD_FN float splat_to_other(int d, int D) { return (float)(256ll * d + D) * 
 OFDG_HD_FN bool splat_resolves(const DevSplatJob& j) {
   return j.rows || j.image[0] || j.image[1] || j.to_own[0] || j.to_own[1] || j.to_other[0] || j.to_other[1] || j.mask[0] || j.mask[1] || j.fate[0] || j.fate[1];
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* splat_plane_size(const DevSplatJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
+inline const char* splat_plane_size(const DevSplatJob& j, int* width, int* height) { return job_plane_size(j, width, height); }  // (the name tests/test_splat.py asks for)
 // What the draw reads of a job: the first rule broken, or nullptr.
 inline const char* splat_ranges_error(const DevSplatJob& j) {
   if (j.t_min_q8 < 0 || j.t_min_q8 > 256) return "t_min_q8 must lie in 0..256";
@@ -2337,7 +2201,7 @@ inline const char* splat_ranges_error(const DevSplatJob& j) {
   return nullptr;
 }
 // The argument rules ofdg_splat and ofdg_host_splat share: the first rule broken, or nullptr.  width, height: what
-// splat_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* splat_arg_error(const DevSplatJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (n < 1) return "n_samples must be at least 1";
@@ -2363,32 +2227,24 @@ inline const char* splat_arg_error(const DevSplatJob* j, int n, int width, int h
   if (!j->recs)
     if (const char* why = splat_ranges_error(*j)) return why;
   // no in-place form: a written range may meet no other range of the job
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[24];
-  int nr = 0;
+  RangeSet<23> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
-  const auto add = [&](const void* p, unsigned long long bytes, bool dst) {
-    if (p) r[nr++] = Range{(uintptr_t)p, (uintptr_t)p + (uintptr_t)bytes, dst};
-  };
   for (int f = 0; f < 2; ++f) {
-    add(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
-    add(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
-    add(j->label[f], plane, false);
-    add(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
-    add(j->keys[f], plane * 4, true);
-    add(j->image[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
-    add(j->to_own[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
-    add(j->to_other[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
-    add(j->mask[f], plane, true);
-    add(j->fate[f], plane, true);
+    r.add_if(j->img[f], plane * 3 * fmt_elem_bytes(j->img_fmt), false);
+    r.add_if(j->flow[f], plane * 2 * fmt_elem_bytes(j->flow_fmt), false);
+    r.add_if(j->label[f], plane, false);
+    r.add_if(j->occ[f], plane * fmt_elem_bytes(j->occ_fmt), false);
+    r.add_if(j->keys[f], plane * 4, true);
+    r.add_if(j->image[f], plane * 3 * fmt_elem_bytes(j->dst_fmt), true);
+    r.add_if(j->to_own[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
+    r.add_if(j->to_other[f], plane * 2 * fmt_elem_bytes(j->oflow_fmt), true);
+    r.add_if(j->mask[f], plane, true);
+    r.add_if(j->fate[f], plane, true);
   }
-  add(j->rows, (unsigned long long)n * sizeof(DevSplatRow), true);
-  add(j->recs, (unsigned long long)n * sizeof(DevSplatRec), false);
-  add(j->recs_out, (unsigned long long)n * sizeof(DevSplatRec), true);
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  r.add_if(j->rows, (unsigned long long)n * sizeof(DevSplatRow), true);
+  r.add_if(j->recs, (unsigned long long)n * sizeof(DevSplatRec), false);
+  r.add_if(j->recs_out, (unsigned long long)n * sizeof(DevSplatRec), true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Flow visualisation (ofdg_flow_vis, include/ofdg.h) --------------------------------------------------------------------
@@ -2534,15 +2390,9 @@ OFDG_HD_FN uint32_t vis_pixel(float u, float v, uint32_t M, float inv_m, bool di
   if (dim) { R >>= 1; G >>= 1; B >>= 1; }
   return R | (G << 8) | (B << 16);
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* vis_plane_size(const DevVisJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 inline bool vis_needs_work(const DevVisJob& j) { return j.norm != OFDG_VIS_NORM_FIXED; }
 // The argument rules ofdg_flow_vis and ofdg_host_flow_vis share: the first rule broken, or nullptr.  width, height: what
-// vis_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
+// job_plane_size gave.  Alignment and `work` are asked by the device entry only (with_work).
 inline const char* vis_arg_error(const DevVisJob* j, int n, int width, int height, bool with_work) {
   if (!j) return "job is NULL";
   if (!j->flow) return "flow is NULL";
@@ -2561,19 +2411,14 @@ inline const char* vis_arg_error(const DevVisJob* j, int n, int width, int heigh
   if (j->norm == OFDG_VIS_NORM_FIXED && !(j->max_flow >= 0.00390625f && j->max_flow <= 1048576.0f)) return "max_flow must lie in [2^-8, 2^20]";
   const bool work = with_work && vis_needs_work(*j);
   if (work && !j->work) return "work is NULL where norm is not OFDG_VIS_NORM_FIXED";
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[5];
-  int nr = 0;
+  RangeSet<5> r;
   const unsigned long long plane = (unsigned long long)n * width * height;
-  r[nr++] = Range{(uintptr_t)j->flow, (uintptr_t)j->flow + (uintptr_t)(2ull * plane * fmt_elem_bytes(j->flow_fmt)), false};
-  if (j->occ) r[nr++] = Range{(uintptr_t)j->occ, (uintptr_t)j->occ + (uintptr_t)(plane * fmt_elem_bytes(j->occ_fmt)), false};
-  r[nr++] = Range{(uintptr_t)j->dst, (uintptr_t)j->dst + (uintptr_t)(3ull * plane), true};
-  if (j->rows_out) r[nr++] = Range{(uintptr_t)j->rows_out, (uintptr_t)j->rows_out + (uintptr_t)n * sizeof(DevVisRow), true};
-  if (work) r[nr++] = Range{(uintptr_t)j->work, (uintptr_t)j->work + (uintptr_t)n * sizeof(unsigned long long), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  r.add(j->flow, 2ull * plane * fmt_elem_bytes(j->flow_fmt), false);
+  r.add_if(j->occ, plane * fmt_elem_bytes(j->occ_fmt), false);
+  r.add(j->dst, 3ull * plane, true);
+  r.add_if(j->rows_out, (unsigned long long)n * sizeof(DevVisRow), true);
+  if (work) r.add(j->work, (unsigned long long)n * sizeof(unsigned long long), true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // ---- Flow error (ofdg_flow_error, include/ofdg.h) --------------------------------------------------------------------------
@@ -2683,14 +2528,8 @@ OFDG_HD_FN uint32_t err_colour(uint32_t Eq, uint32_t Gq, bool dim, const uint32_
   const uint32_t c = table[err_colour_bin(Eq, Gq)];
   return dim ? (c >> 1) & 0x7F7F7Fu : c;
 }
-// The plane size of a job: its own when set, else the one offered (the context's frame, the host twin's arguments).
-inline const char* err_plane_size(const DevErrJob& j, int* width, int* height) {
-  if ((j.width == 0) != (j.height == 0)) return "width and height must both be 0 or both be set";
-  if (j.width != 0) { *width = j.width; *height = j.height; }
-  return plane_size_error(*width, *height);
-}
 // The argument rules ofdg_flow_error and ofdg_host_flow_error share: the first rule broken, or nullptr.  width, height: what
-// err_plane_size gave.  Alignment is asked by the device entry only.
+// job_plane_size gave.  Alignment is asked by the device entry only.
 inline const char* err_arg_error(const DevErrJob* j, int n, int width, int height) {
   if (!j) return "job is NULL";
   if (!j->gt) return "gt is NULL";
@@ -2714,21 +2553,16 @@ inline const char* err_arg_error(const DevErrJob* j, int n, int width, int heigh
   if (!(j->speed_px[0] > 0.0f && j->speed_px[0] <= j->speed_px[1] && j->speed_px[1] <= 1048576.0f)) return "speed_px must be 0 < speed_px[0] <= speed_px[1] <= 2^20";
   if (j->dist2 && !(1 <= j->dist2_edge[0] && j->dist2_edge[0] <= j->dist2_edge[1] && j->dist2_edge[1] <= 255))
     return "dist2_edge must be 1 <= dist2_edge[0] <= dist2_edge[1] <= 255";
-  struct Range { uintptr_t lo, hi; bool dst; };
-  Range r[7];
-  int nr = 0;
+  RangeSet<7> r;
   const unsigned long long all = (unsigned long long)n * plane;
-  r[nr++] = Range{(uintptr_t)j->gt, (uintptr_t)j->gt + (uintptr_t)(2ull * all * fmt_elem_bytes(j->gt_fmt)), false};
-  r[nr++] = Range{(uintptr_t)j->est, (uintptr_t)j->est + (uintptr_t)(2ull * all * fmt_elem_bytes(j->est_fmt)), false};
-  if (j->occ) r[nr++] = Range{(uintptr_t)j->occ, (uintptr_t)j->occ + (uintptr_t)(all * fmt_elem_bytes(j->occ_fmt)), false};
-  if (j->dist2) r[nr++] = Range{(uintptr_t)j->dist2, (uintptr_t)j->dist2 + (uintptr_t)all, false};
-  if (j->rows) r[nr++] = Range{(uintptr_t)j->rows, (uintptr_t)j->rows + sizeof(DevErrRow) * (uintptr_t)((j->flags & OFDG_ERR_ONE_ROW) ? 1 : n), true};
-  if (j->epe) r[nr++] = Range{(uintptr_t)j->epe, (uintptr_t)j->epe + (uintptr_t)(all * fmt_elem_bytes(j->epe_fmt)), true};
-  if (j->picture) r[nr++] = Range{(uintptr_t)j->picture, (uintptr_t)j->picture + (uintptr_t)(3ull * all), true};
-  for (int a = 0; a < nr; ++a)
-    for (int b = 0; b < nr; ++b)
-      if (a != b && r[a].dst && r[a].lo < r[b].hi && r[b].lo < r[a].hi) return "a written range overlaps another range of the job";
-  return nullptr;
+  r.add(j->gt, 2ull * all * fmt_elem_bytes(j->gt_fmt), false);
+  r.add(j->est, 2ull * all * fmt_elem_bytes(j->est_fmt), false);
+  r.add_if(j->occ, all * fmt_elem_bytes(j->occ_fmt), false);
+  r.add_if(j->dist2, all, false);
+  r.add_if(j->rows, sizeof(DevErrRow) * (unsigned long long)((j->flags & OFDG_ERR_ONE_ROW) ? 1 : n), true);
+  r.add_if(j->epe, all * fmt_elem_bytes(j->epe_fmt), true);
+  r.add_if(j->picture, 3ull * all, true);
+  return r.overlap("a written range overlaps another range of the job");
 }
 
 // Background texture preparation of one sample (ofdg_params.background_prep = 1):

@@ -120,6 +120,14 @@ def test_host_twins_read_planes_at_an_odd_address_under_the_sanitizers(san_progr
     assert run_san(san_program, "planes", tmp_path)[-1].endswith("odd=same")
 
 
+def test_range_overlap_checker_gives_its_known_answers_under_the_sanitizers(san_program, tmp_path):
+    """RangeSet and frame_pair_ranges (csrc/ofdg_device.h), the rule every post-processing operation decides with whether a kernel
+    may write to a caller's pointer: touching ranges, a one-byte overlap from either side in either order, read-read, the
+    in-place pair (same pointer and same format only), a written range against another frame's pair, the set at full capacity -
+    17 checks of which 11 are refusals, none wrong, no ASan / UBSan report (exit 0)."""
+    assert run_san(san_program, "overlap", tmp_path)[-1] == "overlap checks=17 refused=11 wrong=0"
+
+
 def test_sanitizer_build_agrees_with_the_library_and_survives_the_mutations(ofdg, san_program, tmp_path):
     """Two builds of one source agree: every line of `check` equals what libofdg.so answers through ctypes; `mutate` ends with
     exit 0 (no ASan / UBSan report, no escaped exception) and refuses most, not all, of what it made."""

@@ -1,4 +1,4 @@
-"""What the post-processing entries (object table, flow statistics, flow pyramid, training crop) answer to bad arguments, at a
+"""What the post-processing entries answer to bad arguments, at a
 parent revision and in the working tree, side by side:
 
     tools/build_rev.sh <rev> parent                      # the parent's library and a checkout with its __init__.py
@@ -10,7 +10,11 @@ the rules of flow_stats_arg_error, flow_pyramid_arg_error and crop_arg_error thr
 ValueError of the six *_format functions of the package (CPU tensors).  With --gpu, also, on a 64x32 context in mode 7: the
 rules only the device entries have (misaligned pointers, OFDG_STREAM_OWN before any call, plane_size_error of the sized
 entries, everything ofdg_object_table refuses), then one valid call of each entry behind a render call with a hash of what it
-wrote.  These are argument refusals: nothing is enqueued by them.  Each side runs in a process of its own (OFDG_LIB names the
+wrote.  Then every job-struct entry (crop, photo, spatial, lens, pack, boundaries, erase, jitter, flow_vis, flow_error, camera,
+jpeg, motion blur, reproject, splat) from the ctypes _fields_ of its job (job_cases): without --gpu the ofdg_host_* twin and the
+ofdg_X_draw entry on a host arena, and the ValueError of every range dict; with --gpu the device entry on a device arena -
+every pointer field misaligned, OFDG_STREAM_OWN before any call, `work` missing, the base job as the valid call, a hash of the
+arena.  Equal rows of these entries are printed as one line an entry.  These are argument refusals: nothing is enqueued by them.  Each side runs in a process of its own (OFDG_LIB names the
 parent's library there).  Exit 0: every row equal."""
 import argparse
 import ctypes as C
@@ -120,6 +124,198 @@ def host_cases(m, np):
         job.recs, job.recs_out, job.crop_w, job.crop_h, job.flags, job.reserved = a["recs"], a["recs_out"], a["crop_w"], a["crop_h"], a["flags"], a["reserved"]
         job.image_fmt, job.flow_fmt, job.occ_fmt = a["image_fmt"], a["flow_fmt"], a["occ_fmt"]
         answer("ofdg_host_crop", label, L.ofdg_host_crop(C.byref(job) if a["job"] else None, a["n"], a["width"], a["height"]))
+    return rows
+
+
+# ---- every job-struct entry, from the ctypes _fields_ of its job -------------------------------------------------------------
+# A valid base job at 8 x 2, n = 1, every pointer in a slot of its own inside ONE arena; then every field alone against a short
+# list of hostile values and every pair of fields that are neighbours in the entry's order of checks, in both orders.  Pointers
+# take NULL or addresses inside the arena only (the other buffers, +-1 byte, a one-byte overlap from either side); n_samples and
+# the plane size take values the parent must refuse (main() asserts that on the parent's answers: rows marked `sized`).
+JW, JH = 8, 2
+PX = JW * JH
+INTS = [-1, 0, 1, 2, 3, 7, 255, 65537, 2 ** 31 - 1, -2 ** 31]
+FLOATS = [-1.0, float("nan"), float("inf"), 0.0, 0.5, 1.0, 4.0, 1e9, float("-inf")]
+SIZED = dict(n_samples=[0, -1, -2 ** 31], width=[0, -1, 4, 12, 7, 2 ** 31 - 1], height=[0, -1, 1, 3, 2 ** 31 - 1])
+F3, F2, F1, B1 = 12 * PX, 8 * PX, 4 * PX, PX  # bytes of a float32 frame, flow, map and of a uint8 plane
+
+
+def job_ops(m):
+    """name -> (job class, base scalars, {pointer field: bytes at the base formats}, order of checks or None, draw entry or None,
+    record bytes)"""
+    eight = lambda: {"%s[%d]" % (w, k): b for w in ("src", "dst") for k, b in enumerate((F3, F3, F2, F2, F1, F1, B1, B1))}  # noqa: E731
+    pair = lambda rec: dict({"%s[%d]" % (w, f): F3 for w in ("src", "dst") for f in (0, 1)}, recs=rec, recs_out=rec)  # noqa: E731
+    two = lambda **kw: {"%s[%d]" % (k, f): b for k, b in kw.items() for f in (0, 1)}  # noqa: E731
+    head = ["n_samples", "job.width", "job.height", "width", "height", "src_fmt", "dst_fmt"]
+    tail = ["src[0]", "dst[0]", "src[1]", "dst[1]", "recs", "recs_out"]
+    return {
+        "crop": (m.CropJob, dict(crop_w=JW, crop_h=JH), dict(eight(), recs=16, recs_out=16), None, None, 16),
+        "photo": (m.PhotoJob, {}, pair(64), head + ["flags", "reserved"] + list(m.PHOTO_RANGES) + tail, "ofdg_photo_draw", 64),
+        "spatial": (m.SpatialJob, dict(out_w=JW, out_h=JH), dict(eight(), recs=112, recs_out=112), None, None, 112),
+        "lens": (m.LensJob, {}, dict(eight(), recs=64, recs_out=64), None, None, 64),
+        "pack": (m.PackJob, {"scale[0]": 1.0, "scale[1]": 1.0, "scale[2]": 1.0, "flow_scale": 1.0},
+                 {"src[0]": F3, "src[1]": F3, "src[2]": F2, "dst[0]": F3, "dst[1]": F3, "dst[2]": F2}, None, None, 0),
+        "boundaries": (m.BoundaryJob, dict(radius=1, min_step=1.0), two(flow=F2, label=B1, edge=B1, dist2=B1), None, None, 0),
+        "erase": (m.EraseJob, dict(flags=7, max_rects=4, min_size=1, max_size=8, prob=1.0),
+                  dict(two(image=F3, occ=F1, flow=F2), recs=96, recs_out=96, work=64), None, "ofdg_erase_draw", 96),
+        "jitter": (m.JitterJob, {}, dict(pair(64), work=64),
+                   head + ["flags", "reserved"] + list(m.JITTER_RANGES) + tail + ["work"], "ofdg_jitter_draw", 64),
+        "flow_vis": (m.FlowVisJob, dict(max_flow=10.0), dict(flow=F2, occ=F1, dst=3 * PX, rows_out=16, work=8), None, None, 0),
+        "flow_error": (m.FlowErrorJob, {"est_scale": 1.0, "speed_px[0]": 1.0, "speed_px[1]": 10.0, "dist2_edge[0]": 1, "dist2_edge[1]": 2},
+                       dict(gt=F2, est=F2, occ=F1, dist2=B1, rows=672, epe=F1, picture=3 * PX), None, None, 0),
+        "camera": (m.CameraJob, dict(pattern=-1), pair(32),
+                   head + ["flags", "reserved", "sigma_min", "sigma_max", "sigma_delta", "blur_prob", "bayer_prob", "pattern"] + tail, "ofdg_camera_draw", 32),
+        "jpeg": (m.JpegJob, dict(quality_min=75, quality_max=75), pair(32),
+                 head + ["reserved[0]", "reserved[1]", "flags", "quality_min", "quality_max", "quality_delta", "prob", "sub_prob", "subsample"] + tail,
+                 "ofdg_jpeg_draw", 32),
+        "motion_blur": (m.MblurJob, dict(taps_side=4), dict(two(src=F3, dst=F3, flow=F2), recs=16, recs_out=16),
+                        head + ["flow_fmt", "flags", "reserved[0]", "reserved[1]", "taps_side", "src[0]", "dst[0]", "flow[0]", "src[1]", "dst[1]", "flow[1]"] +
+                        list(m.MBLUR_RANGES) + ["recs", "recs_out"], "ofdg_motion_blur_draw", 16),
+        "reproject": (m.ReprojectJob, dict(flags=3), dict(two(img=F3, flow=F2, occ=F1, warped=F3, err=B1, mask=B1, fb2=F1), rows=256), None, None, 0),
+        "splat": (m.SplatJob, dict(flags=3, t_min_q8=128, t_max_q8=128),
+                  dict(two(img=F3, flow=F2, label=B1, occ=F1, keys=F1, image=F3, to_own=F2, to_other=F2, mask=B1, fate=B1), rows=128, recs=16, recs_out=16),
+                  None, "ofdg_splat_draw", 16),
+    }
+
+
+def job_fields(cls):
+    """[(name, "p" | "i" | "f")] of a job class, an array's elements one by one"""
+    out = []
+    for name, t in cls._fields_:
+        n = getattr(t, "_length_", None)
+        e = t._type_ if n else t
+        kind = "p" if e is C.c_void_p else "f" if e is C.c_float else "i"
+        out += [("%s[%d]" % (name, k), kind) for k in range(n)] if n else [(name, kind)]
+    return out
+
+
+def job_set(job, name, v):
+    if name.endswith("]"):
+        getattr(job, name[:name.index("[")])[int(name[name.index("[") + 1:-1])] = v
+    else:
+        setattr(job, name, v)
+
+
+def job_cases(m, L, base_adr, slot, device=None):
+    """rows of every job-struct entry; device: None for the ofdg_host_* twins (and the draws), else (ctx handle, stream cases)"""
+    rows = []
+    for op, (cls, scalars, ptrs, order, draw, rec_bytes) in job_ops(m).items():
+        fields = job_fields(cls)
+        kinds = dict(fields)
+        adr = {name: base_adr + slot * k for k, name in enumerate(ptrs)}  # (a slot each: `slot` bytes, far more than any buffer)
+        assert set(ptrs) == {f for f, k in fields if k == "p"}, op
+        base = dict({f: 0 for f, k in fields if k != "p"}, **scalars)
+        base.update(adr)
+        if "recs" in ptrs:
+            base["recs"] = None  # (the draw; a given record array is one of the pointer cases)
+        if device and op == "crop":
+            continue  # (the context's own 64 x 32 frame: gpu_cases above)
+        has_size = "width" in kinds
+        call = dict(n_samples=1, width=JW, height=JH)
+        if device and has_size:
+            base["width"], base["height"] = JW, JH  # (a device entry takes the job's own size; the context's is 64 x 32)
+
+        def hostile(f):
+            if f in call:  # (ofdg_host_crop takes any frame its window fits in: only what it refuses)
+                return [0, -1, 2 ** 31 - 1] if op == "crop" and f != "n_samples" else SIZED[f]
+            name = f[4:] if f.startswith("job.") else f
+            if kinds[name] == "f":
+                return FLOATS
+            if kinds[name] == "i":
+                return [v for v in INTS if v != base[name]][:9] if name not in ("width", "height") else [-1, 1, 2, 3, 7, 255, 65537, 2 ** 31 - 1, -2 ** 31]
+            vals = [None, adr[name] + 1, adr[name] - 1]
+            if device:
+                return vals + [adr[name] + 2, adr[name] + 4, adr[name] + 8]
+            for other in ptrs:
+                if other != name:
+                    vals += [adr[other], adr[other] + ptrs[other] - 1, adr[other] - ptrs[name] + 1]
+            return vals
+
+        def answer(label, muts, sized):
+            job, c = cls(), dict(call)
+            vals = dict(base)
+            for f, v in muts:
+                if f in c:
+                    c[f] = v
+                else:
+                    vals[f[4:] if f.startswith("job.") else f] = v
+            stream = vals.pop("stream", None)
+            for f, v in vals.items():
+                job_set(job, f, v)
+            if device:
+                rc = getattr(L, "ofdg_" + op)(device, C.byref(job), c["n_samples"], stream)
+                why = L.ofdg_last_error(device).decode() if rc else ""
+            else:
+                rc = getattr(L, "ofdg_host_" + op)(C.byref(job), c["n_samples"], c["width"], c["height"])
+                why = L.ofdg_host_last_error().decode() if rc else ""
+            rows.append(("%s %s: %s" % ("ofdg_" + op if device else "ofdg_host_" + op, "sized" if sized else "", label), int(rc), why))
+            if draw and not device and not sized and all(kinds.get(f, "p") != "p" for f, _ in muts):
+                out = C.cast((C.c_uint8 * rec_bytes)(), getattr(L, draw).argtypes[-1])
+                args = (7, 3, JW, JH, C.byref(job), out) if op == "erase" else (7, 3, C.byref(job), out)
+                rc = getattr(L, draw)(*args)
+                rows.append(("%s: %s" % (draw, label), int(rc), L.ofdg_host_last_error().decode() if rc else ""))
+
+        names = list(call) * (not device) + [("job." + f if f in ("width", "height") else f) for f, _ in fields]
+        if device:
+            names = [f for f in names if kinds.get(f) == "p"] + ["stream"]
+            kinds["stream"], base["stream"] = "s", None
+        show = lambda v: "NULL" if v is None else ("arena%+d" % (v - base_adr) if isinstance(v, int) and v > 2 ** 32 else repr(v))  # noqa: E731
+        values = lambda f: [C.c_void_p(m.STREAM_OWN)] if f == "stream" else hostile(f)  # noqa: E731
+        label = lambda f, v: "%s = %s" % (f, "own" if f == "stream" else show(v))  # noqa: E731
+        is_sized = lambda f: f in call or f in ("job.width", "job.height")  # noqa: E731
+        answer("the base job", [], False)
+        for f in names:
+            for v in values(f):
+                answer(label(f, v), [(f, v)], is_sized(f))
+        seq = [f for f in (order or names) if f in names] if not device else names
+        for a, b in zip(seq, seq[1:]):
+            for va in values(a)[:3]:
+                for vb in values(b)[:3]:
+                    answer("%s, %s" % (label(a, va), label(b, vb)), [(a, va), (b, vb)], is_sized(a) or is_sized(b))
+                    answer("%s, %s" % (label(b, vb), label(a, va)), [(b, vb), (a, va)], is_sized(a) or is_sized(b))
+        if draw and not device:
+            out = C.cast((C.c_uint8 * rec_bytes)(), getattr(L, draw).argtypes[-1])
+            job = cls()
+            for who, a in (("ranges NULL", (None, out)), ("out NULL", (C.byref(job), None))):
+                rc = getattr(L, draw)(7, 3, *(((JW, JH) if op == "erase" else ()) + a))
+                rows.append(("%s: %s" % (draw, who), int(rc), L.ofdg_host_last_error().decode() if rc else ""))
+    return rows
+
+
+def host_job_cases(m, np):
+    slot = 4096
+    arena = np.zeros(slot * 48, np.uint8)
+    return job_cases(m, m.lib(), arena.ctypes.data + slot, slot)
+
+
+def range_dict_cases(m):
+    """the ValueError of every range dict for a name it does not know, alone and beside a name it knows; through X_draw where the
+    operation has one that takes the dict (splat has no dict: t=).  Anything but a ValueError ends the run: a mistake of this tool."""
+    rows = []
+    calls = dict(photo=lambda d: m.photo_draw(7, 3, d), spatial=lambda d: m.spatial_draw(7, 3, JW, JH, JW, JH, d), lens=lambda d: m.lens_draw(7, 3, JW, JH, d),
+                 erase=lambda d: m.erase_draw(7, 3, JW, JH, d), jitter=lambda d: m.jitter_draw(7, 3, d), camera=lambda d: m.camera_draw(7, 3, d),
+                 jpeg=lambda d: m.jpeg_draw(7, 3, d), motion_blur=lambda d: m.motion_blur_draw(7, 3, d))
+    known = dict(photo="brightness", spatial="rot", lens="prob", erase="prob", jitter="hue", camera="blur_prob", jpeg="prob", motion_blur="prob")
+    for name, fn in calls.items():
+        for label, d in (("unknown range", dict(bogus=1)), ("a known range, then an unknown one", {known[name]: 0.5, "bogus": 1}),
+                         ("a known range alone", {known[name]: 0.5}), ("no dict", None)):
+            try:
+                fn(d)
+                rows.append(("%s_draw: %s" % (name, label), 0, ""))
+            except ValueError as e:
+                rows.append(("%s_draw: %s" % (name, label), 1, str(e)))
+    return rows
+
+
+def gpu_job_cases(m, torch):
+    """the rules only the device entries have - the alignment of every pointer field, OFDG_STREAM_OWN before any call, `work`
+    missing (a NULL among the pointer values) - and the base job of every entry as its one valid call, with a hash of the arena"""
+    slot = 4096
+    arena = torch.zeros(slot * 48, dtype=torch.uint8, device="cuda")
+    g = m.Generator(m.default_params(width=64, height=32, mode=7, sampler=1, seed=5))  # (no call made on it: OFDG_STREAM_OWN is refused)
+    rows = job_cases(m, m.lib(), arena.data_ptr() + slot, slot, device=g.h)
+    torch.cuda.synchronize()
+    rows.append(("bytes in the arena after every accepted job (sha256)", 0, hashlib.sha256(arena.cpu().numpy().tobytes()).hexdigest()))
     return rows
 
 
@@ -327,9 +523,9 @@ def emit(gpu):
     import numpy as np
     import torch
     m = importlib.import_module(PKG)
-    rows = host_cases(m, np) + format_cases(m, torch)
+    rows = host_cases(m, np) + format_cases(m, torch) + host_job_cases(m, np) + range_dict_cases(m)
     if gpu:
-        rows += gpu_cases(m, torch)
+        rows += gpu_cases(m, torch) + gpu_job_cases(m, torch)
     print("ROWS " + json.dumps(rows))
 
 
@@ -358,14 +554,29 @@ def main():
     differ = 0
     print("%d cases at the parent, %d in the working tree%s" % (len(parent), len(branch), " (with the device entries)" if a.gpu else ""))
     print("case | return code (*_format: 1 = ValueError) | error text: `same` - both sides answer this; DIFF - each side's answer below")
+    inside = [r for r in parent if " sized: " in r[0] and r[1] == 0]
+    if inside:
+        sys.exit("the parent ACCEPTS a job whose n_samples or plane size is not the base's - it may leave the arena: %s" % inside[:5])
+    entry = lambda r: r[0].split(": ")[0]  # noqa: E731
+    count = {}
+    for r in parent:
+        count[entry(r)] = count.get(entry(r), 0) + 1
+    folded = {}  # an entry of the generic generator: its equal rows as one line
     for k in range(max(len(parent), len(branch))):
         p, b = (parent[k] if k < len(parent) else None), (branch[k] if k < len(branch) else None)
         same = p == b
         differ += not same
-        if same:
+        if same and count[entry(p)] > 60:
+            f = folded.setdefault(entry(p), [0, 0, set()])
+            f[0] += 1
+            f[1] += p[1] != 0
+            f[2].add(p[2])
+        elif same:
             print("same  %-72s | %d | %s" % (p[0], p[1], p[2]))
         else:
             print("DIFF  %s\n      parent | %s\n      branch | %s" % ((p or b)[0], p and p[1:], b and b[1:]))
+    for name, (cases, refused, texts) in folded.items():
+        print("same  %-40s | %5d cases equal on both sides: %d accepted, %d refused with %d distinct texts" % (name, cases, cases - refused, refused, len(texts - {""})))
     print("rows that differ: %d of %d" % (differ, max(len(parent), len(branch))))
     sys.exit(1 if differ else 0)
 
