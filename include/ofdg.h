@@ -507,6 +507,16 @@ int ofdg_flow_pyramid_sized(ofdg_ctx* ctx, const void* d_flow, int flow_fmt, con
                             int width, int height, int flags, const struct ofdg_flow_pyramid* pyr, void* stream);
 
 /*
+ * Batch and tensor sizes of the operations on finished planes (ofdg_flow_stats above to ofdg_jpeg below).  n_samples is any
+ * positive int: a launch has min(n_samples, 65535) rows of workgroups and a workgroup walks the samples i, i + rows, ..., so
+ * from n_samples = 65536 on a workgroup serves several samples.  Pixel indices inside a sample are 32-bit (hence the refusal
+ * of 3 * width * height of 2^32 and more); a sample's base is formed in 64 bits, so a tensor may exceed 4 GiB.  Both are
+ * supported and tested for every one of these operations with n_samples = 65551 and tensors of 4.8 GiB and more
+ * (tests/test_gpu_many_samples.py); none refuses them.  The one limit that involves n_samples is OFDG_STATS_ONE_ROW /
+ * OFDG_ERR_ONE_ROW, whose pixel index runs over the whole batch: n_samples * height * width below 2^32.
+ */
+
+/*
  * Training crop: a crop_w x crop_h window of every output of a batch - frames, both flows, both occlusion maps, both label
  * planes -, each sample at its own position, optionally mirrored left-right and / or top-bottom, in ONE launch behind the
  * call that wrote the planes.  The window is a pure function of (seed, global sample index), so a resumed or sharded run
